@@ -9,6 +9,11 @@ forwards; the decoder loop and the post-net scan are whole-chip persistent kerne
 N ranks: one process per GPU, per-GPU batch fixed (weak scaling), no data-path collective; barrier + synchronize on both sides,
 MAX over ranks.
 
+A plain run sets up, warms up, times the K steps and prints the headline line; everything else the line can carry (forward
+latency alone, per-stage timings, the exact-fp32 / fp32-grade / coalesced / launch-per-stage companions, the train-step companion, the
+CPU baselines, the finiteness check) runs only with `--full`.  `--dump-outputs DIR` writes what the last timed step computed
+(mel, alignments, stop step, linear spectrogram -- the arrays PlanPool.result() hands a caller) as DIR/<name>.npy.
+
 Prints ONE JSON line on rank 0 (see DESIGN.md 'Measurement' for every field)."""
 import argparse
 import json
@@ -213,6 +218,38 @@ def source_hash():
     return h.hexdigest()[:16]
 
 
+DUMP_BUDGET_BYTES = 64_000_000     # --dump-outputs: at most 64 MB in all
+
+
+def dump_outputs(dirname, arrays, seed=0):
+    """`--dump-outputs DIR`: write `arrays` ((name, numpy array) pairs, in the order given) as DIR/<name>.npy, floats as float32,
+    integers as float64.  An array that does not fit in what is left of DUMP_BUDGET_BYTES (the linear spectrogram at C2: 67 MB) is
+    written as a fixed sample of its frames (axis 1): the frames RandomState(seed) draws -- the same ones in every run of the same
+    shape -- as <name>_sampled.npy, their indices as <name>_sampled_frames.npy.  Returns name -> shape of what was written."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    left, written = DUMP_BUDGET_BYTES, {}
+
+    def save(name, a):
+        nonlocal left
+        np.save(os.path.join(dirname, name + ".npy"), np.ascontiguousarray(a))
+        left -= a.nbytes + 4096                    # (the .npy header, generously)
+        written[name] = list(a.shape)
+    for name, a in arrays:
+        a = np.asarray(a)
+        a = a.astype(np.float32 if a.dtype.kind == "f" else np.float64)
+        if a.nbytes + 4096 > left:
+            T = a.shape[1]
+            keep = (left - 2 * 4096 - 8 * T) // (a.nbytes // T)
+            if keep < 1:
+                raise RuntimeError("--dump-outputs: no room left for a sample of %s %s" % (name, a.shape))
+            frames = np.sort(np.random.RandomState(seed).choice(T, int(keep), replace=False))
+            save(name + "_sampled_frames", frames.astype(np.float64))
+            a, name = a[:, frames], name + "_sampled"
+        save(name, a)
+    return written
+
+
 def cpu_arm(name, seed, threads, budget_s):
     """One arm of the CPU baseline, run in a process of its own (`bench.py --cpu-arm THREADS`): the fp32 torch-CPU restatement on the FULL batch of
     the workload with `threads` intra-op threads; 3 warm-up + 10 timed runs, median -- cut to what fits `budget_s` seconds (never fewer than
@@ -359,7 +396,7 @@ def train_step_line(args):
                       "launch": rep["launch"]},
            "roofline": rep["roofline"], "phase_ms": rep["phase_ms"], "engine": rep["engine"], "deterministic": rep["deterministic"],
            "per_rank_ms_per_step": rep["per_rank_ms_per_step"], "steps_per_s": rep["value"]}
-    if world == 1 and not args.no_cpu_baseline:
+    if world == 1 and args.full and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline_train(1237)
     print(json.dumps(out))
 
@@ -402,6 +439,12 @@ def main():
                     help="skip the per-stage timings (roofline.stages): counter passes must see nothing but whole forwards, or their per-forward figures count the extra stage runs")
     ap.add_argument("--decoder-engine", type=int, default=1, help="1 persistent XCD-local decoder (default), 0 launch per stage, 2 persistent write-through")
     ap.add_argument("--chip-turns", type=int, default=1, help="debug A/B: 0 switches off the per-device ordering of whole-chip kernels across streams (taco_debug_set_chip_turns)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beside the headline: forward latency alone, per-stage timings, the companions, "
+                         "the CPU baselines, the finiteness of the outputs (a plain run does only the timed steps)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last step computed as DIR/<name>.npy (float32 / float64, at most 64 MB in all; "
+                         "an array beyond that as a fixed, seeded sample of its frames)")
     ap.add_argument("--cpu-arm", type=int, default=0, help=argparse.SUPPRESS)          # internal: one arm of cpu_baseline() in its own process
     ap.add_argument("--cpu-seed", type=int, default=1234, help=argparse.SUPPRESS)
     ap.add_argument("--cpu-budget", type=float, default=20.0, help=argparse.SUPPRESS)
@@ -430,8 +473,12 @@ def main():
         if dist is not None:
             dist.destroy_process_group()
         return
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
     if args.coalesce < 1 or (args.coalesce > 1 and (args.eager or args.steps % args.coalesce or args.warmup % args.coalesce)):
         ap.error("--coalesce c needs hipGraph plans and steps / warmup that are multiples of c")
+    if args.workload == "C4" and args.dump_outputs:
+        ap.error("--dump-outputs writes the outputs of the inference path; --workload C4 times the train step")
     if args.workload == "C4":
         return train_step_line(args)
 
@@ -538,18 +585,30 @@ def main():
     wall = D.max_over_ranks(wall, device=dev if dist is not None else "cpu")
     dev_ms = D.max_over_ranks(dev_ms, device=dev if dist is not None else "cpu")
     device_errors = D.max_over_ranks(1.0 if device_errors else 0.0, device=dev if dist is not None else "cpu") > 0
-    # latency of one forward with nothing else in flight (for the record; `value` is the throughput above)
-    lat0, lat1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    with torch.cuda.stream(pool.streams[0]):
-        lat0.record()
-        for _ in range(3):
-            pool.plans[0].launch()
-        lat1.record()
-    torch.cuda.synchronize()
-    latency_ms = lat0.elapsed_time(lat1) / 3
+    dumped = None
+    if rank == 0 and args.dump_outputs:
+        # the forward that carried the last timed step (with coalesce c it carries c identical batches: the last one is that step's)
+        last = args.steps - 1
+        lane = (last // co) % lanes if co > 1 else last % lanes
+        p = pool.plans[lane]
+        rows = slice((co - 1) * B, co * B)
+        stop = int(pool.slot_stop[lane][co - 1].item()) if co > 1 else int(p.stop.item())
+        dumped = dump_outputs(args.dump_outputs, [("stop_step", np.array([stop])), ("mel", p.mel[rows].cpu().numpy()),
+                                                  ("alignments", p.align[rows].cpu().numpy()), ("linear", p.linear[rows].cpu().numpy())])
+    latency_ms = None
+    if args.full:
+        # latency of one forward with nothing else in flight (for the record; `value` is the throughput above)
+        lat0, lat1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        with torch.cuda.stream(pool.streams[0]):
+            lat0.record()
+            for _ in range(3):
+                pool.plans[0].launch()
+            lat1.record()
+        torch.cuda.synchronize()
+        latency_ms = lat0.elapsed_time(lat1) / 3
     # the three stages of the path one by one (stage-level C ABI, eager launches, nothing else in flight), HIP events on their stream
     stage_ms = {}
-    if rank == 0 and not args.no_stage_timing:
+    if rank == 0 and args.full and not args.no_stage_timing:
         p0 = pool.plans[0]
         spk0 = p0.speaker_id if ns > 1 else None
         with torch.cuda.stream(pool.streams[0]):
@@ -581,7 +640,7 @@ def main():
             finally:            # an exception above must not leave the model with its scans skipped for the companions
                 model._lib.taco_debug_set_skip_scans(model._handle, 0)
         model.check_device_errors()
-    finite = all(bool(torch.isfinite(p.mel).all().item() and torch.isfinite(p.linear).all().item()) for p in pool.plans)
+    finite = all(bool(torch.isfinite(p.mel).all().item() and torch.isfinite(p.linear).all().item()) for p in pool.plans) if args.full else None
 
     def timed_pool(pl, nlanes, nsteps):
         """nsteps forwards round-robin over nlanes lanes of pool pl; returns seconds per forward (HIP events, as the timed region)."""
@@ -601,7 +660,7 @@ def main():
         return e0.elapsed_time(e1) / 1e3 / nsteps
 
     companions = {}
-    if rank == 0 and world == 1 and not args.no_companions and co == 1 and not args.eager:
+    if rank == 0 and world == 1 and args.full and not args.no_companions and co == 1 and not args.eager:
         ksteps = max(4, min(args.steps, 12))
 
         def fill(pl, reps):
@@ -753,7 +812,7 @@ def main():
                        "decoder_engine": "launch per stage" if pool.engine != "persistent" else
                                          {1: "persistent XCD-local (csrc/taco_decoder_xcd.h)", 2: "persistent, write-through exchanges"}[args.decoder_engine],
                        "launch": "eager" if args.eager else "hipGraph plan (%d nodes)" % plan.num_nodes,
-                       "forwards_in_flight": lanes, "requests_per_forward": co, "forward_latency_ms_alone": latency_ms},
+                       "forwards_in_flight": lanes, "requests_per_forward": co},
             "roofline": {"bound": "hbm", "achieved": abytes / fwd_s / 1e9, "peak": HBM_PEAK_GBS, "unit": "GB/s",
                          "frac": abytes / fwd_s / 1e9 / HBM_PEAK_GBS, "traffic": None,
                          "kernel": "whole forward (one hipGraph launch); algorithmic bytes %.3f GB per forward, "
@@ -774,9 +833,14 @@ def main():
             "per_rank_ms_per_step": per_rank_ms,
             "device_errors": bool(device_errors),
             "decoder_protocol": headline_engine.get("protocol"),
-            "companions": companions,
-            "outputs_finite": finite,
+            "full": bool(args.full),
         }
+        if args.full:
+            out["config"]["forward_latency_ms_alone"] = latency_ms
+            out["companions"] = companions
+            out["outputs_finite"] = finite
+        if dumped is not None:
+            out["outputs"] = {"dir": args.dump_outputs, "arrays": dumped}
         # HBM-side traffic per forward from the committed PMC passes (profiles/*pmc_hbm_traffic.json), same workload only, and only
         # when that profile was taken from THIS build of the kernels (sha256 over csrc/, recorded by tools/pmc_traffic.py)
         try:
@@ -802,7 +866,7 @@ def main():
         if "fp32_grade_x6" in companions:
             companions["fp32_grade_x6"]["roofline_frac"] = abytes / (companions["fp32_grade_x6"]["forward_ms"] * 1e-3) / 1e9 / HBM_PEAK_GBS
             out["roofline"]["frac_fp32_grade_x6"] = companions["fp32_grade_x6"]["roofline_frac"]
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(args.workload, seed)
         print(json.dumps(out))
     if dist is not None:

@@ -9,7 +9,8 @@ exactly like the slice tests, so the fixtures are oracle-made: 'parity unpinned'
 files hold float32 subsets sized for the repository -- mel in full (C3) or every 4th decoder step (C5), the linear output on a frame
 stride, alignments in full (C3) or their arg-max / peak per step plus every 8th step (C5), gradients as per-tensor norms plus a fixed random
 sample of elements -- together with the inputs.  Weights are re-created by the tests from the seeds recorded here.
-Minutes of CPU per file:  python tests/golden/make_full_size_golden.py [C3] [C5] [C4]"""
+Every fixture is stored as parts under 1 MiB (<name>.partNN.npz, save_parts / load: an array too large for one part is cut along its
+first axis).  Minutes of CPU per fixture:  python tests/golden/make_full_size_golden.py [C3] [C5] [C4]"""
 import os
 import sys
 import time
@@ -23,6 +24,54 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 import taco_oracle as O  # noqa: E402
 
 C3_LINEAR_STRIDE, C5_LINEAR_STRIDE, C5_STEP_STRIDE, C5_ALIGN_STRIDE, GRAD_SAMPLES = 8, 64, 4, 8, 2000
+PART_BYTES = 900_000          # raw bytes per part: a compressed part stays well under 1 MiB
+
+
+def save_parts(name, **arrays):
+    """Write `arrays` as HERE/<name>.part00.npz, .part01.npz, ... (compressed), each holding at most PART_BYTES of raw data.  An array
+    larger than that is cut along its first axis into pieces stored as '<key>@<i>'; load() joins them again."""
+    base = name[:-len(".npz")]
+    for f in os.listdir(HERE):
+        if f.startswith(base + ".part") and f.endswith(".npz"):
+            os.remove(os.path.join(HERE, f))
+    items = []
+    for k, v in arrays.items():
+        v = np.asarray(v)
+        if v.nbytes <= PART_BYTES:
+            items.append((k, v))
+            continue
+        rows = max(1, PART_BYTES // (v.nbytes // v.shape[0]))
+        items += [("%s@%d" % (k, i), v[j:j + rows]) for i, j in enumerate(range(0, v.shape[0], rows))]
+    parts, cur, size = [], {}, 0
+    for k, v in items:
+        if cur and size + v.nbytes > PART_BYTES:
+            parts.append(cur)
+            cur, size = {}, 0
+        cur[k], size = v, size + v.nbytes
+    parts.append(cur)
+    for i, p in enumerate(parts):
+        np.savez_compressed(os.path.join(HERE, "%s.part%02d.npz" % (base, i)), **p)
+    return len(parts)
+
+
+def load(name):
+    """The arrays save_parts(name, ...) wrote, as a dict; None when the fixture has not been generated."""
+    base = name[:-len(".npz")]
+    files = sorted(f for f in os.listdir(HERE) if f.startswith(base + ".part") and f.endswith(".npz"))
+    if not files:
+        return None
+    out, pieces = {}, {}
+    for f in files:
+        with np.load(os.path.join(HERE, f)) as z:
+            for k in z.files:
+                if "@" in k:
+                    key, i = k.rsplit("@", 1)
+                    pieces.setdefault(key, []).append((int(i), z[k]))
+                else:
+                    out[k] = z[k]
+    for k, ps in pieces.items():
+        out[k] = np.concatenate([v for _, v in sorted(ps, key=lambda p: p[0])], axis=0)
+    return out
 
 
 def c3_case():
@@ -65,10 +114,10 @@ def make_c3():
     w = O.init_weights(hp, ns, seed)
     t = time.time()
     out = O.forward(w, hp, ids, L, speaker_id=spk, num_speakers=ns, honor_stop=False)
-    np.savez_compressed(os.path.join(HERE, "full_C3.npz"), seed=seed, inputs=ids, input_lengths=L, speaker_id=spk,
-                        mel=out["mel"].astype(np.float32), alignments=out["alignments"].astype(np.float32),
-                        linear_stride=C3_LINEAR_STRIDE, linear=out["linear"][:, ::C3_LINEAR_STRIDE].astype(np.float32),
-                        stop_step=int(out["stop_step"]))
+    save_parts("full_C3.npz", seed=seed, inputs=ids, input_lengths=L, speaker_id=spk,
+               mel=out["mel"].astype(np.float32), alignments=out["alignments"].astype(np.float32),
+               linear_stride=C3_LINEAR_STRIDE, linear=out["linear"][:, ::C3_LINEAR_STRIDE].astype(np.float32),
+               stop_step=int(out["stop_step"]))
     print("full_C3.npz: %.0f s" % (time.time() - t))
 
 
@@ -80,13 +129,13 @@ def make_c5():
     B, n, r, M = ids.shape[0], hp.max_iters, hp.reduction_factor, hp.num_mels
     mel_steps = out["mel"].reshape(B, n, r * M)[:, ::C5_STEP_STRIDE]
     al = out["alignments"]                                                       # [B, T_in, n]
-    np.savez_compressed(os.path.join(HERE, "full_C5.npz"), seed=seed, inputs=ids, input_lengths=L,
-                        step_stride=C5_STEP_STRIDE, mel_steps=mel_steps.astype(np.float32),
-                        align_argmax=al.argmax(axis=1).astype(np.int16), align_peak=al.max(axis=1).astype(np.float64),
-                        align_second=np.sort(al, axis=1)[:, -2, :].astype(np.float64),
-                        align_stride=C5_ALIGN_STRIDE, alignments=al[:, :, ::C5_ALIGN_STRIDE].astype(np.float32),
-                        linear_stride=C5_LINEAR_STRIDE, linear=out["linear"][:, ::C5_LINEAR_STRIDE].astype(np.float32),
-                        stop_step=int(out["stop_step"]))
+    save_parts("full_C5.npz", seed=seed, inputs=ids, input_lengths=L,
+               step_stride=C5_STEP_STRIDE, mel_steps=mel_steps.astype(np.float32),
+               align_argmax=al.argmax(axis=1).astype(np.int16), align_peak=al.max(axis=1).astype(np.float64),
+               align_second=np.sort(al, axis=1)[:, -2, :].astype(np.float64),
+               align_stride=C5_ALIGN_STRIDE, alignments=al[:, :, ::C5_ALIGN_STRIDE].astype(np.float32),
+               linear_stride=C5_LINEAR_STRIDE, linear=out["linear"][:, ::C5_LINEAR_STRIDE].astype(np.float32),
+               stop_step=int(out["stop_step"]))
     print("full_C5.npz: %.0f s" % (time.time() - t))
 
 
@@ -103,7 +152,7 @@ def make_c4():
         save["norm:" + k] = float(np.sqrt((v * v).sum()))
         save["max:" + k] = float(np.abs(v).max()) if v.size else 0.0
         save["sample:" + k] = v[grad_sample_index(k, v.size)]
-    np.savez_compressed(os.path.join(HERE, "full_C4_grads.npz"), **save)
+    save_parts("full_C4_grads.npz", **save)
     print("full_C4_grads.npz: %.0f s, loss %.6f, %d tensors" % (time.time() - t, loss, len(names)))
 
 

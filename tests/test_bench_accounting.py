@@ -68,3 +68,27 @@ def test_the_train_step_companion_hands_measure_every_switch_it_reads(monkeypatc
     monkeypatch.setattr(bench, "_bench_train_module", lambda: types.SimpleNamespace(measure=lambda ns: seen.update(vars(ns)) or {}))
     bench.train_step_report(2, 1)
     assert read <= set(seen), sorted(read - set(seen))
+
+
+def test_dump_outputs_stays_within_64_mb_and_samples_the_same_frames(tmp_path):
+    """`bench.py --dump-outputs`: the C2 outputs (mel, alignments, stop step, and the 67 MB linear spectrogram) fit in 64 MB in all, in
+    float32 / float64; the array that does not fit is a sample of its frames, and two dumps of the same arrays are identical file for file."""
+    import numpy as np
+    B, T_in, r, n, ns, mt = bench.WORKLOADS["C2"]
+    rs = np.random.RandomState(3)
+    arrays = [("stop_step", np.array([n], np.int32)), ("mel", rs.rand(B, n * r, 80).astype(np.float32)),
+              ("alignments", rs.rand(B, T_in, n).astype(np.float32)), ("linear", rs.rand(B, n * r, 1025).astype(np.float32))]
+    dumps = []
+    for d in ("a", "b"):
+        shapes = bench.dump_outputs(str(tmp_path / d), arrays)
+        files = sorted(os.listdir(tmp_path / d))
+        assert files == sorted(k + ".npy" for k in shapes)
+        assert sum(os.path.getsize(tmp_path / d / f) for f in files) <= 64_000_000
+        dumps.append({f: np.load(tmp_path / d / f) for f in files})
+    got = dumps[0]
+    assert all(a.dtype in (np.float32, np.float64) for a in got.values())
+    assert got["stop_step.npy"].tolist() == [n] and got["mel.npy"].shape == (B, n * r, 80)
+    frames = got["linear_sampled_frames.npy"].astype(np.int64)
+    assert 0 < len(frames) < n * r and (np.diff(frames) > 0).all()
+    np.testing.assert_array_equal(got["linear_sampled.npy"], arrays[3][1][:, frames])
+    assert all(np.array_equal(got[f], dumps[1][f]) for f in got)

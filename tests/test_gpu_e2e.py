@@ -774,10 +774,11 @@ def test_alignment_argmax_is_compared_on_every_step_of_a_full_horizon(atype, bia
 
 # ---- full size x full horizon against oracle outputs committed as fixtures (tests/golden/make_full_size_golden.py) ----
 def _golden(name):
-    p = os.path.join(os.path.dirname(__file__), "golden", name)
-    if not os.path.exists(p):
+    import make_full_size_golden as G
+    g = G.load(name)                  # (stored as parts under 1 MiB: tests/golden/<name>.partNN.npz)
+    if g is None:
         pytest.skip("%s not generated (python tests/golden/make_full_size_golden.py)" % name)
-    return np.load(p)
+    return g
 
 
 def test_C3_all_32_rows_all_128_steps_against_the_committed_oracle_outputs():

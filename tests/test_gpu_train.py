@@ -924,13 +924,11 @@ def test_C4_shard_gradients_at_32_rows_against_the_committed_autograd_fixture():
     """BASELINE.json configs[3], one data-parallel shard at its real size: B = 32, T_in = 128, T_out = 512 at the reference widths -- every
     gradient tensor's norm and a fixed sample of 2000 of its elements against float64 reverse-mode autograd of the independent torch
     formulation (tests/golden/full_C4_grads.npz, made by tests/golden/make_full_size_golden.py; round 5 compared a 2-row slice)."""
-    import os
     import torch
     import make_full_size_golden as G
-    p = os.path.join(os.path.dirname(__file__), "golden", "full_C4_grads.npz")
-    if not os.path.exists(p):
+    g = G.load("full_C4_grads.npz")      # (stored as parts under 1 MiB: tests/golden/full_C4_grads.partNN.npz)
+    if g is None:
         pytest.skip("full_C4_grads.npz not generated (python tests/golden/make_full_size_golden.py C4)")
-    g = np.load(p)
     hp, seed, ids, L, mt, lt = G.c4_case()
     assert int(g["seed"]) == seed
     tr = _trainer(hp, O.init_weights(hp, 1, seed))

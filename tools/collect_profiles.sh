@@ -17,16 +17,16 @@ if [ "$2" = "core" ]; then
   timeout 400 rocprofv3 --kernel-trace --stats -d $out/ks -o ks --output-format csv -- python bench.py --no-cpu-baseline --no-companions --no-stage-timing --steps 5 --warmup 2 --lanes 1 > $out/ks.log 2>&1
   cp $out/ks/*kernel_stats.csv $out/kernel_stats.csv 2>/dev/null
   python -c "import bench; print(bench.source_hash())" > $out/kernel_stats.hash
-  timeout 600 python bench.py --steps 20 --warmup 4 > $out/bench_C2.json 2> $out/bench_C2.err
+  timeout 600 python bench.py --full --steps 20 --warmup 4 > $out/bench_C2.json 2> $out/bench_C2.err
   rm -rf $out/ks/*kernel_trace.csv $out/pmc_f $out/pmc_w
   tail -c 400 $out/bench_C2.json
   exit 0
 fi
 [ -x tools/time_stages_native ] && timeout 60 ./tools/time_stages_native > $out/time_stages_native.txt 2>&1     # C ABI only, no Python: seconds
-timeout 600 python bench.py --steps 20 --warmup 4 > $out/bench_C2.json 2> $out/bench_C2.err
-timeout 300 python bench.py --workload C1 --steps 12 --warmup 3 > $out/bench_C1.json 2>> $out/bench_C2.err      # (with its CPU baseline: one utterance is cheap)
-for w in C3 C5; do timeout 300 python bench.py --no-cpu-baseline --workload $w --steps 12 --warmup 3 > $out/bench_$w.json 2>> $out/bench_C2.err; done
-timeout 300 python bench.py --no-cpu-baseline --coalesce 2 --steps 24 --warmup 4 > $out/bench_C2_coalesce2.json 2>> $out/bench_C2.err
+timeout 600 python bench.py --full --steps 20 --warmup 4 > $out/bench_C2.json 2> $out/bench_C2.err
+timeout 300 python bench.py --full --workload C1 --steps 12 --warmup 3 > $out/bench_C1.json 2>> $out/bench_C2.err      # (with its CPU baseline: one utterance is cheap)
+for w in C3 C5; do timeout 300 python bench.py --full --no-cpu-baseline --workload $w --steps 12 --warmup 3 > $out/bench_$w.json 2>> $out/bench_C2.err; done
+timeout 300 python bench.py --full --no-cpu-baseline --coalesce 2 --steps 24 --warmup 4 > $out/bench_C2_coalesce2.json 2>> $out/bench_C2.err
 timeout 300 python tools/bench_train.py > $out/train_step.json 2> $out/train.err
 timeout 300 python tools/bench_train.py --deterministic 0 > $out/train_step_atomics.json 2>> $out/train.err      # fp32 atomics instead of the ordered sums (the default since round 4)
 timeout 300 python tools/bench_train.py --exact-gemm 0 > $out/train_step_splitbf16.json 2>> $out/train.err
@@ -49,7 +49,7 @@ timeout 300 python tools/time_decoder.py C2:8 --json $out/decoder_timeline.json 
 [ -x tools/time_layers_native ] && timeout 120 ./tools/time_layers_native 20 > $out/time_layers_native.txt 2>&1
 [ -x tools/time_train_native ] && timeout 120 ./tools/time_train_native > $out/time_train_native.txt 2>&1      # one C4-shard training step through the C ABI, no Python
 [ -f multi-speaker-tacotron-tensorflow_amd/csrc/libtaco_hip_trace.so ] && TACO_LIB=$GRAFT_REPO_ROOT/multi-speaker-tacotron-tensorflow_amd/csrc/libtaco_hip_trace.so timeout 200 python tools/trace_chain.py 2>&1 | grep -v "amdgpu.ids\|RuntimeWarning\|load_library()" > $out/chain_timeline.txt
-timeout 600 python bench.py --workload C4 --steps 10 --warmup 2 > $out/bench_C4.json 2>> $out/bench_C2.err
+timeout 600 python bench.py --full --workload C4 --steps 10 --warmup 2 > $out/bench_C4.json 2>> $out/bench_C2.err
 timeout 400 rocprofv3 --kernel-trace --stats -d $out/tks -o tks --output-format csv -- python tools/bench_train.py --steps 4 --warmup 1 > $out/tks.log 2>&1
 cp $out/tks/*kernel_stats.csv $out/train_kernel_stats.csv 2>/dev/null; rm -rf $out/tks
 timeout 400 rocprofv3 --kernel-trace --stats -d $out/ks -o ks --output-format csv -- python bench.py --no-cpu-baseline --no-companions --no-stage-timing --steps 5 --warmup 2 --lanes 1 > $out/ks.log 2>&1

@@ -1,5 +1,5 @@
 """Where the HIP path's alignment arg-max differs from the oracle's, and how accurately the HIP path tracks the oracle's peak as the peak decays
-(tests/util.py's floor and tie criterion rest on these numbers).  python tools/scratch/argmax_probe.py [C3|C5]   (needs tests/golden/full_*.npz)"""
+(tests/util.py's floor and tie criterion rest on these numbers).  python tools/scratch/argmax_probe.py [C3|C5]   (needs tests/golden/full_*.partNN.npz)"""
 import sys, os, numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 for p in ("tests", "oracle", os.path.join("tests", "golden"), "."):
@@ -9,7 +9,7 @@ from util import build_model
 import torch
 which = sys.argv[1] if len(sys.argv) > 1 else "C3"
 if which == "C3":
-    g = np.load(os.path.join(ROOT, "tests/golden/full_C3.npz"))
+    g = G.load("full_C3.npz")
     hp, ns, seed, ids, L, spk = G.c3_case()
     m = build_model(hp, O.init_weights(hp, ns, seed), num_speakers=ns)
     lin, al = m.run(inputs=ids, input_lengths=L, speaker_id=spk, honor_stop=False)
@@ -18,7 +18,7 @@ if which == "C3":
     peak = ref.max(1); refmax = ref.argmax(1); second = np.sort(ref, axis=1)[:, -2, :]
     hip_at_ref = np.take_along_axis(al, refmax[:, None, :], 1)[:, 0, :]
 else:
-    g = np.load(os.path.join(ROOT, "tests/golden/full_C5.npz"))
+    g = G.load("full_C5.npz")
     hp, seed, ids, L = G.c5_case()
     m = build_model(hp, O.init_weights(hp, 1, seed))
     lin, al = m.run(inputs=ids, input_lengths=L, honor_stop=False)
