@@ -12,9 +12,16 @@
 extern "C" {
 #endif
 
-/* test hook: 0 = per-step launches for the sequential loops, 1 (default) = the persistent kernels that fit (post-net scan: k_bigru_duo);
- * 2..7 select earlier scan kernels, 8 = k_bigru_xcd (round 2: one direction per group of 16 CUs), 9 its two-workgroups-per-CU geometry
- * (tests / A-B timing) */
+/* test hook: which BiGRU scan runs (tests / A-B timing).  Any other value is refused with TACO_ERR_ARG and changes nothing.
+ *    0 = two launches per step
+ *    1 = (default) the fastest kernel that fits: k_bigru_oct (H = 256, 9 to 32 rows) or k_bigru_duo (up to 64 rows) on a whole MI355X,
+ *        else k_bigru_resw (H = 256), k_bigru_quad (H = 128), k_bigru_rows (other widths)
+ *    2 = k_bigru_rows (weights streamed every step)
+ *    3 = k_bigru_res (one unit per thread, libm transcendentals; H = 256 / 128)
+ *    7 = k_bigru_resw (H = 256: one CU per direction and row)
+ *   10 = k_bigru_oct wherever it fits (also below 9 rows), else k_bigru_duo
+ *   11 = k_bigru_duo, never k_bigru_oct
+ * A forced kernel that does not fit the width or the device falls back to k_bigru_rows. */
 int taco_debug_set_persistent(taco_model* m, int on);
 
 /* test hook: on = 1 (default) runs the feed-forward GEMMs of inference on the bf16 matrix cores with 3-term split

@@ -1,36 +1,26 @@
 // taco_bigru_xcd.h -- the BiGRU scan of a CBHG (modules.py:82-96: bidirectional_dynamic_rnn over two GRUCell(H))
-// at H = 256 (the post-net) as ONE persistent launch on the exchange machinery of taco_decoder_xcd.h.
+// at H = 256 (the post-net) as ONE persistent launch on the exchange machinery of taco_decoder_xcd.h, forward and backward.
 //
 // The input projection is hoisted (one GEMM over all frames, taco_lib.hip); what is sequential is, per direction and batch row,
 // T steps of  r,u = sigmoid(xg + h Wg_h);  c = tanh(xc + (r*h) Wc_h);  h' = u*h + (1-u)*c  -- 196 K MACs and two dependent
-// mat-vecs per step.  k_bigru_resw gives every (direction, row) chain one CU and keeps 2/3 of the recurrent weights on it:
-// 3.74 us per step on 64 of the 256 CUs (post-net, C2: 1.9 ms).  Here the 64 chains are spread over the whole chip:
-//   * groups of 16 members; a group owns ONE direction and RG batch rows for all T steps; member m owns hidden units
-//     16m..16m+15, wave w of it UPW = 16 / NWV consecutive units, and every lane keeps its 4-input slice of the wave's 3 UPW
-//     weight columns (r, u per unit, then the candidates) in VGPRs for the whole scan: nothing is re-read;
-//   * per step two exchanges through the XCD's L2 (8-byte {value, tag} granules, see taco_decoder_xcd.h): r*h after the gates,
-//     h' after the candidate.  The x-parts come from HBM / the Infinity Cache (100 MB at C2): the member's slice of them is fetched
-//     16 steps at a time, one block ahead, STRAIGHT INTO an LDS ring (global_load_lds_dwordx4: no VGPR is involved, so nothing can
-//     be demoted to scratch and nothing is waited for where the load is issued).  Loads return in order, so the first exchange
-//     poll after the issue also waits for it -- once per 16 steps, behind the gates pass of that step.  (Round 2 staged the block
-//     through a float4 array that the compiler kept in scratch: the far load was waited for at issue.)
-// Two geometries (NWV = waves per workgroup):
-//   NWV = 8 (default): 256 workgroups of 512 threads, one per CU, 16 groups (two per XCD), 2 units per wave.
-//   NWV = 4 (taco_debug_set_persistent(m, 9)): 512 workgroups of 256 threads, TWO per CU, 32 groups (four per XCD) of half as
-//            many rows, 4 units per wave; the two workgroups of a CU belong to different groups, i.e. to independent chains, so
-//            one could compute alone on its SIMDs while the other waits for an exchange.  Measured at C2: 6088 clocks per step
-//            against 5224 -- the compute phases do not shrink (they are chains of dependent instructions, not issue-bound) and
-//            the epilogue of four units per lane is longer.  Kept as the record of that experiment and as a second test geometry.
+// mat-vecs per step.  k_bigru_resw (taco_kernels.h) gives every (direction, row) chain one CU and keeps 2/3 of the recurrent
+// weights on it: 3.74 us per step on 64 of the 256 CUs.  The kernels here spread the chains over the whole chip instead: every
+// lane keeps its slice of the recurrent weight columns in VGPRs for the whole scan (nothing is re-read), and per direction-step
+// two exchanges go through the XCD's L2 (8-byte {value, tag} granules, see taco_decoder_xcd.h): r*h after the gates, h' after the
+// candidate.  The x-parts come from HBM / the Infinity Cache: a member's slice of them is fetched GX_BLK steps at a time, one block
+// ahead, STRAIGHT INTO an LDS ring (global_load_lds_dwordx4: no VGPR is involved, so nothing can be demoted to scratch and nothing
+// is waited for where the load is issued).
+//   k_bigru_duo<RG, TAPE, TRACE>  both directions of RG rows per group of 32 CUs, software-pipelined against each other (up to 64 rows)
+//   k_bigru_oct<UPW, TAPE, TRACE> ONE row and both directions per cluster of 32 / UPW CUs (up to 32 rows; the default from 9 rows on)
+//   k_bigru_duo_bwd<RG>, k_bigru_oct_bwd   the backward scans of a training step on the same two geometries
+// Round 2's whole-chip scan (one direction per group of 16 CUs, one dependent chain per step) was removed: its last source is in
+// commit 7a862c2, its measurements in profiles/HISTORY.md.
 // Length masking and the reverse_sequence time mapping of the backward direction follow A.7 exactly as k_bigru_resw does.
 #pragma once
 #include "taco_decoder_xcd.h"
 
-#define GX_MEMBERS 16
 #define GX_H 256
 #define GX_BLK 16            // steps per block of prefetched x-parts
-__host__ __device__ inline int gx_nreg(int NWV) { return 12 * (16 / NWV); }              // weight registers per thread
-__host__ __device__ inline int gx_ngroups(int NWV) { return 8 * (16 / NWV); }            // 16 (NWV 8: two per XCD) or 32 (NWV 4: four)
-__host__ __device__ inline size_t gx_lds_floats(int RG) { return (size_t)2 * RG * GX_H + (size_t)2 * GX_BLK * RG * 48 + 64; }
 typedef __attribute__((address_space(3))) float gx_lds_float;
 // one 16-byte-per-lane load from global memory straight into LDS: the wave's 64 x 16 bytes land contiguously at LDS byte address
 // `lds_dst` (wave-uniform, handed over in M0) + 16 * lane.  hipcc does not count this load: the caller waits (s_waitcnt vmcnt) before the
@@ -41,196 +31,11 @@ __device__ __forceinline__ void gx_load_lds16(const float* gsrc, unsigned lds_ds
                : "=&s"(keep) : "v"(gsrc), "s"(lds_dst) : "memory");
 }
 
-struct GxArgs {
-  const float* wpack0; const float* wpack1;   // [16 members][gx_nreg][64 NWV] per direction
-  const float* xproj;                         // [B*T, 6H] hoisted input projection, biases folded, backward direction time-reversed
-  const float* h0;                            // [B, 2H] initial states (fw | bw) or null
-  const int* lengths;                         // [B] or null (= T)
-  float* out;                                 // [B, T, 2H]
-  unsigned long long* xbuf; unsigned* ctl; unsigned* err; long long* trace;
-  int B, T, force_wt;
-};
-#define GX_STAMP(slot)                                                                                            \
-  do {                                                                                                            \
-    if (tracer && s >= 8 && s < 8 + DX_TRACE_STEPS) a.trace[(s - 8) * DX_TRACE_SLOTS + (slot)] = (long long)__builtin_readcyclecounter(); \
-  } while (0)
-// exchange granules of a launch: groups x [r*h | h'] x RG rows x H (the same for both geometries at their largest RG: 16 x 8 = 32 x 4)
-__host__ __device__ inline size_t gx_xbuf_granules(int ngroups, int RG) { return (size_t)ngroups * 2 * RG * GX_H; }
-
-template <int RG, int NWV>
-__global__ __launch_bounds__(64 * NWV) void k_bigru_xcd(const GxArgs a_in) {
-  extern __shared__ __attribute__((aligned(16))) float gx_smem[];
-  GxArgs a = a_in;
-  constexpr int NT = 64 * NWV, UPW = 16 / NWV, NREG = 12 * UPW;
-  constexpr int GPX = 1024 / NT;              // groups per XCD: 2 or 4
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  constexpr int H = GX_H, RL = DxRL<RG>::value;
-  float* xq = gx_smem;                 // [2][GX_BLK][RG][3][16]: x-parts of the member's 16 units, two blocks of GX_BLK steps (first:
-                                       // its LDS addresses go through M0 and stay below 48 KB)
-  float* hs = xq + 2 * GX_BLK * RG * 48;   // [RG][H] state
-  float* xs = hs + RG * H;             // [RG][H] r * h
-  int* ictl = reinterpret_cast<int*>(xs + RG * H);
-  dx_gu32* errw = (dx_gu32*)a.err;
-  dx_census((dx_gu32*)a.ctl, errw, a.force_wt, ictl, tid, 24);
-  const int place = __builtin_amdgcn_readfirstlane(ictl[0]), slot = __builtin_amdgcn_readfirstlane(ictl[1]);
-  DxRt rt; rt.err = errw; rt.wt = ictl[2] != 0; rt.dead = ictl[3] != 0;
-  // XCD-local: the workgroups of an XCD are dealt round-robin to its GPX groups (two workgroups that arrive together -- the pair
-  // of one CU, most likely -- end up in different groups); otherwise (slot = blockIdx / 8, place = blockIdx % 8) the same
-  // arithmetic gives 8 GPX groups of 16 by block index
-  const int group = place * GPX + (slot % GPX), member = slot / GPX;
-  const int dir = group & 1, row0 = (group >> 1) * RG;
-  if (row0 >= a.B) return;
-  const int T = a.T;
-  const bool tracer = a.trace && group == 0 && member == 0 && tid == 0;
-
-  float W[NREG];
-  {
-    const float* wp = (dir ? a.wpack1 : a.wpack0) + ((size_t)member * NREG) * NT + tid;
-#pragma unroll
-    for (int j = 0; j < NREG; ++j) W[j] = wp[(size_t)j * NT];
-  }
-  dx_gu64* X = (dx_gu64*)a.xbuf + (size_t)group * 2 * RG * H;       // [r*h : RG x H][h' : RG x H]
-  for (int i = tid; i < RG * H; i += NT) {
-    const int r = i / H, n = i % H, b = row0 + r;
-    hs[i] = (a.h0 && b < a.B) ? a.h0[(size_t)b * 2 * H + dir * H + n] : 0.f;
-    xs[i] = 0.f;
-  }
-  // epilogue role: quad 0 of every wave owns (rows dx_row(lane, q), units u0 .. u0+UPW-1)
-  const bool epl = lane < (RG >= 4 ? 4 : RG);
-  const int u0 = member * 16 + wave * UPW;
-  int erow[RL], eL[RL];
-  bool evalid[RL];
-#pragma unroll
-  for (int q = 0; q < RL; ++q) {
-    erow[q] = dx_row<RG>(lane & 3, q);
-    evalid[q] = epl && (row0 + erow[q] < a.B);
-    eL[q] = evalid[q] ? (a.lengths ? a.lengths[row0 + erow[q]] : T) : 0;
-  }
-  // x-part blocks: item i = (step j, row r, gate g, quarter c4) of a block -> one float4 of the member's 16 units; item i of a block
-  // lives at float offset 4 * i of its ring slot, so the 64 items of one wave-load are contiguous in LDS as the LDS-direct load needs
-  constexpr int NIT = GX_BLK * RG * 3 * 4, NLD = (NIT + NT - 1) / NT;
-  static_assert(NIT % 64 == 0, "a wave's 64 items are all inside the block or all outside");
-  const unsigned xq_lds = (unsigned)(size_t)(gx_lds_float*)xq;
-  auto blk_fetch = [&](int s0, int ring) {       // unconditional addresses (clamped); nothing is waited for here
-#pragma unroll
-    for (int u = 0; u < NLD; ++u) {
-      if (u * NT + wave * 64 < NIT) {            // wave-uniform
-        const int i = u * NT + tid;
-        const int c4 = i & 3, g = (i >> 2) % 3, r = (i / 12) % RG, j = i / (12 * RG);
-        const int b = min(row0 + r, a.B - 1), sx = min(s0 + j, T - 1);
-        const float* src = a.xproj + ((size_t)b * T + sx) * 6 * H + dir * 3 * H + g * H + member * 16 + 4 * c4;
-        const unsigned dst = __builtin_amdgcn_readfirstlane(xq_lds + (unsigned)(ring * GX_BLK * RG * 48 + 4 * (u * NT + wave * 64)) * 4u);
-        gx_load_lds16(src, dst);
-      }
-    }
-  };
-  blk_fetch(0, 0);
-  blk_fetch(GX_BLK, 1);
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  __syncthreads();
-
-  const int tid_outer = tid, lane_outer = lane;
-  for (int s = 0; s < T; ++s) {
-    const unsigned tag = (unsigned)s + 1u;
-    int tid = tid_outer, lane = lane_outer;                 // opaque per-iteration copies: see taco_decoder_xcd.h
-    asm volatile("" : "+v"(tid), "+v"(lane));
-    GX_STAMP(0);
-    const int sb = s & (GX_BLK - 1), ring = (s / GX_BLK) & 1;
-    // the block after next goes into the slot whose last reader finished before the barrier that ended the previous step; it is
-    // first read GX_BLK steps from now
-    if (sb == 0 && s > 0) blk_fetch(s + GX_BLK, ring ^ 1);
-    float x0[RL][3][UPW];
-#pragma unroll
-    for (int q = 0; q < RL; ++q)
-#pragma unroll
-      for (int g = 0; g < 3; ++g) {
-        const float* xp = xq + ((size_t)(ring * GX_BLK + sb) * RG + erow[q]) * 48 + g * 16 + wave * UPW;
-        if constexpr (UPW == 4) { const float4 v = *reinterpret_cast<const float4*>(xp); x0[q][g][0] = v.x; x0[q][g][1] = v.y; x0[q][g][2] = v.z; x0[q][g][3] = v.w; }
-        else { const float2 v = *reinterpret_cast<const float2*>(xp); x0[q][g][0] = v.x; x0[q][g][1] = v.y; }
-      }
-    float hv[RL][UPW], gv[RL][UPW];
-#pragma unroll
-    for (int q = 0; q < RL; ++q)
-#pragma unroll
-      for (int i = 0; i < UPW; ++i) hv[q][i] = hs[erow[q] * H + u0 + i];
-    // ---- gates: r, u of the wave's units (columns r_0, u_0, r_1, u_1, ...) ----
-    {
-      float acc[2 * UPW][RG], sm[2 * UPW][RL];
-      dx_zero<2 * UPW, RG>(acc);
-      dx_pass<0, 2 * UPW, RG, NREG, GX_H>(W, hs, lane, acc);
-      dx_reduce<2 * UPW, RG>(acc, sm, lane);
-      GX_STAMP(1);
-      // straight-line epilogue: all sigmoids first (independent chains interleave), then all stores behind one branch
-      float rh[RL][UPW];
-#pragma unroll
-      for (int q = 0; q < RL; ++q)
-#pragma unroll
-        for (int i = 0; i < UPW; ++i) {
-          const float rr = dx_sigmoid_fast(sm[2 * i][q] + x0[q][0][i]);
-          gv[q][i] = dx_sigmoid_fast(sm[2 * i + 1][q] + x0[q][1][i]);
-          rh[q][i] = rr * hv[q][i];
-        }
-      if (epl) {
-#pragma unroll
-        for (int q = 0; q < RL; ++q) dx_publish_n<UPW>(X + erow[q] * H + u0, 1, rh[q], tag, rt);
-      }
-    }
-    GX_STAMP(2);
-    dx_gather<RG, GX_H, false, GX_H, NT>(X, tag, xs, 0, 0, 0, tid, rt);
-    GX_STAMP(3);
-    __syncthreads();
-    GX_STAMP(4);
-    // ---- candidate and the new state ----
-    {
-      float acc[UPW][RG], sm[UPW][RL];
-      dx_zero<UPW, RG>(acc);
-      dx_pass<8 * UPW, UPW, RG, NREG, GX_H>(W, xs, lane, acc);
-      dx_reduce<UPW, RG>(acc, sm, lane);
-      GX_STAMP(5);
-      float nv[RL][UPW];
-      bool active[RL];
-#pragma unroll
-      for (int q = 0; q < RL; ++q) {
-        active[q] = s < eL[q];                               // A.7: row active iff s < L; forward t = s, backward t = L-1-s
-#pragma unroll
-        for (int i = 0; i < UPW; ++i) {
-          const float cc = taco_tanh_fast(sm[i][q] + x0[q][2][i]);
-          float blend = gv[q][i] * hv[q][i] + (1.f - gv[q][i]) * cc;
-          DX_PIN(blend);
-          nv[q][i] = active[q] ? blend : hv[q][i];
-        }
-      }
-      if (epl) {
-#pragma unroll
-        for (int q = 0; q < RL; ++q) dx_publish_n<UPW>(X + RG * H + erow[q] * H + u0, 1, nv[q], tag, rt);
-      }
-#pragma unroll
-      for (int q = 0; q < RL; ++q)
-        if (evalid[q]) {
-          const int t = (dir && active[q]) ? (eL[q] - 1 - s) : s;
-          float* po = a.out + ((size_t)(row0 + erow[q]) * T + t) * 2 * H + dir * H + u0;
-          if constexpr (UPW == 4) *reinterpret_cast<float4*>(po) = active[q] ? make_float4(nv[q][0], nv[q][1], nv[q][2], nv[q][3]) : make_float4(0.f, 0.f, 0.f, 0.f);
-          else *reinterpret_cast<float2*>(po) = active[q] ? make_float2(nv[q][0], nv[q][1]) : make_float2(0.f, 0.f);
-        }
-    }
-    GX_STAMP(6);
-    dx_gather<RG, GX_H, false, GX_H, NT>(X + RG * H, tag, hs, 0, 0, 0, tid, rt);
-    GX_STAMP(7);
-    // the slot fetched at the start of this block is read from the next step on: every wave makes sure ITS part has landed (it
-    // has, long ago: waves that poll have waited for it at their first poll already) ahead of the barrier that publishes it
-    if (sb == GX_BLK - 1) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    GX_STAMP(8);
-    __syncthreads();
-    GX_STAMP(9);
-  }
-}
-
 // ------------------------------------------------------------------------------------------------------------------------------
 // k_bigru_duo<RG>: the same scan with BOTH directions of RG batch rows owned by one group of 32 CUs (one XCD), the two directions
 // software-pipelined against each other inside every wave.
 //
-// k_bigru_xcd spends 42 % of a step waiting for its two exchanges: publish -> L2 -> poll is ~0.5 us and nothing else can run,
+// Round 2's scan (one direction per group) spent 42 % of a step waiting for its two exchanges: publish -> L2 -> poll is ~0.5 us and nothing else can run,
 // because the step is one dependent chain.  The forward and the backward direction of a BiGRU are two INDEPENDENT chains.  Here a
 // member owns hidden units 8m .. 8m+7 of both directions (wave w: unit 8m + w, three weight columns per direction = 24 VGPRs, the
 // same register budget as before), and a step interleaves them:
@@ -241,15 +46,15 @@ __global__ __launch_bounds__(64 * NWV) void k_bigru_xcd(const GxArgs a_in) {
 // so that every exchange has one compute phase of the other direction between its publish and its gather.  The polls are issued
 // EARLY as well: the loads of a gather are requested before the compute phase in front of it and examined after it (an L2 read
 // round trip is ~300 clocks even when the granule is already there), and only re-polled if a producer was late.  The per-wave
-// instruction count of a step is the same as k_bigru_xcd's (each direction still does RG rows per pass: the DPP reduction cost is
-// per column, not per row, so splitting the ROWS in two sets would have doubled it -- which is what the NWV = 4 geometry measured).
+// instruction count of a step is the same as that scan's (each direction still does RG rows per pass: the DPP reduction cost is
+// per column, not per row, so splitting the ROWS in two sets would have doubled it -- which is what its 4-wave geometry measured).
 // Rows per group: B <= 8: 1, <= 16: 2, <= 32: 4, <= 64: 8.
 // ------------------------------------------------------------------------------------------------------------------------------
 #define GD_MEMBERS 32
 #define GD_NREG 24           // weight registers per thread: [dir][r | u | c][4 inputs]
 __host__ __device__ inline size_t gd_ring_floats(int RG) { return (size_t)2 * 2 * GX_BLK * RG * 24; }      // [slot][dir][step][row][gate][8 units]
 __host__ __device__ inline size_t gd_lds_floats(int RG) { return gd_ring_floats(RG) + (size_t)4 * RG * GX_H + 64; }
-__host__ __device__ inline size_t gd_xbuf_granules(int RG) { return (size_t)DX_NGROUP * 4 * RG * GX_H; }  // groups x [dir][r*h | h'] x RG x H
+__host__ __device__ constexpr size_t gd_xbuf_granules(int RG) { return (size_t)DX_NGROUP * 4 * RG * GX_H; }  // groups x [dir][r*h | h'] x RG x H
 
 // the loads of a gather, requested now and examined later (dx_gather split in two)
 template <int RG, int NT>
@@ -510,7 +315,7 @@ __global__ __launch_bounds__(512) void k_bigru_duo(const GdArgs a_in) {
 // ------------------------------------------------------------------------------------------------------------------------------
 __host__ __device__ inline size_t go_ring_floats(int UPW) { return (size_t)2 * 2 * GX_BLK * 3 * 8 * UPW; }      // [slot][dir][step][gate][8 UPW units]
 __host__ __device__ inline size_t go_lds_floats(int UPW) { return go_ring_floats(UPW) + (size_t)4 * GX_H + 64; }
-__host__ __device__ inline size_t go_xbuf_granules() { return (size_t)DX_NGROUP * 4 * 4 * GX_H; }            // <= 32 clusters x [dir][r*h | h'] x H
+__host__ __device__ constexpr size_t go_xbuf_granules() { return (size_t)DX_NGROUP * 4 * 4 * GX_H; }            // <= 32 clusters x [dir][r*h | h'] x H
 
 template <int UPW, int NG>
 __device__ __forceinline__ void go_reduce(const float (&v)[UPW * NG], float (&out)[NG]) {

@@ -214,7 +214,6 @@ struct Cbhg {
   size_t gd_pack = 0, gb_pack = 0;                     // k_bigru_duo / k_bigru_duo_bwd: [2 dirs][32 members][12][512]
   size_t gob_pack = 0;                                 // k_bigru_oct_bwd (training): [2 dirs][8 members][48][512]
   size_t go_pack[3] = {0, 0, 0};                       // k_bigru_oct<UPW>, UPW = 1, 2, 4: [2 dirs][32 / UPW members][12 UPW][512]
-  size_t gx_pack[2] = {0, 0}, gx_pack4[2] = {0, 0};   // per-thread weight packs of k_bigru_xcd (8-wave and 4-wave workgroups), H = 256 only
   // fused front (taco_front.h): per bank width (same order as `bank`) the produce pack [k32 step][16-channel tile][lane][8] (hi, lo)
   // and its step count; front_kind 0 = not built, 1 = <TN 2, XS 80, CINP 80, KWMAX 8> (post-net), 2 = <TN 1, XS 144, CINP 128, KWMAX 16> (encoder)
   std::vector<size_t> fr_wh, fr_wl; std::vector<int> fr_ns; int front_kind = 0;
@@ -253,7 +252,7 @@ struct taco_model {
   std::vector<size_t> spk_table;   // speaker_embedding_size == 1 variant
   int force_cfg = -1;
   unsigned* d_err = nullptr;   // set by a persistent kernel whose bounded spin expired
-  int persist = 1;             // use the persistent BiGRU kernel when it fits
+  int persist = 1;             // which BiGRU scan runs: a ScanMode (scan_plan; taco_debug_set_persistent)
   int ff_rot = 1;              // k_pointwise_chain: workgroups of an XCD start their K loops at different steps (0: taco_model_set_batch_invariant)
   int bf3 = 1;                 // feed-forward GEMMs (both CBHGs, linear head) on the bf16 matrix cores with 3-term split operands
   int bf3x6 = 0;               // training shadow model: feed-forward GEMMs on the six-product (fp32-grade) split-bf16 instantiation
@@ -745,26 +744,6 @@ static void make_cbhg(taco_model* m, Cbhg& c, const std::string& sc, int in_dim,
             }
         c.res_g2p[dir] = arena_put(m, g2p.data(), g2p.size());
         c.res_c1p[dir] = arena_put(m, c1p.data(), c1p.size());
-        if (!m->tp) {   // k_bigru_xcd<RG, NWV>: member mem, wave w owns units 16 mem + UPW w .. + UPW - 1 (UPW = 16 / NWV); lane l holds
-                        // h rows 4l..4l+3 of the columns r_0, u_0, r_1, u_1, ... and then of the candidates c_0, c_1, ...
-          for (int nwv = 8; nwv >= 4; nwv -= 4) {
-            const int NT = 64 * nwv, UPW = 16 / nwv, NREG = gx_nreg(nwv);
-            std::vector<float> gp((size_t)GX_MEMBERS * NREG * NT, 0.f);
-            for (int mem = 0; mem < GX_MEMBERS; ++mem)
-              for (int tid = 0; tid < NT; ++tid) {
-                const int w = tid >> 6, l = tid & 63, u0 = mem * 16 + UPW * w;
-                for (int e = 0; e < 4; ++e) {
-                  const size_t kr = (size_t)(I + 4 * l + e);
-                  auto put = [&](int reg, float v) { gp[((size_t)mem * NREG + reg) * NT + tid] = v; };
-                  for (int i = 0; i < UPW; ++i) {
-                    put(8 * i + e, gk[kr * 2 * H + u0 + i]);  put(8 * i + 4 + e, gk[kr * 2 * H + H + u0 + i]);   // r_i, u_i
-                    put(8 * UPW + 4 * i + e, ck[kr * H + u0 + i]);                                              // c_i
-                  }
-                }
-              }
-            (nwv == 8 ? c.gx_pack : c.gx_pack4)[dir] = arena_put(m, gp.data(), gp.size());
-          }
-        }
       } }
   }
   if (H == GX_H) {
@@ -1170,7 +1149,9 @@ static void carve_cbhg(Carver& cv, const Cbhg& c, int B, int T, CbhgWs& w) {
   w.hi0 = cv.f(M * c.rnn); w.hi1 = cv.f(M * c.rnn);
   w.xproj = cv.f(M * 6 * c.rnn);
   w.h = cv.f((size_t)2 * B * c.rnn); w.rh = cv.f((size_t)2 * B * c.rnn); w.u = cv.f((size_t)2 * B * c.rnn);
-  w.gxbuf_bytes = gx_xbuf_granules(16, 8) * sizeof(unsigned long long);  // k_bigru_xcd exchange granules (16 groups x 8 rows = 32 groups x 4 rows; k_bigru_duo / k_bigru_oct need no more)
+  // exchange granules of the whole-chip forward scans: k_bigru_duo at its 8 rows per group needs the most (a training tape carves its own)
+  static_assert(gd_xbuf_granules(8) == (size_t)16 * 2 * 8 * 256 && gd_xbuf_granules(8) >= go_xbuf_granules(), "gxbuf holds the granules of k_bigru_duo<8> and of k_bigru_oct");
+  w.gxbuf_bytes = gd_xbuf_granules(8) * sizeof(unsigned long long);
   w.gxbuf = (unsigned long long*)cv.raw(w.gxbuf_bytes);
   w.gxctl = (unsigned*)cv.raw(256);
 }
@@ -1192,69 +1173,123 @@ static size_t bigru_res_lds(int H, int KL, int R) {
   return ((size_t)3 * R * H + (size_t)NQ * R * 3 * H) * sizeof(float) + (size_t)KL * NQ * H * 3 * sizeof(float);
 }
 
-// k_bigru_duo (taco_bigru_xcd.h) usable for this scan?  (H = 256, a whole MI355X, at most 64 rows)
-static bool duo_usable(const taco_model* m, const Cbhg& c, int B, int T) {
-  return (m->persist == 1 || m->persist == 10 || m->persist == 11) && m->dx_mode && c.gd_pack && c.rnn == GX_H && B <= 64 && T >= 2 && m->cu_count >= 256;
+// ---- which BiGRU scan runs ----
+// taco_debug_set_persistent(m, mode): SCAN_AUTO is the default; the others force one engine where it fits (A/B tests, tools/).
+enum ScanMode { SCAN_PER_STEP = 0, SCAN_AUTO = 1, SCAN_ROWS = 2, SCAN_RES = 3, SCAN_RESW = 7, SCAN_OCT = 10, SCAN_DUO = 11 };
+enum ScanKernel { SCAN_K_STEPS, SCAN_K_ROWS, SCAN_K_RES, SCAN_K_QUAD, SCAN_K_RESW, SCAN_K_DUO, SCAN_K_OCT };
+enum ScanBwd { SCAN_BWD_ROWS, SCAN_BWD_DUO, SCAN_BWD_OCT };       // ROWS: the per-row kernels (k_bigru_resb / k_bigru_rows_bwd, picked by width)
+enum ScanWhyNot { SCAN_WHY_NONE, SCAN_WHY_ENGINE_OFF, SCAN_WHY_CUS, SCAN_WHY_ROWS, SCAN_WHY_MODE, SCAN_WHY_WIDTH, SCAN_WHY_FRAMES };
+struct ScanPlan {
+  ScanKernel kernel;        // what bigru_scan launches (the training forward runs the TAPE instantiation of it where there is one)
+  int upw;                  // k_bigru_oct: units per wave -- one row per cluster of 32 / upw CUs
+  int rg;                   // k_bigru_duo / k_bigru_duo_bwd: rows per group of 32 CUs
+  ScanBwd bwd;              // the backward scan of a training step
+  ScanWhyNot why_not_whole_chip;      // first reason against k_bigru_duo (NONE: it fits; k_bigru_oct needs no more, only fewer rows)
+};
+// The one place that decides.  Pure: launches nothing, touches no device state.
+// tape: the training forward -- below the whole-chip kernels only k_bigru_res / k_bigru_quad / k_bigru_rows have TAPE instantiations,
+// and a forced mode does not choose among them (SCAN_K_STEPS then means: no kernel fits).
+static ScanPlan scan_plan(const taco_model* m, const Cbhg& c, int B, int T, bool tape = false) {
+  const int mode = m->persist, H = c.rnn;
+  ScanPlan p = {SCAN_K_STEPS, 0, 1, SCAN_BWD_ROWS, SCAN_WHY_NONE};
+  while (p.rg * DX_NGROUP < B) p.rg *= 2;
+  // the whole-chip kernels (taco_bigru_xcd.h): H = 256, an unpartitioned MI355X, the decoder engine not switched off
+  const bool chip = m->dx_mode && H == GX_H && T >= 2 && m->cu_count >= 256;
+  if (!m->dx_mode) p.why_not_whole_chip = SCAN_WHY_ENGINE_OFF;
+  else if (m->cu_count < 256) p.why_not_whole_chip = SCAN_WHY_CUS;
+  else if (B > 8 * DX_NGROUP) p.why_not_whole_chip = SCAN_WHY_ROWS;
+  else if (mode != SCAN_AUTO && mode != SCAN_OCT && mode != SCAN_DUO) p.why_not_whole_chip = SCAN_WHY_MODE;
+  else if (H != GX_H || !c.gd_pack) p.why_not_whole_chip = SCAN_WHY_WIDTH;
+  else if (T < 2) p.why_not_whole_chip = SCAN_WHY_FRAMES;
+  // k_bigru_oct: up to 32 rows.  SCAN_AUTO: from 9 rows on -- up to eight rows k_bigru_duo<1> IS the one-row geometry on 32 CUs;
+  // SCAN_OCT: wherever it fits; SCAN_DUO: never (round 4's engine)
+  if (chip && (mode == SCAN_AUTO || mode == SCAN_OCT) && c.go_pack[0] && B <= 32) p.upw = B > 16 ? 4 : B > 8 ? 2 : mode == SCAN_OCT ? 1 : 0;
+  if (p.upw) p.kernel = SCAN_K_OCT;
+  else if (p.why_not_whole_chip == SCAN_WHY_NONE) p.kernel = SCAN_K_DUO;
+  // weights resident on the CU, one (direction, row) per workgroup.  H = 256: four units per thread, k_bigru_resw 3.74 us/step (one unit
+  // per thread, k_bigru_res: 5.7; re-streaming everything, k_bigru_rows: 7.1); H = 128: k_bigru_quad (SCAN_RES: its libm reference)
+  else if (!tape && (mode == SCAN_AUTO || mode == SCAN_RESW) && H == 256) p.kernel = SCAN_K_RESW;
+  else if ((tape || mode == SCAN_AUTO || mode == SCAN_RES) && (H == 256 || H == 128)) p.kernel = H == 128 && mode == SCAN_AUTO ? SCAN_K_QUAD : SCAN_K_RES;
+  else {      // any other width, or a forced mode that does not fit: the whole scan in one launch, weights streamed from L2 every step
+    int R = 0; size_t lds = 0;
+    p.kernel = (tape || mode != SCAN_PER_STEP) && bigru_rows_cfg(B, H, &R, &lds) ? SCAN_K_ROWS : SCAN_K_STEPS;
+  }
+  // the backward scans run on the geometry of the forward one where the training packs exist
+  if (p.why_not_whole_chip == SCAN_WHY_NONE && c.gb_pack) p.bwd = p.upw && c.gob_pack ? SCAN_BWD_OCT : SCAN_BWD_DUO;
+  return p;
+}
+static const char* scan_kernel_name(ScanKernel k) {
+  static const char* const names[] = {"two launches per step", "k_bigru_rows", "k_bigru_res", "k_bigru_quad", "k_bigru_resw", "k_bigru_duo", "k_bigru_oct"};
+  return names[k];
+}
+
+// A/B build -DGO_KNOB_RT: the twelve knobs of k_bigru_oct and (entries 12..15) the four second requests of k_bigru_oct_bwd from
+// TACO_GO_KNOB (taco_bigru_xcd.h); eager launches only
+static int go_knob_upload() {
+#ifdef GO_KNOB_RT
+  int d[16]; for (int i = 0; i < 16; ++i) d[i] = i < 12 ? go_knob_default(i) : gob_knob_default(i - 12);
+  if (const char* e = getenv("TACO_GO_KNOB")) { int i = 0; const char* p = e; while (*p && i < 16) { d[i++] = atoi(p); while (*p && *p != ',') ++p; if (*p == ',') ++p; } }
+  HIPCHK(hipMemcpyToSymbol(HIP_SYMBOL(g_go_knob), d, sizeof d));
+#endif
+  return 0;
+}
+template <bool TAPE, bool TRACE>
+static void duo_launch_rg(int RG, dim3 grid, dim3 blk, size_t lds, hipStream_t st, const GdArgs& a) {
+  switch (RG) {
+    case 1: hipLaunchKernelGGL((k_bigru_duo<1, TAPE, TRACE>), grid, blk, lds, st, a); break;
+    case 2: hipLaunchKernelGGL((k_bigru_duo<2, TAPE, TRACE>), grid, blk, lds, st, a); break;
+    case 4: hipLaunchKernelGGL((k_bigru_duo<4, TAPE, TRACE>), grid, blk, lds, st, a); break;
+    default: hipLaunchKernelGGL((k_bigru_duo<8, TAPE, TRACE>), grid, blk, lds, st, a); break;
+  }
+}
+template <bool TAPE, bool TRACE>
+static void oct_launch_upw(int UPW, dim3 grid, dim3 blk, size_t lds, hipStream_t st, const GdArgs& a) {
+  switch (UPW) {
+    case 1: hipLaunchKernelGGL((k_bigru_oct<1, TAPE, TRACE>), grid, blk, lds, st, a); break;
+    case 2: hipLaunchKernelGGL((k_bigru_oct<2, TAPE, TRACE>), grid, blk, lds, st, a); break;
+    default: hipLaunchKernelGGL((k_bigru_oct<4, TAPE, TRACE>), grid, blk, lds, st, a); break;
+  }
 }
 // both directions of RG rows on one group of 32 CUs, software-pipelined against each other; gsave != null: the TAPE instantiation
-static int duo_launch(const taco_model* m, hipStream_t st, const Cbhg& c, int B, int T, const float* xproj, const int* lengths, const float* init_state,
+static int duo_launch(const taco_model* m, hipStream_t st, const Cbhg& c, int RG, int B, int T, const float* xproj, const int* lengths, const float* init_state,
                       float* out, float* gsave, unsigned long long* gxbuf, unsigned* gxctl) {
   ChipTurn turn(m->device, st);
   GdArgs a; memset(&a, 0, sizeof a);
   a.wpack = AP(m, c.gd_pack); a.xproj = xproj; a.h0 = init_state; a.lengths = lengths; a.out = out; a.gsave = gsave;
-  a.xbuf = gxbuf; a.ctl = gxctl; a.err = m->d_err; a.trace = (m->trace_on && m->d_trace) ? m->d_trace + DX_TRACE_STEPS * DX_TRACE_SLOTS : nullptr;
+  a.xbuf = gxbuf; a.ctl = gxctl; a.err = m->d_err; a.trace = (m->trace_on && m->d_trace && !gsave) ? m->d_trace + DX_TRACE_STEPS * DX_TRACE_SLOTS : nullptr;
   a.B = B; a.T = T; a.force_wt = m->dx_mode == 2 ? 1 : 0;
-  int RG = 1;
-  while (RG * DX_NGROUP < B) RG *= 2;
   HIPCHK(clear_polled(gxbuf, (size_t)((char*)gxctl - (char*)gxbuf) + 256, st));
   const size_t lds = std::max(gd_lds_floats(RG) * sizeof(float), (size_t)96 * 1024);      // one workgroup per CU
   const dim3 grid(DX_NGROUP * GD_MEMBERS), blk(512);
-  if (gsave) a.trace = nullptr;
-  if (a.trace) {          // the stamped instantiations (tools/trace_bigru.py): inference only
-    switch (RG) {
-      case 1: hipLaunchKernelGGL((k_bigru_duo<1, false, true>), grid, blk, lds, st, a); break;
-      case 2: hipLaunchKernelGGL((k_bigru_duo<2, false, true>), grid, blk, lds, st, a); break;
-      case 4: hipLaunchKernelGGL((k_bigru_duo<4, false, true>), grid, blk, lds, st, a); break;
-      default: hipLaunchKernelGGL((k_bigru_duo<8, false, true>), grid, blk, lds, st, a); break;
-    }
-  } else if (gsave) {
-    switch (RG) {
-      case 1: hipLaunchKernelGGL((k_bigru_duo<1, true>), grid, blk, lds, st, a); break;
-      case 2: hipLaunchKernelGGL((k_bigru_duo<2, true>), grid, blk, lds, st, a); break;
-      case 4: hipLaunchKernelGGL((k_bigru_duo<4, true>), grid, blk, lds, st, a); break;
-      default: hipLaunchKernelGGL((k_bigru_duo<8, true>), grid, blk, lds, st, a); break;
-    }
-  } else {
-    switch (RG) {
-      case 1: hipLaunchKernelGGL((k_bigru_duo<1, false>), grid, blk, lds, st, a); break;
-      case 2: hipLaunchKernelGGL((k_bigru_duo<2, false>), grid, blk, lds, st, a); break;
-      case 4: hipLaunchKernelGGL((k_bigru_duo<4, false>), grid, blk, lds, st, a); break;
-      default: hipLaunchKernelGGL((k_bigru_duo<8, false>), grid, blk, lds, st, a); break;
-    }
+  if (a.trace) duo_launch_rg<false, true>(RG, grid, blk, lds, st, a);          // the stamped instantiations (tools/trace_bigru.py): inference only
+  else if (gsave) duo_launch_rg<true, false>(RG, grid, blk, lds, st, a);
+  else duo_launch_rg<false, false>(RG, grid, blk, lds, st, a);
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+// the backward scan on the geometry of k_bigru_duo: both directions of RG rows per group of 32 CUs, software-pipelined against each other
+static int duo_bwd_launch(const taco_model* m, hipStream_t st, const Cbhg& c, int RG, int B, int T, const float* dout, const float* out, const float* gsave,
+                          const float* h0, const int* lengths, float* dg, float* rh, float* dh0, unsigned long long* gxbuf, unsigned* gxctl) {
+  ChipTurn turn(m->device, st);
+  GbArgs a; memset(&a, 0, sizeof a);
+  a.wpack = AP(m, c.gb_pack); a.dout = dout; a.out = out; a.gsave = gsave; a.h0 = h0; a.lengths = lengths; a.dg = dg; a.rh = rh; a.dh0 = dh0;
+  a.xbuf = gxbuf; a.ctl = gxctl; a.err = m->d_err; a.B = B; a.T = T; a.force_wt = m->dx_mode == 2 ? 1 : 0;
+  const size_t lds = std::max(gb_lds_floats(RG) * sizeof(float), (size_t)96 * 1024);      // one workgroup per CU
+  const dim3 grid(DX_NGROUP * GD_MEMBERS), blk(512);
+  switch (RG) {
+    case 1: hipLaunchKernelGGL((k_bigru_duo_bwd<1>), grid, blk, lds, st, a); break;
+    case 2: hipLaunchKernelGGL((k_bigru_duo_bwd<2>), grid, blk, lds, st, a); break;
+    case 4: hipLaunchKernelGGL((k_bigru_duo_bwd<4>), grid, blk, lds, st, a); break;
+    default: hipLaunchKernelGGL((k_bigru_duo_bwd<8>), grid, blk, lds, st, a); break;
   }
   HIPCHK(hipGetLastError());
   return 0;
 }
-// k_bigru_oct: one row per cluster of 32 / UPW CUs (UPW = 4: up to 32 rows, 2: 16, 1: 8).  persist 1 (default): from 9 rows on -- up to eight
-// rows k_bigru_duo<1> IS the one-row geometry on 32 CUs --; persist 10: wherever it fits (A/B); persist 11: never (round 4's k_bigru_duo)
-static int oct_upw(const taco_model* m, const Cbhg& c, int B, int T) {
-  if (!(m->persist == 1 || m->persist == 10) || !m->dx_mode || !c.go_pack[0] || c.rnn != GX_H || B > 32 || T < 2 || m->cu_count < 256) return 0;
-  if (B > 16) return 4;
-  if (B > 8) return 2;
-  return m->persist == 10 ? 1 : 0;
-}
-// the backward scan on the same geometry (k_bigru_oct_bwd; four units per wave: up to 32 rows), where the forward scan runs on k_bigru_oct
-static bool oct_bwd_usable(const taco_model* m, const Cbhg& c, int B, int T) { return c.gob_pack && oct_upw(m, c, B, T) != 0; }
+// the backward scan on the geometry of k_bigru_oct (k_bigru_oct_bwd; four units per wave: up to 32 rows), where the forward scan runs on it
 static int oct_bwd_launch(const taco_model* m, hipStream_t st, const Cbhg& c, int B, int T, const float* dout, const float* out, const float* gsave,
                           const float* h0, const int* lengths, float* dg, float* rh, float* dh0, unsigned long long* gxbuf, unsigned* gxctl) {
   ChipTurn turn(m->device, st);
-#ifdef GO_KNOB_RT
-  {   // A/B build: entries 12..15 of TACO_GO_KNOB are the backward scan's four second requests
-    int d[16]; for (int i = 0; i < 16; ++i) d[i] = i < 12 ? go_knob_default(i) : gob_knob_default(i - 12);
-    if (const char* e = getenv("TACO_GO_KNOB")) { int i = 0; const char* p = e; while (*p && i < 16) { d[i++] = atoi(p); while (*p && *p != ',') ++p; if (*p == ',') ++p; } }
-    HIPCHK(hipMemcpyToSymbol(HIP_SYMBOL(g_go_knob), d, sizeof d));
-  }
-#endif
+  TRY(go_knob_upload());
   GbArgs a; memset(&a, 0, sizeof a);
   a.wpack = AP(m, c.gob_pack); a.dout = dout; a.out = out; a.gsave = gsave; a.h0 = h0; a.lengths = lengths; a.dg = dg; a.rh = rh; a.dh0 = dh0;
   a.xbuf = gxbuf; a.ctl = gxctl; a.err = m->d_err; a.B = B; a.T = T; a.force_wt = m->dx_mode == 2 ? 1 : 0;
@@ -1263,16 +1298,11 @@ static int oct_bwd_launch(const taco_model* m, hipStream_t st, const Cbhg& c, in
   HIPCHK(hipGetLastError());
   return 0;
 }
+// k_bigru_oct: one row per cluster of 32 / UPW CUs (UPW = 4: up to 32 rows, 2: 16, 1: 8); gsave != null: the TAPE instantiation
 static int oct_launch(const taco_model* m, hipStream_t st, const Cbhg& c, int UPW, int B, int T, const float* xproj, const int* lengths, const float* init_state,
                       float* out, float* gsave, unsigned long long* gxbuf, unsigned* gxctl) {
   ChipTurn turn(m->device, st);
-#ifdef GO_KNOB_RT
-  {   // A/B build: the twelve knobs of k_bigru_oct from TACO_GO_KNOB (taco_bigru_xcd.h); eager launches only
-    int d[16]; for (int i = 0; i < 16; ++i) d[i] = i < 12 ? go_knob_default(i) : gob_knob_default(i - 12);
-    if (const char* e = getenv("TACO_GO_KNOB")) { int i = 0; const char* p = e; while (*p && i < 16) { d[i++] = atoi(p); while (*p && *p != ',') ++p; if (*p == ',') ++p; } }
-    HIPCHK(hipMemcpyToSymbol(HIP_SYMBOL(g_go_knob), d, sizeof d));
-  }
-#endif
+  TRY(go_knob_upload());
   GdArgs a; memset(&a, 0, sizeof a);
   a.wpack = AP(m, c.go_pack[UPW == 4 ? 2 : UPW == 2 ? 1 : 0]); a.xproj = xproj; a.h0 = init_state; a.lengths = lengths; a.out = out; a.gsave = gsave;
   a.xbuf = gxbuf; a.ctl = gxctl; a.err = m->d_err; a.trace = (m->trace_on && m->d_trace && !gsave) ? m->d_trace + DX_TRACE_STEPS * DX_TRACE_SLOTS : nullptr;
@@ -1280,114 +1310,50 @@ static int oct_launch(const taco_model* m, hipStream_t st, const Cbhg& c, int UP
   HIPCHK(clear_polled(gxbuf, (size_t)((char*)gxctl - (char*)gxbuf) + 256, st));
   const size_t lds = std::max(go_lds_floats(UPW) * sizeof(float), (size_t)96 * 1024);      // one workgroup per CU
   const dim3 grid(DX_NGROUP * DX_GROUP), blk(512);
-  if (a.trace) {          // the stamped instantiation (tools/trace_bigru.py): inference only
-    switch (UPW) {
-      case 1: hipLaunchKernelGGL((k_bigru_oct<1, false, true>), grid, blk, lds, st, a); break;
-      case 2: hipLaunchKernelGGL((k_bigru_oct<2, false, true>), grid, blk, lds, st, a); break;
-      default: hipLaunchKernelGGL((k_bigru_oct<4, false, true>), grid, blk, lds, st, a); break;
-    }
-  } else if (gsave) {
-    switch (UPW) {
-      case 1: hipLaunchKernelGGL((k_bigru_oct<1, true>), grid, blk, lds, st, a); break;
-      case 2: hipLaunchKernelGGL((k_bigru_oct<2, true>), grid, blk, lds, st, a); break;
-      default: hipLaunchKernelGGL((k_bigru_oct<4, true>), grid, blk, lds, st, a); break;
-    }
-  } else {
-    switch (UPW) {
-      case 1: hipLaunchKernelGGL((k_bigru_oct<1, false>), grid, blk, lds, st, a); break;
-      case 2: hipLaunchKernelGGL((k_bigru_oct<2, false>), grid, blk, lds, st, a); break;
-      default: hipLaunchKernelGGL((k_bigru_oct<4, false>), grid, blk, lds, st, a); break;
-    }
-  }
+  if (a.trace) oct_launch_upw<false, true>(UPW, grid, blk, lds, st, a);        // the stamped instantiations (tools/trace_bigru.py): inference only
+  else if (gsave) oct_launch_upw<true, false>(UPW, grid, blk, lds, st, a);
+  else oct_launch_upw<false, false>(UPW, grid, blk, lds, st, a);
   HIPCHK(hipGetLastError());
   return 0;
 }
 
 // BiGRU (modules.py:82-96 -> TF bidirectional_dynamic_rnn, A.7): hoisted x.[Wg_x|Wc_x]+b for both
-// directions as one GEMM, then T sequential steps of two launches (gates; candidate+update), both
-// directions side by side in each launch.  x [B*T, rnn], out [B*T, 2*rnn].
+// directions as one GEMM, then the scan that scan_plan picks; without a single-launch kernel, T sequential steps of two launches
+// (gates; candidate+update), both directions side by side in each launch.  x [B*T, rnn], out [B*T, 2*rnn].
 static int bigru_scan(const taco_model* m, hipStream_t st, const Cbhg& c, int B, int T,
                       const int* lengths, const float* init_state, float* out, const CbhgWs& w) {
   const int H = c.rnn;
   if (m->skip_scans) return 0;
-  if (const int upw = oct_upw(m, c, B, T)) return oct_launch(m, st, c, upw, B, T, w.xproj, lengths, init_state, out, nullptr, w.gxbuf, w.gxctl);
-  if (duo_usable(m, c, B, T)) return duo_launch(m, st, c, B, T, w.xproj, lengths, init_state, out, nullptr, w.gxbuf, w.gxctl);
-  if ((m->persist == 8 || m->persist == 9) && m->dx_mode && c.gx_pack[0] && H == GX_H && B <= 64 && T >= 2 && m->cu_count >= 256) {
-    // the 2B chains spread over the whole chip, recurrent weights stationary in registers (taco_bigru_xcd.h): 256 workgroups of 8
-    // waves, one per CU.  persist 9: 512 workgroups of 4 waves, two per CU from independent chains -- measured slower (6088 vs 5224
-    // clocks per step at C2): the phases of a step are chains of dependent instructions, a wave alone on its SIMD is no faster
-    const int NWV = m->persist == 9 ? 4 : 8, rowgroups = gx_ngroups(NWV) / 2;     // persist 8: round 2's default geometry
-    ChipTurn turn(m->device, st);
-    GxArgs a; memset(&a, 0, sizeof a);
-    const size_t* pk = NWV == 8 ? c.gx_pack : c.gx_pack4;
-    a.wpack0 = AP(m, pk[0]); a.wpack1 = AP(m, pk[1]); a.xproj = w.xproj; a.h0 = init_state; a.lengths = lengths; a.out = out;
-    a.xbuf = w.gxbuf; a.ctl = w.gxctl; a.err = m->d_err; a.trace = (m->trace_on && m->d_trace) ? m->d_trace + DX_TRACE_STEPS * DX_TRACE_SLOTS : nullptr; a.B = B; a.T = T; a.force_wt = m->dx_mode == 2 ? 1 : 0;
-    int RG = 1;
-    while (RG * rowgroups < B) RG *= 2;
-    // granules and census words are carved back to back: one fill launch covers both
-    HIPCHK(zero_async(w.gxbuf, (size_t)((char*)w.gxctl - (char*)w.gxbuf) + 256, st));
-    // the kernel needs only a few KB of LDS and < 110 VGPRs: the LDS request is what fixes the number of workgroups a CU takes
-    // (one of 96 KB, or two of 72 KB), so that all of them are resident at once (the census checks placement per XCD, not per CU)
-    const size_t lds = std::max(gx_lds_floats(RG) * sizeof(float), (size_t)(NWV == 8 ? 96 : 72) * 1024);
-    const dim3 grid(gx_ngroups(NWV) * GX_MEMBERS), blk(64 * NWV);
-    if (NWV == 8) {
-      switch (RG) {
-        case 1: hipLaunchKernelGGL((k_bigru_xcd<1, 8>), grid, blk, lds, st, a); break;
-        case 2: hipLaunchKernelGGL((k_bigru_xcd<2, 8>), grid, blk, lds, st, a); break;
-        case 4: hipLaunchKernelGGL((k_bigru_xcd<4, 8>), grid, blk, lds, st, a); break;
-        default: hipLaunchKernelGGL((k_bigru_xcd<8, 8>), grid, blk, lds, st, a); break;
-      }
-    } else {
-      switch (RG) {
-        case 1: hipLaunchKernelGGL((k_bigru_xcd<1, 4>), grid, blk, lds, st, a); break;
-        case 2: hipLaunchKernelGGL((k_bigru_xcd<2, 4>), grid, blk, lds, st, a); break;
-        default: hipLaunchKernelGGL((k_bigru_xcd<4, 4>), grid, blk, lds, st, a); break;
-      }
-    }
-    HIPCHK(hipGetLastError());
-    return 0;
-  }
-  if ((m->persist == 1 || (m->persist >= 4 && m->persist <= 7)) && H == 256) {
-    // weights resident on the CU, 4 hidden units per thread: k_bigru_resw 3.74 us/step; its predecessor k_bigru_resu (persist 6)
-    // 5.16, one unit per thread (k_bigru_res, persist 3) 5.7, re-streaming everything (k_bigru_rows, persist 2) 7.1
-    BigruSArgs a; memset(&a, 0, sizeof a);
-    a.xproj = w.xproj; a.g2_0 = (const float2*)AP(m, c.res_g2[0]); a.g2_1 = (const float2*)AP(m, c.res_g2[1]);
-    a.c1_0 = AP(m, c.raw_ch[0]); a.c1_1 = AP(m, c.raw_ch[1]); a.h0 = init_state; a.lengths = lengths; a.out = out; a.B = B; a.T = T;
-    auto lds = [&](int UJ, int KL) { const int NQ = 512 / (H / UJ); return ((size_t)3 * H + (size_t)NQ * 3 * H) * sizeof(float) + (size_t)KL * NQ * H * 12; };
-    if (m->persist == 1 || m->persist == 7) {      // wave-local exchanges, a thread's four units adjacent in the (column-permuted) packs
-      a.g2_0 = (const float2*)AP(m, c.res_g2p[0]); a.g2_1 = (const float2*)AP(m, c.res_g2p[1]); a.c1_0 = AP(m, c.res_c1p[0]); a.c1_1 = AP(m, c.res_c1p[1]);
-      hipLaunchKernelGGL((k_bigru_resw<16, 4, 2>), dim3(2 * B), dim3(512), lds(4, 4), st, a);
-    }
-    else if (m->persist == 4) hipLaunchKernelGGL((k_bigru_resu<256, 4, 12, 5, 3, false>), dim3(2 * B), dim3(512), lds(4, 5), st, a);
-    else if (m->persist == 5) hipLaunchKernelGGL((k_bigru_resu<256, 2, 32, 10, 2, false>), dim3(2 * B), dim3(512), lds(2, 10), st, a);
-    else hipLaunchKernelGGL((k_bigru_resu<256, 4, 16, 4, 2, false>), dim3(2 * B), dim3(512), lds(4, 4), st, a);      // persist 6: the predecessor
-    HIPCHK(hipGetLastError());
-    return 0;
-  }
-  if ((m->persist == 1 || m->persist == 3) && (H == 256 || H == 128)) {
-    // weights resident on the CU (registers + LDS), one batch row per workgroup: no re-streaming of the recurrent kernels
+  const ScanPlan sp = scan_plan(m, c, B, T);
+  if (sp.kernel == SCAN_K_OCT) return oct_launch(m, st, c, sp.upw, B, T, w.xproj, lengths, init_state, out, nullptr, w.gxbuf, w.gxctl);
+  if (sp.kernel == SCAN_K_DUO) return duo_launch(m, st, c, sp.rg, B, T, w.xproj, lengths, init_state, out, nullptr, w.gxbuf, w.gxctl);
+  if (sp.kernel == SCAN_K_RESW || sp.kernel == SCAN_K_RES || sp.kernel == SCAN_K_QUAD) {
     BigruSArgs a; memset(&a, 0, sizeof a);
     a.xproj = w.xproj; a.g2_0 = (const float2*)AP(m, c.res_g2[0]); a.g2_1 = (const float2*)AP(m, c.res_g2[1]);
     a.c1_0 = AP(m, c.raw_ch[0]); a.c1_1 = AP(m, c.raw_ch[1]); a.h0 = init_state; a.lengths = lengths; a.out = out; a.B = B; a.T = T;
     const dim3 grid(2 * B);
-    if (H == 256) hipLaunchKernelGGL((k_bigru_res<256, 64, 24, 1, false>), grid, dim3(512), bigru_res_lds(256, 24, 1), st, a);
-    else if (m->persist == 1) hipLaunchKernelGGL(k_bigru_quad<false>, grid, dim3(512), 0, st, a);       // quad-local K split: two barriers per step (persist 3: k_bigru_res)
+    if (sp.kernel == SCAN_K_RESW) {      // wave-local exchanges, a thread's four units adjacent in the (column-permuted) packs
+      a.g2_0 = (const float2*)AP(m, c.res_g2p[0]); a.g2_1 = (const float2*)AP(m, c.res_g2p[1]); a.c1_0 = AP(m, c.res_c1p[0]); a.c1_1 = AP(m, c.res_c1p[1]);
+      const size_t lds = ((size_t)3 * H + (size_t)8 * 3 * H) * sizeof(float) + (size_t)4 * 8 * H * 12;      // state, r*h, u; 8 waves of partial sums; KL = 4 rows per K-slice
+      hipLaunchKernelGGL((k_bigru_resw<16, 4, 2>), grid, dim3(512), lds, st, a);
+    }
+    else if (sp.kernel == SCAN_K_QUAD) hipLaunchKernelGGL(k_bigru_quad<false>, grid, dim3(512), 0, st, a);       // quad-local K split: two barriers per step
+    else if (H == 256) hipLaunchKernelGGL((k_bigru_res<256, 64, 24, 1, false>), grid, dim3(512), bigru_res_lds(256, 24, 1), st, a);
     else hipLaunchKernelGGL((k_bigru_res<128, 32, 0, 1, false>), grid, dim3(512), bigru_res_lds(128, 0, 1), st, a);
     HIPCHK(hipGetLastError());
     return 0;
   }
-  {  // row-parallel persistent kernel: the whole scan in one launch, weights streamed from L2 every step
+  if (sp.kernel == SCAN_K_ROWS) {
     int R = 0; size_t lds = 0;
-    if (m->persist && bigru_rows_cfg(B, H, &R, &lds)) {   // persist == 2: this kernel even where the resident one applies (A/B tests)
-      BigruRArgs a; memset(&a, 0, sizeof a);
-      a.xproj = w.xproj; a.wg0 = AP(m, c.raw_gh[0]); a.wg1 = AP(m, c.raw_gh[1]); a.wc0 = AP(m, c.raw_ch[0]); a.wc1 = AP(m, c.raw_ch[1]);
-      a.h0 = init_state; a.lengths = lengths; a.out = out; a.B = B; a.T = T; a.H = H;
-      const dim3 grid(2 * cdiv(B, R));
-      if (R == 2) hipLaunchKernelGGL((k_bigru_rows<2, false>), grid, dim3(RP_NT), lds, st, a);
-      else hipLaunchKernelGGL((k_bigru_rows<1, false>), grid, dim3(RP_NT), lds, st, a);
-      HIPCHK(hipGetLastError());
-      return 0;
-    }
+    bigru_rows_cfg(B, H, &R, &lds);
+    BigruRArgs a; memset(&a, 0, sizeof a);
+    a.xproj = w.xproj; a.wg0 = AP(m, c.raw_gh[0]); a.wg1 = AP(m, c.raw_gh[1]); a.wc0 = AP(m, c.raw_ch[0]); a.wc1 = AP(m, c.raw_ch[1]);
+    a.h0 = init_state; a.lengths = lengths; a.out = out; a.B = B; a.T = T; a.H = H;
+    const dim3 grid(2 * cdiv(B, R));
+    if (R == 2) hipLaunchKernelGGL((k_bigru_rows<2, false>), grid, dim3(RP_NT), lds, st, a);
+    else hipLaunchKernelGGL((k_bigru_rows<1, false>), grid, dim3(RP_NT), lds, st, a);
+    HIPCHK(hipGetLastError());
+    return 0;
   }
   for (int dir = 0; dir < 2; ++dir)
     hipLaunchKernelGGL(k_copy2d, dim3(cdiv(B * H, 256)), dim3(256), 0, st, init_state ? init_state + dir * H : nullptr,
@@ -2497,10 +2463,7 @@ int taco_model_finalize(taco_model* m) {
   HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_bigru_res<128, 32, 0, 1, false>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
   HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_bigru_res<256, 64, 24, 1, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
   HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_bigru_res<128, 32, 0, 1, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-  HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_bigru_resu<256, 4, 16, 4, 2, false>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
   HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_bigru_resw<16, 4, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-  HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_bigru_resu<256, 4, 12, 5, 3, false>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-  HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_bigru_resu<256, 2, 32, 10, 2, false>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
   HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_bigru_rows<1, false>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
   HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_bigru_rows<2, false>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
   HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_bigru_rows<1, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
@@ -2509,13 +2472,6 @@ int taco_model_finalize(taco_model* m) {
   HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_head_sweep<512>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
   HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_head_sweep<256>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
   HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_pointwise_chain<128>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-  HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_bigru_xcd<1, 8>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-  HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_bigru_xcd<2, 8>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-  HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_bigru_xcd<4, 8>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-  HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_bigru_xcd<8, 8>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-  HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_bigru_xcd<1, 4>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-  HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_bigru_xcd<2, 4>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-  HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_bigru_xcd<4, 4>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
   HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_decoder_xcd<1>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
   HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_decoder_xcd<2>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
   HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_decoder_xcd<4>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
@@ -2651,6 +2607,11 @@ int taco_debug_set_overlap(taco_model* m, int on) {
 
 int taco_debug_set_persistent(taco_model* m, int on) {
   if (!m) return fail(TACO_ERR_ARG, "null model");
+  switch (on) {
+    case SCAN_PER_STEP: case SCAN_AUTO: case SCAN_ROWS: case SCAN_RES: case SCAN_RESW: case SCAN_OCT: case SCAN_DUO: break;
+    default: return fail(TACO_ERR_ARG, "scan mode %d: accepted are 0 (two launches per step), 1 (default: the fastest kernel that fits), 2 (k_bigru_rows), "
+                                       "3 (k_bigru_res), 7 (k_bigru_resw), 10 (k_bigru_oct wherever it fits), 11 (k_bigru_duo, never k_bigru_oct)", on);
+  }
   m->persist = on;
   return 0;
 }
@@ -2699,29 +2660,40 @@ int taco_model_engine_plan(taco_model* m, int B, int T_in, int T_mel, int manual
                           std::string(m->dx_mode == 2 ? "write-through exchanges forced" : "XCD-local exchanges when the census finds 32 workgroups per XCD") + ")";
     else s += "decoder loop: one launch per stage -- " + why;
   }
+  // the two scans, from the plan bigru_scan itself follows
+  auto scan_why = [&](const Cbhg& c, const ScanPlan& sp, const char* width_name, int rows) -> std::string {
+    switch (sp.why_not_whole_chip) {
+      case SCAN_WHY_MODE: return "taco_debug_set_persistent(" + std::to_string(m->persist) + "): " + scan_kernel_name(sp.kernel);
+      case SCAN_WHY_WIDTH: return std::string(width_name) + " " + std::to_string(c.rnn) + " != 256";
+      case SCAN_WHY_FRAMES: return "fewer than 2 frames";
+      default: return why_common(rows);
+    }
+  };
   {  // post-net scan
     const Cbhg& c = m->post;
-    std::string why = why_common(B);
-    if (why.empty() && m->persist != 1 && m->persist != 8 && m->persist != 9 && m->persist != 10 && m->persist != 11) why = "taco_debug_set_persistent(" + std::to_string(m->persist) + ")";
-    if (why.empty() && (c.rnn != GX_H || !c.gd_pack)) why = "post_rnn_size " + std::to_string(c.rnn) + " != 256";
-    if (why.empty() && T_mel < 2) why = "fewer than 2 frames";
-    int RG = 1;
-    while (RG * DX_NGROUP < B) RG *= 2;
-    const int upw = why.empty() ? oct_upw(m, c, B, T_mel) : 0;
-    if (upw) s += "; post-net scan: persistent k_bigru_oct<" + std::to_string(upw) + "> (one row per cluster of " + std::to_string(DX_GROUP / upw) + " CUs)";
-    else if (why.empty()) s += "; post-net scan: persistent " + std::string(m->persist == 8 || m->persist == 9 ? "k_bigru_xcd<" : "k_bigru_duo<") + std::to_string(RG) + ">";
-    else if (c.rnn == 128 && m->persist == 1) s += "; post-net scan: k_bigru_quad (post_rnn_size 128: a row and direction per workgroup, its weights resident, no exchange between workgroups)";
-    else s += "; post-net scan: resident per-row kernels -- " + why;
+    const ScanPlan sp = scan_plan(m, c, B, T_mel, m->tp != nullptr);
+    if (sp.kernel == SCAN_K_OCT) s += "; post-net scan: persistent k_bigru_oct<" + std::to_string(sp.upw) + "> (one row per cluster of " + std::to_string(DX_GROUP / sp.upw) + " CUs)";
+    else if (sp.kernel == SCAN_K_DUO) s += "; post-net scan: persistent k_bigru_duo<" + std::to_string(sp.rg) + ">";
+    else if (sp.kernel == SCAN_K_QUAD) s += "; post-net scan: k_bigru_quad (post_rnn_size 128: a row and direction per workgroup, its weights resident, no exchange between workgroups)";
+    else s += "; post-net scan: resident per-row kernels -- " + scan_why(c, sp, "post_rnn_size", B);
   }
-  s += m->enc.rnn == 128 && m->persist == 1 ? "; encoder scan: k_bigru_quad (a row and direction per workgroup, K split inside a quad of lanes); feed-forward: "
-                                            : "; encoder scan: k_bigru_res (rows resident per workgroup); feed-forward: ";
+  {  // encoder scan
+    const Cbhg& c = m->enc;
+    const ScanPlan sp = scan_plan(m, c, B, T_in, m->tp != nullptr);
+    if (sp.kernel == SCAN_K_OCT) s += "; encoder scan: persistent k_bigru_oct<" + std::to_string(sp.upw) + ">";
+    else if (sp.kernel == SCAN_K_DUO) s += "; encoder scan: persistent k_bigru_duo<" + std::to_string(sp.rg) + ">";
+    else if (sp.kernel == SCAN_K_QUAD) s += "; encoder scan: k_bigru_quad (a row and direction per workgroup, K split inside a quad of lanes)";
+    else if (sp.kernel == SCAN_K_RES || sp.kernel == SCAN_K_RESW) s += std::string("; encoder scan: ") + scan_kernel_name(sp.kernel) + " (rows resident per workgroup)";
+    else s += std::string("; encoder scan: ") + scan_kernel_name(sp.kernel);
+    s += "; feed-forward: ";
+  }
   s += m->bf3 ? "split-bf16 MFMA (k_gemm_bf3 / k_pointwise_chain)" : "exact-fp32 MFMA (k_gemm)";
   if (!m->tp) s += prenet_chain_fits(m) ? "; encoder prenet: one k_pointwise_chain launch (embedding rows gathered, both layers; the forward's zero fills ride in it)"
                                         : "; encoder prenet: one GEMM launch per layer";
   else {        // the training step's backward scans (taco_train.h: cbhg_backward)
     const Cbhg& c = m->post;
-    s += std::string("; backward scans: post-net ") + (duo_usable(m, c, B, T_mel) && c.gb_pack ? (oct_bwd_usable(m, c, B, T_mel) ? "k_bigru_oct_bwd (one row per cluster of 8 CUs)" : "k_bigru_duo_bwd")
-                                                                                                : "k_bigru_rows_bwd") +
+    const ScanBwd bwd = scan_plan(m, c, B, T_mel).bwd;
+    s += std::string("; backward scans: post-net ") + (bwd == SCAN_BWD_OCT ? "k_bigru_oct_bwd (one row per cluster of 8 CUs)" : bwd == SCAN_BWD_DUO ? "k_bigru_duo_bwd" : "k_bigru_rows_bwd") +
          ", encoder " + (m->enc.rnn == 128 ? "k_bigru_resb (recurrent kernels in registers)" : "k_bigru_rows_bwd");
   }
   snprintf(out, (size_t)out_len, "%s", s.c_str());

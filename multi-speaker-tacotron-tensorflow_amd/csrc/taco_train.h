@@ -663,21 +663,22 @@ static int cbhg_forward_train(const TrainCtx& x, const Cbhg& c, const CbhgT& ct,
   { GemmCall xp; xp.x = w.hx[c.depth]; xp.ldx = H; xp.M = M; xp.T = T; xp.out = w.xproj; xp.ldo = 6 * H; xp.rev_len = lengths; xp.rev_col0 = 3 * H;
     TRY(run_gemm(m, st, &c.xproj, 1, false, xp)); }
   if (lengths) HIPCHK(zero_async(w.gsave, (size_t)M * 6 * H * sizeof(float), st));      // (without lengths -- the post-net -- every step of every row is active and written)
-  if (const int upw = oct_upw(m, c, B, T))     // the whole-chip scans of inference with the gate tape (k_bigru_oct<UPW, true> / k_bigru_duo<RG, true>)
-    return oct_launch(m, st, c, upw, B, T, w.xproj, lengths, init_state, w.out, w.gsave, w.gxbuf, w.gxctl);
-  if (duo_usable(m, c, B, T))
-    return duo_launch(m, st, c, B, T, w.xproj, lengths, init_state, w.out, w.gsave, w.gxbuf, w.gxctl);
-  if (H == 256 || H == 128) {     // recurrent weights resident on the CU (k_bigru_res; H = 128: k_bigru_quad, as inference runs it), gates saved for the backward scan
+  const ScanPlan sp = scan_plan(m, c, B, T, true);
+  if (sp.kernel == SCAN_K_OCT)     // the whole-chip scans of inference with the gate tape (k_bigru_oct<UPW, true> / k_bigru_duo<RG, true>)
+    return oct_launch(m, st, c, sp.upw, B, T, w.xproj, lengths, init_state, w.out, w.gsave, w.gxbuf, w.gxctl);
+  if (sp.kernel == SCAN_K_DUO)
+    return duo_launch(m, st, c, sp.rg, B, T, w.xproj, lengths, init_state, w.out, w.gsave, w.gxbuf, w.gxctl);
+  if (sp.kernel == SCAN_K_RES || sp.kernel == SCAN_K_QUAD) {     // recurrent weights resident on the CU (k_bigru_res; H = 128: k_bigru_quad, as inference runs it), gates saved for the backward scan
     BigruSArgs a; memset(&a, 0, sizeof a);
     a.xproj = w.xproj; a.g2_0 = (const float2*)AP(m, c.res_g2[0]); a.g2_1 = (const float2*)AP(m, c.res_g2[1]);
     a.c1_0 = AP(m, c.raw_ch[0]); a.c1_1 = AP(m, c.raw_ch[1]); a.lengths = lengths; a.out = w.out; a.gsave = w.gsave; a.B = B; a.T = T;
     a.h0 = init_state;
     if (H == 256) hipLaunchKernelGGL((k_bigru_res<256, 64, 24, 1, true>), dim3(2 * B), dim3(512), bigru_res_lds(256, 24, 1), st, a);
-    else if (m->persist == 1 && x.t->resident_bwd_scan) hipLaunchKernelGGL(k_bigru_quad<true>, dim3(2 * B), dim3(512), 0, st, a);      // (the A/B engine keeps k_bigru_res)
+    else if (sp.kernel == SCAN_K_QUAD && x.t->resident_bwd_scan) hipLaunchKernelGGL(k_bigru_quad<true>, dim3(2 * B), dim3(512), 0, st, a);      // (the A/B engine keeps k_bigru_res)
     else hipLaunchKernelGGL((k_bigru_res<128, 32, 0, 1, true>), dim3(2 * B), dim3(512), bigru_res_lds(128, 0, 1), st, a);
   } else {
     int R = 0; size_t lds = 0;
-    if (!bigru_rows_cfg(B, H, &R, &lds)) return fail(TACO_ERR_UNSUPPORTED, "rnn size %d does not fit the row-parallel BiGRU kernel", H);
+    if (sp.kernel != SCAN_K_ROWS || !bigru_rows_cfg(B, H, &R, &lds)) return fail(TACO_ERR_UNSUPPORTED, "rnn size %d does not fit the row-parallel BiGRU kernel", H);
     BigruRArgs a; memset(&a, 0, sizeof a);
     a.xproj = w.xproj; a.wg0 = AP(m, c.raw_gh[0]); a.wg1 = AP(m, c.raw_gh[1]); a.wc0 = AP(m, c.raw_ch[0]); a.wc1 = AP(m, c.raw_ch[1]);
     a.lengths = lengths; a.out = w.out; a.gsave = w.gsave; a.B = B; a.T = T; a.H = H; a.h0 = init_state;
@@ -742,7 +743,8 @@ static int cbhg_backward(const TrainCtx& x, const Cbhg& c, const CbhgT& ct, cons
   const int M = B * T, KC = c.K * c.C, H = c.rnn, I = c.rnn;
   // ---- BiGRU ----
   // (the backward scans write the steps inside a row's length only; k_bigru_duo_bwd without lengths -- the post-net -- writes every element)
-  const bool duo_bwd = duo_usable(m, c, B, T) && c.gb_pack;
+  const ScanPlan sp = scan_plan(m, c, B, T, true);
+  const bool duo_bwd = sp.bwd != SCAN_BWD_ROWS;       // a whole-chip backward scan (k_bigru_duo_bwd / k_bigru_oct_bwd)
   ZeroBatch zb(st);
   if (!(duo_bwd && !lengths)) {
     HIPCHK(zb.add(w.dg, (size_t)M * 6 * H * sizeof(float)));
@@ -750,26 +752,12 @@ static int cbhg_backward(const TrainCtx& x, const Cbhg& c, const CbhgT& ct, cons
   }
   if (duo_bwd) HIPCHK(zb.add(w.gxbuf, (size_t)((char*)w.gxctl - (char*)w.gxbuf) + 256));
   HIPCHK(zb.run());
-  if (duo_bwd && oct_bwd_usable(m, c, B, T)) {
+  if (sp.bwd == SCAN_BWD_OCT) {
     // one row per cluster of 8 CUs, as the forward scan of these shapes (k_bigru_oct_bwd)
     TRY(oct_bwd_launch(m, st, c, B, T, dout, w.out, w.gsave, h0, lengths, w.dg, w.rh, dh0, w.gxbuf, w.gxctl));
   } else if (duo_bwd) {
     // both directions of RG rows per group of 32 CUs, the directions software-pipelined against each other (k_bigru_duo_bwd)
-    ChipTurn turn(m->device, st);
-    GbArgs a; memset(&a, 0, sizeof a);
-    a.wpack = AP(m, c.gb_pack); a.dout = dout; a.out = w.out; a.gsave = w.gsave; a.h0 = h0; a.lengths = lengths; a.dg = w.dg; a.rh = w.rh; a.dh0 = dh0;
-    a.xbuf = w.gxbuf; a.ctl = w.gxctl; a.err = m->d_err; a.B = B; a.T = T; a.force_wt = m->dx_mode == 2 ? 1 : 0;
-    int RG = 1;
-    while (RG * DX_NGROUP < B) RG *= 2;
-    const size_t lds = std::max(gb_lds_floats(RG) * sizeof(float), (size_t)96 * 1024);      // one workgroup per CU
-    const dim3 grid(DX_NGROUP * GD_MEMBERS), blk(512);
-    switch (RG) {
-      case 1: hipLaunchKernelGGL((k_bigru_duo_bwd<1>), grid, blk, lds, st, a); break;
-      case 2: hipLaunchKernelGGL((k_bigru_duo_bwd<2>), grid, blk, lds, st, a); break;
-      case 4: hipLaunchKernelGGL((k_bigru_duo_bwd<4>), grid, blk, lds, st, a); break;
-      default: hipLaunchKernelGGL((k_bigru_duo_bwd<8>), grid, blk, lds, st, a); break;
-    }
-    HIPCHK(hipGetLastError());
+    TRY(duo_bwd_launch(m, st, c, sp.rg, B, T, dout, w.out, w.gsave, h0, lengths, w.dg, w.rh, dh0, w.gxbuf, w.gxctl));
   } else if (H == 128 && x.t->resident_bwd_scan) {
     // recurrent kernels resident in registers, one workgroup per (direction, row) (k_bigru_resb): the encoder at the reference width
     BigruQArgs a; memset(&a, 0, sizeof a);

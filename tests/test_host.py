@@ -172,7 +172,7 @@ def test_no_persistent_kernel_uses_scratch():
     spec.loader.exec_module(mod)
     kernels, rows, bad = mod.check(path)
     names = [n for n, _ in kernels]
-    assert any("k_bigru_xcdILi4ELi8" in n for n in names) and any("k_decoder_xcdILi4" in n for n in names)
+    assert any("k_bigru_octILi4" in n for n in names) and any("k_bigru_duoILi8" in n for n in names) and any("k_decoder_xcdILi4" in n for n in names)
     assert not bad, bad
 
 

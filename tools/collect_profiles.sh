@@ -34,10 +34,10 @@ timeout 300 python tools/bench_train.py --exact-gemm 1 > $out/train_step_exact.j
 timeout 300 python tools/bench_train.py --bptt 0 > $out/train_step_bptt_per_stage.json 2>> $out/train.err
 timeout 300 python tools/trace_bptt.py 2>&1 | grep -v amdgpu.ids > $out/bptt_timeline.txt
 timeout 300 python tools/bench_audio.py > $out/griffin_lim.json 2> $out/audio.err
-# round 3: scan timelines (k_bigru_duo vs k_bigru_xcd), manual / simple decoder modes, feed-forward-under-the-scan experiment, training kernel statistics
+# round 3: scan timelines (k_bigru_duo), manual / simple decoder modes, feed-forward-under-the-scan experiment, training kernel statistics
 rm -f $out/scan_timeline.json
-# round 5: k_bigru_oct (persist 1 from 9 to 32 rows; 10: wherever it fits) vs k_bigru_duo (11) vs k_bigru_xcd (8); --json feeds bench.py's latency_floor_ms
-{ for sh in "32 512 1" "16 512 1" "64 512 1" "8 4000 1" "32 512 11" "16 512 11" "8 4000 10" "32 512 8"; do python tools/trace_bigru.py $sh --json $out/scan_timeline.json; done; } 2>&1 | grep -v "amdgpu.ids\|RuntimeWarning\|warnings.warn" > $out/scan_timeline.txt
+# round 5: k_bigru_oct (persist 1 from 9 to 32 rows; 10: wherever it fits) vs k_bigru_duo (11); --json feeds bench.py's latency_floor_ms
+{ for sh in "32 512 1" "16 512 1" "64 512 1" "8 4000 1" "32 512 11" "16 512 11" "8 4000 10"; do python tools/trace_bigru.py $sh --json $out/scan_timeline.json; done; } 2>&1 | grep -v "amdgpu.ids\|RuntimeWarning\|warnings.warn" > $out/scan_timeline.txt
 timeout 300 python tools/time_manual.py 2>&1 | grep -v amdgpu.ids > $out/time_manual.txt
 timeout 300 python tools/overlap_scan_ff.py 2>&1 | grep -v amdgpu.ids > $out/overlap_scan_ff.txt
 timeout 300 python tools/time_stages.py C2 32 64 2>&1 | grep -v amdgpu.ids > $out/time_stages.txt

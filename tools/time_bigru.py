@@ -16,7 +16,7 @@ def timeit(fn, n=10):
     e1.record(); torch.cuda.synchronize()
     return e0.elapsed_time(e1) / n * 1e3
 import os
-L.taco_debug_set_persistent(m._handle, int(os.environ.get("PERSIST", "1")))
+taco_amd._lib.check(L.taco_debug_set_persistent(m._handle, int(os.environ.get("PERSIST", "1"))))      # 0, 1, 2, 3, 7, 10, 11: include/taco_debug.h
 for scope, I in (("post_cbhg", 256), ("encoder_cbhg", 128)):
     for B in (32, 8):
         prev = None

@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """Phase timeline of the whole-chip post-net scans (row / group 0, member 0, thread 0 shader-clock stamps, steps 8-15):
 python tools/trace_bigru.py [B] [T] [persist] [--json out.json]   (--json appends one record to a JSON list: bench.py's latency_floor_ms reads it)"""
-import os, sys, json, ctypes as C
+import os, re, sys, json, ctypes as C
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np, torch, taco_amd
 argv = list(sys.argv[1:])
@@ -10,12 +10,13 @@ if "--json" in argv:
     i = argv.index("--json"); jpath = argv[i + 1]; del argv[i:i + 2]
 B = int(argv[0]) if len(argv) > 0 else 32
 T = int(argv[1]) if len(argv) > 1 else 512
-# 1: the default (k_bigru_oct from 9 to 32 rows, else k_bigru_duo); 10: k_bigru_oct wherever it fits; 11: k_bigru_duo; 8: k_bigru_xcd, one 8-wave workgroup per CU; 9: two 4-wave workgroups per CU
+# 1: the default (k_bigru_oct from 9 to 32 rows, else k_bigru_duo); 10: k_bigru_oct wherever it fits; 11: k_bigru_duo (the other modes of
+# taco_debug_set_persistent select per-row kernels, which are timed but carry no stamps)
 PERSIST = int(argv[2]) if len(argv) > 2 else 1
 hp = taco_amd.hparams.copy(max_iters=128)
 m = taco_amd.create_model(hp); m.initialize(None, None, 1, None)
 L = m._lib
-L.taco_debug_set_persistent(m._handle, PERSIST)
+taco_amd._lib.check(L.taco_debug_set_persistent(m._handle, PERSIST))
 st = lambda: C.c_void_p(torch.cuda.current_stream().cuda_stream)
 P = lambda t: C.c_void_p(t.data_ptr() if t is not None else None)
 x = torch.randn(B, T, 256, device="cuda") * 0.3; out = torch.empty(B, T, 512, device="cuda")
@@ -42,18 +43,17 @@ m.decoder_trace(True)
 fn(); torch.cuda.synchronize()
 tr = m.decoder_trace(True, read=True, scan=True); m.decoder_trace(False)
 m.check_device_errors()
-if PERSIST in (1, 10, 11):
-    names = ["gates F (+publish)", "collect h'(B) + barrier", "request + gates B (+publish)", "collect r*h(F) + barrier", "request + cand F (+publish, store)",
-             "collect r*h(B) + barrier", "request + cand B (+publish, store)", "collect h'(F) + barrier"]
-    d = np.diff(tr[:, :9], axis=1).astype(np.float64)
-else:
-    names = ["gates pass+reduce", "gates epilogue+publish", "poll r*h", "barrier", "cand pass+reduce", "cand epilogue+publish+store", "poll h'", "x-part fetch issue", "barrier"]
-    d = np.diff(tr[:, :10], axis=1).astype(np.float64)
+kernel = re.search(r"k_bigru_\w+(<\d+>)?|two launches per step", m.engine_plan(B, 128, T).split("post-net scan: ")[1].split(";")[0]).group(0)     # what the library itself picks
+if not kernel.startswith(("k_bigru_oct", "k_bigru_duo")):
+    print("B=%d T=%d persist %d kernel %s: %.1f us total (input projection %.1f + scan %.1f = %.3f us per step); only the whole-chip scans are stamped"
+          % (B, T, PERSIST, kernel, us, us_gemm, us - us_gemm, (us - us_gemm) / T))
+    sys.exit(0)
+names = ["gates F (+publish)", "collect h'(B) + barrier", "request + gates B (+publish)", "collect r*h(F) + barrier", "request + cand F (+publish, store)",
+         "collect r*h(B) + barrier", "request + cand B (+publish, store)", "collect h'(F) + barrier"]
+d = np.diff(tr[:, :9], axis=1).astype(np.float64)
 step = float(np.median((tr[1:, 0] - tr[:-1, 0]).astype(np.float64)))
 scan_us = us - us_gemm
 cpu = step * T / scan_us if scan_us > 0 else 0.0
-oct_ = PERSIST in (1, 10) and B <= 32 and (B > 8 or PERSIST == 10)
-kernel = ("k_bigru_oct<%d>" % (4 if B > 16 else 2 if B > 8 else 1)) if oct_ else ("k_bigru_duo<%d>" % max(1, 1 << int(np.ceil(np.log2(max(1, (B + 7) // 8)))))) if PERSIST in (1, 10, 11) else "k_bigru_xcd"
 print("B=%d T=%d persist %d kernel %s: %.1f us total (input projection %.1f + scan %.1f = %.3f us per step), step = %.0f clocks, %.0f clocks per us"
       % (B, T, PERSIST, kernel, us, us_gemm, scan_us, scan_us / T, step, cpu))
 med = np.median(d[1:], axis=0)
