@@ -289,8 +289,10 @@ int taco_train_forward_backward(taco_train* t, void* hip_stream, float* d_params
 int taco_model_device_errors(taco_model* m, int* out);
 /* Which engine a forward of this shape WOULD run on -- and, when it is not the persistent whole-chip one, why not (widths, rows, LDS,
  * compute units of the device, debug switches).  Nothing is launched.  `out` receives a NUL-terminated line (out_len >= 64; truncated
- * if shorter than the text).  The run-time facts (exchange protocol the census chose) are in taco_debug_decoder_info afterwards. */
-int taco_model_engine_plan(taco_model* m, int B, int T_in, int T_mel, int manual, char* out, int out_len);
+ * if shorter than the text).  The run-time facts (exchange protocol the census chose) are in taco_debug_decoder_info afterwards.
+ * flags: bit 0 = manual alignments; for a taco_decoder_forward call, bit 1 = teacher frames, bit 2 = the per-step state dump (which keeps
+ * up to 64 rows in one pass).  For a training shadow model (taco_train_model) the line describes a training step, backward loops included. */
+int taco_model_engine_plan(taco_model* m, int B, int T_in, int T_mel, int flags, char* out, int out_len);
 /* Batch-position bit-invariance for serving setups that need it (a request's outputs must not depend on which rows it was batched or
  * sharded with).  on = 1: every row tile of the fused point-wise kernel walks a layer's contraction from step 0, so a row's fp32
  * accumulation order is the same wherever the row lands: outputs are bitwise equal under batch permutation / re-sharding at any

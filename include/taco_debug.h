@@ -55,7 +55,9 @@ int taco_debug_set_overlap(taco_model* m, int on);
  * cells, prenet 256/128, two decoder GRUs), model_type single or deepvoice, no manual alignments, no teacher forcing, the
  * attention memory slice of a member fits its LDS; every other call uses the launch-per-stage loop.  mode 0: always launch per
  * stage.  mode 2: persistent with write-through (placement-independent) exchanges even when the census finds one group per XCD.
- * rows_per_group: 0 = smallest of 1/2/4/8 that covers the batch with 8 groups; a larger value packs the batch onto fewer XCDs. */
+ * rows_per_group: 0 = smallest of 1/2/4/8 that covers the batch with 8 groups; 1, 2, 4 or 8 packs the batch onto fewer XCDs (any other
+ * value: TACO_ERR_ARG, nothing changes).  A value that does not fit a call -- fewer than B rows on 8 groups, or below 4 outside the
+ * reference widths -- is ignored for that call.  Which kernel a call then gets: decoder_plan (csrc/taco_lib.hip), told by taco_model_engine_plan. */
 int taco_debug_set_decoder_persist(taco_model* m, int mode, int rows_per_group);
 /* test hook: set the sticky device error word (as a persistent kernel does when its bounded spin expires) to `value` */
 int taco_debug_raise_device_error(taco_model* m, int value);

@@ -1173,6 +1173,9 @@ static size_t bigru_res_lds(int H, int KL, int R) {
   return ((size_t)3 * R * H + (size_t)NQ * R * 3 * H) * sizeof(float) + (size_t)KL * NQ * H * 3 * sizeof(float);
 }
 
+// The whole-chip persistent kernels (BiGRU scans, decoder loop and its backward loop): one workgroup per CU, all resident at once -- only on a whole MI355X (a partition
+// of it -- CPX / DPX modes -- or a smaller part would leave workgroups waiting for CUs held by workgroups that wait for them); at most 8 rows on each of the 8 groups
+static constexpr int CHIP_CUS = DX_NGROUP * DX_GROUP, CHIP_ROWS = 8 * DX_NGROUP;
 // ---- which BiGRU scan runs ----
 // taco_debug_set_persistent(m, mode): SCAN_AUTO is the default; the others force one engine where it fits (A/B tests, tools/).
 enum ScanMode { SCAN_PER_STEP = 0, SCAN_AUTO = 1, SCAN_ROWS = 2, SCAN_RES = 3, SCAN_RESW = 7, SCAN_OCT = 10, SCAN_DUO = 11 };
@@ -1194,10 +1197,10 @@ static ScanPlan scan_plan(const taco_model* m, const Cbhg& c, int B, int T, bool
   ScanPlan p = {SCAN_K_STEPS, 0, 1, SCAN_BWD_ROWS, SCAN_WHY_NONE};
   while (p.rg * DX_NGROUP < B) p.rg *= 2;
   // the whole-chip kernels (taco_bigru_xcd.h): H = 256, an unpartitioned MI355X, the decoder engine not switched off
-  const bool chip = m->dx_mode && H == GX_H && T >= 2 && m->cu_count >= 256;
+  const bool chip = m->dx_mode && H == GX_H && T >= 2 && m->cu_count >= CHIP_CUS;
   if (!m->dx_mode) p.why_not_whole_chip = SCAN_WHY_ENGINE_OFF;
-  else if (m->cu_count < 256) p.why_not_whole_chip = SCAN_WHY_CUS;
-  else if (B > 8 * DX_NGROUP) p.why_not_whole_chip = SCAN_WHY_ROWS;
+  else if (m->cu_count < CHIP_CUS) p.why_not_whole_chip = SCAN_WHY_CUS;
+  else if (B > CHIP_ROWS) p.why_not_whole_chip = SCAN_WHY_ROWS;
   else if (mode != SCAN_AUTO && mode != SCAN_OCT && mode != SCAN_DUO) p.why_not_whole_chip = SCAN_WHY_MODE;
   else if (H != GX_H || !c.gd_pack) p.why_not_whole_chip = SCAN_WHY_WIDTH;
   else if (T < 2) p.why_not_whole_chip = SCAN_WHY_FRAMES;
@@ -1294,7 +1297,7 @@ static int oct_bwd_launch(const taco_model* m, hipStream_t st, const Cbhg& c, in
   a.wpack = AP(m, c.gob_pack); a.dout = dout; a.out = out; a.gsave = gsave; a.h0 = h0; a.lengths = lengths; a.dg = dg; a.rh = rh; a.dh0 = dh0;
   a.xbuf = gxbuf; a.ctl = gxctl; a.err = m->d_err; a.B = B; a.T = T; a.force_wt = m->dx_mode == 2 ? 1 : 0;
   const size_t lds = std::max(gob_lds_floats() * sizeof(float), (size_t)96 * 1024);      // one workgroup per CU
-  hipLaunchKernelGGL(k_bigru_oct_bwd, dim3(DX_NGROUP * DX_GROUP), dim3(512), lds, st, a);
+  hipLaunchKernelGGL(k_bigru_oct_bwd, dim3(CHIP_CUS), dim3(512), lds, st, a);
   HIPCHK(hipGetLastError());
   return 0;
 }
@@ -1309,7 +1312,7 @@ static int oct_launch(const taco_model* m, hipStream_t st, const Cbhg& c, int UP
   a.B = B; a.T = T; a.force_wt = m->dx_mode == 2 ? 1 : 0;
   HIPCHK(clear_polled(gxbuf, (size_t)((char*)gxctl - (char*)gxbuf) + 256, st));
   const size_t lds = std::max(go_lds_floats(UPW) * sizeof(float), (size_t)96 * 1024);      // one workgroup per CU
-  const dim3 grid(DX_NGROUP * DX_GROUP), blk(512);
+  const dim3 grid(CHIP_CUS), blk(512);
   if (a.trace) oct_launch_upw<false, true>(UPW, grid, blk, lds, st, a);        // the stamped instantiations (tools/trace_bigru.py): inference only
   else if (gsave) oct_launch_upw<true, false>(UPW, grid, blk, lds, st, a);
   else oct_launch_upw<false, false>(UPW, grid, blk, lds, st, a);
@@ -1693,15 +1696,6 @@ static int encoder_forward(const taco_model* m, hipStream_t st, const int* ids, 
                       is_deepvoice(m) ? w.spk.vec[1] : nullptr, enc_out, w.cb);
 }
 
-static int dx_rows_per_group(const taco_model* m, int B) {
-  // the other presets (attention_size 128 / 512, three prenet layers) are instantiated for 4 and 8 rows per group only: smaller batches run
-  // as padded groups of 4 (a step costs the same there: its time is the chain of exchanges, not the rows)
-  const int lo = dx_reference_widths(m) ? 1 : 4;
-  if (m->dx_rows == 1 || m->dx_rows == 2 || m->dx_rows == 4 || m->dx_rows == 8) { if (m->dx_rows * DX_NGROUP >= B && m->dx_rows >= lo) return m->dx_rows; }
-  int RG = lo;
-  while (RG < 8 && RG * DX_NGROUP < B) RG *= 2;
-  return RG;
-}
 // ---- decoder (tacotron.py:120-214) ----
 struct DecWs {
   float *keys, *zero, *ctx, *pz[4], *h_att, *rh, *u, *xc, *q, *align, *o[5], *hd[4], *Y, *escr;
@@ -1736,37 +1730,65 @@ static void carve_dec(Carver& cv, const taco_model* m, int B, int T_in, int n, D
     w.rowbias = cv.f(is_simple(m) ? (size_t)B * DXRB_N * DX_W : 1);
   }
 }
-// persistent decoder: usable for this call?  (reference widths, no teacher forcing, the member's LDS fits)
-static bool dx_usable(const taco_model* m, int B, int T_in, const float* manual, const float* teacher) {
-  // 256 workgroups, one per CU, all resident at once: only on a whole MI355X (a partition of it -- CPX / DPX modes -- or a smaller
-  // part would leave workgroups waiting for CUs held by workgroups that wait for them)
-  (void)manual;   // manual alignments are a mode of the persistent kernel (the score phases are skipped)
-  // teacher forcing needs the raw prenet rows in the registers where inference keeps the frame-projection composite: only the
-  // training shadow model's pack has them (taco_model_finalize)
-  if (!m->dx_mode || !m->dx_pack || B > 8 * DX_NGROUP || m->cu_count < DX_NGROUP * DX_GROUP) return false;
-  // teacher forcing: the TAPE instantiation -- the training shadow model (pack in teacher form), or an inference model at the reference widths
-  // (raw frame rows of prenet layer 1 kept beside the composite pack), with or without manual alignments
-  if (teacher && !(m->tp || (m->dx_p1o_raw && m->hp.num_mels <= DX_P2))) return false;
-  const int RG = dx_rows_per_group(m, B);
-  if (m->hp.attention_size == 512 && RG > 4) return false;        // 128 score channels per member: no instantiation (query registers, the q / v slots)
-  return dx_lds_floats(RG, T_in, m->tp != nullptr || teacher != nullptr, m->hp.attention_size) * sizeof(float) <= 160 * 1024;
+// ---- which engine runs the decoder loop ----
+static constexpr size_t DX_LDS_BUDGET = 160 * 1024;      // dynamic LDS a member of k_decoder_xcd / k_decoder_bwd_xcd may request
+enum DecUse { DEC_INFER, DEC_TEACHER, DEC_TRAIN_FWD, DEC_TRAIN_BWD };      // TEACHER: taco_decoder_forward with teacher frames; TRAIN_*: taco_train.h
+enum DecWhyNot { DEC_WHY_NONE, DEC_WHY_ENGINE_OFF, DEC_WHY_CUS, DEC_WHY_ROWS, DEC_WHY_WIDTHS, DEC_WHY_TEACHER_ROWS, DEC_WHY_NO_INSTANTIATION, DEC_WHY_LDS, DEC_WHY_TAPE_LAYOUT };
+static_assert((int)DEC_WHY_ENGINE_OFF == SCAN_WHY_ENGINE_OFF && (int)DEC_WHY_CUS == SCAN_WHY_CUS && (int)DEC_WHY_ROWS == SCAN_WHY_ROWS, "taco_model_engine_plan words the shared reasons once");
+struct DecPlan {
+  bool persistent;          // the whole loop as ONE launch: k_decoder_xcd (DEC_TRAIN_BWD: k_decoder_bwd_xcd); else one launch per stage
+  int rg, aw, pd;           // the instantiation: rows per group of 32 CUs, attention_size, prenet layers
+  bool tape;                // the TAPE instantiation: the training forward, or teacher frames on an inference model (manual alignments: a launch argument)
+  size_t lds_bytes;         // what the launch requests
+  DecWhyNot why;            // first reason against the persistent kernel (NONE: it runs)
+};
+// The one place that decides.  Pure: launches nothing, touches no device state.  n: decoder steps (the training tape's extent; unused otherwise)
+static DecPlan decoder_plan(const taco_model* m, int B, int T_in, int n, DecUse use) {
+  const taco_hparams& hp = m->hp;
+  const bool bwd = use == DEC_TRAIN_BWD, train = bwd || use == DEC_TRAIN_FWD;
+  DecPlan p = {false, 0, hp.attention_size, dx_prenet_depth(m), use != DEC_INFER, 0, DEC_WHY_NONE};
+  // rows per group: the smallest of 1 / 2 / 4 / 8 that covers the batch with 8 groups.  The other presets (attention_size 128 / 512, three prenet layers) are instantiated
+  // for 4 and 8 only: smaller batches run as padded groups of 4 (a step costs the same there: its time is the chain of exchanges, not the rows)
+  const int lo = dx_reference_widths(m) ? 1 : 4;
+  for (p.rg = lo; p.rg < 8 && p.rg * DX_NGROUP < B; p.rg *= 2) {}
+  if (m->dx_rows >= lo && m->dx_rows * DX_NGROUP >= B) p.rg = m->dx_rows;      // taco_debug_set_decoder_persist: an override that does not fit this call is ignored
+  p.lds_bytes = (bwd ? db_lds_floats(p.rg, T_in) : dx_lds_floats(p.rg, T_in, p.tape, p.aw)) * sizeof(float);
+  if (!m->dx_mode) p.why = DEC_WHY_ENGINE_OFF;
+  else if (m->cu_count < CHIP_CUS) p.why = DEC_WHY_CUS;
+  else if (B > CHIP_ROWS) p.why = DEC_WHY_ROWS;
+  else if (!(bwd ? m->dbx_pack : m->dx_pack)) p.why = DEC_WHY_WIDTHS;      // the packs exist where dx_widths_ok(m) (taco_model_finalize; dbx_pack: training shadow model)
+  // teacher frames need the raw prenet rows where inference keeps the frame-projection composite: the shadow model's pack has them, an inference model beside its pack (dx_build_pack)
+  else if (use == DEC_TEACHER && !m->tp && !(m->dx_p1o_raw && hp.num_mels <= DX_P2)) p.why = DEC_WHY_TEACHER_ROWS;
+  else if (p.aw == 512 && p.rg > 4) p.why = DEC_WHY_NO_INSTANTIATION;      // 128 score channels per member: query registers, the q / v slots
+  else if (p.lds_bytes > DX_LDS_BUDGET) p.why = DEC_WHY_LDS;
+  // the tape (carve_dec_tape): the step's own frame in a 128-wide slot (forward only), 32-bit element offsets over the DXT_N slots of [B, n, 256]
+  else if (train && ((!bwd && hp.num_mels > DX_P2) || (size_t)DXT_N * B * n * DX_W >= (1u << 31))) p.why = DEC_WHY_TAPE_LAYOUT;
+  p.persistent = p.why == DEC_WHY_NONE;
+  return p;
 }
 template <int RG, bool TAPE, int AW = DX_W, int PD = 2>
 static int dx_launch_rg(hipStream_t st, const DxArgs& a_in, size_t lds) {
   DxArgs a = a_in;
   if constexpr (!TAPE && AW == DX_W && PD == 2) {      // the stamped instantiation (tools/time_decoder.py): the plain decoder at the reference widths only
-    if (a.trace && !a.manual) { hipLaunchKernelGGL((k_decoder_xcd<RG, false, false, AW, PD, true>), dim3(DX_NGROUP * DX_GROUP), dim3(DX_NT), lds, st, a); HIPCHK(hipGetLastError()); return 0; }
+    if (a.trace && !a.manual) { hipLaunchKernelGGL((k_decoder_xcd<RG, false, false, AW, PD, true>), dim3(CHIP_CUS), dim3(DX_NT), lds, st, a); HIPCHK(hipGetLastError()); return 0; }
   }
   a.trace = nullptr;
   // manual alignments: their own instantiation (the score phases are compiled out); with teacher frames as well (round 6: teacher-forced decoding under
   // manual alignments on an inference model -- taco_decoder_forward with both -- used to fall to the launch-per-stage loop)
-  if (a.manual) { hipLaunchKernelGGL((k_decoder_xcd<RG, TAPE, true, AW, PD>), dim3(DX_NGROUP * DX_GROUP), dim3(DX_NT), lds, st, a); HIPCHK(hipGetLastError()); return 0; }
-  hipLaunchKernelGGL((k_decoder_xcd<RG, TAPE, false, AW, PD>), dim3(DX_NGROUP * DX_GROUP), dim3(DX_NT), lds, st, a);
+  if (a.manual) { hipLaunchKernelGGL((k_decoder_xcd<RG, TAPE, true, AW, PD>), dim3(CHIP_CUS), dim3(DX_NT), lds, st, a); HIPCHK(hipGetLastError()); return 0; }
+  hipLaunchKernelGGL((k_decoder_xcd<RG, TAPE, false, AW, PD>), dim3(CHIP_CUS), dim3(DX_NT), lds, st, a);
   HIPCHK(hipGetLastError());
   return 0;
 }
-// `tape`: null (inference), or the TAPE instantiation's extra arguments already filled in (teacher, tape pointers; training forward)
-static int dx_launch(const taco_model* m, hipStream_t st, const float* enc_out, const int* speaker_id, const float* spk_rows, int B, int T_in, int n,
+// Every (rows per group, TAPE, attention_size, prenet layers) k_decoder_xcd is instantiated for, each with and without manual alignments: the reference
+// widths plain (these also stamped, tools/time_decoder.py) and TAPE (teacher frames; the training forward), and the presets of hparams.py:71-117 that the reference
+// ships switched off -- "Single Speaker", "Single Speaker with generalization", the first "Deep Voice 2" block, and the two remaining combinations
+#define DX_REFERENCE(X) X(1, false, DX_W, 2) X(2, false, DX_W, 2) X(4, false, DX_W, 2) X(8, false, DX_W, 2)
+#define DX_REFERENCE_TAPE(X) X(1, true, DX_W, 2) X(2, true, DX_W, 2) X(4, true, DX_W, 2) X(8, true, DX_W, 2)
+#define DX_PRESETS(X) X(4, false, 128, 2) X(8, false, 128, 2) X(4, false, 256, 3) X(8, false, 256, 3) X(4, false, 512, 3) X(4, false, 128, 3) X(8, false, 128, 3) X(4, false, 512, 2)
+static constexpr int dx_inst(int rg, bool tape, int aw, int pd) { return rg | (tape ? 16 : 0) | pd << 8 | aw << 12; }
+// dp: decoder_plan's, persistent; `tape`: null, or where dp.tape the TAPE instantiation's extra arguments already filled in (teacher, tape pointers)
+static int dx_launch(const taco_model* m, hipStream_t st, const DecPlan& dp, const float* enc_out, const int* speaker_id, const float* spk_rows, int B, int T_in, int n,
                      const float* manual, float* mel, float* align_out, float* dbg, int dbgw, const float* keys, int* nz,
                      unsigned long long* xbuf, unsigned* dxctl, float* rowbias, const float* h_att0, const float* h10, const float* h20,
                      const DxArgs* tape = nullptr) {
@@ -1775,14 +1797,12 @@ static int dx_launch(const taco_model* m, hipStream_t st, const float* enc_out, 
   {   // A/B build: the eleven first-poll sleeps (units of 64 clocks) from TACO_DX_DLY = "a,b,c,..." (sites 0..10 of taco_decoder_xcd.h); eager launches only
     int d[32]; const int dflt[11] = {DX_POLL_DELAY_B, DX_FIRST_POLL_DELAY, DX_FIRST_POLL_DELAY, DX_FIRST_POLL_DELAY, DX_POLL_DELAY_B, DX_FIRST_POLL_DELAY,
                                      DX_FIRST_POLL_DELAY, DX_POLL_DELAY_B, DX_FIRST_POLL_DELAY, DX_POLL_DELAY_B, DX_FIRST_POLL_DELAY};
-    const int RGs = dx_rows_per_group(m, B);
-    for (int i = 0; i < 32; ++i) d[i] = (i & 15) < 11 ? dx_site_delay(i & 15, dflt[i & 15], RGs) : 0;
+    for (int i = 0; i < 32; ++i) d[i] = (i & 15) < 11 ? dx_site_delay(i & 15, dflt[i & 15], dp.rg) : 0;
     if (const char* e = getenv("TACO_DX_DLY")) { int i = 0; const char* p = e; while (*p && i < 11) { d[i] = d[16 + i] = atoi(p); ++i; while (*p && *p != ',') ++p; if (*p == ',') ++p; } }
     if (const char* e = getenv("TACO_DX_DLY_B")) { int i = 0; const char* p = e; while (*p && i < 11) { d[16 + i] = atoi(p); ++i; while (*p && *p != ',') ++p; if (*p == ',') ++p; } }      // waves 4-7
     HIPCHK(hipMemcpyToSymbol(HIP_SYMBOL(g_dx_dly), d, sizeof d));
   }
 #endif
-  const int RG = dx_rows_per_group(m, B);
   DxArgs a; memset(&a, 0, sizeof a);
   if (tape) a = *tape;
   a.manual = manual;
@@ -1793,7 +1813,7 @@ static int dx_launch(const taco_model* m, hipStream_t st, const float* enc_out, 
     a.rowbias = rowbias;
   }
   a.wpack = AP(m, m->dx_pack);
-  a.qpack = AP(m, m->dx_qpack[RG == 1 ? 0 : RG == 2 ? 1 : RG == 4 ? 2 : 3]);
+  a.qpack = AP(m, m->dx_qpack[dp.rg == 1 ? 0 : dp.rg == 2 ? 1 : dp.rg == 4 ? 2 : 3]);
   a.b_p1_0 = AP(m, m->dx_b_p1_0); a.b_p1c = AP(m, m->dx_b_p1c); a.b_p2 = AP(m, m->dx_b_p2); a.b_p3 = AP(m, m->dx_b_p3); a.b_ag = AP(m, m->dx_b_ag); a.b_ac = AP(m, m->dx_b_ac);
   a.b_g1f = AP(m, m->dx_b_g1f); a.b_g1c = AP(m, m->dx_b_g1c); a.b_g2g = AP(m, m->dx_b_g2g); a.b_g2c = AP(m, m->dx_b_g2c);
   a.b_f = AP(m, m->dx_b_f);
@@ -1804,46 +1824,23 @@ static int dx_launch(const taco_model* m, hipStream_t st, const float* enc_out, 
   if (a.trace) { const char* e = getenv("TACO_TRACE_MEMBER"); a.trc_member = e ? atoi(e) : 0; e = getenv("TACO_TRACE_TID"); a.trc_tid = e ? atoi(e) : 0; }
   a.B = B; a.T_in = T_in; a.n = n; a.rM = m->hp.num_mels * m->hp.reduction_factor; a.att_type = m->hp.attention_type;
   a.mels = m->hp.num_mels;
-  a.grp0 = 0; a.ngroups = cdiv(B, RG); a.force_wt = m->dx_mode == 2 ? 1 : 0;
+  a.grp0 = 0; a.ngroups = cdiv(B, dp.rg); a.force_wt = m->dx_mode == 2 ? 1 : 0;
   // every polled word starts from zero on every launch (tags are step numbers, the census counts arrivals)
   HIPCHK(clear_polled(xbuf, (size_t)((char*)dxctl - (char*)xbuf) + 256, st));   // carved back to back: one fill launch
-  const size_t lds = dx_lds_floats(RG, T_in, tape != nullptr, m->hp.attention_size) * sizeof(float);
-  if (!dx_reference_widths(m)) {      // the presets of hparams.py:71-117 that the reference ships switched off: (attention_size, prenet layers)
-    const int aw = m->hp.attention_size, pd = dx_prenet_depth(m);
-    if (tape) return fail(TACO_ERR_UNSUPPORTED, "the persistent training forward exists at the reference widths only");
-    if (aw == 128 && pd == 2) return RG == 4 ? dx_launch_rg<4, false, 128, 2>(st, a, lds) : dx_launch_rg<8, false, 128, 2>(st, a, lds);      // "Single Speaker"
-    if (aw == 256 && pd == 3) return RG == 4 ? dx_launch_rg<4, false, 256, 3>(st, a, lds) : dx_launch_rg<8, false, 256, 3>(st, a, lds);      // "Single Speaker with generalization"
-    if (aw == 512 && pd == 3 && RG == 4) return dx_launch_rg<4, false, 512, 3>(st, a, lds);                                                   // "Deep Voice 2" (the first, disabled block)
-    if (aw == 128 && pd == 3) return RG == 4 ? dx_launch_rg<4, false, 128, 3>(st, a, lds) : dx_launch_rg<8, false, 128, 3>(st, a, lds);
-    if (aw == 512 && pd == 2 && RG == 4) return dx_launch_rg<4, false, 512, 2>(st, a, lds);
-    return fail(TACO_ERR_STATE, "no persistent decoder instantiation for attention_size %d, %d prenet layers, %d rows per group", aw, pd, RG);
-  }
-  if (tape) {
-    switch (RG) {
-      case 1: return dx_launch_rg<1, true>(st, a, lds);
-      case 2: return dx_launch_rg<2, true>(st, a, lds);
-      case 4: return dx_launch_rg<4, true>(st, a, lds);
-      default: return dx_launch_rg<8, true>(st, a, lds);
-    }
-  }
-  switch (RG) {
-    case 1: return dx_launch_rg<1, false>(st, a, lds);
-    case 2: return dx_launch_rg<2, false>(st, a, lds);
-    case 4: return dx_launch_rg<4, false>(st, a, lds);
-    default: return dx_launch_rg<8, false>(st, a, lds);
+  switch (dx_inst(dp.rg, dp.tape, dp.aw, dp.pd)) {
+#define X(RG, TAPE, AW, PD) case dx_inst(RG, TAPE, AW, PD): return dx_launch_rg<RG, TAPE, AW, PD>(st, a, dp.lds_bytes);
+    DX_REFERENCE(X) DX_REFERENCE_TAPE(X) DX_PRESETS(X)
+#undef X
+    default: return fail(TACO_ERR_STATE, "no persistent decoder instantiation for attention_size %d, %d prenet layers, %d rows per group%s", dp.aw, dp.pd, dp.rg, dp.tape ? ", tape" : "");
   }
 }
-// persistent BPTT (taco_decoder_bwd_xcd.h): same placement rules as the forward kernel
+// persistent BPTT (taco_decoder_bwd_xcd.h); dp: decoder_plan(..., DEC_TRAIN_BWD), persistent
 static size_t dbx_xbuf_granules(int T_in) {
   size_t g = 0;
   for (int RG = 1; RG <= 8; RG *= 2) g = std::max(g, (size_t)db_xlayout(RG, T_in).total);
   return g;
 }
-static bool dbx_usable(const taco_model* m, int B, int T_in) {
-  if (!m->dx_mode || !m->dbx_pack || !m->tp || B > 8 * DX_NGROUP || m->cu_count < DX_NGROUP * DX_GROUP) return false;
-  return db_lds_floats(dx_rows_per_group(m, B), T_in) * sizeof(float) <= 160 * 1024;
-}
-static int dbx_launch(const taco_model* m, hipStream_t st, DbArgs a, int B, int T_in, int n, unsigned long long* xbuf, unsigned* dxctl) {
+static int dbx_launch(const taco_model* m, hipStream_t st, const DecPlan& dp, DbArgs a, int B, int T_in, int n, unsigned long long* xbuf, unsigned* dxctl) {
   ChipTurn turn(m->device, st);
 #ifdef DX_DLY_RT
   {   // A/B build: the twelve first-poll sleeps of the backward loop from TACO_DB_DLY (sites 0..11 of taco_decoder_bwd_xcd.h)
@@ -1853,26 +1850,24 @@ static int dbx_launch(const taco_model* m, hipStream_t st, DbArgs a, int B, int 
     HIPCHK(hipMemcpyToSymbol(HIP_SYMBOL(g_db_dly), d, sizeof d));
   }
 #endif
-  const int RG = dx_rows_per_group(m, B);
   a.wpack = AP(m, m->dbx_pack);
   a.att_v = AP(m, m->att_v); a.att_b = AP(m, m->att_b); a.score_bias = AP(m, m->att_sb);
   a.xbuf = xbuf; a.ctl = dxctl; a.err = m->d_err; a.trace = (m->trace_on && m->d_trace) ? m->d_trace + 2 * DX_TRACE_STEPS * DX_TRACE_SLOTS : nullptr;
   a.B = B; a.T_in = T_in; a.n = n; a.att_type = m->hp.attention_type;
   a.force_wt = m->dx_mode == 2 ? 1 : 0;
   HIPCHK(zero_async(xbuf, (size_t)((char*)dxctl - (char*)xbuf) + 256, st));
-  const size_t lds = db_lds_floats(RG, T_in) * sizeof(float);
-  const dim3 grid(DX_NGROUP * DX_GROUP), blk(DX_NT);
-  if (a.trace && RG == 4) {      // the stamped instantiation (tools/trace_bptt.py): the C4 shard's geometry only
-    hipLaunchKernelGGL((k_decoder_bwd_xcd<4, true>), grid, blk, lds, st, a);
+  const dim3 grid(CHIP_CUS), blk(DX_NT);
+  if (a.trace && dp.rg == 4) {      // the stamped instantiation (tools/trace_bptt.py): the C4 shard's geometry only
+    hipLaunchKernelGGL((k_decoder_bwd_xcd<4, true>), grid, blk, dp.lds_bytes, st, a);
     HIPCHK(hipGetLastError());
     return 0;
   }
   a.trace = nullptr;
-  switch (RG) {
-    case 1: hipLaunchKernelGGL((k_decoder_bwd_xcd<1>), grid, blk, lds, st, a); break;
-    case 2: hipLaunchKernelGGL((k_decoder_bwd_xcd<2>), grid, blk, lds, st, a); break;
-    case 4: hipLaunchKernelGGL((k_decoder_bwd_xcd<4>), grid, blk, lds, st, a); break;
-    default: hipLaunchKernelGGL((k_decoder_bwd_xcd<8>), grid, blk, lds, st, a); break;
+  switch (dp.rg) {
+    case 1: hipLaunchKernelGGL((k_decoder_bwd_xcd<1>), grid, blk, dp.lds_bytes, st, a); break;
+    case 2: hipLaunchKernelGGL((k_decoder_bwd_xcd<2>), grid, blk, dp.lds_bytes, st, a); break;
+    case 4: hipLaunchKernelGGL((k_decoder_bwd_xcd<4>), grid, blk, dp.lds_bytes, st, a); break;
+    default: hipLaunchKernelGGL((k_decoder_bwd_xcd<8>), grid, blk, dp.lds_bytes, st, a); break;
   }
   HIPCHK(hipGetLastError());
   return 0;
@@ -1902,12 +1897,12 @@ static int decoder_forward(const taco_model* m, hipStream_t st, const float* enc
   const int ldY = n * rM;   // mel buffer viewed as Y [B, n, r*num_mels] (tacotron.py:213-214 is a pure reshape)
   const int dbgw = As + D + L * Hd;
   HIPCHK(clear_polled(w.nz, (size_t)n * B * sizeof(int), st));
-  if (dx_usable(m, B, T_in, manual, teacher) && !after_step) {
+  if (const DecPlan dp = decoder_plan(m, B, T_in, n, teacher ? DEC_TEACHER : DEC_INFER); dp.persistent && !after_step) {      // (after_step: see overlap_chunk)
     // the whole loop as ONE persistent launch (taco_decoder_xcd.h), which builds its initial state itself (zeros or the deepvoice
     // vectors); the launch-per-stage loop below is the general path
     DxArgs ta; memset(&ta, 0, sizeof ta);
     if (teacher) { ta.teacher = teacher; ta.p1o_raw = m->tp ? nullptr : AP(m, m->dx_p1o_raw); }     // teacher-forced: the TAPE instantiation without a tape
-    TRY(dx_launch(m, st, enc_out, speaker_id, nullptr, B, T_in, n, manual, mel, align_out, dbg, dbgw, w.keys, w.nz, w.xbuf, w.dxctl, w.rowbias,
+    TRY(dx_launch(m, st, dp, enc_out, speaker_id, nullptr, B, T_in, n, manual, mel, align_out, dbg, dbgw, w.keys, w.nz, w.xbuf, w.dxctl, w.rowbias,
                   dv ? spk->vec[2] : nullptr, dv ? spk->vec[3] : nullptr, dv ? spk->vec[4] : nullptr, teacher ? &ta : nullptr));
     if (stop_step) {
       hipLaunchKernelGGL(k_stop_step, dim3(1), dim3(1024), 0, st, w.nz, B, n, stop_step);
@@ -2058,6 +2053,11 @@ static int latch_errors(const taco_model* m, hipStream_t st, int32_t* stop) {
   return 0;
 }
 
+// taco_debug_set_overlap: steps per chunk where forward_pass runs the post-net's feed-forward stages behind a decoder loop of n steps (then one launch per stage); else 0
+static int overlap_chunk(const taco_model* m, int n) {
+  const int CH = m->overlap > 16 ? m->overlap : 16;
+  return m->overlap && (size_t)(n / CH + 4) <= m->events.size() ? CH : 0;
+}
 // One pass of at most 64 batch rows (what the persistent kernels place on one chip: 8 groups x 8 rows).
 static int forward_pass(taco_model* m, hipStream_t st, const int32_t* ids, const int32_t* lengths, const int32_t* spk,
                         int B, int T_in, int n, const float* manual, float* mel, float* linear, float* align,
@@ -2071,8 +2071,8 @@ static int forward_pass(taco_model* m, hipStream_t st, const int32_t* ids, const
   carve_full(cv, m, B, T_in, n, w);
   if (!cv.ok()) return fail(TACO_ERR_STATE, "workspace too small: need %zu bytes, have %zu", cv.off, ws_bytes);
   const int r = m->hp.reduction_factor, T_mel = n * r;
-  const int CH = m->overlap > 16 ? m->overlap : 16;   // decoder steps per post-net chunk
-  if (!m->overlap || (size_t)(n / CH + 4) > m->events.size()) {
+  const int CH = overlap_chunk(m, n);
+  if (!CH) {
     // every word a persistent kernel polls and the stop flags, cleared by ONE launch in front of the forward; the stop rule and the
     // error latch are ONE launch behind it (11 graph nodes at C2 with the clears riding in the prenet launch; 13 in round 4, 20 in round 3)
     ZeroRegions z; memset(&z, 0, sizeof z);
@@ -2132,11 +2132,11 @@ static int forward_pass(taco_model* m, hipStream_t st, const int32_t* ids, const
 struct PassPlan { int passes, rows; };
 static PassPlan pass_plan(int B, int cap = 64) { PassPlan p; p.passes = (B + cap - 1) / cap; p.rows = p.passes ? (B + p.passes - 1) / p.passes : 0; return p; }
 // Rows one pass of the decoder loop may hold: 64 (8 groups x 8 rows) -- but an inference model with attention_size 512 (hparams.py:71-82, the first
-// "Deep Voice 2" block) has no persistent instantiation at 8 rows per group (128 score channels per member do not fit the query registers), so its
-// passes hold at most 32 rows: two passes on the persistent decoder instead of one on the launch-per-stage loop, which is four times slower per step.
-static int pass_cap(const taco_model* m) {
-  if (m && !m->tp && m->hp.attention_size == 512 && m->dx_mode && m->dx_pack && m->cu_count >= DX_NGROUP * DX_GROUP) return 32;
-  return 64;
+// "Deep Voice 2" block) has no persistent instantiation at 8 rows per group, so its passes hold at most 32 rows: two passes on the persistent decoder
+// instead of one on the launch-per-stage loop, which is four times slower per step.  state_dump (taco_decoder_forward's, laid out [step][row]): one pass.
+static int decoder_pass_rows(const taco_model* m, bool state_dump = false) {
+  // (with the call's T_in and n passed down: `&& decoder_plan(m, CHIP_ROWS / 2, T_in, n, DEC_INFER).persistent` -- today the rule looks at no shape)
+  return !state_dump && decoder_plan(m, CHIP_ROWS, 0, 0, DEC_INFER).why == DEC_WHY_NO_INSTANTIATION ? CHIP_ROWS / 2 : CHIP_ROWS;
 }
 __global__ void k_stop_combine(const int* pstop, int np, int* stop) {
   if (threadIdx.x == 0) {
@@ -2146,23 +2146,21 @@ __global__ void k_stop_combine(const int* pstop, int np, int* stop) {
   }
 }
 static size_t forward_workspace(const taco_model* m, int B, int T_in, int n, FullWs* w_out, int32_t** pstop, void* ws, size_t ws_bytes, bool* ok) {
-  const PassPlan pp = pass_plan(B, pass_cap(m));
+  const PassPlan pp = pass_plan(B, decoder_pass_rows(m));
   Carver cv(ws, ws_bytes);
   FullWs w;
   carve_full(cv, m, pp.rows, T_in, n, w);
-  const size_t pass_bytes = cv.off;
   int32_t* ps = pp.passes > 1 ? (int32_t*)cv.i((size_t)pp.passes) : nullptr;
   if (w_out) *w_out = w;
   if (pstop) *pstop = ps;
   if (ok) *ok = cv.ok();
-  (void)pass_bytes;
   return cv.off;
 }
 static int forward_enqueue(taco_model* m, hipStream_t st, const int32_t* ids, const int32_t* lengths, const int32_t* spk,
                            int B, int T_in, int n, const float* manual, float* mel, float* linear, float* align,
                            int32_t* stop, void* ws, size_t ws_bytes) {
   if (!m) return fail(TACO_ERR_ARG, "null model");
-  const int cap = pass_cap(m);
+  const int cap = decoder_pass_rows(m);
   if (B <= cap) return forward_pass(m, st, ids, lengths, spk, B, T_in, n, manual, mel, linear, align, stop, ws, ws_bytes);
   if (T_in <= 0 || n <= 0) return fail(TACO_ERR_ARG, "bad time %d / steps %d", T_in, n);
   if (!ids || !lengths || !mel || !linear || !align || !ws) return fail(TACO_ERR_ARG, "null buffer");
@@ -2472,28 +2470,17 @@ int taco_model_finalize(taco_model* m) {
   HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_head_sweep<512>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
   HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_head_sweep<256>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
   HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_pointwise_chain<128>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-  HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_decoder_xcd<1>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-  HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_decoder_xcd<2>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-  HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_decoder_xcd<4>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-  HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_decoder_xcd<8>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-  HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_decoder_xcd<1, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-  HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_decoder_xcd<2, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-  HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_decoder_xcd<4, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-  HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_decoder_xcd<8, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-#define DX_ATTR_T(RG) \
-  HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_decoder_xcd<RG, true, false>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)); \
-  HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_decoder_xcd<RG, true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-  DX_ATTR_T(1) DX_ATTR_T(2) DX_ATTR_T(4) DX_ATTR_T(8)      // teacher frames (with and without manual alignments)
-#undef DX_ATTR_T
-  HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_decoder_xcd<1, false, false, DX_W, 2, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));      // the stamped instantiations
-  HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_decoder_xcd<2, false, false, DX_W, 2, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-  HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_decoder_xcd<4, false, false, DX_W, 2, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-  HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_decoder_xcd<8, false, false, DX_W, 2, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-#define DX_ATTR(RG, AW, PD) \
-  HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_decoder_xcd<RG, false, false, AW, PD>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)); \
-  HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_decoder_xcd<RG, false, true, AW, PD>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-  DX_ATTR(4, 128, 2) DX_ATTR(8, 128, 2) DX_ATTR(4, 256, 3) DX_ATTR(8, 256, 3) DX_ATTR(4, 512, 3) DX_ATTR(4, 128, 3) DX_ATTR(8, 128, 3) DX_ATTR(4, 512, 2)
+#define DX_ATTR(...) HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_decoder_xcd<__VA_ARGS__>), hipFuncAttributeMaxDynamicSharedMemorySize, DX_LDS_BUDGET));
+#define PLAIN(RG, TAPE, AW, PD) DX_ATTR(RG, TAPE, false, AW, PD)
+#define MANUAL(RG, TAPE, AW, PD) DX_ATTR(RG, TAPE, true, AW, PD)
+#define BOTH(RG, TAPE, AW, PD) PLAIN(RG, TAPE, AW, PD) MANUAL(RG, TAPE, AW, PD)
+#define STAMPED(RG, TAPE, AW, PD) DX_ATTR(RG, TAPE, false, AW, PD, true)
+  DX_REFERENCE(PLAIN) DX_REFERENCE(MANUAL) DX_REFERENCE_TAPE(BOTH) DX_REFERENCE(STAMPED) DX_PRESETS(BOTH)      // (the order of the kernels in the code object)
 #undef DX_ATTR
+#undef PLAIN
+#undef MANUAL
+#undef BOTH
+#undef STAMPED
   HIPCHK(hipStreamCreateWithFlags(&m->side, hipStreamNonBlocking));
   m->events.resize(192);
   for (auto& e : m->events) HIPCHK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
@@ -2619,6 +2606,8 @@ int taco_debug_set_persistent(taco_model* m, int on) {
 int taco_debug_set_decoder_persist(taco_model* m, int mode, int rows_per_group) {
   if (!m) return fail(TACO_ERR_ARG, "null model");
   if (mode < 0 || mode > 2) return fail(TACO_ERR_ARG, "mode must be 0 (launch per stage), 1 (persistent) or 2 (persistent, write-through exchanges)");
+  if (rows_per_group != 0 && rows_per_group != 1 && rows_per_group != 2 && rows_per_group != 4 && rows_per_group != 8)
+    return fail(TACO_ERR_ARG, "rows_per_group %d: accepted are 0 (the smallest that covers the batch), 1, 2, 4 and 8", rows_per_group);
   m->dx_mode = mode; m->dx_rows = rows_per_group;
   return 0;
 }
@@ -2633,32 +2622,39 @@ int taco_debug_decoder_info(taco_model* m, int* out16) {
   out16[15] = m->dx_pack ? 1 : 0;
   return 0;
 }
-// Which engine a call of this shape would run on, and why not the persistent one when it would not (nothing is launched).
-int taco_model_engine_plan(taco_model* m, int B, int T_in, int T_mel, int manual, char* out, int out_len) {
+// Which engine a call of this shape would run on, and why not the persistent one when it would not (nothing is launched).  flags: taco_abi.h
+int taco_model_engine_plan(taco_model* m, int B, int T_in, int T_mel, int flags, char* out, int out_len) {
   if (!m || !m->finalized || !out || out_len < 64) return fail(TACO_ERR_ARG, "bad argument");
   std::string s;
-  if (B > pass_cap(m) && !m->tp) {      // taco_forward_infer / taco_plan_create serve any batch as passes of at most 64 rows (32: attention_size 512); the plan below is a pass's
-    const PassPlan pp = pass_plan(B, pass_cap(m));
+  const int cap = decoder_pass_rows(m, (flags & 4) != 0), n = std::max(1, T_mel / std::max(1, m->hp.reduction_factor));
+  if (B > cap && !m->tp) {      // taco_forward_infer / taco_plan_create serve any batch as passes of at most 64 rows (32: attention_size 512); the plan below is a pass's
+    const PassPlan pp = pass_plan(B, cap);
     s = std::to_string(B) + " rows = " + std::to_string(pp.passes) + " passes of " + std::to_string(pp.rows) + " (the last one " + std::to_string(B - (pp.passes - 1) * pp.rows) + "); per pass: ";
     B = pp.rows;
   }
-  auto why_common = [&](int rows) -> std::string {
-    if (!m->dx_mode) return "switched off (taco_debug_set_decoder_persist 0)";
-    if (m->cu_count < DX_NGROUP * DX_GROUP) return "the device exposes " + std::to_string(m->cu_count) + " compute units (a partition of an MI355X, or another part): the whole-chip kernels need 256";
-    if (rows > 8 * DX_NGROUP) return std::to_string(rows) + " rows > 64 per launch";
-    return "";
+  auto why_common = [&](int why, int rows) -> std::string {      // SCAN_WHY_* / DEC_WHY_*: the reasons all whole-chip kernels share
+    if (why == DEC_WHY_ENGINE_OFF) return "switched off (taco_debug_set_decoder_persist 0)";
+    if (why == DEC_WHY_CUS) return "the device exposes " + std::to_string(m->cu_count) + " compute units (a partition of an MI355X, or another part): the whole-chip kernels need 256";
+    return why == DEC_WHY_ROWS ? std::to_string(rows) + " rows > 64 per launch" : "";
+  };
+  auto dec_why = [&](const DecPlan& dp) -> std::string {
+    switch (dp.why) {
+      case DEC_WHY_WIDTHS: return "widths outside the presets (256-wide decoder cells and memory, attention_size 128 / 256 / 512, prenet 256-128[-64], 2 decoder layers, r * num_mels <= 512)";
+      case DEC_WHY_TEACHER_ROWS: return "teacher frames on an inference model outside the reference widths (attention_size 256, prenet 256-128, num_mels <= 128)";
+      case DEC_WHY_NO_INSTANTIATION: return "attention_size 512 with more than 32 rows (no instantiation at 8 rows per group)";
+      case DEC_WHY_LDS: return "T_in = " + std::to_string(T_in) + " does not fit a member's LDS at " + std::to_string(dp.rg) + " rows per group";
+      case DEC_WHY_TAPE_LAYOUT: return "a tape of " + std::to_string(B) + " rows x " + std::to_string(n) + " steps at num_mels " + std::to_string(m->hp.num_mels) + " is outside the kernel's layout (num_mels <= 128, 20 x rows x steps x 256 < 2^31)";
+      default: return why_common(dp.why, B);
+    }
   };
   {  // decoder loop
-    std::string why = why_common(B);
-    if (why.empty() && !m->dx_pack) why = "widths outside the presets (256-wide decoder cells and memory, attention_size 128 / 256 / 512, prenet 256-128[-64], 2 decoder layers, r * num_mels <= 512)";
-    const int RG = dx_rows_per_group(m, B);
-    if (why.empty() && m->hp.attention_size == 512 && RG > 4) why = "attention_size 512 with more than 32 rows (no instantiation at 8 rows per group)";
-    if (why.empty() && dx_lds_floats(RG, T_in, m->tp != nullptr, m->hp.attention_size) * sizeof(float) > 160 * 1024)
-      why = "T_in = " + std::to_string(T_in) + " does not fit a member's LDS at " + std::to_string(RG) + " rows per group";
-    if (why.empty()) s += "decoder loop: persistent k_decoder_xcd<" + std::to_string(RG) + (dx_reference_widths(m) ? std::string("") : ", attention " + std::to_string(m->hp.attention_size) + ", " +
-                          std::to_string(dx_prenet_depth(m)) + " prenet layers") + "> (" + std::string(manual ? "manual alignments" : "computed alignments") + ", " +
-                          std::string(m->dx_mode == 2 ? "write-through exchanges forced" : "XCD-local exchanges when the census finds 32 workgroups per XCD") + ")";
-    else s += "decoder loop: one launch per stage -- " + why;
+    const DecPlan dp = decoder_plan(m, B, T_in, n, m->tp ? DEC_TRAIN_FWD : (flags & 2) ? DEC_TEACHER : DEC_INFER);
+    const int chunk = m->tp || (flags & 6) ? 0 : overlap_chunk(m, n);      // forward_pass only
+    if (dp.persistent && !chunk)
+      s += "decoder loop: persistent k_decoder_xcd<" + std::to_string(dp.rg) + (dx_reference_widths(m) ? std::string("") : ", attention " + std::to_string(dp.aw) + ", " +
+           std::to_string(dp.pd) + " prenet layers") + "> (" + std::string((flags & 1) ? "manual alignments" : "computed alignments") + ", " +
+           std::string(m->dx_mode == 2 ? "write-through exchanges forced" : "XCD-local exchanges when the census finds 32 workgroups per XCD") + ")";
+    else s += "decoder loop: one launch per stage -- " + (dp.persistent ? "taco_debug_set_overlap: the post-net's feed-forward stages follow the loop in chunks of " + std::to_string(chunk) + " steps" : dec_why(dp));
   }
   // the two scans, from the plan bigru_scan itself follows
   auto scan_why = [&](const Cbhg& c, const ScanPlan& sp, const char* width_name, int rows) -> std::string {
@@ -2666,7 +2662,7 @@ int taco_model_engine_plan(taco_model* m, int B, int T_in, int T_mel, int manual
       case SCAN_WHY_MODE: return "taco_debug_set_persistent(" + std::to_string(m->persist) + "): " + scan_kernel_name(sp.kernel);
       case SCAN_WHY_WIDTH: return std::string(width_name) + " " + std::to_string(c.rnn) + " != 256";
       case SCAN_WHY_FRAMES: return "fewer than 2 frames";
-      default: return why_common(rows);
+      default: return why_common(sp.why_not_whole_chip, rows);
     }
   };
   {  // post-net scan
@@ -2695,6 +2691,8 @@ int taco_model_engine_plan(taco_model* m, int B, int T_in, int T_mel, int manual
     const ScanBwd bwd = scan_plan(m, c, B, T_mel).bwd;
     s += std::string("; backward scans: post-net ") + (bwd == SCAN_BWD_OCT ? "k_bigru_oct_bwd (one row per cluster of 8 CUs)" : bwd == SCAN_BWD_DUO ? "k_bigru_duo_bwd" : "k_bigru_rows_bwd") +
          ", encoder " + (m->enc.rnn == 128 ? "k_bigru_resb (recurrent kernels in registers)" : "k_bigru_rows_bwd");
+    const DecPlan bp = decoder_plan(m, B, T_in, n, DEC_TRAIN_BWD);      // (taco_train_set_bptt_engine(t, 0) switches it off per trainer)
+    s += "; decoder backward loop: " + (bp.persistent ? "persistent k_decoder_bwd_xcd<" + std::to_string(bp.rg) + ">" : "one launch per stage -- " + dec_why(bp));
   }
   snprintf(out, (size_t)out_len, "%s", s.c_str());
   return 0;
@@ -2738,11 +2736,11 @@ size_t taco_stage_workspace_bytes(const taco_model* m, int B, int T) {
   // large enough for any single stage at (B, T): encoder at T_in=T, decoder with T_in=T and n_steps=T, post-net at T_mel=T
   Carver a(nullptr, 0), b(nullptr, 0), c(nullptr, 0);
   const int R = B > 64 ? pass_plan(B).rows : B;      // more than 64 rows: passes over one pass's workspace (+ the passes' stop words)
-  const int Rd = B > pass_cap(m) ? pass_plan(B, pass_cap(m)).rows : B;
+  const int cap = decoder_pass_rows(m), Rd = B > cap ? pass_plan(B, cap).rows : B;      // (a state dump of 33..64 rows is one pass of B rows)
   EncWs e; carve_enc(a, m, R, T, e);
   DecWs d; carve_dec(b, m, Rd, T, T, d);
   PostWs p; carve_post(c, m, R, T, p);
-  return std::max(a.off, std::max(b.off, c.off)) + (B > pass_cap(m) ? 256 : 0);
+  return std::max(a.off, std::max(b.off, c.off)) + (B > cap ? 256 : 0);
 }
 
 int taco_forward_infer(taco_model* m, void* hip_stream, const int32_t* d_inputs, const int32_t* d_input_lengths,
@@ -2832,9 +2830,9 @@ int taco_decoder_forward(taco_model* m, void* hip_stream, const float* d_encoder
                          int T_in, int n_steps, const float* d_manual_alignments, const float* d_teacher_frames,
                          float* d_mel, float* d_alignments, int32_t* d_stop_step, float* d_dbg_states, void* d_workspace,
                          size_t workspace_bytes) {
-  if (m && m->finalized && B > pass_cap(m) && !(d_dbg_states && B <= 64) && T_in > 0 && n_steps > 0 && d_encoder_out && d_mel && d_alignments && d_workspace) {      // passes of at most 64 (32) rows
+  if (m && m->finalized && B > decoder_pass_rows(m, d_dbg_states != nullptr) && T_in > 0 && n_steps > 0 && d_encoder_out && d_mel && d_alignments && d_workspace) {      // passes of at most 64 (32) rows
     if (d_dbg_states) return fail(TACO_ERR_UNSUPPORTED, "the per-step state dump is laid out [step][row]: at most 64 rows per call");
-    const PassPlan pp = pass_plan(B, pass_cap(m));
+    const PassPlan pp = pass_plan(B, decoder_pass_rows(m));
     const size_t rM = (size_t)m->hp.reduction_factor * m->hp.num_mels, D = (size_t)2 * m->hp.enc_rnn_size;
     if (workspace_bytes < 256) return fail(TACO_ERR_STATE, "workspace too small");
     int32_t* pstop = (int32_t*)((char*)d_workspace + ((workspace_bytes - (size_t)pp.passes * sizeof(int32_t)) & ~(size_t)255));      // the tail of the caller's buffer

@@ -932,13 +932,13 @@ static int decoder_forward_train(const TrainCtx& x, const float* enc_out, int B,
     hipLaunchKernelGGL(k_tile_rows, EWGRID((size_t)B * n * S), 0, st, spk_emb, w.pz[np - 1], Pz, Pl, B, n, S);
     HIPCHK(hipGetLastError());
   }
-  if (w.tape256 && hp.dec_layer_num == 2 && hp.num_mels <= DX_P2 && (size_t)DXT_N * w.tstride < (1u << 31) && dx_usable(m, B, T_in, nullptr, teach)) {
+  if (const DecPlan dp = decoder_plan(m, B, T_in, n, DEC_TRAIN_FWD); dp.persistent) {      // (the widths of carve_dec_tape's tape256 layout among its terms)
     // the whole teacher-forced loop as ONE persistent launch that also writes the tape (k_decoder_xcd<RG, true>, taco_decoder_xcd.h);
     // rnn_decoder_test_mode (feed_back): the same launch, the step's own last frame exchanged in place of the teacher's
     DxArgs ta; memset(&ta, 0, sizeof ta);
     ta.teacher = feed_back ? nullptr : teach; ta.own_fb = feed_back ? 1 : 0; ta.tape = w.tape256; ta.tstride = w.tstride; ta.tp_p2 = w.pz[np - 1]; ta.ld_p2 = Pz; ta.tp_ctx = w.ctx; ta.ld_ctx = Dc;
     ta.tp_e = w.g_e; ta.tp_alpha = w.alpha;
-    return dx_launch(m, st, enc_out, nullptr, spk_emb, B, T_in, n, nullptr, mel, align_hist, nullptr, 0, w.keys, w.nz, w.xbuf, w.dxctl, w.rowbias,
+    return dx_launch(m, st, dp, enc_out, nullptr, spk_emb, B, T_in, n, nullptr, mel, align_hist, nullptr, 0, w.keys, w.nz, w.xbuf, w.dxctl, w.rowbias,
                      att_init, dec_init ? dec_init[0] : nullptr, dec_init ? dec_init[1] : nullptr, &ta);
   }
   for (int t = 0; t < n; ++t) {
@@ -1045,8 +1045,8 @@ static int decoder_backward(const TrainCtx& x, const float* enc_out, int B, int 
   if (attn_lds > 160 * 1024 || (As % 4) || (D % 4) || (A % 4)) return fail(TACO_ERR_UNSUPPORTED, "attention sizes not supported by the backward kernel");
   // the whole loop as ONE persistent launch (k_decoder_bwd_xcd, taco_decoder_bwd_xcd.h) when the forward left its tape in that
   // kernel's layout; the launch-per-stage loop below is the general path (other widths, 'simple', more than 64 rows)
-  const bool persistent = x.t->bptt_persistent && w.tape256 && L == 2 && np == 2 && (size_t)DXT_N * w.tstride < (1u << 31) &&
-                          dbx_usable(m, B, T_in);
+  const DecPlan bp = decoder_plan(m, B, T_in, n, DEC_TRAIN_BWD);
+  const bool persistent = x.t->bptt_persistent && bp.persistent;
   x.t->sm->last_bptt = persistent ? 1 : 0;
   if (persistent) {
     DbArgs a; memset(&a, 0, sizeof a);
@@ -1060,7 +1060,7 @@ static int decoder_backward(const TrainCtx& x, const float* enc_out, int B, int 
     a.g_dcpA = w.g_dcpA; a.g_dgpA = w.g_dgpA; a.g_dz1 = w.g_dz[0]; a.g_dz2 = w.g_dz[1]; a.g_dq = w.g_dq; a.g_de = w.g_de; a.g_dctx = w.g_dctx;
     a.d_att_init = d_att_init; a.d_h10 = d_dec_init ? d_dec_init[0] : nullptr; a.d_h20 = d_dec_init ? d_dec_init[1] : nullptr;
     a.dsb_acc = w.dsb_acc;
-    TRY(dbx_launch(m, st, a, B, T_in, n, w.xbuf, w.dxctl));
+    TRY(dbx_launch(m, st, bp, a, B, T_in, n, w.xbuf, w.dxctl));
     if (S) {
       // 'simple': d speaker embedding = sum over steps of [d o0 . Wcc^T]_spk + [d c_pre(att) . Wc^T + d gates(att) . Wg^T]_spk.  Linear in the
       // pre-activation gradients: sum those over time first, then ONE transposed product each (the per-stage chain adds step by step).

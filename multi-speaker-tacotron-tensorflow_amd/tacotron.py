@@ -586,13 +586,15 @@ class Tacotron(object):
         _lib.check(self._lib.taco_debug_decoder_info(self._handle, v))
         return {"protocol": int(v[0]), "per_xcd": [int(x) for x in v[1:9]], "has_pack": bool(v[15]), "compute_units": int(v[14])}
 
-    def engine_plan(self, batch, t_in, t_mel=None, manual=False):
+    def engine_plan(self, batch, t_in, t_mel=None, manual=False, teacher=False, debug=False):
         """One line saying which engine a forward of this shape would run on and, if not the persistent whole-chip kernels, why not
         (widths, rows per launch, LDS, compute units of the device, debug switches).  Nothing is launched; PlanPool(lanes > 1) additionally
-        switches its lanes to the launch-per-stage engine (two whole-chip kernels cannot share the chip)."""
+        switches its lanes to the launch-per-stage engine (two whole-chip kernels cannot share the chip).  teacher / debug: the plan of a
+        decoder() call with teacher_frames / debug=True."""
         buf = C.create_string_buffer(1024)
         t_mel = t_mel if t_mel is not None else self._hparams.max_iters * self._hparams.reduction_factor
-        _lib.check(self._lib.taco_model_engine_plan(self._handle, int(batch), int(t_in), int(t_mel), 1 if manual else 0, buf, 1024))
+        flags = (1 if manual else 0) | (2 if teacher else 0) | (4 if debug else 0)
+        _lib.check(self._lib.taco_model_engine_plan(self._handle, int(batch), int(t_in), int(t_mel), flags, buf, 1024))
         return buf.value.decode()
 
     def decoder_trace(self, enable=True, read=False, scan=False):

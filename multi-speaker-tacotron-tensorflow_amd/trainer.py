@@ -187,6 +187,14 @@ class Trainer(object):
         return {"protocol": int(v[0]), "per_xcd": [int(x) for x in v[1:9]], "has_pack": bool(v[15]), "compute_units": int(v[14]),
                 "bptt_protocol": int(v[9])}       # 0: the last decoder backward was the chain of per-stage launches
 
+    def engine_plan(self, batch, t_in, t_mel):
+        """One line saying which kernels a training step of this shape runs on (decoder loop and its backward loop, scans), and why not the
+        persistent whole-chip ones where it does not; set_bptt_engine(False) is this trainer's own switch and not in it.  Nothing is launched."""
+        mh = C.c_void_p(self._lib.taco_train_model(self._h))
+        buf = C.create_string_buffer(1024)
+        _lib.check(self._lib.taco_model_engine_plan(mh, int(batch), int(t_in), int(t_mel), 0, buf, 1024))
+        return buf.value.decode()
+
     def raise_device_error_for_test(self, value=2):
         """Test hook: sets the sticky device error word, as a persistent kernel whose bounded spin expired does."""
         mh = C.c_void_p(self._lib.taco_train_model(self._h))

@@ -480,6 +480,96 @@ def test_engine_plan_says_which_engine_a_call_gets_and_why_not():
     assert "encoder prenet: one GEMM launch per layer" in plan, plan
 
 
+PLAN_CASES = {   # name: (hparams, engine mode, B, T_in, decoder() / engine_plan() keywords, persistent?, the words of the reason)
+    "fits": (dict(), 1, 5, 19, dict(), True, "k_decoder_xcd<1>"),
+    "switched_off": (dict(), 0, 5, 19, dict(), False, "switched off"),
+    "widths_outside_the_presets": (None, 1, 4, 9, dict(), False, "widths outside the presets"),
+    "lds_at_long_t_in": (dict(), 1, 16, 1200, dict(), False, "T_in = 1200 does not fit a member's LDS at 2 rows per group"),
+    "attention_512_state_dump_of_40_rows": (PRESETS["attention_512_two_prenet_layers"], 1, 40, 21, dict(debug=True), False, "no instantiation at 8 rows per group"),
+    "attention_512_40_rows_as_two_passes": (PRESETS["attention_512_two_prenet_layers"], 1, 40, 21, dict(), True, "40 rows = 2 passes of 20"),
+    "teacher_frames_on_an_inference_model": (dict(), 1, 9, 19, dict(teacher=True), True, "k_decoder_xcd<2>"),
+    "teacher_frames_outside_the_reference_widths": (PRESETS["single_speaker"], 1, 9, 19, dict(teacher=True), False, "teacher frames on an inference model"),
+}
+
+
+@pytest.mark.parametrize("case", sorted(PLAN_CASES))
+def test_engine_plan_agrees_with_the_launch(case):
+    """decoder_plan (csrc/taco_lib.hip) is what decoder_forward follows and what engine_plan words: one decoder() call per reason against
+    the persistent kernel that a whole MI355X can reach, and the calls that fit, on a fresh model each (the protocol word keeps the last
+    persistent launch's answer) -- the plan says "persistent" exactly when the launch reports an exchange protocol."""
+    import torch
+    from util import tiny_hp
+    kw, mode, B, T_in, call, persistent, words = PLAN_CASES[case]
+    n = 2
+    ohp = tiny_hp(max_iters=n) if kw is None else O.OracleHParams(max_iters=n, **kw)
+    m = build_model(ohp, O.init_weights(ohp, 1, 421))
+    m.set_decoder_engine(mode)
+    plan = m.engine_plan(B, T_in, **call)
+    enc = np.random.RandomState(422).uniform(-1, 1, (B, T_in, 2 * ohp.enc_rnn_size)).astype(np.float32)
+    teacher = np.random.RandomState(423).rand(B, n, ohp.num_mels).astype(np.float32) if call.get("teacher") else None
+    mel, _, stop, _ = m.decoder(enc, n, teacher_frames=teacher, debug=call.get("debug", False))
+    torch.cuda.synchronize()
+    info = m.decoder_engine_info()
+    m.check_device_errors()
+    print(case, info["protocol"], plan)
+    assert ("decoder loop: persistent" in plan) == persistent and (info["protocol"] in (1, 2)) == persistent, (info, plan)
+    assert persistent or info["protocol"] == 0, info
+    assert words in plan, plan
+    assert np.isfinite(mel.cpu().numpy()).all() and int(stop.item()) == n
+
+
+@pytest.mark.parametrize("mode", [1, 0])
+def test_engine_plan_agrees_with_a_training_step(mode):
+    """... and for a training shadow model: the forward loop (k_decoder_xcd, TAPE) and the backward loop (k_decoder_bwd_xcd) of one
+    Trainer step against Trainer.engine_plan, with the engine on and switched off."""
+    import torch
+    import taco_amd
+    from util import to_product_hp
+    n, B, T_in = 4, 6, 11
+    hp = O.OracleHParams(max_iters=n)
+    tr = taco_amd.Trainer(to_product_hp(hp), O.init_weights(hp, 1, 431))
+    tr.set_decoder_engine(mode)
+    ids, L = O.synthetic_inputs(B, T_in, 432, ragged=True)
+    rs = np.random.RandomState(433)
+    T_out = n * hp.reduction_factor
+    tr.train_step(ids, L, rs.rand(B, T_out, hp.num_mels), rs.rand(B, T_out, hp.num_freq), np.ones(B))
+    torch.cuda.synchronize()
+    tr.check_device_errors()
+    info, plan = tr.decoder_engine_info(), tr.engine_plan(B, T_in, T_out)
+    print(mode, info, plan)
+    assert ("decoder loop: persistent k_decoder_xcd<1>" in plan) == (mode == 1) == (info["protocol"] in (1, 2)), (info, plan)
+    assert ("decoder backward loop: persistent k_decoder_bwd_xcd<1>" in plan) == (mode == 1) == (info["bptt_protocol"] in (1, 2)), (info, plan)
+    assert mode == 1 or (info["protocol"] == 0 and plan.count("one launch per stage -- switched off") == 2), (info, plan)
+
+
+def test_decoder_engine_hook_refuses_other_rows_per_group():
+    """taco_debug_set_decoder_persist accepts 0 (automatic), 1, 2, 4, 8 rows per group; any other number is TACO_ERR_ARG and changes
+    nothing: the model still decodes, on the engine and rows it had."""
+    import torch
+    import taco_amd
+    n, B = 3, 8
+    ohp = O.OracleHParams(max_iters=n)
+    m = build_model(ohp, O.init_weights(ohp, 1, 441))
+    enc = np.random.RandomState(442).uniform(-1, 1, (B, 17, 2 * ohp.enc_rnn_size)).astype(np.float32)
+    m.set_decoder_engine(1, 2)
+    assert "k_decoder_xcd<2>" in m.engine_plan(B, 17)
+    mel0, al0, _, _ = m.decoder(enc, n)
+    for rows in (3, 5, 6, 7, 16, -1):
+        with pytest.raises(taco_amd._lib.TacoError):
+            m.set_decoder_engine(1, rows)
+        with pytest.raises(taco_amd._lib.TacoError):
+            m.set_decoder_engine(0, rows)      # (nor does a refused call switch the engine off)
+    for rows in (0, 1, 2, 4, 8):
+        m.set_decoder_engine(1, rows)
+    m.set_decoder_engine(1, 2)
+    assert "k_decoder_xcd<2>" in m.engine_plan(B, 17)
+    mel1, al1, _, _ = m.decoder(enc, n)
+    torch.cuda.synchronize()
+    assert m.decoder_engine_info()["protocol"] in (1, 2)
+    m.check_device_errors()
+    assert np.array_equal(mel1.cpu().numpy(), mel0.cpu().numpy()) and np.array_equal(al1.cpu().numpy(), al0.cpu().numpy())
+
+
 def test_a_device_fault_is_reported_by_the_forward_that_saw_it():
     """the sticky device error word, raised by hand here (taco_debug_raise_device_error), comes back in the stop word
     of the next forward (negative), Tacotron.run and PlanPool.result raise on it and acknowledge it, and the forward after that is
