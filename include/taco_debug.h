@@ -32,7 +32,13 @@ int taco_debug_set_persistent(taco_model* m, int on);
  * one launch per layer instead of ONE launch with the activations resident on the CU (csrc/taco_chain.h, the default with on = 1).
  * on bit 3 (on = 9): conv bank and proj_1 of a CBHG as two launches instead of the fused front (csrc/taco_front.h).
  * on bit 4 (on = 17): with the fused front, proj_1's epilogue (k_front_combine) and proj_2 as launches of their own instead of the fused
- * entry of the point-wise chain (csrc/taco_chain.h). */
+ * entry of the point-wise chain (csrc/taco_chain.h).
+ * on bit 5 (on = 33): the linear head on k_gemm_bf3's tiles instead of the row sweep k_head_sweep (csrc/taco_head.h).
+ * on bit 6 (on = 65): every feed-forward layer on the six-product instantiation k_gemm_bf3<..., X6> (operands split three ways: fp32-grade
+ * products on the bf16 pipe), one launch per layer: the fused kernels (front, chain, head sweep) are three-product kernels and stay out.
+ * Ignored on a training shadow model (taco_train_set_exact_gemm picks its level).
+ * A forced tile, a forced k_gemm config (taco_debug_force_gemm_config) and on = 0 switch all fused kernels off too.  Which kernels a call
+ * then gets: ff_plan, prenet_chain_why and head_sweep_why (csrc/taco_lib.hip), told by taco_model_engine_plan. */
 int taco_debug_set_bf3(taco_model* m, int on, int tile_n);
 
 /* test hook: > 0 = taco_forward_infer runs the post-net feed-forward stages behind the decoder on a second stream

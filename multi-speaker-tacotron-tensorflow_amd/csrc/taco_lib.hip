@@ -958,6 +958,31 @@ static int pick_cfg(const taco_model* m, int M, int N, int nvar) {
 }
 
 static thread_local int g_gemm_force_bf3 = 0;     // set around a call by run_dgrad (taco_train.h): this GEMM on the split-bf16 kernel although the model's switch is off
+// ---- which kernels run the feed-forward launches ----
+// The arithmetic of a layer that run_gemm serves: exact fp32 (k_gemm), or operands split into bf16 planes with three products (k_gemm_bf3; the fused
+// kernels exist at this level only) or six (k_gemm_bf3<..., X6>, fp32-grade: a training shadow model's default, taco_debug_set_bf3 bit 6)
+enum GemmLevel { GEMM_EXACT, GEMM_BF3, GEMM_BF3X6 };
+static GemmLevel gemm_level(const taco_model* m, const ConvL& L) {
+  if (!((m->bf3 || m->bf3x6 || g_gemm_force_bf3) && m->force_cfg < 0 && L.bh)) return GEMM_EXACT;
+  return (m->bf3x6 && !g_gemm_force_bf3) || (m->bf3 && L.x6) ? GEMM_BF3X6 : GEMM_BF3;
+}
+// First reason against a fused kernel (k_cbhg_front, k_pointwise_chain, the chain's fused entry, k_head_sweep); NONE: it runs
+enum FfWhyNot { FF_WHY_NONE, FF_WHY_EXACT, FF_WHY_X6, FF_WHY_CFG, FF_WHY_TILE, FF_WHY_SWITCH, FF_WHY_WIDTHS, FF_WHY_NEEDS_BOTH };
+// The term all of them share, once: L (a layer the kernel would serve) at the three-product level -- split-bf16 on, not the six-product
+// level, no forced k_gemm config -- and no forced k_gemm_bf3 tile
+static FfWhyNot ff_fused_why(const taco_model* m, const ConvL& L) {
+  const GemmLevel lv = gemm_level(m, L);
+  return lv == GEMM_BF3X6 ? FF_WHY_X6 : lv == GEMM_EXACT ? (m->force_cfg >= 0 ? FF_WHY_CFG : FF_WHY_EXACT) : m->bf3_tn ? FF_WHY_TILE : FF_WHY_NONE;
+}
+// k_head_sweep (taco_head.h) for a dense layer L over the rows of call c: a wide layer over many rows with a plain epilogue (the linear head).
+// Pure: the one term left to the launch is the 16-byte alignment of c.x -- a workspace carved by Carver (256-byte steps) has it.
+static FfWhyNot head_sweep_why(const taco_model* m, const ConvL& L, int nvar, bool dual, const GemmCall& c) {
+  if (const FfWhyNot why = ff_fused_why(m, L)) return why;
+  if (!m->head_sweep) return FF_WHY_SWITCH;
+  return nvar == 1 && !dual && L.kw == 1 && c.mpw <= 1 && !c.gather && !c.res && !c.rev_len && c.rev_col0 < 0 && c.t_len == 0 && !c.aux0 && !c.aux1 &&
+         c.act == ACT_NONE && !L.bns && c.ldx % 4 == 0 && (L.cin == 256 || L.cin == 512) && L.N >= 512 && L.N % 32 == L.ntail && (L.ntail == 0 || L.wtail) &&
+         c.M >= 256 && (long)c.M * c.ldo < (1L << 30) ? FF_WHY_NONE : FF_WHY_WIDTHS;
+}
 static int run_gemm(const taco_model* m, hipStream_t st, const ConvL* layers, int nvar, bool dual, const GemmCall& c) {
   GemmArgs a;
   memset(&a, 0, sizeof a);
@@ -974,7 +999,7 @@ static int run_gemm(const taco_model* m, hipStream_t st, const ConvL* layers, in
     a.v[i] = m->hvars[layers[i].var_index];
   }
   if (nvar > 16) return fail(TACO_ERR_UNSUPPORTED, "conv bank wider than 16 is not supported");
-  if ((m->bf3 || m->bf3x6 || g_gemm_force_bf3) && m->force_cfg < 0 && L0.bh) {   // split-bf16 path (every feed-forward layer of inference)
+  if (const GemmLevel level = gemm_level(m, L0); level != GEMM_EXACT) {   // split-bf16 path (every feed-forward layer of inference)
     // tiles (rows x cols): 1 = 128x64, 2 = 128x128, 3 = 64x256 (one staged 64-row tile feeds 8 MFMA column tiles)
     // measured (tools/time_gemm_layers.py): 64x256 wins when K or N is large (proj_1, linear, GRU projection), 128x64 otherwise
     const int Ktot = L0.kw * L0.cin;
@@ -985,10 +1010,8 @@ static int run_gemm(const taco_model* m, hipStream_t st, const ConvL* layers, in
     // weight fragment is fetched twice by a workgroup (the 2x2 arrangements of tiles 1-3 fetch each one twice through a 16 KB L1
     // that cannot hold them: measured 20-30 % slower on every large layer, tools/time_gemm_layers.py).
     // a wide dense layer over many rows (the linear head): every workgroup keeps its 64 rows for ALL columns (taco_head.h)
-    bool x6 = (m->bf3x6 && !g_gemm_force_bf3) || (m->bf3 && L0.x6);
-    if (m->head_sweep && !m->bf3_tn && !x6 && nvar == 1 && !dual && L0.kw == 1 && c.mpw <= 1 && !c.gather && !c.res && !c.rev_len && c.rev_col0 < 0 &&
-        c.t_len == 0 && !c.aux0 && !c.aux1 && c.act == ACT_NONE && !L0.bns && a.vec_ok && (L0.cin == 256 || L0.cin == 512) && L0.N >= 512 &&
-        L0.N % 32 == L0.ntail && (L0.ntail == 0 || L0.wtail) && c.M >= 256 && (long)c.M * c.ldo < (1L << 30)) {
+    bool x6 = level == GEMM_BF3X6;
+    if (a.vec_ok && head_sweep_why(m, L0, nvar, dual, c) == FF_WHY_NONE) {
       HeadArgs h;
       memset(&h, 0, sizeof h);
       h.x = c.x; h.ldx = c.ldx; h.bh = a.v[0].bh; h.bl = a.v[0].bl; h.NT = a.v[0].NT; h.K16 = L0.cin / 16; h.bias = a.v[0].bias;
@@ -1384,6 +1407,7 @@ static int bigru_scan(const taco_model* m, hipStream_t st, const Cbhg& c, int B,
 }
 
 // ---- the point-wise tail of a CBHG as one launch (taco_chain.h) ----
+// the widths k_pointwise_chain serves (a term of ff_plan)
 static bool chain_fits(const Cbhg& c, int in_dim) {
   const int W = c.rnn;
   if (W != 128 && W != 256) return false;
@@ -1419,10 +1443,6 @@ static int run_chain(const taco_model* m, hipStream_t st, const Cbhg& c, const f
 }
 
 // ---- conv bank -> max-pool -> proj_1 as one launch (taco_front.h) ----
-static bool front_usable(const taco_model* m, const Cbhg& c) {
-  return m->bf3 && !m->bf3x6 && m->front && m->force_cfg < 0 && !m->bf3_tn && c.front_kind != 0 && !c.proj.empty() && c.proj[0].bh &&
-         c.proj[0].cin == c.K * c.C && c.proj[0].cin_pad16 == c.K * c.C;
-}
 static int run_front(const taco_model* m, hipStream_t st, const Cbhg& c, const float* x, int B, int T, const CbhgWs& w, bool combine, int* P_out) {
   FrArgs a; memset(&a, 0, sizeof a);
   const int TN = c.front_kind == 1 ? 2 : 1, cinp = c.front_kind == 1 ? 80 : 128, kwmax = c.front_kind == 1 ? 8 : 16;
@@ -1493,6 +1513,33 @@ static int run_front(const taco_model* m, hipStream_t st, const Cbhg& c, const f
 // behind a producer of its input frames (the decoder): every stage is advanced as far as the frames
 // available to it allow (a conv needs its right halo; the last chunk gets TF's zero padding).
 struct FfProg { int w_bank = 0, w_p[4] = {0, 0, 0, 0}, w_pt = 0; };
+// ---- which kernels run the feed-forward part of a CBHG that is served in one piece ----
+struct FfPlan {
+  GemmLevel level;          // of the layers that stay launches of their own (k_gemm / k_gemm_bf3, one per layer; the conv bank is one)
+  int front_kind;           // k_cbhg_front: conv bank -> max-pool -> proj_1 as one launch, this instantiation (Cbhg::front_kind); 0: two GEMM launches
+  bool entry;               // the sum of the front's parts, proj_1's epilogue and proj_2 (+ residual) inside the chain's entry: front + chain = 2 launches
+  int chain_w;              // k_pointwise_chain<chain_w>: dense, highways and the hoisted GRU projection as one launch; 0: one launch per layer
+  int launches;
+  FfWhyNot why_front, why_entry, why_chain;      // first reason against each (NONE: used)
+};
+// The one place that decides.  Pure: launches nothing.  A call served chunk by chunk (cbhg_ff_advance with avail < T: taco_debug_set_overlap) runs
+// one launch per layer and chunk whatever the plan says; that term stays with the caller, as overlap_chunk does for the decoder loop.
+static FfPlan ff_plan(const taco_model* m, const Cbhg& c) {
+  const ConvL& P1 = c.proj[0]; const ConvL& P2 = c.proj.back();
+  FfPlan p; memset(&p, 0, sizeof p);
+  p.level = gemm_level(m, P1);
+  p.why_front = ff_fused_why(m, P1);
+  if (!p.why_front) p.why_front = !m->front ? FF_WHY_SWITCH : c.front_kind != 0 && P1.cin == c.K * c.C && P1.cin_pad16 == c.K * c.C ? FF_WHY_NONE : FF_WHY_WIDTHS;
+  p.why_chain = ff_fused_why(m, c.xproj);
+  if (!p.why_chain) p.why_chain = !m->chain ? FF_WHY_SWITCH : chain_fits(c, P2.N) ? FF_WHY_NONE : FF_WHY_WIDTHS;
+  p.why_entry = p.why_front || p.why_chain ? FF_WHY_NEEDS_BOTH : !m->front_entry ? FF_WHY_SWITCH :
+                c.proj.size() == 2 && P2.bh && P2.kw == 3 && P2.cin == P1.N && P2.cin_pad16 == P1.N && P1.N == c.rnn && P2.N <= c.rnn && c.in_dim == P2.N
+                    ? FF_WHY_NONE : FF_WHY_WIDTHS;     // (k16 steps of proj_2: 3 rnn / 16 = a multiple of the entry's block pairs)
+  p.front_kind = p.why_front ? 0 : c.front_kind; p.entry = !p.why_entry; p.chain_w = p.why_chain ? 0 : c.rnn;
+  // front (+ k_front_combine) or bank + proj_1; the other projections; the tail
+  p.launches = (p.entry ? 1 : 2) + ((int)c.proj.size() - (p.entry ? 2 : 1)) + (p.chain_w ? 1 : (c.has_dense ? 1 : 0) + c.depth + 1);
+  return p;
+}
 static int cbhg_ff_advance(const taco_model* m, hipStream_t st, const Cbhg& c, const float* x, int B, int T,
                            const int* lengths, const float* before_highway, const CbhgWs& w, FfProg& pg, int avail,
                            const float** ff_out) {
@@ -1502,12 +1549,10 @@ static int cbhg_ff_advance(const taco_model* m, hipStream_t st, const Cbhg& c, c
   // the whole window at once: bank -> max-pool -> proj_1 as ONE launch, the bank tensor never leaves the CU (taco_front.h)
   // ... and with it proj_1's epilogue and proj_2 (+ residual) move into the entry of the point-wise chain: front + chain = the whole
   // feed-forward part of a CBHG in two launches
-  bool entry = false; int parts = 1;
-  if (avail >= T && pg.w_bank == 0 && pg.w_p[0] == 0 && front_usable(m, c)) {
-    const bool chain_next = m->chain && c.proj.size() == 2 && chain_fits(c, c.proj[1].N);
-    const ConvL& P2 = c.proj.back();
-    entry = chain_next && m->front_entry && P2.bh && P2.kw == 3 && P2.cin == c.proj[0].N && P2.cin_pad16 == c.proj[0].N &&
-            c.proj[0].N == c.rnn && (c.rnn == 128 || c.rnn == 256) && P2.N <= c.rnn && c.in_dim == P2.N;     // (k16 steps of proj_2: 3 rnn / 16 = a multiple of the entry's block pairs)
+  const FfPlan fp = ff_plan(m, c);
+  const bool front = fp.front_kind && avail >= T && pg.w_bank == 0 && pg.w_p[0] == 0, entry = front && fp.entry;      // (all frames in this call: the tail below is whole too)
+  int parts = 1;
+  if (front) {
     TRY(run_front(m, st, c, x, B, T, w, !entry, &parts));
     pg.w_bank = T; pg.w_p[0] = T;
     if (entry) pg.w_p[1] = T;
@@ -1545,8 +1590,7 @@ static int cbhg_ff_advance(const taco_model* m, hipStream_t st, const Cbhg& c, c
   // point-wise chain: optional dense (modules.py:72-73), highway x depth (:76-77), hoisted BiGRU input projection
   const int wlast = pg.w_p[c.proj.size() - 1];
   const int t0 = pg.w_pt, tl = wlast - pg.w_pt;
-  if (entry && !(m->chain && t0 == 0 && tl == T && chain_fits(c, curd))) return fail(TACO_ERR_STATE, "fused chain entry planned but the chain kernel does not apply");
-  if (m->bf3 && !m->bf3x6 && m->chain && m->force_cfg < 0 && !m->bf3_tn && t0 == 0 && tl == T && chain_fits(c, curd)) {
+  if (fp.chain_w && t0 == 0 && tl == T) {
     // the whole tail as ONE launch, activations resident on the CU from layer to layer (taco_chain.h)
     ChainEntry E; memset(&E, 0, sizeof E);
     if (entry) {
@@ -1643,12 +1687,15 @@ static void carve_enc(Carver& cv, const taco_model* m, int B, int T, EncWs& w) {
 // The encoder prenet (modules.py:18-25: two dense + ReLU layers over the looked-up embeddings) as ONE launch of the point-wise chain kernel
 // (taco_chain.h): gathered rows -> planes, a 256-wide ReLU layer, and the second layer as the chain's last link (stored straight to the
 // prenet output).  Two k_gemm_bf3 launches of 11 us each at C2 otherwise -- a 64-row tile of 4096 rows leaves them latency-bound.
-static bool prenet_chain_fits(const taco_model* m) {
+// NONE: that launch; else one GEMM launch per layer.  One answer per forward: the caller asks once and hands it to encoder_forward.
+static FfWhyNot prenet_chain_why(const taco_model* m) {
   const taco_hparams& hp = m->hp;
-  if (!(m->bf3 && !m->bf3x6 && m->chain && m->force_cfg < 0 && !m->bf3_tn) || hp.enc_prenet_n != 2) return false;
+  if (const FfWhyNot why = ff_fused_why(m, m->enc_prenet[0])) return why;
+  if (!m->chain) return FF_WHY_SWITCH;
+  if (hp.enc_prenet_n != 2) return FF_WHY_WIDTHS;
   const ConvL& a = m->enc_prenet[0]; const ConvL& b = m->enc_prenet[1];
-  return a.bh && b.bh && a.kw == 1 && b.kw == 1 && a.N == 256 && a.cin == hp.embedding_size && a.cin_pad16 <= 256 && (hp.embedding_size & 3) == 0 &&
-         b.cin == 256 && b.N == hp.enc_prenet[1] && a.var_index >= 0 && b.var_index >= 0;
+  return b.bh && a.kw == 1 && b.kw == 1 && a.N == 256 && a.cin == hp.embedding_size && a.cin_pad16 <= 256 && (hp.embedding_size & 3) == 0 &&
+         b.cin == 256 && b.N == hp.enc_prenet[1] && a.var_index >= 0 && b.var_index >= 0 ? FF_WHY_NONE : FF_WHY_WIDTHS;
 }
 // riders (nullable): regions the launch's spare workgroups clear -- the words the persistent kernels of the same forward poll (forward_enqueue)
 static int run_prenet_chain(const taco_model* m, hipStream_t st, const int* ids, int M, float* out, const ZeroRegions* riders) {
@@ -1674,14 +1721,15 @@ static int run_prenet_chain(const taco_model* m, hipStream_t st, const int* ids,
   if (riders) register_cleared(*riders);      // the riders are in the stream now: the persistent kernels behind this launch need no fill of their own
   return 0;
 }
-// riders: see run_prenet_chain; only passed where prenet_chain_fits(m) (the caller clears the regions itself otherwise)
+// prenet_chain: prenet_chain_why(m) == NONE, asked once by the caller; riders: see run_prenet_chain -- they travel in that launch only (the caller
+// clears the regions itself otherwise)
 static int encoder_forward(const taco_model* m, hipStream_t st, const int* ids, const int* lengths, const int* speaker_id,
-                           int B, int T, float* enc_out, const EncWs& w, bool spk_done, const ZeroRegions* riders = nullptr) {
+                           int B, int T, float* enc_out, const EncWs& w, bool spk_done, bool prenet_chain, const ZeroRegions* riders = nullptr) {
   const taco_hparams& hp = m->hp;
   const int M = B * T;
   if (is_deepvoice(m) && !spk_done) TRY(spk_forward(m, st, speaker_id, B, w.spk));
   const float* cur = AP(m, m->emb); int curd = hp.embedding_size;
-  if (prenet_chain_fits(m)) {
+  if (prenet_chain) {
     TRY(run_prenet_chain(m, st, ids, M, w.pre[1], riders));
     return cbhg_forward(m, st, m->enc, w.pre[1], B, T, lengths, is_deepvoice(m) ? w.spk.vec[0] : nullptr,
                         is_deepvoice(m) ? w.spk.vec[1] : nullptr, enc_out, w.cb);
@@ -2072,6 +2120,7 @@ static int forward_pass(taco_model* m, hipStream_t st, const int32_t* ids, const
   if (!cv.ok()) return fail(TACO_ERR_STATE, "workspace too small: need %zu bytes, have %zu", cv.off, ws_bytes);
   const int r = m->hp.reduction_factor, T_mel = n * r;
   const int CH = overlap_chunk(m, n);
+  const bool ride = prenet_chain_why(m) == FF_WHY_NONE;      // the encoder prenet as the chain launch: asked once per forward
   if (!CH) {
     // every word a persistent kernel polls and the stop flags, cleared by ONE launch in front of the forward; the stop rule and the
     // error latch are ONE launch behind it (11 graph nodes at C2 with the clears riding in the prenet launch; 13 in round 4, 20 in round 3)
@@ -2082,15 +2131,14 @@ static int forward_pass(taco_model* m, hipStream_t st, const int32_t* ids, const
     z.p[3] = (uint32_t*)w.enc.cb.gxbuf; z.nw[3] = ((size_t)((char*)w.enc.cb.gxctl - (char*)w.enc.cb.gxbuf) + 256) / 4;     // (an encoder of width 256 scans on k_bigru_duo too)
     // (they ride in the encoder prenet's launch where that is the chain kernel -- the first launch of the forward, with CUs to spare)
     // The regions count as cleared (zero_async then skips its own fill) only from the point where the launch that clears them HAS been
-    // enqueued: here for the fill kernel, inside run_prenet_chain for the riders -- never on the strength of a predicate evaluated twice.
+    // enqueued: here for the fill kernel, inside run_prenet_chain for the riders.
     struct Guard { Guard() { g_cleared.cnt = 0; } ~Guard() { g_cleared.cnt = 0; } } guard;
-    const bool ride = prenet_chain_fits(m);
     if (!ride) {
       hipLaunchKernelGGL(k_zero_fill_multi, dim3(256, 4), dim3(256), 0, st, z);
       HIPCHK(hipGetLastError());
       register_cleared(z);
     }
-    TRY(encoder_forward(m, st, ids, lengths, spk, B, T_in, w.enc_out, w.enc, false, ride ? &z : nullptr));
+    TRY(encoder_forward(m, st, ids, lengths, spk, B, T_in, w.enc_out, w.enc, false, ride, ride ? &z : nullptr));
     TRY(decoder_forward(m, st, w.enc_out, spk, B, T_in, n, manual, nullptr, mel, align, nullptr, nullptr, w.dec, true, &w.enc.spk));
     TRY(postnet_forward(m, st, mel, spk, B, T_mel, linear, nullptr, w.post));
     if (stop) {
@@ -2099,7 +2147,7 @@ static int forward_pass(taco_model* m, hipStream_t st, const int32_t* ids, const
     }
     return 0;
   }
-  TRY(encoder_forward(m, st, ids, lengths, spk, B, T_in, w.enc_out, w.enc, false));
+  TRY(encoder_forward(m, st, ids, lengths, spk, B, T_in, w.enc_out, w.enc, false, ride));
   // The decoder loop is a chain of tiny dependent launches that occupies < 1/5 of the CUs; the post-net's
   // feed-forward stages (conv bank, projections, highways, hoisted GRU projection: ~1.3 ms of fp32 MFMA work @C2)
   // need only frames that already exist plus a conv halo.  They run on a second stream, one chunk of CH steps
@@ -2683,10 +2731,44 @@ int taco_model_engine_plan(taco_model* m, int B, int T_in, int T_mel, int flags,
     else s += std::string("; encoder scan: ") + scan_kernel_name(sp.kernel);
     s += "; feed-forward: ";
   }
-  s += m->bf3 ? "split-bf16 MFMA (k_gemm_bf3 / k_pointwise_chain)" : "exact-fp32 MFMA (k_gemm)";
-  if (!m->tp) s += prenet_chain_fits(m) ? "; encoder prenet: one k_pointwise_chain launch (embedding rows gathered, both layers; the forward's zero fills ride in it)"
-                                        : "; encoder prenet: one GEMM launch per layer";
-  else {        // the training step's backward scans (taco_train.h: cbhg_backward)
+  // the feed-forward launches, from the plans cbhg_ff_advance, forward_pass and run_gemm themselves follow (ff_plan, prenet_chain_why, head_sweep_why);
+  // a training forward (taco_train.h) runs every layer as a launch of its own, between its BatchNorm passes
+  const int chunk = m->tp || (flags & 6) ? 0 : overlap_chunk(m, n);
+  auto gemm_name = [](GemmLevel lv) { return lv == GEMM_BF3 ? "k_gemm_bf3" : lv == GEMM_BF3X6 ? "k_gemm_bf3<..., X6>" : "k_gemm"; };
+  auto launches = [](int k) { return std::to_string(k) + (k == 1 ? " launch" : " launches"); };
+  auto ff_why = [&](const char* kernel, FfWhyNot why, int bit, const char* widths = "widths outside the presets") -> std::string {
+    static const char* const words[] = {"", "exact fp32 is switched on", "the six-product level has no fused kernels", "taco_debug_force_gemm_config", "a k_gemm_bf3 tile is forced"};
+    return std::string(" -- no ") + kernel + ": " + (why == FF_WHY_SWITCH ? "taco_debug_set_bf3 bit " + std::to_string(bit) : why == FF_WHY_WIDTHS ? std::string(widths) : std::string(words[why]));
+  };
+  auto cbhg_ff = [&](const char* name, const Cbhg& c, bool chunked) -> std::string {
+    const FfPlan fp = ff_plan(m, c);
+    const int per_layer = 1 + (int)c.proj.size() + (c.has_dense ? 1 : 0) + c.depth + 1;
+    std::string r = std::string("; ") + name + " CBHG: ";
+    if (m->tp) return r + launches(per_layer) + " of " + gemm_name(fp.level) + ", one per layer";
+    if (chunked) return r + launches(per_layer) + " of " + gemm_name(fp.level) + " per chunk, one per layer (taco_debug_set_overlap)";
+    r += launches(fp.launches) + ": ";
+    r += fp.front_kind == 1 ? "k_cbhg_front<2, 80, 80, 8>" : fp.front_kind ? "k_cbhg_front<1, 144, 128, 16>" : std::string("conv bank and proj_1 on ") + gemm_name(fp.level);
+    if (fp.front_kind && !fp.entry) r += " + k_front_combine";
+    if (const int np = (int)c.proj.size() - (fp.entry ? 2 : 1)) r += ", " + std::to_string(np) + (np == 1 ? " projection on " : " projections on ") + gemm_name(fp.level);
+    if (fp.chain_w) r += ", k_pointwise_chain<" + std::to_string(fp.chain_w) + ">" + (fp.entry ? " (the last projection in its entry)" : "");
+    else r += ", " + std::to_string(fp.launches - 1 - (int)c.proj.size()) + " point-wise layers on " + gemm_name(fp.level);
+    if (fp.why_front) r += ff_why("k_cbhg_front", fp.why_front, 3);
+    if (fp.why_chain) r += ff_why("k_pointwise_chain", fp.why_chain, 2);
+    if (fp.why_entry && fp.why_entry != FF_WHY_NEEDS_BOTH) r += ff_why("fused chain entry", fp.why_entry, 4);
+    return r;
+  };
+  { const GemmLevel lv = gemm_level(m, m->linear);
+    s += lv == GEMM_BF3 ? "split-bf16 MFMA, three products (k_gemm_bf3 and the fused kernels)" : lv == GEMM_BF3X6 ? "split-bf16 MFMA, six products (k_gemm_bf3<..., X6>: fp32-grade)" : "exact-fp32 MFMA (k_gemm)";
+    s += cbhg_ff("encoder", m->enc, false) + cbhg_ff("post-net", m->post, chunk != 0);
+    const FfWhyNot pw = prenet_chain_why(m);
+    if (!m->tp && !pw) s += std::string("; encoder prenet: one k_pointwise_chain launch (1 launch: embedding rows gathered, both layers") + (chunk ? ")" : "; the forward's zero fills ride in it)");
+    else s += "; encoder prenet: one GEMM launch per layer (" + launches(m->hp.enc_prenet_n) + " of " + gemm_name(gemm_level(m, m->enc_prenet[0])) +
+              (m->tp ? ")" : std::string(chunk ? "" : " + 1 launch of k_zero_fill_multi in front: the forward's zero fills") + ff_why("k_pointwise_chain", pw, 2) + ")");
+    GemmCall g; g.ldx = 2 * m->hp.post_rnn_size; g.M = B * T_mel; g.ldo = m->hp.num_freq;      // the call of postnet_tail (and of the training forward)
+    const FfWhyNot hw = head_sweep_why(m, m->linear, 1, false, g);
+    s += std::string("; linear head: 1 launch of ") + (hw ? gemm_name(lv) + ff_why("k_head_sweep", hw, 5, "it serves 256 rows and more, 256 or 512 inputs, 512 columns and more") :
+                                                                m->linear.cin == 512 ? "k_head_sweep<512>" : "k_head_sweep<256>"); }
+  if (m->tp) {        // the training step's backward scans (taco_train.h: cbhg_backward)
     const Cbhg& c = m->post;
     const ScanBwd bwd = scan_plan(m, c, B, T_mel).bwd;
     s += std::string("; backward scans: post-net ") + (bwd == SCAN_BWD_OCT ? "k_bigru_oct_bwd (one row per cluster of 8 CUs)" : bwd == SCAN_BWD_DUO ? "k_bigru_duo_bwd" : "k_bigru_rows_bwd") +
@@ -2823,7 +2905,7 @@ int taco_encoder_forward(taco_model* m, void* hip_stream, const int32_t* d_input
   Carver cv(d_workspace, workspace_bytes);
   EncWs w; carve_enc(cv, m, B, T_in, w);
   if (!cv.ok()) return fail(TACO_ERR_STATE, "workspace too small: need %zu bytes", cv.off);
-  return encoder_forward(m, (hipStream_t)hip_stream, d_inputs, d_input_lengths, d_speaker_id, B, T_in, d_encoder_out, w, false);
+  return encoder_forward(m, (hipStream_t)hip_stream, d_inputs, d_input_lengths, d_speaker_id, B, T_in, d_encoder_out, w, false, prenet_chain_why(m) == FF_WHY_NONE);
 }
 
 int taco_decoder_forward(taco_model* m, void* hip_stream, const float* d_encoder_out, const int32_t* d_speaker_id, int B,

@@ -437,7 +437,8 @@ static int run_dgrad(const taco_model* m, hipStream_t st, const ConvL& Ld, const
 // ---------------------------------------------------------------------------------------------------------------
 // tape layout
 // ---------------------------------------------------------------------------------------------------------------
-// BatchNorm + max-pool of a conv bank as one pass (k_bn_pool_bank_v4): the widths fit the pointer table and the columns go four at a time
+// BatchNorm + max-pool of a conv bank as one pass (k_bn_pool_bank_v4): the widths fit the pointer table and the columns go four at a time.
+// The tape layout, the forward and the backward read this alone; the 16-byte alignment the pass needs is the workspace's (train_forward_backward refuses another)
 static inline bool bank_pool_fused(const Cbhg& c) { return c.K <= BNB_MAXK && (c.C & 3) == 0; }
 struct CbhgTape {
   float *bank_a, *bank_y, *pool, *bank_mu, *bank_rs;
@@ -623,7 +624,7 @@ static int cbhg_forward_train(const TrainCtx& x, const Cbhg& c, const CbhgT& ct,
     // column block k-1 of the concatenation belongs to conv1d_k (modules.py:35-44)
     for (int k = 1; k <= c.K; ++k) { names.push_back(sc + "/conv_bank/conv1d_" + std::to_string(k)); cols.push_back(c.C); }
     TRY(bn_stats(x, w.bank_a, KC, M, KC, w.bank_mu, w.bank_rs, w.stat, names.data(), cols.data(), c.K));
-    if (bank_pool_fused(c) && al16h(w.bank_a) && al16h(w.pool)) {      // BatchNorm of all widths + the max-pool in ONE pass: the BatchNorm output is never stored (k_bn_pool_bank_v4)
+    if (bank_pool_fused(c)) {      // BatchNorm of all widths + the max-pool in ONE pass: the BatchNorm output is never stored (k_bn_pool_bank_v4)
       BnBank nb; memset(&nb, 0, sizeof nb); nb.Cw = c.C;
       for (int k = 1; k <= c.K; ++k) { nb.gamma[k - 1] = x.p(names[k - 1] + "/gamma"); nb.beta[k - 1] = x.p(names[k - 1] + "/beta"); }
       hipLaunchKernelGGL(k_bn_pool_bank_v4, EWGRID((size_t)M * KC / 4), 0, st, (const float*)w.bank_a, KC, (const float*)w.bank_mu, (const float*)w.bank_rs, nb, w.pool, KC, M, T, KC, c.maxpool);
@@ -841,7 +842,7 @@ static int cbhg_backward(const TrainCtx& x, const Cbhg& c, const CbhgT& ct, cons
     if (i > 0) { /* dnext == dcur already holds the gradient of py[i-1] */ }
   }
   // ---- maxpool + conv bank ----
-  if (bank_pool_fused(c) && al16h(w.bank_a) && al16h(w.pool)) {      // (the forward's test: the pool's input is recomputed from the bank's activations)
+  if (bank_pool_fused(c)) {      // (the forward's test: the pool's input is recomputed from the bank's activations)
     BnBank nb; memset(&nb, 0, sizeof nb); nb.Cw = c.C;
     for (int k = 1; k <= c.K; ++k) { const std::string n = sc + "/conv_bank/conv1d_" + std::to_string(k); nb.gamma[k - 1] = x.p(n + "/gamma"); nb.beta[k - 1] = x.p(n + "/beta"); }
     hipLaunchKernelGGL(k_maxpool_bwd_bn_v4, EWGRID((size_t)M * KC / 4), 0, st, (const float*)w.bank_a, KC, (const float*)w.bank_mu, (const float*)w.bank_rs, nb, (const float*)w.dbig0, w.dbig1, M, T, KC, c.maxpool);
@@ -1200,6 +1201,7 @@ static int train_forward_backward(taco_train* t, hipStream_t st, float* P, float
   const int n = T_out / r;
   if (n > hp.max_iters) return fail(TACO_ERR_SHAPE, "T_out/r = %d exceeds max_iters %d", n, hp.max_iters);
   TRY(check_common(m, B, T_in));
+  if (!al16h(ws)) return fail(TACO_ERR_ARG, "workspace %p is not 16-byte aligned (the tape is carved in 256-byte steps from it; its four-column kernels need the alignment)", ws);
   struct EngineGuard {  // the GEMM helpers see this trainer's engine switches for the duration of this step only
     int w, d, e, p;
     EngineGuard(const taco_train* t) : w(g_wgrad_bf3), d(g_dgrad_bf3), e(g_dgrad_exact), p(g_wgrad_planes) { g_wgrad_bf3 = t->wgrad_bf3; g_dgrad_bf3 = t->dgrad_bf3; g_dgrad_exact = t->dgrad_exact; g_wgrad_planes = t->wgrad_planes; }

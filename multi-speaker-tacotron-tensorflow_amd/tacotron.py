@@ -591,10 +591,10 @@ class Tacotron(object):
         (widths, rows per launch, LDS, compute units of the device, debug switches).  Nothing is launched; PlanPool(lanes > 1) additionally
         switches its lanes to the launch-per-stage engine (two whole-chip kernels cannot share the chip).  teacher / debug: the plan of a
         decoder() call with teacher_frames / debug=True."""
-        buf = C.create_string_buffer(1024)
+        buf = C.create_string_buffer(4096)
         t_mel = t_mel if t_mel is not None else self._hparams.max_iters * self._hparams.reduction_factor
         flags = (1 if manual else 0) | (2 if teacher else 0) | (4 if debug else 0)
-        _lib.check(self._lib.taco_model_engine_plan(self._handle, int(batch), int(t_in), int(t_mel), flags, buf, 1024))
+        _lib.check(self._lib.taco_model_engine_plan(self._handle, int(batch), int(t_in), int(t_mel), flags, buf, 4096))
         return buf.value.decode()
 
     def decoder_trace(self, enable=True, read=False, scan=False):

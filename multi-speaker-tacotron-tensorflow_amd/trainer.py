@@ -191,8 +191,8 @@ class Trainer(object):
         """One line saying which kernels a training step of this shape runs on (decoder loop and its backward loop, scans), and why not the
         persistent whole-chip ones where it does not; set_bptt_engine(False) is this trainer's own switch and not in it.  Nothing is launched."""
         mh = C.c_void_p(self._lib.taco_train_model(self._h))
-        buf = C.create_string_buffer(1024)
-        _lib.check(self._lib.taco_model_engine_plan(mh, int(batch), int(t_in), int(t_mel), 0, buf, 1024))
+        buf = C.create_string_buffer(4096)
+        _lib.check(self._lib.taco_model_engine_plan(mh, int(batch), int(t_in), int(t_mel), 0, buf, 4096))
         return buf.value.decode()
 
     def raise_device_error_for_test(self, value=2):

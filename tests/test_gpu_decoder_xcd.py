@@ -542,6 +542,136 @@ def test_engine_plan_agrees_with_a_training_step(mode):
     assert mode == 1 or (info["protocol"] == 0 and plan.count("one launch per stage -- switched off") == 2), (info, plan)
 
 
+def _ff_clauses(plan):
+    """The feed-forward clauses of an engine_plan sentence by name, and the launches they state in all."""
+    import re
+    ff = plan.split("; feed-forward: ")[1].split("; backward scans: ")[0]
+    clauses = {c.split(": ")[0]: c for c in re.split(r"; (?=(?:encoder CBHG|post-net CBHG|encoder prenet|linear head): )", "feed-forward: " + ff)}
+    assert sorted(clauses) == ["encoder CBHG", "encoder prenet", "feed-forward", "linear head", "post-net CBHG"], plan
+    return clauses, sum(int(k) for k in re.findall(r"(\d+) launch", ff))
+
+
+FF_MODES = {   # taco_debug_set_bf3(on): words that include/taco_debug.h documents for the mode, and words that must be absent
+    1: (["three products", "k_cbhg_front<1, 144, 128, 16>", "k_cbhg_front<2, 80, 80, 8>", "k_pointwise_chain<128> (the last projection in its entry)",
+         "k_pointwise_chain<256> (the last projection in its entry)", "encoder prenet: one k_pointwise_chain launch", "k_head_sweep<512>"], [" -- no ", "k_front_combine"]),
+    5: (["no k_pointwise_chain: taco_debug_set_bf3 bit 2", "point-wise layers on k_gemm_bf3", "k_cbhg_front<", "k_front_combine", "1 projection on k_gemm_bf3",
+         "encoder prenet: one GEMM launch per layer", "k_zero_fill_multi", "k_head_sweep<512>"], ["k_pointwise_chain<"]),
+    9: (["conv bank and proj_1 on k_gemm_bf3", "no k_cbhg_front: taco_debug_set_bf3 bit 3", "k_pointwise_chain<256>", "encoder prenet: one k_pointwise_chain launch"],
+        ["k_cbhg_front<", "k_front_combine", "in its entry"]),
+    17: (["k_cbhg_front<1, 144, 128, 16> + k_front_combine", "no fused chain entry: taco_debug_set_bf3 bit 4", "k_pointwise_chain<256>"], ["in its entry"]),
+    33: (["linear head: 1 launch of k_gemm_bf3 -- no k_head_sweep: taco_debug_set_bf3 bit 5", "k_cbhg_front<", "in its entry"], ["k_head_sweep<"]),
+    65: (["six products (k_gemm_bf3<..., X6>", "conv bank and proj_1 on k_gemm_bf3<..., X6>", "point-wise layers on k_gemm_bf3<..., X6>", "the six-product level has no fused kernels",
+          "encoder prenet: one GEMM launch per layer", "linear head: 1 launch of k_gemm_bf3<..., X6>"], ["k_cbhg_front<", "k_pointwise_chain<", "k_head_sweep<", "three products"]),
+    0: (["exact-fp32 MFMA (k_gemm)", "conv bank and proj_1 on k_gemm,", "point-wise layers on k_gemm ", "exact fp32 is switched on", "encoder prenet: one GEMM launch per layer",
+         "linear head: 1 launch of k_gemm "], ["k_gemm_bf3", "k_cbhg_front<", "k_pointwise_chain<", "k_head_sweep<", "split-bf16"]),
+}
+
+
+def test_feed_forward_plan_agrees_with_the_launches():
+    """ff_plan / prenet_chain_why / head_sweep_why (csrc/taco_lib.hip) are what the launches follow and what engine_plan words.  There is no
+    protocol word for feed-forward kernels, but a captured plan counts its kernel nodes: in every taco_debug_set_bf3 mode the node count moves
+    against mode 1 by exactly the launches the sentence states, and the sentence names the kernels include/taco_debug.h documents for the
+    mode.  Then a model outside the presets: one launch per layer, with the reason.  (Overlap mode is left out: its graph has event nodes.)"""
+    from util import tiny_hp
+    B, T_in = 8, 24
+    ohp = O.OracleHParams(max_iters=16)
+    assert B * ohp.max_iters * ohp.reduction_factor >= 256          # (the head sweep serves 256 rows and more)
+    m = build_model(ohp, O.init_weights(ohp, 1, 451))
+    nodes, stated = {}, {}
+    for mode in (1, 5, 9, 17, 33, 65, 0, 1):
+        m._lib.taco_debug_set_bf3(m._handle, mode, 0)
+        m._plans.clear()                                             # a captured plan keeps the kernels it was captured with
+        plan = m.engine_plan(B, T_in)
+        clauses, count = _ff_clauses(plan)
+        n = m.plan_for(B, T_in).num_nodes
+        print(mode, n, count, plan.split("; feed-forward: ")[1])
+        assert nodes.setdefault(mode, n) == n and stated.setdefault(mode, count) == count, (mode, n, count)      # (mode 1 twice: the hook leaves nothing behind)
+        ff = "; ".join(clauses[k] for k in ("feed-forward", "encoder CBHG", "post-net CBHG", "encoder prenet", "linear head")) + " "
+        present, absent = FF_MODES[mode]
+        assert all(w in ff for w in present) and not any(w in ff for w in absent), (mode, ff)
+    m.check_device_errors()
+    for mode in nodes:
+        assert nodes[mode] - nodes[1] == stated[mode] - stated[1], (mode, nodes, stated)
+    assert stated[1] == 2 + 2 + 1 + 1 and len(set(nodes.values())) >= 3, (nodes, stated)      # front + chain per CBHG, prenet, head; the modes do move the count
+    # outside the presets: every layer a launch of its own
+    thp = tiny_hp()
+    t = build_model(thp, O.init_weights(thp, 1, 452))
+    tn = {}
+    for mode in (1, 0):
+        t._lib.taco_debug_set_bf3(t._handle, mode, 0)
+        t._plans.clear()
+        clauses, count = _ff_clauses(t.engine_plan(3, 9))
+        tn[mode] = (t.plan_for(3, 9).num_nodes, count)
+        print(mode, tn[mode], clauses)
+        kernel = "k_gemm_bf3" if mode else "k_gemm"
+        for name in ("encoder CBHG", "post-net CBHG"):
+            assert "conv bank and proj_1 on " + kernel in clauses[name] and "point-wise layers on " + kernel in clauses[name], clauses
+            assert ("no k_cbhg_front: widths outside the presets" in clauses[name] and "no k_pointwise_chain: widths outside the presets" in clauses[name]) == (mode == 1), clauses
+        assert "one GEMM launch per layer" in clauses["encoder prenet"] and "linear head: 1 launch of " + kernel + " -- no k_head_sweep: " in clauses["linear head"], clauses
+    assert tn[1] == tn[0], tn
+    t.check_device_errors()
+
+
+def test_engine_plan_tells_a_training_shadow_model_its_gemm_level():
+    """A trainer's forward GEMMs run on the six-product split by default (taco_train_set_exact_gemm mode 4), one launch per layer, and on
+    k_gemm after set_exact_gemm(1): Trainer.engine_plan names the level and the kernel of each (it said k_gemm for both)."""
+    import taco_amd
+    from util import to_product_hp
+    hp = O.OracleHParams(max_iters=4)
+    tr = taco_amd.Trainer(to_product_hp(hp), O.init_weights(hp, 1, 461))
+    clauses, _ = _ff_clauses(tr.engine_plan(6, 11, 4 * hp.reduction_factor))
+    print(clauses)
+    assert "six products (k_gemm_bf3<..., X6>" in clauses["feed-forward"], clauses
+    for name in ("encoder CBHG", "post-net CBHG", "encoder prenet", "linear head"):
+        assert "of k_gemm_bf3<..., X6>" in clauses[name] and "k_cbhg_front" not in clauses[name] and "k_pointwise_chain" not in clauses[name], clauses
+    tr.set_exact_gemm(1)
+    clauses, _ = _ff_clauses(tr.engine_plan(6, 11, 4 * hp.reduction_factor))
+    print(clauses)
+    assert "exact-fp32 MFMA (k_gemm)" in clauses["feed-forward"], clauses
+    assert all("of k_gemm" in c and "k_gemm_bf3" not in c for k, c in clauses.items() if k != "feed-forward"), clauses
+    tr.close()
+
+
+def test_training_step_refuses_a_misaligned_workspace():
+    """taco_train_forward_backward with the workspace pointer advanced by 4 bytes: TACO_ERR_ARG that names the alignment, before anything is
+    enqueued (the tape's four-column kernels rely on the 16-byte alignment of what Carver hands out); the next, aligned step of the same
+    trainer equals the step of a fresh trainer to the bit."""
+    import torch
+    import taco_amd
+    from util import to_product_hp
+    n, B, T_in = 3, 4, 9
+    hp = O.OracleHParams(max_iters=n)
+    w = O.init_weights(hp, 1, 471)
+    ids, L = O.synthetic_inputs(B, T_in, 472, ragged=True)
+    rs = np.random.RandomState(473)
+    T_out = n * hp.reduction_factor
+    batch = (ids, L, rs.rand(B, T_out, hp.num_mels).astype(np.float32), rs.rand(B, T_out, hp.num_freq).astype(np.float32), np.ones(B, np.float32))
+    tr = taco_amd.Trainer(to_product_hp(hp), w)
+    nb = int(tr._lib.taco_train_workspace_bytes(tr._h, B, T_in, T_out))
+    big = torch.empty(nb + 64, dtype=torch.uint8, device=tr.device)
+    assert big.data_ptr() % 16 == 0
+    tr._ws = big[4:]                                     # large enough, so forward_backward hands it on as it is
+    assert tr._ws.data_ptr() % 16 == 4 and tr._ws.numel() >= nb
+    before = tr.params.clone()
+    with pytest.raises(taco_amd._lib.TacoError) as e:
+        tr.forward_backward(*batch)
+    assert e.value.code == taco_amd._lib.TACO_ERR_ARG and "not 16-byte aligned" in str(e.value), str(e.value)
+    torch.cuda.synchronize()
+    tr.check_device_errors()
+    assert torch.equal(tr.params, before)
+    tr._ws = None
+    fresh = taco_amd.Trainer(to_product_hp(hp), w)
+    outs = []
+    for t in (tr, fresh):
+        step, loss = t.train_step(*batch)
+        torch.cuda.synchronize()
+        t.check_device_errors()
+        outs.append((step, float(loss), t.grads.cpu().numpy().copy(), t.params.cpu().numpy().copy()))
+    assert outs[0][0] == outs[1][0] == 1 and outs[0][1] == outs[1][1] and np.isfinite(outs[0][1])
+    assert np.array_equal(outs[0][2], outs[1][2]) and np.array_equal(outs[0][3], outs[1][3])
+    tr.close(); fresh.close()
+
+
 def test_decoder_engine_hook_refuses_other_rows_per_group():
     """taco_debug_set_decoder_persist accepts 0 (automatic), 1, 2, 4, 8 rows per group; any other number is TACO_ERR_ARG and changes
     nothing: the model still decodes, on the engine and rows it had."""
