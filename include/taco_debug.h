@@ -25,9 +25,11 @@ extern "C" {
 int taco_debug_set_persistent(taco_model* m, int on);
 
 /* test hook: on = 1 (default) runs the feed-forward GEMMs of inference on the bf16 matrix cores with 3-term split
- * operands (fp32-grade accuracy, ~1e-5); 0 = exact-fp32 MFMA everywhere.  tile_n: 0 auto, 1 = 128x64, 2 = 128x128,
- * 3 = 64x256 (2x2 waves), 4 = 64x64, 5 = 64x64 with four wave groups splitting K inside the workgroup, 7 = 64x256 by 1x8 waves,
- * 9 = 64x128 by 1x4 waves, 10 = tile 7 with two wave groups splitting K, 11 = 128x256 by 1x8 waves (auto picks 4 / 5 / 7 / 9 / 10 / 11).
+ * operands (fp32-grade accuracy, ~1e-5); 0 = exact-fp32 MFMA everywhere.  tile_n: 0 auto, 4 = 64x64, 5 = 64x64 with four wave groups
+ * splitting K inside the workgroup, 7 = 64x256 by 1x8 waves, 9 = 64x128 by 1x4 waves, 10 = tile 7 with two wave groups splitting K (auto
+ * picks among these five).  Any other tile_n -- the retired tiles 1, 2, 3 and 11 included -- is TACO_ERR_ARG and changes nothing, `on` included.
+ * A forced tile that a launch has no instantiation for is answered by gemm_plan (csrc/taco_lib.hip): tile 10 exists at three products for
+ * one weight matrix only, so a highway layer or a six-product launch under it runs tile 7; a six-product highway layer under tile 5 runs tile 4.
  * on bit 2 (on = 5): the point-wise tail of a CBHG ([dense ->] highway x depth -> BiGRU input projection; modules.py:72-96) runs as
  * one launch per layer instead of ONE launch with the activations resident on the CU (csrc/taco_chain.h, the default with on = 1).
  * on bit 3 (on = 9): conv bank and proj_1 of a CBHG as two launches instead of the fused front (csrc/taco_front.h).
@@ -38,7 +40,7 @@ int taco_debug_set_persistent(taco_model* m, int on);
  * products on the bf16 pipe), one launch per layer: the fused kernels (front, chain, head sweep) are three-product kernels and stay out.
  * Ignored on a training shadow model (taco_train_set_exact_gemm picks its level).
  * A forced tile, a forced k_gemm config (taco_debug_force_gemm_config) and on = 0 switch all fused kernels off too.  Which kernels a call
- * then gets: ff_plan, prenet_chain_why and head_sweep_why (csrc/taco_lib.hip), told by taco_model_engine_plan. */
+ * then gets: ff_plan, prenet_chain_why, head_sweep_why and gemm_plan (csrc/taco_lib.hip), told by taco_model_engine_plan. */
 int taco_debug_set_bf3(taco_model* m, int on, int tile_n);
 
 /* test hook: > 0 = taco_forward_infer runs the post-net feed-forward stages behind the decoder on a second stream
@@ -88,7 +90,8 @@ int taco_debug_set_skip_scans(taco_model* m, int on);
  * taco_abi.h); two persistent forwards on different streams then starve each other until their bounded spins report a device fault */
 int taco_debug_set_chip_turns(int on);
 
-/* test hook: force the k_gemm tile configuration (0: 128x64, 1: 64x64, 2: 32x64 split-K, 3: 128x128; -1 auto) */
+/* test hook: force the exact-fp32 k_gemm and its tile configuration (1: 64x64, 2: 32x64 split-K; -1: the model's level, automatic choice).
+ * Any other value -- the retired configs 0 and 3 included -- is TACO_ERR_ARG and changes nothing. */
 int taco_debug_force_gemm_config(taco_model* m, int cfg);
 
 /* tuning hook of k_cbhg_front (csrc/taco_front.h: conv bank -> max-pool -> proj_1 as one launch): the second K half of every workgroup

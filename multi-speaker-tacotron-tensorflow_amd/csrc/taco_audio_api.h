@@ -47,6 +47,7 @@ int taco_gl_create(const taco_audio_hparams* hp, int device, taco_gl** out) {
     v.bh = (const unsigned short*)AP(gm, (size_t)v.bh); v.bl = (const unsigned short*)AP(gm, (size_t)v.bl); v.bh2 = nullptr; v.bl2 = nullptr;
   }
   gm->harena.clear(); gm->harena.shrink_to_fit();
+  if (const int rc = gemm_set_attributes()) { (void)hipFree(gm->darena); delete gm; delete g; return rc; }      // (this model does not pass through taco_model_finalize)
   gm->finalized = true;
   *out = g;
   return 0;

@@ -384,7 +384,7 @@ __device__ long long taco_trace[64];
 // lo*lo, lo*hi, hi*lo, hi*hi, as k_wgrad_bf3 -- i.e. fp32-grade products on the bf16 pipe (2^-24 per product instead of 2^-16): the
 // forward GEMMs of the TRAINING step, whose ReLU / max-pool decisions must not differ from fp32's (taco_train_set_exact_gemm mode 4).
 template <int WM, int WN, int TM, int TN, bool DUAL, int GPI, int KS = 1, bool X6 = false>
-__global__ __launch_bounds__(64 * WM * WN * KS, (KS == 1 && GPI == 1 && TM < 4 && !X6 && !(DUAL && TM * TN >= 4)) ? 2 : 1) void k_gemm_bf3(const GemmArgs a_in) {
+__global__ __launch_bounds__(64 * WM * WN * KS, (KS == 1 && GPI == 1 && !X6) ? 2 : 1) void k_gemm_bf3(const GemmArgs a_in) {
   constexpr int NTHR = 64 * WM * WN * KS;
   constexpr int NPL = X6 ? 3 : 2;                                  // planes of a staged tile
   constexpr int SUBSZ = NPL * (WM * TM * 32 + 15) * BF3_LDSW;     // bf16 elements of one sub-chunk tile (hi plane, then lo plane[, then l3])

@@ -42,7 +42,7 @@ static int fail(int code, const char* fmt, ...) {
 // ------------------------------------------------------------------------------------------------
 // one whole-chip kernel at a time per device and process
 // ------------------------------------------------------------------------------------------------
-// The persistent kernels (k_decoder_xcd, k_bigru_oct / duo / xcd and their backward twins) need all 256 workgroups resident at once.  Two of them
+// The persistent kernels (k_decoder_xcd, k_bigru_oct / duo and their backward twins) need all 256 workgroups resident at once.  Two of them
 // dispatched to one device together -- two models or plans of ONE process on different streams or threads -- can each end up waiting for compute
 // units the other one holds until their bounded spins expire.  A ChipTurn in the scope of every such launch (and of every replay of a plan that
 // contains one) puts them in a total order: under a per-device mutex, a launch on ANOTHER stream than the previous whole-chip launch first records
@@ -250,13 +250,13 @@ struct taco_model {
   size_t att_v = 0, att_b = 0, att_sb = 0, emb = 0, spk_emb = 0, raw_wq = 0;
   std::vector<SkW> spk_dense;      // deepvoice: before_highway, enc_init, att_init, dec_init_i
   std::vector<size_t> spk_table;   // speaker_embedding_size == 1 variant
-  int force_cfg = -1;
+  int force_cfg = -1;          // debug: force the exact-fp32 k_gemm and its config (a GemmCfg; CFG_AUTO: the model's level, gemm_plan's heuristic)
   unsigned* d_err = nullptr;   // set by a persistent kernel whose bounded spin expired
   int persist = 1;             // which BiGRU scan runs: a ScanMode (scan_plan; taco_debug_set_persistent)
   int ff_rot = 1;              // k_pointwise_chain: workgroups of an XCD start their K loops at different steps (0: taco_model_set_batch_invariant)
   int bf3 = 1;                 // feed-forward GEMMs (both CBHGs, linear head) on the bf16 matrix cores with 3-term split operands
   int bf3x6 = 0;               // training shadow model: feed-forward GEMMs on the six-product (fp32-grade) split-bf16 instantiation
-  int bf3_tn = 0;              // debug: force the bf3 tile width (1: 128x64, 2: 128x128)
+  int bf3_tn = 0;              // debug: force the k_gemm_bf3 tile (a GemmTile; TILE_AUTO: gemm_plan's heuristic)
   int chain = 1;               // point-wise tail of a CBHG as one launch (taco_chain.h); 0: one launch per layer
   int front_entry = 1;         // proj_1's epilogue + proj_2 inside the point-wise chain's entry (taco_chain.h) when the fused front ran
   int front_prio = 1; int front_delay = 0;      // shader clocks by which the second K half of a k_cbhg_front workgroup starts late (taco_front.h)
@@ -892,6 +892,7 @@ static int add_var(taco_model* m, ConvL& L, int coff) {
 // ------------------------------------------------------------------------------------------------
 // launch helpers
 // ------------------------------------------------------------------------------------------------
+enum GemmForce { GEMM_FORCE_NONE, GEMM_FORCE_EXACT, GEMM_FORCE_BF3 };
 struct GemmCall {
   const float* x = nullptr; const int* gather = nullptr; int ldx = 0;
   int M = 0, T = 0, mpw = 1, act = ACT_NONE;
@@ -901,181 +902,216 @@ struct GemmCall {
   int t_begin = 0, t_len = 0;      // time window [t_begin, t_begin + t_len) of every batch row (t_len 0 = all rows)
   float* out = nullptr; int ldo = 0;
   float* aux0 = nullptr; float* aux1 = nullptr;   // highway H / T saved for the backward pass (training tape)
+  int force = GEMM_FORCE_NONE;     // this call's level whatever the model's switches say (gemm_level): exact fp32, or split-bf16 at three products
 };
 
-template <int WM, int WN, int TM, int TN, int KS, bool DUAL>
-static int launch_gemm_cfg(hipStream_t st, const GemmArgs& a, int nvar, int kw_max, int Nmax) {
-  constexpr int BM = WM * TM * 32, BN = WN * TN * 32, NTHR = 64 * WM * WN * KS;
-  size_t lds = (size_t)(BM + kw_max - 1) * TACO_LDSW * sizeof(float);
-  if (KS > 1) lds = std::max(lds, (size_t)(KS - 1) * WM * WN * TM * TN * 1024 * (DUAL ? 2 : 1) * sizeof(float));
-  GemmArgs aa = a;
-  int gx = cdiv(a.M, BM);
-  if (a.t_len > 0) { aa.tiles_per_b = cdiv(a.t_len, BM); gx = (a.M / a.T) * aa.tiles_per_b; }
-  dim3 grid(gx, cdiv(Nmax, BN), nvar);
-  hipLaunchKernelGGL((k_gemm<WM, WN, TM, TN, KS, DUAL>), grid, dim3(NTHR), lds, st, aa);
-  HIPCHK(hipGetLastError());
-  return 0;
-}
-
-template <int WM, int WN, int TM, int TN, bool DUAL, int KS = 1, bool X6 = false>
-static int launch_gemm_bf3(hipStream_t st, const GemmArgs& a, int nvar, int kw_max, int Nmax, int gpi = 0) {
-  constexpr int BM = WM * TM * 32, BN = WN * TN * 32;
-  size_t lds = (size_t)KS * (X6 ? 3 : 2) * (BM + 15) * BF3_LDSW * sizeof(unsigned short);
-  if (KS > 1) lds = std::max(lds, (size_t)(KS - 1) * WM * WN * TM * TN * 16 * 64 * (DUAL ? 2 : 1) * sizeof(float));   // split-K reduction
-  GemmArgs aa = a;
-  int gx = cdiv(a.M, BM);
-  if (a.t_len > 0) { aa.tiles_per_b = cdiv(a.t_len, BM); gx = (a.M / a.T) * aa.tiles_per_b; }
-  (void)kw_max;
-  dim3 grid(gx, cdiv(Nmax, BN), nvar);
-  if constexpr (KS > 1) {
-    static bool attr_set = false;      // > 64 KB of dynamic LDS has to be asked for once per kernel
-    if (!attr_set) { HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_gemm_bf3<WM, WN, TM, TN, DUAL, 1, KS, X6>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)); attr_set = true; }
-    hipLaunchKernelGGL((k_gemm_bf3<WM, WN, TM, TN, DUAL, 1, KS, X6>), grid, dim3(64 * WM * WN * KS), lds, st, aa);
-    HIPCHK(hipGetLastError());
-    return 0;
-  }
-  if constexpr (X6) {      // six products per k16 group: one prefetch depth only
-    hipLaunchKernelGGL((k_gemm_bf3<WM, WN, TM, TN, DUAL, 1, 1, true>), grid, dim3(64 * WM * WN), lds, st, aa);
-    HIPCHK(hipGetLastError());
-    return 0;
-  }
-  // prefetch depth: two k16 steps ahead when the grid leaves at most ~2 workgroups per CU (occupancy is grid-limited there)
-  if (gpi == 0) gpi = (!DUAL && BN == 256 && (long)grid.x * grid.y * grid.z <= 320) ? 2 : 1;
-  for (int i = 0; i < nvar; ++i) if (a.v[i].cin_pad16 % 64) gpi = 1;     // GPI = 2 needs four k16 steps in every chunk (even group count)
-  if (gpi == 2) hipLaunchKernelGGL((k_gemm_bf3<WM, WN, TM, TN, DUAL, 2>), grid, dim3(64 * WM * WN), lds, st, aa);
-  else hipLaunchKernelGGL((k_gemm_bf3<WM, WN, TM, TN, DUAL, 1>), grid, dim3(64 * WM * WN), lds, st, aa);
-  HIPCHK(hipGetLastError());
-  return 0;
-}
-
-static int pick_cfg(const taco_model* m, int M, int N, int nvar) {
-  if (m->force_cfg >= 0) return m->force_cfg;
-  // measured (tools/time_gemm_layers.py): the 64x64 tile (32 VGPRs, 8 waves/SIMD) beats 128x64 and 128x128 on
-  // every large layer -- the kernel is bound by latency hiding, not operand reuse; small-M layers need split-K
-  const long b1 = (long)cdiv(M, 64) * cdiv(N, 64) * nvar;
-  if (b1 >= 512) return 1;
-  return 2;
-}
-
-static thread_local int g_gemm_force_bf3 = 0;     // set around a call by run_dgrad (taco_train.h): this GEMM on the split-bf16 kernel although the model's switch is off
 // ---- which kernels run the feed-forward launches ----
 // The arithmetic of a layer that run_gemm serves: exact fp32 (k_gemm), or operands split into bf16 planes with three products (k_gemm_bf3; the fused
-// kernels exist at this level only) or six (k_gemm_bf3<..., X6>, fp32-grade: a training shadow model's default, taco_debug_set_bf3 bit 6)
+// kernels exist at this level only) or six (k_gemm_bf3<..., X6>, fp32-grade: a training shadow model's default, taco_debug_set_bf3 bit 6).
+// force (GemmCall::force): one call's override of the model's switches
 enum GemmLevel { GEMM_EXACT, GEMM_BF3, GEMM_BF3X6 };
-static GemmLevel gemm_level(const taco_model* m, const ConvL& L) {
-  if (!((m->bf3 || m->bf3x6 || g_gemm_force_bf3) && m->force_cfg < 0 && L.bh)) return GEMM_EXACT;
-  return (m->bf3x6 && !g_gemm_force_bf3) || (m->bf3 && L.x6) ? GEMM_BF3X6 : GEMM_BF3;
+static GemmLevel gemm_level(const taco_model* m, const ConvL& L, int force = GEMM_FORCE_NONE) {
+  const bool bf3 = force == GEMM_FORCE_BF3;
+  if (force == GEMM_FORCE_EXACT || !((m->bf3 || m->bf3x6 || bf3) && m->force_cfg < 0 && L.bh)) return GEMM_EXACT;
+  return (m->bf3x6 && !bf3) || (m->bf3 && L.x6) ? GEMM_BF3X6 : GEMM_BF3;
 }
 // First reason against a fused kernel (k_cbhg_front, k_pointwise_chain, the chain's fused entry, k_head_sweep); NONE: it runs
 enum FfWhyNot { FF_WHY_NONE, FF_WHY_EXACT, FF_WHY_X6, FF_WHY_CFG, FF_WHY_TILE, FF_WHY_SWITCH, FF_WHY_WIDTHS, FF_WHY_NEEDS_BOTH };
 // The term all of them share, once: L (a layer the kernel would serve) at the three-product level -- split-bf16 on, not the six-product
 // level, no forced k_gemm config -- and no forced k_gemm_bf3 tile
-static FfWhyNot ff_fused_why(const taco_model* m, const ConvL& L) {
-  const GemmLevel lv = gemm_level(m, L);
+static FfWhyNot ff_fused_why(const taco_model* m, const ConvL& L, int force = GEMM_FORCE_NONE) {
+  const GemmLevel lv = gemm_level(m, L, force);
   return lv == GEMM_BF3X6 ? FF_WHY_X6 : lv == GEMM_EXACT ? (m->force_cfg >= 0 ? FF_WHY_CFG : FF_WHY_EXACT) : m->bf3_tn ? FF_WHY_TILE : FF_WHY_NONE;
 }
 // k_head_sweep (taco_head.h) for a dense layer L over the rows of call c: a wide layer over many rows with a plain epilogue (the linear head).
 // Pure: the one term left to the launch is the 16-byte alignment of c.x -- a workspace carved by Carver (256-byte steps) has it.
 static FfWhyNot head_sweep_why(const taco_model* m, const ConvL& L, int nvar, bool dual, const GemmCall& c) {
-  if (const FfWhyNot why = ff_fused_why(m, L)) return why;
+  if (const FfWhyNot why = ff_fused_why(m, L, c.force)) return why;
   if (!m->head_sweep) return FF_WHY_SWITCH;
   return nvar == 1 && !dual && L.kw == 1 && c.mpw <= 1 && !c.gather && !c.res && !c.rev_len && c.rev_col0 < 0 && c.t_len == 0 && !c.aux0 && !c.aux1 &&
          c.act == ACT_NONE && !L.bns && c.ldx % 4 == 0 && (L.cin == 256 || L.cin == 512) && L.N >= 512 && L.N % 32 == L.ntail && (L.ntail == 0 || L.wtail) &&
          c.M >= 256 && (long)c.M * c.ldo < (1L << 30) ? FF_WHY_NONE : FF_WHY_WIDTHS;
 }
+
+// ---- which instantiation of k_gemm_bf3 / k_gemm a launch gets ----
+// k_gemm_bf3 tiles (rows x columns of the output per workgroup); the numbers are taco_debug_set_bf3's tile_n
+enum GemmTile {
+  TILE_AUTO = 0,
+  TILE_64x64 = 4,          // 2 x 2 waves
+  TILE_64x64_K4 = 5,       // the same by four wave groups that split K
+  TILE_64x256 = 7,         // one row of 8 waves side by side over the columns, two row tiles each
+  TILE_64x128 = 9,         // one row of 4 waves
+  TILE_64x256_K2 = 10,     // 64x256 by two wave groups that split K (16 waves per CU)
+};
+// k_gemm configs; the numbers are taco_debug_force_gemm_config's cfg
+enum GemmCfg {
+  CFG_AUTO = -1,
+  CFG_64x64 = 1,           // 2 x 2 waves
+  CFG_32x64_K4 = 2,        // 1 x 2 waves by four wave groups that split K
+};
+static inline bool gemm_tile_known(int t) { return t == TILE_AUTO || t == TILE_64x64 || t == TILE_64x64_K4 || t == TILE_64x256 || t == TILE_64x128 || t == TILE_64x256_K2; }
+static inline bool gemm_cfg_known(int c) { return c == CFG_AUTO || c == CFG_64x64 || c == CFG_32x64_K4; }
+// Every instantiation that exists, once: the plan takes a member's shape from here, run_gemm its kernel, gemm_set_attributes its LDS attribute.
+//   X(tile, WM, WN, TM, DUAL, GPI, KS, X6): WM x WN waves per wave group, TM row tiles of 32 per wave, KS wave groups.
+// What is NOT here is a rule of gemm_plan: the split-K-by-two tile exists at three products without DUAL only, GPI = 2 on the plain 64x256 tile only,
+// and six products with DUAL have no four-wave-group tile (it would spill with two accumulator sets and three planes).
+#define GEMM_BF3_LIST(X) \
+  X(TILE_64x64, 2, 2, 1, false, 1, 1, false)     X(TILE_64x64, 2, 2, 1, true, 1, 1, false) \
+  X(TILE_64x64_K4, 2, 2, 1, false, 1, 4, false)  X(TILE_64x64_K4, 2, 2, 1, true, 1, 4, false) \
+  X(TILE_64x256, 1, 8, 2, false, 1, 1, false)    X(TILE_64x256, 1, 8, 2, true, 1, 1, false)    X(TILE_64x256, 1, 8, 2, false, 2, 1, false) \
+  X(TILE_64x128, 1, 4, 2, false, 1, 1, false)    X(TILE_64x128, 1, 4, 2, true, 1, 1, false) \
+  X(TILE_64x256_K2, 1, 8, 2, false, 1, 2, false) \
+  X(TILE_64x64, 2, 2, 1, false, 1, 1, true)      X(TILE_64x64, 2, 2, 1, true, 1, 1, true) \
+  X(TILE_64x64_K4, 2, 2, 1, false, 1, 4, true) \
+  X(TILE_64x256, 1, 8, 2, false, 1, 1, true)     X(TILE_64x256, 1, 8, 2, true, 1, 1, true) \
+  X(TILE_64x128, 1, 4, 2, false, 1, 1, true)     X(TILE_64x128, 1, 4, 2, true, 1, 1, true)
+//   X(cfg, WM, WN, KS, DUAL): one 32 x 32 tile per wave
+#define GEMM_EXACT_LIST(X) \
+  X(CFG_64x64, 2, 2, 1, false)     X(CFG_64x64, 2, 2, 1, true) \
+  X(CFG_32x64_K4, 1, 2, 4, false)  X(CFG_32x64_K4, 1, 2, 4, true)
+#define GEMM_BF3_KERNEL(TILE, WM, WN, TM, DUAL, GPI, KS, X6) k_gemm_bf3<WM, WN, TM, 1, DUAL, GPI, KS, X6>
+#define GEMM_EXACT_KERNEL(CFG, WM, WN, KS, DUAL) k_gemm<WM, WN, 1, 1, KS, DUAL>
+// a member's name inside one level (tile: a GemmTile, or a GemmCfg for the exact level)
+static constexpr int gemm_key(int tile, bool dual, int gpi, bool x6) { return tile | (dual ? 16 : 0) | (gpi == 2 ? 32 : 0) | (x6 ? 64 : 0); }
+
+struct GemmPlan {
+  GemmLevel level = GEMM_EXACT;
+  bool head_sweep = false;     // k_head_sweep<K> instead of a tile kernel (three-product level only)
+  bool x6 = false;             // the six-product instantiation (level GEMM_BF3X6 and every layer of the launch has its third planes)
+  int tile = 0;                // GemmTile (split-bf16 levels) or GemmCfg (exact level)
+  int gpi = 1;                 // k_gemm_bf3: k16 steps per weight prefetch group
+  dim3 grid = dim3(0, 0, 0); unsigned block = 0; size_t lds = 0;      // block 0: the list has no such member
+  int tiles_per_b = 0;         // GemmArgs::tiles_per_b (time-window mode)
+};
+// Everything a run_gemm launch decides, from integers and the model's switches alone (x_aligned: c.x on a 16-byte boundary, see head_sweep_why)
+static GemmPlan gemm_plan(const taco_model* m, const ConvL* layers, int nvar, bool dual, const GemmCall& c, bool x_aligned) {
+  GemmPlan p;
+  const ConvL& L0 = layers[0];
+  int kw_max = 1, Nmax = 0;
+  for (int i = 0; i < nvar; ++i) { kw_max = std::max(kw_max, layers[i].kw); Nmax = std::max(Nmax, layers[i].N); }
+  const int T = c.T > 0 ? c.T : c.M, nb = c.M / T;
+  const long Meff = c.t_len > 0 ? (long)nb * c.t_len : c.M;      // rows that are computed (t_len > 0: a time window of every batch row)
+  const bool vec_ok = c.ldx % 4 == 0 && L0.cin % 4 == 0 && x_aligned;
+  p.level = gemm_level(m, L0, c.force);
+  int BM = 0, BN = 0, KS = 1, waves = 0, tiles = 0;      // of the member: rows, columns, wave groups, waves per group, 32 x 32 tiles per wave
+  if (p.level != GEMM_EXACT) {      // split-bf16 (every feed-forward layer of inference)
+    // a wide dense layer over many rows (the linear head): every workgroup keeps its 64 rows for ALL columns (taco_head.h)
+    if (vec_ok && head_sweep_why(m, L0, nvar, dual, c) == FF_WHY_NONE) {
+      p.head_sweep = true;
+      p.grid = dim3(cdiv(c.M, HD_BM)); p.block = 512; p.lds = (size_t)2 * HD_BM * (L0.cin + 8) * sizeof(unsigned short);
+      return p;
+    }
+    p.tile = m->bf3_tn;
+    if (p.tile == TILE_AUTO) {
+      // measured (tools/time_gemm_layers.py).  Small-M layers (encoder, short utterances): 64x64 tiles; if even those leave most CUs idle, four
+      // wave groups per workgroup split K.  Otherwise one row of waves side by side over the columns (64x256 by 1x8 waves, 64x128 by 1x4): every
+      // wave streams its OWN weight columns and all of them share the staged activation tile, so no weight fragment is fetched twice by a
+      // workgroup (2x2 arrangements of larger tiles fetch each one twice through a 16 KB L1 that cannot hold them: measured 20-30 % slower on
+      // every large layer; a 128 x 256 tile by 1 x 8 waves measured slower on the linear head, 116 vs 85 us: one workgroup of 8 waves per CU and
+      // three rounds of workgroups.  Both were retired.)
+      const int Ktot = L0.kw * L0.cin;
+      const long g128 = (long)cdiv(Meff, 128) * cdiv(Nmax, 64) * nvar, g64 = (long)cdiv(Meff, 64) * cdiv(Nmax, 64) * nvar;
+      const long wide = (long)cdiv(Meff, 64) * cdiv(Nmax, 256) * nvar;      // workgroups of the 64x256 tile
+      if (g128 < 384 && !((Ktot >= 1024 || Nmax > 512) && wide >= 192)) p.tile = g64 >= 384 ? TILE_64x64 : TILE_64x64_K4;
+      else if (Nmax <= 128) p.tile = TILE_64x128;
+      else p.tile = (!dual && wide <= 320) ? TILE_64x256_K2 : TILE_64x256;      // few workgroups: two wave groups split K (16 waves/CU)
+    }
+    // six products (fp32-grade): the training forward (taco_train_set_exact_gemm mode 4); needs the third planes of every layer of the launch
+    p.x6 = p.level == GEMM_BF3X6;
+    for (int i = 0; i < nvar; ++i) p.x6 = p.x6 && layers[i].bl3 && (!dual || layers[i].bl3_2);
+    // what the list does not have, chosen or forced: the same tile without split-K
+    if (p.tile == TILE_64x256_K2 && (dual || p.x6)) p.tile = TILE_64x256;
+    if (p.tile == TILE_64x64_K4 && dual && p.x6) p.tile = TILE_64x64;
+    switch (gemm_key(p.tile, dual, 1, p.x6)) {
+#define X(TILE, WM, WN, TM, DUAL, GPI, KS_, X6) case gemm_key(TILE, DUAL, GPI, X6): BM = WM * TM * 32; BN = WN * 32; KS = KS_; waves = WM * WN; tiles = TM; break;
+      GEMM_BF3_LIST(X)
+#undef X
+      default: return p;
+    }
+    p.lds = (size_t)KS * (p.x6 ? 3 : 2) * (BM + 15) * BF3_LDSW * sizeof(unsigned short);
+    if (KS > 1) p.lds = std::max(p.lds, (size_t)(KS - 1) * waves * tiles * 16 * 64 * (dual ? 2 : 1) * sizeof(float));      // split-K reduction
+  } else {
+    p.tile = m->force_cfg;
+    if (p.tile == CFG_AUTO) {
+      // measured (tools/time_gemm_layers.py): the 64x64 tile (32 VGPRs, 8 waves/SIMD) beats 128x64 and 128x128 (retired) on
+      // every large layer -- the kernel is bound by latency hiding, not operand reuse; small-M layers need split-K
+      p.tile = (long)cdiv(Meff, 64) * cdiv(Nmax, 64) * nvar >= 512 ? CFG_64x64 : CFG_32x64_K4;
+    }
+    switch (gemm_key(p.tile, dual, 1, false)) {
+#define X(CFG, WM, WN, KS_, DUAL) case gemm_key(CFG, DUAL, 1, false): BM = WM * 32; BN = WN * 32; KS = KS_; waves = WM * WN; tiles = 1; break;
+      GEMM_EXACT_LIST(X)
+#undef X
+      default: return p;
+    }
+    p.lds = (size_t)(BM + kw_max - 1) * TACO_LDSW * sizeof(float);
+    if (KS > 1) p.lds = std::max(p.lds, (size_t)(KS - 1) * waves * 1024 * (dual ? 2 : 1) * sizeof(float));
+  }
+  int gx = cdiv(c.M, BM);
+  if (c.t_len > 0) { p.tiles_per_b = cdiv(c.t_len, BM); gx = nb * p.tiles_per_b; }
+  p.grid = dim3(gx, cdiv(Nmax, BN), nvar);
+  p.block = 64 * waves * KS;
+  // weight prefetch depth of k_gemm_bf3: two k16 steps ahead when the grid leaves at most ~2 workgroups per CU (occupancy is grid-limited there);
+  // instantiated for the plain 64x256 tile only, and it needs four k16 steps in every chunk (even group count)
+  if (p.level != GEMM_EXACT && p.tile == TILE_64x256 && !dual && !p.x6 && (long)p.grid.x * p.grid.y * p.grid.z <= 320) {
+    p.gpi = 2;
+    for (int i = 0; i < nvar; ++i) if (layers[i].cin_pad16 % 64) p.gpi = 1;
+  }
+  return p;
+}
+// > 64 KB of dynamic LDS has to be asked for, per kernel and device: the split-K members (taco_model_finalize, taco_gl_create)
+static int gemm_set_attributes() {
+#define X(TILE, WM, WN, TM, DUAL, GPI, KS, X6) \
+  if (KS > 1) HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&GEMM_BF3_KERNEL(TILE, WM, WN, TM, DUAL, GPI, KS, X6)), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+  GEMM_BF3_LIST(X)
+#undef X
+  return 0;
+}
 static int run_gemm(const taco_model* m, hipStream_t st, const ConvL* layers, int nvar, bool dual, const GemmCall& c) {
   GemmArgs a;
   memset(&a, 0, sizeof a);
   const ConvL& L0 = layers[0];
+  const bool x_aligned = (reinterpret_cast<uintptr_t>(c.x) & 15) == 0;
   a.x = c.x; a.gather = c.gather; a.res = c.res; a.rowvec = c.rowvec; a.out = c.out;
   a.ldx = c.ldx; a.M = c.M; a.T = c.T > 0 ? c.T : c.M; a.Cin = L0.cin; a.cin_pad = L0.cin_pad; a.mpw = c.mpw;
   a.act = c.act; a.ldres = c.ldres; a.ldrv = c.ldrv; a.ldo = c.ldo; a.rev_len = c.rev_len; a.rev_col0 = c.rev_col0;
   a.t_begin = c.t_begin; a.t_len = c.t_len; a.aux0 = c.aux0; a.aux1 = c.aux1;
-  a.vec_ok = (c.ldx % 4 == 0) && (L0.cin % 4 == 0) && ((reinterpret_cast<uintptr_t>(c.x) & 15) == 0);
-  int kw_max = 1, Nmax = 0;
-  for (int i = 0; i < nvar; ++i) {
-    kw_max = std::max(kw_max, layers[i].kw); Nmax = std::max(Nmax, layers[i].N);
+  a.vec_ok = (c.ldx % 4 == 0) && (L0.cin % 4 == 0) && x_aligned;
+  for (int i = 0; i < nvar && i < 16; ++i) {
     if (layers[i].var_index < 0) return fail(TACO_ERR_STATE, "layer has no GemmVar");
     a.v[i] = m->hvars[layers[i].var_index];
   }
   if (nvar > 16) return fail(TACO_ERR_UNSUPPORTED, "conv bank wider than 16 is not supported");
-  if (const GemmLevel level = gemm_level(m, L0); level != GEMM_EXACT) {   // split-bf16 path (every feed-forward layer of inference)
-    // tiles (rows x cols): 1 = 128x64, 2 = 128x128, 3 = 64x256 (one staged 64-row tile feeds 8 MFMA column tiles)
-    // measured (tools/time_gemm_layers.py): 64x256 wins when K or N is large (proj_1, linear, GRU projection), 128x64 otherwise
-    const int Ktot = L0.kw * L0.cin;
-    const long Meff = c.t_len > 0 ? (long)(c.M / a.T) * c.t_len : c.M;
-    // small-M layers (encoder, short utterances): 64x64 tiles; if even those leave most CUs idle, four wave groups per
-    // workgroup split K (tile 4 / 5).  Otherwise one row of waves side by side over the columns (tile 7: 64x256 by 1x8 waves,
-    // tile 9: 64x128 by 1x4): every wave streams its OWN weight columns and all of them share the staged activation tile, so no
-    // weight fragment is fetched twice by a workgroup (the 2x2 arrangements of tiles 1-3 fetch each one twice through a 16 KB L1
-    // that cannot hold them: measured 20-30 % slower on every large layer, tools/time_gemm_layers.py).
-    // a wide dense layer over many rows (the linear head): every workgroup keeps its 64 rows for ALL columns (taco_head.h)
-    bool x6 = level == GEMM_BF3X6;
-    if (a.vec_ok && head_sweep_why(m, L0, nvar, dual, c) == FF_WHY_NONE) {
-      HeadArgs h;
-      memset(&h, 0, sizeof h);
-      h.x = c.x; h.ldx = c.ldx; h.bh = a.v[0].bh; h.bl = a.v[0].bl; h.NT = a.v[0].NT; h.K16 = L0.cin / 16; h.bias = a.v[0].bias;
-      h.wtail = L0.wtail ? AP(m, L0.wtail) : nullptr; h.ntail = L0.ntail; h.rowvec = c.rowvec; h.ldrv = c.ldrv; h.T = a.T;
-      h.out = c.out; h.ldo = c.ldo; h.M = c.M; h.K = L0.cin; h.N = L0.N;
-      if (L0.cin == 512) hipLaunchKernelGGL(k_head_sweep<512>, dim3(cdiv(c.M, HD_BM)), dim3(512), (size_t)2 * HD_BM * (512 + 8) * sizeof(unsigned short), st, h);
-      else hipLaunchKernelGGL(k_head_sweep<256>, dim3(cdiv(c.M, HD_BM)), dim3(512), (size_t)2 * HD_BM * (256 + 8) * sizeof(unsigned short), st, h);
-      HIPCHK(hipGetLastError());
-      return 0;
-    }
-    int tn = m->bf3_tn;
-    if (!tn) {
-      const long g128 = (long)cdiv(Meff, 128) * cdiv(Nmax, 64) * nvar, g64 = (long)cdiv(Meff, 64) * cdiv(Nmax, 64) * nvar;
-      if (g128 < 384 && !((Ktot >= 1024 || Nmax > 512) && (long)cdiv(Meff, 64) * cdiv(Nmax, 256) * nvar >= 192)) tn = (g64 >= 384) ? 4 : 5;
-      else if (Nmax <= 128) tn = 9;
-      else tn = (!dual && (long)cdiv(Meff, 64) * cdiv(Nmax, 256) * nvar <= 320) ? 10 : 7;   // few workgroups: two wave groups split K (16 waves/CU)
-      // (tile 11, 128 x 256 by 1 x 8 waves -- every weight fragment meets four row tiles -- measured SLOWER on the linear head, 116 vs 85 us:
-      // one workgroup of 8 waves per CU and three rounds of workgroups; selectable for A/B only)
-    }
-    // six-product (fp32-grade) instantiations: the training forward (taco_train_set_exact_gemm mode 4); the tiles the heuristic picks
-    for (int i = 0; i < nvar; ++i) x6 = x6 && a.v[i].bl3 && (!dual || a.v[i].bl3_2);
-    if (x6) {
-      if (tn == 10) tn = 7;
-      if (dual) {
-        if (tn == 7) return launch_gemm_bf3<1, 8, 2, 1, true, 1, true>(st, a, nvar, kw_max, Nmax);
-        if (tn == 9) return launch_gemm_bf3<1, 4, 2, 1, true, 1, true>(st, a, nvar, kw_max, Nmax);
-        return launch_gemm_bf3<2, 2, 1, 1, true, 1, true>(st, a, nvar, kw_max, Nmax);      // (the four-wave-group tile would spill with two accumulator sets and three planes)
-      }
-      if (tn == 7) return launch_gemm_bf3<1, 8, 2, 1, false, 1, true>(st, a, nvar, kw_max, Nmax);
-      if (tn == 9) return launch_gemm_bf3<1, 4, 2, 1, false, 1, true>(st, a, nvar, kw_max, Nmax);
-      if (tn == 5) return launch_gemm_bf3<2, 2, 1, 1, false, 4, true>(st, a, nvar, kw_max, Nmax);
-      return launch_gemm_bf3<2, 2, 1, 1, false, 1, true>(st, a, nvar, kw_max, Nmax);
-    }
-    if (dual) {
-      if (tn == 7) return launch_gemm_bf3<1, 8, 2, 1, true>(st, a, nvar, kw_max, Nmax);
-      if (tn == 9) return launch_gemm_bf3<1, 4, 2, 1, true>(st, a, nvar, kw_max, Nmax);
-      if (tn == 5) return launch_gemm_bf3<2, 2, 1, 1, true, 4>(st, a, nvar, kw_max, Nmax);
-      if (tn == 4) return launch_gemm_bf3<2, 2, 1, 1, true>(st, a, nvar, kw_max, Nmax);
-      if (tn == 3) return launch_gemm_bf3<2, 2, 1, 4, true>(st, a, nvar, kw_max, Nmax);
-      return tn == 2 ? launch_gemm_bf3<2, 2, 2, 2, true>(st, a, nvar, kw_max, Nmax) : launch_gemm_bf3<2, 2, 2, 1, true>(st, a, nvar, kw_max, Nmax);
-    }
-    if (tn == 11) return launch_gemm_bf3<1, 8, 4, 1, false>(st, a, nvar, kw_max, Nmax, 1);      // 128 x 256: every weight fragment meets four row tiles
-    if (tn == 10) return launch_gemm_bf3<1, 8, 2, 1, false, 2>(st, a, nvar, kw_max, Nmax);
-    if (tn == 9) return launch_gemm_bf3<1, 4, 2, 1, false>(st, a, nvar, kw_max, Nmax);
-    if (tn == 7) return launch_gemm_bf3<1, 8, 2, 1, false>(st, a, nvar, kw_max, Nmax);
-    if (tn == 5) return launch_gemm_bf3<2, 2, 1, 1, false, 4>(st, a, nvar, kw_max, Nmax);
-    if (tn == 4) return launch_gemm_bf3<2, 2, 1, 1, false>(st, a, nvar, kw_max, Nmax);
-    if (tn == 3) return launch_gemm_bf3<2, 2, 1, 4, false>(st, a, nvar, kw_max, Nmax);
-    return tn == 2 ? launch_gemm_bf3<2, 2, 2, 2, false>(st, a, nvar, kw_max, Nmax) : launch_gemm_bf3<2, 2, 2, 1, false>(st, a, nvar, kw_max, Nmax);
+  const GemmPlan p = gemm_plan(m, layers, nvar, dual, c, x_aligned);
+  a.tiles_per_b = p.tiles_per_b;
+  if (p.head_sweep) {
+    HeadArgs h;
+    memset(&h, 0, sizeof h);
+    h.x = c.x; h.ldx = c.ldx; h.bh = a.v[0].bh; h.bl = a.v[0].bl; h.NT = a.v[0].NT; h.K16 = L0.cin / 16; h.bias = a.v[0].bias;
+    h.wtail = L0.wtail ? AP(m, L0.wtail) : nullptr; h.ntail = L0.ntail; h.rowvec = c.rowvec; h.ldrv = c.ldrv; h.T = a.T;
+    h.out = c.out; h.ldo = c.ldo; h.M = c.M; h.K = L0.cin; h.N = L0.N;
+    if (L0.cin == 512) hipLaunchKernelGGL(k_head_sweep<512>, p.grid, dim3(p.block), p.lds, st, h);
+    else hipLaunchKernelGGL(k_head_sweep<256>, p.grid, dim3(p.block), p.lds, st, h);
+    HIPCHK(hipGetLastError());
+    return 0;
   }
-  const int cfg = pick_cfg(m, c.t_len > 0 ? (c.M / a.T) * c.t_len : c.M, Nmax, nvar);
-  if (dual) {
-    switch (cfg) {
-      case 0: case 3: return launch_gemm_cfg<2, 2, 2, 1, 1, true>(st, a, nvar, kw_max, Nmax);
-      case 1: return launch_gemm_cfg<2, 2, 1, 1, 1, true>(st, a, nvar, kw_max, Nmax);
-      default: return launch_gemm_cfg<1, 2, 1, 1, 4, true>(st, a, nvar, kw_max, Nmax);
+  void (*kernel)(const GemmArgs) = nullptr;
+  if (p.level != GEMM_EXACT) {
+    switch (gemm_key(p.tile, dual, p.gpi, p.x6)) {
+#define X(TILE, WM, WN, TM, DUAL, GPI, KS, X6) case gemm_key(TILE, DUAL, GPI, X6): kernel = GEMM_BF3_KERNEL(TILE, WM, WN, TM, DUAL, GPI, KS, X6); break;
+      GEMM_BF3_LIST(X)
+#undef X
+    }
+  } else {
+    switch (gemm_key(p.tile, dual, 1, false)) {
+#define X(CFG, WM, WN, KS, DUAL) case gemm_key(CFG, DUAL, 1, false): kernel = GEMM_EXACT_KERNEL(CFG, WM, WN, KS, DUAL); break;
+      GEMM_EXACT_LIST(X)
+#undef X
     }
   }
-  switch (cfg) {
-    case 0: return launch_gemm_cfg<2, 2, 2, 1, 1, false>(st, a, nvar, kw_max, Nmax);
-    case 1: return launch_gemm_cfg<2, 2, 1, 1, 1, false>(st, a, nvar, kw_max, Nmax);
-    case 3: return launch_gemm_cfg<2, 2, 2, 2, 1, false>(st, a, nvar, kw_max, Nmax);
-    default: return launch_gemm_cfg<1, 2, 1, 1, 4, false>(st, a, nvar, kw_max, Nmax);
-  }
+  if (!kernel) return fail(TACO_ERR_STATE, "gemm_plan names a k_gemm / k_gemm_bf3 instantiation that does not exist");
+  hipLaunchKernelGGL(kernel, p.grid, dim3(p.block), p.lds, st, a);
+  HIPCHK(hipGetLastError());
+  return 0;
 }
 
 // ---- skinny jobs ----
@@ -2518,6 +2554,7 @@ int taco_model_finalize(taco_model* m) {
   HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_head_sweep<512>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
   HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_head_sweep<256>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
   HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_pointwise_chain<128>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+  TRY(gemm_set_attributes());
 #define DX_ATTR(...) HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_decoder_xcd<__VA_ARGS__>), hipFuncAttributeMaxDynamicSharedMemorySize, DX_LDS_BUDGET));
 #define PLAIN(RG, TAPE, AW, PD) DX_ATTR(RG, TAPE, false, AW, PD)
 #define MANUAL(RG, TAPE, AW, PD) DX_ATTR(RG, TAPE, true, AW, PD)
@@ -2572,6 +2609,7 @@ int taco_debug_raise_device_error(taco_model* m, int value) {
 
 int taco_debug_set_bf3(taco_model* m, int on, int tile_n) {
   if (!m) return fail(TACO_ERR_ARG, "null model");
+  if (!gemm_tile_known(tile_n)) return fail(TACO_ERR_ARG, "tile_n is not one of 0, 4, 5, 7, 9, 10");
   m->bf3 = (on & 1) != 0; m->bf3_tn = tile_n;
   m->chain = (on & 4) ? 0 : 1;     // on = 5: split-bf16 GEMMs with one launch per point-wise layer (A/B of taco_chain.h)
   m->front = (on & 8) ? 0 : 1;     // on = 9: conv bank and proj_1 as two k_gemm_bf3 launches (A/B of taco_front.h)
@@ -2804,6 +2842,7 @@ int taco_debug_set_skip_scans(taco_model* m, int on) {
 
 int taco_debug_force_gemm_config(taco_model* m, int cfg) {
   if (!m) return fail(TACO_ERR_ARG, "null model");
+  if (!gemm_cfg_known(cfg)) return fail(TACO_ERR_ARG, "cfg is not one of -1, 1, 2");
   m->force_cfg = cfg;
   return 0;
 }

@@ -429,8 +429,7 @@ static thread_local int g_dgrad_exact = 0;     // taco_train_set_exact_gemm(t, 2
 static int run_dgrad(const taco_model* m, hipStream_t st, const ConvL& Ld, const float* dy, int lddy, int M, int T, float* out, int ldo,
                      const float* res = nullptr, int ldres = 0) {
   GemmCall g; g.x = dy; g.ldx = lddy; g.M = M; g.T = T; g.out = out; g.ldo = ldo; g.res = res; g.ldres = ldres;
-  if (g_dgrad_exact) { ConvL E = Ld; E.bh = E.bl = 0; return run_gemm(m, st, &E, 1, false, g); }
-  if (g_dgrad_bf3) { g_gemm_force_bf3 = 1; const int rc = run_gemm(m, st, &Ld, 1, false, g); g_gemm_force_bf3 = 0; return rc; }
+  g.force = g_dgrad_exact ? GEMM_FORCE_EXACT : g_dgrad_bf3 ? GEMM_FORCE_BF3 : GEMM_FORCE_NONE;
   return run_gemm(m, st, &Ld, 1, false, g);
 }
 

@@ -10,6 +10,8 @@ from util import tiny_hp, build_model, dev, ptr, stream, maxabs
 
 pytestmark = pytest.mark.gpu
 TOL = 3e-5
+GEMM_TILES_RETIRED = (1, 2, 3, 11)     # k_gemm_bf3 tiles (128x64, 128x128, 64x256 by 2x2 waves, 128x256) that only taco_debug_set_bf3 ever reached
+GEMM_CFGS_RETIRED = (0, 3)             # k_gemm configs (128x64, 128x128) that only taco_debug_force_gemm_config ever reached
 TOL_SPLIT = 1e-4   # feed-forward GEMMs run as 3-term split-bf16 products (~2^-16 relative per product): N(0,1) inputs, K = 3 x 128 channels
 
 
@@ -41,7 +43,11 @@ def test_conv_bank_member(ctx, k, cfg):
     rs = np.random.RandomState(100 + k)
     x = rs.randn(3, 37, ohp.enc_prenet_sizes[-1])
     name = "encoder_cbhg/conv_bank/conv1d_%d" % k
-    m._lib.taco_debug_force_gemm_config(m._handle, cfg)
+    rc = m._lib.taco_debug_force_gemm_config(m._handle, cfg)
+    if cfg in GEMM_CFGS_RETIRED:      # refused, nothing changed: the check below runs on the model's own level and the automatic choice
+        assert rc == L.TACO_ERR_ARG
+    else:
+        L.check(rc)
     try:
         y = _conv(ctx, name, x, 1)
     finally:
@@ -126,41 +132,74 @@ def test_stop_steps_per_group_of_rows(ctx):
         L.check(m._lib.taco_stop_steps(stream(), ptr(yd), B, n, width, 5, ptr(out)))      # 12 rows do not split into groups of 5
 
 
-@pytest.mark.parametrize("tile", [1, 2, 3, 4, 5, 7, 9, 10])
-def test_split_bf16_gemm_every_tile_shape(ctx, tile):
-    """k_gemm_bf3 under each of its tile shapes (1: 128x64, 2: 128x128, 3: 64x256, 4: 64x64, 5: 64x64 with four wave groups
-    splitting K inside the workgroup, 7: 64x256 by 1x8 waves, 9: 64x128 by 1x4 waves, 10: tile 7 with two wave groups splitting K): conv with taps over ragged row counts and several batch rows, projection with the fused
-    max-pool and several LDS chunks, dense with an odd column count, highway (two weight matrices).  The automatic choice picks
-    4/5 at these sizes, so the large-layer tiles (7, 9 and the older 1-3) are pinned here."""
+def _split_bf16_gemm_checks(ctx, seed):
+    """The five checks of test_split_bf16_gemm_every_tile_shape on whatever tile is in force; returns the outputs."""
     import torch
     ohp, w, m, L = ctx
-    L.check(m._lib.taco_debug_set_bf3(m._handle, 1, tile))
-    try:
-        rs = np.random.RandomState(40 + tile)
-        x = rs.randn(5, 61, ohp.enc_prenet_sizes[-1])
-        for k in (1, 4, 5):
-            name = "encoder_cbhg/conv_bank/conv1d_%d" % k
-            assert maxabs(_conv(ctx, name, x, 1), O.conv1d_bn(x, w, name, O.relu)) < TOL_SPLIT
-        xc = rs.randn(3, 70, ohp.enc_bank_size * ohp.enc_bank_channel_size)
-        ref = O.conv1d_bn(O.maxpool_same_stride1(xc, 2), w, "encoder_cbhg/proj_1", O.relu)
-        assert maxabs(_conv(ctx, "encoder_cbhg/proj_1", xc, 1, mpw=2), ref) < TOL_SPLIT
-        xp = rs.randn(2, 131, ohp.post_bank_size * ohp.post_bank_channel_size)
-        ref = O.conv1d_bn(xp, w, "post_cbhg/proj_1", O.relu)
-        assert maxabs(_conv(ctx, "post_cbhg/proj_1", xp, 1, mpw=1), ref) < TOL_SPLIT
-        rows = 201
-        xd0 = rs.randn(rows, w["linear/kernel"].shape[0])
-        out = torch.full((rows, w["linear/kernel"].shape[1]), float("nan"), device="cuda")
-        xd = dev(xd0, torch.float32)
-        L.check(m._lib.taco_dense_f32(m._handle, stream(), b"linear", ptr(xd), rows, 0, ptr(out)))
+    outs = []
+    rs = np.random.RandomState(seed)
+    x = rs.randn(5, 61, ohp.enc_prenet_sizes[-1])
+    for k in (1, 4, 5):
+        name = "encoder_cbhg/conv_bank/conv1d_%d" % k
+        outs.append(_conv(ctx, name, x, 1))
+        assert maxabs(outs[-1], O.conv1d_bn(x, w, name, O.relu)) < TOL_SPLIT
+    xc = rs.randn(3, 70, ohp.enc_bank_size * ohp.enc_bank_channel_size)
+    ref = O.conv1d_bn(O.maxpool_same_stride1(xc, 2), w, "encoder_cbhg/proj_1", O.relu)
+    outs.append(_conv(ctx, "encoder_cbhg/proj_1", xc, 1, mpw=2))
+    assert maxabs(outs[-1], ref) < TOL_SPLIT
+    xp = rs.randn(2, 131, ohp.post_bank_size * ohp.post_bank_channel_size)
+    ref = O.conv1d_bn(xp, w, "post_cbhg/proj_1", O.relu)
+    outs.append(_conv(ctx, "post_cbhg/proj_1", xp, 1, mpw=1))
+    assert maxabs(outs[-1], ref) < TOL_SPLIT
+    rows = 201
+    xd0 = rs.randn(rows, w["linear/kernel"].shape[0])
+    out = torch.full((rows, w["linear/kernel"].shape[1]), float("nan"), device="cuda")
+    xd = dev(xd0, torch.float32)
+    L.check(m._lib.taco_dense_f32(m._handle, stream(), b"linear", ptr(xd), rows, 0, ptr(out)))
+    torch.cuda.synchronize()
+    outs.append(out.cpu().numpy())
+    assert maxabs(outs[-1], O.dense(xd0, w, "linear", None)) < TOL_SPLIT
+    for scope, D in (("encoder_cbhg", ohp.enc_rnn_size), ("post_cbhg", ohp.post_rnn_size)):
+        xh = rs.randn(150, D)
+        outh = torch.full((150, D), float("nan"), device="cuda")
+        xhd = dev(xh, torch.float32)
+        L.check(m._lib.taco_highway_f32(m._handle, stream(), (scope + "/highway_1").encode(), ptr(xhd), 150, ptr(outh)))
         torch.cuda.synchronize()
-        assert maxabs(out.cpu().numpy(), O.dense(xd0, w, "linear", None)) < TOL_SPLIT
-        for scope, D in (("encoder_cbhg", ohp.enc_rnn_size), ("post_cbhg", ohp.post_rnn_size)):
-            xh = rs.randn(150, D)
-            outh = torch.full((150, D), float("nan"), device="cuda")
-            xhd = dev(xh, torch.float32)
-            L.check(m._lib.taco_highway_f32(m._handle, stream(), (scope + "/highway_1").encode(), ptr(xhd), 150, ptr(outh)))
-            torch.cuda.synchronize()
-            assert maxabs(outh.cpu().numpy(), O.highwaynet(xh, w, scope + "/highway_1")) < TOL_SPLIT
+        outs.append(outh.cpu().numpy())
+        assert maxabs(outs[-1], O.highwaynet(xh, w, scope + "/highway_1")) < TOL_SPLIT
+    return outs
+
+
+@pytest.mark.parametrize("tile", [1, 2, 3, 4, 5, 7, 9, 10, 11])
+def test_split_bf16_gemm_every_tile_shape(ctx, tile):
+    """k_gemm_bf3 under each of its tile shapes (4: 64x64, 5: 64x64 with four wave groups splitting K inside the workgroup, 7: 64x256 by
+    1x8 waves, 9: 64x128 by 1x4 waves, 10: tile 7 with two wave groups splitting K): conv with taps over ragged row counts and several
+    batch rows, projection with the fused max-pool and several LDS chunks, dense with an odd column count, highway (two weight matrices;
+    tile 10 has no such form and runs tile 7).  The automatic choice picks 4/5 at these sizes, so the large-layer tiles (7, 9, 10) are
+    pinned here.  The retired numbers (1: 128x64, 2: 128x128, 3: 64x256 by 2x2 waves, 11: 128x256) are refused with TACO_ERR_ARG and
+    change nothing: the same checks then run on the automatic choice."""
+    ohp, w, m, L = ctx
+    rc = m._lib.taco_debug_set_bf3(m._handle, 1, tile)
+    if tile in GEMM_TILES_RETIRED:
+        assert rc == L.TACO_ERR_ARG
+    else:
+        L.check(rc)
+    try:
+        _split_bf16_gemm_checks(ctx, 40 + tile)
+    finally:
+        L.check(m._lib.taco_debug_set_bf3(m._handle, 1, 0))
+
+
+def test_refused_gemm_tile_keeps_the_forced_one(ctx):
+    """taco_debug_set_bf3 with a retired tile number after tile 7 was forced: TACO_ERR_ARG, and the model still runs tile 7 -- every
+    output matches the oracle and equals, to the bit, what tile 7 forced alone computes."""
+    ohp, w, m, L = ctx
+    try:
+        L.check(m._lib.taco_debug_set_bf3(m._handle, 1, 7))
+        alone = _split_bf16_gemm_checks(ctx, 47)
+        assert m._lib.taco_debug_set_bf3(m._handle, 1, 3) == L.TACO_ERR_ARG
+        after = _split_bf16_gemm_checks(ctx, 47)
+        assert len(alone) == len(after) and all(np.array_equal(a, b) for a, b in zip(alone, after))
     finally:
         L.check(m._lib.taco_debug_set_bf3(m._handle, 1, 0))
 

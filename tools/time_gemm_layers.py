@@ -31,8 +31,8 @@ for kind, layer, B, T, Cin, Cout, kw, mpw, act in cases:
     gf = 2.0 * B * T * Cin * Cout * kw * (2 if kind == "hw" else 1) / 1e9
     row = []
     for cfg in (1, 2):
-        L.taco_debug_set_bf3(m._handle, 0, 0)
-        L.taco_debug_force_gemm_config(m._handle, cfg)
+        taco_amd._lib.check(L.taco_debug_set_bf3(m._handle, 0, 0))
+        taco_amd._lib.check(L.taco_debug_force_gemm_config(m._handle, cfg))
         if kind == "conv":
             fn = lambda: taco_amd._lib.check(L.taco_conv1d_bn_f32(m._handle, st(), layer.encode(), C.c_void_p(x.data_ptr()), B, T, act, mpw, C.c_void_p(out.data_ptr())))
         elif kind == "dense":
@@ -41,11 +41,11 @@ for kind, layer, B, T, Cin, Cout, kw, mpw, act in cases:
             fn = lambda: taco_amd._lib.check(L.taco_highway_f32(m._handle, st(), layer.encode(), C.c_void_p(x.data_ptr()), B * T, C.c_void_p(out.data_ptr())))
         us = timeit(fn)
         row.append("cfg%d %7.1f us %5.1f TF" % (cfg, us, gf / us * 1e-3 * 1e3 / 1e3 * 1e3 / 1e3 if False else gf / (us * 1e-6) / 1e3))
-    L.taco_debug_force_gemm_config(m._handle, -1)
+    taco_amd._lib.check(L.taco_debug_force_gemm_config(m._handle, -1))
     if True:
-        for tn in (1, 3, 4, 5, 7, 9, 10):
-            L.taco_debug_set_bf3(m._handle, 1, tn)
+        for tn in (4, 5, 7, 9, 10):
+            taco_amd._lib.check(L.taco_debug_set_bf3(m._handle, 1, tn))
             us = timeit(fn)
             row.append("bf3t%d %7.1f us %5.1f TFeq" % (tn, us, gf / (us * 1e-6) / 1e3))
-        L.taco_debug_set_bf3(m._handle, 1, 0)
+        taco_amd._lib.check(L.taco_debug_set_bf3(m._handle, 1, 0))
     print("%-36s %6.1f GFLOP | " % (layer, gf) + " | ".join(row))
