@@ -180,6 +180,24 @@ size_t taco_gl_workspace_bytes(const taco_gl* g, int B, int T);
  * hash of `seed`).  iters < 0: griffin_lim_iters.  d_wav [B, taco_gl_num_samples(T)].  Needs hop*(T-1) > n_fft/2. */
 int taco_gl_inv_spectrogram(taco_gl* g, void* hip_stream, const float* d_spec, const float* d_init_uniform,
                             unsigned long long seed, int B, int T, int iters, float* d_wav, void* d_workspace, size_t workspace_bytes);
+/* The same per utterance length, as synthesizer.py:242-264 does it (`wav = wav[:spec_end_idx]; inv_spectrogram(wav.T)`): row b of d_wav
+ * [B, taco_gl_num_samples(T)] holds inv_spectrogram(spec[b, :f_b]) in its first hop*(f_b-1) samples and exact zeros after; frames
+ * t >= f_b have magnitude 0, take no part in the row's window sum-square, and every iteration's reflect padding is taken at the
+ * row's own ends.  d_frames [B] is device memory (NULL: every row keeps T) -- taco_attention_trim's d_spec_end as it stands -- and
+ * is only read on the device: no read-back, synchronisation or allocation, capturable.  Each value is clamped on the device to
+ * [taco_gl_min_frames, T], and d_num_samples [B] (nullable) receives hop*(f_b-1) for the clamped value.  NOT reproduced: the
+ * reference's trim can return 3 frames, which librosa serves by reflecting more than once; such a row is synthesised from
+ * taco_gl_min_frames frames here.  d_init_uniform[b, t, :] is used for t < f_b; with NULL the hash is indexed as in
+ * taco_gl_inv_spectrogram, so a row that keeps T frames gets that entry point's phases (and its output, bit for bit).
+ * T < taco_gl_min_frames: TACO_ERR_SHAPE.  Workspace: taco_gl_rows_workspace_bytes. */
+int taco_gl_min_frames(const taco_gl* g);                    /* smallest T with hop*(T-1) > n_fft/2: n_fft/2/hop + 2 */
+size_t taco_gl_rows_workspace_bytes(const taco_gl* g, int B, int T);
+int taco_gl_inv_spectrogram_rows(taco_gl* g, void* hip_stream, const float* d_spec, const int32_t* d_frames, const float* d_init_uniform,
+                                 unsigned long long seed, int B, int T, int iters, float* d_wav, int32_t* d_num_samples, void* d_workspace,
+                                 size_t workspace_bytes);
+/* save_audio's scaling to 16-bit PCM (audio/__init__.py:23-24) per row of d_wav [B, L]: peak = max|x| over the first d_num_samples[b]
+ * samples (NULL: L), pcm = (int16) trunc(x * (32767 / max(0.01, peak))), zeros past them.  d_pcm [B, L].  One launch. */
+int taco_wav_to_pcm16(void* hip_stream, const float* d_wav, const int32_t* d_num_samples, int B, int L, int16_t* d_pcm);
 
 /* ---- training-side entry points on flat buffers (loss, schedule, clip + Adam); forward/backward: taco_train_* below ---- */
 /* add_loss (tacotron.py:274-302).  d_mel_* [B,T,num_mels], d_lin_* [B,T,num_freq], d_loss_coeff [B] (nullable = 1).

@@ -121,6 +121,10 @@ PROTOTYPES = {
     "taco_gl_num_samples": (_I, [_P, _I]),
     "taco_gl_workspace_bytes": (_S, [_P, _I, _I]),
     "taco_gl_inv_spectrogram": (_I, [_P, _P, _P, _P, C.c_ulonglong, _I, _I, _I, _P, _P, _S]),
+    "taco_gl_min_frames": (_I, [_P]),
+    "taco_gl_rows_workspace_bytes": (_S, [_P, _I, _I]),
+    "taco_gl_inv_spectrogram_rows": (_I, [_P, _P, _P, _P, _P, C.c_ulonglong, _I, _I, _I, _P, _P, _P, _S]),
+    "taco_wav_to_pcm16": (_I, [_P, _P, _P, _I, _I, _P]),
     "taco_attention_trim": (_I, [_P, _P, _P, _I, _I, _I, _I, _P]),
     "taco_loss_f32": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _S]),
     "taco_learning_rate": (C.c_float, [C.c_longlong, C.c_float, _I, _I]),

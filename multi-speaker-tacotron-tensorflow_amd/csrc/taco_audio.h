@@ -14,13 +14,17 @@ struct taco_gl {
 };
 
 // ---- kernels ----
-// S = (10^((clip(x,0,1) * -min_db + min_db + ref_db) / 20))^power ; rows t >= T of every utterance slot are zero
-__global__ void k_gl_magnitude(const float* spec, float* S, int B, int T, int Tr, int F, float min_db, float ref_db, float power) {
+// Frames utterance b keeps: T, or frames[b] (device memory, taco_gl_inv_spectrogram_rows) clamped to [fmin, T].  Every kernel that
+// depends on an utterance's length takes the nullable `frames` and calls this; with NULL each one computes what it did before.
+__device__ __forceinline__ int gl_frames(const int* frames, int b, int T, int fmin) { return frames ? min(max(frames[b], fmin), T) : T; }
+// S = (10^((clip(x,0,1) * -min_db + min_db + ref_db) / 20))^power ; rows t >= the utterance's frames of every slot are zero
+__global__ void k_gl_magnitude(const float* spec, float* S, const int* frames, int fmin, int B, int T, int Tr, int F, float min_db,
+                               float ref_db, float power) {
   const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= (size_t)B * Tr * F) return;
   const int f = (int)(i % F); const size_t row = i / F; const int t = (int)(row % Tr), b = (int)(row / Tr);
   float v = 0.f;
-  if (t < T) {
+  if (t < gl_frames(frames, b, T, fmin)) {
     const float x = fminf(fmaxf(spec[((size_t)b * T + t) * F + f], 0.f), 1.f);
     const float db = x * -min_db + min_db + ref_db;
     v = powf(powf(10.f, db * 0.05f), power);
@@ -33,12 +37,13 @@ __device__ __forceinline__ float gl_hash_uniform(unsigned long long seed, size_t
   return (float)(z >> 40) * (1.0f / 16777216.0f);
 }
 // X = S * exp(2 pi i u): u from the caller ([B,T,F], np.random.rand of audio/__init__.py:77) or from the counter hash
-__global__ void k_gl_init_phase(const float* S, const float* u, unsigned long long seed, float* X, int B, int T, int Tr, int F) {
+__global__ void k_gl_init_phase(const float* S, const float* u, unsigned long long seed, float* X, const int* frames, int fmin, int B,
+                                int T, int Tr, int F) {
   const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= (size_t)B * Tr * F) return;
   const int f = (int)(i % F); const size_t row = i / F; const int t = (int)(row % Tr), b = (int)(row / Tr);
   float re = 0.f, im = 0.f;
-  if (t < T) {
+  if (t < gl_frames(frames, b, T, fmin)) {
     const float uu = u ? u[((size_t)b * T + t) * F + f] : gl_hash_uniform(seed, i);
     float sn, cs; sincosf(6.283185307179586f * uu, &sn, &cs);
     re = S[i] * cs; im = S[i] * sn;
@@ -65,39 +70,46 @@ __global__ void k_gl_wss(const float* w2, float* inv, int T, int n_fft, int hop)
   for (int t = t1; t >= 0 && p - t * hop < n_fft; --t) s += w2[p - t * hop];
   inv[p] = s > 1.17549435e-38f ? 1.0f / s : 1.0f;
 }
-// overlap-add of the windowed frames Y [B, Tr, win] -> centre part of ypad [B, slot]; then reflect padding of n_fft/2 on both sides
-__global__ void k_gl_overlap_add(const float* Y, const float* wss_inv, float* ypad, int B, int T, int Tr, int win, int hop, int lpad,
-                                 int n_fft, size_t slot) {
-  const int L = hop * (T - 1);
-  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= (size_t)B * L) return;
-  const int b = (int)(i / L), s = (int)(i % L), p = s + n_fft / 2;
-  float acc = 0.f;
-  const int t1 = min(T - 1, (p - lpad) / hop);
+// overlap-add of the windowed frames Y [B, Tr, win] -> centre part of ypad [B, slot], and the reflect padding of n_fft/2 on both sides
+// (np.pad mode="reflect": y[-k] = y[k], y[L-1+k] = y[L-1-k], k = 1 .. n_fft/2), written by the thread that owns the mirrored sample.
+// An utterance that keeps fewer than T frames is written up to its own L = hop*(frames-1) samples and reflected there (what lies
+// beyond in its slot is read only by STFT frames whose magnitude is 0); it divides by the window sum-square of its own frames,
+// summed here from w2 alongside the samples, while one that keeps all T uses the table of k_gl_wss.
+// grid (blocks of a row, B): the utterance is uniform in a workgroup.
+__global__ void k_gl_overlap_add(const float* Y, const float* wss_inv, const float* w2, float* ypad, const int* frames, int fmin,
+                                 int T, int Tr, int win, int hop, int lpad, int n_fft, size_t slot) {
+  const int half = n_fft / 2;
+  const int b = blockIdx.y, s = blockIdx.x * blockDim.x + threadIdx.x, p = s + half;
+  const int fb = gl_frames(frames, b, T, fmin), L = hop * (fb - 1);          // L > n_fft/2 by the clamp to fmin
+  if (s >= L) return;
+  const bool own = fb < T;
+  float acc = 0.f, ws = 0.f;
+  const int t1 = min(fb - 1, (p - lpad) / hop);
   for (int t = t1; t >= 0; --t) {
     const int off = p - t * hop - lpad;
     if (off >= win) break;
     acc += Y[((size_t)b * Tr + t) * win + off];
+    if (own) ws += w2[lpad + off];
   }
-  ypad[(size_t)b * slot + p] = acc * wss_inv[p];
-}
-__global__ void k_gl_reflect(float* ypad, int B, int T, int hop, int n_fft, size_t slot) {
-  const int half = n_fft / 2, L = hop * (T - 1);
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= B * half) return;
-  const int b = i / half, k = i % half + 1;            // k = 1 .. n_fft/2
+  const float v = acc * (own ? (ws > 1.17549435e-38f ? 1.0f / ws : 1.0f) : wss_inv[p]);
   float* y = ypad + (size_t)b * slot + half;             // y[0 .. L)
-  y[-k] = y[k];
-  y[L - 1 + k] = y[L - 1 - k];
+  y[s] = v;
+  if (s >= 1 && s <= half) y[-s] = v;
+  if (s >= L - 1 - half && s <= L - 2) y[2 * (L - 1) - s] = v;
 }
-// scipy.signal.lfilter([1], [1, -a], x): out[n] = x[n] + a*out[n-1]; one workgroup per utterance, chunked scan
-__global__ __launch_bounds__(1024) void k_inv_preemphasis(const float* ypad, float* wav, int L, int half, size_t slot, float a) {
+// scipy.signal.lfilter([1], [1, -a], x): out[n] = x[n] + a*out[n-1]; one workgroup per utterance, chunked scan.  The utterance's
+// own hop*(frames-1) samples are filtered, the rest of its row of L is zero; num_samples (nullable) receives that count.
+__global__ __launch_bounds__(1024) void k_inv_preemphasis(const float* ypad, float* wav, const int* frames, int fmin, int T, int hop,
+                                                          int* num_samples, int L, int half, size_t slot, float a) {
   __shared__ float ends[1024];
   __shared__ float carry[1024];
   const int b = blockIdx.x, tid = threadIdx.x;
   const float* x = ypad + (size_t)b * slot + half;
   float* out = wav + (size_t)b * L;
-  const int C = (L + 1023) / 1024, i0 = tid * C, i1 = min(L, i0 + C);
+  const int Lb = hop * (gl_frames(frames, b, T, fmin) - 1);
+  if (num_samples && tid == 0) num_samples[b] = Lb;
+  const int C = (L + 1023) / 1024, i0 = tid * C, i1 = min(Lb, i0 + C);
+  for (int i = max(i0, Lb); i < min(L, i0 + C); ++i) out[i] = 0.f;
   float acc = 0.f;
   for (int i = i0; i < i1; ++i) { acc = x[i] + a * acc; out[i] = acc; }
   ends[tid] = acc;
@@ -111,6 +123,24 @@ __global__ __launch_bounds__(1024) void k_inv_preemphasis(const float* ypad, flo
   const float c = carry[tid];
   float f = a;
   for (int i = i0; i < i1; ++i) { out[i] += f * c; f *= a; }
+}
+// save_audio's scaling (audio/__init__.py:23-24): x * 32767 / max(0.01, max|x|) truncated to int16, per utterance over its first
+// num_samples[b] (NULL: L) samples, zeros after.  One workgroup per utterance: the peak (a max: the same in any order), then the scaling.
+__global__ __launch_bounds__(1024) void k_wav_to_pcm16(const float* wav, const int* num_samples, int L, short* pcm) {
+  __shared__ float part[16];
+  const int b = blockIdx.x, tid = threadIdx.x;
+  const float* x = wav + (size_t)b * L;
+  short* out = pcm + (size_t)b * L;
+  const int n = num_samples ? min(max(num_samples[b], 0), L) : L;
+  float peak = 0.f;
+  for (int i = tid; i < n; i += 1024) peak = fmaxf(peak, fabsf(x[i]));
+  for (int o = 32; o > 0; o >>= 1) peak = fmaxf(peak, __shfl_xor(peak, o));
+  if ((tid & 63) == 0) part[tid >> 6] = peak;
+  __syncthreads();
+  peak = part[0];
+  for (int k = 1; k < 16; ++k) peak = fmaxf(peak, part[k]);
+  const float scale = 32767.0f / fmaxf(0.01f, peak);
+  for (int i = tid; i < L; i += 1024) out[i] = i < n ? (short)(int)fminf(fmaxf(truncf(x[i] * scale), -32767.f), 32767.f) : (short)0;
 }
 
 // ---- host ----

@@ -61,17 +61,23 @@ void taco_gl_destroy(taco_gl* g) {
 
 int taco_gl_num_samples(const taco_gl* g, int T) { return (g && T > 0) ? g->hop * (T - 1) : 0; }
 
+int taco_gl_min_frames(const taco_gl* g) { return g ? g->n_fft / 2 / g->hop + 2 : 0; }    // smallest T with hop*(T-1) > n_fft/2
+
 size_t taco_gl_workspace_bytes(const taco_gl* g, int B, int T) {
   if (!g || B <= 0 || T <= 1) return 0;
   Carver cv(nullptr, 0);
   GlWs w; carve_gl(cv, g, B, T, w);
   return cv.off;
 }
+size_t taco_gl_rows_workspace_bytes(const taco_gl* g, int B, int T) { return taco_gl_workspace_bytes(g, B, T); }   // same slot layout
 
-int taco_gl_inv_spectrogram(taco_gl* g, void* hip_stream, const float* d_spec, const float* d_init_uniform, unsigned long long seed,
-                            int B, int T, int iters, float* d_wav, void* d_workspace, size_t workspace_bytes) {
+// d_frames NULL: every utterance keeps T frames (taco_gl_inv_spectrogram); else the kernels read each utterance's count from it,
+// clamped to [taco_gl_min_frames, T]
+int taco_gl_inv_spectrogram_rows(taco_gl* g, void* hip_stream, const float* d_spec, const int32_t* d_frames, const float* d_init_uniform,
+                                 unsigned long long seed, int B, int T, int iters, float* d_wav, int32_t* d_num_samples, void* d_workspace,
+                                 size_t workspace_bytes) {
   if (!g || !d_spec || !d_wav || !d_workspace || B <= 0 || T <= 1) return fail(TACO_ERR_ARG, "bad argument");
-  const int L = g->hop * (T - 1), half = g->n_fft / 2;
+  const int L = g->hop * (T - 1), half = g->n_fft / 2, fmin = taco_gl_min_frames(g);
   if (L <= half) return fail(TACO_ERR_SHAPE, "utterance too short for reflect padding: hop*(T-1) = %d <= n_fft/2 = %d", L, half);
   HIPCHK(hipSetDevice(g->gm->device));
   hipStream_t st = (hipStream_t)hip_stream;
@@ -83,27 +89,43 @@ int taco_gl_inv_spectrogram(taco_gl* g, void* hip_stream, const float* d_spec, c
   if (iters < 0) iters = g->hp.griffin_lim_iters;
   HIPCHK(zero_async(w.ypad, ((size_t)B * slot + 2 * g->n_fft + g->win) * sizeof(float), st));
   hipLaunchKernelGGL(k_gl_wss, EWGRID((size_t)L + g->n_fft), 0, st, AP(g->gm, g->w2), w.wss, T, g->n_fft, g->hop);
-  hipLaunchKernelGGL(k_gl_magnitude, EWGRID(R * F), 0, st, d_spec, w.S, B, T, Tr, F, g->hp.min_level_db, g->hp.ref_level_db, g->hp.power);
-  hipLaunchKernelGGL(k_gl_init_phase, EWGRID(R * F), 0, st, w.S, d_init_uniform, seed, w.X, B, T, Tr, F);
+  hipLaunchKernelGGL(k_gl_magnitude, EWGRID(R * F), 0, st, d_spec, w.S, d_frames, fmin, B, T, Tr, F, g->hp.min_level_db, g->hp.ref_level_db,
+                     g->hp.power);
+  hipLaunchKernelGGL(k_gl_init_phase, EWGRID(R * F), 0, st, w.S, d_init_uniform, seed, w.X, d_frames, fmin, B, T, Tr, F);
   HIPCHK(hipGetLastError());
-  auto synth = [&]() -> int {     // y = istft(X): frames = X . IDFT_w ; overlap-add / window sum-square ; reflect pad for the next stft
+  auto synth = [&]() -> int {     // y = istft(X): frames = X . IDFT_w ; overlap-add / window sum-square with the reflect pad for the next stft
     GemmCall c; c.x = w.X; c.ldx = 2 * F; c.M = (int)R; c.out = w.Y; c.ldo = g->win;
     TRY(run_gemm(g->gm, st, &g->inv, 1, false, c));
-    hipLaunchKernelGGL(k_gl_overlap_add, EWGRID((size_t)B * L), 0, st, w.Y, w.wss, w.ypad, B, T, Tr, g->win, g->hop, g->lpad, g->n_fft, slot);
-    hipLaunchKernelGGL(k_gl_reflect, EWGRID((size_t)B * half), 0, st, w.ypad, B, T, g->hop, g->n_fft, slot);
+    hipLaunchKernelGGL(k_gl_overlap_add, dim3((L + 255) / 256, B), dim3(256), 0, st, w.Y, w.wss, AP(g->gm, g->w2), w.ypad, d_frames, fmin, T, Tr,
+                       g->win, g->hop, g->lpad, g->n_fft, slot);
     HIPCHK(hipGetLastError());
     return 0;
   };
   TRY(synth());
   for (int it = 0; it < iters; ++it) {
-    // est = stft(y): row (b, t) of the frame matrix is the hop-strided window ypad[b*slot + t*hop + lpad ...][0 .. win)
+    // est = stft(y): row (b, t) of the frame matrix is the hop-strided window ypad[b*slot + t*hop + lpad ...][0 .. win); rows past an
+    // utterance's own frames read whatever its slot holds there and are multiplied by S = 0 in k_gl_project
     GemmCall c; c.x = w.ypad + g->lpad; c.ldx = g->hop; c.M = (int)R; c.out = w.est; c.ldo = 2 * F;
     TRY(run_gemm(g->gm, st, &g->fwd, 1, false, c));
     hipLaunchKernelGGL(k_gl_project, EWGRID(R * F), 0, st, w.est, w.S, w.X, R, F);
     HIPCHK(hipGetLastError());
     TRY(synth());
   }
-  hipLaunchKernelGGL(k_inv_preemphasis, dim3(B), dim3(1024), 0, st, w.ypad, d_wav, L, half, slot, g->hp.preemphasis);
+  hipLaunchKernelGGL(k_inv_preemphasis, dim3(B), dim3(1024), 0, st, w.ypad, d_wav, d_frames, fmin, T, g->hop, d_num_samples, L, half, slot,
+                     g->hp.preemphasis);
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
+int taco_gl_inv_spectrogram(taco_gl* g, void* hip_stream, const float* d_spec, const float* d_init_uniform, unsigned long long seed,
+                            int B, int T, int iters, float* d_wav, void* d_workspace, size_t workspace_bytes) {
+  return taco_gl_inv_spectrogram_rows(g, hip_stream, d_spec, nullptr, d_init_uniform, seed, B, T, iters, d_wav, nullptr, d_workspace,
+                                      workspace_bytes);
+}
+
+int taco_wav_to_pcm16(void* hip_stream, const float* d_wav, const int32_t* d_num_samples, int B, int L, int16_t* d_pcm) {
+  if (!d_wav || !d_pcm || B <= 0 || L <= 0) return fail(TACO_ERR_ARG, "bad argument");
+  hipLaunchKernelGGL(k_wav_to_pcm16, dim3(B), dim3(1024), 0, (hipStream_t)hip_stream, d_wav, d_num_samples, L, d_pcm);
   HIPCHK(hipGetLastError());
   return 0;
 }

@@ -82,11 +82,8 @@ class Synthesizer(object):
         self.model.initialize(None, None, self.num_speakers, None, device=device)   # placeholders (:39-52)
         return self
 
-    def synthesize(self, texts=None, tokens=None, base_path=None, paths=None, speaker_ids=None,
-                   start_of_sentence=None, end_of_sentence=True, pre_word_num=0, post_word_num=0,
-                   pre_surplus_idx=0, post_surplus_idx=1, use_short_concat=False,
-                   manual_attention_mode=0, base_alignment_path=None, librosa_trim=False,
-                   attention_trim=True, manual_alignments=None, vocode=False):
+    def _token_rows(self, texts, tokens):
+        """texts (through the tokeniser) or ready token rows -> [N, T_in] array"""
         if type(texts) == str:
             texts = [texts]
         if texts is not None and tokens is None:
@@ -109,6 +106,14 @@ class Synthesizer(object):
         sequences = np.asarray(sequences)
         if sequences.ndim != 2:
             raise Exception("token rows must have equal length (pre-pad with 0 as eval.py / train.py:27-40 do)")
+        return sequences
+
+    def synthesize(self, texts=None, tokens=None, base_path=None, paths=None, speaker_ids=None,
+                   start_of_sentence=None, end_of_sentence=True, pre_word_num=0, post_word_num=0,
+                   pre_surplus_idx=0, post_surplus_idx=1, use_short_concat=False,
+                   manual_attention_mode=0, base_alignment_path=None, librosa_trim=False,
+                   attention_trim=True, manual_alignments=None, vocode=False):
+        sequences = self._token_rows(texts, tokens)
         input_lengths = np.argmax(sequences == EOS_ID, 1).astype(np.int32)             # synthesizer.py:120
         if type(speaker_ids) == dict:
             raise Exception("dict-valued speaker_ids is broken in the reference (synthesizer.py:153-164) and not supported")
@@ -136,12 +141,41 @@ class Synthesizer(object):
             self.wavs = self.inv_spectrogram(linear, self.spec_end_idx)
         return linear, alignments
 
-    def inv_spectrogram(self, linear, spec_end_idx=None):
-        """audio/__init__.py:54-56 for a batch [N, T, num_freq]; returns a list of 1-D float32 arrays (each cut to the samples its
-        own frames produce when spec_end_idx is given: Griffin-Lim runs on the padded batch, frames past the end are silence-level)."""
+    def synthesize_audio(self, texts=None, tokens=None, speaker_ids=None, end_of_sentence=True, attention_trim=True,
+                         manual_alignments=None, seed=0, iters=None, pcm=True):
+        """The reference's synthesize -> plot_graph_and_save_audio chain up to the samples save_audio writes (synthesizer.py:119-126,
+        242-264; audio/__init__.py:22-25), everything between the token upload and the audio download on the device: the forward, the
+        attention trim on the device alignments, Griffin-Lim on every utterance's own frames read from the trim kernel's output, the
+        scaling to 16-bit PCM.  Returns a list of 1-D arrays, int16 (pcm) or float32, each cut to its own length; `spec_end_idx` is set
+        as by `synthesize`.  Frame counts below GriffinLim.min_frames() are raised to it (include/taco_abi.h).  `seed` picks the
+        initial phases (the reference draws np.random.rand).  Copies to the host: the audio buffer and two [N] int vectors."""
+        sequences = self._token_rows(texts, tokens)
+        input_lengths = np.argmax(sequences == EOS_ID, 1).astype(np.int32)             # synthesizer.py:120
+        if type(speaker_ids) == dict:
+            raise Exception("dict-valued speaker_ids is broken in the reference (synthesizer.py:153-164) and not supported")
+        linear, alignments = self.model.run(
+            inputs=sequences.astype(np.int32), input_lengths=input_lengths, speaker_id=speaker_ids,
+            manual_alignments=manual_alignments, is_manual_attention=manual_alignments is not None)
+        frames = None
+        if attention_trim and end_of_sentence:
+            frames = self._attention_trim_device(alignments, [len(seq) for seq in sequences])
+        gl = self._griffin_lim()
+        wav, num_samples = gl.inv_spectrogram_rows(linear, frames, seed=seed, iters=iters)
+        audio = gl.pcm16(wav, num_samples) if pcm else wav
+        self.spec_end_idx = None if frames is None else frames.cpu().numpy()
+        audio = audio.cpu().numpy()
+        return [a[:n] for a, n in zip(audio, num_samples.cpu().numpy())]
+
+    def _griffin_lim(self):
         from .audio import GriffinLim
         if getattr(self, "_gl", None) is None:
             self._gl = GriffinLim(self.hparams, device=str(self.model.device))
+        return self._gl
+
+    def inv_spectrogram(self, linear, spec_end_idx=None):
+        """audio/__init__.py:54-56 for a batch [N, T, num_freq]; returns a list of 1-D float32 arrays (each cut to the samples its
+        own frames produce when spec_end_idx is given: Griffin-Lim runs on the padded batch, frames past the end are silence-level)."""
+        self._griffin_lim()
         x = np.array(linear, np.float32, copy=True)
         if spec_end_idx is not None:
             for i, e in enumerate(spec_end_idx):
@@ -154,6 +188,9 @@ class Synthesizer(object):
 
     def attention_trim_end(self, alignments, sequence_lengths):
         """spec_end_idx = reduction_factor * j + 3 per utterance (synthesizer.py:242-262); alignments [N, T_in, T_dec]."""
+        return self._attention_trim_device(alignments, sequence_lengths).cpu().numpy()
+
+    def _attention_trim_device(self, alignments, sequence_lengths):
         import ctypes as C
         import torch
         from . import _lib
@@ -166,4 +203,4 @@ class Synthesizer(object):
         with torch.cuda.device(al.device):
             _lib.check(m._lib.taco_attention_trim(C.c_void_p(torch.cuda.current_stream().cuda_stream), p(al), p(sl), N, T_in, n,
                                                   self.hparams.reduction_factor, p(out)))
-        return out.cpu().numpy()
+        return out

@@ -1,6 +1,9 @@
 #!/usr/bin/env python
 """Spectrogram -> waveform (Griffin-Lim, 60 iterations) at the C2 output shape: B=32 utterances x 512 frames x 1025 bins.
-Prints one JSON line: audio seconds produced per second, with the NumPy oracle (FFT-based, one utterance) timed beside it."""
+Prints one JSON line: audio seconds produced per second, with the NumPy oracle (FFT-based, one utterance) timed beside it.
+"rows" holds the per-utterance-length entry point (GriffinLim.inv_spectrogram_rows) timed in the same run, alternating with the
+existing one: all rows full (must cost what the existing entry point costs, within that entry point's own window-to-window spread)
+and a seeded spread of lengths uniform in [T/4, T], followed by the PCM16 kernel."""
 import json, os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "oracle"))
@@ -11,16 +14,31 @@ hp = taco_amd.hparams
 gl = taco_amd.GriffinLim(hp)
 rs = np.random.RandomState(0)
 spec = torch.from_numpy(rs.rand(B, T, F).astype(np.float32)).cuda()
-for _ in range(2):
-    wav = gl.inv_spectrogram(spec)
+full = torch.full((B,), T, dtype=torch.int32, device="cuda")
+ragged = torch.from_numpy(np.random.RandomState(1).randint(T // 4, T + 1, B).astype(np.int32)).cuda()
+arms = {"existing": lambda: gl.inv_spectrogram(spec), "rows_full": lambda: gl.inv_spectrogram_rows(spec, full)[0],
+        "rows_ragged": lambda: gl.inv_spectrogram_rows(spec, ragged)[0]}
+for f in arms.values():
+    for _ in range(2):
+        f()
 torch.cuda.synchronize()
 e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-n = 5
-e0.record()
-for _ in range(n):
-    wav = gl.inv_spectrogram(spec)
-e1.record(); torch.cuda.synchronize()
-ms = e0.elapsed_time(e1) / n
+n = 10
+def window(f):
+    e0.record()
+    for _ in range(n):
+        out = f()
+    e1.record(); torch.cuda.synchronize()
+    return e0.elapsed_time(e1) / n, out
+times = {k: [] for k in arms}
+for _ in range(4):                                             # existing, rows_full, existing, rows_ragged: the versions alternate
+    for k in ("existing", "rows_full", "existing", "rows_ragged"):
+        times[k].append(window(arms[k])[0])
+ms, wav = window(arms["existing"]); times["existing"].append(ms)
+ms = float(np.median(times["existing"]))
+same = bool(torch.equal(arms["rows_full"](), wav))
+rw, rn = gl.inv_spectrogram_rows(spec, ragged)
+pcm_ms = window(lambda: gl.pcm16(rw, rn))[0]
 L = wav.shape[1]; audio_s = B * L / hp.sample_rate
 gflop = 2.0 * 2 * (B * (T + 7)) * 1200 * 2050 * 61 / 1e9      # two windowed-DFT products per iteration (+1 synthesis)
 ahp = A.AudioHParams()
@@ -28,5 +46,10 @@ t0 = time.perf_counter(); A.inv_spectrogram(spec[0].cpu().numpy().astype(np.floa
 print(json.dumps({"metric": "audio seconds synthesised per second (Griffin-Lim, 60 iterations)", "value": audio_s / (ms / 1e3), "unit": "x realtime",
                   "ms_per_batch": ms, "batch": "B=%d x T=%d frames x %d bins -> %d samples each (%.1f s of audio at %d Hz)" % (B, T, F, L, L / hp.sample_rate, hp.sample_rate),
                   "dft_gemm_TFLOPs_equiv": gflop / ms, "finite": bool(torch.isfinite(wav).all()),
+                  "rows": {"windows": "%d calls each, alternating" % n, "existing_ms": times["existing"],
+                           "existing_spread_ms": max(times["existing"]) - min(times["existing"]), "rows_full_ms": times["rows_full"],
+                           "rows_full_minus_existing_ms": float(np.median(times["rows_full"])) - ms, "rows_full_equals_existing": same,
+                           "rows_ragged_ms": times["rows_ragged"], "ragged_frames": "seeded, uniform in [%d, %d], mean %.0f" % (T // 4, T, float(ragged.float().mean())),
+                           "ragged_audio_s": float(rn.sum()) / hp.sample_rate, "pcm16_ms": pcm_ms},
                   "cpu_baseline": {"kind": "port", "sample": "oracle/audio_oracle.py (NumPy FFT, float64), 1 utterance", "seconds_per_utterance": cpu_s,
                                    "value": (L / hp.sample_rate) / cpu_s, "unit": "x realtime", "cores": 1}}))
