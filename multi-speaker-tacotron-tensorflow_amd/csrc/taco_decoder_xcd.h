@@ -330,6 +330,20 @@ __device__ __forceinline__ void dx_reduce(const float (&a)[NC][RG], float (&out)
     for (int q = 0; q < RL; ++q) out[c][q] = dx_xrow32(d[c][q]);
 }
 
+// A pass that runs AHEAD of the gather behind it has to be finished when the poll starts (round 7): its sums are first used after the barrier, and
+// the compiler sank the FMAs to that use -- behind the poll, on the critical path of the stage that waits for the vector.  These keep the
+// accumulators where the source forms them.
+template <int RG>
+__device__ __forceinline__ void dx_ahead(taco_f32x2 (&a)[RG]) {
+#pragma unroll
+  for (int r = 0; r < RG; ++r) asm volatile("" : "+v"(a[r]) : : "memory");
+}
+template <int RG>
+__device__ __forceinline__ void dx_ahead(float (&a)[1][RG]) {
+#pragma unroll
+  for (int r = 0; r < RG; ++r) asm volatile("" : "+v"(a[0][r]) : : "memory");
+}
+
 // ---- round 5: the step's VALU diet (the passes and reductions of k_decoder_xcd are issue bound: two waves per SIMD, ~130 instructions
 // each per gates stage) ----
 #ifndef DX_DIET
@@ -357,6 +371,21 @@ __host__ __device__ constexpr int dxw_src(int k, int h, int PD) {      // pack r
   if (r >= DXR_F) return dxw_two(DXR_F, r, h);
   return r + h;                                                         // single columns: P2, AC, G1C, the third column of G2X, G2C, P1C, P1O
 }
+// The input rows of a pass, all requested before the first FMA (round 7).  Left to the scheduler, the single-column passes -- the three candidate
+// stages and prenet layer 2, each on the step's critical path -- read one row, waited for it, ran its four FMAs and only then asked for the next:
+// RG LDS round trips in a row where one is needed.  The empty asm makes every row of a block of four live at one point, so the four reads are
+// issued back to back and waited for once; the FMAs that follow are the same instructions in the same order.
+typedef float dx_f32x4 __attribute__((ext_vector_type(4)));
+template <int RG, int LD>
+__device__ __forceinline__ void dx_rows4(const float* x, int lane, dx_f32x4 (&xv)[RG]) {
+#pragma unroll
+  for (int r = 0; r < RG; ++r) xv[r] = *reinterpret_cast<const dx_f32x4*>(x + r * LD + 4 * lane);
+#pragma unroll
+  for (int r0 = 0; r0 < RG; r0 += 4) {
+    if constexpr (RG >= 4) asm volatile("" : "+v"(xv[r0]), "+v"(xv[r0 + 1]), "+v"(xv[r0 + 2]), "+v"(xv[r0 + 3]));
+    else if constexpr (RG == 2) asm volatile("" : "+v"(xv[0]), "+v"(xv[1]));
+  }
+}
 #define DXQ_FMA(acc, xs, wp) \
   do { if (DX_DIET) acc = __builtin_elementwise_fma((taco_f32x2){xs, xs}, wp, acc); else { acc.x = fmaf((wp).x, xs, acc.x); acc.y = fmaf((wp).y, xs, acc.y); } } while (0)
 template <int RG>
@@ -368,9 +397,11 @@ __device__ __forceinline__ void dxq_zero(taco_f32x2 (&acc)[RG]) {
 template <int REG0, int RG, int LD = DXS_LD>
 __device__ __forceinline__ void dxw_single(const taco_f32x2 (&WP)[DX_NWP], const float* x, int lane, float (&acc)[1][RG]) {
   constexpr int k = REG0 / 2;
+  dx_f32x4 xr[RG];
+  dx_rows4<RG, LD>(x, lane, xr);
 #pragma unroll
   for (int r = 0; r < RG; ++r) {
-    const float4 xv = *reinterpret_cast<const float4*>(x + r * LD + 4 * lane);
+    const dx_f32x4 xv = xr[r];
     acc[0][r] = fmaf(WP[k].x, xv.x, acc[0][r]); acc[0][r] = fmaf(WP[k].y, xv.y, acc[0][r]);
     acc[0][r] = fmaf(WP[k + 1].x, xv.z, acc[0][r]); acc[0][r] = fmaf(WP[k + 1].y, xv.w, acc[0][r]);
   }
@@ -379,9 +410,11 @@ __device__ __forceinline__ void dxw_single(const taco_f32x2 (&WP)[DX_NWP], const
 template <int REG0, int RG, int LD = DXS_LD>
 __device__ __forceinline__ void dxw_pair(const taco_f32x2 (&WP)[DX_NWP], const float* x, int lane, taco_f32x2 (&acc)[RG]) {
   constexpr int k = REG0 / 2;
+  dx_f32x4 xr[RG];
+  dx_rows4<RG, LD>(x, lane, xr);
 #pragma unroll
   for (int r = 0; r < RG; ++r) {
-    const float4 xv = *reinterpret_cast<const float4*>(x + r * LD + 4 * lane);
+    const dx_f32x4 xv = xr[r];
     DXQ_FMA(acc[r], xv.x, WP[k]); DXQ_FMA(acc[r], xv.y, WP[k + 1]); DXQ_FMA(acc[r], xv.z, WP[k + 2]); DXQ_FMA(acc[r], xv.w, WP[k + 3]);
   }
 }
@@ -389,9 +422,11 @@ __device__ __forceinline__ void dxw_pair(const taco_f32x2 (&WP)[DX_NWP], const f
 template <int REG0, int RG, int LD = DXS_LD>
 __device__ __forceinline__ void dxw_quad(const taco_f32x2 (&WP)[DX_NWP], const float* x, int lane, taco_f32x2 (&p0)[RG], taco_f32x2 (&p1)[RG]) {
   constexpr int k = REG0 / 2;
+  dx_f32x4 xr[RG];
+  dx_rows4<RG, LD>(x, lane, xr);
 #pragma unroll
   for (int r = 0; r < RG; ++r) {
-    const float4 xv = *reinterpret_cast<const float4*>(x + r * LD + 4 * lane);
+    const dx_f32x4 xv = xr[r];
     DXQ_FMA(p0[r], xv.x, WP[k]); DXQ_FMA(p1[r], xv.x, WP[k + 4]);
     DXQ_FMA(p0[r], xv.y, WP[k + 1]); DXQ_FMA(p1[r], xv.y, WP[k + 5]);
     DXQ_FMA(p0[r], xv.z, WP[k + 2]); DXQ_FMA(p1[r], xv.z, WP[k + 6]);
@@ -402,9 +437,11 @@ __device__ __forceinline__ void dxw_quad(const taco_f32x2 (&WP)[DX_NWP], const f
 template <int REGP, int REGS, int RG, int LD = DXS_LD>
 __device__ __forceinline__ void dxw_pair_single(const taco_f32x2 (&WP)[DX_NWP], const float* x, int lane, taco_f32x2 (&p)[RG], float (&sg)[1][RG]) {
   constexpr int k = REGP / 2, ks = REGS / 2;
+  dx_f32x4 xr[RG];
+  dx_rows4<RG, LD>(x, lane, xr);
 #pragma unroll
   for (int r = 0; r < RG; ++r) {
-    const float4 xv = *reinterpret_cast<const float4*>(x + r * LD + 4 * lane);
+    const dx_f32x4 xv = xr[r];
     DXQ_FMA(p[r], xv.x, WP[k]); sg[0][r] = fmaf(WP[ks].x, xv.x, sg[0][r]);
     DXQ_FMA(p[r], xv.y, WP[k + 1]); sg[0][r] = fmaf(WP[ks].y, xv.y, sg[0][r]);
     DXQ_FMA(p[r], xv.z, WP[k + 2]); sg[0][r] = fmaf(WP[ks + 1].x, xv.z, sg[0][r]);
@@ -507,7 +544,10 @@ __device__ __forceinline__ void dxs_reduce(const float (&a)[NC][RG], float (&out
 #pragma unroll
     for (int c = 0; c < NC; ++c)
 #pragma unroll
-      for (int q = 0; q < RL; ++q) out[c][q] = d[c][q] + DX_DPP0(d[c][q], 0x140);      // row_mirror
+      for (int q = 0; q < RL; ++q) {
+        out[c][q] = d[c][q] + DX_DPP0(d[c][q], 0x140);      // row_mirror
+        asm("" : "+v"(out[c][q]));      // (round 7: the add stays here, one v_add_f32_dpp; sunk into the epilogue's branch it became a zeroing move, a DPP move and an add)
+      }
   }
 }
 
@@ -560,6 +600,12 @@ __device__ __forceinline__ void dx_store_local(dx_gu64* p, unsigned long long g)
   else if (DX_PUB_MODE == 3) *p = g;
   else __hip_atomic_store(p, g, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);           // sc0: stays in this XCD's L2
 }
+// Granule `idx` of a group's exchange buffer as the buffer's (wave-uniform) base + a 32-bit byte offset (round 7): the access is one instruction
+// with the base in an SGPR pair and the offset in one VGPR.  As X + xl.field + index the compiler kept a 64-bit base per exchange field in SGPRs
+// (spilled to VGPR lanes and read back with v_readlane inside the step) and built every address with 64-bit VALU adds.  The buffer is far below 4 GB.
+__device__ __forceinline__ dx_gu64* dx_at(const dx_gu64* X, unsigned idx) {
+  return (dx_gu64*)((__attribute__((address_space(1))) char*)X + (size_t)(idx * 8u));
+}
 template <int WTC = -1>
 __device__ __forceinline__ void dx_publish(dx_gu64* p, float v, unsigned tag, const DxRt& rt) {
   const unsigned long long g = ((unsigned long long)tag << 32) | (unsigned long long)__float_as_uint(v);
@@ -587,7 +633,7 @@ __device__ __forceinline__ void dx_publish_n(dx_gu64* p, int stride, const float
 // Poll N granules (p0 + u*stride) until every one carries `tag` (L1-bypassing loads).  All N are re-requested together on every
 // round, so a late producer costs one L2 round trip after its store lands, not one per granule.  Bounded.
 template <int N, int DLY = 0>
-__device__ __forceinline__ void dx_poll(const dx_gu64* p0, size_t stride, unsigned tag, float (&v)[N], DxRt& rt) {
+__device__ __forceinline__ void dx_poll_at(const dx_gu64* X, unsigned idx0, unsigned stride, unsigned tag, float (&v)[N], DxRt& rt) {
   // (keeping a second round of requests in flight behind the one being examined was measured: 11.8 -> 14.2 us per decoder step at
   // C2 -- the extra L2 requests of 16 K pollers delay the very stores they are waiting for)
   unsigned long long g[N];
@@ -596,7 +642,7 @@ __device__ __forceinline__ void dx_poll(const dx_gu64* p0, size_t stride, unsign
   for (;;) {
     bool ok = true;
 #pragma unroll
-    for (int u = 0; u < N; ++u) g[u] = __hip_atomic_load(p0 + u * stride, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    for (int u = 0; u < N; ++u) g[u] = __hip_atomic_load(dx_at(X, idx0 + (unsigned)u * stride), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 #pragma unroll
     for (int u = 0; u < N; ++u) ok = ok && ((unsigned)(g[u] >> 32) == tag);
     if (ok || rt.dead) break;
@@ -611,7 +657,11 @@ __device__ __forceinline__ void dx_poll(const dx_gu64* p0, size_t stride, unsign
 #pragma unroll
   for (int u = 0; u < N; ++u) v[u] = __uint_as_float((unsigned)g[u]);
 }
-// all-gather of a published [RG][N] vector into the LDS state vector at column offset `off` (N a power of two);
+template <int N, int DLY = 0>
+__device__ __forceinline__ void dx_poll(const dx_gu64* p0, size_t stride, unsigned tag, float (&v)[N], DxRt& rt) {
+  dx_poll_at<N, DLY>(p0, 0u, (unsigned)stride, tag, v, rt);
+}
+// all-gather of a published [RG][N] vector (granules X[base ..]) into the LDS state vector at column offset `off` (N a power of two);
 // RES: dst2[r][n] = value + res[r][n] as well (ResidualWrapper output, tacotron.py:172)
 // Two ADJACENT granules with one 16-byte request (each 8-byte half is one producer's single 8-byte store; a half that has not landed
 // fails its own tag test and the pair is asked for again).  Used where a thread collects four or more granules per gather (eight rows
@@ -619,7 +669,7 @@ __device__ __forceinline__ void dx_poll(const dx_gu64* p0, size_t stride, unsign
 // (tools/ubench_rowsets, variant T) 13.96 -> 12.63 us per step at eight rows, and nothing at two granules per thread (C2's decoder).
 typedef unsigned long long dx_u64x2 __attribute__((ext_vector_type(2)));
 template <int NP, int DLY = 0>
-__device__ __forceinline__ void dx_poll_pairs(const dx_gu64* p0, size_t stride, unsigned tag, float (&v)[2 * NP], DxRt& rt) {
+__device__ __forceinline__ void dx_poll_pairs(const dx_gu64* X, unsigned idx0, unsigned stride, unsigned tag, float (&v)[2 * NP], DxRt& rt) {
   dx_u64x2 g[NP];
   unsigned spins = 0;
   dx_first_poll_sleep<DLY>(rt);
@@ -627,7 +677,7 @@ __device__ __forceinline__ void dx_poll_pairs(const dx_gu64* p0, size_t stride, 
     bool ok = true;
 #pragma unroll
     for (int u = 0; u < NP; ++u) {
-      const dx_gu64* p = p0 + u * stride;
+      const dx_gu64* p = dx_at(X, idx0 + (unsigned)u * stride);
       asm volatile("global_load_dwordx4 %0, %1, off sc1" : "=v"(g[u]) : "v"(p) : "memory");
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -645,15 +695,15 @@ __device__ __forceinline__ void dx_poll_pairs(const dx_gu64* p0, size_t stride, 
   for (int u = 0; u < NP; ++u) { v[2 * u] = __uint_as_float((unsigned)g[u][0]); v[2 * u + 1] = __uint_as_float((unsigned)g[u][1]); }
 }
 template <int RG, int N, bool RES, int LD = DXS_LD, int NT = DX_NT, int DLY = 0>
-__device__ __forceinline__ void dx_gather(const dx_gu64* X, unsigned tag, float* st, int off, int off_res, int off2, int tid, DxRt& rt) {
+__device__ __forceinline__ void dx_gather_at(const dx_gu64* X, unsigned base, unsigned tag, float* st, int off, int off_res, int off2, int tid, DxRt& rt) {
   constexpr int NI = (RG * N + NT - 1) / NT;
   if constexpr (NI >= 4 && NI % 2 == 0 && (RG * N) % (2 * NT) == 0 && N % 2 == 0) {
     constexpr int NP = NI / 2;
     float v[NI];
-    dx_poll_pairs<NP, DLY>(X + 2 * tid, (size_t)2 * NT, tag, v, rt);
+    dx_poll_pairs<NP, DLY>(X, base + 2u * (unsigned)tid, 2u * NT, tag, v, rt);
 #pragma unroll
     for (int u = 0; u < NP; ++u) {
-      const int i = 2 * (u * NT + tid), r = i / N, n = i % N;
+      const unsigned i = 2u * ((unsigned)(u * NT) + (unsigned)tid), r = i / (unsigned)N, n = i % (unsigned)N;
       *reinterpret_cast<float2*>(st + r * LD + off + n) = make_float2(v[2 * u], v[2 * u + 1]);
       if (RES) {
         const float2 rs = *reinterpret_cast<const float2*>(st + r * LD + off_res + n);
@@ -665,15 +715,19 @@ __device__ __forceinline__ void dx_gather(const dx_gu64* X, unsigned tag, float*
   const bool act = (RG * N >= NT) || tid < RG * N;
   if (act) {
     float v[NI];
-    dx_poll<NI, DLY>(X + tid, NT, tag, v, rt);
+    dx_poll_at<NI, DLY>(X, base + (unsigned)tid, NT, tag, v, rt);
 #pragma unroll
     for (int u = 0; u < NI; ++u) {
-      const int i = u * NT + tid;
-      const int r = i / N, n = i % N;
+      const unsigned i = (unsigned)(u * NT) + (unsigned)tid;      // (unsigned: a shift and a mask; the signed forms cost five instructions each)
+      const unsigned r = i / (unsigned)N, n = i % (unsigned)N;
       st[r * LD + off + n] = v[u];
       if (RES) st[r * LD + off2 + n] = v[u] + st[r * LD + off_res + n];
     }
   }
+}
+template <int RG, int N, bool RES, int LD = DXS_LD, int NT = DX_NT, int DLY = 0>
+__device__ __forceinline__ void dx_gather(const dx_gu64* X, unsigned tag, float* st, int off, int off_res, int off2, int tid, DxRt& rt) {
+  dx_gather_at<RG, N, RES, LD, NT, DLY>(X, 0u, tag, st, off, off_res, off2, tid, rt);
 }
 
 // The alignment normaliser of one row by ONE wave, lane = `cnt` (<= CMAX) consecutive positions starting at j0, values held in
@@ -964,6 +1018,11 @@ __device__ __forceinline__ void dx_body(const DxArgs& a, float* dx_smem, int gro
 #pragma unroll
   for (int q = 0; q < RL; ++q) erow[q] = dxs_row<RG>(lane, q);
 #define DX_RB(slot, q) rbl[((slot) * RG + erow[q]) * DX_NW + wave]
+  // Own-column bias of a stage whose epilogue is a branch of the publishing lanes (round 7): read from LDS BEFORE the gather the stage waits on and
+  // pinned behind it, so that the value is in a register when the reduction ends.  Read where it is used, the compiler put the ds_read and its wait
+  // inside that branch: one LDS round trip between the last add of the reduction and the publish, in every such stage.
+#define DX_BIAS_AHEAD(var, slot) float var = bl[(slot) * DX_NW + wave]
+#define DX_BIAS_HERE(var) asm volatile("" : "+v"(var))
   float g_u[RL], g_cx[RL], g_h[RL], g_o0[RL];            // live between the two stages of a GRU cell
   // tape (TAPE): the lane that owns (row, column) of a stage writes it; trow = float offset of step 0 of the lane's row in a [B, n, 256] array
   // (32-bit element offsets: the host checks DXT_N * tstride < 2^31, so an address is the SGPR base + one VGPR)
@@ -1014,14 +1073,16 @@ __device__ __forceinline__ void dx_body(const DxArgs& a, float* dx_smem, int gro
     // ================= prenet layer 2 (modules.py:18-25); LDS T = prenet layer 1 =================
     if (wave < 4) {
       float acc[1][RG], s[1][RL];
+      DX_BIAS_AHEAD(b_p2, DXB_P2);
       dx_zero<1, RG>(acc);
       dxw_single<DXR_P2, RG>(WP, st + DXS_T, lane, acc);
+      DX_BIAS_HERE(b_p2);
       dxs_reduce<1, RG>(acc, s, lane);
       if (epl) {
 #pragma unroll
         for (int q = 0; q < RL; ++q) {
-          const float p2v = fmaxf(s[0][q] + bl[DXB_P2 * DX_NW + wave], 0.f);
-          dx_publish<WTC>(X + xl.p2 + erow[q] * DX_P2 + member * 4 + wave, p2v, tag, rt);
+          const float p2v = fmaxf(s[0][q] + b_p2, 0.f);
+          dx_publish<WTC>(dx_at(X, (unsigned)(xl.p2 + erow[q] * DX_P2 + member * 4 + wave)), p2v, tag, rt);
           if (TAPE && tval[q] && a.tp_p2) a.tp_p2[((size_t)(row0 + erow[q]) * a.n + t) * a.ld_p2 + member * 4 + wave] = p2v;
         }
       }
@@ -1033,7 +1094,8 @@ __device__ __forceinline__ void dx_body(const DxArgs& a, float* dx_smem, int gro
     dxq_zero<RG>(ag01);
     dx_zero<1, RG>(ag2);
     dxw_pair<DXR_AGH, RG>(WP, st + DXS_HATT, lane, ag01);
-    dx_gather<RG, DX_P2, false, DXS_LD, DX_NT, DX_DLY(0, DX_POLL_DELAY_B)>(X + xl.p2, tag, st, DXS_P2, 0, 0, tid, rt);
+    dx_ahead<RG>(ag01);
+    dx_gather_at<RG, DX_P2, false, DXS_LD, DX_NT, DX_DLY(0, DX_POLL_DELAY_B)>(X, (unsigned)xl.p2, tag, st, DXS_P2, 0, 0, tid, rt);
     __syncthreads();
     if constexpr (PD == 3) {
       // ================= prenet layer 3 (64 columns, two per member); its output takes the OUT2 slot, dead until the end of the step =================
@@ -1045,10 +1107,10 @@ __device__ __forceinline__ void dx_body(const DxArgs& a, float* dx_smem, int gro
         if (epl) {
 #pragma unroll
           for (int q = 0; q < RL; ++q)
-            dx_publish<WTC>(X + xl.p3 + erow[q] * DX_P3 + member * 2 + wave, fmaxf(s[0][q] + bl[DXB_P3 * DX_NW + wave], 0.f), tag, rt);
+            dx_publish<WTC>(dx_at(X, (unsigned)(xl.p3 + erow[q] * DX_P3 + member * 2 + wave)), fmaxf(s[0][q] + bl[DXB_P3 * DX_NW + wave], 0.f), tag, rt);
         }
       }
-      dx_gather<RG, DX_P3, false, DXS_LD, DX_NT, DX_DLY(1, DX_FIRST_POLL_DELAY)>(X + xl.p3, tag, st, DXS_OUT2, 0, 0, tid, rt);
+      dx_gather_at<RG, DX_P3, false, DXS_LD, DX_NT, DX_DLY(1, DX_FIRST_POLL_DELAY)>(X, (unsigned)xl.p3, tag, st, DXS_OUT2, 0, 0, tid, rt);
       __syncthreads();
     }
     DX_STAMP(1);
@@ -1066,11 +1128,13 @@ __device__ __forceinline__ void dx_body(const DxArgs& a, float* dx_smem, int gro
         const float rg = dx_sigmoid_fast(s[0][q] + DX_RB(DXRB_AR, q));
         g_u[q] = dx_sigmoid_fast(s[1][q] + DX_RB(DXRB_AU, q));
         g_cx[q] = s[2][q] + DX_RB(DXRB_AX, q);
-        if (epl) dx_publish<WTC>(X + xl.rha + erow[q] * DX_W + en, rg * g_h[q], tag, rt);
+        if (epl) dx_publish<WTC>(dx_at(X, (unsigned)(xl.rha + erow[q] * DX_W + en)), rg * g_h[q], tag, rt);
         DX_TAPE(DXT_RA, q, rg); DX_TAPE(DXT_UA, q, g_u[q]); DX_TAPE(DXT_RHA, q, rg * g_h[q]);
       }
     }
-    dx_gather<RG, DX_W, false, DXS_LD, DX_NT, DX_DLY(2, DX_FIRST_POLL_DELAY)>(X + xl.rha, tag, st, DXS_T, 0, 0, tid, rt);
+    DX_BIAS_AHEAD(b_ac, DXB_AC);
+    dx_gather_at<RG, DX_W, false, DXS_LD, DX_NT, DX_DLY(2, DX_FIRST_POLL_DELAY)>(X, (unsigned)xl.rha, tag, st, DXS_T, 0, 0, tid, rt);
+    DX_BIAS_HERE(b_ac);
     __syncthreads();
     DX_STAMP(2);
     {
@@ -1080,15 +1144,15 @@ __device__ __forceinline__ void dx_body(const DxArgs& a, float* dx_smem, int gro
       dxs_reduce<1, RG>(acc, s, lane);
 #pragma unroll
       for (int q = 0; q < RL; ++q) {
-        const float c = taco_tanh_fast(g_cx[q] + s[0][q] + bl[DXB_AC * DX_NW + wave]);
+        const float c = taco_tanh_fast(g_cx[q] + s[0][q] + b_ac);
         const float hn = g_u[q] * g_h[q] + (1.f - g_u[q]) * c;
-        if (epl) dx_publish<WTC>(X + xl.ha + erow[q] * DX_W + en, hn, tag, rt);
+        if (epl) dx_publish<WTC>(dx_at(X, (unsigned)(xl.ha + erow[q] * DX_W + en)), hn, tag, rt);
         DX_TAPE(DXT_CA, q, c); DX_TAPE(DXT_HA, q, hn);
       }
     }
 #pragma unroll
     for (int q = 0; q < RL; ++q) g_h[q] = st[erow[q] * DXS_LD + DXS_H1 + en];
-    dx_gather<RG, DX_W, false, DXS_LD, DX_NT, DX_DLY(3, DX_FIRST_POLL_DELAY)>(X + xl.ha, tag, st, DXS_HATT, 0, 0, tid, rt);
+    dx_gather_at<RG, DX_W, false, DXS_LD, DX_NT, DX_DLY(3, DX_FIRST_POLL_DELAY)>(X, (unsigned)xl.ha, tag, st, DXS_HATT, 0, 0, tid, rt);
     __syncthreads();
     DX_STAMP(3);
     // ================= attention (rnn_wrappers.py:304-341) =================
@@ -1139,7 +1203,7 @@ __device__ __forceinline__ void dx_body(const DxArgs& a, float* dx_smem, int gro
             }
           }
           e = dx_quadsum(e);
-          if (cp == 0 && j < psn) dx_publish<WTC>(X + xl.sc + (size_t)(arow * Pc + cb) * T + ps0 + j, e, tag, rt);
+          if (cp == 0 && j < psn) dx_publish<WTC>(dx_at(X, (unsigned)(xl.sc + (arow * Pc + cb) * T + ps0 + j)), e, tag, rt);
         }
       }
     }
@@ -1152,6 +1216,7 @@ __device__ __forceinline__ void dx_body(const DxArgs& a, float* dx_smem, int gro
     if (G1_AHEAD) {
       dxw_pair<DXR_G1H, RG>(WP, st + DXS_H1, lane, g1p0);
       dxw_quad<DXR_G1A, RG>(WP, st + DXS_HATT, lane, g1p0, g1p1);
+      dx_ahead<RG>(g1p0); dx_ahead<RG>(g1p1);
     }
     int aoff = 0;                  // the step's alignments are sc[aoff + j]: computed (sc itself) or manual (mrow, a region of the same LDS array)
     if (!man) {
@@ -1162,7 +1227,7 @@ __device__ __forceinline__ void dx_body(const DxArgs& a, float* dx_smem, int gro
           float s = 0.f;
           if (j < T) {
             float v[NP];
-            dx_poll<NP, DX_DLY(4, DX_POLL_DELAY_B)>(X + xl.sc + (size_t)(arow * Pc + part * NP) * T + j, (size_t)T, tag, v, rt);
+            dx_poll_at<NP, DX_DLY(4, DX_POLL_DELAY_B)>(X, (unsigned)(xl.sc + (arow * Pc + part * NP) * T + j), (unsigned)T, tag, v, rt);
 #pragma unroll
             for (int u = 0; u < NP; ++u) s += v[u];
           }
@@ -1189,13 +1254,7 @@ __device__ __forceinline__ void dx_body(const DxArgs& a, float* dx_smem, int gro
       __syncthreads();
       aoff = (int)(mrow - sc);
     }
-    {  // alignment state + history (tacotron.py:238-239 layout) for the member's block of positions; context channel block
-      for (int j = tid; j < T; j += DX_NT) alp[j] = sc[aoff + j];
-      const int p0 = asl * TP;
-      if (tid < TP && p0 + tid < T && brow < a.B) {
-        if (a.hist) a.hist[((size_t)brow * T + p0 + tid) * a.n + t] = sc[aoff + p0 + tid];
-        if (TAPE && a.tp_alpha) a.tp_alpha[((size_t)brow * (a.n + 1) + t + 1) * T + p0 + tid] = sc[aoff + p0 + tid];
-      }
+    {  // context channel block
       constexpr int JL = 64 / DC;                    // positions handled side by side inside a wave
       const int d = lane % DC, jsub = lane / DC;
       float part = 0.f;
@@ -1210,10 +1269,19 @@ __device__ __forceinline__ void dx_body(const DxArgs& a, float* dx_smem, int gro
       float s = 0.f;
 #pragma unroll
       for (int w = 0; w < DX_NW; ++w) s += cpart[w * 64 + tid];
-      dx_publish<WTC>(X + xl.ctx + arow * DX_W + asl * DC + tid, s, tag, rt);
+      dx_publish<WTC>(dx_at(X, (unsigned)(xl.ctx + arow * DX_W + asl * DC + tid)), s, tag, rt);
       if (TAPE && a.tp_ctx && brow < a.B) a.tp_ctx[((size_t)brow * a.n + t) * a.ld_ctx + asl * DC + tid] = s;
     }
-    dx_gather<RG, DX_W, false, DXS_LD, DX_NT, DX_DLY(5, DX_FIRST_POLL_DELAY)>(X + xl.ctx, tag, st, DXS_CTX, 0, 0, tid, rt);
+    {  // alignment state + history (tacotron.py:238-239 layout) for the member's block of positions -- BEHIND the context publish (round 7: wave 0, which
+       // has just normalised the row while the others waited, did this in front of it); sc is next written by the following step's score sum
+      for (int j = tid; j < T; j += DX_NT) alp[j] = sc[aoff + j];
+      const int p0 = asl * TP;
+      if (tid < TP && p0 + tid < T && brow < a.B) {
+        if (a.hist) a.hist[((size_t)brow * T + p0 + tid) * a.n + t] = sc[aoff + p0 + tid];
+        if (TAPE && a.tp_alpha) a.tp_alpha[((size_t)brow * (a.n + 1) + t + 1) * T + p0 + tid] = sc[aoff + p0 + tid];
+      }
+    }
+    dx_gather_at<RG, DX_W, false, DXS_LD, DX_NT, DX_DLY(5, DX_FIRST_POLL_DELAY)>(X, (unsigned)xl.ctx, tag, st, DXS_CTX, 0, 0, tid, rt);
     __syncthreads();
     DX_STAMP(6);
     // ================= concat projection folded into residual GRU 1 (rnn_wrappers.py:405-415; tacotron.py:166-172) =================
@@ -1236,12 +1304,14 @@ __device__ __forceinline__ void dx_body(const DxArgs& a, float* dx_smem, int gro
         g_u[q] = dx_sigmoid_fast(s[1][q] + DX_RB(DXRB_G1U, q));
         g_cx[q] = s[2][q] + DX_RB(DXRB_G1X, q);
         g_o0[q] = s[3][q] + DX_RB(DXRB_O0, q);
-        if (epl) dx_publish<WTC>(X + xl.rh1 + erow[q] * DX_W + en, rg * g_h[q], tag, rt);
+        if (epl) dx_publish<WTC>(dx_at(X, (unsigned)(xl.rh1 + erow[q] * DX_W + en)), rg * g_h[q], tag, rt);
         DX_TAPE(DXT_R1, q, rg); DX_TAPE(DXT_U1, q, g_u[q]); DX_TAPE(DXT_RH1, q, rg * g_h[q]); DX_TAPE(DXT_O0, q, g_o0[q]);
       }
       DX_STAMP(13);
     }
-    dx_gather<RG, DX_W, false, DXS_LD, DX_NT, DX_DLY(6, DX_FIRST_POLL_DELAY)>(X + xl.rh1, tag, st, DXS_T, 0, 0, tid, rt);
+    DX_BIAS_AHEAD(b_g1c, DXB_G1C);
+    dx_gather_at<RG, DX_W, false, DXS_LD, DX_NT, DX_DLY(6, DX_FIRST_POLL_DELAY)>(X, (unsigned)xl.rh1, tag, st, DXS_T, 0, 0, tid, rt);
+    DX_BIAS_HERE(b_g1c);
     DX_STAMP(14);
     __syncthreads();
     DX_STAMP(7);
@@ -1252,12 +1322,12 @@ __device__ __forceinline__ void dx_body(const DxArgs& a, float* dx_smem, int gro
       dxs_reduce<1, RG>(acc, s, lane);
 #pragma unroll
       for (int q = 0; q < RL; ++q) {
-        const float c = taco_tanh_fast(g_cx[q] + s[0][q] + bl[DXB_G1C * DX_NW + wave]);
+        const float c = taco_tanh_fast(g_cx[q] + s[0][q] + b_g1c);
         const float hn = g_u[q] * g_h[q] + (1.f - g_u[q]) * c;
         g_o1[q] = hn + g_o0[q];
         if (epl) {
-          dx_publish<WTC>(X + xl.h1 + erow[q] * DX_W + en, hn, tag, rt);
-          dx_publish<WTC>(X + xl.o1 + erow[q] * DX_W + en, hn + g_o0[q], tag, rt);       // ResidualWrapper: cell output + cell input
+          dx_publish<WTC>(dx_at(X, (unsigned)(xl.h1 + erow[q] * DX_W + en)), hn, tag, rt);
+          dx_publish<WTC>(dx_at(X, (unsigned)(xl.o1 + erow[q] * DX_W + en)), hn + g_o0[q], tag, rt);       // ResidualWrapper: cell output + cell input
         }
         DX_TAPE(DXT_C1, q, c); DX_TAPE(DXT_H1, q, hn); DX_TAPE(DXT_O1, q, g_o1[q]);
       }
@@ -1268,9 +1338,9 @@ __device__ __forceinline__ void dx_body(const DxArgs& a, float* dx_smem, int gro
     float g2c[1][RG];
     dxq_zero<RG>(g2p);
     dx_zero<1, RG>(g2c);
-    if (G1_AHEAD) dxw_pair<DXR_G2H, RG>(WP, st + DXS_H2, lane, g2p);
-    dx_gather<RG, DX_W, false, DXS_LD, DX_NT, DX_DLY(7, DX_POLL_DELAY_B)>(X + xl.h1, tag, st, DXS_H1, 0, 0, tid, rt);
-    dx_gather<RG, DX_W, false, DXS_LD, DX_NT, 0>(X + xl.o1, tag, st, DXS_OUT1, 0, 0, tid, rt);
+    if (G1_AHEAD) { dxw_pair<DXR_G2H, RG>(WP, st + DXS_H2, lane, g2p); dx_ahead<RG>(g2p); }
+    dx_gather_at<RG, DX_W, false, DXS_LD, DX_NT, DX_DLY(7, DX_POLL_DELAY_B)>(X, (unsigned)xl.h1, tag, st, DXS_H1, 0, 0, tid, rt);
+    dx_gather_at<RG, DX_W, false, DXS_LD, DX_NT, 0>(X, (unsigned)xl.o1, tag, st, DXS_OUT1, 0, 0, tid, rt);
     __syncthreads();
     DX_STAMP(8);
     // ================= residual GRU 2 =================
@@ -1287,11 +1357,13 @@ __device__ __forceinline__ void dx_body(const DxArgs& a, float* dx_smem, int gro
         const float rg = dx_sigmoid_fast(s[0][q] + bl[DXB_G2R * DX_NW + wave]);
         g_u[q] = dx_sigmoid_fast(s[1][q] + bl[DXB_G2U * DX_NW + wave]);
         g_cx[q] = s[2][q];
-        if (epl) dx_publish<WTC>(X + xl.rh2 + erow[q] * DX_W + en, rg * g_h[q], tag, rt);
+        if (epl) dx_publish<WTC>(dx_at(X, (unsigned)(xl.rh2 + erow[q] * DX_W + en)), rg * g_h[q], tag, rt);
         DX_TAPE(DXT_R2, q, rg); DX_TAPE(DXT_U2, q, g_u[q]); DX_TAPE(DXT_RH2, q, rg * g_h[q]);
       }
     }
-    dx_gather<RG, DX_W, false, DXS_LD, DX_NT, DX_DLY(8, DX_FIRST_POLL_DELAY)>(X + xl.rh2, tag, st, DXS_T, 0, 0, tid, rt);
+    DX_BIAS_AHEAD(b_g2c, DXB_G2C);
+    dx_gather_at<RG, DX_W, false, DXS_LD, DX_NT, DX_DLY(8, DX_FIRST_POLL_DELAY)>(X, (unsigned)xl.rh2, tag, st, DXS_T, 0, 0, tid, rt);
+    DX_BIAS_HERE(b_g2c);
     __syncthreads();
     DX_STAMP(9);
     {
@@ -1301,17 +1373,19 @@ __device__ __forceinline__ void dx_body(const DxArgs& a, float* dx_smem, int gro
       dxs_reduce<1, RG>(acc, s, lane);
 #pragma unroll
       for (int q = 0; q < RL; ++q) {
-        const float c = taco_tanh_fast(g_cx[q] + s[0][q] + bl[DXB_G2C * DX_NW + wave]);
+        const float c = taco_tanh_fast(g_cx[q] + s[0][q] + b_g2c);
         const float hn = g_u[q] * g_h[q] + (1.f - g_u[q]) * c;
-        if (epl) dx_publish<WTC>(X + xl.h2 + erow[q] * DX_W + en, hn, tag, rt);
+        if (epl) dx_publish<WTC>(dx_at(X, (unsigned)(xl.h2 + erow[q] * DX_W + en)), hn, tag, rt);
         DX_TAPE(DXT_C2, q, c); DX_TAPE(DXT_H2, q, hn); DX_TAPE(DXT_O2, q, hn + g_o1[q]);
       }
     }
     // ahead of its turn: next step's prenet layer 1, context rows
     float p1a[1][RG];
     dx_zero<1, RG>(p1a);
-    if (G1_AHEAD) dxw_single<DXR_P1C, RG>(WP, st + DXS_CTX, lane, p1a);
-    dx_gather<RG, DX_W, true, DXS_LD, DX_NT, DX_DLY(9, DX_POLL_DELAY_B)>(X + xl.h2, tag, st, DXS_H2, DXS_OUT1, DXS_OUT2, tid, rt);
+    if (G1_AHEAD) { dxw_single<DXR_P1C, RG>(WP, st + DXS_CTX, lane, p1a); dx_ahead<RG>(p1a); }
+    DX_BIAS_AHEAD(b_p1, DXB_P1); DX_BIAS_AHEAD(b_f0, DXB_F0); DX_BIAS_AHEAD(b_f1, DXB_F1);
+    dx_gather_at<RG, DX_W, true, DXS_LD, DX_NT, DX_DLY(9, DX_POLL_DELAY_B)>(X, (unsigned)xl.h2, tag, st, DXS_H2, DXS_OUT1, DXS_OUT2, tid, rt);
+    DX_BIAS_HERE(b_p1); DX_BIAS_HERE(b_f0); DX_BIAS_HERE(b_f1);
     __syncthreads();
     DX_STAMP(10);
     // ================= prenet layer 1 of step t+1 (composite: frame projection folded in, helpers.py:31) and the frame
@@ -1329,8 +1403,8 @@ __device__ __forceinline__ void dx_body(const DxArgs& a, float* dx_smem, int gro
       }
       if (share) {                                                         // last of the r frames -> every member's copy of the next prenet input
         const int f0 = a.rM - a.mels;
-        if (v0 && n0 >= f0) dx_publish<WTC>(X + xl.fb + erow[q] * DX_P2 + (n0 - f0), y0, tag, rt);
-        if (v1 && n1 >= f0) dx_publish<WTC>(X + xl.fb + erow[q] * DX_P2 + (n1 - f0), y1, tag, rt);
+        if (v0 && n0 >= f0) dx_publish<WTC>(dx_at(X, (unsigned)(xl.fb + erow[q] * DX_P2 + (n0 - f0))), y0, tag, rt);
+        if (v1 && n1 >= f0) dx_publish<WTC>(dx_at(X, (unsigned)(xl.fb + erow[q] * DX_P2 + (n1 - f0))), y1, tag, rt);
       }
     };
     if (TAPE && a.own_fb) {
@@ -1352,7 +1426,7 @@ __device__ __forceinline__ void dx_body(const DxArgs& a, float* dx_smem, int gro
         for (int i = tid; i < RG * a.mels; i += DX_NT) {
           const int r = i / a.mels, j = i - r * a.mels;
           float v[1];
-          dx_poll<1>(X + xl.fb + r * DX_P2 + j, 0, tag, v, rt);
+          dx_poll_at<1>(X, (unsigned)(xl.fb + r * DX_P2 + j), 0u, tag, v, rt);
           tfb[r * DX_W + j] = v[0];
         }
       }
@@ -1368,7 +1442,7 @@ __device__ __forceinline__ void dx_body(const DxArgs& a, float* dx_smem, int gro
 #pragma unroll
           for (int q = 0; q < RL; ++q) {
             const float p1v = fmaxf(s[0][q] + bl[DXB_P1 * DX_NW + wave], 0.f);
-            dx_publish<WTC>(X + xl.p1 + erow[q] * DX_W + en, p1v, tag, rt);
+            dx_publish<WTC>(dx_at(X, (unsigned)(xl.p1 + erow[q] * DX_W + en)), p1v, tag, rt);
             if (tval[q]) a.tape[(unsigned)DXT_P1 * tstr + trow[q] + (unsigned)(t + 1) * DX_W] = p1v;
           }
         }
@@ -1391,11 +1465,11 @@ __device__ __forceinline__ void dx_body(const DxArgs& a, float* dx_smem, int gro
 #pragma unroll
         for (int q = 0; q < RL; ++q) {
           if (t + 1 < a.n) {
-            const float p1v = fmaxf(s[2][q] + bl[DXB_P1 * DX_NW + wave], 0.f);
-            dx_publish<WTC>(X + xl.p1 + erow[q] * DX_W + en, p1v, tag, rt);
+            const float p1v = fmaxf(s[2][q] + b_p1, 0.f);
+            dx_publish<WTC>(dx_at(X, (unsigned)(xl.p1 + erow[q] * DX_W + en)), p1v, tag, rt);
             if (TAPE && tval[q]) a.tape[(unsigned)DXT_P1 * tstr + trow[q] + (unsigned)(t + 1) * DX_W] = p1v;
           }
-          store_frame(q, s[0][q] + bl[DXB_F0 * DX_NW + wave], s[1][q] + bl[DXB_F1 * DX_NW + wave], false);
+          store_frame(q, s[0][q] + b_f0, s[1][q] + b_f1, false);
         }
       }
     }
@@ -1406,7 +1480,7 @@ __device__ __forceinline__ void dx_body(const DxArgs& a, float* dx_smem, int gro
         if (b < a.B) a.dbg[((size_t)t * a.B + b) * a.dbgw + q * DX_W + nn] = st[r * DXS_LD + off + nn];
       }
     }
-    if (t + 1 < a.n) dx_gather<RG, DX_W, false, DXS_LD, DX_NT, DX_DLY(10, DX_FIRST_POLL_DELAY)>(X + xl.p1, tag, st, DXS_T, 0, 0, tid, rt);
+    if (t + 1 < a.n) dx_gather_at<RG, DX_W, false, DXS_LD, DX_NT, DX_DLY(10, DX_FIRST_POLL_DELAY)>(X, (unsigned)xl.p1, tag, st, DXS_T, 0, 0, tid, rt);
     __syncthreads();
     DX_STAMP(11);
   }
