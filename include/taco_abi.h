@@ -199,6 +199,33 @@ int taco_gl_inv_spectrogram_rows(taco_gl* g, void* hip_stream, const float* d_sp
  * samples (NULL: L), pcm = (int16) trunc(x * (32767 / max(0.01, peak))), zeros past them.  d_pcm [B, L].  One launch. */
 int taco_wav_to_pcm16(void* hip_stream, const float* d_wav, const int32_t* d_num_samples, int B, int L, int16_t* d_pcm);
 
+/* ---- waveform -> linear and mel training targets (audio/__init__.py:48-51,64-67,142-147,155-156,161-162; datasets/generate_data.py:151-158),
+ * on the taco_gl handle: the same windowed-DFT pack, slots and frame rows as the Griffin-Lim loop ---- */
+/* The mel filter bank, host memory [num_mels, num_freq] row-major (librosa.filters.mel of the reference's _build_mel_basis; the Python
+ * package restates it, audio.mel_basis).  Each filter is kept as the band from its first to its last non-zero bin plus that band's
+ * weights, so a dense basis works too (full bands).  Calling it again replaces the basis (it waits for launches that read the old one).
+ * Allocates device memory: call it at set-up time, not under stream capture. */
+int taco_gl_set_mel_basis(taco_gl* g, const float* host_basis, int num_mels);
+int taco_spec_num_mels(const taco_gl* g);                    /* filters of the basis in use; 0 = none set */
+/* 1 + n_samples / hop_length (librosa stft with center=True), hop_length as taco_gl_create derives it.  Host arithmetic only:
+ * takes the parameters, not a handle, so it also answers where there is no device. */
+int taco_spec_num_frames(const taco_audio_hparams* hp, int n_samples);
+size_t taco_spec_workspace_bytes(const taco_gl* g, int B, int Lmax);
+/* spectrogram(y) and melspectrogram(y) of B utterances: d_wav [B, Lmax] float32, d_num_samples [B] device memory (NULL: every row has
+ * Lmax samples), only read on the device.  With Tmax = 1 + Lmax / hop_length: d_linear [B, Tmax, num_freq] and d_mel
+ * [B, Tmax, num_mels] (NULL: no mel output; otherwise TACO_ERR_STATE until taco_gl_set_mel_basis was called) in the model's layout
+ * (generate_data.py stores the reference functions' outputs transposed the same way); row b holds its own T_b = 1 + n_b / hop frames
+ * and exact zeros after (the value _pad_target pads with, datafeeder.py:322-323); d_num_frames [B] (nullable) receives T_b.
+ * Per row: pre-emphasis y[i] - preemphasis*y[i-1], |stft| with the reflect padding taken at the row's OWN ends, then
+ * linear = clip((20 log10(max(1e-5, D)) - ref_level_db - min_level_db) / -min_level_db, 0, 1) and
+ * mel = clip((20 log10(max(1e-5, basis . D)) - min_level_db) / -min_level_db, 0, 1) (no ref_level_db on the mel side, as in the reference).
+ * Reflect padding needs n_b > n_fft/2: Lmax <= n_fft/2 is TACO_ERR_SHAPE, and each count is clamped on the device to
+ * [n_fft/2 + 1, Lmax] (d_num_frames reports the clamped row).  NOT reproduced: librosa serves a shorter recording by reflecting more
+ * than once; such a row is analysed as its first n_fft/2 + 1 samples of d_wav here (what lies past its count in d_wav is then read).
+ * Asynchronous on the stream; no allocation, read-back or synchronisation: capturable.  Two calls on the same input return the same bits. */
+int taco_spec_targets(taco_gl* g, void* hip_stream, const float* d_wav, const int32_t* d_num_samples, int B, int Lmax, float* d_linear,
+                      float* d_mel, int32_t* d_num_frames, void* d_workspace, size_t workspace_bytes);
+
 /* ---- training-side entry points on flat buffers (loss, schedule, clip + Adam); forward/backward: taco_train_* below ---- */
 /* add_loss (tacotron.py:274-302).  d_mel_* [B,T,num_mels], d_lin_* [B,T,num_freq], d_loss_coeff [B] (nullable = 1).
  * d_losses[4] = loss, mel_loss, linear_loss, loss_without_coeff.  Workspace >= 64 KiB. */

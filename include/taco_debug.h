@@ -107,6 +107,11 @@ int taco_train_debug_bigru(taco_train* t, void* hip_stream, const float* d_xproj
                            const float* d_dout, int B, int T, int persistent, float* d_out, float* d_gsave, float* d_dg, float* d_rh,
                            float* d_dh0, void* d_scratch, size_t scratch_bytes);
 
+/* Test hook: k_spec_targets (the fused back end of taco_spec_targets: magnitude -> dB -> normalise, mel projection) alone on a
+ * caller-supplied d_est [R, 2*num_freq] (Re | Im of R frames) -> d_linear [R, num_freq], d_mel [R, num_mels] (nullable).  Lets the
+ * dB / normalise arithmetic be held against the reference's own recorded outputs, and the kernel be timed alone. */
+int taco_debug_spec_epilogue(taco_gl* g, void* hip_stream, const float* d_est, int R, float* d_linear, float* d_mel);
+
 #ifdef __cplusplus
 }
 #endif

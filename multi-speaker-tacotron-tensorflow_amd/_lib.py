@@ -125,6 +125,12 @@ PROTOTYPES = {
     "taco_gl_rows_workspace_bytes": (_S, [_P, _I, _I]),
     "taco_gl_inv_spectrogram_rows": (_I, [_P, _P, _P, _P, _P, C.c_ulonglong, _I, _I, _I, _P, _P, _P, _S]),
     "taco_wav_to_pcm16": (_I, [_P, _P, _P, _I, _I, _P]),
+    "taco_gl_set_mel_basis": (_I, [_P, _P, _I]),
+    "taco_spec_num_mels": (_I, [_P]),
+    "taco_spec_num_frames": (_I, [C.POINTER(TacoAudioHParams), _I]),
+    "taco_spec_workspace_bytes": (_S, [_P, _I, _I]),
+    "taco_spec_targets": (_I, [_P, _P, _P, _P, _I, _I, _P, _P, _P, _P, _S]),
+    "taco_debug_spec_epilogue": (_I, [_P, _P, _P, _I, _P, _P]),
     "taco_attention_trim": (_I, [_P, _P, _P, _I, _I, _I, _I, _P]),
     "taco_loss_f32": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _S]),
     "taco_learning_rate": (C.c_float, [C.c_longlong, C.c_float, _I, _I]),

@@ -1,6 +1,9 @@
 """Spectrogram -> waveform on the GPU: `inv_spectrogram` of the reference's audio/__init__.py:54-56 (denormalise, dB -> amplitude,
 ^power, Griffin-Lim with librosa-semantics STFT/ISTFT, inverse pre-emphasis), the step synthesizer.py:264 runs on the CPU for
-every utterance.  All arithmetic is in libtaco_hip (taco_gl_*); PyTorch holds the buffers."""
+every utterance -- and waveform -> the linear and mel targets training consumes: `spectrogram` / `melspectrogram` of
+audio/__init__.py:48-51,64-67, which datasets/generate_data.py:151-158 runs on the CPU for every corpus file (class Spectrogram).
+All arithmetic is in libtaco_hip (taco_gl_*, taco_spec_*); PyTorch holds the buffers.  The one host computation is the mel filter
+bank (mel_basis), built once in float64 and uploaded."""
 import ctypes as C
 
 import numpy as np
@@ -9,14 +12,57 @@ import torch
 from . import _lib
 
 
+def hz_to_mel(f):
+    """Slaney's scale (librosa.hz_to_mel, htk=False): linear below 1 kHz (200/3 Hz per mel), logarithmic above (27 mels per factor 6.4)."""
+    f = np.asarray(f, np.float64)
+    lin = f / (200.0 / 3)
+    return np.where(f >= 1000.0, 15.0 + np.log(np.maximum(f, 1000.0) / 1000.0) / (np.log(6.4) / 27.0), lin)
+
+
+def mel_to_hz(m):
+    m = np.asarray(m, np.float64)
+    return np.where(m >= 15.0, 1000.0 * np.exp((np.log(6.4) / 27.0) * (np.maximum(m, 15.0) - 15.0)), (200.0 / 3) * m)
+
+
+def mel_basis(hparams):
+    """The filter bank of the reference's _build_mel_basis (audio/__init__.py:142-144): librosa.filters.mel(sample_rate, n_fft,
+    n_mels=num_mels) with librosa's defaults -- fmin 0, fmax sample_rate/2, Slaney's mel scale (htk=False), Slaney's area
+    normalisation -- restated in NumPy float64 from librosa's documented algorithm (0.5/0.6 era): num_mels + 2 points evenly spaced
+    in mels, and on the grid of bin frequencies the triangle max(0, min(rising ramp, falling ramp)) times 2 / (its width in Hz).
+    Returns [num_mels, num_freq].  UNPINNED on librosa itself (this project does not depend on it and no test runs it): it is held by an
+    independently written per-filter formulation (tests/spec_reference.py, tests/test_spec_host.py) and by the scale's known
+    points.  Whether librosa of that era returned float32 or float64 is unknown as well; this stays float64 and is cast to float32
+    at upload."""
+    g = lambda k, d: getattr(hparams, k, d)
+    sr, num_freq, n_mels = float(g("sample_rate", 24000)), int(g("num_freq", 1025)), int(g("num_mels", 80))
+    fftfreqs = np.linspace(0.0, sr / 2, num_freq)
+    mel_f = mel_to_hz(np.linspace(hz_to_mel(0.0), hz_to_mel(sr / 2), n_mels + 2))
+    fdiff = np.diff(mel_f)
+    ramps = mel_f[:, None] - fftfreqs[None, :]
+    lower = -ramps[:-2] / fdiff[:-1, None]
+    upper = ramps[2:] / fdiff[1:, None]
+    weights = np.maximum(0.0, np.minimum(lower, upper))
+    return weights * (2.0 / (mel_f[2:] - mel_f[:-2]))[:, None]
+
+
+def c_audio_hparams(hparams):
+    g = lambda k, d: getattr(hparams, k, d)
+    return _lib.TacoAudioHParams(
+        num_freq=int(g("num_freq", 1025)), sample_rate=int(g("sample_rate", 24000)), griffin_lim_iters=int(g("griffin_lim_iters", 60)),
+        frame_length_ms=float(g("frame_length_ms", 50)), frame_shift_ms=float(g("frame_shift_ms", 12.5)),
+        preemphasis=float(g("preemphasis", 0.97)), min_level_db=float(g("min_level_db", -100)), ref_level_db=float(g("ref_level_db", 20)),
+        power=float(g("power", 1.5)))
+
+
+def num_frames(hparams, n_samples):
+    """Frames of spectrogram(y) for n_samples samples: 1 + n_samples // hop (taco_spec_num_frames; host arithmetic, no GPU needed)."""
+    hp = c_audio_hparams(hparams)
+    return int(_lib.load_library().taco_spec_num_frames(C.byref(hp), int(n_samples)))
+
+
 class GriffinLim(object):
     def __init__(self, hparams, device="cuda:0"):
-        g = lambda k, d: getattr(hparams, k, d)
-        self.hp = _lib.TacoAudioHParams(
-            num_freq=int(g("num_freq", 1025)), sample_rate=int(g("sample_rate", 24000)), griffin_lim_iters=int(g("griffin_lim_iters", 60)),
-            frame_length_ms=float(g("frame_length_ms", 50)), frame_shift_ms=float(g("frame_shift_ms", 12.5)),
-            preemphasis=float(g("preemphasis", 0.97)), min_level_db=float(g("min_level_db", -100)), ref_level_db=float(g("ref_level_db", 20)),
-            power=float(g("power", 1.5)))
+        self.hp = c_audio_hparams(hparams)
         self.device = torch.device(device)
         if self.device.type != "cuda":
             raise _lib.TacoError(_lib.TACO_ERR_ARG, "GriffinLim runs on a GPU (got %s); there is no CPU fallback" % device)
@@ -105,3 +151,74 @@ class GriffinLim(object):
             self.close()
         except Exception:
             pass
+
+
+class Spectrogram(GriffinLim):
+    """Waveform -> training targets on the GPU, on the handle (windowed-DFT pack, slots, workspace) of GriffinLim.
+    basis: "slaney" (default) uploads mel_basis(hparams); an array [num_mels, num_freq] uploads that; None uploads nothing, and mel
+    outputs raise TacoError until set_mel_basis is called."""
+
+    def __init__(self, hparams, device="cuda:0", basis="slaney"):
+        super(Spectrogram, self).__init__(hparams, device)
+        if basis is not None:
+            self.set_mel_basis(mel_basis(hparams) if isinstance(basis, str) else basis)
+
+    def set_mel_basis(self, basis):
+        b = np.ascontiguousarray(np.asarray(basis), dtype=np.float32)
+        if b.ndim != 2 or b.shape[1] != self.hp.num_freq:
+            raise Exception("basis must be [num_mels, num_freq = %d], got %s" % (self.hp.num_freq, b.shape))
+        _lib.check(self._lib.taco_gl_set_mel_basis(self._h, b.ctypes.data_as(C.c_void_p), b.shape[0]))
+
+    @property
+    def num_mels(self):
+        return int(self._lib.taco_spec_num_mels(self._h))
+
+    def num_frames(self, n_samples):
+        return int(self._lib.taco_spec_num_frames(C.byref(self.hp), int(n_samples)))
+
+    def targets(self, wav, num_samples=None, mel=True):
+        """wav [B, Lmax] (numpy or tensor), num_samples [B] (a device int32 tensor is used as it is; host data is uploaded; None:
+        all Lmax) -> (linear [B, Tmax, num_freq], mel [B, Tmax, num_mels] or None with mel=False, num_frames [B] int32), device
+        tensors, Tmax = 1 + Lmax // hop.  Row b holds its own 1 + n_b // hop frames and exact zeros after."""
+        dev = self.device
+        x = (wav if torch.is_tensor(wav) else torch.as_tensor(np.asarray(wav))).to(dev, torch.float32).contiguous()
+        if x.dim() != 2:
+            raise Exception("wav must be [B, Lmax], got shape %s" % (tuple(x.shape),))
+        B, L = x.shape
+        ns = None if num_samples is None else (num_samples if torch.is_tensor(num_samples) else torch.as_tensor(np.asarray(num_samples))).to(dev, torch.int32).contiguous()
+        if ns is not None and tuple(ns.shape) != (B,):
+            raise Exception("num_samples must be [B] = [%d], got %s" % (B, tuple(ns.shape)))
+        nb = int(self._lib.taco_spec_workspace_bytes(self._h, B, L))
+        if self._ws is None or self._ws.numel() < nb:
+            self._ws = torch.empty(nb, dtype=torch.uint8, device=dev)
+        T = self.num_frames(L)
+        lin = torch.empty((B, T, self.hp.num_freq), dtype=torch.float32, device=dev)
+        if mel and not self.num_mels:
+            raise _lib.TacoError(_lib.TACO_ERR_STATE, "the mel output needs a filter bank: call set_mel_basis first (or pass mel=False)")
+        m = torch.empty((B, T, self.num_mels), dtype=torch.float32, device=dev) if mel else None
+        nf = torch.empty((B,), dtype=torch.int32, device=dev)
+        p = lambda t: C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)
+        with torch.cuda.device(dev):
+            _lib.check(self._lib.taco_spec_targets(self._h, C.c_void_p(torch.cuda.current_stream().cuda_stream), p(x), p(ns), B, L, p(lin),
+                                                   p(m), p(nf), p(self._ws), self._ws.numel()))
+        return lin, m, nf
+
+    def spectrogram(self, y):
+        """The reference's spectrogram(y): one 1-D waveform -> [num_freq, T] (device tensor)."""
+        return self.targets(torch.as_tensor(np.asarray(y) if not torch.is_tensor(y) else y).reshape(1, -1), mel=False)[0][0].t()
+
+    def melspectrogram(self, y):
+        """The reference's melspectrogram(y): one 1-D waveform -> [num_mels, T] (device tensor)."""
+        return self.targets(torch.as_tensor(np.asarray(y) if not torch.is_tensor(y) else y).reshape(1, -1))[1][0].t()
+
+    def process(self, wavs):
+        """A list of 1-D waveforms of any lengths, as ONE batch -> a list of {"linear": [T_b, num_freq], "mel": [T_b, num_mels]},
+        float32 NumPy arrays cut to each row's own frames (what generate_data.py:156-158 stores per file)."""
+        wavs = [np.asarray(w, np.float32).reshape(-1) for w in wavs]
+        n = np.array([len(w) for w in wavs], np.int32)
+        x = np.zeros((len(wavs), int(n.max())), np.float32)
+        for b, w in enumerate(wavs):
+            x[b, :len(w)] = w
+        lin, m, nf = self.targets(x, n)
+        lin, m, nf = lin.cpu().numpy(), m.cpu().numpy(), nf.cpu().numpy()
+        return [{"linear": lin[b, :nf[b]].copy(), "mel": m[b, :nf[b]].copy()} for b in range(len(wavs))]

@@ -3,6 +3,8 @@
 // librosa's stft/istft are restated as what they are for this window: a hop-strided gather of win_length samples, one
 // windowed-DFT matrix product per direction (on the matrix cores through the same implicit-GEMM kernels as the model,
 // 3-term split-bf16), overlap-add with the window sum-square normalisation, reflect padding.  Included from taco_lib.hip.
+// The analysis direction (waveform -> the linear and mel targets training consumes) uses the same pack, slots and frame rows:
+// k_spec_prepare, the forward product, k_spec_targets.
 #pragma once
 
 struct taco_gl {
@@ -11,6 +13,10 @@ struct taco_gl {
   taco_model* gm = nullptr;      // container for the two DFT weight packs (GemmVar table + arena)
   ConvL fwd, inv;                // [win -> 2F] analysis, [2F -> win] synthesis (window folded into both)
   size_t w2 = 0;                 // squared padded window [n_fft] (arena offset)
+  // analysis (taco_spec_targets): the mel filter bank as bands, device memory of its own (taco_gl_set_mel_basis; 0 filters = not set)
+  int num_mels = 0;
+  int* mel_band = nullptr;       // [3, num_mels]: first bin, one past the last bin, offset of the filter's weights in mel_w
+  float* mel_w = nullptr;        // the weights of every filter's [lo, hi), packed one filter after the other
 };
 
 // ---- kernels ----
@@ -143,6 +149,92 @@ __global__ __launch_bounds__(1024) void k_wav_to_pcm16(const float* wav, const i
   for (int i = tid; i < L; i += 1024) out[i] = i < n ? (short)(int)fminf(fmaxf(truncf(x[i] * scale), -32767.f), 32767.f) : (short)0;
 }
 
+
+// ---- waveform -> linear and mel targets (audio/__init__.py:48-51,64-67,142-147,155-156,161-162; datasets/generate_data.py:151-158) ----
+#define SPEC_ROWS 4            // frame rows per workgroup of k_spec_targets: the band table is fetched once for four rows
+// Samples utterance b keeps: Lmax, or num_samples[b] (device memory) clamped to [n_fft/2 + 1, Lmax] -- reflect padding needs n > n_fft/2
+__device__ __forceinline__ int spec_samples(const int* num_samples, int b, int Lmax, int half) {
+  return num_samples ? min(max(num_samples[b], half + 1), Lmax) : Lmax;
+}
+// Pre-emphasis p[i] = y[i] - a*y[i-1], y[-1] = 0 (scipy.signal.lfilter([1, -a], [1], y)) of wav [B, Lmax] into the centre of each
+// utterance's slot of ypad, and the reflect padding of n_fft/2 at the utterance's OWN ends, written by the thread that owns the
+// mirrored sample (as k_gl_overlap_add does).  Everything else of the slot -- and, behind the last slot, the slack the tail rows of
+// the frame matrix read -- is zeroed, so no frame row reads another call's data.  nf_ws [B] and num_frames [B] (nullable) receive
+// 1 + n_b / hop.  grid (blocks of a slot, B).
+__global__ void k_spec_prepare(const float* wav, const int* num_samples, float* ypad, int* nf_ws, int* num_frames, int B, int Lmax, int hop,
+                               int half, size_t slot, size_t tail, float a) {
+  const int b = blockIdx.y;
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= slot + (b == B - 1 ? tail : 0)) return;
+  const int n = spec_samples(num_samples, b, Lmax, half);
+  if (i == 0) { nf_ws[b] = 1 + n / hop; if (num_frames) num_frames[b] = 1 + n / hop; }
+  float* y = ypad + (size_t)b * slot + half;             // y[0 .. n)
+  if (i < (size_t)n) {
+    const int s = (int)i;
+    const float* x = wav + (size_t)b * Lmax;
+    const float v = s ? x[s] - a * x[s - 1] : x[0];
+    y[s] = v;
+    if (s >= 1 && s <= half) y[-s] = v;
+    if (s >= n - 1 - half && s <= n - 2) y[2 * (n - 1) - s] = v;
+  }
+  if (i >= (size_t)n + 2 * half) y[(ptrdiff_t)i - half] = 0.f;
+}
+// clip((20 log10(max(1e-5, amp)) - sub_db - min_db) / -min_db, 0, 1): _normalize(_amp_to_db(amp) - sub_db)
+__device__ __forceinline__ float spec_normalize(float amp, float sub_db, float min_db) {
+  const float db = 20.f * log10f(fmaxf(1e-5f, amp));
+  return fminf(fmaxf((db - sub_db - min_db) / -min_db, 0.f), 1.f);
+}
+// The back end of the analysis, fused: per frame row of est [B*Tr, 2F] (Re | Im) the magnitude |D| goes to LDS once; the linear row
+// is written from it, and the num_mels filter sums are formed from the same LDS copy -- the magnitude never goes to memory.
+// A filter is its band [lo, hi) of bins and hi - lo packed weights.  Sixteen lanes share one (row, filter): lane l sums bins lo + l,
+// lo + l + 16, ... in that order and the sixteen partial sums meet in a butterfly of fixed shape, so a sum has one order whatever
+// runs beside it (no atomics).  Rows t >= the utterance's frames (nframes [B], NULL: T) are stored as zeros.
+// grid (blocks of SPEC_ROWS frames, B), 256 threads, SPEC_ROWS * F floats of LDS.
+__global__ __launch_bounds__(256) void k_spec_targets(const float* est, const int* nframes, int T, int Tr, int F, const int* band,
+                                                      const float* mw, int M, float* lin, float* mel, float min_db, float ref_db) {
+  extern __shared__ float spec_mag[];      // [SPEC_ROWS, F]
+  const int b = blockIdx.y, t0 = blockIdx.x * SPEC_ROWS, tid = threadIdx.x;
+  const int Tb = nframes ? min(nframes[b], T) : T;
+#pragma unroll
+  for (int r = 0; r < SPEC_ROWS; ++r) {
+    const int t = t0 + r;
+    if (t >= T) break;
+    float* lo = lin + ((size_t)b * T + t) * F;
+    if (t < Tb) {
+      const float* e = est + ((size_t)b * Tr + t) * 2 * F;
+      for (int f = tid; f < F; f += 256) {
+        const float re = e[f], im = e[F + f];
+        const float m = sqrtf(re * re + im * im);
+        spec_mag[r * F + f] = m;
+        lo[f] = spec_normalize(m, ref_db, min_db);
+      }
+    } else {
+      for (int f = tid; f < F; f += 256) lo[f] = 0.f;
+    }
+  }
+  if (!mel) return;
+  __syncthreads();
+  const int g = tid >> 4, l = tid & 15;
+  for (int r = 0; r < SPEC_ROWS; ++r) {
+    const int t = t0 + r;
+    if (t >= T) break;
+    float* mo = mel + ((size_t)b * T + t) * M;
+    if (t >= Tb) {
+      for (int m = tid; m < M; m += 256) mo[m] = 0.f;
+      continue;
+    }
+    const float* mg = spec_mag + r * F;
+    for (int m = g; m < M; m += 16) {                    // (the sixteen lanes of a group take every branch together)
+      const int k0 = band[m], k1 = band[M + m];
+      const float* w = mw + band[2 * M + m] - k0;
+      float acc = 0.f;
+      for (int k = k0 + l; k < k1; k += 16) acc = fmaf(w[k], mg[k], acc);
+      acc += __shfl_xor(acc, 8, 16); acc += __shfl_xor(acc, 4, 16); acc += __shfl_xor(acc, 2, 16); acc += __shfl_xor(acc, 1, 16);
+      if (l == 0) mo[m] = spec_normalize(acc, 0.f, min_db);
+    }
+  }
+}
+
 // ---- host ----
 static int gl_rows(const taco_gl* g, int T) { return T + cdiv(g->n_fft, g->hop); }                 // frames per utterance slot (tail frames read the slack)
 static size_t gl_slot(const taco_gl* g, int T) { return (size_t)gl_rows(g, T) * g->hop; }          // samples per utterance slot >= hop*(T-1) + n_fft
@@ -152,4 +244,12 @@ static void carve_gl(Carver& cv, const taco_gl* g, int B, int T, GlWs& w) {
   w.S = cv.f(R * g->F); w.X = cv.f(R * 2 * g->F); w.est = cv.f(R * 2 * g->F); w.Y = cv.f(R * g->win);
   w.ypad = cv.f((size_t)B * gl_slot(g, T) + 2 * g->n_fft + g->win);
   w.wss = cv.f((size_t)g->hop * (T - 1) + g->n_fft);
+}
+// analysis: T = 1 + Lmax / hop frames per utterance in the slot geometry above (a padded utterance is Lmax + n_fft <= gl_slot samples)
+struct SpecWs { float *ypad, *est; int* nf; };
+static size_t spec_tail(const taco_gl* g) { return (size_t)2 * g->n_fft + g->win; }                // slack behind the last slot
+static void carve_spec(Carver& cv, const taco_gl* g, int B, int T, SpecWs& w) {
+  w.ypad = cv.f((size_t)B * gl_slot(g, T) + spec_tail(g));
+  w.est = cv.f((size_t)B * gl_rows(g, T) * 2 * g->F);
+  w.nf = cv.i(B);
 }

@@ -1,4 +1,4 @@
-// taco_audio_api.h -- C ABI of the spectrogram -> waveform step; included inside extern "C".
+// taco_audio_api.h -- C ABI of the spectrogram -> waveform step and of the waveform -> training targets step; included inside extern "C".
 
 int taco_gl_create(const taco_audio_hparams* hp, int device, taco_gl** out) {
   if (!hp || !out) return fail(TACO_ERR_ARG, "null argument");
@@ -56,6 +56,8 @@ int taco_gl_create(const taco_audio_hparams* hp, int device, taco_gl** out) {
 void taco_gl_destroy(taco_gl* g) {
   if (!g) return;
   if (g->gm) { if (g->gm->darena) (void)hipFree(g->gm->darena); delete g->gm; }
+  if (g->mel_band) (void)hipFree(g->mel_band);
+  if (g->mel_w) (void)hipFree(g->mel_w);
   delete g;
 }
 
@@ -128,4 +130,94 @@ int taco_wav_to_pcm16(void* hip_stream, const float* d_wav, const int32_t* d_num
   hipLaunchKernelGGL(k_wav_to_pcm16, dim3(B), dim3(1024), 0, (hipStream_t)hip_stream, d_wav, d_num_samples, L, d_pcm);
   HIPCHK(hipGetLastError());
   return 0;
+}
+
+// ---- waveform -> linear and mel targets ----
+int taco_gl_set_mel_basis(taco_gl* g, const float* host_basis, int num_mels) {
+  if (!g || !host_basis || num_mels <= 0) return fail(TACO_ERR_ARG, "bad argument");
+  const int F = g->F;
+  std::vector<int> band((size_t)3 * num_mels, 0);
+  std::vector<float> w;
+  for (int m = 0; m < num_mels; ++m) {               // the band of a filter: from its first to its last non-zero bin (a dense row: all of them)
+    const float* row = host_basis + (size_t)m * F;
+    int lo = F, hi = 0;
+    for (int k = 0; k < F; ++k) if (row[k] != 0.f) { lo = std::min(lo, k); hi = k + 1; }
+    if (hi == 0) lo = 0;
+    band[m] = lo; band[num_mels + m] = hi; band[2 * num_mels + m] = (int)w.size();
+    w.insert(w.end(), row + lo, row + hi);
+  }
+  if (w.empty()) w.push_back(0.f);
+  HIPCHK(hipSetDevice(g->gm->device));
+  int* d_band = nullptr; float* d_w = nullptr;
+  if (hipMalloc((void**)&d_band, band.size() * sizeof(int)) != hipSuccess || hipMalloc((void**)&d_w, w.size() * sizeof(float)) != hipSuccess ||
+      hipMemcpy(d_band, band.data(), band.size() * sizeof(int), hipMemcpyHostToDevice) != hipSuccess ||
+      hipMemcpy(d_w, w.data(), w.size() * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) {
+    if (d_band) (void)hipFree(d_band);
+    if (d_w) (void)hipFree(d_w);
+    return fail(TACO_ERR_HIP, "could not upload the mel filter bank");
+  }
+  if (g->mel_band) (void)hipFree(g->mel_band);       // (hipFree waits for the launches that still read the basis it replaces)
+  if (g->mel_w) (void)hipFree(g->mel_w);
+  g->mel_band = d_band; g->mel_w = d_w; g->num_mels = num_mels;
+  return 0;
+}
+
+int taco_spec_num_mels(const taco_gl* g) { return g ? g->num_mels : 0; }
+
+int taco_spec_num_frames(const taco_audio_hparams* hp, int n_samples) {      // host arithmetic only: needs no handle and no device
+  const int hop = hp ? (int)(hp->frame_shift_ms / 1000.0 * hp->sample_rate) : 0;      // as taco_gl_create
+  return (hop >= 1 && n_samples >= 0) ? 1 + n_samples / hop : 0;
+}
+
+size_t taco_spec_workspace_bytes(const taco_gl* g, int B, int Lmax) {
+  if (!g || B <= 0 || Lmax <= 0) return 0;
+  Carver cv(nullptr, 0);
+  SpecWs w; carve_spec(cv, g, B, 1 + Lmax / g->hop, w);
+  return cv.off;
+}
+
+// what k_spec_targets needs of the handle: a filter bank when there is a mel output, SPEC_ROWS rows of magnitudes within 64 KB of LDS
+static int spec_check(const taco_gl* g, const float* d_mel) {
+  if (d_mel && !g->num_mels) return fail(TACO_ERR_STATE, "the mel output needs a filter bank: call taco_gl_set_mel_basis first");
+  if ((size_t)SPEC_ROWS * g->F * sizeof(float) > 64 * 1024)
+    return fail(TACO_ERR_UNSUPPORTED, "num_freq = %d: k_spec_targets keeps %d rows of magnitudes in 64 KB of LDS", g->F, SPEC_ROWS);
+  return 0;
+}
+// (the caller has passed spec_check)
+static int spec_epilogue(taco_gl* g, hipStream_t st, const float* est, const int* nframes, int B, int T, int Tr, float* d_linear, float* d_mel) {
+  const size_t lds = (size_t)SPEC_ROWS * g->F * sizeof(float);
+  hipLaunchKernelGGL(k_spec_targets, dim3(cdiv(T, SPEC_ROWS), B), dim3(256), lds, st, est, nframes, T, Tr, g->F, g->mel_band, g->mel_w, g->num_mels,
+                     d_linear, d_mel, g->hp.min_level_db, g->hp.ref_level_db);
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
+int taco_spec_targets(taco_gl* g, void* hip_stream, const float* d_wav, const int32_t* d_num_samples, int B, int Lmax, float* d_linear,
+                      float* d_mel, int32_t* d_num_frames, void* d_workspace, size_t workspace_bytes) {
+  if (!g || !d_wav || !d_linear || !d_workspace || B <= 0 || B > 65535 || Lmax <= 0) return fail(TACO_ERR_ARG, "bad argument");
+  const int half = g->n_fft / 2, T = 1 + Lmax / g->hop, Tr = gl_rows(g, T), F = g->F;
+  if (Lmax <= half) return fail(TACO_ERR_SHAPE, "utterance too short for reflect padding: Lmax = %d <= n_fft/2 = %d", Lmax, half);
+  TRY(spec_check(g, d_mel));      // before anything is launched
+  if ((size_t)B * Tr > (size_t)0x7fffffff) return fail(TACO_ERR_SHAPE, "too many frame rows: %zu", (size_t)B * Tr);
+  HIPCHK(hipSetDevice(g->gm->device));
+  hipStream_t st = (hipStream_t)hip_stream;
+  Carver cv(d_workspace, workspace_bytes);
+  SpecWs w; carve_spec(cv, g, B, T, w);
+  if (!cv.ok()) return fail(TACO_ERR_STATE, "workspace too small: need %zu bytes, have %zu", cv.off, workspace_bytes);
+  const size_t slot = gl_slot(g, T), tail = spec_tail(g);
+  hipLaunchKernelGGL(k_spec_prepare, dim3((unsigned)((slot + tail + 255) / 256), B), dim3(256), 0, st, d_wav, d_num_samples, w.ypad, w.nf, d_num_frames,
+                     B, Lmax, g->hop, half, slot, tail, g->hp.preemphasis);
+  HIPCHK(hipGetLastError());
+  // D = stft(p): the product the Griffin-Lim loop issues, row (b, t) = ypad[b*slot + t*hop + lpad ...][0 .. win); rows past an utterance's
+  // own frames read zeros or the next slot and are stored as zeros by k_spec_targets
+  GemmCall c; c.x = w.ypad + g->lpad; c.ldx = g->hop; c.M = B * Tr; c.out = w.est; c.ldo = 2 * F;
+  TRY(run_gemm(g->gm, st, &g->fwd, 1, false, c));
+  return spec_epilogue(g, st, w.est, w.nf, B, T, Tr, d_linear, d_mel);
+}
+
+int taco_debug_spec_epilogue(taco_gl* g, void* hip_stream, const float* d_est, int R, float* d_linear, float* d_mel) {
+  if (!g || !d_est || !d_linear || R <= 0) return fail(TACO_ERR_ARG, "bad argument");
+  TRY(spec_check(g, d_mel));
+  HIPCHK(hipSetDevice(g->gm->device));
+  return spec_epilogue(g, (hipStream_t)hip_stream, d_est, nullptr, 1, R, R, d_linear, d_mel);
 }

@@ -3,7 +3,11 @@
 Prints one JSON line: audio seconds produced per second, with the NumPy oracle (FFT-based, one utterance) timed beside it.
 "rows" holds the per-utterance-length entry point (GriffinLim.inv_spectrogram_rows) timed in the same run, alternating with the
 existing one: all rows full (must cost what the existing entry point costs, within that entry point's own window-to-window spread)
-and a seeded spread of lengths uniform in [T/4, T], followed by the PCM16 kernel."""
+and a seeded spread of lengths uniform in [T/4, T], followed by the PCM16 kernel.
+`--analysis` measures the other direction, waveform -> linear and mel training targets (Spectrogram.targets) at the C2 target shape --
+32 rows x 512 frames = 153 300 samples each: the whole call, k_spec_targets alone (through taco_debug_spec_epilogue on the same number
+of frame rows) with the bytes it moves over its time, and the difference of the two medians (k_spec_prepare + the windowed-DFT product; a
+difference, not a measurement).  It runs with `--analysis` only, INSTEAD of the synthesis arms, and prints its own JSON line."""
 import json, os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "oracle"))
@@ -11,6 +15,53 @@ import numpy as np, torch, taco_amd
 import audio_oracle as A
 B, T, F = 32, 512, 1025
 hp = taco_amd.hparams
+
+
+def analysis():
+    import ctypes as C
+    sp = taco_amd.Spectrogram(hp)
+    M = sp.num_mels
+    n_fft = (hp.num_freq - 1) * 2; hop = int(hp.frame_shift_ms / 1000 * hp.sample_rate); win = int(hp.frame_length_ms / 1000 * hp.sample_rate)
+    Tr = T + -(-n_fft // hop)                                    # frame rows per utterance slot the product runs over (gl_rows)
+    L = 153300                                                   # hop * (T - 1): the samples of a 512-frame C2 target
+    assert sp.num_frames(L) == T
+    rs = np.random.RandomState(2)
+    wav = torch.from_numpy((0.1 * rs.randn(B, L)).astype(np.float32)).cuda()
+    ragged = torch.from_numpy(rs.randint(L // 4, L + 1, B).astype(np.int32)).cuda()
+    est = torch.from_numpy(rs.randn(1, 2 * F).astype(np.float32)).cuda().repeat(B * T, 1).contiguous()
+    lin = torch.empty((B * T, F), dtype=torch.float32, device="cuda"); mel = torch.empty((B * T, M), dtype=torch.float32, device="cuda")
+    p = lambda t: C.c_void_p(t.data_ptr())
+    epi = lambda: taco_amd._lib.check(sp._lib.taco_debug_spec_epilogue(sp._h, C.c_void_p(torch.cuda.current_stream().cuda_stream), p(est), B * T, p(lin), p(mel)))
+    arms = {"targets": lambda: sp.targets(wav), "targets_ragged": lambda: sp.targets(wav, ragged), "epilogue": epi}
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    for f in arms.values():
+        for _ in range(3):
+            f()
+    torch.cuda.synchronize()
+    ms = {k: [] for k in arms}
+    for _ in range(5):
+        for k, f in arms.items():
+            e0.record()
+            for _ in range(10):
+                f()
+            e1.record(); torch.cuda.synchronize()
+            ms[k].append(e0.elapsed_time(e1) / 10)
+    med = {k: float(np.median(v)) for k, v in ms.items()}
+    a, b = sp.targets(wav), sp.targets(wav)
+    nbytes = B * T * (2 * F + F + M) * 4                         # est read, linear and mel written
+    out = {"metric": "audio seconds analysed per second (waveform -> linear + mel targets)", "value": B * L / hp.sample_rate / (med["targets"] / 1e3),
+           "unit": "x realtime", "batch": "B=%d x %d samples -> %d frames x (%d + %d)" % (B, L, T, F, M), "windows": "5 windows of 10 calls per arm, alternating",
+           "targets_ms": ms["targets"], "targets_ragged_ms": ms["targets_ragged"], "k_spec_targets_ms": ms["epilogue"],
+           "targets_median_minus_k_spec_targets_median_ms": med["targets"] - med["epilogue"], "k_spec_targets_bytes": nbytes,
+           "k_spec_targets_GBps": nbytes / (med["epilogue"] / 1e3) / 1e9, "dft_gemm_GFLOP": 2.0 * B * Tr * win * 2 * F / 1e9,
+           "identical_bits_on_two_calls": bool(all(torch.equal(x, y) for x, y in zip(a, b))), "finite": bool(torch.isfinite(a[0]).all() and torch.isfinite(a[1]).all())}
+    sp.close()
+    return out
+
+
+if "--analysis" in sys.argv:
+    print(json.dumps(analysis()))
+    sys.exit(0)
 gl = taco_amd.GriffinLim(hp)
 rs = np.random.RandomState(0)
 spec = torch.from_numpy(rs.rand(B, T, F).astype(np.float32)).cuda()
