@@ -199,6 +199,31 @@ int taco_gl_inv_spectrogram_rows(taco_gl* g, void* hip_stream, const float* d_sp
  * samples (NULL: L), pcm = (int16) trunc(x * (32767 / max(0.01, peak))), zeros past them.  d_pcm [B, L].  One launch. */
 int taco_wav_to_pcm16(void* hip_stream, const float* d_wav, const int32_t* d_num_samples, int B, int L, int16_t* d_pcm);
 
+/* Silence trimming of a synthesised waveform: the `librosa.effects.trim(audio_out, frame_length=5120, hop_length=256, top_db=50)` of
+ * synthesizer.py:266-269 (`audio_out = audio_out[:index[-1]]`), per row of d_wav [B, L].  UNPINNED on librosa: the reference pins
+ * librosa==0.5.1, this project does not depend on librosa, and what follows restates the documented algorithm; it could not be
+ * checked against librosa's source or output.  With N = frame_length, frame t of a row of n samples is N samples of
+ * np.pad(y, N/2, mode="reflect") from t*hop_length (a row shorter than N/2 is reflected more than once, as np.pad does: every
+ * n >= 2 is reproduced); the row has 1 + n / hop_length frames.  Two conventions for a frame's energy:
+ *   TACO_TRIM_SPECTRAL  librosa 0.5.x, the reference's pin: rmse goes through the magnitude spectrogram, mse = mean over the N/2 + 1
+ *                       one-sided bins of |rfft(hann_periodic * frame)|^2 (DC and Nyquist at full weight; NOT the time-domain mean
+ *                       square).  Computed without a transform as (N sum xw^2 + (sum xw)^2 + (sum (-1)^i xw)^2) / 2 / (N/2 + 1).
+ *   TACO_TRIM_TIME      librosa >= 0.6: mse = mean of the squares of the unwindowed frame.
+ * Then db = 10 log10(max(1e-10, mse)) - 10 log10(max(1e-10, max_t mse)), a frame is non-silent where db > -top_db, and
+ * d_index[b] = {start, end} = {first*hop_length, min(n, (last + 1)*hop_length)}, {0, 0} when no frame is non-silent.  The reference
+ * cuts the tail only (`[:end]`); start is reported, not applied.  d_num_samples [B] is device memory, only read on the device
+ * (NULL: every row has L samples); each count is clamped to [0, L] and nothing at or past it is read; a row with n < 2 returns
+ * {0, n}.  d_frame_db [B, 1 + L/hop_length] (nullable; for diagnostics and tests) receives db for the row's own frames and exact
+ * zeros after.  Asynchronous on the stream, two launches; no allocation, read-back or synchronisation: capturable.  Two calls on the
+ * same input return the same bits.  TACO_ERR_ARG (before any device call): hop_length < 1, frame_length < 2, unknown energy, a null
+ * pointer, workspace below taco_wav_trim_workspace_bytes.  TACO_ERR_UNSUPPORTED: an odd frame_length, or one whose frame (and
+ * window) does not fit 64 KB of LDS (8192 spectral, 16384 time-domain). */
+#define TACO_TRIM_SPECTRAL 0   /* librosa 0.5.x: one-sided mean of |stft|^2, Hann window (the reference's pin) */
+#define TACO_TRIM_TIME     1   /* librosa >= 0.6: mean square of the unwindowed frame */
+size_t taco_wav_trim_workspace_bytes(int B, int L, int frame_length, int hop_length);
+int taco_wav_trim(void* hip_stream, const float* d_wav, const int32_t* d_num_samples, int B, int L, float top_db, int frame_length,
+                  int hop_length, int energy, int32_t* d_index, float* d_frame_db, void* d_workspace, size_t workspace_bytes);
+
 /* ---- waveform -> linear and mel training targets (audio/__init__.py:48-51,64-67,142-147,155-156,161-162; datasets/generate_data.py:151-158),
  * on the taco_gl handle: the same windowed-DFT pack, slots and frame rows as the Griffin-Lim loop ---- */
 /* The mel filter bank, host memory [num_mels, num_freq] row-major (librosa.filters.mel of the reference's _build_mel_basis; the Python

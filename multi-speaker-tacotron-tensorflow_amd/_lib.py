@@ -9,6 +9,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "csrc", "libtaco_hip.so")
 
 TACO_ERR_ARG, TACO_ERR_SHAPE, TACO_ERR_UNSUPPORTED, TACO_ERR_HIP, TACO_ERR_STATE = -1, -2, -3, -4, -5
+TACO_TRIM_SPECTRAL, TACO_TRIM_TIME = 0, 1      # taco_wav_trim's `energy`
 
 
 class TacoHParams(C.Structure):
@@ -125,6 +126,8 @@ PROTOTYPES = {
     "taco_gl_rows_workspace_bytes": (_S, [_P, _I, _I]),
     "taco_gl_inv_spectrogram_rows": (_I, [_P, _P, _P, _P, _P, C.c_ulonglong, _I, _I, _I, _P, _P, _P, _S]),
     "taco_wav_to_pcm16": (_I, [_P, _P, _P, _I, _I, _P]),
+    "taco_wav_trim_workspace_bytes": (_S, [_I, _I, _I, _I]),
+    "taco_wav_trim": (_I, [_P, _P, _P, _I, _I, C.c_float, _I, _I, _I, _P, _P, _P, _S]),
     "taco_gl_set_mel_basis": (_I, [_P, _P, _I]),
     "taco_spec_num_mels": (_I, [_P]),
     "taco_spec_num_frames": (_I, [C.POINTER(TacoAudioHParams), _I]),

@@ -141,6 +141,37 @@ class GriffinLim(object):
             _lib.check(self._lib.taco_wav_to_pcm16(C.c_void_p(torch.cuda.current_stream().cuda_stream), p(x), p(ns), B, L, p(pcm)))
         return pcm
 
+    def trim(self, wav, num_samples=None, top_db=60, frame_length=2048, hop_length=512, energy="spectral", return_db=False):
+        """librosa.effects.trim's index per row (synthesizer.py:266-269 calls it with top_db=50, frame_length=5120, hop_length=256; the
+        defaults here are librosa's): wav [B, L] float32, num_samples [B] (a device int32 tensor is used as it is; None: L) -> index
+        [B, 2] int32 (device tensor), row b = [start, end] of the non-silent part of its first num_samples[b] samples; with return_db
+        also the frames' dB below the loudest frame, [B, 1 + L // hop_length], zeros past a row's own 1 + n_b // hop_length frames.
+        energy "spectral" is librosa 0.5.x (the reference's pin: mean of the one-sided |stft|^2, Hann window), "time" librosa >= 0.6
+        (mean square of the unwindowed frame).  UNPINNED on librosa: a restatement of the documented algorithm (include/taco_abi.h,
+        taco_wav_trim), checked against tests/trim_reference.py, not against librosa."""
+        dev = self.device
+        x = (wav if torch.is_tensor(wav) else torch.as_tensor(np.asarray(wav))).to(dev, torch.float32).contiguous()
+        if x.dim() != 2:
+            raise Exception("wav must be [B, L], got shape %s" % (tuple(x.shape),))
+        B, L = x.shape
+        ns = None if num_samples is None else (num_samples if torch.is_tensor(num_samples) else torch.as_tensor(np.asarray(num_samples))).to(dev, torch.int32).contiguous()
+        if ns is not None and tuple(ns.shape) != (B,):
+            raise Exception("num_samples must be [B] = [%d], got %s" % (B, tuple(ns.shape)))
+        modes = {"spectral": _lib.TACO_TRIM_SPECTRAL, "time": _lib.TACO_TRIM_TIME}
+        if energy not in modes:
+            raise _lib.TacoError(_lib.TACO_ERR_ARG, "energy must be one of %s, got %r" % (sorted(modes), energy))
+        frame_length, hop_length = int(frame_length), int(hop_length)
+        nb = int(self._lib.taco_wav_trim_workspace_bytes(B, L, frame_length, hop_length))
+        if self._ws is None or self._ws.numel() < nb:
+            self._ws = torch.empty(nb, dtype=torch.uint8, device=dev)
+        index = torch.empty((B, 2), dtype=torch.int32, device=dev)
+        db = torch.empty((B, 1 + L // max(hop_length, 1)), dtype=torch.float32, device=dev) if return_db else None
+        p = lambda t: C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)
+        with torch.cuda.device(dev):
+            _lib.check(self._lib.taco_wav_trim(C.c_void_p(torch.cuda.current_stream().cuda_stream), p(x), p(ns), B, L, float(top_db),
+                                               frame_length, hop_length, modes[energy], p(index), p(db), p(self._ws), self._ws.numel()))
+        return (index, db) if return_db else index
+
     def close(self):
         if getattr(self, "_h", None):
             self._lib.taco_gl_destroy(self._h)

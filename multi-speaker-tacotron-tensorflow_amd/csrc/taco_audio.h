@@ -150,6 +150,104 @@ __global__ __launch_bounds__(1024) void k_wav_to_pcm16(const float* wav, const i
 }
 
 
+// ---- silence trimming: librosa.effects.trim (synthesizer.py:266-269), restated; UNPINNED on librosa (include/taco_abi.h) ----
+#define TRIM_THREADS 256       // four waves per workgroup of k_trim_energy
+#define TRIM_FRAMES 16         // frames per tile at most; trim_frames_per_tile lowers it until the tile fits TRIM_LDS_BYTES
+#define TRIM_LDS_BYTES 65536   // dynamic LDS a launch gets without opting in to more
+// Samples row b keeps: L, or num_samples[b] (device memory) clamped to [0, L]
+__device__ __forceinline__ int trim_samples(const int* num_samples, int b, int L) { return num_samples ? min(max(num_samples[b], 0), L) : L; }
+// np.pad(y, N/2, mode="reflect") as an index map: padded position j - N/2 -> a sample in [0, n), period 2(n - 1), n >= 2.  A row
+// shorter than N/2 is reflected more than once; 64-bit because 2(n - 1) and a padded position can pass 2^31.
+__device__ __forceinline__ int trim_reflect(long long j, int n) {
+  if (j >= 0 && j < n) return (int)j;
+  const long long P = 2LL * (n - 1);
+  long long m = j % P;
+  if (m < 0) m += P;
+  return (int)(m < n ? m : P - m);
+}
+// Frame energies of B rows.  Frame t of row b is the N samples of the reflect-padded row from t*hop; a row has 1 + n_b/hop frames.
+//   TACO_TRIM_SPECTRAL  mse = mean over the N/2 + 1 one-sided bins of |rfft(hann * frame)|^2, without a transform: for a real frame
+//                       of even length, sum_{k=0..N/2} |X_k|^2 = (N sum xw^2 + (sum xw)^2 + (sum (-1)^i xw)^2) / 2  (Parseval; DC and
+//                       Nyquist count once in the full spectrum and are added back) -- every term is positive
+//   TACO_TRIM_TIME      mse = sum x^2 / N, no window
+// grid (tiles of fpt frames, B), TRIM_THREADS threads.  A workgroup stages its tile's (ft - 1)*hop + N samples in LDS once, each
+// through trim_reflect from wav[b, :n_b] (nothing at or past n_b is read), and the periodic Hann table beside them; its waves take
+// the tile's frames round-robin.  Lane l sums i = l, l + 64, ... in that order, so its (-1)^i is one sign, and a butterfly of fixed
+// shape joins the 64 partial sums: one order per sum, two calls give the same bits.  Frames at or past the row's own count are
+// not written (k_trim_index does not read them).
+__global__ __launch_bounds__(TRIM_THREADS) void k_trim_energy(const float* wav, const int* num_samples, int L, int N, int hop, int fpt,
+                                                              int Fmax, int energy, float* mse) {
+  extern __shared__ __attribute__((aligned(16))) float trim_lds[];      // samples [(fpt - 1)*hop + N] | window [N] (spectral only)
+  const int b = blockIdx.y, t0 = blockIdx.x * fpt, tid = threadIdx.x;
+  const int n = trim_samples(num_samples, b, L);
+  if (n < 2) return;
+  const int nf = 1 + n / hop;
+  if (t0 >= nf) return;
+  const int ft = min(fpt, nf - t0), span = (ft - 1) * hop + N;
+  float* xs = trim_lds;
+  float* win = trim_lds + (size_t)(fpt - 1) * hop + N;
+  const float* x = wav + (size_t)b * L;
+  const long long j0 = (long long)t0 * hop - N / 2;
+  for (int i = tid; i < span; i += TRIM_THREADS) xs[i] = x[trim_reflect(j0 + i, n)];
+  if (energy == TACO_TRIM_SPECTRAL)
+    for (int i = tid; i < N; i += TRIM_THREADS) win[i] = 0.5f - 0.5f * cospif((float)(2 * i) / (float)N);      // periodic Hann
+  __syncthreads();
+  const int wave = tid >> 6, lane = tid & 63;
+  for (int f = wave; f < ft; f += TRIM_THREADS / 64) {
+    const float* fx = xs + f * hop;
+    float s2 = 0.f, s1 = 0.f;
+    if (energy == TACO_TRIM_SPECTRAL) {
+      for (int i = lane; i < N; i += 64) { const float v = fx[i] * win[i]; s2 = fmaf(v, v, s2); s1 += v; }
+    } else {
+      for (int i = lane; i < N; i += 64) { const float v = fx[i]; s2 = fmaf(v, v, s2); }
+    }
+    float sa = (lane & 1) ? -s1 : s1;                     // sum (-1)^i xw: i = lane mod 2 on this lane
+    for (int o = 32; o > 0; o >>= 1) { s2 += __shfl_xor(s2, o); s1 += __shfl_xor(s1, o); sa += __shfl_xor(sa, o); }
+    if (lane == 0)
+      mse[(size_t)b * Fmax + t0 + f] = energy == TACO_TRIM_SPECTRAL ? ((float)N * s2 + s1 * s1 + sa * sa) * 0.5f / (float)(N / 2 + 1)
+                                                                    : s2 / (float)N;
+  }
+}
+// logamplitude(ref_power=np.max) and the index: db[t] = 10 log10(max(1e-10, mse[t])) - 10 log10(max(1e-10, max_t mse)); a frame is
+// non-silent where db > -top_db; index[b] = {first*hop, min(n_b, (last + 1)*hop)}, {0, 0} when no frame is, {0, n_b} for a row of
+// fewer than two samples (it has no frames).  frame_db (nullable) receives db for the row's own frames and zeros after.  One
+// workgroup per row; a maximum and a minimum are the same in any order.
+__global__ __launch_bounds__(256) void k_trim_index(const float* mse, const int* num_samples, int L, int hop, int Fmax, float top_db,
+                                                    int* index, float* frame_db) {
+#pragma clang fp contract(off)      // the product is rounded before the subtraction, as ref was: the loudest frame is exactly 0 dB
+  __shared__ float pmax[4];
+  __shared__ int pfirst[4], plast[4];
+  const int b = blockIdx.x, tid = threadIdx.x;
+  const int n = trim_samples(num_samples, b, L), nf = n < 2 ? 0 : 1 + n / hop;
+  const float* e = mse + (size_t)b * Fmax;
+  float mx = 0.f;                                          // energies are >= 0
+  for (int t = tid; t < nf; t += 256) mx = fmaxf(mx, e[t]);
+  for (int o = 32; o > 0; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o));
+  if ((tid & 63) == 0) pmax[tid >> 6] = mx;
+  __syncthreads();
+  mx = fmaxf(fmaxf(pmax[0], pmax[1]), fmaxf(pmax[2], pmax[3]));
+  const float ref = 10.f * log10f(fmaxf(1e-10f, mx));
+  int first = 0x7fffffff, last = -1;
+  for (int t = tid; t < Fmax; t += 256) {
+    float db = 0.f;
+    if (t < nf) {
+      db = 10.f * log10f(fmaxf(1e-10f, e[t])) - ref;
+      if (db > -top_db) { first = min(first, t); last = max(last, t); }
+    }
+    if (frame_db) frame_db[(size_t)b * Fmax + t] = db;
+  }
+  for (int o = 32; o > 0; o >>= 1) { first = min(first, __shfl_xor(first, o)); last = max(last, __shfl_xor(last, o)); }
+  if ((tid & 63) == 0) { pfirst[tid >> 6] = first; plast[tid >> 6] = last; }
+  __syncthreads();
+  if (tid == 0) {
+    first = min(min(pfirst[0], pfirst[1]), min(pfirst[2], pfirst[3]));
+    last = max(max(plast[0], plast[1]), max(plast[2], plast[3]));
+    int start = 0, end = n < 2 ? n : 0;
+    if (last >= 0) { start = (int)min((long long)first * hop, (long long)n); end = (int)min((long long)n, (long long)(last + 1) * hop); }
+    index[2 * b] = start; index[2 * b + 1] = end;
+  }
+}
+
 // ---- waveform -> linear and mel targets (audio/__init__.py:48-51,64-67,142-147,155-156,161-162; datasets/generate_data.py:151-158) ----
 #define SPEC_ROWS 4            // frame rows per workgroup of k_spec_targets: the band table is fetched once for four rows
 // Samples utterance b keeps: Lmax, or num_samples[b] (device memory) clamped to [n_fft/2 + 1, Lmax] -- reflect padding needs n > n_fft/2
@@ -252,4 +350,13 @@ static void carve_spec(Carver& cv, const taco_gl* g, int B, int T, SpecWs& w) {
   w.ypad = cv.f((size_t)B * gl_slot(g, T) + spec_tail(g));
   w.est = cv.f((size_t)B * gl_rows(g, T) * 2 * g->F);
   w.nf = cv.i(B);
+}
+// silence trimming: frames per tile of k_trim_energy, the most (<= TRIM_FRAMES) whose samples and window fit TRIM_LDS_BYTES; 0 = not even one
+static size_t trim_lds_bytes(int N, int hop, int fpt, int energy) {
+  return ((size_t)(fpt - 1) * hop + N + (energy == TACO_TRIM_SPECTRAL ? N : 0)) * sizeof(float);
+}
+static int trim_frames_per_tile(int N, int hop, int energy) {
+  int fpt = TRIM_FRAMES;
+  while (fpt > 0 && trim_lds_bytes(N, hop, fpt, energy) > TRIM_LDS_BYTES) --fpt;
+  return fpt;
 }

@@ -132,6 +132,37 @@ int taco_wav_to_pcm16(void* hip_stream, const float* d_wav, const int32_t* d_num
   return 0;
 }
 
+// ---- silence trimming (librosa.effects.trim, synthesizer.py:266-269) ----
+size_t taco_wav_trim_workspace_bytes(int B, int L, int frame_length, int hop_length) {
+  (void)frame_length;
+  if (B <= 0 || L <= 0 || hop_length < 1) return 0;
+  Carver cv(nullptr, 0);
+  cv.f((size_t)B * (1 + L / hop_length));                // mse [B, Fmax]
+  return cv.off;
+}
+
+int taco_wav_trim(void* hip_stream, const float* d_wav, const int32_t* d_num_samples, int B, int L, float top_db, int frame_length,
+                  int hop_length, int energy, int32_t* d_index, float* d_frame_db, void* d_workspace, size_t workspace_bytes) {
+  if (!d_wav || !d_index || !d_workspace || B <= 0 || B > 65535 || L <= 0) return fail(TACO_ERR_ARG, "bad argument");
+  if (hop_length < 1 || frame_length < 2) return fail(TACO_ERR_ARG, "bad frame parameters: frame_length %d, hop_length %d", frame_length, hop_length);
+  if (energy != TACO_TRIM_SPECTRAL && energy != TACO_TRIM_TIME) return fail(TACO_ERR_ARG, "unknown energy convention %d", energy);
+  const size_t need = taco_wav_trim_workspace_bytes(B, L, frame_length, hop_length);
+  if (workspace_bytes < need) return fail(TACO_ERR_ARG, "workspace too small: need %zu bytes, have %zu", need, workspace_bytes);
+  if (frame_length & 1) return fail(TACO_ERR_UNSUPPORTED, "frame_length = %d: the one-sided spectrum sum is written for an even length", frame_length);
+  const int fpt = trim_frames_per_tile(frame_length, hop_length, energy);
+  if (fpt < 1)
+    return fail(TACO_ERR_UNSUPPORTED, "frame_length = %d: k_trim_energy keeps a frame%s in %d KB of LDS", frame_length,
+                energy == TACO_TRIM_SPECTRAL ? " and its window" : "", TRIM_LDS_BYTES / 1024);
+  hipStream_t st = (hipStream_t)hip_stream;
+  const int Fmax = 1 + L / hop_length;
+  float* mse = (float*)d_workspace;
+  hipLaunchKernelGGL(k_trim_energy, dim3(cdiv(Fmax, fpt), B), dim3(TRIM_THREADS), trim_lds_bytes(frame_length, hop_length, fpt, energy), st, d_wav,
+                     d_num_samples, L, frame_length, hop_length, fpt, Fmax, energy, mse);
+  hipLaunchKernelGGL(k_trim_index, dim3(B), dim3(256), 0, st, mse, d_num_samples, L, hop_length, Fmax, top_db, d_index, d_frame_db);
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
 // ---- waveform -> linear and mel targets ----
 int taco_gl_set_mel_basis(taco_gl* g, const float* host_basis, int num_mels) {
   if (!g || !host_basis || num_mels <= 0) return fail(TACO_ERR_ARG, "bad argument");

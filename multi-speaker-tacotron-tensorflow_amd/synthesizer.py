@@ -4,7 +4,8 @@ Kept: load() / synthesize() / close() names and arguments; token -> input_length
 (synthesizer.py:120); default speaker id zeros (:43-44); the (linear_outputs, alignments) fetch pair
 (:122-126,166-167); manual-attention second pass for modes 1 and 3 (:171-205; mode 2 is broken in the
 reference: np.pow does not exist); text -> ids with the Korean normaliser (text.py, korean.py); the attention trim
-(:242-262, device kernel) and, with vocode=True, the spectrogram -> waveform step on the GPU (audio.py).
+(:242-262, device kernel) and, with vocode=True, the spectrogram -> waveform step on the GPU (audio.py),
+followed by the silence trim of librosa_trim=True (:266-269, device kernels; without vocode there is no audio and it is a no-op).
 Out of scope: plots, wav / npy file output, sentence concatenation -- `synthesize` returns the model
 outputs as numpy arrays (and keeps `spec_end_idx` / `wavs` as attributes) instead."""
 import glob
@@ -136,19 +137,27 @@ class Synthesizer(object):
         if attention_trim and end_of_sentence:
             self.spec_end_idx = self.attention_trim_end(alignments, [len(seq) for seq in sequences])
         # plot_graph_and_save_audio (:264): wav = wav[:spec_end_idx]; audio_out = inv_spectrogram(wav.T) -- on the GPU, whole batch at once
+        # librosa_trim (:266-269): audio_out[:index[-1]] of librosa.effects.trim(audio_out, frame_length=5120, hop_length=256, top_db=50), on
+        # the GPU.  It acts on the audio, so without vocode there is nothing to cut and the flag is a no-op
         self.wavs = None
+        self.trim_index = None
         if vocode:
-            self.wavs = self.inv_spectrogram(linear, self.spec_end_idx)
+            self.wavs = self.inv_spectrogram(linear, self.spec_end_idx, librosa_trim=librosa_trim and end_of_sentence)
         return linear, alignments
 
     def synthesize_audio(self, texts=None, tokens=None, speaker_ids=None, end_of_sentence=True, attention_trim=True,
-                         manual_alignments=None, seed=0, iters=None, pcm=True):
+                         manual_alignments=None, seed=0, iters=None, pcm=True, librosa_trim=False):
         """The reference's synthesize -> plot_graph_and_save_audio chain up to the samples save_audio writes (synthesizer.py:119-126,
         242-264; audio/__init__.py:22-25), everything between the token upload and the audio download on the device: the forward, the
         attention trim on the device alignments, Griffin-Lim on every utterance's own frames read from the trim kernel's output, the
         scaling to 16-bit PCM.  Returns a list of 1-D arrays, int16 (pcm) or float32, each cut to its own length; `spec_end_idx` is set
         as by `synthesize`.  Frame counts below GriffinLim.min_frames() are raised to it (include/taco_abi.h).  `seed` picks the
-        initial phases (the reference draws np.random.rand).  Copies to the host: the audio buffer and two [N] int vectors."""
+        initial phases (the reference draws np.random.rand).  Copies to the host: the audio buffer and two [N] int vectors.
+        librosa_trim (with end_of_sentence; synthesizer.py:266-269): the silence trim librosa.effects.trim(audio_out, frame_length=5120,
+        hop_length=256, top_db=50) runs on the device between Griffin-Lim and the scaling (GriffinLim.trim; UNPINNED on librosa, the
+        0.5.x energy convention of the reference's pin); its `end` replaces the row's sample count for the PCM peak and for the cut
+        (the reference cuts the tail only), and `trim_index` [N, 2] (start, end) is downloaded in place of the sample counts.  Off
+        (the default): `trim_index` is None and nothing else changes."""
         sequences = self._token_rows(texts, tokens)
         input_lengths = np.argmax(sequences == EOS_ID, 1).astype(np.int32)             # synthesizer.py:120
         if type(speaker_ids) == dict:
@@ -161,10 +170,17 @@ class Synthesizer(object):
             frames = self._attention_trim_device(alignments, [len(seq) for seq in sequences])
         gl = self._griffin_lim()
         wav, num_samples = gl.inv_spectrogram_rows(linear, frames, seed=seed, iters=iters)
+        index = None
+        if librosa_trim and end_of_sentence:
+            index = gl.trim(wav, num_samples, **self.LIBROSA_TRIM)
+            num_samples = index[:, 1].contiguous()
         audio = gl.pcm16(wav, num_samples) if pcm else wav
         self.spec_end_idx = None if frames is None else frames.cpu().numpy()
         audio = audio.cpu().numpy()
-        return [a[:n] for a, n in zip(audio, num_samples.cpu().numpy())]
+        self.trim_index = None if index is None else index.cpu().numpy()
+        return [a[:n] for a, n in zip(audio, num_samples.cpu().numpy() if index is None else self.trim_index[:, 1])]
+
+    LIBROSA_TRIM = dict(top_db=50, frame_length=5120, hop_length=256)      # synthesizer.py:267-268
 
     def _griffin_lim(self):
         from .audio import GriffinLim
@@ -172,19 +188,26 @@ class Synthesizer(object):
             self._gl = GriffinLim(self.hparams, device=str(self.model.device))
         return self._gl
 
-    def inv_spectrogram(self, linear, spec_end_idx=None):
+    def inv_spectrogram(self, linear, spec_end_idx=None, librosa_trim=False):
         """audio/__init__.py:54-56 for a batch [N, T, num_freq]; returns a list of 1-D float32 arrays (each cut to the samples its
-        own frames produce when spec_end_idx is given: Griffin-Lim runs on the padded batch, frames past the end are silence-level)."""
+        own frames produce when spec_end_idx is given: Griffin-Lim runs on the padded batch, frames past the end are silence-level).
+        librosa_trim: each row is then cut to the `end` of GriffinLim.trim on those samples (synthesizer.py:266-269) and
+        `trim_index` [N, 2] is set."""
         self._griffin_lim()
         x = np.array(linear, np.float32, copy=True)
         if spec_end_idx is not None:
             for i, e in enumerate(spec_end_idx):
                 x[i, int(e):] = 0.0                       # normalised 0 = min_level_db: the reference would not have synthesised these frames
-        wav = self._gl.inv_spectrogram(x).cpu().numpy()
+        dwav = self._gl.inv_spectrogram(x)
+        wav = dwav.cpu().numpy()
         hop = self._gl.num_samples(2)
-        if spec_end_idx is None:
+        ends = [wav.shape[1]] * len(wav) if spec_end_idx is None else [hop * max(int(e) - 1, 1) for e in spec_end_idx]
+        if librosa_trim:
+            self.trim_index = self._gl.trim(dwav, np.asarray(ends, np.int32), **self.LIBROSA_TRIM).cpu().numpy()
+            ends = self.trim_index[:, 1]
+        if spec_end_idx is None and not librosa_trim:
             return [w for w in wav]
-        return [w[:hop * max(int(e) - 1, 1)] for w, e in zip(wav, spec_end_idx)]
+        return [w[:int(e)] for w, e in zip(wav, ends)]
 
     def attention_trim_end(self, alignments, sequence_lengths):
         """spec_end_idx = reduction_factor * j + 3 per utterance (synthesizer.py:242-262); alignments [N, T_in, T_dec]."""

@@ -7,7 +7,11 @@ and a seeded spread of lengths uniform in [T/4, T], followed by the PCM16 kernel
 `--analysis` measures the other direction, waveform -> linear and mel training targets (Spectrogram.targets) at the C2 target shape --
 32 rows x 512 frames = 153 300 samples each: the whole call, k_spec_targets alone (through taco_debug_spec_epilogue on the same number
 of frame rows) with the bytes it moves over its time, and the difference of the two medians (k_spec_prepare + the windowed-DFT product; a
-difference, not a measurement).  It runs with `--analysis` only, INSTEAD of the synthesis arms, and prints its own JSON line."""
+difference, not a measurement).  It runs with `--analysis` only, INSTEAD of the synthesis arms, and prints its own JSON line.
+`--trim` measures the silence trim of librosa_trim=True (GriffinLim.trim at 5120 / 256 / 50 dB, synthesizer.py:266-269) on a batch of the C2
+output shape -- 32 rows x 153 300 samples with the seeded per-utterance lengths of the synthesis arms, each row noise with a quiet last
+fifth: the trim alone, the tail of synthesize_audio (pcm16 alone = flag off; trim + end column + pcm16 = flag on), and the float64
+restatement tests/trim_reference.py on the CPU for the same batch, whose indices the device must reproduce.  Its own JSON line, `--trim` only."""
 import json, os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "oracle"))
@@ -59,6 +63,56 @@ def analysis():
     return out
 
 
+def trim():
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import trim_reference as R
+    gl = taco_amd.GriffinLim(hp)
+    L = gl.num_samples(T)
+    frames = np.random.RandomState(1).randint(T // 4, T + 1, B)
+    ns = np.array([gl.num_samples(int(f)) for f in frames], np.int32)
+    rs = np.random.RandomState(3)
+    x = np.zeros((B, L), np.float32)
+    for b, n in enumerate(ns):
+        x[b, :n] = 1e-4 * rs.randn(n)
+        x[b, :4 * n // 5] = 0.1 * rs.randn(4 * n // 5)
+    wav, dn = torch.from_numpy(x).cuda(), torch.from_numpy(ns).cuda()
+    kw = dict(top_db=50, frame_length=5120, hop_length=256)
+    tail_on = lambda: gl.pcm16(wav, gl.trim(wav, dn, **kw)[:, 1].contiguous())
+    arms = {"trim": lambda: gl.trim(wav, dn, **kw), "tail_flag_off": lambda: gl.pcm16(wav, dn), "tail_flag_on": tail_on}
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    for f in arms.values():
+        for _ in range(3):
+            f()
+    torch.cuda.synchronize()
+    ms = {k: [] for k in arms}
+    for _ in range(5):
+        for k, f in arms.items():
+            e0.record()
+            for _ in range(10):
+                f()
+            e1.record(); torch.cuda.synchronize()
+            ms[k].append(e0.elapsed_time(e1) / 10)
+    med = {k: float(np.median(v)) for k, v in ms.items()}
+    index, db = gl.trim(wav, dn, return_db=True, **kw)
+    again = gl.trim(wav, dn, return_db=True, **kw)
+    index = index.cpu().numpy()
+    t0 = time.perf_counter(); ref = [R.trim(x[b, :n], 50, 5120, 256, "spectral") for b, n in enumerate(ns)]; cpu_s = time.perf_counter() - t0
+    ddb = max(float(np.abs(db[b, :len(r[1])].cpu().numpy() - r[1]).max()) for b, r in enumerate(ref))
+    out = {"metric": "silence trim (librosa.effects.trim at 5120/256/50 dB) of a C2-shaped batch", "value": med["trim"], "unit": "ms",
+           "batch": "B=%d x %d samples, lengths %d..%d (%.1f s of audio at %d Hz)" % (B, L, ns.min(), ns.max(), float(ns.sum()) / hp.sample_rate, hp.sample_rate),
+           "windows": "5 windows of 10 calls per arm, alternating", "trim_ms": ms["trim"], "tail_flag_off_ms": ms["tail_flag_off"],
+           "tail_flag_on_ms": ms["tail_flag_on"], "tail_flag_on_minus_off_median_ms": med["tail_flag_on"] - med["tail_flag_off"],
+           "share_of_a_55_ms_griffin_lim_call": med["trim"] / 55.0, "cpu_restatement_float64_s": cpu_s,
+           "indices_equal_to_the_restatement": int(sum(index[b].tolist() == r[0].tolist() for b, r in enumerate(ref))), "rows": B,
+           "smallest_margin_db": min(r[2] for r in ref), "max_abs_db_difference": ddb,
+           "samples_cut": int((ns - index[:, 1]).sum()), "identical_bits_on_two_calls": bool(torch.equal(again[0].cpu(), torch.from_numpy(index)) and torch.equal(again[1], db))}
+    gl.close()
+    return out
+
+
+if "--trim" in sys.argv:
+    print(json.dumps(trim()))
+    sys.exit(0)
 if "--analysis" in sys.argv:
     print(json.dumps(analysis()))
     sys.exit(0)
