@@ -251,6 +251,32 @@ size_t taco_spec_workspace_bytes(const taco_gl* g, int B, int Lmax);
 int taco_spec_targets(taco_gl* g, void* hip_stream, const float* d_wav, const int32_t* d_num_samples, int B, int Lmax, float* d_linear,
                       float* d_mel, int32_t* d_num_frames, void* d_workspace, size_t workspace_bytes);
 
+/* ---- a training batch gathered out of a device-resident corpus (the batching of datasets/datafeeder.py:289-328, _prepare_batch /
+ * _prepare_inputs / _pad_target, with the data already on the device) ----
+ * A STREAM is one field of a batch: a pack of items laid end to end in device memory, tables saying where item i starts and how many
+ * rows it has, and the padded rectangle the batch rows go to.  For every stream and batch row b, with i = d_index[b] and
+ * c = min(rows[i], rows_out): out[b] receives the first c * width words of item i and exact zeros in every word after them (the value
+ * _pad_target and _prepare_inputs pad with), and counts[b] = c.  An index outside [0, N) gives an all-zero row and count 0 and causes
+ * no read; no word outside an item's c * width words is read (neither the pack's slack nor a neighbouring item).  Words are copied as
+ * bits: float and int32 streams alike.
+ * One launch serves all streams of a batch (tokens, mel, linear or samples, loss_coeff, speaker_id); the descriptors travel by value
+ * in the kernel arguments.  Asynchronous on the stream; no allocation, read-back or synchronisation: capturable, and since d_index is
+ * device memory a replayed graph collates a different batch each time.  Offsets are 64-bit.  pack and out must be 4-byte aligned;
+ * any alignment of item starts and batch rows beyond that is served.
+ * TACO_ERR_ARG (before any device call): null streams / d_index / pack / out, n_streams outside [1, TACO_COLLATE_MAX_STREAMS],
+ * width < 1, rows_out < 1, B < 1, N < 1, or start == NULL together with rows != NULL. */
+#define TACO_COLLATE_MAX_STREAMS 8
+typedef struct {
+  const void*      pack;      /* device, 4-byte words (float or int32: bits are copied, never converted) */
+  const long long* start;     /* device [N]: word offset of item i in pack; NULL: item i starts at i * rows_out * width */
+  const int32_t*   rows;      /* device [N]: rows of item i (a row is `width` words); NULL: every item has rows_out rows */
+  int32_t          width;     /* words per row: 1 (tokens, samples, per-item scalars), num_mels, num_freq */
+  int32_t          rows_out;  /* rows per batch row of the output */
+  void*            out;       /* device [B, rows_out, width] */
+  int32_t*         counts;    /* device [B], nullable: rows copied for batch row b */
+} taco_collate_stream;
+int taco_collate(void* hip_stream, const taco_collate_stream* streams, int n_streams, const int32_t* d_index, int B, int N);
+
 /* ---- training-side entry points on flat buffers (loss, schedule, clip + Adam); forward/backward: taco_train_* below ---- */
 /* add_loss (tacotron.py:274-302).  d_mel_* [B,T,num_mels], d_lin_* [B,T,num_freq], d_loss_coeff [B] (nullable = 1).
  * d_losses[4] = loss, mel_loss, linear_loss, loss_without_coeff.  Workspace >= 64 KiB. */

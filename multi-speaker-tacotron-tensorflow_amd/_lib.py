@@ -37,6 +37,15 @@ class TacoAudioHParams(C.Structure):
                 ("min_level_db", C.c_float), ("ref_level_db", C.c_float), ("power", C.c_float)]
 
 
+class TacoCollateStream(C.Structure):
+    """taco_collate_stream (include/taco_abi.h): one field of a batch, gathered out of a device pack."""
+    _fields_ = [("pack", C.c_void_p), ("start", C.c_void_p), ("rows", C.c_void_p), ("width", C.c_int32), ("rows_out", C.c_int32),
+                ("out", C.c_void_p), ("counts", C.c_void_p)]
+
+
+TACO_COLLATE_MAX_STREAMS = 8
+
+
 class TacoError(Exception):
     """Raised for every non-zero return of the C ABI.  The reference raises bare `Exception`
     for unknown model/attention types and shape mismatches (tacotron.py:88,152,192-194)."""
@@ -133,6 +142,7 @@ PROTOTYPES = {
     "taco_spec_num_frames": (_I, [C.POINTER(TacoAudioHParams), _I]),
     "taco_spec_workspace_bytes": (_S, [_P, _I, _I]),
     "taco_spec_targets": (_I, [_P, _P, _P, _P, _I, _I, _P, _P, _P, _P, _S]),
+    "taco_collate": (_I, [_P, C.POINTER(TacoCollateStream), _I, _P, _I, _I]),
     "taco_debug_spec_epilogue": (_I, [_P, _P, _P, _I, _P, _P]),
     "taco_attention_trim": (_I, [_P, _P, _P, _I, _I, _I, _I, _P]),
     "taco_loss_f32": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _S]),

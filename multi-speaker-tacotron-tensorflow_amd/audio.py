@@ -207,10 +207,12 @@ class Spectrogram(GriffinLim):
     def num_frames(self, n_samples):
         return int(self._lib.taco_spec_num_frames(C.byref(self.hp), int(n_samples)))
 
-    def targets(self, wav, num_samples=None, mel=True):
+    def targets(self, wav, num_samples=None, mel=True, out=None):
         """wav [B, Lmax] (numpy or tensor), num_samples [B] (a device int32 tensor is used as it is; host data is uploaded; None:
         all Lmax) -> (linear [B, Tmax, num_freq], mel [B, Tmax, num_mels] or None with mel=False, num_frames [B] int32), device
-        tensors, Tmax = 1 + Lmax // hop.  Row b holds its own 1 + n_b // hop frames and exact zeros after."""
+        tensors, Tmax = 1 + Lmax // hop.  Row b holds its own 1 + n_b // hop frames and exact zeros after.  out = (linear, mel,
+        num_frames): contiguous device tensors of exactly those shapes that are written in place and returned (nothing is allocated
+        once the workspace has its size)."""
         dev = self.device
         x = (wav if torch.is_tensor(wav) else torch.as_tensor(np.asarray(wav))).to(dev, torch.float32).contiguous()
         if x.dim() != 2:
@@ -223,11 +225,19 @@ class Spectrogram(GriffinLim):
         if self._ws is None or self._ws.numel() < nb:
             self._ws = torch.empty(nb, dtype=torch.uint8, device=dev)
         T = self.num_frames(L)
-        lin = torch.empty((B, T, self.hp.num_freq), dtype=torch.float32, device=dev)
         if mel and not self.num_mels:
             raise _lib.TacoError(_lib.TACO_ERR_STATE, "the mel output needs a filter bank: call set_mel_basis first (or pass mel=False)")
-        m = torch.empty((B, T, self.num_mels), dtype=torch.float32, device=dev) if mel else None
-        nf = torch.empty((B,), dtype=torch.int32, device=dev)
+        if out is not None:
+            lin, m, nf = out
+            want = [(lin, (B, T, self.hp.num_freq), torch.float32), (nf, (B,), torch.int32)] + ([(m, (B, T, self.num_mels), torch.float32)] if mel else [])
+            for t, shape, dt in want:
+                if not (torch.is_tensor(t) and t.is_cuda and tuple(t.shape) == shape and t.dtype == dt and t.is_contiguous()):
+                    raise Exception("out= wants contiguous %s tensors [B, Tmax, num_freq] / [B, Tmax, num_mels] / [B] on %s; expected shape %s" % (dt, dev, shape))
+            m = m if mel else None
+        else:
+            lin = torch.empty((B, T, self.hp.num_freq), dtype=torch.float32, device=dev)
+            m = torch.empty((B, T, self.num_mels), dtype=torch.float32, device=dev) if mel else None
+            nf = torch.empty((B,), dtype=torch.int32, device=dev)
         p = lambda t: C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)
         with torch.cuda.device(dev):
             _lib.check(self._lib.taco_spec_targets(self._h, C.c_void_p(torch.cuda.current_stream().cuda_stream), p(x), p(ns), B, L, p(lin),

@@ -2272,6 +2272,7 @@ static int forward_enqueue(taco_model* m, hipStream_t st, const int32_t* ids, co
 // ------------------------------------------------------------------------------------------------
 #include "taco_train.h"
 #include "taco_audio.h"
+#include "taco_feed.h"
 
 extern "C" {
 

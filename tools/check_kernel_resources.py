@@ -8,7 +8,8 @@ issue).  csrc/build.sh compiles with -Rpass-analysis=kernel-resource-usage and k
 this script reads them and fails when
 
 any instantiation of k_bigru_duo, k_bigru_oct, k_pointwise_chain, k_cbhg_front, k_head_sweep, k_decoder_xcd or k_decoder_bwd_xcd -- the persistent kernels -- or of k_spec_targets (one pass, but built on the same
-bargain: its magnitudes live in LDS and nothing may fall to memory) has
+bargain: its magnitudes live in LDS and nothing may fall to memory), or k_collate (a bandwidth kernel whose descriptors arrive by value:
+indexing them dynamically would move the argument block to scratch) has
 ScratchSize > 0 (no allowances since round 4: the last one, the 8-rows-per-group BPTT kernel's 196 bytes, went when the owner rows' tape
 offsets became per-step values instead of 22 hoisted pointers).
 
@@ -19,7 +20,7 @@ import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 DEFAULT = os.path.join(ROOT, "multi-speaker-tacotron-tensorflow_amd", "csrc", "kernel_resources.txt")
-NO_SCRATCH = ("k_bigru_duo", "k_bigru_oct", "k_decoder_xcd", "k_decoder_bwd_xcd", "k_pointwise_chain", "k_cbhg_front", "k_head_sweep", "k_spec_targets")  # k_bigru_duo also matches k_bigru_duo_bwd
+NO_SCRATCH = ("k_bigru_duo", "k_bigru_oct", "k_decoder_xcd", "k_decoder_bwd_xcd", "k_pointwise_chain", "k_cbhg_front", "k_head_sweep", "k_spec_targets", "k_collate")  # k_bigru_duo also matches k_bigru_duo_bwd
 ALLOWED_SCRATCH = {}      # (mangled name -> bytes per lane; empty since round 4)
 
 
