@@ -224,6 +224,43 @@ size_t taco_wav_trim_workspace_bytes(int B, int L, int frame_length, int hop_len
 int taco_wav_trim(void* hip_stream, const float* d_wav, const int32_t* d_num_samples, int B, int L, float top_db, int frame_length,
                   int hop_length, int energy, int32_t* d_index, float* d_frame_db, void* d_workspace, size_t workspace_bytes);
 
+/* Splitting a recording on silence: the `librosa.effects.split(audio, top_db=40, frame_length=1024, hop_length=256)` of
+ * audio/silence.py:44-45,53-54 and the `remove_breath` of audio/silence.py:21-31 (a second split at frame_length=128, hop_length=32
+ * and a mute of the quiet sub-intervals).  UNPINNED on librosa, exactly as the trim above: what follows restates the documented
+ * algorithm and could not be checked against librosa's source or output.
+ * taco_wav_split, per row of d_wav [B, L]: frames, energies (both conventions), db and `non_silent = db > -top_db` are the trim's,
+ * computed by the same first launch.  Then, as librosa.effects.split does: edges = flatnonzero(diff(non_silent)) + 1, a 0 prepended if
+ * frame 0 is non-silent, len(non_silent) appended if the last frame is, frames_to_samples (times hop_length), minimum(edges, n),
+ * reshape(-1, 2) -- the maximal runs of non-silent frames in order, run r = {s*hop_length, min(n, e*hop_length)} with s its first
+ * frame and e one past its last.  d_counts[b] always receives the true number of runs; d_intervals [B, max_intervals, 2] receives the
+ * first max_intervals of them and exact zeros in every other word ((Fmax + 1) / 2 runs is the most Fmax = 1 + L/hop_length frames
+ * can hold).  A row with n < 2 has no frames: count 0.  An interval may be empty, {n, n}, when n % hop_length == 0 and only the last
+ * frame is non-silent; it is reported like any other.  The identity that ties the split to the trim: on the same input and
+ * parameters, intervals[b, 0, 0] and intervals[b, count - 1, 1] equal the trim's d_index[b] for every row with n >= 2 (and count 0
+ * where the trim returns {0, 0}).  d_num_samples, d_frame_db, the energy conventions, their LDS limits and TACO_ERR_UNSUPPORTED
+ * cases are the trim's.  Asynchronous on the stream, two launches; no allocation, read-back or synchronisation: capturable.  The order
+ * of the runs comes from a prefix count, not from atomics: two calls on the same input return the same bits.
+ * taco_wav_breath_mute, per row of d_wav [S, L] with that row's interval table and count (a split of the same rectangle): interval k
+ * is muted iff abs_mean(audio[start:end]) < abs_mean(audio) - threshold (0.05 in the reference), abs_mean = mean |x|, and because
+ * the reference mutes in place, abs_mean(audio) is re-evaluated after every mute.  Restated: total = sum |x| over the row's n
+ * samples; walking the intervals in order, k is muted iff len_k > 0 and sum_k/len_k < total/n - threshold, and a muted interval's sum
+ * is then subtracted from total.  An empty interval is never muted (NumPy's mean of nothing is NaN; the comparison is false).  d_out
+ * [S, L] receives the row with the muted intervals as exact zeros, every other sample bit for bit, zeros at and past n; it may be
+ * d_wav itself.  Nothing at or past n is read.  Of a row whose count exceeds max_intervals only the first max_intervals intervals
+ * are considered.  d_muted [S, max_intervals] (nullable) receives the flags; d_abs_mean [S, 1 + max_intervals] (nullable) total/n
+ * before any mute (0 for an empty row), then every interval's mean (NaN for an empty one); entries past a row's count are zero.
+ * One launch, capturable; every sum has one order, two calls return the same bits.
+ * TACO_ERR_ARG (before any device call): a null required pointer, B, S or L < 1, hop_length < 1, frame_length < 2, max_intervals < 1,
+ * unknown energy, workspace below taco_wav_split_workspace_bytes. */
+size_t taco_wav_split_workspace_bytes(int B, int L, int frame_length, int hop_length);
+int taco_wav_split(void* hip_stream, const float* d_wav, const int32_t* d_num_samples, int B, int L, float top_db,
+                   int frame_length, int hop_length, int energy, int max_intervals,
+                   int32_t* d_intervals /* [B, max_intervals, 2] */, int32_t* d_counts /* [B] */,
+                   float* d_frame_db /* nullable */, void* d_workspace, size_t workspace_bytes);
+int taco_wav_breath_mute(void* hip_stream, const float* d_wav, const int32_t* d_num_samples, int S, int L,
+                         const int32_t* d_intervals, const int32_t* d_counts, int max_intervals, float threshold,
+                         float* d_out, int32_t* d_muted /* nullable */, float* d_abs_mean /* nullable */);
+
 /* ---- waveform -> linear and mel training targets (audio/__init__.py:48-51,64-67,142-147,155-156,161-162; datasets/generate_data.py:151-158),
  * on the taco_gl handle: the same windowed-DFT pack, slots and frame rows as the Griffin-Lim loop ---- */
 /* The mel filter bank, host memory [num_mels, num_freq] row-major (librosa.filters.mel of the reference's _build_mel_basis; the Python

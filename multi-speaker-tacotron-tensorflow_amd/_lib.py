@@ -137,6 +137,9 @@ PROTOTYPES = {
     "taco_wav_to_pcm16": (_I, [_P, _P, _P, _I, _I, _P]),
     "taco_wav_trim_workspace_bytes": (_S, [_I, _I, _I, _I]),
     "taco_wav_trim": (_I, [_P, _P, _P, _I, _I, C.c_float, _I, _I, _I, _P, _P, _P, _S]),
+    "taco_wav_split_workspace_bytes": (_S, [_I, _I, _I, _I]),
+    "taco_wav_split": (_I, [_P, _P, _P, _I, _I, C.c_float, _I, _I, _I, _I, _P, _P, _P, _P, _S]),
+    "taco_wav_breath_mute": (_I, [_P, _P, _P, _I, _I, _P, _P, _I, C.c_float, _P, _P, _P]),
     "taco_gl_set_mel_basis": (_I, [_P, _P, _I]),
     "taco_spec_num_mels": (_I, [_P]),
     "taco_spec_num_frames": (_I, [C.POINTER(TacoAudioHParams), _I]),

@@ -172,6 +172,67 @@ class GriffinLim(object):
                                                frame_length, hop_length, modes[energy], p(index), p(db), p(self._ws), self._ws.numel()))
         return (index, db) if return_db else index
 
+    def _rows(self, wav, num_samples):
+        """(x [B, L] float32 contiguous on the device, num_samples [B] int32 on the device or None)"""
+        dev = self.device
+        x = (wav if torch.is_tensor(wav) else torch.as_tensor(np.asarray(wav))).to(dev, torch.float32).contiguous()
+        if x.dim() != 2:
+            raise Exception("wav must be [B, L], got shape %s" % (tuple(x.shape),))
+        ns = None if num_samples is None else (num_samples if torch.is_tensor(num_samples) else torch.as_tensor(np.asarray(num_samples))).to(dev, torch.int32).contiguous()
+        if ns is not None and tuple(ns.shape) != (x.shape[0],):
+            raise Exception("num_samples must be [B] = [%d], got %s" % (x.shape[0], tuple(ns.shape)))
+        return x, ns
+
+    def split(self, wav, num_samples=None, top_db=60, frame_length=2048, hop_length=512, energy="spectral", max_intervals=None, return_db=False):
+        """librosa.effects.split per row (audio/silence.py:44-45 calls it with top_db=40, frame_length=1024, hop_length=256, remove_breath
+        with 40 / 128 / 32; the defaults here are librosa's): wav [B, L] float32, num_samples [B] (a device int32 tensor is used as it
+        is; None: L) -> (intervals [B, M, 2], counts [B]), device int32 tensors: row b's maximal runs of non-silent frames in order as
+        [start, end) in samples, counts[b] of them, exact zeros after; with return_db also the frames' dB as `trim` returns them.  M =
+        max_intervals, by default (Fmax + 1) // 2 with Fmax = 1 + L // hop_length, the most runs Fmax frames can hold, so the table
+        never overflows; with a smaller M counts still holds the true number and the first M runs are written.  Frames, energies and
+        the threshold are `trim`'s: intervals[b, 0, 0] and intervals[b, counts[b] - 1, 1] are its index.  UNPINNED on librosa
+        (include/taco_abi.h, taco_wav_split), checked against tests/split_reference.py, not against librosa."""
+        x, ns = self._rows(wav, num_samples)
+        B, L = x.shape
+        dev = self.device
+        modes = {"spectral": _lib.TACO_TRIM_SPECTRAL, "time": _lib.TACO_TRIM_TIME}
+        if energy not in modes:
+            raise _lib.TacoError(_lib.TACO_ERR_ARG, "energy must be one of %s, got %r" % (sorted(modes), energy))
+        frame_length, hop_length = int(frame_length), int(hop_length)
+        fmax = 1 + L // max(hop_length, 1)
+        M = (fmax + 1) // 2 if max_intervals is None else int(max_intervals)
+        nb = int(self._lib.taco_wav_split_workspace_bytes(B, L, frame_length, hop_length))
+        if self._ws is None or self._ws.numel() < nb:
+            self._ws = torch.empty(nb, dtype=torch.uint8, device=dev)
+        intervals = torch.empty((B, max(M, 1), 2), dtype=torch.int32, device=dev)
+        counts = torch.empty((B,), dtype=torch.int32, device=dev)
+        db = torch.empty((B, fmax), dtype=torch.float32, device=dev) if return_db else None
+        p = lambda t: C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)
+        with torch.cuda.device(dev):
+            _lib.check(self._lib.taco_wav_split(C.c_void_p(torch.cuda.current_stream().cuda_stream), p(x), p(ns), B, L, float(top_db), frame_length,
+                                                hop_length, modes[energy], M, p(intervals), p(counts), p(db), p(self._ws), self._ws.numel()))
+        return (intervals, counts, db) if return_db else (intervals, counts)
+
+    def remove_breath(self, wav, num_samples=None, top_db=40, frame_length=128, hop_length=32, threshold=0.05, energy="spectral", return_info=False):
+        """remove_breath of audio/silence.py:21-31 per row of a rectangle (the defaults are its constants): `split` at 128 / 32, then
+        every interval whose mean |x| lies more than `threshold` below the row's -- re-evaluated after every mute, as the reference
+        mutes in place -- is set to zero.  wav [B, L], num_samples [B] or None -> the muted waveforms [B, L] (a new device tensor:
+        bits of the input outside the muted intervals, zeros past num_samples[b]); with return_info also (intervals, counts, muted
+        [B, M] int32, abs_mean [B, 1 + M] float32: the row's mean before any mute, then each interval's)."""
+        x, ns = self._rows(wav, num_samples)
+        B, L = x.shape
+        dev = self.device
+        intervals, counts = self.split(x, ns, top_db=top_db, frame_length=frame_length, hop_length=hop_length, energy=energy)
+        M = intervals.shape[1]
+        out = torch.empty_like(x)
+        muted = torch.empty((B, M), dtype=torch.int32, device=dev) if return_info else None
+        mean = torch.empty((B, 1 + M), dtype=torch.float32, device=dev) if return_info else None
+        p = lambda t: C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)
+        with torch.cuda.device(dev):
+            _lib.check(self._lib.taco_wav_breath_mute(C.c_void_p(torch.cuda.current_stream().cuda_stream), p(x), p(ns), B, L, p(intervals), p(counts),
+                                                      M, float(threshold), p(out), p(muted), p(mean)))
+        return (out, (intervals, counts, muted, mean)) if return_info else out
+
     def close(self):
         if getattr(self, "_h", None):
             self._lib.taco_gl_destroy(self._h)

@@ -248,6 +248,147 @@ __global__ __launch_bounds__(256) void k_trim_index(const float* mse, const int*
   }
 }
 
+// ---- splitting on silence: librosa.effects.split and remove_breath (audio/silence.py:21-31,44-45,53-54), restated; UNPINNED on librosa ----
+#define SPLIT_THREADS 256      // four waves: a chunk of k_split_edges is 256 frames
+// The maximal runs of non-silent frames of row b, in order, from the mse table k_trim_energy wrote.  db[t] is formed with exactly the
+// arithmetic of k_trim_index (contraction off, the same ref, non-silent where db > -top_db).  An EDGE is a frame t in [0, nf] whose
+// state differs from frame t - 1's, with frames -1 and nf counted as silent: that is flatnonzero(diff(non_silent)) + 1 with the 0
+// prepended when frame 0 is non-silent and len(non_silent) appended when the last frame is.  Edge number k (even: a run starts, odd:
+// one ends) goes to word k of the row's table as min(n, t*hop) -- so run r is {s*hop, min(n, e*hop)}, and {n, n} when n % hop == 0
+// and only the last frame is non-silent.  k comes from a block-wide prefix count: ballot and popcount inside a wave, the four wave
+// totals through LDS, and a running count carried across the 256-frame chunks of a long row -- no atomics, so the order does not
+// depend on scheduling and two calls return the same bits.  counts[b] receives the true number of runs; only the first
+// max_intervals are written and every other word of the row's table is an exact zero.  frame_db as in k_trim_index.  One workgroup
+// per row; a row of fewer than two samples has no frames and count 0.
+__global__ __launch_bounds__(SPLIT_THREADS) void k_split_edges(const float* mse, const int* num_samples, int L, int hop, int Fmax, float top_db,
+                                                               int max_intervals, int* intervals, int* counts, float* frame_db) {
+#pragma clang fp contract(off)      // as k_trim_index: the product is rounded before the subtraction
+  __shared__ float pmax[4];
+  __shared__ unsigned long long wmask[4];
+  __shared__ int wedges[4];
+  const int b = blockIdx.x, tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+  const int n = trim_samples(num_samples, b, L), nf = n < 2 ? 0 : 1 + n / hop;
+  const float* e = mse + (size_t)b * Fmax;
+  int* tab = intervals + (size_t)b * max_intervals * 2;
+  const long long cap = 2LL * max_intervals;
+  float mx = 0.f;                                          // energies are >= 0
+  for (int t = tid; t < nf; t += SPLIT_THREADS) mx = fmaxf(mx, e[t]);
+  for (int o = 32; o > 0; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o));
+  if (lane == 0) pmax[wave] = mx;
+  __syncthreads();
+  mx = fmaxf(fmaxf(pmax[0], pmax[1]), fmaxf(pmax[2], pmax[3]));
+  const float ref = 10.f * log10f(fmaxf(1e-10f, mx));
+  const int last = max(nf, frame_db ? Fmax - 1 : 0);       // frames 0 .. last are visited: nf itself closes a run that reaches the end
+  long long seen = 0;                                      // edges in the chunks before this one (the same in every thread)
+  bool carry = false;                                      // the state of the last frame of the chunk before this one
+  for (int t0 = 0; t0 <= last; t0 += SPLIT_THREADS) {
+    const int t = t0 + tid;
+    float db = 0.f;
+    bool loud = false;
+    if (t < nf) {
+      db = 10.f * log10f(fmaxf(1e-10f, e[t])) - ref;
+      loud = db > -top_db;
+    }
+    if (frame_db && t < Fmax) frame_db[(size_t)b * Fmax + t] = db;
+    const unsigned long long m = __ballot(loud);
+    if (lane == 0) wmask[wave] = m;
+    __syncthreads();
+    const bool before = lane ? (m >> (lane - 1)) & 1 : (wave ? (wmask[wave - 1] >> 63) & 1 : carry);
+    carry = (wmask[3] >> 63) & 1;
+    const bool edge = t <= nf && loud != before;
+    const unsigned long long em = __ballot(edge);
+    if (lane == 0) wedges[wave] = __popcll(em);
+    __syncthreads();
+    long long k = seen + __popcll(em & ((1ull << lane) - 1));
+    for (int w = 0; w < wave; ++w) k += wedges[w];
+    if (edge && k < cap) tab[k] = (int)min((long long)n, (long long)t * hop);
+    seen += wedges[0] + wedges[1] + wedges[2] + wedges[3];
+  }
+  if (tid == 0) counts[b] = (int)(seen / 2);               // every run that starts also ends: frame nf is silent
+  for (long long i = min(seen, cap) + tid; i < cap; i += SPLIT_THREADS) tab[i] = 0;
+}
+#define MUTE_THREADS 1024      // sixteen waves per row of k_breath_mute
+#define MUTE_BATCH 1024        // intervals whose sums are held in LDS at a time
+// remove_breath (audio/silence.py:21-31) on row s of a rectangle [S, L], given the row's interval table (k_split_edges at 128 / 32)
+// and count: interval k is muted iff abs_mean(audio[start:end]) < abs_mean(audio) - threshold, and since the reference mutes in
+// place, abs_mean(audio) is re-evaluated after every mute.  Restated with sums: total = sum |x| over the row's n samples, sum_k over
+// interval k (the intervals are disjoint, so muting one changes no other's sum); ONE thread walks the intervals in order with a
+// running total: muted iff len_k > 0 and sum_k/len_k < total/n - threshold, and a muted interval's sum leaves the total.  An empty
+// interval is never muted (NumPy's mean of nothing is NaN and the comparison is false).  Every sum has one order: thread i of the
+// row's 1024 (lane i of an interval's wave) adds its samples i, i + stride, ... in that order, and butterflies and a fixed chain
+// join the partial sums.  The row is first copied to out (zeros past n; out may alias wav, the copy is then each thread's own word),
+// then the table is taken MUTE_BATCH intervals at a time -- sums by the waves round-robin, the walk, the zeros of the muted ones by
+// the waves round-robin -- so a table of any length is served from a fixed LDS footprint, bounded, without a spin.  Only the first
+// max_intervals intervals of a row exist for it; bounds are clamped to [0, n] and nothing at or past n is read.
+// muted [S, max_intervals] and abs_mean [S, 1 + max_intervals] (both nullable): the flags, and total/n (0 for an empty row) followed
+// by every interval's mean (NaN for an empty one, as NumPy's); entries past the row's count are zero.
+__global__ __launch_bounds__(MUTE_THREADS) void k_breath_mute(const float* wav, const int* num_samples, int L, const int* intervals,
+                                                              const int* counts, int max_intervals, float threshold, float* out, int* muted,
+                                                              float* abs_mean) {
+#pragma clang fp contract(off)      // the means are rounded before they are compared, as the reported ones are
+  __shared__ float part[MUTE_THREADS / 64];
+  __shared__ float isum[MUTE_BATCH];
+  __shared__ int ilo[MUTE_BATCH], ihi[MUTE_BATCH];
+  __shared__ int iflag[MUTE_BATCH];
+  __shared__ float total_s;
+  const int s = blockIdx.x, tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+  const int n = trim_samples(num_samples, s, L);
+  const int cnt = min(max(counts[s], 0), max_intervals);
+  const float* x = wav + (size_t)s * L;
+  float* y = out + (size_t)s * L;
+  const int* tab = intervals + (size_t)s * max_intervals * 2;
+  float acc = 0.f;
+  for (int i = tid; i < L; i += MUTE_THREADS) {
+    const float v = i < n ? x[i] : 0.f;
+    acc += fabsf(v);
+    y[i] = v;
+  }
+  for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o);
+  if (lane == 0) part[wave] = acc;
+  __syncthreads();
+  if (tid == 0) {
+    float t = 0.f;
+    for (int w = 0; w < MUTE_THREADS / 64; ++w) t += part[w];
+    total_s = t;
+    if (abs_mean) abs_mean[(size_t)s * (1 + max_intervals)] = n > 0 ? t / (float)n : 0.f;
+  }
+  for (int k0 = 0; k0 < cnt; k0 += MUTE_BATCH) {
+    const int kb = min(MUTE_BATCH, cnt - k0);
+    for (int j = wave; j < kb; j += MUTE_THREADS / 64) {
+      const int lo = min(max(tab[2 * (k0 + j)], 0), n), hi = min(max(tab[2 * (k0 + j) + 1], lo), n);
+      float a = 0.f;
+      for (int i = lo + lane; i < hi; i += 64) a += fabsf(x[i]);
+      for (int o = 32; o > 0; o >>= 1) a += __shfl_xor(a, o);
+      if (lane == 0) { isum[j] = a; ilo[j] = lo; ihi[j] = hi; }
+    }
+    __syncthreads();                                       // (also orders the copy above before the zeros below)
+    if (tid == 0) {
+      float total = total_s;
+      const float fn = (float)n;
+      for (int j = 0; j < kb; ++j) {
+        const int len = ihi[j] - ilo[j];
+        const bool m = len > 0 && isum[j] / (float)len < total / fn - threshold;
+        if (m) total -= isum[j];
+        iflag[j] = m;
+      }
+      total_s = total;
+    }
+    __syncthreads();
+    for (int j = tid; j < kb; j += MUTE_THREADS) {
+      if (muted) muted[(size_t)s * max_intervals + k0 + j] = iflag[j];
+      if (abs_mean) abs_mean[(size_t)s * (1 + max_intervals) + 1 + k0 + j] = isum[j] / (float)(ihi[j] - ilo[j]);
+    }
+    for (int j = wave; j < kb; j += MUTE_THREADS / 64)
+      if (iflag[j])
+        for (int i = ilo[j] + lane; i < ihi[j]; i += 64) y[i] = 0.f;
+    __syncthreads();                                       // the next batch overwrites isum / ilo / ihi
+  }
+  for (int k = cnt + tid; k < max_intervals; k += MUTE_THREADS) {
+    if (muted) muted[(size_t)s * max_intervals + k] = 0;
+    if (abs_mean) abs_mean[(size_t)s * (1 + max_intervals) + 1 + k] = 0.f;
+  }
+}
+
 // ---- waveform -> linear and mel targets (audio/__init__.py:48-51,64-67,142-147,155-156,161-162; datasets/generate_data.py:151-158) ----
 #define SPEC_ROWS 4            // frame rows per workgroup of k_spec_targets: the band table is fetched once for four rows
 // Samples utterance b keeps: Lmax, or num_samples[b] (device memory) clamped to [n_fft/2 + 1, Lmax] -- reflect padding needs n > n_fft/2

@@ -163,6 +163,46 @@ int taco_wav_trim(void* hip_stream, const float* d_wav, const int32_t* d_num_sam
   return 0;
 }
 
+// ---- splitting on silence (librosa.effects.split and remove_breath, audio/silence.py:21-31,44-45,53-54) ----
+size_t taco_wav_split_workspace_bytes(int B, int L, int frame_length, int hop_length) {
+  return taco_wav_trim_workspace_bytes(B, L, frame_length, hop_length);      // the same mse [B, Fmax]
+}
+
+int taco_wav_split(void* hip_stream, const float* d_wav, const int32_t* d_num_samples, int B, int L, float top_db, int frame_length,
+                   int hop_length, int energy, int max_intervals, int32_t* d_intervals, int32_t* d_counts, float* d_frame_db, void* d_workspace,
+                   size_t workspace_bytes) {
+  if (!d_wav || !d_intervals || !d_counts || !d_workspace || B <= 0 || B > 65535 || L <= 0) return fail(TACO_ERR_ARG, "bad argument");
+  if (hop_length < 1 || frame_length < 2) return fail(TACO_ERR_ARG, "bad frame parameters: frame_length %d, hop_length %d", frame_length, hop_length);
+  if (max_intervals < 1) return fail(TACO_ERR_ARG, "max_intervals = %d", max_intervals);
+  if (energy != TACO_TRIM_SPECTRAL && energy != TACO_TRIM_TIME) return fail(TACO_ERR_ARG, "unknown energy convention %d", energy);
+  const size_t need = taco_wav_split_workspace_bytes(B, L, frame_length, hop_length);
+  if (workspace_bytes < need) return fail(TACO_ERR_ARG, "workspace too small: need %zu bytes, have %zu", need, workspace_bytes);
+  if (frame_length & 1) return fail(TACO_ERR_UNSUPPORTED, "frame_length = %d: the one-sided spectrum sum is written for an even length", frame_length);
+  const int fpt = trim_frames_per_tile(frame_length, hop_length, energy);
+  if (fpt < 1)
+    return fail(TACO_ERR_UNSUPPORTED, "frame_length = %d: k_trim_energy keeps a frame%s in %d KB of LDS", frame_length,
+                energy == TACO_TRIM_SPECTRAL ? " and its window" : "", TRIM_LDS_BYTES / 1024);
+  hipStream_t st = (hipStream_t)hip_stream;
+  const int Fmax = 1 + L / hop_length;
+  float* mse = (float*)d_workspace;
+  hipLaunchKernelGGL(k_trim_energy, dim3(cdiv(Fmax, fpt), B), dim3(TRIM_THREADS), trim_lds_bytes(frame_length, hop_length, fpt, energy), st, d_wav,
+                     d_num_samples, L, frame_length, hop_length, fpt, Fmax, energy, mse);
+  hipLaunchKernelGGL(k_split_edges, dim3(B), dim3(SPLIT_THREADS), 0, st, mse, d_num_samples, L, hop_length, Fmax, top_db, max_intervals, d_intervals,
+                     d_counts, d_frame_db);
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
+int taco_wav_breath_mute(void* hip_stream, const float* d_wav, const int32_t* d_num_samples, int S, int L, const int32_t* d_intervals,
+                         const int32_t* d_counts, int max_intervals, float threshold, float* d_out, int32_t* d_muted, float* d_abs_mean) {
+  if (!d_wav || !d_intervals || !d_counts || !d_out || S <= 0 || L <= 0) return fail(TACO_ERR_ARG, "bad argument");
+  if (max_intervals < 1) return fail(TACO_ERR_ARG, "max_intervals = %d", max_intervals);
+  hipLaunchKernelGGL(k_breath_mute, dim3(S), dim3(MUTE_THREADS), 0, (hipStream_t)hip_stream, d_wav, d_num_samples, L, d_intervals, d_counts,
+                     max_intervals, threshold, d_out, d_muted, d_abs_mean);
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
 // ---- waveform -> linear and mel targets ----
 int taco_gl_set_mel_basis(taco_gl* g, const float* host_basis, int num_mels) {
   if (!g || !host_basis || num_mels <= 0) return fail(TACO_ERR_ARG, "bad argument");

@@ -11,7 +11,12 @@ difference, not a measurement).  It runs with `--analysis` only, INSTEAD of the 
 `--trim` measures the silence trim of librosa_trim=True (GriffinLim.trim at 5120 / 256 / 50 dB, synthesizer.py:266-269) on a batch of the C2
 output shape -- 32 rows x 153 300 samples with the seeded per-utterance lengths of the synthesis arms, each row noise with a quiet last
 fifth: the trim alone, the tail of synthesize_audio (pcm16 alone = flag off; trim + end column + pcm16 = flag on), and the float64
-restatement tests/trim_reference.py on the CPU for the same batch, whose indices the device must reproduce.  Its own JSON line, `--trim` only."""
+restatement tests/trim_reference.py on the CPU for the same batch, whose indices the device must reproduce.  Its own JSON line, `--trim` only.
+`--split` measures splitting a recording on silence (audio/silence.py:33-76) on a synthetic recording of three minutes at 24 kHz -- seeded
+utterances of 2-9 s, each loud phrases with quieter breaths between short pauses, separated by 0.5-1.5 s of noise floor: the split alone
+(GriffinLim.split at 1024 / 256 / 40 dB, one row), the whole taco_amd.split_on_silence (two splits, the intervals gathered, remove_breath at
+128 / 32, scattered back, intervals downloaded), and the float64 restatement tests/split_reference.py on the CPU, whose segments the device
+must reproduce.  Its own JSON line, `--split` only."""
 import json, os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "oracle"))
@@ -110,6 +115,77 @@ def trim():
     return out
 
 
+def split_recording(seconds=180, seed=5):
+    """float32 [seconds * sample_rate]: noise floor 1e-5; utterances of 2-9 s made of phrases (0.15-0.3) of 0.4-1.2 s, pauses of 15-30 ms at 1e-4 (shorter than the 1024-sample frame, longer than the 128-sample one)
+    and now and then a breath (0.01-0.03) of 0.2-0.4 s between two pauses."""
+    sr = hp.sample_rate
+    rs = np.random.RandomState(seed)
+    n = seconds * sr
+    x = 1e-5 * rs.randn(n)
+    t = int(0.5 * sr)
+    while True:
+        end = t + int(rs.uniform(2.0, 9.0) * sr)
+        if end >= n - sr:
+            break
+        while t < end:
+            m = min(end - t, int(rs.uniform(0.4, 1.2) * sr))
+            x[t:t + m] = rs.uniform(0.15, 0.3) * rs.randn(m); t += m
+            m = min(end - t, int(rs.uniform(0.015, 0.03) * sr))
+            x[t:t + m] = 1e-4 * rs.randn(m); t += m
+            if rs.rand() < 0.4 and t < end:
+                m = min(end - t, int(rs.uniform(0.2, 0.4) * sr))
+                x[t:t + m] = rs.uniform(0.01, 0.03) * rs.randn(m); t += m
+                m = min(end - t, int(rs.uniform(0.015, 0.03) * sr))
+                x[t:t + m] = 1e-4 * rs.randn(m); t += m
+        t = end + int(rs.uniform(0.5, 1.5) * sr)
+    return x.astype(np.float32)
+
+
+def split():
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import split_reference as R
+    x = split_recording()
+    dev = taco_amd.silence.SilenceDevice(hp)
+    gl = dev.gl
+    wav = dev.upload(x)
+    kw = dict(top_db=40, frame_length=1024, hop_length=256)
+    arms = {"split": (lambda: gl.split(wav, None, **kw), 10), "split_on_silence": (lambda: taco_amd.split_on_silence(x, hp, device=dev), 2)}
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    for f, _ in arms.values():
+        for _ in range(2):
+            f()
+    torch.cuda.synchronize()
+    ms = {k: [] for k in arms}
+    for _ in range(5):
+        for k, (f, reps) in arms.items():
+            e0.record()
+            for _ in range(reps):
+                f()
+            e1.record(); torch.cuda.synchronize()
+            ms[k].append(e0.elapsed_time(e1) / reps)
+    med = {k: float(np.median(v)) for k, v in ms.items()}
+    no_breath, segments = taco_amd.split_on_silence(x, hp, device=dev)
+    again = taco_amd.split_on_silence(x, hp, device=dev)
+    first = dev.split(wav, 40, 1024, 256)
+    t0 = time.perf_counter(); ref = R.split_on_silence(x, hp.sample_rate); cpu_s = time.perf_counter() - t0
+    out = {"metric": "split on silence (audio/silence.py:33-76: split at 1024/256/40 dB, remove_breath at 128/32, second split) of one recording",
+           "value": med["split_on_silence"], "unit": "ms", "recording": "%.0f s at %d Hz, %d samples" % (len(x) / hp.sample_rate, hp.sample_rate, len(x)),
+           "windows": "5 windows per arm, alternating: 10 calls of the split, 2 of split_on_silence", "split_ms": ms["split"],
+           "split_on_silence_ms": ms["split_on_silence"], "split_median_ms": med["split"], "x_realtime": len(x) / hp.sample_rate / (med["split_on_silence"] / 1e3),
+           "cpu_restatement_float64_s": cpu_s, "intervals_first_split": int(len(first)), "intervals_second_split": int(len(ref["second"])),
+           "segments_kept": len(segments), "samples_muted": int(((no_breath == 0) & (x != 0)).sum()),
+           "first_split_equals_the_restatement": bool(np.array_equal(first, ref["first"])),
+           "segments_equal_to_the_restatement": bool([s[:3] for s in segments] == ref["kept"]),
+           "no_breath_equals_the_restatement": bool(np.array_equal(no_breath, ref["no_breath"].astype(np.float32))),
+           "restatement_db_margin": ref["db_margin"], "restatement_decision_margin": ref["decision_margin"],
+           "identical_bits_on_two_calls": bool(np.array_equal(again[0], no_breath) and [s[:3] for s in again[1]] == [s[:3] for s in segments])}
+    dev.close()
+    return out
+
+
+if "--split" in sys.argv:
+    print(json.dumps(split()))
+    sys.exit(0)
 if "--trim" in sys.argv:
     print(json.dumps(trim()))
     sys.exit(0)
