@@ -261,6 +261,70 @@ int taco_wav_breath_mute(void* hip_stream, const float* d_wav, const int32_t* d_
                          const int32_t* d_intervals, const int32_t* d_counts, int max_intervals, float threshold,
                          float* d_out, int32_t* d_muted /* nullable */, float* d_abs_mean /* nullable */);
 
+/* ---- recordings to the model's sample rate: librosa.core.load(path, sr=hparams.sample_rate) after decoding, and resample_audio
+ * (audio/__init__.py:12-20,30-32; recognition/google.py:48: 24 kHz -> 16 kHz) -- resampy.resample's band-limited sinc interpolation
+ * (filter 'kaiser_best') and librosa.core.resample's fix_length, restated ----
+ * UNPINNED on resampy and librosa (the reference pins resampy 0.2.0 and librosa 0.5.1; neither is a dependency and no test runs
+ * them): a restatement of the documented algorithm, held by tests/resample_reference.py, not by either library.
+ * The filter.  The caller supplies the half window of resampy's sinc_window(num_zeros, precision, kaiser(beta), rolloff): with
+ * num_table = 2^precision and n = num_table*num_zeros, half[i] = rolloff * sinc(rolloff * i/num_table) * kaiser(2n + 1, beta)[n + i],
+ * i = 0..n (n_window = n + 1 entries; the Python package builds it in float64, audio.kaiser_window -- the precedent is
+ * taco_gl_set_mel_basis).  With ratio = (double)target_sr/orig_sr: win = half*ratio if ratio < 1 else half; delta[i] = win[i+1] - win[i],
+ * delta[last] = 0; scale = min(1, ratio); step = (int)(scale*num_table).  An output at input position tau = n + rem (n integer) is
+ *   left wing:  frac = scale*rem, f = frac*num_table, off = (int)f, eta = f - off;
+ *               sum over i < (n_window - off)/step of (win[off + i*step] + eta*delta[off + i*step]) * x[n - i]
+ *   right wing: the same with frac = scale - scale*rem, over k < (n_window - off)/step, on x[n + k + 1]
+ * and a tap outside [0, n_samples) contributes nothing (the bounds of resampy's loops).  No rescaling (librosa's scale=False).
+ * EXACT POSITIONS -- where this departs from the pin.  resampy 0.2.0 advances tau by `time_register += 1/ratio`, a serial float64 sum
+ * whose rounding depends on every output before it; no parallel kernel reproduces it.  Here tau = t*orig_sr/target_sr exactly: with
+ * g = gcd(orig_sr, target_sr), P = target_sr/g, Q = orig_sr/g, output t has n = (t*Q) div P and r = (t*Q) mod P in 64-bit integers and
+ * rem = (double)r/P.  The weights of an output then depend on r alone: the filter is a POLYPHASE BANK of P rows, built once by
+ * taco_resample_create on the host in double with exactly the operations above in that order (no fused multiply-add), rounded to
+ * fp32.  Against the accumulated register (checked in float64 for 44100, 48000, 22050, 16000, 32000, 11025 -> 24000 and 24000 -> 16000
+ * over 2e6 outputs each): int(t*(1/ratio)) is the exact n everywhere, and the accumulated register lands on a different integer only
+ * at outputs with r == 0 (a rounding to one side of an integer position or the other; 18 286 of 2e6 outputs at 44100 -> 24000,
+ * 419 430 of 2e6 at 16000 -> 24000).  When up-sampling, step == num_table and the two evaluations are continuous across that
+ * boundary: the values agree to ~1e-10.  When down-sampling, step is truncated and they differ: up to 8e-4 on a row of 3000
+ * unit-scale samples at 44100 -> 24000 (2.4e-3 with kaiser_best and 1.8e-2 with a 4-zero filter in tests/test_resample_host.py), at
+ * those outputs only.  At every other output the two share n and differ by the register's own rounding (~1e-12 of the position)
+ * times the filter's slope.  This is inherent, not an error bound of the kernel.
+ * The bank.  Row r has LW + RW = taco_resample_taps entries, LW = taco_resample_left_taps the most left-wing taps any phase has and
+ * RW the most right-wing taps; entry j weighs x[n - (LW - 1) + j]: the left wing runs backwards from j = LW - 1 (x[n]) to j = 0, the
+ * right wing forwards from j = LW (x[n + 1]); a phase with fewer taps in a wing has exact zeros at that end.  taco_resample_bank copies
+ * the fp32 bank to host memory as [P, taps] in this order (for tests and native callers).
+ * taco_resample_create needs no device: the bank is uploaded by the first taco_wav_resample on the handle (that first call allocates
+ * and copies: make it outside stream capture).  TACO_ERR_ARG with a message: a null pointer, a rate <= 0, num_table < 1, n_window < 2,
+ * (int)(scale*num_table) == 0, a filter without taps, a bank of more than 2^22 entries (16 MB; every pair among 8000, 11025, 16000,
+ * 22050, 24000, 32000, 44100, 48000 Hz with kaiser_best fits: the largest are 32000 -> 11025, 441 x 372, and 11025 -> 32000, 1280 x
+ * 128).  TACO_ERR_UNSUPPORTED: a ratio so small that the inputs of one tile of outputs (taco_resample_tile = 1024 consecutive outputs
+ * of a row) and the filter's reach exceed 64 KB of LDS (orig_sr/target_sr above ~14 with kaiser_best).
+ * Lengths, the float64 expressions of the reference: taco_resample_computed_len = (int)(n*ratio), what resampy computes;
+ * taco_resample_out_len = (int)ceil(n*ratio), what librosa.core.resample returns after fix_length (at most one trailing zero). */
+typedef struct taco_resample taco_resample;
+int taco_resample_create(int orig_sr, int target_sr, const double* host_half_window, int n_window, int num_table, int device,
+                         taco_resample** out);
+void taco_resample_destroy(taco_resample* r);
+int taco_resample_out_len(const taco_resample* r, int n);
+int taco_resample_computed_len(const taco_resample* r, int n);
+int taco_resample_phases(const taco_resample* r);            /* P */
+int taco_resample_taps(const taco_resample* r);              /* LW + RW: the length of a bank row */
+int taco_resample_left_taps(const taco_resample* r);         /* LW: entry LW - 1 of a row weighs x[n] */
+int taco_resample_tile(const taco_resample* r);              /* consecutive outputs of a row one workgroup computes */
+int taco_resample_bank(const taco_resample* r, float* host_out /* [P, taps] */);
+/* B rows at once.  d_in [B, L, channels], interleaved, of in_format TACO_WAV_F32 (float) or TACO_WAV_PCM16 (int16_t, converted as
+ * s * (1/32768): audioread's buf_to_float); channels > 1 takes the mean over channels (librosa.to_mono) while the inputs are staged --
+ * the sum in double, rounded to fp32 once; no mono copy reaches memory.  d_num_samples [B] device int32 (NULL: every row has L),
+ * clamped to [0, L] and only read on the device.  Row b of d_out [B, L_out]: outputs [0, computed_len(n_b)) are computed, exact zeros
+ * follow up to L_out, and d_out_samples[b] (nullable) = out_len(n_b) -- both lengths formed on the device in double from the
+ * expressions above.  L_out >= taco_resample_out_len(r, L).  fp32 products and sums, taps in the order j = 0, 1, ... by fused
+ * multiply-add: an output's bits depend on its row's samples alone, not on the batch, the tile or the call.  One launch, no workspace,
+ * no read-back or synchronisation: capturable (after the handle's first call).  TACO_ERR_ARG (before any device call): a null
+ * required pointer, B < 1 or > 65535, L < 1, an unknown in_format, channels < 1, L_out below taco_resample_out_len(r, L). */
+#define TACO_WAV_F32 0
+#define TACO_WAV_PCM16 1
+int taco_wav_resample(taco_resample* r, void* hip_stream, const void* d_in, int in_format, int channels,
+                      const int32_t* d_num_samples, int B, int L, float* d_out, int L_out, int32_t* d_out_samples);
+
 /* ---- waveform -> linear and mel training targets (audio/__init__.py:48-51,64-67,142-147,155-156,161-162; datasets/generate_data.py:151-158),
  * on the taco_gl handle: the same windowed-DFT pack, slots and frame rows as the Griffin-Lim loop ---- */
 /* The mel filter bank, host memory [num_mels, num_freq] row-major (librosa.filters.mel of the reference's _build_mel_basis; the Python

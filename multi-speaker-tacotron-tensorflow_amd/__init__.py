@@ -4,7 +4,7 @@ csrc/libtaco_hip.so (hand-written gfx950 HIP); this package is the thin host mir
 from .hparams import hparams, HParams, basic_params, load_hparams, save_hparams   # noqa: F401
 from .tacotron import Tacotron, create_model, input_lengths_from_tokens            # noqa: F401
 from .synthesizer import Synthesizer                                               # noqa: F401
-from .audio import GriffinLim, Spectrogram                                        # noqa: F401
+from .audio import GriffinLim, Spectrogram, Resampler                                   # noqa: F401
 from .trainer import Trainer                                                       # noqa: F401
 from .feeder import DeviceCorpus                                                   # noqa: F401
 from .silence import split_on_silence                                              # noqa: F401

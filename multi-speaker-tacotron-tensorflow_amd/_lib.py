@@ -10,6 +10,7 @@ LIB_PATH = os.path.join(_HERE, "csrc", "libtaco_hip.so")
 
 TACO_ERR_ARG, TACO_ERR_SHAPE, TACO_ERR_UNSUPPORTED, TACO_ERR_HIP, TACO_ERR_STATE = -1, -2, -3, -4, -5
 TACO_TRIM_SPECTRAL, TACO_TRIM_TIME = 0, 1      # taco_wav_trim's `energy`
+TACO_WAV_F32, TACO_WAV_PCM16 = 0, 1            # taco_wav_resample's `in_format`
 
 
 class TacoHParams(C.Structure):
@@ -140,6 +141,16 @@ PROTOTYPES = {
     "taco_wav_split_workspace_bytes": (_S, [_I, _I, _I, _I]),
     "taco_wav_split": (_I, [_P, _P, _P, _I, _I, C.c_float, _I, _I, _I, _I, _P, _P, _P, _P, _S]),
     "taco_wav_breath_mute": (_I, [_P, _P, _P, _I, _I, _P, _P, _I, C.c_float, _P, _P, _P]),
+    "taco_resample_create": (_I, [_I, _I, _P, _I, _I, _I, C.POINTER(_P)]),
+    "taco_resample_destroy": (None, [_P]),
+    "taco_resample_out_len": (_I, [_P, _I]),
+    "taco_resample_computed_len": (_I, [_P, _I]),
+    "taco_resample_phases": (_I, [_P]),
+    "taco_resample_taps": (_I, [_P]),
+    "taco_resample_left_taps": (_I, [_P]),
+    "taco_resample_tile": (_I, [_P]),
+    "taco_resample_bank": (_I, [_P, _P]),
+    "taco_wav_resample": (_I, [_P, _P, _P, _I, _I, _P, _I, _I, _P, _I, _P]),
     "taco_gl_set_mel_basis": (_I, [_P, _P, _I]),
     "taco_spec_num_mels": (_I, [_P]),
     "taco_spec_num_frames": (_I, [C.POINTER(TacoAudioHParams), _I]),

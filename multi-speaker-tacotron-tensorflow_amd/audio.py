@@ -3,7 +3,10 @@
 every utterance -- and waveform -> the linear and mel targets training consumes: `spectrogram` / `melspectrogram` of
 audio/__init__.py:48-51,64-67, which datasets/generate_data.py:151-158 runs on the CPU for every corpus file (class Spectrogram).
 All arithmetic is in libtaco_hip (taco_gl_*, taco_spec_*); PyTorch holds the buffers.  The one host computation is the mel filter
-bank (mel_basis), built once in float64 and uploaded."""
+bank (mel_basis), built once in float64 and uploaded.
+Recordings reach the model's sample rate through class Resampler (taco_resample_*, taco_wav_resample): librosa.core.load's and
+resample_audio's band-limited sinc interpolation (audio/__init__.py:12-20,30-32), whose one host computation is the Kaiser-windowed
+half filter (kaiser_window)."""
 import ctypes as C
 
 import numpy as np
@@ -324,3 +327,118 @@ class Spectrogram(GriffinLim):
         lin, m, nf = self.targets(x, n)
         lin, m, nf = lin.cpu().numpy(), m.cpu().numpy(), nf.cpu().numpy()
         return [{"linear": lin[b, :nf[b]].copy(), "mel": m[b, :nf[b]].copy()} for b in range(len(wavs))]
+
+
+def kaiser_window(num_zeros=64, precision=9, beta=14.769656459379492, rolloff=0.9475937167399596):
+    """The half window of resampy's sinc_window(num_zeros, precision, kaiser(beta), rolloff) in float64 (the defaults are
+    'kaiser_best'): with num_table = 2**precision and n = num_table * num_zeros, half[i] = rolloff * sinc(rolloff * i / num_table) *
+    kaiser(2n + 1, beta)[n + i], i = 0..n.  UNPINNED on resampy: restated from its documented algorithm, not run against it."""
+    num_table = 2 ** int(precision)
+    n = num_table * int(num_zeros)
+    return rolloff * np.sinc(rolloff * (np.arange(n + 1) / num_table)) * np.kaiser(2 * n + 1, beta)[n:]
+
+
+# resampy's named filters as arguments of kaiser_window.  kaiser_best is the reference's (librosa 0.5.1's default res_type; the
+# constants are those of the issue that introduced this path).  kaiser_fast's constants are RECALLED from resampy's documentation and
+# were not verified against it here.
+FILTERS = {"kaiser_best": dict(num_zeros=64, precision=9, beta=14.769656459379492, rolloff=0.9475937167399596),
+           "kaiser_fast": dict(num_zeros=16, precision=9, beta=8.555504641634386, rolloff=0.85)}
+
+
+class Resampler(object):
+    """Recordings at orig_sr -> target_sr on the GPU, as librosa.core.resample(y, orig_sr, target_sr) with resampy's sinc interpolation
+    does, but with every output at its exact position t * orig_sr / target_sr (include/taco_abi.h says where resampy 0.2.0's
+    accumulated position differs).  filter: a name in FILTERS, a dict of kaiser_window's arguments, or a float64 half window (then
+    num_table = entries per zero crossing is required).  UNPINNED on resampy and librosa; held by tests/resample_reference.py.
+    The handle is made without a device; the filter bank is uploaded by the first `resample`."""
+
+    def __init__(self, orig_sr, target_sr, filter="kaiser_best", num_table=None, device="cuda:0"):
+        self.orig_sr, self.target_sr = int(orig_sr), int(target_sr)
+        self.device = torch.device(device)
+        if self.device.type != "cuda":
+            raise _lib.TacoError(_lib.TACO_ERR_ARG, "Resampler runs on a GPU (got %s); there is no CPU fallback" % device)
+        if isinstance(filter, str):
+            if filter not in FILTERS:
+                raise _lib.TacoError(_lib.TACO_ERR_ARG, "filter must be one of %s, a dict or a half window, got %r" % (sorted(FILTERS), filter))
+            filter = FILTERS[filter]
+        if isinstance(filter, dict):
+            half, table = kaiser_window(**filter), 2 ** int(filter.get("precision", 9))
+        else:
+            if num_table is None:
+                raise _lib.TacoError(_lib.TACO_ERR_ARG, "a half window needs num_table, its entries per zero crossing")
+            half, table = filter, num_table
+        half = np.ascontiguousarray(np.asarray(half, np.float64).reshape(-1))
+        self.num_table = int(table if num_table is None else num_table)
+        self._lib = _lib.load_library()
+        self._h = C.c_void_p()
+        idx = self.device.index if self.device.index is not None else torch.cuda.current_device()
+        _lib.check(self._lib.taco_resample_create(self.orig_sr, self.target_sr, half.ctypes.data_as(C.c_void_p), len(half), self.num_table, idx,
+                                                  C.byref(self._h)))
+
+    def out_len(self, n):
+        """int(ceil(n * ratio)): samples librosa.core.resample returns for n (fix_length)"""
+        return int(self._lib.taco_resample_out_len(self._h, int(n)))
+
+    def computed_len(self, n):
+        """int(n * ratio): samples resampy computes; out_len(n) - computed_len(n) in {0, 1} trailing zeros follow"""
+        return int(self._lib.taco_resample_computed_len(self._h, int(n)))
+
+    @property
+    def phases(self):
+        return int(self._lib.taco_resample_phases(self._h))
+
+    @property
+    def taps(self):
+        return int(self._lib.taco_resample_taps(self._h))
+
+    @property
+    def left_taps(self):
+        return int(self._lib.taco_resample_left_taps(self._h))
+
+    @property
+    def tile(self):
+        return int(self._lib.taco_resample_tile(self._h))
+
+    def bank(self):
+        """The fp32 filter bank [phases, taps] (NumPy): entry j of row r weighs x[n - (left_taps - 1) + j]."""
+        b = np.empty((self.phases, self.taps), np.float32)
+        _lib.check(self._lib.taco_resample_bank(self._h, b.ctypes.data_as(C.c_void_p)))
+        return b
+
+    def resample(self, wav, num_samples=None, channels=1):
+        """wav [B, L] (channels = 1) or [B, L, channels] interleaved, float32 or int16 (16-bit PCM, taken as s / 32768; any other dtype
+        is converted to float32); num_samples [B] (a device int32 tensor is used as it is; host data is uploaded; None: L) ->
+        (out [B, out_len(L)] float32, out_samples [B] int32), device tensors.  More than one channel is averaged (librosa.to_mono).
+        Row b holds its computed_len(n_b) outputs, exact zeros after, and out_samples[b] = out_len(n_b)."""
+        dev = self.device
+        x = wav if torch.is_tensor(wav) else torch.as_tensor(np.asarray(wav))
+        x = x.to(dev, torch.int16 if x.dtype == torch.int16 else torch.float32).contiguous()
+        channels = int(channels)
+        if x.dim() == 3 and channels == 1:
+            channels = int(x.shape[2])
+        if x.dim() not in (2, 3) or (x.dim() == 3 and x.shape[2] != channels) or (x.dim() == 2 and x.shape[1] % max(channels, 1)):
+            raise Exception("wav must be [B, L] or [B, L, channels = %d], got shape %s" % (channels, tuple(x.shape)))
+        B, L = int(x.shape[0]), int(x.shape[1]) // (channels if x.dim() == 2 else 1)
+        ns = None if num_samples is None else (num_samples if torch.is_tensor(num_samples) else torch.as_tensor(np.asarray(num_samples))).to(dev, torch.int32).contiguous()
+        if ns is not None and tuple(ns.shape) != (B,):
+            raise Exception("num_samples must be [B] = [%d], got %s" % (B, tuple(ns.shape)))
+        L_out = self.out_len(L)
+        out = torch.empty((B, L_out), dtype=torch.float32, device=dev)
+        on = torch.empty((B,), dtype=torch.int32, device=dev)
+        fmt = _lib.TACO_WAV_PCM16 if x.dtype == torch.int16 else _lib.TACO_WAV_F32
+        p = lambda t: C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)
+        with torch.cuda.device(dev):
+            _lib.check(self._lib.taco_wav_resample(self._h, C.c_void_p(torch.cuda.current_stream().cuda_stream), p(x), fmt, channels, p(ns), B, L,
+                                                   p(out), L_out, p(on)))
+        return out, on
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._lib.taco_resample_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass

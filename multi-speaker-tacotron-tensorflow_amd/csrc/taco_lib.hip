@@ -2272,6 +2272,7 @@ static int forward_enqueue(taco_model* m, hipStream_t st, const int32_t* ids, co
 // ------------------------------------------------------------------------------------------------
 #include "taco_train.h"
 #include "taco_audio.h"
+#include "taco_resample.h"
 #include "taco_feed.h"
 
 extern "C" {
@@ -3163,5 +3164,6 @@ int taco_adam_step_f32(void* hip_stream, float* d_params, const float* d_grads, 
 
 #include "taco_train_api.h"
 #include "taco_audio_api.h"
+#include "taco_resample_api.h"
 
 }  // extern "C"

@@ -27,6 +27,22 @@ class SilenceDevice(object):
         self.gl = griffin_lim or GriffinLim(hparams, device)
         self._own = griffin_lim is None
         self.chunk_rows = max(1, int(chunk_rows))
+        self.sample_rate = int(getattr(hparams, "sample_rate", 24000))
+        self._resamplers = {}
+
+    def resample(self, audio, orig_sr):
+        """A recording at orig_sr -- 1-D, or [n, channels] interleaved; int16 is 16-bit PCM -- -> [1, n'] float32 on the device at
+        hparams.sample_rate (audio.Resampler: librosa.core.load's resampling; channels are averaged)."""
+        import torch
+        from .audio import Resampler
+        a = np.asarray(audio)
+        a = np.ascontiguousarray(a if a.dtype == np.int16 else a.astype(np.float32))
+        if a.ndim > 2:
+            raise Exception("a recording is [n] or [n, channels], got shape %s" % (a.shape,))
+        rs = self._resamplers.get(int(orig_sr))
+        if rs is None:
+            rs = self._resamplers[int(orig_sr)] = Resampler(orig_sr, self.sample_rate, device=self.gl.device)
+        return rs.resample(torch.as_tensor(a.reshape((1,) + a.shape)), channels=a.shape[1] if a.ndim == 2 else 1)[0]
 
     def upload(self, audio):
         import torch
@@ -77,13 +93,18 @@ class SilenceDevice(object):
         return new
 
     def close(self):
+        for rs in self._resamplers.values():
+            rs.close()
+        self._resamplers = {}
         if self._own:
             self.gl.close()
 
 
 def split_on_silence(audio, hparams, top_db=40, frame_length=1024, hop_length=256, skip_idx=0, min_segment_length=3, max_segment_length=8,
-                     pre_silence_length=0, post_silence_length=0, device="cuda:0", chunk_rows=32):
-    """audio: one recording, 1-D float samples at hparams.sample_rate.  -> (no_breath, segments): the recording after remove_breath on
+                     pre_silence_length=0, post_silence_length=0, device="cuda:0", chunk_rows=32, orig_sr=None):
+    """audio: one recording, 1-D float samples at hparams.sample_rate -- or, with orig_sr given, at orig_sr (1-D or [n, channels]; int16
+    is 16-bit PCM): it is then resampled to hparams.sample_rate on the device before anything else (SilenceDevice.resample), and
+    every sample index below counts at hparams.sample_rate.  -> (no_breath, segments): the recording after remove_breath on
     every interval [skip_idx:] of the first split and zeros elsewhere (what the reference saves as NAME.no_breath), float32; and a
     list of (idx, start, end, segment) for the intervals [skip_idx:] of the second split whose duration (end - start) / sample_rate
     lies strictly between min_segment_length and max_segment_length -- idx counts as the reference's `enumerate(edges[skip_idx:])`
@@ -92,7 +113,7 @@ def split_on_silence(audio, hparams, top_db=40, frame_length=1024, hop_length=25
     sr = int(getattr(hparams, "sample_rate", 24000))
     dev = device if hasattr(device, "remove_breath") else SilenceDevice(hparams, device, chunk_rows)
     try:
-        x = dev.upload(audio)
+        x = dev.upload(audio) if orig_sr is None else dev.resample(audio, orig_sr)
         edges = dev.split(x, top_db, frame_length, hop_length)
         y = dev.remove_breath(x, edges[skip_idx:])
         edges = dev.split(y, top_db, frame_length, hop_length)

@@ -16,7 +16,11 @@ restatement tests/trim_reference.py on the CPU for the same batch, whose indices
 utterances of 2-9 s, each loud phrases with quieter breaths between short pauses, separated by 0.5-1.5 s of noise floor: the split alone
 (GriffinLim.split at 1024 / 256 / 40 dB, one row), the whole taco_amd.split_on_silence (two splits, the intervals gathered, remove_breath at
 128 / 32, scattered back, intervals downloaded), and the float64 restatement tests/split_reference.py on the CPU, whose segments the device
-must reproduce.  Its own JSON line, `--split` only."""
+must reproduce.  Its own JSON line, `--split` only.
+`--resample` measures resampling to the model's rate (audio.Resampler, kaiser_best) on three minutes at 44100 -> 24000 Hz: mono float32
+and stereo 16-bit PCM, the call alone (input and outputs on the device), as output samples per second and as the bytes of the stream it
+moves (input once, output once) over its time; beside it the vectorised float64 restatement tests/resample_reference.py on the CPU for
+the same mono input, whose values bound the device's error; and three minutes at 16000 -> 24000 Hz, mono float32, the up-sampling shape.  Its own JSON line, `--resample` only."""
 import json, os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "oracle"))
@@ -183,6 +187,58 @@ def split():
     return out
 
 
+def resample():
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import resample_reference as R
+    so, sn, seconds = 44100, 24000, 180
+    n = so * seconds
+    rs_ = np.random.RandomState(9)
+    x = R.chirp_rows(n, [n], 9)[0].astype(np.float32)
+    q2 = np.stack([np.round(x * 8000), np.round(4000 * rs_.randn(n))], axis=1).astype(np.int16).reshape(1, n, 2)
+    rs = taco_amd.Resampler(so, sn)
+    mono, pcm = torch.from_numpy(x.reshape(1, n)).cuda(), torch.from_numpy(q2).cuda()
+    up = taco_amd.Resampler(16000, sn)                             # the up-sampling shape of the same kernel: 3 phases x 127 taps
+    mono16 = mono[:, :16000 * seconds].contiguous()
+    arms = {"mono_f32": lambda: rs.resample(mono), "stereo_pcm16": lambda: rs.resample(pcm, channels=2), "up_16000_mono_f32": lambda: up.resample(mono16)}
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    for f in arms.values():
+        for _ in range(3):
+            f()
+    torch.cuda.synchronize()
+    ms = {k: [] for k in arms}
+    for _ in range(5):
+        for k, f in arms.items():
+            e0.record()
+            for _ in range(20):
+                f()
+            e1.record(); torch.cuda.synchronize()
+            ms[k].append(e0.elapsed_time(e1) / 20)
+    med = {k: float(np.median(v)) for k, v in ms.items()}
+    y, yn = rs.resample(mono)
+    again = rs.resample(mono)
+    n_out = int(yn[0])
+    half = taco_amd.audio.kaiser_window()
+    t0 = time.perf_counter(); ref, A = R.resample_bank(x.astype(np.float64), so, sn, half, 512); cpu_s = time.perf_counter() - t0
+    ratio = np.abs(y[0, :len(ref)].cpu().numpy().astype(np.float64) - ref) / ((rs.taps + 4) * 2.0 ** -24 * A + 4 * 2.0 ** -149)
+    nbytes = {"mono_f32": n * 4 + n_out * 4, "stereo_pcm16": n * 4 + n_out * 4}
+    out = {"metric": "resampling 44100 -> 24000 Hz (kaiser_best, %d phases x %d taps) of three minutes of audio" % (rs.phases, rs.taps),
+           "value": n_out / (med["mono_f32"] / 1e3), "unit": "output samples per second (mono float32)",
+           "recording": "%d s at %d Hz, %d samples -> %d" % (seconds, so, n, n_out), "windows": "5 windows of 20 calls per arm, alternating",
+           "mono_f32_ms": ms["mono_f32"], "stereo_pcm16_ms": ms["stereo_pcm16"], "mono_f32_median_ms": med["mono_f32"], "stereo_pcm16_median_ms": med["stereo_pcm16"],
+           "stereo_pcm16_output_samples_per_s": n_out / (med["stereo_pcm16"] / 1e3), "x_realtime_mono": seconds / (med["mono_f32"] / 1e3),
+           "up_16000_24000_mono_f32_ms": ms["up_16000_mono_f32"], "up_16000_24000_median_ms": med["up_16000_mono_f32"],
+           "up_16000_24000_output_samples_per_s": n_out / (med["up_16000_mono_f32"] / 1e3), "up_16000_24000_filter": "%d phases x %d taps" % (up.phases, up.taps),
+           "stream_bytes": nbytes, "stream_GBps": {k: nbytes[k] / (med[k] / 1e3) / 1e9 for k in nbytes},
+           "GFLOPs_mono": 2.0 * n_out * rs.taps / (med["mono_f32"] / 1e3) / 1e9,
+           "cpu_restatement_float64_s": cpu_s, "cpu_restatement_output_samples_per_s": n_out / cpu_s,
+           "largest_error_over_the_derived_bound": float(ratio.max()), "identical_bits_on_two_calls": bool(torch.equal(again[0], y) and torch.equal(again[1], yn))}
+    rs.close(); up.close()
+    return out
+
+
+if "--resample" in sys.argv:
+    print(json.dumps(resample()))
+    sys.exit(0)
 if "--split" in sys.argv:
     print(json.dumps(split()))
     sys.exit(0)

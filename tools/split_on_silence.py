@@ -1,12 +1,14 @@
 #!/usr/bin/env python
 """Long recordings -> utterance-sized segments: what the reference's audio/silence.py:33-76 (split_on_silence_with_librosa) writes per
 recording -- NAME.no_breath and NAME.0000, NAME.0001, ... -- with both splits and remove_breath computed on the GPU
-(taco_amd.split_on_silence) instead of librosa on the CPU.  Recordings are `.npy` files of float samples at hparams.sample_rate;
-decoding wav / mp3 files stays outside, and so does the pydub method.  The segments are waveforms
+(taco_amd.split_on_silence) instead of librosa on the CPU.  Recordings are `.npy` files of float samples at hparams.sample_rate -- or,
+with --orig-sr N, at N Hz (float, or int16 PCM; [n] or [n, channels]): each is then resampled to hparams.sample_rate on the device
+first (taco_amd.Resampler, what librosa.core.load does on the CPU); decoding wav / mp3 files stays outside, and so does the pydub method.  The segments are waveforms
 tools/generate_data.py takes as they are.
 
     python tools/split_on_silence.py OUT_DIR a.npy b.npy ... [--top-db 40] [--frame-length 1024] [--hop-length 256] [--skip-idx 0]
                                      [--min-segment-length 3] [--max-segment-length 8] [--pre-silence-length 0] [--post-silence-length 0]
+                                     [--orig-sr N]
 
 Writes OUT_DIR/NAME.no_breath.npy and OUT_DIR/NAME.%04d.npy (float32; the number is the segment's position among the intervals of the
 second split, as in the reference: segments outside the duration bounds leave gaps in the numbering) and prints the paths."""
@@ -58,9 +60,12 @@ def main():
     ap.add_argument("--max-segment-length", type=float, default=8)
     ap.add_argument("--pre-silence-length", type=float, default=0)
     ap.add_argument("--post-silence-length", type=float, default=0)
+    ap.add_argument("--orig-sr", type=int, default=None, help="sample rate of the inputs; they are resampled to hparams.sample_rate on the device")
     a = ap.parse_args()
     kw = dict(top_db=a.top_db, frame_length=a.frame_length, hop_length=a.hop_length, skip_idx=a.skip_idx, min_segment_length=a.min_segment_length,
               max_segment_length=a.max_segment_length, pre_silence_length=a.pre_silence_length, post_silence_length=a.post_silence_length)
+    if a.orig_sr is not None:
+        kw["orig_sr"] = a.orig_sr
     for paths in split_files(a.recordings, a.out_dir, **kw):
         for p in paths:
             print(p)
