@@ -199,6 +199,47 @@ int taco_gl_inv_spectrogram_rows(taco_gl* g, void* hip_stream, const float* d_sp
  * samples (NULL: L), pcm = (int16) trunc(x * (32767 / max(0.01, peak))), zeros past them.  d_pcm [B, L].  One launch. */
 int taco_wav_to_pcm16(void* hip_stream, const float* d_wav, const int32_t* d_num_samples, int B, int L, int16_t* d_pcm);
 
+/* ---- the reference's two other vocoders ---- */
+/* inv_spectrogram_tensorflow (audio/__init__.py:59-61,87-96,109-116,152-153,167-168), the Griffin-Lim the reference builds into its
+ * inference graph as Synthesizer.wav_output (synthesizer.py:53-54).  UNPINNED on TensorFlow: the reference runs tf.contrib.signal.stft /
+ * inverse_stft of TF 1.x, this project does not depend on TensorFlow, and what follows restates their documented algorithm; it could
+ * not be checked against TensorFlow's source or output.  With N = n_fft, W = win_length, h = hop and w[n] = 0.5 - 0.5 cos(2 pi n / W):
+ *   stft(y), pad_end=False   frame t = y[t*h .. t*h + W) for t = 0 .. (len - W) / h, times w, zero-padded AT THE END to N, rfft:
+ *                            X_k = sum_n y[t*h + n] w[n] e^{-2 pi i k n / N} -- the window is left-aligned, where librosa centres it
+ *   inverse_stft(X)          irfft(X, N)[:W] * w, overlap-added at stride h: no window sum-square division (tf's default
+ *                            window_fn is used as the reference passes none other), no reflect padding; h*(T-1) + W samples
+ *   inv_spectrogram_tensorflow(spec)   S = (10^((clip(spec,0,1) * -min_db + min_db + ref_db) / 20))^power; y = inverse_stft(S + 0i)
+ *                            (zero phase, not np.random.rand); griffin_lim_iters times est = stft(y), y = inverse_stft(S * est /
+ *                            max(1e-8, |est|)) -- a bin whose estimate is 0 gives 0; no inverse pre-emphasis.
+ * Deterministic: the same spectrogram gives the same samples, bit for bit.  A handle of taco_gl_create_tf carries this flavour's two
+ * DFT packs and serves taco_gl_inv_spectrogram_tf (and taco_gl_set_inv_mel_basis / taco_gl_mel_to_linear, taco_wav_*) only: the
+ * librosa-flavour entry points (taco_gl_inv_spectrogram*, taco_gl_inv_melspectrogram_rows, taco_spec_targets) return TACO_ERR_STATE
+ * on it, and taco_gl_inv_spectrogram_tf returns TACO_ERR_STATE on a handle of taco_gl_create.
+ * d_spec [B, T, num_freq], T >= 1.  d_frames [B] device memory (NULL: every row keeps T), clamped on the device to [1, T] and never
+ * read on the host; row b of d_wav [B, taco_gl_tf_num_samples(T)] is the vocoding of spec[b, :f_b] -- frames t < f_b touch only
+ * samples those frames produce -- in its first h*(f_b-1) + W samples and exact zeros after; d_num_samples [B] (nullable) receives
+ * that count.  iters < 0: griffin_lim_iters.  No read-back, synchronisation or allocation: capturable. */
+int taco_gl_create_tf(const taco_audio_hparams* hp, int device, taco_gl** out);
+int taco_gl_tf_num_samples(const taco_gl* g, int T);         /* hop_length * (T - 1) + win_length */
+size_t taco_gl_tf_workspace_bytes(const taco_gl* g, int B, int T);
+int taco_gl_inv_spectrogram_tf(taco_gl* g, void* hip_stream, const float* d_spec, const int32_t* d_frames, int B, int T, int iters,
+                               float* d_wav, int32_t* d_num_samples, void* d_workspace, size_t workspace_bytes);
+/* inv_melspectrogram (audio/__init__.py:70-72,136-140): S = max(1e-10, inv_mel_basis . 10^((clip(mel,0,1) * -min_db + min_db) / 20))
+ * (no ref_level_db: melspectrogram never subtracts it), then ^power, Griffin-Lim and inverse pre-emphasis as inv_spectrogram.
+ * host_inv [num_freq, num_mels] is the pseudo-inverse of the filter bank, computed on the host (np.linalg.pinv in float64,
+ * audio.inv_mel_basis; fp32 here) -- UNPINNED on librosa as far as the filter bank is (taco_gl_set_mel_basis).  Works on a handle of
+ * either flavour.  The product is a fixed-order fp32 sum over the mels, m = 0 .. num_mels-1 with fmaf (k_gl_mel_magnitude), not the
+ * split-bf16 product: the pseudo-inverse has entries of both signs and the sum cancels.
+ * taco_gl_mel_to_linear: d_mel [B, T, num_mels] -> d_out [B, T, num_freq] = _mel_to_linear(_db_to_amp(_denormalize(mel))), before ^power.
+ * taco_gl_inv_melspectrogram_rows: taco_gl_inv_spectrogram_rows with those magnitudes^power in place of the linear ones; every other
+ * argument, the clamp of d_frames, the outputs and the workspace (taco_gl_rows_workspace_bytes) are that entry point's.
+ * Both return TACO_ERR_STATE until taco_gl_set_inv_mel_basis was called. */
+int taco_gl_set_inv_mel_basis(taco_gl* g, const float* host_inv, int num_mels);
+int taco_gl_mel_to_linear(taco_gl* g, void* hip_stream, const float* d_mel, int B, int T, float* d_out);
+int taco_gl_inv_melspectrogram_rows(taco_gl* g, void* hip_stream, const float* d_mel, const int32_t* d_frames, const float* d_init_uniform,
+                                    unsigned long long seed, int B, int T, int iters, float* d_wav, int32_t* d_num_samples,
+                                    void* d_workspace, size_t workspace_bytes);
+
 /* Silence trimming of a synthesised waveform: the `librosa.effects.trim(audio_out, frame_length=5120, hop_length=256, top_db=50)` of
  * synthesizer.py:266-269 (`audio_out = audio_out[:index[-1]]`), per row of d_wav [B, L].  UNPINNED on librosa: the reference pins
  * librosa==0.5.1, this project does not depend on librosa, and what follows restates the documented algorithm; it could not be

@@ -112,6 +112,11 @@ int taco_train_debug_bigru(taco_train* t, void* hip_stream, const float* d_xproj
  * dB / normalise arithmetic be held against the reference's own recorded outputs, and the kernel be timed alone. */
 int taco_debug_spec_epilogue(taco_gl* g, void* hip_stream, const float* d_est, int R, float* d_linear, float* d_mel);
 
+/* Test hook: a taco_gl handle of either flavour (tf_flavor != 0: taco_gl_create_tf's) whose packs are built on the host and never
+ * uploaded -- no device is touched.  It serves the argument and state checks of the taco_gl_* entry points, which come before their
+ * first device call, on a machine without a GPU; nothing may be launched on it.  Freed by taco_gl_destroy. */
+int taco_debug_gl_create_host(const taco_audio_hparams* hp, int tf_flavor, taco_gl** out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -136,6 +136,14 @@ PROTOTYPES = {
     "taco_gl_rows_workspace_bytes": (_S, [_P, _I, _I]),
     "taco_gl_inv_spectrogram_rows": (_I, [_P, _P, _P, _P, _P, C.c_ulonglong, _I, _I, _I, _P, _P, _P, _S]),
     "taco_wav_to_pcm16": (_I, [_P, _P, _P, _I, _I, _P]),
+    "taco_gl_create_tf": (_I, [C.POINTER(TacoAudioHParams), _I, C.POINTER(_P)]),
+    "taco_gl_tf_num_samples": (_I, [_P, _I]),
+    "taco_gl_tf_workspace_bytes": (_S, [_P, _I, _I]),
+    "taco_gl_inv_spectrogram_tf": (_I, [_P, _P, _P, _P, _I, _I, _I, _P, _P, _P, _S]),
+    "taco_gl_set_inv_mel_basis": (_I, [_P, _P, _I]),
+    "taco_gl_mel_to_linear": (_I, [_P, _P, _P, _I, _I, _P]),
+    "taco_gl_inv_melspectrogram_rows": (_I, [_P, _P, _P, _P, _P, C.c_ulonglong, _I, _I, _I, _P, _P, _P, _S]),
+    "taco_debug_gl_create_host": (_I, [C.POINTER(TacoAudioHParams), _I, C.POINTER(_P)]),
     "taco_wav_trim_workspace_bytes": (_S, [_I, _I, _I, _I]),
     "taco_wav_trim": (_I, [_P, _P, _P, _I, _I, C.c_float, _I, _I, _I, _P, _P, _P, _S]),
     "taco_wav_split_workspace_bytes": (_S, [_I, _I, _I, _I]),

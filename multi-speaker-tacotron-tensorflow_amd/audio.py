@@ -2,8 +2,11 @@
 ^power, Griffin-Lim with librosa-semantics STFT/ISTFT, inverse pre-emphasis), the step synthesizer.py:264 runs on the CPU for
 every utterance -- and waveform -> the linear and mel targets training consumes: `spectrogram` / `melspectrogram` of
 audio/__init__.py:48-51,64-67, which datasets/generate_data.py:151-158 runs on the CPU for every corpus file (class Spectrogram).
-All arithmetic is in libtaco_hip (taco_gl_*, taco_spec_*); PyTorch holds the buffers.  The one host computation is the mel filter
-bank (mel_basis), built once in float64 and uploaded.
+The reference's two other vocoders are here as well: `inv_spectrogram_tensorflow` (:59-61,87-96, the deterministic Griffin-Lim of its
+inference graph, GriffinLim(flavor="tensorflow")) and `inv_melspectrogram` (:70-72,136-140, GriffinLim.inv_melspectrogram).  With them
+every arithmetic function of the reference's audio/__init__.py runs on the device.
+All arithmetic is in libtaco_hip (taco_gl_*, taco_spec_*); PyTorch holds the buffers.  The host computations are the mel filter
+bank (mel_basis) and its pseudo-inverse (inv_mel_basis), built once in float64 and uploaded.
 Recordings reach the model's sample rate through class Resampler (taco_resample_*, taco_wav_resample): librosa.core.load's and
 resample_audio's band-limited sinc interpolation (audio/__init__.py:12-20,30-32), whose one host computation is the Kaiser-windowed
 half filter (kaiser_window)."""
@@ -48,6 +51,13 @@ def mel_basis(hparams):
     return weights * (2.0 / (mel_f[2:] - mel_f[:-2]))[:, None]
 
 
+def inv_mel_basis(hparams):
+    """The reference's _inv_mel_basis (audio/__init__.py:136-140): np.linalg.pinv(_build_mel_basis()), [num_freq, num_mels], float64
+    (cast to float32 at upload).  The filter bank has full row rank, so mel_basis . inv_mel_basis = I.  As UNPINNED on librosa as
+    mel_basis is."""
+    return np.linalg.pinv(mel_basis(hparams))
+
+
 def c_audio_hparams(hparams):
     g = lambda k, d: getattr(hparams, k, d)
     return _lib.TacoAudioHParams(
@@ -64,16 +74,26 @@ def num_frames(hparams, n_samples):
 
 
 class GriffinLim(object):
-    def __init__(self, hparams, device="cuda:0"):
+    """flavor "librosa" (default): the handle of inv_spectrogram / inv_melspectrogram and of everything Spectrogram adds.  "tensorflow":
+    the handle of inv_spectrogram_tensorflow (tf.contrib.signal's uncentred STFT; the librosa-flavour methods raise TacoError on it).
+    pcm16, trim, split, remove_breath, set_inv_mel_basis and mel_to_linear work on either."""
+
+    def __init__(self, hparams, device="cuda:0", flavor="librosa"):
         self.hp = c_audio_hparams(hparams)
+        self.hparams = hparams
         self.device = torch.device(device)
         if self.device.type != "cuda":
             raise _lib.TacoError(_lib.TACO_ERR_ARG, "GriffinLim runs on a GPU (got %s); there is no CPU fallback" % device)
+        if flavor not in ("librosa", "tensorflow"):
+            raise _lib.TacoError(_lib.TACO_ERR_ARG, "flavor must be 'librosa' or 'tensorflow', got %r" % (flavor,))
+        self.flavor = flavor
         self._lib = _lib.load_library()
         self._h = C.c_void_p()
         idx = self.device.index if self.device.index is not None else torch.cuda.current_device()
-        _lib.check(self._lib.taco_gl_create(C.byref(self.hp), idx, C.byref(self._h)))
+        create = self._lib.taco_gl_create_tf if flavor == "tensorflow" else self._lib.taco_gl_create
+        _lib.check(create(C.byref(self.hp), idx, C.byref(self._h)))
         self._ws = None
+        self._inv_mels = 0
 
     def num_samples(self, T):
         return int(self._lib.taco_gl_num_samples(self._h, T))
@@ -125,6 +145,91 @@ class GriffinLim(object):
             _lib.check(self._lib.taco_gl_inv_spectrogram_rows(self._h, C.c_void_p(torch.cuda.current_stream().cuda_stream), p(x), p(fr), p(u),
                                                               C.c_ulonglong(int(seed)), B, T, -1 if iters is None else int(iters), p(wav),
                                                               p(ns), p(self._ws), self._ws.numel()))
+        return wav, ns
+
+    def _batch(self, x, width, what):
+        """x [B, T, width] float32 contiguous on the device"""
+        x = (x if torch.is_tensor(x) else torch.as_tensor(np.asarray(x))).to(self.device, torch.float32).contiguous()
+        if x.dim() != 3 or x.shape[2] != width:
+            raise Exception("%s must be [B, T, %d], got shape %s" % (what, width, tuple(x.shape)))
+        return x
+
+    def _frames(self, frames, B):
+        fr = None if frames is None else (frames if torch.is_tensor(frames) else torch.as_tensor(np.asarray(frames))).to(self.device, torch.int32).contiguous()
+        if fr is not None and tuple(fr.shape) != (B,):
+            raise Exception("frames must be [B] = [%d], got %s" % (B, tuple(fr.shape)))
+        return fr
+
+    def tf_num_samples(self, T):
+        return int(self._lib.taco_gl_tf_num_samples(self._h, T))
+
+    def inv_spectrogram_tensorflow(self, linear, frames=None, iters=None):
+        """inv_spectrogram_tensorflow of audio/__init__.py:59-61,87-96 (the reference's Synthesizer.wav_output, synthesizer.py:53-54) on
+        a flavor="tensorflow" handle: linear [B, T, num_freq], frames [B] (a device int32 tensor is used as it is; None: all T; clamped
+        to [1, T]) -> (wav [B, hop*(T-1) + win], num_samples [B] int32), device tensors.  Zero initial phase, est / max(1e-8, |est|), no
+        inverse pre-emphasis: the same spectrogram always gives the same samples.  Row b is the vocoding of linear[b, :frames[b]] in
+        its first hop*(frames[b]-1) + win samples, zeros after.  UNPINNED on TensorFlow: tf.contrib.signal.stft / inverse_stft restated
+        (include/taco_abi.h), checked against tests/vocoder_reference.py, not against TensorFlow."""
+        dev = self.device
+        x = self._batch(linear, self.hp.num_freq, "linear")
+        B, T, _ = x.shape
+        fr = self._frames(frames, B)
+        nb = int(self._lib.taco_gl_tf_workspace_bytes(self._h, B, T))
+        if self._ws is None or self._ws.numel() < nb:
+            self._ws = torch.empty(nb, dtype=torch.uint8, device=dev)
+        wav = torch.empty((B, self.tf_num_samples(T)), dtype=torch.float32, device=dev)
+        ns = torch.empty((B,), dtype=torch.int32, device=dev)
+        p = lambda t: C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)
+        with torch.cuda.device(dev):
+            _lib.check(self._lib.taco_gl_inv_spectrogram_tf(self._h, C.c_void_p(torch.cuda.current_stream().cuda_stream), p(x), p(fr), B, T,
+                                                            -1 if iters is None else int(iters), p(wav), p(ns), p(self._ws), self._ws.numel()))
+        return wav, ns
+
+    def set_inv_mel_basis(self, inv=None):
+        """Uploads the pseudo-inverse of the mel filter bank, [num_freq, num_mels]; None: inv_mel_basis(hparams)."""
+        b = np.ascontiguousarray(np.asarray(inv_mel_basis(self.hparams) if inv is None else inv), dtype=np.float32)
+        if b.ndim != 2 or b.shape[0] != self.hp.num_freq:
+            raise Exception("inv must be [num_freq = %d, num_mels], got %s" % (self.hp.num_freq, b.shape))
+        _lib.check(self._lib.taco_gl_set_inv_mel_basis(self._h, b.ctypes.data_as(C.c_void_p), b.shape[1]))
+        self._inv_mels = int(b.shape[1])
+
+    def _mel_batch(self, mel):
+        if not self._inv_mels:
+            raise _lib.TacoError(_lib.TACO_ERR_STATE, "the mel vocoder needs the inverse basis: call set_inv_mel_basis first")
+        return self._batch(mel, self._inv_mels, "mel")
+
+    def mel_to_linear(self, mel):
+        """_mel_to_linear(_db_to_amp(_denormalize(mel))) of audio/__init__.py:71,136-140: mel [B, T, num_mels] (normalised, as the model's
+        mel_outputs) -> linear magnitudes [B, T, num_freq] (device tensor), floored at 1e-10, before ^power."""
+        dev = self.device
+        x = self._mel_batch(mel)
+        B, T, _ = x.shape
+        out = torch.empty((B, T, self.hp.num_freq), dtype=torch.float32, device=dev)
+        with torch.cuda.device(dev):
+            _lib.check(self._lib.taco_gl_mel_to_linear(self._h, C.c_void_p(torch.cuda.current_stream().cuda_stream), C.c_void_p(x.data_ptr()), B, T,
+                                                       C.c_void_p(out.data_ptr())))
+        return out
+
+    def inv_melspectrogram(self, mel, frames=None, init_uniform=None, seed=0, iters=None):
+        """inv_melspectrogram of audio/__init__.py:70-72 per utterance length: mel [B, T, num_mels] -> (wav [B, hop*(T-1)], num_samples [B]
+        int32), device tensors; frames, init_uniform, seed and iters as inv_spectrogram_rows."""
+        dev = self.device
+        x = self._mel_batch(mel)
+        B, T, _ = x.shape
+        u = None if init_uniform is None else self._batch(init_uniform, self.hp.num_freq, "init_uniform")
+        if u is not None and tuple(u.shape[:2]) != (B, T):
+            raise Exception("init_uniform must be [B, T, num_freq] = [%d, %d, %d], got %s" % (B, T, self.hp.num_freq, tuple(u.shape)))
+        fr = self._frames(frames, B)
+        nb = int(self._lib.taco_gl_rows_workspace_bytes(self._h, B, T))
+        if self._ws is None or self._ws.numel() < nb:
+            self._ws = torch.empty(nb, dtype=torch.uint8, device=dev)
+        wav = torch.empty((B, self.num_samples(T)), dtype=torch.float32, device=dev)
+        ns = torch.empty((B,), dtype=torch.int32, device=dev)
+        p = lambda t: C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)
+        with torch.cuda.device(dev):
+            _lib.check(self._lib.taco_gl_inv_melspectrogram_rows(self._h, C.c_void_p(torch.cuda.current_stream().cuda_stream), p(x), p(fr), p(u),
+                                                                 C.c_ulonglong(int(seed)), B, T, -1 if iters is None else int(iters), p(wav),
+                                                                 p(ns), p(self._ws), self._ws.numel()))
         return wav, ns
 
     def pcm16(self, wav, num_samples=None):

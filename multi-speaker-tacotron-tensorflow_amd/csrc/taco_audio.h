@@ -7,6 +7,7 @@
 // k_spec_prepare, the forward product, k_spec_targets.
 #pragma once
 
+enum GlFlavor { GL_LIBROSA = 0, GL_TF = 1 };
 struct taco_gl {
   taco_audio_hparams hp;
   int n_fft = 0, hop = 0, win = 0, lpad = 0, F = 0;
@@ -17,6 +18,10 @@ struct taco_gl {
   int num_mels = 0;
   int* mel_band = nullptr;       // [3, num_mels]: first bin, one past the last bin, offset of the filter's weights in mel_w
   float* mel_w = nullptr;        // the weights of every filter's [lo, hi), packed one filter after the other
+  // the two other vocoders of audio/__init__.py
+  int flavor = GL_LIBROSA;       // GL_TF (taco_gl_create_tf): tf.contrib.signal's uncentred STFT, lpad = 0, w2 unused
+  int inv_mels = 0;              // inv_mel_basis: filters of the pseudo-inverse in use (taco_gl_set_inv_mel_basis; 0 = not set)
+  float* inv_mel = nullptr;      // [inv_mels, F] mel-major: consecutive lanes read consecutive bins
 };
 
 // ---- kernels ----
@@ -149,6 +154,95 @@ __global__ __launch_bounds__(1024) void k_wav_to_pcm16(const float* wav, const i
   for (int i = tid; i < L; i += 1024) out[i] = i < n ? (short)(int)fminf(fmaxf(truncf(x[i] * scale), -32767.f), 32767.f) : (short)0;
 }
 
+// ---- inv_spectrogram_tensorflow (audio/__init__.py:59-61,87-96,109-116): tf.contrib.signal.stft / inverse_stft restated; UNPINNED on TensorFlow ----
+// X = S * est / max(1e-8, |est|) (audio/__init__.py:94): a bin whose estimate is zero gives 0, not S as k_gl_project does
+__global__ void k_gl_project_tf(const float* est, const float* S, float* X, size_t rows, int F) {
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= rows * F) return;
+  const size_t row = i / F; const int f = (int)(i % F);
+  const float re = est[row * 2 * F + f], im = est[row * 2 * F + F + f], s = S[i];
+  const float d = fmaxf(1e-8f, sqrtf(re * re + im * im));
+  // (rows past an utterance's frames have S = 0 and are written as exact zeros whatever their estimate is)
+  X[row * 2 * F + f] = s != 0.f ? s * (re / d) : 0.f;
+  X[row * 2 * F + F + f] = s != 0.f ? s * (im / d) : 0.f;
+}
+// inverse_stft's overlap-add: y[s] = sum over the frames t that cover s of Y[t, s - t*hop], Y [B, Tr, win] the windowed irfft frames.  No
+// window sum-square and no reflect padding; the frames are visited in the order of k_gl_overlap_add.  Utterance b writes its own
+// hop*(frames-1) + win samples from the START of its slot of ypad, where the next forward product reads frame t at t*hop (ldx = hop);
+// the rest of the slot keeps the zeros it was filled with.  grid (blocks of a row, B).
+__global__ void k_gl_overlap_add_tf(const float* Y, float* ypad, const int* frames, int T, int Tr, int win, int hop, size_t slot) {
+  const int b = blockIdx.y, s = blockIdx.x * blockDim.x + threadIdx.x;
+  const int fb = gl_frames(frames, b, T, 1);
+  if (s >= hop * (fb - 1) + win) return;
+  float acc = 0.f;
+  for (int t = min(fb - 1, s / hop); t >= 0; --t) {
+    const int off = s - t * hop;
+    if (off >= win) break;
+    acc += Y[((size_t)b * Tr + t) * win + off];
+  }
+  ypad[(size_t)b * slot + s] = acc;
+}
+// The utterance's own samples out of its slot, exact zeros after in its row of L; num_samples (nullable) receives the count
+__global__ void k_gl_output_tf(const float* ypad, float* wav, const int* frames, int T, int win, int hop, int* num_samples, int L, size_t slot) {
+  const int b = blockIdx.y, s = blockIdx.x * blockDim.x + threadIdx.x;
+  if (s >= L) return;
+  const int Lb = hop * (gl_frames(frames, b, T, 1) - 1) + win;
+  if (num_samples && s == 0) num_samples[b] = Lb;
+  wav[(size_t)b * L + s] = s < Lb ? ypad[(size_t)b * slot + s] : 0.f;
+}
+
+// ---- inv_melspectrogram (audio/__init__.py:70-72,136-140): mel -> linear magnitudes through the pseudo-inverse of the filter bank ----
+#define MELMAG_ROWS 8          // frame rows per workgroup of k_gl_mel_magnitude: a weight of the inverse basis is fetched once for eight rows
+// out[b, t, f] = max(1e-10, sum_m inv[m, f] * amp[b, t, m]) (then ^power with apply_pow), amp = 10^((clip(mel,0,1) * -min_db + min_db) / 20):
+// _mel_to_linear(_db_to_amp(_denormalize(mel))) -- no ref_level_db, melspectrogram never subtracts it.  A workgroup stages the
+// amplitudes of its MELMAG_ROWS rows in LDS ([m][row], so a thread reads the eight of one m as two 16-byte words); the exponent and
+// the power of ten are formed in double there (num_mels values per row: nothing beside the sum), so an amplitude carries one
+// rounding.  Each thread owns bins f = tid, tid + 256, ... and sums m = 0 .. M-1 in that order with fmaf in fp32: the pseudo-inverse
+// has entries of both signs and the sum cancels heavily, so it does NOT go through the split-bf16 product; in this fixed order it
+// has the dot-product bound tests/test_gpu_vocoder.py holds it to.  Rows t >= the utterance's frames (and the slot's tail rows
+// t >= T) are zero.  out has Tr rows per utterance (the S buffer of the Griffin-Lim workspace; Tr = T for taco_gl_mel_to_linear).
+// grid (blocks of MELMAG_ROWS rows, B), 256 threads, MELMAG_ROWS * M floats of LDS.
+__global__ __launch_bounds__(256) void k_gl_mel_magnitude(const float* mel, const float* inv, float* out, const int* frames, int fmin, int T,
+                                                          int Tr, int F, int M, float min_db, float power, int apply_pow) {
+  extern __shared__ __attribute__((aligned(16))) float melmag_amp[];      // [M, MELMAG_ROWS]
+  const int b = blockIdx.y, t0 = blockIdx.x * MELMAG_ROWS, tid = threadIdx.x;
+  const int fb = gl_frames(frames, b, T, fmin);
+  for (int i = tid; i < MELMAG_ROWS * M; i += 256) {
+    const int r = i / M, m = i - r * M, t = t0 + r;
+    float a = 0.f;
+    if (t < fb) {
+      const double x = (double)fminf(fmaxf(mel[((size_t)b * T + t) * M + m], 0.f), 1.f);
+      a = (float)pow(10.0, (x * -(double)min_db + (double)min_db) * 0.05);
+    }
+    melmag_amp[m * MELMAG_ROWS + r] = a;
+  }
+  __syncthreads();
+  const float4* amp4 = reinterpret_cast<const float4*>(melmag_amp);
+  for (int f = tid; f < F; f += 256) {
+    float acc[MELMAG_ROWS];
+#pragma unroll
+    for (int r = 0; r < MELMAG_ROWS; ++r) acc[r] = 0.f;
+    for (int m = 0; m < M; ++m) {
+      const float w = inv[(size_t)m * F + f];
+      const float4 a0 = amp4[2 * m], a1 = amp4[2 * m + 1];
+      acc[0] = fmaf(w, a0.x, acc[0]); acc[1] = fmaf(w, a0.y, acc[1]); acc[2] = fmaf(w, a0.z, acc[2]); acc[3] = fmaf(w, a0.w, acc[3]);
+      acc[4] = fmaf(w, a1.x, acc[4]); acc[5] = fmaf(w, a1.y, acc[5]); acc[6] = fmaf(w, a1.z, acc[6]); acc[7] = fmaf(w, a1.w, acc[7]);
+    }
+#pragma unroll
+    for (int r = 0; r < MELMAG_ROWS; ++r) {
+      const int t = t0 + r;
+      if (t < Tr) {
+        float v = 0.f;
+        if (t < fb) {
+          v = fmaxf(1e-10f, acc[r]);
+          if (apply_pow) v = powf(v, power);
+        }
+        out[((size_t)b * Tr + t) * F + f] = v;
+      }
+    }
+  }
+}
+static_assert(MELMAG_ROWS == 8, "k_gl_mel_magnitude reads a mel's eight amplitudes as two float4");
 
 // ---- silence trimming: librosa.effects.trim (synthesizer.py:266-269), restated; UNPINNED on librosa (include/taco_abi.h) ----
 #define TRIM_THREADS 256       // four waves per workgroup of k_trim_energy
@@ -484,6 +578,7 @@ static void carve_gl(Carver& cv, const taco_gl* g, int B, int T, GlWs& w) {
   w.ypad = cv.f((size_t)B * gl_slot(g, T) + 2 * g->n_fft + g->win);
   w.wss = cv.f((size_t)g->hop * (T - 1) + g->n_fft);
 }
+static size_t mel_lds_bytes(int num_mels) { return (size_t)MELMAG_ROWS * num_mels * sizeof(float); }   // k_gl_mel_magnitude's amplitudes
 // analysis: T = 1 + Lmax / hop frames per utterance in the slot geometry above (a padded utterance is Lmax + n_fft <= gl_slot samples)
 struct SpecWs { float *ypad, *est; int* nf; };
 static size_t spec_tail(const taco_gl* g) { return (size_t)2 * g->n_fft + g->win; }                // slack behind the last slot

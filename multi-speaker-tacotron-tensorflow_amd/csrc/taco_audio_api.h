@@ -1,14 +1,20 @@
 // taco_audio_api.h -- C ABI of the spectrogram -> waveform step and of the waveform -> training targets step; included inside extern "C".
 
-int taco_gl_create(const taco_audio_hparams* hp, int device, taco_gl** out) {
+// The handle of either flavour.  GL_LIBROSA centres the window in n_fft (lpad = (n_fft - win) / 2: librosa pads the window, and the frame with
+// it); GL_TF leaves it at the start (lpad = 0: tf.contrib.signal.stft multiplies the win samples by the window and zero-pads at the END
+// to n_fft, and inverse_stft keeps irfft(X, n_fft)[:win]).  Both are the same two packs: X_k = sum_n f[n] w[n] e^{-2 pi i k (n + lpad) / N}
+// and its transpose with the irfft weights, win columns, in double with the angle reduced exactly.  upload = false (taco_debug_gl_create_host)
+// stops before the device is touched: such a handle serves the argument and state checks only.
+static int gl_create(const taco_audio_hparams* hp, int device, int flavor, bool upload, taco_gl** out) {
   if (!hp || !out) return fail(TACO_ERR_ARG, "null argument");
   taco_gl* g = new taco_gl();
   g->hp = *hp;
+  g->flavor = flavor;
   g->F = hp->num_freq; g->n_fft = (hp->num_freq - 1) * 2;                       // audio/__init__.py:118-122
   g->hop = (int)(hp->frame_shift_ms / 1000.0 * hp->sample_rate);
   g->win = (int)(hp->frame_length_ms / 1000.0 * hp->sample_rate);
   if (g->F < 2 || g->hop < 1 || g->win < 2 || g->win > g->n_fft) { delete g; return fail(TACO_ERR_ARG, "bad STFT parameters"); }
-  g->lpad = (g->n_fft - g->win) / 2;
+  g->lpad = flavor == GL_TF ? 0 : (g->n_fft - g->win) / 2;
   const int N = g->n_fft, F = g->F, W = g->win;
   const double PI2 = 6.283185307179586476925286766559;
   std::vector<double> w(W);
@@ -38,6 +44,7 @@ int taco_gl_create(const taco_audio_hparams* hp, int device, taco_gl** out) {
   pack_bf3(gm, iv.data(), 1, 2 * F, W, &g->inv.bh, &g->inv.bl, &g->inv.K16, &g->inv.cin_pad16);
   g->w2 = arena_put(gm, w2.data(), w2.size());
   add_var(gm, g->fwd, 0); add_var(gm, g->inv, 0);
+  if (!upload) { *out = g; return 0; }
   if (hipSetDevice(device) != hipSuccess || hipMalloc((void**)&gm->darena, gm->harena.size() * sizeof(float)) != hipSuccess ||
       hipMemcpy(gm->darena, gm->harena.data(), gm->harena.size() * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) {
     delete gm; delete g; return fail(TACO_ERR_HIP, "could not upload the DFT packs");
@@ -53,11 +60,18 @@ int taco_gl_create(const taco_audio_hparams* hp, int device, taco_gl** out) {
   return 0;
 }
 
+int taco_gl_create(const taco_audio_hparams* hp, int device, taco_gl** out) { return gl_create(hp, device, GL_LIBROSA, true, out); }
+int taco_gl_create_tf(const taco_audio_hparams* hp, int device, taco_gl** out) { return gl_create(hp, device, GL_TF, true, out); }
+int taco_debug_gl_create_host(const taco_audio_hparams* hp, int tf_flavor, taco_gl** out) {
+  return gl_create(hp, -1, tf_flavor ? GL_TF : GL_LIBROSA, false, out);
+}
+
 void taco_gl_destroy(taco_gl* g) {
   if (!g) return;
   if (g->gm) { if (g->gm->darena) (void)hipFree(g->gm->darena); delete g->gm; }
   if (g->mel_band) (void)hipFree(g->mel_band);
   if (g->mel_w) (void)hipFree(g->mel_w);
+  if (g->inv_mel) (void)hipFree(g->inv_mel);
   delete g;
 }
 
@@ -73,12 +87,16 @@ size_t taco_gl_workspace_bytes(const taco_gl* g, int B, int T) {
 }
 size_t taco_gl_rows_workspace_bytes(const taco_gl* g, int B, int T) { return taco_gl_workspace_bytes(g, B, T); }   // same slot layout
 
+// The librosa-flavour vocoder behind taco_gl_inv_spectrogram_rows (d_mel NULL: magnitudes from d_spec by k_gl_magnitude) and
+// taco_gl_inv_melspectrogram_rows (d_mel: by k_gl_mel_magnitude); everything after the magnitudes is shared.
 // d_frames NULL: every utterance keeps T frames (taco_gl_inv_spectrogram); else the kernels read each utterance's count from it,
 // clamped to [taco_gl_min_frames, T]
-int taco_gl_inv_spectrogram_rows(taco_gl* g, void* hip_stream, const float* d_spec, const int32_t* d_frames, const float* d_init_uniform,
-                                 unsigned long long seed, int B, int T, int iters, float* d_wav, int32_t* d_num_samples, void* d_workspace,
-                                 size_t workspace_bytes) {
-  if (!g || !d_spec || !d_wav || !d_workspace || B <= 0 || T <= 1) return fail(TACO_ERR_ARG, "bad argument");
+static int gl_vocode_rows(taco_gl* g, void* hip_stream, const float* d_spec, const float* d_mel, const int32_t* d_frames,
+                          const float* d_init_uniform, unsigned long long seed, int B, int T, int iters, float* d_wav, int32_t* d_num_samples,
+                          void* d_workspace, size_t workspace_bytes) {
+  if (!g || !(d_spec || d_mel) || !d_wav || !d_workspace || B <= 0 || T <= 1) return fail(TACO_ERR_ARG, "bad argument");
+  if (g->flavor != GL_LIBROSA) return fail(TACO_ERR_STATE, "a handle of taco_gl_create_tf serves taco_gl_inv_spectrogram_tf only");
+  if (d_mel && !g->inv_mels) return fail(TACO_ERR_STATE, "the mel vocoder needs the inverse basis: call taco_gl_set_inv_mel_basis first");
   const int L = g->hop * (T - 1), half = g->n_fft / 2, fmin = taco_gl_min_frames(g);
   if (L <= half) return fail(TACO_ERR_SHAPE, "utterance too short for reflect padding: hop*(T-1) = %d <= n_fft/2 = %d", L, half);
   HIPCHK(hipSetDevice(g->gm->device));
@@ -91,8 +109,12 @@ int taco_gl_inv_spectrogram_rows(taco_gl* g, void* hip_stream, const float* d_sp
   if (iters < 0) iters = g->hp.griffin_lim_iters;
   HIPCHK(zero_async(w.ypad, ((size_t)B * slot + 2 * g->n_fft + g->win) * sizeof(float), st));
   hipLaunchKernelGGL(k_gl_wss, EWGRID((size_t)L + g->n_fft), 0, st, AP(g->gm, g->w2), w.wss, T, g->n_fft, g->hop);
-  hipLaunchKernelGGL(k_gl_magnitude, EWGRID(R * F), 0, st, d_spec, w.S, d_frames, fmin, B, T, Tr, F, g->hp.min_level_db, g->hp.ref_level_db,
-                     g->hp.power);
+  if (d_mel)
+    hipLaunchKernelGGL(k_gl_mel_magnitude, dim3(cdiv(Tr, MELMAG_ROWS), B), dim3(256), mel_lds_bytes(g->inv_mels), st, d_mel, g->inv_mel, w.S, d_frames, fmin, T,
+                       Tr, F, g->inv_mels, g->hp.min_level_db, g->hp.power, 1);
+  else
+    hipLaunchKernelGGL(k_gl_magnitude, EWGRID(R * F), 0, st, d_spec, w.S, d_frames, fmin, B, T, Tr, F, g->hp.min_level_db, g->hp.ref_level_db,
+                       g->hp.power);
   hipLaunchKernelGGL(k_gl_init_phase, EWGRID(R * F), 0, st, w.S, d_init_uniform, seed, w.X, d_frames, fmin, B, T, Tr, F);
   HIPCHK(hipGetLastError());
   auto synth = [&]() -> int {     // y = istft(X): frames = X . IDFT_w ; overlap-add / window sum-square with the reflect pad for the next stft
@@ -119,10 +141,109 @@ int taco_gl_inv_spectrogram_rows(taco_gl* g, void* hip_stream, const float* d_sp
   return 0;
 }
 
+int taco_gl_inv_spectrogram_rows(taco_gl* g, void* hip_stream, const float* d_spec, const int32_t* d_frames, const float* d_init_uniform,
+                                 unsigned long long seed, int B, int T, int iters, float* d_wav, int32_t* d_num_samples, void* d_workspace,
+                                 size_t workspace_bytes) {
+  if (!d_spec) return fail(TACO_ERR_ARG, "bad argument");
+  return gl_vocode_rows(g, hip_stream, d_spec, nullptr, d_frames, d_init_uniform, seed, B, T, iters, d_wav, d_num_samples, d_workspace,
+                        workspace_bytes);
+}
+
 int taco_gl_inv_spectrogram(taco_gl* g, void* hip_stream, const float* d_spec, const float* d_init_uniform, unsigned long long seed,
                             int B, int T, int iters, float* d_wav, void* d_workspace, size_t workspace_bytes) {
   return taco_gl_inv_spectrogram_rows(g, hip_stream, d_spec, nullptr, d_init_uniform, seed, B, T, iters, d_wav, nullptr, d_workspace,
                                       workspace_bytes);
+}
+
+// ---- inv_melspectrogram (audio/__init__.py:70-72,136-140) ----
+int taco_gl_set_inv_mel_basis(taco_gl* g, const float* host_inv, int num_mels) {
+  if (!g || !host_inv || num_mels <= 0) return fail(TACO_ERR_ARG, "bad argument");
+  if (mel_lds_bytes(num_mels) > 64 * 1024)
+    return fail(TACO_ERR_UNSUPPORTED, "num_mels = %d: k_gl_mel_magnitude keeps %d rows of amplitudes in 64 KB of LDS", num_mels, MELMAG_ROWS);
+  const int F = g->F;
+  std::vector<float> t((size_t)num_mels * F);          // [num_freq, num_mels] as np.linalg.pinv returns it -> mel-major
+  for (int f = 0; f < F; ++f)
+    for (int m = 0; m < num_mels; ++m) t[(size_t)m * F + f] = host_inv[(size_t)f * num_mels + m];
+  HIPCHK(hipSetDevice(g->gm->device));
+  float* d = nullptr;
+  if (hipMalloc((void**)&d, t.size() * sizeof(float)) != hipSuccess ||
+      hipMemcpy(d, t.data(), t.size() * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) {
+    if (d) (void)hipFree(d);
+    return fail(TACO_ERR_HIP, "could not upload the inverse mel basis");
+  }
+  if (g->inv_mel) (void)hipFree(g->inv_mel);           // (hipFree waits for the launches that still read the basis it replaces)
+  g->inv_mel = d; g->inv_mels = num_mels;
+  return 0;
+}
+
+int taco_gl_mel_to_linear(taco_gl* g, void* hip_stream, const float* d_mel, int B, int T, float* d_out) {
+  if (!g || !d_mel || !d_out || B <= 0 || B > 65535 || T <= 0) return fail(TACO_ERR_ARG, "bad argument");
+  if (!g->inv_mels) return fail(TACO_ERR_STATE, "mel to linear needs the inverse basis: call taco_gl_set_inv_mel_basis first");
+  HIPCHK(hipSetDevice(g->gm->device));
+  hipLaunchKernelGGL(k_gl_mel_magnitude, dim3(cdiv(T, MELMAG_ROWS), B), dim3(256), mel_lds_bytes(g->inv_mels), (hipStream_t)hip_stream, d_mel,
+                     g->inv_mel, d_out, nullptr, 0, T, T, g->F, g->inv_mels, g->hp.min_level_db, 1.0f, 0);
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
+int taco_gl_inv_melspectrogram_rows(taco_gl* g, void* hip_stream, const float* d_mel, const int32_t* d_frames, const float* d_init_uniform,
+                                    unsigned long long seed, int B, int T, int iters, float* d_wav, int32_t* d_num_samples, void* d_workspace,
+                                    size_t workspace_bytes) {
+  if (!d_mel) return fail(TACO_ERR_ARG, "bad argument");
+  return gl_vocode_rows(g, hip_stream, nullptr, d_mel, d_frames, d_init_uniform, seed, B, T, iters, d_wav, d_num_samples, d_workspace,
+                        workspace_bytes);
+}
+
+// ---- inv_spectrogram_tensorflow (audio/__init__.py:59-61,87-96,109-116,152-153,167-168; synthesizer.py:53-54) ----
+int taco_gl_tf_num_samples(const taco_gl* g, int T) { return (g && T > 0) ? g->hop * (T - 1) + g->win : 0; }
+
+size_t taco_gl_tf_workspace_bytes(const taco_gl* g, int B, int T) {      // the slot layout of the librosa flavour, without its wss table in use
+  if (!g || B <= 0 || T <= 0) return 0;
+  Carver cv(nullptr, 0);
+  GlWs w; carve_gl(cv, g, B, T, w);
+  return cv.off;
+}
+
+int taco_gl_inv_spectrogram_tf(taco_gl* g, void* hip_stream, const float* d_spec, const int32_t* d_frames, int B, int T, int iters, float* d_wav,
+                               int32_t* d_num_samples, void* d_workspace, size_t workspace_bytes) {
+  if (!g || !d_spec || !d_wav || !d_workspace || B <= 0 || B > 65535 || T <= 0) return fail(TACO_ERR_ARG, "bad argument");
+  if (g->flavor != GL_TF) return fail(TACO_ERR_STATE, "taco_gl_inv_spectrogram_tf needs a handle of taco_gl_create_tf");
+  HIPCHK(hipSetDevice(g->gm->device));
+  hipStream_t st = (hipStream_t)hip_stream;
+  Carver cv(d_workspace, workspace_bytes);
+  GlWs w; carve_gl(cv, g, B, T, w);
+  if (!cv.ok()) return fail(TACO_ERR_STATE, "workspace too small: need %zu bytes, have %zu", cv.off, workspace_bytes);
+  const int Tr = gl_rows(g, T), F = g->F, L = taco_gl_tf_num_samples(g, T);
+  const size_t R = (size_t)B * Tr, slot = gl_slot(g, T);
+  if (iters < 0) iters = g->hp.griffin_lim_iters;
+  // every slot starts as zeros: an utterance's overlap-add writes its own samples only, and what a tail row of the frame matrix reads
+  // behind them must be finite (it is multiplied by S = 0).  est is filled with zeros to serve as the "uniform" of zero phase:
+  // k_gl_init_phase then writes X = [S cos 0 | S sin 0] = [S | 0] exactly (audio/__init__.py:90-91, S cast to complex64)
+  HIPCHK(zero_async(w.ypad, ((size_t)B * slot + 2 * g->n_fft + g->win) * sizeof(float), st));
+  HIPCHK(zero_async(w.est, R * 2 * F * sizeof(float), st));
+  hipLaunchKernelGGL(k_gl_magnitude, EWGRID(R * F), 0, st, d_spec, w.S, d_frames, 1, B, T, Tr, F, g->hp.min_level_db, g->hp.ref_level_db,
+                     g->hp.power);
+  hipLaunchKernelGGL(k_gl_init_phase, EWGRID(R * F), 0, st, w.S, w.est, 0ull, w.X, d_frames, 1, B, T, Tr, F);
+  HIPCHK(hipGetLastError());
+  auto synth = [&]() -> int {     // y = inverse_stft(X): frames = X . IDFT_w (win columns), plain overlap-add to the start of each slot
+    GemmCall c; c.x = w.X; c.ldx = 2 * F; c.M = (int)R; c.out = w.Y; c.ldo = g->win;
+    TRY(run_gemm(g->gm, st, &g->inv, 1, false, c));
+    hipLaunchKernelGGL(k_gl_overlap_add_tf, dim3((L + 255) / 256, B), dim3(256), 0, st, w.Y, w.ypad, d_frames, T, Tr, g->win, g->hop, slot);
+    HIPCHK(hipGetLastError());
+    return 0;
+  };
+  TRY(synth());
+  for (int it = 0; it < iters; ++it) {
+    // est = stft(y), pad_end=False: row (b, t) is ypad[b*slot + t*hop ...][0 .. win); the utterance's hop*(f-1) + win samples hold exactly f frames
+    GemmCall c; c.x = w.ypad; c.ldx = g->hop; c.M = (int)R; c.out = w.est; c.ldo = 2 * F;
+    TRY(run_gemm(g->gm, st, &g->fwd, 1, false, c));
+    hipLaunchKernelGGL(k_gl_project_tf, EWGRID(R * F), 0, st, w.est, w.S, w.X, R, F);
+    HIPCHK(hipGetLastError());
+    TRY(synth());
+  }
+  hipLaunchKernelGGL(k_gl_output_tf, dim3((L + 255) / 256, B), dim3(256), 0, st, w.ypad, d_wav, d_frames, T, g->win, g->hop, d_num_samples, L, slot);
+  HIPCHK(hipGetLastError());
+  return 0;
 }
 
 int taco_wav_to_pcm16(void* hip_stream, const float* d_wav, const int32_t* d_num_samples, int B, int L, int16_t* d_pcm) {
@@ -266,6 +387,7 @@ static int spec_epilogue(taco_gl* g, hipStream_t st, const float* est, const int
 int taco_spec_targets(taco_gl* g, void* hip_stream, const float* d_wav, const int32_t* d_num_samples, int B, int Lmax, float* d_linear,
                       float* d_mel, int32_t* d_num_frames, void* d_workspace, size_t workspace_bytes) {
   if (!g || !d_wav || !d_linear || !d_workspace || B <= 0 || B > 65535 || Lmax <= 0) return fail(TACO_ERR_ARG, "bad argument");
+  if (g->flavor != GL_LIBROSA) return fail(TACO_ERR_STATE, "a handle of taco_gl_create_tf serves taco_gl_inv_spectrogram_tf only");
   const int half = g->n_fft / 2, T = 1 + Lmax / g->hop, Tr = gl_rows(g, T), F = g->F;
   if (Lmax <= half) return fail(TACO_ERR_SHAPE, "utterance too short for reflect padding: Lmax = %d <= n_fft/2 = %d", Lmax, half);
   TRY(spec_check(g, d_mel));      // before anything is launched

@@ -146,7 +146,7 @@ class Synthesizer(object):
         return linear, alignments
 
     def synthesize_audio(self, texts=None, tokens=None, speaker_ids=None, end_of_sentence=True, attention_trim=True,
-                         manual_alignments=None, seed=0, iters=None, pcm=True, librosa_trim=False):
+                         manual_alignments=None, seed=0, iters=None, pcm=True, librosa_trim=False, vocoder="griffin_lim"):
         """The reference's synthesize -> plot_graph_and_save_audio chain up to the samples save_audio writes (synthesizer.py:119-126,
         242-264; audio/__init__.py:22-25), everything between the token upload and the audio download on the device: the forward, the
         attention trim on the device alignments, Griffin-Lim on every utterance's own frames read from the trim kernel's output, the
@@ -157,7 +157,15 @@ class Synthesizer(object):
         hop_length=256, top_db=50) runs on the device between Griffin-Lim and the scaling (GriffinLim.trim; UNPINNED on librosa, the
         0.5.x energy convention of the reference's pin); its `end` replaces the row's sample count for the PCM peak and for the cut
         (the reference cuts the tail only), and `trim_index` [N, 2] (start, end) is downloaded in place of the sample counts.  Off
-        (the default): `trim_index` is None and nothing else changes."""
+        (the default): `trim_index` is None and nothing else changes.
+        vocoder: "griffin_lim" (default) is inv_spectrogram as above.  "tensorflow" runs model.linear_outputs through
+        inv_spectrogram_tensorflow (audio/__init__.py:59-61), the reference's Synthesizer.wav_output (synthesizer.py:53-54), with the
+        attention trim's frame counts: deterministic, `seed` is not used.  "mel" runs model.mel_outputs -- what the decoder produced
+        before the post-net -- through inv_melspectrogram (:70-72).  Both UNPINNED (include/taco_abi.h).  pcm, librosa_trim and the
+        returned list behave the same for all three; any other name raises TacoError(TACO_ERR_ARG)."""
+        from . import _lib
+        if vocoder not in ("griffin_lim", "tensorflow", "mel"):
+            raise _lib.TacoError(_lib.TACO_ERR_ARG, "vocoder must be 'griffin_lim', 'tensorflow' or 'mel', got %r" % (vocoder,))
         sequences = self._token_rows(texts, tokens)
         input_lengths = np.argmax(sequences == EOS_ID, 1).astype(np.int32)             # synthesizer.py:120
         if type(speaker_ids) == dict:
@@ -168,8 +176,19 @@ class Synthesizer(object):
         frames = None
         if attention_trim and end_of_sentence:
             frames = self._attention_trim_device(alignments, [len(seq) for seq in sequences])
-        gl = self._griffin_lim()
-        wav, num_samples = gl.inv_spectrogram_rows(linear, frames, seed=seed, iters=iters)
+        if vocoder == "tensorflow":
+            gl = self._griffin_lim_tf()
+            wav, num_samples = gl.inv_spectrogram_tensorflow(linear, frames, iters=iters)
+        elif vocoder == "mel":
+            gl = self._griffin_lim()
+            if not gl._inv_mels:
+                gl.set_inv_mel_basis()
+            mel = self.model.mel_outputs                       # [N, steps, r * num_mels] or [N, frames, num_mels]: the same memory
+            mel = mel.reshape(mel.shape[0], -1, self.hparams.num_mels)
+            wav, num_samples = gl.inv_melspectrogram(mel, frames, seed=seed, iters=iters)
+        else:
+            gl = self._griffin_lim()
+            wav, num_samples = gl.inv_spectrogram_rows(linear, frames, seed=seed, iters=iters)
         index = None
         if librosa_trim and end_of_sentence:
             index = gl.trim(wav, num_samples, **self.LIBROSA_TRIM)
@@ -187,6 +206,12 @@ class Synthesizer(object):
         if getattr(self, "_gl", None) is None:
             self._gl = GriffinLim(self.hparams, device=str(self.model.device))
         return self._gl
+
+    def _griffin_lim_tf(self):
+        from .audio import GriffinLim
+        if getattr(self, "_gl_tf", None) is None:
+            self._gl_tf = GriffinLim(self.hparams, device=str(self.model.device), flavor="tensorflow")
+        return self._gl_tf
 
     def inv_spectrogram(self, linear, spec_end_idx=None, librosa_trim=False):
         """audio/__init__.py:54-56 for a batch [N, T, num_freq]; returns a list of 1-D float32 arrays (each cut to the samples its

@@ -20,7 +20,12 @@ must reproduce.  Its own JSON line, `--split` only.
 `--resample` measures resampling to the model's rate (audio.Resampler, kaiser_best) on three minutes at 44100 -> 24000 Hz: mono float32
 and stereo 16-bit PCM, the call alone (input and outputs on the device), as output samples per second and as the bytes of the stream it
 moves (input once, output once) over its time; beside it the vectorised float64 restatement tests/resample_reference.py on the CPU for
-the same mono input, whose values bound the device's error; and three minutes at 16000 -> 24000 Hz, mono float32, the up-sampling shape.  Its own JSON line, `--resample` only."""
+the same mono input, whose values bound the device's error; and three minutes at 16000 -> 24000 Hz, mono float32, the up-sampling shape.  Its own JSON line, `--resample` only.
+`--vocoders` times the reference's three vocoders in one run at the C2 output shape (32 x 512 frames, 60 iterations), windows alternating: the
+existing inv_spectrogram, inv_spectrogram_tensorflow (GriffinLim(flavor="tensorflow")) and inv_melspectrogram (80 mels), plus
+k_gl_mel_magnitude alone (GriffinLim.mel_to_linear on the same batch: the kernel without its ^power) -- each arm's ms, the TF arm relative
+to the existing one, and k_gl_mel_magnitude relative to one Griffin-Lim iteration of the same run (the existing arm at 60 and at 0 iterations,
+their difference over 60).  Its own JSON line, `--vocoders` only."""
 import json, os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "oracle"))
@@ -236,6 +241,54 @@ def resample():
     return out
 
 
+def vocoders():
+    gl, tf = taco_amd.GriffinLim(hp), taco_amd.GriffinLim(hp, flavor="tensorflow")
+    gl.set_inv_mel_basis()
+    M = int(hp.num_mels)
+    rs = np.random.RandomState(0)
+    spec = torch.from_numpy(rs.rand(B, T, F).astype(np.float32)).cuda()
+    mel = torch.from_numpy(rs.rand(B, T, M).astype(np.float32)).cuda()
+    arms = {"inv_spectrogram": (lambda: gl.inv_spectrogram(spec), 4), "inv_spectrogram_0_iters": (lambda: gl.inv_spectrogram(spec, iters=0), 20),
+            "inv_spectrogram_tensorflow": (lambda: tf.inv_spectrogram_tensorflow(spec)[0], 4),
+            "inv_melspectrogram": (lambda: gl.inv_melspectrogram(mel)[0], 4), "k_gl_mel_magnitude": (lambda: gl.mel_to_linear(mel), 50)}
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    for f, _ in arms.values():
+        for _ in range(2):
+            f()
+    torch.cuda.synchronize()
+    ms = {k: [] for k in arms}
+    for _ in range(5):
+        for k, (f, reps) in arms.items():
+            e0.record()
+            for _ in range(reps):
+                f()
+            e1.record(); torch.cuda.synchronize()
+            ms[k].append(e0.elapsed_time(e1) / reps)
+    med = {k: float(np.median(v)) for k, v in ms.items()}
+    a, b = tf.inv_spectrogram_tensorflow(spec), tf.inv_spectrogram_tensorflow(spec)
+    w = gl.inv_melspectrogram(mel)[0]
+    iteration = (med["inv_spectrogram"] - med["inv_spectrogram_0_iters"]) / hp.griffin_lim_iters
+    nbytes = B * T * (M + F) * 4                                 # mel read, magnitudes written (the basis stays in cache)
+    out = {"metric": "the three vocoders at the C2 output shape (Griffin-Lim, %d iterations)" % hp.griffin_lim_iters, "value": med["inv_spectrogram_tensorflow"],
+           "unit": "ms (inv_spectrogram_tensorflow)", "batch": "B=%d x T=%d frames x %d bins (%d mels)" % (B, T, F, M),
+           "windows": "5 windows per arm, alternating: 4 calls of a vocoder, 20 of the 0-iteration call, 50 of k_gl_mel_magnitude",
+           "inv_spectrogram_ms": ms["inv_spectrogram"], "inv_spectrogram_tensorflow_ms": ms["inv_spectrogram_tensorflow"],
+           "inv_melspectrogram_ms": ms["inv_melspectrogram"], "inv_spectrogram_0_iters_ms": ms["inv_spectrogram_0_iters"],
+           "k_gl_mel_magnitude_ms": ms["k_gl_mel_magnitude"], "median_ms": med,
+           "tensorflow_over_existing": med["inv_spectrogram_tensorflow"] / med["inv_spectrogram"],
+           "mel_over_existing": med["inv_melspectrogram"] / med["inv_spectrogram"],
+           "one_iteration_ms": iteration, "k_gl_mel_magnitude_over_one_iteration": med["k_gl_mel_magnitude"] / iteration,
+           "k_gl_mel_magnitude_bytes": nbytes, "k_gl_mel_magnitude_GBps": nbytes / (med["k_gl_mel_magnitude"] / 1e3) / 1e9,
+           "k_gl_mel_magnitude_GFLOPs": 2.0 * B * T * M * F / (med["k_gl_mel_magnitude"] / 1e3) / 1e9,
+           "tensorflow_identical_bits_on_two_calls": bool(torch.equal(a[0], b[0]) and torch.equal(a[1], b[1])),
+           "finite": bool(torch.isfinite(a[0]).all() and torch.isfinite(w).all())}
+    gl.close(); tf.close()
+    return out
+
+
+if "--vocoders" in sys.argv:
+    print(json.dumps(vocoders()))
+    sys.exit(0)
 if "--resample" in sys.argv:
     print(json.dumps(resample()))
     sys.exit(0)
