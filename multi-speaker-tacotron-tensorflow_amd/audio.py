@@ -9,7 +9,9 @@ All arithmetic is in libtaco_hip (taco_gl_*, taco_spec_*); PyTorch holds the buf
 bank (mel_basis) and its pseudo-inverse (inv_mel_basis), built once in float64 and uploaded.
 Recordings reach the model's sample rate through class Resampler (taco_resample_*, taco_wav_resample): librosa.core.load's and
 resample_audio's band-limited sinc interpolation (audio/__init__.py:12-20,30-32), whose one host computation is the Kaiser-windowed
-half filter (kaiser_window)."""
+half filter (kaiser_window).
+Every public method reaches the library through one marshalling layer: _tensor / _lengths (inputs onto the device, shape checks),
+_workspace (the handle's scratch memory) and _call (device, stream, pointers, status)."""
 import ctypes as C
 
 import numpy as np
@@ -73,10 +75,75 @@ def num_frames(hparams, n_samples):
     return int(_lib.load_library().taco_spec_num_frames(C.byref(hp), int(n_samples)))
 
 
-class GriffinLim(object):
+# ---- the one marshalling layer between the public methods below and libtaco_hip ----
+_STREAM = object()      # in _call's arguments: the place of the current stream
+_ENERGY = {"spectral": _lib.TACO_TRIM_SPECTRAL, "time": _lib.TACO_TRIM_TIME}      # frame energies of trim / split
+
+
+def _tensor(x, device, dtype, what, dims=None):
+    """numpy or tensor -> a contiguous `dtype` tensor on the device (one that already is that is used as it is).  dtype may be a tuple:
+    the input's own if it is among them, else the first.  dims: per dimension its name (any size) or (name, size); None: the caller
+    checks the shape."""
+    x = x if torch.is_tensor(x) else torch.as_tensor(np.asarray(x))
+    if isinstance(dtype, tuple):
+        dtype = x.dtype if x.dtype in dtype else dtype[0]
+    x = x.to(device, dtype).contiguous()
+    if dims is not None and (x.dim() != len(dims) or any(not isinstance(d, str) and x.shape[i] != d[1] for i, d in enumerate(dims))):
+        raise Exception("%s must be [%s], got shape %s" % (what, ", ".join(d if isinstance(d, str) else "%s = %d" % d for d in dims), tuple(x.shape)))
+    return x
+
+
+def _lengths(v, device, B, what):
+    """The optional [B] int32 vector (frames, num_samples): a device int32 tensor is used as it is, host data is uploaded, None stays None."""
+    return None if v is None else _tensor(v, device, torch.int32, what, (("B", B),))
+
+
+def _energy(name):
+    if name not in _ENERGY:
+        raise _lib.TacoError(_lib.TACO_ERR_ARG, "energy must be one of %s, got %r" % (sorted(_ENERGY), name))
+    return _ENERGY[name]
+
+
+def _workspace(handle, nbytes):
+    """The handle's workspace, grown to nbytes"""
+    if handle._ws is None or handle._ws.numel() < nbytes:
+        handle._ws = torch.empty(int(nbytes), dtype=torch.uint8, device=handle.device)
+    return handle._ws
+
+
+def _call(device, fn, *args):
+    """fn(*args) on the device's current stream (where args holds _STREAM): tensors and None go as pointers, the status is checked."""
+    def arg(a):
+        if a is _STREAM:
+            return C.c_void_p(torch.cuda.current_stream().cuda_stream)
+        if a is None or torch.is_tensor(a):
+            return C.c_void_p(0 if a is None else a.data_ptr())
+        return a
+    with torch.cuda.device(device):
+        _lib.check(fn(*[arg(a) for a in args]))
+
+
+class _Handle(object):
+    """A library handle `_h` on `device`, released by the function named `_destroy`."""
+    _destroy = None
+
+    def close(self):
+        if getattr(self, "_h", None):
+            getattr(self._lib, self._destroy)(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class GriffinLim(_Handle):
     """flavor "librosa" (default): the handle of inv_spectrogram / inv_melspectrogram and of everything Spectrogram adds.  "tensorflow":
     the handle of inv_spectrogram_tensorflow (tf.contrib.signal's uncentred STFT; the librosa-flavour methods raise TacoError on it).
     pcm16, trim, split, remove_breath, set_inv_mel_basis and mel_to_linear work on either."""
+    _destroy = "taco_gl_destroy"
 
     def __init__(self, hparams, device="cuda:0", flavor="librosa"):
         self.hp = c_audio_hparams(hparams)
@@ -98,67 +165,33 @@ class GriffinLim(object):
     def num_samples(self, T):
         return int(self._lib.taco_gl_num_samples(self._h, T))
 
+    def min_frames(self):
+        return int(self._lib.taco_gl_min_frames(self._h))
+
     def inv_spectrogram(self, linear, init_uniform=None, seed=0, iters=None):
         """linear [B, T, num_freq] (model layout; numpy or tensor) -> waveforms [B, hop*(T-1)] (device tensor).
         init_uniform [B, T, num_freq] in [0,1) replaces the reference's np.random.rand initial phases (default: hash of seed)."""
-        dev = self.device
-        x = (linear if torch.is_tensor(linear) else torch.as_tensor(np.asarray(linear))).to(dev, torch.float32).contiguous()
-        u = None if init_uniform is None else (init_uniform if torch.is_tensor(init_uniform) else torch.as_tensor(np.asarray(init_uniform))).to(dev, torch.float32).contiguous()
-        B, T, F = x.shape
-        if F != self.hp.num_freq:
-            raise Exception("last dimension must be num_freq = %d, got %d" % (self.hp.num_freq, F))
-        nb = int(self._lib.taco_gl_workspace_bytes(self._h, B, T))
-        if self._ws is None or self._ws.numel() < nb:
-            self._ws = torch.empty(nb, dtype=torch.uint8, device=dev)
-        wav = torch.empty((B, self.num_samples(T)), dtype=torch.float32, device=dev)
-        p = lambda t: C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)
-        with torch.cuda.device(dev):
-            _lib.check(self._lib.taco_gl_inv_spectrogram(self._h, C.c_void_p(torch.cuda.current_stream().cuda_stream), p(x), p(u),
-                                                         C.c_ulonglong(int(seed)), B, T, -1 if iters is None else int(iters), p(wav),
-                                                         p(self._ws), self._ws.numel()))
-        return wav
-
-    def min_frames(self):
-        return int(self._lib.taco_gl_min_frames(self._h))
+        return self.inv_spectrogram_rows(linear, None, init_uniform, seed, iters)[0]
 
     def inv_spectrogram_rows(self, linear, frames, init_uniform=None, seed=0, iters=None):
         """Per utterance length (synthesizer.py:242-264: `inv_spectrogram(wav[:spec_end_idx].T)`): linear [B, T, num_freq], frames [B]
         (a device int32 tensor is used as it is and never read on the host -- Synthesizer.attention_trim's kernel output; host data is
         uploaded; None: all T) -> (wav [B, hop*(T-1)], num_samples [B] int32), device tensors.  Row b holds the waveform of its first
         frames[b] frames (clamped to [min_frames(), T]) in its first num_samples[b] samples and zeros after."""
+        return self._vocode_rows(self._lib.taco_gl_inv_spectrogram_rows, linear, "linear", ("num_freq", self.hp.num_freq), frames, init_uniform, seed, iters)
+
+    def _vocode_rows(self, fn, x, what, width, frames, init_uniform, seed, iters):
+        """The librosa-flavour vocoders: fn is the entry point, x [B, T, width[1]] its input, named `what` and its last dimension width[0] in errors"""
         dev = self.device
-        x = (linear if torch.is_tensor(linear) else torch.as_tensor(np.asarray(linear))).to(dev, torch.float32).contiguous()
-        u = None if init_uniform is None else (init_uniform if torch.is_tensor(init_uniform) else torch.as_tensor(np.asarray(init_uniform))).to(dev, torch.float32).contiguous()
-        B, T, F = x.shape
-        if F != self.hp.num_freq:
-            raise Exception("last dimension must be num_freq = %d, got %d" % (self.hp.num_freq, F))
-        fr = None if frames is None else (frames if torch.is_tensor(frames) else torch.as_tensor(np.asarray(frames))).to(dev, torch.int32).contiguous()
-        if fr is not None and tuple(fr.shape) != (B,):
-            raise Exception("frames must be [B] = [%d], got %s" % (B, tuple(fr.shape)))
-        nb = int(self._lib.taco_gl_rows_workspace_bytes(self._h, B, T))
-        if self._ws is None or self._ws.numel() < nb:
-            self._ws = torch.empty(nb, dtype=torch.uint8, device=dev)
+        x = _tensor(x, dev, torch.float32, what, ("B", "T", width))
+        B, T, _ = x.shape
+        u = None if init_uniform is None else _tensor(init_uniform, dev, torch.float32, "init_uniform", (("B", B), ("T", T), ("num_freq", self.hp.num_freq)))
+        fr = _lengths(frames, dev, B, "frames")
+        ws = _workspace(self, self._lib.taco_gl_rows_workspace_bytes(self._h, B, T))
         wav = torch.empty((B, self.num_samples(T)), dtype=torch.float32, device=dev)
         ns = torch.empty((B,), dtype=torch.int32, device=dev)
-        p = lambda t: C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)
-        with torch.cuda.device(dev):
-            _lib.check(self._lib.taco_gl_inv_spectrogram_rows(self._h, C.c_void_p(torch.cuda.current_stream().cuda_stream), p(x), p(fr), p(u),
-                                                              C.c_ulonglong(int(seed)), B, T, -1 if iters is None else int(iters), p(wav),
-                                                              p(ns), p(self._ws), self._ws.numel()))
+        _call(dev, fn, self._h, _STREAM, x, fr, u, C.c_ulonglong(int(seed)), B, T, -1 if iters is None else int(iters), wav, ns, ws, ws.numel())
         return wav, ns
-
-    def _batch(self, x, width, what):
-        """x [B, T, width] float32 contiguous on the device"""
-        x = (x if torch.is_tensor(x) else torch.as_tensor(np.asarray(x))).to(self.device, torch.float32).contiguous()
-        if x.dim() != 3 or x.shape[2] != width:
-            raise Exception("%s must be [B, T, %d], got shape %s" % (what, width, tuple(x.shape)))
-        return x
-
-    def _frames(self, frames, B):
-        fr = None if frames is None else (frames if torch.is_tensor(frames) else torch.as_tensor(np.asarray(frames))).to(self.device, torch.int32).contiguous()
-        if fr is not None and tuple(fr.shape) != (B,):
-            raise Exception("frames must be [B] = [%d], got %s" % (B, tuple(fr.shape)))
-        return fr
 
     def tf_num_samples(self, T):
         return int(self._lib.taco_gl_tf_num_samples(self._h, T))
@@ -171,18 +204,13 @@ class GriffinLim(object):
         its first hop*(frames[b]-1) + win samples, zeros after.  UNPINNED on TensorFlow: tf.contrib.signal.stft / inverse_stft restated
         (include/taco_abi.h), checked against tests/vocoder_reference.py, not against TensorFlow."""
         dev = self.device
-        x = self._batch(linear, self.hp.num_freq, "linear")
+        x = _tensor(linear, dev, torch.float32, "linear", ("B", "T", ("num_freq", self.hp.num_freq)))
         B, T, _ = x.shape
-        fr = self._frames(frames, B)
-        nb = int(self._lib.taco_gl_tf_workspace_bytes(self._h, B, T))
-        if self._ws is None or self._ws.numel() < nb:
-            self._ws = torch.empty(nb, dtype=torch.uint8, device=dev)
+        fr = _lengths(frames, dev, B, "frames")
+        ws = _workspace(self, self._lib.taco_gl_tf_workspace_bytes(self._h, B, T))
         wav = torch.empty((B, self.tf_num_samples(T)), dtype=torch.float32, device=dev)
         ns = torch.empty((B,), dtype=torch.int32, device=dev)
-        p = lambda t: C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)
-        with torch.cuda.device(dev):
-            _lib.check(self._lib.taco_gl_inv_spectrogram_tf(self._h, C.c_void_p(torch.cuda.current_stream().cuda_stream), p(x), p(fr), B, T,
-                                                            -1 if iters is None else int(iters), p(wav), p(ns), p(self._ws), self._ws.numel()))
+        _call(dev, self._lib.taco_gl_inv_spectrogram_tf, self._h, _STREAM, x, fr, B, T, -1 if iters is None else int(iters), wav, ns, ws, ws.numel())
         return wav, ns
 
     def set_inv_mel_basis(self, inv=None):
@@ -193,60 +221,38 @@ class GriffinLim(object):
         _lib.check(self._lib.taco_gl_set_inv_mel_basis(self._h, b.ctypes.data_as(C.c_void_p), b.shape[1]))
         self._inv_mels = int(b.shape[1])
 
-    def _mel_batch(self, mel):
+    @property
+    def inv_mels(self):
+        """Filters of the inverse basis in use; 0: set_inv_mel_basis has not been called"""
+        return self._inv_mels
+
+    def _need_inv_mels(self):
         if not self._inv_mels:
             raise _lib.TacoError(_lib.TACO_ERR_STATE, "the mel vocoder needs the inverse basis: call set_inv_mel_basis first")
-        return self._batch(mel, self._inv_mels, "mel")
+        return self._inv_mels
 
     def mel_to_linear(self, mel):
         """_mel_to_linear(_db_to_amp(_denormalize(mel))) of audio/__init__.py:71,136-140: mel [B, T, num_mels] (normalised, as the model's
         mel_outputs) -> linear magnitudes [B, T, num_freq] (device tensor), floored at 1e-10, before ^power."""
-        dev = self.device
-        x = self._mel_batch(mel)
+        x = _tensor(mel, self.device, torch.float32, "mel", ("B", "T", ("num_mels", self._need_inv_mels())))
         B, T, _ = x.shape
-        out = torch.empty((B, T, self.hp.num_freq), dtype=torch.float32, device=dev)
-        with torch.cuda.device(dev):
-            _lib.check(self._lib.taco_gl_mel_to_linear(self._h, C.c_void_p(torch.cuda.current_stream().cuda_stream), C.c_void_p(x.data_ptr()), B, T,
-                                                       C.c_void_p(out.data_ptr())))
+        out = torch.empty((B, T, self.hp.num_freq), dtype=torch.float32, device=self.device)
+        _call(self.device, self._lib.taco_gl_mel_to_linear, self._h, _STREAM, x, B, T, out)
         return out
 
     def inv_melspectrogram(self, mel, frames=None, init_uniform=None, seed=0, iters=None):
         """inv_melspectrogram of audio/__init__.py:70-72 per utterance length: mel [B, T, num_mels] -> (wav [B, hop*(T-1)], num_samples [B]
         int32), device tensors; frames, init_uniform, seed and iters as inv_spectrogram_rows."""
-        dev = self.device
-        x = self._mel_batch(mel)
-        B, T, _ = x.shape
-        u = None if init_uniform is None else self._batch(init_uniform, self.hp.num_freq, "init_uniform")
-        if u is not None and tuple(u.shape[:2]) != (B, T):
-            raise Exception("init_uniform must be [B, T, num_freq] = [%d, %d, %d], got %s" % (B, T, self.hp.num_freq, tuple(u.shape)))
-        fr = self._frames(frames, B)
-        nb = int(self._lib.taco_gl_rows_workspace_bytes(self._h, B, T))
-        if self._ws is None or self._ws.numel() < nb:
-            self._ws = torch.empty(nb, dtype=torch.uint8, device=dev)
-        wav = torch.empty((B, self.num_samples(T)), dtype=torch.float32, device=dev)
-        ns = torch.empty((B,), dtype=torch.int32, device=dev)
-        p = lambda t: C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)
-        with torch.cuda.device(dev):
-            _lib.check(self._lib.taco_gl_inv_melspectrogram_rows(self._h, C.c_void_p(torch.cuda.current_stream().cuda_stream), p(x), p(fr), p(u),
-                                                                 C.c_ulonglong(int(seed)), B, T, -1 if iters is None else int(iters), p(wav),
-                                                                 p(ns), p(self._ws), self._ws.numel()))
-        return wav, ns
+        return self._vocode_rows(self._lib.taco_gl_inv_melspectrogram_rows, mel, "mel", ("num_mels", self._need_inv_mels()), frames, init_uniform, seed, iters)
 
     def pcm16(self, wav, num_samples=None):
         """save_audio's scaling (audio/__init__.py:23-24) per row: wav [B, L] float32, num_samples [B] (None: L) -> int16 [B, L] (device
         tensor); row b is x * 32767 / max(0.01, max|x[:num_samples[b]]|) truncated, zeros past num_samples[b]."""
-        dev = self.device
-        x = (wav if torch.is_tensor(wav) else torch.as_tensor(np.asarray(wav))).to(dev, torch.float32).contiguous()
-        if x.dim() != 2:
-            raise Exception("wav must be [B, L], got shape %s" % (tuple(x.shape),))
+        x = _tensor(wav, self.device, torch.float32, "wav", ("B", "L"))
         B, L = x.shape
-        ns = None if num_samples is None else (num_samples if torch.is_tensor(num_samples) else torch.as_tensor(np.asarray(num_samples))).to(dev, torch.int32).contiguous()
-        if ns is not None and tuple(ns.shape) != (B,):
-            raise Exception("num_samples must be [B] = [%d], got %s" % (B, tuple(ns.shape)))
-        pcm = torch.empty((B, L), dtype=torch.int16, device=dev)
-        p = lambda t: C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)
-        with torch.cuda.device(dev):
-            _lib.check(self._lib.taco_wav_to_pcm16(C.c_void_p(torch.cuda.current_stream().cuda_stream), p(x), p(ns), B, L, p(pcm)))
+        ns = _lengths(num_samples, self.device, B, "num_samples")
+        pcm = torch.empty((B, L), dtype=torch.int16, device=self.device)
+        _call(self.device, self._lib.taco_wav_to_pcm16, _STREAM, x, ns, B, L, pcm)
         return pcm
 
     def trim(self, wav, num_samples=None, top_db=60, frame_length=2048, hop_length=512, energy="spectral", return_db=False):
@@ -258,38 +264,15 @@ class GriffinLim(object):
         (mean square of the unwindowed frame).  UNPINNED on librosa: a restatement of the documented algorithm (include/taco_abi.h,
         taco_wav_trim), checked against tests/trim_reference.py, not against librosa."""
         dev = self.device
-        x = (wav if torch.is_tensor(wav) else torch.as_tensor(np.asarray(wav))).to(dev, torch.float32).contiguous()
-        if x.dim() != 2:
-            raise Exception("wav must be [B, L], got shape %s" % (tuple(x.shape),))
+        x = _tensor(wav, dev, torch.float32, "wav", ("B", "L"))
         B, L = x.shape
-        ns = None if num_samples is None else (num_samples if torch.is_tensor(num_samples) else torch.as_tensor(np.asarray(num_samples))).to(dev, torch.int32).contiguous()
-        if ns is not None and tuple(ns.shape) != (B,):
-            raise Exception("num_samples must be [B] = [%d], got %s" % (B, tuple(ns.shape)))
-        modes = {"spectral": _lib.TACO_TRIM_SPECTRAL, "time": _lib.TACO_TRIM_TIME}
-        if energy not in modes:
-            raise _lib.TacoError(_lib.TACO_ERR_ARG, "energy must be one of %s, got %r" % (sorted(modes), energy))
-        frame_length, hop_length = int(frame_length), int(hop_length)
-        nb = int(self._lib.taco_wav_trim_workspace_bytes(B, L, frame_length, hop_length))
-        if self._ws is None or self._ws.numel() < nb:
-            self._ws = torch.empty(nb, dtype=torch.uint8, device=dev)
+        ns = _lengths(num_samples, dev, B, "num_samples")
+        mode, frame_length, hop_length = _energy(energy), int(frame_length), int(hop_length)
+        ws = _workspace(self, self._lib.taco_wav_trim_workspace_bytes(B, L, frame_length, hop_length))
         index = torch.empty((B, 2), dtype=torch.int32, device=dev)
         db = torch.empty((B, 1 + L // max(hop_length, 1)), dtype=torch.float32, device=dev) if return_db else None
-        p = lambda t: C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)
-        with torch.cuda.device(dev):
-            _lib.check(self._lib.taco_wav_trim(C.c_void_p(torch.cuda.current_stream().cuda_stream), p(x), p(ns), B, L, float(top_db),
-                                               frame_length, hop_length, modes[energy], p(index), p(db), p(self._ws), self._ws.numel()))
+        _call(dev, self._lib.taco_wav_trim, _STREAM, x, ns, B, L, float(top_db), frame_length, hop_length, mode, index, db, ws, ws.numel())
         return (index, db) if return_db else index
-
-    def _rows(self, wav, num_samples):
-        """(x [B, L] float32 contiguous on the device, num_samples [B] int32 on the device or None)"""
-        dev = self.device
-        x = (wav if torch.is_tensor(wav) else torch.as_tensor(np.asarray(wav))).to(dev, torch.float32).contiguous()
-        if x.dim() != 2:
-            raise Exception("wav must be [B, L], got shape %s" % (tuple(x.shape),))
-        ns = None if num_samples is None else (num_samples if torch.is_tensor(num_samples) else torch.as_tensor(np.asarray(num_samples))).to(dev, torch.int32).contiguous()
-        if ns is not None and tuple(ns.shape) != (x.shape[0],):
-            raise Exception("num_samples must be [B] = [%d], got %s" % (x.shape[0], tuple(ns.shape)))
-        return x, ns
 
     def split(self, wav, num_samples=None, top_db=60, frame_length=2048, hop_length=512, energy="spectral", max_intervals=None, return_db=False):
         """librosa.effects.split per row (audio/silence.py:44-45 calls it with top_db=40, frame_length=1024, hop_length=256, remove_breath
@@ -300,25 +283,19 @@ class GriffinLim(object):
         never overflows; with a smaller M counts still holds the true number and the first M runs are written.  Frames, energies and
         the threshold are `trim`'s: intervals[b, 0, 0] and intervals[b, counts[b] - 1, 1] are its index.  UNPINNED on librosa
         (include/taco_abi.h, taco_wav_split), checked against tests/split_reference.py, not against librosa."""
-        x, ns = self._rows(wav, num_samples)
-        B, L = x.shape
         dev = self.device
-        modes = {"spectral": _lib.TACO_TRIM_SPECTRAL, "time": _lib.TACO_TRIM_TIME}
-        if energy not in modes:
-            raise _lib.TacoError(_lib.TACO_ERR_ARG, "energy must be one of %s, got %r" % (sorted(modes), energy))
-        frame_length, hop_length = int(frame_length), int(hop_length)
+        x = _tensor(wav, dev, torch.float32, "wav", ("B", "L"))
+        B, L = x.shape
+        ns = _lengths(num_samples, dev, B, "num_samples")
+        mode, frame_length, hop_length = _energy(energy), int(frame_length), int(hop_length)
         fmax = 1 + L // max(hop_length, 1)
         M = (fmax + 1) // 2 if max_intervals is None else int(max_intervals)
-        nb = int(self._lib.taco_wav_split_workspace_bytes(B, L, frame_length, hop_length))
-        if self._ws is None or self._ws.numel() < nb:
-            self._ws = torch.empty(nb, dtype=torch.uint8, device=dev)
+        ws = _workspace(self, self._lib.taco_wav_split_workspace_bytes(B, L, frame_length, hop_length))
         intervals = torch.empty((B, max(M, 1), 2), dtype=torch.int32, device=dev)
         counts = torch.empty((B,), dtype=torch.int32, device=dev)
         db = torch.empty((B, fmax), dtype=torch.float32, device=dev) if return_db else None
-        p = lambda t: C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)
-        with torch.cuda.device(dev):
-            _lib.check(self._lib.taco_wav_split(C.c_void_p(torch.cuda.current_stream().cuda_stream), p(x), p(ns), B, L, float(top_db), frame_length,
-                                                hop_length, modes[energy], M, p(intervals), p(counts), p(db), p(self._ws), self._ws.numel()))
+        _call(dev, self._lib.taco_wav_split, _STREAM, x, ns, B, L, float(top_db), frame_length, hop_length, mode, M, intervals, counts, db, ws,
+              ws.numel())
         return (intervals, counts, db) if return_db else (intervals, counts)
 
     def remove_breath(self, wav, num_samples=None, top_db=40, frame_length=128, hop_length=32, threshold=0.05, energy="spectral", return_info=False):
@@ -327,30 +304,17 @@ class GriffinLim(object):
         mutes in place -- is set to zero.  wav [B, L], num_samples [B] or None -> the muted waveforms [B, L] (a new device tensor:
         bits of the input outside the muted intervals, zeros past num_samples[b]); with return_info also (intervals, counts, muted
         [B, M] int32, abs_mean [B, 1 + M] float32: the row's mean before any mute, then each interval's)."""
-        x, ns = self._rows(wav, num_samples)
-        B, L = x.shape
         dev = self.device
+        x = _tensor(wav, dev, torch.float32, "wav", ("B", "L"))
+        B, L = x.shape
+        ns = _lengths(num_samples, dev, B, "num_samples")
         intervals, counts = self.split(x, ns, top_db=top_db, frame_length=frame_length, hop_length=hop_length, energy=energy)
         M = intervals.shape[1]
         out = torch.empty_like(x)
         muted = torch.empty((B, M), dtype=torch.int32, device=dev) if return_info else None
         mean = torch.empty((B, 1 + M), dtype=torch.float32, device=dev) if return_info else None
-        p = lambda t: C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)
-        with torch.cuda.device(dev):
-            _lib.check(self._lib.taco_wav_breath_mute(C.c_void_p(torch.cuda.current_stream().cuda_stream), p(x), p(ns), B, L, p(intervals), p(counts),
-                                                      M, float(threshold), p(out), p(muted), p(mean)))
+        _call(dev, self._lib.taco_wav_breath_mute, _STREAM, x, ns, B, L, intervals, counts, M, float(threshold), out, muted, mean)
         return (out, (intervals, counts, muted, mean)) if return_info else out
-
-    def close(self):
-        if getattr(self, "_h", None):
-            self._lib.taco_gl_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 class Spectrogram(GriffinLim):
@@ -383,16 +347,10 @@ class Spectrogram(GriffinLim):
         num_frames): contiguous device tensors of exactly those shapes that are written in place and returned (nothing is allocated
         once the workspace has its size)."""
         dev = self.device
-        x = (wav if torch.is_tensor(wav) else torch.as_tensor(np.asarray(wav))).to(dev, torch.float32).contiguous()
-        if x.dim() != 2:
-            raise Exception("wav must be [B, Lmax], got shape %s" % (tuple(x.shape),))
+        x = _tensor(wav, dev, torch.float32, "wav", ("B", "Lmax"))
         B, L = x.shape
-        ns = None if num_samples is None else (num_samples if torch.is_tensor(num_samples) else torch.as_tensor(np.asarray(num_samples))).to(dev, torch.int32).contiguous()
-        if ns is not None and tuple(ns.shape) != (B,):
-            raise Exception("num_samples must be [B] = [%d], got %s" % (B, tuple(ns.shape)))
-        nb = int(self._lib.taco_spec_workspace_bytes(self._h, B, L))
-        if self._ws is None or self._ws.numel() < nb:
-            self._ws = torch.empty(nb, dtype=torch.uint8, device=dev)
+        ns = _lengths(num_samples, dev, B, "num_samples")
+        ws = _workspace(self, self._lib.taco_spec_workspace_bytes(self._h, B, L))
         T = self.num_frames(L)
         if mel and not self.num_mels:
             raise _lib.TacoError(_lib.TACO_ERR_STATE, "the mel output needs a filter bank: call set_mel_basis first (or pass mel=False)")
@@ -407,10 +365,7 @@ class Spectrogram(GriffinLim):
             lin = torch.empty((B, T, self.hp.num_freq), dtype=torch.float32, device=dev)
             m = torch.empty((B, T, self.num_mels), dtype=torch.float32, device=dev) if mel else None
             nf = torch.empty((B,), dtype=torch.int32, device=dev)
-        p = lambda t: C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)
-        with torch.cuda.device(dev):
-            _lib.check(self._lib.taco_spec_targets(self._h, C.c_void_p(torch.cuda.current_stream().cuda_stream), p(x), p(ns), B, L, p(lin),
-                                                   p(m), p(nf), p(self._ws), self._ws.numel()))
+        _call(dev, self._lib.taco_spec_targets, self._h, _STREAM, x, ns, B, L, lin, m, nf, ws, ws.numel())
         return lin, m, nf
 
     def spectrogram(self, y):
@@ -450,12 +405,14 @@ FILTERS = {"kaiser_best": dict(num_zeros=64, precision=9, beta=14.76965645937949
            "kaiser_fast": dict(num_zeros=16, precision=9, beta=8.555504641634386, rolloff=0.85)}
 
 
-class Resampler(object):
+
+class Resampler(_Handle):
     """Recordings at orig_sr -> target_sr on the GPU, as librosa.core.resample(y, orig_sr, target_sr) with resampy's sinc interpolation
     does, but with every output at its exact position t * orig_sr / target_sr (include/taco_abi.h says where resampy 0.2.0's
     accumulated position differs).  filter: a name in FILTERS, a dict of kaiser_window's arguments, or a float64 half window (then
     num_table = entries per zero crossing is required).  UNPINNED on resampy and librosa; held by tests/resample_reference.py.
     The handle is made without a device; the filter bank is uploaded by the first `resample`."""
+    _destroy = "taco_resample_destroy"
 
     def __init__(self, orig_sr, target_sr, filter="kaiser_best", num_table=None, device="cuda:0"):
         self.orig_sr, self.target_sr = int(orig_sr), int(target_sr)
@@ -516,34 +473,17 @@ class Resampler(object):
         (out [B, out_len(L)] float32, out_samples [B] int32), device tensors.  More than one channel is averaged (librosa.to_mono).
         Row b holds its computed_len(n_b) outputs, exact zeros after, and out_samples[b] = out_len(n_b)."""
         dev = self.device
-        x = wav if torch.is_tensor(wav) else torch.as_tensor(np.asarray(wav))
-        x = x.to(dev, torch.int16 if x.dtype == torch.int16 else torch.float32).contiguous()
+        x = _tensor(wav, dev, (torch.float32, torch.int16), "wav")
         channels = int(channels)
         if x.dim() == 3 and channels == 1:
             channels = int(x.shape[2])
         if x.dim() not in (2, 3) or (x.dim() == 3 and x.shape[2] != channels) or (x.dim() == 2 and x.shape[1] % max(channels, 1)):
             raise Exception("wav must be [B, L] or [B, L, channels = %d], got shape %s" % (channels, tuple(x.shape)))
         B, L = int(x.shape[0]), int(x.shape[1]) // (channels if x.dim() == 2 else 1)
-        ns = None if num_samples is None else (num_samples if torch.is_tensor(num_samples) else torch.as_tensor(np.asarray(num_samples))).to(dev, torch.int32).contiguous()
-        if ns is not None and tuple(ns.shape) != (B,):
-            raise Exception("num_samples must be [B] = [%d], got %s" % (B, tuple(ns.shape)))
+        ns = _lengths(num_samples, dev, B, "num_samples")
         L_out = self.out_len(L)
         out = torch.empty((B, L_out), dtype=torch.float32, device=dev)
         on = torch.empty((B,), dtype=torch.int32, device=dev)
         fmt = _lib.TACO_WAV_PCM16 if x.dtype == torch.int16 else _lib.TACO_WAV_F32
-        p = lambda t: C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)
-        with torch.cuda.device(dev):
-            _lib.check(self._lib.taco_wav_resample(self._h, C.c_void_p(torch.cuda.current_stream().cuda_stream), p(x), fmt, channels, p(ns), B, L,
-                                                   p(out), L_out, p(on)))
+        _call(dev, self._lib.taco_wav_resample, self._h, _STREAM, x, fmt, channels, ns, B, L, out, L_out, on)
         return out, on
-
-    def close(self):
-        if getattr(self, "_h", None):
-            self._lib.taco_resample_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass

@@ -81,8 +81,15 @@ __global__ void k_gl_wss(const float* w2, float* inv, int T, int n_fft, int hop)
   for (int t = t1; t >= 0 && p - t * hop < n_fft; --t) s += w2[p - t * hop];
   inv[p] = s > 1.17549435e-38f ? 1.0f / s : 1.0f;
 }
+// y[s] = v, and v again where np.pad mode="reflect" mirrors sample s of y[0 .. n) within `half` of either end (y[-k] = y[k],
+// y[n-1+k] = y[n-1-k], k = 1 .. half): the thread that owns a sample writes its reflections
+__device__ __forceinline__ void store_reflected(float* y, int s, int n, int half, float v) {
+  y[s] = v;
+  if (s >= 1 && s <= half) y[-s] = v;
+  if (s >= n - 1 - half && s <= n - 2) y[2 * (n - 1) - s] = v;
+}
 // overlap-add of the windowed frames Y [B, Tr, win] -> centre part of ypad [B, slot], and the reflect padding of n_fft/2 on both sides
-// (np.pad mode="reflect": y[-k] = y[k], y[L-1+k] = y[L-1-k], k = 1 .. n_fft/2), written by the thread that owns the mirrored sample.
+// (store_reflected).
 // An utterance that keeps fewer than T frames is written up to its own L = hop*(frames-1) samples and reflected there (what lies
 // beyond in its slot is read only by STFT frames whose magnitude is 0); it divides by the window sum-square of its own frames,
 // summed here from w2 alongside the samples, while one that keeps all T uses the table of k_gl_wss.
@@ -103,10 +110,7 @@ __global__ void k_gl_overlap_add(const float* Y, const float* wss_inv, const flo
     if (own) ws += w2[lpad + off];
   }
   const float v = acc * (own ? (ws > 1.17549435e-38f ? 1.0f / ws : 1.0f) : wss_inv[p]);
-  float* y = ypad + (size_t)b * slot + half;             // y[0 .. L)
-  y[s] = v;
-  if (s >= 1 && s <= half) y[-s] = v;
-  if (s >= L - 1 - half && s <= L - 2) y[2 * (L - 1) - s] = v;
+  store_reflected(ypad + (size_t)b * slot + half, s, L, half, v);      // y[0 .. L)
 }
 // scipy.signal.lfilter([1], [1, -a], x): out[n] = x[n] + a*out[n-1]; one workgroup per utterance, chunked scan.  The utterance's
 // own hop*(frames-1) samples are filtered, the rest of its row of L is zero; num_samples (nullable) receives that count.
@@ -302,30 +306,40 @@ __global__ __launch_bounds__(TRIM_THREADS) void k_trim_energy(const float* wav, 
                                                                     : s2 / (float)N;
   }
 }
+// The frame dB law of k_trim_index and k_split_edges, written once so that the two agree by construction (tests/test_gpu_split.py).
+// trim_db_ref: 10 log10(max(1e-10, max_t e[t])) over a row's nf energies, by a workgroup of 256 threads (four waves), the same
+// value in every thread; a maximum is the same in any order.
+__device__ __forceinline__ float trim_db_ref(const float* e, int nf) {
+  __shared__ float pmax[4];
+  const int tid = threadIdx.x;
+  float mx = 0.f;                                          // energies are >= 0
+  for (int t = tid; t < nf; t += 256) mx = fmaxf(mx, e[t]);
+  for (int o = 32; o > 0; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o));
+  if ((tid & 63) == 0) pmax[tid >> 6] = mx;
+  __syncthreads();
+  return 10.f * log10f(fmaxf(1e-10f, fmaxf(fmaxf(pmax[0], pmax[1]), fmaxf(pmax[2], pmax[3]))));
+}
+// One frame's dB below ref
+__device__ __forceinline__ float trim_db(float e, float ref) {
+#pragma clang fp contract(off)      // the product is rounded before the subtraction, as ref was: the loudest frame is exactly 0 dB
+  return 10.f * log10f(fmaxf(1e-10f, e)) - ref;
+}
 // logamplitude(ref_power=np.max) and the index: db[t] = 10 log10(max(1e-10, mse[t])) - 10 log10(max(1e-10, max_t mse)); a frame is
 // non-silent where db > -top_db; index[b] = {first*hop, min(n_b, (last + 1)*hop)}, {0, 0} when no frame is, {0, n_b} for a row of
 // fewer than two samples (it has no frames).  frame_db (nullable) receives db for the row's own frames and zeros after.  One
 // workgroup per row; a maximum and a minimum are the same in any order.
 __global__ __launch_bounds__(256) void k_trim_index(const float* mse, const int* num_samples, int L, int hop, int Fmax, float top_db,
                                                     int* index, float* frame_db) {
-#pragma clang fp contract(off)      // the product is rounded before the subtraction, as ref was: the loudest frame is exactly 0 dB
-  __shared__ float pmax[4];
   __shared__ int pfirst[4], plast[4];
   const int b = blockIdx.x, tid = threadIdx.x;
   const int n = trim_samples(num_samples, b, L), nf = n < 2 ? 0 : 1 + n / hop;
   const float* e = mse + (size_t)b * Fmax;
-  float mx = 0.f;                                          // energies are >= 0
-  for (int t = tid; t < nf; t += 256) mx = fmaxf(mx, e[t]);
-  for (int o = 32; o > 0; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o));
-  if ((tid & 63) == 0) pmax[tid >> 6] = mx;
-  __syncthreads();
-  mx = fmaxf(fmaxf(pmax[0], pmax[1]), fmaxf(pmax[2], pmax[3]));
-  const float ref = 10.f * log10f(fmaxf(1e-10f, mx));
+  const float ref = trim_db_ref(e, nf);
   int first = 0x7fffffff, last = -1;
   for (int t = tid; t < Fmax; t += 256) {
     float db = 0.f;
     if (t < nf) {
-      db = 10.f * log10f(fmaxf(1e-10f, e[t])) - ref;
+      db = trim_db(e[t], ref);
       if (db > -top_db) { first = min(first, t); last = max(last, t); }
     }
     if (frame_db) frame_db[(size_t)b * Fmax + t] = db;
@@ -344,8 +358,9 @@ __global__ __launch_bounds__(256) void k_trim_index(const float* mse, const int*
 
 // ---- splitting on silence: librosa.effects.split and remove_breath (audio/silence.py:21-31,44-45,53-54), restated; UNPINNED on librosa ----
 #define SPLIT_THREADS 256      // four waves: a chunk of k_split_edges is 256 frames
-// The maximal runs of non-silent frames of row b, in order, from the mse table k_trim_energy wrote.  db[t] is formed with exactly the
-// arithmetic of k_trim_index (contraction off, the same ref, non-silent where db > -top_db).  An EDGE is a frame t in [0, nf] whose
+static_assert(SPLIT_THREADS == 256, "trim_db_ref joins the maxima of four waves");
+// The maximal runs of non-silent frames of row b, in order, from the mse table k_trim_energy wrote.  db[t] is k_trim_index's: the same
+// trim_db_ref and trim_db, non-silent where db > -top_db.  An EDGE is a frame t in [0, nf] whose
 // state differs from frame t - 1's, with frames -1 and nf counted as silent: that is flatnonzero(diff(non_silent)) + 1 with the 0
 // prepended when frame 0 is non-silent and len(non_silent) appended when the last frame is.  Edge number k (even: a run starts, odd:
 // one ends) goes to word k of the row's table as min(n, t*hop) -- so run r is {s*hop, min(n, e*hop)}, and {n, n} when n % hop == 0
@@ -356,8 +371,6 @@ __global__ __launch_bounds__(256) void k_trim_index(const float* mse, const int*
 // per row; a row of fewer than two samples has no frames and count 0.
 __global__ __launch_bounds__(SPLIT_THREADS) void k_split_edges(const float* mse, const int* num_samples, int L, int hop, int Fmax, float top_db,
                                                                int max_intervals, int* intervals, int* counts, float* frame_db) {
-#pragma clang fp contract(off)      // as k_trim_index: the product is rounded before the subtraction
-  __shared__ float pmax[4];
   __shared__ unsigned long long wmask[4];
   __shared__ int wedges[4];
   const int b = blockIdx.x, tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
@@ -365,13 +378,7 @@ __global__ __launch_bounds__(SPLIT_THREADS) void k_split_edges(const float* mse,
   const float* e = mse + (size_t)b * Fmax;
   int* tab = intervals + (size_t)b * max_intervals * 2;
   const long long cap = 2LL * max_intervals;
-  float mx = 0.f;                                          // energies are >= 0
-  for (int t = tid; t < nf; t += SPLIT_THREADS) mx = fmaxf(mx, e[t]);
-  for (int o = 32; o > 0; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o));
-  if (lane == 0) pmax[wave] = mx;
-  __syncthreads();
-  mx = fmaxf(fmaxf(pmax[0], pmax[1]), fmaxf(pmax[2], pmax[3]));
-  const float ref = 10.f * log10f(fmaxf(1e-10f, mx));
+  const float ref = trim_db_ref(e, nf);
   const int last = max(nf, frame_db ? Fmax - 1 : 0);       // frames 0 .. last are visited: nf itself closes a run that reaches the end
   long long seen = 0;                                      // edges in the chunks before this one (the same in every thread)
   bool carry = false;                                      // the state of the last frame of the chunk before this one
@@ -380,7 +387,7 @@ __global__ __launch_bounds__(SPLIT_THREADS) void k_split_edges(const float* mse,
     float db = 0.f;
     bool loud = false;
     if (t < nf) {
-      db = 10.f * log10f(fmaxf(1e-10f, e[t])) - ref;
+      db = trim_db(e[t], ref);
       loud = db > -top_db;
     }
     if (frame_db && t < Fmax) frame_db[(size_t)b * Fmax + t] = db;
@@ -490,8 +497,8 @@ __device__ __forceinline__ int spec_samples(const int* num_samples, int b, int L
   return num_samples ? min(max(num_samples[b], half + 1), Lmax) : Lmax;
 }
 // Pre-emphasis p[i] = y[i] - a*y[i-1], y[-1] = 0 (scipy.signal.lfilter([1, -a], [1], y)) of wav [B, Lmax] into the centre of each
-// utterance's slot of ypad, and the reflect padding of n_fft/2 at the utterance's OWN ends, written by the thread that owns the
-// mirrored sample (as k_gl_overlap_add does).  Everything else of the slot -- and, behind the last slot, the slack the tail rows of
+// utterance's slot of ypad, and the reflect padding of n_fft/2 at the utterance's OWN ends (store_reflected,
+// as k_gl_overlap_add).  Everything else of the slot -- and, behind the last slot, the slack the tail rows of
 // the frame matrix read -- is zeroed, so no frame row reads another call's data.  nf_ws [B] and num_frames [B] (nullable) receive
 // 1 + n_b / hop.  grid (blocks of a slot, B).
 __global__ void k_spec_prepare(const float* wav, const int* num_samples, float* ypad, int* nf_ws, int* num_frames, int B, int Lmax, int hop,
@@ -505,10 +512,7 @@ __global__ void k_spec_prepare(const float* wav, const int* num_samples, float* 
   if (i < (size_t)n) {
     const int s = (int)i;
     const float* x = wav + (size_t)b * Lmax;
-    const float v = s ? x[s] - a * x[s - 1] : x[0];
-    y[s] = v;
-    if (s >= 1 && s <= half) y[-s] = v;
-    if (s >= n - 1 - half && s <= n - 2) y[2 * (n - 1) - s] = v;
+    store_reflected(y, s, n, half, s ? x[s] - a * x[s - 1] : x[0]);
   }
   if (i >= (size_t)n + 2 * half) y[(ptrdiff_t)i - half] = 0.f;
 }

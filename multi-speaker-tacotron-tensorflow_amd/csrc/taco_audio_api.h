@@ -1,4 +1,5 @@
 // taco_audio_api.h -- C ABI of the spectrogram -> waveform step and of the waveform -> training targets step; included inside extern "C".
+// Shared by the entry points: gl_iterate (the Griffin-Lim loop of both flavours), gl_carved_bytes, wav_frame_energies (trim and split).
 
 // The handle of either flavour.  GL_LIBROSA centres the window in n_fft (lpad = (n_fft - win) / 2: librosa pads the window, and the frame with
 // it); GL_TF leaves it at the start (lpad = 0: tf.contrib.signal.stft multiplies the win samples by the window and zero-pads at the END
@@ -79,13 +80,37 @@ int taco_gl_num_samples(const taco_gl* g, int T) { return (g && T > 0) ? g->hop 
 
 int taco_gl_min_frames(const taco_gl* g) { return g ? g->n_fft / 2 / g->hop + 2 : 0; }    // smallest T with hop*(T-1) > n_fft/2
 
-size_t taco_gl_workspace_bytes(const taco_gl* g, int B, int T) {
-  if (!g || B <= 0 || T <= 1) return 0;
-  Carver cv(nullptr, 0);
-  GlWs w; carve_gl(cv, g, B, T, w);
-  return cv.off;
-}
+// The Griffin-Lim workspace of either flavour (carve_gl); the exported sizes differ in the fewest frames they serve
+static size_t gl_carved_bytes(const taco_gl* g, int B, int T) { Carver cv(nullptr, 0); GlWs w; carve_gl(cv, g, B, T, w); return cv.off; }
+size_t taco_gl_workspace_bytes(const taco_gl* g, int B, int T) { return (!g || B <= 0 || T <= 1) ? 0 : gl_carved_bytes(g, B, T); }
 size_t taco_gl_rows_workspace_bytes(const taco_gl* g, int B, int T) { return taco_gl_workspace_bytes(g, B, T); }   // same slot layout
+
+// The Griffin-Lim iteration of either flavour, on a workspace whose S and X the flavour's prologue has filled: y = istft(X), then
+// `iters` times est = stft(y), X = project(est, S), y = istft(X).  The two matrix products are the same for both; overlap_add()
+// launches the flavour's overlap-add of the frames w.Y into w.ypad, `project` is its projection kernel.
+static int gl_iterate(taco_gl* g, hipStream_t st, const GlWs& w, size_t R, int iters, void (*project)(const float*, const float*, float*, size_t, int),
+                      const std::function<void()>& overlap_add) {
+  const int F = g->F;
+  auto synth = [&]() -> int {     // frames = X . IDFT_w (win columns), then the flavour's overlap-add
+    GemmCall c; c.x = w.X; c.ldx = 2 * F; c.M = (int)R; c.out = w.Y; c.ldo = g->win;
+    TRY(run_gemm(g->gm, st, &g->inv, 1, false, c));
+    overlap_add();
+    HIPCHK(hipGetLastError());
+    return 0;
+  };
+  TRY(synth());
+  for (int it = 0; it < iters; ++it) {
+    // est = stft(y): row (b, t) of the frame matrix is the hop-strided window ypad[b*slot + t*hop + lpad ...][0 .. win) (lpad = 0 on a TF
+    // handle: pad_end=False, the utterance's hop*(f-1) + win samples hold exactly f frames); rows past an utterance's own frames read
+    // whatever its slot holds there and are multiplied by S = 0 in the projection
+    GemmCall c; c.x = w.ypad + g->lpad; c.ldx = g->hop; c.M = (int)R; c.out = w.est; c.ldo = 2 * F;
+    TRY(run_gemm(g->gm, st, &g->fwd, 1, false, c));
+    hipLaunchKernelGGL(project, EWGRID(R * F), 0, st, w.est, w.S, w.X, R, F);
+    HIPCHK(hipGetLastError());
+    TRY(synth());
+  }
+  return 0;
+}
 
 // The librosa-flavour vocoder behind taco_gl_inv_spectrogram_rows (d_mel NULL: magnitudes from d_spec by k_gl_magnitude) and
 // taco_gl_inv_melspectrogram_rows (d_mel: by k_gl_mel_magnitude); everything after the magnitudes is shared.
@@ -117,24 +142,11 @@ static int gl_vocode_rows(taco_gl* g, void* hip_stream, const float* d_spec, con
                        g->hp.power);
   hipLaunchKernelGGL(k_gl_init_phase, EWGRID(R * F), 0, st, w.S, d_init_uniform, seed, w.X, d_frames, fmin, B, T, Tr, F);
   HIPCHK(hipGetLastError());
-  auto synth = [&]() -> int {     // y = istft(X): frames = X . IDFT_w ; overlap-add / window sum-square with the reflect pad for the next stft
-    GemmCall c; c.x = w.X; c.ldx = 2 * F; c.M = (int)R; c.out = w.Y; c.ldo = g->win;
-    TRY(run_gemm(g->gm, st, &g->inv, 1, false, c));
+  // y = istft(X): overlap-add / window sum-square with the reflect pad for the next stft
+  TRY(gl_iterate(g, st, w, R, iters, k_gl_project, [&] {
     hipLaunchKernelGGL(k_gl_overlap_add, dim3((L + 255) / 256, B), dim3(256), 0, st, w.Y, w.wss, AP(g->gm, g->w2), w.ypad, d_frames, fmin, T, Tr,
                        g->win, g->hop, g->lpad, g->n_fft, slot);
-    HIPCHK(hipGetLastError());
-    return 0;
-  };
-  TRY(synth());
-  for (int it = 0; it < iters; ++it) {
-    // est = stft(y): row (b, t) of the frame matrix is the hop-strided window ypad[b*slot + t*hop + lpad ...][0 .. win); rows past an
-    // utterance's own frames read whatever its slot holds there and are multiplied by S = 0 in k_gl_project
-    GemmCall c; c.x = w.ypad + g->lpad; c.ldx = g->hop; c.M = (int)R; c.out = w.est; c.ldo = 2 * F;
-    TRY(run_gemm(g->gm, st, &g->fwd, 1, false, c));
-    hipLaunchKernelGGL(k_gl_project, EWGRID(R * F), 0, st, w.est, w.S, w.X, R, F);
-    HIPCHK(hipGetLastError());
-    TRY(synth());
-  }
+  }));
   hipLaunchKernelGGL(k_inv_preemphasis, dim3(B), dim3(1024), 0, st, w.ypad, d_wav, d_frames, fmin, T, g->hop, d_num_samples, L, half, slot,
                      g->hp.preemphasis);
   HIPCHK(hipGetLastError());
@@ -197,12 +209,8 @@ int taco_gl_inv_melspectrogram_rows(taco_gl* g, void* hip_stream, const float* d
 // ---- inv_spectrogram_tensorflow (audio/__init__.py:59-61,87-96,109-116,152-153,167-168; synthesizer.py:53-54) ----
 int taco_gl_tf_num_samples(const taco_gl* g, int T) { return (g && T > 0) ? g->hop * (T - 1) + g->win : 0; }
 
-size_t taco_gl_tf_workspace_bytes(const taco_gl* g, int B, int T) {      // the slot layout of the librosa flavour, without its wss table in use
-  if (!g || B <= 0 || T <= 0) return 0;
-  Carver cv(nullptr, 0);
-  GlWs w; carve_gl(cv, g, B, T, w);
-  return cv.off;
-}
+// (the slot layout of the librosa flavour, without its wss table in use)
+size_t taco_gl_tf_workspace_bytes(const taco_gl* g, int B, int T) { return (!g || B <= 0 || T <= 0) ? 0 : gl_carved_bytes(g, B, T); }
 
 int taco_gl_inv_spectrogram_tf(taco_gl* g, void* hip_stream, const float* d_spec, const int32_t* d_frames, int B, int T, int iters, float* d_wav,
                                int32_t* d_num_samples, void* d_workspace, size_t workspace_bytes) {
@@ -225,22 +233,10 @@ int taco_gl_inv_spectrogram_tf(taco_gl* g, void* hip_stream, const float* d_spec
                      g->hp.power);
   hipLaunchKernelGGL(k_gl_init_phase, EWGRID(R * F), 0, st, w.S, w.est, 0ull, w.X, d_frames, 1, B, T, Tr, F);
   HIPCHK(hipGetLastError());
-  auto synth = [&]() -> int {     // y = inverse_stft(X): frames = X . IDFT_w (win columns), plain overlap-add to the start of each slot
-    GemmCall c; c.x = w.X; c.ldx = 2 * F; c.M = (int)R; c.out = w.Y; c.ldo = g->win;
-    TRY(run_gemm(g->gm, st, &g->inv, 1, false, c));
+  // y = inverse_stft(X): plain overlap-add to the start of each slot
+  TRY(gl_iterate(g, st, w, R, iters, k_gl_project_tf, [&] {
     hipLaunchKernelGGL(k_gl_overlap_add_tf, dim3((L + 255) / 256, B), dim3(256), 0, st, w.Y, w.ypad, d_frames, T, Tr, g->win, g->hop, slot);
-    HIPCHK(hipGetLastError());
-    return 0;
-  };
-  TRY(synth());
-  for (int it = 0; it < iters; ++it) {
-    // est = stft(y), pad_end=False: row (b, t) is ypad[b*slot + t*hop ...][0 .. win); the utterance's hop*(f-1) + win samples hold exactly f frames
-    GemmCall c; c.x = w.ypad; c.ldx = g->hop; c.M = (int)R; c.out = w.est; c.ldo = 2 * F;
-    TRY(run_gemm(g->gm, st, &g->fwd, 1, false, c));
-    hipLaunchKernelGGL(k_gl_project_tf, EWGRID(R * F), 0, st, w.est, w.S, w.X, R, F);
-    HIPCHK(hipGetLastError());
-    TRY(synth());
-  }
+  }));
   hipLaunchKernelGGL(k_gl_output_tf, dim3((L + 255) / 256, B), dim3(256), 0, st, w.ypad, d_wav, d_frames, T, g->win, g->hop, d_num_samples, L, slot);
   HIPCHK(hipGetLastError());
   return 0;
@@ -262,10 +258,15 @@ size_t taco_wav_trim_workspace_bytes(int B, int L, int frame_length, int hop_len
   return cv.off;
 }
 
-int taco_wav_trim(void* hip_stream, const float* d_wav, const int32_t* d_num_samples, int B, int L, float top_db, int frame_length,
-                  int hop_length, int energy, int32_t* d_index, float* d_frame_db, void* d_workspace, size_t workspace_bytes) {
-  if (!d_wav || !d_index || !d_workspace || B <= 0 || B > 65535 || L <= 0) return fail(TACO_ERR_ARG, "bad argument");
+// The front of taco_wav_trim and taco_wav_split: their shared argument checks in one order, then the frame energies mse [B, Fmax]
+// into the workspace (k_trim_energy).  outputs: the entry point's own result pointers are all there; max_intervals: taco_wav_split's
+// table rows, checked where it always was (NULL: taco_wav_trim has none).
+static int wav_frame_energies(hipStream_t st, const float* d_wav, const int32_t* d_num_samples, bool outputs, int B, int L, int frame_length,
+                              int hop_length, int energy, const int* max_intervals, void* d_workspace, size_t workspace_bytes, float** mse,
+                              int* Fmax) {
+  if (!d_wav || !outputs || !d_workspace || B <= 0 || B > 65535 || L <= 0) return fail(TACO_ERR_ARG, "bad argument");
   if (hop_length < 1 || frame_length < 2) return fail(TACO_ERR_ARG, "bad frame parameters: frame_length %d, hop_length %d", frame_length, hop_length);
+  if (max_intervals && *max_intervals < 1) return fail(TACO_ERR_ARG, "max_intervals = %d", *max_intervals);
   if (energy != TACO_TRIM_SPECTRAL && energy != TACO_TRIM_TIME) return fail(TACO_ERR_ARG, "unknown energy convention %d", energy);
   const size_t need = taco_wav_trim_workspace_bytes(B, L, frame_length, hop_length);
   if (workspace_bytes < need) return fail(TACO_ERR_ARG, "workspace too small: need %zu bytes, have %zu", need, workspace_bytes);
@@ -274,11 +275,18 @@ int taco_wav_trim(void* hip_stream, const float* d_wav, const int32_t* d_num_sam
   if (fpt < 1)
     return fail(TACO_ERR_UNSUPPORTED, "frame_length = %d: k_trim_energy keeps a frame%s in %d KB of LDS", frame_length,
                 energy == TACO_TRIM_SPECTRAL ? " and its window" : "", TRIM_LDS_BYTES / 1024);
+  *Fmax = 1 + L / hop_length;
+  *mse = (float*)d_workspace;
+  hipLaunchKernelGGL(k_trim_energy, dim3(cdiv(*Fmax, fpt), B), dim3(TRIM_THREADS), trim_lds_bytes(frame_length, hop_length, fpt, energy), st, d_wav,
+                     d_num_samples, L, frame_length, hop_length, fpt, *Fmax, energy, *mse);
+  return 0;
+}
+
+int taco_wav_trim(void* hip_stream, const float* d_wav, const int32_t* d_num_samples, int B, int L, float top_db, int frame_length,
+                  int hop_length, int energy, int32_t* d_index, float* d_frame_db, void* d_workspace, size_t workspace_bytes) {
   hipStream_t st = (hipStream_t)hip_stream;
-  const int Fmax = 1 + L / hop_length;
-  float* mse = (float*)d_workspace;
-  hipLaunchKernelGGL(k_trim_energy, dim3(cdiv(Fmax, fpt), B), dim3(TRIM_THREADS), trim_lds_bytes(frame_length, hop_length, fpt, energy), st, d_wav,
-                     d_num_samples, L, frame_length, hop_length, fpt, Fmax, energy, mse);
+  float* mse; int Fmax;
+  TRY(wav_frame_energies(st, d_wav, d_num_samples, d_index, B, L, frame_length, hop_length, energy, nullptr, d_workspace, workspace_bytes, &mse, &Fmax));
   hipLaunchKernelGGL(k_trim_index, dim3(B), dim3(256), 0, st, mse, d_num_samples, L, hop_length, Fmax, top_db, d_index, d_frame_db);
   HIPCHK(hipGetLastError());
   return 0;
@@ -292,22 +300,10 @@ size_t taco_wav_split_workspace_bytes(int B, int L, int frame_length, int hop_le
 int taco_wav_split(void* hip_stream, const float* d_wav, const int32_t* d_num_samples, int B, int L, float top_db, int frame_length,
                    int hop_length, int energy, int max_intervals, int32_t* d_intervals, int32_t* d_counts, float* d_frame_db, void* d_workspace,
                    size_t workspace_bytes) {
-  if (!d_wav || !d_intervals || !d_counts || !d_workspace || B <= 0 || B > 65535 || L <= 0) return fail(TACO_ERR_ARG, "bad argument");
-  if (hop_length < 1 || frame_length < 2) return fail(TACO_ERR_ARG, "bad frame parameters: frame_length %d, hop_length %d", frame_length, hop_length);
-  if (max_intervals < 1) return fail(TACO_ERR_ARG, "max_intervals = %d", max_intervals);
-  if (energy != TACO_TRIM_SPECTRAL && energy != TACO_TRIM_TIME) return fail(TACO_ERR_ARG, "unknown energy convention %d", energy);
-  const size_t need = taco_wav_split_workspace_bytes(B, L, frame_length, hop_length);
-  if (workspace_bytes < need) return fail(TACO_ERR_ARG, "workspace too small: need %zu bytes, have %zu", need, workspace_bytes);
-  if (frame_length & 1) return fail(TACO_ERR_UNSUPPORTED, "frame_length = %d: the one-sided spectrum sum is written for an even length", frame_length);
-  const int fpt = trim_frames_per_tile(frame_length, hop_length, energy);
-  if (fpt < 1)
-    return fail(TACO_ERR_UNSUPPORTED, "frame_length = %d: k_trim_energy keeps a frame%s in %d KB of LDS", frame_length,
-                energy == TACO_TRIM_SPECTRAL ? " and its window" : "", TRIM_LDS_BYTES / 1024);
   hipStream_t st = (hipStream_t)hip_stream;
-  const int Fmax = 1 + L / hop_length;
-  float* mse = (float*)d_workspace;
-  hipLaunchKernelGGL(k_trim_energy, dim3(cdiv(Fmax, fpt), B), dim3(TRIM_THREADS), trim_lds_bytes(frame_length, hop_length, fpt, energy), st, d_wav,
-                     d_num_samples, L, frame_length, hop_length, fpt, Fmax, energy, mse);
+  float* mse; int Fmax;
+  TRY(wav_frame_energies(st, d_wav, d_num_samples, d_intervals && d_counts, B, L, frame_length, hop_length, energy, &max_intervals, d_workspace,
+                         workspace_bytes, &mse, &Fmax));
   hipLaunchKernelGGL(k_split_edges, dim3(B), dim3(SPLIT_THREADS), 0, st, mse, d_num_samples, L, hop_length, Fmax, top_db, max_intervals, d_intervals,
                      d_counts, d_frame_db);
   HIPCHK(hipGetLastError());

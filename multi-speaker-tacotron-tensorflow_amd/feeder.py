@@ -266,6 +266,23 @@ def waveform_length(t_out, hop):
     return (int(t_out) - 1) * int(hop)
 
 
+def collate_streams(device, streams, index, n_rows, n_items):
+    """ONE taco_collate launch on the device's current stream: row i of every stream's `out` (and entry i of its `counts`) is item
+    index[i] (device int32 [n_rows]) of the n_items its `pack` holds.  A stream is a dict of TacoCollateStream's fields (include/taco_abi.h):
+    pack, start, rows, out, counts are device tensors or None, width and rows_out ints."""
+    import ctypes as C
+    import torch
+    from . import _lib
+    ptr = lambda t: None if t is None else t.data_ptr()
+    arr = (_lib.TacoCollateStream * len(streams))()
+    for a, d in zip(arr, streams):
+        a.pack, a.start, a.rows, a.out, a.counts = ptr(d["pack"]), ptr(d["start"]), ptr(d["rows"]), ptr(d["out"]), ptr(d["counts"])
+        a.width, a.rows_out = d["width"], d["rows_out"]
+    with torch.cuda.device(device):
+        _lib.check(_lib.load_library().taco_collate(C.c_void_p(torch.cuda.current_stream().cuda_stream), arr, len(streams),
+                                                    C.c_void_p(index.data_ptr()), n_rows, n_items))
+
+
 class RefSource(object):
     """NpzSource's draw sequence over the Refs of a DeviceCorpus: the cursor starts at the third item, wraps to 0 and -- for training
     data -- reshuffles the list with the shared generator (the same number of draws as shuffling the path list); an item the corpus
@@ -481,9 +498,7 @@ class DeviceCorpus(object):
         (uploaded, 4 * B bytes) or a device int32 tensor, which the host cannot see: the shapes then come from `out` or, without it,
         from the corpus-wide maxima, and an index outside the corpus gives an all-zero row.  out: a Batch of preallocated contiguous
         tensors of the right shapes, written in place (nothing is allocated)."""
-        import ctypes as C
         import torch
-        from . import _lib
         if not self._on_device:
             raise Exception("call finalize() first")
         r, p = int(reduction_factor), self._packs
@@ -521,7 +536,6 @@ class DeviceCorpus(object):
                 t = getattr(out, k)
                 if not (torch.is_tensor(t) and t.is_cuda and tuple(t.shape) == s and t.dtype == dt and t.is_contiguous()):
                     raise Exception("out.%s must be a contiguous %s device tensor of shape %s" % (k, dt, s))
-        ptr = lambda t: None if t is None else t.data_ptr()
         st = [dict(pack=p["tok_pack"], start=p["tok_start"], rows=p["tok_rows"], width=1, rows_out=t_in, out=out.inputs, counts=out.input_lengths),
               dict(pack=p["coeff"], start=None, rows=None, width=1, rows_out=1, out=out.loss_coeff, counts=None)]
         if spk:
@@ -537,13 +551,7 @@ class DeviceCorpus(object):
             wav = self._buffer("wav", (B, lmax), torch.float32)
             ns = self._buffer("num_samples", (B,), torch.int32)
             st.append(dict(pack=p["wav_pack"], start=p["wav_start"], rows=p["wav_rows"], width=1, rows_out=lmax, out=wav, counts=ns))
-        arr = (_lib.TacoCollateStream * len(st))()
-        for a, d in zip(arr, st):
-            a.pack, a.start, a.rows, a.out, a.counts = ptr(d["pack"]), ptr(d["start"]), ptr(d["rows"]), ptr(d["out"]), ptr(d["counts"])
-            a.width, a.rows_out = d["width"], d["rows_out"]
-        lib = _lib.load_library()
-        with torch.cuda.device(self._dev):
-            _lib.check(lib.taco_collate(C.c_void_p(torch.cuda.current_stream().cuda_stream), arr, len(st), C.c_void_p(idx.data_ptr()), B, len(self)))
+        collate_streams(self._dev, st, idx, B, len(self))
         if self.kind == "waveform":
             nf = self._buffer("num_frames", (B,), torch.int32)
             self._spec.targets(wav, ns, out=(out.linear_targets, out.mel_targets, nf))

@@ -9,11 +9,9 @@ taco_collate (the intervals gathered into padded rectangles) and taco_wav_breath
 corpus preparation, and it needs them to name the segments -- and the finished recording.  UNPINNED on librosa, as the trim is
 (include/taco_abi.h): held by tests/split_reference.py, not by librosa.  The pydub method (:81-117) and decoding audio files stay
 outside."""
-import ctypes as C
-
 import numpy as np
 
-from . import _lib
+from .feeder import collate_streams
 
 RECT_WORDS = 1 << 26      # a rectangle of intervals holds at most this many samples (256 MB), however many rows chunk_rows allows
 
@@ -74,7 +72,6 @@ class SilenceDevice(object):
         import torch
         dev = self.gl.device
         new = torch.zeros_like(x)
-        lib = self.gl._lib
         for k, rows, longest in self.chunks(edges):
             e = np.asarray(edges[k:k + rows], np.int64)
             start = torch.as_tensor(np.ascontiguousarray(e[:, 0])).to(dev)
@@ -82,11 +79,7 @@ class SilenceDevice(object):
             index = torch.arange(rows, dtype=torch.int32, device=dev)
             rect = torch.empty((rows, longest), dtype=torch.float32, device=dev)
             ns = torch.empty((rows,), dtype=torch.int32, device=dev)
-            st = (_lib.TacoCollateStream * 1)()
-            st[0].pack, st[0].start, st[0].rows, st[0].out, st[0].counts = x.data_ptr(), start.data_ptr(), length.data_ptr(), rect.data_ptr(), ns.data_ptr()
-            st[0].width, st[0].rows_out = 1, longest
-            with torch.cuda.device(dev):
-                _lib.check(lib.taco_collate(C.c_void_p(torch.cuda.current_stream().cuda_stream), st, 1, C.c_void_p(index.data_ptr()), rows, rows))
+            collate_streams(dev, [dict(pack=x, start=start, rows=length, width=1, rows_out=longest, out=rect, counts=ns)], index, rows, rows)
             out = self.gl.remove_breath(rect, ns)
             for j, (a, b) in enumerate(e.tolist()):
                 new[0, a:b] = out[j, :b - a]

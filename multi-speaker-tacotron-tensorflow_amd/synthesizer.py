@@ -181,7 +181,7 @@ class Synthesizer(object):
             wav, num_samples = gl.inv_spectrogram_tensorflow(linear, frames, iters=iters)
         elif vocoder == "mel":
             gl = self._griffin_lim()
-            if not gl._inv_mels:
+            if not gl.inv_mels:
                 gl.set_inv_mel_basis()
             mel = self.model.mel_outputs                       # [N, steps, r * num_mels] or [N, frames, num_mels]: the same memory
             mel = mel.reshape(mel.shape[0], -1, self.hparams.num_mels)

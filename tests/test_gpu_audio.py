@@ -109,3 +109,63 @@ def test_synthesizer_vocode_surface(tmp_path):
     assert len(s.wavs) == 2 and all(w.ndim == 1 and np.isfinite(w).all() and len(w) > 0 for w in s.wavs)
     assert len(s.wavs[0]) == 20 * max(int(s.spec_end_idx[0]) - 1, 1)
     s.close()
+
+
+# ---- the one marshalling layer of audio.py, through every public method that takes device data ----
+_LIN, _MEL, _WAV = ("linear", (2, 8, 65)), ("mel", (2, 8, 12)), ("wav", (2, 140))
+_METHODS = [      # handle, method, (its main argument, a good shape), its [B] vector
+    ("gl", "inv_spectrogram", _LIN, None), ("gl", "inv_spectrogram_rows", _LIN, "frames"), ("tf", "inv_spectrogram_tensorflow", _LIN, "frames"),
+    ("gl", "mel_to_linear", _MEL, None), ("gl", "inv_melspectrogram", _MEL, "frames"), ("gl", "pcm16", _WAV, "num_samples"),
+    ("gl", "trim", _WAV, "num_samples"), ("gl", "split", _WAV, "num_samples"), ("gl", "remove_breath", _WAV, "num_samples"),
+    ("sp", "targets", _WAV, "num_samples"), ("rs", "resample", _WAV, "num_samples")]
+_BAD = [(h, m, a, v, kind) for h, m, a, v in _METHODS for kind in ("rank", "last", "vector", "init_uniform")
+        if (kind != "last" or len(a[1]) == 3 or m == "resample") and (kind != "vector" or v)
+        and (kind != "init_uniform" or m in ("inv_spectrogram", "inv_spectrogram_rows", "inv_melspectrogram"))]
+
+
+@pytest.fixture(scope="module")
+def handles():
+    import taco_amd
+    hp = _HP(A.AudioHParams(num_freq=65, sample_rate=1600, frame_length_ms=50, frame_shift_ms=12.5, griffin_lim_iters=2))
+    hp.num_mels = 12
+    h = {"gl": taco_amd.GriffinLim(hp), "tf": taco_amd.GriffinLim(hp, flavor="tensorflow"), "sp": taco_amd.Spectrogram(hp),
+         "rs": taco_amd.audio.Resampler(3, 2)}
+    h["gl"].set_inv_mel_basis()
+    assert h["gl"].inv_mels == 12 and h["tf"].inv_mels == 0 and h["gl"].min_frames() == 5
+    yield h
+    for x in h.values():
+        x.close()
+
+
+@pytest.mark.parametrize("handle,method,arg,vector,kind", _BAD, ids=["%s-%s" % (m, k) for _, m, _, _, k in _BAD])
+def test_every_method_refuses_a_bad_shape_by_the_arguments_name(handles, handle, method, arg, vector, kind):
+    """A wrong rank, a wrong last dimension (where the method fixes one; for resample: a row that is no whole number of channels), a
+    [B + 1] length vector and a narrower init_uniform each raise a plain Exception -- not TacoError: the library is never called --
+    whose message names the argument."""
+    import taco_amd
+    name, shape = arg
+    x, kw, blamed = np.zeros(shape, np.float32), {}, name
+    if kind == "rank":
+        x = x[0]
+    elif kind == "last" and method == "resample":
+        x, kw = x[:, :7], {"channels": 2}
+    elif kind == "last":
+        x = np.zeros(shape[:2] + (shape[2] + 1,), np.float32)
+    elif kind == "vector":
+        kw, blamed = {vector: [5] * (shape[0] + 1)}, vector
+    else:
+        kw, blamed = {"init_uniform": np.zeros((2, 8, 64), np.float32)}, "init_uniform"
+    if method == "inv_spectrogram_rows":
+        kw.setdefault("frames", None)
+    with pytest.raises(Exception) as e:
+        getattr(handles[handle], method)(x, **kw)
+    print("%s %s: %s" % (method, kind, e.value))
+    assert not isinstance(e.value, taco_amd._lib.TacoError) and blamed in str(e.value), (type(e.value), str(e.value))
+
+
+@pytest.mark.parametrize("method", ["trim", "split", "remove_breath"])
+def test_an_unknown_energy_is_an_argument_error(handles, method):
+    import taco_amd
+    with pytest.raises(taco_amd._lib.TacoError) as e:
+        getattr(handles["gl"], method)(np.zeros((2, 140), np.float32), energy="loud")
+    assert e.value.code == taco_amd._lib.TACO_ERR_ARG and "energy" in str(e.value)

@@ -100,6 +100,22 @@ def test_full_length_rows_are_the_old_entry_point():
     gl.close()
 
 
+def test_the_batch_entry_point_is_the_rows_entry_point_without_frames():
+    """inv_spectrogram is inv_spectrogram_rows(x, None, ...)[0]: the same bits, and a full-length frames vector reports hop*(T-1)."""
+    import torch, taco_amd
+    rs = np.random.RandomState(8)
+    B, T = 2, 8
+    spec, u = rs.rand(B, T, 65) * 1.2 - 0.1, rs.rand(B, T, 65)
+    gl = taco_amd.GriffinLim(_HP(_small()))
+    assert gl.min_frames() == 5
+    old = gl.inv_spectrogram(spec, u, iters=2).cpu().numpy()
+    assert old.shape == (B, 140) and np.isfinite(old).all() and np.abs(old).max() > 0
+    assert np.array_equal(gl.inv_spectrogram_rows(spec, None, u, iters=2)[0].cpu().numpy().view(np.uint32), old.view(np.uint32))
+    wav, ns = gl.inv_spectrogram_rows(spec, [8, 8], u, iters=2)
+    assert ns.cpu().numpy().tolist() == [140, 140] and np.array_equal(wav.cpu().numpy().view(np.uint32), old.view(np.uint32))
+    gl.close()
+
+
 def test_frames_are_clamped_and_short_batches_refused():
     import torch, taco_amd
     ahp = _small()

@@ -104,6 +104,24 @@ def test_ragged_rows_intervals_equal_the_restatement(gl, N, hop, energy):
     assert counts[5] == 0 and counts[0] > 1
 
 
+@pytest.mark.parametrize("energy", R.ENERGIES)
+@pytest.mark.parametrize("N,hop", PARAMS)
+def test_trim_and_split_return_the_same_frame_db_bits(gl, N, hop, energy):
+    """k_trim_index and k_split_edges form a frame's dB with the same device functions, so the two tables are equal as bits, and the
+    loudest frame of every row that has frames (two samples or more) is exactly 0 dB (the product is rounded before the subtraction)."""
+    w, ns = _device_rows()
+    _, tdb = gl.trim(w, ns, top_db=TOP_DB, frame_length=N, hop_length=hop, energy=energy, return_db=True)
+    _, _, sdb = gl.split(w, ns, top_db=TOP_DB, frame_length=N, hop_length=hop, energy=energy, return_db=True)
+    tdb, sdb = tdb.cpu().numpy(), sdb.cpu().numpy()
+    assert tdb.shape == sdb.shape == (6, 1 + L // hop) and np.isfinite(tdb).all()
+    assert np.array_equal(tdb.view(np.uint32), sdb.view(np.uint32))
+    for b, n in enumerate(LENGTHS):
+        nf = 1 + n // hop if n >= 2 else 0
+        assert np.all(tdb[b, nf:] == 0.0)
+        if nf:
+            assert tdb[b, :nf].max() == 0.0 and sdb[b, :nf].max() == 0.0, (b, tdb[b, :nf].max(), sdb[b, :nf].max())
+
+
 def test_overflow_keeps_the_counts_and_writes_only_zeros_past_the_first_two(gl):
     """max_intervals = 2 on the 16/2 input, through the library into a table with a sentinel on both sides of it."""
     import torch
