@@ -457,7 +457,7 @@ taco_model* taco_train_model(taco_train* t);
 int taco_train_set_deterministic(taco_train* t, int on);
 /* Weight gradients: on = 0 (default) computes dW = X^T . dY on the bf16 matrix cores with operands split three ways (24 bits) and
  * six products per tile, fp32 accumulation (k_wgrad_bf3: fp32-grade, ~2^-24 per product); on = 1 keeps them on the
- * exact-fp32 MFMA (k_wgrad, round 1).  Process-wide A/B and test hook. */
+ * exact-fp32 MFMA (k_wgrad, round 1).  Per trainer (as every taco_train_set_* switch): A/B and test hook. */
 int taco_train_set_exact_wgrad(taco_train* t, int on);
 /* Split-bf16 weight gradients from PRE-SPLIT operands (csrc/taco_wgrad_planes.h): mode 1 (default) converts the operands of the large
  * problems -- a whole conv bank, proj_1, the linear head -- once into bf16 planes and multiplies them with a kernel that converts

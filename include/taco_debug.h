@@ -107,6 +107,18 @@ int taco_train_debug_bigru(taco_train* t, void* hip_stream, const float* d_xproj
                            const float* d_dout, int B, int T, int persistent, float* d_out, float* d_gsave, float* d_dg, float* d_rh,
                            float* d_dh0, void* d_scratch, size_t scratch_bytes);
 
+/* Test hook: which kernel the training step gives a weight gradient, and how it slices the rows -- wgrad_plan / wgrad_bank_plan of
+ * csrc/taco_train.h, pure host functions: no handle, no device.  Inputs: the trainer's switches (wgrad_bf3: 0 = exact-fp32 weight
+ * gradients are on; wgrad_planes: the mode of taco_train_set_wgrad_planes), whether the deterministic scratch exists and its floats, the
+ * plane scratch in 16-byte units (0: none), whether a batching region is open, and the problem: dW [kw][K][N] summed over M rows (T per
+ * batch row, 0: no time axis), left padding padl, whether x / dy rows are gathered.  nw > 0 asks for a whole conv bank instead: widths
+ * 1 .. nw of N channels each over a K-wide input (kw, padl, ygather unused).
+ * out8: [0] engine (0 cannot run / bank not eligible, 1 pre-split planes, 2 k_wgrad_bf3<4>, 3 k_wgrad_bf3<1> alone, 4 k_wgrad_bf3<1> in the
+ * group launch, 5 k_wgrad), [1] rows per slice, [2] slices, [3] planes: x carries the tap copies, [4] planes: padded rows, [5] [6] planes:
+ * 16-byte units of the x / dy plane sets, [7] 1 = cannot run (the step fails with TACO_ERR_STATE). */
+int taco_debug_wgrad_plan(int wgrad_bf3, int wgrad_planes, int deterministic, long long det_floats, long long planes_uint4, int region_open,
+                          int M, int T, int K, int N, int kw, int padl, int gather, int ygather, int nw, int* out8);
+
 /* Test hook: k_spec_targets (the fused back end of taco_spec_targets: magnitude -> dB -> normalise, mel projection) alone on a
  * caller-supplied d_est [R, 2*num_freq] (Re | Im of R frames) -> d_linear [R, num_freq], d_mel [R, num_mels] (nullable).  Lets the
  * dB / normalise arithmetic be held against the reference's own recorded outputs, and the kernel be timed alone. */

@@ -40,7 +40,7 @@ struct taco_train {
   size_t NP = 0, arena_n = 0;
   float* d_map = nullptr;              // index map of the arena
   size_t n_bf3 = 0; int n_bf3_segs = 0; bool want_bf3_planes = false; bool bf3_current = false;   // planes regenerated from the current parameters by the last refresh?
-  int wgrad_bf3 = 1, dgrad_bf3 = 0, dgrad_exact = 0;   // engine switches of THIS trainer (taco_train_set_exact_wgrad / _gemm); a step installs them in the thread-local g_* the helpers read
+  int wgrad_bf3 = 1, dgrad_bf3 = 0, dgrad_exact = 0;   // engine switches of THIS trainer (taco_train_set_exact_wgrad / _gemm): run_wgrad / run_dgrad read them through the step's TrainCtx
   unsigned* d_bf3_idx = nullptr; Bf3Seg* d_bf3_segs = nullptr;   // index list and segment table of the split-bf16 packs (k_bf3_gather)
   float* d_fold = nullptr;             // [Z + 1, 3H] concat projection folded into decoder GRU 1 (k_dx_fold), the index map's second source
   // synchronised BatchNorm over the data-parallel group: the host sums a device vector in place over all ranks
@@ -50,7 +50,7 @@ struct taco_train {
   int sync_world = 1;
   int resident_bwd_scan = 1;           // the encoder's backward scan with the recurrent kernels in registers (k_bigru_resb); 0 (with taco_train_set_bptt_engine(t, 0)): k_bigru_rows_bwd
   int bptt_persistent = 1;             // taco_train_set_bptt_engine: the decoder's BPTT as one persistent launch (k_decoder_bwd_xcd) where it fits
-  mutable int planes_problems = 0;     // weight gradients of the last backward pass that were computed from pre-split planes (a conv bank counts once)
+  int planes_problems = 0;     // weight gradients of the last backward pass that were computed from pre-split planes (a conv bank counts once)
   int wgrad_planes = 1;                // taco_train_set_wgrad_planes: 1 = large weight gradients from pre-split bf16 planes (taco_wgrad_planes.h), 2 = every eligible one (tests), 0 = off
   int deterministic = 1;               // taco_train_set_deterministic: ordered two-stage sums (default since round 4) or fp32 atomics; the former needs DET_SCRATCH_FLOATS of workspace
 };
@@ -190,247 +190,254 @@ static int build_train_packs(taco_model* m) {
 // ---------------------------------------------------------------------------------------------------------------
 #define EWGRID(n) dim3((unsigned)(((size_t)(n) + 255) / 256)), dim3(256)
 static inline bool al16h(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }      // may a matrix be read four columns at a time (the _v4 kernels)
-// Deterministic reductions (taco_train_set_deterministic): the sums over rows that normally leave their workgroups through fp32
-// atomics (weight gradients, bias / BatchNorm sums, embedding gradients, d attention_v) are written as per-slice partials into this
-// scratch and added up in a fixed order by a second launch -- the step becomes run-to-run reproducible, as the reference's
-// single-device step is.  Scratch of the step in flight; thread-local because the launch helpers below have no context argument
-// (one step per host thread at a time: the library's threading contract).
-struct DetScratch { float* p = nullptr; size_t cap = 0; };
-static thread_local DetScratch g_det;
-// Batching region for small weight gradients (k_wgrad_bf3_group): between wg_begin and wg_end, run_wgrad calls that take the one-wave
-// tile are collected and launched together -- at wg_flush / wg_end, or when the table is full.  The caller flushes before anything
-// overwrites an operand of a collected problem or reads one of their outputs.
+// Batching region for small weight gradients (k_wgrad_bf3_group): while a WgRegion is open, run_wgrad calls that take the one-wave
+// tile are collected and launched together -- at wg_flush / the region's end, or when the table is full.  The caller flushes before
+// anything overwrites an operand of a collected problem or reads one of their outputs.
 // Deterministic mode: the collected problems write per-slice partials into consecutive regions of the deterministic scratch (det_used: the
 // cursor; a problem that does not fit flushes the region first) and two more group launches add the slices up in a fixed order.  (Problems
 // launched on their own in between use the scratch from its start: everything is stream ordered, the group's kernels run at the flush.)
-struct WgBatch { WgGroup g; ColGroup c; WgRedGroup r; ColRedGroup cr; size_t det_used = 0; bool active = false; hipStream_t st = nullptr; };
-static thread_local WgBatch g_wgb;
-static int wg_flush() {      // (column sums of the region ride along: same hazards, same flush points)
-  WgGroup& G = g_wgb.g; ColGroup& Cg = g_wgb.c;
-  if (Cg.n > 0) hipLaunchKernelGGL(k_colsum_group, dim3(Cg.start[Cg.n]), dim3(256), 0, g_wgb.st, Cg);
-  if (G.n > 0) hipLaunchKernelGGL(k_wgrad_bf3_group, dim3(G.start[G.n]), dim3(64), 0, g_wgb.st, G);
-  if (g_wgb.cr.n > 0) hipLaunchKernelGGL(k_colsum_reduce_group, dim3(g_wgb.cr.start[g_wgb.cr.n]), dim3(256), 0, g_wgb.st, g_wgb.cr);
-  if (g_wgb.r.n > 0) hipLaunchKernelGGL(k_wgrad_reduce_group, dim3(g_wgb.r.start[g_wgb.r.n]), dim3(256), 0, g_wgb.st, g_wgb.r);
-  if (Cg.n > 0 || G.n > 0) HIPCHK(hipGetLastError());
-  G.n = 0; G.start[0] = 0; Cg.n = 0; Cg.start[0] = 0;
-  g_wgb.r.n = 0; g_wgb.r.start[0] = 0; g_wgb.cr.n = 0; g_wgb.cr.start[0] = 0; g_wgb.det_used = 0;
+struct WgBatch { WgGroup g; ColGroup c; WgRedGroup r; ColRedGroup cr; size_t det_used = 0; bool active = false; };
+// The mutable state of the step in flight: one object on the stack of train_forward_backward, reached through TrainCtx::s.
+// det: deterministic reductions (taco_train_set_deterministic) -- the sums over rows that normally leave their workgroups through fp32
+// atomics (weight gradients, bias / BatchNorm sums, embedding gradients, d attention_v) are written as per-slice partials into this
+// scratch and added up in a fixed order by a second launch: the step becomes run-to-run reproducible, as the reference's
+// single-device step is.  Null: atomics.
+struct StepState {
+  float* det = nullptr; size_t det_cap = 0;
+  uint4* wps = nullptr; size_t wps_cap = 0;      // bf16 planes of the weight gradients' operands (taco_wgrad_planes.h); null: that path is off
+  int planes_problems = 0;                       // weight gradients of this step that were computed from pre-split planes so far
+  WgBatch wgb;
+};
+struct TrainCtx {
+  const taco_train* t; hipStream_t st; float* P; float* G;    // flat parameters (moving statistics are updated in place) and gradients
+  bool update_moving;   // BatchNorm moving averages follow this pass (UPDATE_OPS run only as a dependency of `optimize`, tacotron.py:334)
+  StepState* s;
+  float* p(const std::string& n) const { return P + t->poff.at(n); }
+  float* g(const std::string& n) const { return G + t->poff.at(n); }
+};
+static void wg_reset(WgBatch& b) { b.g.n = 0; b.g.start[0] = 0; b.c.n = 0; b.c.start[0] = 0; b.r.n = 0; b.r.start[0] = 0; b.cr.n = 0; b.cr.start[0] = 0; b.det_used = 0; }
+static int wg_flush(const TrainCtx& x) {      // (column sums of the region ride along: same hazards, same flush points)
+  WgBatch& b = x.s->wgb;
+  if (b.c.n > 0) hipLaunchKernelGGL(k_colsum_group, dim3(b.c.start[b.c.n]), dim3(256), 0, x.st, b.c);
+  if (b.g.n > 0) hipLaunchKernelGGL(k_wgrad_bf3_group, dim3(b.g.start[b.g.n]), dim3(64), 0, x.st, b.g);
+  if (b.cr.n > 0) hipLaunchKernelGGL(k_colsum_reduce_group, dim3(b.cr.start[b.cr.n]), dim3(256), 0, x.st, b.cr);
+  if (b.r.n > 0) hipLaunchKernelGGL(k_wgrad_reduce_group, dim3(b.r.start[b.r.n]), dim3(256), 0, x.st, b.r);
+  if (b.c.n > 0 || b.g.n > 0) HIPCHK(hipGetLastError());
+  wg_reset(b);
   return 0;
 }
-static void wg_begin(hipStream_t st) {
-  g_wgb.active = true; g_wgb.st = st; g_wgb.g.n = 0; g_wgb.g.start[0] = 0; g_wgb.c.n = 0; g_wgb.c.start[0] = 0;
-  g_wgb.r.n = 0; g_wgb.r.start[0] = 0; g_wgb.cr.n = 0; g_wgb.cr.start[0] = 0; g_wgb.det_used = 0;
-}
-static int wg_end() { const int rc = wg_flush(); g_wgb.active = false; return rc; }
-struct WgRegion {      // RAII: a region ends (and flushes) on every return path
-  explicit WgRegion(hipStream_t st) { wg_begin(st); }
-  ~WgRegion() { if (g_wgb.active) (void)wg_end(); }
+struct WgRegion {      // RAII: a region ends (and flushes) on every return path; end() for the caller that must see the flush's status
+  const TrainCtx& x;
+  explicit WgRegion(const TrainCtx& x_) : x(x_) { wg_reset(x.s->wgb); x.s->wgb.active = true; }
+  int end() { const int rc = wg_flush(x); x.s->wgb.active = false; return rc; }
+  ~WgRegion() { if (x.s->wgb.active) (void)end(); }
 };
-static int run_colsum(hipStream_t st, const float* a, int lda, const float* b, int ldb, const float* mu, const float* rstd,
+// A problem joins the region's group launch in deterministic mode: `need` floats of the scratch at the cursor for its partials, summed by the
+// group's reduce launch.  Two problems of one reduce launch must not add into the same output: their read-modify-writes would race, where
+// the atomics of the other mode simply accumulate (e.g. the five speaker projections of model type deepvoice sum into one embedding
+// gradient) -- so a problem whose output (o1, o2; nullable) is already written by the region, or that does not fit, flushes the region first.
+static int wg_reserve(const TrainCtx& x, const float* o1, const float* o2, size_t need, float** part) {
+  WgBatch& b = x.s->wgb;
+  bool clash = false;
+  for (const float* o : {o1, o2}) {
+    for (int i = 0; o && i < b.cr.n; ++i) clash = clash || b.cr.p[i].out1 == o || b.cr.p[i].out2 == o;
+    for (int i = 0; o && i < b.r.n; ++i) clash = clash || b.r.p[i].dw == o;
+  }
+  if (clash || b.det_used + need > x.s->det_cap) TRY(wg_flush(x));
+  *part = x.s->det + b.det_used; b.det_used += need;
+  return 0;
+}
+static int run_colsum(const TrainCtx& x, const float* a, int lda, const float* b, int ldb, const float* mu, const float* rstd,
                       float* out1, float* out2, int M, int C, int mode, bool assign = false) {
   // assign (deterministic mode only -- the caller zero-fills otherwise): the ordered sums replace out1 / out2 instead of being added to them
   ColArgs g; g.a = a; g.b = b; g.mu = mu; g.rstd = rstd; g.out1 = out1; g.out2 = out2; g.lda = lda; g.ldb = ldb; g.M = M; g.C = C;
   g.mode = mode; g.rpb = 256; g.part = nullptr;
-  if (g_det.p) {
-    while ((size_t)cdiv(M, g.rpb) * 2 * C > g_det.cap) g.rpb *= 2;
-    g.part = g_det.p;
+  if (x.s->det) {
+    while ((size_t)cdiv(M, g.rpb) * 2 * C > x.s->det_cap) g.rpb *= 2;
+    g.part = x.s->det;
   }
   const int nchunks = cdiv(M, g.rpb);
-  if (g_wgb.active) {      // inside a batching region: joins the group launch (the caller flushes before the sums are read)
-    if (g.part) {          // deterministic: its own region of the scratch, summed by the group's reduce launch
-      const size_t need = (size_t)nchunks * 2 * C;
-      // (two problems of one reduce launch must not add into the same vector: their read-modify-writes would race, where the atomics
-      // of the other mode simply accumulate -- e.g. the five speaker projections of model type deepvoice sum into one embedding gradient)
-      bool clash = false;
-      for (int i = 0; i < g_wgb.cr.n; ++i)
-        clash = clash || (out1 && (g_wgb.cr.p[i].out1 == out1 || g_wgb.cr.p[i].out2 == out1)) || (out2 && (g_wgb.cr.p[i].out1 == out2 || g_wgb.cr.p[i].out2 == out2));
-      if (clash || g_wgb.det_used + need > g_det.cap) TRY(wg_flush());
-      g.part = g_det.p + g_wgb.det_used; g_wgb.det_used += need;
-      ColRedGroup& R = g_wgb.cr;
+  if (x.s->wgb.active) {      // inside a batching region: joins the group launch (the caller flushes before the sums are read)
+    if (g.part) {
+      TRY(wg_reserve(x, out1, out2, (size_t)nchunks * 2 * C, &g.part));
+      ColRedGroup& R = x.s->wgb.cr;
       R.p[R.n].part = g.part; R.p[R.n].out1 = out1; R.p[R.n].out2 = out2; R.p[R.n].nchunks = nchunks; R.p[R.n].C = C; R.p[R.n].mode = mode | (assign ? 8 : 0);
       R.start[R.n + 1] = R.start[R.n] + cdiv(C, 256); ++R.n;
     }
-    ColGroup& G = g_wgb.c;
+    ColGroup& G = x.s->wgb.c;
     G.p[G.n] = g;
     G.start[G.n + 1] = G.start[G.n] + cdiv(C, 64) * nchunks;
-    if (++G.n == COL_MAXP) return wg_flush();
+    if (++G.n == COL_MAXP) return wg_flush(x);
     return 0;
   }
-  hipLaunchKernelGGL(k_colsum, dim3(cdiv(C, 64), nchunks), dim3(256), 0, st, g);
-  if (g.part) hipLaunchKernelGGL(k_colsum_reduce, EWGRID(C), 0, st, (const float*)g.part, nchunks, C, mode | (assign ? 8 : 0), out1, out2);
+  hipLaunchKernelGGL(k_colsum, dim3(cdiv(C, 64), nchunks), dim3(256), 0, x.st, g);
+  if (g.part) hipLaunchKernelGGL(k_colsum_reduce, EWGRID(C), 0, x.st, (const float*)g.part, nchunks, C, mode | (assign ? 8 : 0), out1, out2);
   HIPCHK(hipGetLastError());
   return 0;
 }
-// ---- weight gradients from pre-split planes (taco_wgrad_planes.h) ----
-// The operands of a LARGE weight gradient are converted once into bf16 planes (k_wp_split: fragment-major, the tap shifts and their
-// batch-row masks applied to copies of the narrower operand) and multiplied by a kernel that converts nothing (k_wp_gemm).  Measured per
-// problem against k_wgrad_bf3 (tools/ubench_wgrad_planes.hip, profiles/r06_ubench_wgrad_planes.txt): the conversion pass is bound by
-// its 10 bytes per element, so it pays where an element meets many products -- post-net proj_1 (542 -> 382 us), the linear head
-// (365 -> 208), a whole conv bank as ONE product launch over one conversion of its dz (post-net: ~1240 -> ~330) -- and loses on
-// 256 x 256-sized problems (highway, GRU kernels, the decoder's hoisted gradients), which stay on k_wgrad_bf3.
-static thread_local int g_wgrad_planes = 1;            // installed from the trainer for the duration of a step (EngineGuard)
-struct WpScratch { uint4* p = nullptr; size_t cap = 0; };
-static thread_local WpScratch g_wps;
-static thread_local int g_wp_count = 0;               // problems of the step in flight that took this path
-#define WP_MIN_MACS 3.0e9                               // mode 1: problems below this many multiply-adds stay on k_wgrad_bf3
-constexpr int WP_SM = 1, WP_NB = 3;                    // 16-row stages, ring of three
-template <int WK, int WN>
-static int wp_gemm_launch_t(hipStream_t st, const WpGemmArgs& g, int z) {
-  constexpr size_t lds = (size_t)WP_NB * 3 * 2 * (WK + WN) * WP_SM * 1024;
-  static const hipError_t attr = hipFuncSetAttribute((const void*)k_wp_gemm<WK, WN, WP_SM, WP_NB>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  HIPCHK(attr);
-  hipLaunchKernelGGL((k_wp_gemm<WK, WN, WP_SM, WP_NB>), dim3(cdiv(g.K, 64 * WK), cdiv(g.N, 64 * WN), z), dim3(64 * WK * WN), lds, st, g);
-  HIPCHK(hipGetLastError());
-  return 0;
-}
-// workgroup tile (k x n): 128 x 128 (four waves, 72 KB of LDS, two workgroups per CU)
-static void wp_tile(int K, int N, int& tk, int& tn) { (void)K; (void)N; tk = 128; tn = 128; }
-static int wp_gemm_launch(hipStream_t st, const WpGemmArgs& g, int tk, int tn, int z) {
-  if (tk == 128 && tn == 128) return wp_gemm_launch_t<2, 2>(st, g, z);
-  return fail(TACO_ERR_STATE, "no k_wp_gemm instantiation for a %d x %d tile", tk, tn);
-}
-static int wp_rows_per_slice(int Mp, long tiles, size_t per) {      // ~768 workgroups; in deterministic mode the slices' partial tiles must fit the scratch
-  int rpb = Mp;
-  while (rpb > 256 && tiles * cdiv(Mp, rpb) < 768) rpb >>= 1;
-  rpb = cdiv(rpb, 16 * WP_SM) * 16 * WP_SM;
-  if (g_det.p) while ((size_t)cdiv(Mp, rpb) * per > g_det.cap && rpb < Mp) rpb *= 2;
-  return rpb;
-}
-static void wp_split_launch(hipStream_t st, const float* src, const int* gather, int ld, int M, int T, int C, int Mp, int ncopy, int sigma0, int dsigma, uint4* out) {
-  WpSplitArgs a; a.src = src; a.gather = gather; a.out = out; a.ld = ld; a.M = M; a.T = T; a.C = C; a.Mp = Mp; a.ncopy = ncopy; a.sigma0 = sigma0; a.dsigma = dsigma;
-  hipLaunchKernelGGL(k_wp_split, dim3(cdiv(cdiv(C, 32), 4), Mp / 64, ncopy), dim3(256), 0, st, a);
-}
-// one weight gradient (the arguments of run_wgrad); handled = false: not eligible, nothing was launched
-static int run_wgrad_planes(hipStream_t st, const float* x, const int* gather, int ldx, const float* dy, int ldy, float* dw, int lddw,
-                            int M, int T, int K, int N, int kw, int padl, bool& handled) {
-  handled = false;
-  if (!g_wgrad_planes || !g_wps.p) return 0;
-  if (g_wgrad_planes == 1 && (double)M * K * N * kw < WP_MIN_MACS) return 0;
-  const bool shifted = kw > 1 || padl != 0;
-  if (shifted && (gather || T <= 0)) return 0;
-  const int Mp = cdiv(M, 64) * 64;
-  const bool a_per_tap = K <= N;            // the narrower operand carries the tap copies
-  const size_t na = wp_plane_uint4(K, Mp, a_per_tap ? kw : 1), nb = wp_plane_uint4(N, Mp, a_per_tap ? 1 : kw);
-  const size_t per = (size_t)kw * K * N;
-  if (na + nb > g_wps.cap || (g_det.p && per > g_det.cap)) return 0;
-  uint4* pa = g_wps.p; uint4* pb = g_wps.p + na;
-  // dW[tap] = sum_m X[m + s] dY[m], s = tap - padl: either X carries the shift s, or dY carries -s (m' = m + s)
-  wp_split_launch(st, x, gather, ldx, M, T, K, Mp, a_per_tap ? kw : 1, (shifted && a_per_tap) ? -padl : 0, a_per_tap ? 1 : 0, pa);
-  wp_split_launch(st, dy, nullptr, ldy, M, T, N, Mp, a_per_tap ? 1 : kw, (shifted && !a_per_tap) ? padl : 0, a_per_tap ? 0 : -1, pb);
-  WpGemmArgs g; memset(&g, 0, sizeof g);
-  g.a = pa; g.b = pb; g.K = K; g.N = N; g.Mp = Mp; g.kw = kw; g.a_per_tap = a_per_tap ? 1 : 0; g.dw = dw; g.lddw = lddw; g.nw = 0;
-  int tk, tn; wp_tile(K, N, tk, tn);
-  const long tiles = (long)cdiv(K, tk) * cdiv(N, tn) * kw;
-  g.rpb = wp_rows_per_slice(Mp, tiles, per);
-  g.part = g_det.p;
-  const int nsplit = cdiv(Mp, g.rpb);
-  TRY(wp_gemm_launch(st, g, tk, tn, kw * nsplit));
-  if (g.part) hipLaunchKernelGGL(k_wgrad_reduce, EWGRID(per), 0, st, (const float*)g.part, nsplit, kw, K, N, dw, lddw);
-  HIPCHK(hipGetLastError());
-  handled = true; ++g_wp_count;
-  return 0;
-}
-// ALL widths 1 .. nw of a conv bank (dz of every width complete in dY [M, nw * Cw]): one conversion of dz, nw shifted copies of the
-// bank's input, one product launch, one ordered sum per width (a group launch).  dwk[k - 1] = the kernel gradient of width k [k][K][Cw].
-static int run_wgrad_bank_planes(hipStream_t st, const float* x, int ldx, const float* dY, int ldy, float* const* dwk, int M, int T, int K, int Cw, int nw, bool& handled) {
-  handled = false;
-  if (!g_wgrad_planes || !g_wps.p || nw < 2 || nw > WP_MAXW || (Cw & 31) || T <= 0) return 0;
-  const int ntap = nw * (nw + 1) / 2;
-  if (g_wgrad_planes == 1 && (double)M * K * Cw * ntap < WP_MIN_MACS) return 0;
-  const int Mp = cdiv(M, 64) * 64;
-  const size_t na = wp_plane_uint4(K, Mp, nw), nb = wp_plane_uint4(nw * Cw, Mp, 1);
-  const size_t per = (size_t)ntap * K * Cw;
-  if (na + nb > g_wps.cap || (g_det.p && per > g_det.cap) || nw > WG_MAXP) return 0;
-  uint4* pa = g_wps.p; uint4* pb = g_wps.p + na;
-  wp_split_launch(st, x, nullptr, ldx, M, T, K, Mp, nw, -((nw - 1) / 2), 1, pa);       // copy j: shift j - (nw - 1) / 2; width k, tap: shift tap - (k - 1) / 2
-  wp_split_launch(st, dY, nullptr, ldy, M, T, nw * Cw, Mp, 1, 0, 0, pb);
-  WpGemmArgs g; memset(&g, 0, sizeof g);
-  g.a = pa; g.b = pb; g.K = K; g.N = Cw; g.Mp = Mp; g.kw = 1; g.a_per_tap = 1; g.lddw = Cw; g.nw = nw;
-  int tk, tn; wp_tile(K, Cw, tk, tn);
-  const long tiles = (long)cdiv(K, tk) * cdiv(Cw, tn) * ntap;
-  g.rpb = wp_rows_per_slice(Mp, tiles, per);
-  g.part = g_det.p;
-  const int nsplit = cdiv(Mp, g.rpb);
-  size_t off = 0;
-  for (int k = 1; k <= nw; ++k) { g.dwk[k - 1] = dwk[k - 1]; g.part_off[k - 1] = (unsigned)off; off += (size_t)nsplit * k * K * Cw; }
-  TRY(wp_gemm_launch(st, g, tk, tn, ntap * nsplit));
-  if (g.part) {
-    WgRedGroup R; R.n = 0; R.start[0] = 0;
-    for (int k = 1; k <= nw; ++k) {
-      R.p[R.n].part = g.part + g.part_off[k - 1]; R.p[R.n].dw = dwk[k - 1]; R.p[R.n].nsplit = nsplit; R.p[R.n].kw = k; R.p[R.n].K = K; R.p[R.n].N = Cw; R.p[R.n].lddw = Cw;
-      R.start[R.n + 1] = R.start[R.n] + cdiv(k * K * Cw, 256); ++R.n;
-    }
-    hipLaunchKernelGGL(k_wgrad_reduce_group, dim3(R.start[R.n]), dim3(256), 0, st, R);
-  }
-  HIPCHK(hipGetLastError());
-  handled = true; ++g_wp_count;
-  return 0;
-}
+// ---- which kernel a weight gradient gets: wgrad_plan / wgrad_bank_plan decide, run_wgrad / run_wgrad_bank_planes launch what they say ----
 // 1 (default): weight gradients on the bf16 matrix cores with operands split three ways and six products per tile (k_wgrad_bf3:
 // fp32-grade); 0: exact-fp32 MFMA (k_wgrad).  taco_train_set_exact_wgrad.
-static thread_local int g_wgrad_bf3 = 1;     // installed from the trainer for the duration of a step (EngineGuard)
-static int run_wgrad(hipStream_t st, const float* x, const int* gather, int ldx, const float* dy, int ldy, float* dw, int lddw,
-                     int M, int T, int K, int N, int kw = 1, int padl = 0, const int* ygather = nullptr) {
-  WgArgs g; g.ygather = ygather; g.x = x; g.gather = gather; g.dy = dy; g.dw = dw; g.ldx = ldx; g.ldy = ldy; g.lddw = lddw; g.M = M; g.T = T; g.K = K; g.N = N;
-  g.kw = kw; g.padl = padl;
-  const bool bf3 = g_wgrad_bf3 != 0;
-  if (bf3 && !ygather) {                     // large problems: from pre-split planes
-    bool handled = false;
-    TRY(run_wgrad_planes(st, x, gather, ldx, dy, ldy, dw, lddw, M, T, K, N, kw, padl, handled));
-    if (handled) return 0;
+// From pre-split planes (taco_wgrad_planes.h): the operands of a LARGE weight gradient are converted once into bf16 planes (k_wp_split:
+// fragment-major, the tap shifts and their batch-row masks applied to copies of the narrower operand) and multiplied by a kernel that
+// converts nothing (k_wp_gemm).  Measured per problem against k_wgrad_bf3 (tools/ubench_wgrad_planes.hip, profiles/r06_ubench_wgrad_planes.txt):
+// the conversion pass is bound by its 10 bytes per element, so it pays where an element meets many products -- post-net proj_1 (542 -> 382 us),
+// the linear head (365 -> 208), a whole conv bank as ONE product launch over one conversion of its dz (post-net: ~1240 -> ~330) -- and loses on
+// 256 x 256-sized problems (highway, GRU kernels, the decoder's hoisted gradients), which stay on k_wgrad_bf3.
+#define WP_MIN_MACS 3.0e9                               // planes mode 1: problems below this many multiply-adds stay on k_wgrad_bf3
+constexpr int WP_WK = 2, WP_WN = 2, WP_SM = 1, WP_NB = 3;      // k_wp_gemm: 128 x 128 workgroup tile (2 x 2 waves, 72 KB of LDS, two workgroups per CU), 16-row stages, ring of three
+constexpr size_t WP_LDS = (size_t)WP_NB * 3 * 2 * (WP_WK + WP_WN) * WP_SM * 1024;      // (taco_train_create raises the kernel's dynamic-LDS limit to this)
+enum { WG_NONE = 0, WG_PLANES, WG_BF3_4W, WG_BF3_1W, WG_BF3_GROUP, WG_EXACT };      // NONE: cannot run (WgPlan::why) / a bank that is not eligible
+struct WgEnv {         // everything besides the problem that a plan may depend on
+  int bf3, planes;     // the trainer's switches (wgrad_bf3, wgrad_planes)
+  bool det; size_t det_cap, wps_cap;      // deterministic scratch present, its floats; plane scratch in uint4 (0: none)
+  bool region;         // a batching region is open
+};
+struct WgPlan {
+  int engine = WG_NONE, rpb = 0, nsplit = 0;       // rows per M-slice, slices
+  int a_per_tap = 0, Mp = 0; size_t na = 0, nb = 0;      // planes: the x planes carry the tap copies (else dy's), padded rows, uint4 of the two plane sets
+  const char* why = nullptr;
+};
+static WgEnv wg_env(const TrainCtx& x) { return WgEnv{x.t->wgrad_bf3, x.s->wps ? x.t->wgrad_planes : 0, x.s->det != nullptr, x.s->det_cap, x.s->wps_cap, x.s->wgb.active}; }
+// slices of a planes product: ~768 workgroups; in deterministic mode the slices' partial tiles (`per` floats each) must fit the scratch
+static void wp_slices(const WgEnv& e, long tiles, size_t per, WgPlan& p) {
+  int rpb = p.Mp;
+  while (rpb > 256 && tiles * cdiv(p.Mp, rpb) < 768) rpb >>= 1;
+  rpb = cdiv(rpb, 16 * WP_SM) * 16 * WP_SM;
+  if (e.det) while ((size_t)cdiv(p.Mp, rpb) * per > e.det_cap && rpb < p.Mp) rpb *= 2;
+  p.rpb = rpb; p.nsplit = cdiv(p.Mp, rpb);
+}
+// one weight gradient dW [kw][K][N] = sum over M rows (T per batch row; 0: no time axis) of x (shifted by tap - padl) . dy
+static WgPlan wgrad_plan(const WgEnv& e, int M, int T, int K, int N, int kw, int padl, bool gather, bool ygather) {
+  WgPlan p;
+  const size_t per = (size_t)kw * K * N;
+  if (e.det && per > e.det_cap) { p.why = "deterministic-reduction scratch too small"; return p; }
+  const bool bf3 = e.bf3 != 0, shifted = kw > 1 || padl != 0;
+  if (bf3 && !ygather && e.planes && !(e.planes == 1 && (double)M * K * N * kw < WP_MIN_MACS) && !(shifted && (gather || T <= 0))) {
+    const int Mp = cdiv(M, 64) * 64;
+    const bool a_per_tap = K <= N;            // the narrower operand carries the tap copies
+    const size_t na = wp_plane_uint4(K, Mp, a_per_tap ? kw : 1), nb = wp_plane_uint4(N, Mp, a_per_tap ? 1 : kw);
+    if (na + nb <= e.wps_cap) {
+      p.engine = WG_PLANES; p.a_per_tap = a_per_tap ? 1 : 0; p.Mp = Mp; p.na = na; p.nb = nb;
+      wp_slices(e, (long)cdiv(K, 64 * WP_WK) * cdiv(N, 64 * WP_WN) * kw, per, p);
+      return p;
+    }
   }
   // split-bf16 kernel: 128 x 128 tiles (4 waves) when those alone give a few hundred workgroups, else 64 x 64 tiles (1 wave): every
   // M-slice a workgroup takes ends in one atomic per output element, so slices are kept LONG (>= 256 rows where the grid allows)
   const long t128 = (long)cdiv(K, 128) * cdiv(N, 128) * kw, t64 = (long)cdiv(K, 64) * cdiv(N, 64) * kw;
   const bool big = bf3 && t128 >= 64;
-  { const long tiles = big ? t128 : t64; int rpb = 1024;
-    const long want = bf3 ? (big ? 768 : 1024) : 2048;      // workgroups (one-wave workgroups: four times as many fit a CU).  (Ordered sums: halving or doubling the
-                                                             // slices of the small problems changes nothing, 15.87 / 15.88 ms; a quarter of them: 16.14 -- the partials' traffic is not what the mode costs)
-    while (rpb > (bf3 ? 128 : 64) && tiles * cdiv(M, rpb) < want) rpb >>= 1;
-    g.rpb = rpb; }
-  g.part = nullptr;
-  if (g_det.p) {   // per-slice partial tiles + an ordered sum instead of atomics; fewer, longer slices if the scratch is short
-    const size_t per = (size_t)kw * K * N;
-    if (per > g_det.cap) return fail(TACO_ERR_STATE, "deterministic-reduction scratch too small for a %d x %d x %d weight gradient", kw, K, N);
-    while ((size_t)cdiv(M, g.rpb) * per > g_det.cap) g.rpb *= 2;
-    g.part = g_det.p;
+  const long tiles = big ? t128 : t64;
+  const long want = bf3 ? (big ? 768 : 1024) : 2048;      // workgroups (one-wave workgroups: four times as many fit a CU).  (Ordered sums: halving or doubling the
+                                                           // slices of the small problems changes nothing, 15.87 / 15.88 ms; a quarter of them: 16.14 -- the partials' traffic is not what the mode costs)
+  p.rpb = 1024;
+  while (p.rpb > (bf3 ? 128 : 64) && tiles * cdiv(M, p.rpb) < want) p.rpb >>= 1;
+  if (e.det) while ((size_t)cdiv(M, p.rpb) * per > e.det_cap) p.rpb *= 2;      // fewer, longer slices if the scratch is short
+  p.nsplit = cdiv(M, p.rpb);
+  p.engine = !bf3 ? WG_EXACT : big ? WG_BF3_4W : e.region ? WG_BF3_GROUP : WG_BF3_1W;      // a small problem inside a batching region joins the group launch
+  return p;
+}
+// ALL widths 1 .. nw of a conv bank as one planes problem (run_wgrad_bank_planes); engine WG_NONE: not eligible, the widths go one by one
+static WgPlan wgrad_bank_plan(const WgEnv& e, int M, int T, int K, int Cw, int nw, bool gather) {
+  WgPlan p;
+  if (!e.bf3 || !e.planes || gather || nw < 2 || nw > WP_MAXW || (Cw & 31) || T <= 0) return p;
+  const int ntap = nw * (nw + 1) / 2;
+  if (e.planes == 1 && (double)M * K * Cw * ntap < WP_MIN_MACS) return p;
+  const int Mp = cdiv(M, 64) * 64;
+  const size_t na = wp_plane_uint4(K, Mp, nw), nb = wp_plane_uint4(nw * Cw, Mp, 1), per = (size_t)ntap * K * Cw;
+  if (na + nb > e.wps_cap || (e.det && per > e.det_cap)) return p;
+  p.engine = WG_PLANES; p.a_per_tap = 1; p.Mp = Mp; p.na = na; p.nb = nb;
+  wp_slices(e, (long)cdiv(K, 64 * WP_WK) * cdiv(Cw, 64 * WP_WN) * ntap, per, p);
+  return p;
+}
+static void wp_split_launch(hipStream_t st, const float* src, const int* gather, int ld, int M, int T, int C, int Mp, int ncopy, int sigma0, int dsigma, uint4* out) {
+  WpSplitArgs a; a.src = src; a.gather = gather; a.out = out; a.ld = ld; a.M = M; a.T = T; a.C = C; a.Mp = Mp; a.ncopy = ncopy; a.sigma0 = sigma0; a.dsigma = dsigma;
+  hipLaunchKernelGGL(k_wp_split, dim3(cdiv(cdiv(C, 32), 4), Mp / 64, ncopy), dim3(256), 0, st, a);
+}
+static void wp_gemm_launch(hipStream_t st, const WpGemmArgs& g, int z) {
+  hipLaunchKernelGGL((k_wp_gemm<WP_WK, WP_WN, WP_SM, WP_NB>), dim3(cdiv(g.K, 64 * WP_WK), cdiv(g.N, 64 * WP_WN), z), dim3(64 * WP_WK * WP_WN), WP_LDS, st, g);
+}
+// one weight gradient from planes (the arguments of run_wgrad, its plan)
+static int run_wgrad_planes(const TrainCtx& x, const WgPlan& p, const float* xs, const int* gather, int ldx, const float* dy, int ldy, float* dw, int lddw,
+                            int M, int T, int K, int N, int kw, int padl) {
+  const bool shifted = kw > 1 || padl != 0, a_per_tap = p.a_per_tap != 0;
+  uint4* pa = x.s->wps; uint4* pb = x.s->wps + p.na;
+  // dW[tap] = sum_m X[m + s] dY[m], s = tap - padl: either X carries the shift s, or dY carries -s (m' = m + s)
+  wp_split_launch(x.st, xs, gather, ldx, M, T, K, p.Mp, a_per_tap ? kw : 1, (shifted && a_per_tap) ? -padl : 0, a_per_tap ? 1 : 0, pa);
+  wp_split_launch(x.st, dy, nullptr, ldy, M, T, N, p.Mp, a_per_tap ? 1 : kw, (shifted && !a_per_tap) ? padl : 0, a_per_tap ? 0 : -1, pb);
+  WpGemmArgs g; memset(&g, 0, sizeof g);
+  g.a = pa; g.b = pb; g.K = K; g.N = N; g.Mp = p.Mp; g.kw = kw; g.a_per_tap = p.a_per_tap; g.dw = dw; g.lddw = lddw; g.nw = 0;
+  g.rpb = p.rpb; g.part = x.s->det;
+  wp_gemm_launch(x.st, g, kw * p.nsplit);
+  if (g.part) hipLaunchKernelGGL(k_wgrad_reduce, EWGRID((size_t)kw * K * N), 0, x.st, (const float*)g.part, p.nsplit, kw, K, N, dw, lddw);
+  HIPCHK(hipGetLastError());
+  ++x.s->planes_problems;
+  return 0;
+}
+// ALL widths 1 .. nw of a conv bank (dz of every width complete in dY [M, nw * Cw]; p: their wgrad_bank_plan): one conversion of dz, nw shifted copies
+// of the bank's input, one product launch, one ordered sum per width (a group launch).  dwk[k - 1] = the kernel gradient of width k [k][K][Cw].
+static int run_wgrad_bank_planes(const TrainCtx& x, const WgPlan& p, const float* xs, int ldx, const float* dY, int ldy, float* const* dwk, int M, int T, int K, int Cw, int nw) {
+  const int ntap = nw * (nw + 1) / 2;
+  uint4* pa = x.s->wps; uint4* pb = x.s->wps + p.na;
+  wp_split_launch(x.st, xs, nullptr, ldx, M, T, K, p.Mp, nw, -((nw - 1) / 2), 1, pa);       // copy j: shift j - (nw - 1) / 2; width k, tap: shift tap - (k - 1) / 2
+  wp_split_launch(x.st, dY, nullptr, ldy, M, T, nw * Cw, p.Mp, 1, 0, 0, pb);
+  WpGemmArgs g; memset(&g, 0, sizeof g);
+  g.a = pa; g.b = pb; g.K = K; g.N = Cw; g.Mp = p.Mp; g.kw = 1; g.a_per_tap = 1; g.lddw = Cw; g.nw = nw;
+  g.rpb = p.rpb; g.part = x.s->det;
+  size_t off = 0;
+  for (int k = 1; k <= nw; ++k) { g.dwk[k - 1] = dwk[k - 1]; g.part_off[k - 1] = (unsigned)off; off += (size_t)p.nsplit * k * K * Cw; }
+  wp_gemm_launch(x.st, g, ntap * p.nsplit);
+  if (g.part) {
+    WgRedGroup R; R.n = 0; R.start[0] = 0;
+    for (int k = 1; k <= nw; ++k) {
+      R.p[R.n].part = g.part + g.part_off[k - 1]; R.p[R.n].dw = dwk[k - 1]; R.p[R.n].nsplit = p.nsplit; R.p[R.n].kw = k; R.p[R.n].K = K; R.p[R.n].N = Cw; R.p[R.n].lddw = Cw;
+      R.start[R.n + 1] = R.start[R.n] + cdiv(k * K * Cw, 256); ++R.n;
+    }
+    hipLaunchKernelGGL(k_wgrad_reduce_group, dim3(R.start[R.n]), dim3(256), 0, x.st, R);
   }
-  const int nsplit = cdiv(M, g.rpb);
-  if (g_wgb.active && bf3 && !big) {       // small problem inside a batching region: joins the group launch
-    if (g.part) {                          // deterministic: its own region of the scratch, summed by the group's reduce launch
-      const size_t need = (size_t)nsplit * kw * K * N;
-      bool clash = false;                  // (same rule as for the column sums: one writer per output per reduce launch)
-      for (int i = 0; i < g_wgb.r.n; ++i) clash = clash || g_wgb.r.p[i].dw == dw;
-      if (clash || g_wgb.det_used + need > g_det.cap) TRY(wg_flush());
-      g.part = g_det.p + g_wgb.det_used; g_wgb.det_used += need;
-      WgRedGroup& R = g_wgb.r;
-      R.p[R.n].part = g.part; R.p[R.n].dw = dw; R.p[R.n].nsplit = nsplit; R.p[R.n].kw = kw; R.p[R.n].K = K; R.p[R.n].N = N; R.p[R.n].lddw = lddw;
+  HIPCHK(hipGetLastError());
+  ++x.s->planes_problems;
+  return 0;
+}
+static int run_wgrad(const TrainCtx& x, const float* xs, const int* gather, int ldx, const float* dy, int ldy, float* dw, int lddw,
+                     int M, int T, int K, int N, int kw = 1, int padl = 0, const int* ygather = nullptr) {
+  const WgPlan p = wgrad_plan(wg_env(x), M, T, K, N, kw, padl, gather != nullptr, ygather != nullptr);
+  if (p.engine == WG_NONE) return fail(TACO_ERR_STATE, "%s for a %d x %d x %d weight gradient", p.why, kw, K, N);
+  if (p.engine == WG_PLANES) return run_wgrad_planes(x, p, xs, gather, ldx, dy, ldy, dw, lddw, M, T, K, N, kw, padl);
+  WgArgs g; g.ygather = ygather; g.x = xs; g.gather = gather; g.dy = dy; g.dw = dw; g.ldx = ldx; g.ldy = ldy; g.lddw = lddw; g.M = M; g.T = T; g.K = K; g.N = N;
+  g.kw = kw; g.padl = padl; g.rpb = p.rpb;
+  g.part = x.s->det;      // per-slice partial tiles + an ordered sum instead of atomics
+  if (p.engine == WG_BF3_GROUP) {
+    if (g.part) {
+      TRY(wg_reserve(x, dw, nullptr, (size_t)p.nsplit * kw * K * N, &g.part));
+      WgRedGroup& R = x.s->wgb.r;
+      R.p[R.n].part = g.part; R.p[R.n].dw = dw; R.p[R.n].nsplit = p.nsplit; R.p[R.n].kw = kw; R.p[R.n].K = K; R.p[R.n].N = N; R.p[R.n].lddw = lddw;
       R.start[R.n + 1] = R.start[R.n] + cdiv(kw * K * N, 256); ++R.n;
     }
-    WgGroup& G = g_wgb.g;
+    WgGroup& G = x.s->wgb.g;
     G.p[G.n] = g;
-    G.start[G.n + 1] = G.start[G.n] + cdiv(K, 64) * cdiv(N, 64) * kw * nsplit;
-    if (++G.n == WG_MAXP) return wg_flush();
+    G.start[G.n + 1] = G.start[G.n] + cdiv(K, 64) * cdiv(N, 64) * kw * p.nsplit;
+    if (++G.n == WG_MAXP) return wg_flush(x);
     return 0;
   }
-  if (bf3 && big) hipLaunchKernelGGL((k_wgrad_bf3<4>), dim3(cdiv(K, 128), cdiv(N, 128), kw * nsplit), dim3(256), 0, st, g);
-  else if (bf3) hipLaunchKernelGGL((k_wgrad_bf3<1>), dim3(cdiv(K, 64), cdiv(N, 64), kw * nsplit), dim3(64), 0, st, g);
-  else hipLaunchKernelGGL(k_wgrad, dim3(cdiv(K, 64), cdiv(N, 64), kw * nsplit), dim3(256), 0, st, g);
-  if (g.part) hipLaunchKernelGGL(k_wgrad_reduce, EWGRID((size_t)kw * K * N), 0, st, (const float*)g.part, nsplit, kw, K, N, dw, lddw);
+  if (p.engine == WG_BF3_4W) hipLaunchKernelGGL((k_wgrad_bf3<4>), dim3(cdiv(K, 128), cdiv(N, 128), kw * p.nsplit), dim3(256), 0, x.st, g);
+  else if (p.engine == WG_BF3_1W) hipLaunchKernelGGL((k_wgrad_bf3<1>), dim3(cdiv(K, 64), cdiv(N, 64), kw * p.nsplit), dim3(64), 0, x.st, g);
+  else hipLaunchKernelGGL(k_wgrad, dim3(cdiv(K, 64), cdiv(N, 64), kw * p.nsplit), dim3(256), 0, x.st, g);
+  if (g.part) hipLaunchKernelGGL(k_wgrad_reduce, EWGRID((size_t)kw * K * N), 0, x.st, (const float*)g.part, p.nsplit, kw, K, N, dw, lddw);
   HIPCHK(hipGetLastError());
   return 0;
 }
-static void run_embed_bwd(hipStream_t st, const float* dx, const int* ids, float* dE, int M, int E, int V) {
-  if (g_det.p) hipLaunchKernelGGL(k_embed_bwd_det, EWGRID((size_t)V * ((E + 63) / 64) * 64), 0, st, dx, ids, dE, M, E, V);      // one wave per (table row, 64 columns)
-  else hipLaunchKernelGGL(k_embed_bwd, EWGRID((size_t)M * E), 0, st, dx, ids, dE, M, E);
+static void run_embed_bwd(const TrainCtx& x, const float* dx, const int* ids, float* dE, int M, int E, int V) {
+  if (x.s->det) hipLaunchKernelGGL(k_embed_bwd_det, EWGRID((size_t)V * ((E + 63) / 64) * 64), 0, x.st, dx, ids, dE, M, E, V);      // one wave per (table row, 64 columns)
+  else hipLaunchKernelGGL(k_embed_bwd, EWGRID((size_t)M * E), 0, x.st, dx, ids, dE, M, E);
 }
-static thread_local int g_dgrad_bf3 = 0;       // taco_train_set_exact_gemm(t, 3): forward GEMMs exact fp32, data gradients split-bf16
-static thread_local int g_dgrad_exact = 0;     // taco_train_set_exact_gemm(t, 2): data gradients on the exact-fp32 MFMA, forward GEMMs split-bf16 (A/B hook)
-// y = x . W^T style data gradient through k_gemm: out = conv_T(dy) (+ res)
-static int run_dgrad(const taco_model* m, hipStream_t st, const ConvL& Ld, const float* dy, int lddy, int M, int T, float* out, int ldo,
+// y = x . W^T style data gradient through k_gemm: out = conv_T(dy) (+ res).  taco_train_set_exact_gemm(t, 3): forward GEMMs exact fp32, data
+// gradients split-bf16; (t, 2): data gradients on the exact-fp32 MFMA, forward GEMMs split-bf16 (A/B hook)
+static int run_dgrad(const TrainCtx& x, const ConvL& Ld, const float* dy, int lddy, int M, int T, float* out, int ldo,
                      const float* res = nullptr, int ldres = 0) {
   GemmCall g; g.x = dy; g.ldx = lddy; g.M = M; g.T = T; g.out = out; g.ldo = ldo; g.res = res; g.ldres = ldres;
-  g.force = g_dgrad_exact ? GEMM_FORCE_EXACT : g_dgrad_bf3 ? GEMM_FORCE_BF3 : GEMM_FORCE_NONE;
-  return run_gemm(m, st, &Ld, 1, false, g);
+  g.force = x.t->dgrad_exact ? GEMM_FORCE_EXACT : x.t->dgrad_bf3 ? GEMM_FORCE_BF3 : GEMM_FORCE_NONE;
+  return run_gemm(x.t->sm, x.st, &Ld, 1, false, g);
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -560,12 +567,6 @@ static void carve_train(Carver& cv, const taco_train* t, int B, int T_in, int n,
 // ---------------------------------------------------------------------------------------------------------------
 // CBHG: training forward with tape, and backward
 // ---------------------------------------------------------------------------------------------------------------
-struct TrainCtx {
-  const taco_train* t; hipStream_t st; float* P; float* G;    // flat parameters (moving statistics are updated in place) and gradients
-  bool update_moving;   // BatchNorm moving averages follow this pass (UPDATE_OPS run only as a dependency of `optimize`, tacotron.py:334)
-  float* p(const std::string& n) const { return P + t->poff.at(n); }
-  float* g(const std::string& n) const { return G + t->poff.at(n); }
-};
 // batch statistics of a [M, C] activation -> mu, rstd (and the moving averages of layer `name` in the parameter buffer)
 static int bn_stats(const TrainCtx& x, const float* a, int lda, int M, int C, float* mu, float* rstd, float* scratch,
                     const std::string* names, const int* cols, int nnames) {
@@ -574,11 +575,11 @@ static int bn_stats(const TrainCtx& x, const float* a, int lda, int M, int C, fl
   // the whole batch computes (modules.py:131) -- merged from the ranks' own (mean, centred sum) pairs
   const bool sync = x.t->sync_fn && x.t->sync_world > 1;
   const float invM = 1.0f / ((float)M * (sync ? x.t->sync_world : 1));
-  const bool det = g_det.p != nullptr;      // the ordered sums replace the scratch; the atomics of the other mode need it cleared
+  const bool det = x.s->det != nullptr;      // the ordered sums replace the scratch; the atomics of the other mode need it cleared
   if (!det) HIPCHK(zero_async(scratch, (size_t)2 * C * sizeof(float), st));
-  TRY(run_colsum(st, a, lda, nullptr, 0, nullptr, nullptr, scratch, nullptr, M, C, 0, det));
+  TRY(run_colsum(x, a, lda, nullptr, 0, nullptr, nullptr, scratch, nullptr, M, C, 0, det));
   hipLaunchKernelGGL(k_bn_mean, EWGRID(C), 0, st, scratch, mu, C, 1.0f / (float)M);
-  TRY(run_colsum(st, a, lda, nullptr, 0, mu, nullptr, nullptr, scratch + C, M, C, 1, det));
+  TRY(run_colsum(x, a, lda, nullptr, 0, mu, nullptr, nullptr, scratch + C, M, C, 1, det));
   if (sync) {
     // ONE exchange per layer (the layer's columns, or all widths of a conv bank at once): rank means, centred sums, squared means
     // (means are exchanged as offsets from the layer's moving mean, which every rank holds identically: k_bn_sync_pack)
@@ -696,9 +697,9 @@ static int cbhg_forward_train(const TrainCtx& x, const Cbhg& c, const CbhgT& ct,
 static int conv_bn_backward_sums(const TrainCtx& x, const std::string& name, const float* a, int lda, const float* dy, int lddy, const float* mu,
                                  const float* rstd, int M, int C, float* sync_scratch, int c0, int Ctot) {
   hipStream_t st = x.st;
-  TRY(run_colsum(st, a, lda, dy, lddy, mu, rstd, x.g(name + "/beta"), x.g(name + "/gamma"), M, C, 2));
+  TRY(run_colsum(x, a, lda, dy, lddy, mu, rstd, x.g(name + "/beta"), x.g(name + "/gamma"), M, C, 2));
   if (x.t->sync_fn && x.t->sync_world > 1) {
-    TRY(wg_flush());                  // (the sums are copied right here)
+    TRY(wg_flush(x));                  // (the sums are copied right here)
     // the gradient buffers keep this rank's own sums (the flat all-reduce after backward averages them like every other gradient)
     HIPCHK(hipMemcpyAsync(sync_scratch + c0, x.g(name + "/beta"), (size_t)C * sizeof(float), hipMemcpyDeviceToDevice, st));
     HIPCHK(hipMemcpyAsync(sync_scratch + Ctot + c0, x.g(name + "/gamma"), (size_t)C * sizeof(float), hipMemcpyDeviceToDevice, st));
@@ -723,14 +724,14 @@ static int conv_bn_backward_apply(const TrainCtx& x, const std::string& name, co
   else
   hipLaunchKernelGGL(k_bn_bwd, EWGRID((size_t)M * C), 0, st, a, lda, dy, lddy, mu, rstd, x.p(name + "/gamma"), sdy,
                      sdyxh, relu ? 1 : 0, dz, lddz, M, C, invM);
-  TRY(run_colsum(st, dz, lddz, nullptr, 0, nullptr, nullptr, x.g(name + "/bias"), nullptr, M, C, 0));
+  TRY(run_colsum(x, dz, lddz, nullptr, 0, nullptr, nullptr, x.g(name + "/bias"), nullptr, M, C, 0));
   HIPCHK(hipGetLastError());
   return 0;
 }
 static int conv_bn_backward(const TrainCtx& x, const std::string& name, const float* a, int lda, const float* dy, int lddy, const float* mu,
                             const float* rstd, bool relu, float* dz, int lddz, int M, int C, float* sync_scratch) {
   TRY(conv_bn_backward_sums(x, name, a, lda, dy, lddy, mu, rstd, M, C, sync_scratch, 0, C));
-  TRY(wg_flush());                    // (inside a batching region the sums above are still queued)
+  TRY(wg_flush(x));                    // (inside a batching region the sums above are still queued)
   conv_bn_backward_exchange(x, sync_scratch, C);
   return conv_bn_backward_apply(x, name, a, lda, dy, lddy, mu, rstd, relu, dz, lddz, M, C, sync_scratch, 0, C);
 }
@@ -738,7 +739,6 @@ static int conv_bn_backward(const TrainCtx& x, const std::string& name, const fl
 static int cbhg_backward(const TrainCtx& x, const Cbhg& c, const CbhgT& ct, const std::string& sc, const float* in, const int* in_gather,
                          int B, int T, const int* lengths, const float* dout, float* din, const CbhgTape& w,
                          const float* h0 = nullptr, float* dh0 = nullptr, float* d_before = nullptr, int* rowidx = nullptr) {
-  (void)in_gather;
   const taco_model* m = x.t->sm; hipStream_t st = x.st;
   const int M = B * T, KC = c.K * c.C, H = c.rnn, I = c.rnn;
   // ---- BiGRU ----
@@ -777,29 +777,29 @@ static int cbhg_backward(const TrainCtx& x, const Cbhg& c, const CbhgT& ct, cons
     HIPCHK(hipGetLastError());
   }
   const float* hlast = w.hx[c.depth];
-  WgRegion wgr(st);          // small weight gradients of this CBHG join group launches; flushed wherever an operand is about to be reused
+  WgRegion wgr(x);           // small weight gradients of this CBHG join group launches; flushed wherever an operand is about to be reused
   for (int dir = 0; dir < 2; ++dir) {
     const std::string n = sc + "/bigru/" + (dir ? "bw" : "fw");
     const float* dgg = w.dg + dir * 3 * H;          // gates columns (r|u), candidate at +2H
     float* Gg = x.g(n + "/gates/kernel"); float* Gc = x.g(n + "/candidate/kernel");
-    TRY(run_wgrad(st, hlast, nullptr, I, dgg, 6 * H, Gg, 2 * H, M, T, I, 2 * H));                                   // x rows of gates
-    TRY(run_wgrad(st, hlast, nullptr, I, dgg + 2 * H, 6 * H, Gc, H, M, T, I, H));                                    // x rows of candidate
+    TRY(run_wgrad(x, hlast, nullptr, I, dgg, 6 * H, Gg, 2 * H, M, T, I, 2 * H));                                   // x rows of gates
+    TRY(run_wgrad(x, hlast, nullptr, I, dgg + 2 * H, 6 * H, Gc, H, M, T, I, H));                                    // x rows of candidate
     // h rows: state before the step = output one step earlier in the direction's own time (zero at the sequence start / past the length)
-    TRY(run_wgrad(st, w.out + dir * H, nullptr, 2 * H, dgg, 6 * H, Gg + (size_t)I * 2 * H, 2 * H, M, T, H, 2 * H, 1, dir ? -1 : 1));
-    TRY(run_wgrad(st, w.rh + dir * H, nullptr, 2 * H, dgg + 2 * H, 6 * H, Gc + (size_t)I * H, H, M, T, H, H));
+    TRY(run_wgrad(x, w.out + dir * H, nullptr, 2 * H, dgg, 6 * H, Gg + (size_t)I * 2 * H, 2 * H, M, T, H, 2 * H, 1, dir ? -1 : 1));
+    TRY(run_wgrad(x, w.rh + dir * H, nullptr, 2 * H, dgg + 2 * H, 6 * H, Gc + (size_t)I * H, H, M, T, H, H));
     if (h0) {   // first step of the direction: the state before it is the initial state, not a row of the output tape
-      if (dir == 0) TRY(run_wgrad(st, h0, nullptr, 2 * H, dgg, T * 6 * H, Gg + (size_t)I * 2 * H, 2 * H, B, 0, H, 2 * H));
+      if (dir == 0) TRY(run_wgrad(x, h0, nullptr, 2 * H, dgg, T * 6 * H, Gg + (size_t)I * 2 * H, 2 * H, B, 0, H, 2 * H));
       else {
         hipLaunchKernelGGL(k_last_row_index, EWGRID(B), 0, st, lengths, rowidx, B, T);
-        TRY(run_wgrad(st, h0 + H, nullptr, 2 * H, dgg, 6 * H, Gg + (size_t)I * 2 * H, 2 * H, B, 0, H, 2 * H, 1, 0, rowidx));
+        TRY(run_wgrad(x, h0 + H, nullptr, 2 * H, dgg, 6 * H, Gg + (size_t)I * 2 * H, 2 * H, B, 0, H, 2 * H, 1, 0, rowidx));
       }
     }
-    TRY(run_colsum(st, dgg, 6 * H, nullptr, 0, nullptr, nullptr, x.g(n + "/gates/bias"), nullptr, M, 2 * H, 0));
-    TRY(run_colsum(st, dgg + 2 * H, 6 * H, nullptr, 0, nullptr, nullptr, x.g(n + "/candidate/bias"), nullptr, M, H, 0));
+    TRY(run_colsum(x, dgg, 6 * H, nullptr, 0, nullptr, nullptr, x.g(n + "/gates/bias"), nullptr, M, 2 * H, 0));
+    TRY(run_colsum(x, dgg + 2 * H, 6 * H, nullptr, 0, nullptr, nullptr, x.g(n + "/candidate/bias"), nullptr, M, H, 0));
   }
-  TRY(wg_flush());
+  TRY(wg_flush(x));
   float* dcur = w.d0; float* dalt = w.d1;
-  TRY(run_dgrad(m, st, ct.xproj_d, w.dg, 6 * H, M, T, dcur, I));
+  TRY(run_dgrad(x, ct.xproj_d, w.dg, 6 * H, M, T, dcur, I));
   // ---- highways ----
   for (int i = c.depth - 1; i >= 0; --i) {
     const std::string n = sc + "/highway_" + std::to_string(i + 1);
@@ -807,20 +807,20 @@ static int cbhg_backward(const TrainCtx& x, const Cbhg& c, const CbhgT& ct, cons
       hipLaunchKernelGGL(k_highway_bwd_v4, EWGRID((size_t)M * H / 4), 0, st, (const float*)dcur, (const float*)w.hx[i], (const float*)w.hH[i], (const float*)w.hT[i], w.dcat, dalt, M, H);
     else hipLaunchKernelGGL(k_highway_bwd, EWGRID((size_t)M * H), 0, st, dcur, w.hx[i], w.hH[i], w.hT[i], w.dcat, dalt, M, H);
     HIPCHK(hipGetLastError());
-    TRY(run_wgrad(st, w.hx[i], nullptr, H, w.dcat, 2 * H, x.g(n + "/H/kernel"), H, M, 0, H, H));
-    TRY(run_wgrad(st, w.hx[i], nullptr, H, w.dcat + H, 2 * H, x.g(n + "/T/kernel"), H, M, 0, H, H));
-    TRY(run_colsum(st, w.dcat, 2 * H, nullptr, 0, nullptr, nullptr, x.g(n + "/H/bias"), nullptr, M, H, 0));
-    TRY(run_colsum(st, w.dcat + H, 2 * H, nullptr, 0, nullptr, nullptr, x.g(n + "/T/bias"), nullptr, M, H, 0));
-    TRY(run_dgrad(m, st, ct.hw_d[i], w.dcat, 2 * H, M, 0, dalt, H, dalt, H));   // += direct path
-    TRY(wg_flush());                                                            // (dcat is the next layer's scratch)
+    TRY(run_wgrad(x, w.hx[i], nullptr, H, w.dcat, 2 * H, x.g(n + "/H/kernel"), H, M, 0, H, H));
+    TRY(run_wgrad(x, w.hx[i], nullptr, H, w.dcat + H, 2 * H, x.g(n + "/T/kernel"), H, M, 0, H, H));
+    TRY(run_colsum(x, w.dcat, 2 * H, nullptr, 0, nullptr, nullptr, x.g(n + "/H/bias"), nullptr, M, H, 0));
+    TRY(run_colsum(x, w.dcat + H, 2 * H, nullptr, 0, nullptr, nullptr, x.g(n + "/T/bias"), nullptr, M, H, 0));
+    TRY(run_dgrad(x, ct.hw_d[i], w.dcat, 2 * H, M, 0, dalt, H, dalt, H));   // += direct path
+    TRY(wg_flush(x));                                                            // (dcat is the next layer's scratch)
     std::swap(dcur, dalt);
   }
   // ---- dense (post-net) ----
   if (c.has_dense) {
-    TRY(run_wgrad(st, w.res, nullptr, c.in_dim, dcur, H, x.g(sc + "/dense/kernel"), H, M, 0, c.in_dim, H));
-    TRY(run_colsum(st, dcur, H, nullptr, 0, nullptr, nullptr, x.g(sc + "/dense/bias"), nullptr, M, H, 0));
-    TRY(run_dgrad(m, st, ct.dense_d, dcur, H, M, 0, dalt, c.in_dim));
-    TRY(wg_flush());
+    TRY(run_wgrad(x, w.res, nullptr, c.in_dim, dcur, H, x.g(sc + "/dense/kernel"), H, M, 0, c.in_dim, H));
+    TRY(run_colsum(x, dcur, H, nullptr, 0, nullptr, nullptr, x.g(sc + "/dense/bias"), nullptr, M, H, 0));
+    TRY(run_dgrad(x, ct.dense_d, dcur, H, M, 0, dalt, c.in_dim));
+    TRY(wg_flush(x));
     std::swap(dcur, dalt);
   }
   // dcur = gradient of (proj_last + x (+ before_highway)): keep a copy for the residual path
@@ -834,10 +834,10 @@ static int cbhg_backward(const TrainCtx& x, const Cbhg& c, const CbhgT& ct, cons
     const int N = c.proj_dim[i];
     const float* xin = (i == 0) ? w.pool : w.py[i - 1]; const int xd = (i == 0) ? KC : c.proj_dim[i - 1];
     TRY(conv_bn_backward(x, n, w.pa[i], N, dcur, N, w.pmu[i], w.prs[i], i + 1 != c.nproj, dalt, N, M, N, w.stat));
-    TRY(run_wgrad(st, xin, nullptr, xd, dalt, N, x.g(n + "/kernel"), N, M, T, xd, N, c.pw, (c.pw - 1) / 2));
+    TRY(run_wgrad(x, xin, nullptr, xd, dalt, N, x.g(n + "/kernel"), N, M, T, xd, N, c.pw, (c.pw - 1) / 2));
     float* dnext = (i == 0) ? w.dbig0 : dcur;
-    TRY(run_dgrad(m, st, ct.proj_d[i], dalt, N, M, T, dnext, xd));
-    TRY(wg_flush());                                                            // (dalt is rewritten by the next projection)
+    TRY(run_dgrad(x, ct.proj_d[i], dalt, N, M, T, dnext, xd));
+    TRY(wg_flush(x));                                                            // (dalt is rewritten by the next projection)
     if (i > 0) { /* dnext == dcur already holds the gradient of py[i-1] */ }
   }
   // ---- maxpool + conv bank ----
@@ -852,7 +852,7 @@ static int cbhg_backward(const TrainCtx& x, const Cbhg& c, const CbhgT& ct, cons
     const std::string n = sc + "/conv_bank/conv1d_" + std::to_string(k);
     TRY(conv_bn_backward_sums(x, n, w.bank_a + c0, KC, w.dbig1 + c0, KC, w.bank_mu + c0, w.bank_rs + c0, M, c.C, w.stat, c0, KC));
   }
-  TRY(wg_flush());                    // the sums of all widths: one group launch
+  TRY(wg_flush(x));                    // the sums of all widths: one group launch
   conv_bn_backward_exchange(x, w.stat, KC);
   // dz of ALL widths in one launch (their BatchNorm sums are complete: the flush above); the layers' own vectors through a pointer table
   bool bank_dz = false;
@@ -876,18 +876,19 @@ static int cbhg_backward(const TrainCtx& x, const Cbhg& c, const CbhgT& ct, cons
       bank_dz = true;
     }
   }
-  bool bank_wg = false;                 // every width's kernel gradient from ONE conversion of dz and one product launch (taco_wgrad_planes.h)
-  if (bank_dz && g_wgrad_bf3 && !in_gather && (int)c.bank.size() <= WP_MAXW) {
+  // every width's kernel gradient from ONE conversion of dz and one product launch (taco_wgrad_planes.h), where dz of all widths is complete
+  const WgPlan bank_plan = bank_dz ? wgrad_bank_plan(wg_env(x), M, T, c.in_dim, c.C, c.K, in_gather != nullptr) : WgPlan();
+  if (bank_plan.engine == WG_PLANES) {
     float* dwk[WP_MAXW];
     for (size_t bi = 0; bi < c.bank.size(); ++bi) dwk[c.bank[bi].kw - 1] = x.g(sc + "/conv_bank/conv1d_" + std::to_string(c.bank[bi].kw) + "/kernel");
-    TRY(run_wgrad_bank_planes(st, in, c.in_dim, w.dbig0, KC, dwk, M, T, c.in_dim, c.C, c.K, bank_wg));
+    TRY(run_wgrad_bank_planes(x, bank_plan, in, c.in_dim, w.dbig0, KC, dwk, M, T, c.in_dim, c.C, c.K));
   }
   for (size_t bi = 0; bi < c.bank.size(); ++bi) {
     const int k = c.bank[bi].kw, c0 = (k - 1) * c.C;
     const std::string n = sc + "/conv_bank/conv1d_" + std::to_string(k);
     TRY(conv_bn_backward_apply(x, n, w.bank_a + c0, KC, w.dbig1 + c0, KC, w.bank_mu + c0, w.bank_rs + c0, true, w.dbig0 + c0, KC, M, c.C, w.stat, c0, KC, bank_dz));
-    if (!bank_wg) TRY(run_wgrad(st, in, in_gather, c.in_dim, w.dbig0 + c0, KC, x.g(n + "/kernel"), c.C, M, T, c.in_dim, c.C, k, (k - 1) / 2));
-    TRY(run_dgrad(m, st, ct.bank_d[bi], w.dbig0 + c0, KC, M, T, din, c.in_dim, din, c.in_dim));   // accumulates onto the residual path
+    if (bank_plan.engine != WG_PLANES) TRY(run_wgrad(x, in, in_gather, c.in_dim, w.dbig0 + c0, KC, x.g(n + "/kernel"), c.C, M, T, c.in_dim, c.C, k, (k - 1) / 2));
+    TRY(run_dgrad(x, ct.bank_d[bi], w.dbig0 + c0, KC, M, T, din, c.in_dim, din, c.in_dim));   // accumulates onto the residual path
   }
   return 0;
 }
@@ -1010,14 +1011,13 @@ static int gru_cell_backward(const TrainCtx& x, const GruT& gt, int B, const flo
 }
 static int gru_weight_grads(const TrainCtx& x, const std::string& name, int I, int H, const float* xin, int ldx, const float* hseq,
                             const float* rh, const float* g_dgp, const float* g_dcp, int R, int n) {
-  hipStream_t st = x.st;
   float* Gg = x.g(name + "/gates/kernel"); float* Gc = x.g(name + "/candidate/kernel");
-  TRY(run_wgrad(st, xin, nullptr, ldx, g_dgp, 2 * H, Gg, 2 * H, R, 0, I, 2 * H));
-  TRY(run_wgrad(st, hseq, nullptr, H, g_dgp, 2 * H, Gg + (size_t)I * 2 * H, 2 * H, R, n, H, 2 * H, 1, 1));   // previous state = one step earlier
-  TRY(run_wgrad(st, xin, nullptr, ldx, g_dcp, H, Gc, H, R, 0, I, H));
-  TRY(run_wgrad(st, rh, nullptr, H, g_dcp, H, Gc + (size_t)I * H, H, R, 0, H, H));
-  TRY(run_colsum(st, g_dgp, 2 * H, nullptr, 0, nullptr, nullptr, x.g(name + "/gates/bias"), nullptr, R, 2 * H, 0));
-  TRY(run_colsum(st, g_dcp, H, nullptr, 0, nullptr, nullptr, x.g(name + "/candidate/bias"), nullptr, R, H, 0));
+  TRY(run_wgrad(x, xin, nullptr, ldx, g_dgp, 2 * H, Gg, 2 * H, R, 0, I, 2 * H));
+  TRY(run_wgrad(x, hseq, nullptr, H, g_dgp, 2 * H, Gg + (size_t)I * 2 * H, 2 * H, R, n, H, 2 * H, 1, 1));   // previous state = one step earlier
+  TRY(run_wgrad(x, xin, nullptr, ldx, g_dcp, H, Gc, H, R, 0, I, H));
+  TRY(run_wgrad(x, rh, nullptr, H, g_dcp, H, Gc + (size_t)I * H, H, R, 0, H, H));
+  TRY(run_colsum(x, g_dgp, 2 * H, nullptr, 0, nullptr, nullptr, x.g(name + "/gates/bias"), nullptr, R, 2 * H, 0));
+  TRY(run_colsum(x, g_dcp, H, nullptr, 0, nullptr, nullptr, x.g(name + "/candidate/bias"), nullptr, R, H, 0));
   return 0;
 }
 static int decoder_backward(const TrainCtx& x, const float* enc_out, int B, int T_in, int n, const float* teach, const float* dmel,
@@ -1053,7 +1053,7 @@ static int decoder_backward(const TrainCtx& x, const float* enc_out, int B, int 
     a.tape = w.tape256; a.tstride = w.tstride; a.tp_p2 = w.pz[1]; a.ld_p2 = Pz; a.tp_e = w.g_e; a.tp_alpha = w.alpha;
     a.keys = w.keys; a.values = enc_out;
     // d o2 of every step does not depend on the recurrence: ONE GEMM [B n, r M] x [r M, 256] ahead of the loop
-    TRY(run_dgrad(m, st, tp.frame_d, dmel, rM, R, 0, w.g_do2, Hd));
+    TRY(run_dgrad(x, tp.frame_d, dmel, rM, R, 0, w.g_do2, Hd));
     a.g_do2 = w.g_do2;
     a.h_att0 = att_init; a.h10 = dec_init ? dec_init[0] : nullptr; a.h20 = dec_init ? dec_init[1] : nullptr;
     a.g_dcp2 = w.g_dcp[1]; a.g_dgp2 = w.g_dgp[1]; a.g_dcp1 = w.g_dcp[0]; a.g_dgp1 = w.g_dgp[0]; a.g_do0 = w.g_do0;
@@ -1133,33 +1133,32 @@ static int decoder_backward(const TrainCtx& x, const float* enc_out, int B, int 
     if (d_dec_init && d_dec_init[i]) hipLaunchKernelGGL(k_copy2d, EWGRID((size_t)B * Hd), 0, st, w.dh[i], Hd, d_dec_init[i], Hd, B, Hd);
   HIPCHK(hipGetLastError());
   // first-step terms of the recurrent kernels' gates rows: the state before step 0 is the initial state, not a tape row
-  if (att_init) TRY(run_wgrad(st, att_init, nullptr, As, w.g_dgpA, n * 2 * As, x.g("decoder/attention_gru/gates/kernel") + (size_t)Pz * 2 * As, 2 * As, B, 0, As, 2 * As));
+  if (att_init) TRY(run_wgrad(x, att_init, nullptr, As, w.g_dgpA, n * 2 * As, x.g("decoder/attention_gru/gates/kernel") + (size_t)Pz * 2 * As, 2 * As, B, 0, As, 2 * As));
   for (int i = 0; i < L; ++i)
     if (dec_init && dec_init[i])
-      TRY(run_wgrad(st, dec_init[i], nullptr, Hd, w.g_dgp[i], n * 2 * Hd, x.g("decoder/gru_" + std::to_string(i + 1) + "/gates/kernel") + (size_t)Hd * 2 * Hd, 2 * Hd, B, 0, Hd, 2 * Hd));
+      TRY(run_wgrad(x, dec_init[i], nullptr, Hd, w.g_dgp[i], n * 2 * Hd, x.g("decoder/gru_" + std::to_string(i + 1) + "/gates/kernel") + (size_t)Hd * 2 * Hd, 2 * Hd, B, 0, Hd, 2 * Hd));
   // ---- weight gradients, hoisted over all steps: rows (b, t) of the [B, n, .] tapes ----
-  wg_begin(st);              // ~50 small products over final tapes: a few group launches (ended before d values is read below)
-  struct WgEnd { ~WgEnd() { if (g_wgb.active) (void)wg_end(); } } wg_end_guard;
-  TRY(run_wgrad(st, w.o[L], nullptr, Hd, dmel, rM, x.g("decoder/frame_projection/kernel"), rM, R, 0, Hd, rM));
-  TRY(run_colsum(st, dmel, rM, nullptr, 0, nullptr, nullptr, x.g("decoder/frame_projection/bias"), nullptr, R, rM, 0));
+  WgRegion wgr(x);           // ~50 small products over final tapes: a few group launches (ended before d values is read below)
+  TRY(run_wgrad(x, w.o[L], nullptr, Hd, dmel, rM, x.g("decoder/frame_projection/kernel"), rM, R, 0, Hd, rM));
+  TRY(run_colsum(x, dmel, rM, nullptr, 0, nullptr, nullptr, x.g("decoder/frame_projection/bias"), nullptr, R, rM, 0));
   for (int i = 0; i < L; ++i)
     TRY(gru_weight_grads(x, "decoder/gru_" + std::to_string(i + 1), Hd, Hd, w.o[i], Hd, w.h[i], w.rh[i], w.g_dgp[i], w.g_dcp[i], R, n));
   { float* Gk = x.g("decoder/concat_projection/kernel");
-    TRY(run_wgrad(st, w.hA, nullptr, As, w.g_do0, Hd, Gk, Hd, R, 0, As, Hd));
-    TRY(run_wgrad(st, w.ctx, nullptr, Dc, w.g_do0, Hd, Gk + (size_t)As * Hd, Hd, R, 0, Dc, Hd));     // context (+ speaker) rows
-    TRY(run_colsum(st, w.g_do0, Hd, nullptr, 0, nullptr, nullptr, x.g("decoder/concat_projection/bias"), nullptr, R, Hd, 0)); }
-  TRY(run_wgrad(st, w.hA, nullptr, As, w.g_dq, A, x.g("attention/query_layer/kernel"), A, R, 0, As, A));
+    TRY(run_wgrad(x, w.hA, nullptr, As, w.g_do0, Hd, Gk, Hd, R, 0, As, Hd));
+    TRY(run_wgrad(x, w.ctx, nullptr, Dc, w.g_do0, Hd, Gk + (size_t)As * Hd, Hd, R, 0, Dc, Hd));     // context (+ speaker) rows
+    TRY(run_colsum(x, w.g_do0, Hd, nullptr, 0, nullptr, nullptr, x.g("decoder/concat_projection/bias"), nullptr, R, Hd, 0)); }
+  TRY(run_wgrad(x, w.hA, nullptr, As, w.g_dq, A, x.g("attention/query_layer/kernel"), A, R, 0, As, A));
   TRY(gru_weight_grads(x, "decoder/attention_gru", Pz, As, w.pz[np - 1], Pz, w.hA, w.rhA, w.g_dgpA, w.g_dcpA, R, n));
   for (int i = np - 1; i >= 0; --i) {
     const int P = hp.dec_prenet[i];
     const std::string nm = "decoder/prenet/dense_" + std::to_string(i + 1);
     float* Gk = x.g(nm + "/kernel");
-    if (i > 0) TRY(run_wgrad(st, w.pz[i - 1], nullptr, hp.dec_prenet[i - 1], w.g_dz[i], P, Gk, P, R, 0, hp.dec_prenet[i - 1], P));
+    if (i > 0) TRY(run_wgrad(x, w.pz[i - 1], nullptr, hp.dec_prenet[i - 1], w.g_dz[i], P, Gk, P, R, 0, hp.dec_prenet[i - 1], P));
     else {   // input = concat(previous teacher frame, previous context): both one step earlier, zero at t = 0
-      TRY(run_wgrad(st, teach, nullptr, Mm, w.g_dz[0], P, Gk, P, R, n, Mm, P, 1, 1));
-      TRY(run_wgrad(st, w.ctx, nullptr, Dc, w.g_dz[0], P, Gk + (size_t)Mm * P, P, R, n, D, P, 1, 1));
+      TRY(run_wgrad(x, teach, nullptr, Mm, w.g_dz[0], P, Gk, P, R, n, Mm, P, 1, 1));
+      TRY(run_wgrad(x, w.ctx, nullptr, Dc, w.g_dz[0], P, Gk + (size_t)Mm * P, P, R, n, D, P, 1, 1));
     }
-    TRY(run_colsum(st, w.g_dz[i], P, nullptr, 0, nullptr, nullptr, x.g(nm + "/bias"), nullptr, R, P, 0));
+    TRY(run_colsum(x, w.g_dz[i], P, nullptr, 0, nullptr, nullptr, x.g(nm + "/bias"), nullptr, R, P, 0));
   }
   { const bool vn = hp.attention_type == 1;   // bah_norm: the kernels see v_hat = g*v/|v|; its gradient is mapped back to v and g below
     float* dvdst = vn ? w.dv_acc : x.g("attention/attention_v");
@@ -1167,22 +1166,22 @@ static int decoder_backward(const TrainCtx& x, const float* enc_out, int B, int 
     AttnKArgs k; k.keys = w.keys; k.q = w.g_q; k.de = w.g_de; k.v = AP(m, m->att_v); k.battn = AP(m, m->att_b); k.dkeys = w.dkeys; k.dv = dvdst;
     k.T_in = T_in; k.A = A; k.n = n;
     const int nj = cdiv(T_in, ATK_J);
-    k.part = (g_det.p && (size_t)B * nj * A <= g_det.cap) ? g_det.p : nullptr;
+    k.part = (x.s->det && (size_t)B * nj * A <= x.s->det_cap) ? x.s->det : nullptr;
     hipLaunchKernelGGL(k_attention_keys_bwd, dim3(cdiv(A, 256), nj, B), dim3(256), 0, st, k);
     if (k.part) hipLaunchKernelGGL(k_rows_reduce, EWGRID(A), 0, st, (const float*)k.part, B * nj, A, dvdst);
     if (vn) {
       hipLaunchKernelGGL(k_vnorm_bwd, dim3(1), dim3(256), 0, st, x.p("attention/attention_v"), x.p("attention/attention_g"), w.dv_acc,
                          x.g("attention/attention_v"), x.g("attention/attention_g"), A);
-      TRY(run_colsum(st, w.g_dq, A, nullptr, 0, nullptr, nullptr, x.g("attention/attention_b"), nullptr, R, A, 0));   // b enters like the query
+      TRY(run_colsum(x, w.g_dq, A, nullptr, 0, nullptr, nullptr, x.g("attention/attention_b"), nullptr, R, A, 0));   // b enters like the query
     }
     HIPCHK(hipGetLastError()); }
   for (int b = 0; b < B; ++b)    // d values[b] = alpha[b]^T . dctx[b]  ([T_in x n] . [n x D])
-    TRY(run_wgrad(st, w.alpha + ((size_t)b * (n + 1) + 1) * T_in, nullptr, T_in, w.g_dctx + (size_t)b * n * D, D,
+    TRY(run_wgrad(x, w.alpha + ((size_t)b * (n + 1) + 1) * T_in, nullptr, T_in, w.g_dctx + (size_t)b * n * D, D,
                   w.dvalues + (size_t)b * T_in * D, D, n, 0, T_in, D));
   if (hp.attention_type == 2) { hipLaunchKernelGGL(k_sum_all, dim3(1), dim3(256), 0, st, w.dsb_acc, B, x.g("attention/attention_score_bias")); HIPCHK(hipGetLastError()); }
-  TRY(run_wgrad(st, enc_out, nullptr, D, w.dkeys, A, x.g("attention/memory_layer/kernel"), A, B * T_in, 0, D, A));
-  TRY(wg_end());             // d values (the per-row products above) is an operand of the data gradient below
-  TRY(run_dgrad(m, st, tp.mem_d, w.dkeys, A, B * T_in, 0, denc, D, w.dvalues, D));
+  TRY(run_wgrad(x, enc_out, nullptr, D, w.dkeys, A, x.g("attention/memory_layer/kernel"), A, B * T_in, 0, D, A));
+  TRY(wgr.end());            // d values (the per-row products above) is an operand of the data gradient below
+  TRY(run_dgrad(x, tp.mem_d, w.dkeys, A, B * T_in, 0, denc, D, w.dvalues, D));
   return 0;
 }
 
@@ -1201,25 +1200,15 @@ static int train_forward_backward(taco_train* t, hipStream_t st, float* P, float
   if (n > hp.max_iters) return fail(TACO_ERR_SHAPE, "T_out/r = %d exceeds max_iters %d", n, hp.max_iters);
   TRY(check_common(m, B, T_in));
   if (!al16h(ws)) return fail(TACO_ERR_ARG, "workspace %p is not 16-byte aligned (the tape is carved in 256-byte steps from it; its four-column kernels need the alignment)", ws);
-  struct EngineGuard {  // the GEMM helpers see this trainer's engine switches for the duration of this step only
-    int w, d, e, p;
-    EngineGuard(const taco_train* t) : w(g_wgrad_bf3), d(g_dgrad_bf3), e(g_dgrad_exact), p(g_wgrad_planes) { g_wgrad_bf3 = t->wgrad_bf3; g_dgrad_bf3 = t->dgrad_bf3; g_dgrad_exact = t->dgrad_exact; g_wgrad_planes = t->wgrad_planes; }
-    ~EngineGuard() { g_wgrad_bf3 = w; g_dgrad_bf3 = d; g_dgrad_exact = e; g_wgrad_planes = p; }
-  } engine_guard(t);
-  if ((m->bf3 || m->bf3x6 || g_dgrad_bf3) && !t->bf3_current) return fail(TACO_ERR_STATE, "taco_train_set_exact_gemm(0) needs a taco_train_refresh before the next step (the split-bf16 weight planes are stale)");
+  if ((m->bf3 || m->bf3x6 || t->dgrad_bf3) && !t->bf3_current) return fail(TACO_ERR_STATE, "taco_train_set_exact_gemm(0) needs a taco_train_refresh before the next step (the split-bf16 weight planes are stale)");
   Carver cv(ws, ws_bytes);
   TrainWs w; carve_train(cv, t, B, T_in, n, w);
   if (!cv.ok()) return fail(TACO_ERR_STATE, "workspace too small: need %zu bytes, have %zu", cv.off, ws_bytes);
-  TrainCtx x{t, st, P, G, do_backward && !freeze_moving};
-  struct DetGuard {     // the reduction helpers see the scratch for the duration of this step only
-    DetGuard(float* p, size_t cap) { g_det.p = p; g_det.cap = cap; }
-    ~DetGuard() { g_det.p = nullptr; g_det.cap = 0; }
-  } det_guard(t->deterministic ? w.detscr : nullptr, t->deterministic ? DET_SCRATCH_FLOATS : 0);
-  struct WpGuard {      // the plane scratch of the weight gradients, for the duration of this step only
-    const taco_train* t;
-    WpGuard(const taco_train* t_, uint4* p, size_t cap) : t(t_) { g_wps.p = p; g_wps.cap = cap; g_wp_count = 0; }
-    ~WpGuard() { g_wps.p = nullptr; g_wps.cap = 0; t->planes_problems = g_wp_count; }
-  } wp_guard(t, t->wgrad_planes ? w.wpscr : nullptr, t->wgrad_planes ? w.wps_uint4 : 0);
+  StepState s;
+  if (t->deterministic) { s.det = w.detscr; s.det_cap = DET_SCRATCH_FLOATS; }
+  if (t->wgrad_planes) { s.wps = w.wpscr; s.wps_cap = w.wps_uint4; }
+  TrainCtx x{t, st, P, G, do_backward && !freeze_moving, &s};
+  const auto step = [&]() -> int {      // (a lambda so that the count below is published on every path out of the step, one that fails half-way included)
   const int Me = B * T_in, Mp = B * T_out;
   // ---- forward ----
   const float* cur = x.p("embedding"); int curd = hp.embedding_size;
@@ -1271,25 +1260,25 @@ static int train_forward_backward(taco_train* t, hipStream_t st, float* P, float
   hipLaunchKernelGGL(k_l1_grad, EWGRID((size_t)Mp * F), 0, st, lin, lin_tgt, loss_coeff, Mp, T_out, F, s_lin, c_lo, c_hi, s_band, w.dlin);
   HIPCHK(hipGetLastError());
   const int Hp2 = 2 * hp.post_rnn_size;
-  TRY(run_wgrad(st, w.post.out, nullptr, Hp2, w.dlin, F, x.g("linear/kernel") + (simple ? (size_t)S * F : 0), F, Mp, 0, Hp2, F));
+  TRY(run_wgrad(x, w.post.out, nullptr, Hp2, w.dlin, F, x.g("linear/kernel") + (simple ? (size_t)S * F : 0), F, Mp, 0, Hp2, F));
   if (simple) {      // speaker rows of the head: the embedding is constant over time, so they see the time-summed gradient
     HIPCHK(zero_async(w.dspk_emb, (size_t)B * S * sizeof(float), st));
     hipLaunchKernelGGL(k_time_sum, EWGRID((size_t)B * F), 0, st, w.dlin, w.dlin_sum, B, T_out, F);
     HIPCHK(hipGetLastError());
-    TRY(run_wgrad(st, w.spk.emb, nullptr, S, w.dlin_sum, F, x.g("linear/kernel"), F, B, 0, S, F));
+    TRY(run_wgrad(x, w.spk.emb, nullptr, S, w.dlin_sum, F, x.g("linear/kernel"), F, B, 0, S, F));
     SkJob j = sk_T(m, t->tp.lin_spk_T, w.dlin_sum, F, w.dspk_emb, S);
     TRY(run_skinny(st, B, &j, 1));
   }
-  TRY(run_colsum(st, w.dlin, F, nullptr, 0, nullptr, nullptr, x.g("linear/bias"), nullptr, Mp, F, 0));
+  TRY(run_colsum(x, w.dlin, F, nullptr, 0, nullptr, nullptr, x.g("linear/bias"), nullptr, Mp, F, 0));
   float* dpost = w.dpost; float* dmel_post = w.dmel_post;
-  TRY(run_dgrad(m, st, t->tp.lin_d, w.dlin, F, Mp, 0, dpost, Hp2));
+  TRY(run_dgrad(x, t->tp.lin_d, w.dlin, F, Mp, 0, dpost, Hp2));
   TRY(cbhg_backward(x, m->post, t->tp.post, "post_cbhg", mel, nullptr, B, T_out, nullptr, dpost, dmel_post, w.post));
   hipLaunchKernelGGL(k_add2d, EWGRID((size_t)Mp * Mm), 0, st, w.dmel, Mm, dmel_post, Mm, Mp, Mm);
   HIPCHK(hipGetLastError());
   TRY(decoder_backward(x, enc_out, B, T_in, n, w.teach, w.dmel, w.denc, w.dec, dv ? w.spk.vec[2] : nullptr, dv ? dec_init : nullptr,
                        dv ? w.dvec[2] : nullptr, dv ? d_dec_init : nullptr, simple ? w.dspk_emb : nullptr));
   if (simple) {
-    run_embed_bwd(st, w.dspk_emb, speaker_id, x.g("speaker_embedding"), B, S, hp.num_speakers);
+    run_embed_bwd(x, w.dspk_emb, speaker_id, x.g("speaker_embedding"), B, S, hp.num_speakers);
     HIPCHK(hipGetLastError());
   }
   float* dpre = w.dpre[hp.enc_prenet_n - 1];
@@ -1302,20 +1291,20 @@ static int train_forward_backward(taco_train* t, hipStream_t st, float* P, float
     if (S == 1) {
       for (size_t i = 0; i < names.size(); ++i) {
         const int dd = i < 3 ? dims[i] : hp.dec_rnn_size;
-        run_embed_bwd(st, w.dvec[i], speaker_id, x.g("spk/" + names[i] + "/table"), B, dd, hp.num_speakers);
+        run_embed_bwd(x, w.dvec[i], speaker_id, x.g("spk/" + names[i] + "/table"), B, dd, hp.num_speakers);
       }
     } else {
       HIPCHK(zero_async(w.dspk_emb, (size_t)B * S * sizeof(float), st));
       for (size_t i = 0; i < names.size(); ++i) {
         const int dd = i < 3 ? dims[i] : hp.dec_rnn_size;
         hipLaunchKernelGGL(k_softsign_bwd, EWGRID((size_t)B * dd), 0, st, w.dvec[i], w.spk.vec[i], w.dzs, B * dd);
-        TRY(run_wgrad(st, w.spk.emb, nullptr, S, w.dzs, dd, x.g("spk/" + names[i] + "/kernel"), dd, B, 0, S, dd));
-        TRY(run_colsum(st, w.dzs, dd, nullptr, 0, nullptr, nullptr, x.g("spk/" + names[i] + "/bias"), nullptr, B, dd, 0));
+        TRY(run_wgrad(x, w.spk.emb, nullptr, S, w.dzs, dd, x.g("spk/" + names[i] + "/kernel"), dd, B, 0, S, dd));
+        TRY(run_colsum(x, w.dzs, dd, nullptr, 0, nullptr, nullptr, x.g("spk/" + names[i] + "/bias"), nullptr, B, dd, 0));
         SkJob j = sk_T(m, t->tp.spk_T[i], w.dzs, dd, w.dec.tmp1, S);
         TRY(run_skinny(st, B, &j, 1));
         hipLaunchKernelGGL(k_add2d, EWGRID((size_t)B * S), 0, st, w.dspk_emb, S, w.dec.tmp1, S, B, S);
       }
-      run_embed_bwd(st, w.dspk_emb, speaker_id, x.g("speaker_embedding"), B, S, hp.num_speakers);
+      run_embed_bwd(x, w.dspk_emb, speaker_id, x.g("speaker_embedding"), B, S, hp.num_speakers);
     }
     HIPCHK(hipGetLastError());
   }
@@ -1324,15 +1313,19 @@ static int train_forward_backward(taco_train* t, hipStream_t st, float* P, float
     const std::string nm = "prenet/dense_" + std::to_string(i + 1);
     hipLaunchKernelGGL(k_relu_bwd, EWGRID((size_t)Me * N), 0, st, dpre, N, w.pre[i], N, dpre, N, Me, N);
     HIPCHK(hipGetLastError());
-    if (i > 0) TRY(run_wgrad(st, w.pre[i - 1], nullptr, hp.enc_prenet[i - 1], dpre, N, x.g(nm + "/kernel"), N, Me, 0, hp.enc_prenet[i - 1], N));
-    else TRY(run_wgrad(st, x.p("embedding"), ids, hp.embedding_size, dpre, N, x.g(nm + "/kernel"), N, Me, 0, hp.embedding_size, N));
-    TRY(run_colsum(st, dpre, N, nullptr, 0, nullptr, nullptr, x.g(nm + "/bias"), nullptr, Me, N, 0));
+    if (i > 0) TRY(run_wgrad(x, w.pre[i - 1], nullptr, hp.enc_prenet[i - 1], dpre, N, x.g(nm + "/kernel"), N, Me, 0, hp.enc_prenet[i - 1], N));
+    else TRY(run_wgrad(x, x.p("embedding"), ids, hp.embedding_size, dpre, N, x.g(nm + "/kernel"), N, Me, 0, hp.embedding_size, N));
+    TRY(run_colsum(x, dpre, N, nullptr, 0, nullptr, nullptr, x.g(nm + "/bias"), nullptr, Me, N, 0));
     float* dnext = (i > 0) ? w.dpre[i - 1] : w.demb;
     const int nd = (i > 0) ? hp.enc_prenet[i - 1] : hp.embedding_size;
-    TRY(run_dgrad(m, st, t->tp.encpre_d[i], dpre, N, Me, 0, dnext, nd));
+    TRY(run_dgrad(x, t->tp.encpre_d[i], dpre, N, Me, 0, dnext, nd));
     dpre = dnext;
   }
-  run_embed_bwd(st, dpre, ids, x.g("embedding"), (int)Me, hp.embedding_size, hp.num_symbols);
+  run_embed_bwd(x, dpre, ids, x.g("embedding"), (int)Me, hp.embedding_size, hp.num_symbols);
   HIPCHK(hipGetLastError());
   return 0;
+  };
+  const int rc = step();
+  t->planes_problems = s.planes_problems;
+  return rc;
 }

@@ -45,6 +45,7 @@ int taco_train_create(const taco_hparams* hp, int device, taco_train** out) {
   (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_bigru_rows_bwd<1>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
   (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_bigru_rows_bwd<2>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
   (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_attention_bwd), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+  (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_wp_gemm<WP_WK, WP_WN, WP_SM, WP_NB>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)WP_LDS);
   *out = t;
   return 0;
 }
@@ -69,7 +70,7 @@ int taco_train_set_sync_bn(taco_train* t, taco_sync_sum_fn fn, void* user, int w
 }
 int taco_train_set_exact_wgrad(taco_train* t, int on) {
   if (!t) return fail(TACO_ERR_ARG, "null argument");
-  t->wgrad_bf3 = on ? 0 : 1;          // per trainer: a step installs it for its own duration
+  t->wgrad_bf3 = on ? 0 : 1;          // per trainer: run_wgrad reads it through the step's TrainCtx
   return 0;
 }
 int taco_train_set_wgrad_planes(taco_train* t, int mode) {
@@ -141,6 +142,16 @@ int taco_train_debug_bigru(taco_train* t, void* hip_stream, const float* xproj, 
     if (R == 2) hipLaunchKernelGGL(k_bigru_rows_bwd<2>, dim3(2 * cdiv(B, R)), dim3(RP_NT), lds, st, a);
     else hipLaunchKernelGGL(k_bigru_rows_bwd<1>, dim3(2 * cdiv(B, R)), dim3(RP_NT), lds, st, a); }
   HIPCHK(hipGetLastError());
+  return 0;
+}
+// Test hook: what wgrad_plan (nw = 0) / wgrad_bank_plan (nw > 0: a conv bank of widths 1 .. nw, N = channels per width) decide -- no handle, no device.
+int taco_debug_wgrad_plan(int wgrad_bf3, int wgrad_planes, int deterministic, long long det_floats, long long planes_uint4, int region_open,
+                          int M, int T, int K, int N, int kw, int padl, int gather, int ygather, int nw, int* out8) {
+  if (!out8 || det_floats < 0 || planes_uint4 < 0 || M < 1 || K < 1 || N < 1 || kw < 1 || nw < 0) return fail(TACO_ERR_ARG, "bad argument");
+  const WgEnv e{wgrad_bf3, planes_uint4 ? wgrad_planes : 0, deterministic != 0, (size_t)det_floats, (size_t)planes_uint4, region_open != 0};
+  const WgPlan p = nw ? wgrad_bank_plan(e, M, T, K, N, nw, gather != 0) : wgrad_plan(e, M, T, K, N, kw, padl, gather != 0, ygather != 0);
+  const int o[8] = {p.engine, p.rpb, p.nsplit, p.a_per_tap, p.Mp, (int)p.na, (int)p.nb, p.why ? 1 : 0};
+  memcpy(out8, o, sizeof o);
   return 0;
 }
 size_t taco_train_num_params(const taco_train* t) { return t ? t->NP : 0; }

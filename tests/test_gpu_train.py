@@ -993,3 +993,41 @@ def test_weight_gradients_from_pre_split_planes_equal_the_in_kernel_split(wide, 
     rep, _ = _grad_report(got[2], g)
     assert rep[0][0] < 5e-2, rep[:5]       # (loose: the L1 sign flips of test_gradients_at_full_reference_widths move both engines alike; the tight check is the one above)
     tr.close()
+
+
+def test_two_trainers_interleaved_on_one_thread_keep_their_own_switches():
+    """The engine switches, the scratches and the count of planes problems belong to a trainer and to its step in flight (TrainCtx /
+    StepState in csrc/taco_train.h), not to the thread: trainer A (exact-fp32 weight gradients, planes off) and trainer B (every eligible
+    weight gradient from planes), same weights and batch, take turns on one thread.  Each repeats its own gradients to the bit
+    (deterministic sums, the default), keeps its own count, and the two differ -- so the switches did reach the kernels.  The tiny
+    model at B = 3, T_in = 9, T_out = 12: in mode 2 the planes path takes rows that are not a multiple of 64 and widths that are
+    not a multiple of 32."""
+    import torch
+    hp, w, ids, L, mt, lt, co = _setup("bah_mon", B=3, T_in=9, T_out=12)
+
+    def make(exact, planes):
+        tr = _trainer(hp, w)
+        tr.set_exact_wgrad(exact)
+        tr.set_wgrad_planes(planes)
+        return tr
+
+    def step(tr):
+        tr.forward_backward(ids, L, mt, lt, co, freeze_moving_averages=True)
+        torch.cuda.synchronize()
+        tr.check_device_errors()
+        return tr.grads.clone(), tr.planes_problems()
+
+    alone = make(False, 2)
+    g_alone, n_alone = step(alone)
+    alone.close()
+    a, b = make(True, 0), make(False, 2)
+    (ga1, na1), (gb1, nb1), (ga2, na2), (gb2, nb2) = step(a), step(b), step(a), step(b)
+    print("interleaved trainers: planes problems A %d / %d, B %d / %d (B alone: %d)" % (na1, na2, nb1, nb2, n_alone))
+    assert bool(torch.isfinite(ga1).all()) and bool(torch.isfinite(gb1).all())
+    assert torch.equal(ga1, ga2) and torch.equal(gb1, gb2)
+    assert na1 == 0 and na2 == 0
+    assert n_alone > 0 and nb1 == n_alone and nb2 == n_alone
+    assert torch.equal(gb1, g_alone)
+    assert not torch.equal(ga1, gb1)
+    a.close()
+    b.close()
