@@ -107,6 +107,48 @@ int taco_plan_num_nodes(const taco_plan* p);
 int taco_plan_whole_chip(const taco_plan* p);
 void taco_plan_destroy(taco_plan* p);
 
+/* ---- speaker mixtures: blending trained speakers at inference ----
+ * The reference's Synthesizer.synthesize takes `speaker_ids` as a dict {speaker_id: weight} and forms weight * speaker_embed_table[
+ * speaker_id] (synthesizer.py:153-164); that branch never ran there (an undefined `sess`, an argument-less np.tile()), but its intent
+ * is plain and linear: the speaker vector of a row is a weighted sum of table rows.  The *_mix entry points are their namesakes with
+ * `const float* d_speaker_weights` where `const int32_t* d_speaker_id` stands; every other argument, output and rule is the namesake's.
+ * d_speaker_weights is float32 [B, num_speakers], row-major, on the device.  For row b, every table lookup the model would do with
+ * speaker_id[b] (tacotron.py:41-94) is replaced by sum_s weights[b,s] * table[s,:]:
+ *   speaker_embedding_size != 1       the one table `speaker_embedding` is mixed; 'deepvoice' feeds the mixed row to its five dense +
+ *                                     softsign layers (tacotron.py:67-86), 'simple' concatenates it at the three places it goes today
+ *                                     (rnn_wrappers.py:372-376,408-413; tacotron.py:226-233).
+ *   'deepvoice', size == 1            (the get_embed tables, tacotron.py:52-66) each of the 3 + dec_layer_num tables `spk/<name>/table`
+ *                                     is mixed with the same weights.
+ * Weights are used as given: not normalised and not required to sum to 1 (the reference multiplies raw weights).  The sum is taken
+ * in ascending s with one fmaf per term, starting from +0 (k_mix_rows): deterministic, and a one-hot row reproduces the looked-up row
+ * -- and with it the whole forward -- exactly for finite tables (a table entry of -0 comes out as +0).  The added work is
+ * B * D * num_speakers multiply-adds per table of width D, one small launch each; nothing else of the forward changes.
+ * The buffer is read only by kernels: no host read, synchronisation or allocation, so the calls stay capturable.  A plan made by
+ * taco_plan_create_mix reads its weights buffer on every replay: the caller changes voices between replays by writing the buffer.
+ * More than 64 rows run as passes (as the namesakes do); the weights of the pass that starts at row b0 start at b0 * num_speakers.
+ * TACO_ERR_ARG with a message, before any launch: null weights on a multi-speaker model; non-null weights on a single-speaker model
+ * (they are not ignored).  taco_postnet_forward_mix reads the weights only for model_type 'simple', like its namesake its ids.
+ * Training with mixtures is not offered: taco_train_* take ids. */
+int taco_forward_infer_mix(taco_model* m, void* hip_stream, const int32_t* d_inputs, const int32_t* d_input_lengths,
+                           const float* d_speaker_weights /* [B,num_speakers] */, int B, int T_in, int n_steps,
+                           const float* d_manual_alignments, float* d_mel, float* d_linear, float* d_alignments,
+                           int32_t* d_stop_step, void* d_workspace, size_t workspace_bytes);
+int taco_plan_create_mix(taco_model* m, const int32_t* d_inputs, const int32_t* d_input_lengths,
+                         const float* d_speaker_weights, int B, int T_in, int n_steps,
+                         const float* d_manual_alignments, float* d_mel, float* d_linear,
+                         float* d_alignments, int32_t* d_stop_step, void* d_workspace, size_t workspace_bytes,
+                         taco_plan** out);
+int taco_encoder_forward_mix(taco_model* m, void* hip_stream, const int32_t* d_inputs,
+                             const int32_t* d_input_lengths, const float* d_speaker_weights, int B, int T_in,
+                             float* d_encoder_out, void* d_workspace, size_t workspace_bytes);
+int taco_decoder_forward_mix(taco_model* m, void* hip_stream, const float* d_encoder_out,
+                             const float* d_speaker_weights, int B, int T_in, int n_steps,
+                             const float* d_manual_alignments, const float* d_teacher_frames,
+                             float* d_mel, float* d_alignments, int32_t* d_stop_step, float* d_dbg_states,
+                             void* d_workspace, size_t workspace_bytes);
+int taco_postnet_forward_mix(taco_model* m, void* hip_stream, const float* d_mel, const float* d_speaker_weights, int B, int T_mel,
+                             float* d_linear, float* d_post_out, void* d_workspace, size_t workspace_bytes);
+
 /* ---- stage-level entry points (parity tests, profiling) ---- */
 /* embedding -> prenet -> encoder CBHG (tacotron.py:34-112).  d_encoder_out [B,T_in,2*enc_rnn_size]. */
 int taco_encoder_forward(taco_model* m, void* hip_stream, const int32_t* d_inputs,

@@ -2,7 +2,7 @@
 linear spectrogram) behind the reference's Tacotron / Synthesizer surface.  Compute lives in
 csrc/libtaco_hip.so (hand-written gfx950 HIP); this package is the thin host mirror."""
 from .hparams import hparams, HParams, basic_params, load_hparams, save_hparams   # noqa: F401
-from .tacotron import Tacotron, create_model, input_lengths_from_tokens            # noqa: F401
+from .tacotron import Tacotron, create_model, input_lengths_from_tokens, speaker_weights  # noqa: F401
 from .synthesizer import Synthesizer                                               # noqa: F401
 from .audio import GriffinLim, Spectrogram, Resampler                                   # noqa: F401
 from .trainer import Trainer                                                       # noqa: F401

@@ -113,14 +113,19 @@ PROTOTYPES = {
     "taco_workspace_bytes": (_S, [_P, _I, _I, _I]),
     "taco_stage_workspace_bytes": (_S, [_P, _I, _I]),
     "taco_forward_infer": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _P, _P, _P, _P, _P, _P, _S]),
+    "taco_forward_infer_mix": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _P, _P, _P, _P, _P, _P, _S]),
     "taco_plan_create": (_I, [_P, _P, _P, _P, _I, _I, _I, _P, _P, _P, _P, _P, _P, _S, C.POINTER(_P)]),
+    "taco_plan_create_mix": (_I, [_P, _P, _P, _P, _I, _I, _I, _P, _P, _P, _P, _P, _P, _S, C.POINTER(_P)]),
     "taco_plan_launch": (_I, [_P, _P]),
     "taco_plan_num_nodes": (_I, [_P]),
     "taco_plan_whole_chip": (_I, [_P]),
     "taco_plan_destroy": (None, [_P]),
     "taco_encoder_forward": (_I, [_P, _P, _P, _P, _P, _I, _I, _P, _P, _S]),
+    "taco_encoder_forward_mix": (_I, [_P, _P, _P, _P, _P, _I, _I, _P, _P, _S]),
     "taco_decoder_forward": (_I, [_P, _P, _P, _P, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _S]),
+    "taco_decoder_forward_mix": (_I, [_P, _P, _P, _P, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _S]),
     "taco_postnet_forward": (_I, [_P, _P, _P, _P, _I, _I, _P, _P, _P, _S]),
+    "taco_postnet_forward_mix": (_I, [_P, _P, _P, _P, _I, _I, _P, _P, _P, _S]),
     "taco_conv1d_bn_f32": (_I, [_P, _P, C.c_char_p, _P, _I, _I, _I, _I, _P]),
     "taco_dense_f32": (_I, [_P, _P, C.c_char_p, _P, _I, _I, _P]),
     "taco_highway_f32": (_I, [_P, _P, C.c_char_p, _P, _I, _P]),

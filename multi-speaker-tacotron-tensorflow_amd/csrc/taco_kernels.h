@@ -2037,6 +2037,20 @@ __global__ void k_gather_rows(const float* table, const int* idx, int R, int D, 
   if (i < R * D) { const int r = i / D, d = i % D; out[i] = table[(size_t)(idx ? idx[r] : 0) * D + d]; }
 }
 
+// rows mixture: out[r, :] = sum_s weights[r, s] * table[s, :] (speaker blending, synthesizer.py:153-164).  One thread per output
+// element, the sum in ascending s with one fmaf per term from +0: deterministic, and a one-hot row returns the table row's bits
+// (0 * finite = +-0, +0 + -0 = +0, 1 * x + 0 = x; a table entry of -0 comes back as +0).  NS is the number of trained speakers.
+__global__ void k_mix_rows(const float* table, const float* weights, int R, int NS, int D, float* out) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < R * D) {
+    const int r = i / D, d = i % D;
+    const float* w = weights + (size_t)r * NS;
+    float acc = 0.f;
+    for (int s = 0; s < NS; ++s) acc = fmaf(w[s], table[(size_t)s * D + d], acc);
+    out[i] = acc;
+  }
+}
+
 // strided 2-D copy (debug state dumps, initial states)
 __global__ void k_copy2d(const float* src, int lds, float* dst, int ldd, int R, int C) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;

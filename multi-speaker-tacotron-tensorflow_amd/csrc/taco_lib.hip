@@ -1685,22 +1685,45 @@ static void carve_spk(Carver& cv, const taco_model* m, int B, SpkWs& w) {
 static bool is_deepvoice(const taco_model* m) { return m->hp.num_speakers > 1 && m->hp.model_type == 2; }
 static bool is_simple(const taco_model* m) { return m->hp.num_speakers > 1 && m->hp.model_type == 1; }
 static int simple_S(const taco_model* m) { return is_simple(m) ? m->hp.speaker_embedding_size : 0; }
+static size_t spk_weights_offset(int b0, int num_speakers) { return (size_t)b0 * (size_t)num_speakers; }      // where row b0 of [B, num_speakers] starts
+// Which speaker each batch row speaks with: one trained speaker by id [B], or a mixture of all of them by weights [B, num_speakers]
+// (taco_abi.h, "speaker mixtures") -- never both.  Device pointers, read by kernels only.
+struct SpkSel {
+  const int* id = nullptr;
+  const float* w = nullptr;
+  bool given() const { return id || w; }
+  SpkSel rows_from(int b0, int num_speakers) const { SpkSel s; s.id = id ? id + b0 : nullptr; s.w = w ? w + spk_weights_offset(b0, num_speakers) : nullptr; return s; }
+};
+static SpkSel spk_ids(const int* id) { SpkSel s; s.id = id; return s; }
+static SpkSel spk_mix(const float* w) { SpkSel s; s.w = w; return s; }
+// a _mix entry point's selector: weights are required exactly where the model has speakers to mix
+static int spk_mix_check(const taco_model* m, const float* w) {
+  if (!m) return fail(TACO_ERR_ARG, "null model");
+  if (m->hp.num_speakers > 1 && !w) return fail(TACO_ERR_ARG, "speaker_weights required for a multi-speaker model");
+  if (m->hp.num_speakers <= 1 && w) return fail(TACO_ERR_ARG, "speaker_weights given to a single-speaker model");
+  return 0;
+}
+// out[b, :] = the speaker row of batch row b out of table [num_speakers, D]: looked up by id, or mixed by weights
+static int spk_rows(const taco_model* m, hipStream_t st, const SpkSel& sel, const float* table, int B, int D, float* out) {
+  if (sel.w) hipLaunchKernelGGL(k_mix_rows, dim3(cdiv(B * D, 256)), dim3(256), 0, st, table, sel.w, B, m->hp.num_speakers, D, out);
+  else hipLaunchKernelGGL(k_gather_rows, dim3(cdiv(B * D, 256)), dim3(256), 0, st, table, sel.id, B, D, out);
+  HIPCHK(hipGetLastError());
+  return 0;
+}
 // computes vec[0..2+L) = before_highway, encoder_rnn_init, attention_rnn_init, decoder_rnn_init_i
-static int spk_forward(const taco_model* m, hipStream_t st, const int* speaker_id, int B, const SpkWs& w) {
+static int spk_forward(const taco_model* m, hipStream_t st, const SpkSel& sel, int B, const SpkWs& w) {
   const taco_hparams& hp = m->hp;
   const int nv = 3 + hp.dec_layer_num;
   const int dims[3] = {hp.enc_prenet[hp.enc_prenet_n - 1], hp.enc_rnn_size * 2, hp.attention_state_size};
   if (hp.speaker_embedding_size == 1) {
     for (int i = 0; i < nv; ++i) {
       const int D = i < 3 ? dims[i] : hp.dec_rnn_size;
-      hipLaunchKernelGGL(k_gather_rows, dim3(cdiv(B * D, 256)), dim3(256), 0, st, AP(m, m->spk_table[i]), speaker_id, B, D, w.vec[i]);
+      TRY(spk_rows(m, st, sel, AP(m, m->spk_table[i]), B, D, w.vec[i]));
     }
-    HIPCHK(hipGetLastError());
     return 0;
   }
   const int S = hp.speaker_embedding_size;
-  hipLaunchKernelGGL(k_gather_rows, dim3(cdiv(B * S, 256)), dim3(256), 0, st, AP(m, m->spk_emb), speaker_id, B, S, w.emb);
-  HIPCHK(hipGetLastError());
+  TRY(spk_rows(m, st, sel, AP(m, m->spk_emb), B, S, w.emb));
   for (int i0 = 0; i0 < nv; i0 += SK_MAXJOBS) {
     SkJob js[SK_MAXJOBS];
     const int nj = std::min(SK_MAXJOBS, nv - i0);
@@ -1759,11 +1782,11 @@ static int run_prenet_chain(const taco_model* m, hipStream_t st, const int* ids,
 }
 // prenet_chain: prenet_chain_why(m) == NONE, asked once by the caller; riders: see run_prenet_chain -- they travel in that launch only (the caller
 // clears the regions itself otherwise)
-static int encoder_forward(const taco_model* m, hipStream_t st, const int* ids, const int* lengths, const int* speaker_id,
+static int encoder_forward(const taco_model* m, hipStream_t st, const int* ids, const int* lengths, const SpkSel& sel,
                            int B, int T, float* enc_out, const EncWs& w, bool spk_done, bool prenet_chain, const ZeroRegions* riders = nullptr) {
   const taco_hparams& hp = m->hp;
   const int M = B * T;
-  if (is_deepvoice(m) && !spk_done) TRY(spk_forward(m, st, speaker_id, B, w.spk));
+  if (is_deepvoice(m) && !spk_done) TRY(spk_forward(m, st, sel, B, w.spk));
   const float* cur = AP(m, m->emb); int curd = hp.embedding_size;
   if (prenet_chain) {
     TRY(run_prenet_chain(m, st, ids, M, w.pre[1], riders));
@@ -1872,7 +1895,8 @@ static int dx_launch_rg(hipStream_t st, const DxArgs& a_in, size_t lds) {
 #define DX_PRESETS(X) X(4, false, 128, 2) X(8, false, 128, 2) X(4, false, 256, 3) X(8, false, 256, 3) X(4, false, 512, 3) X(4, false, 128, 3) X(8, false, 128, 3) X(4, false, 512, 2)
 static constexpr int dx_inst(int rg, bool tape, int aw, int pd) { return rg | (tape ? 16 : 0) | pd << 8 | aw << 12; }
 // dp: decoder_plan's, persistent; `tape`: null, or where dp.tape the TAPE instantiation's extra arguments already filled in (teacher, tape pointers)
-static int dx_launch(const taco_model* m, hipStream_t st, const DecPlan& dp, const float* enc_out, const int* speaker_id, const float* spk_rows, int B, int T_in, int n,
+// 'simple': the speaker rows are ready_rows [B, S] if given (training), else sel's -- ids looked up by k_dx_rowbias itself, weights mixed into mix_rows [B, S] first
+static int dx_launch(const taco_model* m, hipStream_t st, const DecPlan& dp, const float* enc_out, const SpkSel& sel, const float* ready_rows, float* mix_rows, int B, int T_in, int n,
                      const float* manual, float* mel, float* align_out, float* dbg, int dbgw, const float* keys, int* nz,
                      unsigned long long* xbuf, unsigned* dxctl, float* rowbias, const float* h_att0, const float* h10, const float* h20,
                      const DxArgs* tape = nullptr) {
@@ -1891,7 +1915,8 @@ static int dx_launch(const taco_model* m, hipStream_t st, const DecPlan& dp, con
   if (tape) a = *tape;
   a.manual = manual;
   if (is_simple(m)) {   // the speaker embedding's share of the attention GRU and GRU 1 pre-activations, once per launch
-    hipLaunchKernelGGL(k_dx_rowbias, dim3(B), dim3(DX_W), 0, st, spk_rows ? spk_rows : AP(m, m->spk_emb), spk_rows ? (const int*)nullptr : speaker_id,
+    if (!ready_rows && sel.w) { TRY(spk_rows(m, st, sel, AP(m, m->spk_emb), B, m->hp.speaker_embedding_size, mix_rows)); ready_rows = mix_rows; }
+    hipLaunchKernelGGL(k_dx_rowbias, dim3(B), dim3(DX_W), 0, st, ready_rows ? ready_rows : AP(m, m->spk_emb), ready_rows ? (const int*)nullptr : sel.id,
                        AP(m, m->dx_spkw), m->hp.speaker_embedding_size, rowbias);
     HIPCHK(hipGetLastError());
     a.rowbias = rowbias;
@@ -1956,7 +1981,7 @@ static int dbx_launch(const taco_model* m, hipStream_t st, const DecPlan& dp, Db
   HIPCHK(hipGetLastError());
   return 0;
 }
-static int decoder_forward(const taco_model* m, hipStream_t st, const float* enc_out, const int* speaker_id, int B,
+static int decoder_forward(const taco_model* m, hipStream_t st, const float* enc_out, const SpkSel& sel, int B,
                            int T_in, int n, const float* manual, const float* teacher, float* mel, float* align_out,
                            int* stop_step, float* dbg, const DecWs& w, bool spk_ready, const SpkWs* spk_in,
                            const std::function<int(int)>* after_step = nullptr) {
@@ -1966,8 +1991,8 @@ static int decoder_forward(const taco_model* m, hipStream_t st, const float* enc
   if (T_in > ATT_MAXT) return fail(TACO_ERR_UNSUPPORTED, "T_in %d > %d", T_in, ATT_MAXT);
   if ((A % 4) || (D % 4)) return fail(TACO_ERR_UNSUPPORTED, "attention_size and 2*enc_rnn_size must be multiples of 4");
   const SpkWs* spk = spk_in ? spk_in : &w.spk;
-  if (is_deepvoice(m) && !spk_ready) TRY(spk_forward(m, st, speaker_id, B, *spk));
-  if (is_simple(m) && !speaker_id) return fail(TACO_ERR_ARG, "speaker_id required for a multi-speaker model");
+  if (is_deepvoice(m) && !spk_ready) TRY(spk_forward(m, st, sel, B, *spk));
+  if (is_simple(m) && !sel.given()) return fail(TACO_ERR_ARG, "speaker_id required for a multi-speaker model");
   // attention memory: keys = values . W_mem, no bias, no length mask (A.8)
   { GemmCall g; g.x = enc_out; g.ldx = D; g.M = B * T_in; g.out = w.keys; g.ldo = A;
     TRY(run_gemm(m, st, &m->memory_layer, 1, false, g)); }
@@ -1986,7 +2011,7 @@ static int decoder_forward(const taco_model* m, hipStream_t st, const float* enc
     // vectors); the launch-per-stage loop below is the general path
     DxArgs ta; memset(&ta, 0, sizeof ta);
     if (teacher) { ta.teacher = teacher; ta.p1o_raw = m->tp ? nullptr : AP(m, m->dx_p1o_raw); }     // teacher-forced: the TAPE instantiation without a tape
-    TRY(dx_launch(m, st, dp, enc_out, speaker_id, nullptr, B, T_in, n, manual, mel, align_out, dbg, dbgw, w.keys, w.nz, w.xbuf, w.dxctl, w.rowbias,
+    TRY(dx_launch(m, st, dp, enc_out, sel, nullptr, spk->emb, B, T_in, n, manual, mel, align_out, dbg, dbgw, w.keys, w.nz, w.xbuf, w.dxctl, w.rowbias,
                   dv ? spk->vec[2] : nullptr, dv ? spk->vec[3] : nullptr, dv ? spk->vec[4] : nullptr, teacher ? &ta : nullptr));
     if (stop_step) {
       hipLaunchKernelGGL(k_stop_step, dim3(1), dim3(1024), 0, st, w.nz, B, n, stop_step);
@@ -1997,7 +2022,7 @@ static int decoder_forward(const taco_model* m, hipStream_t st, const float* enc
   fill(nullptr, 0, w.zero, Mm);
   hipLaunchKernelGGL(k_copy2d, dim3(cdiv(B * D, 256)), dim3(256), 0, st, (const float*)nullptr, 0, w.ctx, ldc, B, D);
   if (S) {  // speaker_embed = embedding_lookup(table, speaker_id) (tacotron.py:44-49), parked behind ctx and behind the prenet output
-    hipLaunchKernelGGL(k_gather_rows, dim3(cdiv(B * S, 256)), dim3(256), 0, st, AP(m, m->spk_emb), speaker_id, B, S, spk->emb);
+    TRY(spk_rows(m, st, sel, AP(m, m->spk_emb), B, S, spk->emb));
     hipLaunchKernelGGL(k_copy2d, dim3(cdiv(B * S, 256)), dim3(256), 0, st, spk->emb, S, w.ctx + D, ldc, B, S);
     hipLaunchKernelGGL(k_copy2d, dim3(cdiv(B * S, 256)), dim3(256), 0, st, spk->emb, S, w.pz[np - 1] + Ilast, ldz, B, S);
   }
@@ -2087,28 +2112,27 @@ static void carve_post(Carver& cv, const taco_model* m, int B, int T, PostWs& w)
   w.spk_emb = cv.f((size_t)B * std::max(simple_S(m), 1));
   w.rowvec = cv.f((size_t)B * m->hp.num_freq);
 }
-static int postnet_tail(const taco_model* m, hipStream_t st, const int* speaker_id, int B, int T, float* linear,
+static int postnet_tail(const taco_model* m, hipStream_t st, const SpkSel& sel, int B, int T, float* linear,
                         float* post_out_user, const PostWs& w) {
   float* po = post_out_user ? post_out_user : w.post_out;
   TRY(bigru_scan(m, st, m->post, B, T, nullptr, nullptr, po, w.cb));
   GemmCall g; g.x = po; g.ldx = 2 * m->hp.post_rnn_size; g.M = B * T; g.out = linear; g.ldo = m->hp.num_freq;
   if (is_simple(m)) {
     // linear(concat(tiled speaker_embed, post)) (tacotron.py:226-235) = post . W[S:] + (speaker_embed . W[:S]) per batch row
-    if (!speaker_id) return fail(TACO_ERR_ARG, "speaker_id required for a multi-speaker model");
+    if (!sel.given()) return fail(TACO_ERR_ARG, "speaker_id required for a multi-speaker model");
     const int S = simple_S(m), F = m->hp.num_freq;
-    hipLaunchKernelGGL(k_gather_rows, dim3(cdiv(B * S, 256)), dim3(256), 0, st, AP(m, m->spk_emb), speaker_id, B, S, w.spk_emb);
-    HIPCHK(hipGetLastError());
+    TRY(spk_rows(m, st, sel, AP(m, m->spk_emb), B, S, w.spk_emb));
     SkJob j = sk_linear(m, m->lin_spk, w.spk_emb, S, S, nullptr, 0, ACT_NONE, w.rowvec, F);
     TRY(run_skinny(st, B, &j, 1));
     g.T = T; g.rowvec = w.rowvec; g.ldrv = F;
   }
   return run_gemm(m, st, &m->linear, 1, false, g);
 }
-static int postnet_forward(const taco_model* m, hipStream_t st, const float* mel, const int* speaker_id, int B, int T,
+static int postnet_forward(const taco_model* m, hipStream_t st, const float* mel, const SpkSel& sel, int B, int T,
                            float* linear, float* post_out_user, const PostWs& w) {
   FfProg pg;
   TRY(cbhg_ff_advance(m, st, m->post, mel, B, T, nullptr, nullptr, w.cb, pg, T, nullptr));
-  return postnet_tail(m, st, speaker_id, B, T, linear, post_out_user, w);
+  return postnet_tail(m, st, sel, B, T, linear, post_out_user, w);
 }
 
 struct FullWs { EncWs enc; DecWs dec; PostWs post; float* enc_out; };
@@ -2143,13 +2167,13 @@ static int overlap_chunk(const taco_model* m, int n) {
   return m->overlap && (size_t)(n / CH + 4) <= m->events.size() ? CH : 0;
 }
 // One pass of at most 64 batch rows (what the persistent kernels place on one chip: 8 groups x 8 rows).
-static int forward_pass(taco_model* m, hipStream_t st, const int32_t* ids, const int32_t* lengths, const int32_t* spk,
+static int forward_pass(taco_model* m, hipStream_t st, const int32_t* ids, const int32_t* lengths, const SpkSel& spk,
                         int B, int T_in, int n, const float* manual, float* mel, float* linear, float* align,
                         int32_t* stop, void* ws, size_t ws_bytes) {
   TRY(check_common(m, B, T_in));
   if (n <= 0) return fail(TACO_ERR_ARG, "n_steps must be positive");
   if (!ids || !lengths || !mel || !linear || !align || !ws) return fail(TACO_ERR_ARG, "null buffer");
-  if (m->hp.num_speakers > 1 && !spk) return fail(TACO_ERR_ARG, "speaker_id required for a multi-speaker model");
+  if (m->hp.num_speakers > 1 && !spk.given()) return fail(TACO_ERR_ARG, "speaker_id required for a multi-speaker model");
   Carver cv(ws, ws_bytes);
   FullWs w;
   carve_full(cv, m, B, T_in, n, w);
@@ -2240,7 +2264,7 @@ static size_t forward_workspace(const taco_model* m, int B, int T_in, int n, Ful
   if (ok) *ok = cv.ok();
   return cv.off;
 }
-static int forward_enqueue(taco_model* m, hipStream_t st, const int32_t* ids, const int32_t* lengths, const int32_t* spk,
+static int forward_enqueue(taco_model* m, hipStream_t st, const int32_t* ids, const int32_t* lengths, const SpkSel& spk,
                            int B, int T_in, int n, const float* manual, float* mel, float* linear, float* align,
                            int32_t* stop, void* ws, size_t ws_bytes) {
   if (!m) return fail(TACO_ERR_ARG, "null model");
@@ -2256,7 +2280,7 @@ static int forward_enqueue(taco_model* m, hipStream_t st, const int32_t* ids, co
   for (int p = 0; p < pp.passes; ++p) {
     const int b0 = p * pp.rows, rows = std::min(pp.rows, B - b0);
     if (rows <= 0) break;
-    TRY(forward_pass(m, st, ids + (size_t)b0 * T_in, lengths + b0, spk ? spk + b0 : nullptr, rows, T_in, n,
+    TRY(forward_pass(m, st, ids + (size_t)b0 * T_in, lengths + b0, spk.rows_from(b0, m->hp.num_speakers), rows, T_in, n,
                      manual ? manual + (size_t)b0 * n * T_in : nullptr, mel + (size_t)b0 * n * rM, linear + (size_t)b0 * T_mel * m->hp.num_freq,
                      align + (size_t)b0 * T_in * n, stop ? pstop + p : nullptr, ws, ws_bytes));
   }
@@ -2871,7 +2895,16 @@ int taco_forward_infer(taco_model* m, void* hip_stream, const int32_t* d_inputs,
                        float* d_mel, float* d_linear, float* d_alignments, int32_t* d_stop_step, void* d_workspace,
                        size_t workspace_bytes) {
   if (m) HIPCHK(hipSetDevice(m->device));
-  return forward_enqueue(m, (hipStream_t)hip_stream, d_inputs, d_input_lengths, d_speaker_id, B, T_in, n_steps,
+  return forward_enqueue(m, (hipStream_t)hip_stream, d_inputs, d_input_lengths, spk_ids(d_speaker_id), B, T_in, n_steps,
+                         d_manual_alignments, d_mel, d_linear, d_alignments, d_stop_step, d_workspace, workspace_bytes);
+}
+int taco_forward_infer_mix(taco_model* m, void* hip_stream, const int32_t* d_inputs, const int32_t* d_input_lengths,
+                           const float* d_speaker_weights, int B, int T_in, int n_steps, const float* d_manual_alignments,
+                           float* d_mel, float* d_linear, float* d_alignments, int32_t* d_stop_step, void* d_workspace,
+                           size_t workspace_bytes) {
+  TRY(spk_mix_check(m, d_speaker_weights));
+  HIPCHK(hipSetDevice(m->device));
+  return forward_enqueue(m, (hipStream_t)hip_stream, d_inputs, d_input_lengths, spk_mix(d_speaker_weights), B, T_in, n_steps,
                          d_manual_alignments, d_mel, d_linear, d_alignments, d_stop_step, d_workspace, workspace_bytes);
 }
 
@@ -2883,9 +2916,9 @@ struct taco_plan {
   bool whole_chip = false;      // the graph contains a whole-chip persistent kernel: a replay takes the device's turn (ChipTurn)
 };
 
-int taco_plan_create(taco_model* m, const int32_t* d_inputs, const int32_t* d_input_lengths, const int32_t* d_speaker_id,
-                     int B, int T_in, int n_steps, const float* d_manual_alignments, float* d_mel, float* d_linear,
-                     float* d_alignments, int32_t* d_stop_step, void* d_workspace, size_t workspace_bytes, taco_plan** out) {
+static int plan_create(taco_model* m, const int32_t* d_inputs, const int32_t* d_input_lengths, const SpkSel& sel,
+                       int B, int T_in, int n_steps, const float* d_manual_alignments, float* d_mel, float* d_linear,
+                       float* d_alignments, int32_t* d_stop_step, void* d_workspace, size_t workspace_bytes, taco_plan** out) {
   if (!m || !out) return fail(TACO_ERR_ARG, "null argument");
   HIPCHK(hipSetDevice(m->device));
   hipStream_t cs;
@@ -2893,7 +2926,7 @@ int taco_plan_create(taco_model* m, const int32_t* d_inputs, const int32_t* d_in
   hipError_t e = hipStreamBeginCapture(cs, hipStreamCaptureModeThreadLocal);
   if (e != hipSuccess) { (void)hipStreamDestroy(cs); return fail(TACO_ERR_HIP, "hipStreamBeginCapture: %s", hipGetErrorString(e)); }
   g_captured_whole_chip = false;
-  int rc = forward_enqueue(m, cs, d_inputs, d_input_lengths, d_speaker_id, B, T_in, n_steps, d_manual_alignments, d_mel,
+  int rc = forward_enqueue(m, cs, d_inputs, d_input_lengths, sel, B, T_in, n_steps, d_manual_alignments, d_mel,
                            d_linear, d_alignments, d_stop_step, d_workspace, workspace_bytes);
   const bool whole_chip = g_captured_whole_chip;
   hipGraph_t g = nullptr;
@@ -2908,6 +2941,20 @@ int taco_plan_create(taco_model* m, const int32_t* d_inputs, const int32_t* d_in
   (void)hipGraphGetNodes(g, nullptr, &p->nodes);
   *out = p;
   return 0;
+}
+int taco_plan_create(taco_model* m, const int32_t* d_inputs, const int32_t* d_input_lengths, const int32_t* d_speaker_id,
+                     int B, int T_in, int n_steps, const float* d_manual_alignments, float* d_mel, float* d_linear,
+                     float* d_alignments, int32_t* d_stop_step, void* d_workspace, size_t workspace_bytes, taco_plan** out) {
+  return plan_create(m, d_inputs, d_input_lengths, spk_ids(d_speaker_id), B, T_in, n_steps, d_manual_alignments, d_mel, d_linear, d_alignments,
+                     d_stop_step, d_workspace, workspace_bytes, out);
+}
+// the weights buffer is baked in like every other pointer and read on every replay: the caller changes voices by writing it
+int taco_plan_create_mix(taco_model* m, const int32_t* d_inputs, const int32_t* d_input_lengths, const float* d_speaker_weights,
+                         int B, int T_in, int n_steps, const float* d_manual_alignments, float* d_mel, float* d_linear,
+                         float* d_alignments, int32_t* d_stop_step, void* d_workspace, size_t workspace_bytes, taco_plan** out) {
+  TRY(spk_mix_check(m, d_speaker_weights));
+  return plan_create(m, d_inputs, d_input_lengths, spk_mix(d_speaker_weights), B, T_in, n_steps, d_manual_alignments, d_mel, d_linear, d_alignments,
+                     d_stop_step, d_workspace, workspace_bytes, out);
 }
 
 int taco_plan_launch(taco_plan* p, void* hip_stream) {
@@ -2929,27 +2976,38 @@ void taco_plan_destroy(taco_plan* p) {
   delete p;
 }
 
-int taco_encoder_forward(taco_model* m, void* hip_stream, const int32_t* d_inputs, const int32_t* d_input_lengths,
-                         const int32_t* d_speaker_id, int B, int T_in, float* d_encoder_out, void* d_workspace,
+static int encoder_entry(taco_model* m, void* hip_stream, const int32_t* d_inputs, const int32_t* d_input_lengths,
+                         const SpkSel& sel, int B, int T_in, float* d_encoder_out, void* d_workspace,
                          size_t workspace_bytes) {
   if (m && m->finalized && B > 64 && T_in > 0 && d_inputs && d_input_lengths && d_encoder_out) {      // passes of at most 64 rows (forward_enqueue)
     const PassPlan pp = pass_plan(B);
     for (int b0 = 0; b0 < B; b0 += pp.rows)
-      TRY(taco_encoder_forward(m, hip_stream, d_inputs + (size_t)b0 * T_in, d_input_lengths + b0, d_speaker_id ? d_speaker_id + b0 : nullptr, std::min(pp.rows, B - b0),
+      TRY(encoder_entry(m, hip_stream, d_inputs + (size_t)b0 * T_in, d_input_lengths + b0, sel.rows_from(b0, m->hp.num_speakers), std::min(pp.rows, B - b0),
                                T_in, d_encoder_out + (size_t)b0 * T_in * 2 * m->hp.enc_rnn_size, d_workspace, workspace_bytes));
     return 0;
   }
   TRY(check_common(m, B, T_in));
   if (!d_inputs || !d_input_lengths || !d_encoder_out || !d_workspace) return fail(TACO_ERR_ARG, "null buffer");
-  if (m->hp.num_speakers > 1 && !d_speaker_id) return fail(TACO_ERR_ARG, "speaker_id required for a multi-speaker model");
+  if (m->hp.num_speakers > 1 && !sel.given()) return fail(TACO_ERR_ARG, "speaker_id required for a multi-speaker model");
   HIPCHK(hipSetDevice(m->device));
   Carver cv(d_workspace, workspace_bytes);
   EncWs w; carve_enc(cv, m, B, T_in, w);
   if (!cv.ok()) return fail(TACO_ERR_STATE, "workspace too small: need %zu bytes", cv.off);
-  return encoder_forward(m, (hipStream_t)hip_stream, d_inputs, d_input_lengths, d_speaker_id, B, T_in, d_encoder_out, w, false, prenet_chain_why(m) == FF_WHY_NONE);
+  return encoder_forward(m, (hipStream_t)hip_stream, d_inputs, d_input_lengths, sel, B, T_in, d_encoder_out, w, false, prenet_chain_why(m) == FF_WHY_NONE);
+}
+int taco_encoder_forward(taco_model* m, void* hip_stream, const int32_t* d_inputs, const int32_t* d_input_lengths,
+                         const int32_t* d_speaker_id, int B, int T_in, float* d_encoder_out, void* d_workspace,
+                         size_t workspace_bytes) {
+  return encoder_entry(m, hip_stream, d_inputs, d_input_lengths, spk_ids(d_speaker_id), B, T_in, d_encoder_out, d_workspace, workspace_bytes);
+}
+int taco_encoder_forward_mix(taco_model* m, void* hip_stream, const int32_t* d_inputs, const int32_t* d_input_lengths,
+                             const float* d_speaker_weights, int B, int T_in, float* d_encoder_out, void* d_workspace,
+                             size_t workspace_bytes) {
+  TRY(spk_mix_check(m, d_speaker_weights));
+  return encoder_entry(m, hip_stream, d_inputs, d_input_lengths, spk_mix(d_speaker_weights), B, T_in, d_encoder_out, d_workspace, workspace_bytes);
 }
 
-int taco_decoder_forward(taco_model* m, void* hip_stream, const float* d_encoder_out, const int32_t* d_speaker_id, int B,
+static int decoder_entry(taco_model* m, void* hip_stream, const float* d_encoder_out, const SpkSel& sel, int B,
                          int T_in, int n_steps, const float* d_manual_alignments, const float* d_teacher_frames,
                          float* d_mel, float* d_alignments, int32_t* d_stop_step, float* d_dbg_states, void* d_workspace,
                          size_t workspace_bytes) {
@@ -2962,7 +3020,7 @@ int taco_decoder_forward(taco_model* m, void* hip_stream, const float* d_encoder
     const size_t pass_bytes = (size_t)((char*)pstop - (char*)d_workspace);
     int p = 0;
     for (int b0 = 0; b0 < B; b0 += pp.rows, ++p)
-      TRY(taco_decoder_forward(m, hip_stream, d_encoder_out + (size_t)b0 * T_in * D, d_speaker_id ? d_speaker_id + b0 : nullptr, std::min(pp.rows, B - b0), T_in, n_steps,
+      TRY(decoder_entry(m, hip_stream, d_encoder_out + (size_t)b0 * T_in * D, sel.rows_from(b0, m->hp.num_speakers), std::min(pp.rows, B - b0), T_in, n_steps,
                                d_manual_alignments ? d_manual_alignments + (size_t)b0 * n_steps * T_in : nullptr,
                                d_teacher_frames ? d_teacher_frames + (size_t)b0 * n_steps * m->hp.num_mels : nullptr, d_mel + (size_t)b0 * n_steps * rM,
                                d_alignments + (size_t)b0 * T_in * n_steps, d_stop_step ? pstop + p : nullptr, nullptr, d_workspace, pass_bytes));
@@ -2974,21 +3032,36 @@ int taco_decoder_forward(taco_model* m, void* hip_stream, const float* d_encoder
   }
   TRY(check_common(m, B, T_in));
   if (n_steps <= 0 || !d_encoder_out || !d_mel || !d_alignments || !d_workspace) return fail(TACO_ERR_ARG, "bad argument");
-  if (m->hp.num_speakers > 1 && !d_speaker_id) return fail(TACO_ERR_ARG, "speaker_id required for a multi-speaker model");
+  if (m->hp.num_speakers > 1 && !sel.given()) return fail(TACO_ERR_ARG, "speaker_id required for a multi-speaker model");
   HIPCHK(hipSetDevice(m->device));
   Carver cv(d_workspace, workspace_bytes);
   DecWs w; carve_dec(cv, m, B, T_in, n_steps, w);
   if (!cv.ok()) return fail(TACO_ERR_STATE, "workspace too small: need %zu bytes", cv.off);
-  return decoder_forward(m, (hipStream_t)hip_stream, d_encoder_out, d_speaker_id, B, T_in, n_steps, d_manual_alignments,
+  return decoder_forward(m, (hipStream_t)hip_stream, d_encoder_out, sel, B, T_in, n_steps, d_manual_alignments,
                          d_teacher_frames, d_mel, d_alignments, d_stop_step, d_dbg_states, w, false, nullptr);
 }
+int taco_decoder_forward(taco_model* m, void* hip_stream, const float* d_encoder_out, const int32_t* d_speaker_id, int B,
+                         int T_in, int n_steps, const float* d_manual_alignments, const float* d_teacher_frames,
+                         float* d_mel, float* d_alignments, int32_t* d_stop_step, float* d_dbg_states, void* d_workspace,
+                         size_t workspace_bytes) {
+  return decoder_entry(m, hip_stream, d_encoder_out, spk_ids(d_speaker_id), B, T_in, n_steps, d_manual_alignments, d_teacher_frames, d_mel,
+                       d_alignments, d_stop_step, d_dbg_states, d_workspace, workspace_bytes);
+}
+int taco_decoder_forward_mix(taco_model* m, void* hip_stream, const float* d_encoder_out, const float* d_speaker_weights, int B,
+                             int T_in, int n_steps, const float* d_manual_alignments, const float* d_teacher_frames,
+                             float* d_mel, float* d_alignments, int32_t* d_stop_step, float* d_dbg_states, void* d_workspace,
+                             size_t workspace_bytes) {
+  TRY(spk_mix_check(m, d_speaker_weights));
+  return decoder_entry(m, hip_stream, d_encoder_out, spk_mix(d_speaker_weights), B, T_in, n_steps, d_manual_alignments, d_teacher_frames, d_mel,
+                       d_alignments, d_stop_step, d_dbg_states, d_workspace, workspace_bytes);
+}
 
-int taco_postnet_forward(taco_model* m, void* hip_stream, const float* d_mel, const int32_t* d_speaker_id, int B, int T_mel,
+static int postnet_entry(taco_model* m, void* hip_stream, const float* d_mel, const SpkSel& sel, int B, int T_mel,
                          float* d_linear, float* d_post_out, void* d_workspace, size_t workspace_bytes) {
   if (m && m->finalized && B > 64 && T_mel > 0 && d_mel && d_linear) {      // passes of at most 64 rows
     const PassPlan pp = pass_plan(B);
     for (int b0 = 0; b0 < B; b0 += pp.rows)
-      TRY(taco_postnet_forward(m, hip_stream, d_mel + (size_t)b0 * T_mel * m->hp.num_mels, d_speaker_id ? d_speaker_id + b0 : nullptr, std::min(pp.rows, B - b0), T_mel,
+      TRY(postnet_entry(m, hip_stream, d_mel + (size_t)b0 * T_mel * m->hp.num_mels, sel.rows_from(b0, m->hp.num_speakers), std::min(pp.rows, B - b0), T_mel,
                                d_linear + (size_t)b0 * T_mel * m->hp.num_freq, d_post_out ? d_post_out + (size_t)b0 * T_mel * 2 * m->hp.post_rnn_size : nullptr,
                                d_workspace, workspace_bytes));
     return 0;
@@ -2999,7 +3072,16 @@ int taco_postnet_forward(taco_model* m, void* hip_stream, const float* d_mel, co
   Carver cv(d_workspace, workspace_bytes);
   PostWs w; carve_post(cv, m, B, T_mel, w);
   if (!cv.ok()) return fail(TACO_ERR_STATE, "workspace too small: need %zu bytes", cv.off);
-  return postnet_forward(m, (hipStream_t)hip_stream, d_mel, d_speaker_id, B, T_mel, d_linear, d_post_out, w);
+  return postnet_forward(m, (hipStream_t)hip_stream, d_mel, sel, B, T_mel, d_linear, d_post_out, w);
+}
+int taco_postnet_forward(taco_model* m, void* hip_stream, const float* d_mel, const int32_t* d_speaker_id, int B, int T_mel,
+                         float* d_linear, float* d_post_out, void* d_workspace, size_t workspace_bytes) {
+  return postnet_entry(m, hip_stream, d_mel, spk_ids(d_speaker_id), B, T_mel, d_linear, d_post_out, d_workspace, workspace_bytes);
+}
+int taco_postnet_forward_mix(taco_model* m, void* hip_stream, const float* d_mel, const float* d_speaker_weights, int B, int T_mel,
+                             float* d_linear, float* d_post_out, void* d_workspace, size_t workspace_bytes) {
+  TRY(spk_mix_check(m, d_speaker_weights));
+  return postnet_entry(m, hip_stream, d_mel, spk_mix(d_speaker_weights), B, T_mel, d_linear, d_post_out, d_workspace, workspace_bytes);
 }
 
 static const ConvL* find_conv(taco_model* m, const char* layer) {

@@ -939,7 +939,7 @@ static int decoder_forward_train(const TrainCtx& x, const float* enc_out, int B,
     DxArgs ta; memset(&ta, 0, sizeof ta);
     ta.teacher = feed_back ? nullptr : teach; ta.own_fb = feed_back ? 1 : 0; ta.tape = w.tape256; ta.tstride = w.tstride; ta.tp_p2 = w.pz[np - 1]; ta.ld_p2 = Pz; ta.tp_ctx = w.ctx; ta.ld_ctx = Dc;
     ta.tp_e = w.g_e; ta.tp_alpha = w.alpha;
-    return dx_launch(m, st, dp, enc_out, nullptr, spk_emb, B, T_in, n, nullptr, mel, align_hist, nullptr, 0, w.keys, w.nz, w.xbuf, w.dxctl, w.rowbias,
+    return dx_launch(m, st, dp, enc_out, SpkSel(), spk_emb, nullptr, B, T_in, n, nullptr, mel, align_hist, nullptr, 0, w.keys, w.nz, w.xbuf, w.dxctl, w.rowbias,
                      att_init, dec_init ? dec_init[0] : nullptr, dec_init ? dec_init[1] : nullptr, &ta);
   }
   for (int t = 0; t < n; ++t) {
@@ -1224,7 +1224,7 @@ static int train_forward_backward(taco_train* t, hipStream_t st, float* P, float
     hipLaunchKernelGGL(k_gather_rows, EWGRID((size_t)B * S), 0, st, AP(m, m->spk_emb), speaker_id, B, S, w.spk.emb);
     HIPCHK(hipGetLastError());
   }
-  if (dv) TRY(spk_forward(m, st, speaker_id, B, w.spk));       // before_highway, encoder / attention / decoder initial states (tacotron.py:52-79)
+  if (dv) TRY(spk_forward(m, st, spk_ids(speaker_id), B, w.spk));       // before_highway, encoder / attention / decoder initial states (tacotron.py:52-79)
   const int L = hp.dec_layer_num;
   const float* dec_init[4] = {nullptr, nullptr, nullptr, nullptr}; float* d_dec_init[4] = {nullptr, nullptr, nullptr, nullptr};
   for (int i = 0; i < L && dv; ++i) { dec_init[i] = w.spk.vec[3 + i]; d_dec_init[i] = w.dvec[3 + i]; }

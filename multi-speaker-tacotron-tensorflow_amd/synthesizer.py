@@ -1,7 +1,9 @@
 """`Synthesizer` -- the inference driver of the reference (synthesizer.py:23-207), re-hosted.
 
 Kept: load() / synthesize() / close() names and arguments; token -> input_lengths rule
-(synthesizer.py:120); default speaker id zeros (:43-44); the (linear_outputs, alignments) fetch pair
+(synthesizer.py:120); default speaker id zeros (:43-44); speaker mixtures (`speaker_ids` a dict {id: weight},
+:153-164 -- a branch that never ran in the reference; its intent, the sum of weight * speaker_embed_table[id], is served by the
+library's _mix entry points); the (linear_outputs, alignments) fetch pair
 (:122-126,166-167); manual-attention second pass for modes 1 and 3 (:171-205; mode 2 is broken in the
 reference: np.pow does not exist); text -> ids with the Korean normaliser (text.py, korean.py); the attention trim
 (:242-262, device kernel) and, with vocode=True, the spectrogram -> waveform step on the GPU (audio.py),
@@ -15,7 +17,7 @@ import re
 import numpy as np
 
 from .hparams import hparams, load_hparams, EOS_ID
-from .tacotron import create_model
+from .tacotron import create_model, speaker_weights
 from .weights import load_weights
 
 
@@ -109,6 +111,14 @@ class Synthesizer(object):
             raise Exception("token rows must have equal length (pre-pad with 0 as eval.py / train.py:27-40 do)")
         return sequences
 
+    def _speaker_feed(self, speaker_ids, batch):
+        """`speaker_ids` -> the model's speaker feed.  A dict {id: weight} (the reference's form, synthesizer.py:153-164: one mixture
+        for every row) or a list with a dict among its items (per row: an int or a dict) blends trained speakers and goes through
+        speaker_weights(); anything else -- None, an all-int list, an array -- is speaker ids as before."""
+        if isinstance(speaker_ids, dict) or (isinstance(speaker_ids, (list, tuple)) and any(isinstance(v, dict) for v in speaker_ids)):
+            return {"speaker_weights": speaker_weights(speaker_ids, self.num_speakers, batch)}
+        return {"speaker_id": speaker_ids}
+
     def synthesize(self, texts=None, tokens=None, base_path=None, paths=None, speaker_ids=None,
                    start_of_sentence=None, end_of_sentence=True, pre_word_num=0, post_word_num=0,
                    pre_surplus_idx=0, post_surplus_idx=1, use_short_concat=False,
@@ -116,20 +126,19 @@ class Synthesizer(object):
                    attention_trim=True, manual_alignments=None, vocode=False):
         sequences = self._token_rows(texts, tokens)
         input_lengths = np.argmax(sequences == EOS_ID, 1).astype(np.int32)             # synthesizer.py:120
-        if type(speaker_ids) == dict:
-            raise Exception("dict-valued speaker_ids is broken in the reference (synthesizer.py:153-164) and not supported")
+        speaker = self._speaker_feed(speaker_ids, len(sequences))
         if manual_alignments is None and base_alignment_path is not None:               # :134-150
             alignment_path = os.path.join(base_alignment_path, os.path.basename(base_path))
             loaded = [np.load("{}.{}.npy".format(alignment_path, idx)) for idx in range(len(sequences))]
             manual_alignments = np.transpose(loaded, [0, 2, 1])
         linear, alignments = self.model.run(
-            inputs=sequences.astype(np.int32), input_lengths=input_lengths, speaker_id=speaker_ids,
+            inputs=sequences.astype(np.int32), input_lengths=input_lengths, **speaker,
             manual_alignments=manual_alignments, is_manual_attention=manual_alignments is not None)
         linear, alignments = linear.cpu().numpy(), alignments.cpu().numpy()
         if manual_attention_mode > 0:                                                    # :171-205
             new_alignments = manual_alignments_of(alignments, manual_attention_mode)
             linear, alignments = self.model.run(
-                inputs=sequences.astype(np.int32), input_lengths=input_lengths, speaker_id=speaker_ids,
+                inputs=sequences.astype(np.int32), input_lengths=input_lengths, **speaker,
                 manual_alignments=new_alignments, is_manual_attention=True)
             linear, alignments = linear.cpu().numpy(), alignments.cpu().numpy()
         # attention_trim (:242-262): frames to keep per utterance, from the argmax walk over the alignments (device kernel)
@@ -168,10 +177,9 @@ class Synthesizer(object):
             raise _lib.TacoError(_lib.TACO_ERR_ARG, "vocoder must be 'griffin_lim', 'tensorflow' or 'mel', got %r" % (vocoder,))
         sequences = self._token_rows(texts, tokens)
         input_lengths = np.argmax(sequences == EOS_ID, 1).astype(np.int32)             # synthesizer.py:120
-        if type(speaker_ids) == dict:
-            raise Exception("dict-valued speaker_ids is broken in the reference (synthesizer.py:153-164) and not supported")
+        speaker = self._speaker_feed(speaker_ids, len(sequences))
         linear, alignments = self.model.run(
-            inputs=sequences.astype(np.int32), input_lengths=input_lengths, speaker_id=speaker_ids,
+            inputs=sequences.astype(np.int32), input_lengths=input_lengths, **speaker,
             manual_alignments=manual_alignments, is_manual_attention=manual_alignments is not None)
         frames = None
         if attention_trim and end_of_sentence:

@@ -26,10 +26,65 @@ def _stream():
     return C.c_void_p(torch.cuda.current_stream().cuda_stream)
 
 
-class _Plan(object):
-    """Static buffers + one captured hipGraph for a (B, T_in, n_steps, manual?) shape."""
+def speaker_weights(spec, num_speakers, batch):
+    """Host helper: per-row speaker mixture weights, float32 [batch, num_speakers] (taco_abi.h, "speaker mixtures"), from
+      * a dict {speaker_id: weight} -- the same mixture for every row, the form of synthesizer.py:153-164;
+      * a list of length `batch` whose items are ints (that speaker alone: a one-hot row) or such dicts;
+      * an array already of that shape.
+    Weights are used as given: not normalised, not required to sum to 1 (the reference multiplies raw weights).  Raises ValueError for
+    ids outside [0, num_speakers), non-finite weights, a wrong length or shape, and an empty dict."""
+    num_speakers, batch = int(num_speakers), int(batch)
+    if num_speakers < 1 or batch < 1:
+        raise ValueError("num_speakers and batch must be positive, got %d and %d" % (num_speakers, batch))
 
-    def __init__(self, model, B, T_in, n, manual):
+    def is_int(v):
+        return isinstance(v, (int, np.integer)) and not isinstance(v, (bool, np.bool_))
+
+    def check_id(sid):
+        if not is_int(sid):
+            raise ValueError("speaker ids must be integers, got %r" % (sid,))
+        if not 0 <= int(sid) < num_speakers:
+            raise ValueError("speaker id %d outside [0, %d)" % (int(sid), num_speakers))
+        return int(sid)
+
+    def row(item):
+        out = np.zeros((num_speakers,), np.float32)
+        if isinstance(item, dict):
+            if not item:
+                raise ValueError("an empty speaker mixture")
+            for sid, wt in item.items():
+                with np.errstate(over="ignore"):
+                    wt = float(np.float32(wt))
+                if not np.isfinite(wt):
+                    raise ValueError("speaker weight %r of speaker %r is not a finite float32" % (wt, sid))
+                out[check_id(sid)] = wt
+        else:
+            out[check_id(item)] = 1.0
+        return out
+
+    if isinstance(spec, dict):
+        return np.tile(row(spec)[None], (batch, 1))
+    if isinstance(spec, (list, tuple)) and all(is_int(v) or isinstance(v, dict) for v in spec):
+        if len(spec) != batch:
+            raise ValueError("%d speaker entries for a batch of %d rows" % (len(spec), batch))
+        return np.stack([row(v) for v in spec])
+    if torch.is_tensor(spec):
+        spec = spec.detach().cpu().numpy()
+    arr = np.asarray(spec)
+    if arr.dtype.kind not in "fiu" or arr.shape != (batch, num_speakers):
+        raise ValueError("speaker weights must be a numeric array of shape (%d, %d), got %s of shape %s"
+                         % (batch, num_speakers, arr.dtype, arr.shape))
+    with np.errstate(over="ignore"):
+        arr = np.ascontiguousarray(arr, dtype=np.float32)
+    if not np.isfinite(arr).all():
+        raise ValueError("speaker weights must be finite float32 values")
+    return arr
+
+
+class _Plan(object):
+    """Static buffers + one captured hipGraph for a (B, T_in, n_steps, manual?, speaker ids or mixture weights?) shape."""
+
+    def __init__(self, model, B, T_in, n, manual, mix=False):
         hp, dev = model._hparams, model.device
         lib = model._lib
         r, M, F = hp.reduction_factor, hp.num_mels, hp.num_freq
@@ -37,6 +92,8 @@ class _Plan(object):
         self.inputs = torch.zeros((B, T_in), dtype=torch.int32, device=dev)
         self.lengths = torch.zeros((B,), dtype=torch.int32, device=dev)
         self.speaker_id = torch.zeros((B,), dtype=torch.int32, device=dev)
+        # a mix plan reads this buffer on every replay (taco_plan_create_mix): writing it changes the voices
+        self.speaker_weights = torch.zeros((B, model.num_speakers), dtype=torch.float32, device=dev) if mix else None
         self.manual = torch.zeros((B, n, T_in), dtype=torch.float32, device=dev) if manual else None
         self.mel = torch.empty((B, n * r, M), dtype=torch.float32, device=dev)
         self.linear = torch.empty((B, n * r, F), dtype=torch.float32, device=dev)
@@ -47,8 +104,8 @@ class _Plan(object):
         self.ws_bytes = nbytes
         self.handle = C.c_void_p()
         self._lib = lib
-        spk = self.speaker_id if model.num_speakers > 1 else None
-        _lib.check(lib.taco_plan_create(
+        spk = self.speaker_weights if mix else self.speaker_id if model.num_speakers > 1 else None
+        _lib.check((lib.taco_plan_create_mix if mix else lib.taco_plan_create)(
             model._handle, _ptr(self.inputs), _ptr(self.lengths), _ptr(spk), B, T_in, n, _ptr(self.manual),
             _ptr(self.mel), _ptr(self.linear), _ptr(self.align), _ptr(self.stop), _ptr(self.ws), nbytes,
             C.byref(self.handle)))
@@ -122,8 +179,10 @@ class PlanPool(object):
     The reference serves one `sess.run` at a time (synthesizer.py:166-167); this is the same call with
     several requests outstanding.  submit() enqueues and returns immediately; result() waits for that lane."""
 
-    def __init__(self, model, B, T_in, n_steps=None, lanes=1, coalesce=1, engine="auto"):
-        """coalesce > 1: every lane's plan serves `coalesce` requests of B rows at once (one forward over coalesce*B rows: rows are
+    def __init__(self, model, B, T_in, n_steps=None, lanes=1, coalesce=1, engine="auto", speaker_mix=False):
+        """speaker_mix: the lanes' plans take per-row speaker mixture weights (submit(speaker_weights=...)) instead of speaker ids; a
+        request that names ids is then served as one-hot rows (the same bits, k_mix_rows).
+        coalesce > 1: every lane's plan serves `coalesce` requests of B rows at once (one forward over coalesce*B rows: rows are
         independent at inference, and the decoder stages and scans cost almost the same for twice the rows).  submit() then
         returns a ticket (lane, slot), the lane is launched when its last slot is filled (or by flush()), and result(ticket)
         returns that request's rows -- the same function of the request as serving it alone (rows never interact; a layer may pick a
@@ -134,6 +193,9 @@ class PlanPool(object):
             raise ValueError("lanes and coalesce must be >= 1")
         if engine not in ("auto", "persistent", "launch"):
             raise ValueError("engine must be 'auto', 'persistent' or 'launch'")
+        if speaker_mix and model.num_speakers <= 1:
+            raise _lib.TacoError(_lib.TACO_ERR_ARG, "speaker mixtures need a multi-speaker model")
+        self.speaker_mix = bool(speaker_mix)
         current = getattr(model, "_decoder_engine", (1, 0))
         if engine == "launch" or (engine == "auto" and lanes > 1):
             capture_with = (0, 0)
@@ -155,7 +217,7 @@ class PlanPool(object):
             try:
                 for st in self.streams:
                     with torch.cuda.stream(st):
-                        self.plans.append(_Plan(model, B * coalesce, T_in, n, False))
+                        self.plans.append(_Plan(model, B * coalesce, T_in, n, False, self.speaker_mix))
                         self.plans[-1].launch()      # first replay uploads the graph: keep that out of the serving path
                     self.done.append(torch.cuda.Event())
                     self.pending.append(False)
@@ -187,9 +249,16 @@ class PlanPool(object):
             self.filled[lane] = self.coalesce       # launched directly (bench): every slot counts
         self.taken[lane] = 0
 
-    def submit(self, inputs, input_lengths, speaker_id=None, lane=None):
+    def submit(self, inputs, input_lengths, speaker_id=None, lane=None, speaker_weights=None):
         """Enqueue one request of B rows.  Returns what result() takes: the lane (coalesce == 1) or the ticket (lane, slot).
-        Inputs may be host or device arrays."""
+        Inputs may be host or device arrays.  speaker_weights [B, num_speakers] (a pool made with speaker_mix=True) or speaker_id [B],
+        never both."""
+        if speaker_weights is not None:
+            if speaker_id is not None:
+                raise _lib.TacoError(_lib.TACO_ERR_ARG, "speaker_id and speaker_weights are mutually exclusive")
+            if not self.speaker_mix:
+                raise _lib.TacoError(_lib.TACO_ERR_ARG, "this pool's plans were captured with speaker ids: make it with speaker_mix=True")
+            speaker_weights = self.model._weights_dev(speaker_weights, self.B)
         if self.coalesce > 1:
             if lane is not None:
                 raise ValueError("with coalesce > 1 the pool picks the lane")
@@ -216,7 +285,19 @@ class PlanPool(object):
             # or it may hand their blocks out again while these copies are still pending
             ids.record_stream(self.streams[lane])
             lens.record_stream(self.streams[lane])
-            if m.num_speakers > 1:
+            if self.speaker_mix:
+                if speaker_weights is not None:
+                    plan.speaker_weights[rows].copy_(speaker_weights, non_blocking=True)
+                    speaker_weights.record_stream(self.streams[lane])
+                else:       # ids (none: zeros) as one-hot rows
+                    plan.speaker_weights[rows].zero_()
+                    if speaker_id is None:
+                        plan.speaker_weights[rows, 0] = 1.0
+                    else:
+                        spk = m._as_dev(speaker_id, torch.int64)
+                        plan.speaker_weights[rows].scatter_(1, spk.view(-1, 1), 1.0)
+                        spk.record_stream(self.streams[lane])
+            elif m.num_speakers > 1:
                 if speaker_id is None:
                     plan.speaker_id[rows].zero_()
                 else:
@@ -445,9 +526,29 @@ class Tacotron(object):
             x = torch.as_tensor(np.asarray(x))
         return x.to(device=self.device, dtype=dtype).contiguous()
 
-    def plan_for(self, B, T_in, n_steps=None, manual=False):
+    def _weights_dev(self, speaker_weights, B):
+        """speaker_weights [B, num_speakers] as a float32 device tensor; raises where the library would (TACO_ERR_ARG)."""
+        if self.num_speakers <= 1:
+            raise _lib.TacoError(_lib.TACO_ERR_ARG, "speaker_weights given to a single-speaker model")
+        w = self._as_dev(speaker_weights, torch.float32)
+        if tuple(w.shape) != (B, self.num_speakers):
+            raise _lib.TacoError(_lib.TACO_ERR_ARG, "speaker_weights must be [batch, num_speakers] = (%d, %d), got %s"
+                                 % (B, self.num_speakers, tuple(w.shape)))
+        return w
+
+    def _stage_speaker(self, speaker_id, speaker_weights, B):
+        """(entry point suffix, device tensor or None) of a stage call: ids or mixture weights, never both."""
+        if speaker_weights is None:
+            return "", self._as_dev(speaker_id, torch.int32)
+        if speaker_id is not None:
+            raise _lib.TacoError(_lib.TACO_ERR_ARG, "speaker_id and speaker_weights are mutually exclusive")
+        return "_mix", self._weights_dev(speaker_weights, B)
+
+    def plan_for(self, B, T_in, n_steps=None, manual=False, mix=False):
+        """The cached plan of a shape.  mix: the plan captured with per-row speaker mixture weights (its own static
+        [B, num_speakers] buffer) rather than speaker ids; the two kinds are cached side by side."""
         n = self._hparams.max_iters if n_steps is None else n_steps
-        key = (B, T_in, n, bool(manual))
+        key = (B, T_in, n, bool(manual), "mix") if mix else (B, T_in, n, bool(manual))
         plan = self._plans.pop(key, None)
         if plan is None:
             # every distinct shape owns a captured graph plus output / workspace buffers (tens of MB): keep the most recently used
@@ -455,22 +556,25 @@ class Tacotron(object):
             while len(self._plans) >= self.MAX_PLANS:
                 self._plans.pop(next(iter(self._plans)))
             with torch.cuda.device(self.device):
-                plan = _Plan(self, B, T_in, n, manual)
+                plan = _Plan(self, B, T_in, n, manual, bool(mix))
         self._plans[key] = plan          # (re)inserted last = most recently used
         return plan
 
-    def plan_pool(self, B, T_in, n_steps=None, lanes=1, coalesce=1, engine="auto"):
+    def plan_pool(self, B, T_in, n_steps=None, lanes=1, coalesce=1, engine="auto", speaker_mix=False):
         """`lanes` forwards of this shape in flight at once, each serving `coalesce` requests of B rows (PlanPool)."""
-        return PlanPool(self, B, T_in, n_steps, lanes, coalesce, engine)
+        return PlanPool(self, B, T_in, n_steps, lanes, coalesce, engine, speaker_mix)
 
     def run(self, inputs=None, input_lengths=None, speaker_id=None, manual_alignments=None,
-            is_manual_attention=None, n_steps=None, honor_stop=True):
+            is_manual_attention=None, n_steps=None, honor_stop=True, speaker_weights=None):
         """One forward.  Returns (linear_outputs, alignments) as device tensors and refreshes the
         public attributes.  `manual_alignments` [B,T_dec,T_in] + `is_manual_attention`
         (rnn_wrappers.py:313-317).  With honor_stop the outputs are cut where the reference's stop rule
-        (helpers.py:29 + dynamic_decode) would have ended the loop (one host sync)."""
+        (helpers.py:29 + dynamic_decode) would have ended the loop (one host sync).  `speaker_weights` [B, num_speakers] (see
+        speaker_weights()) blends the trained speakers per row, the intent of synthesizer.py:153-164; it excludes `speaker_id`."""
         if self._handle is None:
             raise RuntimeError("initialize() must be called first")
+        if speaker_weights is not None and speaker_id is not None:
+            raise _lib.TacoError(_lib.TACO_ERR_ARG, "speaker_id and speaker_weights are mutually exclusive")
         inputs = self.inputs if inputs is None else inputs
         input_lengths = self.input_lengths if input_lengths is None else input_lengths
         speaker_id = self.speaker_id if speaker_id is None else speaker_id
@@ -484,11 +588,16 @@ class Tacotron(object):
         B, T_in = ids.shape
         lens = self._as_dev(input_lengths, torch.int32)
         manual = bool(is_manual_attention)
-        plan = self.plan_for(B, T_in, n_steps, manual)
+        mix = speaker_weights is not None
+        if mix:
+            speaker_weights = self._weights_dev(speaker_weights, B)
+        plan = self.plan_for(B, T_in, n_steps, manual, mix)
         with torch.cuda.device(self.device):
             plan.inputs.copy_(ids)
             plan.lengths.copy_(lens)
-            if self.num_speakers > 1:
+            if mix:
+                plan.speaker_weights.copy_(speaker_weights)
+            elif self.num_speakers > 1:
                 if speaker_id is None:      # placeholder_with_default(zeros) (synthesizer.py:43-44)
                     plan.speaker_id.zero_()
                 else:
@@ -514,7 +623,10 @@ class Tacotron(object):
                     r = self._hparams.reduction_factor
                     mel = mel.view(B, plan.n, -1)[:, :stop].reshape(B, stop * r, self._hparams.num_mels).contiguous()
                     align = align[:, :, :stop].contiguous()
-                    linear = self.postnet(mel, speaker_id=plan.speaker_id if self.num_speakers > 1 else None)
+                    if mix:
+                        linear = self.postnet(mel, speaker_weights=plan.speaker_weights)
+                    else:
+                        linear = self.postnet(mel, speaker_id=plan.speaker_id if self.num_speakers > 1 else None)
         self.mel_outputs, self.linear_outputs, self.alignments = mel, linear, align
         return linear, align
 
@@ -523,21 +635,22 @@ class Tacotron(object):
         n = int(self._lib.taco_stage_workspace_bytes(self._handle, B, T))
         return torch.empty((n,), dtype=torch.uint8, device=self.device), n
 
-    def encoder(self, inputs, input_lengths, speaker_id=None):
+    def encoder(self, inputs, input_lengths, speaker_id=None, speaker_weights=None):
         ids, lens = self._as_dev(inputs, torch.int32), self._as_dev(input_lengths, torch.int32)
-        spk = self._as_dev(speaker_id, torch.int32)
         B, T = ids.shape
+        mix, spk = self._stage_speaker(speaker_id, speaker_weights, B)
         out = torch.empty((B, T, 2 * self._hparams.enc_rnn_size), dtype=torch.float32, device=self.device)
         ws, n = self._stage_ws(B, T)
-        _lib.check(self._lib.taco_encoder_forward(self._handle, _stream(), _ptr(ids), _ptr(lens), _ptr(spk), B, T,
-                                                  _ptr(out), _ptr(ws), n))
+        _lib.check(getattr(self._lib, "taco_encoder_forward" + mix)(self._handle, _stream(), _ptr(ids), _ptr(lens), _ptr(spk), B, T,
+                                                                    _ptr(out), _ptr(ws), n))
         return out
 
-    def decoder(self, encoder_out, n_steps, speaker_id=None, manual_alignments=None, teacher_frames=None, debug=False):
+    def decoder(self, encoder_out, n_steps, speaker_id=None, manual_alignments=None, teacher_frames=None, debug=False,
+                speaker_weights=None):
         hp = self._hparams
         enc = self._as_dev(encoder_out, torch.float32)
         B, T_in, _ = enc.shape
-        spk = self._as_dev(speaker_id, torch.int32)
+        mix, spk = self._stage_speaker(speaker_id, speaker_weights, B)
         man = self._as_dev(manual_alignments, torch.float32)
         tf_ = self._as_dev(teacher_frames, torch.float32)
         r, M = hp.reduction_factor, hp.num_mels
@@ -547,21 +660,21 @@ class Tacotron(object):
         dbgw = hp.attention_state_size + 2 * hp.enc_rnn_size + hp.dec_layer_num * hp.dec_rnn_size
         dbg = torch.empty((n_steps, B, dbgw), dtype=torch.float32, device=self.device) if debug else None
         ws, n = self._stage_ws(B, max(T_in, n_steps))
-        _lib.check(self._lib.taco_decoder_forward(self._handle, _stream(), _ptr(enc), _ptr(spk), B, T_in, n_steps,
-                                                  _ptr(man), _ptr(tf_), _ptr(mel), _ptr(align), _ptr(stop), _ptr(dbg),
-                                                  _ptr(ws), n))
+        _lib.check(getattr(self._lib, "taco_decoder_forward" + mix)(self._handle, _stream(), _ptr(enc), _ptr(spk), B, T_in, n_steps,
+                                                                    _ptr(man), _ptr(tf_), _ptr(mel), _ptr(align), _ptr(stop), _ptr(dbg),
+                                                                    _ptr(ws), n))
         return mel, align, stop, dbg
 
-    def postnet(self, mel, return_post=False, speaker_id=None):
+    def postnet(self, mel, return_post=False, speaker_id=None, speaker_weights=None):
         hp = self._hparams
         mel = self._as_dev(mel, torch.float32)
-        spk = self._as_dev(speaker_id, torch.int32)
         B, T, _ = mel.shape
+        mix, spk = self._stage_speaker(speaker_id, speaker_weights, B)
         lin = torch.empty((B, T, hp.num_freq), dtype=torch.float32, device=self.device)
         post = torch.empty((B, T, 2 * hp.post_rnn_size), dtype=torch.float32, device=self.device) if return_post else None
         ws, n = self._stage_ws(B, T)
-        _lib.check(self._lib.taco_postnet_forward(self._handle, _stream(), _ptr(mel), _ptr(spk), B, T, _ptr(lin), _ptr(post),
-                                                  _ptr(ws), n))
+        _lib.check(getattr(self._lib, "taco_postnet_forward" + mix)(self._handle, _stream(), _ptr(mel), _ptr(spk), B, T, _ptr(lin),
+                                                                    _ptr(post), _ptr(ws), n))
         return (lin, post) if return_post else lin
 
     def set_batch_invariant(self, on=True):
