@@ -506,7 +506,12 @@ __device__ __forceinline__ void go_body(const GdArgs& a, float* gx_smem, int pla
       constexpr int R0 = (NREG / 2) * D;
 #pragma unroll
       for (int g = 0; g < 3; ++g) x0[D][g] = xq[(size_t)ring * SLOT + ((size_t)(D * GX_BLK + sb) * 3 + g) * UPM + wave * UPW + ui];
-      // (r_i, u_i) of unit i in one v_pk_fma_f32 per input: registers R0 + 8i + e (r) and R0 + 8i + 4 + e (u), the state value broadcast
+      // (r_i, u_i) of unit i in one v_pk_fma_f32 per input: registers R0 + 8i + e (r) and R0 + 8i + 4 + e (u), the state value broadcast.
+      // (Round 8, measured and NOT adopted: r alone in front of the publish -- units (i, i + 1) per v_pk_fma_f32, go_reduce<UPW, 1> -- and u's products,
+      // reduction and sigmoid behind the store.  Bit-identical, 79 -> 60 and 48 -> 29 VALU instructions between barrier and publish, the store 108 / 28
+      // clocks earlier in the phase -- but the traced phases grew from 676 / 568 to 752 / 704 clocks, the collects did not shrink by as much, and
+      // k_bigru_oct<4> went from 766 to 805 us per C2 scan: a wave's deferred work sits in front of ITS collect, and the other wave of the SIMD is still
+      // in front of its publish.  profiles/r08_ab_publish_first.txt.)
       const float4 hx = *reinterpret_cast<const float4*>(hs + D * H + 4 * lane);
       taco_f32x2 acc[UPW];
 #pragma unroll
@@ -529,6 +534,7 @@ __device__ __forceinline__ void go_body(const GdArgs& a, float* gx_smem, int pla
       float rh = rr * hv[D];
       asm volatile("" : "+v"(pre), "+v"(pre2), "+v"(rh));      // the gather in flight has landed: wait for it HERE, ahead of the publish store (see gd_landed)
       if (pub) { if (GO_DYN) dx_publish(X + (size_t)D * 2 * H + unit, rh, tag, rt); else go_publish<WT>(X + (size_t)D * 2 * H + unit, rh, tag); }
+      GO_STAMP(9 + D);                  // the publish store of a gates phase is issued (TRACE: tools/trace_bigru.py)
       if (TAPE && pub && active) {      // gates of the active steps at their true time (modules.py:82-96 / A.7), for the backward scan -- BEHIND the publish: the exchange is the critical path
         float* gs = a.gsave + ((size_t)row * T + (D ? L - 1 - s : s)) * 6 * H + D * 3 * H + unit;
         gs[0] = rr; gs[H] = gv[D];

@@ -469,6 +469,49 @@ __device__ __forceinline__ void dxw_agx1(const taco_f32x2 (&WP)[DX_NWP], const f
     DXQ_FMA(p[r], xv, WP[k]); sg[0][r] = fmaf(WP[k + 1].x, xv, sg[0][r]);
   }
 }
+// The same two passes split by consumer (round 8, DX_PUB_FIRST): the (r, u) pair, which the publish of r * h waits for, and the candidate-x
+// column, which runs behind that publish.  Per accumulator the FMAs and their order are those of dxw_agx2 / dxw_agx1.
+template <int RG>
+__device__ __forceinline__ void dxw_agx2_pair(const taco_f32x2 (&WP)[DX_NWP], const float* x, int lane, taco_f32x2 (&p)[RG]) {
+  constexpr int k = DXR_AGX / 2;
+#pragma unroll
+  for (int r = 0; r < RG; ++r) {
+    const float2 xv = *reinterpret_cast<const float2*>(x + r * DXS_LD + 2 * lane);
+    DXQ_FMA(p[r], xv.x, WP[k]); DXQ_FMA(p[r], xv.y, WP[k + 1]);
+  }
+}
+template <int RG>
+__device__ __forceinline__ void dxw_agx2_single(const taco_f32x2 (&WP)[DX_NWP], const float* x, int lane, float (&sg)[1][RG]) {
+  constexpr int k = DXR_AGX / 2;
+#pragma unroll
+  for (int r = 0; r < RG; ++r) {
+    const float2 xv = *reinterpret_cast<const float2*>(x + r * DXS_LD + 2 * lane);
+    sg[0][r] = fmaf(WP[k + 2].x, xv.x, sg[0][r]); sg[0][r] = fmaf(WP[k + 2].y, xv.y, sg[0][r]);
+  }
+}
+template <int RG>
+__device__ __forceinline__ void dxw_agx1_pair(const taco_f32x2 (&WP)[DX_NWP], const float* x, int lane, taco_f32x2 (&p)[RG]) {
+  constexpr int k = DXR_AGX / 2;
+#pragma unroll
+  for (int r = 0; r < RG; ++r) DXQ_FMA(p[r], x[r * DXS_LD + lane], WP[k]);
+}
+template <int RG>
+__device__ __forceinline__ void dxw_agx1_single(const taco_f32x2 (&WP)[DX_NWP], const float* x, int lane, float (&sg)[1][RG]) {
+  constexpr int k = DXR_AGX / 2;
+#pragma unroll
+  for (int r = 0; r < RG; ++r) sg[0][r] = fmaf(WP[k + 1].x, x[r * DXS_LD + lane], sg[0][r]);
+}
+// Round 8: a GRU gates stage publishes r * h, which needs the reset gate alone.  With DX_PUB_FIRST the stage runs, behind its gather, the (r, u)
+// pair's input rows (r and u share every v_pk_fma_f32: leaving u out would save no instruction), reduces the r column ALONE, publishes, and only
+// then runs the candidate-x column (GRU 1: the (candidate-x, o0) pair), reduces u and those columns and takes u's sigmoid -- in the window in which
+// the gather behind the stage sleeps before its first poll.  Every column keeps its FMA chain and its reduction tree (dxs_reduce acts per column).
+// The deferred passes read their input rows from LDS a second time; the regions (P2 / OUT2, CTX, OUT1) are next written behind the barrier that
+// follows the stage's own gather, so the second read sees what the first saw.  Bit 0: attention GRU, bit 1: GRU 1, bit 2: GRU 2.
+#ifndef DX_PUB_FIRST
+#define DX_PUB_FIRST 7
+#endif
+// what follows in the source is issued behind the publish stores in front of it: its LDS reads cannot be merged with earlier ones or hoisted
+__device__ __forceinline__ void dx_behind_publish() { asm volatile("" ::: "memory"); }
 // prenet layer 3 (PD = 3): one column over the 128-wide prenet-2 output, registers DXR_AGX + 3, + 4
 template <int RG>
 __device__ __forceinline__ void dxw_p3(const taco_f32x2 (&WP)[DX_NWP], const float* x, int lane, float (&acc)[1][RG]) {
@@ -563,7 +606,7 @@ __device__ __forceinline__ void dxs_reduce(const float (&a)[NC][RG], float (&out
 #endif
 __host__ __device__ constexpr int dx_site_delay(int site, int dflt, int RG = 4) {
   //                          p2 p3 rha ha sc ctx rh1 h1 rh2 h2 p1
-  constexpr int tuned4[11] = {4, 5, 6, 5, 0, 0, 5, 5, 0, 4, 0};      // swept at C2 (four rows per group); also serves one and two rows (C1 / C5 got faster with it)
+  constexpr int tuned4[11] = {2, 5, 0, 5, 0, 3, 2, 3, 0, 3, 0};      // swept at C2 (four rows per group) on the publish-first gate stages (round 8; rounds 6-7: 4 5 6 5 0 0 5 5 0 4 0); also serves one and two rows
   constexpr int tuned8[11] = {7, 5, 3, 5, 0, 6, 5, 6, 4, 6, 2};      // swept on a 64-row pass (eight rows per group: longer producer phases): 1972 (all 5) / 1980 (the table above) -> 1940 us per call
   return DX_DLY_TUNED ? (RG == 8 ? tuned8[site] : tuned4[site]) : dflt;
 }
@@ -1024,6 +1067,8 @@ __device__ __forceinline__ void dx_body(const DxArgs& a, float* dx_smem, int gro
 #define DX_BIAS_AHEAD(var, slot) float var = bl[(slot) * DX_NW + wave]
 #define DX_BIAS_HERE(var) asm volatile("" : "+v"(var))
   float g_u[RL], g_cx[RL], g_h[RL], g_o0[RL];            // live between the two stages of a GRU cell
+  // publish r * h first (DX_PUB_FIRST); eight rows per group keeps the one-pass order: 256 VGPRs and none to spare
+  constexpr bool PF_A = (DX_PUB_FIRST & 1) && RG < 8, PF_1 = (DX_PUB_FIRST & 2) && RG < 8, PF_2 = (DX_PUB_FIRST & 4) && RG < 8;
   // tape (TAPE): the lane that owns (row, column) of a stage writes it; trow = float offset of step 0 of the lane's row in a [B, n, 256] array
   // (32-bit element offsets: the host checks DXT_N * tstride < 2^31, so an address is the SGPR base + one VGPR)
   unsigned trow[RL];
@@ -1115,7 +1160,32 @@ __device__ __forceinline__ void dx_body(const DxArgs& a, float* dx_smem, int gro
     }
     DX_STAMP(1);
     // ================= attention GRUCell (tacotron.py:127-130; A.6): gates, then candidate =================
-    {
+    if constexpr (PF_A) {
+      float ar[1][RG], sr[1][RL], rgv[RL];
+      if constexpr (PD == 3) dxw_agx1_pair<RG>(WP, st + DXS_OUT2, lane, ag01);
+      else dxw_agx2_pair<RG>(WP, st + DXS_P2, lane, ag01);
+#pragma unroll
+      for (int r = 0; r < RG; ++r) ar[0][r] = ag01[r].x;
+      dxs_reduce<1, RG>(ar, sr, lane);
+#pragma unroll
+      for (int q = 0; q < RL; ++q) {
+        rgv[q] = dx_sigmoid_fast(sr[0][q] + DX_RB(DXRB_AR, q));
+        if (epl) dx_publish<WTC>(dx_at(X, (unsigned)(xl.rha + erow[q] * DX_W + en)), rgv[q] * g_h[q], tag, rt);
+      }
+      dx_behind_publish();
+      float au[2][RG], su[2][RL];
+      if constexpr (PD == 3) dxw_agx1_single<RG>(WP, st + DXS_OUT2, lane, ag2);
+      else dxw_agx2_single<RG>(WP, st + DXS_P2, lane, ag2);
+#pragma unroll
+      for (int r = 0; r < RG; ++r) { au[0][r] = ag01[r].y; au[1][r] = ag2[0][r]; }
+      dxs_reduce<2, RG>(au, su, lane);
+#pragma unroll
+      for (int q = 0; q < RL; ++q) {
+        g_u[q] = dx_sigmoid_fast(su[0][q] + DX_RB(DXRB_AU, q));
+        g_cx[q] = su[1][q] + DX_RB(DXRB_AX, q);
+        DX_TAPE(DXT_RA, q, rgv[q]); DX_TAPE(DXT_UA, q, g_u[q]); DX_TAPE(DXT_RHA, q, rgv[q] * g_h[q]);
+      }
+    } else {
       float s[3][RL];
       if constexpr (PD == 3) dxw_agx1<RG>(WP, st + DXS_OUT2, lane, ag01, ag2);
       else dxw_agx2<RG>(WP, st + DXS_P2, lane, ag01, ag2);
@@ -1292,6 +1362,33 @@ __device__ __forceinline__ void dx_body(const DxArgs& a, float* dx_smem, int gro
         dxw_pair<DXR_G1H, RG>(WP, st + DXS_H1, lane, g1p0);
         dxw_quad<DXR_G1A, RG>(WP, st + DXS_HATT, lane, g1p0, g1p1);
       }
+      if constexpr (PF_1) {
+        float ar[1][RG], sr[1][RL], rgv[RL];
+        dxw_pair<DXR_G1B, RG>(WP, st + DXS_CTX, lane, g1p0);
+#pragma unroll
+        for (int r = 0; r < RG; ++r) ar[0][r] = g1p0[r].x;
+        dxs_reduce<1, RG>(ar, sr, lane);
+        DX_STAMP(12);
+#pragma unroll
+        for (int q = 0; q < RL; ++q) {
+          rgv[q] = dx_sigmoid_fast(sr[0][q] + DX_RB(DXRB_G1R, q));
+          if (epl) dx_publish<WTC>(dx_at(X, (unsigned)(xl.rh1 + erow[q] * DX_W + en)), rgv[q] * g_h[q], tag, rt);
+        }
+        DX_STAMP(13);
+        dx_behind_publish();
+        dxw_pair<DXR_G1B + 8, RG>(WP, st + DXS_CTX, lane, g1p1);
+        float g1d[3][RG], sd[3][RL];
+#pragma unroll
+        for (int r = 0; r < RG; ++r) { g1d[0][r] = g1p0[r].y; g1d[1][r] = g1p1[r].x; g1d[2][r] = g1p1[r].y; }
+        dxs_reduce<3, RG>(g1d, sd, lane);
+#pragma unroll
+        for (int q = 0; q < RL; ++q) {
+          g_u[q] = dx_sigmoid_fast(sd[0][q] + DX_RB(DXRB_G1U, q));
+          g_cx[q] = sd[1][q] + DX_RB(DXRB_G1X, q);
+          g_o0[q] = sd[2][q] + DX_RB(DXRB_O0, q);
+          DX_TAPE(DXT_R1, q, rgv[q]); DX_TAPE(DXT_U1, q, g_u[q]); DX_TAPE(DXT_RH1, q, rgv[q] * g_h[q]); DX_TAPE(DXT_O0, q, g_o0[q]);
+        }
+      } else {
       dxw_quad<DXR_G1B, RG>(WP, st + DXS_CTX, lane, g1p0, g1p1);
       float g1a[4][RG];
 #pragma unroll
@@ -1308,6 +1405,7 @@ __device__ __forceinline__ void dx_body(const DxArgs& a, float* dx_smem, int gro
         DX_TAPE(DXT_R1, q, rg); DX_TAPE(DXT_U1, q, g_u[q]); DX_TAPE(DXT_RH1, q, rg * g_h[q]); DX_TAPE(DXT_O0, q, g_o0[q]);
       }
       DX_STAMP(13);
+      }
     }
     DX_BIAS_AHEAD(b_g1c, DXB_G1C);
     dx_gather_at<RG, DX_W, false, DXS_LD, DX_NT, DX_DLY(6, DX_FIRST_POLL_DELAY)>(X, (unsigned)xl.rh1, tag, st, DXS_T, 0, 0, tid, rt);
@@ -1347,6 +1445,30 @@ __device__ __forceinline__ void dx_body(const DxArgs& a, float* dx_smem, int gro
     {
       float s[3][RL];
       if (!G1_AHEAD) dxw_pair<DXR_G2H, RG>(WP, st + DXS_H2, lane, g2p);
+      if constexpr (PF_2) {
+        float ar[1][RG], sr[1][RL], rgv[RL];
+        dxw_pair<DXR_G2X, RG>(WP, st + DXS_OUT1, lane, g2p);
+#pragma unroll
+        for (int r = 0; r < RG; ++r) ar[0][r] = g2p[r].x;
+        dxs_reduce<1, RG>(ar, sr, lane);
+#pragma unroll
+        for (int q = 0; q < RL; ++q) {
+          rgv[q] = dx_sigmoid_fast(sr[0][q] + bl[DXB_G2R * DX_NW + wave]);
+          if (epl) dx_publish<WTC>(dx_at(X, (unsigned)(xl.rh2 + erow[q] * DX_W + en)), rgv[q] * g_h[q], tag, rt);
+        }
+        dx_behind_publish();
+        dxw_single<DXR_G2X + 8, RG>(WP, st + DXS_OUT1, lane, g2c);
+        float g2d[2][RG], sd[2][RL];
+#pragma unroll
+        for (int r = 0; r < RG; ++r) { g2d[0][r] = g2p[r].y; g2d[1][r] = g2c[0][r]; }
+        dxs_reduce<2, RG>(g2d, sd, lane);
+#pragma unroll
+        for (int q = 0; q < RL; ++q) {
+          g_u[q] = dx_sigmoid_fast(sd[0][q] + bl[DXB_G2U * DX_NW + wave]);
+          g_cx[q] = sd[1][q];
+          DX_TAPE(DXT_R2, q, rgv[q]); DX_TAPE(DXT_U2, q, g_u[q]); DX_TAPE(DXT_RH2, q, rgv[q] * g_h[q]);
+        }
+      } else {
       dxw_pair_single<DXR_G2X, DXR_G2X + 8, RG>(WP, st + DXS_OUT1, lane, g2p, g2c);
       float g2a[3][RG];
 #pragma unroll
@@ -1359,6 +1481,7 @@ __device__ __forceinline__ void dx_body(const DxArgs& a, float* dx_smem, int gro
         g_cx[q] = s[2][q];
         if (epl) dx_publish<WTC>(dx_at(X, (unsigned)(xl.rh2 + erow[q] * DX_W + en)), rg * g_h[q], tag, rt);
         DX_TAPE(DXT_R2, q, rg); DX_TAPE(DXT_U2, q, g_u[q]); DX_TAPE(DXT_RH2, q, rg * g_h[q]);
+      }
       }
     }
     DX_BIAS_AHEAD(b_g2c, DXB_G2C);

@@ -58,9 +58,15 @@ print("B=%d T=%d persist %d kernel %s: %.1f us total (input projection %.1f + sc
       % (B, T, PERSIST, kernel, us, us_gemm, scan_us, scan_us / T, step, cpu))
 med = np.median(d[1:], axis=0)
 print("  " + "  ".join("%s %.0f" % (n, c) for n, c in zip(names, med)) + "   (clocks)")
+# k_bigru_oct stamps the publish store of its two gates phases (slots 9, 10): where in the phase r*h leaves, and what runs behind it
+pub = None
+if kernel.startswith("k_bigru_oct") and (tr[1:, 9:11] > 0).all():
+    pub = {"gates F": (float(np.median(tr[1:, 9] - tr[1:, 0])), float(med[0])), "gates B": (float(np.median(tr[1:, 10] - tr[1:, 2])), float(med[2]))}
+    print("  publish store issued at clock " + ", ".join("%.0f of %.0f in %s" % (at, of, n) for n, (at, of) in pub.items()))
 if jpath:
     recs = json.load(open(jpath)) if os.path.exists(jpath) else []
     import bench
     recs.append({"kernel_source_hash": bench.source_hash(), "B": B, "T": T, "persist": PERSIST, "kernel": kernel, "total_us": us, "input_projection_us": us_gemm, "scan_us": scan_us,
-                 "step_clocks": step, "clocks_per_us": cpu, "phases_clocks": {n: float(c) for n, c in zip(names, med)}})
+                 "step_clocks": step, "clocks_per_us": cpu, "phases_clocks": {n: float(c) for n, c in zip(names, med)},
+                 "gates_publish_clock": {n: at for n, (at, of) in pub.items()} if pub else None})
     json.dump(recs, open(jpath, "w"), indent=1)
