@@ -43,9 +43,9 @@ int taco_debug_set_persistent(taco_model* m, int on);
  * then gets: ff_plan, prenet_chain_why, head_sweep_why and gemm_plan (csrc/taco_lib.hip), told by taco_model_engine_plan. */
 int taco_debug_set_bf3(taco_model* m, int on, int tile_n);
 
-/* test hook: > 0 = taco_forward_infer runs the post-net feed-forward stages behind the decoder on a second stream
- * (fork/join by events, a parallel branch in the hipGraph) in chunks of max(on,16) decoder steps; 0 (default) =
- * strictly sequential, which measures faster on MI355X (profiles/README.md) */
+/* retired: the chunked post-net overlap (feed-forward stages on a second stream behind a launch-per-stage decoder loop; it measured slower,
+ * profiles/README.md).  on = 0 returns 0; any other value is TACO_ERR_ARG and changes nothing.  Kept because bench.py --overlap calls it. */
+int taco_debug_set_overlap(taco_model* m, int on);
 /* debug/test: 0 = run decoder prenet layer 1 as its own launch every step (default 1: folded into the previous step's
  * frame-projection launch through composite weights; same function, rounding differs at the 1e-7 level) */
 int taco_debug_set_fuse_prenet(taco_model* m, int on);
@@ -56,7 +56,6 @@ int taco_debug_set_fuse_concat(taco_model* m, int on);
 /* debug/test: attention launch shape.  -1 (default): one workgroup per batch row, or -- few rows, long inputs (B <= 16, T_in >= 256) --
  * two launches with 4 slices per row; 0: always one workgroup per row; n > 1: always n slices per row */
 int taco_debug_set_att_split(taco_model* m, int slices);
-int taco_debug_set_overlap(taco_model* m, int on);
 
 /* Decoder loop engine (reference: rnn_wrappers.py:218-341,367-415; helpers.py:9-32).  mode 1 (default): the whole loop runs as ONE
  * persistent, weight-stationary launch (csrc/taco_decoder_xcd.h) whenever the configuration fits it -- reference widths (256-wide

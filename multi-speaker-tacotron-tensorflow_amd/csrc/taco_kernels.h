@@ -97,7 +97,6 @@ struct GemmArgs {
                           // (tf.reverse_sequence, A.7); null lengths = T
   float* out;             // [M, ldo]
   int ldx, M, T, Cin, cin_pad, mpw, act, ldres, ldrv, ldo, vec_ok, rev_col0;
-  int t_begin, t_len, tiles_per_b;   // time-window mode (t_len > 0): rows (b, t_begin + i), i < t_len, for every batch row b
   float* aux0; float* aux1;          // training tape (DUAL only, nullable): highway H = relu(.) and T = sigmoid(.), [M, ldo]
   GemmVar v[16];          // one per blockIdx.z (conv-bank widths); by value so the fields arrive by scalar loads
 };
@@ -150,12 +149,11 @@ __global__ __launch_bounds__(64 * WM * WN * KS) void k_gemm(const GemmArgs a_in)
   constexpr int BM = WM * TM * 32, BN = WN * TN * 32;
   extern __shared__ __attribute__((aligned(16))) float smem[];
   struct { const float* x; const int* gather; const float* res; const float* rowvec; const int* rev_len; float* out;
-           int ldx, M, T, Cin, cin_pad, mpw, act, ldres, ldrv, ldo, vec_ok, rev_col0, t_begin, t_len, tiles_per_b;
+           int ldx, M, T, Cin, cin_pad, mpw, act, ldres, ldrv, ldo, vec_ok, rev_col0;
            float* aux0; float* aux1; } a =
       {a_in.x, a_in.gather, a_in.res, a_in.rowvec, a_in.rev_len, a_in.out, a_in.ldx, a_in.M, a_in.T, a_in.Cin, a_in.cin_pad,
-       a_in.mpw, a_in.act, a_in.ldres, a_in.ldrv, a_in.ldo, a_in.vec_ok, a_in.rev_col0, a_in.t_begin, a_in.t_len, a_in.tiles_per_b,
+       a_in.mpw, a_in.act, a_in.ldres, a_in.ldrv, a_in.ldo, a_in.vec_ok, a_in.rev_col0,
        a_in.aux0, a_in.aux1};
-  PIN(a.t_begin); PIN(a.t_len); PIN(a.tiles_per_b);
   PIN(a.rev_len); PIN(a.rev_col0); PIN(a.aux0); PIN(a.aux1);
   PIN(a.x); PIN(a.gather); PIN(a.res); PIN(a.rowvec); PIN(a.out);
   PIN(a.ldx); PIN(a.M); PIN(a.T); PIN(a.Cin); PIN(a.cin_pad); PIN(a.mpw); PIN(a.act); PIN(a.ldres); PIN(a.ldrv); PIN(a.ldo); PIN(a.vec_ok);
@@ -165,15 +163,7 @@ __global__ __launch_bounds__(64 * WM * WN * KS) void k_gemm(const GemmArgs a_in)
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int ks = wave / (WM * WN), wmn = wave % (WM * WN), wm = wmn / WN, wn = wmn % WN;
-  // flat mode: M-tiles over rows m = b*T + t; window mode: tiles over [t_begin, t_begin + t_len) of every batch row
-  // (the post-net's feed-forward stages run chunk by chunk behind the decoder; halo rows outside the window are
-  //  read like any other row -- they were produced by earlier chunks)
-  int m0 = blockIdx.x * BM, row_limit = a.M;
-  if (a.t_len > 0) {
-    const int bb = blockIdx.x / a.tiles_per_b, tile = blockIdx.x - bb * a.tiles_per_b;
-    m0 = bb * a.T + a.t_begin + tile * BM;
-    row_limit = bb * a.T + a.t_begin + a.t_len;
-  }
+  const int m0 = blockIdx.x * BM, row_limit = a.M;
   const int n0 = blockIdx.y * BN;
   const int l31 = lane & 31, lh = lane >> 5;
   const int rows = BM + v.kw - 1;
@@ -396,25 +386,20 @@ __global__ __launch_bounds__(64 * WM * WN * KS, (KS == 1 && GPI == 1 && !X6) ? 2
   constexpr int BM = WM * TM * 32, BN = WN * TN * 32;
   extern __shared__ __attribute__((aligned(16))) float smem[];
   struct { const float* x; const int* gather; const float* res; const float* rowvec; const int* rev_len; float* out;
-           int ldx, M, T, Cin, cin_pad, mpw, act, ldres, ldrv, ldo, vec_ok, rev_col0, t_begin, t_len, tiles_per_b; float* aux0; float* aux1; } a =
+           int ldx, M, T, Cin, cin_pad, mpw, act, ldres, ldrv, ldo, vec_ok, rev_col0; float* aux0; float* aux1; } a =
       {a_in.x, a_in.gather, a_in.res, a_in.rowvec, a_in.rev_len, a_in.out, a_in.ldx, a_in.M, a_in.T, a_in.Cin, a_in.cin_pad,
-       a_in.mpw, a_in.act, a_in.ldres, a_in.ldrv, a_in.ldo, a_in.vec_ok, a_in.rev_col0, a_in.t_begin, a_in.t_len, a_in.tiles_per_b,
+       a_in.mpw, a_in.act, a_in.ldres, a_in.ldrv, a_in.ldo, a_in.vec_ok, a_in.rev_col0,
        a_in.aux0, a_in.aux1};
   PIN(a.x); PIN(a.gather); PIN(a.res); PIN(a.rowvec); PIN(a.out); PIN(a.rev_len); PIN(a.aux0); PIN(a.aux1);
   PIN(a.ldx); PIN(a.M); PIN(a.T); PIN(a.Cin); PIN(a.mpw); PIN(a.act); PIN(a.ldres); PIN(a.ldrv); PIN(a.ldo); PIN(a.vec_ok);
-  PIN(a.rev_col0); PIN(a.t_begin); PIN(a.t_len); PIN(a.tiles_per_b);
+  PIN(a.rev_col0);
   GemmVar v = a_in.v[blockIdx.z];
   PIN(v.bias); PIN(v.bias2); PIN(v.bn_scale); PIN(v.bn_shift); PIN(v.bh); PIN(v.bl); PIN(v.bh2); PIN(v.bl2); PIN(v.bl3); PIN(v.bl3_2);
   PIN(v.kw); PIN(v.padl); PIN(v.NT); PIN(v.N); PIN(v.coff); PIN(v.K16); PIN(v.cin_pad16);
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int ks = wave / (WM * WN), wmn = wave % (WM * WN), wm = wmn / WN, wn = wmn % WN;
-  int m0 = blockIdx.x * BM, row_limit = a.M;
-  if (a.t_len > 0) {
-    const int bb = blockIdx.x / a.tiles_per_b, tile = blockIdx.x - bb * a.tiles_per_b;
-    m0 = bb * a.T + a.t_begin + tile * BM;
-    row_limit = bb * a.T + a.t_begin + a.t_len;
-  }
+  const int m0 = blockIdx.x * BM, row_limit = a.M;
   const int n0 = blockIdx.y * BN;
   const int l31 = lane & 31, lh = lane >> 5;
   const int rows = BM + v.kw - 1;
@@ -1938,7 +1923,8 @@ __global__ __launch_bounds__(64 * ATS_NW) void k_att_context(const AttnArgs a_in
 // all exactly 0; the loop ends after the first step at which every row is finished.
 // nz [n_steps, B] : 1 if row b emitted any non-zero at step t.
 // errw (nullable): the sticky device error word of the persistent kernels; when it is set the stop word becomes its negative (the
-// forward's own error latch, see latch_errors() in taco_lib.hip) -- the whole forward ends in this one launch
+// forward's own error latch: the caller that reads the stop step learns that THIS forward's outputs are invalid without a second
+// transfer) -- the whole forward ends in this one launch
 __global__ __launch_bounds__(1024) void k_stop_step(const int* nz, int B, int n_steps, int* stop, const unsigned* errw = nullptr) {
   // all loads independent (a per-row serial walk with an early exit was a chain of n_steps dependent cache misses: 34 us at C2); 1024 threads,
   // (step, row) advanced without a division: four loads per thread at C2 (round 5: 10.7 -> ~4 us on the tail of every forward)
@@ -1967,11 +1953,6 @@ __global__ __launch_bounds__(1024) void k_stop_step(const int* nz, int B, int n_
     const unsigned e = errw ? errw[0] : 0u;
     *stop = e ? -(int)e : min(worst + 1, n_steps);
   }
-}
-
-// see latch_errors() in taco_lib.hip
-__global__ void k_latch_errors(const unsigned* errw, int* stop) {
-  if (threadIdx.x == 0) { const unsigned e = errw[0]; if (e) *stop = -(int)e; }
 }
 
 // The same stop rule evaluated on a finished mel buffer for groups of `rows` consecutive batch rows (requests that were served

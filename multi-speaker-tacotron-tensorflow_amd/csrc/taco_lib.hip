@@ -262,8 +262,6 @@ struct taco_model {
   int front_prio = 1; int front_delay = 0;      // shader clocks by which the second K half of a k_cbhg_front workgroup starts late (taco_front.h)
   int head_sweep = 1;          // wide dense layers over many rows (the linear head) as a row sweep (taco_head.h); 0: k_gemm_bf3 tiles
   int front = 1;               // conv bank -> max-pool -> proj_1 of a CBHG as one launch (taco_front.h); 0: bank and proj_1 as two k_gemm_bf3 launches
-  int overlap = 0;             // >0: run the post-net feed-forward stages behind the decoder on a second stream, chunks of
-                               // max(overlap,16) steps.  Measured SLOWER on MI355X (13.2 -> 14.4-17 ms @C2): off by default
   // persistent XCD-local decoder (taco_decoder_xcd.h): per-thread weight pack and the bias vectors its epilogues read
   size_t dx_fold_n = 0;        // training shadow model: elements of the GRU-1 fold buffer (k_dx_fold), addressed by the index map as NP + 1 + i
   size_t dx_spkw = 0;          // 'simple': speaker rows of the attention GRU and of the folded GRU 1, [S][DXRB_N][256] (k_dx_rowbias)
@@ -280,8 +278,6 @@ struct taco_model {
                                   // allocated on first use and kept until the model is destroyed (captured plans may hold the pointer)
   int trace_on = 0;
   int skip_scans = 0;          // timing hook (taco_debug_set_skip_scans): the recurrent scans of both CBHGs are not launched
-  hipStream_t side = nullptr;  // that second stream
-  std::vector<hipEvent_t> events;
   struct TrainPacks* tp = nullptr;   // set on the shadow model of a taco_train: finalize also builds the backward packs
 };
 static int build_train_packs(taco_model* m);   // taco_train.h
@@ -899,8 +895,8 @@ struct GemmCall {
   const float* res = nullptr; int ldres = 0;
   const float* rowvec = nullptr; int ldrv = 0;
   const int* rev_len = nullptr; int rev_col0 = -1;
-  int t_begin = 0, t_len = 0;      // time window [t_begin, t_begin + t_len) of every batch row (t_len 0 = all rows)
   float* out = nullptr; int ldo = 0;
+  bool tiles_only = false;         // never k_head_sweep (a CBHG's dense layer: the sweep is the linear head's kernel, cbhg_ff)
   float* aux0 = nullptr; float* aux1 = nullptr;   // highway H / T saved for the backward pass (training tape)
   int force = GEMM_FORCE_NONE;     // this call's level whatever the model's switches say (gemm_level): exact fp32, or split-bf16 at three products
 };
@@ -928,7 +924,7 @@ static FfWhyNot ff_fused_why(const taco_model* m, const ConvL& L, int force = GE
 static FfWhyNot head_sweep_why(const taco_model* m, const ConvL& L, int nvar, bool dual, const GemmCall& c) {
   if (const FfWhyNot why = ff_fused_why(m, L, c.force)) return why;
   if (!m->head_sweep) return FF_WHY_SWITCH;
-  return nvar == 1 && !dual && L.kw == 1 && c.mpw <= 1 && !c.gather && !c.res && !c.rev_len && c.rev_col0 < 0 && c.t_len == 0 && !c.aux0 && !c.aux1 &&
+  return nvar == 1 && !dual && L.kw == 1 && c.mpw <= 1 && !c.gather && !c.res && !c.rev_len && c.rev_col0 < 0 && !c.tiles_only && !c.aux0 && !c.aux1 &&
          c.act == ACT_NONE && !L.bns && c.ldx % 4 == 0 && (L.cin == 256 || L.cin == 512) && L.N >= 512 && L.N % 32 == L.ntail && (L.ntail == 0 || L.wtail) &&
          c.M >= 256 && (long)c.M * c.ldo < (1L << 30) ? FF_WHY_NONE : FF_WHY_WIDTHS;
 }
@@ -981,7 +977,6 @@ struct GemmPlan {
   int tile = 0;                // GemmTile (split-bf16 levels) or GemmCfg (exact level)
   int gpi = 1;                 // k_gemm_bf3: k16 steps per weight prefetch group
   dim3 grid = dim3(0, 0, 0); unsigned block = 0; size_t lds = 0;      // block 0: the list has no such member
-  int tiles_per_b = 0;         // GemmArgs::tiles_per_b (time-window mode)
 };
 // Everything a run_gemm launch decides, from integers and the model's switches alone (x_aligned: c.x on a 16-byte boundary, see head_sweep_why)
 static GemmPlan gemm_plan(const taco_model* m, const ConvL* layers, int nvar, bool dual, const GemmCall& c, bool x_aligned) {
@@ -989,8 +984,6 @@ static GemmPlan gemm_plan(const taco_model* m, const ConvL* layers, int nvar, bo
   const ConvL& L0 = layers[0];
   int kw_max = 1, Nmax = 0;
   for (int i = 0; i < nvar; ++i) { kw_max = std::max(kw_max, layers[i].kw); Nmax = std::max(Nmax, layers[i].N); }
-  const int T = c.T > 0 ? c.T : c.M, nb = c.M / T;
-  const long Meff = c.t_len > 0 ? (long)nb * c.t_len : c.M;      // rows that are computed (t_len > 0: a time window of every batch row)
   const bool vec_ok = c.ldx % 4 == 0 && L0.cin % 4 == 0 && x_aligned;
   p.level = gemm_level(m, L0, c.force);
   int BM = 0, BN = 0, KS = 1, waves = 0, tiles = 0;      // of the member: rows, columns, wave groups, waves per group, 32 x 32 tiles per wave
@@ -1010,8 +1003,8 @@ static GemmPlan gemm_plan(const taco_model* m, const ConvL* layers, int nvar, bo
       // every large layer; a 128 x 256 tile by 1 x 8 waves measured slower on the linear head, 116 vs 85 us: one workgroup of 8 waves per CU and
       // three rounds of workgroups.  Both were retired.)
       const int Ktot = L0.kw * L0.cin;
-      const long g128 = (long)cdiv(Meff, 128) * cdiv(Nmax, 64) * nvar, g64 = (long)cdiv(Meff, 64) * cdiv(Nmax, 64) * nvar;
-      const long wide = (long)cdiv(Meff, 64) * cdiv(Nmax, 256) * nvar;      // workgroups of the 64x256 tile
+      const long g128 = (long)cdiv(c.M, 128) * cdiv(Nmax, 64) * nvar, g64 = (long)cdiv(c.M, 64) * cdiv(Nmax, 64) * nvar;
+      const long wide = (long)cdiv(c.M, 64) * cdiv(Nmax, 256) * nvar;      // workgroups of the 64x256 tile
       if (g128 < 384 && !((Ktot >= 1024 || Nmax > 512) && wide >= 192)) p.tile = g64 >= 384 ? TILE_64x64 : TILE_64x64_K4;
       else if (Nmax <= 128) p.tile = TILE_64x128;
       else p.tile = (!dual && wide <= 320) ? TILE_64x256_K2 : TILE_64x256;      // few workgroups: two wave groups split K (16 waves/CU)
@@ -1035,7 +1028,7 @@ static GemmPlan gemm_plan(const taco_model* m, const ConvL* layers, int nvar, bo
     if (p.tile == CFG_AUTO) {
       // measured (tools/time_gemm_layers.py): the 64x64 tile (32 VGPRs, 8 waves/SIMD) beats 128x64 and 128x128 (retired) on
       // every large layer -- the kernel is bound by latency hiding, not operand reuse; small-M layers need split-K
-      p.tile = (long)cdiv(Meff, 64) * cdiv(Nmax, 64) * nvar >= 512 ? CFG_64x64 : CFG_32x64_K4;
+      p.tile = (long)cdiv(c.M, 64) * cdiv(Nmax, 64) * nvar >= 512 ? CFG_64x64 : CFG_32x64_K4;
     }
     switch (gemm_key(p.tile, dual, 1, false)) {
 #define X(CFG, WM, WN, KS_, DUAL) case gemm_key(CFG, DUAL, 1, false): BM = WM * 32; BN = WN * 32; KS = KS_; waves = WM * WN; tiles = 1; break;
@@ -1046,9 +1039,7 @@ static GemmPlan gemm_plan(const taco_model* m, const ConvL* layers, int nvar, bo
     p.lds = (size_t)(BM + kw_max - 1) * TACO_LDSW * sizeof(float);
     if (KS > 1) p.lds = std::max(p.lds, (size_t)(KS - 1) * waves * 1024 * (dual ? 2 : 1) * sizeof(float));
   }
-  int gx = cdiv(c.M, BM);
-  if (c.t_len > 0) { p.tiles_per_b = cdiv(c.t_len, BM); gx = nb * p.tiles_per_b; }
-  p.grid = dim3(gx, cdiv(Nmax, BN), nvar);
+  p.grid = dim3(cdiv(c.M, BM), cdiv(Nmax, BN), nvar);
   p.block = 64 * waves * KS;
   // weight prefetch depth of k_gemm_bf3: two k16 steps ahead when the grid leaves at most ~2 workgroups per CU (occupancy is grid-limited there);
   // instantiated for the plain 64x256 tile only, and it needs four k16 steps in every chunk (even group count)
@@ -1074,7 +1065,7 @@ static int run_gemm(const taco_model* m, hipStream_t st, const ConvL* layers, in
   a.x = c.x; a.gather = c.gather; a.res = c.res; a.rowvec = c.rowvec; a.out = c.out;
   a.ldx = c.ldx; a.M = c.M; a.T = c.T > 0 ? c.T : c.M; a.Cin = L0.cin; a.cin_pad = L0.cin_pad; a.mpw = c.mpw;
   a.act = c.act; a.ldres = c.ldres; a.ldrv = c.ldrv; a.ldo = c.ldo; a.rev_len = c.rev_len; a.rev_col0 = c.rev_col0;
-  a.t_begin = c.t_begin; a.t_len = c.t_len; a.aux0 = c.aux0; a.aux1 = c.aux1;
+  a.aux0 = c.aux0; a.aux1 = c.aux1;
   a.vec_ok = (c.ldx % 4 == 0) && (L0.cin % 4 == 0) && x_aligned;
   for (int i = 0; i < nvar && i < 16; ++i) {
     if (layers[i].var_index < 0) return fail(TACO_ERR_STATE, "layer has no GemmVar");
@@ -1082,7 +1073,6 @@ static int run_gemm(const taco_model* m, hipStream_t st, const ConvL* layers, in
   }
   if (nvar > 16) return fail(TACO_ERR_UNSUPPORTED, "conv bank wider than 16 is not supported");
   const GemmPlan p = gemm_plan(m, layers, nvar, dual, c, x_aligned);
-  a.tiles_per_b = p.tiles_per_b;
   if (p.head_sweep) {
     HeadArgs h;
     memset(&h, 0, sizeof h);
@@ -1454,12 +1444,11 @@ static bool chain_fits(const Cbhg& c, int in_dim) {
   return c.xproj.bh && c.xproj.cin == W && c.xproj.N == 6 * W;
 }
 static int run_chain(const taco_model* m, hipStream_t st, const Cbhg& c, const float* x, int in_dim, int M, int T, const int* lengths,
-                     const CbhgWs& w, const float** ff_out, const ChainEntry* entry = nullptr) {
+                     const CbhgWs& w, const ChainEntry* entry = nullptr) {
   ChainArgs a; memset(&a, 0, sizeof a);
   if (entry) a.e = *entry;
   a.x = x; a.ldx = in_dim; a.Cin = in_dim; a.out = w.xproj; a.ldo = 6 * c.rnn; a.rev_len = lengths; a.rev_col0 = 3 * c.rnn;
   a.M = M; a.T = T; a.krot = m->ff_rot;
-  if (ff_out) { a.y = w.hi0; a.ldy = c.rnn; *ff_out = w.hi0; }
   auto add = [&](const ConvL& L, int type) {
     const GemmVar& v = m->hvars[L.var_index];
     ChainLayer& l = a.L[a.nlayers++];
@@ -1545,11 +1534,7 @@ static int run_front(const taco_model* m, hipStream_t st, const Cbhg& c, const f
   return 0;
 }
 
-// Feed-forward part of a CBHG (modules.py:27-77) with per-stage watermarks, so it can run chunk by chunk
-// behind a producer of its input frames (the decoder): every stage is advanced as far as the frames
-// available to it allow (a conv needs its right halo; the last chunk gets TF's zero padding).
-struct FfProg { int w_bank = 0, w_p[4] = {0, 0, 0, 0}, w_pt = 0; };
-// ---- which kernels run the feed-forward part of a CBHG that is served in one piece ----
+// ---- which kernels run the feed-forward part of a CBHG ----
 struct FfPlan {
   GemmLevel level;          // of the layers that stay launches of their own (k_gemm / k_gemm_bf3, one per layer; the conv bank is one)
   int front_kind;           // k_cbhg_front: conv bank -> max-pool -> proj_1 as one launch, this instantiation (Cbhg::front_kind); 0: two GEMM launches
@@ -1558,8 +1543,7 @@ struct FfPlan {
   int launches;
   FfWhyNot why_front, why_entry, why_chain;      // first reason against each (NONE: used)
 };
-// The one place that decides.  Pure: launches nothing.  A call served chunk by chunk (cbhg_ff_advance with avail < T: taco_debug_set_overlap) runs
-// one launch per layer and chunk whatever the plan says; that term stays with the caller, as overlap_chunk does for the decoder loop.
+// The one place that decides.  Pure: launches nothing.
 static FfPlan ff_plan(const taco_model* m, const Cbhg& c) {
   const ConvL& P1 = c.proj[0]; const ConvL& P2 = c.proj.back();
   FfPlan p; memset(&p, 0, sizeof p);
@@ -1576,60 +1560,43 @@ static FfPlan ff_plan(const taco_model* m, const Cbhg& c) {
   p.launches = (p.entry ? 1 : 2) + ((int)c.proj.size() - (p.entry ? 2 : 1)) + (p.chain_w ? 1 : (c.has_dense ? 1 : 0) + c.depth + 1);
   return p;
 }
-static int cbhg_ff_advance(const taco_model* m, hipStream_t st, const Cbhg& c, const float* x, int B, int T,
-                           const int* lengths, const float* before_highway, const CbhgWs& w, FfProg& pg, int avail,
-                           const float** ff_out) {
+// Feed-forward part of a CBHG (modules.py:27-77), by ff_plan: x [B*T, in_dim] -> the hoisted BiGRU input projection in w.xproj
+static int cbhg_ff(const taco_model* m, hipStream_t st, const Cbhg& c, const float* x, int B, int T,
+                   const int* lengths, const float* before_highway, const CbhgWs& w) {
   const int M = B * T;
-  auto right = [](int k) { return k - 1 - (k - 1) / 2; };
-  auto advance = [&](int win, int reach) { return win >= T ? T : std::max(0, win - reach); };
-  // the whole window at once: bank -> max-pool -> proj_1 as ONE launch, the bank tensor never leaves the CU (taco_front.h)
-  // ... and with it proj_1's epilogue and proj_2 (+ residual) move into the entry of the point-wise chain: front + chain = the whole
-  // feed-forward part of a CBHG in two launches
   const FfPlan fp = ff_plan(m, c);
-  const bool front = fp.front_kind && avail >= T && pg.w_bank == 0 && pg.w_p[0] == 0, entry = front && fp.entry;      // (all frames in this call: the tail below is whole too)
+  // bank -> max-pool -> proj_1 as ONE launch, the bank tensor never leaves the CU (taco_front.h); with the entry, proj_1's epilogue and
+  // proj_2 (+ residual) move into the point-wise chain: front + chain = the whole feed-forward part in two launches
   int parts = 1;
-  if (front) {
-    TRY(run_front(m, st, c, x, B, T, w, !entry, &parts));
-    pg.w_bank = T; pg.w_p[0] = T;
-    if (entry) pg.w_p[1] = T;
+  if (fp.front_kind) TRY(run_front(m, st, c, x, B, T, w, !fp.entry, &parts));
+  else {  // conv bank: all K widths in one launch, written channel-concatenated (modules.py:35-44)
+    GemmCall g; g.x = x; g.ldx = c.in_dim; g.M = M; g.T = T; g.act = ACT_RELU; g.out = w.bank; g.ldo = c.K * c.C;
+    // (c.bank is ordered widest first, so the longest workgroups are dispatched first; narrowest first measured 0.47 vs 0.445 ms
+    // for the encoder stage)
+    TRY(run_gemm(m, st, c.bank.data(), c.K, false, g));
   }
-  // conv bank: all K widths in one launch, written channel-concatenated (modules.py:35-44)
-  { const int nw = advance(avail, right(c.K));
-    if (nw > pg.w_bank) {
-      GemmCall g; g.x = x; g.ldx = c.in_dim; g.M = M; g.T = T; g.act = ACT_RELU; g.out = w.bank; g.ldo = c.K * c.C;
-      g.t_begin = pg.w_bank; g.t_len = nw - pg.w_bank;
-      // (c.bank is ordered widest first, so the longest workgroups are dispatched first; narrowest first measured 0.47 vs 0.445 ms
-      // for the encoder stage)
-      TRY(run_gemm(m, st, c.bank.data(), c.K, false, g));
-      pg.w_bank = nw;
-    } }
-  // maxpool (fused into the staging of proj_1) + projections (modules.py:47-59)
+  // maxpool (fused into the staging of proj_1) + projections (modules.py:47-59); the front has run proj_1, and the chain's entry runs proj_2
+  const size_t absorbed = fp.front_kind ? (fp.entry ? 2 : 1) : 0;
   const float* cur = w.bank; int curd = c.K * c.C;
   for (size_t i = 0; i < c.proj.size(); ++i) {
-    const int win = (i == 0) ? pg.w_bank : pg.w_p[i - 1];
-    const int nw = advance(win, right(c.pw) + ((i == 0) ? right(c.maxpool) : 0));
-    if (nw > pg.w_p[i]) {
+    if (i >= absorbed) {
       GemmCall p;
       p.x = cur; p.ldx = curd; p.M = M; p.T = T; p.mpw = (i == 0) ? c.maxpool : 1;
       p.act = (i + 1 == c.proj.size()) ? ACT_NONE : ACT_RELU;
       p.out = w.p[i]; p.ldo = c.proj[i].N;
-      p.t_begin = pg.w_p[i]; p.t_len = nw - pg.w_p[i];
       if (i + 1 == c.proj.size()) {  // residual (modules.py:62-69)
         p.res = x; p.ldres = c.in_dim;
         p.rowvec = before_highway; p.ldrv = c.in_dim;
       }
       TRY(run_gemm(m, st, &c.proj[i], 1, false, p));
-      pg.w_p[i] = nw;
     }
     cur = w.p[i]; curd = c.proj[i].N;
   }
   // point-wise chain: optional dense (modules.py:72-73), highway x depth (:76-77), hoisted BiGRU input projection
-  const int wlast = pg.w_p[c.proj.size() - 1];
-  const int t0 = pg.w_pt, tl = wlast - pg.w_pt;
-  if (fp.chain_w && t0 == 0 && tl == T) {
+  if (fp.chain_w) {
     // the whole tail as ONE launch, activations resident on the CU from layer to layer (taco_chain.h)
     ChainEntry E; memset(&E, 0, sizeof E);
-    if (entry) {
+    if (fp.entry) {
       const ConvL& P1 = c.proj[0]; const ConvL& P2 = c.proj[1];
       const GemmVar& v2 = m->hvars[P2.var_index];
       E.part = w.bank; E.P = parts; E.MN = (size_t)M * P1.N; E.N1 = P1.N;
@@ -1638,39 +1605,33 @@ static int cbhg_ff_advance(const taco_model* m, hipStream_t st, const Cbhg& c, c
       E.b2 = AP(m, P2.bias); E.s2 = AP(m, P2.bns); E.h2 = AP(m, P2.bnb);
       E.res = x; E.ldres = c.in_dim; E.rowvec = before_highway; E.ldrv = c.in_dim;
     }
-    TRY(run_chain(m, st, c, cur, curd, M, T, lengths, w, ff_out, entry ? &E : nullptr));
-    pg.w_pt = wlast;
-    return 0;
+    return run_chain(m, st, c, cur, curd, M, T, lengths, w, fp.entry ? &E : nullptr);
   }
   if (c.has_dense) {
-    if (tl > 0) { GemmCall d; d.x = cur; d.ldx = curd; d.M = M; d.T = T; d.out = w.hi0; d.ldo = c.rnn; d.t_begin = t0; d.t_len = tl;
-      TRY(run_gemm(m, st, &c.dense, 1, false, d)); }
+    // (tiles_only: at 256 or 512 inputs and 512 outputs and more this layer has the linear head's shape, and it stays on the tile kernel
+    // that ff_plan's launch count and engine_plan's sentence name)
+    GemmCall d; d.x = cur; d.ldx = curd; d.M = M; d.T = T; d.out = w.hi0; d.ldo = c.rnn; d.tiles_only = true;
+    TRY(run_gemm(m, st, &c.dense, 1, false, d));
     cur = w.hi0;
   }
   float* bufs[2] = {w.hi0, w.hi1};
   int sel = (cur == w.hi0) ? 1 : 0;
   for (int i = 0; i < c.depth; ++i) {
-    if (tl > 0) { GemmCall h; h.x = cur; h.ldx = c.rnn; h.M = M; h.T = T; h.out = bufs[sel]; h.ldo = c.rnn; h.t_begin = t0; h.t_len = tl;
-      TRY(run_gemm(m, st, &c.hw[i], 1, true, h)); }
+    GemmCall h; h.x = cur; h.ldx = c.rnn; h.M = M; h.T = T; h.out = bufs[sel]; h.ldo = c.rnn;
+    TRY(run_gemm(m, st, &c.hw[i], 1, true, h));
     cur = bufs[sel]; sel ^= 1;
   }
-  if (tl > 0) {  // backward-direction columns are stored time-reversed per row (reverse_sequence), so scan step s reads row s
-    const int H = c.rnn;
-    GemmCall xp; xp.x = cur; xp.ldx = c.rnn; xp.M = M; xp.T = T; xp.out = w.xproj; xp.ldo = 6 * H;
-    xp.rev_len = lengths; xp.rev_col0 = 3 * H; xp.t_begin = t0; xp.t_len = tl;
-    TRY(run_gemm(m, st, &c.xproj, 1, false, xp));
-    pg.w_pt = wlast;
-  }
-  if (ff_out) *ff_out = cur;
-  return 0;
+  // backward-direction columns are stored time-reversed per row (reverse_sequence), so scan step s reads row s
+  GemmCall xp; xp.x = cur; xp.ldx = c.rnn; xp.M = M; xp.T = T; xp.out = w.xproj; xp.ldo = 6 * c.rnn;
+  xp.rev_len = lengths; xp.rev_col0 = 3 * c.rnn;
+  return run_gemm(m, st, &c.xproj, 1, false, xp);
 }
 
 // modules.py:27-96.  x [B*T, in_dim], out [B*T, 2*rnn].
 static int cbhg_forward(const taco_model* m, hipStream_t st, const Cbhg& c, const float* x, int B, int T,
                         const int* lengths, const float* before_highway, const float* init_state, float* out,
                         const CbhgWs& w) {
-  FfProg pg;
-  TRY(cbhg_ff_advance(m, st, c, x, B, T, lengths, before_highway, w, pg, T, nullptr));
+  TRY(cbhg_ff(m, st, c, x, B, T, lengths, before_highway, w));
   return bigru_scan(m, st, c, B, T, lengths, init_state, out, w);
 }
 
@@ -1983,8 +1944,7 @@ static int dbx_launch(const taco_model* m, hipStream_t st, const DecPlan& dp, Db
 }
 static int decoder_forward(const taco_model* m, hipStream_t st, const float* enc_out, const SpkSel& sel, int B,
                            int T_in, int n, const float* manual, const float* teacher, float* mel, float* align_out,
-                           int* stop_step, float* dbg, const DecWs& w, bool spk_ready, const SpkWs* spk_in,
-                           const std::function<int(int)>* after_step = nullptr) {
+                           int* stop_step, float* dbg, const DecWs& w, bool spk_ready, const SpkWs* spk_in) {
   const taco_hparams& hp = m->hp;
   const int D = 2 * hp.enc_rnn_size, As = hp.attention_state_size, Hd = hp.dec_rnn_size, A = hp.attention_size;
   const int Mm = hp.num_mels, rM = hp.num_mels * hp.reduction_factor, L = hp.dec_layer_num;
@@ -2006,7 +1966,7 @@ static int decoder_forward(const taco_model* m, hipStream_t st, const float* enc
   const int ldY = n * rM;   // mel buffer viewed as Y [B, n, r*num_mels] (tacotron.py:213-214 is a pure reshape)
   const int dbgw = As + D + L * Hd;
   HIPCHK(clear_polled(w.nz, (size_t)n * B * sizeof(int), st));
-  if (const DecPlan dp = decoder_plan(m, B, T_in, n, teacher ? DEC_TEACHER : DEC_INFER); dp.persistent && !after_step) {      // (after_step: see overlap_chunk)
+  if (const DecPlan dp = decoder_plan(m, B, T_in, n, teacher ? DEC_TEACHER : DEC_INFER); dp.persistent) {
     // the whole loop as ONE persistent launch (taco_decoder_xcd.h), which builds its initial state itself (zeros or the deepvoice
     // vectors); the launch-per-stage loop below is the general path
     DxArgs ta; memset(&ta, 0, sizeof ta);
@@ -2087,7 +2047,6 @@ static int decoder_forward(const taco_model* m, hipStream_t st, const float* enc
       int nj = 1;
       if (fuse_p1 && t + 1 < n) { j[1] = sk_linear(m, m->prenet1_next, w.o[L], Hd, Hd, w.ctx, ldc, ACT_RELU, w.pz[0], hp.dec_prenet[0]); nj = 2; }
       TRY(run_skinny(st, B, j, nj)); }
-    if (after_step) TRY((*after_step)(t));
     if (dbg) {
       float* d = dbg + (size_t)t * B * dbgw;
       hipLaunchKernelGGL(k_copy2d, dim3(cdiv(B * As, 256)), dim3(256), 0, st, w.h_att, ldc, d, dbgw, B, As);
@@ -2112,8 +2071,9 @@ static void carve_post(Carver& cv, const taco_model* m, int B, int T, PostWs& w)
   w.spk_emb = cv.f((size_t)B * std::max(simple_S(m), 1));
   w.rowvec = cv.f((size_t)B * m->hp.num_freq);
 }
-static int postnet_tail(const taco_model* m, hipStream_t st, const SpkSel& sel, int B, int T, float* linear,
-                        float* post_out_user, const PostWs& w) {
+static int postnet_forward(const taco_model* m, hipStream_t st, const float* mel, const SpkSel& sel, int B, int T,
+                           float* linear, float* post_out_user, const PostWs& w) {
+  TRY(cbhg_ff(m, st, m->post, mel, B, T, nullptr, nullptr, w.cb));
   float* po = post_out_user ? post_out_user : w.post_out;
   TRY(bigru_scan(m, st, m->post, B, T, nullptr, nullptr, po, w.cb));
   GemmCall g; g.x = po; g.ldx = 2 * m->hp.post_rnn_size; g.M = B * T; g.out = linear; g.ldo = m->hp.num_freq;
@@ -2127,12 +2087,6 @@ static int postnet_tail(const taco_model* m, hipStream_t st, const SpkSel& sel, 
     g.T = T; g.rowvec = w.rowvec; g.ldrv = F;
   }
   return run_gemm(m, st, &m->linear, 1, false, g);
-}
-static int postnet_forward(const taco_model* m, hipStream_t st, const float* mel, const SpkSel& sel, int B, int T,
-                           float* linear, float* post_out_user, const PostWs& w) {
-  FfProg pg;
-  TRY(cbhg_ff_advance(m, st, m->post, mel, B, T, nullptr, nullptr, w.cb, pg, T, nullptr));
-  return postnet_tail(m, st, sel, B, T, linear, post_out_user, w);
 }
 
 struct FullWs { EncWs enc; DecWs dec; PostWs post; float* enc_out; };
@@ -2151,21 +2105,6 @@ static int check_common(const taco_model* m, int B, int T) {
   return 0;
 }
 
-// Last node of a forward: if a persistent kernel of this (or an earlier, still unacknowledged) forward gave up -- the device error
-// word is sticky and makes every later persistent launch drain at once -- the forward's own stop word becomes -(error), so the
-// caller that reads the stop step learns that THIS forward's outputs are invalid without a second transfer.
-static int latch_errors(const taco_model* m, hipStream_t st, int32_t* stop) {
-  if (!stop) return 0;
-  hipLaunchKernelGGL(k_latch_errors, dim3(1), dim3(64), 0, st, (const unsigned*)m->d_err, stop);
-  HIPCHK(hipGetLastError());
-  return 0;
-}
-
-// taco_debug_set_overlap: steps per chunk where forward_pass runs the post-net's feed-forward stages behind a decoder loop of n steps (then one launch per stage); else 0
-static int overlap_chunk(const taco_model* m, int n) {
-  const int CH = m->overlap > 16 ? m->overlap : 16;
-  return m->overlap && (size_t)(n / CH + 4) <= m->events.size() ? CH : 0;
-}
 // One pass of at most 64 batch rows (what the persistent kernels place on one chip: 8 groups x 8 rows).
 static int forward_pass(taco_model* m, hipStream_t st, const int32_t* ids, const int32_t* lengths, const SpkSel& spk,
                         int B, int T_in, int n, const float* manual, float* mel, float* linear, float* align,
@@ -2179,57 +2118,31 @@ static int forward_pass(taco_model* m, hipStream_t st, const int32_t* ids, const
   carve_full(cv, m, B, T_in, n, w);
   if (!cv.ok()) return fail(TACO_ERR_STATE, "workspace too small: need %zu bytes, have %zu", cv.off, ws_bytes);
   const int r = m->hp.reduction_factor, T_mel = n * r;
-  const int CH = overlap_chunk(m, n);
   const bool ride = prenet_chain_why(m) == FF_WHY_NONE;      // the encoder prenet as the chain launch: asked once per forward
-  if (!CH) {
-    // every word a persistent kernel polls and the stop flags, cleared by ONE launch in front of the forward; the stop rule and the
-    // error latch are ONE launch behind it (11 graph nodes at C2 with the clears riding in the prenet launch; 13 in round 4, 20 in round 3)
-    ZeroRegions z; memset(&z, 0, sizeof z);
-    z.p[0] = (uint32_t*)w.dec.xbuf; z.nw[0] = ((size_t)((char*)w.dec.dxctl - (char*)w.dec.xbuf) + 256) / 4;
-    z.p[1] = (uint32_t*)w.dec.nz; z.nw[1] = (size_t)n * B;
-    z.p[2] = (uint32_t*)w.post.cb.gxbuf; z.nw[2] = ((size_t)((char*)w.post.cb.gxctl - (char*)w.post.cb.gxbuf) + 256) / 4;
-    z.p[3] = (uint32_t*)w.enc.cb.gxbuf; z.nw[3] = ((size_t)((char*)w.enc.cb.gxctl - (char*)w.enc.cb.gxbuf) + 256) / 4;     // (an encoder of width 256 scans on k_bigru_duo too)
-    // (they ride in the encoder prenet's launch where that is the chain kernel -- the first launch of the forward, with CUs to spare)
-    // The regions count as cleared (zero_async then skips its own fill) only from the point where the launch that clears them HAS been
-    // enqueued: here for the fill kernel, inside run_prenet_chain for the riders.
-    struct Guard { Guard() { g_cleared.cnt = 0; } ~Guard() { g_cleared.cnt = 0; } } guard;
-    if (!ride) {
-      hipLaunchKernelGGL(k_zero_fill_multi, dim3(256, 4), dim3(256), 0, st, z);
-      HIPCHK(hipGetLastError());
-      register_cleared(z);
-    }
-    TRY(encoder_forward(m, st, ids, lengths, spk, B, T_in, w.enc_out, w.enc, false, ride, ride ? &z : nullptr));
-    TRY(decoder_forward(m, st, w.enc_out, spk, B, T_in, n, manual, nullptr, mel, align, nullptr, nullptr, w.dec, true, &w.enc.spk));
-    TRY(postnet_forward(m, st, mel, spk, B, T_mel, linear, nullptr, w.post));
-    if (stop) {
-      hipLaunchKernelGGL(k_stop_step, dim3(1), dim3(1024), 0, st, (const int*)w.dec.nz, B, n, stop, (const unsigned*)m->d_err);
-      HIPCHK(hipGetLastError());
-    }
-    return 0;
+  // every word a persistent kernel polls and the stop flags, cleared by ONE launch in front of the forward; the stop rule and the
+  // error latch are ONE launch behind it (11 graph nodes at C2 with the clears riding in the prenet launch; 13 in round 4, 20 in round 3)
+  ZeroRegions z; memset(&z, 0, sizeof z);
+  z.p[0] = (uint32_t*)w.dec.xbuf; z.nw[0] = ((size_t)((char*)w.dec.dxctl - (char*)w.dec.xbuf) + 256) / 4;
+  z.p[1] = (uint32_t*)w.dec.nz; z.nw[1] = (size_t)n * B;
+  z.p[2] = (uint32_t*)w.post.cb.gxbuf; z.nw[2] = ((size_t)((char*)w.post.cb.gxctl - (char*)w.post.cb.gxbuf) + 256) / 4;
+  z.p[3] = (uint32_t*)w.enc.cb.gxbuf; z.nw[3] = ((size_t)((char*)w.enc.cb.gxctl - (char*)w.enc.cb.gxbuf) + 256) / 4;     // (an encoder of width 256 scans on k_bigru_duo too)
+  // (they ride in the encoder prenet's launch where that is the chain kernel -- the first launch of the forward, with CUs to spare)
+  // The regions count as cleared (zero_async then skips its own fill) only from the point where the launch that clears them HAS been
+  // enqueued: here for the fill kernel, inside run_prenet_chain for the riders.
+  struct Guard { Guard() { g_cleared.cnt = 0; } ~Guard() { g_cleared.cnt = 0; } } guard;
+  if (!ride) {
+    hipLaunchKernelGGL(k_zero_fill_multi, dim3(256, 4), dim3(256), 0, st, z);
+    HIPCHK(hipGetLastError());
+    register_cleared(z);
   }
-  TRY(encoder_forward(m, st, ids, lengths, spk, B, T_in, w.enc_out, w.enc, false, ride));
-  // The decoder loop is a chain of tiny dependent launches that occupies < 1/5 of the CUs; the post-net's
-  // feed-forward stages (conv bank, projections, highways, hoisted GRU projection: ~1.3 ms of fp32 MFMA work @C2)
-  // need only frames that already exist plus a conv halo.  They run on a second stream, one chunk of CH steps
-  // behind the decoder (fork/join by events; captured into the hipGraph as a parallel branch).
-  hipStream_t s2 = m->side;
-  size_t ev = 0;
-  HIPCHK(hipEventRecord(m->events[ev], st));
-  HIPCHK(hipStreamWaitEvent(s2, m->events[ev], 0));
-  ++ev;
-  FfProg pg;
-  const std::function<int(int)> hook = [&](int t) -> int {
-    if ((t + 1) % CH != 0 && t != n - 1) return 0;
-    HIPCHK(hipEventRecord(m->events[ev], st));
-    HIPCHK(hipStreamWaitEvent(s2, m->events[ev], 0));
-    ++ev;
-    return cbhg_ff_advance(m, s2, m->post, mel, B, T_mel, nullptr, nullptr, w.post.cb, pg, (t + 1) * r, nullptr);
-  };
-  TRY(decoder_forward(m, st, w.enc_out, spk, B, T_in, n, manual, nullptr, mel, align, stop, nullptr, w.dec, true, &w.enc.spk, &hook));
-  HIPCHK(hipEventRecord(m->events[ev], s2));
-  HIPCHK(hipStreamWaitEvent(st, m->events[ev], 0));
-  TRY(postnet_tail(m, st, spk, B, T_mel, linear, nullptr, w.post));
-  return latch_errors(m, st, stop);
+  TRY(encoder_forward(m, st, ids, lengths, spk, B, T_in, w.enc_out, w.enc, false, ride, ride ? &z : nullptr));
+  TRY(decoder_forward(m, st, w.enc_out, spk, B, T_in, n, manual, nullptr, mel, align, nullptr, nullptr, w.dec, true, &w.enc.spk));
+  TRY(postnet_forward(m, st, mel, spk, B, T_mel, linear, nullptr, w.post));
+  if (stop) {
+    hipLaunchKernelGGL(k_stop_step, dim3(1), dim3(1024), 0, st, (const int*)w.dec.nz, B, n, stop, (const unsigned*)m->d_err);
+    HIPCHK(hipGetLastError());
+  }
+  return 0;
 }
 
 // Any batch size (synthesizer.py:120-131 and eval.py:86-119 put no cap on it): more than 64 rows run as ceil(B / 64) passes of equal
@@ -2592,9 +2505,6 @@ int taco_model_finalize(taco_model* m) {
 #undef MANUAL
 #undef BOTH
 #undef STAMPED
-  HIPCHK(hipStreamCreateWithFlags(&m->side, hipStreamNonBlocking));
-  m->events.resize(192);
-  for (auto& e : m->events) HIPCHK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
   HIPCHK(hipMalloc((void**)&m->d_err, 256));
   HIPCHK(hipMemset(m->d_err, 0, 256));
   m->arena_n = m->harena.size();
@@ -2609,8 +2519,6 @@ void taco_model_destroy(taco_model* m) {
   if (m->darena) (void)hipFree(m->darena);
   if (m->d_err) (void)hipFree(m->d_err);
   if (m->d_trace) (void)hipFree(m->d_trace);
-  for (auto& e : m->events) (void)hipEventDestroy(e);
-  if (m->side) (void)hipStreamDestroy(m->side);
   delete m;
 }
 
@@ -2700,8 +2608,7 @@ int taco_debug_set_fuse_concat(taco_model* m, int on) {
 }
 int taco_debug_set_overlap(taco_model* m, int on) {
   if (!m) return fail(TACO_ERR_ARG, "null model");
-  m->overlap = on;
-  return 0;
+  return on ? fail(TACO_ERR_ARG, "the chunked post-net overlap is retired") : 0;
 }
 
 int taco_debug_set_persistent(taco_model* m, int on) {
@@ -2761,12 +2668,11 @@ int taco_model_engine_plan(taco_model* m, int B, int T_in, int T_mel, int flags,
   };
   {  // decoder loop
     const DecPlan dp = decoder_plan(m, B, T_in, n, m->tp ? DEC_TRAIN_FWD : (flags & 2) ? DEC_TEACHER : DEC_INFER);
-    const int chunk = m->tp || (flags & 6) ? 0 : overlap_chunk(m, n);      // forward_pass only
-    if (dp.persistent && !chunk)
+    if (dp.persistent)
       s += "decoder loop: persistent k_decoder_xcd<" + std::to_string(dp.rg) + (dx_reference_widths(m) ? std::string("") : ", attention " + std::to_string(dp.aw) + ", " +
            std::to_string(dp.pd) + " prenet layers") + "> (" + std::string((flags & 1) ? "manual alignments" : "computed alignments") + ", " +
            std::string(m->dx_mode == 2 ? "write-through exchanges forced" : "XCD-local exchanges when the census finds 32 workgroups per XCD") + ")";
-    else s += "decoder loop: one launch per stage -- " + (dp.persistent ? "taco_debug_set_overlap: the post-net's feed-forward stages follow the loop in chunks of " + std::to_string(chunk) + " steps" : dec_why(dp));
+    else s += "decoder loop: one launch per stage -- " + dec_why(dp);
   }
   // the two scans, from the plan bigru_scan itself follows
   auto scan_why = [&](const Cbhg& c, const ScanPlan& sp, const char* width_name, int rows) -> std::string {
@@ -2795,21 +2701,19 @@ int taco_model_engine_plan(taco_model* m, int B, int T_in, int T_mel, int flags,
     else s += std::string("; encoder scan: ") + scan_kernel_name(sp.kernel);
     s += "; feed-forward: ";
   }
-  // the feed-forward launches, from the plans cbhg_ff_advance, forward_pass and run_gemm themselves follow (ff_plan, prenet_chain_why, head_sweep_why);
+  // the feed-forward launches, from the plans cbhg_ff, forward_pass and run_gemm themselves follow (ff_plan, prenet_chain_why, head_sweep_why);
   // a training forward (taco_train.h) runs every layer as a launch of its own, between its BatchNorm passes
-  const int chunk = m->tp || (flags & 6) ? 0 : overlap_chunk(m, n);
   auto gemm_name = [](GemmLevel lv) { return lv == GEMM_BF3 ? "k_gemm_bf3" : lv == GEMM_BF3X6 ? "k_gemm_bf3<..., X6>" : "k_gemm"; };
   auto launches = [](int k) { return std::to_string(k) + (k == 1 ? " launch" : " launches"); };
   auto ff_why = [&](const char* kernel, FfWhyNot why, int bit, const char* widths = "widths outside the presets") -> std::string {
     static const char* const words[] = {"", "exact fp32 is switched on", "the six-product level has no fused kernels", "taco_debug_force_gemm_config", "a k_gemm_bf3 tile is forced"};
     return std::string(" -- no ") + kernel + ": " + (why == FF_WHY_SWITCH ? "taco_debug_set_bf3 bit " + std::to_string(bit) : why == FF_WHY_WIDTHS ? std::string(widths) : std::string(words[why]));
   };
-  auto cbhg_ff = [&](const char* name, const Cbhg& c, bool chunked) -> std::string {
+  auto cbhg_words = [&](const char* name, const Cbhg& c) -> std::string {
     const FfPlan fp = ff_plan(m, c);
     const int per_layer = 1 + (int)c.proj.size() + (c.has_dense ? 1 : 0) + c.depth + 1;
     std::string r = std::string("; ") + name + " CBHG: ";
     if (m->tp) return r + launches(per_layer) + " of " + gemm_name(fp.level) + ", one per layer";
-    if (chunked) return r + launches(per_layer) + " of " + gemm_name(fp.level) + " per chunk, one per layer (taco_debug_set_overlap)";
     r += launches(fp.launches) + ": ";
     r += fp.front_kind == 1 ? "k_cbhg_front<2, 80, 80, 8>" : fp.front_kind ? "k_cbhg_front<1, 144, 128, 16>" : std::string("conv bank and proj_1 on ") + gemm_name(fp.level);
     if (fp.front_kind && !fp.entry) r += " + k_front_combine";
@@ -2823,12 +2727,12 @@ int taco_model_engine_plan(taco_model* m, int B, int T_in, int T_mel, int flags,
   };
   { const GemmLevel lv = gemm_level(m, m->linear);
     s += lv == GEMM_BF3 ? "split-bf16 MFMA, three products (k_gemm_bf3 and the fused kernels)" : lv == GEMM_BF3X6 ? "split-bf16 MFMA, six products (k_gemm_bf3<..., X6>: fp32-grade)" : "exact-fp32 MFMA (k_gemm)";
-    s += cbhg_ff("encoder", m->enc, false) + cbhg_ff("post-net", m->post, chunk != 0);
+    s += cbhg_words("encoder", m->enc) + cbhg_words("post-net", m->post);
     const FfWhyNot pw = prenet_chain_why(m);
-    if (!m->tp && !pw) s += std::string("; encoder prenet: one k_pointwise_chain launch (1 launch: embedding rows gathered, both layers") + (chunk ? ")" : "; the forward's zero fills ride in it)");
+    if (!m->tp && !pw) s += "; encoder prenet: one k_pointwise_chain launch (1 launch: embedding rows gathered, both layers; the forward's zero fills ride in it)";
     else s += "; encoder prenet: one GEMM launch per layer (" + launches(m->hp.enc_prenet_n) + " of " + gemm_name(gemm_level(m, m->enc_prenet[0])) +
-              (m->tp ? ")" : std::string(chunk ? "" : " + 1 launch of k_zero_fill_multi in front: the forward's zero fills") + ff_why("k_pointwise_chain", pw, 2) + ")");
-    GemmCall g; g.ldx = 2 * m->hp.post_rnn_size; g.M = B * T_mel; g.ldo = m->hp.num_freq;      // the call of postnet_tail (and of the training forward)
+              (m->tp ? ")" : std::string(" + 1 launch of k_zero_fill_multi in front: the forward's zero fills") + ff_why("k_pointwise_chain", pw, 2) + ")");
+    GemmCall g; g.ldx = 2 * m->hp.post_rnn_size; g.M = B * T_mel; g.ldo = m->hp.num_freq;      // the call of postnet_forward (and of the training forward)
     const FfWhyNot hw = head_sweep_why(m, m->linear, 1, false, g);
     s += std::string("; linear head: 1 launch of ") + (hw ? gemm_name(lv) + ff_why("k_head_sweep", hw, 5, "it serves 256 rows and more, 256 or 512 inputs, 512 columns and more") :
                                                                 m->linear.cin == 512 ? "k_head_sweep<512>" : "k_head_sweep<256>"); }

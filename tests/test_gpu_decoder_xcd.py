@@ -571,7 +571,7 @@ def test_feed_forward_plan_agrees_with_the_launches():
     """ff_plan / prenet_chain_why / head_sweep_why (csrc/taco_lib.hip) are what the launches follow and what engine_plan words.  There is no
     protocol word for feed-forward kernels, but a captured plan counts its kernel nodes: in every taco_debug_set_bf3 mode the node count moves
     against mode 1 by exactly the launches the sentence states, and the sentence names the kernels include/taco_debug.h documents for the
-    mode.  Then a model outside the presets: one launch per layer, with the reason.  (Overlap mode is left out: its graph has event nodes.)"""
+    mode.  Then a model outside the presets: one launch per layer, with the reason."""
     from util import tiny_hp
     B, T_in = 8, 24
     ohp = O.OracleHParams(max_iters=16)

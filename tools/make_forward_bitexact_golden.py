@@ -1,0 +1,40 @@
+#!/usr/bin/env python
+"""Records what tests/test_gpu_forward_bitexact.py compares against: run it on the build whose results are to be kept (TACO_LIB names a
+library other than the tree's), on a whole MI355X.  Every case runs twice, and nothing is written when the two runs of that build differ.
+Writes forward_bitexact.json (sha256 of the complete arrays) and forward_bitexact.npz (first and last frames of two rows of every array)
+into the directory given (default tests/golden).
+    python tools/make_forward_bitexact_golden.py [DIR]"""
+import json
+import os
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+for p in (ROOT, os.path.join(ROOT, "oracle"), os.path.join(ROOT, "tests")):
+    sys.path.insert(0, p)
+import numpy as np
+import test_gpu_forward_bitexact as F
+
+
+def main():
+    out = sys.argv[1] if len(sys.argv) > 1 else F.GOLDEN
+    os.makedirs(out, exist_ok=True)
+    doc, arrays = {}, {}
+    for name in sorted(F.CASES):
+        first, second = F.run_case(name), F.run_case(name)
+        for mode in F.CASES[name][3]:
+            for array, a, b in zip(F.ARRAYS, first[mode], second[mode]):
+                k = F.key(name, mode, array)
+                if a.shape != b.shape or not np.array_equal(a.view(np.uint32), b.view(np.uint32)):
+                    raise SystemExit("nothing written: two runs of this build differ in " + k)
+                doc[k + "_shape"] = list(a.shape)
+                doc[k + "_sha256"] = F.digest(a)
+                arrays[k] = F.sample(a)
+                print(k, doc[k + "_shape"], doc[k + "_sha256"], flush=True)
+    np.savez(os.path.join(out, "forward_bitexact.npz"), **arrays)
+    with open(os.path.join(out, "forward_bitexact.json"), "w") as f:
+        json.dump(doc, f, indent=1)
+        f.write("\n")
+
+
+if __name__ == "__main__":
+    main()
