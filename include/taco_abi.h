@@ -344,6 +344,72 @@ int taco_wav_breath_mute(void* hip_stream, const float* d_wav, const int32_t* d_
                          const int32_t* d_intervals, const int32_t* d_counts, int max_intervals, float threshold,
                          float* d_out, int32_t* d_muted /* nullable */, float* d_abs_mean /* nullable */);
 
+/* Splitting and levelling 16-bit PCM on silence, the pydub way: `pydub.silence.detect_nonsilent` as split_on_silence_with_pydub
+ * (audio/silence.py:81-117, the method the reference's README and scripts/prepare_*.sh run: min_silence_len=100, silence_thresh=-40)
+ * and amplify (app.py:27-53: silence_thresh=-50, min_silence_len=300, every non-silent stretch brought to -20 dBFS) call it.
+ * UNPINNED on pydub: the reference pins pydub==0.20.0, this project does not depend on pydub, and what follows restates pydub's
+ * published silence.py with seek_step = 1; it could not be checked against pydub's source or output, only against the standard
+ * library's audioop, which pydub calls (tests/pydub_reference.py).  Where the 0.20.0 pin may differ, the rule taken: (1) a window is
+ * silent when rms <= thresh, not <: the two part only for an integral threshold; (2) two runs of silent windows whose starts lie no
+ * more than min_silence_len apart are reported as ONE silent range (detect_silence's `silence_has_gap`); an older detect_silence that
+ * closes a range at every break would report two.
+ * Input: d_pcm [B, L, channels] int16, interleaved, as pydub's AudioSegment holds PCM and audioop sees every channel of a frame; row b
+ * has n_b = d_num_frames[b] frames (device memory, only read on the device, clamped to [0, L]; NULL: L) at sample_rate (sr).
+ * The millisecond grid.  p(j) = floor(j*sr/1000) in 64-bit integers is the frame at which millisecond j starts -- pydub evaluates
+ * int(j * (sr/1000.0)) in double, and the two are equal at every j whenever fl(sr/1000.0) >= sr/1000 (every multiple of 1000 Hz,
+ * 11025, 22050, 44100, 88200, 176400 Hz; the product can then not fall below an integral j*sr/1000, and stays within 1/1000 of any
+ * other).  A rate whose quotient rounds DOWN (1001 Hz: they part at j = 1000; 11024 Hz) is TACO_ERR_UNSUPPORTED;
+ * taco_pcm_rate_supported answers 1 / 0 for a rate on the host, without a device.  A row is M = round_half_even(
+ * 1000.0 * (n / (double)sr)) milliseconds long, Python's round of pydub's expression.  A frame index at or past n reads as a zero frame
+ * but still counts as a frame (pydub pads a slice's missing frames with silence; it happens only where M was rounded up).
+ * Windows.  W = min_silence_len.  Window i, 0 <= i <= M - W, covers the frames [p(i), p(i + W)) over all channels; S_i is the sum of
+ * the squares of its samples and c_i their number, frames x channels.  audioop.rms returns (unsigned)sqrt(S/c) in double (0 for an
+ * empty fragment) and pydub calls the window silent when rms <= thresh = 10^(dB/20) * 32768.  With k = floor(thresh), formed by the
+ * CALLER in double (the device evaluates no pow or log): silent iff c_i == 0 or S_i < (k + 1)^2 * c_i, an integer comparison, equal to
+ * the double one while c_i * (k + 1)^2 < 2^52 -- beyond that TACO_ERR_UNSUPPORTED.  No rms passes 32768, so taco_pcm_nonsilent takes a k
+ * above 32768 as 32768 (before that limit is checked).
+ * detect_silence.  M < W: no silent range.  Otherwise the maximal runs [a..b] of consecutive silent starts give the ranges [a, b + W];
+ * a run opens a new range only if a > b_prev + W and otherwise extends the one before it.
+ * detect_nonsilent.  No silent range: [[0, M]].  One silent range [0, M]: [].  Otherwise the gaps [prev_end, start] with prev_end = 0
+ * at first, [prev_end, M] added if the last silent range does not end at M, a leading [0, 0] removed.  Milliseconds, in order.
+ * taco_pcm_nonsilent writes, per row, the true number of non-silent ranges to d_counts[b], the first max_ranges of them to d_ranges
+ * [B, max_ranges, 2] and exact zeros to every other word of the table; M to d_len_ms[b] (nullable); S_i of the row's own windows and
+ * zeros in every other word to d_window_sumsq [B, Mmax] (nullable, uint64; for tests and diagnostics), Mmax = the M of a row of L
+ * frames.  Three launches: (1) E[b, j], uint64, the sum of squares of millisecond j's frames [p(j), p(j + 1)) -- the only pass over
+ * the samples, 16-byte loads, a tile's span staged in LDS, nothing at or past n_b read; (2) the flags: a tile of window starts takes its
+ * tile + W energies into LDS and forms their prefix sums there (windows sit on the millisecond grid: no scan across tiles);
+ * TACO_ERR_UNSUPPORTED when 256 + W energies exceed 64 KB (W above 7904), or when one millisecond of samples exceeds 48 KB; (3) one
+ * workgroup per row orders the ranges with a prefix count, as taco_wav_split does, without atomics.  The workspace BEGINS with E
+ * [B, Mmax] uint64: pass it to taco_pcm_range_sumsq as d_energy.
+ * taco_pcm_range_sumsq: for a table of ranges [B, max_ranges, 2] in milliseconds, each clamped to 0 <= s <= e <= M, the exact
+ * d_sumsq[b, k] = E[s] + ... + E[e - 1] (the frames [p(s), p(e)), zero frames past n) and d_samples[b, k] = (p(e) - p(s)) * channels;
+ * zeros at and past d_counts[b].  d_energy holds only the entries j < M_b the taco_pcm_nonsilent call wrote: B, L, sample_rate and
+ * d_num_frames must be the ones given to that call (another d_num_frames would read words that were never written).  The caller forms rms_k = (unsigned)sqrt(S_k/c_k) and amplify's factor_k = 10^((target - 20
+ * log10(rms_k/32768))/20) from them on the host in double, where the reference forms them: a device log or pow could part by an ulp
+ * and flip a floor.
+ * taco_pcm_apply_gains: audioop.mul per range and amplify's cut.  Row b of d_out [B, L_out, channels] receives the frames
+ * [p(s_0), p(M)) of the row (s_0 the start of its first range: what precedes it is dropped, as the reference drops it; zero frames
+ * at or past n), a sample x inside range k as clip(floor((double)x * d_gains[b, k]), -32768, 32767), a sample between ranges
+ * unchanged; zeros after; d_out_frames[b] (nullable) = p(M) - p(s_0), 0 for a row without a range.  Only the first min(count,
+ * max_ranges) ranges of a row exist for it, and they must be in order, as taco_pcm_nonsilent writes them.  A DEPARTURE: a range whose
+ * S_k is 0 would be multiplied by infinity in the reference; the Python caller gives it the gain 1.0, a copy.
+ * All three: asynchronous on the stream; no allocation, read-back or synchronisation: capturable; integer sums and one double product
+ * per sample: two calls return the same bits.  TACO_ERR_ARG (before any device call): a null required pointer, B, L, channels,
+ * sample_rate, min_silence_len, max_ranges or L_out < 1, B > 65535, k < 0, a misaligned pointer, workspace below
+ * taco_pcm_nonsilent_workspace_bytes.  TACO_ERR_SHAPE: more milliseconds than int32 holds. */
+int taco_pcm_rate_supported(int sample_rate);
+size_t taco_pcm_nonsilent_workspace_bytes(int B, int L, int sample_rate);
+int taco_pcm_nonsilent(void* hip_stream, const int16_t* d_pcm, const int32_t* d_num_frames /* nullable */, int B, int L, int channels,
+                       int sample_rate, int min_silence_len, int k, int max_ranges, int32_t* d_ranges /* [B, max_ranges, 2] */,
+                       int32_t* d_counts /* [B] */, int32_t* d_len_ms /* nullable */, uint64_t* d_window_sumsq /* nullable */,
+                       void* d_workspace, size_t workspace_bytes);
+int taco_pcm_range_sumsq(void* hip_stream, const uint64_t* d_energy /* [B, Mmax] */, const int32_t* d_num_frames, int B, int L, int channels,
+                         int sample_rate, const int32_t* d_ranges, const int32_t* d_counts, int max_ranges,
+                         uint64_t* d_sumsq /* [B, max_ranges] */, int64_t* d_samples /* [B, max_ranges] */);
+int taco_pcm_apply_gains(void* hip_stream, const int16_t* d_pcm, const int32_t* d_num_frames, int B, int L, int channels, int sample_rate,
+                         const int32_t* d_ranges, const int32_t* d_counts, int max_ranges, const double* d_gains /* [B, max_ranges] */,
+                         int16_t* d_out /* [B, L_out, channels] */, int L_out, int32_t* d_out_frames /* nullable */);
+
 /* ---- recordings to the model's sample rate: librosa.core.load(path, sr=hparams.sample_rate) after decoding, and resample_audio
  * (audio/__init__.py:12-20,30-32; recognition/google.py:48: 24 kHz -> 16 kHz) -- resampy.resample's band-limited sinc interpolation
  * (filter 'kaiser_best') and librosa.core.resample's fix_length, restated ----

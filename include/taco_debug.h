@@ -123,6 +123,11 @@ int taco_debug_wgrad_plan(int wgrad_bf3, int wgrad_planes, int deterministic, lo
  * dB / normalise arithmetic be held against the reference's own recorded outputs, and the kernel be timed alone. */
 int taco_debug_spec_epilogue(taco_gl* g, void* hip_stream, const float* d_est, int R, float* d_linear, float* d_mel);
 
+/* Timing hook: k_pcm_energy, the first launch of taco_pcm_nonsilent and its only pass over the samples, alone: d_energy [B, Mmax]
+ * uint64 receives E[b, j] for every j < M_b (include/taco_abi.h).  Arguments and errors as taco_pcm_nonsilent's. */
+int taco_debug_pcm_energy(void* hip_stream, const int16_t* d_pcm, const int32_t* d_num_frames, int B, int L, int channels, int sample_rate,
+                          uint64_t* d_energy);
+
 /* Test hook: a taco_gl handle of either flavour (tf_flavor != 0: taco_gl_create_tf's) whose packs are built on the host and never
  * uploaded -- no device is touched.  It serves the argument and state checks of the taco_gl_* entry points, which come before their
  * first device call, on a machine without a GPU; nothing may be launched on it.  Freed by taco_gl_destroy. */

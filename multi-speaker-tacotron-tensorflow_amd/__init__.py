@@ -7,5 +7,5 @@ from .synthesizer import Synthesizer                                            
 from .audio import GriffinLim, Spectrogram, Resampler                                   # noqa: F401
 from .trainer import Trainer                                                       # noqa: F401
 from .feeder import DeviceCorpus                                                   # noqa: F401
-from .silence import split_on_silence                                              # noqa: F401
+from .silence import split_on_silence, split_on_silence_pydub, amplify             # noqa: F401
 from . import audio, weights, dist, _lib, train_ops, tf_checkpoint, text, korean, feeder, silence  # noqa: F401

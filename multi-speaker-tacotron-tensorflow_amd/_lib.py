@@ -154,6 +154,11 @@ PROTOTYPES = {
     "taco_wav_split_workspace_bytes": (_S, [_I, _I, _I, _I]),
     "taco_wav_split": (_I, [_P, _P, _P, _I, _I, C.c_float, _I, _I, _I, _I, _P, _P, _P, _P, _S]),
     "taco_wav_breath_mute": (_I, [_P, _P, _P, _I, _I, _P, _P, _I, C.c_float, _P, _P, _P]),
+    "taco_pcm_rate_supported": (_I, [_I]),
+    "taco_pcm_nonsilent_workspace_bytes": (_S, [_I, _I, _I]),
+    "taco_pcm_nonsilent": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _S]),
+    "taco_pcm_range_sumsq": (_I, [_P, _P, _P, _I, _I, _I, _I, _P, _P, _I, _P, _P]),
+    "taco_pcm_apply_gains": (_I, [_P, _P, _P, _I, _I, _I, _I, _P, _P, _I, _P, _P, _I, _P]),
     "taco_resample_create": (_I, [_I, _I, _P, _I, _I, _I, C.POINTER(_P)]),
     "taco_resample_destroy": (None, [_P]),
     "taco_resample_out_len": (_I, [_P, _I]),
@@ -170,6 +175,7 @@ PROTOTYPES = {
     "taco_spec_workspace_bytes": (_S, [_P, _I, _I]),
     "taco_spec_targets": (_I, [_P, _P, _P, _P, _I, _I, _P, _P, _P, _P, _S]),
     "taco_collate": (_I, [_P, C.POINTER(TacoCollateStream), _I, _P, _I, _I]),
+    "taco_debug_pcm_energy": (_I, [_P, _P, _P, _I, _I, _I, _I, _P]),
     "taco_debug_spec_epilogue": (_I, [_P, _P, _P, _I, _P, _P]),
     "taco_attention_trim": (_I, [_P, _P, _P, _I, _I, _I, _I, _P]),
     "taco_loss_f32": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _S]),

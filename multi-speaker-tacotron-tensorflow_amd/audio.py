@@ -104,6 +104,22 @@ def _energy(name):
     return _ENERGY[name]
 
 
+def pcm_frame_of_ms(j, sample_rate):
+    """The frame at which millisecond j starts: floor(j * sr / 1000), pydub's int(j * (sr / 1000.0)) (include/taco_abi.h)"""
+    return int(j) * int(sample_rate) // 1000
+
+
+def pcm_len_ms(n, sample_rate):
+    """Milliseconds of n frames: pydub's len(AudioSegment) = round(1000 * (n / sr)), Python's round (half to even)"""
+    return int(round(1000.0 * (int(n) / float(sample_rate))))
+
+
+def pcm_threshold(silence_thresh):
+    """The integer bound k = floor(10^(dB/20) * 32768) of taco_pcm_nonsilent: audioop.rms returns an integer, so pydub's rms <= thresh
+    is rms <= k.  No rms passes 32768, so a larger k means what 32768 does."""
+    return int(min(np.floor(10 ** (float(silence_thresh) / 20) * 32768.0), 32768.0))
+
+
 def _workspace(handle, nbytes):
     """The handle's workspace, grown to nbytes"""
     if handle._ws is None or handle._ws.numel() < nbytes:
@@ -142,7 +158,7 @@ class _Handle(object):
 class GriffinLim(_Handle):
     """flavor "librosa" (default): the handle of inv_spectrogram / inv_melspectrogram and of everything Spectrogram adds.  "tensorflow":
     the handle of inv_spectrogram_tensorflow (tf.contrib.signal's uncentred STFT; the librosa-flavour methods raise TacoError on it).
-    pcm16, trim, split, remove_breath, set_inv_mel_basis and mel_to_linear work on either."""
+    pcm16, trim, split, remove_breath, nonsilent, range_sumsq, apply_gains, set_inv_mel_basis and mel_to_linear work on either."""
     _destroy = "taco_gl_destroy"
 
     def __init__(self, hparams, device="cuda:0", flavor="librosa"):
@@ -315,6 +331,91 @@ class GriffinLim(_Handle):
         mean = torch.empty((B, 1 + M), dtype=torch.float32, device=dev) if return_info else None
         _call(dev, self._lib.taco_wav_breath_mute, _STREAM, x, ns, B, L, intervals, counts, M, float(threshold), out, muted, mean)
         return (out, (intervals, counts, muted, mean)) if return_info else out
+
+    def _pcm(self, pcm):
+        """int16 [B, L] (one channel) or [B, L, channels] interleaved, numpy or tensor -> a contiguous [B, L, channels] device tensor"""
+        x = pcm if torch.is_tensor(pcm) else torch.as_tensor(np.asarray(pcm))
+        if x.dtype != torch.int16:
+            raise _lib.TacoError(_lib.TACO_ERR_ARG, "pcm must be int16 (16-bit PCM, as pydub's AudioSegment holds it), got %s: pcm16 turns a float "
+                                 "waveform into it" % (x.dtype,))
+        if x.dim() not in (2, 3):
+            raise Exception("pcm must be [B, L] or [B, L, channels], got shape %s" % (tuple(x.shape),))
+        x = x.to(self.device).contiguous()
+        return x.unsqueeze(2) if x.dim() == 2 else x
+
+    def nonsilent(self, pcm, num_frames=None, sample_rate=None, min_silence_len=1000, silence_thresh=-16, max_ranges=None, return_window_sumsq=False,
+                  return_energy=False):
+        """pydub.silence.detect_nonsilent (seek_step=1) per row (audio/silence.py:90-92 calls it with min_silence_len=100,
+        silence_thresh=-40, app.py:34-35 with 300 / -50; the defaults here are pydub's): pcm int16 [B, L] or [B, L, channels] interleaved
+        (a float input is refused: see pcm16), num_frames [B] (a device int32 tensor is used as it is; None: L), sample_rate (None:
+        hparams.sample_rate) -> (ranges [B, R, 2], counts [B], len_ms [B]), device int32 tensors: row b's non-silent ranges in
+        milliseconds in order, counts[b] of them, exact zeros after, and the row's length in milliseconds.  R = max_ranges, by default
+        Mmax // (min_silence_len + 1) + 2, the most ranges Mmax = pcm_len_ms(L) milliseconds can hold; with a smaller R counts still
+        holds the true number and the first R ranges are written.  return_window_sumsq: also every window's sum of squares, int64
+        [B, Mmax], zeros past a row's own windows; return_energy: also the per-millisecond sums of squares int64 [B, Mmax] range_sumsq
+        takes (the call then works in a workspace of its own, which the tensor keeps alive; entries at or past a row's len_ms are
+        not written).  The threshold reaches the device as the integer k = pcm_threshold(silence_thresh).  UNPINNED on pydub
+        (include/taco_abi.h, taco_pcm_nonsilent), checked against tests/pydub_reference.py and the standard library's audioop."""
+        dev = self.device
+        x = self._pcm(pcm)
+        B, L, ch = x.shape
+        sr = int(getattr(self.hparams, "sample_rate", 24000) if sample_rate is None else sample_rate)
+        W = int(min_silence_len)
+        nf = _lengths(num_frames, dev, B, "num_frames")
+        mmax = pcm_len_ms(L, sr) if sr >= 1 and L >= 1 else 0
+        R = mmax // (max(W, 1) + 1) + 2 if max_ranges is None else int(max_ranges)
+        nbytes = self._lib.taco_pcm_nonsilent_workspace_bytes(B, L, sr)
+        ws = torch.empty(max(int(nbytes), 8), dtype=torch.uint8, device=dev) if return_energy else _workspace(self, max(nbytes, 8))
+        ranges = torch.empty((B, max(R, 1), 2), dtype=torch.int32, device=dev)
+        counts = torch.empty((B,), dtype=torch.int32, device=dev)
+        len_ms = torch.empty((B,), dtype=torch.int32, device=dev)
+        wss = torch.empty((B, mmax), dtype=torch.int64, device=dev) if return_window_sumsq else None
+        _call(dev, self._lib.taco_pcm_nonsilent, _STREAM, x, nf, B, L, ch, sr, W, pcm_threshold(silence_thresh), R, ranges, counts, len_ms, wss, ws,
+              ws.numel())
+        out = (ranges, counts, len_ms)
+        if return_window_sumsq:
+            out += (wss,)
+        if return_energy:
+            out += (ws[:B * mmax * 8].view(torch.int64).view(B, mmax),)
+        return out
+
+    def range_sumsq(self, energy, ranges, counts, L, channels, num_frames=None, sample_rate=None):
+        """The exact sum of squares and the number of samples of every range of a table in milliseconds: energy int64 [B, Mmax] as
+        `nonsilent(..., return_energy=True)` of a rectangle of L frames returned it, ranges int32 [B, R, 2], counts [B] -> (sumsq, samples),
+        int64 [B, R] device tensors, zeros at and past counts[b] (taco_pcm_range_sumsq)."""
+        dev = self.device
+        sr = int(getattr(self.hparams, "sample_rate", 24000) if sample_rate is None else sample_rate)
+        L, channels = int(L), int(channels)
+        ranges = _tensor(ranges, dev, torch.int32, "ranges", ("B", "R", ("2", 2)))
+        B, R, _ = ranges.shape
+        mmax = pcm_len_ms(L, sr) if sr >= 1 and L >= 1 else 0
+        energy = _tensor(energy, dev, torch.int64, "energy", (("B", B), ("Mmax", mmax)))
+        counts = _lengths(counts, dev, B, "counts")
+        nf = _lengths(num_frames, dev, B, "num_frames")
+        sumsq = torch.empty((B, R), dtype=torch.int64, device=dev)
+        samples = torch.empty((B, R), dtype=torch.int64, device=dev)
+        _call(dev, self._lib.taco_pcm_range_sumsq, _STREAM, energy if mmax else sumsq, nf, B, L, channels, sr, ranges, counts, R, sumsq, samples)
+        return sumsq, samples
+
+    def apply_gains(self, pcm, ranges, counts, gains, num_frames=None, sample_rate=None):
+        """audioop.mul per range and the cut of app.py's amplify: pcm int16 [B, L(, channels)], ranges int32 [B, R, 2] in milliseconds
+        and in order, counts [B], gains float64 [B, R] -> (out int16 [B, L_out, channels], out_frames [B] int32), device tensors: row b
+        holds the frames from its first range's start to its end in milliseconds, a sample inside range k as clip(floor(x * gains[b,
+        k])), a sample between ranges unchanged, zeros after out_frames[b]; L_out = pcm_frame_of_ms(pcm_len_ms(L)) (taco_pcm_apply_gains)."""
+        dev = self.device
+        x = self._pcm(pcm)
+        B, L, ch = x.shape
+        sr = int(getattr(self.hparams, "sample_rate", 24000) if sample_rate is None else sample_rate)
+        ranges = _tensor(ranges, dev, torch.int32, "ranges", (("B", B), "R", ("2", 2)))
+        R = ranges.shape[1]
+        counts = _lengths(counts, dev, B, "counts")
+        gains = _tensor(gains, dev, torch.float64, "gains", (("B", B), ("R", R)))
+        nf = _lengths(num_frames, dev, B, "num_frames")
+        L_out = max(1, pcm_frame_of_ms(pcm_len_ms(L, sr), sr)) if sr >= 1 else 1
+        out = torch.empty((B, L_out, ch), dtype=torch.int16, device=dev)
+        on = torch.empty((B,), dtype=torch.int32, device=dev)
+        _call(dev, self._lib.taco_pcm_apply_gains, _STREAM, x, nf, B, L, ch, sr, ranges, counts, R, gains, out, L_out, on)
+        return out, on
 
 
 class Spectrogram(GriffinLim):

@@ -600,3 +600,218 @@ static int trim_frames_per_tile(int N, int hop, int energy) {
   while (fpt > 0 && trim_lds_bytes(N, hop, fpt, energy) > TRIM_LDS_BYTES) --fpt;
   return fpt;
 }
+
+// ---- splitting and levelling 16-bit PCM on silence: pydub.silence.detect_nonsilent (audio/silence.py:81-117, app.py:27-53), restated;
+// UNPINNED on pydub (include/taco_abi.h).  Everything below is integer arithmetic: any order of a sum gives the same bits. ----
+#define PCM_THREADS 256        // four waves per workgroup of every kernel below
+#define PCM_E_MS 64            // milliseconds per tile of k_pcm_energy at most; pcm_energy_tile lowers it until the span fits PCM_E_LDS_WORDS
+#define PCM_E_LDS_WORDS 24576  // 16-bit words of LDS a tile's span may take (48 KB)
+#define PCM_W_TILE 256         // window starts per tile of k_pcm_windows: one per thread
+#define PCM_W_LDS_BYTES 65536  // dynamic LDS a launch gets without opting in to more: PCM_W_TILE + W energies of 8 bytes
+// Frame at which millisecond j starts: floor(j*sr/1000), pydub's int(j * (sr/1000.0)) (tests/test_pydub_host.py holds the two equal)
+__host__ __device__ __forceinline__ long long pcm_frame_of_ms(long long j, int sr) { return j * sr / 1000; }
+// Length in milliseconds of n frames: pydub's round(1000 * (n / sr)), Python's round (half to even), in double as pydub forms it.
+// One multiplication after one division: nothing to contract, and both are correctly rounded on the host and on the device.
+__host__ __device__ __forceinline__ int pcm_len_ms(int n, int sr) { return (int)rint(1000.0 * ((double)n / (double)sr)); }
+// Frames row b keeps: L, or num_frames[b] (device memory) clamped to [0, L]
+__device__ __forceinline__ int pcm_frames(const int* num_frames, int b, int L) { return num_frames ? min(max(num_frames[b], 0), L) : L; }
+
+// E[b, j] = sum of squares over frames [p(j), min(p(j + 1), n_b)) x channels of row b, for the row's own j < M_b = pcm_len_ms(n_b);
+// entries at or past M_b are not written (nothing reads them).  The only pass over the samples.  grid (tiles of ept milliseconds,
+// B), PCM_THREADS threads.  A workgroup stages its tile's span -- the words [(p(j0) - 0)*C, min(p(j0 + jt), n_b)*C) of the row -- in
+// LDS once: whole 16-byte lines of global memory by one 16-byte load each, the words before the first whole line and after the
+// last one by one 2-byte load each, so nothing before the row's first word and nothing at or past n_b is read.  The LDS image is
+// shifted by the span's offset within its 16-byte line, which makes every 16-byte store to LDS aligned as well.  Sixteen lanes then
+// take one millisecond: lane l adds the squares of words l, l + 16, ... and a butterfly joins the sixteen sums.
+__global__ __launch_bounds__(PCM_THREADS) void k_pcm_energy(const short* pcm, const int* num_frames, int L, int C, int sr, int ept, int Mmax,
+                                                            unsigned long long* E) {
+  extern __shared__ __attribute__((aligned(16))) short pcm_lds[];      // [8 + span + 8]
+  const int b = blockIdx.y, j0 = blockIdx.x * ept, tid = threadIdx.x;
+  const int n = pcm_frames(num_frames, b, L), M = pcm_len_ms(n, sr);
+  if (j0 >= M) return;
+  const int jt = min(ept, M - j0);
+  const long long f0 = min(pcm_frame_of_ms(j0, sr), (long long)n), f1 = min(pcm_frame_of_ms(j0 + jt, sr), (long long)n);
+  const short* src = pcm + ((size_t)b * L + (size_t)f0) * C;            // the span's first word
+  const int span = (int)(f1 - f0) * C;
+  const int shift = (int)((reinterpret_cast<uintptr_t>(src) & 15) >> 1);  // words between the 16-byte line and src
+  const int head = min((8 - shift) & 7, span), nvec = (span - head) >> 3, tail0 = head + (nvec << 3);
+  short* xs = pcm_lds + shift;                                            // xs[i] = src[i]; xs + head is 16-byte aligned
+  for (int i = tid; i < head; i += PCM_THREADS) xs[i] = src[i];
+  for (int v = tid; v < nvec; v += PCM_THREADS)
+    *reinterpret_cast<uint4*>(xs + head + (v << 3)) = *reinterpret_cast<const uint4*>(src + head + (v << 3));
+  for (int i = tail0 + tid; i < span; i += PCM_THREADS) xs[i] = src[i];
+  __syncthreads();
+  const int sub = tid >> 4, l = tid & 15;
+  for (int j = sub; j < jt; j += PCM_THREADS / 16) {
+    const long long a = min(pcm_frame_of_ms(j0 + j, sr), (long long)n), e = min(pcm_frame_of_ms(j0 + j + 1, sr), (long long)n);
+    const int lo = (int)(a - f0) * C, hi = (int)(e - f0) * C;
+    unsigned long long s = 0;
+    for (int i = lo + l; i < hi; i += 16) { const int v = xs[i]; s += (unsigned long long)(unsigned)(v * v); }
+    for (int o = 8; o > 0; o >>= 1) s += __shfl_xor(s, o, 16);
+    if (l == 0) E[(size_t)b * Mmax + j0 + j] = s;
+  }
+}
+
+// The silence flag of every window of W milliseconds on the millisecond grid.  Window i of row b, 0 <= i <= M_b - W, covers
+// frames [p(i), p(i + W)) over all channels: S_i = E[i] + ... + E[i + W - 1], c_i = (p(i + W) - p(i))*C samples -- a frame at or past
+// n_b is a zero frame that still counts -- and it is silent iff c_i == 0 or S_i < kk*c_i, kk = (k + 1)^2: audioop.rms's
+// (unsigned)sqrt(S/c) <= k (and its 0 for an empty fragment) as an integer comparison.  grid (tiles of PCM_W_TILE starts, B).  A
+// tile takes its PCM_W_TILE + W energies into LDS (zeros at and past M_b) and turns them into their exclusive prefix sums there --
+// every thread its own run of consecutive entries, the 256 run totals through a scan of shuffles and four wave totals -- so
+// S_i = P[i + W] - P[i] with no scan across tiles.  silent [B, Mmax] receives the flags of the row's own windows; window_sumsq
+// [B, Mmax] (nullable) S_i for them and zeros in every other word.
+__global__ __launch_bounds__(PCM_THREADS) void k_pcm_windows(const unsigned long long* E, const int* num_frames, int L, int C, int sr, int W,
+                                                             unsigned long long kk, int Mmax, unsigned char* silent,
+                                                             unsigned long long* window_sumsq) {
+  extern __shared__ __attribute__((aligned(16))) unsigned long long pcm_pre[];      // [PCM_W_TILE + W]
+  __shared__ unsigned long long wtot[PCM_THREADS / 64];
+  const int b = blockIdx.y, i0 = blockIdx.x * PCM_W_TILE, tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+  const int n = pcm_frames(num_frames, b, L), M = pcm_len_ms(n, sr);
+  const int nwin = M >= W ? M - W + 1 : 0, i = i0 + tid;
+  if (i0 >= nwin) {                                        // (the whole workgroup: no window of the row starts in this tile)
+    if (window_sumsq && i < Mmax) window_sumsq[(size_t)b * Mmax + i] = 0;
+    return;
+  }
+  const int items = PCM_W_TILE + W, q = (items + PCM_THREADS - 1) / PCM_THREADS;
+  const unsigned long long* e = E + (size_t)b * Mmax;
+  for (int m = tid; m < items; m += PCM_THREADS) pcm_pre[m] = i0 + m < M ? e[i0 + m] : 0ull;
+  __syncthreads();
+  const int m0 = min(tid * q, items), m1 = min(m0 + q, items);
+  unsigned long long run = 0;
+  for (int m = m0; m < m1; ++m) run += pcm_pre[m];
+  unsigned long long inc = run;                            // inclusive scan of the run totals inside the wave
+  for (int o = 1; o < 64; o <<= 1) { const unsigned long long up = __shfl_up(inc, o); if (lane >= o) inc += up; }
+  if (lane == 63) wtot[wave] = inc;
+  __syncthreads();
+  unsigned long long base = inc - run;
+  for (int w = 0; w < wave; ++w) base += wtot[w];
+  for (int m = m0; m < m1; ++m) { const unsigned long long v = pcm_pre[m]; pcm_pre[m] = base; base += v; }
+  __syncthreads();
+  unsigned long long S = 0;
+  if (i < nwin) {
+    S = pcm_pre[tid + W] - pcm_pre[tid];
+    const unsigned long long c = (unsigned long long)(pcm_frame_of_ms((long long)i + W, sr) - pcm_frame_of_ms(i, sr)) * (unsigned long long)C;
+    silent[(size_t)b * Mmax + i] = (c == 0 || S < kk * c) ? 1 : 0;
+  }
+  if (window_sumsq && i < Mmax) window_sumsq[(size_t)b * Mmax + i] = S;
+}
+
+// detect_silence and detect_nonsilent of row b from the flags k_pcm_windows wrote, in milliseconds and in order.  pydub joins the
+// silent starts into ranges [a, b + W] and opens a new one only at a start a > b_prev + W, b_prev the silent start before it; the
+// non-silent ranges are the gaps.  Restated per window start i, with `prev` the last silent start before i (none: -1): i OPENS a
+// silent range iff it is silent and (prev is none or i - prev > W), and the non-silent range that ends there is [0, i] for the first
+// opening (dropped when i == 0: pydub's removed [0, 0]) and [prev + W, i] for every later one.  After the last window: no silent
+// start at all gives [0, M] (also when M < W); otherwise [last + W, M] unless last + W == M.  So every range is written whole by one
+// thread from a look BACK alone: prev comes from the ballots of the chunk's four waves and a value carried across the 256-start
+// chunks of a long row, the range's position from a prefix count of the openings as k_split_edges counts its edges -- no atomics,
+// two calls return the same bits.  counts[b] receives the true number of ranges; only the first max_ranges are written and every
+// other word of the row's table is an exact zero.  len_ms[b] (nullable) receives M.  One workgroup per row.
+__global__ __launch_bounds__(PCM_THREADS) void k_pcm_ranges(const unsigned char* silent, const int* num_frames, int L, int sr, int W, int Mmax,
+                                                            int max_ranges, int* ranges, int* counts, int* len_ms) {
+  __shared__ unsigned long long wmask[4];
+  __shared__ int wopen[4];
+  const int b = blockIdx.x, tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+  const int n = pcm_frames(num_frames, b, L), M = pcm_len_ms(n, sr);
+  const int nwin = M >= W ? M - W + 1 : 0;
+  const unsigned char* f = silent + (size_t)b * Mmax;
+  int* tab = ranges + (size_t)b * max_ranges * 2;
+  long long seen = 0;                                      // ranges of the chunks before this one (the same in every thread)
+  int last = -1;                                           // the last silent start of the chunks before this one
+  for (int t0 = 0; t0 < nwin; t0 += PCM_THREADS) {
+    const int i = t0 + tid;
+    const bool s = i < nwin && f[i] != 0;
+    const unsigned long long m = __ballot(s);
+    if (lane == 0) wmask[wave] = m;
+    __syncthreads();
+    int prev = last;
+    const unsigned long long below = m & ((1ull << lane) - 1);
+    if (below) prev = t0 + wave * 64 + 63 - __clzll(below);
+    else
+      for (int w = wave - 1; w >= 0; --w)
+        if (wmask[w]) { prev = t0 + w * 64 + 63 - __clzll(wmask[w]); break; }
+    const bool open = s && i > 0 && (prev < 0 || i - prev > W);      // (i == 0 opens the range whose gap [0, 0] pydub removes)
+    const unsigned long long om = __ballot(open);
+    if (lane == 0) wopen[wave] = __popcll(om);
+    __syncthreads();
+    long long k = seen + __popcll(om & ((1ull << lane) - 1));
+    for (int w = 0; w < wave; ++w) k += wopen[w];
+    if (open && k < max_ranges) { tab[2 * k] = prev < 0 ? 0 : prev + W; tab[2 * k + 1] = i; }
+    seen += wopen[0] + wopen[1] + wopen[2] + wopen[3];
+    for (int w = 3; w >= 0; --w)
+      if (wmask[w]) { last = t0 + w * 64 + 63 - __clzll(wmask[w]); break; }
+    __syncthreads();                                       // wmask and wopen are rewritten by the next chunk
+  }
+  if (last < 0 || last + W != M) {                         // the range that runs to the end of the row
+    if (tid == 0 && seen < max_ranges) { tab[2 * seen] = last < 0 ? 0 : last + W; tab[2 * seen + 1] = M; }
+    seen += 1;
+  }
+  if (tid == 0) { counts[b] = (int)seen; if (len_ms) len_ms[b] = M; }
+  for (long long w = 2 * min(seen, (long long)max_ranges) + tid; w < 2LL * max_ranges; w += PCM_THREADS) tab[w] = 0;
+}
+
+// The exact sum of squares and the number of samples of every range of a table [B, max_ranges, 2] in milliseconds, from the energies
+// k_pcm_energy wrote: range k of row b = [s, e) clamped to 0 <= s <= e <= M_b has sumsq = E[s] + ... + E[e - 1] -- the frames
+// [p(s), p(e)) over all channels, zero frames at or past n_b -- and samples = (p(e) - p(s))*C.  Ranges at or past counts[b] give zeros.
+// grid (groups of four ranges, B): a wave per range, lane l adds entries l, l + 64, ..., a butterfly joins them.
+__global__ __launch_bounds__(PCM_THREADS) void k_pcm_range_sumsq(const unsigned long long* E, const int* num_frames, int L, int C, int sr, int Mmax,
+                                                                 const int* ranges, const int* counts, int max_ranges,
+                                                                 unsigned long long* sumsq, long long* samples) {
+  const int b = blockIdx.y, k = blockIdx.x * (PCM_THREADS / 64) + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+  if (k >= max_ranges) return;
+  const int n = pcm_frames(num_frames, b, L), M = pcm_len_ms(n, sr);
+  unsigned long long acc = 0;
+  long long c = 0;
+  if (k < counts[b]) {
+    const int* r = ranges + ((size_t)b * max_ranges + k) * 2;
+    const int s = min(max(r[0], 0), M), e = min(max(r[1], s), M);
+    const unsigned long long* row = E + (size_t)b * Mmax;
+    for (int j = s + lane; j < e; j += 64) acc += row[j];
+    c = (pcm_frame_of_ms(e, sr) - pcm_frame_of_ms(s, sr)) * C;
+  }
+  for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o);
+  if (lane == 0) { sumsq[(size_t)b * max_ranges + k] = acc; samples[(size_t)b * max_ranges + k] = c; }
+}
+
+// audioop.mul per range, and the cut app.py's amplify makes: row b of out [B, L_out, C] receives the frames [p(s_0), p(M_b)) of row
+// b of pcm -- s_0 the start of its first range; zero frames at or past n_b -- where a sample x of a frame inside range k becomes
+// clip(floor((double)x * gains[b, k]), -32768, 32767) and a sample between ranges is copied.  A frame f lies in millisecond
+// j(f) = ((f + 1)*1000 - 1) / sr, the largest j with p(j) <= f, so f is inside [p(s), p(e)) iff s <= j(f) < e: the range is found by
+// bisection over the row's first min(counts[b], max_ranges) starts, which are in order.  out_frames[b] receives the row's true length
+// p(M_b) - p(s_0), 0 without a range; frames past it, and past L_out, are zeros resp. not written.  grid (tiles of 256 frames, B).
+__global__ __launch_bounds__(PCM_THREADS) void k_pcm_apply_gains(const short* pcm, const int* num_frames, int L, int C, int sr, const int* ranges,
+                                                                 const int* counts, int max_ranges, const double* gains, short* out, int L_out,
+                                                                 int* out_frames) {
+  const int b = blockIdx.y, fo = blockIdx.x * PCM_THREADS + threadIdx.x;
+  const int n = pcm_frames(num_frames, b, L), M = pcm_len_ms(n, sr);
+  const int cnt = min(max(counts[b], 0), max_ranges);
+  const int* tab = ranges + (size_t)b * max_ranges * 2;
+  const long long first = cnt > 0 ? pcm_frame_of_ms(min(max(tab[0], 0), M), sr) : 0;
+  const long long len = cnt > 0 ? pcm_frame_of_ms(M, sr) - first : 0;
+  if (fo == 0 && out_frames) out_frames[b] = (int)len;
+  if (fo >= L_out) return;
+  short* y = out + ((size_t)b * L_out + fo) * C;
+  const long long f = first + fo;
+  if (fo >= len || f >= n) {                               // past the row's output, or a zero frame: floor(0 * g) = 0
+    for (int c = 0; c < C; ++c) y[c] = 0;
+    return;
+  }
+  const int j = (int)(((f + 1) * 1000 - 1) / sr);
+  int lo = 0, hi = cnt;                                    // the last range with start <= j, if any: lo - 1
+  while (lo < hi) { const int mid = (lo + hi) >> 1; if (tab[2 * mid] <= j) lo = mid + 1; else hi = mid; }
+  const bool inside = lo > 0 && j < tab[2 * lo - 1];
+  const short* x = pcm + ((size_t)b * L + (size_t)f) * C;
+  if (!inside) {
+    for (int c = 0; c < C; ++c) y[c] = x[c];
+    return;
+  }
+  const double g = gains[(size_t)b * max_ranges + lo - 1];
+  for (int c = 0; c < C; ++c) y[c] = (short)fmin(fmax(floor((double)x[c] * g), -32768.0), 32767.0);
+}
+
+// Milliseconds per tile of k_pcm_energy: the most, up to PCM_E_MS, whose span fits PCM_E_LDS_WORDS; 0 = not even one
+static size_t pcm_energy_span_words(int ept, int C, int sr) { return (size_t)(((long long)ept * sr + 999) / 1000 + 1) * C; }
+static int pcm_energy_tile(int C, int sr) {
+  int ept = PCM_E_MS;
+  while (ept > 0 && pcm_energy_span_words(ept, C, sr) + 16 > PCM_E_LDS_WORDS) --ept;
+  return ept;
+}

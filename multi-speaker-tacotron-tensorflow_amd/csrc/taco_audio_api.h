@@ -410,3 +410,143 @@ int taco_debug_spec_epilogue(taco_gl* g, void* hip_stream, const float* d_est, i
   HIPCHK(hipSetDevice(g->gm->device));
   return spec_epilogue(g, (hipStream_t)hip_stream, d_est, nullptr, 1, R, R, d_linear, d_mel);
 }
+
+// ---- splitting and levelling 16-bit PCM on silence: pydub.silence.detect_nonsilent (audio/silence.py:81-117, app.py:27-53) ----
+// The workspace of taco_pcm_nonsilent: the energies E [B, Mmax] first (taco_pcm_range_sumsq reads them from there), then the flags
+struct PcmWs { unsigned long long* E; unsigned char* silent; };
+static void carve_pcm(Carver& cv, int B, int Mmax, PcmWs& w) {
+  w.E = (unsigned long long*)cv.raw((size_t)B * Mmax * sizeof(unsigned long long));
+  w.silent = (unsigned char*)cv.raw((size_t)B * Mmax);
+}
+// Milliseconds of a row of L frames (every row's M_b is at most this); -1 where it passes what an int32 table can hold
+static long long pcm_len_max(int L, int sample_rate) {
+  const double m = rint(1000.0 * ((double)L / (double)sample_rate));
+  return m <= 2.0e9 ? (long long)m : -1;
+}
+// The front of the three entry points: the shape of the rectangle and the grid of milliseconds, in one order.  The rate rule: with
+// r = fl(sr/1000.0) >= sr/1000, fl(j*r) is never below an integral j*sr/1000 and stays within 1/1000 of any other while j*sr/1000 <
+// 2^52/1000, so pydub's int(j * (sr/1000.0)) equals floor(j*sr/1000) at every millisecond of any row; with r below sr/1000 (1001 Hz
+// at j = 1000) it does not, and such a rate is refused.  fma forms r*1000 - sr with one rounding: its sign is exact.
+static int pcm_grid(int B, int L, int channels, int sample_rate, int max_ranges, int* Mmax) {
+  if (B < 1 || B > 65535 || L < 1 || channels < 1 || sample_rate < 1)
+    return fail(TACO_ERR_ARG, "bad argument: B %d, L %d, channels %d, sample_rate %d", B, L, channels, sample_rate);
+  if (max_ranges < 1) return fail(TACO_ERR_ARG, "max_ranges = %d", max_ranges);
+  const long long m = pcm_len_max(L, sample_rate);
+  if (m < 0) return fail(TACO_ERR_SHAPE, "L = %d frames at %d Hz: more milliseconds than an int32 table holds", L, sample_rate);
+  *Mmax = (int)m;
+  return 0;
+}
+static int pcm_rate_check(int sample_rate) {
+  if (!taco_pcm_rate_supported(sample_rate))
+    return fail(TACO_ERR_UNSUPPORTED, "sample_rate = %d: sample_rate/1000.0 rounds below the quotient, where pydub's int(j * (sr/1000.0)) "
+                "and floor(j*sr/1000) part", sample_rate);
+  return 0;
+}
+
+int taco_pcm_rate_supported(int sample_rate) {      // host arithmetic only: needs no device
+  return sample_rate >= 1 && std::fma((double)sample_rate / 1000.0, 1000.0, -(double)sample_rate) >= 0.0;
+}
+
+// k_pcm_energy on a rectangle the caller has checked (pcm_grid, pcm_rate_check, ept >= 1, Mmax > 0)
+static void pcm_launch_energy(hipStream_t st, const int16_t* d_pcm, const int32_t* d_num_frames, int B, int L, int channels, int sample_rate, int ept,
+                              int Mmax, unsigned long long* E) {
+  hipLaunchKernelGGL(k_pcm_energy, dim3(cdiv(Mmax, ept), B), dim3(PCM_THREADS), (pcm_energy_span_words(ept, channels, sample_rate) + 16) * sizeof(short),
+                     st, d_pcm, d_num_frames, L, channels, sample_rate, ept, Mmax, E);
+}
+
+size_t taco_pcm_nonsilent_workspace_bytes(int B, int L, int sample_rate) {
+  if (B < 1 || L < 1 || sample_rate < 1) return 0;
+  const long long m = pcm_len_max(L, sample_rate);
+  if (m < 0) return 0;
+  Carver cv(nullptr, 0);
+  PcmWs w; carve_pcm(cv, B, (int)m, w);
+  return cv.off;
+}
+
+int taco_pcm_nonsilent(void* hip_stream, const int16_t* d_pcm, const int32_t* d_num_frames, int B, int L, int channels, int sample_rate,
+                       int min_silence_len, int k, int max_ranges, int32_t* d_ranges, int32_t* d_counts, int32_t* d_len_ms,
+                       uint64_t* d_window_sumsq, void* d_workspace, size_t workspace_bytes) {
+  if (!d_pcm || !d_ranges || !d_counts || !d_workspace) return fail(TACO_ERR_ARG, "null argument");
+  int Mmax;
+  TRY(pcm_grid(B, L, channels, sample_rate, max_ranges, &Mmax));
+  if (min_silence_len < 1) return fail(TACO_ERR_ARG, "min_silence_len = %d", min_silence_len);
+  if (k < 0) return fail(TACO_ERR_ARG, "k = %d: the bound floor(10^(dB/20) * 32768) is not negative", k);
+  if ((reinterpret_cast<uintptr_t>(d_pcm) & 1) || (reinterpret_cast<uintptr_t>(d_workspace) & 7) || (reinterpret_cast<uintptr_t>(d_window_sumsq) & 7))
+    return fail(TACO_ERR_ARG, "misaligned pointer: d_pcm holds 2-byte words, the workspace and d_window_sumsq 8-byte words");
+  const size_t need = taco_pcm_nonsilent_workspace_bytes(B, L, sample_rate);
+  if (workspace_bytes < need) return fail(TACO_ERR_ARG, "workspace too small: need %zu bytes, have %zu", need, workspace_bytes);
+  TRY(pcm_rate_check(sample_rate));
+  if (k > 32768) k = 32768;      // no rms passes 32768: a larger bound means what 32768 does
+  const int W = min_silence_len, ept = pcm_energy_tile(channels, sample_rate);
+  if (ept < 1)
+    return fail(TACO_ERR_UNSUPPORTED, "sample_rate %d x %d channels: k_pcm_energy keeps a millisecond of samples in %d KB of LDS", sample_rate, channels,
+                PCM_E_LDS_WORDS * 2 / 1024);
+  const size_t wlds = ((size_t)PCM_W_TILE + W) * sizeof(unsigned long long);
+  if (wlds + 256 > PCM_W_LDS_BYTES)
+    return fail(TACO_ERR_UNSUPPORTED, "min_silence_len = %d: k_pcm_windows keeps %d + min_silence_len energies in %d KB of LDS", W, PCM_W_TILE,
+                PCM_W_LDS_BYTES / 1024);
+  const unsigned __int128 kk = (unsigned __int128)(k + 1LL) * (unsigned __int128)(k + 1LL);
+  const unsigned __int128 cmax = (unsigned __int128)((long long)W * sample_rate / 1000 + 1) * (unsigned)channels;
+  if (kk * cmax >= ((unsigned __int128)1 << 52))
+    return fail(TACO_ERR_UNSUPPORTED, "(k + 1)^2 times the samples of a window reaches 2^52 (k %d, min_silence_len %d, sample_rate %d, channels %d): "
+                "the integer comparison stands for audioop.rms's double only below that", k, W, sample_rate, channels);
+  hipStream_t st = (hipStream_t)hip_stream;
+  Carver cv(d_workspace, workspace_bytes);
+  PcmWs w; carve_pcm(cv, B, Mmax, w);
+  if (Mmax > 0) {      // (a rectangle shorter than half a millisecond has no energies and no windows: every row is [[0, 0]])
+    pcm_launch_energy(st, d_pcm, d_num_frames, B, L, channels, sample_rate, ept, Mmax, w.E);
+    hipLaunchKernelGGL(k_pcm_windows, dim3(cdiv(Mmax, PCM_W_TILE), B), dim3(PCM_THREADS), wlds, st, w.E, d_num_frames, L, channels, sample_rate, W,
+                       (unsigned long long)kk, Mmax, w.silent, (unsigned long long*)d_window_sumsq);
+  }
+  hipLaunchKernelGGL(k_pcm_ranges, dim3(B), dim3(PCM_THREADS), 0, st, w.silent, d_num_frames, L, sample_rate, W, Mmax, max_ranges, d_ranges, d_counts,
+                     d_len_ms);
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
+int taco_pcm_range_sumsq(void* hip_stream, const uint64_t* d_energy, const int32_t* d_num_frames, int B, int L, int channels, int sample_rate,
+                         const int32_t* d_ranges, const int32_t* d_counts, int max_ranges, uint64_t* d_sumsq, int64_t* d_samples) {
+  if (!d_energy || !d_ranges || !d_counts || !d_sumsq || !d_samples) return fail(TACO_ERR_ARG, "null argument");
+  int Mmax;
+  TRY(pcm_grid(B, L, channels, sample_rate, max_ranges, &Mmax));
+  if ((reinterpret_cast<uintptr_t>(d_energy) & 7) || (reinterpret_cast<uintptr_t>(d_sumsq) & 7) || (reinterpret_cast<uintptr_t>(d_samples) & 7))
+    return fail(TACO_ERR_ARG, "misaligned pointer: d_energy, d_sumsq and d_samples hold 8-byte words");
+  TRY(pcm_rate_check(sample_rate));
+  hipLaunchKernelGGL(k_pcm_range_sumsq, dim3(cdiv(max_ranges, PCM_THREADS / 64), B), dim3(PCM_THREADS), 0, (hipStream_t)hip_stream,
+                     (const unsigned long long*)d_energy, d_num_frames, L, channels, sample_rate, Mmax, d_ranges, d_counts, max_ranges,
+                     (unsigned long long*)d_sumsq, (long long*)d_samples);
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
+int taco_pcm_apply_gains(void* hip_stream, const int16_t* d_pcm, const int32_t* d_num_frames, int B, int L, int channels, int sample_rate,
+                         const int32_t* d_ranges, const int32_t* d_counts, int max_ranges, const double* d_gains, int16_t* d_out, int L_out,
+                         int32_t* d_out_frames) {
+  if (!d_pcm || !d_ranges || !d_counts || !d_gains || !d_out) return fail(TACO_ERR_ARG, "null argument");
+  int Mmax;
+  TRY(pcm_grid(B, L, channels, sample_rate, max_ranges, &Mmax));
+  if (L_out < 1) return fail(TACO_ERR_ARG, "L_out = %d", L_out);
+  if ((reinterpret_cast<uintptr_t>(d_pcm) & 1) || (reinterpret_cast<uintptr_t>(d_out) & 1) || (reinterpret_cast<uintptr_t>(d_gains) & 7))
+    return fail(TACO_ERR_ARG, "misaligned pointer: d_pcm and d_out hold 2-byte words, d_gains 8-byte words");
+  TRY(pcm_rate_check(sample_rate));
+  hipLaunchKernelGGL(k_pcm_apply_gains, dim3(cdiv(L_out, PCM_THREADS), B), dim3(PCM_THREADS), 0, (hipStream_t)hip_stream, d_pcm, d_num_frames, L,
+                     channels, sample_rate, d_ranges, d_counts, max_ranges, d_gains, d_out, L_out, d_out_frames);
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
+int taco_debug_pcm_energy(void* hip_stream, const int16_t* d_pcm, const int32_t* d_num_frames, int B, int L, int channels, int sample_rate,
+                          uint64_t* d_energy) {
+  if (!d_pcm || !d_energy) return fail(TACO_ERR_ARG, "null argument");
+  int Mmax;
+  TRY(pcm_grid(B, L, channels, sample_rate, 1, &Mmax));
+  if ((reinterpret_cast<uintptr_t>(d_pcm) & 1) || (reinterpret_cast<uintptr_t>(d_energy) & 7))
+    return fail(TACO_ERR_ARG, "misaligned pointer: d_pcm holds 2-byte words, d_energy 8-byte words");
+  TRY(pcm_rate_check(sample_rate));
+  const int ept = pcm_energy_tile(channels, sample_rate);
+  if (ept < 1) return fail(TACO_ERR_UNSUPPORTED, "sample_rate %d x %d channels: k_pcm_energy keeps a millisecond of samples in %d KB of LDS", sample_rate, channels,
+                           PCM_E_LDS_WORDS * 2 / 1024);
+  if (Mmax > 0) pcm_launch_energy((hipStream_t)hip_stream, d_pcm, d_num_frames, B, L, channels, sample_rate, ept, Mmax, (unsigned long long*)d_energy);
+  HIPCHK(hipGetLastError());
+  return 0;
+}

@@ -25,7 +25,14 @@ the same mono input, whose values bound the device's error; and three minutes at
 existing inv_spectrogram, inv_spectrogram_tensorflow (GriffinLim(flavor="tensorflow")) and inv_melspectrogram (80 mels), plus
 k_gl_mel_magnitude alone (GriffinLim.mel_to_linear on the same batch: the kernel without its ^power) -- each arm's ms, the TF arm relative
 to the existing one, and k_gl_mel_magnitude relative to one Griffin-Lim iteration of the same run (the existing arm at 60 and at 0 iterations,
-their difference over 60).  Its own JSON line, `--vocoders` only."""
+their difference over 60).  Its own JSON line, `--vocoders` only.
+`--pydub` measures the reference's other way of splitting (audio/silence.py:81-117) and app.py's amplify on three minutes of seeded
+speech-like bursts at 44100 Hz, stereo, 16-bit PCM: GriffinLim.nonsilent alone (100 ms / -40 dBFS, the recording on the device), the whole
+silence.split_on_silence_pydub and the whole silence.amplify (upload, kernels, tables and results downloaded), windows alternating; the
+energy pass alone (k_pcm_energy through taco_debug_pcm_energy: the only launch that reads the samples) with the bytes of the recording
+over its time, beside a device copy of the same buffer (which reads and writes those bytes); and on the host the restatement tests/pydub_reference.py: its
+fast form on the whole recording and its literal audioop form on the first ten seconds ("literal, 10 s": not extrapolated).  Its own JSON
+line, `--pydub` only."""
 import json, os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "oracle"))
@@ -286,6 +293,89 @@ def vocoders():
     return out
 
 
+def pydub_recording(seconds=180, sr=44100, seed=7):
+    """int16 [seconds * sr, 2]: a floor of +-3; utterances of 1-6 s made of phrases (uniform in +-3000..9000) of 0.3-1.0 s with pauses of
+    20-80 ms at +-20 between them, separated by 0.3-1.2 s of floor."""
+    rs = np.random.RandomState(seed)
+    n = seconds * sr
+    x = rs.randint(-3, 4, size=(n, 2))
+    t = int(0.4 * sr)
+    while True:
+        end = t + int(rs.uniform(1.0, 6.0) * sr)
+        if end >= n - sr:
+            break
+        while t < end:
+            m = min(end - t, int(rs.uniform(0.3, 1.0) * sr)); a = int(rs.uniform(3000, 9000))
+            x[t:t + m] = rs.randint(-a, a + 1, size=(m, 2)); t += m
+            m = min(end - t, int(rs.uniform(0.02, 0.08) * sr))
+            x[t:t + m] = rs.randint(-20, 21, size=(m, 2)); t += m
+        t = end + int(rs.uniform(0.3, 1.2) * sr)
+    return x.astype(np.int16)
+
+
+def pydub():
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import pydub_reference as R
+    from taco_amd import silence
+    sr, seconds = 44100, 180
+    x = pydub_recording(seconds, sr)
+    dev = silence.PcmDevice(hp)
+    gl = dev.gl
+    pcm = dev.upload(x)["pcm"]
+    import ctypes as C
+    energy = torch.empty((1, R.len_ms(len(x), sr)), dtype=torch.int64, device="cuda")
+    ptr = lambda t: C.c_void_p(t.data_ptr())
+    energy_pass = lambda: taco_amd._lib.check(gl._lib.taco_debug_pcm_energy(C.c_void_p(torch.cuda.current_stream().cuda_stream), ptr(pcm), None, 1, len(x), 2, sr, ptr(energy)))
+    arms = {"nonsilent": (lambda: gl.nonsilent(pcm, None, sr, 100, -40), 20), "energy_pass": (energy_pass, 20), "device_copy": (lambda: pcm.clone(), 20),
+            "split_on_silence_pydub": (lambda: silence.split_on_silence_pydub(x, sr, device=dev), 2), "amplify": (lambda: silence.amplify(x, sr, device=dev), 2)}
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    for f, _ in arms.values():
+        for _ in range(2):
+            f()
+    torch.cuda.synchronize()
+    ms = {k: [] for k in arms}
+    for _ in range(5):
+        for k, (f, reps) in arms.items():
+            e0.record()
+            for _ in range(reps):
+                f()
+            e1.record(); torch.cuda.synchronize()
+            ms[k].append(e0.elapsed_time(e1) / reps)
+    med = {k: float(np.median(v)) for k, v in ms.items()}
+    a, b = gl.nonsilent(pcm, None, sr, 100, -40), gl.nonsilent(pcm, None, sr, 100, -40)
+    ranges = a[0][0, :int(a[1][0])].cpu().numpy().tolist()
+    segments = silence.split_on_silence_pydub(x, sr, device=dev)
+    loud = silence.amplify(x, sr, device=dev)
+    t0 = time.perf_counter(); ref_ranges, M = R.detect_nonsilent(x, sr, 100, -40); fast_s = time.perf_counter() - t0
+    ref_segments = R.split_on_silence_with_pydub(x, sr)
+    t0 = time.perf_counter(); ref_loud = R.amplify(x, sr); fast_amplify_s = time.perf_counter() - t0
+    literal_s = None
+    if R.HAVE_AUDIOOP:
+        head = x[:10 * sr]
+        t0 = time.perf_counter(); lit = R.detect_nonsilent_literal(R.Segment.of(head, sr), 100, -40); literal_s = time.perf_counter() - t0
+        assert lit == R.detect_nonsilent(head, sr, 100, -40)[0]
+    nbytes = x.nbytes
+    out = {"metric": "pydub method (audio/silence.py:81-117: detect_nonsilent at 100 ms / -40 dBFS, merge, keep_silence) of one recording",
+           "value": med["split_on_silence_pydub"], "unit": "ms", "recording": "%d s at %d Hz, stereo PCM16, %d frames, %d ms" % (seconds, sr, len(x), M),
+           "windows": "5 windows per arm, alternating: 20 calls of nonsilent, of the energy pass and of the copy, 2 of split_on_silence_pydub and of amplify",
+           "nonsilent_ms": ms["nonsilent"], "split_on_silence_pydub_ms": ms["split_on_silence_pydub"], "amplify_ms": ms["amplify"],
+           "device_copy_ms": ms["device_copy"], "median_ms": med, "x_realtime": seconds / (med["split_on_silence_pydub"] / 1e3),
+           "energy_pass_ms": ms["energy_pass"], "recording_bytes": nbytes, "energy_pass_read_GBps": nbytes / (med["energy_pass"] / 1e3) / 1e9,
+           "device_copy_read_GBps": nbytes / (med["device_copy"] / 1e3) / 1e9, "device_copy_read_plus_write_GBps": 2 * nbytes / (med["device_copy"] / 1e3) / 1e9,
+           "cpu_restatement_fast_form_s": fast_s, "cpu_restatement_fast_form_amplify_s": fast_amplify_s,
+           "cpu_restatement_literal_audioop_s": literal_s, "cpu_restatement_literal_audioop_label": "literal, 10 s",
+           "nonsilent_ranges": len(ranges), "segments": len(segments), "amplified_frames": int(len(loud)),
+           "ranges_equal_to_the_restatement": bool(ranges == ref_ranges),
+           "segments_equal_to_the_restatement": bool([g[:3] for g in segments] == [r[:3] for r in ref_segments] and all(np.array_equal(g[3], r[3]) for g, r in zip(segments, ref_segments))),
+           "amplify_equals_the_restatement": bool(np.array_equal(loud, ref_loud)),
+           "identical_bits_on_two_calls": bool(all(torch.equal(u, v) for u, v in zip(a, b)))}
+    dev.close()
+    return out
+
+
+if "--pydub" in sys.argv:
+    print(json.dumps(pydub()))
+    sys.exit(0)
 if "--vocoders" in sys.argv:
     print(json.dumps(vocoders()))
     sys.exit(0)
