@@ -106,6 +106,34 @@ int taco_train_debug_bigru(taco_train* t, void* hip_stream, const float* d_xproj
                            const float* d_dout, int B, int T, int persistent, float* d_out, float* d_gsave, float* d_dg, float* d_rh,
                            float* d_dh0, void* d_scratch, size_t scratch_bytes);
 
+/* Test hook: ONE CBHG of a trainer alone -- the training forward with its tape (cbhg_forward_train), then its backward (cbhg_backward) -- on caller
+ * data, exactly as the step calls them: the step's context and state objects, the tape layout of the step, the trainer's current switches
+ * (taco_train_set_exact_gemm, _set_exact_wgrad, _set_wgrad_planes, _set_deterministic, _set_bptt_engine) and the batching region for small weight
+ * gradients that the backward opens.  BatchNorm uses batch statistics; the moving statistics in d_params are not touched.
+ * which: 0 = encoder CBHG (in_dim = last encoder prenet width, rnn = enc_rnn_size), 1 = post CBHG (in_dim = num_mels, rnn = post_rnn_size).
+ * d_in [B*T, in_dim], d_dout [B*T, 2*rnn] -> d_out [B*T, 2*rnn], d_din [B*T, in_dim].  Nullable: d_lengths [B]; d_h0 [B, 2*rnn] (initial states)
+ * with d_dh0; d_before [B, in_dim] (the vector added before the highway layers) with d_dbefore; a gradient output without its input is TACO_ERR_ARG.
+ * d_params: the trainer's flat parameters, as of the last taco_train_refresh.  The parameter gradients of the scope are ADDED into d_grads at their
+ * taco_train_param_offset -- zero-fill the scope first, as the step zero-fills the whole buffer; no other element of d_grads is written.
+ * d_ws: at least taco_train_debug_cbhg_workspace_bytes(t, which, B, T) bytes (ask again after a switch that changes the step's workspace),
+ * 16-byte aligned; else TACO_ERR_STATE / TACO_ERR_ARG, as the step answers.
+ * paths (nullable) receives which branch each dispatch of THIS call took, OR-ed in at the dispatch site where the kernel is launched:
+ *   bit  0 / 1   conv bank forward: BatchNorm + max-pool fused (k_bn_pool_bank_v4) / k_bn_apply per width + k_maxpool_fwd
+ *   bit  2 / 3   max-pool backward: BatchNorm-fused (k_maxpool_bwd_bn_v4) / k_maxpool_bwd
+ *   bit  4 / 5   BatchNorm apply of a projection: k_bn_apply_v4 / k_bn_apply
+ *   bit  6 / 7   BatchNorm backward of one layer: k_bn_bwd_v4 / k_bn_bwd (projections; bank widths too when bit 9 is set)
+ *   bit  8 / 9   dz of the conv bank: all widths in one launch (k_bn_bwd_bank_v4) / one BatchNorm backward per width
+ *   bit 10 / 11  kernel gradients of the conv bank: one product from pre-split planes / one weight gradient per width
+ *   bit 12 / 13  highway backward: k_highway_bwd_v4 / k_highway_bwd
+ *   bits 16-19   forward scan launched: 1 k_bigru_rows, 2 k_bigru_res, 3 k_bigru_quad, 5 k_bigru_duo, 6 k_bigru_oct (TAPE instantiations)
+ *   bits 20-23   backward scan launched: 1 k_bigru_rows_bwd, 2 k_bigru_resb, 3 k_bigru_duo_bwd, 4 k_bigru_oct_bwd
+ * Both bits of a pair are set when layers of one call went different ways (e.g. 18- and 16-wide projections).  Bit 13 cannot be reached through a
+ * trainer: taco_train_create accepts only rnn sizes that are multiples of 4, and the tape is carved in 256-byte steps. */
+size_t taco_train_debug_cbhg_workspace_bytes(const taco_train* t, int which, int B, int T);
+int taco_train_debug_cbhg(taco_train* t, void* hip_stream, int which, float* d_params, float* d_grads, const float* d_in, const int32_t* d_lengths,
+                          const float* d_h0, const float* d_before, const float* d_dout, int B, int T, float* d_out, float* d_din, float* d_dh0,
+                          float* d_dbefore, void* d_ws, size_t ws_bytes, uint32_t* paths);
+
 /* Test hook: which kernel the training step gives a weight gradient, and how it slices the rows -- wgrad_plan / wgrad_bank_plan of
  * csrc/taco_train.h, pure host functions: no handle, no device.  Inputs: the trainer's switches (wgrad_bf3: 0 = exact-fp32 weight
  * gradients are on; wgrad_planes: the mode of taco_train_set_wgrad_planes), whether the deterministic scratch exists and its floats, the

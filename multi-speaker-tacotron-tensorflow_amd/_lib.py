@@ -196,6 +196,8 @@ PROTOTYPES = {
     "taco_train_set_exact_gemm": (_I, [_P, _I]),
     "taco_debug_wgrad_plan": (_I, [_I, _I, _I, C.c_longlong, C.c_longlong, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, C.POINTER(_I)]),
     "taco_train_debug_bigru": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _P, _P, _P, _P, _P, _P, _S]),
+    "taco_train_debug_cbhg_workspace_bytes": (_S, [_P, _I, _I, _I]),
+    "taco_train_debug_cbhg": (_I, [_P, _P, _I, _P, _P, _P, _P, _P, _P, _P, _I, _I, _P, _P, _P, _P, _P, _S, _P]),
     "taco_train_workspace_bytes": (_S, [_P, _I, _I, _I]),
     "taco_train_forward_backward": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _P, _I, _P, _S]),
     "taco_debug_force_gemm_config": (_I, [_P, _I]),

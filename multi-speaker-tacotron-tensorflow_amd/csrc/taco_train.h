@@ -206,8 +206,23 @@ struct StepState {
   float* det = nullptr; size_t det_cap = 0;
   uint4* wps = nullptr; size_t wps_cap = 0;      // bf16 planes of the weight gradients' operands (taco_wgrad_planes.h); null: that path is off
   int planes_problems = 0;                       // weight gradients of this step that were computed from pre-split planes so far
+  unsigned paths = 0;                            // CBHG_PATH_* bits: which branch each dispatch of a CBHG took, OR-ed in where it is taken (taco_train_debug_cbhg)
   WgBatch wgb;
 };
+// The word of taco_train_debug_cbhg (include/taco_debug.h documents the layout): one bit per form of every two-way dispatch of
+// cbhg_forward_train / cbhg_backward, and the scan kernels that were launched.  Set at the launch, never recomputed from the predicates.
+enum : unsigned {
+  CBHG_PATH_BANK_FWD_FUSED = 1u << 0, CBHG_PATH_BANK_FWD_PLAIN = 1u << 1,      // k_bn_pool_bank_v4 | k_bn_apply per width + k_maxpool_fwd
+  CBHG_PATH_POOL_BWD_FUSED = 1u << 2, CBHG_PATH_POOL_BWD_PLAIN = 1u << 3,      // k_maxpool_bwd_bn_v4 | k_maxpool_bwd
+  CBHG_PATH_PROJ_BN_V4 = 1u << 4, CBHG_PATH_PROJ_BN_PLAIN = 1u << 5,           // k_bn_apply_v4 | k_bn_apply on a projection
+  CBHG_PATH_BN_BWD_V4 = 1u << 6, CBHG_PATH_BN_BWD_PLAIN = 1u << 7,             // k_bn_bwd_v4 | k_bn_bwd (projections, and bank widths without the one-launch dz)
+  CBHG_PATH_BANK_DZ_ONE = 1u << 8, CBHG_PATH_BANK_DZ_EACH = 1u << 9,           // k_bn_bwd_bank_v4 | dz per width
+  CBHG_PATH_BANK_WG_PLANES = 1u << 10, CBHG_PATH_BANK_WG_EACH = 1u << 11,      // run_wgrad_bank_planes | run_wgrad per width
+  CBHG_PATH_HW_BWD_V4 = 1u << 12, CBHG_PATH_HW_BWD_PLAIN = 1u << 13,           // k_highway_bwd_v4 | k_highway_bwd
+  CBHG_PATH_SCAN_FWD_SHIFT = 16, CBHG_PATH_SCAN_BWD_SHIFT = 20                 // four bits each: ScanKernel of the forward launch; CBHG_SCAN_BWD_* of the backward one
+};
+enum { CBHG_SCAN_BWD_ROWS = 1, CBHG_SCAN_BWD_RESB = 2, CBHG_SCAN_BWD_DUO = 3, CBHG_SCAN_BWD_OCT = 4 };
+
 struct TrainCtx {
   const taco_train* t; hipStream_t st; float* P; float* G;    // flat parameters (moving statistics are updated in place) and gradients
   bool update_moving;   // BatchNorm moving averages follow this pass (UPDATE_OPS run only as a dependency of `optimize`, tacotron.py:334)
@@ -536,6 +551,13 @@ struct TrainWs {
   float* detscr;                                                         // deterministic reductions: per-slice partial sums
   uint4* wpscr; size_t wps_uint4;                                        // bf16 planes of the weight gradients' operands (taco_wgrad_planes.h)
 };
+// plane scratch of a step whose longest row set has `rows` rows, in uint4 (1: the planes path is off)
+static size_t wps_scratch_uint4(const taco_train* t, size_t rows) {
+  const taco_hparams& hp = t->sm->hp;
+  const size_t rp = (size_t)cdiv((int)rows, 64) * 64;
+  const size_t cols = (size_t)std::max(hp.enc_bank_size * hp.enc_bank_channels, hp.post_bank_size * hp.post_bank_channels) + WP_SCRATCH_COLS;
+  return t->wgrad_planes ? rp / 16 * (cols / 32) * 3 * 64 : 1;
+}
 static void carve_train(Carver& cv, const taco_train* t, int B, int T_in, int n, TrainWs& w) {
   const taco_model* m = t->sm;
   const taco_hparams& hp = m->hp;
@@ -558,10 +580,8 @@ static void carve_train(Carver& cv, const taco_train* t, int B, int T_in, int n,
   const size_t nrv = is_simple(m) ? (size_t)B * hp.num_freq : 1;
   w.linrv = cv.f(nrv); w.dlin_sum = cv.f(nrv);
   w.detscr = cv.f(t->deterministic ? DET_SCRATCH_FLOATS : 1);
-  { const size_t rows = (size_t)cdiv((int)std::max(Me, Mp), 64) * 64;
-    const size_t cols = (size_t)std::max(hp.enc_bank_size * hp.enc_bank_channels, hp.post_bank_size * hp.post_bank_channels) + WP_SCRATCH_COLS;
-    w.wps_uint4 = t->wgrad_planes ? rows / 16 * (cols / 32) * 3 * 64 : 1;
-    w.wpscr = (uint4*)cv.raw(w.wps_uint4 * sizeof(uint4)); }
+  w.wps_uint4 = wps_scratch_uint4(t, std::max(Me, Mp));
+  w.wpscr = (uint4*)cv.raw(w.wps_uint4 * sizeof(uint4));
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -628,7 +648,9 @@ static int cbhg_forward_train(const TrainCtx& x, const Cbhg& c, const CbhgT& ct,
       BnBank nb; memset(&nb, 0, sizeof nb); nb.Cw = c.C;
       for (int k = 1; k <= c.K; ++k) { nb.gamma[k - 1] = x.p(names[k - 1] + "/gamma"); nb.beta[k - 1] = x.p(names[k - 1] + "/beta"); }
       hipLaunchKernelGGL(k_bn_pool_bank_v4, EWGRID((size_t)M * KC / 4), 0, st, (const float*)w.bank_a, KC, (const float*)w.bank_mu, (const float*)w.bank_rs, nb, w.pool, KC, M, T, KC, c.maxpool);
+      x.s->paths |= CBHG_PATH_BANK_FWD_FUSED;
     } else {
+    x.s->paths |= CBHG_PATH_BANK_FWD_PLAIN;
     for (int k = 1; k <= c.K; ++k) {
       const int c0 = (k - 1) * c.C;
       hipLaunchKernelGGL(k_bn_apply, EWGRID((size_t)M * c.C), 0, st, w.bank_a + c0, KC, w.bank_mu + c0, w.bank_rs + c0,
@@ -644,9 +666,13 @@ static int cbhg_forward_train(const TrainCtx& x, const Cbhg& c, const CbhgT& ct,
     GemmCall p; p.x = cur; p.ldx = curd; p.M = M; p.T = T; p.act = (i + 1 == c.nproj) ? ACT_NONE : ACT_RELU; p.out = w.pa[i]; p.ldo = N;
     TRY(run_gemm(m, st, &ct.proj_f[i], 1, false, p));
     TRY(bn_stats(x, w.pa[i], N, M, N, w.pmu[i], w.prs[i], w.stat, &n, &N, 1));
-    if ((N & 3) == 0 && al16h(w.pa[i]) && al16h(w.py[i]))
+    if ((N & 3) == 0 && al16h(w.pa[i]) && al16h(w.py[i])) {
+      x.s->paths |= CBHG_PATH_PROJ_BN_V4;
       hipLaunchKernelGGL(k_bn_apply_v4, EWGRID((size_t)M * N / 4), 0, st, (const float*)w.pa[i], N, (const float*)w.pmu[i], (const float*)w.prs[i], (const float*)x.p(n + "/gamma"), (const float*)x.p(n + "/beta"), w.py[i], N, M, N);
-    else hipLaunchKernelGGL(k_bn_apply, EWGRID((size_t)M * N), 0, st, w.pa[i], N, w.pmu[i], w.prs[i], x.p(n + "/gamma"), x.p(n + "/beta"), w.py[i], N, M, N);
+    } else {
+      x.s->paths |= CBHG_PATH_PROJ_BN_PLAIN;
+      hipLaunchKernelGGL(k_bn_apply, EWGRID((size_t)M * N), 0, st, w.pa[i], N, w.pmu[i], w.prs[i], x.p(n + "/gamma"), x.p(n + "/beta"), w.py[i], N, M, N);
+    }
     cur = w.py[i]; curd = N;
   }
   // residual (modules.py:62-69)
@@ -665,6 +691,7 @@ static int cbhg_forward_train(const TrainCtx& x, const Cbhg& c, const CbhgT& ct,
     TRY(run_gemm(m, st, &c.xproj, 1, false, xp)); }
   if (lengths) HIPCHK(zero_async(w.gsave, (size_t)M * 6 * H * sizeof(float), st));      // (without lengths -- the post-net -- every step of every row is active and written)
   const ScanPlan sp = scan_plan(m, c, B, T, true);
+  if (sp.kernel == SCAN_K_OCT || sp.kernel == SCAN_K_DUO) x.s->paths |= (unsigned)sp.kernel << CBHG_PATH_SCAN_FWD_SHIFT;
   if (sp.kernel == SCAN_K_OCT)     // the whole-chip scans of inference with the gate tape (k_bigru_oct<UPW, true> / k_bigru_duo<RG, true>)
     return oct_launch(m, st, c, sp.upw, B, T, w.xproj, lengths, init_state, w.out, w.gsave, w.gxbuf, w.gxctl);
   if (sp.kernel == SCAN_K_DUO)
@@ -674,8 +701,10 @@ static int cbhg_forward_train(const TrainCtx& x, const Cbhg& c, const CbhgT& ct,
     a.xproj = w.xproj; a.g2_0 = (const float2*)AP(m, c.res_g2[0]); a.g2_1 = (const float2*)AP(m, c.res_g2[1]);
     a.c1_0 = AP(m, c.raw_ch[0]); a.c1_1 = AP(m, c.raw_ch[1]); a.lengths = lengths; a.out = w.out; a.gsave = w.gsave; a.B = B; a.T = T;
     a.h0 = init_state;
+    const bool quad = H != 256 && sp.kernel == SCAN_K_QUAD && x.t->resident_bwd_scan;      // (the A/B engine keeps k_bigru_res)
+    x.s->paths |= (unsigned)(quad ? SCAN_K_QUAD : SCAN_K_RES) << CBHG_PATH_SCAN_FWD_SHIFT;
     if (H == 256) hipLaunchKernelGGL((k_bigru_res<256, 64, 24, 1, true>), dim3(2 * B), dim3(512), bigru_res_lds(256, 24, 1), st, a);
-    else if (sp.kernel == SCAN_K_QUAD && x.t->resident_bwd_scan) hipLaunchKernelGGL(k_bigru_quad<true>, dim3(2 * B), dim3(512), 0, st, a);      // (the A/B engine keeps k_bigru_res)
+    else if (quad) hipLaunchKernelGGL(k_bigru_quad<true>, dim3(2 * B), dim3(512), 0, st, a);
     else hipLaunchKernelGGL((k_bigru_res<128, 32, 0, 1, true>), dim3(2 * B), dim3(512), bigru_res_lds(128, 0, 1), st, a);
   } else {
     int R = 0; size_t lds = 0;
@@ -683,6 +712,7 @@ static int cbhg_forward_train(const TrainCtx& x, const Cbhg& c, const CbhgT& ct,
     BigruRArgs a; memset(&a, 0, sizeof a);
     a.xproj = w.xproj; a.wg0 = AP(m, c.raw_gh[0]); a.wg1 = AP(m, c.raw_gh[1]); a.wc0 = AP(m, c.raw_ch[0]); a.wc1 = AP(m, c.raw_ch[1]);
     a.lengths = lengths; a.out = w.out; a.gsave = w.gsave; a.B = B; a.T = T; a.H = H; a.h0 = init_state;
+    x.s->paths |= (unsigned)SCAN_K_ROWS << CBHG_PATH_SCAN_FWD_SHIFT;
     if (R == 2) hipLaunchKernelGGL((k_bigru_rows<2, true>), dim3(2 * cdiv(B, R)), dim3(RP_NT), lds, st, a);
     else hipLaunchKernelGGL((k_bigru_rows<1, true>), dim3(2 * cdiv(B, R)), dim3(RP_NT), lds, st, a);
   }
@@ -718,12 +748,15 @@ static int conv_bn_backward_apply(const TrainCtx& x, const std::string& name, co
   const float* sdyxh = sync ? sync_scratch + Ctot + c0 : x.g(name + "/gamma");
   const float invM = 1.0f / ((float)M * (sync ? x.t->sync_world : 1));
   if (dz_done) {}
-  else if ((C & 3) == 0 && (lda & 3) == 0 && (lddy & 3) == 0 && (lddz & 3) == 0 && al16h(a) && al16h(dy) && al16h(dz))
+  else if ((C & 3) == 0 && (lda & 3) == 0 && (lddy & 3) == 0 && (lddz & 3) == 0 && al16h(a) && al16h(dy) && al16h(dz)) {
+    x.s->paths |= CBHG_PATH_BN_BWD_V4;
     hipLaunchKernelGGL(k_bn_bwd_v4, EWGRID((size_t)M * C / 4), 0, st, a, lda, dy, lddy, mu, rstd, (const float*)x.p(name + "/gamma"), sdy,
                        sdyxh, relu ? 1 : 0, dz, lddz, M, C, invM);
-  else
+  } else {
+  x.s->paths |= CBHG_PATH_BN_BWD_PLAIN;
   hipLaunchKernelGGL(k_bn_bwd, EWGRID((size_t)M * C), 0, st, a, lda, dy, lddy, mu, rstd, x.p(name + "/gamma"), sdy,
                      sdyxh, relu ? 1 : 0, dz, lddz, M, C, invM);
+  }
   TRY(run_colsum(x, dz, lddz, nullptr, 0, nullptr, nullptr, x.g(name + "/bias"), nullptr, M, C, 0));
   HIPCHK(hipGetLastError());
   return 0;
@@ -754,15 +787,18 @@ static int cbhg_backward(const TrainCtx& x, const Cbhg& c, const CbhgT& ct, cons
   HIPCHK(zb.run());
   if (sp.bwd == SCAN_BWD_OCT) {
     // one row per cluster of 8 CUs, as the forward scan of these shapes (k_bigru_oct_bwd)
+    x.s->paths |= (unsigned)CBHG_SCAN_BWD_OCT << CBHG_PATH_SCAN_BWD_SHIFT;
     TRY(oct_bwd_launch(m, st, c, B, T, dout, w.out, w.gsave, h0, lengths, w.dg, w.rh, dh0, w.gxbuf, w.gxctl));
   } else if (duo_bwd) {
     // both directions of RG rows per group of 32 CUs, the directions software-pipelined against each other (k_bigru_duo_bwd)
+    x.s->paths |= (unsigned)CBHG_SCAN_BWD_DUO << CBHG_PATH_SCAN_BWD_SHIFT;
     TRY(duo_bwd_launch(m, st, c, sp.rg, B, T, dout, w.out, w.gsave, h0, lengths, w.dg, w.rh, dh0, w.gxbuf, w.gxctl));
   } else if (H == 128 && x.t->resident_bwd_scan) {
     // recurrent kernels resident in registers, one workgroup per (direction, row) (k_bigru_resb): the encoder at the reference width
     BigruQArgs a; memset(&a, 0, sizeof a);
     a.dout = dout; a.out = w.out; a.gsave = w.gsave; a.gh0 = AP(m, c.raw_gh[0]); a.gh1 = AP(m, c.raw_gh[1]); a.ch0 = AP(m, c.raw_ch[0]); a.ch1 = AP(m, c.raw_ch[1]);
     a.lengths = lengths; a.dg = w.dg; a.rh = w.rh; a.h0 = h0; a.dh0 = dh0; a.B = B; a.T = T;
+    x.s->paths |= (unsigned)CBHG_SCAN_BWD_RESB << CBHG_PATH_SCAN_BWD_SHIFT;
     hipLaunchKernelGGL(k_bigru_resb<128>, dim3(2 * B), dim3(512), 0, st, a);
     HIPCHK(hipGetLastError());
   } else {
@@ -772,6 +808,7 @@ static int cbhg_backward(const TrainCtx& x, const Cbhg& c, const CbhgT& ct, cons
     BigruBArgs a; memset(&a, 0, sizeof a);
     a.dout = dout; a.out = w.out; a.gsave = w.gsave; a.wgT0 = AP(m, ct.ghT[0]); a.wgT1 = AP(m, ct.ghT[1]); a.wcT0 = AP(m, ct.chT[0]); a.wcT1 = AP(m, ct.chT[1]);
     a.lengths = lengths; a.dg = w.dg; a.rh = w.rh; a.B = B; a.T = T; a.H = H; a.h0 = h0; a.dh0 = dh0;
+    x.s->paths |= (unsigned)CBHG_SCAN_BWD_ROWS << CBHG_PATH_SCAN_BWD_SHIFT;
     if (R == 2) hipLaunchKernelGGL(k_bigru_rows_bwd<2>, dim3(2 * cdiv(B, R)), dim3(RP_NT), lds, st, a);
     else hipLaunchKernelGGL(k_bigru_rows_bwd<1>, dim3(2 * cdiv(B, R)), dim3(RP_NT), lds, st, a);
     HIPCHK(hipGetLastError());
@@ -803,9 +840,13 @@ static int cbhg_backward(const TrainCtx& x, const Cbhg& c, const CbhgT& ct, cons
   // ---- highways ----
   for (int i = c.depth - 1; i >= 0; --i) {
     const std::string n = sc + "/highway_" + std::to_string(i + 1);
-    if ((H & 3) == 0 && al16h(dcur) && al16h(w.hx[i]) && al16h(w.hH[i]) && al16h(w.hT[i]) && al16h(w.dcat) && al16h(dalt))
+    if ((H & 3) == 0 && al16h(dcur) && al16h(w.hx[i]) && al16h(w.hH[i]) && al16h(w.hT[i]) && al16h(w.dcat) && al16h(dalt)) {
+      x.s->paths |= CBHG_PATH_HW_BWD_V4;
       hipLaunchKernelGGL(k_highway_bwd_v4, EWGRID((size_t)M * H / 4), 0, st, (const float*)dcur, (const float*)w.hx[i], (const float*)w.hH[i], (const float*)w.hT[i], w.dcat, dalt, M, H);
-    else hipLaunchKernelGGL(k_highway_bwd, EWGRID((size_t)M * H), 0, st, dcur, w.hx[i], w.hH[i], w.hT[i], w.dcat, dalt, M, H);
+    } else {
+      x.s->paths |= CBHG_PATH_HW_BWD_PLAIN;
+      hipLaunchKernelGGL(k_highway_bwd, EWGRID((size_t)M * H), 0, st, dcur, w.hx[i], w.hH[i], w.hT[i], w.dcat, dalt, M, H);
+    }
     HIPCHK(hipGetLastError());
     TRY(run_wgrad(x, w.hx[i], nullptr, H, w.dcat, 2 * H, x.g(n + "/H/kernel"), H, M, 0, H, H));
     TRY(run_wgrad(x, w.hx[i], nullptr, H, w.dcat + H, 2 * H, x.g(n + "/T/kernel"), H, M, 0, H, H));
@@ -845,7 +886,11 @@ static int cbhg_backward(const TrainCtx& x, const Cbhg& c, const CbhgT& ct, cons
     BnBank nb; memset(&nb, 0, sizeof nb); nb.Cw = c.C;
     for (int k = 1; k <= c.K; ++k) { const std::string n = sc + "/conv_bank/conv1d_" + std::to_string(k); nb.gamma[k - 1] = x.p(n + "/gamma"); nb.beta[k - 1] = x.p(n + "/beta"); }
     hipLaunchKernelGGL(k_maxpool_bwd_bn_v4, EWGRID((size_t)M * KC / 4), 0, st, (const float*)w.bank_a, KC, (const float*)w.bank_mu, (const float*)w.bank_rs, nb, (const float*)w.dbig0, w.dbig1, M, T, KC, c.maxpool);
-  } else hipLaunchKernelGGL(k_maxpool_bwd, EWGRID((size_t)M * KC), 0, st, w.bank_y, w.dbig0, w.dbig1, M, T, KC, c.maxpool);
+    x.s->paths |= CBHG_PATH_POOL_BWD_FUSED;
+  } else {
+    hipLaunchKernelGGL(k_maxpool_bwd, EWGRID((size_t)M * KC), 0, st, w.bank_y, w.dbig0, w.dbig1, M, T, KC, c.maxpool);
+    x.s->paths |= CBHG_PATH_POOL_BWD_PLAIN;
+  }
   HIPCHK(hipGetLastError());
   for (size_t bi = 0; bi < c.bank.size(); ++bi) {     // the bank's BatchNorm sums of all widths, then one exchange for all of them
     const int k = c.bank[bi].kw, c0 = (k - 1) * c.C;
@@ -876,8 +921,10 @@ static int cbhg_backward(const TrainCtx& x, const Cbhg& c, const CbhgT& ct, cons
       bank_dz = true;
     }
   }
+  x.s->paths |= bank_dz ? CBHG_PATH_BANK_DZ_ONE : CBHG_PATH_BANK_DZ_EACH;
   // every width's kernel gradient from ONE conversion of dz and one product launch (taco_wgrad_planes.h), where dz of all widths is complete
   const WgPlan bank_plan = bank_dz ? wgrad_bank_plan(wg_env(x), M, T, c.in_dim, c.C, c.K, in_gather != nullptr) : WgPlan();
+  x.s->paths |= bank_plan.engine == WG_PLANES ? CBHG_PATH_BANK_WG_PLANES : CBHG_PATH_BANK_WG_EACH;
   if (bank_plan.engine == WG_PLANES) {
     float* dwk[WP_MAXW];
     for (size_t bi = 0; bi < c.bank.size(); ++bi) dwk[c.bank[bi].kw - 1] = x.g(sc + "/conv_bank/conv1d_" + std::to_string(c.bank[bi].kw) + "/kernel");

@@ -144,6 +144,59 @@ int taco_train_debug_bigru(taco_train* t, void* hip_stream, const float* xproj, 
   HIPCHK(hipGetLastError());
   return 0;
 }
+// Test hook: ONE CBHG of the trainer -- cbhg_forward_train, then cbhg_backward -- on caller data, as the step calls them: the same TrainCtx and
+// StepState (deterministic scratch, plane scratch sized as the step's), the tape of carve_cbhg_tape, the trainer's current switches; cbhg_backward opens
+// its own WgRegion, as in the step.  Moving statistics are frozen.  The scope's parameter gradients are ADDED into d_grads at their
+// taco_train_param_offset (the step zero-fills the buffer first: so does the caller, inside the scope); nothing else of d_grads is written.
+struct CbhgDebugWs { CbhgTape tape; float* detscr; uint4* wpscr; size_t wps_uint4; int* rowidx; };
+static void carve_cbhg_debug(Carver& cv, const taco_train* t, const Cbhg& c, int B, int T, CbhgDebugWs& w) {
+  carve_cbhg_tape(cv, c, B, T, w.tape);
+  w.detscr = cv.f(t->deterministic ? DET_SCRATCH_FLOATS : 1);
+  w.wps_uint4 = wps_scratch_uint4(t, (size_t)B * T);
+  w.wpscr = (uint4*)cv.raw(w.wps_uint4 * sizeof(uint4));
+  w.rowidx = cv.i(B);
+}
+size_t taco_train_debug_cbhg_workspace_bytes(const taco_train* t, int which, int B, int T) {
+  if (!t || (which != 0 && which != 1) || B <= 0 || T <= 0) return 0;
+  Carver cv(nullptr, 0);
+  CbhgDebugWs w; carve_cbhg_debug(cv, t, which ? t->sm->post : t->sm->enc, B, T, w);
+  return cv.off;
+}
+int taco_train_debug_cbhg(taco_train* t, void* hip_stream, int which, float* d_params, float* d_grads, const float* d_in, const int32_t* d_lengths,
+                          const float* d_h0, const float* d_before, const float* d_dout, int B, int T, float* d_out, float* d_din, float* d_dh0,
+                          float* d_dbefore, void* d_ws, size_t ws_bytes, uint32_t* paths) {
+  if (!t || !d_params || !d_grads || !d_in || !d_dout || !d_out || !d_din || !d_ws) return fail(TACO_ERR_ARG, "null argument");
+  if (which != 0 && which != 1) return fail(TACO_ERR_ARG, "which %d (0 encoder CBHG, 1 post CBHG)", which);
+  if ((d_dh0 && !d_h0) || (d_dbefore && !d_before)) return fail(TACO_ERR_ARG, "a gradient output without its input");
+  taco_model* m = t->sm;
+  HIPCHK(hipSetDevice(m->device));
+  TRY(check_common(m, B, T));
+  if (!al16h(d_ws)) return fail(TACO_ERR_ARG, "workspace %p is not 16-byte aligned", d_ws);
+  if ((m->bf3 || m->bf3x6 || t->dgrad_bf3) && !t->bf3_current) return fail(TACO_ERR_STATE, "taco_train_set_exact_gemm(0) needs a taco_train_refresh before the next step (the split-bf16 weight planes are stale)");
+  const Cbhg& c = which ? m->post : m->enc;
+  const CbhgT& ct = which ? t->tp.post : t->tp.enc;
+  const char* sc = which ? "post_cbhg" : "encoder_cbhg";
+  Carver cv(d_ws, ws_bytes);
+  CbhgDebugWs w; carve_cbhg_debug(cv, t, c, B, T, w);
+  if (!cv.ok()) return fail(TACO_ERR_STATE, "workspace too small: need %zu bytes, have %zu", cv.off, ws_bytes);
+  hipStream_t st = (hipStream_t)hip_stream;
+  StepState s;
+  if (t->deterministic) { s.det = w.detscr; s.det_cap = DET_SCRATCH_FLOATS; }
+  if (t->wgrad_planes) { s.wps = w.wpscr; s.wps_cap = w.wps_uint4; }
+  TrainCtx x{t, st, d_params, d_grads, false, &s};
+  const auto run = [&]() -> int {
+    TRY(cbhg_forward_train(x, c, ct, sc, d_in, B, T, d_lengths, w.tape, d_before, d_h0));
+    TRY(cbhg_backward(x, c, ct, sc, d_in, nullptr, B, T, d_lengths, d_dout, d_din, w.tape, d_h0, d_dh0, d_dbefore, w.rowidx));
+    HIPCHK(hipMemcpyAsync(d_out, w.tape.out, (size_t)B * T * 2 * c.rnn * sizeof(float), hipMemcpyDeviceToDevice, st));
+    return 0;
+  };
+  const int rc = run();
+  t->planes_problems = s.planes_problems;
+  // (k_highway_bwd, the plain form of the highway backward, cannot be reached through a trainer: taco_model_create requires rnn sizes that are
+  // multiples of 4 and the tape is carved in 256-byte steps, so CBHG_PATH_HW_BWD_PLAIN stays clear in every word this hook returns)
+  if (paths) *paths = s.paths;
+  return rc;
+}
 // Test hook: what wgrad_plan (nw = 0) / wgrad_bank_plan (nw > 0: a conv bank of widths 1 .. nw, N = channels per width) decide -- no handle, no device.
 int taco_debug_wgrad_plan(int wgrad_bf3, int wgrad_planes, int deterministic, long long det_floats, long long planes_uint4, int region_open,
                           int M, int T, int K, int N, int kw, int padl, int gather, int ygather, int nw, int* out8) {

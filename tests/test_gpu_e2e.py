@@ -825,3 +825,35 @@ def test_C5_all_8_rows_all_1000_steps_against_the_committed_oracle_outputs():
     got = al.argmax(axis=1)
     print("C5 arg-max: %d of %d steps compared (the monotonic mass of random weights leaks past the last encoder step)" % (int(sel.sum()), sel.size))
     assert sel.sum() > 1200 and np.array_equal(got[sel], g["align_argmax"][sel].astype(got.dtype))
+
+
+@pytest.mark.parametrize("name,over", [("odd_bank", dict(enc_bank_channel_size=6, post_bank_channel_size=10)),
+                                       ("odd_proj", dict(enc_prenet_sizes=[32, 18], enc_proj_sizes=[14, 18], post_proj_sizes=[22, 8]))])
+def test_layer_widths_that_are_no_multiple_of_four_run_on_the_gemm_fallback(name, over):
+    """Bank channels, projection widths and prenet widths are free (only the rnn sizes and num_mels must be multiples of 4): 6 / 10 bank
+    channels and 18- / 14- / 22-wide layers through the whole forward at the three arithmetic levels -- default (taco_debug_set_bf3 1),
+    six products (65), exact fp32 (0) -- against the oracle, with engine_plan showing that the per-layer GEMM launches are what ran
+    (no fused front, no point-wise chain at these widths).  The training block at the same widths: tests/test_gpu_cbhg_train.py."""
+    ohp = tiny_hp(**over)
+    w = O.init_weights(ohp, 1, 23)
+    B, T_in = 3, 11
+    ids, L = O.synthetic_inputs(B, T_in, 33, ragged=True)
+    ref = O.forward(w, ohp, ids, L)
+    m = build_model(ohp, w)
+    words = {1: (["conv bank and proj_1 on k_gemm_bf3,", "point-wise layers on k_gemm_bf3 "], ["X6", "k_cbhg_front<", "k_pointwise_chain<"]),
+             65: (["conv bank and proj_1 on k_gemm_bf3<..., X6>", "point-wise layers on k_gemm_bf3<..., X6>"], ["k_cbhg_front<", "k_pointwise_chain<"]),
+             0: (["exact-fp32 MFMA (k_gemm)", "conv bank and proj_1 on k_gemm,", "point-wise layers on k_gemm "], ["k_gemm_bf3", "k_cbhg_front<", "k_pointwise_chain<"])}
+    errs = {}
+    for mode in (1, 65, 0):
+        m._lib.taco_debug_set_bf3(m._handle, mode, 0)
+        m._plans.clear()
+        ff = m.engine_plan(B, T_in).split("; feed-forward: ")[1] + " "
+        present, absent = words[mode]
+        assert all(x in ff for x in present) and not any(x in ff for x in absent), (name, mode, ff)
+        got = _run(m, ids, L)
+        m.check_device_errors()
+        _check(got, ref, tol=2e-4)
+        errs[mode] = [maxabs(got[0], ref["mel"]), maxabs(got[1], ref["linear"])]
+    print("%s max |err| vs the float64 oracle (mel, linear):" % name, {k: ["%.2e" % x for x in v] for k, v in errs.items()})
+    assert errs[65][0] <= max(2 * errs[0][0], 5e-6) and errs[65][1] <= max(2 * errs[0][1], 5e-6)
+    m.close()
