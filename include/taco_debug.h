@@ -161,6 +161,17 @@ int taco_debug_pcm_energy(void* hip_stream, const int16_t* d_pcm, const int32_t*
  * first device call, on a machine without a GPU; nothing may be launched on it.  Freed by taco_gl_destroy. */
 int taco_debug_gl_create_host(const taco_audio_hparams* hp, int tf_flavor, taco_gl** out);
 
+/* Test hook: the host half of taco_model_finalize alone -- model_pack_host (csrc/taco_pack.h): every weight pack, the GemmVar table and, on a
+ * shadow model, the index lists and backward packs -- with no handle and no device.  shadow = 0: flat_weights holds every tensor of the spec in
+ * spec order, TF layout, no padding (the flat layout of taco_train_create); another n_floats is TACO_ERR_SHAPE.  shadow = 1: flat_weights must
+ * be NULL; the index-valued weights of a trainer's shadow model are filled in exactly as taco_train_create does, with a TrainPacks attached.
+ * out[0] = arena length in floats, out[1] = FNV-1a-64 of the arena bytes, out[2] = FNV-1a-64 of the GemmVar table before pointer resolution
+ * (arena offsets + 1 in the pointer fields), out[3] = FNV-1a-64 of bf3_idx followed by bf3_segs (0: both empty), out[4] = which optional packs
+ * were built: bit 0 dx_pack, 1 dx_p1o_raw, 2 dx_spkw, 3-6 dx_qpack[0..3], 7 dbx_pack, 8 / 9 gd and go packs of the encoder / post CBHG,
+ * 10 / 11 gb and gob packs, 12 / 13 fused-front packs, 14 a wtail, 15 spk_table, 16 spk_dense, 17 att_b, 18 att_sb, 19 gru1_fold,
+ * 20 res_g2p packs of either CBHG.  Everything is freed before it returns. */
+int taco_debug_pack_host(const taco_hparams* hp, int shadow, const float* flat_weights, size_t n_floats, uint64_t out[5]);
+
 #ifdef __cplusplus
 }
 #endif

@@ -195,6 +195,7 @@ PROTOTYPES = {
     "taco_train_set_bptt_engine": (_I, [_P, _I]),
     "taco_train_set_exact_gemm": (_I, [_P, _I]),
     "taco_debug_wgrad_plan": (_I, [_I, _I, _I, C.c_longlong, C.c_longlong, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, C.POINTER(_I)]),
+    "taco_debug_pack_host": (_I, [C.POINTER(TacoHParams), _I, _P, _S, C.POINTER(C.c_uint64)]),
     "taco_train_debug_bigru": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _P, _P, _P, _P, _P, _P, _S]),
     "taco_train_debug_cbhg_workspace_bytes": (_S, [_P, _I, _I, _I]),
     "taco_train_debug_cbhg": (_I, [_P, _P, _I, _P, _P, _P, _P, _P, _P, _P, _I, _I, _P, _P, _P, _P, _P, _S, _P]),

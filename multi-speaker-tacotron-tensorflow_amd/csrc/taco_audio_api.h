@@ -36,12 +36,11 @@ static int gl_create(const taco_audio_hparams* hp, int device, int flavor, bool 
   taco_model* gm = new taco_model();
   gm->device = device; gm->bf3 = 1;
   g->gm = gm;
-  int Kq, NT;
   g->fwd.kw = 1; g->fwd.cin = W; g->fwd.N = 2 * F;
-  g->fwd.wp = pack_w32(gm, fw.data(), 1, W, 2 * F, &g->fwd.cin_pad, &Kq, &NT);
+  g->fwd.wp = pack_w32(gm, fw.data(), 1, W, 2 * F, &g->fwd.cin_pad);
   pack_bf3(gm, fw.data(), 1, W, 2 * F, &g->fwd.bh, &g->fwd.bl, &g->fwd.K16, &g->fwd.cin_pad16);
   g->inv.kw = 1; g->inv.cin = 2 * F; g->inv.N = W;
-  g->inv.wp = pack_w32(gm, iv.data(), 1, 2 * F, W, &g->inv.cin_pad, &Kq, &NT);
+  g->inv.wp = pack_w32(gm, iv.data(), 1, 2 * F, W, &g->inv.cin_pad);
   pack_bf3(gm, iv.data(), 1, 2 * F, W, &g->inv.bh, &g->inv.bl, &g->inv.K16, &g->inv.cin_pad16);
   g->w2 = arena_put(gm, w2.data(), w2.size());
   add_var(gm, g->fwd, 0); add_var(gm, g->inv, 0);

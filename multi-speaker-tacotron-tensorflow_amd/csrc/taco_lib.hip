@@ -211,9 +211,9 @@ struct Cbhg {
   SkW gh[2], ch[2];
   size_t raw_gh[2] = {0, 0}, raw_ch[2] = {0, 0};   // h-rows of the GRU kernels in TF layout (row-parallel scan)
   size_t res_g2[2] = {0, 0};                       // h-rows of gates/kernel as (r, u) pairs per unit: [H][H][2] (k_bigru_res)
-  size_t gd_pack = 0, gb_pack = 0;                     // k_bigru_duo / k_bigru_duo_bwd: [2 dirs][32 members][12][512]
-  size_t gob_pack = 0;                                 // k_bigru_oct_bwd (training): [2 dirs][8 members][48][512]
-  size_t go_pack[3] = {0, 0, 0};                       // k_bigru_oct<UPW>, UPW = 1, 2, 4: [2 dirs][32 / UPW members][12 UPW][512]
+  size_t gd_pack = 0;                                  // k_bigru_duo: the UPW = 1 layout of bigru_fwd_pack (taco_pack.h) -- the same bytes as go_pack[0], both kept
+  size_t go_pack[3] = {0, 0, 0};                       // k_bigru_oct<UPW>, UPW = 1, 2, 4
+  size_t gb_pack = 0, gob_pack = 0;                    // training: k_bigru_duo_bwd (one unit per wave) / k_bigru_oct_bwd (four)
   // fused front (taco_front.h): per bank width (same order as `bank`) the produce pack [k32 step][16-channel tile][lane][8] (hi, lo)
   // and its step count; front_kind 0 = not built, 1 = <TN 2, XS 80, CINP 80, KWMAX 8> (post-net), 2 = <TN 1, XS 144, CINP 128, KWMAX 16> (encoder)
   std::vector<size_t> fr_wh, fr_wl; std::vector<int> fr_ns; int front_kind = 0;
@@ -280,14 +280,6 @@ struct taco_model {
   int skip_scans = 0;          // timing hook (taco_debug_set_skip_scans): the recurrent scans of both CBHGs are not launched
   struct TrainPacks* tp = nullptr;   // set on the shadow model of a taco_train: finalize also builds the backward packs
 };
-static int build_train_packs(taco_model* m);   // taco_train.h
-
-static size_t arena_put(taco_model* m, const float* src, size_t n) {
-  size_t off = rup_sz(m->harena.size(), 16);
-  m->harena.resize(off + rup_sz(std::max<size_t>(n, 1), 16), 0.f);
-  if (src) memcpy(&m->harena[off], src, n * sizeof(float));
-  return off + 1;
-}
 static inline const float* AP(const taco_model* m, size_t off1) { return off1 ? m->darena + (off1 - 1) : nullptr; }
 
 // ---- required tensor list (tests/test_host.py checks it against the CPU checker) ----
@@ -323,7 +315,12 @@ static void spec_cbhg(taco_model* m, const std::string& sc, int in_dim, int K, i
   spec_gru(m, sc + "/bigru/fw", rnn, rnn);
   spec_gru(m, sc + "/bigru/bw", rnn, rnn);
 }
-static const char* kSpkNames[3] = {"before_highway", "encoder_rnn_init", "attention_rnn_init"};
+// deepvoice: the vectors computed from the speaker embedding, in the order of SpkWs::vec (before_highway, the three initial states)
+static std::vector<std::string> spk_vector_names(const taco_hparams& hp) {
+  std::vector<std::string> names = {"before_highway", "encoder_rnn_init", "attention_rnn_init"};
+  for (int i = 0; i < hp.dec_layer_num; ++i) names.push_back("decoder_rnn_init_" + std::to_string(i + 1));
+  return names;
+}
 
 static int build_spec(taco_model* m) {
   const taco_hparams& hp = m->hp;
@@ -334,13 +331,12 @@ static int build_spec(taco_model* m) {
   if (multi) {
     if (spk != 1) spec_add(m, "speaker_embedding", {hp.num_speakers, spk});
     if (hp.model_type == 2) {
-      std::vector<std::pair<std::string, int>> dims = {{kSpkNames[0], hp.enc_prenet[hp.enc_prenet_n - 1]},
-                                                       {kSpkNames[1], hp.enc_rnn_size * 2},
-                                                       {kSpkNames[2], hp.attention_state_size}};
-      for (int i = 0; i < hp.dec_layer_num; ++i) dims.push_back({"decoder_rnn_init_" + std::to_string(i + 1), hp.dec_rnn_size});
-      for (auto& d : dims) {
-        if (spk == 1) spec_add(m, "spk/" + d.first + "/table", {hp.num_speakers, d.second});
-        else spec_dense(m, "spk/" + d.first, spk, d.second);
+      const int dims[3] = {hp.enc_prenet[hp.enc_prenet_n - 1], hp.enc_rnn_size * 2, hp.attention_state_size};
+      const std::vector<std::string> names = spk_vector_names(hp);
+      for (size_t i = 0; i < names.size(); ++i) {
+        const int dd = i < 3 ? dims[i] : hp.dec_rnn_size;
+        if (spk == 1) spec_add(m, "spk/" + names[i] + "/table", {hp.num_speakers, dd});
+        else spec_dense(m, "spk/" + names[i], spk, dd);
       }
     }
   }
@@ -376,514 +372,7 @@ static int build_spec(taco_model* m) {
   return 0;
 }
 
-// ---- packing ----
-// W32 pack of a [kw, cin, N] kernel (dense: kw = 1): see taco_kernels.h.
-static size_t pack_w32(taco_model* m, const float* W, int kw, int cin, int N, int* cin_pad_out, int* Kq_out, int* NT_out) {
-  const int cin_pad = rup(cin, 8), Kq = kw * cin_pad / 4, NT = cdiv(N, 32);
-  std::vector<float> p((size_t)NT * Kq * 32 * 4, 0.f);
-  for (int nt = 0; nt < NT; ++nt)
-    for (int kq = 0; kq < Kq; ++kq)
-      for (int j = 0; j < 32; ++j)
-        for (int e = 0; e < 4; ++e) {
-          const int k = 4 * kq + e, tap = k / cin_pad, c = k % cin_pad, n = 32 * nt + j;
-          if (c < cin && n < N) p[(((size_t)nt * Kq + kq) * 32 + j) * 4 + e] = W[((size_t)tap * cin + c) * N + n];
-        }
-  *cin_pad_out = cin_pad; *Kq_out = Kq; *NT_out = NT;
-  return arena_put(m, p.data(), p.size());
-}
-// split-bf16 pack of a [kw, cin, N] kernel for k_gemm_bf3: hi = bf16(w), lo = bf16(w - hi), layout in taco_kernels.h
-static unsigned short bf16_rne_host(float x) {
-  unsigned u; memcpy(&u, &x, 4);
-  return (unsigned short)((u + 0x7FFFu + ((u >> 16) & 1u)) >> 16);
-}
-static void pack_bf3(taco_model* m, const float* W, int kw, int cin, int N, size_t* hi_out, size_t* lo_out, int* K16_out, int* cp16_out, size_t* l3_out = nullptr) {
-  const int cp16 = rup(cin, 32), K16 = kw * cp16 / 16, NT = cdiv(N, 32);   // multiple of 32: k_gemm_bf3 walks k16 groups in pairs
-  std::vector<unsigned short> hi((size_t)NT * K16 * 2 * 32 * 8, 0), lo(hi.size(), 0);
-  std::vector<unsigned> idx(m->tp ? hi.size() : 0, 0u);
-  const bool want_l3 = l3_out && !m->tp && *l3_out == (size_t)1;     // inference model, caller asks (*l3_out preset to 1) for the third plane too
-  std::vector<unsigned short> l3v(want_l3 ? hi.size() : 0, 0);
-  for (int nt = 0; nt < NT; ++nt)
-    for (int k16 = 0; k16 < K16; ++k16)
-      for (int h = 0; h < 2; ++h)
-        for (int j = 0; j < 32; ++j)
-          for (int e = 0; e < 8; ++e) {
-            const int k = 16 * k16 + 8 * h + e, tap = k / cp16, c = k % cp16, n = 32 * nt + j;
-            if (c < cin && n < N) {
-              const float w = W[((size_t)tap * cin + c) * N + n];
-              const size_t oi = ((((size_t)k16 * NT + nt) * 2 + h) * 32 + j) * 8 + e;
-              if (m->tp) { idx[oi] = (unsigned)w; continue; }       // shadow model: `w` is 1 + a parameter index (k_bf3_gather splits the live value)
-              const unsigned short hb = bf16_rne_host(w);
-              unsigned hu = (unsigned)hb << 16; float hf; memcpy(&hf, &hu, 4);
-              const size_t o = ((((size_t)k16 * NT + nt) * 2 + h) * 32 + j) * 8 + e;   // k16-major: see the layout note in taco_kernels.h
-              hi[o] = hb; lo[o] = bf16_rne_host(w - hf);
-              if (want_l3) { unsigned lu = (unsigned)lo[o] << 16; float lf; memcpy(&lf, &lu, 4); l3v[o] = bf16_rne_host(w - hf - lf); }
-            }
-          }
-  auto put = [&](const std::vector<unsigned short>& v) {
-    std::vector<float> f((v.size() + 1) / 2, 0.f);
-    memcpy(f.data(), v.data(), v.size() * sizeof(unsigned short));
-    return arena_put(m, f.data(), f.size());
-  };
-  *hi_out = put(hi); *lo_out = put(lo); *K16_out = K16; *cp16_out = cp16;
-  if (want_l3) *l3_out = put(l3v);
-  else if (l3_out && !m->tp) *l3_out = 0;
-  if (m->tp) {
-    // third plane (zeros here: k_bf3_gather fills all three from the live parameters): the operand of the six-product instantiation
-    const size_t l3 = put(std::vector<unsigned short>(hi.size(), 0));
-    if (l3_out) *l3_out = l3;
-    m->bf3_segs.push_back(Bf3Seg{(unsigned)m->bf3_idx.size(), (unsigned)idx.size(), (unsigned long long)(*hi_out - 1), (unsigned long long)(*lo_out - 1), (unsigned long long)(l3 - 1)});
-    m->bf3_idx.insert(m->bf3_idx.end(), idx.begin(), idx.end());
-  }
-}
-
-// W16 pack of rows [r0, r0+K) and columns [c0, c0+N) of a row-major [*, ldw] matrix.
-static SkW pack_w16(taco_model* m, const float* W, int ldw, int r0, int K, int c0, int N, const float* bias) {
-  SkW s;
-  s.K = K; s.N = N;
-  const int Kpad = rup(K, 16), NT = cdiv(N, 16);
-  s.Kq = Kpad / 4;
-  std::vector<float> p((size_t)NT * s.Kq * 16 * 4, 0.f);
-  for (int nt = 0; nt < NT; ++nt)
-    for (int kq = 0; kq < s.Kq; ++kq)
-      for (int j = 0; j < 16; ++j)
-        for (int e = 0; e < 4; ++e) {
-          const int k = 4 * kq + e, n = 16 * nt + j;
-          if (k < K && n < N) p[(((size_t)nt * s.Kq + kq) * 16 + j) * 4 + e] = W[(size_t)(r0 + k) * ldw + c0 + n];
-        }
-  s.wp = arena_put(m, p.data(), p.size());
-  if (bias) s.bias = arena_put(m, bias + c0, N);
-  return s;
-}
-
-static const HostTensor& T_(taco_model* m, const std::string& n) { return m->raw[n]; }
-
-static ConvL make_conv(taco_model* m, const std::string& name, bool bn, bool has_bias = true, bool bf3 = false, bool x6 = false) {
-  const HostTensor& k = T_(m, name + "/kernel");
-  ConvL L;
-  if (k.shape.size() == 3) { L.kw = (int)k.shape[0]; L.cin = (int)k.shape[1]; L.N = (int)k.shape[2]; }
-  else { L.kw = 1; L.cin = (int)k.shape[0]; L.N = (int)k.shape[1]; }
-  int Kq, NT;
-  L.wp = pack_w32(m, k.data.data(), L.kw, L.cin, L.N, &L.cin_pad, &Kq, &NT);
-  if (bf3 && !m->tp) L.bl3 = 1;              // (preset 1 = "build the third plane in an inference model too": every layer can run the six-product instantiation, taco_debug_set_bf3 bit 64)
-  if (x6) L.x6 = true;                       // ... and this one does by default
-  if (bf3) pack_bf3(m, k.data.data(), L.kw, L.cin, L.N, &L.bh, &L.bl, &L.K16, &L.cin_pad16, &L.bl3);
-  if (bf3 && L.kw == 1 && L.N >= 512 && L.N % 32 > 0 && L.N % 32 <= 4 && (L.cin == 256 || L.cin == 512)) {
-    L.ntail = L.N % 32;
-    std::vector<float> wt((size_t)L.ntail * L.cin);
-    for (int t = 0; t < L.ntail; ++t)
-      for (int kk = 0; kk < L.cin; ++kk) wt[(size_t)t * L.cin + kk] = k.data[(size_t)kk * L.N + (L.N - L.ntail + t)];
-    L.wtail = arena_put(m, wt.data(), wt.size());
-  }
-  if (has_bias) L.bias = arena_put(m, T_(m, name + "/bias").data.data(), L.N);
-  if (bn) {  // BatchNorm inference folded to y*scale + shift (A.2; epsilon 1e-3 = tf.layers default)
-    const auto& g = T_(m, name + "/gamma").data; const auto& b = T_(m, name + "/beta").data;
-    const auto& mu = T_(m, name + "/moving_mean").data; const auto& var = T_(m, name + "/moving_variance").data;
-    std::vector<float> sc(L.N), sh(L.N);
-    for (int i = 0; i < L.N; ++i) {
-      const double s = (double)g[i] / std::sqrt((double)var[i] + 1e-3);
-      sc[i] = (float)s; sh[i] = (float)((double)b[i] - (double)mu[i] * s);
-    }
-    L.bns = arena_put(m, sc.data(), L.N); L.bnb = arena_put(m, sh.data(), L.N);
-  }
-  return L;
-}
-
-static GruDec make_grudec(taco_model* m, const std::string& name, int I, int H) {
-  GruDec g; g.I = I; g.H = H;
-  const auto& gk = T_(m, name + "/gates/kernel").data; const auto& gb = T_(m, name + "/gates/bias").data;
-  const auto& ck = T_(m, name + "/candidate/kernel").data; const auto& cb = T_(m, name + "/candidate/bias").data;
-  // one [I+H, 3H] matrix: columns [0,2H) = gates/kernel, columns [2H,3H) = candidate/kernel rows of x
-  // (rows of h zero: the candidate's h part needs r first and runs in the second launch)
-  std::vector<float> W((size_t)(I + H) * 3 * H, 0.f), b(3 * H, 0.f);
-  for (int i = 0; i < I + H; ++i) {
-    for (int j = 0; j < 2 * H; ++j) W[(size_t)i * 3 * H + j] = gk[(size_t)i * 2 * H + j];
-    if (i < I) for (int j = 0; j < H; ++j) W[(size_t)i * 3 * H + 2 * H + j] = ck[(size_t)i * H + j];
-  }
-  for (int j = 0; j < 2 * H; ++j) b[j] = gb[j];
-  g.gx = pack_w16(m, W.data(), 3 * H, 0, I + H, 0, 3 * H, b.data());
-  g.ch = pack_w16(m, ck.data(), H, I, H, 0, H, cb.data());    // h rows of candidate/kernel (+ candidate bias)
-  return g;
-}
-
-static bool is_simple(const taco_model* m);
-
-// ---- persistent XCD-local decoder: per-thread weight packs (mirror of the pass mapping in taco_decoder_xcd.h) ----
-// The persistent decoder exists for 256-wide cells and memory, two decoder layers, and the attention widths / prenet depths of the presets of
-// hparams.py:71-117: attention_size 128 / 256 / 512, dec_prenet_sizes [256, 128] or [256, 128, 64].
-static int dx_prenet_depth(const taco_model* m) {
-  const taco_hparams& hp = m->hp;
-  if (hp.dec_prenet_n == 2 && hp.dec_prenet[0] == DX_W && hp.dec_prenet[1] == DX_P2) return 2;
-  if (hp.dec_prenet_n == 3 && hp.dec_prenet[0] == DX_W && hp.dec_prenet[1] == DX_P2 && hp.dec_prenet[2] == DX_P3) return 3;
-  return 0;
-}
-static bool dx_reference_widths(const taco_model* m) { return m->hp.attention_size == DX_W && dx_prenet_depth(m) == 2; }
-static bool dx_widths_ok(const taco_model* m) {
-  const taco_hparams& hp = m->hp;
-  const bool aw = hp.attention_size == 128 || hp.attention_size == 256 || hp.attention_size == 512;
-  return hp.attention_state_size == DX_W && hp.dec_rnn_size == DX_W && aw && 2 * hp.enc_rnn_size == DX_W && dx_prenet_depth(m) != 0 &&
-         hp.dec_layer_num == 2 && hp.num_mels * hp.reduction_factor <= 16 * DX_GROUP &&
-         (dx_reference_widths(m) || !m->tp);       // the training forward / BPTT kernels: reference widths only
-}
-// one weight column of a pass: registers reg0 .. reg0+kw-1 of every thread = W[row0 + kw*lane + e][col(wave)]  (col < 0: none)
-template <class ColFn>
-static void dx_fill_col(std::vector<float>& pack, int nreg, int member, int reg0, int kw, const float* W, int ldw, int row0, ColFn col) {
-  for (int tid = 0; tid < DX_NT; ++tid) {
-    const int wave = tid >> 6, lane = tid & 63, n = col(wave);
-    if (n < 0) continue;
-    for (int e = 0; e < kw; ++e)
-      pack[((size_t)member * nreg + reg0 + e) * DX_NT + tid] = W[(size_t)(row0 + kw * lane + e) * ldw + n];
-  }
-}
-// Wc/bc: composite prenet layer 1 of the next step ([o | ctx] rows); Wf/bf: GRU 1 with the concat projection folded in
-// ([h_att | ctx | h1] rows x [r | u | candidate-x | o0] columns), both formed in double by taco_model_finalize
-static int dx_build_pack(taco_model* m, const std::vector<float>& Wc, const std::vector<float>& bc, const std::vector<float>& Wf,
-                         const std::vector<float>& bf) {
-  if (!dx_widths_ok(m)) return 0;
-  const taco_hparams& hp = m->hp;
-  const int H = DX_W, rM = hp.num_mels * hp.reduction_factor, NCF = cdiv(rM, DX_GROUP);
-  const int S = is_simple(m) ? hp.speaker_embedding_size : 0;     // 'simple': S speaker rows behind the prenet output / behind [h_att | ctx]
-  const int PD = dx_prenet_depth(m), AW = hp.attention_size;
-  const int IA = (PD == 3 ? DX_P3 : DX_P2) + S, Z = 2 * H + S;    // first h row of the attention GRU kernels / of the folded GRU 1 matrix
-  std::vector<float> pack((size_t)DX_GROUP * DX_NREG * DX_NT, 0.f);
-  const auto& W2 = T_(m, "decoder/prenet/dense_2/kernel").data;
-  const auto& agk = T_(m, "decoder/attention_gru/gates/kernel").data; const auto& ack = T_(m, "decoder/attention_gru/candidate/kernel").data;
-  const auto& wq = T_(m, "attention/query_layer/kernel").data;
-  const auto& c1k = T_(m, "decoder/gru_1/candidate/kernel").data;
-  const auto& g2k = T_(m, "decoder/gru_2/gates/kernel").data; const auto& c2k = T_(m, "decoder/gru_2/candidate/kernel").data;
-  const auto& fk = T_(m, "decoder/frame_projection/kernel").data;
-  for (int mem = 0; mem < DX_GROUP; ++mem) {
-    auto c8 = [&](int w) { return mem * 8 + w; };
-    auto cu = [&](int w) { return H + mem * 8 + w; };                       // update-gate column (A.6: gates kernel = r | u)
-    auto c4 = [&](int w) { return w < 4 ? mem * 4 + w : -1; };
-    auto f0 = [&](int w) { const int n = mem * NCF + w; return (w < NCF && n < rM) ? n : -1; };
-    auto f1 = [&](int w) { const int n = mem * NCF + w + 8; return (w + 8 < NCF && n < rM) ? n : -1; };
-    auto put = [&](int reg0, int kw, const float* W, int ldw, int row0, auto col) { dx_fill_col(pack, DX_NREG, mem, reg0, kw, W, ldw, row0, col); };
-    put(DXR_P2, 4, W2.data(), DX_P2, 0, c4);
-    put(DXR_AGH, 4, agk.data(), 2 * H, IA, c8); put(DXR_AGH + 4, 4, agk.data(), 2 * H, IA, cu);                  // h rows
-    if (PD == 3) {      // 64 input rows, one per lane: r, u, candidate-x in one register each; behind them prenet layer 3 (p2 -> column 2m + w, waves 0-1)
-      put(DXR_AGX, 1, agk.data(), 2 * H, 0, c8); put(DXR_AGX + 1, 1, agk.data(), 2 * H, 0, cu); put(DXR_AGX + 2, 1, ack.data(), H, 0, c8);
-      put(DXR_AGX + 3, 2, T_(m, "decoder/prenet/dense_3/kernel").data.data(), DX_P3, 0, [&](int w) { return w < 2 ? mem * 2 + w : -1; });
-    } else {
-      put(DXR_AGX, 2, agk.data(), 2 * H, 0, c8); put(DXR_AGX + 2, 2, agk.data(), 2 * H, 0, cu); put(DXR_AGX + 4, 2, ack.data(), H, 0, c8);
-    }
-    put(DXR_AC, 4, ack.data(), H, IA, c8);
-    auto fx = [&](int w) { return 2 * H + mem * 8 + w; };
-    auto fo = [&](int w) { return 3 * H + mem * 8 + w; };
-    put(DXR_G1H, 4, Wf.data(), 4 * H, Z, c8); put(DXR_G1H + 4, 4, Wf.data(), 4 * H, Z, cu);                        // h1 rows
-    put(DXR_G1A, 4, Wf.data(), 4 * H, 0, c8); put(DXR_G1A + 4, 4, Wf.data(), 4 * H, 0, cu);                        // h_att rows
-    put(DXR_G1A + 8, 4, Wf.data(), 4 * H, 0, fx); put(DXR_G1A + 12, 4, Wf.data(), 4 * H, 0, fo);
-    put(DXR_G1B, 4, Wf.data(), 4 * H, H, c8); put(DXR_G1B + 4, 4, Wf.data(), 4 * H, H, cu);                        // context rows
-    put(DXR_G1B + 8, 4, Wf.data(), 4 * H, H, fx); put(DXR_G1B + 12, 4, Wf.data(), 4 * H, H, fo);
-    put(DXR_G1C, 4, c1k.data(), H, H, c8);
-    put(DXR_G2H, 4, g2k.data(), 2 * H, H, c8); put(DXR_G2H + 4, 4, g2k.data(), 2 * H, H, cu);
-    put(DXR_G2X, 4, g2k.data(), 2 * H, 0, c8); put(DXR_G2X + 4, 4, g2k.data(), 2 * H, 0, cu); put(DXR_G2X + 8, 4, c2k.data(), H, 0, c8);
-    put(DXR_G2C, 4, c2k.data(), H, H, c8);
-    put(DXR_P1C, 4, Wc.data(), DX_W, H, c8);                                                                        // context rows of [o | ctx]
-    put(DXR_P1O, 4, Wc.data(), DX_W, 0, c8);
-    put(DXR_F, 4, fk.data(), rM, 0, f0); put(DXR_F + 4, 4, fk.data(), rM, 0, f1);
-  }
-  m->dx_pack = arena_put(m, pack.data(), pack.size());
-  if (!m->tp && dx_reference_widths(m)) {
-    // teacher-forced decoding on an inference model (taco_decoder_forward with teacher frames): the TAPE instantiation reads the teacher's
-    // frame with the RAW frame rows of prenet layer 1 where this pack holds the frame-projection composite -- four registers per thread
-    const auto& W1 = T_(m, "decoder/prenet/dense_1/kernel").data;
-    std::vector<float> raw((size_t)DX_W * DX_W, 0.f), alt((size_t)DX_GROUP * 4 * DX_NT, 0.f);
-    for (int k = 0; k < hp.num_mels; ++k) for (int q = 0; q < DX_W; ++q) raw[(size_t)k * DX_W + q] = W1[(size_t)k * DX_W + q];
-    for (int mem = 0; mem < DX_GROUP; ++mem) dx_fill_col(alt, 4, mem, 0, 4, raw.data(), DX_W, 0, [&](int w) { return mem * 8 + w; });
-    m->dx_p1o_raw = arena_put(m, alt.data(), alt.size());
-  }
-  if (S) {   // speaker rows: [k][slot][n], slots in DXRB_* order
-    std::vector<float> sw((size_t)S * DXRB_N * H);
-    for (int k = 0; k < S; ++k)
-      for (int n = 0; n < H; ++n) {
-        float* o = &sw[(size_t)k * DXRB_N * H + n];
-        const int px = IA - S;                                      // prenet output rows in front of the speaker rows
-        o[DXRB_AR * H] = agk[(size_t)(px + k) * 2 * H + n]; o[DXRB_AU * H] = agk[(size_t)(px + k) * 2 * H + H + n];
-        o[DXRB_AX * H] = ack[(size_t)(px + k) * H + n];
-        const float* wf = &Wf[(size_t)(2 * H + k) * 4 * H];
-        o[DXRB_G1R * H] = wf[n]; o[DXRB_G1U * H] = wf[H + n]; o[DXRB_G1X * H] = wf[2 * H + n]; o[DXRB_O0 * H] = wf[3 * H + n];
-      }
-    m->dx_spkw = arena_put(m, sw.data(), sw.size());
-  }
-  // query layer: slot s of a row (s = member % Pr) scores channel block s % Pc and holds columns (s % Pc)*DS + w*QC + i of it; one pack
-  // per rows-per-group
-  for (int q = 0; q < 4; ++q) {
-    const int RG = 1 << q, Pr = DX_GROUP / RG, Pc = dx_score_blocks(RG), DS = AW / Pc, QC = DS / 8, QR = dx_q_regs(RG, AW);
-    if (DS < 8 || DS > 64) continue;                                // (no instantiation: attention_size 128 below / 512 above 4 rows per group)
-    std::vector<float> qp((size_t)DX_GROUP * QR * DX_NT, 0.f);
-    for (int mem = 0; mem < DX_GROUP; ++mem)
-      for (int i = 0; i < QC; ++i) {
-        const int cb = (mem % Pr) % Pc;
-        dx_fill_col(qp, QR, mem, 4 * i, 4, wq.data(), AW, 0, [&](int w) { return cb * DS + w * QC + i; });
-      }
-    m->dx_qpack[q] = arena_put(m, qp.data(), qp.size());
-  }
-  auto putv = [&](const std::vector<float>& v) { return arena_put(m, v.data(), v.size()); };
-  m->dx_b_p1_0 = putv(T_(m, "decoder/prenet/dense_1/bias").data);
-  m->dx_b_p1c = putv(bc);
-  m->dx_b_p2 = putv(T_(m, "decoder/prenet/dense_2/bias").data);
-  if (PD == 3) m->dx_b_p3 = putv(T_(m, "decoder/prenet/dense_3/bias").data);
-  m->dx_b_ag = putv(T_(m, "decoder/attention_gru/gates/bias").data);
-  m->dx_b_ac = putv(T_(m, "decoder/attention_gru/candidate/bias").data);
-  m->dx_b_g1f = putv(bf);
-  m->dx_b_g1c = putv(T_(m, "decoder/gru_1/candidate/bias").data);
-  m->dx_b_g2g = putv(T_(m, "decoder/gru_2/gates/bias").data);
-  m->dx_b_g2c = putv(T_(m, "decoder/gru_2/candidate/bias").data);
-  m->dx_b_f = putv(T_(m, "decoder/frame_projection/bias").data);
-  return 0;
-}
-
-// The persistent BPTT kernel's registers (taco_decoder_bwd_xcd.h, DBR_*): ROWS of the kernels -- wave w of member m holds row 8m + w
-// (128-wide inputs: row 4m + w on waves 0-3) of every matrix a gradient is pulled back through, inputs 4*lane .. 4*lane + 3 per register quad.
-static int dbx_build_pack(taco_model* m) {
-  if (!dx_widths_ok(m)) return 0;
-  const taco_hparams& hp = m->hp;
-  const int H = DX_W, Mm = hp.num_mels;
-  // 'simple': S speaker rows sit between the prenet rows and the h rows of the attention GRU kernels (and behind [h_att | ctx] in the
-  // concat projection).  The embedding is constant over the loop, so its gradient is a sum over steps of products with those rows --
-  // formed once after the launch from the time-summed pre-activation gradients (decoder_backward); the kernel only skips the rows.
-  const int IA = DX_P2 + (is_simple(m) ? hp.speaker_embedding_size : 0);
-  std::vector<float> pack((size_t)DX_GROUP * DB_NREG * DX_NT, 0.f);
-  const auto& g2k = T_(m, "decoder/gru_2/gates/kernel").data; const auto& c2k = T_(m, "decoder/gru_2/candidate/kernel").data;
-  const auto& g1k = T_(m, "decoder/gru_1/gates/kernel").data; const auto& c1k = T_(m, "decoder/gru_1/candidate/kernel").data;
-  const auto& cck = T_(m, "decoder/concat_projection/kernel").data;
-  const auto& wq = T_(m, "attention/query_layer/kernel").data;
-  const auto& agk = T_(m, "decoder/attention_gru/gates/kernel").data; const auto& ack = T_(m, "decoder/attention_gru/candidate/kernel").data;
-  const auto& W2 = T_(m, "decoder/prenet/dense_2/kernel").data; const auto& W1 = T_(m, "decoder/prenet/dense_1/kernel").data;
-  for (int mem = 0; mem < DX_GROUP; ++mem)
-    for (int tid = 0; tid < DX_NT; ++tid) {
-      const int wave = tid >> 6, lane = tid & 63, en = mem * 8 + wave, en2 = wave < 4 ? mem * 4 + wave : -1;
-      float* R = &pack[((size_t)mem * DB_NREG) * DX_NT + tid];
-      // registers reg0 .. reg0 + kw - 1 = W[row][col0 + kw*lane + e] (zero past ncols)
-      auto row = [&](int reg0, int kw, const std::vector<float>& W, int ldw, int r, int col0, int ncols) {
-        if (r < 0) return;
-        for (int e = 0; e < kw; ++e) { const int c = col0 + kw * lane + e; if (c < ncols) R[(size_t)(reg0 + e) * DX_NT] = W[(size_t)r * ldw + c]; }
-      };
-      row(DBR_C2X, 4, c2k, H, en, 0, H); row(DBR_C2H, 4, c2k, H, H + en, 0, H);
-      row(DBR_G2X, 4, g2k, 2 * H, en, 0, 2 * H); row(DBR_G2X + 4, 4, g2k, 2 * H, en, 256, 2 * H);
-      row(DBR_G2H, 4, g2k, 2 * H, H + en, 0, 2 * H); row(DBR_G2H + 4, 4, g2k, 2 * H, H + en, 256, 2 * H);
-      row(DBR_C1X, 4, c1k, H, en, 0, H); row(DBR_C1H, 4, c1k, H, H + en, 0, H);
-      row(DBR_G1X, 4, g1k, 2 * H, en, 0, 2 * H); row(DBR_G1X + 4, 4, g1k, 2 * H, en, 256, 2 * H);
-      row(DBR_G1H, 4, g1k, 2 * H, H + en, 0, 2 * H); row(DBR_G1H + 4, 4, g1k, 2 * H, H + en, 256, 2 * H);
-      row(DBR_CCA, 4, cck, H, en, 0, H); row(DBR_CCC, 4, cck, H, H + en, 0, H);
-      row(DBR_Q, 4, wq, H, en, 0, H);
-      row(DBR_CAX, 4, ack, H, en2, 0, H); row(DBR_CAH, 4, ack, H, IA + en, 0, H);
-      row(DBR_GAX, 4, agk, 2 * H, en2, 0, 2 * H); row(DBR_GAX + 4, 4, agk, 2 * H, en2, 256, 2 * H);
-      row(DBR_GAH, 4, agk, 2 * H, IA + en, 0, 2 * H); row(DBR_GAH + 4, 4, agk, 2 * H, IA + en, 256, 2 * H);
-      row(DBR_P2, 2, W2, DX_P2, en, 0, DX_P2);
-      row(DBR_P1C, 4, W1, H, Mm + en, 0, H);
-    }
-  m->dbx_pack = arena_put(m, pack.data(), pack.size());
-  return 0;
-}
-
-static void cbhg_dims(Cbhg& c, int in_dim, int K, int C, int maxpool, int depth, int rnn, const int* projs, int nproj, int pw) {
-  c.in_dim = in_dim; c.K = K; c.C = C; c.maxpool = maxpool; c.depth = depth; c.rnn = rnn; c.pw = pw;
-  c.nproj = nproj;
-  for (int i = 0; i < nproj; ++i) c.proj_dim[i] = projs[i];
-}
-
-static void make_cbhg(taco_model* m, Cbhg& c, const std::string& sc, int in_dim, int K, int C, int maxpool,
-                      int depth, int rnn, const int* projs, int nproj, int pw, bool bf3 = false) {
-  cbhg_dims(c, in_dim, K, C, maxpool, depth, rnn, projs, nproj, pw);
-  for (int k = K; k >= 1; --k) {
-    const std::string n = sc + "/conv_bank/conv1d_" + std::to_string(k);
-    ConvL L = make_conv(m, n, true, true, bf3);
-    c.bank.push_back(L);
-    m->convs[n] = L;
-  }
-  for (int i = 0; i < nproj; ++i) {
-    const std::string n = sc + "/proj_" + std::to_string(i + 1);
-    c.proj.push_back(make_conv(m, n, true, true, bf3));
-    m->convs[n] = c.proj.back();
-  }
-  const int last = projs[nproj - 1];
-  c.has_dense = last != rnn;
-  if (c.has_dense) { c.dense = make_conv(m, sc + "/dense", false, true, bf3); m->convs[sc + "/dense"] = c.dense; }
-  for (int i = 0; i < depth; ++i) {
-    const std::string n = sc + "/highway_" + std::to_string(i + 1);
-    ConvL L = make_conv(m, n + "/H", false, true, bf3);
-    ConvL Tt = make_conv(m, n + "/T", false, true, bf3);
-    L.wp2 = Tt.wp; L.bias2 = Tt.bias; L.bh2 = Tt.bh; L.bl2 = Tt.bl; L.bl3_2 = Tt.bl3;
-    c.hw.push_back(L);
-    m->convs[n] = L;
-  }
-  // BiGRU: hoisted input projection [rnn, 2*(2H+H)] = [fw gates(r|u) | fw cand | bw gates | bw cand]
-  const int H = rnn, I = rnn;
-  std::vector<float> Wx((size_t)I * 6 * H), bx(6 * H);
-  for (int dir = 0; dir < 2; ++dir) {
-    const std::string n = sc + "/bigru/" + (dir ? "bw" : "fw");
-    const auto& gk = T_(m, n + "/gates/kernel").data; const auto& gb = T_(m, n + "/gates/bias").data;
-    const auto& ck = T_(m, n + "/candidate/kernel").data; const auto& cb = T_(m, n + "/candidate/bias").data;
-    for (int i = 0; i < I; ++i) {
-      for (int j = 0; j < 2 * H; ++j) Wx[(size_t)i * 6 * H + dir * 3 * H + j] = gk[(size_t)i * 2 * H + j];
-      for (int j = 0; j < H; ++j) Wx[(size_t)i * 6 * H + dir * 3 * H + 2 * H + j] = ck[(size_t)i * H + j];
-    }
-    for (int j = 0; j < 2 * H; ++j) bx[dir * 3 * H + j] = gb[j];
-    for (int j = 0; j < H; ++j) bx[dir * 3 * H + 2 * H + j] = cb[j];
-    c.gh[dir] = pack_w16(m, gk.data(), 2 * H, I, H, 0, 2 * H, nullptr);
-    c.ch[dir] = pack_w16(m, ck.data(), H, I, H, 0, H, nullptr);
-    c.raw_gh[dir] = arena_put(m, gk.data() + (size_t)I * 2 * H, (size_t)H * 2 * H);
-    c.raw_ch[dir] = arena_put(m, ck.data() + (size_t)I * H, (size_t)H * H);
-    { std::vector<float> g2((size_t)H * H * 2);
-      for (int k = 0; k < H; ++k)
-        for (int j = 0; j < H; ++j) { g2[((size_t)k * H + j) * 2] = gk[(size_t)(I + k) * 2 * H + j]; g2[((size_t)k * H + j) * 2 + 1] = gk[(size_t)(I + k) * 2 * H + H + j]; }
-      c.res_g2[dir] = arena_put(m, g2.data(), g2.size());
-      if (H == 256) {
-        std::vector<float> g2p(g2.size()), c1p((size_t)H * H);
-        for (int k = 0; k < H; ++k)
-          for (int jb = 0; jb < 64; ++jb)
-            for (int u = 0; u < 4; ++u) {
-              const int j = jb + 64 * u, cp = jb * 4 + u;
-              g2p[((size_t)k * H + cp) * 2] = g2[((size_t)k * H + j) * 2]; g2p[((size_t)k * H + cp) * 2 + 1] = g2[((size_t)k * H + j) * 2 + 1];
-              c1p[(size_t)k * H + cp] = ck[(size_t)(I + k) * H + j];
-            }
-        c.res_g2p[dir] = arena_put(m, g2p.data(), g2p.size());
-        c.res_c1p[dir] = arena_put(m, c1p.data(), c1p.size());
-      } }
-  }
-  if (H == GX_H) {
-    // k_bigru_duo<RG>: member mem, wave w owns unit 8 mem + w of BOTH directions; lane l holds h rows 4l..4l+3 of its r, u and c columns
-    std::vector<float> gp((size_t)2 * GD_MEMBERS * 12 * 512, 0.f);
-    for (int dir = 0; dir < 2; ++dir) {
-      const std::string n = sc + "/bigru/" + (dir ? "bw" : "fw");
-      const auto& gk = T_(m, n + "/gates/kernel").data; const auto& ck = T_(m, n + "/candidate/kernel").data;
-      for (int mem = 0; mem < GD_MEMBERS; ++mem)
-        for (int tid = 0; tid < 512; ++tid) {
-          const int w = tid >> 6, l = tid & 63, u = mem * 8 + w;
-          for (int e = 0; e < 4; ++e) {
-            const size_t kr = (size_t)(I + 4 * l + e);
-            float* base = &gp[(((size_t)dir * GD_MEMBERS + mem) * 12) * 512 + tid];
-            base[(size_t)(0 + e) * 512] = gk[kr * 2 * H + u];
-            base[(size_t)(4 + e) * 512] = gk[kr * 2 * H + H + u];
-            base[(size_t)(8 + e) * 512] = ck[kr * H + u];
-          }
-        }
-    }
-    c.gd_pack = arena_put(m, gp.data(), gp.size());
-    // k_bigru_oct<UPW>: member mem of a cluster of 32 / UPW, wave w owns units 8 UPW mem + UPW w + i of BOTH directions; lane l holds h rows
-    // 4l..4l+3 of the columns r_0, u_0, r_1, u_1, ... (registers 8i + 4g + e) and then of the candidates c_i (8 UPW + 4i + e)
-    for (int lg = 0; lg < 3; ++lg) {
-      const int UPW = 1 << lg, MB = DX_GROUP / UPW, NR = 12 * UPW;
-      std::vector<float> op((size_t)2 * MB * NR * 512, 0.f);
-      for (int dir = 0; dir < 2; ++dir) {
-        const std::string n = sc + "/bigru/" + (dir ? "bw" : "fw");
-        const auto& gk = T_(m, n + "/gates/kernel").data; const auto& ck = T_(m, n + "/candidate/kernel").data;
-        for (int mem = 0; mem < MB; ++mem)
-          for (int tid = 0; tid < 512; ++tid) {
-            const int w = tid >> 6, l = tid & 63;
-            float* base = &op[(((size_t)dir * MB + mem) * NR) * 512 + tid];
-            for (int i = 0; i < UPW; ++i) {
-              const int u = mem * 8 * UPW + w * UPW + i;
-              for (int e = 0; e < 4; ++e) {
-                const size_t kr = (size_t)(I + 4 * l + e);
-                base[(size_t)(8 * i + e) * 512] = gk[kr * 2 * H + u];
-                base[(size_t)(8 * i + 4 + e) * 512] = gk[kr * 2 * H + H + u];
-                base[(size_t)(8 * UPW + 4 * i + e) * 512] = ck[kr * H + u];
-              }
-            }
-          }
-      }
-      c.go_pack[lg] = arena_put(m, op.data(), op.size());
-    }
-    if (m->tp) {   // k_bigru_duo_bwd (training only): ROWS of the recurrent kernels -- unit u's row of Wc_h, then of Wg_h (r half, u half)
-      std::vector<float> bp((size_t)2 * GD_MEMBERS * 12 * 512, 0.f);
-      for (int dir = 0; dir < 2; ++dir) {
-        const std::string n = sc + "/bigru/" + (dir ? "bw" : "fw");
-        const auto& gk = T_(m, n + "/gates/kernel").data; const auto& ck = T_(m, n + "/candidate/kernel").data;
-        for (int mem = 0; mem < GD_MEMBERS; ++mem)
-          for (int tid = 0; tid < 512; ++tid) {
-            const int w = tid >> 6, l = tid & 63, u = mem * 8 + w;
-            float* base = &bp[(((size_t)dir * GD_MEMBERS + mem) * 12) * 512 + tid];
-            for (int e = 0; e < 4; ++e) {
-              base[(size_t)(0 + e) * 512] = ck[(size_t)(I + u) * H + 4 * l + e];
-              base[(size_t)(4 + e) * 512] = gk[(size_t)(I + u) * 2 * H + 4 * l + e];
-              base[(size_t)(8 + e) * 512] = gk[(size_t)(I + u) * 2 * H + H + 4 * l + e];
-            }
-          }
-      }
-      c.gb_pack = arena_put(m, bp.data(), bp.size());
-      // k_bigru_oct_bwd: member mem of a cluster of 8, wave w owns units 32 mem + 4 w + i; lane l holds inputs 4l..4l+3 of the unit's ROWS: registers
-      // 8 p + 4 j + e = Wc_h row of unit 2 p + j (p = 0, 1); 16 + 8 i + e / 16 + 8 i + 4 + e = Wg_h row of unit i, r half / u half
-      std::vector<float> ob((size_t)2 * (DX_GROUP / GOB_UPW) * 48 * 512, 0.f);
-      for (int dir = 0; dir < 2; ++dir) {
-        const std::string n = sc + "/bigru/" + (dir ? "bw" : "fw");
-        const auto& gk = T_(m, n + "/gates/kernel").data; const auto& ck = T_(m, n + "/candidate/kernel").data;
-        for (int mem = 0; mem < DX_GROUP / GOB_UPW; ++mem)
-          for (int tid = 0; tid < 512; ++tid) {
-            const int w = tid >> 6, l = tid & 63;
-            float* base = &ob[(((size_t)dir * (DX_GROUP / GOB_UPW) + mem) * 48) * 512 + tid];
-            for (int i = 0; i < GOB_UPW; ++i) {
-              const int u = mem * GOB_UPM + w * GOB_UPW + i;
-              for (int e = 0; e < 4; ++e) {
-                base[(size_t)(8 * (i >> 1) + 4 * (i & 1) + e) * 512] = ck[(size_t)(I + u) * H + 4 * l + e];
-                base[(size_t)(16 + 8 * i + e) * 512] = gk[(size_t)(I + u) * 2 * H + 4 * l + e];
-                base[(size_t)(16 + 8 * i + 4 + e) * 512] = gk[(size_t)(I + u) * 2 * H + H + 4 * l + e];
-              }
-            }
-          }
-      }
-      c.gob_pack = arena_put(m, ob.data(), ob.size());
-    }
-  }
-  ConvL X; X.kw = 1; X.cin = I; X.N = 6 * H;
-  int Kq, NT;
-  X.wp = pack_w32(m, Wx.data(), 1, I, 6 * H, &X.cin_pad, &Kq, &NT);
-  if (bf3 && !m->tp) X.bl3 = 1;
-  if (bf3) pack_bf3(m, Wx.data(), 1, I, 6 * H, &X.bh, &X.bl, &X.K16, &X.cin_pad16, &X.bl3);
-  X.bias = arena_put(m, bx.data(), 6 * H);
-  c.xproj = X;
-  // fused front (taco_front.h): inference models only (the training forward needs the bank tensor for its batch statistics)
-  c.front_kind = 0;
-  if (bf3 && !m->tp && maxpool == 2 && pw == 3 && nproj >= 1 && C % FR_CH == 0 && K * (C / FR_CH) <= FR_MAXCH && K <= FR_MAXW) {
-    const int cinp = rup(in_dim, 16), N1 = projs[0];
-    // (N1 % 32: k_front_combine and the chain's fused entry read the partial sums, bias and BatchNorm operands as float4 at n = i % N1 and
-    // consume them in 32-column tiles -- a custom first projection size such as 250 takes the two-launch path)
-    if (cinp == 80 && K <= 8 && N1 <= 256 && N1 % 32 == 0) c.front_kind = 1;
-    else if (cinp == 128 && K <= 16 && N1 <= 128 && N1 % 32 == 0) c.front_kind = 2;
-    if (c.front_kind) {
-      for (const ConvL& L : c.bank) {
-        const HostTensor& kt = T_(m, sc + "/conv_bank/conv1d_" + std::to_string(L.kw) + "/kernel");
-        const int ns = rup(cdiv(L.kw * cinp, 32), 2), nct = C / 16;     // even: the kernel walks the steps in pairs (a padding step has zero weights)
-        std::vector<unsigned short> hi((size_t)ns * nct * 512, 0), lo(hi.size(), 0);
-        for (int st = 0; st < ns; ++st)
-          for (int ct = 0; ct < nct; ++ct)
-            for (int q = 0; q < 4; ++q)
-              for (int i = 0; i < 16; ++i)
-                for (int e = 0; e < 8; ++e) {
-                  const int kk = 32 * st + 8 * q + e, tap = kk / cinp, cc = kk % cinp;
-                  if (tap >= L.kw || cc >= in_dim) continue;
-                  const float w = kt.data[((size_t)tap * in_dim + cc) * C + 16 * ct + i];
-                  const unsigned short hb = bf16_rne_host(w);
-                  unsigned hu = (unsigned)hb << 16; float hf; memcpy(&hf, &hu, 4);
-                  const size_t o = (((size_t)st * nct + ct) * 64 + q * 16 + i) * 8 + e;
-                  hi[o] = hb; lo[o] = bf16_rne_host(w - hf);
-                }
-        auto put = [&](const std::vector<unsigned short>& v) {
-          std::vector<float> f((v.size() + 1) / 2, 0.f);
-          memcpy(f.data(), v.data(), v.size() * sizeof(unsigned short));
-          return arena_put(m, f.data(), f.size());
-        };
-        c.fr_wh.push_back(put(hi)); c.fr_wl.push_back(put(lo)); c.fr_ns.push_back(ns);
-      }
-    }
-  }
-}
-
-static int add_var(taco_model* m, ConvL& L, int coff) {
-  GemmVar v;
-  memset(&v, 0, sizeof v);
-  // pointers are resolved after the arena upload (see finalize): store offsets for now
-  v.wp = (const float*)L.wp; v.wp2 = (const float*)L.wp2; v.bias = (const float*)L.bias; v.bias2 = (const float*)L.bias2;
-  v.bn_scale = (const float*)L.bns; v.bn_shift = (const float*)L.bnb;
-  v.bh = (const unsigned short*)L.bh; v.bl = (const unsigned short*)L.bl; v.bh2 = (const unsigned short*)L.bh2; v.bl2 = (const unsigned short*)L.bl2;
-  v.bl3 = (const unsigned short*)L.bl3; v.bl3_2 = (const unsigned short*)L.bl3_2;
-  v.K16 = L.K16; v.cin_pad16 = L.cin_pad16;
-  v.kw = L.kw; v.padl = (L.kw - 1) / 2; v.Kq = L.kw * L.cin_pad / 4; v.NT = cdiv(L.N, 32); v.N = L.N; v.coff = coff;
-  L.var_index = (int)m->hvars.size();
-  m->hvars.push_back(v);
-  return L.var_index;
-}
+#include "taco_pack.h"      // the model build: every pack builder, the composite weights, model_pack_host
 
 // ------------------------------------------------------------------------------------------------
 // launch helpers
@@ -1643,9 +1132,6 @@ static void carve_spk(Carver& cv, const taco_model* m, int B, SpkWs& w) {
   const int dims[3] = {hp.enc_prenet[hp.enc_prenet_n - 1], hp.enc_rnn_size * 2, hp.attention_state_size};
   for (int i = 0; i < 3 + hp.dec_layer_num; ++i) w.vec[i] = cv.f((size_t)B * (i < 3 ? dims[i] : hp.dec_rnn_size));
 }
-static bool is_deepvoice(const taco_model* m) { return m->hp.num_speakers > 1 && m->hp.model_type == 2; }
-static bool is_simple(const taco_model* m) { return m->hp.num_speakers > 1 && m->hp.model_type == 1; }
-static int simple_S(const taco_model* m) { return is_simple(m) ? m->hp.speaker_embedding_size : 0; }
 static size_t spk_weights_offset(int b0, int num_speakers) { return (size_t)b0 * (size_t)num_speakers; }      // where row b0 of [B, num_speakers] starts
 // Which speaker each batch row speaks with: one trained speaker by id [B], or a mixture of all of them by weights [B, num_speakers]
 // (taco_abi.h, "speaker mixtures") -- never both.  Device pointers, read by kernels only.
@@ -2278,198 +1764,14 @@ int taco_model_set_weight(taco_model* m, const char* name, const float* host, co
   return fail(TACO_ERR_ARG, "unknown weight name '%s'", name);
 }
 
-int taco_model_finalize(taco_model* m) {
-  if (!m) return fail(TACO_ERR_ARG, "null model");
-  if (m->finalized) return 0;
-  for (auto& s : m->spec)
-    if (!m->raw.count(s.first) || !m->raw[s.first].set) return fail(TACO_ERR_STATE, "weight '%s' was never set", s.first.c_str());
-  const taco_hparams& hp = m->hp;
+// step 3 of taco_model_finalize: the arena on the device, the GemmVar table's offsets resolved to pointers into it, the sticky error word
+static int model_upload(taco_model* m) {
   HIPCHK(hipSetDevice(m->device));
   HIPCHK(hipDeviceGetAttribute(&m->cu_count, hipDeviceAttributeMultiprocessorCount, m->device));
-  m->harena.clear(); m->hvars.clear();
-  m->emb = arena_put(m, T_(m, "embedding").data.data(), T_(m, "embedding").data.size());
-  for (int i = 0; i < hp.enc_prenet_n; ++i) {
-    const std::string n = "prenet/dense_" + std::to_string(i + 1);
-    m->enc_prenet.push_back(make_conv(m, n, false, true, true));
-  }
-  make_cbhg(m, m->enc, "encoder_cbhg", hp.enc_prenet[hp.enc_prenet_n - 1], hp.enc_bank_size, hp.enc_bank_channels,
-            hp.enc_maxpool, hp.enc_highway_depth, hp.enc_rnn_size, hp.enc_proj, hp.enc_proj_n, hp.enc_proj_width, true);
-  // fp32-grade: the keys feed the alignment argmax, the one output held to "bit-identical".  Rounds 1-3: the exact-fp32 MFMA (k_gemm, +35 us per
-  // C2 forward over the three-product split); round 4: the SIX-product split (operands split three ways, 2^-24 per product) on the bf16 pipe
-  m->memory_layer = make_conv(m, "attention/memory_layer", false, false, true, true);
-  make_cbhg(m, m->post, "post_cbhg", hp.num_mels, hp.post_bank_size, hp.post_bank_channels, hp.post_maxpool,
-            hp.post_highway_depth, hp.post_rnn_size, hp.post_proj, hp.post_proj_n, hp.post_proj_width, true);
-  if (hp.num_speakers > 1 && hp.model_type == 1) {
-    // linear head input = concat(speaker_embed, post_outputs) (tacotron.py:226-235): rows [0,S) of the kernel
-    // multiply the per-utterance embedding -> a per-batch-row vector; rows [S,..) stay a GEMM over the frames
-    const int S = hp.speaker_embedding_size, F = hp.num_freq;
-    HostTensor& k = m->raw["linear/kernel"];
-    m->lin_spk = pack_w16(m, k.data.data(), F, 0, S, 0, F, nullptr);
-    { HostTensor head; head.shape = {(int64_t)S, (int64_t)F}; head.data.assign(k.data.begin(), k.data.begin() + (size_t)S * F); head.set = true;
-      m->raw["linear/kernel_spk"] = head; }     // kept for the training packs (transposed speaker rows)
-    HostTensor rest; rest.shape = {k.shape[0] - S, (int64_t)F};
-    rest.data.assign(k.data.begin() + (size_t)S * F, k.data.end());
-    rest.set = true;
-    m->raw["linear/kernel"] = rest;
-    m->spk_emb = arena_put(m, T_(m, "speaker_embedding").data.data(), T_(m, "speaker_embedding").data.size());
-  }
-  m->linear = make_conv(m, "linear", false, true, true);
-  // decoder (skinny packs)
-  const int D = 2 * hp.enc_rnn_size, As = hp.attention_state_size, Hd = hp.dec_rnn_size, A = hp.attention_size;
-  int d = hp.num_mels + D;
-  for (int i = 0; i < hp.dec_prenet_n; ++i) {
-    const std::string n = "decoder/prenet/dense_" + std::to_string(i + 1);
-    m->dec_prenet.push_back(pack_w16(m, T_(m, n + "/kernel").data.data(), hp.dec_prenet[i], 0, d, 0, hp.dec_prenet[i], T_(m, n + "/bias").data.data()));
-    m->skinny[n] = m->dec_prenet.back();
-    d = hp.dec_prenet[i];
-  }
-  m->att_gru = make_grudec(m, "decoder/attention_gru", d + simple_S(m), As);   // simple: input = concat(prenet_out, speaker_embed)
-  m->grus["decoder/attention_gru"] = m->att_gru;
-  m->query = pack_w16(m, T_(m, "attention/query_layer/kernel").data.data(), A, 0, As, 0, A, nullptr);
-  m->skinny["attention/query_layer"] = m->query;
-  m->raw_wq = arena_put(m, T_(m, "attention/query_layer/kernel").data.data(), (size_t)As * A);
-  m->concat_proj = pack_w16(m, T_(m, "decoder/concat_projection/kernel").data.data(), Hd, 0, As + D + simple_S(m), 0, Hd, T_(m, "decoder/concat_projection/bias").data.data());
-  m->skinny["decoder/concat_projection"] = m->concat_proj;
-  for (int i = 0; i < hp.dec_layer_num; ++i) {
-    const std::string n = "decoder/gru_" + std::to_string(i + 1);
-    m->dec_gru.push_back(make_grudec(m, n, Hd, Hd));
-    m->grus[n] = m->dec_gru.back();
-  }
-  const int rM = hp.num_mels * hp.reduction_factor;
-  m->frame_proj = pack_w16(m, T_(m, "decoder/frame_projection/kernel").data.data(), rM, 0, Hd, 0, rM, T_(m, "decoder/frame_projection/bias").data.data());
-  m->skinny["decoder/frame_projection"] = m->frame_proj;
-  std::vector<float> dx_Wc, dx_bc;   // kept for the persistent decoder's pack (dx_build_pack)
-  {  // prenet layer 1 of the NEXT step, fed with this step's outputs (helpers.py:31 feeds back the last of the r frames):
-     //   relu([frame, ctx] . W1 + b1), frame = o . Wf[:, rM-M:] + bf[rM-M:]   =>   relu([o, ctx] . [Wf_last . W1a ; W1b] + (b1 + bf_last . W1a))
-     // computed in the same launch as the frame projection: one dependent launch less per decoder step.
-    const int Mm = hp.num_mels, P0 = hp.dec_prenet[0];
-    const auto& Wf = T_(m, "decoder/frame_projection/kernel").data; const auto& bf = T_(m, "decoder/frame_projection/bias").data;
-    const auto& W1 = T_(m, "decoder/prenet/dense_1/kernel").data; const auto& b1 = T_(m, "decoder/prenet/dense_1/bias").data;
-    std::vector<float>& Wc = dx_Wc; std::vector<float>& bc = dx_bc;
-    Wc.assign((size_t)(Hd + D) * P0, 0.f); bc.assign(P0, 0.f);
-    for (int k = 0; k < Hd; ++k)
-      for (int q = 0; q < P0; ++q) {
-        double acc = 0;
-        for (int j = 0; j < Mm; ++j) acc += (double)Wf[(size_t)k * rM + (rM - Mm) + j] * (double)W1[(size_t)j * P0 + q];
-        Wc[(size_t)k * P0 + q] = (float)acc;
-      }
-    for (int k = 0; k < D; ++k)
-      for (int q = 0; q < P0; ++q) Wc[(size_t)(Hd + k) * P0 + q] = W1[(size_t)(Mm + k) * P0 + q];
-    for (int q = 0; q < P0; ++q) {
-      double acc = b1[q];
-      for (int j = 0; j < Mm; ++j) acc += (double)bf[(rM - Mm) + j] * (double)W1[(size_t)j * P0 + q];
-      bc[q] = (float)acc;
-    }
-    m->prenet1_next = pack_w16(m, Wc.data(), P0, 0, Hd + D, 0, P0, bc.data());
-  }
-  if (!m->tp && hp.dec_layer_num > 0) {
-    // Decoder GRU 1 with the concat projection folded in.  o0 = z . Wc + bc is linear in z = [h_att | ctx (| spk)], so
-    //   gates:      [o0, h] . Wg + bg = z . (Wc . Wg_x) + h . Wg_h + (bg + bc . Wg_x)
-    //   candidate x: o0 . Wk_x       = z . (Wc . Wk_x) + bc . Wk_x
-    // and o0 itself (the ResidualWrapper input, tacotron.py:172) comes out of the same launch as Hd extra columns: one dependent
-    // launch less per decoder step.  Products are formed in double and rounded once.  (Not built for the training shadow model.)
-    const int Z = As + D + simple_S(m), N4 = 4 * Hd;
-    const auto& Wc = T_(m, "decoder/concat_projection/kernel").data; const auto& bcv = T_(m, "decoder/concat_projection/bias").data;
-    const auto& gk = T_(m, "decoder/gru_1/gates/kernel").data; const auto& gb = T_(m, "decoder/gru_1/gates/bias").data;
-    const auto& ck = T_(m, "decoder/gru_1/candidate/kernel").data; const auto& cb = T_(m, "decoder/gru_1/candidate/bias").data;
-    std::vector<float> W((size_t)(Z + Hd) * N4, 0.f), bb(N4, 0.f);
-    std::vector<double> row(3 * Hd);
-    for (int z = 0; z <= Z; ++z) {      // row Z of this loop = the bias row (z . Wc replaced by bc)
-      std::fill(row.begin(), row.end(), 0.0);
-      for (int k = 0; k < Hd; ++k) {
-        const double c = (z < Z) ? (double)Wc[(size_t)z * Hd + k] : (double)bcv[k];
-        for (int j = 0; j < 2 * Hd; ++j) row[j] += c * (double)gk[(size_t)k * 2 * Hd + j];
-        for (int j = 0; j < Hd; ++j) row[2 * Hd + j] += c * (double)ck[(size_t)k * Hd + j];
-      }
-      if (z < Z) {
-        for (int j = 0; j < 3 * Hd; ++j) W[(size_t)z * N4 + j] = (float)row[j];
-        for (int j = 0; j < Hd; ++j) W[(size_t)z * N4 + 3 * Hd + j] = Wc[(size_t)z * Hd + j];
-      } else {
-        for (int j = 0; j < 2 * Hd; ++j) bb[j] = (float)(row[j] + (double)gb[j]);
-        for (int j = 0; j < Hd; ++j) { bb[2 * Hd + j] = (float)row[2 * Hd + j]; bb[3 * Hd + j] = bcv[j]; }
-      }
-    }
-    for (int k = 0; k < Hd; ++k)
-      for (int j = 0; j < 2 * Hd; ++j) W[(size_t)(Z + k) * N4 + j] = gk[(size_t)(Hd + k) * 2 * Hd + j];
-    m->gru1_fold.I = Z; m->gru1_fold.H = Hd;
-    m->gru1_fold.gx = pack_w16(m, W.data(), N4, 0, Z + Hd, 0, N4, bb.data());
-    m->gru1_fold.ch = pack_w16(m, ck.data(), Hd, Hd, Hd, 0, Hd, cb.data());
-    m->fuse_concat = 1;
-    if (hp.dec_layer_num == 2) TRY(dx_build_pack(m, dx_Wc, dx_bc, W, bb));
-  }
-  if (m->tp && hp.dec_layer_num == 2 && dx_widths_ok(m)) {
-    // Training shadow model: every "weight" here is 1 + the flat index of a parameter, and the arena doubles as the index map of
-    // taco_train_refresh.  The persistent decoder's pack is built in TEACHER form: the next step's prenet layer 1 reads the
-    // teacher's frame, so its registers hold the raw kernel rows (zero beyond num_mels) instead of the frame-projection composite;
-    // the one composite that remains -- the concat projection folded into GRU 1 -- is computed on the device after every
-    // optimizer step (k_dx_fold) into a buffer that the index map addresses as NP + 1 + i.
-    const int Mm = hp.num_mels, P0 = hp.dec_prenet[0], H = Hd, Z = As + D + simple_S(m), N4 = 4 * H;
-    const auto& W1 = T_(m, "decoder/prenet/dense_1/kernel").data;
-    std::vector<float> Wc_t((size_t)(Hd + D) * P0, 0.f);
-    for (int k = 0; k < Mm; ++k) for (int q = 0; q < P0; ++q) Wc_t[(size_t)k * P0 + q] = W1[(size_t)k * P0 + q];                 // frame rows (k < num_mels)
-    for (int k = 0; k < D; ++k) for (int q = 0; q < P0; ++q) Wc_t[(size_t)(Hd + k) * P0 + q] = W1[(size_t)(Mm + k) * P0 + q];    // context rows
-    const auto& Wcc = T_(m, "decoder/concat_projection/kernel").data; const auto& bcv = T_(m, "decoder/concat_projection/bias").data;
-    const auto& gk = T_(m, "decoder/gru_1/gates/kernel").data;
-    size_t NP = 0;
-    for (auto& sp : m->spec) { size_t c = 1; for (int64_t d : sp.second) c *= (size_t)d; NP += c; }
-    std::vector<float> Wf_t((size_t)(Z + Hd) * N4, 0.f), bf_t(N4, 0.f);
-    for (int z = 0; z <= Z; ++z)
-      for (int j = 0; j < 3 * H; ++j) {
-        const float idx = (float)(NP + 1 + (size_t)z * 3 * H + j);
-        if (z < Z) Wf_t[(size_t)z * N4 + j] = idx; else bf_t[j] = idx;
-      }
-    for (int z = 0; z < Z; ++z) for (int j = 0; j < H; ++j) Wf_t[(size_t)z * N4 + 3 * H + j] = Wcc[(size_t)z * Hd + j];
-    for (int j = 0; j < H; ++j) bf_t[3 * H + j] = bcv[j];
-    for (int k = 0; k < Hd; ++k) for (int j = 0; j < 2 * H; ++j) Wf_t[(size_t)(Z + k) * N4 + j] = gk[(size_t)(Hd + k) * 2 * H + j];
-    m->dx_fold_n = (size_t)(Z + 1) * 3 * H;
-    if (NP + m->dx_fold_n >= (1u << 24)) return fail(TACO_ERR_UNSUPPORTED, "parameter + fold indices exceed 2^24");
-    TRY(dx_build_pack(m, Wc_t, T_(m, "decoder/prenet/dense_1/bias").data, Wf_t, bf_t));
-    TRY(dbx_build_pack(m));
-  }
-  {  // attention vectors; bah_norm: v_hat = g * v / |v| (A.9)
-    std::vector<float> v = T_(m, "attention/attention_v").data;
-    if (hp.attention_type == 1) {
-      double nrm = 0; for (float x : v) nrm += (double)x * x;
-      const double sc = (double)T_(m, "attention/attention_g").data[0] / std::sqrt(nrm);
-      for (float& x : v) x = (float)(x * sc);
-      m->att_b = arena_put(m, T_(m, "attention/attention_b").data.data(), A);
-    }
-    m->att_v = arena_put(m, v.data(), A);
-    if (hp.attention_type == 2) m->att_sb = arena_put(m, T_(m, "attention/attention_score_bias").data.data(), 1);
-  }
-  if (is_deepvoice(m)) {
-    std::vector<std::string> names = {kSpkNames[0], kSpkNames[1], kSpkNames[2]};
-    for (int i = 0; i < hp.dec_layer_num; ++i) names.push_back("decoder_rnn_init_" + std::to_string(i + 1));
-    if (hp.speaker_embedding_size == 1) {
-      for (auto& n : names) m->spk_table.push_back(arena_put(m, T_(m, "spk/" + n + "/table").data.data(), T_(m, "spk/" + n + "/table").data.size()));
-    } else {
-      m->spk_emb = arena_put(m, T_(m, "speaker_embedding").data.data(), T_(m, "speaker_embedding").data.size());
-      for (auto& n : names) {
-        const HostTensor& k = T_(m, "spk/" + n + "/kernel");
-        m->spk_dense.push_back(pack_w16(m, k.data.data(), (int)k.shape[1], 0, (int)k.shape[0], 0, (int)k.shape[1], T_(m, "spk/" + n + "/bias").data.data()));
-      }
-    }
-  }
-  // GemmVar table (bank variants must be contiguous)
-  for (int i = 0; i < hp.enc_prenet_n; ++i) add_var(m, m->enc_prenet[i], 0);
-  for (Cbhg* c : {&m->enc, &m->post}) {
-    for (size_t i = 0; i < c->bank.size(); ++i) add_var(m, c->bank[i], (c->bank[i].kw - 1) * c->C);
-    for (auto& L : c->proj) add_var(m, L, 0);
-    if (c->has_dense) add_var(m, c->dense, 0);
-    for (auto& L : c->hw) add_var(m, L, 0);
-    add_var(m, c->xproj, 0);
-  }
-  add_var(m, m->memory_layer, 0);
-  add_var(m, m->linear, 0);
-  // stand-alone copies for the op-level entry points (coff 0)
-  for (auto& kv : m->convs) add_var(m, kv.second, 0);
-  for (int i = 0; i < hp.enc_prenet_n; ++i) m->convs["prenet/dense_" + std::to_string(i + 1)] = m->enc_prenet[i];
-  m->convs["attention/memory_layer"] = m->memory_layer;
-  m->convs["linear"] = m->linear;
-  if (m->tp) TRY(build_train_packs(m));
-  // upload
   HIPCHK(hipMalloc((void**)&m->darena, m->harena.size() * sizeof(float)));
   HIPCHK(hipMemcpy(m->darena, m->harena.data(), m->harena.size() * sizeof(float), hipMemcpyHostToDevice));
+  m->arena_n = m->harena.size();
+  m->harena.clear(); m->harena.shrink_to_fit();
   for (auto& v : m->hvars) {
     v.wp = AP(m, (size_t)v.wp); v.wp2 = AP(m, (size_t)v.wp2); v.bias = AP(m, (size_t)v.bias); v.bias2 = AP(m, (size_t)v.bias2);
     v.bn_scale = AP(m, (size_t)v.bn_scale); v.bn_shift = AP(m, (size_t)v.bn_shift);
@@ -2477,24 +1779,22 @@ int taco_model_finalize(taco_model* m) {
     v.bh2 = (const unsigned short*)AP(m, (size_t)v.bh2); v.bl2 = (const unsigned short*)AP(m, (size_t)v.bl2);
     v.bl3 = (const unsigned short*)AP(m, (size_t)v.bl3); v.bl3_2 = (const unsigned short*)AP(m, (size_t)v.bl3_2);
   }
-  // persistent kernels carve up to the full 160 KiB of LDS
-  HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_cbhg_front<2, 80, 80, 8>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-  HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_cbhg_front<1, 144, 128, 16>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-  HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_bigru_res<256, 64, 24, 1, false>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-  HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_bigru_res<128, 32, 0, 1, false>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-  HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_bigru_res<256, 64, 24, 1, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-  HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_bigru_res<128, 32, 0, 1, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-  HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_bigru_resw<16, 4, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-  HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_bigru_rows<1, false>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-  HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_bigru_rows<2, false>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-  HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_bigru_rows<1, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-  HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_bigru_rows<2, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-  HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_pointwise_chain<256>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-  HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_head_sweep<512>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-  HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_head_sweep<256>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-  HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_pointwise_chain<128>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+  HIPCHK(hipMalloc((void**)&m->d_err, 256));
+  HIPCHK(hipMemset(m->d_err, 0, 256));
+  return 0;
+}
+// step 4: > 64 KB of dynamic LDS has to be asked for, per kernel and device; the persistent kernels carve up to the full 160 KiB
+static int set_kernel_attributes() {
+#define LDS_ATTR(bytes, ...) HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&__VA_ARGS__), hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
+#define LDS_160K(...) LDS_ATTR(160 * 1024, __VA_ARGS__)
+  LDS_160K(k_cbhg_front<2, 80, 80, 8>) LDS_160K(k_cbhg_front<1, 144, 128, 16>)
+  LDS_160K(k_bigru_res<256, 64, 24, 1, false>) LDS_160K(k_bigru_res<128, 32, 0, 1, false>)
+  LDS_160K(k_bigru_res<256, 64, 24, 1, true>) LDS_160K(k_bigru_res<128, 32, 0, 1, true>)
+  LDS_160K(k_bigru_resw<16, 4, 2>)
+  LDS_160K(k_bigru_rows<1, false>) LDS_160K(k_bigru_rows<2, false>) LDS_160K(k_bigru_rows<1, true>) LDS_160K(k_bigru_rows<2, true>)
+  LDS_160K(k_pointwise_chain<256>) LDS_160K(k_head_sweep<512>) LDS_160K(k_head_sweep<256>) LDS_160K(k_pointwise_chain<128>)
   TRY(gemm_set_attributes());
-#define DX_ATTR(...) HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_decoder_xcd<__VA_ARGS__>), hipFuncAttributeMaxDynamicSharedMemorySize, DX_LDS_BUDGET));
+#define DX_ATTR(...) LDS_ATTR(DX_LDS_BUDGET, k_decoder_xcd<__VA_ARGS__>)
 #define PLAIN(RG, TAPE, AW, PD) DX_ATTR(RG, TAPE, false, AW, PD)
 #define MANUAL(RG, TAPE, AW, PD) DX_ATTR(RG, TAPE, true, AW, PD)
 #define BOTH(RG, TAPE, AW, PD) PLAIN(RG, TAPE, AW, PD) MANUAL(RG, TAPE, AW, PD)
@@ -2505,10 +1805,19 @@ int taco_model_finalize(taco_model* m) {
 #undef MANUAL
 #undef BOTH
 #undef STAMPED
-  HIPCHK(hipMalloc((void**)&m->d_err, 256));
-  HIPCHK(hipMemset(m->d_err, 0, 256));
-  m->arena_n = m->harena.size();
-  m->harena.clear(); m->harena.shrink_to_fit();
+#undef LDS_160K
+#undef LDS_ATTR
+  return 0;
+}
+
+int taco_model_finalize(taco_model* m) {
+  if (!m) return fail(TACO_ERR_ARG, "null model");
+  if (m->finalized) return 0;
+  for (auto& s : m->spec)
+    if (!m->raw.count(s.first) || !m->raw[s.first].set) return fail(TACO_ERR_STATE, "weight '%s' was never set", s.first.c_str());
+  TRY(model_pack_host(m));
+  TRY(model_upload(m));
+  TRY(set_kernel_attributes());
   m->raw.clear();
   m->finalized = true;
   return 0;

@@ -58,7 +58,7 @@ struct taco_train {
 #define DET_SCRATCH_FLOATS ((size_t)48 << 20)      // 192 MB: e.g. 30 M-slices of the largest weight gradient (post-net proj_1, 3 x 2048 x 256)
 
 // ---------------------------------------------------------------------------------------------------------------
-// backward packs (run inside taco_model_finalize of the shadow model, before the arena upload)
+// backward packs (the last part of model_pack_host on a shadow model, taco_pack.h: host only, before the arena upload)
 // ---------------------------------------------------------------------------------------------------------------
 static ConvL make_conv_T(taco_model* m, const float* W, int kw, int cin, int N) {
   // data gradient of y[t] = sum_j W[j] x[t + j - padl] is the SAME-padded correlation of dy with
@@ -68,8 +68,7 @@ static ConvL make_conv_T(taco_model* m, const float* W, int kw, int cin, int N) 
     for (int c = 0; c < cin; ++c)
       for (int n = 0; n < N; ++n) WT[((size_t)(kw - 1 - j) * N + n) * cin + c] = W[((size_t)j * cin + c) * N + n];
   ConvL L; L.kw = kw; L.cin = N; L.N = cin;
-  int Kq, NT;
-  L.wp = pack_w32(m, WT.data(), kw, N, cin, &L.cin_pad, &Kq, &NT);
+  L.wp = pack_w32(m, WT.data(), kw, N, cin, &L.cin_pad);
   pack_bf3(m, WT.data(), kw, N, cin, &L.bh, &L.bl, &L.K16, &L.cin_pad16);
   add_var(m, L, 0);
   m->hvars[L.var_index].padl = kw - 1 - (kw - 1) / 2;
@@ -115,8 +114,7 @@ static void build_cbhg_T(taco_model* m, const Cbhg& c, const std::string& sc, Cb
     for (int r = 0; r < D; ++r)
       for (int q = 0; q < D; ++q) { cat[(size_t)q * D + r] = WH[(size_t)r * D + q]; cat[(size_t)(D + q) * D + r] = WT[(size_t)r * D + q]; }
     ConvL L; L.kw = 1; L.cin = 2 * D; L.N = D;
-    int Kq, NT;
-    L.wp = pack_w32(m, cat.data(), 1, 2 * D, D, &L.cin_pad, &Kq, &NT);
+    L.wp = pack_w32(m, cat.data(), 1, 2 * D, D, &L.cin_pad);
     pack_bf3(m, cat.data(), 1, 2 * D, D, &L.bh, &L.bl, &L.K16, &L.cin_pad16);
     add_var(m, L, 0);
     t.hw_d.push_back(L);
@@ -124,8 +122,8 @@ static void build_cbhg_T(taco_model* m, const Cbhg& c, const std::string& sc, Cb
   const int H = c.rnn, I = c.rnn;
   std::vector<float> WxT((size_t)6 * H * I);              // [6H, I]: transposed hoisted input projection
   for (int dir = 0; dir < 2; ++dir) {
-    const std::string n = sc + "/bigru/" + (dir ? "bw" : "fw");
-    const auto& gk = T_(m, n + "/gates/kernel").data; const auto& ck = T_(m, n + "/candidate/kernel").data;
+    const GruW w = bigru_w(m, sc, dir);
+    const auto &gk = w.gk, &ck = w.ck;
     for (int i = 0; i < I; ++i) {
       for (int j = 0; j < 2 * H; ++j) WxT[(size_t)(dir * 3 * H + j) * I + i] = gk[(size_t)i * 2 * H + j];
       for (int j = 0; j < H; ++j) WxT[(size_t)(dir * 3 * H + 2 * H + j) * I + i] = ck[(size_t)i * H + j];
@@ -136,8 +134,7 @@ static void build_cbhg_T(taco_model* m, const Cbhg& c, const std::string& sc, Cb
     t.chT[dir] = arena_put(m, cT.data(), cT.size());
   }
   ConvL X; X.kw = 1; X.cin = 6 * H; X.N = I;
-  int Kq, NT;
-  X.wp = pack_w32(m, WxT.data(), 1, 6 * H, I, &X.cin_pad, &Kq, &NT);
+  X.wp = pack_w32(m, WxT.data(), 1, 6 * H, I, &X.cin_pad);
   pack_bf3(m, WxT.data(), 1, 6 * H, I, &X.bh, &X.bl, &X.K16, &X.cin_pad16);
   add_var(m, X, 0);
   t.xproj_d = X;
@@ -175,9 +172,7 @@ static int build_train_packs(taco_model* m) {
   { std::vector<float> wqT = transpose2d(T_(m, "attention/query_layer/kernel").data.data(), As, A);
     tp.wqT = arena_put(m, wqT.data(), wqT.size()); }
   if (is_deepvoice(m) && hp.speaker_embedding_size != 1) {
-    std::vector<std::string> names = {kSpkNames[0], kSpkNames[1], kSpkNames[2]};
-    for (int i = 0; i < hp.dec_layer_num; ++i) names.push_back("decoder_rnn_init_" + std::to_string(i + 1));
-    for (auto& n : names) {
+    for (auto& n : spk_vector_names(hp)) {
       const HostTensor& k = T_(m, "spk/" + n + "/kernel");
       tp.spk_T.push_back(pack_w16_T(m, k.data.data(), (int)k.shape[0], (int)k.shape[1]));
     }
@@ -1332,8 +1327,7 @@ static int train_forward_backward(taco_train* t, hipStream_t st, float* P, float
   TRY(cbhg_backward(x, m->enc, t->tp.enc, "encoder_cbhg", cur, nullptr, B, T_in, lengths, w.denc, dpre, w.enc,
                     dv ? w.spk.vec[1] : nullptr, dv ? w.dvec[1] : nullptr, dv ? w.dvec[0] : nullptr, w.rowidx));
   if (dv) {   // speaker conditioning backward (tacotron.py:52-79)
-    std::vector<std::string> names = {kSpkNames[0], kSpkNames[1], kSpkNames[2]};
-    for (int i = 0; i < L; ++i) names.push_back("decoder_rnn_init_" + std::to_string(i + 1));
+    const std::vector<std::string> names = spk_vector_names(hp);
     const int dims[3] = {hp.enc_prenet[hp.enc_prenet_n - 1], hp.enc_rnn_size * 2, hp.attention_state_size};
     if (S == 1) {
       for (size_t i = 0; i < names.size(); ++i) {

@@ -1,10 +1,7 @@
 // taco_train_api.h -- C ABI of the training path (declared in include/taco_abi.h); included inside extern "C".
 
-int taco_train_create(const taco_hparams* hp, int device, taco_train** out) {
-  if (!hp || !out) return fail(TACO_ERR_ARG, "null argument");
-  taco_train* t = new taco_train();
-  int rc = taco_model_create(hp, device, &t->sm);
-  if (rc != 0) { delete t; return rc; }
+// index-valued "weights" of a trainer's shadow model (the packs become index maps) and its TrainPacks
+static int train_shadow_weights(taco_train* t) {
   taco_model* sm = t->sm;
   size_t off = 0;
   for (auto& s : sm->spec) {          // flat layout = spec order, TF tensor layout, no padding
@@ -17,9 +14,20 @@ int taco_train_create(const taco_hparams* hp, int device, taco_train** out) {
     off += cnt;
   }
   t->NP = off;
-  if (off >= (1u << 24)) { taco_model_destroy(sm); delete t; return fail(TACO_ERR_UNSUPPORTED, "more than 2^24 parameters"); }
+  if (off >= (1u << 24)) return fail(TACO_ERR_UNSUPPORTED, "more than 2^24 parameters");
   sm->tp = &t->tp;
   sm->bf3 = 1;                        // finalize builds the split-bf16 packs (as index lists) next to the fp32 ones ...
+  return 0;
+}
+
+int taco_train_create(const taco_hparams* hp, int device, taco_train** out) {
+  if (!hp || !out) return fail(TACO_ERR_ARG, "null argument");
+  taco_train* t = new taco_train();
+  int rc = taco_model_create(hp, device, &t->sm);
+  if (rc != 0) { delete t; return rc; }
+  taco_model* sm = t->sm;
+  rc = train_shadow_weights(t);
+  if (rc != 0) { taco_model_destroy(sm); delete t; return rc; }
   rc = taco_model_finalize(sm);
   if (rc != 0) { taco_model_destroy(sm); delete t; return rc; }
   sm->bf3 = 0; sm->bf3x6 = 1;         // ... and the step starts with its forward GEMMs on the six-product split (fp32-grade; mode 4) and its data
@@ -206,6 +214,62 @@ int taco_debug_wgrad_plan(int wgrad_bf3, int wgrad_planes, int deterministic, lo
   const int o[8] = {p.engine, p.rpb, p.nsplit, p.a_per_tap, p.Mp, (int)p.na, (int)p.nb, p.why ? 1 : 0};
   memcpy(out8, o, sizeof o);
   return 0;
+}
+// Test hook: the host half of taco_model_finalize alone (model_pack_host) -- no handle, no device.
+static uint64_t fnv1a64(const void* p, size_t n, uint64_t h = 14695981039346656037ull) {
+  const unsigned char* b = static_cast<const unsigned char*>(p);
+  for (size_t i = 0; i < n; ++i) { h ^= b[i]; h *= 1099511628211ull; }
+  return h;
+}
+static uint64_t pack_mask(const taco_model* m) {
+  uint64_t k = 0;
+  auto bit = [&](int b, bool on) { if (on) k |= 1ull << b; };
+  bit(0, m->dx_pack); bit(1, m->dx_p1o_raw); bit(2, m->dx_spkw);
+  for (int q = 0; q < 4; ++q) bit(3 + q, m->dx_qpack[q]);
+  bit(7, m->dbx_pack);
+  const Cbhg* cb[2] = {&m->enc, &m->post};
+  for (int i = 0; i < 2; ++i) {
+    const Cbhg& c = *cb[i];
+    bit(8 + i, c.gd_pack && c.go_pack[0] && c.go_pack[1] && c.go_pack[2]);
+    bit(10 + i, c.gb_pack && c.gob_pack);
+    bit(12 + i, c.front_kind != 0);
+    bit(20, c.res_g2p[0] && c.res_g2p[1] && c.res_c1p[0] && c.res_c1p[1]);
+  }
+  for (auto& kv : m->convs) bit(14, kv.second.wtail);
+  bit(15, !m->spk_table.empty()); bit(16, !m->spk_dense.empty());
+  bit(17, m->att_b); bit(18, m->att_sb); bit(19, m->gru1_fold.gx.wp);
+  return k;
+}
+int taco_debug_pack_host(const taco_hparams* hp, int shadow, const float* flat_weights, size_t n_floats, uint64_t out[5]) {
+  if (!hp || !out || (shadow != 0) != (flat_weights == nullptr)) return fail(TACO_ERR_ARG, "bad argument (a shadow model takes no weights)");
+  taco_train* t = new taco_train();
+  int rc = taco_model_create(hp, 0, &t->sm);
+  if (rc != 0) { delete t; return rc; }
+  taco_model* m = t->sm;
+  if (shadow) rc = train_shadow_weights(t);
+  else {
+    size_t total = 0;
+    for (auto& s : m->spec) { size_t cnt = 1; for (int64_t d : s.second) cnt *= (size_t)d; total += cnt; }
+    if (n_floats != total) rc = fail(TACO_ERR_SHAPE, "%zu floats, the spec holds %zu", n_floats, total);
+    for (size_t i = 0, off = 0; rc == 0 && i < m->spec.size(); ++i) {
+      HostTensor& ht = m->raw[m->spec[i].first];
+      ht.shape = m->spec[i].second;
+      size_t cnt = 1; for (int64_t d : ht.shape) cnt *= (size_t)d;
+      ht.data.assign(flat_weights + off, flat_weights + off + cnt); ht.set = true;
+      off += cnt;
+    }
+  }
+  if (rc == 0) rc = model_pack_host(m);
+  if (rc == 0) {
+    out[0] = m->harena.size();
+    out[1] = fnv1a64(m->harena.data(), m->harena.size() * sizeof(float));
+    out[2] = fnv1a64(m->hvars.data(), m->hvars.size() * sizeof(GemmVar));
+    out[3] = (m->bf3_idx.empty() && m->bf3_segs.empty()) ? 0
+             : fnv1a64(m->bf3_segs.data(), m->bf3_segs.size() * sizeof(Bf3Seg), fnv1a64(m->bf3_idx.data(), m->bf3_idx.size() * sizeof(unsigned)));
+    out[4] = pack_mask(m);
+  }
+  taco_train_destroy(t);
+  return rc;
 }
 size_t taco_train_num_params(const taco_train* t) { return t ? t->NP : 0; }
 
