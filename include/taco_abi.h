@@ -201,6 +201,18 @@ int taco_gru_cell_f32(taco_model* m, void* hip_stream, const char* name, const f
  * d_seq_len[b] = len(sequence) of the row (tokens incl. EOS and padding, as the reference passes it).  d_spec_end [B]. */
 int taco_attention_trim(void* hip_stream, const float* d_alignments, const int32_t* d_seq_len, int B, int T_in, int n_steps,
                         int reduction_factor, int32_t* d_spec_end);
+/* the alignments of the second pass of the reference's two-pass synthesis (synthesizer.py:171-205, manual_attention_mode 1 and 3), built
+ * from the first pass's d_alignments [B, T_in, n_steps] as the forward writes them into d_manual [B, n_steps, T_in], the layout the
+ * forward's d_manual_alignments takes.  Per batch row and ENCODER position e, d* = argmax over the DECODER steps of d_alignments[b, e, :]
+ * (the reference's axis: alignments[idx].argmax(1)): the first index of the maximum wins, a NaN counts as the maximum and the first NaN
+ * wins (NumPy's rule), +0 and -0 compare equal.  d_manual[b, d, e] = 1 where d == d*; elsewhere +0 (mode 1, "argmax one hot") or the
+ * bits of d_alignments[b, e, d] (mode 3, "prunning").  Padding positions e >= input_length get their one too, as in the reference; a
+ * decoder step may end up with no one or with several.  One launch that writes every element of d_manual exactly once: no memset,
+ * no atomics, deterministic; n_steps and T_in are not bounded by the kernel.
+ * Checked before any HIP call: a null pointer, B, T_in or n_steps < 1, overlapping byte ranges of the two buffers, a mode other than
+ * 1, 2, 3 -> TACO_ERR_ARG; mode 2 -> TACO_ERR_UNSUPPORTED: the reference calls np.pow there, which does not exist (synthesizer.py:181-188),
+ * so mode 2 is refused rather than guessed at. */
+int taco_manual_alignments(void* hip_stream, const float* d_alignments, int B, int T_in, int n_steps, int mode, float* d_manual);
 /* The stop rule (helpers.py:29 + dynamic_decode: the loop ends after the first step at which every row has emitted an all-zero
  * step) evaluated on a finished mel buffer d_mel [B, n_steps, width = r*num_mels] per group of rows_per_group consecutive rows:
  * d_stop[B / rows_per_group].  For requests that were served together through one plan (PlanPool coalesce > 1), whose plan-wide

@@ -17,6 +17,7 @@
 // and the TF 1.4 ops they call); each kernel cites the reference lines it implements.
 #pragma once
 #include <hip/hip_runtime.h>
+#include <limits.h>
 #include <stdint.h>
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
@@ -2003,6 +2004,81 @@ __global__ __launch_bounds__(64) void k_attention_trim(const float* align, const
       } else break;
     }
     spec_end[b] = r * jdx + 3;
+  }
+}
+
+// The alignments of the reference's second synthesis pass (synthesizer.py:171-205, manual_attention_mode 1 and 3) from the first pass's:
+// A [B, T_in, n] -> O [B, n, T_in].  For every encoder position e, d* = np.argmax(A[b, e, :]) over DECODER steps (the reference's axis): the
+// first index of the maximum, a NaN counting as the maximum (the first NaN wins), +0 == -0.  O[b, d, e] = 1 where d == d*(b, e); elsewhere
+// +0 (mode 1) or the bits of A[b, e, d] (mode 3).  Padding positions get their one too, as in the reference.
+// A workgroup of 8 waves owns MA_TE encoder positions of one batch row over every step, and writes each of its elements of O exactly once:
+// no memset, no atomics.  Phase 1: a wave takes MA_ROWS positions at a time (their loads and reductions are independent, so they overlap),
+// lanes stride d (contiguous), butterfly reduction that prefers the greater value and on equal values the smaller index.  Phase 2: tiles
+// of MA_TE positions x MA_TD steps of A go through LDS (rows padded to MA_TD + 1 words: the transposed read of position e at step d is
+// bank (e + d) % 32, conflict-free within a half wave) so that the read runs along d and the write along e, a half wave per step (128 B).
+// Mode 1 needs no values and skips the tile.  The loop over d bounds nothing by LDS size.
+#define MA_TE 32
+#define MA_TD 64
+#define MA_ROWS 4
+__device__ __forceinline__ bool ma_beats(float a, float b) { return a > b || (a != a && b == b); }      // NaN above every number
+// (a, ia) before (b, ib) in np.argmax's order: the greater value, on equal values (or two NaNs) the smaller index.  Indices never tie.
+__device__ __forceinline__ bool ma_wins(float a, int ia, float b, int ib) { return ma_beats(a, b) | (!ma_beats(b, a) & (ia < ib)); }
+__global__ __launch_bounds__(512) void k_manual_alignments(const float* __restrict__ A, int T_in, int n, int tiles, int mode, float* __restrict__ O) {
+  __shared__ int dstar[MA_TE];
+  __shared__ unsigned tile[MA_TE][MA_TD + 1];
+  const int b = blockIdx.x / tiles, e0 = (blockIdx.x - b * tiles) * MA_TE;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int ne = min(MA_TE, T_in - e0);
+  const float* Ab = A + ((size_t)b * T_in + e0) * n;          // [ne, n]
+  float* Ob = O + (size_t)b * n * T_in + e0;                  // [n, T_in] from column e0
+  {
+    const float* row[MA_ROWS];
+    // a lane that has seen nothing (n < 64) holds (-inf, INT_MAX): it loses to every real element, to -inf by its index, to NaN by ma_beats
+    float best[MA_ROWS]; int arg[MA_ROWS];
+#pragma unroll
+    for (int r = 0; r < MA_ROWS; ++r) {                       // a position past the tile's last re-reads the last one; its result is dropped
+      row[r] = Ab + (size_t)min(wave * MA_ROWS + r, ne - 1) * n; best[r] = -INFINITY; arg[r] = INT_MAX;
+    }
+    for (int d = lane; d < n; d += 64) {
+      float v[MA_ROWS];
+#pragma unroll
+      for (int r = 0; r < MA_ROWS; ++r) v[r] = row[r][d];
+#pragma unroll
+      for (int r = 0; r < MA_ROWS; ++r) {                     // ascending d: the first maximum stays (d < arg only for the lane's first element)
+        const bool take = ma_wins(v[r], d, best[r], arg[r]);
+        best[r] = take ? v[r] : best[r]; arg[r] = take ? d : arg[r];
+      }
+    }
+    // (selects, not `if (...) { best[r] = ov; arg[r] = oa; }`: with the four rows unrolled that form compiled to code that never took the
+    // other lane's pair (ROCm 7.2 hipcc, -O3) -- tests/test_gpu_manual.py caught it on the first reference run)
+    for (int off = 32; off; off >>= 1) {
+#pragma unroll
+      for (int r = 0; r < MA_ROWS; ++r) {
+        const float ov = __shfl_xor(best[r], off); const int oa = __shfl_xor(arg[r], off);
+        const bool take = ma_wins(ov, oa, best[r], arg[r]);
+        best[r] = take ? ov : best[r]; arg[r] = take ? oa : arg[r];
+      }
+    }
+#pragma unroll
+    for (int r = 0; r < MA_ROWS; ++r)
+      if (lane == 0 && wave * MA_ROWS + r < ne) dstar[wave * MA_ROWS + r] = arg[r];
+  }
+  __syncthreads();
+  const int el = lane & 31, half = lane >> 5;                 // a half wave per step: position el of step 2 * k + half
+  const int mine = el < ne ? dstar[el] : -1;
+  for (int d0 = 0; d0 < n; d0 += MA_TD) {
+    const int nd = min(MA_TD, n - d0);
+    if (mode == 3) {
+      for (int r = wave; r < ne; r += 8)
+        if (lane < nd) tile[r][lane] = __float_as_uint(Ab[(size_t)r * n + d0 + lane]);
+      __syncthreads();
+    }
+    if (el < ne)
+      for (int dl = 2 * wave + half; dl < nd; dl += 16) {
+        const unsigned bits = mine == d0 + dl ? 0x3f800000u : mode == 3 ? tile[el][dl] : 0u;
+        Ob[(size_t)(d0 + dl) * T_in + el] = __uint_as_float(bits);
+      }
+    if (mode == 3) __syncthreads();
   }
 }
 

@@ -1874,6 +1874,22 @@ int taco_attention_trim(void* hip_stream, const float* d_alignments, const int32
   return 0;
 }
 
+int taco_manual_alignments(void* hip_stream, const float* d_alignments, int B, int T_in, int n_steps, int mode, float* d_manual) {
+  if (!d_alignments || !d_manual) return fail(TACO_ERR_ARG, "null pointer");
+  if (B < 1 || T_in < 1 || n_steps < 1) return fail(TACO_ERR_ARG, "B, T_in and n_steps must be >= 1, got %d, %d, %d", B, T_in, n_steps);
+  const unsigned __int128 bytes = (unsigned __int128)B * (unsigned)T_in * (unsigned)n_steps * sizeof(float);
+  const unsigned __int128 in = (uintptr_t)d_alignments, out = (uintptr_t)d_manual;
+  if (in < out + bytes && out < in + bytes) return fail(TACO_ERR_ARG, "d_alignments and d_manual overlap: the transpose cannot run in place");
+  if (mode == 2) return fail(TACO_ERR_UNSUPPORTED, "manual_attention_mode 2 is broken in the reference (np.pow, synthesizer.py:181-188)");
+  if (mode != 1 && mode != 3) return fail(TACO_ERR_ARG, "manual_attention_mode %d: accepted are 1 (argmax one hot) and 3 (prunning)", mode);
+  const int tiles = (T_in + MA_TE - 1) / MA_TE;
+  if ((long long)B * tiles > 0x7fffffffLL) return fail(TACO_ERR_UNSUPPORTED, "more than 2^31 - 1 workgroups (B * ceil(T_in / %d))", MA_TE);
+  hipLaunchKernelGGL(k_manual_alignments, dim3((unsigned)(B * tiles)), dim3(MA_TE / MA_ROWS * 64), 0, (hipStream_t)hip_stream, d_alignments, T_in, n_steps, tiles, mode,
+                     d_manual);
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
 int taco_stop_steps(void* hip_stream, const float* d_mel, int B, int n_steps, int width, int rows_per_group, int32_t* d_stop) {
   if (!d_mel || !d_stop || B <= 0 || n_steps <= 0 || width <= 0 || rows_per_group <= 0 || B % rows_per_group)
     return fail(TACO_ERR_ARG, "bad argument");

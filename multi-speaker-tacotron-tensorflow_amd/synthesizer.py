@@ -4,8 +4,8 @@ Kept: load() / synthesize() / close() names and arguments; token -> input_length
 (synthesizer.py:120); default speaker id zeros (:43-44); speaker mixtures (`speaker_ids` a dict {id: weight},
 :153-164 -- a branch that never ran in the reference; its intent, the sum of weight * speaker_embed_table[id], is served by the
 library's _mix entry points); the (linear_outputs, alignments) fetch pair
-(:122-126,166-167); manual-attention second pass for modes 1 and 3 (:171-205; mode 2 is broken in the
-reference: np.pow does not exist); text -> ids with the Korean normaliser (text.py, korean.py); the attention trim
+(:122-126,166-167); manual-attention second pass for modes 1 and 3 (:171-205; its alignments are built on the device from the
+first pass's, Tacotron.run(manual_attention_mode=); mode 2 is broken in the reference: np.pow does not exist); text -> ids with the Korean normaliser (text.py, korean.py); the attention trim
 (:242-262, device kernel) and, with vocode=True, the spectrogram -> waveform step on the GPU (audio.py),
 followed by the silence trim of librosa_trim=True (:266-269, device kernels; without vocode there is no audio and it is a no-op).
 Out of scope: plots, wav / npy file output, sentence concatenation -- `synthesize` returns the model
@@ -131,16 +131,13 @@ class Synthesizer(object):
             alignment_path = os.path.join(base_alignment_path, os.path.basename(base_path))
             loaded = [np.load("{}.{}.npy".format(alignment_path, idx)) for idx in range(len(sequences))]
             manual_alignments = np.transpose(loaded, [0, 2, 1])
+        # manual_attention_mode > 0 (:171-205): the second pass runs inside run(), its alignments built on the device from the first
+        # pass's (k_manual_alignments; manual_alignments_of above is the host restatement).  Only the pass that is returned is downloaded
         linear, alignments = self.model.run(
             inputs=sequences.astype(np.int32), input_lengths=input_lengths, **speaker,
-            manual_alignments=manual_alignments, is_manual_attention=manual_alignments is not None)
+            manual_alignments=manual_alignments, is_manual_attention=manual_alignments is not None,
+            manual_attention_mode=manual_attention_mode)
         linear, alignments = linear.cpu().numpy(), alignments.cpu().numpy()
-        if manual_attention_mode > 0:                                                    # :171-205
-            new_alignments = manual_alignments_of(alignments, manual_attention_mode)
-            linear, alignments = self.model.run(
-                inputs=sequences.astype(np.int32), input_lengths=input_lengths, **speaker,
-                manual_alignments=new_alignments, is_manual_attention=True)
-            linear, alignments = linear.cpu().numpy(), alignments.cpu().numpy()
         # attention_trim (:242-262): frames to keep per utterance, from the argmax walk over the alignments (device kernel)
         self.spec_end_idx = None
         if attention_trim and end_of_sentence:
@@ -155,7 +152,8 @@ class Synthesizer(object):
         return linear, alignments
 
     def synthesize_audio(self, texts=None, tokens=None, speaker_ids=None, end_of_sentence=True, attention_trim=True,
-                         manual_alignments=None, seed=0, iters=None, pcm=True, librosa_trim=False, vocoder="griffin_lim"):
+                         manual_alignments=None, seed=0, iters=None, pcm=True, librosa_trim=False, vocoder="griffin_lim",
+                         manual_attention_mode=0):
         """The reference's synthesize -> plot_graph_and_save_audio chain up to the samples save_audio writes (synthesizer.py:119-126,
         242-264; audio/__init__.py:22-25), everything between the token upload and the audio download on the device: the forward, the
         attention trim on the device alignments, Griffin-Lim on every utterance's own frames read from the trim kernel's output, the
@@ -171,8 +169,15 @@ class Synthesizer(object):
         inv_spectrogram_tensorflow (audio/__init__.py:59-61), the reference's Synthesizer.wav_output (synthesizer.py:53-54), with the
         attention trim's frame counts: deterministic, `seed` is not used.  "mel" runs model.mel_outputs -- what the decoder produced
         before the post-net -- through inv_melspectrogram (:70-72).  Both UNPINNED (include/taco_abi.h).  pcm, librosa_trim and the
-        returned list behave the same for all three; any other name raises TacoError(TACO_ERR_ARG)."""
+        returned list behave the same for all three; any other name raises TacoError(TACO_ERR_ARG).
+        manual_attention_mode 1 or 3 (synthesizer.py:171-205): the two-pass synthesis of `synthesize`, still without leaving the device
+        -- forward, the second pass's alignments from the first pass's (Tacotron.manual_alignments_from), second forward -- and the trim,
+        the vocoder and the PCM step then run on the second pass.  It excludes an explicit `manual_alignments` (TacoError(TACO_ERR_ARG));
+        mode 2 raises as manual_alignments_of does."""
         from . import _lib
+        if manual_attention_mode > 0 and manual_alignments is not None:
+            raise _lib.TacoError(_lib.TACO_ERR_ARG, "manual_attention_mode builds the second pass's alignments itself: it cannot be "
+                                 "combined with manual_alignments")
         if vocoder not in ("griffin_lim", "tensorflow", "mel"):
             raise _lib.TacoError(_lib.TACO_ERR_ARG, "vocoder must be 'griffin_lim', 'tensorflow' or 'mel', got %r" % (vocoder,))
         sequences = self._token_rows(texts, tokens)
@@ -180,7 +185,8 @@ class Synthesizer(object):
         speaker = self._speaker_feed(speaker_ids, len(sequences))
         linear, alignments = self.model.run(
             inputs=sequences.astype(np.int32), input_lengths=input_lengths, **speaker,
-            manual_alignments=manual_alignments, is_manual_attention=manual_alignments is not None)
+            manual_alignments=manual_alignments, is_manual_attention=manual_alignments is not None,
+            manual_attention_mode=manual_attention_mode)
         frames = None
         if attention_trim and end_of_sentence:
             frames = self._attention_trim_device(alignments, [len(seq) for seq in sequences])

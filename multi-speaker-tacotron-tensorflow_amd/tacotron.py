@@ -564,15 +564,53 @@ class Tacotron(object):
         """`lanes` forwards of this shape in flight at once, each serving `coalesce` requests of B rows (PlanPool)."""
         return PlanPool(self, B, T_in, n_steps, lanes, coalesce, engine, speaker_mix)
 
+    def _stop_of(self, plan):
+        """The stop word of the plan's last forward.  It doubles as the forward's error latch (negative: a persistent kernel gave up,
+        taco_abi.h); reading it is the one host sync of a forward, with or without honor_stop."""
+        stop = int(plan.stop.item())
+        if stop < 0:
+            self.check_device_errors()
+            raise _lib.TacoError(_lib.TACO_ERR_HIP, "a persistent kernel reported error %d; outputs are invalid" % -stop)
+        return stop
+
+    def manual_alignments_from(self, alignments, mode, out=None):
+        """The second pass's `manual_alignments` [B, n, T_in] from a first pass's `alignments` [B, T_in, n] (synthesizer.py:171-205, modes 1
+        and 3), built on the device by taco_manual_alignments: what synthesizer.manual_alignments_of does on the host, bit for bit.
+        `out`: a float32 device tensor of that shape to write into (a plan's static `manual` buffer); it must not share memory with
+        `alignments`.  Asynchronous on the current stream.  Mode 2 raises the Exception of manual_alignments_of."""
+        if mode == 2:
+            raise Exception("manual_attention_mode 2 is broken in the reference (np.pow, synthesizer.py:181-188)")
+        if self._handle is None:
+            raise RuntimeError("initialize() must be called first")
+        al = self._as_dev(alignments, torch.float32)
+        if al.dim() != 3:
+            raise Exception("alignments must be [B, T_in, T_dec], got shape %s" % (tuple(al.shape),))
+        B, T_in, n = al.shape
+        if out is None:
+            out = torch.empty((B, n, T_in), dtype=torch.float32, device=al.device)
+        elif tuple(out.shape) != (B, n, T_in) or out.dtype != torch.float32 or out.device != al.device or not out.is_contiguous():
+            raise Exception("out must be a contiguous float32 tensor [B, T_dec, T_in] = %s on %s" % ((B, n, T_in), al.device))
+        with torch.cuda.device(al.device):
+            _lib.check(self._lib.taco_manual_alignments(_stream(), _ptr(al), B, T_in, n, int(mode), _ptr(out)))
+        return out
+
     def run(self, inputs=None, input_lengths=None, speaker_id=None, manual_alignments=None,
-            is_manual_attention=None, n_steps=None, honor_stop=True, speaker_weights=None):
+            is_manual_attention=None, n_steps=None, honor_stop=True, speaker_weights=None, manual_attention_mode=0):
         """One forward.  Returns (linear_outputs, alignments) as device tensors and refreshes the
         public attributes.  `manual_alignments` [B,T_dec,T_in] + `is_manual_attention`
         (rnn_wrappers.py:313-317).  With honor_stop the outputs are cut where the reference's stop rule
         (helpers.py:29 + dynamic_decode) would have ended the loop (one host sync).  `speaker_weights` [B, num_speakers] (see
-        speaker_weights()) blends the trained speakers per row, the intent of synthesizer.py:153-164; it excludes `speaker_id`."""
+        speaker_weights()) blends the trained speakers per row, the intent of synthesizer.py:153-164; it excludes `speaker_id`.
+        manual_attention_mode 1 or 3: the reference's two-pass synthesis (synthesizer.py:171-205).  The forward above is the first pass;
+        its alignments go through manual_alignments_from() straight into the `manual` buffer of the manual plan of the same shape, whose
+        staged inputs and speaker feed are copied device to device from the first plan, and that plan's forward is what is returned.
+        Nothing of the first pass is read on the host but its stop word; its alignments stay in `first_pass_alignments` (the reference
+        saves both passes).  A first pass that the stop rule cut short raises the shape Exception a shorter `manual_alignments` raises;
+        mode 2 raises as manual_alignments_of does."""
         if self._handle is None:
             raise RuntimeError("initialize() must be called first")
+        if manual_attention_mode == 2:
+            raise Exception("manual_attention_mode 2 is broken in the reference (np.pow, synthesizer.py:181-188)")
         if speaker_weights is not None and speaker_id is not None:
             raise _lib.TacoError(_lib.TACO_ERR_ARG, "speaker_id and speaker_weights are mutually exclusive")
         inputs = self.inputs if inputs is None else inputs
@@ -609,14 +647,28 @@ class Tacotron(object):
                                     % (tuple(plan.manual.shape), tuple(ma.shape)))
                 plan.manual.copy_(ma)
             plan.launch()
+            stop = self._stop_of(plan)
+            self.first_pass_alignments = None
+            if manual_attention_mode > 0:                                              # synthesizer.py:171-205
+                if honor_stop and stop < plan.n:     # the first pass's alignments are [B, T_in, stop]: not the second pass's shape
+                    raise Exception("manual_alignments must be [B, T_dec, T_in] = %s, got %s"
+                                    % ((B, plan.n, T_in), (B, stop, T_in)))
+                first, plan = plan, self.plan_for(B, T_in, n_steps, True, mix)
+                if plan is first:                    # the first pass ran on manual alignments itself: its outputs are about to be overwritten
+                    self.first_pass_alignments = first.align.clone()
+                else:
+                    self.first_pass_alignments = first.align
+                    plan.inputs.copy_(first.inputs)
+                    plan.lengths.copy_(first.lengths)
+                    if mix:
+                        plan.speaker_weights.copy_(first.speaker_weights)
+                    elif self.num_speakers > 1:
+                        plan.speaker_id.copy_(first.speaker_id)
+                self.manual_alignments_from(first.align, manual_attention_mode, out=plan.manual)
+                plan.launch()
+                stop = self._stop_of(plan)
             mel, linear, align = plan.mel, plan.linear, plan.align
             self.stop_step = plan.n
-            # the stop word doubles as the forward's error latch (negative: a persistent kernel gave up, taco_abi.h); reading it is
-            # the one host sync of a run(), with or without honor_stop
-            stop = int(plan.stop.item())
-            if stop < 0:
-                self.check_device_errors()
-                raise _lib.TacoError(_lib.TACO_ERR_HIP, "a persistent kernel reported error %d; outputs are invalid" % -stop)
             if honor_stop:
                 self.stop_step = stop
                 if stop < plan.n:   # dynamic_decode ended early: re-run the post-net on the frames that exist
