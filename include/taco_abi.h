@@ -70,7 +70,12 @@ int taco_model_finalize(taco_model* m); /* repack: MFMA fragment layouts, BN -> 
 void taco_model_destroy(taco_model* m);
 
 /* ---- whole forward: replaces sess.run([linear_outputs, alignments]) at synthesizer.py:166-167
- *      over the graph of models/tacotron.py:29-239 (inference, is_training False). */
+ *      over the graph of models/tacotron.py:29-239 (inference, is_training False).
+ * Any B: more rows than one pass holds (64; 32 for an inference model with attention_size 512) run as passes of equal size over ONE
+ * pass's workspace, with the passes' stop words carved behind it -- taco_workspace_bytes counts both.  The arguments are validated once,
+ * before the batch is split: a null model or buffer, a bad shape, a missing speaker_id, a model not finalized and a workspace too small
+ * get the same code and message at every B (a call of more than 64 rows with such an argument used to be answered "batch ... > 64 rows
+ * per device is not supported" or "bad time ... / steps ..."). */
 size_t taco_workspace_bytes(const taco_model* m, int B, int T_in, int n_steps);
 
 int taco_forward_infer(taco_model* m, void* hip_stream,
@@ -149,7 +154,10 @@ int taco_decoder_forward_mix(taco_model* m, void* hip_stream, const float* d_enc
 int taco_postnet_forward_mix(taco_model* m, void* hip_stream, const float* d_mel, const float* d_speaker_weights, int B, int T_mel,
                              float* d_linear, float* d_post_out, void* d_workspace, size_t workspace_bytes);
 
-/* ---- stage-level entry points (parity tests, profiling) ---- */
+/* ---- stage-level entry points (parity tests, profiling) ----
+ * Any B, validated once and served as passes like the whole forward (above); taco_decoder_forward combines the passes' stop words, and
+ * refuses d_dbg_states with more than 64 rows (the dump is laid out [step][row]: one pass).  taco_stage_workspace_bytes(m, B, T) is
+ * enough for each of the three at (B, T) -- the decoder with T_in = n_steps = T, with or without d_dbg_states, stop words included. */
 /* embedding -> prenet -> encoder CBHG (tacotron.py:34-112).  d_encoder_out [B,T_in,2*enc_rnn_size]. */
 int taco_encoder_forward(taco_model* m, void* hip_stream, const int32_t* d_inputs,
                          const int32_t* d_input_lengths, const int32_t* d_speaker_id, int B, int T_in,

@@ -31,7 +31,9 @@ int taco_debug_set_persistent(taco_model* m, int on);
  * A forced tile that a launch has no instantiation for is answered by gemm_plan (csrc/taco_lib.hip): tile 10 exists at three products for
  * one weight matrix only, so a highway layer or a six-product launch under it runs tile 7; a six-product highway layer under tile 5 runs tile 4.
  * on bit 2 (on = 5): the point-wise tail of a CBHG ([dense ->] highway x depth -> BiGRU input projection; modules.py:72-96) runs as
- * one launch per layer instead of ONE launch with the activations resident on the CU (csrc/taco_chain.h, the default with on = 1).
+ * one launch per layer instead of ONE launch with the activations resident on the CU (csrc/taco_chain.h, the default with on = 1).  The
+ * encoder prenet then runs as one GEMM launch per layer too, and the forward's zero fills -- riders of its chain launch otherwise -- as
+ * one launch of k_zero_fill in front.
  * on bit 3 (on = 9): conv bank and proj_1 of a CBHG as two launches instead of the fused front (csrc/taco_front.h).
  * on bit 4 (on = 17): with the fused front, proj_1's epilogue (k_front_combine) and proj_2 as launches of their own instead of the fused
  * entry of the point-wise chain (csrc/taco_chain.h).

@@ -38,6 +38,7 @@
 #define CH_ROT 1
 #endif
 #define CH_BM 64
+constexpr int CH_RIDERS = 4;       // regions a launch's spare workgroups clear (ChainArgs::zp / znw): the words a forward's persistent kernels poll (forward_pass lists them)
 enum { CH_DENSE = 0, CH_HIGHWAY = 1, CH_XPROJ = 2 };
 struct ChainLayer {
   const unsigned short* bh; const unsigned short* bl; const unsigned short* bh2; const unsigned short* bl2;   // split-bf16 packs (pack_bf3)
@@ -65,9 +66,9 @@ struct ChainArgs {
   const int* rev_len; int rev_col0;
   int M, T, nlayers;
   int krot;                        // 1: workgroups start their K loops at different steps (CH_ROT, the default); 0: every tile walks K from step 0
-  // riders: with ntiles > 0 the workgroups ntiles .. gridDim.x - 1 own no tile; they clear up to four regions of 32-bit words (the words the
+  // riders: with ntiles > 0 the workgroups ntiles .. gridDim.x - 1 own no tile; they clear up to CH_RIDERS regions of 32-bit words (the words the
   // persistent kernels of the same forward poll: a launch of its own otherwise -- the encoder prenet's chain leaves three quarters of the CUs free)
-  int ntiles; unsigned* zp[4]; unsigned long long znw[4];
+  int ntiles; unsigned* zp[CH_RIDERS]; unsigned long long znw[CH_RIDERS];
   ChainLayer L[CH_MAXL];
 };
 
@@ -175,7 +176,7 @@ __global__ __launch_bounds__(512) void k_pointwise_chain(const ChainArgs a_in) {
   const int wm = wave / WN, wn = wave % WN;
   if (a_in.ntiles > 0 && (int)blockIdx.x >= a_in.ntiles) {
     const size_t i0 = (size_t)((int)blockIdx.x - a_in.ntiles) * 512 + tid, stride = (size_t)((int)gridDim.x - a_in.ntiles) * 512;
-    for (int rg = 0; rg < 4; ++rg) {
+    for (int rg = 0; rg < CH_RIDERS; ++rg) {
       unsigned* p = a_in.zp[rg];
       const size_t nw = a_in.znw[rg];
       if (!p || !nw) continue;

@@ -82,17 +82,12 @@ struct ChipTurn {
 
 // Stream-ordered zero fill as a kernel launch.  hipMemsetAsync nodes of a captured graph were seen to fill with a stale 16-byte
 // pattern after another plan of the process had been destroyed (round 2: the census words and the exchange tags of a decoder plan,
-// the BatchNorm sums of a captured train step); a kernel node has no such state.  p 4-byte aligned, bytes a multiple of 4.
-__global__ __launch_bounds__(256) void k_zero_fill(uint32_t* __restrict__ p, size_t n16, size_t nw) {
-  const size_t i0 = (size_t)blockIdx.x * blockDim.x + threadIdx.x, stride = (size_t)gridDim.x * blockDim.x;
-  uint4* q = reinterpret_cast<uint4*>(p);
-  for (size_t i = i0; i < n16; i += stride) q[i] = make_uint4(0u, 0u, 0u, 0u);
-  for (size_t i = n16 * 4 + i0; i < nw; i += stride) p[i] = 0u;
-}
-// several regions in ONE launch (a forward clears the decoder's exchange buffers, the stop flags and the post-net scan's exchange
-// buffers up front: three fill launches and their graph edges less); every region 4-byte aligned and sized
-struct ZeroRegions { uint32_t* p[4]; unsigned long long nw[4]; };
-__global__ void k_zero_fill_multi(const ZeroRegions z) {
+// the BatchNorm sums of a captured train step); a kernel node has no such state.
+// Up to ZERO_MAX regions in ONE launch, blockIdx.y picks the region (a forward clears every word its persistent kernels poll up front, the
+// backward pass a dozen small accumulators in a row: the fill launches and their graph edges less); every region 4-byte aligned and sized
+#define ZERO_MAX 12
+struct ZeroList { uint32_t* p[ZERO_MAX]; unsigned long long nw[ZERO_MAX]; };
+__global__ __launch_bounds__(256) void k_zero_fill(const ZeroList z) {
   uint32_t* p = z.p[blockIdx.y];
   const size_t nw = z.nw[blockIdx.y];
   const size_t n16 = (reinterpret_cast<uintptr_t>(p) & 15) ? 0 : nw / 4;
@@ -101,59 +96,51 @@ __global__ void k_zero_fill_multi(const ZeroRegions z) {
   for (size_t i = i0; i < n16; i += stride) q[i] = make_uint4(0u, 0u, 0u, 0u);
   for (size_t i = n16 * 4 + i0; i < nw; i += stride) p[i] = 0u;
 }
-// up to ZM_MAX regions in one launch (the backward pass clears a dozen small accumulators in a row)
-#define ZM_MAX 12
-struct ZeroMany { uint32_t* p[ZM_MAX]; unsigned long long nw[ZM_MAX]; };
-__global__ void k_zero_fill_many(const ZeroMany z) {
-  uint32_t* p = z.p[blockIdx.y];
-  const size_t nw = z.nw[blockIdx.y];
-  const size_t n16 = (reinterpret_cast<uintptr_t>(p) & 15) ? 0 : nw / 4;
-  const size_t i0 = (size_t)blockIdx.x * blockDim.x + threadIdx.x, stride = (size_t)gridDim.x * blockDim.x;
-  uint4* q = reinterpret_cast<uint4*>(p);
-  for (size_t i = i0; i < n16; i += stride) q[i] = make_uint4(0u, 0u, 0u, 0u);
-  for (size_t i = n16 * 4 + i0; i < nw; i += stride) p[i] = 0u;
-}
-// Regions a caller up the stack has already cleared on this stream (forward_enqueue: ONE fill launch for every word the persistent kernels of a
-// forward poll).  A stage clears its polled words through clear_polled(): skipped only when exactly that region -- same start, at least as many
-// bytes -- is registered, so a stage whose region changes (or a new stage) clears itself instead of trusting a list kept elsewhere.
-struct ClearedSet { const void* p[8]; size_t n[8]; int cnt; };
-static thread_local ClearedSet g_cleared = {};
-static void register_cleared(const ZeroRegions& z) {      // called by whoever has JUST enqueued the launch that clears z's regions
-  for (int i = 0; i < 4; ++i)
-    if (z.p[i] && g_cleared.cnt < 8) { g_cleared.p[g_cleared.cnt] = z.p[i]; g_cleared.n[g_cleared.cnt++] = z.nw[i] * 4; }
-}
-static hipError_t zero_async(void* p, size_t bytes, hipStream_t st);
-static hipError_t clear_polled(void* p, size_t bytes, hipStream_t st) {
-  for (int i = 0; i < g_cleared.cnt; ++i)
-    if (g_cleared.p[i] == p && g_cleared.n[i] >= bytes) return hipSuccess;
-  return zero_async(p, bytes, st);
-}
-static hipError_t zero_async(void* p, size_t bytes, hipStream_t st) {
+static hipError_t zero_async(void* p, size_t bytes, hipStream_t st) {      // the one-region case
   if (!bytes) return hipSuccess;
   if ((reinterpret_cast<uintptr_t>(p) & 3) || (bytes & 3)) return hipMemsetAsync(p, 0, bytes, st);
   const size_t nw = bytes / 4;
+  ZeroList z; memset(&z, 0, sizeof z);
+  z.p[0] = static_cast<uint32_t*>(p); z.nw[0] = nw;
   const size_t n16 = (reinterpret_cast<uintptr_t>(p) & 15) ? 0 : nw / 4;
   const size_t items = n16 ? n16 + (nw - n16 * 4) : nw;
   const unsigned blocks = (unsigned)std::min<size_t>((items + 255) / 256, 2048);
-  hipLaunchKernelGGL(k_zero_fill, dim3(blocks), dim3(256), 0, st, static_cast<uint32_t*>(p), n16, nw);
+  hipLaunchKernelGGL(k_zero_fill, dim3(blocks), dim3(256), 0, st, z);
   return hipGetLastError();
 }
+// The regions a caller up the stack clears with ONE launch (forward_pass: every word the persistent kernels of a forward poll; the first CH_RIDERS
+// entries of z).  It lives on that caller's stack; `enqueued` is set by whoever has JUST put that launch into the stream -- never before.
+struct UpFrontClear {
+  ZeroList z; bool enqueued = false;
+  bool covers(const void* q, size_t bytes) const {
+    for (int i = 0; enqueued && i < CH_RIDERS; ++i)
+      if (z.p[i] == q && z.nw[i] * 4 >= bytes) return true;
+    return false;
+  }
+};
+// Words a persistent kernel polls: zero when it is launched.  The stage that launches it clears them through clear(): skipped only when exactly this
+// region -- same start, at least as many bytes -- is in the caller's launch, so a stage whose region changes (or a new stage) clears itself instead of
+// trusting a list kept elsewhere.  cleared is null wherever a stage runs on its own: a stage entry, the training step, a debug hook.
+struct Polled {
+  void* p = nullptr; size_t bytes = 0; const UpFrontClear* cleared = nullptr;
+  hipError_t clear(hipStream_t st) const { return cleared && cleared->covers(p, bytes) ? hipSuccess : zero_async(p, bytes, st); }
+};
 
 // collects zero fills that follow one another on a stream and issues them as one launch (run() -- also from the destructor's caller)
 struct ZeroBatch {
-  ZeroMany z; int n = 0; size_t big = 0; hipStream_t st;
+  ZeroList z; int n = 0; size_t big = 0; hipStream_t st;
   explicit ZeroBatch(hipStream_t s) : st(s) { memset(&z, 0, sizeof z); }
   hipError_t add(void* p, size_t bytes) {
     if (!bytes) return hipSuccess;
     if ((reinterpret_cast<uintptr_t>(p) & 3) || (bytes & 3)) return zero_async(p, bytes, st);
-    if (n == ZM_MAX) { hipError_t e = run(); if (e != hipSuccess) return e; }
+    if (n == ZERO_MAX) { hipError_t e = run(); if (e != hipSuccess) return e; }
     z.p[n] = static_cast<uint32_t*>(p); z.nw[n] = bytes / 4; big = std::max(big, bytes / 16); ++n;
     return hipSuccess;
   }
   hipError_t run() {
     if (!n) return hipSuccess;
     const unsigned blocks = (unsigned)std::min<size_t>(std::max<size_t>((big + 255) / 256, 1), 1024);
-    hipLaunchKernelGGL(k_zero_fill_many, dim3(blocks, n), dim3(256), 0, st, z);
+    hipLaunchKernelGGL(k_zero_fill, dim3(blocks, n), dim3(256), 0, st, z);
     n = 0; big = 0; memset(&z, 0, sizeof z);
     return hipGetLastError();
   }
@@ -679,7 +666,14 @@ struct Carver {
   bool ok() const { return !base || off <= cap; }
 };
 
-struct CbhgWs { float *bank, *p[4], *hi0, *hi1, *xproj, *h, *rh, *u; unsigned long long* gxbuf; size_t gxbuf_bytes; unsigned* gxctl; };
+// The exchange of a whole-chip persistent kernel: its granules and, carved back to back behind them, 256 bytes of census words -- all of it polled
+struct Xchg : Polled {
+  void carve(Carver& cv, size_t granules) { bytes = rup_sz(granules * sizeof(unsigned long long), 256) + 256; p = cv.raw(bytes); }
+  unsigned long long* buf() const { return static_cast<unsigned long long*>(p); }
+  unsigned* ctl() const { return p ? reinterpret_cast<unsigned*>(static_cast<char*>(p) + bytes - 256) : nullptr; }
+};
+
+struct CbhgWs { float *bank, *p[4], *hi0, *hi1, *xproj, *h, *rh, *u; Xchg gx; };
 static void carve_cbhg(Carver& cv, const Cbhg& c, int B, int T, CbhgWs& w) {
   const size_t M = (size_t)B * T;
   w.bank = cv.f(M * c.K * c.C);
@@ -688,10 +682,8 @@ static void carve_cbhg(Carver& cv, const Cbhg& c, int B, int T, CbhgWs& w) {
   w.xproj = cv.f(M * 6 * c.rnn);
   w.h = cv.f((size_t)2 * B * c.rnn); w.rh = cv.f((size_t)2 * B * c.rnn); w.u = cv.f((size_t)2 * B * c.rnn);
   // exchange granules of the whole-chip forward scans: k_bigru_duo at its 8 rows per group needs the most (a training tape carves its own)
-  static_assert(gd_xbuf_granules(8) == (size_t)16 * 2 * 8 * 256 && gd_xbuf_granules(8) >= go_xbuf_granules(), "gxbuf holds the granules of k_bigru_duo<8> and of k_bigru_oct");
-  w.gxbuf_bytes = gd_xbuf_granules(8) * sizeof(unsigned long long);
-  w.gxbuf = (unsigned long long*)cv.raw(w.gxbuf_bytes);
-  w.gxctl = (unsigned*)cv.raw(256);
+  static_assert(gd_xbuf_granules(8) == (size_t)16 * 2 * 8 * 256 && gd_xbuf_granules(8) >= go_xbuf_granules(), "gx holds the granules of k_bigru_duo<8> and of k_bigru_oct");
+  w.gx.carve(cv, gd_xbuf_granules(8));
 }
 
 // Row-parallel persistent BiGRU: R rows per workgroup.  Returns false when it does not fit.
@@ -793,13 +785,13 @@ static void oct_launch_upw(int UPW, dim3 grid, dim3 blk, size_t lds, hipStream_t
 }
 // both directions of RG rows on one group of 32 CUs, software-pipelined against each other; gsave != null: the TAPE instantiation
 static int duo_launch(const taco_model* m, hipStream_t st, const Cbhg& c, int RG, int B, int T, const float* xproj, const int* lengths, const float* init_state,
-                      float* out, float* gsave, unsigned long long* gxbuf, unsigned* gxctl) {
+                      float* out, float* gsave, const Xchg& gx) {
   ChipTurn turn(m->device, st);
   GdArgs a; memset(&a, 0, sizeof a);
   a.wpack = AP(m, c.gd_pack); a.xproj = xproj; a.h0 = init_state; a.lengths = lengths; a.out = out; a.gsave = gsave;
-  a.xbuf = gxbuf; a.ctl = gxctl; a.err = m->d_err; a.trace = (m->trace_on && m->d_trace && !gsave) ? m->d_trace + DX_TRACE_STEPS * DX_TRACE_SLOTS : nullptr;
+  a.xbuf = gx.buf(); a.ctl = gx.ctl(); a.err = m->d_err; a.trace = (m->trace_on && m->d_trace && !gsave) ? m->d_trace + DX_TRACE_STEPS * DX_TRACE_SLOTS : nullptr;
   a.B = B; a.T = T; a.force_wt = m->dx_mode == 2 ? 1 : 0;
-  HIPCHK(clear_polled(gxbuf, (size_t)((char*)gxctl - (char*)gxbuf) + 256, st));
+  HIPCHK(gx.clear(st));
   const size_t lds = std::max(gd_lds_floats(RG) * sizeof(float), (size_t)96 * 1024);      // one workgroup per CU
   const dim3 grid(DX_NGROUP * GD_MEMBERS), blk(512);
   if (a.trace) duo_launch_rg<false, true>(RG, grid, blk, lds, st, a);          // the stamped instantiations (tools/trace_bigru.py): inference only
@@ -808,13 +800,14 @@ static int duo_launch(const taco_model* m, hipStream_t st, const Cbhg& c, int RG
   HIPCHK(hipGetLastError());
   return 0;
 }
-// the backward scan on the geometry of k_bigru_duo: both directions of RG rows per group of 32 CUs, software-pipelined against each other
+// the backward scan on the geometry of k_bigru_duo: both directions of RG rows per group of 32 CUs, software-pipelined against each other.
+// Unlike the forward launchers, this one and oct_bwd_launch do not clear gx: their caller has (cbhg_backward says why)
 static int duo_bwd_launch(const taco_model* m, hipStream_t st, const Cbhg& c, int RG, int B, int T, const float* dout, const float* out, const float* gsave,
-                          const float* h0, const int* lengths, float* dg, float* rh, float* dh0, unsigned long long* gxbuf, unsigned* gxctl) {
+                          const float* h0, const int* lengths, float* dg, float* rh, float* dh0, const Xchg& gx) {
   ChipTurn turn(m->device, st);
   GbArgs a; memset(&a, 0, sizeof a);
   a.wpack = AP(m, c.gb_pack); a.dout = dout; a.out = out; a.gsave = gsave; a.h0 = h0; a.lengths = lengths; a.dg = dg; a.rh = rh; a.dh0 = dh0;
-  a.xbuf = gxbuf; a.ctl = gxctl; a.err = m->d_err; a.B = B; a.T = T; a.force_wt = m->dx_mode == 2 ? 1 : 0;
+  a.xbuf = gx.buf(); a.ctl = gx.ctl(); a.err = m->d_err; a.B = B; a.T = T; a.force_wt = m->dx_mode == 2 ? 1 : 0;
   const size_t lds = std::max(gb_lds_floats(RG) * sizeof(float), (size_t)96 * 1024);      // one workgroup per CU
   const dim3 grid(DX_NGROUP * GD_MEMBERS), blk(512);
   switch (RG) {
@@ -828,12 +821,12 @@ static int duo_bwd_launch(const taco_model* m, hipStream_t st, const Cbhg& c, in
 }
 // the backward scan on the geometry of k_bigru_oct (k_bigru_oct_bwd; four units per wave: up to 32 rows), where the forward scan runs on it
 static int oct_bwd_launch(const taco_model* m, hipStream_t st, const Cbhg& c, int B, int T, const float* dout, const float* out, const float* gsave,
-                          const float* h0, const int* lengths, float* dg, float* rh, float* dh0, unsigned long long* gxbuf, unsigned* gxctl) {
+                          const float* h0, const int* lengths, float* dg, float* rh, float* dh0, const Xchg& gx) {
   ChipTurn turn(m->device, st);
   TRY(go_knob_upload());
   GbArgs a; memset(&a, 0, sizeof a);
   a.wpack = AP(m, c.gob_pack); a.dout = dout; a.out = out; a.gsave = gsave; a.h0 = h0; a.lengths = lengths; a.dg = dg; a.rh = rh; a.dh0 = dh0;
-  a.xbuf = gxbuf; a.ctl = gxctl; a.err = m->d_err; a.B = B; a.T = T; a.force_wt = m->dx_mode == 2 ? 1 : 0;
+  a.xbuf = gx.buf(); a.ctl = gx.ctl(); a.err = m->d_err; a.B = B; a.T = T; a.force_wt = m->dx_mode == 2 ? 1 : 0;
   const size_t lds = std::max(gob_lds_floats() * sizeof(float), (size_t)96 * 1024);      // one workgroup per CU
   hipLaunchKernelGGL(k_bigru_oct_bwd, dim3(CHIP_CUS), dim3(512), lds, st, a);
   HIPCHK(hipGetLastError());
@@ -841,14 +834,14 @@ static int oct_bwd_launch(const taco_model* m, hipStream_t st, const Cbhg& c, in
 }
 // k_bigru_oct: one row per cluster of 32 / UPW CUs (UPW = 4: up to 32 rows, 2: 16, 1: 8); gsave != null: the TAPE instantiation
 static int oct_launch(const taco_model* m, hipStream_t st, const Cbhg& c, int UPW, int B, int T, const float* xproj, const int* lengths, const float* init_state,
-                      float* out, float* gsave, unsigned long long* gxbuf, unsigned* gxctl) {
+                      float* out, float* gsave, const Xchg& gx) {
   ChipTurn turn(m->device, st);
   TRY(go_knob_upload());
   GdArgs a; memset(&a, 0, sizeof a);
   a.wpack = AP(m, c.go_pack[UPW == 4 ? 2 : UPW == 2 ? 1 : 0]); a.xproj = xproj; a.h0 = init_state; a.lengths = lengths; a.out = out; a.gsave = gsave;
-  a.xbuf = gxbuf; a.ctl = gxctl; a.err = m->d_err; a.trace = (m->trace_on && m->d_trace && !gsave) ? m->d_trace + DX_TRACE_STEPS * DX_TRACE_SLOTS : nullptr;
+  a.xbuf = gx.buf(); a.ctl = gx.ctl(); a.err = m->d_err; a.trace = (m->trace_on && m->d_trace && !gsave) ? m->d_trace + DX_TRACE_STEPS * DX_TRACE_SLOTS : nullptr;
   a.B = B; a.T = T; a.force_wt = m->dx_mode == 2 ? 1 : 0;
-  HIPCHK(clear_polled(gxbuf, (size_t)((char*)gxctl - (char*)gxbuf) + 256, st));
+  HIPCHK(gx.clear(st));
   const size_t lds = std::max(go_lds_floats(UPW) * sizeof(float), (size_t)96 * 1024);      // one workgroup per CU
   const dim3 grid(CHIP_CUS), blk(512);
   if (a.trace) oct_launch_upw<false, true>(UPW, grid, blk, lds, st, a);        // the stamped instantiations (tools/trace_bigru.py): inference only
@@ -866,8 +859,8 @@ static int bigru_scan(const taco_model* m, hipStream_t st, const Cbhg& c, int B,
   const int H = c.rnn;
   if (m->skip_scans) return 0;
   const ScanPlan sp = scan_plan(m, c, B, T);
-  if (sp.kernel == SCAN_K_OCT) return oct_launch(m, st, c, sp.upw, B, T, w.xproj, lengths, init_state, out, nullptr, w.gxbuf, w.gxctl);
-  if (sp.kernel == SCAN_K_DUO) return duo_launch(m, st, c, sp.rg, B, T, w.xproj, lengths, init_state, out, nullptr, w.gxbuf, w.gxctl);
+  if (sp.kernel == SCAN_K_OCT) return oct_launch(m, st, c, sp.upw, B, T, w.xproj, lengths, init_state, out, nullptr, w.gx);
+  if (sp.kernel == SCAN_K_DUO) return duo_launch(m, st, c, sp.rg, B, T, w.xproj, lengths, init_state, out, nullptr, w.gx);
   if (sp.kernel == SCAN_K_RESW || sp.kernel == SCAN_K_RES || sp.kernel == SCAN_K_QUAD) {
     BigruSArgs a; memset(&a, 0, sizeof a);
     a.xproj = w.xproj; a.g2_0 = (const float2*)AP(m, c.res_g2[0]); a.g2_1 = (const float2*)AP(m, c.res_g2[1]);
@@ -1203,8 +1196,8 @@ static FfWhyNot prenet_chain_why(const taco_model* m) {
   return b.bh && a.kw == 1 && b.kw == 1 && a.N == 256 && a.cin == hp.embedding_size && a.cin_pad16 <= 256 && (hp.embedding_size & 3) == 0 &&
          b.cin == 256 && b.N == hp.enc_prenet[1] && a.var_index >= 0 && b.var_index >= 0 ? FF_WHY_NONE : FF_WHY_WIDTHS;
 }
-// riders (nullable): regions the launch's spare workgroups clear -- the words the persistent kernels of the same forward poll (forward_enqueue)
-static int run_prenet_chain(const taco_model* m, hipStream_t st, const int* ids, int M, float* out, const ZeroRegions* riders) {
+// riders (nullable): its regions are cleared by the launch's spare workgroups -- the words the persistent kernels of the same forward poll (forward_pass)
+static int run_prenet_chain(const taco_model* m, hipStream_t st, const int* ids, int M, float* out, UpFrontClear* riders) {
   const taco_hparams& hp = m->hp;
   ChainArgs a; memset(&a, 0, sizeof a);
   a.x = AP(m, m->emb); a.ldx = hp.embedding_size; a.Cin = hp.embedding_size; a.gather = ids;
@@ -1219,28 +1212,26 @@ static int run_prenet_chain(const taco_model* m, hipStream_t st, const int* ids,
   int nwg = cdiv(M, CH_BM);
   if (riders) {
     a.ntiles = nwg;
-    for (int i = 0; i < 4; ++i) { a.zp[i] = riders->p[i]; a.znw[i] = riders->nw[i]; }
+    for (int i = 0; i < CH_RIDERS; ++i) { a.zp[i] = riders->z.p[i]; a.znw[i] = riders->z.nw[i]; }
     nwg += std::min(192, std::max(16, 256 - nwg));
   }
   hipLaunchKernelGGL((k_pointwise_chain<256>), dim3(nwg), dim3(512), (size_t)2 * CH_BM * (256 + 8) * sizeof(unsigned short), st, a);
   HIPCHK(hipGetLastError());
-  if (riders) register_cleared(*riders);      // the riders are in the stream now: the persistent kernels behind this launch need no fill of their own
+  if (riders) riders->enqueued = true;      // the riders are in the stream now: the persistent kernels behind this launch need no fill of their own
   return 0;
 }
 // prenet_chain: prenet_chain_why(m) == NONE, asked once by the caller; riders: see run_prenet_chain -- they travel in that launch only (the caller
 // clears the regions itself otherwise)
 static int encoder_forward(const taco_model* m, hipStream_t st, const int* ids, const int* lengths, const SpkSel& sel,
-                           int B, int T, float* enc_out, const EncWs& w, bool spk_done, bool prenet_chain, const ZeroRegions* riders = nullptr) {
+                           int B, int T, float* enc_out, const EncWs& w, bool spk_done, bool prenet_chain, UpFrontClear* riders = nullptr) {
   const taco_hparams& hp = m->hp;
   const int M = B * T;
   if (is_deepvoice(m) && !spk_done) TRY(spk_forward(m, st, sel, B, w.spk));
   const float* cur = AP(m, m->emb); int curd = hp.embedding_size;
   if (prenet_chain) {
     TRY(run_prenet_chain(m, st, ids, M, w.pre[1], riders));
-    return cbhg_forward(m, st, m->enc, w.pre[1], B, T, lengths, is_deepvoice(m) ? w.spk.vec[0] : nullptr,
-                        is_deepvoice(m) ? w.spk.vec[1] : nullptr, enc_out, w.cb);
-  }
-  for (int i = 0; i < hp.enc_prenet_n; ++i) {  // embedding_lookup fused as a row gather (tacotron.py:38-39)
+    cur = w.pre[1];
+  } else for (int i = 0; i < hp.enc_prenet_n; ++i) {  // embedding_lookup fused as a row gather (tacotron.py:38-39)
     GemmCall g; g.x = cur; g.ldx = curd; g.gather = (i == 0) ? ids : nullptr; g.M = M; g.act = ACT_RELU;
     g.out = w.pre[i]; g.ldo = hp.enc_prenet[i];
     TRY(run_gemm(m, st, &m->enc_prenet[i], 1, false, g));
@@ -1253,8 +1244,9 @@ static int encoder_forward(const taco_model* m, hipStream_t st, const int* ids, 
 // ---- decoder (tacotron.py:120-214) ----
 struct DecWs {
   float *keys, *zero, *ctx, *pz[4], *h_att, *rh, *u, *xc, *q, *align, *o[5], *hd[4], *Y, *escr;
-  int* nz;
-  unsigned long long* xbuf; size_t xbuf_bytes; unsigned* dxctl;   // persistent decoder: exchange granules, census words
+  Polled nz;                                                      // the rows' stop flags [n, B] (int): polled by the persistent decoder, read by k_stop_step
+  int* nzp() const { return static_cast<int*>(nz.p); }
+  Xchg dx;                                                        // persistent decoder: exchange granules, census words
   float* rowbias;                                                 // persistent decoder, 'simple': [B, DXRB_N, 256]
   SpkWs spk;
 };
@@ -1275,12 +1267,10 @@ static void carve_dec(Carver& cv, const taco_model* m, int B, int T_in, int n, D
   for (int i = 0; i <= hp.dec_layer_num; ++i) w.o[i] = cv.f((size_t)B * Hd);
   for (int i = 0; i < hp.dec_layer_num; ++i) w.hd[i] = cv.f((size_t)B * Hd);
   w.Y = nullptr;
-  w.nz = cv.i((size_t)n * B);
+  w.nz.bytes = (size_t)n * B * sizeof(int); w.nz.p = cv.raw(w.nz.bytes);
   carve_spk(cv, m, B, w.spk);
   {  // persistent decoder (taco_decoder_xcd.h): sized for the largest rows-per-group, so a debug override cannot outgrow it
-    w.xbuf_bytes = (size_t)DX_NGROUP * dx_xlayout(8, T_in).total * sizeof(unsigned long long);
-    w.xbuf = (unsigned long long*)cv.raw(w.xbuf_bytes);
-    w.dxctl = (unsigned*)cv.raw(256);
+    w.dx.carve(cv, (size_t)DX_NGROUP * dx_xlayout(8, T_in).total);
     w.rowbias = cv.f(is_simple(m) ? (size_t)B * DXRB_N * DX_W : 1);
   }
 }
@@ -1345,7 +1335,7 @@ static constexpr int dx_inst(int rg, bool tape, int aw, int pd) { return rg | (t
 // 'simple': the speaker rows are ready_rows [B, S] if given (training), else sel's -- ids looked up by k_dx_rowbias itself, weights mixed into mix_rows [B, S] first
 static int dx_launch(const taco_model* m, hipStream_t st, const DecPlan& dp, const float* enc_out, const SpkSel& sel, const float* ready_rows, float* mix_rows, int B, int T_in, int n,
                      const float* manual, float* mel, float* align_out, float* dbg, int dbgw, const float* keys, int* nz,
-                     unsigned long long* xbuf, unsigned* dxctl, float* rowbias, const float* h_att0, const float* h10, const float* h20,
+                     const Xchg& dx, float* rowbias, const float* h_att0, const float* h10, const float* h20,
                      const DxArgs* tape = nullptr) {
   ChipTurn turn(m->device, st);
 #ifdef DX_DLY_RT
@@ -1376,13 +1366,13 @@ static int dx_launch(const taco_model* m, hipStream_t st, const DecPlan& dp, con
   a.att_v = AP(m, m->att_v); a.att_b = AP(m, m->att_b); a.score_bias = AP(m, m->att_sb);
   a.keys = keys; a.values = enc_out; a.h_att0 = h_att0; a.h10 = h10; a.h20 = h20;
   a.mel = mel; a.hist = align_out; a.nz = nz; a.dbg = dbg; a.dbgw = dbgw;
-  a.xbuf = xbuf; a.ctl = dxctl; a.err = m->d_err; a.trace = m->trace_on ? m->d_trace : nullptr;
+  a.xbuf = dx.buf(); a.ctl = dx.ctl(); a.err = m->d_err; a.trace = m->trace_on ? m->d_trace : nullptr;
   if (a.trace) { const char* e = getenv("TACO_TRACE_MEMBER"); a.trc_member = e ? atoi(e) : 0; e = getenv("TACO_TRACE_TID"); a.trc_tid = e ? atoi(e) : 0; }
   a.B = B; a.T_in = T_in; a.n = n; a.rM = m->hp.num_mels * m->hp.reduction_factor; a.att_type = m->hp.attention_type;
   a.mels = m->hp.num_mels;
   a.grp0 = 0; a.ngroups = cdiv(B, dp.rg); a.force_wt = m->dx_mode == 2 ? 1 : 0;
   // every polled word starts from zero on every launch (tags are step numbers, the census counts arrivals)
-  HIPCHK(clear_polled(xbuf, (size_t)((char*)dxctl - (char*)xbuf) + 256, st));   // carved back to back: one fill launch
+  HIPCHK(dx.clear(st));
   switch (dx_inst(dp.rg, dp.tape, dp.aw, dp.pd)) {
 #define X(RG, TAPE, AW, PD) case dx_inst(RG, TAPE, AW, PD): return dx_launch_rg<RG, TAPE, AW, PD>(st, a, dp.lds_bytes);
     DX_REFERENCE(X) DX_REFERENCE_TAPE(X) DX_PRESETS(X)
@@ -1396,7 +1386,7 @@ static size_t dbx_xbuf_granules(int T_in) {
   for (int RG = 1; RG <= 8; RG *= 2) g = std::max(g, (size_t)db_xlayout(RG, T_in).total);
   return g;
 }
-static int dbx_launch(const taco_model* m, hipStream_t st, const DecPlan& dp, DbArgs a, int B, int T_in, int n, unsigned long long* xbuf, unsigned* dxctl) {
+static int dbx_launch(const taco_model* m, hipStream_t st, const DecPlan& dp, DbArgs a, int B, int T_in, int n, const Xchg& dx) {
   ChipTurn turn(m->device, st);
 #ifdef DX_DLY_RT
   {   // A/B build: the twelve first-poll sleeps of the backward loop from TACO_DB_DLY (sites 0..11 of taco_decoder_bwd_xcd.h)
@@ -1408,10 +1398,10 @@ static int dbx_launch(const taco_model* m, hipStream_t st, const DecPlan& dp, Db
 #endif
   a.wpack = AP(m, m->dbx_pack);
   a.att_v = AP(m, m->att_v); a.att_b = AP(m, m->att_b); a.score_bias = AP(m, m->att_sb);
-  a.xbuf = xbuf; a.ctl = dxctl; a.err = m->d_err; a.trace = (m->trace_on && m->d_trace) ? m->d_trace + 2 * DX_TRACE_STEPS * DX_TRACE_SLOTS : nullptr;
+  a.xbuf = dx.buf(); a.ctl = dx.ctl(); a.err = m->d_err; a.trace = (m->trace_on && m->d_trace) ? m->d_trace + 2 * DX_TRACE_STEPS * DX_TRACE_SLOTS : nullptr;
   a.B = B; a.T_in = T_in; a.n = n; a.att_type = m->hp.attention_type;
   a.force_wt = m->dx_mode == 2 ? 1 : 0;
-  HIPCHK(zero_async(xbuf, (size_t)((char*)dxctl - (char*)xbuf) + 256, st));
+  HIPCHK(dx.clear(st));
   const dim3 grid(CHIP_CUS), blk(DX_NT);
   if (a.trace && dp.rg == 4) {      // the stamped instantiation (tools/trace_bptt.py): the C4 shard's geometry only
     hipLaunchKernelGGL((k_decoder_bwd_xcd<4, true>), grid, blk, dp.lds_bytes, st, a);
@@ -1451,16 +1441,16 @@ static int decoder_forward(const taco_model* m, hipStream_t st, const float* enc
   const int Ilast = hp.dec_prenet[np - 1], ldz = Ilast + S;
   const int ldY = n * rM;   // mel buffer viewed as Y [B, n, r*num_mels] (tacotron.py:213-214 is a pure reshape)
   const int dbgw = As + D + L * Hd;
-  HIPCHK(clear_polled(w.nz, (size_t)n * B * sizeof(int), st));
+  HIPCHK(w.nz.clear(st));
   if (const DecPlan dp = decoder_plan(m, B, T_in, n, teacher ? DEC_TEACHER : DEC_INFER); dp.persistent) {
     // the whole loop as ONE persistent launch (taco_decoder_xcd.h), which builds its initial state itself (zeros or the deepvoice
     // vectors); the launch-per-stage loop below is the general path
     DxArgs ta; memset(&ta, 0, sizeof ta);
     if (teacher) { ta.teacher = teacher; ta.p1o_raw = m->tp ? nullptr : AP(m, m->dx_p1o_raw); }     // teacher-forced: the TAPE instantiation without a tape
-    TRY(dx_launch(m, st, dp, enc_out, sel, nullptr, spk->emb, B, T_in, n, manual, mel, align_out, dbg, dbgw, w.keys, w.nz, w.xbuf, w.dxctl, w.rowbias,
+    TRY(dx_launch(m, st, dp, enc_out, sel, nullptr, spk->emb, B, T_in, n, manual, mel, align_out, dbg, dbgw, w.keys, w.nzp(), w.dx, w.rowbias,
                   dv ? spk->vec[2] : nullptr, dv ? spk->vec[3] : nullptr, dv ? spk->vec[4] : nullptr, teacher ? &ta : nullptr));
     if (stop_step) {
-      hipLaunchKernelGGL(k_stop_step, dim3(1), dim3(1024), 0, st, w.nz, B, n, stop_step);
+      hipLaunchKernelGGL(k_stop_step, dim3(1), dim3(1024), 0, st, w.nzp(), B, n, stop_step);
       HIPCHK(hipGetLastError());
     }
     return 0;
@@ -1529,7 +1519,7 @@ static int decoder_forward(const taco_model* m, hipStream_t st, const float* enc
     // frame projection to r frames (tacotron.py:178-179), written straight into the mel buffer
     { SkJob j[2];
       j[0] = sk_linear(m, m->frame_proj, w.o[L], Hd, Hd, nullptr, 0, ACT_NONE, mel + (size_t)t * rM, ldY);
-      j[0].o2 = reinterpret_cast<float*>(w.nz + (size_t)t * B);
+      j[0].o2 = reinterpret_cast<float*>(w.nzp() + (size_t)t * B);
       int nj = 1;
       if (fuse_p1 && t + 1 < n) { j[1] = sk_linear(m, m->prenet1_next, w.o[L], Hd, Hd, w.ctx, ldc, ACT_RELU, w.pz[0], hp.dec_prenet[0]); nj = 2; }
       TRY(run_skinny(st, B, j, nj)); }
@@ -1543,7 +1533,7 @@ static int decoder_forward(const taco_model* m, hipStream_t st, const float* enc
     }
   }
   if (stop_step) {
-    hipLaunchKernelGGL(k_stop_step, dim3(1), dim3(1024), 0, st, w.nz, B, n, stop_step);
+    hipLaunchKernelGGL(k_stop_step, dim3(1), dim3(1024), 0, st, w.nzp(), B, n, stop_step);
     HIPCHK(hipGetLastError());
   }
   return 0;
@@ -1583,68 +1573,33 @@ static void carve_full(Carver& cv, const taco_model* m, int B, int T_in, int n, 
   carve_post(cv, m, B, n * m->hp.reduction_factor, w.post);
 }
 
-static int check_common(const taco_model* m, int B, int T) {
+static int check_model_shape(const taco_model* m, int B, int T) {
   if (!m) return fail(TACO_ERR_ARG, "null model");
   if (!m->finalized) return fail(TACO_ERR_STATE, "model not finalized");
   if (B <= 0 || T <= 0) return fail(TACO_ERR_ARG, "bad batch/time %d/%d", B, T);
+  return 0;
+}
+static int check_common(const taco_model* m, int B, int T) {      // an entry that serves one pass only
+  TRY(check_model_shape(m, B, T));
   if (B > 64) return fail(TACO_ERR_UNSUPPORTED, "batch %d > 64 rows per device is not supported: shard the batch", B);
   return 0;
 }
 
-// One pass of at most 64 batch rows (what the persistent kernels place on one chip: 8 groups x 8 rows).
-static int forward_pass(taco_model* m, hipStream_t st, const int32_t* ids, const int32_t* lengths, const SpkSel& spk,
-                        int B, int T_in, int n, const float* manual, float* mel, float* linear, float* align,
-                        int32_t* stop, void* ws, size_t ws_bytes) {
-  TRY(check_common(m, B, T_in));
-  if (n <= 0) return fail(TACO_ERR_ARG, "n_steps must be positive");
-  if (!ids || !lengths || !mel || !linear || !align || !ws) return fail(TACO_ERR_ARG, "null buffer");
-  if (m->hp.num_speakers > 1 && !spk.given()) return fail(TACO_ERR_ARG, "speaker_id required for a multi-speaker model");
-  Carver cv(ws, ws_bytes);
-  FullWs w;
-  carve_full(cv, m, B, T_in, n, w);
-  if (!cv.ok()) return fail(TACO_ERR_STATE, "workspace too small: need %zu bytes, have %zu", cv.off, ws_bytes);
-  const int r = m->hp.reduction_factor, T_mel = n * r;
-  const bool ride = prenet_chain_why(m) == FF_WHY_NONE;      // the encoder prenet as the chain launch: asked once per forward
-  // every word a persistent kernel polls and the stop flags, cleared by ONE launch in front of the forward; the stop rule and the
-  // error latch are ONE launch behind it (11 graph nodes at C2 with the clears riding in the prenet launch; 13 in round 4, 20 in round 3)
-  ZeroRegions z; memset(&z, 0, sizeof z);
-  z.p[0] = (uint32_t*)w.dec.xbuf; z.nw[0] = ((size_t)((char*)w.dec.dxctl - (char*)w.dec.xbuf) + 256) / 4;
-  z.p[1] = (uint32_t*)w.dec.nz; z.nw[1] = (size_t)n * B;
-  z.p[2] = (uint32_t*)w.post.cb.gxbuf; z.nw[2] = ((size_t)((char*)w.post.cb.gxctl - (char*)w.post.cb.gxbuf) + 256) / 4;
-  z.p[3] = (uint32_t*)w.enc.cb.gxbuf; z.nw[3] = ((size_t)((char*)w.enc.cb.gxctl - (char*)w.enc.cb.gxbuf) + 256) / 4;     // (an encoder of width 256 scans on k_bigru_duo too)
-  // (they ride in the encoder prenet's launch where that is the chain kernel -- the first launch of the forward, with CUs to spare)
-  // The regions count as cleared (zero_async then skips its own fill) only from the point where the launch that clears them HAS been
-  // enqueued: here for the fill kernel, inside run_prenet_chain for the riders.
-  struct Guard { Guard() { g_cleared.cnt = 0; } ~Guard() { g_cleared.cnt = 0; } } guard;
-  if (!ride) {
-    hipLaunchKernelGGL(k_zero_fill_multi, dim3(256, 4), dim3(256), 0, st, z);
-    HIPCHK(hipGetLastError());
-    register_cleared(z);
-  }
-  TRY(encoder_forward(m, st, ids, lengths, spk, B, T_in, w.enc_out, w.enc, false, ride, ride ? &z : nullptr));
-  TRY(decoder_forward(m, st, w.enc_out, spk, B, T_in, n, manual, nullptr, mel, align, nullptr, nullptr, w.dec, true, &w.enc.spk));
-  TRY(postnet_forward(m, st, mel, spk, B, T_mel, linear, nullptr, w.post));
-  if (stop) {
-    hipLaunchKernelGGL(k_stop_step, dim3(1), dim3(1024), 0, st, (const int*)w.dec.nz, B, n, stop, (const unsigned*)m->d_err);
-    HIPCHK(hipGetLastError());
-  }
-  return 0;
-}
-
-// Any batch size (synthesizer.py:120-131 and eval.py:86-119 put no cap on it): more than 64 rows run as ceil(B / 64) passes of equal
-// size over the SAME workspace, back to back on the caller's stream (batch rows are independent at inference: BatchNorm uses the
-// moving statistics, modules.py:131).  The stop step of the batch (helpers.py:29 with dynamic_decode's all-rows-finished loop condition)
-// is the maximum over the passes' stop steps -- a row's `finished` is sticky, so the loop would have ended when the LAST pass's rows
-// were all done; a negative pass word (a persistent kernel gave up) wins.
+// Any batch size (synthesizer.py:120-131 and eval.py:86-119 put no cap on it): more than `cap` rows -- 64, what the persistent kernels place on one
+// chip: 8 groups x 8 rows -- run as ceil(B / cap) passes of equal size over the SAME workspace, back to back on the caller's stream (batch rows are
+// independent at inference: BatchNorm uses the moving statistics, modules.py:131).  The forward and every stage entry validate their arguments
+// once, carve one pass's workspace at pp.rows, and hand each pass to a single-pass function through for_each_pass.
 struct PassPlan { int passes, rows; };
 static PassPlan pass_plan(int B, int cap = 64) { PassPlan p; p.passes = (B + cap - 1) / cap; p.rows = p.passes ? (B + p.passes - 1) / p.passes : 0; return p; }
-// Rows one pass of the decoder loop may hold: 64 (8 groups x 8 rows) -- but an inference model with attention_size 512 (hparams.py:71-82, the first
-// "Deep Voice 2" block) has no persistent instantiation at 8 rows per group, so its passes hold at most 32 rows: two passes on the persistent decoder
-// instead of one on the launch-per-stage loop, which is four times slower per step.  state_dump (taco_decoder_forward's, laid out [step][row]): one pass.
-static int decoder_pass_rows(const taco_model* m, bool state_dump = false) {
-  // (ADVICE r06, with the call's T_in and n passed down: `&& decoder_plan(m, CHIP_ROWS / 2, T_in, n, DEC_INFER).persistent` -- today the rule looks at no shape)
-  return !state_dump && decoder_plan(m, CHIP_ROWS, 0, 0, DEC_INFER).why == DEC_WHY_NO_INSTANTIATION ? CHIP_ROWS / 2 : CHIP_ROWS;
+template <class Body>
+static int for_each_pass(const PassPlan& pp, int B, Body body) {      // body(b0, rows, pass index): rows b0 .. b0 + rows - 1 of the batch
+  for (int p = 0, b0 = 0; b0 < B; ++p, b0 += pp.rows) TRY(body(b0, std::min(pp.rows, B - b0), p));
+  return 0;
 }
+// The stop step of the batch (helpers.py:29 with dynamic_decode's all-rows-finished loop condition) is the maximum over the passes' stop steps -- a
+// row's `finished` is sticky, so the loop would have ended when the LAST pass's rows were all done; a negative pass word (a persistent kernel gave
+// up) wins.  The passes' words are carved behind the pass workspace (null: one pass, which writes the caller's word itself).
+static int32_t* carve_pass_stops(Carver& cv, const PassPlan& pp) { return pp.passes > 1 ? (int32_t*)cv.i((size_t)pp.passes) : nullptr; }
 __global__ void k_stop_combine(const int* pstop, int np, int* stop) {
   if (threadIdx.x == 0) {
     int worst = 0, err = 0;
@@ -1652,42 +1607,74 @@ __global__ void k_stop_combine(const int* pstop, int np, int* stop) {
     *stop = err ? err : worst;
   }
 }
-static size_t forward_workspace(const taco_model* m, int B, int T_in, int n, FullWs* w_out, int32_t** pstop, void* ws, size_t ws_bytes, bool* ok) {
-  const PassPlan pp = pass_plan(B, decoder_pass_rows(m));
-  Carver cv(ws, ws_bytes);
-  FullWs w;
+static int combine_pass_stops(hipStream_t st, const int32_t* pstop, const PassPlan& pp, int32_t* stop) {
+  if (!stop || !pstop) return 0;
+  hipLaunchKernelGGL(k_stop_combine, dim3(1), dim3(64), 0, st, (const int*)pstop, pp.passes, stop);
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+// Rows one pass of the decoder loop may hold: 64 (8 groups x 8 rows) -- but an inference model with attention_size 512 (hparams.py:71-82, the first
+// "Deep Voice 2" block) has no persistent instantiation at 8 rows per group, so its passes hold at most 32 rows: two passes on the persistent decoder
+// instead of one on the launch-per-stage loop, which is four times slower per step.  state_dump (taco_decoder_forward's, laid out [step][row]): one pass.
+static int decoder_pass_rows(const taco_model* m, bool state_dump = false) {
+  // (ADVICE r06, with the call's T_in and n passed down: `&& decoder_plan(m, CHIP_ROWS / 2, T_in, n, DEC_INFER).persistent` -- today the rule looks at no shape)
+  return !state_dump && decoder_plan(m, CHIP_ROWS, 0, 0, DEC_INFER).why == DEC_WHY_NO_INSTANTIATION ? CHIP_ROWS / 2 : CHIP_ROWS;
+}
+
+// One pass of the forward: B <= decoder_pass_rows(m) rows, arguments validated and w carved (for at least B rows) by forward_enqueue; w is this
+// pass's own copy, so what it learns about cleared regions ends with the pass
+static int forward_pass(taco_model* m, hipStream_t st, const int32_t* ids, const int32_t* lengths, const SpkSel& spk,
+                        int B, int T_in, int n, const float* manual, float* mel, float* linear, float* align,
+                        int32_t* stop, FullWs w) {
+  const int r = m->hp.reduction_factor, T_mel = n * r;
+  const bool ride = prenet_chain_why(m) == FF_WHY_NONE;      // the encoder prenet as the chain launch: asked once per forward
+  // every word a persistent kernel polls and the stop flags, cleared by ONE launch in front of the forward -- riding in the encoder prenet's
+  // launch where that is the chain kernel: the first launch of the forward, with CUs to spare; the stop rule and the error latch are ONE
+  // launch behind it (11 graph nodes at C2 with the clears riding; 13 in round 4, 20 in round 3).  The regions count as cleared
+  // (Polled::clear then skips its own fill) only from the point where the launch that clears them HAS been enqueued: here for the fill
+  // kernel, inside run_prenet_chain for the riders.
+  Polled* const polled[CH_RIDERS] = {&w.dec.dx, &w.dec.nz, &w.post.cb.gx, &w.enc.cb.gx};      // (an encoder of width 256 scans on k_bigru_duo too)
+  UpFrontClear up; memset(&up.z, 0, sizeof up.z);
+  for (int i = 0; i < CH_RIDERS; ++i) { up.z.p[i] = static_cast<uint32_t*>(polled[i]->p); up.z.nw[i] = polled[i]->bytes / 4; polled[i]->cleared = &up; }
+  if (!ride) {
+    hipLaunchKernelGGL(k_zero_fill, dim3(256, CH_RIDERS), dim3(256), 0, st, up.z);
+    HIPCHK(hipGetLastError());
+    up.enqueued = true;
+  }
+  TRY(encoder_forward(m, st, ids, lengths, spk, B, T_in, w.enc_out, w.enc, false, ride, ride ? &up : nullptr));
+  TRY(decoder_forward(m, st, w.enc_out, spk, B, T_in, n, manual, nullptr, mel, align, nullptr, nullptr, w.dec, true, &w.enc.spk));
+  TRY(postnet_forward(m, st, mel, spk, B, T_mel, linear, nullptr, w.post));
+  if (stop) {
+    hipLaunchKernelGGL(k_stop_step, dim3(1), dim3(1024), 0, st, (const int*)w.dec.nzp(), B, n, stop, (const unsigned*)m->d_err);
+    HIPCHK(hipGetLastError());
+  }
+  return 0;
+}
+
+static PassPlan forward_passes(const taco_model* m, int B) { return pass_plan(B, decoder_pass_rows(m)); }
+static int32_t* carve_forward(Carver& cv, const taco_model* m, const PassPlan& pp, int T_in, int n, FullWs& w) {      // -> the passes' stop words
   carve_full(cv, m, pp.rows, T_in, n, w);
-  int32_t* ps = pp.passes > 1 ? (int32_t*)cv.i((size_t)pp.passes) : nullptr;
-  if (w_out) *w_out = w;
-  if (pstop) *pstop = ps;
-  if (ok) *ok = cv.ok();
-  return cv.off;
+  return carve_pass_stops(cv, pp);
 }
 static int forward_enqueue(taco_model* m, hipStream_t st, const int32_t* ids, const int32_t* lengths, const SpkSel& spk,
                            int B, int T_in, int n, const float* manual, float* mel, float* linear, float* align,
                            int32_t* stop, void* ws, size_t ws_bytes) {
-  if (!m) return fail(TACO_ERR_ARG, "null model");
-  const int cap = decoder_pass_rows(m);
-  if (B <= cap) return forward_pass(m, st, ids, lengths, spk, B, T_in, n, manual, mel, linear, align, stop, ws, ws_bytes);
-  if (T_in <= 0 || n <= 0) return fail(TACO_ERR_ARG, "bad time %d / steps %d", T_in, n);
+  TRY(check_model_shape(m, B, T_in));
+  if (n <= 0) return fail(TACO_ERR_ARG, "n_steps must be positive");
   if (!ids || !lengths || !mel || !linear || !align || !ws) return fail(TACO_ERR_ARG, "null buffer");
-  const PassPlan pp = pass_plan(B, cap);
-  int32_t* pstop = nullptr; bool ok = false;
-  const size_t need = forward_workspace(m, B, T_in, n, nullptr, &pstop, ws, ws_bytes, &ok);
-  if (!ok) return fail(TACO_ERR_STATE, "workspace too small: need %zu bytes, have %zu", need, ws_bytes);
+  if (m->hp.num_speakers > 1 && !spk.given()) return fail(TACO_ERR_ARG, "speaker_id required for a multi-speaker model");
+  const PassPlan pp = forward_passes(m, B);
+  Carver cv(ws, ws_bytes);
+  FullWs w;
+  int32_t* pstop = carve_forward(cv, m, pp, T_in, n, w);
+  if (!cv.ok()) return fail(TACO_ERR_STATE, "workspace too small: need %zu bytes, have %zu", cv.off, ws_bytes);
   const size_t rM = (size_t)m->hp.reduction_factor * m->hp.num_mels, T_mel = (size_t)n * m->hp.reduction_factor;
-  for (int p = 0; p < pp.passes; ++p) {
-    const int b0 = p * pp.rows, rows = std::min(pp.rows, B - b0);
-    if (rows <= 0) break;
-    TRY(forward_pass(m, st, ids + (size_t)b0 * T_in, lengths + b0, spk.rows_from(b0, m->hp.num_speakers), rows, T_in, n,
-                     manual ? manual + (size_t)b0 * n * T_in : nullptr, mel + (size_t)b0 * n * rM, linear + (size_t)b0 * T_mel * m->hp.num_freq,
-                     align + (size_t)b0 * T_in * n, stop ? pstop + p : nullptr, ws, ws_bytes));
-  }
-  if (stop) {
-    hipLaunchKernelGGL(k_stop_combine, dim3(1), dim3(64), 0, st, (const int*)pstop, pp.passes, stop);
-    HIPCHK(hipGetLastError());
-  }
-  return 0;
+  TRY(for_each_pass(pp, B, [&](int b0, int rows, int p) {
+    return forward_pass(m, st, ids + (size_t)b0 * T_in, lengths + b0, spk.rows_from(b0, m->hp.num_speakers), rows, T_in, n,
+                        manual ? manual + (size_t)b0 * n * T_in : nullptr, mel + (size_t)b0 * n * rM, linear + (size_t)b0 * T_mel * m->hp.num_freq,
+                        align + (size_t)b0 * T_in * n, !stop ? nullptr : pstop ? pstop + p : stop, w);
+  }));
+  return combine_pass_stops(st, pstop, pp, stop);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -2056,7 +2043,7 @@ int taco_model_engine_plan(taco_model* m, int B, int T_in, int T_mel, int flags,
     const FfWhyNot pw = prenet_chain_why(m);
     if (!m->tp && !pw) s += "; encoder prenet: one k_pointwise_chain launch (1 launch: embedding rows gathered, both layers; the forward's zero fills ride in it)";
     else s += "; encoder prenet: one GEMM launch per layer (" + launches(m->hp.enc_prenet_n) + " of " + gemm_name(gemm_level(m, m->enc_prenet[0])) +
-              (m->tp ? ")" : std::string(" + 1 launch of k_zero_fill_multi in front: the forward's zero fills") + ff_why("k_pointwise_chain", pw, 2) + ")");
+              (m->tp ? ")" : std::string(" + 1 launch of k_zero_fill in front: the forward's zero fills") + ff_why("k_pointwise_chain", pw, 2) + ")");
     GemmCall g; g.ldx = 2 * m->hp.post_rnn_size; g.M = B * T_mel; g.ldo = m->hp.num_freq;      // the call of postnet_forward (and of the training forward)
     const FfWhyNot hw = head_sweep_why(m, m->linear, 1, false, g);
     s += std::string("; linear head: 1 launch of ") + (hw ? gemm_name(lv) + ff_why("k_head_sweep", hw, 5, "it serves 256 rows and more, 256 or 512 inputs, 512 columns and more") :
@@ -2104,19 +2091,25 @@ int taco_debug_force_gemm_config(taco_model* m, int cfg) {
 
 size_t taco_workspace_bytes(const taco_model* m, int B, int T_in, int n_steps) {
   if (!m || B <= 0) return 0;
-  return forward_workspace(m, B, T_in, n_steps, nullptr, nullptr, nullptr, 0, nullptr);      // (more than 64 rows: the workspace of ONE pass + the passes' stop words)
+  Carver cv(nullptr, 0);
+  FullWs w;
+  carve_forward(cv, m, forward_passes(m, B), T_in, n_steps, w);      // (more than one pass: the workspace of ONE pass + the passes' stop words)
+  return cv.off;
 }
 
 size_t taco_stage_workspace_bytes(const taco_model* m, int B, int T) {
   if (!m) return 0;
-  // large enough for any single stage at (B, T): encoder at T_in=T, decoder with T_in=T and n_steps=T, post-net at T_mel=T
-  Carver a(nullptr, 0), b(nullptr, 0), c(nullptr, 0);
-  const int R = B > 64 ? pass_plan(B).rows : B;      // more than 64 rows: passes over one pass's workspace (+ the passes' stop words)
-  const int cap = decoder_pass_rows(m), Rd = B > cap ? pass_plan(B, cap).rows : B;      // (a state dump of 33..64 rows is one pass of B rows)
-  EncWs e; carve_enc(a, m, R, T, e);
-  DecWs d; carve_dec(b, m, Rd, T, T, d);
-  PostWs p; carve_post(c, m, R, T, p);
-  return std::max(a.off, std::max(b.off, c.off)) + (B > cap ? 256 : 0);
+  // large enough for any single stage at (B, T): encoder at T_in=T, decoder with T_in=T and n_steps=T, post-net at T_mel=T -- each from the pass
+  // plan its entry follows; the decoder from the plain plan and from the state dump's (one pass of up to 64 rows), whichever is larger
+  Carver a(nullptr, 0), b(nullptr, 0), bd(nullptr, 0), c(nullptr, 0);
+  const PassPlan pp = pass_plan(B), dec = pass_plan(B, decoder_pass_rows(m)), dump = pass_plan(B, decoder_pass_rows(m, true));
+  EncWs e; carve_enc(a, m, pp.rows, T, e);
+  DecWs d; carve_dec(b, m, dec.rows, T, T, d); carve_dec(bd, m, dump.rows, T, T, d);
+  PostWs p; carve_post(c, m, pp.rows, T, p);
+  Carver all(nullptr, 0);
+  all.off = std::max(std::max(a.off, c.off), std::max(b.off, bd.off));
+  carve_pass_stops(all, dec);      // (no plan has more passes than the plain decoder's)
+  return all.off;
 }
 
 int taco_forward_infer(taco_model* m, void* hip_stream, const int32_t* d_inputs, const int32_t* d_input_lengths,
@@ -2208,21 +2201,19 @@ void taco_plan_destroy(taco_plan* p) {
 static int encoder_entry(taco_model* m, void* hip_stream, const int32_t* d_inputs, const int32_t* d_input_lengths,
                          const SpkSel& sel, int B, int T_in, float* d_encoder_out, void* d_workspace,
                          size_t workspace_bytes) {
-  if (m && m->finalized && B > 64 && T_in > 0 && d_inputs && d_input_lengths && d_encoder_out) {      // passes of at most 64 rows (forward_enqueue)
-    const PassPlan pp = pass_plan(B);
-    for (int b0 = 0; b0 < B; b0 += pp.rows)
-      TRY(encoder_entry(m, hip_stream, d_inputs + (size_t)b0 * T_in, d_input_lengths + b0, sel.rows_from(b0, m->hp.num_speakers), std::min(pp.rows, B - b0),
-                               T_in, d_encoder_out + (size_t)b0 * T_in * 2 * m->hp.enc_rnn_size, d_workspace, workspace_bytes));
-    return 0;
-  }
-  TRY(check_common(m, B, T_in));
+  TRY(check_model_shape(m, B, T_in));
   if (!d_inputs || !d_input_lengths || !d_encoder_out || !d_workspace) return fail(TACO_ERR_ARG, "null buffer");
   if (m->hp.num_speakers > 1 && !sel.given()) return fail(TACO_ERR_ARG, "speaker_id required for a multi-speaker model");
   HIPCHK(hipSetDevice(m->device));
+  const PassPlan pp = pass_plan(B);
   Carver cv(d_workspace, workspace_bytes);
-  EncWs w; carve_enc(cv, m, B, T_in, w);
+  EncWs w; carve_enc(cv, m, pp.rows, T_in, w);
   if (!cv.ok()) return fail(TACO_ERR_STATE, "workspace too small: need %zu bytes", cv.off);
-  return encoder_forward(m, (hipStream_t)hip_stream, d_inputs, d_input_lengths, sel, B, T_in, d_encoder_out, w, false, prenet_chain_why(m) == FF_WHY_NONE);
+  const bool chain = prenet_chain_why(m) == FF_WHY_NONE;
+  return for_each_pass(pp, B, [&](int b0, int rows, int) {
+    return encoder_forward(m, (hipStream_t)hip_stream, d_inputs + (size_t)b0 * T_in, d_input_lengths + b0, sel.rows_from(b0, m->hp.num_speakers), rows, T_in,
+                           d_encoder_out + (size_t)b0 * T_in * 2 * m->hp.enc_rnn_size, w, false, chain);
+  });
 }
 int taco_encoder_forward(taco_model* m, void* hip_stream, const int32_t* d_inputs, const int32_t* d_input_lengths,
                          const int32_t* d_speaker_id, int B, int T_in, float* d_encoder_out, void* d_workspace,
@@ -2240,34 +2231,25 @@ static int decoder_entry(taco_model* m, void* hip_stream, const float* d_encoder
                          int T_in, int n_steps, const float* d_manual_alignments, const float* d_teacher_frames,
                          float* d_mel, float* d_alignments, int32_t* d_stop_step, float* d_dbg_states, void* d_workspace,
                          size_t workspace_bytes) {
-  if (m && m->finalized && B > decoder_pass_rows(m, d_dbg_states != nullptr) && T_in > 0 && n_steps > 0 && d_encoder_out && d_mel && d_alignments && d_workspace) {      // passes of at most 64 (32) rows
-    if (d_dbg_states) return fail(TACO_ERR_UNSUPPORTED, "the per-step state dump is laid out [step][row]: at most 64 rows per call");
-    const PassPlan pp = pass_plan(B, decoder_pass_rows(m));
-    const size_t rM = (size_t)m->hp.reduction_factor * m->hp.num_mels, D = (size_t)2 * m->hp.enc_rnn_size;
-    if (workspace_bytes < 256) return fail(TACO_ERR_STATE, "workspace too small");
-    int32_t* pstop = (int32_t*)((char*)d_workspace + ((workspace_bytes - (size_t)pp.passes * sizeof(int32_t)) & ~(size_t)255));      // the tail of the caller's buffer
-    const size_t pass_bytes = (size_t)((char*)pstop - (char*)d_workspace);
-    int p = 0;
-    for (int b0 = 0; b0 < B; b0 += pp.rows, ++p)
-      TRY(decoder_entry(m, hip_stream, d_encoder_out + (size_t)b0 * T_in * D, sel.rows_from(b0, m->hp.num_speakers), std::min(pp.rows, B - b0), T_in, n_steps,
-                               d_manual_alignments ? d_manual_alignments + (size_t)b0 * n_steps * T_in : nullptr,
-                               d_teacher_frames ? d_teacher_frames + (size_t)b0 * n_steps * m->hp.num_mels : nullptr, d_mel + (size_t)b0 * n_steps * rM,
-                               d_alignments + (size_t)b0 * T_in * n_steps, d_stop_step ? pstop + p : nullptr, nullptr, d_workspace, pass_bytes));
-    if (d_stop_step) {
-      hipLaunchKernelGGL(k_stop_combine, dim3(1), dim3(64), 0, (hipStream_t)hip_stream, (const int*)pstop, pp.passes, d_stop_step);
-      HIPCHK(hipGetLastError());
-    }
-    return 0;
-  }
-  TRY(check_common(m, B, T_in));
+  TRY(check_model_shape(m, B, T_in));
   if (n_steps <= 0 || !d_encoder_out || !d_mel || !d_alignments || !d_workspace) return fail(TACO_ERR_ARG, "bad argument");
   if (m->hp.num_speakers > 1 && !sel.given()) return fail(TACO_ERR_ARG, "speaker_id required for a multi-speaker model");
+  const PassPlan pp = pass_plan(B, decoder_pass_rows(m, d_dbg_states != nullptr));      // passes of at most 64 (32) rows
+  if (pp.passes > 1 && d_dbg_states) return fail(TACO_ERR_UNSUPPORTED, "the per-step state dump is laid out [step][row]: at most 64 rows per call");
   HIPCHK(hipSetDevice(m->device));
+  hipStream_t st = (hipStream_t)hip_stream;
   Carver cv(d_workspace, workspace_bytes);
-  DecWs w; carve_dec(cv, m, B, T_in, n_steps, w);
+  DecWs w; carve_dec(cv, m, pp.rows, T_in, n_steps, w);
+  int32_t* pstop = carve_pass_stops(cv, pp);
   if (!cv.ok()) return fail(TACO_ERR_STATE, "workspace too small: need %zu bytes", cv.off);
-  return decoder_forward(m, (hipStream_t)hip_stream, d_encoder_out, sel, B, T_in, n_steps, d_manual_alignments,
-                         d_teacher_frames, d_mel, d_alignments, d_stop_step, d_dbg_states, w, false, nullptr);
+  const size_t rM = (size_t)m->hp.reduction_factor * m->hp.num_mels, D = (size_t)2 * m->hp.enc_rnn_size;
+  TRY(for_each_pass(pp, B, [&](int b0, int rows, int p) {
+    return decoder_forward(m, st, d_encoder_out + (size_t)b0 * T_in * D, sel.rows_from(b0, m->hp.num_speakers), rows, T_in, n_steps,
+                           d_manual_alignments ? d_manual_alignments + (size_t)b0 * n_steps * T_in : nullptr,
+                           d_teacher_frames ? d_teacher_frames + (size_t)b0 * n_steps * m->hp.num_mels : nullptr, d_mel + (size_t)b0 * n_steps * rM,
+                           d_alignments + (size_t)b0 * T_in * n_steps, !d_stop_step ? nullptr : pstop ? pstop + p : d_stop_step, d_dbg_states, w, false, nullptr);
+  }));
+  return combine_pass_stops(st, pstop, pp, d_stop_step);
 }
 int taco_decoder_forward(taco_model* m, void* hip_stream, const float* d_encoder_out, const int32_t* d_speaker_id, int B,
                          int T_in, int n_steps, const float* d_manual_alignments, const float* d_teacher_frames,
@@ -2287,21 +2269,17 @@ int taco_decoder_forward_mix(taco_model* m, void* hip_stream, const float* d_enc
 
 static int postnet_entry(taco_model* m, void* hip_stream, const float* d_mel, const SpkSel& sel, int B, int T_mel,
                          float* d_linear, float* d_post_out, void* d_workspace, size_t workspace_bytes) {
-  if (m && m->finalized && B > 64 && T_mel > 0 && d_mel && d_linear) {      // passes of at most 64 rows
-    const PassPlan pp = pass_plan(B);
-    for (int b0 = 0; b0 < B; b0 += pp.rows)
-      TRY(postnet_entry(m, hip_stream, d_mel + (size_t)b0 * T_mel * m->hp.num_mels, sel.rows_from(b0, m->hp.num_speakers), std::min(pp.rows, B - b0), T_mel,
-                               d_linear + (size_t)b0 * T_mel * m->hp.num_freq, d_post_out ? d_post_out + (size_t)b0 * T_mel * 2 * m->hp.post_rnn_size : nullptr,
-                               d_workspace, workspace_bytes));
-    return 0;
-  }
-  TRY(check_common(m, B, T_mel));
+  TRY(check_model_shape(m, B, T_mel));
   if (!d_mel || !d_linear || !d_workspace) return fail(TACO_ERR_ARG, "null buffer");
   HIPCHK(hipSetDevice(m->device));
+  const PassPlan pp = pass_plan(B);
   Carver cv(d_workspace, workspace_bytes);
-  PostWs w; carve_post(cv, m, B, T_mel, w);
+  PostWs w; carve_post(cv, m, pp.rows, T_mel, w);
   if (!cv.ok()) return fail(TACO_ERR_STATE, "workspace too small: need %zu bytes", cv.off);
-  return postnet_forward(m, (hipStream_t)hip_stream, d_mel, sel, B, T_mel, d_linear, d_post_out, w);
+  return for_each_pass(pp, B, [&](int b0, int rows, int) {
+    return postnet_forward(m, (hipStream_t)hip_stream, d_mel + (size_t)b0 * T_mel * m->hp.num_mels, sel.rows_from(b0, m->hp.num_speakers), rows, T_mel,
+                           d_linear + (size_t)b0 * T_mel * m->hp.num_freq, d_post_out ? d_post_out + (size_t)b0 * T_mel * 2 * m->hp.post_rnn_size : nullptr, w);
+  });
 }
 int taco_postnet_forward(taco_model* m, void* hip_stream, const float* d_mel, const int32_t* d_speaker_id, int B, int T_mel,
                          float* d_linear, float* d_post_out, void* d_workspace, size_t workspace_bytes) {

@@ -462,7 +462,7 @@ struct CbhgTape {
   float *res, *hx[10], *hH[8], *hT[8];
   float *xproj, *out, *gsave;
   float *dg, *rh, *d0, *d1, *dcat, *dbig0, *dbig1, *stat;
-  unsigned long long* gxbuf = nullptr; unsigned* gxctl = nullptr;      // k_bigru_duo: exchange granules, census words
+  Xchg gx;      // the whole-chip scans, forward and backward: exchange granules, census words
 };
 static void carve_cbhg_tape(Carver& cv, const Cbhg& c, int B, int T, CbhgTape& w) {
   const size_t M = (size_t)B * T, KC = (size_t)c.K * c.C;
@@ -479,14 +479,14 @@ static void carve_cbhg_tape(Carver& cv, const Cbhg& c, int B, int T, CbhgTape& w
   w.dg = cv.f(M * 6 * c.rnn); w.rh = cv.f(M * 2 * c.rnn);
   w.d0 = cv.f(M * wide); w.d1 = cv.f(M * wide); w.dcat = cv.f(M * 2 * c.rnn);
   w.dbig0 = cv.f(M * KC); w.dbig1 = cv.f(M * KC); w.stat = cv.f(5 * std::max<size_t>(KC, wide));   // sums, centred sums + the 3-vector SyncBN exchange pack
-  w.gxbuf = (unsigned long long*)cv.raw(std::max(gd_xbuf_granules(8), gb_xbuf_granules(8)) * sizeof(unsigned long long)); w.gxctl = (unsigned*)cv.raw(256);
+  w.gx.carve(cv, std::max(gd_xbuf_granules(8), gb_xbuf_granules(8)));
 }
 struct DecTape {     // every per-step tensor is [B, n, W]: step t of row b at (b*n + t)*W
   float *keys, *zero, *ctx, *pz[4], *hA, *rA, *uA, *cA, *rhA, *xcA, *alpha, *alpha0;
   float *o[5], *h[4], *r[4], *u[4], *c[4], *rh[4], *xc[4];
   int* nz;
   float* tape256 = nullptr; size_t tstride = 0;          // the 256-wide per-step arrays in DXT_* order, back to back (persistent decoder, TAPE)
-  unsigned long long* xbuf = nullptr; unsigned* dxctl = nullptr; float* rowbias = nullptr;   // its exchange granules, census words, 'simple' row biases
+  Xchg dx; float* rowbias = nullptr;   // its exchange granules and census words (the backward loop's too), 'simple' row biases
   // backward
   float *dkeys, *dvalues, *dv_acc, *dsb_acc, *dalpha, *dctx, *dctx_t, *dhA, *dh[4], *dht, *dhp, *tmp1, *tmp2, *do_[5];
   float *g_dgp[4], *g_dcp[4], *g_dgpA, *g_dcpA, *g_do0, *g_do2, *g_dq, *g_dz[4], *dpz, *dIn;
@@ -517,8 +517,7 @@ static void carve_dec_tape(Carver& cv, const taco_model* m, int B, int T_in, int
     for (int i = 0; i < L; ++i) { w.h[i] = cv.f(R * Hd); w.r[i] = cv.f(R * Hd); w.u[i] = cv.f(R * Hd); w.c[i] = cv.f(R * Hd); w.rh[i] = cv.f(R * Hd); w.xc[i] = cv.f(R * Hd); }
   }
   w.alpha = cv.f((size_t)B * (n + 1) * T_in); w.alpha0 = cv.f((size_t)B * T_in);   // slot 0 = initial alignments, slot t+1 = step t
-  { const size_t xb = (size_t)DX_NGROUP * std::max((size_t)dx_xlayout(8, T_in).total, dbx_xbuf_granules(T_in)) * sizeof(unsigned long long);
-    w.xbuf = (unsigned long long*)cv.raw(xb); w.dxctl = (unsigned*)cv.raw(256);
+  { w.dx.carve(cv, (size_t)DX_NGROUP * std::max((size_t)dx_xlayout(8, T_in).total, dbx_xbuf_granules(T_in)));
     w.rowbias = cv.f(is_simple(m) ? (size_t)B * DXRB_N * DX_W : 1); }
   w.nz = cv.i((size_t)n * B);
   w.dkeys = cv.f((size_t)B * T_in * A); w.dvalues = cv.f((size_t)B * T_in * D); w.dv_acc = cv.f((size_t)B * A); w.dsb_acc = cv.f(B);
@@ -688,9 +687,9 @@ static int cbhg_forward_train(const TrainCtx& x, const Cbhg& c, const CbhgT& ct,
   const ScanPlan sp = scan_plan(m, c, B, T, true);
   if (sp.kernel == SCAN_K_OCT || sp.kernel == SCAN_K_DUO) x.s->paths |= (unsigned)sp.kernel << CBHG_PATH_SCAN_FWD_SHIFT;
   if (sp.kernel == SCAN_K_OCT)     // the whole-chip scans of inference with the gate tape (k_bigru_oct<UPW, true> / k_bigru_duo<RG, true>)
-    return oct_launch(m, st, c, sp.upw, B, T, w.xproj, lengths, init_state, w.out, w.gsave, w.gxbuf, w.gxctl);
+    return oct_launch(m, st, c, sp.upw, B, T, w.xproj, lengths, init_state, w.out, w.gsave, w.gx);
   if (sp.kernel == SCAN_K_DUO)
-    return duo_launch(m, st, c, sp.rg, B, T, w.xproj, lengths, init_state, w.out, w.gsave, w.gxbuf, w.gxctl);
+    return duo_launch(m, st, c, sp.rg, B, T, w.xproj, lengths, init_state, w.out, w.gsave, w.gx);
   if (sp.kernel == SCAN_K_RES || sp.kernel == SCAN_K_QUAD) {     // recurrent weights resident on the CU (k_bigru_res; H = 128: k_bigru_quad, as inference runs it), gates saved for the backward scan
     BigruSArgs a; memset(&a, 0, sizeof a);
     a.xproj = w.xproj; a.g2_0 = (const float2*)AP(m, c.res_g2[0]); a.g2_1 = (const float2*)AP(m, c.res_g2[1]);
@@ -773,21 +772,23 @@ static int cbhg_backward(const TrainCtx& x, const Cbhg& c, const CbhgT& ct, cons
   // (the backward scans write the steps inside a row's length only; k_bigru_duo_bwd without lengths -- the post-net -- writes every element)
   const ScanPlan sp = scan_plan(m, c, B, T, true);
   const bool duo_bwd = sp.bwd != SCAN_BWD_ROWS;       // a whole-chip backward scan (k_bigru_duo_bwd / k_bigru_oct_bwd)
+  // The whole-chip backward scans poll w.gx like the forward ones, but do not clear it themselves: here its clear shares ONE fill launch with
+  // the two accumulators below (a launch and its graph edge less per CBHG and step), so duo_bwd_launch / oct_bwd_launch expect it done
   ZeroBatch zb(st);
   if (!(duo_bwd && !lengths)) {
     HIPCHK(zb.add(w.dg, (size_t)M * 6 * H * sizeof(float)));
     HIPCHK(zb.add(w.rh, (size_t)M * 2 * H * sizeof(float)));
   }
-  if (duo_bwd) HIPCHK(zb.add(w.gxbuf, (size_t)((char*)w.gxctl - (char*)w.gxbuf) + 256));
+  if (duo_bwd) HIPCHK(zb.add(w.gx.p, w.gx.bytes));
   HIPCHK(zb.run());
   if (sp.bwd == SCAN_BWD_OCT) {
     // one row per cluster of 8 CUs, as the forward scan of these shapes (k_bigru_oct_bwd)
     x.s->paths |= (unsigned)CBHG_SCAN_BWD_OCT << CBHG_PATH_SCAN_BWD_SHIFT;
-    TRY(oct_bwd_launch(m, st, c, B, T, dout, w.out, w.gsave, h0, lengths, w.dg, w.rh, dh0, w.gxbuf, w.gxctl));
+    TRY(oct_bwd_launch(m, st, c, B, T, dout, w.out, w.gsave, h0, lengths, w.dg, w.rh, dh0, w.gx));
   } else if (duo_bwd) {
     // both directions of RG rows per group of 32 CUs, the directions software-pipelined against each other (k_bigru_duo_bwd)
     x.s->paths |= (unsigned)CBHG_SCAN_BWD_DUO << CBHG_PATH_SCAN_BWD_SHIFT;
-    TRY(duo_bwd_launch(m, st, c, sp.rg, B, T, dout, w.out, w.gsave, h0, lengths, w.dg, w.rh, dh0, w.gxbuf, w.gxctl));
+    TRY(duo_bwd_launch(m, st, c, sp.rg, B, T, dout, w.out, w.gsave, h0, lengths, w.dg, w.rh, dh0, w.gx));
   } else if (H == 128 && x.t->resident_bwd_scan) {
     // recurrent kernels resident in registers, one workgroup per (direction, row) (k_bigru_resb): the encoder at the reference width
     BigruQArgs a; memset(&a, 0, sizeof a);
@@ -981,7 +982,7 @@ static int decoder_forward_train(const TrainCtx& x, const float* enc_out, int B,
     DxArgs ta; memset(&ta, 0, sizeof ta);
     ta.teacher = feed_back ? nullptr : teach; ta.own_fb = feed_back ? 1 : 0; ta.tape = w.tape256; ta.tstride = w.tstride; ta.tp_p2 = w.pz[np - 1]; ta.ld_p2 = Pz; ta.tp_ctx = w.ctx; ta.ld_ctx = Dc;
     ta.tp_e = w.g_e; ta.tp_alpha = w.alpha;
-    return dx_launch(m, st, dp, enc_out, SpkSel(), spk_emb, nullptr, B, T_in, n, nullptr, mel, align_hist, nullptr, 0, w.keys, w.nz, w.xbuf, w.dxctl, w.rowbias,
+    return dx_launch(m, st, dp, enc_out, SpkSel(), spk_emb, nullptr, B, T_in, n, nullptr, mel, align_hist, nullptr, 0, w.keys, w.nz, w.dx, w.rowbias,
                      att_init, dec_init ? dec_init[0] : nullptr, dec_init ? dec_init[1] : nullptr, &ta);
   }
   for (int t = 0; t < n; ++t) {
@@ -1102,7 +1103,7 @@ static int decoder_backward(const TrainCtx& x, const float* enc_out, int B, int 
     a.g_dcpA = w.g_dcpA; a.g_dgpA = w.g_dgpA; a.g_dz1 = w.g_dz[0]; a.g_dz2 = w.g_dz[1]; a.g_dq = w.g_dq; a.g_de = w.g_de; a.g_dctx = w.g_dctx;
     a.d_att_init = d_att_init; a.d_h10 = d_dec_init ? d_dec_init[0] : nullptr; a.d_h20 = d_dec_init ? d_dec_init[1] : nullptr;
     a.dsb_acc = w.dsb_acc;
-    TRY(dbx_launch(m, st, bp, a, B, T_in, n, w.xbuf, w.dxctl));
+    TRY(dbx_launch(m, st, bp, a, B, T_in, n, w.dx));
     if (S) {
       // 'simple': d speaker embedding = sum over steps of [d o0 . Wcc^T]_spk + [d c_pre(att) . Wc^T + d gates(att) . Wg^T]_spk.  Linear in the
       // pre-activation gradients: sum those over time first, then ONE transposed product each (the per-stage chain adds step by step).

@@ -120,9 +120,9 @@ int taco_train_debug_bigru(taco_train* t, void* hip_stream, const float* xproj, 
   const taco_model* m = t->sm; const Cbhg& c = m->post; const int H = c.rnn;
   hipStream_t st = (hipStream_t)hip_stream;
   HIPCHK(hipSetDevice(m->device));
-  const size_t need = std::max(gd_xbuf_granules(8), gb_xbuf_granules(8)) * sizeof(unsigned long long) + 512;
-  if (scratch_bytes < need) return fail(TACO_ERR_STATE, "scratch too small: need %zu bytes", need);
-  unsigned long long* gxbuf = (unsigned long long*)scratch; unsigned* gxctl = (unsigned*)((char*)scratch + need - 256);
+  Carver cv(scratch, scratch_bytes);
+  Xchg gx; gx.carve(cv, std::max(gd_xbuf_granules(8), gb_xbuf_granules(8)));
+  if (!cv.ok()) return fail(TACO_ERR_STATE, "scratch too small: need %zu bytes", cv.off);
   const size_t M = (size_t)B * T;
   HIPCHK(zero_async(gsave, M * 6 * H * sizeof(float), st));
   HIPCHK(zero_async(dg, M * 6 * H * sizeof(float), st));
@@ -130,11 +130,11 @@ int taco_train_debug_bigru(taco_train* t, void* hip_stream, const float* xproj, 
   if (persistent) {
     const ScanPlan sp = scan_plan(m, c, B, T, true);
     if (sp.bwd == SCAN_BWD_ROWS) return fail(TACO_ERR_UNSUPPORTED, "the whole-chip scans need H = 256, at most 64 rows and an unpartitioned MI355X");
-    if (sp.kernel == SCAN_K_OCT) TRY(oct_launch(m, st, c, sp.upw, B, T, xproj, lengths, h0, out, gsave, gxbuf, gxctl));      // as the training forward picks
-    else TRY(duo_launch(m, st, c, sp.rg, B, T, xproj, lengths, h0, out, gsave, gxbuf, gxctl));
-    HIPCHK(zero_async(gxbuf, need - 256 + 256, st));
-    if (sp.bwd == SCAN_BWD_OCT) return oct_bwd_launch(m, st, c, B, T, dout, out, gsave, h0, lengths, dg, rh, dh0, gxbuf, gxctl);      // as the training step picks
-    return duo_bwd_launch(m, st, c, sp.rg, B, T, dout, out, gsave, h0, lengths, dg, rh, dh0, gxbuf, gxctl);
+    if (sp.kernel == SCAN_K_OCT) TRY(oct_launch(m, st, c, sp.upw, B, T, xproj, lengths, h0, out, gsave, gx));      // as the training forward picks
+    else TRY(duo_launch(m, st, c, sp.rg, B, T, xproj, lengths, h0, out, gsave, gx));
+    HIPCHK(gx.clear(st));      // (the backward launchers expect their caller to have cleared: cbhg_backward)
+    if (sp.bwd == SCAN_BWD_OCT) return oct_bwd_launch(m, st, c, B, T, dout, out, gsave, h0, lengths, dg, rh, dh0, gx);      // as the training step picks
+    return duo_bwd_launch(m, st, c, sp.rg, B, T, dout, out, gsave, h0, lengths, dg, rh, dh0, gx);
   }
   if (H != 256) return fail(TACO_ERR_UNSUPPORTED, "post-net rnn size %d", H);
   { BigruSArgs a; memset(&a, 0, sizeof a);

@@ -204,6 +204,32 @@ def test_other_presets_on_the_persistent_decoder(preset, atype, B):
         assert "persistent k_decoder_xcd<%d, attention %d, %d prenet layers>" % (4 if B <= 32 else 8, ohp.attention_size, len(ohp.dec_prenet_sizes)) in plan, plan
 
 
+def test_state_dump_of_40_rows_at_attention_512_in_the_stage_workspace():
+    """attention_size 512, 40 rows: the plain decoder call is two passes of 20 on the persistent engine, the call with the per-step state dump ONE
+    pass of 40 rows on the launch-per-stage engine -- in a workspace of exactly taco_stage_workspace_bytes(m, 40, 21) bytes (Tacotron._stage_ws),
+    which sizes the decoder from the larger of the two plans.  Same function on both engines: mel and alignments to the 2e-5 of
+    test_write_through_protocol_and_launch_engine_agree, the stop words equal."""
+    import torch
+    B, T_in, n = 40, 21, 5
+    ohp = O.OracleHParams(max_iters=n, **PRESETS["attention_512_two_prenet_layers"])
+    w = O.init_weights(ohp, 1, 343)
+    ids, L = O.synthetic_inputs(B, T_in, 344, ragged=True)
+    m = build_model(ohp, w)
+    assert "no instantiation at 8 rows per group" in m.engine_plan(B, T_in, debug=True) and "40 rows = 2 passes of 20" in m.engine_plan(B, T_in)
+    enc = m.encoder(ids, L)
+    mel_d, al_d, stop_d, dbg = m.decoder(enc, n, debug=True)
+    torch.cuda.synchronize()
+    assert m.decoder_engine_info()["protocol"] == 0 and bool(torch.isfinite(dbg).all())
+    mel_p, al_p, stop_p, _ = m.decoder(enc, n)
+    torch.cuda.synchronize()
+    assert m.decoder_engine_info()["protocol"] in (1, 2)
+    e_mel, e_al = maxabs(mel_d.cpu().numpy(), mel_p.cpu().numpy()), maxabs(al_d.cpu().numpy(), al_p.cpu().numpy())
+    print("state dump vs two passes: max|mel| %.3g  max|alignments| %.3g  stop %d / %d" % (e_mel, e_al, int(stop_d.item()), int(stop_p.item())))
+    assert e_mel < 2e-5 and e_al < 2e-5
+    assert int(stop_d.item()) == int(stop_p.item())
+    m.check_device_errors()
+
+
 @pytest.mark.parametrize("preset,model_type", [("single_speaker", "simple"), ("deep_voice_2_first_block", "simple"), ("single_speaker_generalization", "deepvoice")])
 def test_other_presets_multi_speaker_manual_attention_and_end_to_end(preset, model_type):
     """... with the multi-speaker model types ('simple': the speaker rows of the attention GRU sit behind a 64-row prenet output
@@ -555,7 +581,7 @@ FF_MODES = {   # taco_debug_set_bf3(on): words that include/taco_debug.h documen
     1: (["three products", "k_cbhg_front<1, 144, 128, 16>", "k_cbhg_front<2, 80, 80, 8>", "k_pointwise_chain<128> (the last projection in its entry)",
          "k_pointwise_chain<256> (the last projection in its entry)", "encoder prenet: one k_pointwise_chain launch", "k_head_sweep<512>"], [" -- no ", "k_front_combine"]),
     5: (["no k_pointwise_chain: taco_debug_set_bf3 bit 2", "point-wise layers on k_gemm_bf3", "k_cbhg_front<", "k_front_combine", "1 projection on k_gemm_bf3",
-         "encoder prenet: one GEMM launch per layer", "k_zero_fill_multi", "k_head_sweep<512>"], ["k_pointwise_chain<"]),
+         "encoder prenet: one GEMM launch per layer", "k_zero_fill in front", "k_head_sweep<512>"], ["k_pointwise_chain<"]),
     9: (["conv bank and proj_1 on k_gemm_bf3", "no k_cbhg_front: taco_debug_set_bf3 bit 3", "k_pointwise_chain<256>", "encoder prenet: one k_pointwise_chain launch"],
         ["k_cbhg_front<", "k_front_combine", "in its entry"]),
     17: (["k_cbhg_front<1, 144, 128, 16> + k_front_combine", "no fused chain entry: taco_debug_set_bf3 bit 4", "k_pointwise_chain<256>"], ["in its entry"]),

@@ -616,6 +616,123 @@ def test_more_than_64_rows_on_the_persistent_engine_and_the_eager_entry_point():
     assert m2.stop_step == 1
 
 
+@pytest.mark.parametrize("B", [65, 130])
+def test_stage_entries_serve_more_than_64_rows_as_passes_of_equal_size(B):
+    """taco_encoder_forward, taco_decoder_forward (with its stop word) and taco_postnet_forward on 65 rows (two passes of 33) and 130 (three of
+    44): against the oracle at the tolerance of test_more_than_64_rows_run_as_passes_of_equal_size, and the second pass's rows == those rows
+    served alone, to the bit.  The stop word of the batch is the maximum over the passes.  The per-step state dump is one pass: refused."""
+    import torch
+    import taco_amd
+    ohp = tiny_hp(max_iters=3)
+    n = ohp.max_iters
+    w = O.init_weights(ohp, 1, 55)
+    ids, L = O.synthetic_inputs(B, 7, 56, ragged=True)
+    taps = {}
+    ref = O.forward(w, ohp, ids, L, honor_stop=False, taps=taps)
+    m = build_model(ohp, w)
+    passes = (B + 63) // 64
+    rows = (B + passes - 1) // passes
+    sl = slice(rows, 2 * rows)
+    enc = m.encoder(ids, L)
+    assert torch.equal(enc[sl], m.encoder(ids[sl], L[sl]))
+    assert maxabs(enc.cpu().numpy(), taps["encoder"]) < 1e-3
+    mel, al, stop, _ = m.decoder(enc, n)
+    alone = [m.decoder(enc[p * rows:(p + 1) * rows], n) for p in range(passes)]
+    assert torch.equal(mel[sl], alone[1][0]) and torch.equal(al[sl], alone[1][1])
+    assert int(stop.item()) == max(int(a[2].item()) for a in alone) and 1 <= int(stop.item()) <= n
+    lin = m.postnet(mel)
+    assert torch.equal(lin[sl], m.postnet(mel[sl]))
+    torch.cuda.synchronize()
+    _check((mel.cpu().numpy(), lin.cpu().numpy(), al.cpu().numpy()), ref)
+    if B == 65:
+        with pytest.raises(taco_amd._lib.TacoError, match="the per-step state dump is laid out .step..row.: at most 64 rows per call"):
+            m.decoder(enc, n, debug=True)
+    m.check_device_errors()
+
+
+_POISON_MODELS = {}
+
+
+def _poison_model(name):
+    """The two models of test_a_poisoned_workspace_does_not_reach_the_outputs, built once: the reference widths, and the one existing preset
+    with a 256-wide encoder (tests/test_pack_host.py case 3: its encoder scans on the whole-chip kernels too; deepvoice, three speakers)."""
+    if name not in _POISON_MODELS:
+        if name == "reference":
+            ohp, ns = O.OracleHParams(max_iters=3), 1
+        else:
+            from test_pack_host import CASES
+            ohp, ns = CASES["3_deepvoice_table"][:2]
+        _POISON_MODELS[name] = (build_model(ohp, O.init_weights(ohp, ns, 61), num_speakers=ns), ohp, ns)
+    return _POISON_MODELS[name]
+
+
+@pytest.mark.parametrize("mode", [1, 5])
+@pytest.mark.parametrize("B", [3, 96])
+@pytest.mark.parametrize("name", ["reference", "encoder_256_wide"])
+def test_a_poisoned_workspace_does_not_reach_the_outputs(name, B, mode):
+    """The forward twin of test_a_poisoned_workspace_does_not_reach_the_gradients.  The persistent kernels poll exchange granules, census words
+    and stop flags that must be zero at launch; who clears them travels explicitly (csrc/taco_lib.hip: Polled, UpFrontClear): ONE launch of the
+    forward -- riders of the encoder prenet's chain launch (taco_debug_set_bf3 1) or k_zero_fill in front (5) -- or the stage itself when it is
+    reached through its own entry point.  Eager taco_forward_infer and each stage entry, twice on the same buffers, the workspace all zero
+    bytes the first time and all 0xFF the second: outputs and stop words equal to the bit, no device error.  96 rows: two passes over ONE
+    workspace, each clearing what the one before left behind."""
+    import torch
+    import taco_amd
+    from util import dev, ptr, stream
+    m, ohp, ns = _poison_model(name)
+    lib, h, chk = m._lib, m._handle, taco_amd._lib.check
+    T_in, n, r = 16, 3, ohp.reduction_factor
+    T_mel = n * r
+    ids, L = O.synthetic_inputs(B, T_in, 62, ragged=True)
+    idd, Ld = dev(ids), dev(L)
+    spk = dev((np.arange(B) % ns).astype(np.int32)) if ns > 1 else None
+    rs = np.random.RandomState(63)
+    enc_in = dev(rs.uniform(-1, 1, (B, T_in, 2 * ohp.enc_rnn_size)), torch.float32)
+    mel_in = dev(rs.uniform(0, 1, (B, T_mel, ohp.num_mels)), torch.float32)
+    nb = max(int(lib.taco_workspace_bytes(h, B, T_in, n)), int(lib.taco_stage_workspace_bytes(h, B, max(T_in, T_mel))))
+    ws = torch.empty((nb,), dtype=torch.uint8, device="cuda")
+
+    def nan(*shape):
+        return torch.full(shape, float("nan"), device="cuda")
+
+    def run_all(fill):
+        out = {}
+        mel, lin, al, stop = nan(B, T_mel, ohp.num_mels), nan(B, T_mel, ohp.num_freq), nan(B, T_in, n), torch.full((1,), -7, dtype=torch.int32, device="cuda")
+        ws.fill_(fill)
+        chk(lib.taco_forward_infer(h, stream(), ptr(idd), ptr(Ld), ptr(spk), B, T_in, n, ptr(None), ptr(mel), ptr(lin), ptr(al), ptr(stop), ptr(ws), nb))
+        out["forward"] = (mel, lin, al, stop)
+        enc = nan(B, T_in, 2 * ohp.enc_rnn_size)
+        ws.fill_(fill)
+        chk(lib.taco_encoder_forward(h, stream(), ptr(idd), ptr(Ld), ptr(spk), B, T_in, ptr(enc), ptr(ws), nb))
+        out["encoder"] = (enc,)
+        mel, al, stop = nan(B, T_mel, ohp.num_mels), nan(B, T_in, n), torch.full((1,), -7, dtype=torch.int32, device="cuda")
+        ws.fill_(fill)
+        chk(lib.taco_decoder_forward(h, stream(), ptr(enc_in), ptr(spk), B, T_in, n, ptr(None), ptr(None), ptr(mel), ptr(al), ptr(stop), ptr(None), ptr(ws), nb))
+        out["decoder"] = (mel, al, stop)
+        lin = nan(B, T_mel, ohp.num_freq)
+        ws.fill_(fill)
+        chk(lib.taco_postnet_forward(h, stream(), ptr(mel_in), ptr(spk), B, T_mel, ptr(lin), ptr(None), ptr(ws), nb))
+        out["postnet"] = (lin,)
+        torch.cuda.synchronize()
+        return out
+
+    chk(lib.taco_debug_set_bf3(h, mode, 0))
+    try:
+        plan = m.engine_plan(B, T_in, T_mel)
+        rides = "the forward's zero fills ride in it" in plan
+        assert rides != ("k_zero_fill in front" in plan), plan
+        assert name != "reference" or rides == (mode == 1), plan
+        clean, poisoned = run_all(0), run_all(0xFF)
+        m.check_device_errors()
+        for stage in clean:
+            for a, b in zip(clean[stage], poisoned[stage]):
+                assert bool(torch.isfinite(a.float()).all()), stage
+                assert torch.equal(a, b), stage
+        assert 1 <= int(clean["forward"][3].item()) <= n and 1 <= int(clean["decoder"][2].item()) <= n
+    finally:
+        lib.taco_debug_set_bf3(h, 1, 0)
+
+
 def test_bad_shapes_are_errors():
     ohp = tiny_hp(max_iters=2)
     m = build_model(ohp, O.init_weights(ohp, 1, 55))

@@ -132,6 +132,37 @@ def test_stop_steps_per_group_of_rows(ctx):
         L.check(m._lib.taco_stop_steps(stream(), ptr(yd), B, n, width, 5, ptr(out)))      # 12 rows do not split into groups of 5
 
 
+@pytest.mark.parametrize("groups", [1, 3, 4, 5, 9])
+@pytest.mark.parametrize("offset", [0, 4, 8, 12])
+def test_stop_steps_clears_exactly_its_words_at_any_alignment(ctx, offset, groups):
+    """taco_stop_steps clears d_stop with the fill kernel before k_stop_groups takes its maxima: d_stop at 0 / 4 / 8 / 12 bytes from a 256-byte
+    boundary (16-byte stores only from an aligned base, single words otherwise) and 1 / 3 / 4 / 5 / 9 words (no 16-byte store, one, one and
+    a tail word, two and a tail word), inside a buffer of 0x7F7F7F7F words: the results are those of the restatement of
+    test_stop_steps_per_group_of_rows -- a word left uncleared would win its maximum -- and no word outside the range is touched."""
+    import ctypes as C
+    import torch
+    ohp, w, m, L = ctx
+    rs = np.random.RandomState(100 * offset + groups)
+    rows, n, width = 2, 9, 6
+    B = groups * rows
+    y = rs.randn(B, n, width).astype(np.float32)
+    first = rs.randint(0, n + 3, size=B)                  # >= n: the row never stops
+    for b in range(B):
+        if first[b] < n:
+            y[b, first[b]] = 0.0
+        y[b, :min(first[b], n), 0] += 10.0                # no accidental earlier zero step
+    want = np.array([min(max(min(f, n) for f in first[g * rows:(g + 1) * rows]) + 1, n) for g in range(groups)], np.int32)
+    yd = dev(y, torch.float32)
+    buf = torch.full((256,), 0x7F7F7F7F, dtype=torch.int32, device="cuda")
+    lo = (-buf.data_ptr() % 256) // 4 + 64 + offset // 4          # word index of d_stop: `offset` bytes behind a 256-byte boundary, 64 words and more in front
+    assert (buf.data_ptr() + 4 * lo) % 256 == offset and lo + groups + 64 <= 256
+    L.check(m._lib.taco_stop_steps(stream(), ptr(yd), B, n, width, rows, C.c_void_p(buf.data_ptr() + 4 * lo)))
+    torch.cuda.synchronize()
+    got = buf.cpu().numpy()
+    assert np.array_equal(got[lo:lo + groups], want), (got[lo:lo + groups], want, first)
+    assert (got[:lo] == 0x7F7F7F7F).all() and (got[lo + groups:] == 0x7F7F7F7F).all()
+
+
 def _split_bf16_gemm_checks(ctx, seed):
     """The five checks of test_split_bf16_gemm_every_tile_shape on whatever tile is in force; returns the outputs."""
     import torch

@@ -77,6 +77,23 @@ def test_the_library_exports_the_mix_entry_points_and_the_prototypes_carry_them(
     assert lib.taco_postnet_forward_mix(z, z, z, z, 1, 1, z, z, z, 0) == _lib.TACO_ERR_ARG
 
 
+@pytest.mark.parametrize("B", [8, 96])
+def test_a_null_model_is_refused_the_same_way_at_any_batch_size(B):
+    """The forward and the three stage entries, with ids and with weights: arguments are validated before the batch is split into passes, so a
+    null model is TACO_ERR_ARG ("null model") at 96 rows as at 8 -- and before any HIP call (there is no device to set)."""
+    from taco_amd import _lib
+    lib = _lib.load_library()
+    z = C.c_void_p(0)
+    for sfx in ("", "_mix"):
+        calls = [(getattr(lib, "taco_forward_infer" + sfx), (z, z, z, z, z, B, 5, 3, z, z, z, z, z, z, 0)),
+                 (getattr(lib, "taco_encoder_forward" + sfx), (z, z, z, z, z, B, 5, z, z, 0)),
+                 (getattr(lib, "taco_decoder_forward" + sfx), (z, z, z, z, B, 5, 3, z, z, z, z, z, z, z, 0)),
+                 (getattr(lib, "taco_postnet_forward" + sfx), (z, z, z, z, B, 5, z, z, z, 0))]
+        for fn, a in calls:
+            assert fn(*a) == _lib.TACO_ERR_ARG, (fn.__name__, B)
+            assert lib.taco_last_error() == b"null model", (fn.__name__, B, lib.taco_last_error())
+
+
 def test_the_header_declares_each_mix_entry_point_with_its_namesakes_arguments():
     import os
     text = open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "include", "taco_abi.h")).read()
