@@ -9,7 +9,14 @@
 //   * wave (wm, wn) owns rows 64/WM * wm .. and the 32 columns 32 wn .. of every W-wide layer, streams its weight fragments from
 //     the layer's pack (L2) one k16 step ahead, and keeps its own 32 x 32 (x TM) slice of the layer's fp32 output in registers:
 //     the highway carry  y = H*T + x*(1-T)  needs x exactly where the lane produced it one layer earlier;
-//   * between layers: barrier, the lanes write their outputs into the planes, barrier;
+//   * between layers (a seam): the lanes write their outputs into a SECOND plane set, one barrier, the sets swap.  Round 18 (profiles/r18_*):
+//     until then a seam was barrier ("every wave has read the planes") - 64 ds_write_b16 per lane - barrier.  Now (1) layer l reads one set and
+//     writes the other, so only "all writes done before anyone reads" is left to wait for; (2) the first weight fragments and the biases of the
+//     product loop behind the seam are requested before the epilogue in front of it (ch_request), the entry's first proj_2 block and per-column
+//     operands before the wait for the partial sums; (3) the last link runs its passes from the upper column groups down and no longer waits
+//     for each time-reversed store to be acknowledged (store_group).  Tried and left out, with their numbers where they stood: 32-bit plane
+//     writes by lane pairs (ch_write_planes), four parts' sums in flight at W = 128 (the entry).  No FMA chain, summation order or K rotation
+//     moved: tests/test_gpu_chain_seams.py holds the forward to the bits of the build before;
 //   * the last link (N = 6H columns) loops over column groups of W and stores straight to the projection buffer, the backward
 //     direction's columns time-reversed per row (tf.reverse_sequence, A.7) exactly as k_gemm_bf3's epilogue does.
 //
@@ -72,24 +79,42 @@ struct ChainArgs {
   ChainLayer L[CH_MAXL];
 };
 
-// one layer's K loop for the wave's TM row tiles and one 32-column tile (DUAL: two products that share the A fragments -- the H and
-// T matrices of a highway layer at the same column tile, or two column tiles nt, nt2 of one matrix): weight fragments (hi, lo) one
-// k16 step ahead in two register sets that swap roles (K16 is even: pack_bf3 pads K to a multiple of 32)
+// One product loop of a wave: a layer's K for its TM row tiles and one 32-column tile nt of the pack (bhA, blA); dual: a second product that
+// shares the A fragments -- the T matrix of a highway layer at the same column tile, or column tile nt2 of the same matrix.  rot: the
+// workgroup's first k16 step (CH_ROT): the CUs of an XCD walk the layer's K in the same order but from different starts, so that at any moment
+// they ask the L2 for DIFFERENT 8 KB slices of the pack instead of all 32 for the same one
+struct ChProd {
+  const unsigned short* bhA; const unsigned short* blA; const unsigned short* bhB; const unsigned short* blB;
+  int K16, NT, nt, nt2, rot; bool dual;
+};
+// the register sets of weight fragments (hi, lo; h2, l2: the second product's) that a product loop rotates through
+template <int CH_PF> struct ChFrag { uint4 h[CH_PF], l[CH_PF], h2[CH_PF], l2[CH_PF]; };
+__device__ __forceinline__ int ch_kstep(const ChProd& p, int g) { const int gg = min(g, p.K16 - 1) + p.rot; return gg >= p.K16 ? gg - p.K16 : gg; }
+__device__ __forceinline__ size_t ch_boff(const ChProd& p, int g, int t, int l31, int lh) { return ((((size_t)ch_kstep(p, g) * p.NT + t) * 2 + lh) * 32 + l31) * 8; }
+// The loads a product loop needs before its first MFMA -- steps 0 .. CH_PF - 1 into sets 0 .. CH_PF - 1 -- as a call of their own: the
+// product (ChProd) depends on the layer alone, not on the activations, so the kernel asks for them BEFORE the epilogue and the barrier of
+// the seam in front of the loop, and the L2 round trip runs under the seam instead of behind it.  ch_mma_loop takes the sets as loaded here.
+template <int CH_PF>
+__device__ __forceinline__ void ch_request(const ChProd& p, int l31, int lh, ChFrag<CH_PF>& fr) {
+#pragma unroll
+  for (int i = 0; i < CH_PF; ++i) {
+    const size_t o = ch_boff(p, i, p.nt, l31, lh);
+    fr.h[i] = *reinterpret_cast<const uint4*>(p.bhA + o); fr.l[i] = *reinterpret_cast<const uint4*>(p.blA + o);
+    fr.h2[i] = fr.l2[i] = make_uint4(0, 0, 0, 0);
+    if (p.dual) { const size_t o2 = ch_boff(p, i, p.nt2, l31, lh); fr.h2[i] = *reinterpret_cast<const uint4*>(p.bhB + o2); fr.l2[i] = *reinterpret_cast<const uint4*>(p.blB + o2); }
+  }
+}
+// the loop itself (DUAL == p.dual): weight fragments one k16 step ahead in two register sets that swap roles (K16 is even: pack_bf3 pads K to
+// a multiple of 32); fr holds steps 0 .. CH_PF - 1 on entry (ch_request)
 template <int TM, int LDSW, bool DUAL, int CH_PF>
-__device__ __forceinline__ void ch_mma_loop(int K16, int NT, const unsigned short* bhA, const unsigned short* blA, int nt,
-                                            const unsigned short* bhB, const unsigned short* blB, int nt2,
-                                            const unsigned short* xhi, const unsigned short* xlo, int row0,
-                                            int l31, int lh, f32x16 (&acc)[TM], f32x16 (&acc2)[TM], int rot = 0) {
-  // rot: the workgroup's first k16 step (CH_ROT): the CUs of an XCD walk the layer's K in the same order but from different starts, so
-  // that at any moment they ask the L2 for DIFFERENT 8 KB slices of the pack instead of all 32 for the same one
-  auto kstep = [&](int g) { const int gg = min(g, K16 - 1) + rot; return gg >= K16 ? gg - K16 : gg; };
-  auto boff = [&](int g, int t) { return ((((size_t)kstep(g) * NT + t) * 2 + lh) * 32 + l31) * 8; };
-  uint4 ph, pl, ph2, pl2, qh, ql, qh2, ql2;
-  ph2 = pl2 = qh2 = ql2 = make_uint4(0, 0, 0, 0);
+__device__ __forceinline__ void ch_mma_loop(const ChProd& p, ChFrag<CH_PF>& fr, const unsigned short* xhi, const unsigned short* xlo, int row0,
+                                            int l31, int lh, f32x16 (&acc)[TM], f32x16 (&acc2)[TM]) {
+  const int K16 = p.K16;
+  auto kstep = [&](int g) { return ch_kstep(p, g); };
   auto loadb = [&](int g, uint4& h, uint4& l, uint4& h2, uint4& l2) {
-    const size_t o = boff(g, nt);
-    h = *reinterpret_cast<const uint4*>(bhA + o); l = *reinterpret_cast<const uint4*>(blA + o);
-    if constexpr (DUAL) { const size_t o2 = boff(g, nt2); h2 = *reinterpret_cast<const uint4*>(bhB + o2); l2 = *reinterpret_cast<const uint4*>(blB + o2); }
+    const size_t o = ch_boff(p, g, p.nt, l31, lh);
+    h = *reinterpret_cast<const uint4*>(p.bhA + o); l = *reinterpret_cast<const uint4*>(p.blA + o);
+    if constexpr (DUAL) { const size_t o2 = ch_boff(p, g, p.nt2, l31, lh); h2 = *reinterpret_cast<const uint4*>(p.bhB + o2); l2 = *reinterpret_cast<const uint4*>(p.blB + o2); }
   };
   auto mma = [&](int g, const uint4& h, const uint4& l, const uint4& h2, const uint4& l2) {
     const bf16x8 bh = __builtin_bit_cast(bf16x8, h), bl = __builtin_bit_cast(bf16x8, l);
@@ -117,41 +142,62 @@ __device__ __forceinline__ void ch_mma_loop(int K16, int NT, const unsigned shor
     }
   };
   if constexpr (CH_PF == 2) {
-  loadb(0, ph, pl, ph2, pl2);
-  for (int g = 0; g < K16; g += 2) {
-    loadb(g + 1, qh, ql, qh2, ql2);
+  // steps 0 and 1 are in the sets already: the first round asks for step 2 only
+  __builtin_amdgcn_sched_barrier(0);
+  mma(0, fr.h[0], fr.l[0], fr.h2[0], fr.l2[0]);
+  __builtin_amdgcn_sched_barrier(0);
+  loadb(2, fr.h[0], fr.l[0], fr.h2[0], fr.l2[0]);
+  __builtin_amdgcn_sched_barrier(0);
+  mma(1, fr.h[1], fr.l[1], fr.h2[1], fr.l2[1]);
+  __builtin_amdgcn_sched_barrier(0);
+  for (int g = 2; g < K16; g += 2) {
+    loadb(g + 1, fr.h[1], fr.l[1], fr.h2[1], fr.l2[1]);
     __builtin_amdgcn_sched_barrier(0);
-    mma(g, ph, pl, ph2, pl2);
+    mma(g, fr.h[0], fr.l[0], fr.h2[0], fr.l2[0]);
     __builtin_amdgcn_sched_barrier(0);
-    loadb(g + 2, ph, pl, ph2, pl2);
+    loadb(g + 2, fr.h[0], fr.l[0], fr.h2[0], fr.l2[0]);
     __builtin_amdgcn_sched_barrier(0);
-    mma(g + 1, qh, ql, qh2, ql2);
+    mma(g + 1, fr.h[1], fr.l[1], fr.h2[1], fr.l2[1]);
     __builtin_amdgcn_sched_barrier(0);
   }
   } else {
   // a ring of CH_PF register sets: the fragments of step g + CH_PF - 1 are requested before step g is multiplied.  One step ahead
   // (round 3) left every k16 step waiting for L2: a workgroup had 32 KB in flight, and a CU's share of the L2 stream at that depth
   // is ~27 GB/s -- a quarter of what it reaches with 8 loads per lane outstanding (MI355X_MICROARCH.md, hand-off payload row)
-  uint4 rh[CH_PF], rl[CH_PF], rh2[CH_PF], rl2[CH_PF];
-#pragma unroll
-  for (int i = 0; i < CH_PF; ++i) rh2[i] = rl2[i] = make_uint4(0, 0, 0, 0);
-#pragma unroll
-  for (int i = 0; i < CH_PF - 1; ++i) loadb(i, rh[i], rl[i], rh2[i], rl2[i]);
   for (int g = 0; g < K16; g += CH_PF) {
 #pragma unroll
     for (int i = 0; i < CH_PF; ++i) {
-      loadb(g + i + CH_PF - 1, rh[(i + CH_PF - 1) % CH_PF], rl[(i + CH_PF - 1) % CH_PF], rh2[(i + CH_PF - 1) % CH_PF], rl2[(i + CH_PF - 1) % CH_PF]);
+      const int s = (i + CH_PF - 1) % CH_PF;
+      if (i > 0 || g > 0) loadb(g + i + CH_PF - 1, fr.h[s], fr.l[s], fr.h2[s], fr.l2[s]);      // (step CH_PF - 1 came with ch_request)
       __builtin_amdgcn_sched_barrier(0);
-      if (g + i < K16) mma(g + i, rh[i], rl[i], rh2[i], rl2[i]);
+      if (g + i < K16) mma(g + i, fr.h[i], fr.l[i], fr.h2[i], fr.l2[i]);
       __builtin_amdgcn_sched_barrier(0);
     }
   }
   }
 }
+// The lane's slice of a layer's output -> the (hi, lo) planes: a lane holds ONE column (col) of 16 rows per row tile and writes 2-byte elements.
+// row0: first row of the lane's C elements (row tile 0, register 0); on: the lane's column lies inside the planes.
+// (Round 18 tried 32-bit writes: a lane pair swaps half of its values with one DPP move each, quad_perm [1,0,3,2], and each lane writes words of
+// two neighbouring columns -- half the ds_write count and packed conversions.  Same bits; k_pointwise_chain<256> 118.6 / 118.4 us without it
+// against 119.5 / 118.2 with it, <128> 50.9 / 51.4 against 51.1 / 50.9: the writes of a wave are not what the seam's one barrier waits for.  Left out.)
+template <int TM, int LDSW>
+__device__ __forceinline__ void ch_write_planes(unsigned short* xhi, unsigned short* xlo, int row0, int col, const float (&x)[TM][16], bool on) {
+#pragma unroll
+  for (int tm = 0; tm < TM; ++tm)
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      const float f = x[tm][r];
+      const unsigned hp = taco_pk_bf16(f, 0.f) & 0xffffu;
+      const unsigned lp = taco_pk_bf16(f - __uint_as_float(hp << 16), 0.f) & 0xffffu;
+      const int off = (row0 + tm * 32 + (r & 3) + 8 * (r >> 2)) * LDSW + col;
+      if (on) { xhi[off] = (unsigned short)hp; xlo[off] = (unsigned short)lp; }
+    }
+}
 
 #ifdef TACO_TRACE
 __device__ long long taco_trace_chain[64];      // slots: 0 entry, 1 partial sums in planes, 2 proj_2 products done, 3 entry epilogue done, 4 first barrier; then per layer:
-#define CTRC(i) do { if (trc && (i) < 64) taco_trace_chain[i] = clock64(); } while (0)      // products done, epilogue done, planes free, planes written
+#define CTRC(i) do { if (trc && (i) < 64) taco_trace_chain[i] = clock64(); } while (0)      // products done, epilogue done, plane writes issued, barrier passed; per pass of the last link: products done, stores issued
 #else
 #define CTRC(i) do {} while (0)
 #endif
@@ -165,8 +211,11 @@ __global__ __launch_bounds__(512) void k_pointwise_chain(const ChainArgs a_in) {
   constexpr int PF = W == 256 ? CH_PF256 : CH_PF128;
   constexpr int LDSW = W + 8;                                          // bf16 elements per plane row: (W + 8) * 2 bytes = odd multiple of 16
   extern __shared__ __attribute__((aligned(16))) unsigned short ch_smem[];
+  // two plane sets: a hidden layer reads (xhi, xlo) and writes its output into (yhi, ylo), then the two swap -- one barrier per seam
   unsigned short* xhi = ch_smem;
   unsigned short* xlo = ch_smem + CH_BM * LDSW;
+  unsigned short* yhi = ch_smem + 2 * CH_BM * LDSW;
+  unsigned short* ylo = ch_smem + 3 * CH_BM * LDSW;
   struct { const float* x; float* out; float* y; const int* rev_len; int ldx, Cin, ldo, ldy, rev_col0, M, T, nlayers; } a =
       {a_in.x, a_in.out, a_in.y, a_in.rev_len, a_in.ldx, a_in.Cin, a_in.ldo, a_in.ldy, a_in.rev_col0, a_in.M, a_in.T, a_in.nlayers};
   PIN(a.x); PIN(a.out); PIN(a.y); PIN(a.rev_len); PIN(a.ldx); PIN(a.Cin); PIN(a.ldo); PIN(a.ldy); PIN(a.rev_col0); PIN(a.M); PIN(a.T);
@@ -198,6 +247,34 @@ __global__ __launch_bounds__(512) void k_pointwise_chain(const ChainArgs a_in) {
 #endif
 
   const int l31_outer = l31, lh_outer = lh;
+  // column group of pass ps of the last link.  Two groups per pass share the A fragments; an odd group left over (6H = 3 W at W = 256: the backward
+  // direction's last columns) goes first, and the pairs follow from the LAST to the first: the time-reversed columns (>= rev_col0, the upper groups)
+  // are the slow stores, so they drain behind the products of the passes after them and the kernel ends on a pass of plain stores (at W = 128 the
+  // passes ran (0,1) (2,3) (4,5) until round 18, and the reversed stores of (4,5) were the kernel's tail).  Groups are independent of each other.
+  auto pass_group = [](int ngroups, int ps) { return ((ngroups & 1) && ps == 0) ? ngroups - 1 : 2 * ((ngroups + 1) / 2 - 1 - ps); };
+  // this wave's product of a hidden layer, or of pass ps of the last link
+  auto make_prod = [&](const ChainLayer& L, int ps) {
+    ChProd p;
+    p.bhA = p.bhB = L.bh; p.blA = p.blB = L.bl; p.K16 = L.K16; p.NT = L.NT; p.rot = krot * L.K16 >> 5; p.nt = p.nt2 = wn; p.dual = false;
+    if (L.type == CH_XPROJ) {
+      const int ngroups = (L.N + W - 1) / W, ng = pass_group(ngroups, ps);
+      p.nt = min(ng * WN + wn, L.NT - 1);      // tiles past the pack are clamped, never stored
+      p.dual = ng + 1 < ngroups;
+      p.nt2 = p.dual ? min((ng + 1) * WN + wn, L.NT - 1) : p.nt;
+    } else if (L.type == CH_HIGHWAY) { p.bhB = L.bh2; p.blB = L.bl2; p.dual = true; }
+    return p;
+  };
+  ChFrag<PF> fr;                               // first weight fragments of the NEXT product loop, requested ahead of the seam in front of it (ch_request)
+  float nbia = 0.f, nbia2 = 0.f;               // ... and the biases of the next hidden layer
+  auto request_layer = [&](int li, int l31r, int lhr) {
+    const ChainLayer Ln = a_in.L[li];
+    ch_request<PF>(make_prod(Ln, 0), l31r, lhr, fr);
+    if (Ln.type != CH_XPROJ) {
+      const int c = wn * 32 + l31r;
+      nbia = Ln.bias ? Ln.bias[c] : 0.f;
+      nbia2 = (Ln.type == CH_HIGHWAY && Ln.bias2) ? Ln.bias2[c] : 0.f;
+    }
+  };
   float xreg[TM][16];                          // the lane's slice of the current activation in fp32 (highway carry)
   bool have_x = false;
   if (a_in.e.part) {
@@ -207,11 +284,46 @@ __global__ __launch_bounds__(512) void k_pointwise_chain(const ChainArgs a_in) {
     const unsigned short* gbh = E.bh; const unsigned short* gbl = E.bl;
     const float* gres = E.res; const float* grv = E.rowvec; const float* gb2 = E.b2; const float* gs2 = E.s2; const float* gh2 = E.h2;
     PIN(gpart); PIN(gb1); PIN(gs1); PIN(gh1); PIN(gbh); PIN(gbl); PIN(gres); PIN(grv); PIN(gb2); PIN(gs2); PIN(gh2);
-    const int LDE = E.N1 + 8;                                              // bf16 per plane row (N1 = 128 / 256: odd multiple of 16 bytes)
-    unsigned short* ehi = ch_smem + 2 * CH_BM * LDSW;                      // behind the chain's own planes
+    constexpr int N1 = W;                                                  // (= E.N1: ff_plan admits the entry only where proj_1 is as wide as the chain)
+    constexpr int LDE = N1 + 8;                                            // bf16 per plane row (N1 = 128 / 256: odd multiple of 16 bytes)
+    // behind the first plane set, over the second: the entry's planes are dead once proj_2's products are done, and the first hidden layer writes
+    // plane set B only behind the barrier that ends the entry
+    unsigned short* ehi = ch_smem + 2 * CH_BM * LDSW;
     unsigned short* elo = ehi + (CH_BM + 2) * LDE;
-    const int nq = E.N1 / 4;
-    constexpr int NSTG = ((CH_BM + 2) * (256 / 4) + 511) / 512;          // float4 per thread at the widest N1
+    constexpr int nq = N1 / 4;
+    constexpr int NSTG = ((CH_BM + 2) * nq + 511) / 512;                   // float4 per thread and part: 9 at N1 = 256, 5 at 128
+    constexpr int NPART = 2;                                               // parts whose loads are in flight together
+    // proj_2's plan: wave (wm, wn) owns its TM row tiles x the 32 columns 32 wn .. (waves past the last column tile idle).
+    // W = 256 (one row of eight waves): N2 = 80 columns are three column tiles -- alone, three waves would run the whole contraction on
+    // three SIMDs, one wave each, while five wait (31 K of the workgroup's 220 K clocks at C2).  The contraction is cut in two K halves
+    // instead: waves NT2 .. 2 NT2 - 1 take the second half of the k16 steps of column tile wn - NT2 and hand their partial tile over
+    // through LDS (the chain's own planes are not written yet)
+    const int K0 = a_in.L[0].K16 * 16;                                     // columns of the chain's input planes (>= N2, zero padded)
+    const int col = wn * 32 + l31;
+    const bool cin = col < E.N2;
+    const int KSPL = (WM == 1 && 2 * E.NT2 <= WN) ? 2 : 1;
+    const bool mact = wn < E.NT2 * KSPL;
+    const int ect = mact ? wn % E.NT2 : 0, kp = mact ? wn / E.NT2 : 0;
+    const int nk = (3 * E.K16tap) / KSPL, kbeg = kp * nk, kend = kbeg + nk;      // k16 steps (tap, group) of this wave
+    auto boff = [&](int k) { return ((((size_t)k * E.NT2 + ect) * 2 + lh) * 32 + l31) * 8; };
+    // few waves per SIMD here, so the weight stream is requested a whole block of NB k16 steps ahead (two register
+    // sets that swap roles; nk = 3 N1 / 16 [/ 2] is a multiple of 2 NB): one step ahead left every step waiting ~800 clocks for L2
+    constexpr int NB = 6;                            // nk = 48, 24 (K halves) or 24: a multiple of 2 NB (the host admits N1 = 256 with W = 256, 128 with 128)
+    uint4 pH[NB], pL[NB], qH[NB], qL[NB];
+    auto loadblk = [&](int k0, uint4 (&H)[NB], uint4 (&Lo)[NB]) {
+#pragma unroll
+      for (int i = 0; i < NB; ++i) { const size_t o = boff(min(k0 + i, kend - 1)); H[i] = *reinterpret_cast<const uint4*>(gbh + o); Lo[i] = *reinterpret_cast<const uint4*>(gbl + o); }
+    };
+    // Requested BEFORE the wait for the partial sums, none of it depends on them: proj_2's first weight block and the per-column operands of both
+    // epilogues (proj_1's are the same four columns for every float4 of a thread: 512 is a multiple of nq).  They were one L2 round trip each
+    // behind the sums / behind the products.
+    if (mact) loadblk(kbeg, pH, pL);
+    const int c1 = 4 * (tid % nq);
+    const float4 bi1 = gb1 ? *reinterpret_cast<const float4*>(gb1 + c1) : make_float4(0.f, 0.f, 0.f, 0.f);
+    const float4 sc1 = gs1 ? *reinterpret_cast<const float4*>(gs1 + c1) : make_float4(1.f, 1.f, 1.f, 1.f);
+    const float4 sh1 = gh1 ? *reinterpret_cast<const float4*>(gh1 + c1) : make_float4(0.f, 0.f, 0.f, 0.f);
+    const float bi2 = (cin && gb2) ? gb2[col] : 0.f, sc2 = (cin && gs2) ? gs2[col] : 1.f, sh2 = (cin && gh2) ? gh2[col] : 0.f;
+    __builtin_amdgcn_sched_barrier(0);
     {
       float4 f[NSTG];
       const float* src[NSTG];
@@ -219,29 +331,26 @@ __global__ __launch_bounds__(512) void k_pointwise_chain(const ChainArgs a_in) {
       for (int u = 0; u < NSTG; ++u) {
         const int i = tid + 512 * u, r = i / nq, c = 4 * (i - r * nq), row = m0 - 1 + r;
         f[u] = make_float4(0.f, 0.f, 0.f, 0.f);
-        src[u] = (i < (CH_BM + 2) * nq && row >= 0 && row < a.M) ? gpart + (size_t)row * E.N1 + c : nullptr;
+        src[u] = (i < (CH_BM + 2) * nq && row >= 0 && row < a.M) ? gpart + (size_t)row * N1 + c : nullptr;
       }
-      // parts in a fixed order (part q before part q + 1: bit-reproducible); the loads of TWO parts are in flight together -- a part's 9 loads per
-      // thread alone left a full memory round trip exposed per part (2 at the post-net, 8 at the encoder)
-      int q = 0;
-      for (; q + 1 < E.P; q += 2) {
-        float4 g[NSTG], g2[NSTG];
+      // parts in a fixed order (part q before part q + 1: bit-reproducible); the loads of NPART parts are in flight together -- a part's loads
+      // alone left a full memory round trip exposed per part (2 at the post-net, 8 at the encoder).  (Round 18: FOUR parts in flight at N1 = 128,
+      // where a part is 5 float4 per thread, i.e. two dependent round trips instead of four at the encoder: k_pointwise_chain<128> 51.1 / 50.9 us
+      // against 51.5 / 51.8 with two, inside the 0.8 us the launches of one run scatter by.  Left at two.)
+      for (int q = 0; q < E.P; q += NPART) {
+        float4 g[NPART][NSTG];
 #pragma unroll
-        for (int u = 0; u < NSTG; ++u) {
-          g[u] = src[u] ? *reinterpret_cast<const float4*>(src[u] + (size_t)q * E.MN) : make_float4(0.f, 0.f, 0.f, 0.f);
-          g2[u] = src[u] ? *reinterpret_cast<const float4*>(src[u] + (size_t)(q + 1) * E.MN) : make_float4(0.f, 0.f, 0.f, 0.f);
-        }
+        for (int j = 0; j < NPART; ++j)
+          if (q + j < E.P) {
 #pragma unroll
-        for (int u = 0; u < NSTG; ++u) { f[u].x += g[u].x; f[u].y += g[u].y; f[u].z += g[u].z; f[u].w += g[u].w; }
+            for (int u = 0; u < NSTG; ++u) g[j][u] = src[u] ? *reinterpret_cast<const float4*>(src[u] + (size_t)(q + j) * E.MN) : make_float4(0.f, 0.f, 0.f, 0.f);
+          }
 #pragma unroll
-        for (int u = 0; u < NSTG; ++u) { f[u].x += g2[u].x; f[u].y += g2[u].y; f[u].z += g2[u].z; f[u].w += g2[u].w; }
-      }
-      if (q < E.P) {
-        float4 g[NSTG];
+        for (int j = 0; j < NPART; ++j)
+          if (q + j < E.P) {
 #pragma unroll
-        for (int u = 0; u < NSTG; ++u) g[u] = src[u] ? *reinterpret_cast<const float4*>(src[u] + (size_t)q * E.MN) : make_float4(0.f, 0.f, 0.f, 0.f);
-#pragma unroll
-        for (int u = 0; u < NSTG; ++u) { f[u].x += g[u].x; f[u].y += g[u].y; f[u].z += g[u].z; f[u].w += g[u].w; }
+            for (int u = 0; u < NSTG; ++u) { f[u].x += g[j][u].x; f[u].y += g[j][u].y; f[u].z += g[j][u].z; f[u].w += g[j][u].w; }
+          }
       }
 #pragma unroll
       for (int u = 0; u < NSTG; ++u) {
@@ -249,9 +358,7 @@ __global__ __launch_bounds__(512) void k_pointwise_chain(const ChainArgs a_in) {
         if (i >= (CH_BM + 2) * nq) continue;
         float4 v = f[u];
         if (src[u]) {
-          const float4 bi = gb1 ? *reinterpret_cast<const float4*>(gb1 + c) : make_float4(0.f, 0.f, 0.f, 0.f);
-          const float4 sc = gs1 ? *reinterpret_cast<const float4*>(gs1 + c) : make_float4(1.f, 1.f, 1.f, 1.f);
-          const float4 sh = gh1 ? *reinterpret_cast<const float4*>(gh1 + c) : make_float4(0.f, 0.f, 0.f, 0.f);
+          const float4 bi = bi1, sc = sc1, sh = sh1;
           v.x += bi.x; v.y += bi.y; v.z += bi.z; v.w += bi.w;
           if (E.relu1) { v.x = fmaxf(v.x, 0.f); v.y = fmaxf(v.y, 0.f); v.z = fmaxf(v.z, 0.f); v.w = fmaxf(v.w, 0.f); }
           v.x = v.x * sc.x + sh.x; v.y = v.y * sc.y + sh.y; v.z = v.z * sc.z + sh.z; v.w = v.w * sc.w + sh.w;
@@ -264,11 +371,7 @@ __global__ __launch_bounds__(512) void k_pointwise_chain(const ChainArgs a_in) {
     }
     CTRC(1);
     __syncthreads();
-    // proj_2: wave (wm, wn) owns its TM row tiles x the 32 columns 32 wn .. (waves past the last column tile idle); SAME padding and the
-    // batch-row boundary by masking the A fragment per (row, tap) as k_gemm_bf3 does
-    const int K0 = a_in.L[0].K16 * 16;                                     // columns of the chain's input planes (>= N2, zero padded)
-    const int col = wn * 32 + l31;
-    const bool cin = col < E.N2;
+    // proj_2 (the plan above): SAME padding and the batch-row boundary by masking the A fragment per (row, tap) as k_gemm_bf3 does
     // (requested BEFORE the MFMA loop, whose duration hides them; all residual values of the lane are requested before the first is used: left in one loop with the LDS stores, every element
     // waited for its own load -- 32 memory round trips)
     float rs[TM][16];
@@ -288,27 +391,10 @@ __global__ __launch_bounds__(512) void k_pointwise_chain(const ChainArgs a_in) {
 #pragma unroll
     for (int tm = 0; tm < TM; ++tm)
       for (int r = 0; r < 16; ++r) acc[tm][r] = 0.f;
-    // W = 256 (one row of eight waves): N2 = 80 columns are three column tiles -- alone, three waves would run the whole contraction on
-    // three SIMDs, one wave each, while five wait (31 K of the workgroup's 220 K clocks at C2).  The contraction is cut in two K halves
-    // instead: waves NT2 .. 2 NT2 - 1 take the second half of the k16 steps of column tile wn - NT2 and hand their partial tile over
-    // through LDS (the chain's own planes are not written yet)
-    const int KSPL = (WM == 1 && 2 * E.NT2 <= WN) ? 2 : 1;
-    const bool mact = wn < E.NT2 * KSPL;
-    const int ect = mact ? wn % E.NT2 : 0, kp = mact ? wn / E.NT2 : 0;
     if (mact) {
       int tloc[TM];
 #pragma unroll
       for (int tm = 0; tm < TM; ++tm) tloc[tm] = (m0 + (wm * TM + tm) * 32 + l31) % a.T;
-      const int nk = (3 * E.K16tap) / KSPL, kbeg = kp * nk, kend = kbeg + nk;      // k16 steps (tap, group) of this wave
-      auto boff = [&](int k) { return ((((size_t)k * E.NT2 + ect) * 2 + lh) * 32 + l31) * 8; };
-      // few waves per SIMD here, so the weight stream is requested a whole block of NB k16 steps ahead (two register
-      // sets that swap roles; nk = 3 N1 / 16 [/ 2] is a multiple of 2 NB): one step ahead left every step waiting ~800 clocks for L2
-      constexpr int NB = 6;                            // nk = 48, 24 (K halves) or 24: a multiple of 2 NB (the host admits N1 = 256 with W = 256, 128 with 128)
-      uint4 pH[NB], pL[NB], qH[NB], qL[NB];
-      auto loadblk = [&](int k0, uint4 (&H)[NB], uint4 (&Lo)[NB]) {
-#pragma unroll
-        for (int i = 0; i < NB; ++i) { const size_t o = boff(min(k0 + i, kend - 1)); H[i] = *reinterpret_cast<const uint4*>(gbh + o); Lo[i] = *reinterpret_cast<const uint4*>(gbl + o); }
-      };
       auto mmablk = [&](int k0, const uint4 (&H)[NB], const uint4 (&Lo)[NB]) {
 #pragma unroll
         for (int i = 0; i < NB; ++i) {
@@ -328,8 +414,7 @@ __global__ __launch_bounds__(512) void k_pointwise_chain(const ChainArgs a_in) {
           }
         }
       };
-      loadblk(kbeg, pH, pL);
-      for (int k0 = kbeg; k0 < kend; k0 += 2 * NB) {
+      for (int k0 = kbeg; k0 < kend; k0 += 2 * NB) {      // (block kbeg was requested in front of the partial sums)
         loadblk(k0 + NB, qH, qL);
         __builtin_amdgcn_sched_barrier(0);
         mmablk(k0, pH, pL);
@@ -340,6 +425,8 @@ __global__ __launch_bounds__(512) void k_pointwise_chain(const ChainArgs a_in) {
         __builtin_amdgcn_sched_barrier(0);
       }
     }
+    request_layer(0, l31, lh);                         // the first layer's weights and biases travel under the hand-over and the epilogue
+    __builtin_amdgcn_sched_barrier(0);
     if (KSPL == 2) {                                   // the second K half's partial tile -> the first half's wave (fixed order: bit-reproducible)
       float* red = reinterpret_cast<float*>(ch_smem);
       if (mact && kp == 1) {
@@ -364,7 +451,6 @@ __global__ __launch_bounds__(512) void k_pointwise_chain(const ChainArgs a_in) {
     CTRC(2);
     // epilogue: + bias -> BatchNorm affine -> + residual (+ per-row vector); the chain's input planes (zero beyond N2) and the carry registers
     {
-      const float bi = (cin && gb2) ? gb2[col] : 0.f, sc = (cin && gs2) ? gs2[col] : 1.f, sh = (cin && gh2) ? gh2[col] : 0.f;
 #pragma unroll
       for (int tm = 0; tm < TM; ++tm)
 #pragma unroll
@@ -372,23 +458,16 @@ __global__ __launch_bounds__(512) void k_pointwise_chain(const ChainArgs a_in) {
 #pragma unroll
       for (int tm = 0; tm < TM; ++tm)
 #pragma unroll
-        for (int r = 0; r < 16; ++r) {
-          const int rl = (wm * TM + tm) * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
-          const float v = cin ? (acc[tm][r] + bi) * sc + sh + rs[tm][r] : 0.f;
-          xreg[tm][r] = v;
-          if (col < K0) {
-            const unsigned hp = taco_pk_bf16(v, 0.f) & 0xffffu;
-            const unsigned lp = taco_pk_bf16(v - __uint_as_float(hp << 16), 0.f) & 0xffffu;
-            xhi[rl * LDSW + col] = (unsigned short)hp;
-            xlo[rl * LDSW + col] = (unsigned short)lp;
-          }
-        }
+        for (int r = 0; r < 16; ++r) xreg[tm][r] = cin ? (acc[tm][r] + bi2) * sc2 + sh2 + rs[tm][r] : 0.f;
+      ch_write_planes<TM, LDSW>(xhi, xlo, wm * TM * 32 + 4 * lh, col, xreg, col < K0);
       have_x = true;
     }
     CTRC(3);
   } else
   // ---- stage the input rows: fp32 -> (hi, lo) planes, zero padded to the first layer's K ----
   {
+    request_layer(0, l31, lh);                 // the first layer's weights and biases travel under the staging
+    __builtin_amdgcn_sched_barrier(0);
     const int K0 = a_in.L[0].K16 * 16;
     for (int i = tid; i < CH_BM * (K0 / 4); i += 512) {
       const int r = i / (K0 / 4), c = 4 * (i % (K0 / 4));
@@ -424,10 +503,9 @@ __global__ __launch_bounds__(512) void k_pointwise_chain(const ChainArgs a_in) {
       const int bb0 = m0 / a.T;                // a tile of 64 rows spans at most two batch rows when T >= 64: their lengths once, not once per stored element
       const int nbrow = (a.M - 1) / a.T;
       const int Lb0 = a.rev_len ? a.rev_len[min(bb0, nbrow)] : a.T, Lb1 = a.rev_len ? a.rev_len[min(bb0 + 1, nbrow)] : a.T;
-      auto store_group = [&](int ng, const f32x16 (&acc)[TM]) {
+      auto store_group = [&](int ng, const f32x16 (&acc)[TM], float bia) {
         const int ocol = ng * W + col;
         if (ocol >= L.N) return;
-        const float bia = L.bias ? L.bias[ocol] : 0.f;
         const bool rev = a.rev_col0 >= 0 && ocol >= a.rev_col0;
         const bool relu_out = L.act == ACT_RELU;                       // (a chain that ends in a ReLU layer: the encoder prenet; otherwise the value passes as it is, a NaN included)
         if (full && !rev) {
@@ -440,41 +518,69 @@ __global__ __launch_bounds__(512) void k_pointwise_chain(const ChainArgs a_in) {
         } else {                               // the backward direction's columns go to the time-reversed row of the batch row
           int lhs = lh;                        // (opaque per call: the 32 reversed row indices are formed here, not kept -- and spilled -- across the column groups)
           asm volatile("" : "+v"(lhs));
+          // Two copies of the loop.  T >= 64: the tile's two lengths are in registers, no load on the way to a store.  T < 64: a length is loaded
+          // per element.  As ONE loop every element's code joined a path with a load pending, the compiler put a wait for ALL vector-memory
+          // traffic in front of every store, and each reversed store waited for the one before it to be acknowledged (32 round trips: the
+          // 13 - 17 K clocks of "stores" behind the encoder's reversed pass in the timelines up to round 18)
+          if (a.T >= CH_BM) {
 #pragma unroll
-          for (int tm = 0; tm < TM; ++tm)
+            for (int tm = 0; tm < TM; ++tm)
 #pragma unroll
-            for (int r = 0; r < 16; ++r) {
-              const int row = m0 + (wm * TM + tm) * 32 + (r & 3) + 8 * (r >> 2) + 4 * lhs;
-              int orow = row;
-              if (rev) {
-                const int bb = a.T >= CH_BM ? bb0 + (row >= (bb0 + 1) * a.T ? 1 : 0) : row / a.T;
-                const int tt = row - bb * a.T, Lb = a.T >= CH_BM ? (bb == bb0 ? Lb0 : Lb1) : (a.rev_len ? a.rev_len[min(bb, (a.M - 1) / a.T)] : a.T);
-                orow = tt < Lb ? bb * a.T + (Lb - 1 - tt) : row;
+              for (int r = 0; r < 16; ++r) {
+                const int row = m0 + (wm * TM + tm) * 32 + (r & 3) + 8 * (r >> 2) + 4 * lhs;
+                int orow = row;
+                if (rev) {
+                  const int bb = bb0 + (row >= (bb0 + 1) * a.T ? 1 : 0);
+                  const int tt = row - bb * a.T, Lb = bb == bb0 ? Lb0 : Lb1;
+                  orow = tt < Lb ? bb * a.T + (Lb - 1 - tt) : row;
+                }
+                if (row < a.M) { const float v = acc[tm][r] + bia; a.out[(size_t)orow * a.ldo + ocol] = relu_out ? fmaxf(v, 0.f) : v; }
               }
-              if (row < a.M) { const float v = acc[tm][r] + bia; a.out[(size_t)orow * a.ldo + ocol] = relu_out ? fmaxf(v, 0.f) : v; }
-            }
+          } else {
+#pragma unroll
+            for (int tm = 0; tm < TM; ++tm)
+#pragma unroll
+              for (int r = 0; r < 16; ++r) {
+                const int row = m0 + (wm * TM + tm) * 32 + (r & 3) + 8 * (r >> 2) + 4 * lhs;
+                int orow = row;
+                if (rev) {
+                  const int bb = row / a.T;
+                  const int tt = row - bb * a.T, Lb = a.rev_len ? a.rev_len[min(bb, (a.M - 1) / a.T)] : a.T;
+                  orow = tt < Lb ? bb * a.T + (Lb - 1 - tt) : row;
+                }
+                if (row < a.M) { const float v = acc[tm][r] + bia; a.out[(size_t)orow * a.ldo + ocol] = relu_out ? fmaxf(v, 0.f) : v; }
+              }
+          }
         }
       };
-      // two column groups per pass share the A fragments; an odd group left over (6H = 3 W at W = 256: the backward direction's last
-      // columns, whose time-reversed stores are the slow ones) goes FIRST, so that its stores drain behind the products of the pass after it
-      const int npass = (ngroups + 1) / 2, odd = ngroups & 1;
+      // the passes in pass_group's order.  The first pass's fragments were requested before the last seam; a later pass's are requested BEHIND
+      // the stores of the pass in front of it: the wait for a load covers every store issued before it, and in front of them it would hold
+      // the next products until those stores are acknowledged instead of letting them drain behind the products.  A pass's biases are
+      // requested before its products, and they and the tile's lengths are waited for ONCE, before the first store.
+      const int npass = (ngroups + 1) / 2;
       for (int ps = 0; ps < npass; ++ps) {
-        const int ng = (odd && ps == 0) ? ngroups - 1 : 2 * (ps - odd);
-        const int nt = min(ng * WN + wn, L.NT - 1), nt2 = min((ng + 1) * WN + wn, L.NT - 1);   // tiles past the pack are clamped, never stored
+        const int ng = pass_group(ngroups, ps);
+        const ChProd pr = make_prod(L, ps);
+        const float biaA = (L.bias && ng * W + col < L.N) ? L.bias[ng * W + col] : 0.f;
+        const float biaB = (L.bias && pr.dual && (ng + 1) * W + col < L.N) ? L.bias[(ng + 1) * W + col] : 0.f;
         f32x16 acc[TM], acc2[TM];
 #pragma unroll
         for (int tm = 0; tm < TM; ++tm)
           for (int r = 0; r < 16; ++r) { acc[tm][r] = 0.f; acc2[tm][r] = 0.f; }
-        if (ng + 1 < ngroups) ch_mma_loop<TM, LDSW, true, PF>(L.K16, L.NT, L.bh, L.bl, nt, L.bh, L.bl, nt2, xhi, xlo, wm * TM * 32, l31, lh, acc, acc2, krot * L.K16 >> 5);
-        else ch_mma_loop<TM, LDSW, false, PF>(L.K16, L.NT, L.bh, L.bl, nt, L.bh, L.bl, nt, xhi, xlo, wm * TM * 32, l31, lh, acc, acc2, krot * L.K16 >> 5);     // the odd group: one matrix
+        if (pr.dual) ch_mma_loop<TM, LDSW, true, PF>(pr, fr, xhi, xlo, wm * TM * 32, l31, lh, acc, acc2);
+        else ch_mma_loop<TM, LDSW, false, PF>(pr, fr, xhi, xlo, wm * TM * 32, l31, lh, acc, acc2);     // the odd group: one matrix
 #ifdef TACO_TRACE
         CTRC(trci); ++trci;
 #endif
-        store_group(ng, acc);
-        if (ng + 1 < ngroups) store_group(ng + 1, acc2);
+        asm volatile("" :: "v"(biaA), "v"(biaB), "v"(Lb0), "v"(Lb1));
+        store_group(ng, acc, biaA);
+        if (pr.dual) store_group(ng + 1, acc2, biaB);
 #ifdef TACO_TRACE
         CTRC(trci); ++trci;
 #endif
+        __builtin_amdgcn_sched_barrier(0);
+        if (ps + 1 < npass) ch_request<PF>(make_prod(L, ps + 1), l31, lh, fr);
+        else if (li + 1 < a.nlayers) request_layer(li + 1, l31, lh);
       }
       continue;
     }
@@ -492,13 +598,15 @@ __global__ __launch_bounds__(512) void k_pointwise_chain(const ChainArgs a_in) {
 #pragma unroll
       for (int tm = 0; tm < TM; ++tm)
         for (int r = 0; r < 16; ++r) { acc[tm][r] = 0.f; acc2[tm][r] = 0.f; }
-      const float bia = L.bias ? L.bias[col] : 0.f;
+      const float bia = nbia, bia2 = nbia2;      // (request_layer, in front of the seam before this layer)
+      const ChProd pr = make_prod(L, 0);
       if (dual) {
-        const float bia2 = L.bias2 ? L.bias2[col] : 0.f;
-        ch_mma_loop<TM, LDSW, true, PF>(L.K16, L.NT, L.bh, L.bl, wn, L.bh2, L.bl2, wn, xhi, xlo, wm * TM * 32, l31, lh, acc, acc2, krot * L.K16 >> 5);
+        ch_mma_loop<TM, LDSW, true, PF>(pr, fr, xhi, xlo, wm * TM * 32, l31, lh, acc, acc2);
 #ifdef TACO_TRACE
         CTRC(trci); ++trci;
 #endif
+        if (li + 1 < a.nlayers) request_layer(li + 1, l31, lh);      // the next layer's first fragments and biases: under this epilogue and the barrier
+        __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
         for (int tm = 0; tm < TM; ++tm)
 #pragma unroll
@@ -508,10 +616,12 @@ __global__ __launch_bounds__(512) void k_pointwise_chain(const ChainArgs a_in) {
             xreg[tm][r] = Hh * Tg + xreg[tm][r] * (1.f - Tg);
           }
       } else {
-        ch_mma_loop<TM, LDSW, false, PF>(L.K16, L.NT, L.bh, L.bl, wn, L.bh, L.bl, wn, xhi, xlo, wm * TM * 32, l31, lh, acc, acc2, krot * L.K16 >> 5);
+        ch_mma_loop<TM, LDSW, false, PF>(pr, fr, xhi, xlo, wm * TM * 32, l31, lh, acc, acc2);
 #ifdef TACO_TRACE
         CTRC(trci); ++trci;
 #endif
+        if (li + 1 < a.nlayers) request_layer(li + 1, l31, lh);
+        __builtin_amdgcn_sched_barrier(0);
         const bool relu = L.act == ACT_RELU;
 #pragma unroll
         for (int tm = 0; tm < TM; ++tm)
@@ -532,21 +642,15 @@ __global__ __launch_bounds__(512) void k_pointwise_chain(const ChainArgs a_in) {
 #ifdef TACO_TRACE
     CTRC(trci); ++trci;
 #endif
-    __syncthreads();                            // every wave has read the planes of this layer
+    // The seam: the output goes into the OTHER plane set, so nobody has to wait until every wave has read this layer's planes; one barrier -- all
+    // writes of the new set done before anyone reads it.  When the layer after next writes back into this set, every wave is past that barrier,
+    // and a wave passes it only behind its own reads of this layer's planes (its MFMAs have consumed them).
+    ch_write_planes<TM, LDSW>(yhi, ylo, wm * TM * 32 + 4 * lh, col, xreg, true);
 #ifdef TACO_TRACE
     CTRC(trci); ++trci;
 #endif
-#pragma unroll
-    for (int tm = 0; tm < TM; ++tm)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const float f = xreg[tm][r];
-        const unsigned hp = taco_pk_bf16(f, 0.f) & 0xffffu;
-        const unsigned lp = taco_pk_bf16(f - __uint_as_float(hp << 16), 0.f) & 0xffffu;
-        xhi[rloc(tm, r) * LDSW + col] = (unsigned short)hp;
-        xlo[rloc(tm, r) * LDSW + col] = (unsigned short)lp;
-      }
     __syncthreads();
+    { unsigned short* t = xhi; xhi = yhi; yhi = t; t = xlo; xlo = ylo; ylo = t; }
 #ifdef TACO_TRACE
     CTRC(trci); ++trci;
 #endif

@@ -925,6 +925,12 @@ static bool chain_fits(const Cbhg& c, int in_dim) {
   for (const ConvL& h : c.hw) if (!h.bh || !h.bh2 || h.cin != W || h.N != W) return false;
   return c.xproj.bh && c.xproj.cin == W && c.xproj.N == 6 * W;
 }
+// LDS of a chain launch: two plane sets (a layer reads one and writes the other); the entry's planes of proj_1's output (+ 1 frame each side)
+// lie behind the first set, over the second, which is first written when they are dead.  W = 256: 67584 + max(67584, 69696) = 137280 bytes
+static size_t chain_lds(int W, bool entry) {
+  const size_t set = (size_t)2 * CH_BM * (W + 8) * sizeof(unsigned short), ent = (size_t)2 * (CH_BM + 2) * (W + 8) * sizeof(unsigned short);
+  return set + std::max(set, entry ? ent : (size_t)0);
+}
 static int run_chain(const taco_model* m, hipStream_t st, const Cbhg& c, const float* x, int in_dim, int M, int T, const int* lengths,
                      const CbhgWs& w, const ChainEntry* entry = nullptr) {
   ChainArgs a; memset(&a, 0, sizeof a);
@@ -941,8 +947,7 @@ static int run_chain(const taco_model* m, hipStream_t st, const Cbhg& c, const f
   for (int i = 0; i < c.depth; ++i) add(c.hw[i], CH_HIGHWAY);
   add(c.xproj, CH_XPROJ);
   const dim3 grid(cdiv(M, CH_BM)), blk(512);
-  size_t lds = (size_t)2 * CH_BM * (c.rnn + 8) * sizeof(unsigned short);
-  if (entry) lds += (size_t)2 * (CH_BM + 2) * (entry->N1 + 8) * sizeof(unsigned short);      // planes of proj_1's output (+ 1 frame each side)
+  const size_t lds = chain_lds(c.rnn, entry != nullptr);      // (entry: N1 == rnn, ff_plan)
   if (c.rnn == 256) hipLaunchKernelGGL((k_pointwise_chain<256>), grid, blk, lds, st, a);
   else hipLaunchKernelGGL((k_pointwise_chain<128>), grid, blk, lds, st, a);
   HIPCHK(hipGetLastError());
@@ -1215,7 +1220,7 @@ static int run_prenet_chain(const taco_model* m, hipStream_t st, const int* ids,
     for (int i = 0; i < CH_RIDERS; ++i) { a.zp[i] = riders->z.p[i]; a.znw[i] = riders->z.nw[i]; }
     nwg += std::min(192, std::max(16, 256 - nwg));
   }
-  hipLaunchKernelGGL((k_pointwise_chain<256>), dim3(nwg), dim3(512), (size_t)2 * CH_BM * (256 + 8) * sizeof(unsigned short), st, a);
+  hipLaunchKernelGGL((k_pointwise_chain<256>), dim3(nwg), dim3(512), chain_lds(256, false), st, a);
   HIPCHK(hipGetLastError());
   if (riders) riders->enqueued = true;      // the riders are in the stream now: the persistent kernels behind this launch need no fill of their own
   return 0;

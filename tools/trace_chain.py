@@ -23,7 +23,8 @@ def show(name, fn, hidden, passes):
     print(name, "entry: partial sums -> planes %d | proj_2 products %d | epilogue %d | barrier %d" % (rel[1], rel[2] - rel[1], rel[3] - rel[2], rel[4] - rel[3]))
     k = 5
     for li in range(hidden):
-        print("  layer %d: products %6d | epilogue %5d | wait for the other waves %5d | planes + barrier %5d" % (
+        # (the output goes into the other plane set: no wait for the other waves' reads in front of the writes, one barrier behind them)
+        print("  layer %d: products %6d | request next + epilogue %5d | plane writes %5d | barrier %5d" % (
             li, rel[k] - rel[k - 1], rel[k + 1] - rel[k], rel[k + 2] - rel[k + 1], rel[k + 3] - rel[k + 2]))
         k += 4
     npass = 0
