@@ -562,6 +562,39 @@ float taco_learning_rate(long long global_step, float initial_learning_rate, int
 int taco_adam_step_f32(void* hip_stream, float* d_params, const float* d_grads, float* d_m, float* d_v, size_t n,
                        long long global_step, float learning_rate, float beta1, float beta2, float epsilon, float clip_norm,
                        float* d_gnorm_out, void* d_workspace, size_t workspace_bytes);
+/* Segmented norms over a flat fp32 buffer: the gradient scalars of the reference's summaries (add_stats, train.py:50-77; fetched at
+ * train.py:232-240), whose scope 'train' adds max_gradient_norm = reduce_max([tf.norm(g) for g in model.gradients if g is not None]).
+ * Caveat: train.py:156 calls add_stats(model, scope_name='stats'), so in the reference as run the 'train' branch never executes; the
+ * function is reproduced as it stands, and 'train' is the useful scope.  model.gradients are the UNCLIPPED gradients
+ * (tacotron.py:328-330: self.gradients is taken before clip_by_global_norm), so these are norms of the unclipped gradients too.
+ * A plan holds the work table of `n_seg` segments [h_offsets[s], h_offsets[s + 1]) (element indices, ascending, a segment may be empty,
+ * no alignment asked of any offset), built on the host once: pieces of at most taco_segnorm_piece_floats() floats, none across a
+ * segment boundary, ascending.  A call reads the buffer ONCE (16-byte loads in the aligned interior of a piece, scalar loads at its
+ * ragged ends) and writes
+ *   d_norms[s]  = sqrt(sum of x[i]^2 over segment s), 0 for an empty segment; beyond the fp32 range: +inf;
+ *   d_stats[0]  = the largest norm, *d_argmax = its segment: ties go to the first index; if any counted norm is NaN the maximum is NaN
+ *                 and the index is that of the first NaN segment (a step that taco_train_forward_backward poisoned after a device
+ *                 fault -- NaN in d_grads[0] -- stays visible; tf.reduce_max's treatment of NaN is not imitated);
+ *   d_stats[1]  = the norm over all counted segments together (the global norm that clip_by_global_norm divides by).
+ * skip (h_skip[s] != 0): the segment is not read at all, its norm is written as 0, and it takes no part in the maximum, its index
+ * or the global norm; with no counted segment at all: 0, 0 and index -1.
+ * Squares and sums are accumulated in double (an fp32 product is exact in double) in an order fixed by the table -- no
+ * floating-point atomics: the same input gives the same bits on every call, from any stream and in a replayed graph.
+ * Three launches; no allocation, no host synchronisation, no copy and no memset: capturable.  All state is in the plan, so calls on ONE
+ * plan must be ordered among themselves (one stream, or events between streams).
+ * TACO_ERR_ARG, before any HIP call: a null pointer (d_argmax may be null), n_seg < 1, descending offsets, h_offsets[n_seg] > n, an
+ * input that is not 4-byte aligned, d_norms / d_stats / d_argmax overlapping the n floats of the input. */
+typedef struct taco_segnorm_plan taco_segnorm_plan;
+int taco_segment_norms(const taco_segnorm_plan* plan, void* hip_stream, const float* d_flat, size_t n,
+                       float* d_norms /* [n_seg] */, float* d_stats /* [2]: max norm, norm over all counted segments */,
+                       int32_t* d_argmax /* [1] or null */);
+/* P, the largest piece of the work table of taco_segment_norms (train.py:50-77) in floats */
+int taco_segnorm_piece_floats(void);
+/* the plan of taco_segment_norms (train.py:50-77; rules and errors there).  Allocates and copies on `device`: make it outside stream capture. */
+int taco_segnorm_plan_create(const uint64_t* h_offsets /* [n_seg+1], host */, int n_seg,
+                             const uint8_t* h_skip /* [n_seg] or null */, int device, taco_segnorm_plan** out);
+/* frees a plan of taco_segment_norms (train.py:50-77) and its device buffers; null is allowed */
+void taco_segnorm_plan_destroy(taco_segnorm_plan* plan);
 
 /* ---- training path (config C4): teacher-forced forward with batch-statistics BatchNorm
  * (tacotron.py:26,199-202; modules.py:131; helpers.py:35-67), add_loss and its full backward pass (tf.gradients of
@@ -648,6 +681,18 @@ int taco_train_forward_backward(taco_train* t, void* hip_stream, float* d_params
                                 const float* d_loss_coeff, int B, int T_in, int T_out, int prioritize_loss, int sample_rate,
                                 float* d_losses, float* d_mel_out, float* d_linear_out, float* d_alignments,
                                 int rnn_decoder_test_mode, void* d_workspace, size_t workspace_bytes);
+/* The per-variable gradient norms of add_stats' scope 'train' (train.py:50-77; in the reference as run, train.py:156 passes scope
+ * 'stats' and that branch never executes): taco_segment_norms over d_grads (the flat gradients of taco_train_forward_backward, UNCLIPPED as
+ * model.gradients is, tacotron.py:328-330) with one segment per tensor of taco_model_weight_name, in that order.  The BatchNorm moving
+ * statistics (".../moving_mean", ".../moving_variance") are no trainable variables and have no entry in model.gradients: they are
+ * skipped -- norm 0, outside the maximum, its index and the global norm.  d_stats[0] is the reference's max_gradient_norm, d_stats[1]
+ * the global norm that taco_adam_step_f32 computes again for its clip (both accumulated in double, in different orders).  Double accumulation,
+ * determinism, the NaN, tie and skip rules and the argument errors are those of taco_segment_norms.  After a data-parallel all-reduce the
+ * norms are those of the averaged gradient, bit-equal on every rank.  The plan is built from the trainer's layout on the first call
+ * (which allocates: make it outside stream capture) and freed by taco_train_destroy; later calls are capturable. */
+int taco_train_grad_norms(taco_train* t, void* hip_stream, const float* d_grads,
+                          float* d_norms /* [taco_model_num_weights] in taco_model_weight_name order */,
+                          float* d_stats, int32_t* d_argmax);
 
 /* Persistent (multi-workgroup, in-kernel synchronised) kernels bound every spin; if one ever expires it sets a
  * device-side error word and all workgroups leave.  This call synchronises, returns the word in *out and clears it;

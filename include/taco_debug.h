@@ -174,6 +174,20 @@ int taco_debug_gl_create_host(const taco_audio_hparams* hp, int tf_flavor, taco_
  * 20 res_g2p packs of either CBHG.  Everything is freed before it returns. */
 int taco_debug_pack_host(const taco_hparams* hp, int shadow, const float* flat_weights, size_t n_floats, uint64_t out[5]);
 
+/* Test hook: the work table of taco_segment_norms as its host-only builder makes it (csrc/taco_segnorm.h) -- no handle, no device.  Piece i covers
+ * elements [out_begin[i], out_begin[i] + out_len[i]) of segment out_seg[i]; *n_pieces receives their number.  Arguments and errors as
+ * taco_segnorm_plan_create's; more than `cap` pieces is TACO_ERR_ARG too (*n_pieces is still set, nothing is written past cap). */
+int taco_debug_segnorm_pieces(const uint64_t* h_offsets, int n_seg, const uint8_t* h_skip, uint64_t* out_begin, int32_t* out_len,
+                              int32_t* out_seg, int cap, int* n_pieces);
+/* Test hook: a taco_segnorm_plan that stays on the host -- no device is touched.  It serves the argument checks of taco_segment_norms,
+ * which come before its first device call, on a machine without a GPU; a call that passes them returns TACO_ERR_STATE.  Freed by
+ * taco_segnorm_plan_destroy. */
+int taco_debug_segnorm_plan_create_host(const uint64_t* h_offsets, int n_seg, const uint8_t* h_skip, taco_segnorm_plan** out);
+
+/* Timing hook: k_sumsq_partial alone, launched exactly as taco_adam_step_f32 launches it (same grid, same workspace of at least 8 KiB): the
+ * yardstick that tools/bench_train.py --grad-stats holds taco_train_grad_norms against -- both read the same bytes once. */
+int taco_debug_sumsq_partial(void* hip_stream, const float* d_grads, size_t n, void* d_workspace, size_t workspace_bytes);
+
 #ifdef __cplusplus
 }
 #endif

@@ -182,6 +182,15 @@ PROTOTYPES = {
     "taco_loss_f32": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _S]),
     "taco_learning_rate": (C.c_float, [C.c_longlong, C.c_float, _I, _I]),
     "taco_adam_step_f32": (_I, [_P, _P, _P, _P, _P, _S, C.c_longlong, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, _P, _P, _S]),
+    "taco_segment_norms": (_I, [_P, _P, _P, _S, _P, _P, _P]),
+    "taco_segnorm_piece_floats": (_I, []),
+    "taco_segnorm_plan_create": (_I, [C.POINTER(C.c_uint64), _I, C.POINTER(C.c_uint8), _I, C.POINTER(_P)]),
+    "taco_segnorm_plan_destroy": (None, [_P]),
+    "taco_train_grad_norms": (_I, [_P, _P, _P, _P, _P, _P]),
+    "taco_debug_segnorm_pieces": (_I, [C.POINTER(C.c_uint64), _I, C.POINTER(C.c_uint8), C.POINTER(C.c_uint64), C.POINTER(C.c_int32),
+                                       C.POINTER(C.c_int32), _I, C.POINTER(_I)]),
+    "taco_debug_segnorm_plan_create_host": (_I, [C.POINTER(C.c_uint64), _I, C.POINTER(C.c_uint8), C.POINTER(_P)]),
+    "taco_debug_sumsq_partial": (_I, [_P, _P, _S, _P, _S]),
     "taco_train_create": (_I, [C.POINTER(TacoHParams), _I, C.POINTER(_P)]),
     "taco_train_destroy": (None, [_P]),
     "taco_train_model": (_P, [_P]),

@@ -1685,6 +1685,7 @@ static int forward_enqueue(taco_model* m, hipStream_t st, const int32_t* ids, co
 // ------------------------------------------------------------------------------------------------
 // C ABI
 // ------------------------------------------------------------------------------------------------
+#include "taco_segnorm.h"
 #include "taco_train.h"
 #include "taco_audio.h"
 #include "taco_resample.h"

@@ -53,6 +53,7 @@ struct taco_train {
   int planes_problems = 0;     // weight gradients of the last backward pass that were computed from pre-split planes (a conv bank counts once)
   int wgrad_planes = 1;                // taco_train_set_wgrad_planes: 1 = large weight gradients from pre-split bf16 planes (taco_wgrad_planes.h), 2 = every eligible one (tests), 0 = off
   int deterministic = 1;               // taco_train_set_deterministic: ordered two-stage sums (default since round 4) or fp32 atomics; the former needs DET_SCRATCH_FLOATS of workspace
+  taco_segnorm_plan* gn_plan = nullptr;   // taco_train_grad_norms: one segment per spec tensor (poff order), built on the first call
 };
 #define WP_SCRATCH_COLS 2048           // plane scratch: room for (widest conv bank + WP_SCRATCH_COLS) columns of the longest row set, three bf16 planes each
 #define DET_SCRATCH_FLOATS ((size_t)48 << 20)      // 192 MB: e.g. 30 M-slices of the largest weight gradient (post-net proj_1, 3 x 2048 x 256)

@@ -64,6 +64,7 @@ void taco_train_destroy(taco_train* t) {
   if (t->d_fold) (void)hipFree(t->d_fold);
   if (t->d_bf3_idx) (void)hipFree(t->d_bf3_idx);
   if (t->d_bf3_segs) (void)hipFree(t->d_bf3_segs);
+  taco_segnorm_plan_destroy(t->gn_plan);
   if (t->sm) taco_model_destroy(t->sm);
   delete t;
 }
@@ -327,6 +328,128 @@ int taco_train_forward_backward(taco_train* t, void* hip_stream, float* d_params
   // gradients invalid.  The step says so in its own outputs: losses and the first gradient element become NaN -- which survives the
   // data-parallel all-reduce, so EVERY rank's clip-and-Adam (k_adam) sees a non-finite global norm and skips the update.
   hipLaunchKernelGGL(k_train_latch, dim3(1), dim3(64), 0, (hipStream_t)hip_stream, (const unsigned*)t->sm->d_err, d_losses, d_grads);
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
+// ---- segmented norms: per-variable gradient norms, their maximum and the global norm (add_stats, train.py:50-77) ----
+int taco_segnorm_piece_floats(void) { return SEGN_P; }
+
+// Test hook: the host-only piece table builder (taco_segnorm.h) -- no handle, no device.
+int taco_debug_segnorm_pieces(const uint64_t* h_offsets, int n_seg, const uint8_t* h_skip, uint64_t* out_begin, int32_t* out_len,
+                              int32_t* out_seg, int cap, int* n_pieces) {
+  if (!h_offsets || !out_begin || !out_len || !out_seg || !n_pieces || cap < 0) return fail(TACO_ERR_ARG, "null argument or negative cap");
+  std::vector<SegPiece> pieces; std::vector<int> pfirst;
+  if (const char* why = segnorm_pieces(h_offsets, n_seg, h_skip, pieces, pfirst)) return fail(TACO_ERR_ARG, "%s", why);
+  *n_pieces = (int)pieces.size();
+  if (pieces.size() > (size_t)cap) return fail(TACO_ERR_ARG, "%zu pieces, room for %d", pieces.size(), cap);
+  for (size_t i = 0; i < pieces.size(); ++i) { out_begin[i] = pieces[i].begin; out_len[i] = pieces[i].len; out_seg[i] = pieces[i].seg; }
+  return 0;
+}
+
+// the host half of a plan: the table is built and checked, nothing is allocated
+static int segnorm_plan_host(const uint64_t* h_offsets, int n_seg, const uint8_t* h_skip, int device, taco_segnorm_plan** out,
+                             std::vector<SegPiece>& pieces, std::vector<int>& pfirst, std::vector<unsigned char>& skip) {
+  if (!h_offsets || !out) return fail(TACO_ERR_ARG, "null argument");
+  if (const char* why = segnorm_pieces(h_offsets, n_seg, h_skip, pieces, pfirst)) return fail(TACO_ERR_ARG, "%s", why);
+  skip.assign((size_t)n_seg, 0);
+  for (int s = 0; h_skip && s < n_seg; ++s) skip[s] = h_skip[s] ? 1 : 0;
+  taco_segnorm_plan* p = new taco_segnorm_plan();
+  p->device = device; p->n_seg = n_seg; p->n_pieces = (int)pieces.size(); p->end = h_offsets[n_seg];
+  *out = p;
+  return 0;
+}
+// Test hook: a plan that stays on the host -- no device is touched.  It serves the argument checks of taco_segment_norms, which come before
+// its first device call, on a machine without a GPU; a call that passes them is refused with TACO_ERR_STATE.  Freed by taco_segnorm_plan_destroy.
+int taco_debug_segnorm_plan_create_host(const uint64_t* h_offsets, int n_seg, const uint8_t* h_skip, taco_segnorm_plan** out) {
+  std::vector<SegPiece> pieces; std::vector<int> pfirst; std::vector<unsigned char> skip;
+  return segnorm_plan_host(h_offsets, n_seg, h_skip, 0, out, pieces, pfirst, skip);
+}
+
+int taco_segnorm_plan_create(const uint64_t* h_offsets, int n_seg, const uint8_t* h_skip, int device, taco_segnorm_plan** out) {
+  std::vector<SegPiece> pieces; std::vector<int> pfirst; std::vector<unsigned char> skip;
+  taco_segnorm_plan* p = nullptr;
+  if (!out) return fail(TACO_ERR_ARG, "null argument");
+  TRY(segnorm_plan_host(h_offsets, n_seg, h_skip, device, &p, pieces, pfirst, skip));
+  const size_t np = std::max<size_t>(pieces.size(), 1);      // (a table without pieces -- every segment empty or skipped -- launches no k_segsq_piece)
+  if (hipSetDevice(device) != hipSuccess ||
+      hipMalloc((void**)&p->d_pieces, np * sizeof(SegPiece)) != hipSuccess ||
+      hipMalloc((void**)&p->d_partial, np * sizeof(double)) != hipSuccess ||
+      hipMalloc((void**)&p->d_pfirst, pfirst.size() * sizeof(int)) != hipSuccess ||
+      hipMalloc((void**)&p->d_skip, skip.size()) != hipSuccess ||
+      hipMalloc((void**)&p->d_segsum, (size_t)n_seg * sizeof(double)) != hipSuccess ||
+      (!pieces.empty() && hipMemcpy(p->d_pieces, pieces.data(), pieces.size() * sizeof(SegPiece), hipMemcpyHostToDevice) != hipSuccess) ||
+      hipMemcpy(p->d_pfirst, pfirst.data(), pfirst.size() * sizeof(int), hipMemcpyHostToDevice) != hipSuccess ||
+      hipMemcpy(p->d_skip, skip.data(), skip.size(), hipMemcpyHostToDevice) != hipSuccess) {
+    (void)hipGetLastError();
+    taco_segnorm_plan_destroy(p);
+    return fail(TACO_ERR_HIP, "segment table allocation failed");
+  }
+  *out = p;
+  return 0;
+}
+
+void taco_segnorm_plan_destroy(taco_segnorm_plan* p) {
+  if (!p) return;
+  if (p->d_pieces) (void)hipFree(p->d_pieces);
+  if (p->d_partial) (void)hipFree(p->d_partial);
+  if (p->d_pfirst) (void)hipFree(p->d_pfirst);
+  if (p->d_skip) (void)hipFree(p->d_skip);
+  if (p->d_segsum) (void)hipFree(p->d_segsum);
+  delete p;
+}
+
+// the argument checks of a call that do not need the plan: all before any HIP call
+static int segnorm_check_buffers(const float* d_flat, size_t n, int n_seg, const float* d_norms, const float* d_stats, const int32_t* d_argmax) {
+  if (!d_flat || !d_norms || !d_stats) return fail(TACO_ERR_ARG, "null pointer");
+  if (reinterpret_cast<uintptr_t>(d_flat) & 3) return fail(TACO_ERR_ARG, "the input buffer %p is not 4-byte aligned", (const void*)d_flat);
+  const unsigned __int128 in = (uintptr_t)d_flat, in_end = in + (unsigned __int128)n * sizeof(float);
+  const auto overlaps = [&](const void* q, size_t bytes) { const unsigned __int128 o = (uintptr_t)q; return q && in < o + bytes && o < in_end; };
+  if (overlaps(d_norms, (size_t)n_seg * sizeof(float))) return fail(TACO_ERR_ARG, "d_norms and the input buffer overlap");
+  if (overlaps(d_stats, 2 * sizeof(float))) return fail(TACO_ERR_ARG, "d_stats and the input buffer overlap");
+  if (overlaps(d_argmax, sizeof(int32_t))) return fail(TACO_ERR_ARG, "d_argmax and the input buffer overlap");
+  return 0;
+}
+
+int taco_segment_norms(const taco_segnorm_plan* p, void* hip_stream, const float* d_flat, size_t n, float* d_norms, float* d_stats, int32_t* d_argmax) {
+  if (!p) return fail(TACO_ERR_ARG, "null pointer");
+  TRY(segnorm_check_buffers(d_flat, n, p->n_seg, d_norms, d_stats, d_argmax));
+  if (p->end > n) return fail(TACO_ERR_ARG, "the segment table ends at element %llu, the buffer holds %zu", (unsigned long long)p->end, n);
+  if (!p->d_pfirst) return fail(TACO_ERR_STATE, "a host-only plan (taco_debug_segnorm_plan_create_host) cannot run");
+  hipStream_t st = (hipStream_t)hip_stream;
+  HIPCHK(hipSetDevice(p->device));
+  if (p->n_pieces) hipLaunchKernelGGL(k_segsq_piece, dim3((unsigned)p->n_pieces), dim3(TR_NT), 0, st, d_flat, (const SegPiece*)p->d_pieces, p->d_partial);
+  hipLaunchKernelGGL(k_segsq_segment, dim3((unsigned)cdiv(p->n_seg, TR_NT / 64)), dim3(TR_NT), 0, st, (const double*)p->d_partial, (const int*)p->d_pfirst,
+                     p->n_seg, p->d_segsum, d_norms);
+  hipLaunchKernelGGL(k_segnorm_stats, dim3(1), dim3(TR_NT), 0, st, (const double*)p->d_segsum, (const float*)d_norms, (const unsigned char*)p->d_skip,
+                     p->n_seg, d_stats, d_argmax);
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
+int taco_train_grad_norms(taco_train* t, void* hip_stream, const float* d_grads, float* d_norms, float* d_stats, int32_t* d_argmax) {
+  if (!t || !d_grads || !d_norms || !d_stats) return fail(TACO_ERR_ARG, "null pointer");
+  TRY(segnorm_check_buffers(d_grads, t->NP, (int)t->sm->spec.size(), d_norms, d_stats, d_argmax));
+  if (!t->gn_plan) {      // one segment per spec tensor, in spec order = flat order; the BatchNorm moving statistics are no trainable variables
+    const auto ends_with = [](const std::string& s, const char* tail) { const size_t k = strlen(tail); return s.size() >= k && s.compare(s.size() - k, k, tail) == 0; };
+    std::vector<uint64_t> off; std::vector<uint8_t> skip;
+    for (auto& s : t->sm->spec) {
+      off.push_back(t->poff.at(s.first));
+      skip.push_back(ends_with(s.first, "/moving_mean") || ends_with(s.first, "/moving_variance"));
+    }
+    off.push_back(t->NP);
+    TRY(taco_segnorm_plan_create(off.data(), (int)skip.size(), skip.data(), t->sm->device, &t->gn_plan));
+  }
+  return taco_segment_norms(t->gn_plan, hip_stream, d_grads, t->NP, d_norms, d_stats, d_argmax);
+}
+
+// Timing hook: k_sumsq_partial alone, launched as taco_adam_step_f32 launches it -- the yardstick of taco_train_grad_norms (both read the same bytes once).
+int taco_debug_sumsq_partial(void* hip_stream, const float* d_grads, size_t n, void* d_workspace, size_t workspace_bytes) {
+  if (!d_grads || !d_workspace || n == 0) return fail(TACO_ERR_ARG, "bad argument");
+  if (workspace_bytes < (size_t)TR_MAXBLK * sizeof(double)) return fail(TACO_ERR_STATE, "workspace too small");
+  if ((reinterpret_cast<uintptr_t>(d_grads) & 15) != 0) return fail(TACO_ERR_ARG, "gradient buffer must be 16-byte aligned");
+  const int nblk = (int)std::min<size_t>(TR_MAXBLK, (n + TR_NT * 16 - 1) / (TR_NT * 16));
+  hipLaunchKernelGGL(k_sumsq_partial, dim3(nblk), dim3(TR_NT), 0, (hipStream_t)hip_stream, d_grads, n, (double*)d_workspace);
   HIPCHK(hipGetLastError());
   return 0;
 }

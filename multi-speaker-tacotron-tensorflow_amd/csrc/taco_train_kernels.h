@@ -107,3 +107,112 @@ __global__ __launch_bounds__(TR_NT) void k_adam(float* p, const float* g, float*
     p[i] -= lr_t * mi / (sqrtf(vi) + eps);
   }
 }
+
+// ---------------------------------------------------------------------------------------------------------------
+// Segmented sum of squares over a flat fp32 buffer: per-variable gradient norms, their maximum and the global norm
+// (the 'train' branch of add_stats, train.py:50-77: max_gradient_norm = reduce_max([tf.norm(g) for g in model.gradients])).
+// Caveat: train.py:156 calls add_stats(model, scope_name='stats'), so in the reference as run that branch never executes; the function
+// is reproduced as it stands (as the speaker-mixture branch that never ran was), and 'train' is the useful scope.
+// Work table (taco_segnorm.h, built on the host once per plan): ascending pieces of at most SEGN_P floats, none across a segment
+// boundary, none inside a skipped segment.  Three launches, the buffer read once by the first:
+//   k_segsq_piece     one workgroup per piece      -> one double partial per piece
+//   k_segsq_segment   one wave per segment         -> the segment's double sum (its pieces in ascending order, lane-strided, fixed
+//                                                     shuffle tree: no thread walks a list alone, cf. k_loss_final) and its fp32 norm
+//   k_segnorm_stats   one workgroup                -> max norm, its index, the norm over all counted segments
+// Squares and sums are doubles (an fp32 product is exact in double); every order of summation is fixed by the table and the
+// launch shapes, nothing is accumulated through atomics: the same input gives the same bits on every call, stream and graph replay.
+// ---------------------------------------------------------------------------------------------------------------
+#define SEGN_P 4096                        // floats per piece (taco_segnorm_piece_floats)
+#define SEGN_V (SEGN_P / 4 / TR_NT)        // 16-byte loads per thread that cover a whole piece
+struct SegPiece { unsigned long long begin; int len; int seg; };      // elements [begin, begin + len) of segment seg, len in [1, SEGN_P]
+
+__device__ __forceinline__ double segn_wave_sum(double x) {            // fixed tree over the 64 lanes; the total is in lane 0
+  for (int o = 32; o > 0; o >>= 1) x += __shfl_down(x, o, 64);
+  return x;
+}
+
+// The piece's 16-byte-aligned interior goes through 16-byte loads (all of a thread's loads issued before the first use), the up to 3
+// elements in front of it and behind it through scalar loads: variable offsets are no multiples of 4 (biases, scalars, 1025-wide rows).
+__global__ __launch_bounds__(TR_NT) void k_segsq_piece(const float* __restrict__ x, const SegPiece* __restrict__ pieces, double* __restrict__ partial) {
+  __shared__ double sm[TR_NT / 64];
+  const SegPiece pc = pieces[blockIdx.x];
+  const float* p = x + pc.begin;
+  const int tid = threadIdx.x;
+  const int head = min(pc.len, (int)((4u - (unsigned)((reinterpret_cast<uintptr_t>(p) >> 2) & 3u)) & 3u));
+  const int nv = (pc.len - head) >> 2, tail = (pc.len - head) & 3;
+  const float4* q = reinterpret_cast<const float4*>(p + head);
+  float4 v[SEGN_V];
+#pragma unroll
+  for (int k = 0; k < SEGN_V; ++k) {
+    const int i = tid + k * TR_NT;
+    v[k] = i < nv ? q[i] : make_float4(0.f, 0.f, 0.f, 0.f);
+  }
+  float e0 = 0.f, e1 = 0.f;
+  if (tid < head) e0 = p[tid];
+  if (tid < tail) e1 = p[head + 4 * nv + tid];
+  double s = 0;
+#pragma unroll
+  for (int k = 0; k < SEGN_V; ++k)
+    s += (double)v[k].x * v[k].x + (double)v[k].y * v[k].y + (double)v[k].z * v[k].z + (double)v[k].w * v[k].w;
+  s += (double)e0 * e0 + (double)e1 * e1;
+  s = segn_wave_sum(s);
+  if ((tid & 63) == 0) sm[tid >> 6] = s;
+  __syncthreads();
+  if (tid == 0) {
+    double r = sm[0];
+    for (int w = 1; w < TR_NT / 64; ++w) r += sm[w];
+    partial[blockIdx.x] = r;
+  }
+}
+
+// pfirst[s] .. pfirst[s + 1]: the pieces of segment s (none: an empty or a skipped segment, whose sum and norm are 0).
+// A norm beyond the fp32 range becomes +inf in the conversion.
+__global__ __launch_bounds__(TR_NT) void k_segsq_segment(const double* __restrict__ partial, const int* __restrict__ pfirst, int n_seg,
+                                                        double* __restrict__ segsum, float* __restrict__ norms) {
+  const int s = blockIdx.x * (TR_NT / 64) + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+  if (s >= n_seg) return;
+  const int a = pfirst[s], b = pfirst[s + 1];
+  double acc = 0;
+  for (int i = a + lane; i < b; i += 64) acc += partial[i];
+  acc = segn_wave_sum(acc);
+  if (lane == 0) { segsum[s] = acc; norms[s] = (float)sqrt(acc); }
+}
+
+// stats[0] = the largest norm of a counted (not skipped) segment, *argmax = its index: ties go to the first index; if any counted
+// norm is NaN the maximum is NaN and the index is that of the first NaN segment -- a step poisoned by k_train_latch (NaN in
+// grads[0]) stays visible, where tf.reduce_max's treatment of NaN is unspecified and not imitated.  stats[1] = sqrt of the sum of
+// the counted segments' sums.  No counted segment at all: 0, 0 and index -1.
+__global__ __launch_bounds__(TR_NT) void k_segnorm_stats(const double* __restrict__ segsum, const float* __restrict__ norms,
+                                                        const unsigned char* __restrict__ skip, int n_seg, float* __restrict__ stats,
+                                                        int* __restrict__ argmax) {
+  __shared__ double sm[TR_NT];
+  __shared__ float bv[TR_NT];
+  __shared__ int bi[TR_NT], ni[TR_NT];
+  if (blockIdx.x != 0) return;
+  const int tid = threadIdx.x, none = 0x7fffffff;
+  double tot = 0;
+  float best = 0.f; int besti = none, nani = none;
+  for (int s = tid; s < n_seg; s += TR_NT) {
+    if (skip[s]) continue;
+    tot += segsum[s];
+    const float v = norms[s];
+    if (v != v) { if (nani == none) nani = s; }
+    else if (besti == none || v > best) { best = v; besti = s; }
+  }
+  tot = tr_block_sum(tot, sm);
+  bv[tid] = best; bi[tid] = besti; ni[tid] = nani;
+  __syncthreads();
+  for (int o = TR_NT / 2; o > 0; o >>= 1) {
+    if (tid < o) {
+      ni[tid] = min(ni[tid], ni[tid + o]);
+      const float v = bv[tid + o]; const int i = bi[tid + o];
+      if (i != none && (bi[tid] == none || v > bv[tid] || (v == bv[tid] && i < bi[tid]))) { bv[tid] = v; bi[tid] = i; }
+    }
+    __syncthreads();
+  }
+  if (tid != 0) return;
+  const bool anynan = ni[0] != none;
+  stats[0] = anynan ? __uint_as_float(0x7FC00000u) : (bi[0] == none ? 0.f : bv[0]);
+  stats[1] = (float)sqrt(tot);
+  if (argmax) *argmax = anynan ? ni[0] : (bi[0] == none ? -1 : bi[0]);
+}

@@ -510,6 +510,46 @@ class Tacotron(object):
         self._losses = None
         return step, lwc
 
+    def add_stats(self, model2=None, scope_name='train'):
+        """train.py:50-77 as it stands: the scalars of the reference's summary as an ordered dict of floats under its tag names --
+        '<scope>/loss_mel', '<scope>/loss_linear', '<scope>/loss' (which is loss_without_coeff, as there); for scope 'train' only,
+        '<scope>/learning_rate' and '<scope>/max_gradient_norm' = the largest per-variable norm of the UNCLIPPED gradients
+        (tacotron.py:328-330) the shared trainer holds now (Trainer.gradient_stats); with `model2`, 'gap_test-train/loss_mel',
+        '/loss_linear', '/loss' as self - model2.  The losses are those of each model's current feed (add_loss()).
+        Caveat: train.py:156 calls add_stats(model, scope_name='stats'), so in the reference as run the 'train' branch never executes and
+        no gradient norm is ever written; 'train' is the default of the function and the useful scope.  With scope 'train', a model whose
+        trainer has not run a backward pass raises TacoError(TACO_ERR_STATE).
+        What the reference fetches at summary_interval (train.py:232-240) draws fresh train and test batches and applies NO update.  The
+        same here: trainer.forward_backward(train batch, backward=True, freeze_moving_averages=True), a forward of the test model on
+        its batch (initialize(..., rnn_decoder_test_mode=True) + add_loss()), then test_model.add_stats(model, 'test') and
+        model.add_stats().  In a data-parallel run take it after allreduce_gradients: the norms are then those of the averaged gradient,
+        bit-equal on every rank."""
+        from collections import OrderedDict
+
+        def losses(m):
+            if getattr(m, "mel_loss", None) is None:
+                m.add_loss()
+            if getattr(m, "mel_loss", None) is None:
+                raise _lib.TacoError(_lib.TACO_ERR_STATE, "add_stats needs the losses of a feed: initialize(...) with inputs and targets first")
+            return float(m.mel_loss), float(m.linear_loss), float(m.loss_without_coeff)
+
+        tr = getattr(self, "_trainer", None)
+        if tr is None:
+            raise RuntimeError("initialize(..., mel_targets, linear_targets) must be called first")
+        if scope_name == 'train' and not tr.have_gradients:
+            raise _lib.TacoError(_lib.TACO_ERR_STATE, "scope 'train' reports gradient norms: run a backward pass first "
+                                 "(train_step, or forward_backward(..., backward=True))")
+        mel, lin, lwc = losses(self)
+        out = OrderedDict()
+        out[scope_name + '/loss_mel'], out[scope_name + '/loss_linear'], out[scope_name + '/loss'] = mel, lin, lwc
+        if scope_name == 'train':
+            out[scope_name + '/learning_rate'] = float(tr.learning_rate)
+            out[scope_name + '/max_gradient_norm'] = float(tr.gradient_stats()["max_gradient_norm"])
+        if model2 is not None:
+            mel2, lin2, lwc2 = losses(model2)
+            out['gap_test-train/loss_mel'], out['gap_test-train/loss_linear'], out['gap_test-train/loss'] = mel - mel2, lin - lin2, lwc - lwc2
+        return out
+
     def trained_weights(self):
         """Current parameters as a dict (tf.train.Saver.save of train.py:242-244 -> weights.save_weights)."""
         return self._trainer.get_weights()

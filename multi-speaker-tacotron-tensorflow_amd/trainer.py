@@ -27,6 +27,24 @@ def _st():
     return C.c_void_p(torch.cuda.current_stream().cuda_stream)
 
 
+def is_moving_statistic(name):
+    """BatchNorm moving averages: in the flat parameter buffer (a checkpoint holds them), but no trainable variables."""
+    return name.endswith("/moving_mean") or name.endswith("/moving_variance")
+
+
+def tf_variable_name(name):
+    """The TensorFlow variable (under model/inference/) behind a canonical spec name: the longest scope of weights.TF_SCOPE_MAP that
+    leads the name, replaced by its TensorFlow scope.  The attention mechanism's own variables (attention/attention_v, _g, _b,
+    _score_bias) have no scope entry: they sit in the mechanism's scope, beside its query_layer.  Raises KeyError for a name no scope leads."""
+    from .weights import TF_SCOPE_MAP
+    if name.startswith("attention/attention_"):
+        return TF_SCOPE_MAP["attention/query_layer"].rsplit("/", 1)[0] + name[len("attention"):]
+    best = max((s for s in TF_SCOPE_MAP if name == s or name.startswith(s + "/")), key=len, default=None)
+    if best is None:
+        raise KeyError(name)
+    return TF_SCOPE_MAP[best].split(" ")[0] + name[len(best):]
+
+
 class Trainer(object):
     def __init__(self, hparams, weights, device="cuda:0", is_randomly_initialized=True, num_speakers=1):
         """`weights`: dict canonical name -> array (weights.random_weights / load_weights).  num_speakers > 1: model_type 'deepvoice' or 'simple' (pass speaker_id to every step)."""
@@ -70,6 +88,7 @@ class Trainer(object):
         self._sync_err = None
         self.sync_exchanges = 0
         self.mel_outputs = self.linear_outputs = self.alignments = None
+        self.have_gradients = False      # a backward pass has filled self.grads (gradient summaries need one)
 
     # ---- data-parallel SyncBN ----
     def enable_sync_bn(self, on=True, group=None):
@@ -234,6 +253,45 @@ class Trainer(object):
         with torch.cuda.device(self.device):
             _lib.check(self._lib.taco_train_refresh(self._h, _st(), _p(self.params)))
 
+    # ---- summaries: per-variable gradient norms (add_stats, train.py:50-77) ----
+    @property
+    def trainable(self):
+        """The spec names that are trainable variables, in spec order: everything but the BatchNorm moving statistics
+        (`*/moving_mean`, `*/moving_variance`), which TensorFlow updates through UPDATE_OPS and which have no entry in the reference's
+        `model.gradients` (tacotron.py:328-329).  Every remaining spec tensor is exactly one TensorFlow variable and the other way
+        round (tf_variable_name maps each through weights.TF_SCOPE_MAP; the names it gives are distinct), so one norm per name here is
+        one `tf.norm(grad)` there.  The one exception to the table: the vectors and scalars of the attention mechanism
+        (`attention/attention_v`, `attention_g`, `attention_b`, `attention_score_bias`) have no scope entry of their own; they are
+        variables of the mechanism's scope, beside its `query_layer`."""
+        return [name for name, _ in self.spec if not is_moving_statistic(name)]
+
+    def gradient_norms(self):
+        """Device tensors (norms [len(spec)] in spec order, stats [2] = max norm and global norm, argmax [1] int32) of the gradients
+        `self.grads` holds now -- UNCLIPPED, as the reference's `model.gradients` are (tacotron.py:328-330) -- by taco_train_grad_norms:
+        three launches on the current stream, no synchronisation, double accumulation in a fixed order (the same gradients give the
+        same bits on every call).  The slots of the moving statistics are 0 and count nowhere.  A gradient poisoned after a device
+        fault (NaN in grads[0]) gives a NaN maximum that points at the first NaN variable.  In a data-parallel run, call it after
+        allreduce_gradients: the norms are then those of the averaged gradient and bit-equal on every rank.  The first call builds the
+        plan (it allocates): make it before capturing this call into a graph."""
+        dev = self.device
+        norms = torch.empty(len(self.spec), dtype=torch.float32, device=dev)
+        stats = torch.empty(2, dtype=torch.float32, device=dev)
+        argmax = torch.empty(1, dtype=torch.int32, device=dev)
+        with torch.cuda.device(dev):
+            _lib.check(self._lib.taco_train_grad_norms(self._h, _st(), _p(self.grads), _p(norms), _p(stats), _p(argmax)))
+        return norms, stats, argmax
+
+    def gradient_stats(self):
+        """gradient_norms() fetched with one download: {"max_gradient_norm": the reference's summary scalar (train.py:59-63),
+        "argmax": the name of the variable that has it (None when nothing is trainable), "global_norm": what clip_by_global_norm divides
+        by, "norms": {name: norm} for the trainable names}."""
+        norms, stats, argmax = self.gradient_norms()
+        host = torch.cat([norms, stats, argmax.view(torch.float32)]).cpu().numpy()
+        n = len(self.spec)
+        am = int(host[n + 2:n + 3].view(np.int32)[0])
+        return {"max_gradient_norm": float(host[n]), "argmax": self.spec[am][0] if am >= 0 else None, "global_norm": float(host[n + 1]),
+                "norms": {name: float(host[i]) for i, (name, _) in enumerate(self.spec) if not is_moving_statistic(name)}}
+
     # ---- train-state checkpoints (train.py:175 `tf.train.Saver`, :189-203 restore, :242-244 save) ----
     def _layout_id(self):
         h = hashlib.sha256()
@@ -334,6 +392,7 @@ class Trainer(object):
             e, self._sync_err = self._sync_err, None
             raise e
         self.mel_outputs, self.linear_outputs, self.alignments = mel, lin, ali
+        self.have_gradients = self.have_gradients or bool(backward)
         return self.losses
 
     def capture(self, inputs, input_lengths, mel_targets, linear_targets, loss_coeff=None, speaker_id=None):
@@ -378,6 +437,7 @@ class Trainer(object):
         # hipMemsetAsync NODES of a captured graph were seen to fill with stale data once other work had run in between, see zero_async
         # in csrc/taco_lib.hip)
         self._graph.replay()
+        self.have_gradients = True
         return True
 
     def train_step(self, inputs, input_lengths, mel_targets, linear_targets, loss_coeff=None, speaker_id=None):

@@ -123,8 +123,71 @@ def measure(args):
     return report
 
 
+def measure_grad_stats(args):
+    """--grad-stats: taco_train_grad_norms (three launches: per-variable norms, their maximum, the global norm) against k_sumsq_partial
+    alone (one launch: the first half of the clip), over a gradient buffer of the C4-shard parameter count.  Both read the same bytes
+    once.  `reps` calls are captured into one hipGraph per kernel, rotating over `buffers` gradient buffers (8 x 37 MB: more than the
+    256 MiB Infinity Cache holds, so every call reads from HBM; 1: one buffer, served by the cache after the first call); the two graphs
+    are replayed alternately, `rounds` times each, and timed with device events.  One JSON line; no gate is attached."""
+    import ctypes as C
+    import numpy as np, torch, taco_amd
+    from taco_amd import _lib
+    torch.cuda.set_device(0)
+    dev = torch.device("cuda", 0)
+    hp = taco_amd.hparams.copy(max_iters=max(200, args.t_out // 4))
+    tr = taco_amd.Trainer(hp, taco_amd.weights.random_weights(hp, 1, seed=4321), device=str(dev))
+    lib, n = tr._lib, tr.num_params
+    gen = torch.Generator(device=dev); gen.manual_seed(99)
+    bufs = [torch.randn(n, device=dev, generator=gen) * 1e-3 for _ in range(max(1, args.grad_stats_buffers))]
+    norms, stats, am = torch.empty(len(tr.spec), device=dev), torch.empty(2, device=dev), torch.empty(1, dtype=torch.int32, device=dev)
+    ws = torch.empty(1 << 14, dtype=torch.uint8, device=dev)
+    P = lambda t: C.c_void_p(t.data_ptr())
+    st = lambda: C.c_void_p(torch.cuda.current_stream().cuda_stream)
+    ours = lambda g: _lib.check(lib.taco_train_grad_norms(tr._h, st(), P(g), P(norms), P(stats), P(am)))
+    yard = lambda g: _lib.check(lib.taco_debug_sumsq_partial(st(), P(g), n, P(ws), ws.numel()))
+    ours(bufs[0]); yard(bufs[0])                      # the first call builds the plan: outside the capture
+    torch.cuda.synchronize()
+    counted = torch.ones(n, dtype=torch.bool, device=dev)          # the moving statistics count nowhere
+    for name, (o, c) in tr.offsets.items():
+        if name not in set(tr.trainable):
+            counted[o:o + c] = False
+    want = float(torch.sqrt((bufs[0][counted].double() ** 2).sum()))
+    got = float(stats[1])
+    graphs = []
+    for fn in (ours, yard):
+        g = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(g):
+            for i in range(args.grad_stats_reps):
+                fn(bufs[i % len(bufs)])
+        g.replay(); torch.cuda.synchronize()          # warm: the first replay uploads the graph
+        graphs.append(g)
+    times = [[], []]
+    for _ in range(args.grad_stats_rounds):
+        for k, g in enumerate(graphs):                # alternating: the two see the same machine
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record(); g.replay(); e1.record(); torch.cuda.synchronize()
+            times[k].append(e0.elapsed_time(e1) * 1e3 / args.grad_stats_reps)
+    med = [float(np.median(t)) for t in times]
+    pieces = sum(-(-c // lib.taco_segnorm_piece_floats()) for name, (o, c) in tr.offsets.items() if name in set(tr.trainable))
+    rep = {"metric": "gradient summaries per call (C4-shard parameter count)", "value": med[0], "unit": "us",
+           "floats": n, "bytes_read": 4 * n, "variables": len(tr.spec), "trainable": len(tr.trainable), "pieces": pieces,
+           "piece_floats": lib.taco_segnorm_piece_floats(),
+           "grad_norms_us": {"median": med[0], "min": min(times[0]), "max": max(times[0]), "launches": 3},
+           "sumsq_partial_us": {"median": med[1], "min": min(times[1]), "max": max(times[1]), "launches": 1},
+           "grad_norms_TB_per_s": 4 * n / med[0] / 1e6, "sumsq_partial_TB_per_s": 4 * n / med[1] / 1e6,
+           "ratio": med[0] / med[1], "reps_per_graph": args.grad_stats_reps, "rounds": args.grad_stats_rounds,
+           "buffers": len(bufs), "source": "HBM (rotating buffers exceed the Infinity Cache)" if 4 * n * len(bufs) > (256 << 20) else "Infinity Cache after the first call",
+           "global_norm_check": {"device": got, "torch_float64": want}}
+    tr.close()
+    return rep
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--grad-stats", action="store_true", help="time taco_train_grad_norms against k_sumsq_partial alone at the C4-shard parameter count (one JSON line) instead of the train step")
+    ap.add_argument("--grad-stats-reps", type=int, default=200, help="--grad-stats: calls captured into one graph")
+    ap.add_argument("--grad-stats-rounds", type=int, default=20, help="--grad-stats: alternating replays of the two graphs")
+    ap.add_argument("--grad-stats-buffers", type=int, default=8, help="--grad-stats: gradient buffers the calls rotate over (8: HBM reads; 1: cache reads)")
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--batch", type=int, default=32)
@@ -162,7 +225,7 @@ def main():
         if dist is not None:
             dist.barrier(); dist.destroy_process_group()
         return
-    rep = measure(args)
+    rep = measure_grad_stats(args) if args.grad_stats else measure(args)
     if rep is not None:
         print(json.dumps(rep))
 
