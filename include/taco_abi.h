@@ -302,6 +302,34 @@ int taco_gl_inv_melspectrogram_rows(taco_gl* g, void* hip_stream, const float* d
                                     unsigned long long seed, int B, int T, int iters, float* d_wav, int32_t* d_num_samples,
                                     void* d_workspace, size_t workspace_bytes);
 
+/* ---- Fast Griffin-Lim (Perraudin, Balazs, Sondergaard 2013): momentum in the loop of all three vocoders ----
+ * With momentum a and c = a / (1 + a) every iteration projects z = t - c * t_prev in place of t = stft(y), t_prev the estimate of the
+ * iteration before (the first iteration: z = t): librosa.griffinlim's loop (0.7 and later) with the reference's own normalisation --
+ * S * exp(i angle(z)), angle(0) = 0, for inv_spectrogram and inv_melspectrogram, S * z / max(1e-8, |z|) for inv_spectrogram_tensorflow --
+ * in place of librosa's z / (|z| + 1e-16).  Not in the reference: momentum 0, the default, is the reference's loop, bit for bit and
+ * launch for launch.  The momentum is host state of the handle, read when a call is issued: a captured graph keeps the value it was
+ * captured with.  A non-zero momentum adds one [rows, 2*num_freq] estimate buffer to the loop's workspace, so taco_gl_workspace_bytes,
+ * taco_gl_rows_workspace_bytes and taco_gl_tf_workspace_bytes READ THE HANDLE: query them again after taco_gl_set_momentum.
+ * taco_gl_set_momentum: finite and 0 <= momentum <= 1, else TACO_ERR_ARG.  taco_gl_momentum: the value in use, 0 for NULL. */
+int taco_gl_set_momentum(taco_gl* g, float momentum);
+float taco_gl_momentum(const taco_gl* g);
+/* Spectral convergence sc[b] = || |stft(y_b)| - S_b || / || S_b || of B waveforms against the magnitudes they were synthesised
+ * from, over utterance b's own frames t < f_b and all num_freq bins; 0 where S_b is all zero.  d_wav [B, taco_gl_num_samples(T)] is
+ * the output rectangle of taco_gl_inv_spectrogram(_rows) / taco_gl_inv_melspectrogram_rows at any momentum and iteration count:
+ * the analysis is that of taco_spec_targets (pre-emphasis, which undoes the vocoder's inverse pre-emphasis; reflect padding at each
+ * row's own ends; row b has hop*(f_b - 1) samples), followed by a two-stage sum in one fixed order, without atomics: two calls and a
+ * captured replay give the same bits.  d_frames [B] is device memory (NULL: every row keeps T), clamped on the device to
+ * [taco_gl_min_frames, T] as the vocoder clamps it.  The target is formed on the fly from d_target [B, T, num_freq]:
+ *   target_kind 0   a normalised linear spectrogram, as the vocoder takes it: S = (10^((clip(x,0,1) * -min_db + min_db + ref_db) / 20))^power
+ *                   by the very function the vocoder fills its own target with
+ *   target_kind 1   the magnitudes themselves (for the mel vocoder: taco_gl_mel_to_linear's output raised to `power`)
+ * librosa-flavour handles only (a handle of taco_gl_create_tf: TACO_ERR_STATE).  NULL pointers, B outside [1, 65535], T < 2, another
+ * target_kind -> TACO_ERR_ARG; T < taco_gl_min_frames -> TACO_ERR_SHAPE; a workspace below taco_gl_convergence_workspace_bytes ->
+ * TACO_ERR_STATE; all of them before any HIP call.  No allocation, no synchronisation: capturable. */
+size_t taco_gl_convergence_workspace_bytes(const taco_gl* g, int B, int T);
+int taco_gl_convergence(taco_gl* g, void* hip_stream, const float* d_target, int target_kind, const int32_t* d_frames, const float* d_wav,
+                        int B, int T, float* d_sc, void* d_workspace, size_t workspace_bytes);
+
 /* Silence trimming of a synthesised waveform: the `librosa.effects.trim(audio_out, frame_length=5120, hop_length=256, top_db=50)` of
  * synthesizer.py:266-269 (`audio_out = audio_out[:index[-1]]`), per row of d_wav [B, L].  UNPINNED on librosa: the reference pins
  * librosa==0.5.1, this project does not depend on librosa, and what follows restates the documented algorithm; it could not be

@@ -163,6 +163,11 @@ int taco_debug_pcm_energy(void* hip_stream, const int16_t* d_pcm, const int32_t*
  * first device call, on a machine without a GPU; nothing may be launched on it.  Freed by taco_gl_destroy. */
 int taco_debug_gl_create_host(const taco_audio_hparams* hp, int tf_flavor, taco_gl** out);
 
+/* Test and timing hook: the projection kernel of one Griffin-Lim iteration alone, in the handle's flavour, on caller-supplied
+ * d_est, d_prev [R, 2*num_freq] (Re | Im), d_S [R, num_freq] -> d_X [R, 2*num_freq].  d_prev NULL: the plain loop's k_gl_project /
+ * k_gl_project_tf (c is not used); else k_gl_project_fast on z = est - c * prev. */
+int taco_debug_gl_project(taco_gl* g, void* hip_stream, const float* d_est, const float* d_prev, const float* d_S, float* d_X, float c, int R);
+
 /* Test hook: the host half of taco_model_finalize alone -- model_pack_host (csrc/taco_pack.h): every weight pack, the GemmVar table and, on a
  * shadow model, the index lists and backward packs -- with no handle and no device.  shadow = 0: flat_weights holds every tensor of the spec in
  * spec order, TF layout, no padding (the flat layout of taco_train_create); another n_floats is TACO_ERR_SHAPE.  shadow = 1: flat_weights must

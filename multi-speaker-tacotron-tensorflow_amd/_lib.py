@@ -149,6 +149,11 @@ PROTOTYPES = {
     "taco_gl_mel_to_linear": (_I, [_P, _P, _P, _I, _I, _P]),
     "taco_gl_inv_melspectrogram_rows": (_I, [_P, _P, _P, _P, _P, C.c_ulonglong, _I, _I, _I, _P, _P, _P, _S]),
     "taco_debug_gl_create_host": (_I, [C.POINTER(TacoAudioHParams), _I, C.POINTER(_P)]),
+    "taco_gl_set_momentum": (_I, [_P, C.c_float]),
+    "taco_gl_momentum": (C.c_float, [_P]),
+    "taco_gl_convergence_workspace_bytes": (_S, [_P, _I, _I]),
+    "taco_gl_convergence": (_I, [_P, _P, _P, _I, _P, _P, _I, _I, _P, _P, _S]),
+    "taco_debug_gl_project": (_I, [_P, _P, _P, _P, _P, _P, C.c_float, _I]),
     "taco_wav_trim_workspace_bytes": (_S, [_I, _I, _I, _I]),
     "taco_wav_trim": (_I, [_P, _P, _P, _I, _I, C.c_float, _I, _I, _I, _P, _P, _P, _S]),
     "taco_wav_split_workspace_bytes": (_S, [_I, _I, _I, _I]),

@@ -158,10 +158,12 @@ class _Handle(object):
 class GriffinLim(_Handle):
     """flavor "librosa" (default): the handle of inv_spectrogram / inv_melspectrogram and of everything Spectrogram adds.  "tensorflow":
     the handle of inv_spectrogram_tensorflow (tf.contrib.signal's uncentred STFT; the librosa-flavour methods raise TacoError on it).
-    pcm16, trim, split, remove_breath, nonsilent, range_sumsq, apply_gains, set_inv_mel_basis and mel_to_linear work on either."""
+    pcm16, trim, split, remove_breath, nonsilent, range_sumsq, apply_gains, set_inv_mel_basis and mel_to_linear work on either, and
+    so does the momentum of Fast Griffin-Lim (set_momentum; not in the reference, off by default); convergence is librosa-flavour."""
     _destroy = "taco_gl_destroy"
 
-    def __init__(self, hparams, device="cuda:0", flavor="librosa"):
+    def __init__(self, hparams, device="cuda:0", flavor="librosa", momentum=0.0):
+        """momentum: Fast Griffin-Lim (set_momentum); 0, the default, is the reference's loop."""
         self.hp = c_audio_hparams(hparams)
         self.hparams = hparams
         self.device = torch.device(device)
@@ -177,6 +179,24 @@ class GriffinLim(_Handle):
         _lib.check(create(C.byref(self.hp), idx, C.byref(self._h)))
         self._ws = None
         self._inv_mels = 0
+        if momentum:
+            self.set_momentum(momentum)
+
+    def set_momentum(self, momentum):
+        """Fast Griffin-Lim (Perraudin, Balazs, Sondergaard 2013) in the loop of all three vocoders: every iteration projects
+        stft(y) - c * (the estimate before it), c = momentum / (1 + momentum).  0 <= momentum <= 1; 0 is the reference's loop, bit
+        for bit; 0.99 is librosa.griffinlim's default.  Stays set until changed.  A non-zero value adds one estimate buffer to the
+        loop's workspace: every vocoder call asks the library for its size after the momentum is set."""
+        _lib.check(self._lib.taco_gl_set_momentum(self._h, float(momentum)))
+
+    @property
+    def momentum(self):
+        return float(self._lib.taco_gl_momentum(self._h))
+
+    def _momentum(self, momentum):
+        """The momentum keyword of the vocoder methods: None keeps the handle's value, a value is set and stays set"""
+        if momentum is not None:
+            self.set_momentum(momentum)
 
     def num_samples(self, T):
         return int(self._lib.taco_gl_num_samples(self._h, T))
@@ -184,25 +204,28 @@ class GriffinLim(_Handle):
     def min_frames(self):
         return int(self._lib.taco_gl_min_frames(self._h))
 
-    def inv_spectrogram(self, linear, init_uniform=None, seed=0, iters=None):
+    def inv_spectrogram(self, linear, init_uniform=None, seed=0, iters=None, momentum=None):
         """linear [B, T, num_freq] (model layout; numpy or tensor) -> waveforms [B, hop*(T-1)] (device tensor).
-        init_uniform [B, T, num_freq] in [0,1) replaces the reference's np.random.rand initial phases (default: hash of seed)."""
-        return self.inv_spectrogram_rows(linear, None, init_uniform, seed, iters)[0]
+        init_uniform [B, T, num_freq] in [0,1) replaces the reference's np.random.rand initial phases (default: hash of seed).
+        momentum: None keeps the handle's (set_momentum); a value is set for this call and stays set."""
+        return self.inv_spectrogram_rows(linear, None, init_uniform, seed, iters, momentum)[0]
 
-    def inv_spectrogram_rows(self, linear, frames, init_uniform=None, seed=0, iters=None):
+    def inv_spectrogram_rows(self, linear, frames, init_uniform=None, seed=0, iters=None, momentum=None):
         """Per utterance length (synthesizer.py:242-264: `inv_spectrogram(wav[:spec_end_idx].T)`): linear [B, T, num_freq], frames [B]
         (a device int32 tensor is used as it is and never read on the host -- Synthesizer.attention_trim's kernel output; host data is
         uploaded; None: all T) -> (wav [B, hop*(T-1)], num_samples [B] int32), device tensors.  Row b holds the waveform of its first
-        frames[b] frames (clamped to [min_frames(), T]) in its first num_samples[b] samples and zeros after."""
-        return self._vocode_rows(self._lib.taco_gl_inv_spectrogram_rows, linear, "linear", ("num_freq", self.hp.num_freq), frames, init_uniform, seed, iters)
+        frames[b] frames (clamped to [min_frames(), T]) in its first num_samples[b] samples and zeros after.  momentum as inv_spectrogram."""
+        return self._vocode_rows(self._lib.taco_gl_inv_spectrogram_rows, linear, "linear", ("num_freq", self.hp.num_freq), frames, init_uniform, seed, iters,
+                                 momentum)
 
-    def _vocode_rows(self, fn, x, what, width, frames, init_uniform, seed, iters):
+    def _vocode_rows(self, fn, x, what, width, frames, init_uniform, seed, iters, momentum=None):
         """The librosa-flavour vocoders: fn is the entry point, x [B, T, width[1]] its input, named `what` and its last dimension width[0] in errors"""
         dev = self.device
         x = _tensor(x, dev, torch.float32, what, ("B", "T", width))
         B, T, _ = x.shape
         u = None if init_uniform is None else _tensor(init_uniform, dev, torch.float32, "init_uniform", (("B", B), ("T", T), ("num_freq", self.hp.num_freq)))
         fr = _lengths(frames, dev, B, "frames")
+        self._momentum(momentum)      # before the size is asked for: the workspace depends on it
         ws = _workspace(self, self._lib.taco_gl_rows_workspace_bytes(self._h, B, T))
         wav = torch.empty((B, self.num_samples(T)), dtype=torch.float32, device=dev)
         ns = torch.empty((B,), dtype=torch.int32, device=dev)
@@ -212,17 +235,18 @@ class GriffinLim(_Handle):
     def tf_num_samples(self, T):
         return int(self._lib.taco_gl_tf_num_samples(self._h, T))
 
-    def inv_spectrogram_tensorflow(self, linear, frames=None, iters=None):
+    def inv_spectrogram_tensorflow(self, linear, frames=None, iters=None, momentum=None):
         """inv_spectrogram_tensorflow of audio/__init__.py:59-61,87-96 (the reference's Synthesizer.wav_output, synthesizer.py:53-54) on
         a flavor="tensorflow" handle: linear [B, T, num_freq], frames [B] (a device int32 tensor is used as it is; None: all T; clamped
         to [1, T]) -> (wav [B, hop*(T-1) + win], num_samples [B] int32), device tensors.  Zero initial phase, est / max(1e-8, |est|), no
         inverse pre-emphasis: the same spectrogram always gives the same samples.  Row b is the vocoding of linear[b, :frames[b]] in
         its first hop*(frames[b]-1) + win samples, zeros after.  UNPINNED on TensorFlow: tf.contrib.signal.stft / inverse_stft restated
-        (include/taco_abi.h), checked against tests/vocoder_reference.py, not against TensorFlow."""
+        (include/taco_abi.h), checked against tests/vocoder_reference.py, not against TensorFlow.  momentum as inv_spectrogram."""
         dev = self.device
         x = _tensor(linear, dev, torch.float32, "linear", ("B", "T", ("num_freq", self.hp.num_freq)))
         B, T, _ = x.shape
         fr = _lengths(frames, dev, B, "frames")
+        self._momentum(momentum)      # before the size is asked for: the workspace depends on it
         ws = _workspace(self, self._lib.taco_gl_tf_workspace_bytes(self._h, B, T))
         wav = torch.empty((B, self.tf_num_samples(T)), dtype=torch.float32, device=dev)
         ns = torch.empty((B,), dtype=torch.int32, device=dev)
@@ -256,10 +280,32 @@ class GriffinLim(_Handle):
         _call(self.device, self._lib.taco_gl_mel_to_linear, self._h, _STREAM, x, B, T, out)
         return out
 
-    def inv_melspectrogram(self, mel, frames=None, init_uniform=None, seed=0, iters=None):
+    def inv_melspectrogram(self, mel, frames=None, init_uniform=None, seed=0, iters=None, momentum=None):
         """inv_melspectrogram of audio/__init__.py:70-72 per utterance length: mel [B, T, num_mels] -> (wav [B, hop*(T-1)], num_samples [B]
-        int32), device tensors; frames, init_uniform, seed and iters as inv_spectrogram_rows."""
-        return self._vocode_rows(self._lib.taco_gl_inv_melspectrogram_rows, mel, "mel", ("num_mels", self._need_inv_mels()), frames, init_uniform, seed, iters)
+        int32), device tensors; frames, init_uniform, seed, iters and momentum as inv_spectrogram_rows."""
+        return self._vocode_rows(self._lib.taco_gl_inv_melspectrogram_rows, mel, "mel", ("num_mels", self._need_inv_mels()), frames, init_uniform, seed, iters,
+                                 momentum)
+
+    _TARGET_KINDS = {"normalised": 0, "magnitude": 1}
+
+    def convergence(self, target, wav, frames=None, kind="normalised"):
+        """Spectral convergence || |stft(y)| - S || / || S || per utterance (taco_gl_convergence): how consistent the phases of a
+        vocoder's output are with the magnitudes it was made from, at any momentum and iteration count.  wav [B, hop*(T-1)] is the
+        output rectangle of inv_spectrogram(_rows) / inv_melspectrogram, frames [B] the vector that call was given (None: all T).
+        target [B, T, num_freq]: kind "normalised", the linear spectrogram the vocoder took; kind "magnitude", the magnitudes
+        themselves -- for the mel vocoder mel_to_linear(mel) ** hparams.power.  Returns a device tensor [B]; 0 for a silent target.
+        librosa flavour only."""
+        if kind not in self._TARGET_KINDS:
+            raise _lib.TacoError(_lib.TACO_ERR_ARG, "kind must be one of %s, got %r" % (sorted(self._TARGET_KINDS), kind))
+        dev = self.device
+        x = _tensor(target, dev, torch.float32, "target", ("B", "T", ("num_freq", self.hp.num_freq)))
+        B, T, _ = x.shape
+        y = _tensor(wav, dev, torch.float32, "wav", (("B", B), ("hop*(T-1)", self.num_samples(T))))
+        fr = _lengths(frames, dev, B, "frames")
+        ws = _workspace(self, self._lib.taco_gl_convergence_workspace_bytes(self._h, B, T))
+        sc = torch.empty((B,), dtype=torch.float32, device=dev)
+        _call(dev, self._lib.taco_gl_convergence, self._h, _STREAM, x, self._TARGET_KINDS[kind], fr, y, B, T, sc, ws, ws.numel())
+        return sc
 
     def pcm16(self, wav, num_samples=None):
         """save_audio's scaling (audio/__init__.py:23-24) per row: wav [B, L] float32, num_samples [B] (None: L) -> int16 [B, L] (device

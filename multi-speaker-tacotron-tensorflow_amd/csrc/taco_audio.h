@@ -22,24 +22,30 @@ struct taco_gl {
   int flavor = GL_LIBROSA;       // GL_TF (taco_gl_create_tf): tf.contrib.signal's uncentred STFT, lpad = 0, w2 unused
   int inv_mels = 0;              // inv_mel_basis: filters of the pseudo-inverse in use (taco_gl_set_inv_mel_basis; 0 = not set)
   float* inv_mel = nullptr;      // [inv_mels, F] mel-major: consecutive lanes read consecutive bins
+  // Fast Griffin-Lim (taco_gl_set_momentum): 0 = the reference's loop.  Host state, read when a call is issued; non-zero adds the
+  // second estimate buffer to the workspace (carve_gl)
+  float momentum = 0.f;
 };
 
 // ---- kernels ----
 // Frames utterance b keeps: T, or frames[b] (device memory, taco_gl_inv_spectrogram_rows) clamped to [fmin, T].  Every kernel that
 // depends on an utterance's length takes the nullable `frames` and calls this; with NULL each one computes what it did before.
 __device__ __forceinline__ int gl_frames(const int* frames, int b, int T, int fmin) { return frames ? min(max(frames[b], fmin), T) : T; }
-// S = (10^((clip(x,0,1) * -min_db + min_db + ref_db) / 20))^power ; rows t >= the utterance's frames of every slot are zero
+// The magnitude a normalised linear bin x stands for: (10^((clip(x,0,1) * -min_db + min_db + ref_db) / 20))^power.  Written once:
+// k_gl_magnitude fills the loop's target with it and k_gl_convergence_partial judges the result against it
+__device__ __forceinline__ float gl_magnitude_of(float v, float min_db, float ref_db, float power) {
+  const float x = fminf(fmaxf(v, 0.f), 1.f);
+  const float db = x * -min_db + min_db + ref_db;
+  return powf(powf(10.f, db * 0.05f), power);
+}
+// S = gl_magnitude_of(spec) ; rows t >= the utterance's frames of every slot are zero
 __global__ void k_gl_magnitude(const float* spec, float* S, const int* frames, int fmin, int B, int T, int Tr, int F, float min_db,
                                float ref_db, float power) {
   const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= (size_t)B * Tr * F) return;
   const int f = (int)(i % F); const size_t row = i / F; const int t = (int)(row % Tr), b = (int)(row / Tr);
   float v = 0.f;
-  if (t < gl_frames(frames, b, T, fmin)) {
-    const float x = fminf(fmaxf(spec[((size_t)b * T + t) * F + f], 0.f), 1.f);
-    const float db = x * -min_db + min_db + ref_db;
-    v = powf(powf(10.f, db * 0.05f), power);
-  }
+  if (t < gl_frames(frames, b, T, fmin)) v = gl_magnitude_of(spec[((size_t)b * T + t) * F + f], min_db, ref_db, power);
   S[i] = v;
 }
 __device__ __forceinline__ float gl_hash_uniform(unsigned long long seed, size_t i) {   // counter-based: splitmix64 -> [0,1)
@@ -169,6 +175,53 @@ __global__ void k_gl_project_tf(const float* est, const float* S, float* X, size
   // (rows past an utterance's frames have S = 0 and are written as exact zeros whatever their estimate is)
   X[row * 2 * F + f] = s != 0.f ? s * (re / d) : 0.f;
   X[row * 2 * F + F + f] = s != 0.f ? s * (im / d) : 0.f;
+}
+// Fast Griffin-Lim (Perraudin, Balazs, Sondergaard 2013; librosa.griffinlim's loop): the projection of z = est - c * prev, prev the
+// estimate of the iteration before and c = momentum / (1 + momentum).  TF = false: X = S * exp(i angle(z)) with angle(0) = 0, as
+// k_gl_project; TF = true: X = S * z / max(1e-8, |z|), as k_gl_project_tf.  The forward product writes its estimates into two
+// buffers in turn, so est and prev are "this one" and "the other one" and nothing is copied.  A bin with S = 0 -- every bin of a
+// row past its utterance's frames, whose est and prev hold whatever the slot's slack gave the product -- is written as exact
+// zeros without looking at z, so nothing that is not finite there can reach X.
+// V bins per thread: 2 where F is even -- then every offset below is even and est, prev, S and X (8-byte aligned) are read and
+// written as 8-byte words; with F odd (every n_fft that is a multiple of 4, the reference's included) the Im plane of a row starts
+// at an odd word, no pair of both planes is aligned, and V = 1 reads consecutive 4-byte words from consecutive lanes.
+// 28 bytes per bin (est, prev, X: 8 each; S: 4) against k_gl_project's 20.
+template <bool TF, int V>
+__global__ void k_gl_project_fast(const float* est, const float* prev, const float* S, float* X, float c, size_t rows, int F) {
+  const size_t i = ((size_t)blockIdx.x * blockDim.x + threadIdx.x) * V;
+  if (i >= rows * F) return;
+  const size_t row = i / F; const int f = (int)(i % F);
+  const size_t o = row * 2 * F + f;
+  float re[V], im[V], pr[V], pi[V], s[V], xr[V], xi[V];
+  if constexpr (V == 2) {
+    const float2 a = *reinterpret_cast<const float2*>(est + o), b = *reinterpret_cast<const float2*>(est + o + F);
+    const float2 p = *reinterpret_cast<const float2*>(prev + o), q = *reinterpret_cast<const float2*>(prev + o + F);
+    const float2 m = *reinterpret_cast<const float2*>(S + i);
+    re[0] = a.x; re[1] = a.y; im[0] = b.x; im[1] = b.y; pr[0] = p.x; pr[1] = p.y; pi[0] = q.x; pi[1] = q.y; s[0] = m.x; s[1] = m.y;
+  } else {
+    re[0] = est[o]; im[0] = est[o + F]; pr[0] = prev[o]; pi[0] = prev[o + F]; s[0] = S[i];
+  }
+#pragma unroll
+  for (int v = 0; v < V; ++v) {
+    const float zr = re[v] - c * pr[v], zi = im[v] - c * pi[v];
+    const float mag = sqrtf(zr * zr + zi * zi);
+    xr[v] = 0.f; xi[v] = 0.f;
+    if (s[v] != 0.f) {
+      if (TF) {
+        const float d = fmaxf(1e-8f, mag);
+        xr[v] = s[v] * (zr / d); xi[v] = s[v] * (zi / d);
+      } else {
+        xr[v] = mag > 0.f ? s[v] * zr / mag : s[v];
+        xi[v] = mag > 0.f ? s[v] * zi / mag : 0.f;
+      }
+    }
+  }
+  if constexpr (V == 2) {
+    *reinterpret_cast<float2*>(X + o) = make_float2(xr[0], xr[1]);
+    *reinterpret_cast<float2*>(X + o + F) = make_float2(xi[0], xi[1]);
+  } else {
+    X[o] = xr[0]; X[o + F] = xi[0];
+  }
 }
 // inverse_stft's overlap-add: y[s] = sum over the frames t that cover s of Y[t, s - t*hop], Y [B, Tr, win] the windowed irfft frames.  No
 // window sum-square and no reflect padding; the frames are visited in the order of k_gl_overlap_add.  Utterance b writes its own
@@ -572,15 +625,68 @@ __global__ __launch_bounds__(256) void k_spec_targets(const float* est, const in
   }
 }
 
+// ---- spectral convergence of a waveform against its target (taco_gl_convergence) ----
+#define CONV_ROWS 8            // frame rows per workgroup of k_gl_convergence_partial
+// hop * (frames - 1) per utterance, frames clamped as the vocoder clamps them: the sample counts k_spec_prepare takes
+__global__ void k_gl_frames_to_samples(const int* frames, int fmin, int T, int hop, int B, int* num_samples) {
+  const int b = blockIdx.x * blockDim.x + threadIdx.x;
+  if (b < B) num_samples[b] = hop * (gl_frames(frames, b, T, fmin) - 1);
+}
+// Stage one of sc[b] = ||  |est| - S || / || S || over utterance b's own frames t < nframes[b] and all F bins: the workgroup of
+// (tile, b) sums num = (|est| - S)^2 and den = S^2 over its CONV_ROWS frame rows of est [B*Tr, 2F] (Re | Im) into part[b, tile] =
+// {num, den}; a tile past the utterance's frames writes zeros.  S is formed on the fly: kind 0, target [B, T, F] is a normalised
+// linear spectrogram and S = gl_magnitude_of(target), the law of k_gl_magnitude; kind 1, target holds the magnitudes themselves.
+// One order per sum and no atomics: thread i adds the bins i, i + 256, ... of the tile's rows in ascending row with one fmaf each, a
+// butterfly of fixed shape joins the 64 lanes of a wave, and thread 0 adds the four wave sums in ascending order.
+// grid (tiles of CONV_ROWS rows, B), 256 threads.
+__global__ __launch_bounds__(256) void k_gl_convergence_partial(const float* est, const float* target, int kind, const int* nframes, int T, int Tr,
+                                                                int F, float min_db, float ref_db, float power, float* part) {
+  __shared__ float wsum[4][2];
+  const int b = blockIdx.y, t0 = blockIdx.x * CONV_ROWS, tid = threadIdx.x;
+  const int Tb = min(nframes[b], T);
+  float num = 0.f, den = 0.f;
+  for (int r = 0; r < CONV_ROWS; ++r) {
+    const int t = t0 + r;
+    if (t >= Tb) break;
+    const float* e = est + ((size_t)b * Tr + t) * 2 * F;
+    const float* g = target + ((size_t)b * T + t) * F;
+    for (int f = tid; f < F; f += 256) {
+      const float re = e[f], im = e[F + f];
+      const float s = kind ? g[f] : gl_magnitude_of(g[f], min_db, ref_db, power);
+      const float d = sqrtf(re * re + im * im) - s;
+      num = fmaf(d, d, num); den = fmaf(s, s, den);
+    }
+  }
+  for (int o = 32; o > 0; o >>= 1) { num += __shfl_xor(num, o); den += __shfl_xor(den, o); }
+  if ((tid & 63) == 0) { wsum[tid >> 6][0] = num; wsum[tid >> 6][1] = den; }
+  __syncthreads();
+  if (tid == 0) {
+    float* p = part + ((size_t)b * gridDim.x + blockIdx.x) * 2;
+    p[0] = ((wsum[0][0] + wsum[1][0]) + wsum[2][0]) + wsum[3][0];
+    p[1] = ((wsum[0][1] + wsum[1][1]) + wsum[2][1]) + wsum[3][1];
+  }
+}
+// Stage two: sc[b] = sqrt(num / den) from the utterance's P partial pairs, 0 where den == 0 (a silent target).  One wave per
+// utterance: lane l adds the pairs l, l + 64, ... in that order, a butterfly of fixed shape joins the lanes.
+__global__ __launch_bounds__(64) void k_gl_convergence_final(const float* part, int P, float* sc) {
+  const int b = blockIdx.x, lane = threadIdx.x;
+  const float* p = part + (size_t)b * P * 2;
+  float num = 0.f, den = 0.f;
+  for (int i = lane; i < P; i += 64) { num += p[2 * i]; den += p[2 * i + 1]; }
+  for (int o = 32; o > 0; o >>= 1) { num += __shfl_xor(num, o); den += __shfl_xor(den, o); }
+  if (lane == 0) sc[b] = den > 0.f ? sqrtf(num / den) : 0.f;
+}
+
 // ---- host ----
 static int gl_rows(const taco_gl* g, int T) { return T + cdiv(g->n_fft, g->hop); }                 // frames per utterance slot (tail frames read the slack)
 static size_t gl_slot(const taco_gl* g, int T) { return (size_t)gl_rows(g, T) * g->hop; }          // samples per utterance slot >= hop*(T-1) + n_fft
-struct GlWs { float *S, *X, *est, *Y, *ypad, *wss; };
+struct GlWs { float *S, *X, *est, *Y, *ypad, *wss, *est2; };      // est2: the other estimate buffer of the fast loop, NULL at momentum 0
 static void carve_gl(Carver& cv, const taco_gl* g, int B, int T, GlWs& w) {
   const size_t R = (size_t)B * gl_rows(g, T);
   w.S = cv.f(R * g->F); w.X = cv.f(R * 2 * g->F); w.est = cv.f(R * 2 * g->F); w.Y = cv.f(R * g->win);
   w.ypad = cv.f((size_t)B * gl_slot(g, T) + 2 * g->n_fft + g->win);
   w.wss = cv.f((size_t)g->hop * (T - 1) + g->n_fft);
+  w.est2 = g->momentum != 0.f ? cv.f(R * 2 * g->F) : nullptr;      // last, and only then: at momentum 0 the layout and its size are what they were
 }
 static size_t mel_lds_bytes(int num_mels) { return (size_t)MELMAG_ROWS * num_mels * sizeof(float); }   // k_gl_mel_magnitude's amplitudes
 // analysis: T = 1 + Lmax / hop frames per utterance in the slot geometry above (a padded utterance is Lmax + n_fft <= gl_slot samples)
@@ -590,6 +696,13 @@ static void carve_spec(Carver& cv, const taco_gl* g, int B, int T, SpecWs& w) {
   w.ypad = cv.f((size_t)B * gl_slot(g, T) + spec_tail(g));
   w.est = cv.f((size_t)B * gl_rows(g, T) * 2 * g->F);
   w.nf = cv.i(B);
+}
+// convergence: the analysis workspace, the sample counts k_spec_prepare reads and the partial pairs of k_gl_convergence_partial
+struct ConvWs { SpecWs spec; int* ns; float* part; };
+static void carve_conv(Carver& cv, const taco_gl* g, int B, int T, ConvWs& w) {
+  carve_spec(cv, g, B, T, w.spec);
+  w.ns = cv.i(B);
+  w.part = cv.f((size_t)B * cdiv(T, CONV_ROWS) * 2);
 }
 // silence trimming: frames per tile of k_trim_energy, the most (<= TRIM_FRAMES) whose samples and window fit TRIM_LDS_BYTES; 0 = not even one
 static size_t trim_lds_bytes(int N, int hop, int fpt, int energy) {

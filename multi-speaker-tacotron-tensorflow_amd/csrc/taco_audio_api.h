@@ -84,12 +84,38 @@ static size_t gl_carved_bytes(const taco_gl* g, int B, int T) { Carver cv(nullpt
 size_t taco_gl_workspace_bytes(const taco_gl* g, int B, int T) { return (!g || B <= 0 || T <= 1) ? 0 : gl_carved_bytes(g, B, T); }
 size_t taco_gl_rows_workspace_bytes(const taco_gl* g, int B, int T) { return taco_gl_workspace_bytes(g, B, T); }   // same slot layout
 
+// Fast Griffin-Lim: host state of the handle, read by gl_iterate and by carve_gl (the three workspace sizes above and below)
+int taco_gl_set_momentum(taco_gl* g, float momentum) {
+  if (!g) return fail(TACO_ERR_ARG, "null argument");
+  if (!(momentum >= 0.f && momentum <= 1.f)) return fail(TACO_ERR_ARG, "momentum = %g: must be finite and in [0, 1]", (double)momentum);
+  g->momentum = momentum;
+  return 0;
+}
+float taco_gl_momentum(const taco_gl* g) { return g ? g->momentum : 0.f; }
+
 // The Griffin-Lim iteration of either flavour, on a workspace whose S and X the flavour's prologue has filled: y = istft(X), then
 // `iters` times est = stft(y), X = project(est, S), y = istft(X).  The two matrix products are the same for both; overlap_add()
 // launches the flavour's overlap-add of the frames w.Y into w.ypad, `project` is its projection kernel.
+// With the handle's momentum a != 0 (taco_gl_set_momentum) the projection is of z = est - c * prev, c = a / (1 + a), prev the
+// estimate of the iteration before: the forward product writes into w.est and w.est2 in turn and k_gl_project_fast reads "this
+// one" and "the other one".  The first iteration has no previous estimate and takes `project` as it stands.  At a = 0 the
+// launches are the plain loop's, on w.est alone.
+static void gl_launch_project_fast(hipStream_t st, bool tf, const float* est, const float* prev, const float* S, float* X, float c, size_t R, int F) {
+  const bool pair = F % 2 == 0 && !((reinterpret_cast<uintptr_t>(est) | reinterpret_cast<uintptr_t>(prev) | reinterpret_cast<uintptr_t>(S) |
+                                     reinterpret_cast<uintptr_t>(X)) & 7);
+  if (pair) {
+    if (tf) hipLaunchKernelGGL((k_gl_project_fast<true, 2>), EWGRID(R * F / 2), 0, st, est, prev, S, X, c, R, F);
+    else hipLaunchKernelGGL((k_gl_project_fast<false, 2>), EWGRID(R * F / 2), 0, st, est, prev, S, X, c, R, F);
+  } else {
+    if (tf) hipLaunchKernelGGL((k_gl_project_fast<true, 1>), EWGRID(R * F), 0, st, est, prev, S, X, c, R, F);
+    else hipLaunchKernelGGL((k_gl_project_fast<false, 1>), EWGRID(R * F), 0, st, est, prev, S, X, c, R, F);
+  }
+}
 static int gl_iterate(taco_gl* g, hipStream_t st, const GlWs& w, size_t R, int iters, void (*project)(const float*, const float*, float*, size_t, int),
                       const std::function<void()>& overlap_add) {
   const int F = g->F;
+  const float mc = g->momentum / (1.0f + g->momentum);
+  float *cur = w.est, *other = w.est2;
   auto synth = [&]() -> int {     // frames = X . IDFT_w (win columns), then the flavour's overlap-add
     GemmCall c; c.x = w.X; c.ldx = 2 * F; c.M = (int)R; c.out = w.Y; c.ldo = g->win;
     TRY(run_gemm(g->gm, st, &g->inv, 1, false, c));
@@ -102,10 +128,12 @@ static int gl_iterate(taco_gl* g, hipStream_t st, const GlWs& w, size_t R, int i
     // est = stft(y): row (b, t) of the frame matrix is the hop-strided window ypad[b*slot + t*hop + lpad ...][0 .. win) (lpad = 0 on a TF
     // handle: pad_end=False, the utterance's hop*(f-1) + win samples hold exactly f frames); rows past an utterance's own frames read
     // whatever its slot holds there and are multiplied by S = 0 in the projection
-    GemmCall c; c.x = w.ypad + g->lpad; c.ldx = g->hop; c.M = (int)R; c.out = w.est; c.ldo = 2 * F;
+    GemmCall c; c.x = w.ypad + g->lpad; c.ldx = g->hop; c.M = (int)R; c.out = cur; c.ldo = 2 * F;
     TRY(run_gemm(g->gm, st, &g->fwd, 1, false, c));
-    hipLaunchKernelGGL(project, EWGRID(R * F), 0, st, w.est, w.S, w.X, R, F);
+    if (other && it > 0) gl_launch_project_fast(st, g->flavor == GL_TF, cur, other, w.S, w.X, mc, R, F);
+    else hipLaunchKernelGGL(project, EWGRID(R * F), 0, st, cur, w.S, w.X, R, F);
     HIPCHK(hipGetLastError());
+    if (other) std::swap(cur, other);
     TRY(synth());
   }
   return 0;
@@ -408,6 +436,57 @@ int taco_debug_spec_epilogue(taco_gl* g, void* hip_stream, const float* d_est, i
   TRY(spec_check(g, d_mel));
   HIPCHK(hipSetDevice(g->gm->device));
   return spec_epilogue(g, (hipStream_t)hip_stream, d_est, nullptr, 1, R, R, d_linear, d_mel);
+}
+
+// ---- spectral convergence of a vocoder's output against its target ----
+size_t taco_gl_convergence_workspace_bytes(const taco_gl* g, int B, int T) {
+  if (!g || B <= 0 || T <= 1) return 0;
+  Carver cv(nullptr, 0);
+  ConvWs w; carve_conv(cv, g, B, T, w);
+  return cv.off;
+}
+
+// The analysis of taco_spec_targets on the vocoder's own output rectangle -- k_spec_prepare (its pre-emphasis undoes the vocoder's
+// inverse pre-emphasis; reflect padding at each utterance's own ends), the forward product -- then the two convergence kernels on
+// the estimate matrix.  Every check comes before the first HIP call.
+int taco_gl_convergence(taco_gl* g, void* hip_stream, const float* d_target, int target_kind, const int32_t* d_frames, const float* d_wav, int B,
+                        int T, float* d_sc, void* d_workspace, size_t workspace_bytes) {
+  if (!g || !d_target || !d_wav || !d_sc || !d_workspace || B <= 0 || B > 65535 || T <= 1) return fail(TACO_ERR_ARG, "bad argument");
+  if (target_kind != 0 && target_kind != 1) return fail(TACO_ERR_ARG, "unknown target kind %d", target_kind);
+  if (g->flavor != GL_LIBROSA) return fail(TACO_ERR_STATE, "a handle of taco_gl_create_tf serves taco_gl_inv_spectrogram_tf only");
+  const int L = g->hop * (T - 1), half = g->n_fft / 2, Tr = gl_rows(g, T), F = g->F, fmin = taco_gl_min_frames(g);
+  if (L <= half) return fail(TACO_ERR_SHAPE, "utterance too short for reflect padding: hop*(T-1) = %d <= n_fft/2 = %d", L, half);
+  if ((size_t)B * Tr > (size_t)0x7fffffff) return fail(TACO_ERR_SHAPE, "too many frame rows: %zu", (size_t)B * Tr);
+  Carver cv(d_workspace, workspace_bytes);
+  ConvWs w; carve_conv(cv, g, B, T, w);
+  if (!cv.ok()) return fail(TACO_ERR_STATE, "workspace too small: need %zu bytes, have %zu", cv.off, workspace_bytes);
+  HIPCHK(hipSetDevice(g->gm->device));
+  hipStream_t st = (hipStream_t)hip_stream;
+  const size_t slot = gl_slot(g, T), tail = spec_tail(g);
+  if (d_frames) hipLaunchKernelGGL(k_gl_frames_to_samples, EWGRID(B), 0, st, d_frames, fmin, T, g->hop, B, w.ns);
+  // row b keeps hop*(frames_b - 1) > n_fft/2 samples, so k_spec_prepare's own clamp changes nothing and nf = 1 + n/hop = frames_b
+  hipLaunchKernelGGL(k_spec_prepare, dim3((unsigned)((slot + tail + 255) / 256), B), dim3(256), 0, st, d_wav, d_frames ? w.ns : nullptr, w.spec.ypad,
+                     w.spec.nf, (int*)nullptr, B, L, g->hop, half, slot, tail, g->hp.preemphasis);
+  HIPCHK(hipGetLastError());
+  GemmCall c; c.x = w.spec.ypad + g->lpad; c.ldx = g->hop; c.M = B * Tr; c.out = w.spec.est; c.ldo = 2 * F;      // as taco_spec_targets
+  TRY(run_gemm(g->gm, st, &g->fwd, 1, false, c));
+  const int P = cdiv(T, CONV_ROWS);
+  hipLaunchKernelGGL(k_gl_convergence_partial, dim3(P, B), dim3(256), 0, st, w.spec.est, d_target, target_kind, w.spec.nf, T, Tr, F, g->hp.min_level_db,
+                     g->hp.ref_level_db, g->hp.power, w.part);
+  hipLaunchKernelGGL(k_gl_convergence_final, dim3(B), dim3(64), 0, st, w.part, P, d_sc);
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
+int taco_debug_gl_project(taco_gl* g, void* hip_stream, const float* d_est, const float* d_prev, const float* d_S, float* d_X, float c, int R) {
+  if (!g || !d_est || !d_S || !d_X || R <= 0) return fail(TACO_ERR_ARG, "bad argument");
+  HIPCHK(hipSetDevice(g->gm->device));
+  hipStream_t st = (hipStream_t)hip_stream;
+  const bool tf = g->flavor == GL_TF;
+  if (d_prev) gl_launch_project_fast(st, tf, d_est, d_prev, d_S, d_X, c, (size_t)R, g->F);
+  else hipLaunchKernelGGL(tf ? k_gl_project_tf : k_gl_project, EWGRID((size_t)R * g->F), 0, st, d_est, d_S, d_X, (size_t)R, g->F);
+  HIPCHK(hipGetLastError());
+  return 0;
 }
 
 // ---- splitting and levelling 16-bit PCM on silence: pydub.silence.detect_nonsilent (audio/silence.py:81-117, app.py:27-53) ----

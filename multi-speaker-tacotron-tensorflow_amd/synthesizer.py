@@ -153,7 +153,7 @@ class Synthesizer(object):
 
     def synthesize_audio(self, texts=None, tokens=None, speaker_ids=None, end_of_sentence=True, attention_trim=True,
                          manual_alignments=None, seed=0, iters=None, pcm=True, librosa_trim=False, vocoder="griffin_lim",
-                         manual_attention_mode=0):
+                         manual_attention_mode=0, momentum=None, return_convergence=False):
         """The reference's synthesize -> plot_graph_and_save_audio chain up to the samples save_audio writes (synthesizer.py:119-126,
         242-264; audio/__init__.py:22-25), everything between the token upload and the audio download on the device: the forward, the
         attention trim on the device alignments, Griffin-Lim on every utterance's own frames read from the trim kernel's output, the
@@ -173,13 +173,20 @@ class Synthesizer(object):
         manual_attention_mode 1 or 3 (synthesizer.py:171-205): the two-pass synthesis of `synthesize`, still without leaving the device
         -- forward, the second pass's alignments from the first pass's (Tacotron.manual_alignments_from), second forward -- and the trim,
         the vocoder and the PCM step then run on the second pass.  It excludes an explicit `manual_alignments` (TacoError(TACO_ERR_ARG));
-        mode 2 raises as manual_alignments_of does."""
+        mode 2 raises as manual_alignments_of does.
+        momentum: Fast Griffin-Lim in whichever vocoder runs (GriffinLim.set_momentum; not in the reference).  None keeps the
+        vocoder handle's value, 0 unless an earlier call set one; a value is set and stays set.
+        return_convergence: `convergence` is set to a float32 array [N], each utterance's spectral convergence || |stft(y)| - S || /
+        || S || over its own frames (GriffinLim.convergence), measured on the device on the vocoder's output before any librosa_trim;
+        for "griffin_lim" and "mel" -- with "tensorflow" it raises TacoError(TACO_ERR_ARG).  Off (the default): `convergence` is None."""
         from . import _lib
         if manual_attention_mode > 0 and manual_alignments is not None:
             raise _lib.TacoError(_lib.TACO_ERR_ARG, "manual_attention_mode builds the second pass's alignments itself: it cannot be "
                                  "combined with manual_alignments")
         if vocoder not in ("griffin_lim", "tensorflow", "mel"):
             raise _lib.TacoError(_lib.TACO_ERR_ARG, "vocoder must be 'griffin_lim', 'tensorflow' or 'mel', got %r" % (vocoder,))
+        if return_convergence and vocoder == "tensorflow":
+            raise _lib.TacoError(_lib.TACO_ERR_ARG, "return_convergence serves the librosa-flavour vocoders 'griffin_lim' and 'mel', not 'tensorflow'")
         sequences = self._token_rows(texts, tokens)
         input_lengths = np.argmax(sequences == EOS_ID, 1).astype(np.int32)             # synthesizer.py:120
         speaker = self._speaker_feed(speaker_ids, len(sequences))
@@ -192,17 +199,20 @@ class Synthesizer(object):
             frames = self._attention_trim_device(alignments, [len(seq) for seq in sequences])
         if vocoder == "tensorflow":
             gl = self._griffin_lim_tf()
-            wav, num_samples = gl.inv_spectrogram_tensorflow(linear, frames, iters=iters)
+            wav, num_samples = gl.inv_spectrogram_tensorflow(linear, frames, iters=iters, momentum=momentum)
         elif vocoder == "mel":
             gl = self._griffin_lim()
             if not gl.inv_mels:
                 gl.set_inv_mel_basis()
             mel = self.model.mel_outputs                       # [N, steps, r * num_mels] or [N, frames, num_mels]: the same memory
             mel = mel.reshape(mel.shape[0], -1, self.hparams.num_mels)
-            wav, num_samples = gl.inv_melspectrogram(mel, frames, seed=seed, iters=iters)
+            wav, num_samples = gl.inv_melspectrogram(mel, frames, seed=seed, iters=iters, momentum=momentum)
+            sc = gl.convergence(gl.mel_to_linear(mel) ** float(gl.hp.power), wav, frames, kind="magnitude") if return_convergence else None
         else:
             gl = self._griffin_lim()
-            wav, num_samples = gl.inv_spectrogram_rows(linear, frames, seed=seed, iters=iters)
+            wav, num_samples = gl.inv_spectrogram_rows(linear, frames, seed=seed, iters=iters, momentum=momentum)
+            sc = gl.convergence(linear, wav, frames) if return_convergence else None
+        self.convergence = sc.cpu().numpy() if return_convergence else None
         index = None
         if librosa_trim and end_of_sentence:
             index = gl.trim(wav, num_samples, **self.LIBROSA_TRIM)

@@ -32,7 +32,16 @@ silence.split_on_silence_pydub and the whole silence.amplify (upload, kernels, t
 energy pass alone (k_pcm_energy through taco_debug_pcm_energy: the only launch that reads the samples) with the bytes of the recording
 over its time, beside a device copy of the same buffer (which reads and writes those bytes); and on the host the restatement tests/pydub_reference.py: its
 fast form on the whole recording and its literal audioop form on the first ten seconds ("literal, 10 s": not extrapolated).  Its own JSON
-line, `--pydub` only."""
+line, `--pydub` only.
+`--momentum` measures Fast Griffin-Lim (GriffinLim.set_momentum) at the C2 output shape on a CONSISTENT spectrogram -- the STFT
+magnitudes of 32 seeded multi-tone signals of 153 300 samples (Spectrogram.targets on the device, re-encoded so that the vocoder's
+magnitudes are exactly those), not noise: momentum 0 and 0.99 at 10, 20, 30 and 60 iterations, five windows of four calls per cell with
+the two settings alternating, and for each cell the mean and the worst spectral convergence of the batch as the device reports it
+(GriffinLim.convergence).  From them: the smallest iteration count at which 0.99 is at or below the plain loop's 60-iteration
+convergence, and its time over the plain loop's 60-iteration call of the same run; the cost of one iteration of either loop (the 60-
+and the 10-iteration medians, their difference over 50); k_gl_project_fast against k_gl_project alone (taco_debug_gl_project on the
+loop's own number of frame rows) with the bytes each moves over its time; and the convergence call alone.  Its own JSON line,
+`--momentum` only."""
 import json, os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "oracle"))
@@ -373,6 +382,98 @@ def pydub():
     return out
 
 
+def multitone(rows=B, n=153300, seed=11):
+    """float32 [rows, n]: per row six tones of seeded frequency (80 Hz - 9 kHz), amplitude, vibrato and slow tremolo"""
+    rs = np.random.RandomState(seed)
+    t = np.arange(n) / float(hp.sample_rate)
+    x = np.zeros((rows, n))
+    for b in range(rows):
+        for _ in range(6):
+            f0, a = np.exp(rs.uniform(np.log(80.0), np.log(9000.0))), rs.uniform(0.005, 0.03)
+            vib, trem = rs.uniform(0.0, 0.01) * f0 / 5.0, rs.uniform(0.2, 3.0)
+            x[b] += a * (0.6 + 0.4 * np.sin(2 * np.pi * trem * t + rs.uniform(0, 6.28))) * np.sin(2 * np.pi * f0 * t + vib * np.sin(2 * np.pi * 5.0 * t) + rs.uniform(0, 6.28))
+    return x.astype(np.float32)
+
+
+def momentum():
+    import ctypes as C
+    ITERS, MOMENTA, WINDOWS, CALLS = (10, 20, 30, 60), (0.0, 0.99), 5, 4
+    sp, gl = taco_amd.Spectrogram(hp), taco_amd.GriffinLim(hp)
+    L = gl.num_samples(T)
+    lin = sp.targets(torch.from_numpy(multitone(B, L)).cuda(), mel=False)[0]                      # normalised 20 log10 |stft(p)| - ref_level_db
+    assert tuple(lin.shape) == (B, T, F)
+    # the vocoder raises the amplitude it decodes to `power`: encode |stft(p)|^(1/power), so that its magnitudes are |stft(p)| itself
+    db = lin * -hp.min_level_db + hp.min_level_db + hp.ref_level_db
+    spec = ((db / hp.power - hp.ref_level_db - hp.min_level_db) / -hp.min_level_db).clamp_(0.0, 1.0).contiguous()
+    sp.close()
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+
+    def window(f, calls):
+        e0.record()
+        for _ in range(calls):
+            out = f()
+        e1.record(); torch.cuda.synchronize()
+        return e0.elapsed_time(e1) / calls, out
+
+    cells = [(it, m) for it in ITERS for m in MOMENTA]
+    for it, m in cells:                                       # warm: both workspace sizes, every launch shape
+        gl.inv_spectrogram(spec, iters=it, momentum=m)
+    torch.cuda.synchronize()
+    ms, sc = {c: [] for c in cells}, {}
+    for _ in range(WINDOWS):
+        for it, m in cells:                                   # the two settings alternate at every iteration count
+            t, wav = window(lambda: gl.inv_spectrogram(spec, iters=it, momentum=m), CALLS)
+            ms[(it, m)].append(t)
+            sc[(it, m)] = gl.convergence(spec, wav).cpu().numpy()
+    wav = gl.inv_spectrogram(spec, iters=60, momentum=0.99)
+    same = bool(torch.equal(wav, gl.inv_spectrogram(spec, iters=60, momentum=0.99)))
+    conv_ms = [window(lambda: gl.convergence(spec, wav), 20)[0] for _ in range(WINDOWS)]
+    med = {c: float(np.median(v)) for c, v in ms.items()}
+    mean = {c: float(v.mean()) for c, v in sc.items()}
+    reach = [it for it in ITERS if mean[(it, 0.99)] <= mean[(60, 0.0)]]
+    per_it = {m: (med[(60, m)] - med[(10, m)]) / 50.0 for m in MOMENTA}
+    # the projection kernels alone, on the loop's own frame rows
+    n_fft, hop = (F - 1) * 2, int(hp.frame_shift_ms / 1000 * hp.sample_rate)
+    R = B * (T + -(-n_fft // hop))
+    g = torch.Generator(device="cuda"); g.manual_seed(3)
+    est, prev = (torch.randn((R, 2 * F), device="cuda", generator=g) for _ in range(2))
+    S, X = torch.rand((R, F), device="cuda", generator=g), torch.empty((R, 2 * F), device="cuda")
+    p = lambda t: C.c_void_p(None if t is None else t.data_ptr())
+    proj = lambda pv: taco_amd._lib.check(gl._lib.taco_debug_gl_project(gl._h, C.c_void_p(torch.cuda.current_stream().cuda_stream), p(est), p(pv), p(S), p(X),
+                                                                        C.c_float(0.99 / 1.99), R))
+    kern = {"k_gl_project": lambda: proj(None), "k_gl_project_fast": lambda: proj(prev)}
+    for f in kern.values():
+        for _ in range(5):
+            f()
+    torch.cuda.synchronize()
+    kms = {k: [] for k in kern}
+    for _ in range(WINDOWS):
+        for k, f in kern.items():
+            kms[k].append(window(f, 50)[0])
+    kmed = {k: float(np.median(v)) for k, v in kms.items()}
+    kbytes = {"k_gl_project": R * F * 20, "k_gl_project_fast": R * F * 28}
+    key = lambda c: "%d_iters_momentum_%g" % c
+    out = {"metric": "Fast Griffin-Lim at the C2 output shape: time of the smallest iteration count at which momentum 0.99 reaches the plain loop's 60-iteration spectral convergence, over the plain loop's 60-iteration call",
+           "value": med[(reach[0], 0.99)] / med[(60, 0.0)] if reach else None, "unit": "x the plain loop's 60-iteration call",
+           "batch": "B=%d x T=%d frames x %d bins, the STFT magnitudes of seeded six-tone signals (%d samples each)" % (B, T, F, L),
+           "windows": "%d windows of %d calls per cell, momentum 0 and 0.99 alternating; 50 calls per window for a kernel alone, 20 for the convergence call" % (WINDOWS, CALLS),
+           "ms": {key(c): v for c, v in ms.items()}, "median_ms": {key(c): v for c, v in med.items()},
+           "convergence_mean": {key(c): v for c, v in mean.items()}, "convergence_worst": {key(c): float(v.max()) for c, v in sc.items()},
+           "plain_60_iterations_ms": med[(60, 0.0)], "plain_60_iterations_convergence_mean": mean[(60, 0.0)],
+           "smallest_iterations_at_or_below_plain_60": reach[0] if reach else None,
+           "ms_at_that_count": med[(reach[0], 0.99)] if reach else None,
+           "one_iteration_ms": {"momentum_0": per_it[0.0], "momentum_0.99": per_it[0.99]}, "one_iteration_fast_over_plain": per_it[0.99] / per_it[0.0],
+           "same_count_fast_over_plain": {str(it): med[(it, 0.99)] / med[(it, 0.0)] for it in ITERS},
+           "kernel_ms": kms, "kernel_median_ms": kmed, "kernel_bytes": kbytes, "kernel_GBps": {k: kbytes[k] / (kmed[k] / 1e3) / 1e9 for k in kern},
+           "k_gl_project_fast_over_k_gl_project": kmed["k_gl_project_fast"] / kmed["k_gl_project"],
+           "convergence_call_ms": conv_ms, "identical_bits_on_two_calls": same, "finite": bool(torch.isfinite(wav).all())}
+    gl.close()
+    return out
+
+
+if "--momentum" in sys.argv:
+    print(json.dumps(momentum()))
+    sys.exit(0)
 if "--pydub" in sys.argv:
     print(json.dumps(pydub()))
     sys.exit(0)
