@@ -740,6 +740,37 @@ int taco_model_engine_plan(taco_model* m, int B, int T_in, int T_mel, int flags,
  * row tiles of 64 rows).  Takes effect for calls and plans made afterwards. */
 int taco_model_set_batch_invariant(taco_model* m, int on);
 
+/* ---- matching recognised text to script lines (recognition/alignment.py:21-26,107-113) ----
+ * Text is a pool of Unicode code points, d_chars [n_chars] int32, and d_offsets [n_texts + 1]: text t is d_chars[d_offsets[t] ..
+ * d_offsets[t+1]).  The caller strips what the reference's plain_text strips before it packs the pool.
+ *
+ * taco_text_matches: d_matches[p] = M of difflib.SequenceMatcher(None, a, b), a = text d_pairs[2p], b = text d_pairs[2p+1]; the
+ * reference's similarity() is ratio() = 2.0 * M / (len(a) + len(b)), and 1.0 when both are empty, which the caller forms in double.
+ * M is the total length of difflib's matching blocks: the longest common block of a and b, then the same left of it in both strings and
+ * right of it in both.  The tie rule: among the longest blocks the one that starts earliest in a wins, among those the one that starts
+ * earliest in b; M depends on it and the kernel follows it.  Exact equality with difflib holds for len(b) <= 199: from len(b) = 200 on
+ * difflib's autojunk drops the characters of b that occur more than 1 + len(b)/100 times from its index and finds other blocks, so such
+ * a pair is REFUSED, not approximated.  len(a) has no cap.
+ * The -1 convention: a refused pair gets d_matches[p] = -1 and nothing else changes; the stream stays sound.  Refused are: len(b) >= 200;
+ * a text index outside [0, n_texts); offsets of either text that decrease or run outside [0, n_chars].  Score those on the host.
+ *
+ * taco_text_best_two: the decision of :107-113 per group g, the pairs [d_group_offsets[g], d_group_offsets[g+1]) of one utterance
+ * (increasing offsets into the pairs; they are trusted, the pair count is not an argument).  d_best[g] = {the pair of the largest ratio
+ * -- the first such pair on equal ratios --, its M, its T = len(a) + len(b), flag}.  flag = 1 when every other pair of the group has a
+ * strictly smaller ratio (the reference's first[1] > second[1]; a group of one pair has flag 1).  Ratios are compared as M1*T2 against
+ * M2*T1 in 64-bit integers, T == 0 counting as ratio 1; that is the order of the doubles 2.0*M/T wherever T1*T2 < 2^52 (beyond, two
+ * different fractions may round to one double).  Refused pairs (-1) are skipped and set the group's flag to 0, so the caller knows to
+ * redo that group on the host.  An empty group, or one whose pairs are all refused, writes {-1, 0, 0, 0}.
+ *
+ * Both calls launch on hip_stream only: no allocation, no synchronisation, no workspace, plain stores, every output element written
+ * exactly once; safe under stream capture.  Checked before any HIP call (TACO_ERR_ARG): a null pointer (d_chars may be null when
+ * n_chars is 0), a negative count, an output that overlaps an input (for taco_text_best_two's d_matches and d_pairs, whose length it
+ * does not know: their first element).  n_pairs or n_groups of 0 is a no-op.  Byte counts are formed in 128 bits. */
+int taco_text_matches(void* hip_stream, const int32_t* d_chars, long long n_chars, const int32_t* d_offsets /* [n_texts + 1] */, int n_texts,
+                      const int32_t* d_pairs /* [n_pairs, 2]: text index of a, of b */, int n_pairs, int32_t* d_matches /* [n_pairs] */);
+int taco_text_best_two(void* hip_stream, const int32_t* d_matches, const int32_t* d_pairs, const int32_t* d_offsets, int n_texts,
+                       const int32_t* d_group_offsets /* [n_groups + 1] into the pairs */, int n_groups, int32_t* d_best /* [n_groups, 4] */);
+
 #ifdef __cplusplus
 }
 #endif

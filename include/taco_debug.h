@@ -193,6 +193,12 @@ int taco_debug_segnorm_plan_create_host(const uint64_t* h_offsets, int n_seg, co
  * yardstick that tools/bench_train.py --grad-stats holds taco_train_grad_norms against -- both read the same bytes once. */
 int taco_debug_sumsq_partial(void* hip_stream, const float* d_grads, size_t n, void* d_workspace, size_t workspace_bytes);
 
+/* Timing hook: taco_text_matches with the kernel instantiation chosen by the caller.  cols = 0: as taco_text_matches does, one column per lane for
+ * len(b) <= 64 and four above; cols = 4: the four-column kernel for every length -- what tools/bench_align.py holds the one-column form against.
+ * Arguments, results and errors are taco_text_matches's; another cols is TACO_ERR_ARG. */
+int taco_debug_text_matches_cols(void* hip_stream, const int32_t* d_chars, long long n_chars, const int32_t* d_offsets, int n_texts,
+                                 const int32_t* d_pairs, int n_pairs, int32_t* d_matches, int cols);
+
 #ifdef __cplusplus
 }
 #endif

@@ -234,6 +234,9 @@ PROTOTYPES = {
     "taco_model_engine_plan": (_I, [_P, _I, _I, _I, _I, C.c_char_p, _I]),
     "taco_model_set_batch_invariant": (_I, [_P, _I]),
     "taco_debug_decoder_trace": (_I, [_P, _I, C.POINTER(C.c_longlong)]),
+    "taco_text_matches": (_I, [_P, _P, C.c_longlong, _P, _I, _P, _I, _P]),
+    "taco_text_best_two": (_I, [_P, _P, _P, _P, _I, _P, _I, _P]),
+    "taco_debug_text_matches_cols": (_I, [_P, _P, C.c_longlong, _P, _I, _P, _I, _P, _I]),
 }
 
 _lib = None

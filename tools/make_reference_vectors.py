@@ -14,10 +14,14 @@
   * synthesizer.py:171-200   the manual alignments Synthesizer.synthesize builds for its second pass (manual_attention_mode 1 and 3), observed
     through the feed of that pass (a recording stand-in for the session).
   * hparams.py (every effective default after its override chain) and utils/__init__.py:110-126 load_hparams.
+  * recognition/alignment.py:93-136   align_text_fn on the utterances of two scripts of datasets/moon (tests/golden/align_moon holds those
+    inputs), with similarity / search_optimal / plain_text on their own; the utterances that reach text_to_sequence (jamo) are listed, not recorded.
 
 Run in the BUILD container only (it reads /root/reference; the GPU box has no reference):
 
-    python tools/make_reference_vectors.py            # writes tests/golden/korean_vectors.json, feeder_vectors.npz, audio_vectors.npz, trim_vectors.npz, manual_vectors.npz, hparams_vectors.json
+    python tools/make_reference_vectors.py            # writes tests/golden/korean_vectors.json, feeder_vectors.npz, audio_vectors.npz, trim_vectors.npz, manual_vectors.npz, hparams_vectors.json,
+                                                      # alignment_vectors.json and align_moon/
+    python tools/make_reference_vectors.py alignment  # only the last two
 
 The reference modules are loaded BY PATH from where they lie; nothing of their source is copied.  Their import lines name packages
 this image lacks (`jamo`, `tensorflow`, `nltk`, the reference's own `audio` / `utils` / `text` packages, which pull in TensorFlow and
@@ -247,6 +251,70 @@ def manual_vectors():
     return {"first_pass": fp, "mode1": m1, "mode3": m3, "dims": np.array([c[0].shape for c in cases], np.int64),
             "tokens": tok, "input_lengths": np.asarray(feeds[0]["input_lengths"], np.int64), "speaker_id_fed": np.asarray(feeds[0]["speaker_id"], np.int64),
             "manual_alignments_fed_when_off": np.asarray(feeds[0]["manual_alignments"], np.float64)}
+
+
+ALIGN_SCRIPTS = ("005", "006")          # datasets/moon/assets/005.txt (17 utterances) and 006.txt (293)
+
+
+def load_reference_alignment():
+    """recognition/alignment.py by path.  Real: the reference's `utils` (remove_postfix) and its `text` package (remove_puncuations;
+    text_to_sequence up to the jamo decomposition) with the reference's own hparams.  Stand-ins that refuse to be called: `jamo`,
+    `inflect`, audio.get_duration.  text_to_sequence is reached only on the branch of align_text_fn where search_optimal finds nothing
+    (:126); an item that gets there cannot be recorded and is listed as such."""
+    load_reference_audio()                                   # the reference's real `hparams`; tf stand-in
+    j = _stub("jamo", hangul_to_jamo=_refuse("jamo.hangul_to_jamo"), h2j=_refuse("jamo.h2j"), j2h=_refuse("jamo.j2h"))
+    j.__path__ = []
+    _stub("jamo.jamo", _jamo_char_to_hcj=_refuse("jamo._jamo_char_to_hcj"))
+    _stub("inflect", engine=_refuse("inflect.engine"))
+    a = _stub("audio")
+    a.__path__ = []
+    _stub("audio.get_duration", get_durations=_refuse("audio.get_durations"))
+    for name, sub in (("utils", "utils"), ("text", "text")):
+        for k in [k for k in sys.modules if k == name or k.startswith(name + ".")]:
+            del sys.modules[k]
+        spec = importlib.util.spec_from_file_location(name, os.path.join(REF, sub, "__init__.py"), submodule_search_locations=[os.path.join(REF, sub)])
+        m = importlib.util.module_from_spec(spec); sys.modules[name] = m; spec.loader.exec_module(m)
+    spec = importlib.util.spec_from_file_location("refalignment", os.path.join(REF, "recognition", "alignment.py"))
+    A = importlib.util.module_from_spec(spec); spec.loader.exec_module(A)
+    return A
+
+
+def alignment_vectors():
+    """recognition/alignment.py:93-136 align_text_fn on every utterance of two scripts of datasets/moon, score_threshold 0.4 (its default),
+    run from the reference's root as its relative paths need.  Stored: the inputs (the script lines as the files hold them, the
+    recognition.json entries) and the outputs, plus similarity / search_optimal / plain_text on their own for a sample.  Returns
+    (vectors, {script: text of the asset file}, {audio path: recognised text})."""
+    A = load_reference_alignment()
+    with open(os.path.join(REF, "datasets", "moon", "recognition.json"), encoding="utf-8") as f:
+        rec = json.load(f)
+    rec = collections.OrderedDict((k, v) for k, v in rec.items() if any("/audio/%s." % s in k for s in ALIGN_SCRIPTS))
+    scripts = {}
+    for s in ALIGN_SCRIPTS:
+        with open(os.path.join(REF, "datasets", "moon", "assets", s + ".txt"), encoding="utf-8") as f:
+            scripts[s] = f.read()
+    out = {"generated_by": "tools/make_reference_vectors.py: recognition/alignment.py loaded by path; jamo / inflect stand-ins never called",
+           "score_threshold": 0.4, "results": {}, "unrecorded": [], "similarity": [], "search_optimal": [], "plain_text": []}
+    cwd = os.getcwd()
+    os.chdir(REF)
+    try:
+        for path, text in rec.items():
+            try:
+                out["results"].update(A.align_text_fn((path, text), 0.4))
+            except RuntimeError as e:                        # a stand-in was reached (text_to_sequence -> jamo): not recorded
+                out["unrecorded"].append({"path": path, "why": str(e)})
+        items = list(rec.items())
+        for s in ALIGN_SCRIPTS:
+            lines = [ln.strip().replace('"', "").replace("'", "") for ln in scripts[s].splitlines()]
+            mine = [(p, t) for p, t in items if "/audio/%s." % s in p]
+            for p, t in mine[:24]:
+                for ln in lines[:: max(1, len(lines) // 12)]:
+                    out["similarity"].append([ln, t, A.similarity(ln, t)])
+                    out["plain_text"].append([ln, A.plain_text(ln)])
+                best = max(lines, key=lambda ln: A.similarity(ln, t))
+                out["search_optimal"].append([best, t, A.search_optimal(best, t)])
+    finally:
+        os.chdir(cwd)
+    return out, scripts, rec
 
 
 def hparams_vectors():
@@ -570,6 +638,28 @@ def main():
     if not os.path.isdir(REF):
         sys.exit("no reference checkout at %s (this script runs in the build container only)" % REF)
     os.makedirs(GOLD, exist_ok=True)
+    if sys.argv[1:] != ["alignment"]:
+        other_vectors()
+    write_alignment_vectors()
+
+
+def write_alignment_vectors():
+    av, scripts, rec = alignment_vectors()
+    d = os.path.join(GOLD, "align_moon")
+    os.makedirs(os.path.join(d, "assets"), exist_ok=True)
+    for s, text in scripts.items():
+        with open(os.path.join(d, "assets", s + ".txt"), "w", encoding="utf-8") as f:
+            f.write(text)
+    with open(os.path.join(d, "recognition.json"), "w", encoding="utf-8") as f:
+        json.dump(rec, f, ensure_ascii=False, indent=0)
+    with open(os.path.join(GOLD, "alignment_vectors.json"), "w", encoding="utf-8") as f:
+        json.dump(av, f, ensure_ascii=False, indent=0, sort_keys=True)
+    kinds = collections.Counter("str" if isinstance(v, str) else len(v) for v in av["results"].values())
+    print("alignment: %d utterances of scripts %s recorded (%s), %d not recordable; %d similarity, %d search_optimal cases"
+          % (len(av["results"]), "/".join(ALIGN_SCRIPTS), dict(kinds), len(av["unrecorded"]), len(av["similarity"]), len(av["search_optimal"])))
+
+
+def other_vectors():
     K = load_reference_korean()
     kv = korean_vectors(K)
     with open(os.path.join(GOLD, "korean_vectors.json"), "w", encoding="utf-8") as f:
