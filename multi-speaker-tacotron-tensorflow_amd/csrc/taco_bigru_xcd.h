@@ -1,12 +1,12 @@
 // taco_bigru_xcd.h -- the BiGRU scan of a CBHG (modules.py:82-96: bidirectional_dynamic_rnn over two GRUCell(H))
-// at H = 256 (the post-net) as ONE persistent launch on the exchange machinery of taco_decoder_xcd.h, forward and backward.
+// at H = 256 (the post-net) as ONE persistent launch on the exchange machinery of taco_xchg.h, forward and backward.
 //
 // The input projection is hoisted (one GEMM over all frames, taco_lib.hip); what is sequential is, per direction and batch row,
 // T steps of  r,u = sigmoid(xg + h Wg_h);  c = tanh(xc + (r*h) Wc_h);  h' = u*h + (1-u)*c  -- 196 K MACs and two dependent
 // mat-vecs per step.  k_bigru_resw (taco_kernels.h) gives every (direction, row) chain one CU and keeps 2/3 of the recurrent
 // weights on it: 3.74 us per step on 64 of the 256 CUs.  The kernels here spread the chains over the whole chip instead: every
 // lane keeps its slice of the recurrent weight columns in VGPRs for the whole scan (nothing is re-read), and per direction-step
-// two exchanges go through the XCD's L2 (8-byte {value, tag} granules, see taco_decoder_xcd.h): r*h after the gates, h' after the
+// two exchanges go through the XCD's L2 (8-byte {value, tag} granules, see taco_xchg.h): r*h after the gates, h' after the
 // candidate.  The x-parts come from HBM / the Infinity Cache: a member's slice of them is fetched GX_BLK steps at a time, one block
 // ahead, STRAIGHT INTO an LDS ring (global_load_lds_dwordx4: no VGPR is involved, so nothing can be demoted to scratch and nothing
 // is waited for where the load is issued).
@@ -17,7 +17,8 @@
 // commit 7a862c2, its measurements in profiles/HISTORY.md.
 // Length masking and the reverse_sequence time mapping of the backward direction follow A.7 exactly as k_bigru_resw does.
 #pragma once
-#include "taco_decoder_xcd.h"
+#include "taco_xchg.h"             // the exchange (DxRt, dx_publish_n, dx_poll, dx_gather, XgPoll / xg_*), dx_census, dx_pass, dx_reduce, DX_GROUP / DX_NGROUP
+#include "taco_decoder_xcd.h"      // dx_sigmoid_fast; taco_kernels.h through it: taco_f32x2, taco_tanh_fast
 
 #define GX_H 256
 #define GX_BLK 16            // steps per block of prefetched x-parts
@@ -55,49 +56,6 @@ __device__ __forceinline__ void gx_load_lds16(const float* gsrc, unsigned lds_ds
 __host__ __device__ inline size_t gd_ring_floats(int RG) { return (size_t)2 * 2 * GX_BLK * RG * 24; }      // [slot][dir][step][row][gate][8 units]
 __host__ __device__ inline size_t gd_lds_floats(int RG) { return gd_ring_floats(RG) + (size_t)4 * RG * GX_H + 64; }
 __host__ __device__ constexpr size_t gd_xbuf_granules(int RG) { return (size_t)DX_NGROUP * 4 * RG * GX_H; }  // groups x [dir][r*h | h'] x RG x H
-
-// the loads of a gather, requested now and examined later (dx_gather split in two)
-template <int RG, int NT>
-struct GdPoll {
-  static constexpr int NI = (RG * GX_H + NT - 1) / NT;
-  unsigned long long g[NI];
-};
-template <int RG, int NT>
-__device__ __forceinline__ void gd_request(const dx_gu64* X, int tid, GdPoll<RG, NT>& p) {
-  constexpr int NI = GdPoll<RG, NT>::NI;
-  if ((RG * GX_H >= NT) || tid < RG * GX_H) {
-#pragma unroll
-    for (int u = 0; u < NI; ++u) p.g[u] = __hip_atomic_load(X + tid + u * NT, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  }
-}
-// Makes the requested granules "used" at this point of the program: hipcc places the wait for the loads HERE.  Called right before a
-// phase publishes, so that the wait sees only the loads (requested a whole compute phase ago: landed) and not the publish stores
-// issued after them -- vmcnt counts in issue order, and a wait behind the stores would also wait for their acknowledgement.
-// `after` ties the statement to a value of the phase's epilogue, so that the scheduler cannot hoist it (and the wait) above the
-// phase's arithmetic.
-template <int RG, int NT>
-__device__ __forceinline__ void gd_landed(GdPoll<RG, NT>& p, float& after) {
-#pragma unroll
-  for (int u = 0; u < GdPoll<RG, NT>::NI; ++u) asm volatile("" : "+v"(p.g[u]), "+v"(after));
-}
-template <int RG, int NT>
-__device__ __forceinline__ void gd_collect(const dx_gu64* X, unsigned tag, float* st, int tid, GdPoll<RG, NT>& p, DxRt& rt) {
-  constexpr int NI = GdPoll<RG, NT>::NI;
-  if ((RG * GX_H >= NT) || tid < RG * GX_H) {
-    bool ok = true;
-#pragma unroll
-    for (int u = 0; u < NI; ++u) ok = ok && ((unsigned)(p.g[u] >> 32) == tag);
-    float v[NI];
-    if (ok) {
-#pragma unroll
-      for (int u = 0; u < NI; ++u) v[u] = __uint_as_float((unsigned)p.g[u]);
-    } else {
-      dx_poll<NI>(X + tid, NT, tag, v, rt);       // a producer was late: the ordinary bounded poll
-    }
-#pragma unroll
-    for (int u = 0; u < NI; ++u) st[u * NT + tid] = v[u];      // [RG][H] row-major == granule order
-  }
-}
 
 struct GdArgs {
   const float* wpack;                         // [2 dirs][32 members][GD_NREG / 2][512]
@@ -179,9 +137,9 @@ __device__ __forceinline__ void gd_body(const GdArgs& a, float* gx_smem, int gro
 
   // per-direction registers that live from the gates phase to the candidate phase of a step
   float x0[2][RL][3], hv[2][RL], gv[2][RL];
-  GdPoll<RG, NT> pre;       // the gather whose loads are in flight across the current compute phase
+  XgPoll<RG * H, NT> pre;       // the gather whose loads are in flight across the current compute phase
 #pragma unroll
-  for (int u = 0; u < GdPoll<RG, NT>::NI; ++u) pre.g[u] = 0ull;
+  for (int u = 0; u < XgPoll<RG * H, NT>::NI; ++u) pre.g[u] = 0ull;
 
   const int tid_outer = tid, lane_outer = lane;
   for (int s = 0; s < T; ++s) {
@@ -216,7 +174,7 @@ __device__ __forceinline__ void gd_body(const GdArgs& a, float* gx_smem, int gro
           gs[0] = rr; gs[H] = gv[D][q];
         }
       }
-      gd_landed<RG, NT>(pre, rh[RL - 1][0]);
+      xg_landed<RG * H, NT>(pre, rh[RL - 1][0]);
       if (epl) {
 #pragma unroll
         for (int q = 0; q < RL; ++q) dx_publish_n<1, WTC>(X + (size_t)D * 2 * RG * H + erow[q] * H + u0, 1, rh[q], tag, rt);
@@ -239,7 +197,7 @@ __device__ __forceinline__ void gd_body(const GdArgs& a, float* gx_smem, int gro
         nv[q][0] = active[q] ? blend : hv[D][q];
         if (TAPE && evalid[q] && active[q]) a.gsave[((size_t)(row0 + erow[q]) * T + (D ? eL[q] - 1 - s : s)) * 6 * H + D * 3 * H + 2 * H + u0] = cc;
       }
-      gd_landed<RG, NT>(pre, nv[RL - 1][0]);
+      xg_landed<RG * H, NT>(pre, nv[RL - 1][0]);
       if (epl) {
 #pragma unroll
         for (int q = 0; q < RL; ++q) dx_publish_n<1, WTC>(X + (size_t)(D * 2 + 1) * RG * H + erow[q] * H + u0, 1, nv[q], tag, rt);
@@ -258,29 +216,29 @@ __device__ __forceinline__ void gd_body(const GdArgs& a, float* gx_smem, int gro
     // (the loads for h'(B) of the previous step were requested at the end of that step)
     gates(F{});
     GDT_STAMP(1);
-    if (s > 0) gd_collect<RG, NT>(X_hB, tag - 1u, hs + RG * H, tid, pre, rt);
+    if (s > 0) xg_collect<RG * H, NT>(X_hB, tag - 1u, hs + RG * H, tid, pre, rt);
     __syncthreads();
     GDT_STAMP(2);
-    gd_request<RG, NT>(X_rhF, tid, pre);
+    xg_request<RG * H, NT>(X_rhF, tid, pre);
     gates(Bk{});
     GDT_STAMP(3);
-    gd_collect<RG, NT>(X_rhF, tag, xs, tid, pre, rt);
+    xg_collect<RG * H, NT>(X_rhF, tag, xs, tid, pre, rt);
     __syncthreads();
     GDT_STAMP(4);
-    gd_request<RG, NT>(X_rhB, tid, pre);
+    xg_request<RG * H, NT>(X_rhB, tid, pre);
     cand(F{});
     GDT_STAMP(5);
-    gd_collect<RG, NT>(X_rhB, tag, xs + RG * H, tid, pre, rt);
+    xg_collect<RG * H, NT>(X_rhB, tag, xs + RG * H, tid, pre, rt);
     __syncthreads();
     GDT_STAMP(6);
-    gd_request<RG, NT>(X_hF, tid, pre);
+    xg_request<RG * H, NT>(X_hF, tid, pre);
     cand(Bk{});
     GDT_STAMP(7);
-    gd_collect<RG, NT>(X_hF, tag, hs, tid, pre, rt);
+    xg_collect<RG * H, NT>(X_hF, tag, hs, tid, pre, rt);
     if (sb == GX_BLK - 1) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");     // this wave's part of the next ring slot has landed
     __syncthreads();
     GDT_STAMP(8);
-    gd_request<RG, NT>(X_hB, tid, pre);
+    xg_request<RG * H, NT>(X_hB, tid, pre);
   }
 }
 
@@ -361,28 +319,22 @@ __device__ __forceinline__ void go_reduce(const float (&v)[UPW * NG], float (&ou
 // TRACE: shader-clock stamps of row 0 / member 0 (tools/trace_bigru.py); the production instantiation has none of their branches.
 #define GO_STAMP(slot)                                                                                            \
   do {                                                                                                            \
-    if constexpr (TRACE || GO_DYN) { if (tracer && s >= 8 && s < 8 + DX_TRACE_STEPS) a.trace[(s - 8) * DX_TRACE_SLOTS + (slot)] = (long long)__builtin_readcyclecounter(); } \
+    if constexpr (TRACE) { if (tracer && s >= 8 && s < 8 + DX_TRACE_STEPS) a.trace[(s - 8) * DX_TRACE_SLOTS + (slot)] = (long long)__builtin_readcyclecounter(); } \
   } while (0)
-#ifndef GO_REQ2
-#define GO_REQ2 1          // A/B (tools/scratch): 0 = no second, mid-phase request
-#endif
+// The second, mid-phase request of go_body (pre2): 838 against 885 us per C2 scan without it (profiles/r05_scan_variants.txt).
 // (Round 6, measured at C2 on top of the two requests, post-net alone 1.155 ms: without the second request 1.203; a sleep of 2 / 4 units in front of the fallback
 // poll 1.171-1.191 / 1.219-1.225 -- so about one collect in four does fall through to the poll; a THIRD request behind the phase's reduction, checked
 // only by the lanes whose first two answers were stale, 1.243-1.263: the load in front of the publish store delays the store.  Left as it is.)
-#ifndef GO_DYN
-#define GO_DYN 0           // A/B: 1 = the protocol test of every publish and the tracer test of every stamp at run time, as in k_bigru_duo / k_decoder_xcd
-#endif
+// The protocol of every publish and the tracer of every stamp are template parameters of go_body: tested at run time, as in k_bigru_duo / k_decoder_xcd,
+// the 13 sites of a step cost 838 -> 931 us per C2 scan (profiles/r05_scan_variants.txt).
 // A/B build -DGO_KNOB_RT (tools/sweep_go_knobs.py): per phase (gates F, gates B, cand F, cand B) the place of the second request (0: behind the
 // products -- the production code --, 1: behind the reduction, 2: none), a sleep in front of the first request, a sleep in front of the
 // fallback poll of the collect behind the phase; from a constant table the host fills from TACO_GO_KNOB before each launch.
 // tools/sweep_go_knobs.py on that build (profiles/r06_sweep_go_knobs.txt, op-level call at the C2 post-net shape): every sleep loses (64 clocks in
 // front of a request cost 8-16 us per call), the second request belongs behind the products where it is -- except in the gates B phase, where
 // NONE is better (937 -> 929 us per call, both passes): the r*h(F) vector it asks for was published a whole phase + barrier earlier and the
-// first request already has it.  GO_KNOB_TUNED = 0: the second request in all four phases, as rounds 5-6.
-#ifndef GO_KNOB_TUNED
-#define GO_KNOB_TUNED 1
-#endif
-__host__ __device__ constexpr int go_knob_default(int i) { return (GO_KNOB_TUNED && i == 1) ? 2 : 0; }
+// first request already has it.
+__host__ __device__ constexpr int go_knob_default(int i) { return i == 1 ? 2 : 0; }
 #ifdef GO_KNOB_RT
 __constant__ int g_go_knob[16];
 #define GO_KNOB(i) kn[i]
@@ -425,7 +377,7 @@ __device__ __forceinline__ void go_body(const GdArgs& a, float* gx_smem, int pla
   for (int q = 0; q < 12; ++q) kn[q] = __builtin_amdgcn_readfirstlane(g_go_knob[q]);
 #endif
   const int L = __builtin_amdgcn_readfirstlane(a.lengths ? a.lengths[row] : T);
-  const bool tracer = (TRACE || GO_DYN) && a.trace && row == 0 && member == 0 && tid == 0;
+  const bool tracer = TRACE && a.trace && row == 0 && member == 0 && tid == 0;
 
   float W[NREG];
 #pragma unroll
@@ -522,18 +474,18 @@ __device__ __forceinline__ void go_body(const GdArgs& a, float* gx_smem, int pla
       for (int i = 0; i < UPW; ++i) acc[i] = __builtin_elementwise_fma((taco_f32x2){hx.z, hx.z}, (taco_f32x2){W[R0 + 8 * i + 2], W[R0 + 8 * i + 6]}, acc[i]);
 #pragma unroll
       for (int i = 0; i < UPW; ++i) acc[i] = __builtin_elementwise_fma((taco_f32x2){hx.w, hx.w}, (taco_f32x2){W[R0 + 8 * i + 3], W[R0 + 8 * i + 7]}, acc[i]);
-      if (GO_REQ2 && Xn && GO_KNOB(D) == 0) request2(Xn, Dn);
+      if (Xn && GO_KNOB(D) == 0) request2(Xn, Dn);
       else if (GO_KNOB(D) == 2) pre2 = 0ull;      // no second request in this phase: the previous phase's answer must not pass for this one (its tag can be the same)
       float v[2 * UPW], sm[2];
 #pragma unroll
       for (int i = 0; i < UPW; ++i) { v[2 * i] = acc[i].x; v[2 * i + 1] = acc[i].y; }
       go_reduce<UPW, 2>(v, sm);
-      if (GO_REQ2 && Xn && GO_KNOB(D) == 1) request2(Xn, Dn);
+      if (Xn && GO_KNOB(D) == 1) request2(Xn, Dn);
       const float rr = dx_sigmoid_fast(sm[0] + x0[D][0]);
       gv[D] = dx_sigmoid_fast(sm[1] + x0[D][1]);
       float rh = rr * hv[D];
-      asm volatile("" : "+v"(pre), "+v"(pre2), "+v"(rh));      // the gather in flight has landed: wait for it HERE, ahead of the publish store (see gd_landed)
-      if (pub) { if (GO_DYN) dx_publish(X + (size_t)D * 2 * H + unit, rh, tag, rt); else go_publish<WT>(X + (size_t)D * 2 * H + unit, rh, tag); }
+      asm volatile("" : "+v"(pre), "+v"(pre2), "+v"(rh));      // the gather in flight has landed: wait for it HERE, ahead of the publish store (see xg_landed)
+      if (pub) go_publish<WT>(X + (size_t)D * 2 * H + unit, rh, tag);
       GO_STAMP(9 + D);                  // the publish store of a gates phase is issued (TRACE: tools/trace_bigru.py)
       if (TAPE && pub && active) {      // gates of the active steps at their true time (modules.py:82-96 / A.7), for the backward scan -- BEHIND the publish: the exchange is the critical path
         float* gs = a.gsave + ((size_t)row * T + (D ? L - 1 - s : s)) * 6 * H + D * 3 * H + unit;
@@ -562,17 +514,17 @@ __device__ __forceinline__ void go_body(const GdArgs& a, float* gx_smem, int pla
         acc = __builtin_elementwise_fma((taco_f32x2){hx.z, hx.w}, (taco_f32x2){W[R0 + 2], W[R0 + 3]}, acc);
         v[0] = acc.x + acc.y;
       }
-      if (GO_REQ2 && Xn && GO_KNOB(2 + D) == 0) request2(Xn, Dn);
+      if (Xn && GO_KNOB(2 + D) == 0) request2(Xn, Dn);
       else if (GO_KNOB(2 + D) == 2) pre2 = 0ull;
       go_reduce<UPW, 1>(v, sm);
-      if (GO_REQ2 && Xn && GO_KNOB(2 + D) == 1) request2(Xn, Dn);
+      if (Xn && GO_KNOB(2 + D) == 1) request2(Xn, Dn);
       const float cc = taco_tanh_fast(sm[0] + x0[D][2]);
       float blend = gv[D] * hv[D] + (1.f - gv[D]) * cc;
       DX_PIN(blend);
       float nv = active ? blend : hv[D];
       asm volatile("" : "+v"(pre), "+v"(pre2), "+v"(nv));
       if (pub) {
-        if (GO_DYN) dx_publish(X + (size_t)(D * 2 + 1) * H + unit, nv, tag, rt); else go_publish<WT>(X + (size_t)(D * 2 + 1) * H + unit, nv, tag);
+        go_publish<WT>(X + (size_t)(D * 2 + 1) * H + unit, nv, tag);
         const int t = (D && active) ? (L - 1 - s) : s;
         a.out[((size_t)row * T + t) * 2 * H + D * H + unit] = active ? nv : 0.f;
         if (TAPE && active) a.gsave[((size_t)row * T + t) * 6 * H + D * 3 * H + 2 * H + unit] = cc;
@@ -656,42 +608,6 @@ __host__ __device__ inline size_t gb_ring_floats(int RG) { return (size_t)2 * 2 
 __host__ __device__ inline size_t gb_lds_floats(int RG) { return gb_ring_floats(RG) + (size_t)2 * RG * GX_H + (size_t)2 * RG * 2 * GX_H + 64; }
 __host__ __device__ inline size_t gb_xbuf_granules(int RG) { return (size_t)DX_NGROUP * 2 * RG * 3 * GX_H; }     // groups x dir x [d c_pre : H | d gates : 2H] x RG
 
-template <int RG, int W, int NT>
-struct GbPoll {
-  static constexpr int NI = (RG * W + NT - 1) / NT;
-  unsigned long long g[NI];
-};
-template <int RG, int W, int NT>
-__device__ __forceinline__ void gb_request(const dx_gu64* X, int tid, GbPoll<RG, W, NT>& p) {
-  if ((RG * W >= NT) || tid < RG * W) {
-#pragma unroll
-    for (int u = 0; u < GbPoll<RG, W, NT>::NI; ++u) p.g[u] = __hip_atomic_load(X + tid + u * NT, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  }
-}
-template <int RG, int W, int NT>
-__device__ __forceinline__ void gb_landed(GbPoll<RG, W, NT>& p, float& after) {
-#pragma unroll
-  for (int u = 0; u < GbPoll<RG, W, NT>::NI; ++u) asm volatile("" : "+v"(p.g[u]), "+v"(after));
-}
-template <int RG, int W, int NT>
-__device__ __forceinline__ void gb_collect(const dx_gu64* X, unsigned tag, float* st, int tid, GbPoll<RG, W, NT>& p, DxRt& rt) {
-  constexpr int NI = GbPoll<RG, W, NT>::NI;
-  if ((RG * W >= NT) || tid < RG * W) {
-    bool ok = true;
-#pragma unroll
-    for (int u = 0; u < NI; ++u) ok = ok && ((unsigned)(p.g[u] >> 32) == tag);
-    float v[NI];
-    if (ok) {
-#pragma unroll
-      for (int u = 0; u < NI; ++u) v[u] = __uint_as_float((unsigned)p.g[u]);
-    } else {
-      dx_poll<NI>(X + tid, NT, tag, v, rt);
-    }
-#pragma unroll
-    for (int u = 0; u < NI; ++u) st[u * NT + tid] = v[u];
-  }
-}
-
 struct GbArgs {
   const float* wpack;                         // [2 dirs][32 members][12][512]: rows of Wc_h (4) and of Wg_h (4 r-half + 4 u-half) of the wave's unit
   const float* dout; const float* out; const float* gsave;     // [B*T, 2H], [B*T, 2H], [B*T, 6H]
@@ -771,12 +687,12 @@ __device__ __forceinline__ void gb_body(const GbArgs& a, float* gx_smem, int gro
   for (int d = 0; d < 2; ++d)
 #pragma unroll
     for (int q = 0; q < RL; ++q) { keep[d][q] = 0.f; hp[d][q] = 0.f; rg[d][q] = 0.f; dgu[d][q] = 0.f; act[d][q] = false; }
-  GbPoll<RG, H, NT> pre1;            // a d c_pre gather in flight
-  GbPoll<RG, 2 * H, NT> pre2;        // a d gates gather in flight
+  XgPoll<RG * H, NT> pre1;            // a d c_pre gather in flight
+  XgPoll<RG * 2 * H, NT> pre2;        // a d gates gather in flight
 #pragma unroll
-  for (int u = 0; u < GbPoll<RG, H, NT>::NI; ++u) pre1.g[u] = 0ull;
+  for (int u = 0; u < XgPoll<RG * H, NT>::NI; ++u) pre1.g[u] = 0ull;
 #pragma unroll
-  for (int u = 0; u < GbPoll<RG, 2 * H, NT>::NI; ++u) pre2.g[u] = 0ull;
+  for (int u = 0; u < XgPoll<RG * 2 * H, NT>::NI; ++u) pre2.g[u] = 0ull;
 
   const int tid_outer = tid, lane_outer = lane;
   // step index k = T-1-s counts up; tag of the exchanges of step k = k + 1
@@ -833,8 +749,8 @@ __device__ __forceinline__ void gb_body(const GbArgs& a, float* gx_smem, int gro
         }
       }
       if (k < T) {
-        gb_landed<RG, H, NT>(pre1, dcp[RL - 1][0]);        // whichever gather is in flight across this phase has landed by now:
-        gb_landed<RG, 2 * H, NT>(pre2, dcp[RL - 1][0]);    // wait for it HERE, ahead of the publish stores (see gd_landed)
+        xg_landed<RG * H, NT>(pre1, dcp[RL - 1][0]);        // whichever gather is in flight across this phase has landed by now:
+        xg_landed<RG * 2 * H, NT>(pre2, dcp[RL - 1][0]);    // wait for it HERE, ahead of the publish stores (see xg_landed)
         if (epl) {
 #pragma unroll
           for (int q = 0; q < RL; ++q) dx_publish_n<1, WTC>(X + (size_t)D * RG * 3 * H + erow[q] * H + u0, 1, dcp[q], tag, rt);
@@ -861,8 +777,8 @@ __device__ __forceinline__ void gb_body(const GbArgs& a, float* gx_smem, int gro
         }
         gr[q][0] = dgr; gu[q][0] = dgu[D][q];
       }
-      gb_landed<RG, H, NT>(pre1, gr[RL - 1][0]);
-      gb_landed<RG, 2 * H, NT>(pre2, gr[RL - 1][0]);
+      xg_landed<RG * H, NT>(pre1, gr[RL - 1][0]);
+      xg_landed<RG * 2 * H, NT>(pre2, gr[RL - 1][0]);
       if (epl) {
 #pragma unroll
         for (int q = 0; q < RL; ++q) {
@@ -877,23 +793,23 @@ __device__ __forceinline__ void gb_body(const GbArgs& a, float* gx_smem, int gro
     const dx_gu64* Xc1 = X + (size_t)RG * 3 * H;          const dx_gu64* Xg1 = X + (size_t)RG * 3 * H + RG * H;
     // (the gate gradients of F of the previous step were collected at the end of the previous iteration; B's are in flight)
     phase_ca(F{});
-    if (k > 0) gb_collect<RG, 2 * H, NT>(Xg1, tag - 1u, v2 + RG * 2 * H, tid, pre2, rt);
+    if (k > 0) xg_collect<RG * 2 * H, NT>(Xg1, tag - 1u, v2 + RG * 2 * H, tid, pre2, rt);
     __syncthreads();
     if (k == T) { phase_ca(Bk{}); break; }
-    gb_request<RG, H, NT>(Xc0, tid, pre1);
+    xg_request<RG * H, NT>(Xc0, tid, pre1);
     phase_ca(Bk{});
-    gb_collect<RG, H, NT>(Xc0, tag, v1, tid, pre1, rt);
+    xg_collect<RG * H, NT>(Xc0, tag, v1, tid, pre1, rt);
     __syncthreads();
-    gb_request<RG, H, NT>(Xc1, tid, pre1);
+    xg_request<RG * H, NT>(Xc1, tid, pre1);
     phase_b(F{});
-    gb_collect<RG, H, NT>(Xc1, tag, v1 + RG * H, tid, pre1, rt);
+    xg_collect<RG * H, NT>(Xc1, tag, v1 + RG * H, tid, pre1, rt);
     __syncthreads();
-    gb_request<RG, 2 * H, NT>(Xg0, tid, pre2);
+    xg_request<RG * 2 * H, NT>(Xg0, tid, pre2);
     phase_b(Bk{});
-    gb_collect<RG, 2 * H, NT>(Xg0, tag, v2, tid, pre2, rt);
+    xg_collect<RG * 2 * H, NT>(Xg0, tag, v2, tid, pre2, rt);
     if (sb == GX_BLK - 1) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
-    gb_request<RG, 2 * H, NT>(Xg1, tid, pre2);
+    xg_request<RG * 2 * H, NT>(Xg1, tid, pre2);
   }
 }
 
@@ -1055,7 +971,7 @@ __device__ __forceinline__ void gob_body(const GbArgs& a, float* gx_smem, int pl
           keep[D] = g * u;
           hpv[D] = hprev; rgv[D] = r; rhp = r * hprev;
         }
-        asm volatile("" : "+v"(pre), "+v"(pre2), "+v"(dcp));      // the gather in flight has landed: wait for it HERE, ahead of the publish store (see gd_landed)
+        asm volatile("" : "+v"(pre), "+v"(pre2), "+v"(dcp));      // the gather in flight has landed: wait for it HERE, ahead of the publish store (see xg_landed)
         if (pub) {
           go_publish<WT>(X + (size_t)D * 3 * H + unit, dcp, tag);
           if (active) {                                            // (behind the publish: the exchange is the critical path)

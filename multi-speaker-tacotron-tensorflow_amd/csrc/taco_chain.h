@@ -23,27 +23,19 @@
 // Round 5: the same kernel also runs the ENCODER PRENET (taco_lib.hip: run_prenet_chain) -- the embedding rows gathered straight into the planes
 // (ChainArgs.gather), a 256-wide ReLU layer, and the second layer as the chain's last link with a ReLU on its way out (ChainLayer.act) --, and the
 // workgroups of that launch that own no tile clear the words the forward's persistent kernels poll (ChainArgs.ntiles, zp, znw).  The workgroups of
-// an XCD walk every layer's K loop from different starting steps (CH_ROT).
+// an XCD walk every layer's K loop from different starting steps (ChainArgs::krot).
 #pragma once
 #include "taco_kernels.h"
 
 #define CH_MAXL 8
-// Register sets of weight fragments per wave (ch_mma_loop), W = 256 / W = 128.  What bounds the product loops, measured at C2 in round 4
+// Register sets of weight fragments per wave (ch_mma_loop): two, at W = 256 and at W = 128 (deeper rings: profiles/r05_ab_runs.txt, call L, and below).  What bounds the product loops, measured at C2 in round 4
 // (tools/trace_chain.py on ablated builds): a k16 step of a highway layer takes ~1040 ticks for ~650 of matrix work.  Rings 2, 3, 4, 5 deep,
 // the activation fragments requested a step ahead of their MFMAs, four or eight independent accumulator chains per cluster: no change.
 // Every step re-reading the FIRST step's weight fragments (L1 hits, same instruction stream): 16.2 K -> 10.5 K ticks per layer.  So the loops
 // are bound by the stream of weight fragments out of L2: 32 CUs of an XCD x 32 KB per step = 1 MB per step through an L2 that returns ~1 KB
 // per clock -- bandwidth, not latency.  Rows per workgroup set that ratio (every workgroup streams all 3.6 MB of the stage's weights): 128-row
 // tiles would halve the stream but leave half the CUs idle at M = 16384 and double the matrix time per CU, which is the larger term.
-#ifndef CH_PF256
-#define CH_PF256 2
-#endif
-#ifndef CH_PF128
-#define CH_PF128 2
-#endif
-#ifndef CH_ROT
-#define CH_ROT 1
-#endif
+constexpr int CH_PF = 2;
 #define CH_BM 64
 constexpr int CH_RIDERS = 4;       // regions a launch's spare workgroups clear (ChainArgs::zp / znw): the words a forward's persistent kernels poll (forward_pass lists them)
 enum { CH_DENSE = 0, CH_HIGHWAY = 1, CH_XPROJ = 2 };
@@ -72,7 +64,7 @@ struct ChainArgs {
   float* y; int ldy;               // optional: the last highway output [M, W] (null: not stored)
   const int* rev_len; int rev_col0;
   int M, T, nlayers;
-  int krot;                        // 1: workgroups start their K loops at different steps (CH_ROT, the default); 0: every tile walks K from step 0
+  int krot;                        // 1: workgroups start their K loops at different steps (the default; 133.6 -> 130.6 and 60.9 -> 58.9 us at C2, profiles/r05_ab_runs.txt, call J); 0: every tile walks K from step 0
   // riders: with ntiles > 0 the workgroups ntiles .. gridDim.x - 1 own no tile; they clear up to CH_RIDERS regions of 32-bit words (the words the
   // persistent kernels of the same forward poll: a launch of its own otherwise -- the encoder prenet's chain leaves three quarters of the CUs free)
   int ntiles; unsigned* zp[CH_RIDERS]; unsigned long long znw[CH_RIDERS];
@@ -81,21 +73,20 @@ struct ChainArgs {
 
 // One product loop of a wave: a layer's K for its TM row tiles and one 32-column tile nt of the pack (bhA, blA); dual: a second product that
 // shares the A fragments -- the T matrix of a highway layer at the same column tile, or column tile nt2 of the same matrix.  rot: the
-// workgroup's first k16 step (CH_ROT): the CUs of an XCD walk the layer's K in the same order but from different starts, so that at any moment
+// workgroup's first k16 step: the CUs of an XCD walk the layer's K in the same order but from different starts, so that at any moment
 // they ask the L2 for DIFFERENT 8 KB slices of the pack instead of all 32 for the same one
 struct ChProd {
   const unsigned short* bhA; const unsigned short* blA; const unsigned short* bhB; const unsigned short* blB;
   int K16, NT, nt, nt2, rot; bool dual;
 };
 // the register sets of weight fragments (hi, lo; h2, l2: the second product's) that a product loop rotates through
-template <int CH_PF> struct ChFrag { uint4 h[CH_PF], l[CH_PF], h2[CH_PF], l2[CH_PF]; };
+struct ChFrag { uint4 h[CH_PF], l[CH_PF], h2[CH_PF], l2[CH_PF]; };
 __device__ __forceinline__ int ch_kstep(const ChProd& p, int g) { const int gg = min(g, p.K16 - 1) + p.rot; return gg >= p.K16 ? gg - p.K16 : gg; }
 __device__ __forceinline__ size_t ch_boff(const ChProd& p, int g, int t, int l31, int lh) { return ((((size_t)ch_kstep(p, g) * p.NT + t) * 2 + lh) * 32 + l31) * 8; }
 // The loads a product loop needs before its first MFMA -- steps 0 .. CH_PF - 1 into sets 0 .. CH_PF - 1 -- as a call of their own: the
 // product (ChProd) depends on the layer alone, not on the activations, so the kernel asks for them BEFORE the epilogue and the barrier of
 // the seam in front of the loop, and the L2 round trip runs under the seam instead of behind it.  ch_mma_loop takes the sets as loaded here.
-template <int CH_PF>
-__device__ __forceinline__ void ch_request(const ChProd& p, int l31, int lh, ChFrag<CH_PF>& fr) {
+__device__ __forceinline__ void ch_request(const ChProd& p, int l31, int lh, ChFrag& fr) {
 #pragma unroll
   for (int i = 0; i < CH_PF; ++i) {
     const size_t o = ch_boff(p, i, p.nt, l31, lh);
@@ -106,8 +97,8 @@ __device__ __forceinline__ void ch_request(const ChProd& p, int l31, int lh, ChF
 }
 // the loop itself (DUAL == p.dual): weight fragments one k16 step ahead in two register sets that swap roles (K16 is even: pack_bf3 pads K to
 // a multiple of 32); fr holds steps 0 .. CH_PF - 1 on entry (ch_request)
-template <int TM, int LDSW, bool DUAL, int CH_PF>
-__device__ __forceinline__ void ch_mma_loop(const ChProd& p, ChFrag<CH_PF>& fr, const unsigned short* xhi, const unsigned short* xlo, int row0,
+template <int TM, int LDSW, bool DUAL>
+__device__ __forceinline__ void ch_mma_loop(const ChProd& p, ChFrag& fr, const unsigned short* xhi, const unsigned short* xlo, int row0,
                                             int l31, int lh, f32x16 (&acc)[TM], f32x16 (&acc2)[TM]) {
   const int K16 = p.K16;
   auto kstep = [&](int g) { return ch_kstep(p, g); };
@@ -141,7 +132,6 @@ __device__ __forceinline__ void ch_mma_loop(const ChProd& p, ChFrag<CH_PF>& fr, 
       for (int tm = 0; tm < TM; ++tm) acc2[tm] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[tm], bh2, acc2[tm], 0, 0, 0);
     }
   };
-  if constexpr (CH_PF == 2) {
   // steps 0 and 1 are in the sets already: the first round asks for step 2 only
   __builtin_amdgcn_sched_barrier(0);
   mma(0, fr.h[0], fr.l[0], fr.h2[0], fr.l2[0]);
@@ -159,21 +149,6 @@ __device__ __forceinline__ void ch_mma_loop(const ChProd& p, ChFrag<CH_PF>& fr, 
     __builtin_amdgcn_sched_barrier(0);
     mma(g + 1, fr.h[1], fr.l[1], fr.h2[1], fr.l2[1]);
     __builtin_amdgcn_sched_barrier(0);
-  }
-  } else {
-  // a ring of CH_PF register sets: the fragments of step g + CH_PF - 1 are requested before step g is multiplied.  One step ahead
-  // (round 3) left every k16 step waiting for L2: a workgroup had 32 KB in flight, and a CU's share of the L2 stream at that depth
-  // is ~27 GB/s -- a quarter of what it reaches with 8 loads per lane outstanding (MI355X_MICROARCH.md, hand-off payload row)
-  for (int g = 0; g < K16; g += CH_PF) {
-#pragma unroll
-    for (int i = 0; i < CH_PF; ++i) {
-      const int s = (i + CH_PF - 1) % CH_PF;
-      if (i > 0 || g > 0) loadb(g + i + CH_PF - 1, fr.h[s], fr.l[s], fr.h2[s], fr.l2[s]);      // (step CH_PF - 1 came with ch_request)
-      __builtin_amdgcn_sched_barrier(0);
-      if (g + i < K16) mma(g + i, fr.h[i], fr.l[i], fr.h2[i], fr.l2[i]);
-      __builtin_amdgcn_sched_barrier(0);
-    }
-  }
   }
 }
 // The lane's slice of a layer's output -> the (hi, lo) planes: a lane holds ONE column (col) of 16 rows per row tile and writes 2-byte elements.
@@ -208,7 +183,6 @@ __device__ long long taco_trace_chain[64];      // slots: 0 entry, 1 partial sum
 template <int W>
 __global__ __launch_bounds__(512) void k_pointwise_chain(const ChainArgs a_in) {
   constexpr int WN = W / 32, WM = 8 / WN, TM = CH_BM / 32 / WM;      // W = 256: 1 x 8 waves of 64 x 32; W = 128: 2 x 4 waves of 32 x 32
-  constexpr int PF = W == 256 ? CH_PF256 : CH_PF128;
   constexpr int LDSW = W + 8;                                          // bf16 elements per plane row: (W + 8) * 2 bytes = odd multiple of 16
   extern __shared__ __attribute__((aligned(16))) unsigned short ch_smem[];
   // two plane sets: a hidden layer reads (xhi, xlo) and writes its output into (yhi, ylo), then the two swap -- one barrier per seam
@@ -237,9 +211,9 @@ __global__ __launch_bounds__(512) void k_pointwise_chain(const ChainArgs a_in) {
     return;
   }
   const int m0 = blockIdx.x * CH_BM;
-  // first k16 step of this workgroup's K loops, in 32nds of a layer's K (CH_ROT; ChainArgs::krot = 0 switches it off at run time: every row's fp32
+  // first k16 step of this workgroup's K loops, in 32nds of a layer's K (ChainArgs::krot = 0 switches it off at run time: every row's fp32
   // accumulation order is then the same whichever tile the row lands in -- bit-invariance under batch permutation / sharding at any size)
-  const int krot = (CH_ROT && a_in.krot) ? ((int)(blockIdx.x >> 3) & 31) : 0;
+  const int krot = a_in.krot ? ((int)(blockIdx.x >> 3) & 31) : 0;
 #ifdef TACO_TRACE
   const bool trc = (blockIdx.x == (a_in.ntiles > 0 ? a_in.ntiles : gridDim.x) / 2) && threadIdx.x == 0;
   int trci = 5;
@@ -264,11 +238,11 @@ __global__ __launch_bounds__(512) void k_pointwise_chain(const ChainArgs a_in) {
     } else if (L.type == CH_HIGHWAY) { p.bhB = L.bh2; p.blB = L.bl2; p.dual = true; }
     return p;
   };
-  ChFrag<PF> fr;                               // first weight fragments of the NEXT product loop, requested ahead of the seam in front of it (ch_request)
+  ChFrag fr;                               // first weight fragments of the NEXT product loop, requested ahead of the seam in front of it (ch_request)
   float nbia = 0.f, nbia2 = 0.f;               // ... and the biases of the next hidden layer
   auto request_layer = [&](int li, int l31r, int lhr) {
     const ChainLayer Ln = a_in.L[li];
-    ch_request<PF>(make_prod(Ln, 0), l31r, lhr, fr);
+    ch_request(make_prod(Ln, 0), l31r, lhr, fr);
     if (Ln.type != CH_XPROJ) {
       const int c = wn * 32 + l31r;
       nbia = Ln.bias ? Ln.bias[c] : 0.f;
@@ -567,8 +541,8 @@ __global__ __launch_bounds__(512) void k_pointwise_chain(const ChainArgs a_in) {
 #pragma unroll
         for (int tm = 0; tm < TM; ++tm)
           for (int r = 0; r < 16; ++r) { acc[tm][r] = 0.f; acc2[tm][r] = 0.f; }
-        if (pr.dual) ch_mma_loop<TM, LDSW, true, PF>(pr, fr, xhi, xlo, wm * TM * 32, l31, lh, acc, acc2);
-        else ch_mma_loop<TM, LDSW, false, PF>(pr, fr, xhi, xlo, wm * TM * 32, l31, lh, acc, acc2);     // the odd group: one matrix
+        if (pr.dual) ch_mma_loop<TM, LDSW, true>(pr, fr, xhi, xlo, wm * TM * 32, l31, lh, acc, acc2);
+        else ch_mma_loop<TM, LDSW, false>(pr, fr, xhi, xlo, wm * TM * 32, l31, lh, acc, acc2);     // the odd group: one matrix
 #ifdef TACO_TRACE
         CTRC(trci); ++trci;
 #endif
@@ -579,7 +553,7 @@ __global__ __launch_bounds__(512) void k_pointwise_chain(const ChainArgs a_in) {
         CTRC(trci); ++trci;
 #endif
         __builtin_amdgcn_sched_barrier(0);
-        if (ps + 1 < npass) ch_request<PF>(make_prod(L, ps + 1), l31, lh, fr);
+        if (ps + 1 < npass) ch_request(make_prod(L, ps + 1), l31, lh, fr);
         else if (li + 1 < a.nlayers) request_layer(li + 1, l31, lh);
       }
       continue;
@@ -601,7 +575,7 @@ __global__ __launch_bounds__(512) void k_pointwise_chain(const ChainArgs a_in) {
       const float bia = nbia, bia2 = nbia2;      // (request_layer, in front of the seam before this layer)
       const ChProd pr = make_prod(L, 0);
       if (dual) {
-        ch_mma_loop<TM, LDSW, true, PF>(pr, fr, xhi, xlo, wm * TM * 32, l31, lh, acc, acc2);
+        ch_mma_loop<TM, LDSW, true>(pr, fr, xhi, xlo, wm * TM * 32, l31, lh, acc, acc2);
 #ifdef TACO_TRACE
         CTRC(trci); ++trci;
 #endif
@@ -616,7 +590,7 @@ __global__ __launch_bounds__(512) void k_pointwise_chain(const ChainArgs a_in) {
             xreg[tm][r] = Hh * Tg + xreg[tm][r] * (1.f - Tg);
           }
       } else {
-        ch_mma_loop<TM, LDSW, false, PF>(pr, fr, xhi, xlo, wm * TM * 32, l31, lh, acc, acc2);
+        ch_mma_loop<TM, LDSW, false>(pr, fr, xhi, xlo, wm * TM * 32, l31, lh, acc, acc2);
 #ifdef TACO_TRACE
         CTRC(trci); ++trci;
 #endif

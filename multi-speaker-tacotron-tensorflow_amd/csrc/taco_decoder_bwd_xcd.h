@@ -21,25 +21,20 @@
 // Outputs: the pre-activation gradient tapes the hoisted weight-gradient GEMMs read (decoder_backward in taco_train.h), g_de / g_dq /
 // g_dctx for the hoisted key / value gradients, and the gradients of the initial states.
 #pragma once
-#include "taco_decoder_xcd.h"
+#include "taco_decoder_xcd.h"      // DX_W, the tape slots DXT_*, dx_normalise / dx_scan; the exchange toolkit (taco_xchg.h) through it
 #include "taco_backward_kernels.h"
 
-// s_sleep units (64 clocks) in front of the first poll of every gather of the backward loop: as in the forward kernel (DX_FIRST_POLL_DELAY), a poll that
-// reaches the L2 ahead of the group's stores costs a second round trip
-#ifndef DB_POLL_DELAY
-#define DB_POLL_DELAY 5      // measured on the C4-shard step: 0 -> 12.36 ms, 3 -> 12.32, 5 -> 12.29, 7 -> 12.32 (profiles/r06_ab_poll_delay.txt)
-#endif
-// per-site sleeps as in the forward kernel (DX_DLY): the A/B build -DDX_DLY_RT reads the twelve of this kernel from a second constant table (TACO_DB_DLY).
+// s_sleep units (64 clocks) in front of the first poll of every gather of the backward loop: as in the forward kernel (dx_site_delay), a poll that
+// reaches the L2 ahead of the group's stores costs a second round trip.  One value for every site, measured on the C4-shard step: 0 -> 12.36 ms,
+// 3 -> 12.32, 5 -> 12.29, 7 -> 12.32 (profiles/r06_ab_poll_delay.txt).
+// Then per-site sleeps as in the forward kernel (DX_DLY): the A/B build -DDX_DLY_RT reads the twelve of this kernel from a second constant table (TACO_DB_DLY).
 // tools/sweep_db_delays.py (profiles/r06_sweep_db_delays.txt; the measure is the traced step length): 30 388 clocks per step with every site at 5,
 // 29 600-29 700 with the three sites whose curves are clear -- the d q partials (falls monotonically to 0), the d alpha partials, d z2 -- moved; the
-// other nine are flat within the noise around 4-6 and keep 5.  DB_DLY_TUNED = 0 restores DB_POLL_DELAY everywhere.
-#ifndef DB_DLY_TUNED
-#define DB_DLY_TUNED 1
-#endif
+// other nine are flat within the noise around 4-6 and keep 5.
 __host__ __device__ constexpr int db_site_delay(int site) {
   //                      dcp2 dgp2 dcp1 dgp1 do0 dctx da dq dcpa dgpa dz2 dz1
   constexpr int tuned[12] = {5, 5, 5, 5, 5, 5, 1, 0, 5, 5, 2, 5};
-  return DB_DLY_TUNED ? tuned[site] : DB_POLL_DELAY;
+  return tuned[site];
 }
 #ifdef DX_DLY_RT
 __constant__ int g_db_dly[16];

@@ -43,37 +43,11 @@
 //     context) is written to the tape by the lane that produces it -- [B, n, .] arrays, the layout of DecTape in taco_train.h.
 #pragma once
 #include "taco_kernels.h"
+#include "taco_xchg.h"      // granules, publish / poll / gather, census, passes and wave reductions: shared with the scans and the backward loop
 
-typedef __attribute__((address_space(1))) unsigned long long dx_gu64;
-typedef __attribute__((address_space(1))) unsigned dx_gu32;
-
-#define DX_NT 512
-#define DX_NW 8
-#define DX_GROUP 32          // members (CUs) per group
-#define DX_NGROUP 8          // groups (XCDs)
 #define DX_W 256             // attention_state_size = dec_rnn_size = attention_size = 2*enc_rnn_size = dec_prenet[0]
 #define DX_P2 128            // dec_prenet[1]
 #define DX_P3 64             // dec_prenet[2] (PD = 3: presets with a third prenet layer)
-#define DX_SPIN_LIMIT (1u << 21)
-#ifndef DX_POLL_SLEEP
-#define DX_POLL_SLEEP 0          // s_sleep units (64 clocks) between two polls of a stale granule
-#endif
-// s_sleep units (64 clocks) in front of the FIRST poll of a decoder gather (round 6).  A poll that reaches the L2 ahead of the stores it waits
-// for comes back stale and costs a second round trip (~500 clocks); where nothing runs between a wave's publish and its gather (DX_FIRST_POLL_DELAY:
-// r*h of the three cells, h_att, context, the next step's prenet) a short sleep lets the group's stores land first.  Gathers that follow a
-// run-ahead pass (DX_POLL_DELAY_B: p2, the partial scores, h1, h2) start later, and gain as much.  Measured at C2 on two boxes, decoder alone
-// (profiles/r06_ab_poll_delay.txt): 0 / 0 1.336 ms, 4 / 4 1.322, 5 / 5 1.298, 6 / 6 1.299, 7 / 7 1.328, 8 / 8 1.350 -- a flat optimum around 320 clocks.
-#ifndef DX_FIRST_POLL_DELAY
-#define DX_FIRST_POLL_DELAY 5
-#endif
-#ifndef DX_PRIO_OLD
-#define DX_PRIO_OLD 1       // s_setprio level of waves 0-3 (the first wave of every SIMD) for the whole loop; 0: none.  See dx_body.
-#endif
-#ifndef DX_POLL_DELAY_B
-#define DX_POLL_DELAY_B 5
-#endif
-#define DX_TRACE_STEPS 8
-#define DX_TRACE_SLOTS 16
 
 // Register map of the per-thread weight pack (host mirror: dx_build_pack in taco_lib.hip).  A PASS multiplies one 256-wide
 // (AGX: 128-wide) input vector with NCOLS weight columns of the wave; lane l holds inputs 4l..4l+3 (AGX: 2l, 2l+1) of each:
@@ -175,26 +149,6 @@ struct DxArgs {
   int trc_member, trc_tid;                             // TRACE instantiation: the (member, thread) of group 0 that stamps (default 0, 0; TACO_TRACE_MEMBER / TACO_TRACE_TID)
 };
 
-#define DX_DPP0(v, ctrl) __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), (ctrl), 0xF, 0xF, false))
-#define DX_DPPZ(v, ctrl, rmask, bmask) __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), (ctrl), (rmask), (bmask), true))
-// sum over the wave; every lane of a row of 16 first gets its row's total, the row totals are chained into lane 63 and read back
-// as a wave-uniform value
-__device__ __forceinline__ float dx_allsum(float v) {
-  v += DX_DPP0(v, 0xB1);                 // quad_perm [1,0,3,2]
-  v += DX_DPP0(v, 0x4E);                 // quad_perm [2,3,0,1]
-  v += DX_DPP0(v, 0x141);                // row_half_mirror
-  v += DX_DPP0(v, 0x140);                // row_mirror
-  v += DX_DPPZ(v, 0x142, 0xA, 0xF);      // row_bcast:15 -> rows 1, 3
-  v += DX_DPPZ(v, 0x143, 0xC, 0xF);      // row_bcast:31 -> rows 2, 3
-  return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 63));
-}
-__device__ __forceinline__ float dx_allmax(float v) {
-  v = fmaxf(v, DX_DPP0(v, 0xB1)); v = fmaxf(v, DX_DPP0(v, 0x4E)); v = fmaxf(v, DX_DPP0(v, 0x141)); v = fmaxf(v, DX_DPP0(v, 0x140));
-  const float a = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 0)), b = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 16));
-  const float c = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 32)), d = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 48));
-  return fmaxf(fmaxf(a, b), fmaxf(c, d));
-}
-__device__ __forceinline__ float dx_quadsum(float v) { v += DX_DPP0(v, 0xB1); v += DX_DPP0(v, 0x4E); return v; }
 // inclusive prefix sum over the wave on full-rate DPP (row_shr 1,2,3 / 4 / 8, row_bcast 15 / 31)
 __device__ __forceinline__ float dx_scan(float v) {
   float t = v + DX_DPPZ(v, 0x111, 0xF, 0xF);
@@ -207,128 +161,6 @@ __device__ __forceinline__ float dx_scan(float v) {
   return t;
 }
 __device__ __forceinline__ float dx_sigmoid_fast(float x) { return __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(-1.4426950408889634f * x)); }
-
-// one pass: acc[c][r] += sum_e W[REG0 + 4c + e] * x[r][4*lane + e]   (x: LDS, row stride DXS_LD)
-template <int REG0, int NCOLS, int RG, int NW = DX_NREG, int LD = DXS_LD>
-__device__ __forceinline__ void dx_pass(const float (&W)[NW], const float* x, int lane, float (&acc)[NCOLS][RG]) {
-#pragma unroll
-  for (int r = 0; r < RG; ++r) {
-    const float4 xv = *reinterpret_cast<const float4*>(x + r * LD + 4 * lane);
-#pragma unroll
-    for (int c = 0; c < NCOLS; ++c) {
-      acc[c][r] = fmaf(W[REG0 + 4 * c + 0], xv.x, acc[c][r]);
-      acc[c][r] = fmaf(W[REG0 + 4 * c + 1], xv.y, acc[c][r]);
-      acc[c][r] = fmaf(W[REG0 + 4 * c + 2], xv.z, acc[c][r]);
-      acc[c][r] = fmaf(W[REG0 + 4 * c + 3], xv.w, acc[c][r]);
-    }
-  }
-}
-// the 128-wide pass (attention GRU x rows): 2 inputs per lane
-template <int REG0, int NCOLS, int RG>
-__device__ __forceinline__ void dx_pass2(const float (&W)[DX_NREG], const float* x, int lane, float (&acc)[NCOLS][RG]) {
-#pragma unroll
-  for (int r = 0; r < RG; ++r) {
-    const float2 xv = *reinterpret_cast<const float2*>(x + r * DXS_LD + 2 * lane);
-#pragma unroll
-    for (int c = 0; c < NCOLS; ++c) {
-      acc[c][r] = fmaf(W[REG0 + 2 * c + 0], xv.x, acc[c][r]);
-      acc[c][r] = fmaf(W[REG0 + 2 * c + 1], xv.y, acc[c][r]);
-    }
-  }
-}
-// the 64-wide pass (PD = 3: attention GRU x rows): 1 input per lane
-template <int REG0, int NCOLS, int RG>
-__device__ __forceinline__ void dx_pass1(const float (&W)[DX_NREG], const float* x, int lane, float (&acc)[NCOLS][RG]) {
-#pragma unroll
-  for (int r = 0; r < RG; ++r) {
-    const float xv = x[r * DXS_LD + lane];
-#pragma unroll
-    for (int c = 0; c < NCOLS; ++c) acc[c][r] = fmaf(W[REG0 + c], xv, acc[c][r]);
-  }
-}
-template <int NCOLS, int RG>
-__device__ __forceinline__ void dx_zero(float (&acc)[NCOLS][RG]) {
-#pragma unroll
-  for (int c = 0; c < NCOLS; ++c)
-#pragma unroll
-    for (int r = 0; r < RG; ++r) acc[c][r] = 0.f;
-}
-// Wave reduction of NC columns x RG rows of per-lane partial sums.  A plain tree costs 6 cross-lane (DPP) adds per value and DPP
-// adds are the expensive instruction here (about four times a plain VALU op), so the first two levels are a butterfly that also
-// distributes the ROWS over the lanes of a quad: at each level a lane keeps half of its rows, sends the other half to its
-// partner and adds what the partner sends -- the number of live values halves.  After two levels lane l holds, per column, the
-// RG/4 rows  (l&1)*RG/2 + ((l>>1)&1)*RG/4 + q  summed over its quad; row_ror 4 / 8 finish the row of 16 lanes and two
-// permlane swaps the four rows of the wave, all lane-position preserving.  Every lane ends with the wave totals of its rows.
-template <int RG> struct DxRL { static constexpr int value = RG >= 4 ? RG / 4 : 1; };
-template <int RG>
-__device__ __forceinline__ int dx_row(int lane, int q) {
-  if (RG >= 4) return (lane & 1) * (RG / 2) + ((lane >> 1) & 1) * (RG / 4) + q;
-  if (RG == 2) return lane & 1;
-  return 0;
-}
-__device__ __forceinline__ float dx_xrow16(float v) {
-  const unsigned u = __float_as_uint(v);
-  auto r = __builtin_amdgcn_permlane16_swap(u, u, false, false);
-  return __uint_as_float(r[0]) + __uint_as_float(r[1]);
-}
-__device__ __forceinline__ float dx_xrow32(float v) {
-  const unsigned u = __float_as_uint(v);
-  auto r = __builtin_amdgcn_permlane32_swap(u, u, false, false);
-  return __uint_as_float(r[0]) + __uint_as_float(r[1]);
-}
-template <int NC, int RG>
-__device__ __forceinline__ void dx_reduce(const float (&a)[NC][RG], float (&out)[NC][DxRL<RG>::value], int lane) {
-  constexpr int RL = DxRL<RG>::value;
-  const bool b0 = (lane & 1) != 0, b1 = (lane & 2) != 0;
-  float d[NC][RL];
-  if (RG >= 4) {
-    constexpr int H = RG / 2, Q = RG / 4;
-    float b[NC][H];
-#pragma unroll
-    for (int c = 0; c < NC; ++c)
-#pragma unroll
-      for (int p = 0; p < H; ++p) {
-        const float keep = b0 ? a[c][H + p] : a[c][p], send = b0 ? a[c][p] : a[c][H + p];
-        b[c][p] = keep + DX_DPP0(send, 0xB1);
-      }
-#pragma unroll
-    for (int c = 0; c < NC; ++c)
-#pragma unroll
-      for (int q = 0; q < Q; ++q) {
-        const float keep = b1 ? b[c][Q + q] : b[c][q], send = b1 ? b[c][q] : b[c][Q + q];
-        d[c][q] = keep + DX_DPP0(send, 0x4E);
-      }
-  } else if (RG == 2) {
-#pragma unroll
-    for (int c = 0; c < NC; ++c) {
-      const float keep = b0 ? a[c][1] : a[c][0], send = b0 ? a[c][0] : a[c][1];
-      const float t = keep + DX_DPP0(send, 0xB1);
-      d[c][0] = t + DX_DPP0(t, 0x4E);
-    }
-  } else {
-#pragma unroll
-    for (int c = 0; c < NC; ++c) {
-      const float t = a[c][0] + DX_DPP0(a[c][0], 0xB1);
-      d[c][0] = t + DX_DPP0(t, 0x4E);
-    }
-  }
-#pragma unroll
-  for (int c = 0; c < NC; ++c)
-#pragma unroll
-    for (int q = 0; q < RL; ++q) d[c][q] += DX_DPP0(d[c][q], 0x124);     // row_ror:4
-#pragma unroll
-  for (int c = 0; c < NC; ++c)
-#pragma unroll
-    for (int q = 0; q < RL; ++q) d[c][q] += DX_DPP0(d[c][q], 0x128);     // row_ror:8
-#pragma unroll
-  for (int c = 0; c < NC; ++c)
-#pragma unroll
-    for (int q = 0; q < RL; ++q) d[c][q] = dx_xrow16(d[c][q]);
-#pragma unroll
-  for (int c = 0; c < NC; ++c)
-#pragma unroll
-    for (int q = 0; q < RL; ++q) out[c][q] = dx_xrow32(d[c][q]);
-}
 
 // A pass that runs AHEAD of the gather behind it has to be finished when the poll starts (round 7): its sums are first used after the barrier, and
 // the compiler sank the FMAs to that use -- behind the poll, on the critical path of the stage that waits for the vector.  These keep the
@@ -345,10 +177,7 @@ __device__ __forceinline__ void dx_ahead(float (&a)[1][RG]) {
 }
 
 // ---- round 5: the step's VALU diet (the passes and reductions of k_decoder_xcd are issue bound: two waves per SIMD, ~130 instructions
-// each per gates stage) ----
-#ifndef DX_DIET
-#define DX_DIET 1            // A/B: 0 = the scalar passes and the select-based reduction of rounds 2-4
-#endif
+// each per gates stage; against the scalar passes and the select-based reduction of rounds 2-4: decoder 1.385 -> 1.338 ms, profiles/HISTORY.md 3.1c) ----
 // Column PAIRS in one v_pk_fma_f32 per input: the input broadcast to both halves (op_sel), the two columns' weights of that input side by
 // side.  The resident weights ARE register pairs (taco_f32x2 WP[DX_NREG / 2], loaded once in the order the passes consume them; an array of
 // scalars left the pairing to the allocator, which parked 40 of them in scratch): pair k of a pass that starts at register REG0 is
@@ -387,7 +216,7 @@ __device__ __forceinline__ void dx_rows4(const float* x, int lane, dx_f32x4 (&xv
   }
 }
 #define DXQ_FMA(acc, xs, wp) \
-  do { if (DX_DIET) acc = __builtin_elementwise_fma((taco_f32x2){xs, xs}, wp, acc); else { acc.x = fmaf((wp).x, xs, acc.x); acc.y = fmaf((wp).y, xs, acc.y); } } while (0)
+  do { acc = __builtin_elementwise_fma((taco_f32x2){xs, xs}, wp, acc); } while (0)
 template <int RG>
 __device__ __forceinline__ void dxq_zero(taco_f32x2 (&acc)[RG]) {
 #pragma unroll
@@ -469,7 +298,7 @@ __device__ __forceinline__ void dxw_agx1(const taco_f32x2 (&WP)[DX_NWP], const f
     DXQ_FMA(p[r], xv, WP[k]); sg[0][r] = fmaf(WP[k + 1].x, xv, sg[0][r]);
   }
 }
-// The same two passes split by consumer (round 8, DX_PUB_FIRST): the (r, u) pair, which the publish of r * h waits for, and the candidate-x
+// The same two passes split by consumer (round 8, publish first): the (r, u) pair, which the publish of r * h waits for, and the candidate-x
 // column, which runs behind that publish.  Per accumulator the FMAs and their order are those of dxw_agx2 / dxw_agx1.
 template <int RG>
 __device__ __forceinline__ void dxw_agx2_pair(const taco_f32x2 (&WP)[DX_NWP], const float* x, int lane, taco_f32x2 (&p)[RG]) {
@@ -501,15 +330,12 @@ __device__ __forceinline__ void dxw_agx1_single(const taco_f32x2 (&WP)[DX_NWP], 
 #pragma unroll
   for (int r = 0; r < RG; ++r) sg[0][r] = fmaf(WP[k + 1].x, x[r * DXS_LD + lane], sg[0][r]);
 }
-// Round 8: a GRU gates stage publishes r * h, which needs the reset gate alone.  With DX_PUB_FIRST the stage runs, behind its gather, the (r, u)
+// Round 8: a GRU gates stage publishes r * h, which needs the reset gate alone.  Below eight rows per group (PF in dx_body) the stage runs, behind its gather, the (r, u)
 // pair's input rows (r and u share every v_pk_fma_f32: leaving u out would save no instruction), reduces the r column ALONE, publishes, and only
 // then runs the candidate-x column (GRU 1: the (candidate-x, o0) pair), reduces u and those columns and takes u's sigmoid -- in the window in which
 // the gather behind the stage sleeps before its first poll.  Every column keeps its FMA chain and its reduction tree (dxs_reduce acts per column).
 // The deferred passes read their input rows from LDS a second time; the regions (P2 / OUT2, CTX, OUT1) are next written behind the barrier that
-// follows the stage's own gather, so the second read sees what the first saw.  Bit 0: attention GRU, bit 1: GRU 1, bit 2: GRU 2.
-#ifndef DX_PUB_FIRST
-#define DX_PUB_FIRST 7
-#endif
+// follows the stage's own gather, so the second read sees what the first saw.  All three cells do this (profiles/r08_ab_publish_first.txt).
 // what follows in the source is issued behind the publish stores in front of it: its LDS reads cannot be merged with earlier ones or hoisted
 __device__ __forceinline__ void dx_behind_publish() { asm volatile("" ::: "memory"); }
 // prenet layer 3 (PD = 3): one column over the 128-wide prenet-2 output, registers DXR_AGX + 3, + 4
@@ -528,7 +354,6 @@ __device__ __forceinline__ void dxw_p3(const taco_f32x2 (&WP)[DX_NWP], const flo
 // column at four rows (dx_reduce: 15).
 template <int RG>
 __device__ __forceinline__ int dxs_row(int lane, int q) {
-  if (!DX_DIET) return dx_row<RG>(lane & 3, q);
   if (RG >= 8) return ((lane >> 4) & 1) * (RG / 4) + (lane >> 5) * (RG / 2) + q;
   if (RG == 4) return lane >> 4;
   if (RG == 2) return lane >> 5;
@@ -536,243 +361,79 @@ __device__ __forceinline__ int dxs_row(int lane, int q) {
 }
 template <int RG>
 __device__ __forceinline__ bool dxs_epl(int lane) {
-  if (!DX_DIET) return lane < (RG >= 4 ? 4 : RG);
   return RG >= 4 ? (lane & 15) == 0 : RG == 2 ? (lane & 31) == 0 : lane == 0;
 }
 template <int NC, int RG>
 __device__ __forceinline__ void dxs_reduce(const float (&a)[NC][RG], float (&out)[NC][DxRL<RG>::value], int lane) {
-  if constexpr (!DX_DIET) { dx_reduce<NC, RG>(a, out, lane); return; }
-  else {
-    constexpr int RL = DxRL<RG>::value;
-    float d[NC][RL];
-    if constexpr (RG >= 4) {
-      constexpr int Hh = RG / 2, Q = RG / 4;
-      float b[NC][Hh];
+  constexpr int RL = DxRL<RG>::value;
+  float d[NC][RL];
+  if constexpr (RG >= 4) {
+    constexpr int Hh = RG / 2, Q = RG / 4;
+    float b[NC][Hh];
 #pragma unroll
-      for (int c = 0; c < NC; ++c)
+    for (int c = 0; c < NC; ++c)
 #pragma unroll
-        for (int p = 0; p < Hh; ++p) {        // lanes 0-31 keep rows 0 .. RG/2-1, lanes 32-63 rows RG/2 ..
-          auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(a[c][p]), __float_as_uint(a[c][Hh + p]), false, false);
-          b[c][p] = __uint_as_float(r[0]) + __uint_as_float(r[1]);
-        }
-#pragma unroll
-      for (int c = 0; c < NC; ++c)
-#pragma unroll
-        for (int q = 0; q < Q; ++q) {         // even rows of 16 lanes keep the first half of those, odd rows the second
-          auto r = __builtin_amdgcn_permlane16_swap(__float_as_uint(b[c][q]), __float_as_uint(b[c][Q + q]), false, false);
-          d[c][q] = __uint_as_float(r[0]) + __uint_as_float(r[1]);
-        }
-    } else if constexpr (RG == 2) {
-#pragma unroll
-      for (int c = 0; c < NC; ++c) {
-        auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(a[c][0]), __float_as_uint(a[c][1]), false, false);
-        d[c][0] = dx_xrow16(__uint_as_float(r[0]) + __uint_as_float(r[1]));
+      for (int p = 0; p < Hh; ++p) {        // lanes 0-31 keep rows 0 .. RG/2-1, lanes 32-63 rows RG/2 ..
+        auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(a[c][p]), __float_as_uint(a[c][Hh + p]), false, false);
+        b[c][p] = __uint_as_float(r[0]) + __uint_as_float(r[1]);
       }
-    } else {
 #pragma unroll
-      for (int c = 0; c < NC; ++c) d[c][0] = dx_xrow16(dx_xrow32(a[c][0]));
+    for (int c = 0; c < NC; ++c)
+#pragma unroll
+      for (int q = 0; q < Q; ++q) {         // even rows of 16 lanes keep the first half of those, odd rows the second
+        auto r = __builtin_amdgcn_permlane16_swap(__float_as_uint(b[c][q]), __float_as_uint(b[c][Q + q]), false, false);
+        d[c][q] = __uint_as_float(r[0]) + __uint_as_float(r[1]);
+      }
+  } else if constexpr (RG == 2) {
+#pragma unroll
+    for (int c = 0; c < NC; ++c) {
+      auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(a[c][0]), __float_as_uint(a[c][1]), false, false);
+      d[c][0] = dx_xrow16(__uint_as_float(r[0]) + __uint_as_float(r[1]));
     }
+  } else {
 #pragma unroll
-    for (int c = 0; c < NC; ++c)
-#pragma unroll
-      for (int q = 0; q < RL; ++q) d[c][q] += DX_DPP0(d[c][q], 0xB1);      // quad_perm [1,0,3,2]
-#pragma unroll
-    for (int c = 0; c < NC; ++c)
-#pragma unroll
-      for (int q = 0; q < RL; ++q) d[c][q] += DX_DPP0(d[c][q], 0x4E);      // quad_perm [2,3,0,1]
-#pragma unroll
-    for (int c = 0; c < NC; ++c)
-#pragma unroll
-      for (int q = 0; q < RL; ++q) d[c][q] += DX_DPP0(d[c][q], 0x141);     // row_half_mirror
-#pragma unroll
-    for (int c = 0; c < NC; ++c)
-#pragma unroll
-      for (int q = 0; q < RL; ++q) {
-        out[c][q] = d[c][q] + DX_DPP0(d[c][q], 0x140);      // row_mirror
-        asm("" : "+v"(out[c][q]));      // (round 7: the add stays here, one v_add_f32_dpp; sunk into the epilogue's branch it became a zeroing move, a DPP move and an add)
-      }
+    for (int c = 0; c < NC; ++c) d[c][0] = dx_xrow16(dx_xrow32(a[c][0]));
   }
+#pragma unroll
+  for (int c = 0; c < NC; ++c)
+#pragma unroll
+    for (int q = 0; q < RL; ++q) d[c][q] += DX_DPP0(d[c][q], 0xB1);      // quad_perm [1,0,3,2]
+#pragma unroll
+  for (int c = 0; c < NC; ++c)
+#pragma unroll
+    for (int q = 0; q < RL; ++q) d[c][q] += DX_DPP0(d[c][q], 0x4E);      // quad_perm [2,3,0,1]
+#pragma unroll
+  for (int c = 0; c < NC; ++c)
+#pragma unroll
+    for (int q = 0; q < RL; ++q) d[c][q] += DX_DPP0(d[c][q], 0x141);     // row_half_mirror
+#pragma unroll
+  for (int c = 0; c < NC; ++c)
+#pragma unroll
+    for (int q = 0; q < RL; ++q) {
+      out[c][q] = d[c][q] + DX_DPP0(d[c][q], 0x140);      // row_mirror
+      asm("" : "+v"(out[c][q]));      // (round 7: the add stays here, one v_add_f32_dpp; sunk into the epilogue's branch it became a zeroing move, a DPP move and an add)
+    }
 }
 
-// A/B build -DDX_DLY_RT (tools/sweep_dx_delays.py): the sleep in front of every gather's first poll comes from a constant table that the host
-// fills from TACO_DX_DLY before each launch, so that one build sweeps all ten gathers; the production build has the per-site immediates.
-// Round 6, last: ONE build with the eleven sleeps in a constant table (-DDX_DLY_RT) and a coordinate descent over them on the decoder stage alone
+// The sleep in front of every gather's first poll (dx_first_poll_sleep, taco_xchg.h), s_sleep units of 64 clocks per site.  Round 6 first gave all
+// sites one value, decoder alone at C2 (profiles/r06_ab_poll_delay.txt): 0 1.336 ms, 4 1.322, 5 1.298, 6 1.299, 7 1.328, 8 1.350 -- a flat
+// optimum around 320 clocks.  Then ONE build with the eleven sleeps in a constant table (-DDX_DLY_RT: the host fills it from TACO_DX_DLY before each
+// launch; the production build has the per-site immediates) and a coordinate descent over them on the decoder stage alone
 // (tools/sweep_dx_delays.py, profiles/r06_sweep_dx_delays.txt: three passes, every site at 0..9 units, 3 x 20 launches per point) moved the
 // stage from 1330 us (all sites at 5) to 1275 us per call: the gathers behind a SHORT producer phase want no sleep at all (the partial scores,
-// the context, r*h of GRU 2, the next step's prenet 1: their curves fall monotonically to 0), the others stay at 4-6.  DX_DLY_TUNED = 0
-// restores the two classes above for every site.
-#ifndef DX_DLY_TUNED
-#define DX_DLY_TUNED 1
-#endif
-__host__ __device__ constexpr int dx_site_delay(int site, int dflt, int RG = 4) {
+// the context, r*h of GRU 2, the next step's prenet 1: their curves fall monotonically to 0), the others stay at 4-6.
+__host__ __device__ constexpr int dx_site_delay(int site, int RG = 4) {
   //                          p2 p3 rha ha sc ctx rh1 h1 rh2 h2 p1
   constexpr int tuned4[11] = {2, 5, 0, 5, 0, 3, 2, 3, 0, 3, 0};      // swept at C2 (four rows per group) on the publish-first gate stages (round 8; rounds 6-7: 4 5 6 5 0 0 5 5 0 4 0); also serves one and two rows
   constexpr int tuned8[11] = {7, 5, 3, 5, 0, 6, 5, 6, 4, 6, 2};      // swept on a 64-row pass (eight rows per group: longer producer phases): 1972 (all 5) / 1980 (the table above) -> 1940 us per call
-  return DX_DLY_TUNED ? (RG == 8 ? tuned8[site] : tuned4[site]) : dflt;
+  return RG == 8 ? tuned8[site] : tuned4[site];
 }
 #ifdef DX_DLY_RT
 __constant__ int g_dx_dly[32];      // [0..10]: waves 0-3, [16..26]: waves 4-7 (sweep of a per-half table)
-#define DX_DLY(site, dflt) (100 + (site))
+#define DX_DLY(site) (100 + (site))
 #else
-#define DX_DLY(site, dflt) dx_site_delay(site, dflt, RG)
+#define DX_DLY(site) dx_site_delay(site, RG)
 #endif
-struct DxRt {     // run-time state of a thread
-  dx_gu32* err; bool wt; bool dead;
-#ifdef DX_DLY_RT
-  int dly[12];       // this wave's table (waves 0-3 / 4-7 may differ in the A/B build)
-#endif
-};
-template <int DLY>
-__device__ __forceinline__ void dx_first_poll_sleep(const DxRt& rt) {
-#ifdef DX_DLY_RT
-  if constexpr (DLY >= 100) { const int n = __builtin_amdgcn_readfirstlane(rt.dly[DLY - 100]); for (int i = 0; i < n; ++i) __builtin_amdgcn_s_sleep(1); return; }
-#endif
-  if constexpr (DLY > 0 && DLY < 100) __builtin_amdgcn_s_sleep(DLY);
-  (void)rt;
-}
-// WTC: the protocol as a compile-time constant (0: XCD-local, 1: write-through) where the kernel body is instantiated per protocol -- the
-// run-time test (-1) costs a branch per publish, ~30 clocks each on the chain (round 5: 11 % of a post-net scan step, measured)
-// DX_PUB_MODE (A/B, tools/ubench_mfma_stage): how an XCD-local granule leaves the lane.  0 (default): global_store_dwordx2 sc0; 1: a workgroup-scope
-// atomic swap whose result is dropped (executed at the L2); 2: a non-temporal store; 3: a plain store
-#ifndef DX_PUB_MODE
-#define DX_PUB_MODE 0
-#endif
-__device__ __forceinline__ void dx_store_local(dx_gu64* p, unsigned long long g) {
-  if (DX_PUB_MODE == 1) (void)__hip_atomic_exchange(p, g, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-  else if (DX_PUB_MODE == 2) __builtin_nontemporal_store(g, p);
-  else if (DX_PUB_MODE == 3) *p = g;
-  else __hip_atomic_store(p, g, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);           // sc0: stays in this XCD's L2
-}
-// Granule `idx` of a group's exchange buffer as the buffer's (wave-uniform) base + a 32-bit byte offset (round 7): the access is one instruction
-// with the base in an SGPR pair and the offset in one VGPR.  As X + xl.field + index the compiler kept a 64-bit base per exchange field in SGPRs
-// (spilled to VGPR lanes and read back with v_readlane inside the step) and built every address with 64-bit VALU adds.  The buffer is far below 4 GB.
-__device__ __forceinline__ dx_gu64* dx_at(const dx_gu64* X, unsigned idx) {
-  return (dx_gu64*)((__attribute__((address_space(1))) char*)X + (size_t)(idx * 8u));
-}
-template <int WTC = -1>
-__device__ __forceinline__ void dx_publish(dx_gu64* p, float v, unsigned tag, const DxRt& rt) {
-  const unsigned long long g = ((unsigned long long)tag << 32) | (unsigned long long)__float_as_uint(v);
-  if (WTC == 1 || (WTC < 0 && rt.wt)) __hip_atomic_store(p, g, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);         // sc1: write-through, any placement
-  else dx_store_local(p, g);
-}
-// N granules of one lane at once (p + u*stride): ONE uniform branch on the protocol around all stores, so that the epilogue that
-// produced the values stays a single basic block (a branch per value kept the compiler from interleaving the exp/rcp chains of
-// independent units)
-template <int N, int WTC = -1>
-__device__ __forceinline__ void dx_publish_n(dx_gu64* p, int stride, const float (&v)[N], unsigned tag, const DxRt& rt) {
-  unsigned long long g[N];
-#pragma unroll
-  for (int u = 0; u < N; ++u) g[u] = ((unsigned long long)tag << 32) | (unsigned long long)__float_as_uint(v[u]);
-  if (WTC == 1 || (WTC < 0 && rt.wt)) {
-#pragma unroll
-    for (int u = 0; u < N; ++u) __hip_atomic_store(p + u * stride, g[u], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  } else {
-#pragma unroll
-    for (int u = 0; u < N; ++u) dx_store_local(p + u * stride, g[u]);
-  }
-}
-// keeps a value's computation where it is written (LLVM otherwise sinks an expensive operand of a select into a branch)
-#define DX_PIN(x) asm("" : "+v"(x))
-// Poll N granules (p0 + u*stride) until every one carries `tag` (L1-bypassing loads).  All N are re-requested together on every
-// round, so a late producer costs one L2 round trip after its store lands, not one per granule.  Bounded.
-template <int N, int DLY = 0>
-__device__ __forceinline__ void dx_poll_at(const dx_gu64* X, unsigned idx0, unsigned stride, unsigned tag, float (&v)[N], DxRt& rt) {
-  // (keeping a second round of requests in flight behind the one being examined was measured: 11.8 -> 14.2 us per decoder step at
-  // C2 -- the extra L2 requests of 16 K pollers delay the very stores they are waiting for)
-  unsigned long long g[N];
-  unsigned spins = 0;
-  dx_first_poll_sleep<DLY>(rt);
-  for (;;) {
-    bool ok = true;
-#pragma unroll
-    for (int u = 0; u < N; ++u) g[u] = __hip_atomic_load(dx_at(X, idx0 + (unsigned)u * stride), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-#pragma unroll
-    for (int u = 0; u < N; ++u) ok = ok && ((unsigned)(g[u] >> 32) == tag);
-    if (ok || rt.dead) break;
-    if (DX_POLL_SLEEP) __builtin_amdgcn_s_sleep(DX_POLL_SLEEP);
-    if ((++spins & 1023u) == 0) {
-      if (spins >= DX_SPIN_LIMIT || __hip_atomic_load(rt.err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0) {
-        __hip_atomic_store(rt.err, 2u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        rt.dead = true;
-      }
-    }
-  }
-#pragma unroll
-  for (int u = 0; u < N; ++u) v[u] = __uint_as_float((unsigned)g[u]);
-}
-template <int N, int DLY = 0>
-__device__ __forceinline__ void dx_poll(const dx_gu64* p0, size_t stride, unsigned tag, float (&v)[N], DxRt& rt) {
-  dx_poll_at<N, DLY>(p0, 0u, (unsigned)stride, tag, v, rt);
-}
-// all-gather of a published [RG][N] vector (granules X[base ..]) into the LDS state vector at column offset `off` (N a power of two);
-// RES: dst2[r][n] = value + res[r][n] as well (ResidualWrapper output, tacotron.py:172)
-// Two ADJACENT granules with one 16-byte request (each 8-byte half is one producer's single 8-byte store; a half that has not landed
-// fails its own tag test and the pair is asked for again).  Used where a thread collects four or more granules per gather (eight rows
-// per group; the 512-wide gate-gradient vectors of the BPTT kernel): measured on the exchange stage in isolation
-// (tools/ubench_rowsets, variant T) 13.96 -> 12.63 us per step at eight rows, and nothing at two granules per thread (C2's decoder).
-typedef unsigned long long dx_u64x2 __attribute__((ext_vector_type(2)));
-template <int NP, int DLY = 0>
-__device__ __forceinline__ void dx_poll_pairs(const dx_gu64* X, unsigned idx0, unsigned stride, unsigned tag, float (&v)[2 * NP], DxRt& rt) {
-  dx_u64x2 g[NP];
-  unsigned spins = 0;
-  dx_first_poll_sleep<DLY>(rt);
-  for (;;) {
-    bool ok = true;
-#pragma unroll
-    for (int u = 0; u < NP; ++u) {
-      const dx_gu64* p = dx_at(X, idx0 + (unsigned)u * stride);
-      asm volatile("global_load_dwordx4 %0, %1, off sc1" : "=v"(g[u]) : "v"(p) : "memory");
-    }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#pragma unroll
-    for (int u = 0; u < NP; ++u) ok = ok && ((unsigned)(g[u][0] >> 32) == tag) && ((unsigned)(g[u][1] >> 32) == tag);
-    if (ok || rt.dead) break;
-    if ((++spins & 1023u) == 0) {
-      if (spins >= DX_SPIN_LIMIT || __hip_atomic_load(rt.err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0) {
-        __hip_atomic_store(rt.err, 2u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        rt.dead = true;
-      }
-    }
-  }
-#pragma unroll
-  for (int u = 0; u < NP; ++u) { v[2 * u] = __uint_as_float((unsigned)g[u][0]); v[2 * u + 1] = __uint_as_float((unsigned)g[u][1]); }
-}
-template <int RG, int N, bool RES, int LD = DXS_LD, int NT = DX_NT, int DLY = 0>
-__device__ __forceinline__ void dx_gather_at(const dx_gu64* X, unsigned base, unsigned tag, float* st, int off, int off_res, int off2, int tid, DxRt& rt) {
-  constexpr int NI = (RG * N + NT - 1) / NT;
-  if constexpr (NI >= 4 && NI % 2 == 0 && (RG * N) % (2 * NT) == 0 && N % 2 == 0) {
-    constexpr int NP = NI / 2;
-    float v[NI];
-    dx_poll_pairs<NP, DLY>(X, base + 2u * (unsigned)tid, 2u * NT, tag, v, rt);
-#pragma unroll
-    for (int u = 0; u < NP; ++u) {
-      const unsigned i = 2u * ((unsigned)(u * NT) + (unsigned)tid), r = i / (unsigned)N, n = i % (unsigned)N;
-      *reinterpret_cast<float2*>(st + r * LD + off + n) = make_float2(v[2 * u], v[2 * u + 1]);
-      if (RES) {
-        const float2 rs = *reinterpret_cast<const float2*>(st + r * LD + off_res + n);
-        *reinterpret_cast<float2*>(st + r * LD + off2 + n) = make_float2(v[2 * u] + rs.x, v[2 * u + 1] + rs.y);
-      }
-    }
-    return;
-  }
-  const bool act = (RG * N >= NT) || tid < RG * N;
-  if (act) {
-    float v[NI];
-    dx_poll_at<NI, DLY>(X, base + (unsigned)tid, NT, tag, v, rt);
-#pragma unroll
-    for (int u = 0; u < NI; ++u) {
-      const unsigned i = (unsigned)(u * NT) + (unsigned)tid;      // (unsigned: a shift and a mask; the signed forms cost five instructions each)
-      const unsigned r = i / (unsigned)N, n = i % (unsigned)N;
-      st[r * LD + off + n] = v[u];
-      if (RES) st[r * LD + off2 + n] = v[u] + st[r * LD + off_res + n];
-    }
-  }
-}
-template <int RG, int N, bool RES, int LD = DXS_LD, int NT = DX_NT, int DLY = 0>
-__device__ __forceinline__ void dx_gather(const dx_gu64* X, unsigned tag, float* st, int off, int off_res, int off2, int tid, DxRt& rt) {
-  dx_gather_at<RG, N, RES, LD, NT, DLY>(X, 0u, tag, st, off, off_res, off2, tid, rt);
-}
-
 // The alignment normaliser of one row by ONE wave, lane = `cnt` (<= CMAX) consecutive positions starting at j0, values held in
 // registers: sc (scores in, alignments out), alp (previous alignments).
 //   bah_mon: monotonic_attention(mode='parallel') (A.10): p = sigmoid(e + bias); cp = exp(cumsum_excl(log(clip(1-p, tiny, 1))));
@@ -844,47 +505,6 @@ __device__ __forceinline__ void dx_normalise_lds(float* sc, float* tmp, float* t
     const float inv = 1.0f / sm;
     for (int j = j0; j < j1; ++j) sc[j] = sc[j] * inv;
   }
-}
-
-typedef __attribute__((address_space(3))) float dx_lds_float;
-// 4 bytes per lane from global memory straight into LDS: the wave's 64 floats land at LDS byte address lds_dst (wave-uniform) + 4 * lane.
-// Not counted by hipcc: the consumer waits (any later s_waitcnt vmcnt(0) of the issuing wave covers it: loads retire in order).
-__device__ __forceinline__ void dx_load_lds4(const float* gsrc, unsigned lds_dst) {
-  unsigned keep;
-  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dword %1, off\n\ts_mov_b32 m0, %0"
-               : "=&s"(keep) : "v"(gsrc), "s"(lds_dst) : "memory");
-}
-
-// Census of a persistent launch of 256 (or 512: two per CU) workgroups: every workgroup reports the XCD it runs on (HW_REG_XCC_ID)
-// and takes the next slot there; when all have arrived and every XCD hosts exactly gridDim.x / 8 of them, the XCD-local protocol is used (exchange stores stay
-// in the XCD's L2) and a workgroup's place is (xcc, slot); otherwise -- or with force_wt -- places follow blockIdx and the stores
-// are write-through.  out[0] = xcc or blockIdx % 8, out[1] = slot (0..31) or blockIdx / 8, out[2] = write-through?, out[3] = failed?
-// errw[info0..info0+8] report the protocol and the per-XCD counts to the host.  Called by all threads; ends with a barrier.
-__device__ __forceinline__ void dx_census(dx_gu32* ctl, dx_gu32* errw, int force_wt, int* out, int tid, int info0) {
-  if (tid == 0) {
-    const unsigned xcc = __builtin_amdgcn_s_getreg(6164) & 7u;      // HW_REG_XCC_ID (id 20), bits [3:0]
-    const unsigned slot = __hip_atomic_fetch_add(ctl + xcc, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    __hip_atomic_fetch_add(ctl + 8, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    unsigned spins = 0; bool ok = true;
-    while (__hip_atomic_load(ctl + 8, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < gridDim.x) {
-      __builtin_amdgcn_s_sleep(2);
-      if (++spins > (DX_SPIN_LIMIT << 2) || __hip_atomic_load(errw, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0) { ok = false; break; }
-    }
-    bool even = ok;
-    for (int i = 0; i < DX_NGROUP; ++i)
-      even = even && (__hip_atomic_load(ctl + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == gridDim.x / DX_NGROUP);
-    const bool fast = even && !force_wt;
-    if (!ok) __hip_atomic_store(errw, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    out[0] = fast ? (int)xcc : (int)(blockIdx.x & 7);
-    out[1] = fast ? (int)slot : (int)(blockIdx.x >> 3);
-    out[2] = fast ? 0 : 1;
-    out[3] = ok ? 0 : 1;
-    if (blockIdx.x == 0) {   // reported to the host (taco_debug_decoder_info): protocol used, workgroups seen per XCD
-      errw[info0] = fast ? 1u : 2u;
-      for (int i = 0; i < DX_NGROUP; ++i) errw[info0 + 1 + i] = __hip_atomic_load(ctl + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-  }
-  __syncthreads();
 }
 
 // 'simple' speaker term: rowbias[b][slot][n] = sum_k table[speaker_id[b]][k] * spkw[k][slot][n]   (S = speaker_embedding_size rows)
@@ -1067,8 +687,8 @@ __device__ __forceinline__ void dx_body(const DxArgs& a, float* dx_smem, int gro
 #define DX_BIAS_AHEAD(var, slot) float var = bl[(slot) * DX_NW + wave]
 #define DX_BIAS_HERE(var) asm volatile("" : "+v"(var))
   float g_u[RL], g_cx[RL], g_h[RL], g_o0[RL];            // live between the two stages of a GRU cell
-  // publish r * h first (DX_PUB_FIRST); eight rows per group keeps the one-pass order: 256 VGPRs and none to spare
-  constexpr bool PF_A = (DX_PUB_FIRST & 1) && RG < 8, PF_1 = (DX_PUB_FIRST & 2) && RG < 8, PF_2 = (DX_PUB_FIRST & 4) && RG < 8;
+  // publish r * h first, in all three cells (profiles/r08_ab_publish_first.txt); eight rows per group keeps the one-pass order: 256 VGPRs and none to spare
+  constexpr bool PF = RG < 8;
   // tape (TAPE): the lane that owns (row, column) of a stage writes it; trow = float offset of step 0 of the lane's row in a [B, n, 256] array
   // (32-bit element offsets: the host checks DXT_N * tstride < 2^31, so an address is the SGPR base + one VGPR)
   unsigned trow[RL];
@@ -1093,7 +713,7 @@ __device__ __forceinline__ void dx_body(const DxArgs& a, float* dx_smem, int gro
   // by age anyway, with s_setprio 1 it also wins every tie -- the stage's first four columns are published earlier and the vector is complete
   // sooner.  A/B of variant builds on one box (profiles/r06_ab_priority.txt): decoder alone 1.305 -> 1.289-1.295 ms at levels 1, 2, 3 alike;
   // priority for the YOUNGER half instead 1.303 (no gain; in the post-net scan it costs 38 us, and the older half gains nothing there).
-  if (DX_PRIO_OLD && wave < 4) __builtin_amdgcn_s_setprio(DX_PRIO_OLD);
+  if (wave < 4) __builtin_amdgcn_s_setprio(1);
   const int tid_outer = tid, lane_outer = lane;
   for (int t = 0; t < a.n; ++t) {
     const unsigned tag = (unsigned)t + 1u;
@@ -1140,7 +760,7 @@ __device__ __forceinline__ void dx_body(const DxArgs& a, float* dx_smem, int gro
     dx_zero<1, RG>(ag2);
     dxw_pair<DXR_AGH, RG>(WP, st + DXS_HATT, lane, ag01);
     dx_ahead<RG>(ag01);
-    dx_gather_at<RG, DX_P2, false, DXS_LD, DX_NT, DX_DLY(0, DX_POLL_DELAY_B)>(X, (unsigned)xl.p2, tag, st, DXS_P2, 0, 0, tid, rt);
+    dx_gather_at<RG, DX_P2, false, DXS_LD, DX_NT, DX_DLY(0)>(X, (unsigned)xl.p2, tag, st, DXS_P2, 0, 0, tid, rt);
     __syncthreads();
     if constexpr (PD == 3) {
       // ================= prenet layer 3 (64 columns, two per member); its output takes the OUT2 slot, dead until the end of the step =================
@@ -1155,12 +775,12 @@ __device__ __forceinline__ void dx_body(const DxArgs& a, float* dx_smem, int gro
             dx_publish<WTC>(dx_at(X, (unsigned)(xl.p3 + erow[q] * DX_P3 + member * 2 + wave)), fmaxf(s[0][q] + bl[DXB_P3 * DX_NW + wave], 0.f), tag, rt);
         }
       }
-      dx_gather_at<RG, DX_P3, false, DXS_LD, DX_NT, DX_DLY(1, DX_FIRST_POLL_DELAY)>(X, (unsigned)xl.p3, tag, st, DXS_OUT2, 0, 0, tid, rt);
+      dx_gather_at<RG, DX_P3, false, DXS_LD, DX_NT, DX_DLY(1)>(X, (unsigned)xl.p3, tag, st, DXS_OUT2, 0, 0, tid, rt);
       __syncthreads();
     }
     DX_STAMP(1);
     // ================= attention GRUCell (tacotron.py:127-130; A.6): gates, then candidate =================
-    if constexpr (PF_A) {
+    if constexpr (PF) {
       float ar[1][RG], sr[1][RL], rgv[RL];
       if constexpr (PD == 3) dxw_agx1_pair<RG>(WP, st + DXS_OUT2, lane, ag01);
       else dxw_agx2_pair<RG>(WP, st + DXS_P2, lane, ag01);
@@ -1203,7 +823,7 @@ __device__ __forceinline__ void dx_body(const DxArgs& a, float* dx_smem, int gro
       }
     }
     DX_BIAS_AHEAD(b_ac, DXB_AC);
-    dx_gather_at<RG, DX_W, false, DXS_LD, DX_NT, DX_DLY(2, DX_FIRST_POLL_DELAY)>(X, (unsigned)xl.rha, tag, st, DXS_T, 0, 0, tid, rt);
+    dx_gather_at<RG, DX_W, false, DXS_LD, DX_NT, DX_DLY(2)>(X, (unsigned)xl.rha, tag, st, DXS_T, 0, 0, tid, rt);
     DX_BIAS_HERE(b_ac);
     __syncthreads();
     DX_STAMP(2);
@@ -1222,7 +842,7 @@ __device__ __forceinline__ void dx_body(const DxArgs& a, float* dx_smem, int gro
     }
 #pragma unroll
     for (int q = 0; q < RL; ++q) g_h[q] = st[erow[q] * DXS_LD + DXS_H1 + en];
-    dx_gather_at<RG, DX_W, false, DXS_LD, DX_NT, DX_DLY(3, DX_FIRST_POLL_DELAY)>(X, (unsigned)xl.ha, tag, st, DXS_HATT, 0, 0, tid, rt);
+    dx_gather_at<RG, DX_W, false, DXS_LD, DX_NT, DX_DLY(3)>(X, (unsigned)xl.ha, tag, st, DXS_HATT, 0, 0, tid, rt);
     __syncthreads();
     DX_STAMP(3);
     // ================= attention (rnn_wrappers.py:304-341) =================
@@ -1297,7 +917,7 @@ __device__ __forceinline__ void dx_body(const DxArgs& a, float* dx_smem, int gro
           float s = 0.f;
           if (j < T) {
             float v[NP];
-            dx_poll_at<NP, DX_DLY(4, DX_POLL_DELAY_B)>(X, (unsigned)(xl.sc + (arow * Pc + part * NP) * T + j), (unsigned)T, tag, v, rt);
+            dx_poll_at<NP, DX_DLY(4)>(X, (unsigned)(xl.sc + (arow * Pc + part * NP) * T + j), (unsigned)T, tag, v, rt);
 #pragma unroll
             for (int u = 0; u < NP; ++u) s += v[u];
           }
@@ -1351,7 +971,7 @@ __device__ __forceinline__ void dx_body(const DxArgs& a, float* dx_smem, int gro
         if (TAPE && a.tp_alpha) a.tp_alpha[((size_t)brow * (a.n + 1) + t + 1) * T + p0 + tid] = sc[aoff + p0 + tid];
       }
     }
-    dx_gather_at<RG, DX_W, false, DXS_LD, DX_NT, DX_DLY(5, DX_FIRST_POLL_DELAY)>(X, (unsigned)xl.ctx, tag, st, DXS_CTX, 0, 0, tid, rt);
+    dx_gather_at<RG, DX_W, false, DXS_LD, DX_NT, DX_DLY(5)>(X, (unsigned)xl.ctx, tag, st, DXS_CTX, 0, 0, tid, rt);
     __syncthreads();
     DX_STAMP(6);
     // ================= concat projection folded into residual GRU 1 (rnn_wrappers.py:405-415; tacotron.py:166-172) =================
@@ -1362,7 +982,7 @@ __device__ __forceinline__ void dx_body(const DxArgs& a, float* dx_smem, int gro
         dxw_pair<DXR_G1H, RG>(WP, st + DXS_H1, lane, g1p0);
         dxw_quad<DXR_G1A, RG>(WP, st + DXS_HATT, lane, g1p0, g1p1);
       }
-      if constexpr (PF_1) {
+      if constexpr (PF) {
         float ar[1][RG], sr[1][RL], rgv[RL];
         dxw_pair<DXR_G1B, RG>(WP, st + DXS_CTX, lane, g1p0);
 #pragma unroll
@@ -1408,7 +1028,7 @@ __device__ __forceinline__ void dx_body(const DxArgs& a, float* dx_smem, int gro
       }
     }
     DX_BIAS_AHEAD(b_g1c, DXB_G1C);
-    dx_gather_at<RG, DX_W, false, DXS_LD, DX_NT, DX_DLY(6, DX_FIRST_POLL_DELAY)>(X, (unsigned)xl.rh1, tag, st, DXS_T, 0, 0, tid, rt);
+    dx_gather_at<RG, DX_W, false, DXS_LD, DX_NT, DX_DLY(6)>(X, (unsigned)xl.rh1, tag, st, DXS_T, 0, 0, tid, rt);
     DX_BIAS_HERE(b_g1c);
     DX_STAMP(14);
     __syncthreads();
@@ -1437,7 +1057,7 @@ __device__ __forceinline__ void dx_body(const DxArgs& a, float* dx_smem, int gro
     dxq_zero<RG>(g2p);
     dx_zero<1, RG>(g2c);
     if (G1_AHEAD) { dxw_pair<DXR_G2H, RG>(WP, st + DXS_H2, lane, g2p); dx_ahead<RG>(g2p); }
-    dx_gather_at<RG, DX_W, false, DXS_LD, DX_NT, DX_DLY(7, DX_POLL_DELAY_B)>(X, (unsigned)xl.h1, tag, st, DXS_H1, 0, 0, tid, rt);
+    dx_gather_at<RG, DX_W, false, DXS_LD, DX_NT, DX_DLY(7)>(X, (unsigned)xl.h1, tag, st, DXS_H1, 0, 0, tid, rt);
     dx_gather_at<RG, DX_W, false, DXS_LD, DX_NT, 0>(X, (unsigned)xl.o1, tag, st, DXS_OUT1, 0, 0, tid, rt);
     __syncthreads();
     DX_STAMP(8);
@@ -1445,7 +1065,7 @@ __device__ __forceinline__ void dx_body(const DxArgs& a, float* dx_smem, int gro
     {
       float s[3][RL];
       if (!G1_AHEAD) dxw_pair<DXR_G2H, RG>(WP, st + DXS_H2, lane, g2p);
-      if constexpr (PF_2) {
+      if constexpr (PF) {
         float ar[1][RG], sr[1][RL], rgv[RL];
         dxw_pair<DXR_G2X, RG>(WP, st + DXS_OUT1, lane, g2p);
 #pragma unroll
@@ -1485,7 +1105,7 @@ __device__ __forceinline__ void dx_body(const DxArgs& a, float* dx_smem, int gro
       }
     }
     DX_BIAS_AHEAD(b_g2c, DXB_G2C);
-    dx_gather_at<RG, DX_W, false, DXS_LD, DX_NT, DX_DLY(8, DX_FIRST_POLL_DELAY)>(X, (unsigned)xl.rh2, tag, st, DXS_T, 0, 0, tid, rt);
+    dx_gather_at<RG, DX_W, false, DXS_LD, DX_NT, DX_DLY(8)>(X, (unsigned)xl.rh2, tag, st, DXS_T, 0, 0, tid, rt);
     DX_BIAS_HERE(b_g2c);
     __syncthreads();
     DX_STAMP(9);
@@ -1507,7 +1127,7 @@ __device__ __forceinline__ void dx_body(const DxArgs& a, float* dx_smem, int gro
     dx_zero<1, RG>(p1a);
     if (G1_AHEAD) { dxw_single<DXR_P1C, RG>(WP, st + DXS_CTX, lane, p1a); dx_ahead<RG>(p1a); }
     DX_BIAS_AHEAD(b_p1, DXB_P1); DX_BIAS_AHEAD(b_f0, DXB_F0); DX_BIAS_AHEAD(b_f1, DXB_F1);
-    dx_gather_at<RG, DX_W, true, DXS_LD, DX_NT, DX_DLY(9, DX_POLL_DELAY_B)>(X, (unsigned)xl.h2, tag, st, DXS_H2, DXS_OUT1, DXS_OUT2, tid, rt);
+    dx_gather_at<RG, DX_W, true, DXS_LD, DX_NT, DX_DLY(9)>(X, (unsigned)xl.h2, tag, st, DXS_H2, DXS_OUT1, DXS_OUT2, tid, rt);
     DX_BIAS_HERE(b_p1); DX_BIAS_HERE(b_f0); DX_BIAS_HERE(b_f1);
     __syncthreads();
     DX_STAMP(10);
@@ -1603,7 +1223,7 @@ __device__ __forceinline__ void dx_body(const DxArgs& a, float* dx_smem, int gro
         if (b < a.B) a.dbg[((size_t)t * a.B + b) * a.dbgw + q * DX_W + nn] = st[r * DXS_LD + off + nn];
       }
     }
-    if (t + 1 < a.n) dx_gather_at<RG, DX_W, false, DXS_LD, DX_NT, DX_DLY(10, DX_FIRST_POLL_DELAY)>(X, (unsigned)xl.p1, tag, st, DXS_T, 0, 0, tid, rt);
+    if (t + 1 < a.n) dx_gather_at<RG, DX_W, false, DXS_LD, DX_NT, DX_DLY(10)>(X, (unsigned)xl.p1, tag, st, DXS_T, 0, 0, tid, rt);
     __syncthreads();
     DX_STAMP(11);
   }

@@ -9,21 +9,16 @@
 //     MFMAs; round 4: the pair at once); its weight fragments come straight from the layer's pack in L2 through a ring of HD_PF
 //     register sets that runs on across the tiles, so the stream never restarts; the stores of a tile ride inside the product loop
 //     of the next one -- a quarter of a wave's stores is left after its last products;
-//   * the workgroups of an XCD start their sweep at different passes (HD_ROT): they do not all ask the L2 for the same tiles at once;
+//   * the workgroups of an XCD start their sweep at different passes: they do not all ask the L2 for the same tiles at once;
 //   * the columns past the last full tile (ONE at N = 1025) are dot products on the vector ALU from the same planes (hi + lo as fp32,
 //     fp32 weights): a 33rd MFMA tile would hand one wave a third pass while seven idle.  They come FIRST, right behind the staging
 //     barrier: behind the sweep their weight loads queued up behind the last tile's stores.
 #pragma once
 #include "taco_kernels.h"
 
-#ifndef HD_ROT
-#define HD_ROT 1
-#endif
 #define HD_BM 64
 #define HD_KMAX 512      // widest input (the planes of 64 rows x 512 inputs take 133 KB of LDS)
-#ifndef HD_PF
-#define HD_PF 4          // register sets of weight fragments per wave: the fragments of step g + HD_PF - 1 are requested before step g is multiplied (a step is 6 MFMAs = ~200 clocks of the wave's own matrix work: three steps ahead cover an L2 round trip under load)
-#endif
+#define HD_PF 4          // register sets of weight fragments per wave: the fragments of step g + HD_PF - 1 are requested before step g is multiplied (a step is 6 MFMAs = ~200 clocks of the wave's own matrix work: three steps ahead cover an L2 round trip under load; 2 and 8 sets measured: profiles/r05_ab_runs.txt, call K)
 struct HeadArgs {
   const float* x; int ldx;                                     // input rows [M, ldx], K columns used (K % 64 == 0, K <= HD_KMAX)
   const unsigned short* bh; const unsigned short* bl;          // split-bf16 pack of the layer (pack_bf3)
@@ -86,9 +81,9 @@ __global__ __launch_bounds__(512) void k_head_sweep(const HeadArgs a_in) {
   const int NTF = N / 32, npair = (NTF + 1) / 2;
   const int mypass = wave < npair ? (npair - 1 - wave) / 8 + 1 : 0;
   const int ntile = 2 * mypass, nsteps = ntile * K16;
-  // HD_ROT: the workgroups of an XCD start their sweep at different passes (the L2 is asked for different column tiles at a time:
-  // 75 -> 64 us at C2, profiles/r05_*)
-  const int prot = HD_ROT ? (int)(blockIdx.x >> 3) % max(mypass, 1) : 0;
+  // the workgroups of an XCD start their sweep at different passes (the L2 is asked for different column tiles at a time:
+  // 75 -> 64 us at C2, profiles/r05_ab_runs.txt, call J)
+  const int prot = (int)(blockIdx.x >> 3) % max(mypass, 1);
   auto tile_of = [&](int q) { int pp = (q >> 1) + prot; pp = pp >= mypass ? pp - mypass : pp; return 2 * (wave + 8 * pp) + (q & 1); };
   auto bofs = [&](int s) {                                     // flat step (tile, k16) -> element offset of the lane's fragment
     const int sc = min(s, nsteps - 1), q = sc / K16, g = sc - q * K16, t = min(tile_of(q), NT - 1);      // (the second tile of the last pair may not exist: its products are never stored)
