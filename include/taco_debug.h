@@ -136,6 +136,40 @@ int taco_train_debug_cbhg(taco_train* t, void* hip_stream, int which, float* d_p
                           const float* d_h0, const float* d_before, const float* d_dout, int B, int T, float* d_out, float* d_din, float* d_dh0,
                           float* d_dbefore, void* d_ws, size_t ws_bytes, uint32_t* paths);
 
+/* Test hook: the DECODER of a trainer alone -- the teacher-forced training forward with its tape (decoder_forward_train, feed_back = false), then its backward
+ * (decoder_backward: the persistent BPTT or the per-stage chain, the hoisted weight gradients, the attention-memory gradients) -- on caller data, exactly as
+ * the step calls them: the step's context and state objects, the tape layout of the step (carve_dec_tape), the trainer's current switches
+ * (taco_train_set_exact_gemm, _set_exact_wgrad, _set_wgrad_planes, _set_deterministic, _set_bptt_engine; taco_debug_set_decoder_persist on taco_train_model).
+ * Inputs: d_enc_out [B*T_in, D] (D = 2 * enc_rnn_size), d_teacher [B, n, num_mels] (the frame fed to step t + 1 is row t), d_dmel [B, n, r*num_mels] (the
+ * upstream gradient of d_mel).  Nullable: d_att_init [B, attention_state_size] and d_dec_init (dec_layer_num pointers to [B, dec_rnn_size], each nullable) --
+ * model type deepvoice only; d_spk_emb [B, S], the speaker rows -- required by model type 'simple' and refused elsewhere.
+ * Outputs: d_mel [B, n, r*num_mels], d_alignments [B, T_in, n], d_denc [B*T_in, D], and the nullable gradient twins d_datt_init, d_ddec_init (an array as
+ * d_dec_init), d_dspk_emb [B, S] (required with d_spk_emb; overwritten).  A gradient output without its input is TACO_ERR_ARG.
+ * d_params: the trainer's flat parameters, as of the last taco_train_refresh.  The parameter gradients of everything decoder_backward writes (decoder/...,
+ * attention/...) are ADDED into d_grads at their taco_train_param_offset -- zero-fill them first, as the step zero-fills the whole buffer; no other element of
+ * d_grads is written.
+ * d_ws: at least taco_train_debug_decoder_workspace_bytes(t, B, T_in, n) bytes (ask again after a switch that changes the step's workspace), 16-byte aligned.
+ * Errors, as the step's and all returned before the first HIP call: misaligned workspace TACO_ERR_ARG, stale split-bf16 planes (a switch without a
+ * taco_train_refresh) TACO_ERR_STATE, T_in > 2048 (ATT_MAXT) and attention sizes the training kernels do not serve TACO_ERR_UNSUPPORTED, too small a workspace
+ * TACO_ERR_STATE; a host-only trainer (taco_debug_train_create_host) that passes them all TACO_ERR_STATE.
+ * paths (nullable) receives which engine each of the two loops ran on, OR-ed in where it is launched:
+ *   bit  0 / 1   forward: ONE persistent launch (k_decoder_xcd<RG, true>) / one launch per stage
+ *   bit  2 / 3   BPTT: ONE persistent launch (k_decoder_bwd_xcd<RG>) / one launch per stage
+ *   bits 4-7     rows per group (1, 2, 4 or 8) of the persistent forward, 0 when it did not run
+ *   bits 8-11    rows per group of the persistent BPTT, 0 when it did not run
+ *   bit 12 / 13  exchange protocol of each persistent launch of the call: XCD-local plain stores / write-through -- what the census of the launch found
+ *                (taco_debug_decoder_info out16[0] and [9]).  To read them the hook waits for the stream when `paths` is given and a persistent launch ran. */
+size_t taco_train_debug_decoder_workspace_bytes(const taco_train* t, int B, int T_in, int n);
+int taco_train_debug_decoder(taco_train* t, void* hip_stream, float* d_params, float* d_grads, const float* d_enc_out, const float* d_teacher,
+                             const float* d_dmel, const float* d_att_init, const float* const* d_dec_init, const float* d_spk_emb, int B, int T_in, int n,
+                             float* d_mel, float* d_alignments, float* d_denc, float* d_datt_init, float* const* d_ddec_init, float* d_dspk_emb,
+                             void* d_ws, size_t ws_bytes, uint32_t* paths);
+
+/* Test hook: a trainer that stays on the host -- its shadow model is packed and never uploaded, no device is touched.  It serves the argument and state
+ * checks of taco_train_debug_decoder, which come before its first HIP call, on a machine without a GPU; nothing may be launched on it (its split-bf16
+ * planes count as stale until taco_train_set_exact_gemm with on = 1 selects the engines that need none).  Freed by taco_train_destroy. */
+int taco_debug_train_create_host(const taco_hparams* hp, taco_train** out);
+
 /* Test hook: which kernel the training step gives a weight gradient, and how it slices the rows -- wgrad_plan / wgrad_bank_plan of
  * csrc/taco_train.h, pure host functions: no handle, no device.  Inputs: the trainer's switches (wgrad_bf3: 0 = exact-fp32 weight
  * gradients are on; wgrad_planes: the mode of taco_train_set_wgrad_planes), whether the deterministic scratch exists and its floats, the

@@ -203,6 +203,7 @@ struct StepState {
   uint4* wps = nullptr; size_t wps_cap = 0;      // bf16 planes of the weight gradients' operands (taco_wgrad_planes.h); null: that path is off
   int planes_problems = 0;                       // weight gradients of this step that were computed from pre-split planes so far
   unsigned paths = 0;                            // CBHG_PATH_* bits: which branch each dispatch of a CBHG took, OR-ed in where it is taken (taco_train_debug_cbhg)
+  unsigned dec_paths = 0;                        // DEC_PATH_* bits: which engine ran the decoder loop and its BPTT, OR-ed in where each is launched (taco_train_debug_decoder)
   WgBatch wgb;
 };
 // The word of taco_train_debug_cbhg (include/taco_debug.h documents the layout): one bit per form of every two-way dispatch of
@@ -218,6 +219,14 @@ enum : unsigned {
   CBHG_PATH_SCAN_FWD_SHIFT = 16, CBHG_PATH_SCAN_BWD_SHIFT = 20                 // four bits each: ScanKernel of the forward launch; CBHG_SCAN_BWD_* of the backward one
 };
 enum { CBHG_SCAN_BWD_ROWS = 1, CBHG_SCAN_BWD_RESB = 2, CBHG_SCAN_BWD_DUO = 3, CBHG_SCAN_BWD_OCT = 4 };
+// The word of taco_train_debug_decoder (include/taco_debug.h): set where decoder_forward_train / decoder_backward launch, never recomputed from the plan.
+// The two protocol bits are the hook's: it reads them back from the census words of the launches (taco_debug_decoder_info's) once they have run.
+enum : unsigned {
+  DEC_PATH_FWD_PERSISTENT = 1u << 0, DEC_PATH_FWD_STAGES = 1u << 1,            // k_decoder_xcd<RG, true> | one launch per stage
+  DEC_PATH_BWD_PERSISTENT = 1u << 2, DEC_PATH_BWD_STAGES = 1u << 3,            // k_decoder_bwd_xcd<RG> | one launch per stage
+  DEC_PATH_FWD_RG_SHIFT = 4, DEC_PATH_BWD_RG_SHIFT = 8,                        // four bits each: rows per group (1, 2, 4, 8) of the persistent launch
+  DEC_PATH_XCD_LOCAL = 1u << 12, DEC_PATH_WRITE_THROUGH = 1u << 13             // a persistent launch of the call exchanged through XCD-local stores | write-through
+};
 
 struct TrainCtx {
   const taco_train* t; hipStream_t st; float* P; float* G;    // flat parameters (moving statistics are updated in place) and gradients
@@ -951,6 +960,25 @@ static int gru_cell_train(const taco_model* m, hipStream_t st, const GruDec& g, 
   TRY(run_skinny(st, B, &jb, 1, EPI_GRU_CAND));
   return 0;
 }
+// What the training kernels of the decoder serve, asked before anything is launched (the step, and taco_train_debug_decoder ahead of its first HIP call)
+static int decoder_fwd_check(const taco_model* m, int T_in) {
+  const taco_hparams& hp = m->hp;
+  const int D = 2 * hp.enc_rnn_size, As = hp.attention_state_size, A = hp.attention_size;
+  if (T_in > ATT_MAXT) return fail(TACO_ERR_UNSUPPORTED, "T_in %d > %d", T_in, ATT_MAXT);
+  if (!((A % 4 == 0) && A <= ATT_MAXT && A / 4 <= 64 * ATT_NW) || (D % 4) || A > 1024 || D > 1024 || As > 1024)
+    return fail(TACO_ERR_UNSUPPORTED, "attention sizes not supported by the training kernels");
+  return 0;
+}
+static size_t attention_bwd_lds(const taco_model* m, int T_in) {
+  const int D = 2 * m->hp.enc_rnn_size, A = m->hp.attention_size;
+  return (size_t)(2 * ((A + 3) & ~3) + ((D + 3) & ~3) + 5 * ((T_in + 3) & ~3) + ATB_NW * 256) * sizeof(float);
+}
+static int decoder_bwd_check(const taco_model* m, int T_in) {
+  const taco_hparams& hp = m->hp;
+  if (attention_bwd_lds(m, T_in) > 160 * 1024 || (hp.attention_state_size % 4) || ((2 * hp.enc_rnn_size) % 4) || (hp.attention_size % 4))
+    return fail(TACO_ERR_UNSUPPORTED, "attention sizes not supported by the backward kernel");
+  return 0;
+}
 static int decoder_forward_train(const TrainCtx& x, const float* enc_out, int B, int T_in, int n, const float* teach, float* mel,
                                  float* align_hist, const DecTape& w, bool feed_back, const float* att_init = nullptr,
                                  const float* const* dec_init = nullptr, const float* spk_emb = nullptr) {
@@ -958,9 +986,7 @@ static int decoder_forward_train(const TrainCtx& x, const float* enc_out, int B,
   const taco_hparams& hp = m->hp;
   const int D = 2 * hp.enc_rnn_size, As = hp.attention_state_size, Hd = hp.dec_rnn_size, A = hp.attention_size;
   const int Mm = hp.num_mels, rM = Mm * hp.reduction_factor, L = hp.dec_layer_num, np = hp.dec_prenet_n;
-  if (T_in > ATT_MAXT) return fail(TACO_ERR_UNSUPPORTED, "T_in %d > %d", T_in, ATT_MAXT);
-  if (!((A % 4 == 0) && A <= ATT_MAXT && A / 4 <= 64 * ATT_NW) || (D % 4) || A > 1024 || D > 1024 || As > 1024)
-    return fail(TACO_ERR_UNSUPPORTED, "attention sizes not supported by the training kernels");
+  TRY(decoder_fwd_check(m, T_in));
   { GemmCall g; g.x = enc_out; g.ldx = D; g.M = B * T_in; g.out = w.keys; g.ldo = A; TRY(run_gemm(m, st, &m->memory_layer, 1, false, g)); }
   const int Wz = std::max(std::max(Mm, As), std::max(Hd, D));
   hipLaunchKernelGGL(k_copy2d, EWGRID((size_t)B * Wz), 0, st, (const float*)nullptr, 0, w.zero, Wz, B, Wz);
@@ -983,9 +1009,11 @@ static int decoder_forward_train(const TrainCtx& x, const float* enc_out, int B,
     DxArgs ta; memset(&ta, 0, sizeof ta);
     ta.teacher = feed_back ? nullptr : teach; ta.own_fb = feed_back ? 1 : 0; ta.tape = w.tape256; ta.tstride = w.tstride; ta.tp_p2 = w.pz[np - 1]; ta.ld_p2 = Pz; ta.tp_ctx = w.ctx; ta.ld_ctx = Dc;
     ta.tp_e = w.g_e; ta.tp_alpha = w.alpha;
+    x.s->dec_paths |= DEC_PATH_FWD_PERSISTENT | (unsigned)dp.rg << DEC_PATH_FWD_RG_SHIFT;
     return dx_launch(m, st, dp, enc_out, SpkSel(), spk_emb, nullptr, B, T_in, n, nullptr, mel, align_hist, nullptr, 0, w.keys, w.nz, w.dx, w.rowbias,
                      att_init, dec_init ? dec_init[0] : nullptr, dec_init ? dec_init[1] : nullptr, &ta);
   }
+  x.s->dec_paths |= DEC_PATH_FWD_STAGES;
   for (int t = 0; t < n; ++t) {
     // helpers.py:44,66,70-72: previous teacher frame; rnn_decoder_test_mode (:63-64): last of the r frames the decoder just emitted
     const float* frame = (t == 0) ? w.zero : (feed_back ? mel + (size_t)(t - 1) * rM + (rM - Mm) : teach + (size_t)(t - 1) * Mm);
@@ -1085,8 +1113,8 @@ static int decoder_backward(const TrainCtx& x, const float* enc_out, int B, int 
     HIPCHK(zb.add(w.dhA, (size_t)B * As * sizeof(float)));
     for (int i = 0; i < L; ++i) HIPCHK(zb.add(w.dh[i], (size_t)B * Hd * sizeof(float)));
     HIPCHK(zb.run()); }
-  const size_t attn_lds = (size_t)(2 * ((A + 3) & ~3) + ((D + 3) & ~3) + 5 * ((T_in + 3) & ~3) + ATB_NW * 256) * sizeof(float);
-  if (attn_lds > 160 * 1024 || (As % 4) || (D % 4) || (A % 4)) return fail(TACO_ERR_UNSUPPORTED, "attention sizes not supported by the backward kernel");
+  const size_t attn_lds = attention_bwd_lds(m, T_in);
+  TRY(decoder_bwd_check(m, T_in));
   // the whole loop as ONE persistent launch (k_decoder_bwd_xcd, taco_decoder_bwd_xcd.h) when the forward left its tape in that
   // kernel's layout; the launch-per-stage loop below is the general path (other widths, 'simple', more than 64 rows)
   const DecPlan bp = decoder_plan(m, B, T_in, n, DEC_TRAIN_BWD);
@@ -1104,6 +1132,7 @@ static int decoder_backward(const TrainCtx& x, const float* enc_out, int B, int 
     a.g_dcpA = w.g_dcpA; a.g_dgpA = w.g_dgpA; a.g_dz1 = w.g_dz[0]; a.g_dz2 = w.g_dz[1]; a.g_dq = w.g_dq; a.g_de = w.g_de; a.g_dctx = w.g_dctx;
     a.d_att_init = d_att_init; a.d_h10 = d_dec_init ? d_dec_init[0] : nullptr; a.d_h20 = d_dec_init ? d_dec_init[1] : nullptr;
     a.dsb_acc = w.dsb_acc;
+    x.s->dec_paths |= DEC_PATH_BWD_PERSISTENT | (unsigned)bp.rg << DEC_PATH_BWD_RG_SHIFT;
     TRY(dbx_launch(m, st, bp, a, B, T_in, n, w.dx));
     if (S) {
       // 'simple': d speaker embedding = sum over steps of [d o0 . Wcc^T]_spk + [d c_pre(att) . Wc^T + d gates(att) . Wg^T]_spk.  Linear in the
@@ -1120,6 +1149,7 @@ static int decoder_backward(const TrainCtx& x, const float* enc_out, int B, int 
       HIPCHK(hipGetLastError());
     }
   }
+  if (!persistent) x.s->dec_paths |= DEC_PATH_BWD_STAGES;
   for (int t = n - 1; t >= 0 && !persistent; --t) {
     const size_t oh = (size_t)t * Hd, oa = (size_t)t * As;
     { SkJob j = sk_T(m, tp.frame_T, dmel + (size_t)t * rM, n * rM, w.do_[L], Hd); TRY(run_skinny(st, B, &j, 1)); }

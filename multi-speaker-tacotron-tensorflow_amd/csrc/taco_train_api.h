@@ -206,6 +206,99 @@ int taco_train_debug_cbhg(taco_train* t, void* hip_stream, int which, float* d_p
   if (paths) *paths = s.paths;
   return rc;
 }
+// Test hook: the decoder of the trainer alone -- decoder_forward_train (teacher forced, feed_back = false), then decoder_backward -- on caller data, as the
+// step calls them: the same TrainCtx and StepState (deterministic scratch, plane scratch sized as the step's), the tape of carve_dec_tape, the trainer's
+// current switches.  The scope's parameter gradients (decoder/*, attention/*) are ADDED into d_grads at their taco_train_param_offset; nothing else of
+// d_grads is written.  Every refusal below comes before the first HIP call.
+struct DecDebugWs { DecTape tape; float* detscr; uint4* wpscr; size_t wps_uint4; };
+static void carve_dec_debug(Carver& cv, const taco_train* t, int B, int T_in, int n, DecDebugWs& w) {
+  carve_dec_tape(cv, t->sm, B, T_in, n, w.tape);
+  w.detscr = cv.f(t->deterministic ? DET_SCRATCH_FLOATS : 1);
+  w.wps_uint4 = wps_scratch_uint4(t, std::max((size_t)B * T_in, (size_t)B * n * t->sm->hp.reduction_factor));
+  w.wpscr = (uint4*)cv.raw(w.wps_uint4 * sizeof(uint4));
+}
+size_t taco_train_debug_decoder_workspace_bytes(const taco_train* t, int B, int T_in, int n) {
+  if (!t || B <= 0 || T_in <= 0 || n <= 0) return 0;
+  Carver cv(nullptr, 0);
+  DecDebugWs w; carve_dec_debug(cv, t, B, T_in, n, w);
+  return cv.off;
+}
+int taco_train_debug_decoder(taco_train* t, void* hip_stream, float* d_params, float* d_grads, const float* d_enc_out, const float* d_teacher,
+                             const float* d_dmel, const float* d_att_init, const float* const* d_dec_init, const float* d_spk_emb, int B, int T_in, int n,
+                             float* d_mel, float* d_alignments, float* d_denc, float* d_datt_init, float* const* d_ddec_init, float* d_dspk_emb,
+                             void* d_ws, size_t ws_bytes, uint32_t* paths) {
+  if (!t || !d_params || !d_grads || !d_enc_out || !d_teacher || !d_dmel || !d_mel || !d_alignments || !d_denc || !d_ws) return fail(TACO_ERR_ARG, "null argument");
+  taco_model* m = t->sm;
+  const taco_hparams& hp = m->hp;
+  const int L = hp.dec_layer_num, S = simple_S(m);
+  if (L > 4) return fail(TACO_ERR_UNSUPPORTED, "%d decoder layers", L);
+  const float* dec_init[4] = {nullptr, nullptr, nullptr, nullptr}; float* ddec_init[4] = {nullptr, nullptr, nullptr, nullptr};
+  bool any_init = false;
+  for (int i = 0; i < L; ++i) {
+    dec_init[i] = d_dec_init ? d_dec_init[i] : nullptr; ddec_init[i] = d_ddec_init ? d_ddec_init[i] : nullptr;
+    any_init = any_init || dec_init[i];
+    if (ddec_init[i] && !dec_init[i]) return fail(TACO_ERR_ARG, "a gradient output without its input (initial state of decoder layer %d)", i + 1);
+  }
+  if ((d_datt_init && !d_att_init) || (d_dspk_emb && !d_spk_emb)) return fail(TACO_ERR_ARG, "a gradient output without its input");
+  if ((d_att_init || any_init) && !is_deepvoice(m)) return fail(TACO_ERR_ARG, "initial states are model type deepvoice's");
+  if (S && !(d_spk_emb && d_dspk_emb)) return fail(TACO_ERR_ARG, "model type simple: the speaker rows and their gradient buffer are required");
+  if (!S && d_spk_emb) return fail(TACO_ERR_ARG, "speaker rows enter the decoder of model type simple only");
+  TRY(check_common(m, B, T_in));
+  if (n <= 0) return fail(TACO_ERR_ARG, "bad number of decoder steps %d", n);
+  if (n > hp.max_iters) return fail(TACO_ERR_SHAPE, "%d decoder steps exceed max_iters %d", n, hp.max_iters);
+  if (!al16h(d_ws)) return fail(TACO_ERR_ARG, "workspace %p is not 16-byte aligned", d_ws);
+  if ((m->bf3 || m->bf3x6 || t->dgrad_bf3) && !t->bf3_current) return fail(TACO_ERR_STATE, "taco_train_set_exact_gemm(0) needs a taco_train_refresh before the next step (the split-bf16 weight planes are stale)");
+  TRY(decoder_fwd_check(m, T_in));
+  TRY(decoder_bwd_check(m, T_in));
+  Carver cv(d_ws, ws_bytes);
+  DecDebugWs w; carve_dec_debug(cv, t, B, T_in, n, w);
+  if (!cv.ok()) return fail(TACO_ERR_STATE, "workspace too small: need %zu bytes, have %zu", cv.off, ws_bytes);
+  if (!m->d_err) return fail(TACO_ERR_STATE, "a host-only trainer (taco_debug_train_create_host) cannot run");
+  HIPCHK(hipSetDevice(m->device));
+  hipStream_t st = (hipStream_t)hip_stream;
+  StepState s;
+  if (t->deterministic) { s.det = w.detscr; s.det_cap = DET_SCRATCH_FLOATS; }
+  if (t->wgrad_planes) { s.wps = w.wpscr; s.wps_cap = w.wps_uint4; }
+  TrainCtx x{t, st, d_params, d_grads, false, &s};
+  const bool inits = d_att_init || any_init;
+  const auto run = [&]() -> int {
+    TRY(decoder_forward_train(x, d_enc_out, B, T_in, n, d_teacher, d_mel, d_alignments, w.tape, false, d_att_init, inits ? dec_init : nullptr, d_spk_emb));
+    if (S) HIPCHK(zero_async(d_dspk_emb, (size_t)B * S * sizeof(float), st));      // the step zero-fills it ahead of the head's share
+    TRY(decoder_backward(x, d_enc_out, B, T_in, n, d_teacher, d_dmel, d_denc, w.tape, d_att_init, inits ? dec_init : nullptr, d_datt_init,
+                         inits ? ddec_init : nullptr, d_dspk_emb));
+    return 0;
+  };
+  int rc = run();
+  t->planes_problems = s.planes_problems;
+  if (paths) {
+    if (rc == 0 && (s.dec_paths & (DEC_PATH_FWD_PERSISTENT | DEC_PATH_BWD_PERSISTENT))) {      // the census words of the launches, once they have run
+      unsigned fw = 0, bw = 0;
+      HIPCHK(hipStreamSynchronize(st));
+      HIPCHK(hipMemcpy(&fw, m->d_err + 8, sizeof fw, hipMemcpyDeviceToHost));
+      HIPCHK(hipMemcpy(&bw, m->d_err + 40, sizeof bw, hipMemcpyDeviceToHost));
+      for (const unsigned v : {(s.dec_paths & DEC_PATH_FWD_PERSISTENT) ? fw : 0u, (s.dec_paths & DEC_PATH_BWD_PERSISTENT) ? bw : 0u})
+        s.dec_paths |= v == 1 ? DEC_PATH_XCD_LOCAL : v == 2 ? DEC_PATH_WRITE_THROUGH : 0u;
+    }
+    *paths = s.dec_paths;
+  }
+  return rc;
+}
+// Test hook: a trainer that stays on the host -- the shadow model is packed (model_pack_host) and never uploaded, no device is touched.  It serves the
+// argument and state checks of the taco_train_debug_* hooks, which come before their first HIP call; nothing may be launched on it.
+int taco_debug_train_create_host(const taco_hparams* hp, taco_train** out) {
+  if (!hp || !out) return fail(TACO_ERR_ARG, "null argument");
+  taco_train* t = new taco_train();
+  int rc = taco_model_create(hp, 0, &t->sm);
+  if (rc != 0) { delete t; return rc; }
+  rc = train_shadow_weights(t);
+  if (rc == 0) rc = model_pack_host(t->sm);
+  if (rc != 0) { taco_train_destroy(t); return rc; }
+  taco_model* sm = t->sm;
+  sm->raw.clear(); sm->finalized = true;
+  sm->bf3 = 0; sm->bf3x6 = 1; t->dgrad_bf3 = 1; t->want_bf3_planes = true;      // the switches of taco_train_create; the planes were never generated
+  *out = t;
+  return 0;
+}
 // Test hook: what wgrad_plan (nw = 0) / wgrad_bank_plan (nw > 0: a conv bank of widths 1 .. nw, N = channels per width) decide -- no handle, no device.
 int taco_debug_wgrad_plan(int wgrad_bf3, int wgrad_planes, int deterministic, long long det_floats, long long planes_uint4, int region_open,
                           int M, int T, int K, int N, int kw, int padl, int gather, int ygather, int nw, int* out8) {

@@ -104,29 +104,12 @@ def monotonic_closed_form(p, prev):
     return p * cp * torch.cumsum(prev / torch.clamp(cp, 1e-10, 1.0), 1)
 
 
-def forward(w, hp, ids, lengths, speaker_id=None, num_speakers=1, n_steps=None, manual=None, training=False,
-            teacher_frames=None, as_numpy=True):
-    ids = torch.as_tensor(ids, dtype=torch.long)
-    B, T_in = ids.shape
-    r, M = hp.reduction_factor, hp.num_mels
-    n = hp.max_iters if n_steps is None else n_steps
-    x = _t(w, "embedding")[ids]
-    spk = before = enc_init = att_init = dec_inits = None
-    if num_speakers > 1:
-        sid = torch.as_tensor(speaker_id, dtype=torch.long)
-        if hp.speaker_embedding_size != 1:
-            spk = _t(w, "speaker_embedding")[sid]
-        if hp.model_type == "deepvoice":
-            names = ["before_highway", "encoder_rnn_init", "attention_rnn_init"] + \
-                    ["decoder_rnn_init_%d" % (i + 1) for i in range(hp.dec_layer_num)]
-            vs = [(_t(w, "spk/%s/table" % nm)[sid] if hp.speaker_embedding_size == 1 else F.softsign(dense(spk, w, "spk/" + nm)))
-                  for nm in names]
-            before, enc_init, att_init, dec_inits = vs[0], vs[1], vs[2], vs[3:]
-            spk = None
-    for i in range(len(hp.enc_prenet_sizes)):
-        x = F.relu(dense(x, w, "prenet/dense_%d" % (i + 1)))
-    enc = cbhg(x, lengths, w, "encoder_cbhg", hp.enc_bank_size, hp.enc_highway_depth, len(hp.enc_proj_sizes), before, enc_init,
-               training)
+def decoder(w, hp, enc, n, spk=None, att_init=None, dec_inits=None, manual=None, training=False, teacher_frames=None):
+    """The decoder loop alone (rnn_wrappers.py:218-341,367-415; helpers.py:9-67): attention memory `enc` [B, T_in, D] -> (y [B, n, r*num_mels],
+    alignments [B, T_in, n]).  spk [B, S]: the speaker rows of model type 'simple'; att_init / dec_inits: the initial states of deepvoice;
+    teacher_frames [B, n, num_mels]: frame t is fed to step t + 1 (else the step's own last frame is)."""
+    B, T_in = enc.shape[0], enc.shape[1]
+    M = hp.num_mels
     keys = dense(enc, w, "attention/memory_layer", bias=False)
     v = _t(w, "attention/attention_v")
     h_att = torch.zeros(B, hp.attention_state_size, dtype=DT) if att_init is None else att_init.clone()
@@ -168,15 +151,42 @@ def forward(w, hp, ids, lengths, speaker_id=None, num_speakers=1, n_steps=None, 
         frame = y[:, -M:]
         if teacher_frames is not None:
             frame = torch.as_tensor(teacher_frames, dtype=DT)[:, t]
-    mel = torch.stack(ys, 1).reshape(B, n * r, M)
+    return torch.stack(ys, 1), torch.stack(als, 2)
+
+
+def forward(w, hp, ids, lengths, speaker_id=None, num_speakers=1, n_steps=None, manual=None, training=False,
+            teacher_frames=None, as_numpy=True):
+    ids = torch.as_tensor(ids, dtype=torch.long)
+    B, T_in = ids.shape
+    r, M = hp.reduction_factor, hp.num_mels
+    n = hp.max_iters if n_steps is None else n_steps
+    x = _t(w, "embedding")[ids]
+    spk = before = enc_init = att_init = dec_inits = None
+    if num_speakers > 1:
+        sid = torch.as_tensor(speaker_id, dtype=torch.long)
+        if hp.speaker_embedding_size != 1:
+            spk = _t(w, "speaker_embedding")[sid]
+        if hp.model_type == "deepvoice":
+            names = ["before_highway", "encoder_rnn_init", "attention_rnn_init"] + \
+                    ["decoder_rnn_init_%d" % (i + 1) for i in range(hp.dec_layer_num)]
+            vs = [(_t(w, "spk/%s/table" % nm)[sid] if hp.speaker_embedding_size == 1 else F.softsign(dense(spk, w, "spk/" + nm)))
+                  for nm in names]
+            before, enc_init, att_init, dec_inits = vs[0], vs[1], vs[2], vs[3:]
+            spk = None
+    for i in range(len(hp.enc_prenet_sizes)):
+        x = F.relu(dense(x, w, "prenet/dense_%d" % (i + 1)))
+    enc = cbhg(x, lengths, w, "encoder_cbhg", hp.enc_bank_size, hp.enc_highway_depth, len(hp.enc_proj_sizes), before, enc_init,
+               training)
+    y, alignments = decoder(w, hp, enc, n, spk, att_init, dec_inits, manual, training, teacher_frames)
+    mel = y.reshape(B, n * r, M)
     post = cbhg(mel, None, w, "post_cbhg", hp.post_bank_size, hp.post_highway_depth, len(hp.post_proj_sizes),
                 training=training)
     if spk is not None:
         post = torch.cat([spk[:, None].expand(B, post.shape[1], spk.shape[1]), post], -1)
     linear = dense(post, w, "linear")
     if not as_numpy:
-        return dict(mel=mel, linear=linear, alignments=torch.stack(als, 2))
-    return dict(mel=mel.detach().numpy(), linear=linear.detach().numpy(), alignments=torch.stack(als, 2).detach().numpy())
+        return dict(mel=mel, linear=linear, alignments=alignments)
+    return dict(mel=mel.detach().numpy(), linear=linear.detach().numpy(), alignments=alignments.detach().numpy())
 
 
 def add_loss(mel_out, mel_tgt, lin_out, lin_tgt, coeff, prioritize_loss=False, sample_rate=24000):
