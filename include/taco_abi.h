@@ -771,6 +771,43 @@ int taco_text_matches(void* hip_stream, const int32_t* d_chars, long long n_char
 int taco_text_best_two(void* hip_stream, const int32_t* d_matches, const int32_t* d_pairs, const int32_t* d_offsets, int n_texts,
                        const int32_t* d_group_offsets /* [n_groups + 1] into the pairs */, int n_groups, int32_t* d_best /* [n_groups, 4] */);
 
+/* ---- dynamic time warping of two feature sequences (not in the reference: the distance of a free-running decoder's mel frames from
+ * their targets with the drift in time taken out, where tacotron.py:274-302 compares frame t with frame t) ----
+ * Pair p warps d_a[p, :n, :] onto d_b[p, :m, :] (fp32 rectangles [B, Ta, D] and [B, Tb, D]); n = d_len_a[p] clamped to [1, Ta] and
+ * m = d_len_b[p] clamped to [1, Tb] on the device, a NULL length array meaning full rows.  Nothing past the lengths is read: slack may
+ * hold anything, NaN included.
+ * Frame cost c(i, j), summed over d ascending in fp32: cost_kind 0 = (1/D) * sum_d |a_id - b_jd| (the per-frame term of the mel L1 of
+ * tacotron.py:278), cost_kind 1 = sqrt(sum_d (a_id - b_jd)^2).
+ * Recurrence (symmetric steps, diagonal weight 2, so the normaliser does not depend on the path):
+ *   G(0,0) = 2 c(0,0);  G(i,0) = G(i-1,0) + c(i,0);  G(0,j) = G(0,j-1) + c(0,j);
+ *   G(i,j) = min(G(i-1,j-1) + 2 c(i,j), G(i-1,j) + c(i,j), G(i,j-1) + c(i,j));   d_total[p] = G(n-1,m-1);  d_dist[p] = total / (n + m).
+ * For n == m, dist <= the mean of c(i,i).  d_dir [B, Ta, Tb] (nullable) receives for every cell with i < n and j < m where its value
+ * came from: 0 = (i-1,j-1), 1 = (i-1,j), 2 = (i,j-1); border cells their only predecessor, cell (0,0) 0; on ties the diagonal is
+ * tried first, then (i-1,j), then (i,j-1), a later candidate winning under strict '<' only.  Cells outside are left untouched.
+ * If any used element of a pair is NaN or infinite, that pair's total and dist are NaN (a flag carries it, not the minimum); other
+ * pairs are not affected and the call ends normally.
+ * No Ta x Tb memory exists unless d_dir is given: costs are formed on the fly, G lives in registers (csrc/taco_dtw.h).  One fixed
+ * summation order and no atomics: two calls give the same bits.  The call launches on hip_stream only: no allocation, no
+ * synchronisation, no read-back; safe under stream capture.  Ta, Tb and B have no cap; D above 128 is refused (TACO_ERR_UNSUPPORTED:
+ * a column's features are registers).  d_workspace: taco_dtw_workspace_bytes(B, Ta, Tb, D) bytes, which is 0 (and the pointer may
+ * then be NULL) while Tb fits one strip of columns.
+ * Checked before any HIP call: a null d_a, d_b or d_dist, or a null workspace where the query is not 0, B, Ta, Tb or D < 1, an unknown
+ * cost_kind, an output (d_dist, d_total, d_dir, the workspace) that shares a byte with an input or another output -> TACO_ERR_ARG;
+ * D > 128 -> TACO_ERR_UNSUPPORTED; a workspace below the query -> TACO_ERR_STATE.  Byte counts are formed in 128 bits.
+ *
+ * taco_dtw_path: the warping path of every pair from d_dir, ascending from (0,0) to (n-1,m-1): d_path [B, Ta+Tb-1, 2] int32 rows
+ * (i, j), entries from d_path_len[p] on set to -1.  Whatever bytes d_dir holds, the walk ends within n + m - 1 entries inside the
+ * rectangle: a byte above 2 counts as 0, in row 0 the move is to (0,j-1), in column 0 to (i-1,0); garbage gives a wrong path, nothing
+ * worse.  Same stream rules; TACO_ERR_ARG for a null d_dir, d_path or d_path_len, B, Ta or Tb < 1, or an output overlapping an input or
+ * the other output. */
+size_t taco_dtw_workspace_bytes(int B, int Ta, int Tb, int D);
+int taco_dtw(void* hip_stream, const float* d_a, const int32_t* d_len_a, const float* d_b, const int32_t* d_len_b,
+             int B, int Ta, int Tb, int D, int cost_kind,
+             float* d_dist /* [B] */, float* d_total /* [B], nullable */, uint8_t* d_dir /* [B,Ta,Tb], nullable */,
+             void* d_workspace, size_t workspace_bytes);
+int taco_dtw_path(void* hip_stream, const uint8_t* d_dir, const int32_t* d_len_a, const int32_t* d_len_b,
+                  int B, int Ta, int Tb, int32_t* d_path /* [B,Ta+Tb-1,2] */, int32_t* d_path_len /* [B] */);
+
 #ifdef __cplusplus
 }
 #endif

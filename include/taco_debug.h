@@ -233,6 +233,13 @@ int taco_debug_sumsq_partial(void* hip_stream, const float* d_grads, size_t n, v
 int taco_debug_text_matches_cols(void* hip_stream, const int32_t* d_chars, long long n_chars, const int32_t* d_offsets, int n_texts,
                                  const int32_t* d_pairs, int n_pairs, int32_t* d_matches, int cols);
 
+/* Test hook: the sizes at which k_dtw (csrc/taco_dtw.h) changes path, so that tests/test_gpu_dtw.py can sit on either side of each.  The first n (at most 6)
+ * values are written, so a caller's buffer sets what it gets: out[0] =
+ * columns of a strip (Tb beyond it runs as further strips through the workspace), [1] = rows of A staged at a time, [2] = the largest D,
+ * [3] = the step D is rounded up to, [4] = columns of one wave (its last lane hands over through LDS), [5] = rows of the LDS ring (where a
+ * row's slot wraps).  Host only; a null pointer or n < 0 is TACO_ERR_ARG. */
+int taco_debug_dtw_info(int* out, int n);
+
 #ifdef __cplusplus
 }
 #endif

@@ -240,6 +240,10 @@ PROTOTYPES = {
     "taco_text_matches": (_I, [_P, _P, C.c_longlong, _P, _I, _P, _I, _P]),
     "taco_text_best_two": (_I, [_P, _P, _P, _P, _I, _P, _I, _P]),
     "taco_debug_text_matches_cols": (_I, [_P, _P, C.c_longlong, _P, _I, _P, _I, _P, _I]),
+    "taco_dtw_workspace_bytes": (_S, [_I, _I, _I, _I]),
+    "taco_dtw": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _P, _S]),
+    "taco_dtw_path": (_I, [_P, _P, _P, _P, _I, _I, _I, _P, _P]),
+    "taco_debug_dtw_info": (_I, [C.POINTER(_I), _I]),
 }
 
 _lib = None

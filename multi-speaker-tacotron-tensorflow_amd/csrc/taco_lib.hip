@@ -1690,6 +1690,7 @@ static int forward_enqueue(taco_model* m, hipStream_t st, const int32_t* ids, co
 #include "taco_resample.h"
 #include "taco_feed.h"
 #include "taco_align.h"
+#include "taco_dtw.h"
 
 extern "C" {
 
@@ -2461,5 +2462,6 @@ int taco_adam_step_f32(void* hip_stream, float* d_params, const float* d_grads, 
 #include "taco_audio_api.h"
 #include "taco_resample_api.h"
 #include "taco_align_api.h"
+#include "taco_dtw_api.h"
 
 }  // extern "C"

@@ -550,6 +550,20 @@ class Tacotron(object):
             out['gap_test-train/loss_mel'], out['gap_test-train/loss_linear'], out['gap_test-train/loss'] = mel - mel2, lin - lin2, lwc - lwc2
         return out
 
+    def mel_dtw(self, target_lengths=None, output_lengths=None):
+        """The dynamic-time-warping distance of the mel outputs of the current feed from its mel targets, per row, [B] on the device:
+        metrics.dtw_distance(mel_outputs, mel_targets, output_lengths, target_lengths, 'l1') on the tensors the forward left there.  The
+        frame cost is the per-frame term of add_loss's mel L1 (tacotron.py:278), so with equal lengths the value is at most the row's
+        un-weighted mel L1; for the test model (rnn_decoder_test_mode, train.py:158-166), whose frames drift in time against the
+        recording, it is the number to log beside 'test/loss' -- a caller adds 'test/mel_dtw' to its own summaries, add_stats stays the
+        reference's.  Lengths are in frames (None: all T_out)."""
+        from .metrics import dtw_distance
+        if getattr(self, "_trainer", None) is None or self.mel_targets is None:
+            raise RuntimeError("initialize(..., mel_targets, linear_targets) must be called first")
+        if self.mel_outputs is None:
+            raise _lib.TacoError(_lib.TACO_ERR_STATE, "mel_dtw needs the outputs of a feed: initialize(...) with inputs and targets first")
+        return dtw_distance(self.mel_outputs, self.mel_targets, output_lengths, target_lengths, "l1", device=self.device)
+
     def trained_weights(self):
         """Current parameters as a dict (tf.train.Saver.save of train.py:242-244 -> weights.save_weights)."""
         return self._trainer.get_weights()
