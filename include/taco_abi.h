@@ -808,6 +808,52 @@ int taco_dtw(void* hip_stream, const float* d_a, const int32_t* d_len_a, const f
 int taco_dtw_path(void* hip_stream, const uint8_t* d_dir, const int32_t* d_len_a, const int32_t* d_len_b,
                   int B, int Ta, int Tb, int32_t* d_path /* [B,Ta+Tb-1,2] */, int32_t* d_path_len /* [B] */);
 
+/* ---- pitch tracking: YIN F0 tracks, and F0 error statistics along a warping path (not in the reference, which is judged by ear; with
+ * the cepstral distortion above these are the objective numbers of a synthesiser: envelope, intonation, voicing) ----
+ * taco_f0_yin: the YIN estimator (de Cheveigne and Kawahara 2002, steps 2 to 5) per row of d_wav [B, L] (fp32) with that row's own sample
+ * count n = d_num_samples[b] clamped to [0, L] on the device, a NULL array meaning L.  This project's own definition, UNPINNED on any
+ * pitch-tracking package; tests/yin_reference.py restates it in NumPy.
+ *   tau_min = floor(sample_rate / fmax), tau_max = ceil(sample_rate / fmin) (formed in double from the fp32 arguments), W = window,
+ *   F = 1 + L / hop columns; row b owns the frames t < 1 + n / hop -- the grid of taco_spec_num_frames, so a path found on mel frames
+ *   indexes the F0 track directly.  For frame t:
+ *   1. samples: x~[k] for k = s0 .. s0 + W + tau_max, s0 = t * hop - (W + tau_max) / 2 (integer division); x~[k] = x[k] inside [0, n)
+ *      and 0 outside.  Nothing at or past n is read: the slack may hold anything, NaN included.
+ *   2. d(tau) = sum_{j < W} (x~[s0+j] - x~[s0+j+tau])^2 for tau = 0 .. tau_max + 1, in fp32: each difference rounded, its square added to
+ *      the running sum by one fmaf; the sum is formed directly (not as energies minus a correlation, which cancels), in one fixed order
+ *      of the kernel's own (csrc/taco_f0.h: blocks of j, then the blocks' sums).
+ *   3. S(tau) = sum_{k = 1 .. tau} d(k) (fp32, one fixed order); d'(0) = 1; d'(tau) = (d(tau) * tau) / S(tau), the product and the quotient
+ *      two separately rounded fp32 operations; d'(tau) = 1 where S(tau) == 0.
+ *   4. the lag: the smallest tau in [tau_min, tau_max] with d'(tau) < threshold; from there tau -> tau + 1 while tau + 1 <= tau_max and
+ *      d'(tau + 1) < d'(tau).  That is tau*, and the frame is voiced.  If no tau is below the threshold the frame is unvoiced and tau* is
+ *      the first argmin of d' over the range.
+ *   5. y0, y1, y2 = d'(tau* - 1), d'(tau*), d'(tau* + 1); q = (y0 - 2 * y1) + y2; delta = q > 0 ? clamp((0.5 * (y0 - y2)) / q, -0.5, 0.5)
+ *      : 0, every operation rounded on its own (nothing contracted); f0 = sample_rate / (tau* + delta) when voiced, exactly 0 when not.
+ *   Outputs: d_f0 [B, F]; d_aper [B, F] (nullable) = d'(tau*), voiced or not; d_lag [B, F] (nullable) = tau*, int32.  Columns past a
+ *   row's own frames receive exact zeros.  A frame that reads a NaN or an infinity gives NaN in d_f0 and d_aper and -1 in d_lag; other
+ *   frames are not affected.  (Silence: S == 0 everywhere, d' = 1, unvoiced, tau* = tau_min.)
+ * No atomics and one fixed summation order: two calls and a captured replay give the same bits.  Where every d, S and d * tau is an
+ * integer below 2^24 (integer samples in [-8, 8], window <= 256, tau_max <= 255) the sums are exact in any order and the outputs are
+ * bit-equal to the restatement's.
+ *
+ * taco_f0_path_stats: per pair p, over the entries k < d_path_len[p] (clamped to [0, path_cap]) of d_path [B, path_cap, 2] as
+ * taco_dtw_path writes it, with fa = d_f0_a[p, i] ([B, Fa]) and fb = d_f0_b[p, j] ([B, Fb]); a track value is voiced when it is > 0.
+ * Both voiced: c = 1200 * log2(fa / fb) (fp32), c^2 and a count are accumulated; exactly one voiced: a V/UV error is counted; an entry
+ * whose i or j lies outside [0, Fa) x [0, Fb) is skipped (-1 fill included); a NaN track value at a used entry makes that pair's sum
+ * NaN (the entry still counts as used).  d_stats [B, 4] fp32 = {sum c^2, entries voiced on both sides, V/UV errors, entries used}.
+ * One workgroup per pair, strided partial sums and one fixed tree: bit-reproducible.
+ *
+ * Both calls launch on hip_stream only: no allocation, no workspace, no synchronisation, no read-back; safe under stream capture.  The
+ * stream's device must be the current one (a plan above 64 KB of LDS -- a long frame or a long hop -- sets a kernel attribute there).
+ * Checked before any HIP call: a null required pointer; B, L, hop, window, Fa, Fb or path_cap < 1; sample_rate < 1; fmin <= 0 or
+ * fmax <= fmin; tau_min < 2; a threshold outside (0, 1]; an output that shares a byte with an input or another output -> TACO_ERR_ARG;
+ * a frame of window + tau_max + 2 floats above 8192 -> TACO_ERR_UNSUPPORTED (k_yin keeps a frame, its lag sums and their parts in the
+ * 144 KB of LDS it is built for; 24 kHz / 50 ms / 60 Hz needs 1602).  Byte counts are formed in 128 bits. */
+int taco_f0_yin(void* hip_stream, const float* d_wav, const int32_t* d_num_samples /* nullable */, int B, int L,
+                int sample_rate, int hop, int window, float fmin, float fmax, float threshold,
+                float* d_f0, float* d_aper /* nullable */, int32_t* d_lag /* nullable */);
+int taco_f0_path_stats(void* hip_stream, const float* d_f0_a, int Fa, const float* d_f0_b, int Fb,
+                       const int32_t* d_path, const int32_t* d_path_len, int B, int path_cap, float* d_stats);
+
 #ifdef __cplusplus
 }
 #endif

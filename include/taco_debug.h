@@ -240,6 +240,22 @@ int taco_debug_text_matches_cols(void* hip_stream, const int32_t* d_chars, long 
  * row's slot wraps).  Host only; a null pointer or n < 0 is TACO_ERR_ARG. */
 int taco_debug_dtw_info(int* out, int n);
 
+/* Test and timing hook: taco_f0_yin with the difference function formed the plain way, one lag per thread walking j over LDS (k_yin<true>,
+ * csrc/taco_f0.h), in place of the register-blocked form.  Arguments, results and errors are taco_f0_yin's; on inputs whose sums are exact
+ * (include/taco_abi.h) the bits are equal.  Used by tools/bench_f0.py and by one equality test only. */
+int taco_debug_f0_yin_plain(void* hip_stream, const float* d_wav, const int32_t* d_num_samples, int B, int L, int sample_rate, int hop, int window,
+                            float fmin, float fmax, float threshold, float* d_f0, float* d_aper, int32_t* d_lag);
+/* Test hook: the widths at which k_yin changes path, so that tests/test_gpu_f0.py can sit on either side of each.  The first n (at most 7) values
+ * are written: out[0] = lanes of a wave (the lags of the finishing pass are dealt over them), [1] = lags of a thread's block, [2] = values of
+ * j per register block, [3] = frames of one workgroup (they share one staged span), [4] = threads of a workgroup (lag blocks beyond them are
+ * further rounds; below them the j range is cut into parts), [5] = the largest frame (window + tau_max + 2) in floats, [6] = floats of
+ * LDS a workgroup may use.  Host only; a null pointer or n < 0 is TACO_ERR_ARG. */
+int taco_debug_f0_info(int* out, int n);
+/* Test hook: the layout k_yin would run (window, tau_max, hop) with: out[0..4] = lag blocks, parts of the j range, values of j per part,
+ * frames per workgroup (fewer than taco_debug_f0_info's [3] where that many frames' span does not fit the LDS), floats of LDS.  Host only;
+ * TACO_ERR_ARG for a null pointer, window or hop < 1, tau_max < 2 or a frame above the largest. */
+int taco_debug_f0_plan(int window, int tau_max, int hop, int* out);
+
 #ifdef __cplusplus
 }
 #endif

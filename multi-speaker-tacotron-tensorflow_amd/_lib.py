@@ -244,6 +244,11 @@ PROTOTYPES = {
     "taco_dtw": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _P, _S]),
     "taco_dtw_path": (_I, [_P, _P, _P, _P, _I, _I, _I, _P, _P]),
     "taco_debug_dtw_info": (_I, [C.POINTER(_I), _I]),
+    "taco_f0_yin": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, C.c_float, C.c_float, C.c_float, _P, _P, _P]),
+    "taco_f0_path_stats": (_I, [_P, _P, _I, _P, _I, _P, _P, _I, _I, _P]),
+    "taco_debug_f0_yin_plain": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, C.c_float, C.c_float, C.c_float, _P, _P, _P]),
+    "taco_debug_f0_info": (_I, [C.POINTER(_I), _I]),
+    "taco_debug_f0_plan": (_I, [_I, _I, _I, C.POINTER(_I)]),
 }
 
 _lib = None

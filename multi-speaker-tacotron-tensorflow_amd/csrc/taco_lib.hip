@@ -1691,6 +1691,7 @@ static int forward_enqueue(taco_model* m, hipStream_t st, const int32_t* ids, co
 #include "taco_feed.h"
 #include "taco_align.h"
 #include "taco_dtw.h"
+#include "taco_f0.h"
 
 extern "C" {
 
@@ -2463,5 +2464,6 @@ int taco_adam_step_f32(void* hip_stream, float* d_params, const float* d_grads, 
 #include "taco_resample_api.h"
 #include "taco_align_api.h"
 #include "taco_dtw_api.h"
+#include "taco_f0_api.h"
 
 }  // extern "C"

@@ -2,7 +2,11 @@
 (train.py:158-168) compares output frame t with target frame t, which for a decoder fed its own frames mostly measures the drift in
 time; people judge the dumped plots and wavs instead.  Dynamic time warping takes the drift out: the cost of the cheapest monotone
 alignment of the two sequences, normalised by their lengths (taco_dtw, csrc/taco_dtw.h; the definition is in include/taco_abi.h and,
-as float64 NumPy, in tests/dtw_reference.py)."""
+as float64 NumPy, in tests/dtw_reference.py).
+
+That distance, on cepstra, measures the spectral envelope.  The source is measured beside it: YIN F0 tracks of a waveform on the
+spectrogram's frame grid (f0_track: taco_f0_yin, csrc/taco_f0.h) and, along the warping path, the F0 RMSE in cents and the
+voiced/unvoiced error (f0_errors: taco_f0_path_stats); prosody_distance gives all three numbers for two waveform batches."""
 import ctypes as C
 import math
 
@@ -122,3 +126,162 @@ def mel_cepstral_distortion(mel_a, mel_b, len_a=None, len_b=None, hparams=None, 
     ca = mel_cepstra(mel_a, hparams, n_cepstra)
     cb = mel_cepstra(mel_b, hparams, n_cepstra)
     return dtw_distance(ca, cb, len_a, len_b, cost="l2") * mcd_constant()
+
+
+# ---- pitch: YIN F0 tracks, F0 RMSE and V/UV error along a warping path (taco_f0_yin, taco_f0_path_stats: csrc/taco_f0.h) ----
+_F0_BUFFERS = {}                 # (device, B, L, hop) -> f0, aper, lag of that shape;  (device, B, Fa, Fb, cap) -> stats
+_SPEC = {}                       # (device, the audio hparams' values) -> the audio.Spectrogram handle prosody_distance makes its mels with
+
+
+def framing(hparams=None):
+    """(sample_rate, hop, frame length in samples) as audio.c_audio_hparams reads them and the library's spectrogram frames with"""
+    from . import audio
+    from .hparams import hparams as default_hparams
+    hp = audio.c_audio_hparams(hparams if hparams is not None else default_hparams)
+    return int(hp.sample_rate), int(hp.frame_shift_ms / 1000.0 * hp.sample_rate), int(hp.frame_length_ms / 1000.0 * hp.sample_rate)
+
+
+def f0_track(wav, num_samples=None, hparams=None, fmin=60.0, fmax=500.0, threshold=0.1, window=None, return_aperiodicity=False,
+             return_lag=False, device=None):
+    """YIN pitch tracks of wav [B, L] (a device tensor, or an array, which is uploaded), row b using its first num_samples[b] samples
+    (int32 [B], clamped to [0, L] on the device and never read on the host; None: L).  hop and the default window (the frame length)
+    come from hparams as audio.c_audio_hparams reads them, so column t is the frame the spectrogram's column t is centred on:
+    F = 1 + L // hop columns, row b owning 1 + n_b // hop of them, exact zeros after.
+
+    This project's own definition, UNPINNED on any pitch-tracking package (include/taco_abi.h; tests/yin_reference.py is it in NumPy):
+    with tau_min = floor(sr / fmax), tau_max = ceil(sr / fmin), W = window and x~ the row, zero outside [0, n), frame t reads
+    x~[s0 .. s0 + W + tau_max], s0 = t * hop - (W + tau_max) // 2;
+        d(tau)  = sum_{j < W} (x~[s0 + j] - x~[s0 + j + tau])^2,           tau = 0 .. tau_max + 1
+        d'(tau) = d(tau) * tau / sum_{k = 1 .. tau} d(k),   d'(0) = 1, and 1 where the sum is 0
+        tau*    = the first tau in [tau_min, tau_max] with d'(tau) < threshold, walked on to tau + 1 while d' falls: voiced;
+                  no such tau: unvoiced, tau* = the first argmin of d' over the range
+        f0      = sr / (tau* + delta) when voiced, delta the vertex of the parabola through d'(tau* - 1 .. tau* + 1) clamped to
+                  +-0.5 (0 where it opens downwards); exactly 0 when unvoiced.
+    A frame that reads a NaN or an infinity gives NaN (lag -1); other frames are not affected.
+
+    Returns f0 [B, F] (float32, on the device; nothing is downloaded and nothing waits); with return_aperiodicity also d'(tau*) [B, F],
+    with return_lag also tau* [B, F] int32.  The tensors belong to a buffer set kept per shape: the next call of the same shape overwrites
+    them (clone to keep), which is what lets the call be captured in a graph and replayed."""
+    import torch
+    from . import _lib
+    lib = _lib.load_library()
+    if device is None:
+        device = wav.device if torch.is_tensor(wav) and wav.is_cuda else torch.device("cuda:%d" % torch.cuda.current_device())
+    dev = torch.device(device)
+    x = _dev_tensor(wav, torch.float32, dev)
+    if x.dim() != 2:
+        raise _lib.TacoError(_lib.TACO_ERR_SHAPE, "wav must be [B, L], got %s" % (tuple(x.shape),))
+    B, L = x.shape
+    ns = None if num_samples is None else _dev_tensor(num_samples, torch.int32, dev)
+    if ns is not None and tuple(ns.shape) != (B,):
+        raise _lib.TacoError(_lib.TACO_ERR_SHAPE, "num_samples must be [B] = (%d,), got %s" % (B, tuple(ns.shape)))
+    sr, hop, frame = framing(hparams)
+    W = frame if window is None else int(window)
+    if B < 1 or L < 1 or hop < 1:
+        raise _lib.TacoError(_lib.TACO_ERR_ARG, "wav [%d, %d] at hop %d: every one must be >= 1" % (B, L, hop))
+    F = 1 + L // hop
+    key = (str(dev), B, L, hop)
+    buf = _F0_BUFFERS.get(key)
+    if buf is None:
+        buf = _F0_BUFFERS[key] = {"f0": torch.empty((B, F), dtype=torch.float32, device=dev)}
+    if return_aperiodicity and "aper" not in buf:
+        buf["aper"] = torch.empty((B, F), dtype=torch.float32, device=dev)
+    if return_lag and "lag" not in buf:
+        buf["lag"] = torch.empty((B, F), dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+        _lib.check(lib.taco_f0_yin(stream, _ptr(x), _ptr(ns), B, L, sr, hop, W, float(fmin), float(fmax), float(threshold), _ptr(buf["f0"]),
+                                   _ptr(buf["aper"]) if return_aperiodicity else None, _ptr(buf["lag"]) if return_lag else None))
+    out = (buf["f0"],)
+    if return_aperiodicity:
+        out += (buf["aper"],)
+    if return_lag:
+        out += (buf["lag"],)
+    return out[0] if len(out) == 1 else out
+
+
+def f0_path_stats(f0_a, f0_b, path, path_len):
+    """The four sums behind f0_errors, [B, 4] float32 on the device (taco_f0_path_stats): sum of squared cents over the path entries voiced
+    on both sides, their number, the entries voiced on one side only, the entries used.  Kept per shape like every result here."""
+    import torch
+    from . import _lib
+    lib = _lib.load_library()
+    if not (torch.is_tensor(f0_a) and f0_a.is_cuda):
+        raise _lib.TacoError(_lib.TACO_ERR_ARG, "f0_a must be a device tensor (f0_track returns one)")
+    dev = f0_a.device
+    a, b = _dev_tensor(f0_a, torch.float32, dev), _dev_tensor(f0_b, torch.float32, dev)
+    pth, pl = _dev_tensor(path, torch.int32, dev), _dev_tensor(path_len, torch.int32, dev)
+    if a.dim() != 2 or b.dim() != 2 or pth.dim() != 3 or pth.shape[2] != 2 or not (a.shape[0] == b.shape[0] == pth.shape[0]) or \
+            tuple(pl.shape) != (a.shape[0],):
+        raise _lib.TacoError(_lib.TACO_ERR_SHAPE, "f0_a [B, Fa], f0_b [B, Fb], path [B, cap, 2], path_len [B]; got %s, %s, %s, %s"
+                             % (tuple(a.shape), tuple(b.shape), tuple(pth.shape), tuple(pl.shape)))
+    B, Fa = a.shape
+    Fb, cap = b.shape[1], pth.shape[1]
+    key = (str(dev), B, Fa, Fb, cap)
+    stats = _F0_BUFFERS.get(key)
+    if stats is None:
+        stats = _F0_BUFFERS[key] = torch.empty((B, 4), dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+        _lib.check(lib.taco_f0_path_stats(stream, _ptr(a), Fa, _ptr(b), Fb, _ptr(pth), _ptr(pl), B, cap, _ptr(stats)))
+    return stats
+
+
+def f0_errors(f0_a, f0_b, path, path_len):
+    """F0 RMSE in cents and voiced/unvoiced error of two F0 tracks [B, Fa] and [B, Fb] (f0_track's: 0 = unvoiced) along a warping
+    path [B, cap, 2] with path_len [B], as dtw_distance(return_path=True) returns them.  This project's own definition, UNPINNED on
+    any evaluation package: over the path entries (i, j) inside both tracks,
+        rmse_cents    = sqrt(mean of (1200 * log2(f0_a[i] / f0_b[j]))^2 over the entries voiced on both sides), NaN where there is none;
+        vuv_error     = entries voiced on exactly one side / entries used;
+        voiced_frames = entries voiced on both sides.
+    A NaN in a track at a used entry makes that pair's rmse NaN.  Returns (rmse_cents, vuv_error, voiced_frames), each [B] float32 on
+    the device; the sums are taco_f0_path_stats's, the three divisions and the root are torch plumbing.  Nothing is downloaded."""
+    import torch
+    s = f0_path_stats(f0_a, f0_b, path, path_len)
+    return torch.sqrt(s[:, 0] / s[:, 1]), s[:, 2] / s[:, 3], s[:, 1].clone()
+
+
+def _spectrogram(hparams, dev):
+    from . import audio
+    from .hparams import hparams as default_hparams
+    h = hparams if hparams is not None else default_hparams
+    hp = audio.c_audio_hparams(h)
+    key = (str(dev), int(getattr(h, "num_mels", 80))) + tuple(getattr(hp, f) for f, _ in hp._fields_)
+    if key not in _SPEC:
+        _SPEC[key] = audio.Spectrogram(h, device=dev)
+    return _SPEC[key]
+
+
+def prosody_distance(wav_a, wav_b, num_a=None, num_b=None, hparams=None, **f0_kw):
+    """The three objective numbers for two batches of waveforms [B, La] and [B, Lb] (num_a, num_b: samples per row, None = all) in one
+    call: mel targets of both by audio.Spectrogram, mel_cepstra of both, dtw_distance(cost='l2', return_path=True) on the cepstra, f0_track
+    of both (f0_kw goes to it: fmin, fmax, threshold, window) and f0_errors along the path -- the F0 columns are the spectrogram's frames,
+    so the path indexes them directly.  Each piece is this project's own definition, UNPINNED on any package (see mel_cepstral_distortion,
+    f0_track, f0_errors).  Returns a dict of [B] device tensors: mcd (dB), f0_rmse_cents, vuv_error, voiced_frames.  Nothing is
+    downloaded and nothing waits; the spectrogram handle and every buffer set are kept for the next call."""
+    import torch
+    from . import _lib
+    extra = sorted(set(f0_kw) - {"fmin", "fmax", "threshold", "window"})
+    if extra:
+        raise _lib.TacoError(_lib.TACO_ERR_ARG, "prosody_distance passes fmin, fmax, threshold and window on to f0_track, not %s" % ", ".join(extra))
+    dev = None
+    for w in (wav_a, wav_b):
+        if dev is None and torch.is_tensor(w) and w.is_cuda:
+            dev = w.device
+    dev = dev if dev is not None else torch.device("cuda:%d" % torch.cuda.current_device())
+    a, b = _dev_tensor(wav_a, torch.float32, dev), _dev_tensor(wav_b, torch.float32, dev)
+    if a.dim() != 2 or b.dim() != 2 or a.shape[0] != b.shape[0]:
+        raise _lib.TacoError(_lib.TACO_ERR_SHAPE, "wav_a and wav_b must be [B, La] and [B, Lb], got %s and %s" % (tuple(a.shape), tuple(b.shape)))
+    na = None if num_a is None else _dev_tensor(num_a, torch.int32, dev)
+    nb = None if num_b is None else _dev_tensor(num_b, torch.int32, dev)
+    spec = _spectrogram(hparams, dev)
+    _, mel_a, frames_a = spec.targets(a, na)
+    _, mel_b, frames_b = spec.targets(b, nb)
+    ca, cb = mel_cepstra(mel_a, hparams), mel_cepstra(mel_b, hparams)
+    dist, (path, path_len) = dtw_distance(ca, cb, frames_a, frames_b, cost="l2", return_path=True)
+    mcd = dist * mcd_constant()
+    # the two tracks differ in shape or are taken one after the other: the first is cloned out of the buffer set the second may share
+    f0_a = f0_track(a, na, hparams, device=dev, **f0_kw).clone()
+    f0_b = f0_track(b, nb, hparams, device=dev, **f0_kw)
+    rmse, vuv, voiced = f0_errors(f0_a, f0_b, path, path_len)
+    return {"mcd": mcd, "f0_rmse_cents": rmse, "vuv_error": vuv, "voiced_frames": voiced}
