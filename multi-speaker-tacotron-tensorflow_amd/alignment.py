@@ -12,6 +12,10 @@ import os
 import string
 
 import numpy as np
+import torch
+
+from . import _lib
+from ._device import STREAM, call, tensor
 
 _PUNCTUATION = str.maketrans({c: None for c in string.punctuation})
 
@@ -96,29 +100,23 @@ def pack_texts(texts):
 def _device_scores(texts, pairs, group_offsets=None, device=None):
     """taco_text_matches (and taco_text_best_two when group_offsets is given) on the current stream -> (matches [n_pairs], best
     [n_groups, 4] or None) as NumPy arrays."""
-    import ctypes as C
-    import torch
-    from . import _lib
     lib = _lib.load_library()
     dev = torch.device(device or "cuda:0")
     chars, offsets = pack_texts(texts)
     pairs = np.ascontiguousarray(pairs, np.int32).reshape(-1, 2)
     n_pairs = len(pairs)
-    up = lambda x: torch.as_tensor(np.ascontiguousarray(x)).to(dev)
-    ptr = lambda t: C.c_void_p(t.data_ptr())
-    with torch.cuda.device(dev):
-        stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
-        d_chars, d_off, d_pairs = up(chars if len(chars) else np.zeros(1, np.int32)), up(offsets), up(pairs if n_pairs else np.zeros((1, 2), np.int32))
-        d_m = torch.empty(max(n_pairs, 1), dtype=torch.int32, device=dev)
-        _lib.check(lib.taco_text_matches(stream, ptr(d_chars), len(chars), ptr(d_off), len(texts), ptr(d_pairs), n_pairs, ptr(d_m)))
-        best = None
-        if group_offsets is not None:
-            g = np.ascontiguousarray(group_offsets, np.int32)
-            d_g = up(g)
-            d_best = torch.empty((max(len(g) - 1, 1), 4), dtype=torch.int32, device=dev)
-            _lib.check(lib.taco_text_best_two(stream, ptr(d_m), ptr(d_pairs), ptr(d_off), len(texts), ptr(d_g), len(g) - 1, ptr(d_best)))
-            best = d_best[:len(g) - 1].cpu().numpy()
-        return d_m[:n_pairs].cpu().numpy(), best
+    up = lambda x, what: tensor(x, dev, torch.int32, what)
+    d_chars, d_off = up(chars if len(chars) else np.zeros(1, np.int32), "chars"), up(offsets, "offsets")
+    d_pairs = up(pairs if n_pairs else np.zeros((1, 2), np.int32), "pairs")
+    d_m = torch.empty(max(n_pairs, 1), dtype=torch.int32, device=dev)
+    call(dev, lib.taco_text_matches, STREAM, d_chars, len(chars), d_off, len(texts), d_pairs, n_pairs, d_m)
+    best = None
+    if group_offsets is not None:
+        g = np.ascontiguousarray(group_offsets, np.int32)
+        d_best = torch.empty((max(len(g) - 1, 1), 4), dtype=torch.int32, device=dev)
+        call(dev, lib.taco_text_best_two, STREAM, d_m, d_pairs, d_off, len(texts), up(g, "group_offsets"), len(g) - 1, d_best)
+        best = d_best[:len(g) - 1].cpu().numpy()
+    return d_m[:n_pairs].cpu().numpy(), best
 
 
 def match_counts(texts_a, texts_b, pairs, device=None):

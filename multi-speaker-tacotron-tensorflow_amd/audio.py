@@ -10,14 +10,15 @@ bank (mel_basis) and its pseudo-inverse (inv_mel_basis), built once in float64 a
 Recordings reach the model's sample rate through class Resampler (taco_resample_*, taco_wav_resample): librosa.core.load's and
 resample_audio's band-limited sinc interpolation (audio/__init__.py:12-20,30-32), whose one host computation is the Kaiser-windowed
 half filter (kaiser_window).
-Every public method reaches the library through one marshalling layer: _tensor / _lengths (inputs onto the device, shape checks),
-_workspace (the handle's scratch memory) and _call (device, stream, pointers, status)."""
+Every public method reaches the library through the package's one marshalling layer (_device.py): tensor / lengths (inputs onto the
+device, shape checks), workspace (the handle's scratch memory) and call (device, stream, pointers, status)."""
 import ctypes as C
 
 import numpy as np
 import torch
 
 from . import _lib
+from ._device import STREAM, Handle, call, lengths, tensor, workspace
 
 
 def hz_to_mel(f):
@@ -75,27 +76,7 @@ def num_frames(hparams, n_samples):
     return int(_lib.load_library().taco_spec_num_frames(C.byref(hp), int(n_samples)))
 
 
-# ---- the one marshalling layer between the public methods below and libtaco_hip ----
-_STREAM = object()      # in _call's arguments: the place of the current stream
 _ENERGY = {"spectral": _lib.TACO_TRIM_SPECTRAL, "time": _lib.TACO_TRIM_TIME}      # frame energies of trim / split
-
-
-def _tensor(x, device, dtype, what, dims=None):
-    """numpy or tensor -> a contiguous `dtype` tensor on the device (one that already is that is used as it is).  dtype may be a tuple:
-    the input's own if it is among them, else the first.  dims: per dimension its name (any size) or (name, size); None: the caller
-    checks the shape."""
-    x = x if torch.is_tensor(x) else torch.as_tensor(np.asarray(x))
-    if isinstance(dtype, tuple):
-        dtype = x.dtype if x.dtype in dtype else dtype[0]
-    x = x.to(device, dtype).contiguous()
-    if dims is not None and (x.dim() != len(dims) or any(not isinstance(d, str) and x.shape[i] != d[1] for i, d in enumerate(dims))):
-        raise Exception("%s must be [%s], got shape %s" % (what, ", ".join(d if isinstance(d, str) else "%s = %d" % d for d in dims), tuple(x.shape)))
-    return x
-
-
-def _lengths(v, device, B, what):
-    """The optional [B] int32 vector (frames, num_samples): a device int32 tensor is used as it is, host data is uploaded, None stays None."""
-    return None if v is None else _tensor(v, device, torch.int32, what, (("B", B),))
 
 
 def _energy(name):
@@ -120,42 +101,7 @@ def pcm_threshold(silence_thresh):
     return int(min(np.floor(10 ** (float(silence_thresh) / 20) * 32768.0), 32768.0))
 
 
-def _workspace(handle, nbytes):
-    """The handle's workspace, grown to nbytes"""
-    if handle._ws is None or handle._ws.numel() < nbytes:
-        handle._ws = torch.empty(int(nbytes), dtype=torch.uint8, device=handle.device)
-    return handle._ws
-
-
-def _call(device, fn, *args):
-    """fn(*args) on the device's current stream (where args holds _STREAM): tensors and None go as pointers, the status is checked."""
-    def arg(a):
-        if a is _STREAM:
-            return C.c_void_p(torch.cuda.current_stream().cuda_stream)
-        if a is None or torch.is_tensor(a):
-            return C.c_void_p(0 if a is None else a.data_ptr())
-        return a
-    with torch.cuda.device(device):
-        _lib.check(fn(*[arg(a) for a in args]))
-
-
-class _Handle(object):
-    """A library handle `_h` on `device`, released by the function named `_destroy`."""
-    _destroy = None
-
-    def close(self):
-        if getattr(self, "_h", None):
-            getattr(self._lib, self._destroy)(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-class GriffinLim(_Handle):
+class GriffinLim(Handle):
     """flavor "librosa" (default): the handle of inv_spectrogram / inv_melspectrogram and of everything Spectrogram adds.  "tensorflow":
     the handle of inv_spectrogram_tensorflow (tf.contrib.signal's uncentred STFT; the librosa-flavour methods raise TacoError on it).
     pcm16, trim, split, remove_breath, nonsilent, range_sumsq, apply_gains, set_inv_mel_basis and mel_to_linear work on either, and
@@ -221,15 +167,15 @@ class GriffinLim(_Handle):
     def _vocode_rows(self, fn, x, what, width, frames, init_uniform, seed, iters, momentum=None):
         """The librosa-flavour vocoders: fn is the entry point, x [B, T, width[1]] its input, named `what` and its last dimension width[0] in errors"""
         dev = self.device
-        x = _tensor(x, dev, torch.float32, what, ("B", "T", width))
+        x = tensor(x, dev, torch.float32, what, ("B", "T", width))
         B, T, _ = x.shape
-        u = None if init_uniform is None else _tensor(init_uniform, dev, torch.float32, "init_uniform", (("B", B), ("T", T), ("num_freq", self.hp.num_freq)))
-        fr = _lengths(frames, dev, B, "frames")
+        u = None if init_uniform is None else tensor(init_uniform, dev, torch.float32, "init_uniform", (("B", B), ("T", T), ("num_freq", self.hp.num_freq)))
+        fr = lengths(frames, dev, B, "frames")
         self._momentum(momentum)      # before the size is asked for: the workspace depends on it
-        ws = _workspace(self, self._lib.taco_gl_rows_workspace_bytes(self._h, B, T))
+        ws = workspace(self, self._lib.taco_gl_rows_workspace_bytes(self._h, B, T))
         wav = torch.empty((B, self.num_samples(T)), dtype=torch.float32, device=dev)
         ns = torch.empty((B,), dtype=torch.int32, device=dev)
-        _call(dev, fn, self._h, _STREAM, x, fr, u, C.c_ulonglong(int(seed)), B, T, -1 if iters is None else int(iters), wav, ns, ws, ws.numel())
+        call(dev, fn, self._h, STREAM, x, fr, u, C.c_ulonglong(int(seed)), B, T, -1 if iters is None else int(iters), wav, ns, ws, ws.numel())
         return wav, ns
 
     def tf_num_samples(self, T):
@@ -243,14 +189,14 @@ class GriffinLim(_Handle):
         its first hop*(frames[b]-1) + win samples, zeros after.  UNPINNED on TensorFlow: tf.contrib.signal.stft / inverse_stft restated
         (include/taco_abi.h), checked against tests/vocoder_reference.py, not against TensorFlow.  momentum as inv_spectrogram."""
         dev = self.device
-        x = _tensor(linear, dev, torch.float32, "linear", ("B", "T", ("num_freq", self.hp.num_freq)))
+        x = tensor(linear, dev, torch.float32, "linear", ("B", "T", ("num_freq", self.hp.num_freq)))
         B, T, _ = x.shape
-        fr = _lengths(frames, dev, B, "frames")
+        fr = lengths(frames, dev, B, "frames")
         self._momentum(momentum)      # before the size is asked for: the workspace depends on it
-        ws = _workspace(self, self._lib.taco_gl_tf_workspace_bytes(self._h, B, T))
+        ws = workspace(self, self._lib.taco_gl_tf_workspace_bytes(self._h, B, T))
         wav = torch.empty((B, self.tf_num_samples(T)), dtype=torch.float32, device=dev)
         ns = torch.empty((B,), dtype=torch.int32, device=dev)
-        _call(dev, self._lib.taco_gl_inv_spectrogram_tf, self._h, _STREAM, x, fr, B, T, -1 if iters is None else int(iters), wav, ns, ws, ws.numel())
+        call(dev, self._lib.taco_gl_inv_spectrogram_tf, self._h, STREAM, x, fr, B, T, -1 if iters is None else int(iters), wav, ns, ws, ws.numel())
         return wav, ns
 
     def set_inv_mel_basis(self, inv=None):
@@ -274,10 +220,10 @@ class GriffinLim(_Handle):
     def mel_to_linear(self, mel):
         """_mel_to_linear(_db_to_amp(_denormalize(mel))) of audio/__init__.py:71,136-140: mel [B, T, num_mels] (normalised, as the model's
         mel_outputs) -> linear magnitudes [B, T, num_freq] (device tensor), floored at 1e-10, before ^power."""
-        x = _tensor(mel, self.device, torch.float32, "mel", ("B", "T", ("num_mels", self._need_inv_mels())))
+        x = tensor(mel, self.device, torch.float32, "mel", ("B", "T", ("num_mels", self._need_inv_mels())))
         B, T, _ = x.shape
         out = torch.empty((B, T, self.hp.num_freq), dtype=torch.float32, device=self.device)
-        _call(self.device, self._lib.taco_gl_mel_to_linear, self._h, _STREAM, x, B, T, out)
+        call(self.device, self._lib.taco_gl_mel_to_linear, self._h, STREAM, x, B, T, out)
         return out
 
     def inv_melspectrogram(self, mel, frames=None, init_uniform=None, seed=0, iters=None, momentum=None):
@@ -298,23 +244,23 @@ class GriffinLim(_Handle):
         if kind not in self._TARGET_KINDS:
             raise _lib.TacoError(_lib.TACO_ERR_ARG, "kind must be one of %s, got %r" % (sorted(self._TARGET_KINDS), kind))
         dev = self.device
-        x = _tensor(target, dev, torch.float32, "target", ("B", "T", ("num_freq", self.hp.num_freq)))
+        x = tensor(target, dev, torch.float32, "target", ("B", "T", ("num_freq", self.hp.num_freq)))
         B, T, _ = x.shape
-        y = _tensor(wav, dev, torch.float32, "wav", (("B", B), ("hop*(T-1)", self.num_samples(T))))
-        fr = _lengths(frames, dev, B, "frames")
-        ws = _workspace(self, self._lib.taco_gl_convergence_workspace_bytes(self._h, B, T))
+        y = tensor(wav, dev, torch.float32, "wav", (("B", B), ("hop*(T-1)", self.num_samples(T))))
+        fr = lengths(frames, dev, B, "frames")
+        ws = workspace(self, self._lib.taco_gl_convergence_workspace_bytes(self._h, B, T))
         sc = torch.empty((B,), dtype=torch.float32, device=dev)
-        _call(dev, self._lib.taco_gl_convergence, self._h, _STREAM, x, self._TARGET_KINDS[kind], fr, y, B, T, sc, ws, ws.numel())
+        call(dev, self._lib.taco_gl_convergence, self._h, STREAM, x, self._TARGET_KINDS[kind], fr, y, B, T, sc, ws, ws.numel())
         return sc
 
     def pcm16(self, wav, num_samples=None):
         """save_audio's scaling (audio/__init__.py:23-24) per row: wav [B, L] float32, num_samples [B] (None: L) -> int16 [B, L] (device
         tensor); row b is x * 32767 / max(0.01, max|x[:num_samples[b]]|) truncated, zeros past num_samples[b]."""
-        x = _tensor(wav, self.device, torch.float32, "wav", ("B", "L"))
+        x = tensor(wav, self.device, torch.float32, "wav", ("B", "L"))
         B, L = x.shape
-        ns = _lengths(num_samples, self.device, B, "num_samples")
+        ns = lengths(num_samples, self.device, B, "num_samples")
         pcm = torch.empty((B, L), dtype=torch.int16, device=self.device)
-        _call(self.device, self._lib.taco_wav_to_pcm16, _STREAM, x, ns, B, L, pcm)
+        call(self.device, self._lib.taco_wav_to_pcm16, STREAM, x, ns, B, L, pcm)
         return pcm
 
     def trim(self, wav, num_samples=None, top_db=60, frame_length=2048, hop_length=512, energy="spectral", return_db=False):
@@ -326,14 +272,14 @@ class GriffinLim(_Handle):
         (mean square of the unwindowed frame).  UNPINNED on librosa: a restatement of the documented algorithm (include/taco_abi.h,
         taco_wav_trim), checked against tests/trim_reference.py, not against librosa."""
         dev = self.device
-        x = _tensor(wav, dev, torch.float32, "wav", ("B", "L"))
+        x = tensor(wav, dev, torch.float32, "wav", ("B", "L"))
         B, L = x.shape
-        ns = _lengths(num_samples, dev, B, "num_samples")
+        ns = lengths(num_samples, dev, B, "num_samples")
         mode, frame_length, hop_length = _energy(energy), int(frame_length), int(hop_length)
-        ws = _workspace(self, self._lib.taco_wav_trim_workspace_bytes(B, L, frame_length, hop_length))
+        ws = workspace(self, self._lib.taco_wav_trim_workspace_bytes(B, L, frame_length, hop_length))
         index = torch.empty((B, 2), dtype=torch.int32, device=dev)
         db = torch.empty((B, 1 + L // max(hop_length, 1)), dtype=torch.float32, device=dev) if return_db else None
-        _call(dev, self._lib.taco_wav_trim, _STREAM, x, ns, B, L, float(top_db), frame_length, hop_length, mode, index, db, ws, ws.numel())
+        call(dev, self._lib.taco_wav_trim, STREAM, x, ns, B, L, float(top_db), frame_length, hop_length, mode, index, db, ws, ws.numel())
         return (index, db) if return_db else index
 
     def split(self, wav, num_samples=None, top_db=60, frame_length=2048, hop_length=512, energy="spectral", max_intervals=None, return_db=False):
@@ -346,17 +292,17 @@ class GriffinLim(_Handle):
         the threshold are `trim`'s: intervals[b, 0, 0] and intervals[b, counts[b] - 1, 1] are its index.  UNPINNED on librosa
         (include/taco_abi.h, taco_wav_split), checked against tests/split_reference.py, not against librosa."""
         dev = self.device
-        x = _tensor(wav, dev, torch.float32, "wav", ("B", "L"))
+        x = tensor(wav, dev, torch.float32, "wav", ("B", "L"))
         B, L = x.shape
-        ns = _lengths(num_samples, dev, B, "num_samples")
+        ns = lengths(num_samples, dev, B, "num_samples")
         mode, frame_length, hop_length = _energy(energy), int(frame_length), int(hop_length)
         fmax = 1 + L // max(hop_length, 1)
         M = (fmax + 1) // 2 if max_intervals is None else int(max_intervals)
-        ws = _workspace(self, self._lib.taco_wav_split_workspace_bytes(B, L, frame_length, hop_length))
+        ws = workspace(self, self._lib.taco_wav_split_workspace_bytes(B, L, frame_length, hop_length))
         intervals = torch.empty((B, max(M, 1), 2), dtype=torch.int32, device=dev)
         counts = torch.empty((B,), dtype=torch.int32, device=dev)
         db = torch.empty((B, fmax), dtype=torch.float32, device=dev) if return_db else None
-        _call(dev, self._lib.taco_wav_split, _STREAM, x, ns, B, L, float(top_db), frame_length, hop_length, mode, M, intervals, counts, db, ws,
+        call(dev, self._lib.taco_wav_split, STREAM, x, ns, B, L, float(top_db), frame_length, hop_length, mode, M, intervals, counts, db, ws,
               ws.numel())
         return (intervals, counts, db) if return_db else (intervals, counts)
 
@@ -367,15 +313,15 @@ class GriffinLim(_Handle):
         bits of the input outside the muted intervals, zeros past num_samples[b]); with return_info also (intervals, counts, muted
         [B, M] int32, abs_mean [B, 1 + M] float32: the row's mean before any mute, then each interval's)."""
         dev = self.device
-        x = _tensor(wav, dev, torch.float32, "wav", ("B", "L"))
+        x = tensor(wav, dev, torch.float32, "wav", ("B", "L"))
         B, L = x.shape
-        ns = _lengths(num_samples, dev, B, "num_samples")
+        ns = lengths(num_samples, dev, B, "num_samples")
         intervals, counts = self.split(x, ns, top_db=top_db, frame_length=frame_length, hop_length=hop_length, energy=energy)
         M = intervals.shape[1]
         out = torch.empty_like(x)
         muted = torch.empty((B, M), dtype=torch.int32, device=dev) if return_info else None
         mean = torch.empty((B, 1 + M), dtype=torch.float32, device=dev) if return_info else None
-        _call(dev, self._lib.taco_wav_breath_mute, _STREAM, x, ns, B, L, intervals, counts, M, float(threshold), out, muted, mean)
+        call(dev, self._lib.taco_wav_breath_mute, STREAM, x, ns, B, L, intervals, counts, M, float(threshold), out, muted, mean)
         return (out, (intervals, counts, muted, mean)) if return_info else out
 
     def _pcm(self, pcm):
@@ -407,16 +353,16 @@ class GriffinLim(_Handle):
         B, L, ch = x.shape
         sr = int(getattr(self.hparams, "sample_rate", 24000) if sample_rate is None else sample_rate)
         W = int(min_silence_len)
-        nf = _lengths(num_frames, dev, B, "num_frames")
+        nf = lengths(num_frames, dev, B, "num_frames")
         mmax = pcm_len_ms(L, sr) if sr >= 1 and L >= 1 else 0
         R = mmax // (max(W, 1) + 1) + 2 if max_ranges is None else int(max_ranges)
         nbytes = self._lib.taco_pcm_nonsilent_workspace_bytes(B, L, sr)
-        ws = torch.empty(max(int(nbytes), 8), dtype=torch.uint8, device=dev) if return_energy else _workspace(self, max(nbytes, 8))
+        ws = torch.empty(max(int(nbytes), 8), dtype=torch.uint8, device=dev) if return_energy else workspace(self, max(nbytes, 8))
         ranges = torch.empty((B, max(R, 1), 2), dtype=torch.int32, device=dev)
         counts = torch.empty((B,), dtype=torch.int32, device=dev)
         len_ms = torch.empty((B,), dtype=torch.int32, device=dev)
         wss = torch.empty((B, mmax), dtype=torch.int64, device=dev) if return_window_sumsq else None
-        _call(dev, self._lib.taco_pcm_nonsilent, _STREAM, x, nf, B, L, ch, sr, W, pcm_threshold(silence_thresh), R, ranges, counts, len_ms, wss, ws,
+        call(dev, self._lib.taco_pcm_nonsilent, STREAM, x, nf, B, L, ch, sr, W, pcm_threshold(silence_thresh), R, ranges, counts, len_ms, wss, ws,
               ws.numel())
         out = (ranges, counts, len_ms)
         if return_window_sumsq:
@@ -432,15 +378,15 @@ class GriffinLim(_Handle):
         dev = self.device
         sr = int(getattr(self.hparams, "sample_rate", 24000) if sample_rate is None else sample_rate)
         L, channels = int(L), int(channels)
-        ranges = _tensor(ranges, dev, torch.int32, "ranges", ("B", "R", ("2", 2)))
+        ranges = tensor(ranges, dev, torch.int32, "ranges", ("B", "R", ("2", 2)))
         B, R, _ = ranges.shape
         mmax = pcm_len_ms(L, sr) if sr >= 1 and L >= 1 else 0
-        energy = _tensor(energy, dev, torch.int64, "energy", (("B", B), ("Mmax", mmax)))
-        counts = _lengths(counts, dev, B, "counts")
-        nf = _lengths(num_frames, dev, B, "num_frames")
+        energy = tensor(energy, dev, torch.int64, "energy", (("B", B), ("Mmax", mmax)))
+        counts = lengths(counts, dev, B, "counts")
+        nf = lengths(num_frames, dev, B, "num_frames")
         sumsq = torch.empty((B, R), dtype=torch.int64, device=dev)
         samples = torch.empty((B, R), dtype=torch.int64, device=dev)
-        _call(dev, self._lib.taco_pcm_range_sumsq, _STREAM, energy if mmax else sumsq, nf, B, L, channels, sr, ranges, counts, R, sumsq, samples)
+        call(dev, self._lib.taco_pcm_range_sumsq, STREAM, energy if mmax else sumsq, nf, B, L, channels, sr, ranges, counts, R, sumsq, samples)
         return sumsq, samples
 
     def apply_gains(self, pcm, ranges, counts, gains, num_frames=None, sample_rate=None):
@@ -452,15 +398,15 @@ class GriffinLim(_Handle):
         x = self._pcm(pcm)
         B, L, ch = x.shape
         sr = int(getattr(self.hparams, "sample_rate", 24000) if sample_rate is None else sample_rate)
-        ranges = _tensor(ranges, dev, torch.int32, "ranges", (("B", B), "R", ("2", 2)))
+        ranges = tensor(ranges, dev, torch.int32, "ranges", (("B", B), "R", ("2", 2)))
         R = ranges.shape[1]
-        counts = _lengths(counts, dev, B, "counts")
-        gains = _tensor(gains, dev, torch.float64, "gains", (("B", B), ("R", R)))
-        nf = _lengths(num_frames, dev, B, "num_frames")
+        counts = lengths(counts, dev, B, "counts")
+        gains = tensor(gains, dev, torch.float64, "gains", (("B", B), ("R", R)))
+        nf = lengths(num_frames, dev, B, "num_frames")
         L_out = max(1, pcm_frame_of_ms(pcm_len_ms(L, sr), sr)) if sr >= 1 else 1
         out = torch.empty((B, L_out, ch), dtype=torch.int16, device=dev)
         on = torch.empty((B,), dtype=torch.int32, device=dev)
-        _call(dev, self._lib.taco_pcm_apply_gains, _STREAM, x, nf, B, L, ch, sr, ranges, counts, R, gains, out, L_out, on)
+        call(dev, self._lib.taco_pcm_apply_gains, STREAM, x, nf, B, L, ch, sr, ranges, counts, R, gains, out, L_out, on)
         return out, on
 
 
@@ -494,10 +440,10 @@ class Spectrogram(GriffinLim):
         num_frames): contiguous device tensors of exactly those shapes that are written in place and returned (nothing is allocated
         once the workspace has its size)."""
         dev = self.device
-        x = _tensor(wav, dev, torch.float32, "wav", ("B", "Lmax"))
+        x = tensor(wav, dev, torch.float32, "wav", ("B", "Lmax"))
         B, L = x.shape
-        ns = _lengths(num_samples, dev, B, "num_samples")
-        ws = _workspace(self, self._lib.taco_spec_workspace_bytes(self._h, B, L))
+        ns = lengths(num_samples, dev, B, "num_samples")
+        ws = workspace(self, self._lib.taco_spec_workspace_bytes(self._h, B, L))
         T = self.num_frames(L)
         if mel and not self.num_mels:
             raise _lib.TacoError(_lib.TACO_ERR_STATE, "the mel output needs a filter bank: call set_mel_basis first (or pass mel=False)")
@@ -512,7 +458,7 @@ class Spectrogram(GriffinLim):
             lin = torch.empty((B, T, self.hp.num_freq), dtype=torch.float32, device=dev)
             m = torch.empty((B, T, self.num_mels), dtype=torch.float32, device=dev) if mel else None
             nf = torch.empty((B,), dtype=torch.int32, device=dev)
-        _call(dev, self._lib.taco_spec_targets, self._h, _STREAM, x, ns, B, L, lin, m, nf, ws, ws.numel())
+        call(dev, self._lib.taco_spec_targets, self._h, STREAM, x, ns, B, L, lin, m, nf, ws, ws.numel())
         return lin, m, nf
 
     def spectrogram(self, y):
@@ -553,7 +499,7 @@ FILTERS = {"kaiser_best": dict(num_zeros=64, precision=9, beta=14.76965645937949
 
 
 
-class Resampler(_Handle):
+class Resampler(Handle):
     """Recordings at orig_sr -> target_sr on the GPU, as librosa.core.resample(y, orig_sr, target_sr) with resampy's sinc interpolation
     does, but with every output at its exact position t * orig_sr / target_sr (include/taco_abi.h says where resampy 0.2.0's
     accumulated position differs).  filter: a name in FILTERS, a dict of kaiser_window's arguments, or a float64 half window (then
@@ -620,17 +566,17 @@ class Resampler(_Handle):
         (out [B, out_len(L)] float32, out_samples [B] int32), device tensors.  More than one channel is averaged (librosa.to_mono).
         Row b holds its computed_len(n_b) outputs, exact zeros after, and out_samples[b] = out_len(n_b)."""
         dev = self.device
-        x = _tensor(wav, dev, (torch.float32, torch.int16), "wav")
+        x = tensor(wav, dev, (torch.float32, torch.int16), "wav")
         channels = int(channels)
         if x.dim() == 3 and channels == 1:
             channels = int(x.shape[2])
         if x.dim() not in (2, 3) or (x.dim() == 3 and x.shape[2] != channels) or (x.dim() == 2 and x.shape[1] % max(channels, 1)):
             raise Exception("wav must be [B, L] or [B, L, channels = %d], got shape %s" % (channels, tuple(x.shape)))
         B, L = int(x.shape[0]), int(x.shape[1]) // (channels if x.dim() == 2 else 1)
-        ns = _lengths(num_samples, dev, B, "num_samples")
+        ns = lengths(num_samples, dev, B, "num_samples")
         L_out = self.out_len(L)
         out = torch.empty((B, L_out), dtype=torch.float32, device=dev)
         on = torch.empty((B,), dtype=torch.int32, device=dev)
         fmt = _lib.TACO_WAV_PCM16 if x.dtype == torch.int16 else _lib.TACO_WAV_F32
-        _call(dev, self._lib.taco_wav_resample, self._h, _STREAM, x, fmt, channels, ns, B, L, out, L_out, on)
+        call(dev, self._lib.taco_wav_resample, self._h, STREAM, x, fmt, channels, ns, B, L, out, L_out, on)
         return out, on

@@ -1,11 +1,5 @@
 // taco_align_api.h -- C ABI of matching recognised text to script lines (kernels in taco_align.h); included inside extern "C".
 
-// [p, p + bytes) and [q, q + qbytes) share a byte; sizes are 128-bit so that counts near 2^63 are not mistaken for small ones
-static bool ta_overlap(const void* p, unsigned __int128 bytes, const void* q, unsigned __int128 qbytes) {
-  const unsigned __int128 a = (uintptr_t)p, b = (uintptr_t)q;
-  return bytes && qbytes && a < b + qbytes && b < a + bytes;
-}
-
 // cols: 0 = the one-column kernel for len(b) <= 64 and the four-column one above; TA_WIDE = the four-column kernel for every length
 static int ta_matches(void* hip_stream, const int32_t* d_chars, long long n_chars, const int32_t* d_offsets, int n_texts, const int32_t* d_pairs,
                       int n_pairs, int32_t* d_matches, int cols) {
@@ -13,11 +7,10 @@ static int ta_matches(void* hip_stream, const int32_t* d_chars, long long n_char
   if (n_chars < 0 || n_texts < 0 || n_pairs < 0)
     return fail(TACO_ERR_ARG, "n_chars, n_texts and n_pairs must be >= 0, got %lld, %d, %d", n_chars, n_texts, n_pairs);
   if (cols != 0 && cols != TA_WIDE) return fail(TACO_ERR_ARG, "cols = %d: accepted are 0 (by length) and %d", cols, TA_WIDE);
-  const unsigned __int128 out = (unsigned __int128)(unsigned)n_pairs * sizeof(int32_t);
-  if (ta_overlap(d_matches, out, d_chars, (unsigned __int128)(unsigned long long)n_chars * sizeof(int32_t)) ||
-      ta_overlap(d_matches, out, d_offsets, ((unsigned __int128)(unsigned)n_texts + 1) * sizeof(int32_t)) ||
-      ta_overlap(d_matches, out, d_pairs, (unsigned __int128)(unsigned)n_pairs * 2 * sizeof(int32_t)))
-    return fail(TACO_ERR_ARG, "d_matches and an input buffer overlap");
+  TRY(no_overlap({{d_matches, (u128)(unsigned)n_pairs * sizeof(int32_t), "d_matches"},
+                  {d_chars, (u128)(unsigned long long)n_chars * sizeof(int32_t), "d_chars"},
+                  {d_offsets, ((u128)(unsigned)n_texts + 1) * sizeof(int32_t), "d_offsets"},
+                  {d_pairs, (u128)(unsigned)n_pairs * 2 * sizeof(int32_t), "d_pairs"}}, 1));
   if (n_pairs == 0) return 0;
   const dim3 grid((unsigned)cdiv(n_pairs, TA_WAVES)), block(TA_WAVES * 64);
   hipStream_t st = (hipStream_t)hip_stream;
@@ -47,11 +40,10 @@ int taco_text_best_two(void* hip_stream, const int32_t* d_matches, const int32_t
   if (!d_matches || !d_pairs || !d_offsets || !d_group_offsets || !d_best) return fail(TACO_ERR_ARG, "null pointer");
   if (n_texts < 0 || n_groups < 0) return fail(TACO_ERR_ARG, "n_texts and n_groups must be >= 0, got %d, %d", n_texts, n_groups);
   // the pair count is not an argument: of d_matches and d_pairs the first element is what can be checked
-  const unsigned __int128 out = (unsigned __int128)(unsigned)n_groups * 4 * sizeof(int32_t);
-  if (ta_overlap(d_best, out, d_offsets, ((unsigned __int128)(unsigned)n_texts + 1) * sizeof(int32_t)) ||
-      ta_overlap(d_best, out, d_group_offsets, ((unsigned __int128)(unsigned)n_groups + 1) * sizeof(int32_t)) ||
-      ta_overlap(d_best, out, d_matches, sizeof(int32_t)) || ta_overlap(d_best, out, d_pairs, 2 * sizeof(int32_t)))
-    return fail(TACO_ERR_ARG, "d_best and an input buffer overlap");
+  TRY(no_overlap({{d_best, (u128)(unsigned)n_groups * 4 * sizeof(int32_t), "d_best"},
+                  {d_offsets, ((u128)(unsigned)n_texts + 1) * sizeof(int32_t), "d_offsets"},
+                  {d_group_offsets, ((u128)(unsigned)n_groups + 1) * sizeof(int32_t), "d_group_offsets"},
+                  {d_matches, sizeof(int32_t), "d_matches"}, {d_pairs, 2 * sizeof(int32_t), "d_pairs"}}, 1));
   if (n_groups == 0) return 0;
   hipLaunchKernelGGL(k_text_best_two, dim3((unsigned)cdiv(n_groups, TA_WAVES)), dim3(TA_WAVES * 64), 0, (hipStream_t)hip_stream, d_matches, d_pairs,
                      d_offsets, n_texts, d_group_offsets, n_groups, d_best);

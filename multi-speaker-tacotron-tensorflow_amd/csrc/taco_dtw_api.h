@@ -13,17 +13,11 @@ int taco_dtw(void* hip_stream, const float* d_a, const int32_t* d_len_a, const f
   if (cost_kind != 0 && cost_kind != 1) return fail(TACO_ERR_ARG, "cost_kind = %d: accepted are 0 (mean absolute) and 1 (Euclidean)", cost_kind);
   const size_t need = taco_dtw_workspace_bytes(B, Ta, Tb, D);
   if (need && !d_workspace) return fail(TACO_ERR_ARG, "null workspace");
-  {
-    typedef unsigned __int128 u128;
-    const u128 nb = (u128)(unsigned)B;
-    const void* ptr[8] = {d_dist, d_total, d_dir, need ? d_workspace : nullptr, d_a, d_b, d_len_a, d_len_b};      // four outputs, then four inputs
-    const u128 len[8] = {nb * sizeof(float), nb * sizeof(float), nb * (unsigned)Ta * (unsigned)Tb, (u128)need,
-                         nb * (unsigned)Ta * (unsigned)D * sizeof(float), nb * (unsigned)Tb * (unsigned)D * sizeof(float),
-                         nb * sizeof(int32_t), nb * sizeof(int32_t)};
-    for (int o = 0; o < 4; ++o)
-      for (int q = o + 1; q < 8; ++q)
-        if (ptr[o] && ptr[q] && ta_overlap(ptr[o], len[o], ptr[q], len[q])) return fail(TACO_ERR_ARG, "an output overlaps an input or another output");
-  }
+  const u128 nb = (u128)(unsigned)B;
+  TRY(no_overlap({{d_dist, nb * sizeof(float), "d_dist"}, {d_total, nb * sizeof(float), "d_total"}, {d_dir, nb * (unsigned)Ta * (unsigned)Tb, "d_dir"},
+                  {d_workspace, (u128)need, "d_workspace"},                                                        // four outputs, then four inputs
+                  {d_a, nb * (unsigned)Ta * (unsigned)D * sizeof(float), "d_a"}, {d_b, nb * (unsigned)Tb * (unsigned)D * sizeof(float), "d_b"},
+                  {d_len_a, nb * sizeof(int32_t), "d_len_a"}, {d_len_b, nb * sizeof(int32_t), "d_len_b"}}, 4));
   if (D > DTW_DMAX) return fail(TACO_ERR_UNSUPPORTED, "D = %d: taco_dtw keeps a column's features in registers, up to D = %d", D, DTW_DMAX);
   if (workspace_bytes < need) return fail(TACO_ERR_STATE, "workspace of %zu bytes, taco_dtw_workspace_bytes asks for %zu", workspace_bytes, need);
   hipStream_t st = (hipStream_t)hip_stream;
@@ -41,16 +35,10 @@ int taco_dtw_path(void* hip_stream, const uint8_t* d_dir, const int32_t* d_len_a
                   int32_t* d_path_len) {
   if (!d_dir || !d_path || !d_path_len) return fail(TACO_ERR_ARG, "null pointer");
   if (B < 1 || Ta < 1 || Tb < 1) return fail(TACO_ERR_ARG, "B, Ta and Tb must be >= 1, got %d, %d, %d", B, Ta, Tb);
-  {
-    typedef unsigned __int128 u128;
-    const u128 nb = (u128)(unsigned)B;
-    const void* ptr[5] = {d_path, d_path_len, d_dir, d_len_a, d_len_b};                                           // two outputs, then three inputs
-    const u128 len[5] = {nb * ((u128)(unsigned)Ta + (unsigned)Tb - 1) * 2 * sizeof(int32_t), nb * sizeof(int32_t), nb * (unsigned)Ta * (unsigned)Tb,
-                         nb * sizeof(int32_t), nb * sizeof(int32_t)};
-    for (int o = 0; o < 2; ++o)
-      for (int q = o + 1; q < 5; ++q)
-        if (ptr[o] && ptr[q] && ta_overlap(ptr[o], len[o], ptr[q], len[q])) return fail(TACO_ERR_ARG, "an output overlaps an input or another output");
-  }
+  const u128 nb = (u128)(unsigned)B;
+  TRY(no_overlap({{d_path, nb * ((u128)(unsigned)Ta + (unsigned)Tb - 1) * 2 * sizeof(int32_t), "d_path"}, {d_path_len, nb * sizeof(int32_t), "d_path_len"},
+                  {d_dir, nb * (unsigned)Ta * (unsigned)Tb, "d_dir"},                                              // two outputs, then three inputs
+                  {d_len_a, nb * sizeof(int32_t), "d_len_a"}, {d_len_b, nb * sizeof(int32_t), "d_len_b"}}, 2));
   hipLaunchKernelGGL(k_dtw_path, dim3((unsigned)std::min(B, DTW_MAXGRID)), dim3(64), 0, (hipStream_t)hip_stream, d_dir, d_len_a, d_len_b, B, Ta, Tb,
                      d_path, d_path_len);
   HIPCHK(hipGetLastError());

@@ -12,15 +12,9 @@ static int f0_yin_check(const float* d_wav, const int32_t* d_num_samples, int B,
   if (!(threshold > 0.f) || !(threshold <= 1.f)) return fail(TACO_ERR_ARG, "threshold = %g is outside (0, 1]", (double)threshold);
   const int nf = 1 + L / hop;
   *F = nf;
-  {
-    typedef unsigned __int128 u128;
-    const u128 nb = (u128)(unsigned)B, nout = nb * (unsigned)nf * sizeof(float);
-    const void* ptr[5] = {d_f0, d_aper, d_lag, d_wav, d_num_samples};                                             // three outputs, then two inputs
-    const u128 len[5] = {nout, nout, nout, nb * (unsigned)L * sizeof(float), nb * sizeof(int32_t)};
-    for (int o = 0; o < 3; ++o)
-      for (int q = o + 1; q < 5; ++q)
-        if (ptr[o] && ptr[q] && ta_overlap(ptr[o], len[o], ptr[q], len[q])) return fail(TACO_ERR_ARG, "an output overlaps an input or another output");
-  }
+  const u128 nb = (u128)(unsigned)B, nout = nb * (unsigned)nf * sizeof(float);
+  TRY(no_overlap({{d_f0, nout, "d_f0"}, {d_aper, nout, "d_aper"}, {d_lag, nout, "d_lag"},                         // three outputs, then two inputs
+                  {d_wav, nb * (unsigned)L * sizeof(float), "d_wav"}, {d_num_samples, nb * sizeof(int32_t), "d_num_samples"}}, 3));
   if (hi + (double)window + 2.0 > (double)YIN_FRAME_MAX)
     return fail(TACO_ERR_UNSUPPORTED, "a frame of window + tau_max + 2 = %d + %.0f + 2 floats: k_yin holds a frame and its lag sums in LDS, up to %d",
                 window, hi, YIN_FRAME_MAX);
@@ -30,37 +24,35 @@ static int f0_yin_check(const float* d_wav, const int32_t* d_num_samples, int B,
   return 0;
 }
 
-int taco_f0_yin(void* hip_stream, const float* d_wav, const int32_t* d_num_samples, int B, int L, int sample_rate, int hop, int window, float fmin,
-                float fmax, float threshold, float* d_f0, float* d_aper, int32_t* d_lag) {
+// plain: k_yin<true>, the form that walks j (taco_debug_f0_yin_plain: the benchmark and one equality test)
+static int f0_yin(void* hip_stream, const float* d_wav, const int32_t* d_num_samples, int B, int L, int sample_rate, int hop, int window, float fmin,
+                  float fmax, float threshold, float* d_f0, float* d_aper, int32_t* d_lag, bool plain) {
   int tau_min, tau_max, F;
   YinPlan pl;
   TRY(f0_yin_check(d_wav, d_num_samples, B, L, sample_rate, hop, window, fmin, fmax, threshold, d_f0, d_aper, d_lag, &tau_min, &tau_max, &F, &pl));
-  return yin_launch<false>((hipStream_t)hip_stream, pl, d_wav, d_num_samples, B, L, F, hop, window, tau_min, tau_max, (float)sample_rate, threshold,
-                           d_f0, d_aper, d_lag);
+  const auto launch = !plain ? yin_launch<false> : yin_launch<true>;      // k_yin<false> is instantiated first: the order of the code object
+  return launch((hipStream_t)hip_stream, pl, d_wav, d_num_samples, B, L, F, hop, window, tau_min, tau_max, (float)sample_rate, threshold, d_f0, d_aper,
+                d_lag);
+}
+
+int taco_f0_yin(void* hip_stream, const float* d_wav, const int32_t* d_num_samples, int B, int L, int sample_rate, int hop, int window, float fmin,
+                float fmax, float threshold, float* d_f0, float* d_aper, int32_t* d_lag) {
+  return f0_yin(hip_stream, d_wav, d_num_samples, B, L, sample_rate, hop, window, fmin, fmax, threshold, d_f0, d_aper, d_lag, false);
 }
 
 int taco_debug_f0_yin_plain(void* hip_stream, const float* d_wav, const int32_t* d_num_samples, int B, int L, int sample_rate, int hop, int window,
                             float fmin, float fmax, float threshold, float* d_f0, float* d_aper, int32_t* d_lag) {
-  int tau_min, tau_max, F;
-  YinPlan pl;
-  TRY(f0_yin_check(d_wav, d_num_samples, B, L, sample_rate, hop, window, fmin, fmax, threshold, d_f0, d_aper, d_lag, &tau_min, &tau_max, &F, &pl));
-  return yin_launch<true>((hipStream_t)hip_stream, pl, d_wav, d_num_samples, B, L, F, hop, window, tau_min, tau_max, (float)sample_rate, threshold,
-                          d_f0, d_aper, d_lag);
+  return f0_yin(hip_stream, d_wav, d_num_samples, B, L, sample_rate, hop, window, fmin, fmax, threshold, d_f0, d_aper, d_lag, true);
 }
 
 int taco_f0_path_stats(void* hip_stream, const float* d_f0_a, int Fa, const float* d_f0_b, int Fb, const int32_t* d_path, const int32_t* d_path_len,
                        int B, int path_cap, float* d_stats) {
   if (!d_f0_a || !d_f0_b || !d_path || !d_path_len || !d_stats) return fail(TACO_ERR_ARG, "null pointer");
   if (B < 1 || Fa < 1 || Fb < 1 || path_cap < 1) return fail(TACO_ERR_ARG, "B, Fa, Fb and path_cap must be >= 1, got %d, %d, %d, %d", B, Fa, Fb, path_cap);
-  {
-    typedef unsigned __int128 u128;
-    const u128 nb = (u128)(unsigned)B;
-    const void* ptr[4] = {d_f0_a, d_f0_b, d_path, d_path_len};
-    const u128 len[4] = {nb * (unsigned)Fa * sizeof(float), nb * (unsigned)Fb * sizeof(float), nb * (unsigned)path_cap * 2 * sizeof(int32_t),
-                         nb * sizeof(int32_t)};
-    for (int q = 0; q < 4; ++q)
-      if (ta_overlap(d_stats, nb * 4 * sizeof(float), ptr[q], len[q])) return fail(TACO_ERR_ARG, "the output overlaps an input");
-  }
+  const u128 nb = (u128)(unsigned)B;
+  TRY(no_overlap({{d_stats, nb * 4 * sizeof(float), "d_stats"}, {d_f0_a, nb * (unsigned)Fa * sizeof(float), "d_f0_a"},
+                  {d_f0_b, nb * (unsigned)Fb * sizeof(float), "d_f0_b"}, {d_path, nb * (unsigned)path_cap * 2 * sizeof(int32_t), "d_path"},
+                  {d_path_len, nb * sizeof(int32_t), "d_path_len"}}, 1));
   hipLaunchKernelGGL(k_f0_path_stats, dim3((unsigned)std::min(B, YIN_MAXGRID)), dim3(F0S_NT), 0, (hipStream_t)hip_stream, d_f0_a, Fa, d_f0_b, Fb,
                      d_path, d_path_len, B, path_cap, d_stats);
   HIPCHK(hipGetLastError());

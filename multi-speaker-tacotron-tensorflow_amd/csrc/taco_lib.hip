@@ -22,6 +22,7 @@
 #include <cstring>
 #include <cstdlib>
 #include <functional>
+#include <initializer_list>
 #include <map>
 #include <string>
 #include <vector>
@@ -38,6 +39,25 @@ static int fail(int code, const char* fmt, ...) {
   va_end(ap);
   g_err = buf;
   return code;
+}
+
+// "An output must not overlap an input or another output": an entry point lists its buffers as spans, the outputs first.  Byte counts are
+// 128-bit so that element counts near 2^63 are not mistaken for small ones.
+typedef unsigned __int128 u128;
+struct Span { const void* p; u128 bytes; const char* name; };
+
+// [p, p + bytes) and [q, q + qbytes) share a byte
+static bool ta_overlap(const void* p, u128 bytes, const void* q, u128 qbytes) {
+  const u128 a = (uintptr_t)p, b = (uintptr_t)q;
+  return bytes && qbytes && a < b + qbytes && b < a + bytes;
+}
+
+// each of the first n_out spans against every span behind it; null pointers and spans of no bytes overlap nothing
+static int no_overlap(std::initializer_list<Span> spans, int n_out) {
+  for (const Span* o = spans.begin(); o < spans.begin() + n_out; ++o)
+    for (const Span* q = o + 1; q < spans.end(); ++q)
+      if (o->p && q->p && ta_overlap(o->p, o->bytes, q->p, q->bytes)) return fail(TACO_ERR_ARG, "%s and %s overlap", o->name, q->name);
+  return 0;
 }
 // ------------------------------------------------------------------------------------------------
 // one whole-chip kernel at a time per device and process
@@ -1872,9 +1892,8 @@ int taco_attention_trim(void* hip_stream, const float* d_alignments, const int32
 int taco_manual_alignments(void* hip_stream, const float* d_alignments, int B, int T_in, int n_steps, int mode, float* d_manual) {
   if (!d_alignments || !d_manual) return fail(TACO_ERR_ARG, "null pointer");
   if (B < 1 || T_in < 1 || n_steps < 1) return fail(TACO_ERR_ARG, "B, T_in and n_steps must be >= 1, got %d, %d, %d", B, T_in, n_steps);
-  const unsigned __int128 bytes = (unsigned __int128)B * (unsigned)T_in * (unsigned)n_steps * sizeof(float);
-  const unsigned __int128 in = (uintptr_t)d_alignments, out = (uintptr_t)d_manual;
-  if (in < out + bytes && out < in + bytes) return fail(TACO_ERR_ARG, "d_alignments and d_manual overlap: the transpose cannot run in place");
+  const u128 bytes = (u128)B * (unsigned)T_in * (unsigned)n_steps * sizeof(float);
+  TRY(no_overlap({{d_manual, bytes, "d_manual"}, {d_alignments, bytes, "d_alignments"}}, 1));      // the transpose cannot run in place
   if (mode == 2) return fail(TACO_ERR_UNSUPPORTED, "manual_attention_mode 2 is broken in the reference (np.pow, synthesizer.py:181-188)");
   if (mode != 1 && mode != 3) return fail(TACO_ERR_ARG, "manual_attention_mode %d: accepted are 1 (argmax one hot) and 3 (prunning)", mode);
   const int tiles = (T_in + MA_TE - 1) / MA_TE;

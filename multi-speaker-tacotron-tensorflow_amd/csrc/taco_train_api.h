@@ -496,12 +496,10 @@ void taco_segnorm_plan_destroy(taco_segnorm_plan* p) {
 static int segnorm_check_buffers(const float* d_flat, size_t n, int n_seg, const float* d_norms, const float* d_stats, const int32_t* d_argmax) {
   if (!d_flat || !d_norms || !d_stats) return fail(TACO_ERR_ARG, "null pointer");
   if (reinterpret_cast<uintptr_t>(d_flat) & 3) return fail(TACO_ERR_ARG, "the input buffer %p is not 4-byte aligned", (const void*)d_flat);
-  const unsigned __int128 in = (uintptr_t)d_flat, in_end = in + (unsigned __int128)n * sizeof(float);
-  const auto overlaps = [&](const void* q, size_t bytes) { const unsigned __int128 o = (uintptr_t)q; return q && in < o + bytes && o < in_end; };
-  if (overlaps(d_norms, (size_t)n_seg * sizeof(float))) return fail(TACO_ERR_ARG, "d_norms and the input buffer overlap");
-  if (overlaps(d_stats, 2 * sizeof(float))) return fail(TACO_ERR_ARG, "d_stats and the input buffer overlap");
-  if (overlaps(d_argmax, sizeof(int32_t))) return fail(TACO_ERR_ARG, "d_argmax and the input buffer overlap");
-  return 0;
+  const Span in = {d_flat, (u128)n * sizeof(float), "the input buffer"};      // each output against the input, not against the other outputs
+  TRY(no_overlap({{d_norms, (u128)(size_t)n_seg * sizeof(float), "d_norms"}, in}, 1));
+  TRY(no_overlap({{d_stats, 2 * sizeof(float), "d_stats"}, in}, 1));
+  return no_overlap({{d_argmax, sizeof(int32_t), "d_argmax"}, in}, 1);
 }
 
 int taco_segment_norms(const taco_segnorm_plan* p, void* hip_stream, const float* d_flat, size_t n, float* d_norms, float* d_stats, int32_t* d_argmax) {

@@ -23,6 +23,10 @@ import os
 import collections
 
 import numpy as np
+import torch
+
+from . import _lib
+from ._device import STREAM, call, pointer
 
 Example = collections.namedtuple("Example", "tokens loss_coeff mel linear speaker_id")
 Example.__new__.__defaults__ = (None,)
@@ -270,17 +274,11 @@ def collate_streams(device, streams, index, n_rows, n_items):
     """ONE taco_collate launch on the device's current stream: row i of every stream's `out` (and entry i of its `counts`) is item
     index[i] (device int32 [n_rows]) of the n_items its `pack` holds.  A stream is a dict of TacoCollateStream's fields (include/taco_abi.h):
     pack, start, rows, out, counts are device tensors or None, width and rows_out ints."""
-    import ctypes as C
-    import torch
-    from . import _lib
-    ptr = lambda t: None if t is None else t.data_ptr()
     arr = (_lib.TacoCollateStream * len(streams))()
     for a, d in zip(arr, streams):
-        a.pack, a.start, a.rows, a.out, a.counts = ptr(d["pack"]), ptr(d["start"]), ptr(d["rows"]), ptr(d["out"]), ptr(d["counts"])
+        a.pack, a.start, a.rows, a.out, a.counts = (pointer(d[k]) for k in ("pack", "start", "rows", "out", "counts"))
         a.width, a.rows_out = d["width"], d["rows_out"]
-    with torch.cuda.device(device):
-        _lib.check(_lib.load_library().taco_collate(C.c_void_p(torch.cuda.current_stream().cuda_stream), arr, len(streams),
-                                                    C.c_void_p(index.data_ptr()), n_rows, n_items))
+    call(device, _lib.load_library().taco_collate, STREAM, arr, len(streams), index, n_rows, n_items)
 
 
 class RefSource(object):
@@ -439,7 +437,6 @@ class DeviceCorpus(object):
 
     def finalize(self):
         """Pack the examples and upload them once.  Raises when the corpus does not fit the device's free memory."""
-        import torch
         if self._on_device:
             return self
         if self._packs is None:
@@ -486,7 +483,6 @@ class DeviceCorpus(object):
     # ---- batches ----
     def _buffer(self, name, shape, dtype):
         """Grow-only scratch of the corpus (index upload, waveform rectangle, counts): no allocation once a shape has been seen."""
-        import torch
         n = int(np.prod(shape))
         t = self._scratch.get(name)
         if t is None or t.numel() < n:
@@ -498,7 +494,6 @@ class DeviceCorpus(object):
         (uploaded, 4 * B bytes) or a device int32 tensor, which the host cannot see: the shapes then come from `out` or, without it,
         from the corpus-wide maxima, and an index outside the corpus gives an all-zero row.  out: a Batch of preallocated contiguous
         tensors of the right shapes, written in place (nothing is allocated)."""
-        import torch
         if not self._on_device:
             raise Exception("call finalize() first")
         r, p = int(reduction_factor), self._packs

@@ -7,25 +7,19 @@ as float64 NumPy, in tests/dtw_reference.py).
 That distance, on cepstra, measures the spectral envelope.  The source is measured beside it: YIN F0 tracks of a waveform on the
 spectrogram's frame grid (f0_track: taco_f0_yin, csrc/taco_f0.h) and, along the warping path, the F0 RMSE in cents and the
 voiced/unvoiced error (f0_errors: taco_f0_path_stats); prosody_distance gives all three numbers for two waveform batches."""
-import ctypes as C
 import math
 
 import numpy as np
+import torch
+
+from . import _lib
+from ._device import STREAM, buffers, call, device_of, tensor
 
 COSTS = {"l1": 0, "l2": 1}       # cost_kind of taco_dtw: mean absolute difference per frame / Euclidean distance per frame
 
-_BUFFERS = {}                    # (device, B, Ta, Tb, D) -> the outputs and workspace of that shape; a call reuses them
-
-
-def _dev_tensor(x, dtype, device):
-    import torch
-    if not torch.is_tensor(x):
-        x = torch.as_tensor(np.asarray(x))
-    return x.to(device=device, dtype=dtype).contiguous()
-
-
-def _ptr(t):
-    return C.c_void_p(t.data_ptr()) if t is not None else None
+# the result tensors (and the workspace) of every shape a call was made with; the next call of that shape reuses them:
+# (device, "dtw", B, Ta, Tb, D), (device, "f0", B, L, hop) and (device, "f0_stats", B, Fa, Fb, cap)
+_BUFFERS = {}
 
 
 def dtw_distance(a, b, len_a=None, len_b=None, cost="l1", return_total=False, return_path=False, device=None):
@@ -39,43 +33,29 @@ def dtw_distance(a, b, len_a=None, len_b=None, cost="l1", return_total=False, re
     G(n-1, m-1); with return_path also (path [B, Ta+Tb-1, 2] int32 rows (i, j) from (0, 0) to (n-1, m-1), -1 past path_len; path_len
     [B]).  The result tensors belong to a buffer set kept per shape: the next call of the same shape overwrites them (clone to keep),
     which is also what lets the call be captured in a graph and replayed."""
-    import torch
-    from . import _lib
     lib = _lib.load_library()
     if cost not in COSTS:
         raise _lib.TacoError(_lib.TACO_ERR_ARG, "cost must be one of %s, got %r" % (sorted(COSTS), cost))
-    if device is None:
-        device = a.device if torch.is_tensor(a) and a.is_cuda else (b.device if torch.is_tensor(b) and b.is_cuda else
-                                                                    torch.device("cuda:%d" % torch.cuda.current_device()))
-    dev = torch.device(device)
-    a, b = _dev_tensor(a, torch.float32, dev), _dev_tensor(b, torch.float32, dev)
+    dev = torch.device(device) if device is not None else device_of(a, b)
+    a, b = tensor(a, dev, torch.float32, "a"), tensor(b, dev, torch.float32, "b")
     if a.dim() != 3 or b.dim() != 3 or a.shape[0] != b.shape[0] or a.shape[2] != b.shape[2]:
         raise _lib.TacoError(_lib.TACO_ERR_SHAPE, "a and b must be [B, Ta, D] and [B, Tb, D], got %s and %s" % (tuple(a.shape), tuple(b.shape)))
     B, Ta, D = a.shape
     Tb = b.shape[1]
-    la = None if len_a is None else _dev_tensor(len_a, torch.int32, dev)
-    lb = None if len_b is None else _dev_tensor(len_b, torch.int32, dev)
+    la = None if len_a is None else tensor(len_a, dev, torch.int32, "len_a")
+    lb = None if len_b is None else tensor(len_b, dev, torch.int32, "len_b")
     for l in (la, lb):
         if l is not None and tuple(l.shape) != (B,):
             raise _lib.TacoError(_lib.TACO_ERR_SHAPE, "lengths must be [B] = (%d,), got %s" % (B, tuple(l.shape)))
-    key = (str(dev), B, Ta, Tb, D)
-    buf = _BUFFERS.get(key)
-    if buf is None:
-        nws = int(lib.taco_dtw_workspace_bytes(B, Ta, Tb, D))
-        buf = _BUFFERS[key] = {"dist": torch.empty(B, dtype=torch.float32, device=dev),
-                               "total": torch.empty(B, dtype=torch.float32, device=dev),
-                               "ws": torch.empty(nws, dtype=torch.uint8, device=dev) if nws else None}
-    if return_path and "dir" not in buf:
-        buf["dir"] = torch.empty((B, Ta, Tb), dtype=torch.uint8, device=dev)
-        buf["path"] = torch.empty((B, Ta + Tb - 1, 2), dtype=torch.int32, device=dev)
-        buf["path_len"] = torch.empty(B, dtype=torch.int32, device=dev)
-    ws = buf["ws"]
-    with torch.cuda.device(dev):
-        stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
-        _lib.check(lib.taco_dtw(stream, _ptr(a), _ptr(la), _ptr(b), _ptr(lb), B, Ta, Tb, D, COSTS[cost], _ptr(buf["dist"]), _ptr(buf["total"]),
-                                _ptr(buf["dir"]) if return_path else None, _ptr(ws), ws.numel() if ws is not None else 0))
-        if return_path:
-            _lib.check(lib.taco_dtw_path(stream, _ptr(buf["dir"]), _ptr(la), _ptr(lb), B, Ta, Tb, _ptr(buf["path"]), _ptr(buf["path_len"])))
+    specs = {"dist": ((B,), torch.float32), "total": ((B,), torch.float32), "ws": ((int(lib.taco_dtw_workspace_bytes(B, Ta, Tb, D)),), torch.uint8)}
+    if return_path:
+        specs.update(dir=((B, Ta, Tb), torch.uint8), path=((B, Ta + Tb - 1, 2), torch.int32), path_len=((B,), torch.int32))
+    buf = buffers(_BUFFERS, (str(dev), "dtw", B, Ta, Tb, D), **specs)
+    ws = buf["ws"]            # of no bytes where one strip holds a pair: its pointer is null then
+    call(dev, lib.taco_dtw, STREAM, a, la, b, lb, B, Ta, Tb, D, COSTS[cost], buf["dist"], buf["total"], buf["dir"] if return_path else None,
+         ws, ws.numel())
+    if return_path:
+        call(dev, lib.taco_dtw_path, STREAM, buf["dir"], la, lb, B, Ta, Tb, buf["path"], buf["path_len"])
     out = (buf["dist"],)
     if return_total:
         out += (buf["total"],)
@@ -95,7 +75,6 @@ def mel_cepstra(mel, hparams=None, n_cepstra=13):
     L = (clip(x, 0, 1) * -min_level_db + min_level_db) * ln 10 / 20 (the natural log of the mel amplitude that audio/__init__.py's
     _normalize encoded), c_k = sqrt(2/M) * sum_m L_m cos(pi k (m + 1/2) / M) for k = 1 .. n_cepstra (a DCT-II without its k = 0 term,
     which is the level)."""
-    import torch
     from .hparams import hparams as default_hparams
     hp = hparams if hparams is not None else default_hparams
     x = (mel if torch.is_tensor(mel) else torch.as_tensor(np.asarray(mel))).to(torch.float32)      # stays where it is: plumbing
@@ -129,7 +108,6 @@ def mel_cepstral_distortion(mel_a, mel_b, len_a=None, len_b=None, hparams=None, 
 
 
 # ---- pitch: YIN F0 tracks, F0 RMSE and V/UV error along a warping path (taco_f0_yin, taco_f0_path_stats: csrc/taco_f0.h) ----
-_F0_BUFFERS = {}                 # (device, B, L, hop) -> f0, aper, lag of that shape;  (device, B, Fa, Fb, cap) -> stats
 _SPEC = {}                       # (device, the audio hparams' values) -> the audio.Spectrogram handle prosody_distance makes its mels with
 
 
@@ -162,17 +140,13 @@ def f0_track(wav, num_samples=None, hparams=None, fmin=60.0, fmax=500.0, thresho
     Returns f0 [B, F] (float32, on the device; nothing is downloaded and nothing waits); with return_aperiodicity also d'(tau*) [B, F],
     with return_lag also tau* [B, F] int32.  The tensors belong to a buffer set kept per shape: the next call of the same shape overwrites
     them (clone to keep), which is what lets the call be captured in a graph and replayed."""
-    import torch
-    from . import _lib
     lib = _lib.load_library()
-    if device is None:
-        device = wav.device if torch.is_tensor(wav) and wav.is_cuda else torch.device("cuda:%d" % torch.cuda.current_device())
-    dev = torch.device(device)
-    x = _dev_tensor(wav, torch.float32, dev)
+    dev = torch.device(device) if device is not None else device_of(wav)
+    x = tensor(wav, dev, torch.float32, "wav")
     if x.dim() != 2:
         raise _lib.TacoError(_lib.TACO_ERR_SHAPE, "wav must be [B, L], got %s" % (tuple(x.shape),))
     B, L = x.shape
-    ns = None if num_samples is None else _dev_tensor(num_samples, torch.int32, dev)
+    ns = None if num_samples is None else tensor(num_samples, dev, torch.int32, "num_samples")
     if ns is not None and tuple(ns.shape) != (B,):
         raise _lib.TacoError(_lib.TACO_ERR_SHAPE, "num_samples must be [B] = (%d,), got %s" % (B, tuple(ns.shape)))
     sr, hop, frame = framing(hparams)
@@ -180,18 +154,14 @@ def f0_track(wav, num_samples=None, hparams=None, fmin=60.0, fmax=500.0, thresho
     if B < 1 or L < 1 or hop < 1:
         raise _lib.TacoError(_lib.TACO_ERR_ARG, "wav [%d, %d] at hop %d: every one must be >= 1" % (B, L, hop))
     F = 1 + L // hop
-    key = (str(dev), B, L, hop)
-    buf = _F0_BUFFERS.get(key)
-    if buf is None:
-        buf = _F0_BUFFERS[key] = {"f0": torch.empty((B, F), dtype=torch.float32, device=dev)}
-    if return_aperiodicity and "aper" not in buf:
-        buf["aper"] = torch.empty((B, F), dtype=torch.float32, device=dev)
-    if return_lag and "lag" not in buf:
-        buf["lag"] = torch.empty((B, F), dtype=torch.int32, device=dev)
-    with torch.cuda.device(dev):
-        stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
-        _lib.check(lib.taco_f0_yin(stream, _ptr(x), _ptr(ns), B, L, sr, hop, W, float(fmin), float(fmax), float(threshold), _ptr(buf["f0"]),
-                                   _ptr(buf["aper"]) if return_aperiodicity else None, _ptr(buf["lag"]) if return_lag else None))
+    specs = {"f0": ((B, F), torch.float32)}
+    if return_aperiodicity:
+        specs["aper"] = ((B, F), torch.float32)
+    if return_lag:
+        specs["lag"] = ((B, F), torch.int32)
+    buf = buffers(_BUFFERS, (str(dev), "f0", B, L, hop), **specs)
+    call(dev, lib.taco_f0_yin, STREAM, x, ns, B, L, sr, hop, W, float(fmin), float(fmax), float(threshold), buf["f0"],
+         buf["aper"] if return_aperiodicity else None, buf["lag"] if return_lag else None)
     out = (buf["f0"],)
     if return_aperiodicity:
         out += (buf["aper"],)
@@ -203,27 +173,20 @@ def f0_track(wav, num_samples=None, hparams=None, fmin=60.0, fmax=500.0, thresho
 def f0_path_stats(f0_a, f0_b, path, path_len):
     """The four sums behind f0_errors, [B, 4] float32 on the device (taco_f0_path_stats): sum of squared cents over the path entries voiced
     on both sides, their number, the entries voiced on one side only, the entries used.  Kept per shape like every result here."""
-    import torch
-    from . import _lib
     lib = _lib.load_library()
     if not (torch.is_tensor(f0_a) and f0_a.is_cuda):
         raise _lib.TacoError(_lib.TACO_ERR_ARG, "f0_a must be a device tensor (f0_track returns one)")
     dev = f0_a.device
-    a, b = _dev_tensor(f0_a, torch.float32, dev), _dev_tensor(f0_b, torch.float32, dev)
-    pth, pl = _dev_tensor(path, torch.int32, dev), _dev_tensor(path_len, torch.int32, dev)
+    a, b = tensor(f0_a, dev, torch.float32, "f0_a"), tensor(f0_b, dev, torch.float32, "f0_b")
+    pth, pl = tensor(path, dev, torch.int32, "path"), tensor(path_len, dev, torch.int32, "path_len")
     if a.dim() != 2 or b.dim() != 2 or pth.dim() != 3 or pth.shape[2] != 2 or not (a.shape[0] == b.shape[0] == pth.shape[0]) or \
             tuple(pl.shape) != (a.shape[0],):
         raise _lib.TacoError(_lib.TACO_ERR_SHAPE, "f0_a [B, Fa], f0_b [B, Fb], path [B, cap, 2], path_len [B]; got %s, %s, %s, %s"
                              % (tuple(a.shape), tuple(b.shape), tuple(pth.shape), tuple(pl.shape)))
     B, Fa = a.shape
     Fb, cap = b.shape[1], pth.shape[1]
-    key = (str(dev), B, Fa, Fb, cap)
-    stats = _F0_BUFFERS.get(key)
-    if stats is None:
-        stats = _F0_BUFFERS[key] = torch.empty((B, 4), dtype=torch.float32, device=dev)
-    with torch.cuda.device(dev):
-        stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
-        _lib.check(lib.taco_f0_path_stats(stream, _ptr(a), Fa, _ptr(b), Fb, _ptr(pth), _ptr(pl), B, cap, _ptr(stats)))
+    stats = buffers(_BUFFERS, (str(dev), "f0_stats", B, Fa, Fb, cap), stats=((B, 4), torch.float32))["stats"]
+    call(dev, lib.taco_f0_path_stats, STREAM, a, Fa, b, Fb, pth, pl, B, cap, stats)
     return stats
 
 
@@ -236,7 +199,6 @@ def f0_errors(f0_a, f0_b, path, path_len):
         voiced_frames = entries voiced on both sides.
     A NaN in a track at a used entry makes that pair's rmse NaN.  Returns (rmse_cents, vuv_error, voiced_frames), each [B] float32 on
     the device; the sums are taco_f0_path_stats's, the three divisions and the root are torch plumbing.  Nothing is downloaded."""
-    import torch
     s = f0_path_stats(f0_a, f0_b, path, path_len)
     return torch.sqrt(s[:, 0] / s[:, 1]), s[:, 2] / s[:, 3], s[:, 1].clone()
 
@@ -259,21 +221,15 @@ def prosody_distance(wav_a, wav_b, num_a=None, num_b=None, hparams=None, **f0_kw
     so the path indexes them directly.  Each piece is this project's own definition, UNPINNED on any package (see mel_cepstral_distortion,
     f0_track, f0_errors).  Returns a dict of [B] device tensors: mcd (dB), f0_rmse_cents, vuv_error, voiced_frames.  Nothing is
     downloaded and nothing waits; the spectrogram handle and every buffer set are kept for the next call."""
-    import torch
-    from . import _lib
     extra = sorted(set(f0_kw) - {"fmin", "fmax", "threshold", "window"})
     if extra:
         raise _lib.TacoError(_lib.TACO_ERR_ARG, "prosody_distance passes fmin, fmax, threshold and window on to f0_track, not %s" % ", ".join(extra))
-    dev = None
-    for w in (wav_a, wav_b):
-        if dev is None and torch.is_tensor(w) and w.is_cuda:
-            dev = w.device
-    dev = dev if dev is not None else torch.device("cuda:%d" % torch.cuda.current_device())
-    a, b = _dev_tensor(wav_a, torch.float32, dev), _dev_tensor(wav_b, torch.float32, dev)
+    dev = device_of(wav_a, wav_b)
+    a, b = tensor(wav_a, dev, torch.float32, "wav_a"), tensor(wav_b, dev, torch.float32, "wav_b")
     if a.dim() != 2 or b.dim() != 2 or a.shape[0] != b.shape[0]:
         raise _lib.TacoError(_lib.TACO_ERR_SHAPE, "wav_a and wav_b must be [B, La] and [B, Lb], got %s and %s" % (tuple(a.shape), tuple(b.shape)))
-    na = None if num_a is None else _dev_tensor(num_a, torch.int32, dev)
-    nb = None if num_b is None else _dev_tensor(num_b, torch.int32, dev)
+    na = None if num_a is None else tensor(num_a, dev, torch.int32, "num_a")
+    nb = None if num_b is None else tensor(num_b, dev, torch.int32, "num_b")
     spec = _spectrogram(hparams, dev)
     _, mel_a, frames_a = spec.targets(a, na)
     _, mel_b, frames_b = spec.targets(b, nb)

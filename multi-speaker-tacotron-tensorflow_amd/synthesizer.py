@@ -15,7 +15,9 @@ import os
 import re
 
 import numpy as np
+import torch
 
+from ._device import STREAM, call
 from .hparams import hparams, load_hparams, EOS_ID
 from .tacotron import create_model, speaker_weights
 from .weights import load_weights
@@ -263,16 +265,10 @@ class Synthesizer(object):
         return self._attention_trim_device(alignments, sequence_lengths).cpu().numpy()
 
     def _attention_trim_device(self, alignments, sequence_lengths):
-        import ctypes as C
-        import torch
-        from . import _lib
         m = self.model
         al = m._as_dev(alignments, torch.float32)
         sl = m._as_dev(np.asarray(sequence_lengths, np.int32), torch.int32)
         N, T_in, n = al.shape
         out = torch.zeros((N,), dtype=torch.int32, device=al.device)
-        p = lambda t: C.c_void_p(t.data_ptr())
-        with torch.cuda.device(al.device):
-            _lib.check(m._lib.taco_attention_trim(C.c_void_p(torch.cuda.current_stream().cuda_stream), p(al), p(sl), N, T_in, n,
-                                                  self.hparams.reduction_factor, p(out)))
+        call(al.device, m._lib.taco_attention_trim, STREAM, al, sl, N, T_in, n, self.hparams.reduction_factor, out)
         return out

@@ -14,16 +14,10 @@ import numpy as np
 import torch
 
 from . import _lib
+# (_ptr and _stream: bench.py's eager branch imports the two by these names from this module)
+from ._device import STREAM, Handle, call, tensor, pointer as _ptr, stream as _stream      # noqa: F401
 from .hparams import hparams as default_hparams, EOS_ID
 from .weights import random_weights
-
-
-def _ptr(t):
-    return C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)
-
-
-def _stream():
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
 
 
 def speaker_weights(spec, num_speakers, batch):
@@ -81,8 +75,9 @@ def speaker_weights(spec, num_speakers, batch):
     return arr
 
 
-class _Plan(object):
+class _Plan(Handle):
     """Static buffers + one captured hipGraph for a (B, T_in, n_steps, manual?, speaker ids or mixture weights?) shape."""
+    _destroy, _handle_attr = "taco_plan_destroy", "handle"
 
     def __init__(self, model, B, T_in, n, manual, mix=False):
         hp, dev = model._hparams, model.device
@@ -105,21 +100,12 @@ class _Plan(object):
         self.handle = C.c_void_p()
         self._lib = lib
         spk = self.speaker_weights if mix else self.speaker_id if model.num_speakers > 1 else None
-        _lib.check((lib.taco_plan_create_mix if mix else lib.taco_plan_create)(
-            model._handle, _ptr(self.inputs), _ptr(self.lengths), _ptr(spk), B, T_in, n, _ptr(self.manual),
-            _ptr(self.mel), _ptr(self.linear), _ptr(self.align), _ptr(self.stop), _ptr(self.ws), nbytes,
-            C.byref(self.handle)))
+        call(None, lib.taco_plan_create_mix if mix else lib.taco_plan_create, model._handle, self.inputs, self.lengths, spk, B, T_in, n,
+             self.manual, self.mel, self.linear, self.align, self.stop, self.ws, nbytes, C.byref(self.handle))
         self.num_nodes = lib.taco_plan_num_nodes(self.handle)
 
     def launch(self):
-        _lib.check(self._lib.taco_plan_launch(self.handle, _stream()))
-
-    def __del__(self):
-        try:
-            if self.handle:
-                self._lib.taco_plan_destroy(self.handle)
-        except Exception:
-            pass
+        call(None, self._lib.taco_plan_launch, self.handle, STREAM)
 
 
 def _concurrent_streams(device, want, max_candidates=24):
@@ -241,8 +227,8 @@ class PlanPool(object):
             p = self.plans[lane]
             p.launch()
             if self.coalesce > 1:        # per-request stop steps (the plan's own covers all its rows)
-                _lib.check(self.model._lib.taco_stop_steps(_stream(), _ptr(p.mel), p.B, self.n, hp.reduction_factor * hp.num_mels,
-                                                           self.B, _ptr(self.slot_stop[lane])))
+                call(None, self.model._lib.taco_stop_steps, STREAM, p.mel, p.B, self.n, hp.reduction_factor * hp.num_mels, self.B,
+                     self.slot_stop[lane])
             self.done[lane].record()
         self.pending[lane] = True
         if self.filled[lane] == 0:
@@ -374,7 +360,8 @@ class PlanPool(object):
         self.plans = []
 
 
-class Tacotron(object):
+class Tacotron(Handle):
+    _destroy, _handle_attr = "taco_model_destroy", "_handle"
     MAX_PLANS = 16     # least-recently-used bound of the per-shape plan cache (plan_for)
 
     def __init__(self, hparams=None):
@@ -574,11 +561,7 @@ class Tacotron(object):
 
     # ---- sess.run([linear_outputs, alignments], feed_dict) ----
     def _as_dev(self, x, dtype):
-        if x is None:
-            return None
-        if not torch.is_tensor(x):
-            x = torch.as_tensor(np.asarray(x))
-        return x.to(device=self.device, dtype=dtype).contiguous()
+        return None if x is None else tensor(x, self.device, dtype, "input")
 
     def _weights_dev(self, speaker_weights, B):
         """speaker_weights [B, num_speakers] as a float32 device tensor; raises where the library would (TACO_ERR_ARG)."""
@@ -644,8 +627,7 @@ class Tacotron(object):
             out = torch.empty((B, n, T_in), dtype=torch.float32, device=al.device)
         elif tuple(out.shape) != (B, n, T_in) or out.dtype != torch.float32 or out.device != al.device or not out.is_contiguous():
             raise Exception("out must be a contiguous float32 tensor [B, T_dec, T_in] = %s on %s" % ((B, n, T_in), al.device))
-        with torch.cuda.device(al.device):
-            _lib.check(self._lib.taco_manual_alignments(_stream(), _ptr(al), B, T_in, n, int(mode), _ptr(out)))
+        call(al.device, self._lib.taco_manual_alignments, STREAM, al, B, T_in, n, int(mode), out)
         return out
 
     def run(self, inputs=None, input_lengths=None, speaker_id=None, manual_alignments=None,
@@ -747,8 +729,7 @@ class Tacotron(object):
         mix, spk = self._stage_speaker(speaker_id, speaker_weights, B)
         out = torch.empty((B, T, 2 * self._hparams.enc_rnn_size), dtype=torch.float32, device=self.device)
         ws, n = self._stage_ws(B, T)
-        _lib.check(getattr(self._lib, "taco_encoder_forward" + mix)(self._handle, _stream(), _ptr(ids), _ptr(lens), _ptr(spk), B, T,
-                                                                    _ptr(out), _ptr(ws), n))
+        call(None, getattr(self._lib, "taco_encoder_forward" + mix), self._handle, STREAM, ids, lens, spk, B, T, out, ws, n)
         return out
 
     def decoder(self, encoder_out, n_steps, speaker_id=None, manual_alignments=None, teacher_frames=None, debug=False,
@@ -766,9 +747,8 @@ class Tacotron(object):
         dbgw = hp.attention_state_size + 2 * hp.enc_rnn_size + hp.dec_layer_num * hp.dec_rnn_size
         dbg = torch.empty((n_steps, B, dbgw), dtype=torch.float32, device=self.device) if debug else None
         ws, n = self._stage_ws(B, max(T_in, n_steps))
-        _lib.check(getattr(self._lib, "taco_decoder_forward" + mix)(self._handle, _stream(), _ptr(enc), _ptr(spk), B, T_in, n_steps,
-                                                                    _ptr(man), _ptr(tf_), _ptr(mel), _ptr(align), _ptr(stop), _ptr(dbg),
-                                                                    _ptr(ws), n))
+        call(None, getattr(self._lib, "taco_decoder_forward" + mix), self._handle, STREAM, enc, spk, B, T_in, n_steps, man, tf_, mel, align,
+             stop, dbg, ws, n)
         return mel, align, stop, dbg
 
     def postnet(self, mel, return_post=False, speaker_id=None, speaker_weights=None):
@@ -779,8 +759,7 @@ class Tacotron(object):
         lin = torch.empty((B, T, hp.num_freq), dtype=torch.float32, device=self.device)
         post = torch.empty((B, T, 2 * hp.post_rnn_size), dtype=torch.float32, device=self.device) if return_post else None
         ws, n = self._stage_ws(B, T)
-        _lib.check(getattr(self._lib, "taco_postnet_forward" + mix)(self._handle, _stream(), _ptr(mel), _ptr(spk), B, T, _ptr(lin),
-                                                                    _ptr(post), _ptr(ws), n))
+        call(None, getattr(self._lib, "taco_postnet_forward" + mix), self._handle, STREAM, mel, spk, B, T, lin, post, ws, n)
         return (lin, post) if return_post else lin
 
     def set_batch_invariant(self, on=True):
@@ -842,15 +821,7 @@ class Tacotron(object):
 
     def close(self):
         self._plans.clear()
-        if self._handle is not None and self._lib is not None:
-            self._lib.taco_model_destroy(self._handle)
-            self._handle = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        Handle.close(self)
 
 
 def create_model(hparams):

@@ -8,7 +8,6 @@
                       the loss is a mean over the global batch.
 
 PyTorch provides device memory, the stream and torch.distributed; the arithmetic is in libtaco_hip.so."""
-import ctypes as C
 import glob
 import os
 import re
@@ -16,14 +15,7 @@ import re
 import torch
 
 from . import _lib
-
-
-def _p(t):
-    return C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)
-
-
-def _st():
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
+from ._device import STREAM, call
 
 
 def l1_losses(mel_outputs, mel_targets, linear_outputs, linear_targets, loss_coeff=None, prioritize_loss=False,
@@ -37,8 +29,8 @@ def l1_losses(mel_outputs, mel_targets, linear_outputs, linear_targets, loss_coe
     ws = torch.empty(1 << 16, dtype=torch.uint8, device=mel_outputs.device)
     tens = [t.contiguous().float() for t in (mel_outputs, mel_targets, linear_outputs, linear_targets)]
     coeff = loss_coeff.contiguous().float() if loss_coeff is not None else None
-    _lib.check(lib.taco_loss_f32(_st(), _p(tens[0]), _p(tens[1]), _p(tens[2]), _p(tens[3]), _p(coeff), B, T, M, F,
-                                 int(bool(prioritize_loss)), int(sample_rate), _p(out), _p(ws), ws.numel()))
+    call(None, lib.taco_loss_f32, STREAM, tens[0], tens[1], tens[2], tens[3], coeff, B, T, M, F, int(bool(prioritize_loss)), int(sample_rate),
+         out, ws, ws.numel())
     return out
 
 
@@ -66,9 +58,8 @@ class FlatAdam(object):
     def step(self, flat_grads):
         lr0, b1, b2, eps, mode, rnd, clip = self.hyper
         assert flat_grads.shape == self.params.shape and flat_grads.dtype == torch.float32
-        _lib.check(self._lib.taco_adam_step_f32(_st(), _p(self.params), _p(flat_grads.contiguous()), _p(self.m), _p(self.v),
-                                                self.params.numel(), self.adam_t, self.learning_rate, b1, b2, eps, clip,
-                                                _p(self.gnorm), _p(self._ws), self._ws.numel()))
+        call(None, self._lib.taco_adam_step_f32, STREAM, self.params, flat_grads.contiguous(), self.m, self.v, self.params.numel(),
+             self.adam_t, self.learning_rate, b1, b2, eps, clip, self.gnorm, self._ws, self._ws.numel())
         self.global_step += 1
         self.adam_t += 1
 

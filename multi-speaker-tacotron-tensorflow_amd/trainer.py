@@ -16,15 +16,8 @@ import numpy as np
 import torch
 
 from . import _lib
+from ._device import STREAM, Handle, call, tensor
 from .train_ops import FlatAdam, allreduce_gradients, train_state_paths, list_train_checkpoints, prune_train_checkpoints
-
-
-def _p(t):
-    return C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)
-
-
-def _st():
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
 
 
 def is_moving_statistic(name):
@@ -45,7 +38,9 @@ def tf_variable_name(name):
     return TF_SCOPE_MAP[best].split(" ")[0] + name[len(best):]
 
 
-class Trainer(object):
+class Trainer(Handle):
+    _destroy = "taco_train_destroy"
+
     def __init__(self, hparams, weights, device="cuda:0", is_randomly_initialized=True, num_speakers=1):
         """`weights`: dict canonical name -> array (weights.random_weights / load_weights).  num_speakers > 1: model_type 'deepvoice' or 'simple' (pass speaker_id to every step)."""
         self.hp = hparams
@@ -250,8 +245,7 @@ class Trainer(object):
         return {name: host[o:o + c].reshape(shape).copy() for (name, shape) in self.spec for (o, c) in [self.offsets[name]]}
 
     def refresh(self):
-        with torch.cuda.device(self.device):
-            _lib.check(self._lib.taco_train_refresh(self._h, _st(), _p(self.params)))
+        call(self.device, self._lib.taco_train_refresh, self._h, STREAM, self.params)
 
     # ---- summaries: per-variable gradient norms (add_stats, train.py:50-77) ----
     @property
@@ -277,8 +271,7 @@ class Trainer(object):
         norms = torch.empty(len(self.spec), dtype=torch.float32, device=dev)
         stats = torch.empty(2, dtype=torch.float32, device=dev)
         argmax = torch.empty(1, dtype=torch.int32, device=dev)
-        with torch.cuda.device(dev):
-            _lib.check(self._lib.taco_train_grad_norms(self._h, _st(), _p(self.grads), _p(norms), _p(stats), _p(argmax)))
+        call(dev, self._lib.taco_train_grad_norms, self._h, STREAM, self.grads, norms, stats, argmax)
         return norms, stats, argmax
 
     def gradient_stats(self):
@@ -351,18 +344,15 @@ class Trainer(object):
         The BatchNorm moving averages (in self.params) follow a forward+backward pass only (tacotron.py:334), and not even that with
         freeze_moving_averages (a warm-up whose result is thrown away)."""
         dev = self.device
-        ids = torch.as_tensor(np.asarray(inputs) if not torch.is_tensor(inputs) else inputs).to(dev, torch.int32).contiguous()
-        lens = torch.as_tensor(np.asarray(input_lengths) if not torch.is_tensor(input_lengths) else input_lengths).to(dev, torch.int32).contiguous()
-        mt = torch.as_tensor(np.asarray(mel_targets) if not torch.is_tensor(mel_targets) else mel_targets).to(dev, torch.float32).contiguous()
-        lt = torch.as_tensor(np.asarray(linear_targets) if not torch.is_tensor(linear_targets) else linear_targets).to(dev, torch.float32).contiguous()
-        co = None if loss_coeff is None else torch.as_tensor(np.asarray(loss_coeff) if not torch.is_tensor(loss_coeff) else loss_coeff).to(dev, torch.float32).contiguous()
+        ids, lens = tensor(inputs, dev, torch.int32, "inputs"), tensor(input_lengths, dev, torch.int32, "input_lengths")
+        mt, lt = tensor(mel_targets, dev, torch.float32, "mel_targets"), tensor(linear_targets, dev, torch.float32, "linear_targets")
+        co = None if loss_coeff is None else tensor(loss_coeff, dev, torch.float32, "loss_coeff")
         B, T_in = ids.shape
         T_out = mt.shape[1]
         hp = self.hp
         spk = None
         if self.num_speakers > 1:
-            spk = torch.zeros(B, dtype=torch.int32, device=dev) if speaker_id is None else \
-                torch.as_tensor(np.asarray(speaker_id) if not torch.is_tensor(speaker_id) else speaker_id).to(dev, torch.int32).contiguous()
+            spk = torch.zeros(B, dtype=torch.int32, device=dev) if speaker_id is None else tensor(speaker_id, dev, torch.int32, "speaker_id")
         if mt.shape != (B, T_out, hp.num_mels) or lt.shape != (B, T_out, hp.num_freq):
             raise Exception("targets must be [B, T_out, num_mels] / [B, T_out, num_freq], got %s / %s" % (tuple(mt.shape), tuple(lt.shape)))
         if self._sync_cb is not None:
@@ -383,11 +373,9 @@ class Trainer(object):
             lin = torch.empty((B, T_out, hp.num_freq), dtype=torch.float32, device=dev)
             ali = torch.empty((B, T_in, T_out // hp.reduction_factor), dtype=torch.float32, device=dev)
         self._ws_live = ws      # the workspace of the call in flight (the SyncBN callback reduces slices of it)
-        with torch.cuda.device(dev):
-            _lib.check(self._lib.taco_train_forward_backward(
-                self._h, _st(), _p(self.params), _p(self.grads if backward else None), _p(ids), _p(lens), _p(spk), _p(mt), _p(lt), _p(co),
-                B, T_in, T_out, int(bool(getattr(hp, "prioritize_loss", False))), int(getattr(hp, "sample_rate", 24000)), _p(self.losses),
-                _p(mel), _p(lin), _p(ali), int(bool(rnn_decoder_test_mode)) | (2 if freeze_moving_averages else 0), _p(ws), ws.numel()))
+        call(dev, self._lib.taco_train_forward_backward, self._h, STREAM, self.params, self.grads if backward else None, ids, lens, spk,
+             mt, lt, co, B, T_in, T_out, int(bool(getattr(hp, "prioritize_loss", False))), int(getattr(hp, "sample_rate", 24000)), self.losses,
+             mel, lin, ali, int(bool(rnn_decoder_test_mode)) | (2 if freeze_moving_averages else 0), ws, ws.numel())
         if self._sync_err is not None:
             e, self._sync_err = self._sync_err, None
             raise e
@@ -402,7 +390,7 @@ class Trainer(object):
         dev = self.device
         if self._sync_cb is not None:
             raise _lib.TacoError(_lib.TACO_ERR_STATE, "SyncBN calls back into the host: it cannot be combined with a captured step")
-        cv = lambda x, dt: (x if torch.is_tensor(x) else torch.as_tensor(np.asarray(x))).to(dev, dt).contiguous().clone()
+        cv = lambda x, dt: tensor(x, dev, dt, "input").clone()
         self._g_in = [cv(inputs, torch.int32), cv(input_lengths, torch.int32), cv(mel_targets, torch.float32),
                       cv(linear_targets, torch.float32), None if loss_coeff is None else cv(loss_coeff, torch.float32)]
         self._g_spk = None if speaker_id is None else cv(speaker_id, torch.int32)
@@ -456,14 +444,3 @@ class Trainer(object):
     @property
     def learning_rate(self):
         return self.adam.learning_rate
-
-    def close(self):
-        if getattr(self, "_h", None):
-            self._lib.taco_train_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass

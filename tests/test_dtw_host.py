@@ -218,6 +218,13 @@ def test_every_argument_error_is_returned_without_a_device():
                dict(path=P(dr)), dict(path=P(la)), dict(path=P(lb, 4)), dict(plen=P(dr, dr.nbytes - 1)), dict(plen=P(la, 4)),
                dict(plen=P(path, path.nbytes - 4)), dict(plen=P(path))):
         assert pcall(**kw) == ARG, kw
+    # an overlap says so in its message; the lengths are optional, and without them what is left is still checked.  (A call that passes
+    # these checks reaches the launch, so buffers that only touch are tried where a later check still refuses: taco_dtw above.)
+    for kw in (dict(path=P(dr, dr.nbytes - 1)), dict(plen=P(lb)), dict(la=None, path=P(lb)), dict(lb=None, plen=P(la)),
+               dict(la=None, lb=None, plen=P(path, 8))):
+        assert pcall(**kw) == ARG and b"overlap" in lib.taco_last_error(), kw
+    back = np.zeros(dr.nbytes + dist.nbytes, np.uint8)                                                        # dir and, touching its end, dist
+    assert call(dir=P(back), dist=P(back, dr.nbytes), nws=nws - 1) == STATE
     assert lib.taco_debug_dtw_info(None, 6) == ARG and lib.taco_debug_dtw_info((C.c_int * 6)(), -1) == ARG
     two = (C.c_int * 3)(0, 0, -5)
     assert lib.taco_debug_dtw_info(two, 2) == 0 and two[0] == _info()[0] and two[2] == -5                      # no more than asked for

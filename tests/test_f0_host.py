@@ -235,6 +235,8 @@ def test_every_argument_error_is_returned_without_a_device():
                dict(Fa=-1), dict(stats=P(fa)), dict(stats=P(fa, fa.nbytes - 4)), dict(stats=P(fb, 8)), dict(stats=P(path, path.nbytes - 4)),
                dict(stats=P(plen)), dict(stats=P(plen, 4))):
         assert scall(**kw) == ARG, kw
+    for kw in (dict(stats=P(fa, 4)), dict(stats=P(fb, fb.nbytes - 4)), dict(stats=P(path)), dict(stats=P(plen, 4))):      # and says so
+        assert scall(**kw) == ARG and b"overlap" in lib.taco_last_error(), kw
 
 
 # ---- the share of frames the random tier may leave out ----

@@ -145,6 +145,34 @@ def test_capture_and_replay():
         del g
 
 
+def test_the_model_call_takes_the_current_stream_eagerly_and_in_a_capture(tmp_path):
+    """Tacotron.manual_alignments_from goes through the package's device-call layer: on a side stream it runs there, and inside a graph
+    capture it takes the capturing stream -- a call that took another stream could not be captured (the runtime refuses, the layer
+    raises).  The replay writes the same bits as the eager call."""
+    import torch
+    s = _synth(tmp_path)
+    a = np.array([[[0.25, 0.5], [0.75, 0.125], [0.5, 0.5]]], np.float32)              # [B = 1, T_in = 3, n_steps = 2], one tie
+    src = dev(a)
+    side = torch.cuda.Stream()
+    side.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(side):
+        eager = s.model.manual_alignments_from(src, 1).clone()
+    side.synchronize()
+    assert same_bits(eager.cpu().numpy(), numpy_ref(a, 1))
+    out = torch.full((1, 2, 3), float("nan"), dtype=torch.float32, device="cuda")
+    g = torch.cuda.CUDAGraph()
+    torch.cuda.synchronize()
+    with torch.cuda.graph(g):
+        assert s.model.manual_alignments_from(src, 1, out=out) is out
+    torch.cuda.synchronize()
+    assert np.isnan(out.cpu().numpy()).all()         # captured, not run
+    g.replay()
+    torch.cuda.synchronize()
+    assert same_bits(out.cpu().numpy(), eager.cpu().numpy())
+    del g
+    s.close()
+
+
 def test_refused_modes_leave_the_output_untouched():
     from taco_amd import _lib
     lib = _lib.load_library()
