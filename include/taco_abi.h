@@ -577,7 +577,10 @@ int taco_collate(void* hip_stream, const taco_collate_stream* streams, int n_str
 
 /* ---- training-side entry points on flat buffers (loss, schedule, clip + Adam); forward/backward: taco_train_* below ---- */
 /* add_loss (tacotron.py:274-302).  d_mel_* [B,T,num_mels], d_lin_* [B,T,num_freq], d_loss_coeff [B] (nullable = 1).
- * d_losses[4] = loss, mel_loss, linear_loss, loss_without_coeff.  Workspace >= 64 KiB. */
+ * d_losses[4] = loss, mel_loss, linear_loss, loss_without_coeff.  Workspace >= 64 KiB.
+ * prioritize_loss: the band is bins [int(165 / (sample_rate / 2) * num_freq), int(5000 / (sample_rate / 2) * num_freq)) clamped to num_freq, as the
+ * reference's slice linear_loss[:, :, lower:upper] clamps it (sample rates below 10000 Hz put the 5 kHz bin past the last one); its mean is over the
+ * bins that exist.  The training step's gradient counts the band the same way. */
 int taco_loss_f32(void* hip_stream, const float* d_mel_out, const float* d_mel_tgt, const float* d_lin_out,
                   const float* d_lin_tgt, const float* d_loss_coeff, int B, int T, int num_mels, int num_freq,
                   int prioritize_loss, int sample_rate, float* d_losses, void* d_workspace, size_t workspace_bytes);

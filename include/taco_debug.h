@@ -165,8 +165,53 @@ int taco_train_debug_decoder(taco_train* t, void* hip_stream, float* d_params, f
                              float* d_mel, float* d_alignments, float* d_denc, float* d_datt_init, float* const* d_ddec_init, float* d_dspk_emb,
                              void* d_ws, size_t ws_bytes, uint32_t* paths);
 
+/* Test hook: the INPUT END of a trainer's step alone -- embedding gather, encoder prenet and speaker conditioning forward (front_forward_train), then their
+ * backward (speaker_rows_backward for model type 'simple', front_backward: the deepvoice speaker layers, the prenet, the embedding's gradient) -- on caller
+ * data, exactly as the step calls them: the step's context and state objects, buffers carved as the step carves them, the trainer's current switches
+ * (taco_train_set_exact_gemm, _set_exact_wgrad, _set_wgrad_planes, _set_deterministic).
+ * Inputs: d_ids [B, T_in] (every id below num_symbols; nothing is masked by a length, as the reference masks nothing in the prenet), d_dpre [B*T_in, P] (P = last
+ * encoder prenet width), the upstream gradient of d_pre.  Multi-speaker models: d_speaker_id [B]; deepvoice: d_dvec, 3 + dec_layer_num pointers to the upstream
+ * gradients of before_highway [B, P], encoder_rnn_init [B, 2*enc_rnn_size], attention_rnn_init [B, attention_state_size], decoder_rnn_init_i [B, dec_rnn_size];
+ * simple: d_dspk_emb [B, S], what the decoder and the linear head hand back for the speaker rows.
+ * Outputs: d_pre [B*T_in, P]; deepvoice: d_vec, pointers as d_dvec, the speaker vectors; d_spk_emb [B, S], the gathered speaker rows (required by simple,
+ * nullable for deepvoice with S > 1, refused elsewhere).
+ * d_params: the trainer's flat parameters, as of the last taco_train_refresh.  The gradients of embedding, prenet/dense_*, speaker_embedding and spk/... are ADDED
+ * into d_grads at their taco_train_param_offset -- zero-fill them first, as the step zero-fills the whole buffer; no other element of d_grads is written.
+ * d_ws: at least taco_train_debug_front_workspace_bytes(t, B, T_in) bytes (ask again after a switch that changes the step's workspace), 16-byte aligned.
+ * Errors, all returned before the first HIP call: a null required argument, speaker_id missing on a multi-speaker model, speaker inputs or outputs on a
+ * single-speaker model (or of the other model type), a gradient without its forward output, a misaligned workspace: TACO_ERR_ARG; stale split-bf16 planes (a switch
+ * without a taco_train_refresh) and too small a workspace: TACO_ERR_STATE; more than 64 rows: TACO_ERR_UNSUPPORTED; a host-only trainer
+ * (taco_debug_train_create_host) that passes them all: TACO_ERR_STATE.
+ * paths (nullable) receives which branch each dispatch of THIS call took, OR-ed in where the kernel is launched:
+ *   bit 0 / 1   embedding-style gradients (embedding, speaker_embedding, spk tables): k_embed_bwd_det (ordered) / k_embed_bwd (atomics)
+ *   bit 2 / 3   deepvoice speaker backward: tables (speaker_embedding_size = 1) / softsign + dense layers into speaker_embedding */
+size_t taco_train_debug_front_workspace_bytes(const taco_train* t, int B, int T_in);
+int taco_train_debug_front(taco_train* t, void* hip_stream, float* d_params, float* d_grads, const int32_t* d_ids, const int32_t* d_speaker_id,
+                           const float* d_dpre, const float* const* d_dvec, const float* d_dspk_emb, int B, int T_in, float* d_pre, float* const* d_vec,
+                           float* d_spk_emb, void* d_ws, size_t ws_bytes, uint32_t* paths);
+
+/* Test hook: the OUTPUT END of a trainer's step alone -- the teacher-frame gather (teacher_frames), the linear head and add_loss (head_forward_train:
+ * taco_loss_f32), then the two L1 gradients, the head's weight, bias and data gradients (head_backward) and dmel += dmel_post (head_backward_join) -- on caller
+ * data, exactly as the step calls them: the step's context and state objects, the trainer's current switches.
+ * Inputs: d_post_out [B*T_out, 2*post_rnn_size] (the post CBHG's output), d_mel [B*T_out, num_mels] (the decoder's frames), d_mel_tgt [B, T_out, num_mels],
+ * d_lin_tgt [B, T_out, num_freq], prioritize_loss, sample_rate.  Nullable: d_loss_coeff [B]; d_dmel_post [B*T_out, num_mels], what the post CBHG's backward hands
+ * back, added to d_dmel as the step adds it; d_spk_emb [B, S], the speaker rows -- required by model type 'simple' and refused elsewhere.
+ * Outputs: d_teacher [B, T_out/r, num_mels] (target frame t*r + r-1 of every row), d_lin [B*T_out, num_freq], d_losses[4] (loss, mel_loss, linear_loss,
+ * loss_without_coeff), d_dmel [B*T_out, num_mels], d_dpost [B*T_out, 2*post_rnn_size], d_dspk_emb [B, S] (required with d_spk_emb; overwritten: the head's share
+ * of the gradient of the speaker rows alone).  A gradient output without its input is TACO_ERR_ARG.
+ * The gradients of linear/kernel and linear/bias are ADDED into d_grads at their taco_train_param_offset -- zero-fill them first; no other element is written.
+ * d_ws: at least taco_train_debug_head_workspace_bytes(t, B, T_out) bytes, 16-byte aligned.
+ * Errors, all returned before the first HIP call: null argument, bad shape, misaligned workspace TACO_ERR_ARG; T_out no multiple of the reduction factor or
+ * T_out/r above max_iters TACO_ERR_SHAPE; more than 64 rows TACO_ERR_UNSUPPORTED; stale split-bf16 planes and too small a workspace TACO_ERR_STATE; a host-only
+ * trainer that passes them all TACO_ERR_STATE. */
+size_t taco_train_debug_head_workspace_bytes(const taco_train* t, int B, int T_out);
+int taco_train_debug_head(taco_train* t, void* hip_stream, float* d_params, float* d_grads, const float* d_post_out, const float* d_mel, const float* d_mel_tgt,
+                          const float* d_lin_tgt, const float* d_loss_coeff, const float* d_dmel_post, const float* d_spk_emb, int B, int T_out,
+                          int prioritize_loss, int sample_rate, float* d_teacher, float* d_lin, float* d_losses, float* d_dmel, float* d_dpost,
+                          float* d_dspk_emb, void* d_ws, size_t ws_bytes);
+
 /* Test hook: a trainer that stays on the host -- its shadow model is packed and never uploaded, no device is touched.  It serves the argument and state
- * checks of taco_train_debug_decoder, which come before its first HIP call, on a machine without a GPU; nothing may be launched on it (its split-bf16
+ * checks of taco_train_debug_decoder, taco_train_debug_front and taco_train_debug_head, which come before its first HIP call, on a machine without a GPU; nothing may be launched on it (its split-bf16
  * planes count as stale until taco_train_set_exact_gemm with on = 1 selects the engines that need none).  Freed by taco_train_destroy. */
 int taco_debug_train_create_host(const taco_hparams* hp, taco_train** out);
 

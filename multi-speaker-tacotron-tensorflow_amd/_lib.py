@@ -216,6 +216,10 @@ PROTOTYPES = {
     "taco_train_debug_cbhg": (_I, [_P, _P, _I, _P, _P, _P, _P, _P, _P, _P, _I, _I, _P, _P, _P, _P, _P, _S, _P]),
     "taco_train_debug_decoder_workspace_bytes": (_S, [_P, _I, _I, _I]),
     "taco_train_debug_decoder": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _S, _P]),
+    "taco_train_debug_front_workspace_bytes": (_S, [_P, _I, _I]),
+    "taco_train_debug_front": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _P, _P, _P, _P, _S, _P]),
+    "taco_train_debug_head_workspace_bytes": (_S, [_P, _I, _I]),
+    "taco_train_debug_head": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _S]),
     "taco_debug_train_create_host": (_I, [C.POINTER(TacoHParams), C.POINTER(_P)]),
     "taco_train_workspace_bytes": (_S, [_P, _I, _I, _I]),
     "taco_train_forward_backward": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _P, _I, _P, _S]),

@@ -1705,6 +1705,13 @@ static int forward_enqueue(taco_model* m, hipStream_t st, const int32_t* ids, co
 // C ABI
 // ------------------------------------------------------------------------------------------------
 #include "taco_segnorm.h"
+// The priority band of add_loss (tacotron.py:283-288): bins [lo, hi) of linear_loss[:, :, lo:hi].  A slice clamps its upper end to the axis: below
+// 10000 Hz the 5 kHz bin lies past num_freq (8000 Hz, 1025 bins: 1281), and the band's mean is over the bins that exist.  The loss and the step's
+// L1 gradient (head_backward, taco_train.h) both count the band with this.
+static void loss_band(int sample_rate, int num_freq, int* lo, int* hi) {
+  *hi = std::min((int)(5000 / (sample_rate * 0.5) * num_freq), num_freq);
+  *lo = std::min((int)(165 / (sample_rate * 0.5) * num_freq), *hi);
+}
 #include "taco_train.h"
 #include "taco_audio.h"
 #include "taco_resample.h"
@@ -2434,10 +2441,7 @@ int taco_loss_f32(void* hip_stream, const float* d_mel_out, const float* d_mel_t
   double* pm = (double*)d_workspace; double* pl = pm + (size_t)TR_MAXBLK * 4;
   const int rows = B * T;
   int lo = 0, hi = 0;
-  if (prioritize_loss) {   // tacotron.py:283-285
-    hi = (int)(5000 / (sample_rate * 0.5) * num_freq);
-    lo = (int)(165 / (sample_rate * 0.5) * num_freq);
-  }
+  if (prioritize_loss) loss_band(sample_rate, num_freq, &lo, &hi);
   const int nbm = std::min(TR_MAXBLK, cdiv(rows * num_mels, TR_NT * 8)), nbl = std::min(TR_MAXBLK, cdiv(rows * num_freq, TR_NT * 8));
   hipLaunchKernelGGL(k_l1_partial, dim3(nbm), dim3(TR_NT), 0, st, d_mel_out, d_mel_tgt, d_loss_coeff, rows, T, num_mels, 0, 0, pm);
   hipLaunchKernelGGL(k_l1_partial, dim3(nbl), dim3(TR_NT), 0, st, d_lin_out, d_lin_tgt, d_loss_coeff, rows, T, num_freq, lo, hi, pl);

@@ -204,6 +204,7 @@ struct StepState {
   int planes_problems = 0;                       // weight gradients of this step that were computed from pre-split planes so far
   unsigned paths = 0;                            // CBHG_PATH_* bits: which branch each dispatch of a CBHG took, OR-ed in where it is taken (taco_train_debug_cbhg)
   unsigned dec_paths = 0;                        // DEC_PATH_* bits: which engine ran the decoder loop and its BPTT, OR-ed in where each is launched (taco_train_debug_decoder)
+  unsigned end_paths = 0;                        // FRONT_PATH_* bits: which embedding-gradient kernel and which speaker backward ran, OR-ed in where each is launched (taco_train_debug_front)
   WgBatch wgb;
 };
 // The word of taco_train_debug_cbhg (include/taco_debug.h documents the layout): one bit per form of every two-way dispatch of
@@ -226,6 +227,12 @@ enum : unsigned {
   DEC_PATH_BWD_PERSISTENT = 1u << 2, DEC_PATH_BWD_STAGES = 1u << 3,            // k_decoder_bwd_xcd<RG> | one launch per stage
   DEC_PATH_FWD_RG_SHIFT = 4, DEC_PATH_BWD_RG_SHIFT = 8,                        // four bits each: rows per group (1, 2, 4, 8) of the persistent launch
   DEC_PATH_XCD_LOCAL = 1u << 12, DEC_PATH_WRITE_THROUGH = 1u << 13             // a persistent launch of the call exchanged through XCD-local stores | write-through
+};
+
+// The word of taco_train_debug_front (include/taco_debug.h): set where run_embed_bwd / front_backward launch.
+enum : unsigned {
+  FRONT_PATH_EMBED_DET = 1u << 0, FRONT_PATH_EMBED_ATOMIC = 1u << 1,           // k_embed_bwd_det | k_embed_bwd
+  FRONT_PATH_SPK_TABLES = 1u << 2, FRONT_PATH_SPK_DENSE = 1u << 3              // deepvoice speaker backward: tables (S = 1) | softsign + dense layers
 };
 
 struct TrainCtx {
@@ -448,6 +455,7 @@ static int run_wgrad(const TrainCtx& x, const float* xs, const int* gather, int 
   return 0;
 }
 static void run_embed_bwd(const TrainCtx& x, const float* dx, const int* ids, float* dE, int M, int E, int V) {
+  x.s->end_paths |= x.s->det ? FRONT_PATH_EMBED_DET : FRONT_PATH_EMBED_ATOMIC;
   if (x.s->det) hipLaunchKernelGGL(k_embed_bwd_det, EWGRID((size_t)V * ((E + 63) / 64) * 64), 0, x.st, dx, ids, dE, M, E, V);      // one wave per (table row, 64 columns)
   else hipLaunchKernelGGL(k_embed_bwd, EWGRID((size_t)M * E), 0, x.st, dx, ids, dE, M, E);
 }
@@ -1260,6 +1268,157 @@ static int decoder_backward(const TrainCtx& x, const float* enc_out, int B, int 
 }
 
 // ---------------------------------------------------------------------------------------------------------------
+// The two ends of the step and the seams between its blocks, as the step calls them and as the test hooks taco_train_debug_front /
+// taco_train_debug_head (include/taco_debug.h) call them alone.
+// ---------------------------------------------------------------------------------------------------------------
+// Input end, forward: embedding gather + encoder prenet -> pre[i] [B*T_in, enc_prenet[i]]; the speaker rows of 'simple' -> spk.emb; the speaker
+// vectors of deepvoice (before_highway, encoder / attention / decoder initial states; tacotron.py:52-79) -> spk.vec[]
+static int front_forward_train(const TrainCtx& x, const int* ids, const int* speaker_id, int B, int T_in, float* const* pre, const SpkWs& spk) {
+  taco_model* m = x.t->sm; hipStream_t st = x.st;
+  const taco_hparams& hp = m->hp;
+  const int Me = B * T_in;
+  const float* cur = x.p("embedding"); int curd = hp.embedding_size;
+  for (int i = 0; i < hp.enc_prenet_n; ++i) {
+    GemmCall g; g.x = cur; g.ldx = curd; g.gather = (i == 0) ? ids : nullptr; g.M = Me; g.act = ACT_RELU; g.out = pre[i]; g.ldo = hp.enc_prenet[i];
+    TRY(run_gemm(m, st, &m->enc_prenet[i], 1, false, g));
+    cur = pre[i]; curd = hp.enc_prenet[i];
+  }
+  const bool dv = is_deepvoice(m), simple = is_simple(m);
+  const int S = hp.speaker_embedding_size;
+  if ((dv || simple) && !speaker_id) return fail(TACO_ERR_ARG, "speaker_id required for a multi-speaker model");
+  if (simple) {      // the embedding row of every utterance (tacotron.py:47-50); concatenated in the decoder and the linear head
+    hipLaunchKernelGGL(k_gather_rows, EWGRID((size_t)B * S), 0, st, AP(m, m->spk_emb), speaker_id, B, S, spk.emb);
+    HIPCHK(hipGetLastError());
+  }
+  if (dv) TRY(spk_forward(m, st, spk_ids(speaker_id), B, spk));       // before_highway, encoder / attention / decoder initial states (tacotron.py:52-79)
+  return 0;
+}
+// teacher inputs: every r-th target frame (helpers.py:44): teach[b, t] = mel_targets[b, t*r + r-1]
+static int teacher_frames(const TrainCtx& x, const float* mel_tgt, int B, int n, float* teach) {
+  const taco_hparams& hp = x.t->sm->hp;
+  const int r = hp.reduction_factor, Mm = hp.num_mels;
+  hipLaunchKernelGGL(k_copy2d, EWGRID((size_t)B * n * Mm), 0, x.st, mel_tgt + (size_t)(r - 1) * Mm, r * Mm, teach, Mm, B * n, Mm);
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+// Output end, forward: the linear head over the post CBHG's output [B*T_out, 2*post_rnn_size] -> lin [B*T_out, num_freq] (spk_emb [B, S]: the speaker
+// rows of 'simple', else null; linrv [B, num_freq] their scratch), then add_loss (tacotron.py:274-302) -> d_losses[4] (nullable: no loss)
+static int head_forward_train(const TrainCtx& x, const float* post_out, const float* mel, const float* spk_emb, const float* mel_tgt, const float* lin_tgt,
+                              const float* loss_coeff, int B, int T_out, int prioritize_loss, int sample_rate, float* lin, float* linrv, float* d_losses,
+                              float* losspart) {
+  taco_model* m = x.t->sm; hipStream_t st = x.st;
+  const taco_hparams& hp = m->hp;
+  const int Mm = hp.num_mels, F = hp.num_freq, S = hp.speaker_embedding_size, Mp = B * T_out;
+  { GemmCall g; g.x = post_out; g.ldx = 2 * hp.post_rnn_size; g.M = Mp; g.out = lin; g.ldo = F;
+    if (spk_emb) {    // linear(concat(tiled speaker_embed, post)) (tacotron.py:226-235): the speaker rows give one vector per utterance
+      SkJob j = sk_linear(m, m->lin_spk, spk_emb, S, S, nullptr, 0, ACT_NONE, linrv, F);
+      TRY(run_skinny(st, B, &j, 1));
+      g.T = T_out; g.rowvec = linrv; g.ldrv = F;
+    }
+    TRY(run_gemm(m, st, &m->linear, 1, false, g)); }
+  // ---- loss (tacotron.py:274-302) ----
+  if (d_losses) TRY(taco_loss_f32((void*)st, mel, mel_tgt, lin, lin_tgt, loss_coeff, B, T_out, Mm, F, prioritize_loss, sample_rate, d_losses,
+                                  losspart, (size_t)TR_MAXBLK * 8 * sizeof(double)));
+  return 0;
+}
+// Output end, backward: d loss / d mel -> dmel and d loss / d linear -> dlin (the two L1 gradients, loss_coeff and the priority band included), the
+// gradients of linear/kernel and linear/bias, dpost = dlin . W^T; 'simple' (spk_emb given): the speaker rows of linear/kernel and the head's share of
+// d(speaker rows) -> dspk_emb [B, S] (overwritten), over the time-summed dlin (dlin_sum [B, num_freq])
+static int head_backward(const TrainCtx& x, const float* post_out, const float* mel, const float* lin, const float* spk_emb, const float* mel_tgt,
+                         const float* lin_tgt, const float* loss_coeff, int B, int T_out, int prioritize_loss, int sample_rate, float* dmel, float* dlin,
+                         float* dlin_sum, float* dspk_emb, float* dpost) {
+  const taco_train* t = x.t; taco_model* m = t->sm; hipStream_t st = x.st;
+  const taco_hparams& hp = m->hp;
+  const int Mm = hp.num_mels, F = hp.num_freq, S = hp.speaker_embedding_size, Mp = B * T_out;
+  const bool simple = spk_emb != nullptr;
+  int c_lo = 0, c_hi = 0; float s_lin = 1.0f / ((float)Mp * F), s_band = 0.f;
+  if (prioritize_loss) {
+    loss_band(sample_rate, F, &c_lo, &c_hi);      // clamped to the bins that exist, as the reference's slice is
+    s_lin = 0.5f / ((float)Mp * F); s_band = 0.5f / ((float)Mp * std::max(c_hi - c_lo, 1));
+  }
+  hipLaunchKernelGGL(k_l1_grad, EWGRID((size_t)Mp * Mm), 0, st, mel, mel_tgt, loss_coeff, Mp, T_out, Mm, 1.0f / ((float)Mp * Mm), 0, 0, 0.f, dmel);
+  hipLaunchKernelGGL(k_l1_grad, EWGRID((size_t)Mp * F), 0, st, lin, lin_tgt, loss_coeff, Mp, T_out, F, s_lin, c_lo, c_hi, s_band, dlin);
+  HIPCHK(hipGetLastError());
+  const int Hp2 = 2 * hp.post_rnn_size;
+  TRY(run_wgrad(x, post_out, nullptr, Hp2, dlin, F, x.g("linear/kernel") + (simple ? (size_t)S * F : 0), F, Mp, 0, Hp2, F));
+  if (simple) {      // speaker rows of the head: the embedding is constant over time, so they see the time-summed gradient
+    HIPCHK(zero_async(dspk_emb, (size_t)B * S * sizeof(float), st));
+    hipLaunchKernelGGL(k_time_sum, EWGRID((size_t)B * F), 0, st, dlin, dlin_sum, B, T_out, F);
+    HIPCHK(hipGetLastError());
+    TRY(run_wgrad(x, spk_emb, nullptr, S, dlin_sum, F, x.g("linear/kernel"), F, B, 0, S, F));
+    SkJob j = sk_T(m, t->tp.lin_spk_T, dlin_sum, F, dspk_emb, S);
+    TRY(run_skinny(st, B, &j, 1));
+  }
+  TRY(run_colsum(x, dlin, F, nullptr, 0, nullptr, nullptr, x.g("linear/bias"), nullptr, Mp, F, 0));
+  return run_dgrad(x, t->tp.lin_d, dlin, F, Mp, 0, dpost, Hp2);
+}
+// ... and behind the post CBHG's backward: dmel += dmel_post, the gradient the post-net hands back to the decoder's frames
+static int head_backward_join(const TrainCtx& x, float* dmel, const float* dmel_post, int B, int T_out) {
+  const int Mm = x.t->sm->hp.num_mels, Mp = B * T_out;
+  hipLaunchKernelGGL(k_add2d, EWGRID((size_t)Mp * Mm), 0, x.st, dmel, Mm, dmel_post, Mm, Mp, Mm);
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+// 'simple': what the decoder and the head hand back for the speaker rows, dspk_emb [B, S] -> the gradient of speaker_embedding
+static int speaker_rows_backward(const TrainCtx& x, const float* dspk_emb, const int* speaker_id, int B) {
+  const taco_hparams& hp = x.t->sm->hp;
+  run_embed_bwd(x, dspk_emb, speaker_id, x.g("speaker_embedding"), B, hp.speaker_embedding_size, hp.num_speakers);
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+// Input end, backward.  deepvoice: the speaker conditioning (tacotron.py:52-79) from dvec[i], the gradients of the speaker vectors that the encoder
+// CBHG and the decoder left (S = 1: straight into the tables; else through softsign and the dense layers into speaker_embedding; dspk_emb [B, S],
+// dzs [B, widest vector] and tmp [B, S] are scratch).  Then the encoder prenet from dpre[last] (in place) down to demb, and the embedding's gradient.
+static int front_backward(const TrainCtx& x, const int* ids, const int* speaker_id, int B, int T_in, float* const* pre, float* const* dpre_of, float* demb,
+                          const SpkWs& spk, const float* const* dvec, float* dspk_emb, float* dzs, float* tmp) {
+  const taco_train* t = x.t; taco_model* m = t->sm; hipStream_t st = x.st;
+  const taco_hparams& hp = m->hp;
+  const int Me = B * T_in, S = hp.speaker_embedding_size;
+  if (is_deepvoice(m)) {   // speaker conditioning backward (tacotron.py:52-79)
+    const std::vector<std::string> names = spk_vector_names(hp);
+    const int dims[3] = {hp.enc_prenet[hp.enc_prenet_n - 1], hp.enc_rnn_size * 2, hp.attention_state_size};
+    if (S == 1) {
+      x.s->end_paths |= FRONT_PATH_SPK_TABLES;
+      for (size_t i = 0; i < names.size(); ++i) {
+        const int dd = i < 3 ? dims[i] : hp.dec_rnn_size;
+        run_embed_bwd(x, dvec[i], speaker_id, x.g("spk/" + names[i] + "/table"), B, dd, hp.num_speakers);
+      }
+    } else {
+      x.s->end_paths |= FRONT_PATH_SPK_DENSE;
+      HIPCHK(zero_async(dspk_emb, (size_t)B * S * sizeof(float), st));
+      for (size_t i = 0; i < names.size(); ++i) {
+        const int dd = i < 3 ? dims[i] : hp.dec_rnn_size;
+        hipLaunchKernelGGL(k_softsign_bwd, EWGRID((size_t)B * dd), 0, st, dvec[i], spk.vec[i], dzs, B * dd);
+        TRY(run_wgrad(x, spk.emb, nullptr, S, dzs, dd, x.g("spk/" + names[i] + "/kernel"), dd, B, 0, S, dd));
+        TRY(run_colsum(x, dzs, dd, nullptr, 0, nullptr, nullptr, x.g("spk/" + names[i] + "/bias"), nullptr, B, dd, 0));
+        SkJob j = sk_T(m, t->tp.spk_T[i], dzs, dd, tmp, S);
+        TRY(run_skinny(st, B, &j, 1));
+        hipLaunchKernelGGL(k_add2d, EWGRID((size_t)B * S), 0, st, dspk_emb, S, tmp, S, B, S);
+      }
+      run_embed_bwd(x, dspk_emb, speaker_id, x.g("speaker_embedding"), B, S, hp.num_speakers);
+    }
+    HIPCHK(hipGetLastError());
+  }
+  float* dpre = dpre_of[hp.enc_prenet_n - 1];
+  for (int i = hp.enc_prenet_n - 1; i >= 0; --i) {
+    const int N = hp.enc_prenet[i];
+    const std::string nm = "prenet/dense_" + std::to_string(i + 1);
+    hipLaunchKernelGGL(k_relu_bwd, EWGRID((size_t)Me * N), 0, st, dpre, N, pre[i], N, dpre, N, Me, N);
+    HIPCHK(hipGetLastError());
+    if (i > 0) TRY(run_wgrad(x, pre[i - 1], nullptr, hp.enc_prenet[i - 1], dpre, N, x.g(nm + "/kernel"), N, Me, 0, hp.enc_prenet[i - 1], N));
+    else TRY(run_wgrad(x, x.p("embedding"), ids, hp.embedding_size, dpre, N, x.g(nm + "/kernel"), N, Me, 0, hp.embedding_size, N));
+    TRY(run_colsum(x, dpre, N, nullptr, 0, nullptr, nullptr, x.g(nm + "/bias"), nullptr, Me, N, 0));
+    float* dnext = (i > 0) ? dpre_of[i - 1] : demb;
+    const int nd = (i > 0) ? hp.enc_prenet[i - 1] : hp.embedding_size;
+    TRY(run_dgrad(x, t->tp.encpre_d[i], dpre, N, Me, 0, dnext, nd));
+    dpre = dnext;
+  }
+  run_embed_bwd(x, dpre, ids, x.g("embedding"), (int)Me, hp.embedding_size, hp.num_symbols);
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
+// ---------------------------------------------------------------------------------------------------------------
 // whole step: forward (tape) + loss + backward
 // ---------------------------------------------------------------------------------------------------------------
 static int train_forward_backward(taco_train* t, hipStream_t st, float* P, float* G, const int* ids, const int* lengths, const int* speaker_id, const float* mel_tgt,
@@ -1268,7 +1427,7 @@ static int train_forward_backward(taco_train* t, hipStream_t st, float* P, float
                                   bool do_backward, bool feed_back, bool freeze_moving = false) {
   taco_model* m = t->sm;
   const taco_hparams& hp = m->hp;
-  const int r = hp.reduction_factor, Mm = hp.num_mels, F = hp.num_freq;
+  const int r = hp.reduction_factor;
   if (T_out % r) return fail(TACO_ERR_SHAPE, "T_out %d is not a multiple of the reduction factor %d", T_out, r);
   const int n = T_out / r;
   if (n > hp.max_iters) return fail(TACO_ERR_SHAPE, "T_out/r = %d exceeds max_iters %d", n, hp.max_iters);
@@ -1283,120 +1442,36 @@ static int train_forward_backward(taco_train* t, hipStream_t st, float* P, float
   if (t->wgrad_planes) { s.wps = w.wpscr; s.wps_cap = w.wps_uint4; }
   TrainCtx x{t, st, P, G, do_backward && !freeze_moving, &s};
   const auto step = [&]() -> int {      // (a lambda so that the count below is published on every path out of the step, one that fails half-way included)
-  const int Me = B * T_in, Mp = B * T_out;
   // ---- forward ----
-  const float* cur = x.p("embedding"); int curd = hp.embedding_size;
-  for (int i = 0; i < hp.enc_prenet_n; ++i) {
-    GemmCall g; g.x = cur; g.ldx = curd; g.gather = (i == 0) ? ids : nullptr; g.M = Me; g.act = ACT_RELU; g.out = w.pre[i]; g.ldo = hp.enc_prenet[i];
-    TRY(run_gemm(m, st, &m->enc_prenet[i], 1, false, g));
-    cur = w.pre[i]; curd = hp.enc_prenet[i];
-  }
+  TRY(front_forward_train(x, ids, speaker_id, B, T_in, w.pre, w.spk));
+  const float* cur = w.pre[hp.enc_prenet_n - 1];
   const bool dv = is_deepvoice(m), simple = is_simple(m);
-  const int S = hp.speaker_embedding_size;
-  if ((dv || simple) && !speaker_id) return fail(TACO_ERR_ARG, "speaker_id required for a multi-speaker model");
-  if (simple) {      // the embedding row of every utterance (tacotron.py:47-50); concatenated in the decoder and the linear head
-    hipLaunchKernelGGL(k_gather_rows, EWGRID((size_t)B * S), 0, st, AP(m, m->spk_emb), speaker_id, B, S, w.spk.emb);
-    HIPCHK(hipGetLastError());
-  }
-  if (dv) TRY(spk_forward(m, st, spk_ids(speaker_id), B, w.spk));       // before_highway, encoder / attention / decoder initial states (tacotron.py:52-79)
   const int L = hp.dec_layer_num;
   const float* dec_init[4] = {nullptr, nullptr, nullptr, nullptr}; float* d_dec_init[4] = {nullptr, nullptr, nullptr, nullptr};
   for (int i = 0; i < L && dv; ++i) { dec_init[i] = w.spk.vec[3 + i]; d_dec_init[i] = w.dvec[3 + i]; }
   TRY(cbhg_forward_train(x, m->enc, t->tp.enc, "encoder_cbhg", cur, B, T_in, lengths, w.enc, dv ? w.spk.vec[0] : nullptr, dv ? w.spk.vec[1] : nullptr));
   const float* enc_out = w.enc.out;
-  // teacher inputs: every r-th target frame (helpers.py:44): teach[b, t] = mel_targets[b, t*r + r-1]
-  hipLaunchKernelGGL(k_copy2d, EWGRID((size_t)B * n * Mm), 0, st, mel_tgt + (size_t)(r - 1) * Mm, r * Mm, w.teach, Mm, B * n, Mm);
-  HIPCHK(hipGetLastError());
+  TRY(teacher_frames(x, mel_tgt, B, n, w.teach));
   float* mel = mel_out ? mel_out : w.mel; float* lin = lin_out ? lin_out : w.linear;
   if (feed_back && do_backward) return fail(TACO_ERR_UNSUPPORTED, "rnn_decoder_test_mode is forward-only (the reference uses it for the test model's loss, train.py:158-166)");
   TRY(decoder_forward_train(x, enc_out, B, T_in, n, w.teach, mel, align_out, w.dec, feed_back, dv ? w.spk.vec[2] : nullptr, dv ? dec_init : nullptr,
                             simple ? w.spk.emb : nullptr));
   TRY(cbhg_forward_train(x, m->post, t->tp.post, "post_cbhg", mel, B, T_out, nullptr, w.post));
-  { GemmCall g; g.x = w.post.out; g.ldx = 2 * hp.post_rnn_size; g.M = Mp; g.out = lin; g.ldo = F;
-    if (simple) {    // linear(concat(tiled speaker_embed, post)) (tacotron.py:226-235): the speaker rows give one vector per utterance
-      SkJob j = sk_linear(m, m->lin_spk, w.spk.emb, S, S, nullptr, 0, ACT_NONE, w.linrv, F);
-      TRY(run_skinny(st, B, &j, 1));
-      g.T = T_out; g.rowvec = w.linrv; g.ldrv = F;
-    }
-    TRY(run_gemm(m, st, &m->linear, 1, false, g)); }
-  // ---- loss (tacotron.py:274-302) ----
-  if (d_losses) TRY(taco_loss_f32((void*)st, mel, mel_tgt, lin, lin_tgt, loss_coeff, B, T_out, Mm, F, prioritize_loss, sample_rate, d_losses,
-                                  w.losspart, (size_t)TR_MAXBLK * 8 * sizeof(double)));
+  TRY(head_forward_train(x, w.post.out, mel, simple ? w.spk.emb : nullptr, mel_tgt, lin_tgt, loss_coeff, B, T_out, prioritize_loss, sample_rate, lin, w.linrv,
+                         d_losses, w.losspart));
   if (!do_backward) return 0;
   // ---- backward ----
   HIPCHK(zero_async(G, t->NP * sizeof(float), st));
-  int c_lo = 0, c_hi = 0; float s_lin = 1.0f / ((float)Mp * F), s_band = 0.f;
-  if (prioritize_loss) {
-    c_hi = (int)(5000.0 / (sample_rate * 0.5) * F); c_lo = (int)(165.0 / (sample_rate * 0.5) * F);
-    s_lin = 0.5f / ((float)Mp * F); s_band = 0.5f / ((float)Mp * (c_hi - c_lo));
-  }
-  hipLaunchKernelGGL(k_l1_grad, EWGRID((size_t)Mp * Mm), 0, st, mel, mel_tgt, loss_coeff, Mp, T_out, Mm, 1.0f / ((float)Mp * Mm), 0, 0, 0.f, w.dmel);
-  hipLaunchKernelGGL(k_l1_grad, EWGRID((size_t)Mp * F), 0, st, lin, lin_tgt, loss_coeff, Mp, T_out, F, s_lin, c_lo, c_hi, s_band, w.dlin);
-  HIPCHK(hipGetLastError());
-  const int Hp2 = 2 * hp.post_rnn_size;
-  TRY(run_wgrad(x, w.post.out, nullptr, Hp2, w.dlin, F, x.g("linear/kernel") + (simple ? (size_t)S * F : 0), F, Mp, 0, Hp2, F));
-  if (simple) {      // speaker rows of the head: the embedding is constant over time, so they see the time-summed gradient
-    HIPCHK(zero_async(w.dspk_emb, (size_t)B * S * sizeof(float), st));
-    hipLaunchKernelGGL(k_time_sum, EWGRID((size_t)B * F), 0, st, w.dlin, w.dlin_sum, B, T_out, F);
-    HIPCHK(hipGetLastError());
-    TRY(run_wgrad(x, w.spk.emb, nullptr, S, w.dlin_sum, F, x.g("linear/kernel"), F, B, 0, S, F));
-    SkJob j = sk_T(m, t->tp.lin_spk_T, w.dlin_sum, F, w.dspk_emb, S);
-    TRY(run_skinny(st, B, &j, 1));
-  }
-  TRY(run_colsum(x, w.dlin, F, nullptr, 0, nullptr, nullptr, x.g("linear/bias"), nullptr, Mp, F, 0));
-  float* dpost = w.dpost; float* dmel_post = w.dmel_post;
-  TRY(run_dgrad(x, t->tp.lin_d, w.dlin, F, Mp, 0, dpost, Hp2));
-  TRY(cbhg_backward(x, m->post, t->tp.post, "post_cbhg", mel, nullptr, B, T_out, nullptr, dpost, dmel_post, w.post));
-  hipLaunchKernelGGL(k_add2d, EWGRID((size_t)Mp * Mm), 0, st, w.dmel, Mm, dmel_post, Mm, Mp, Mm);
-  HIPCHK(hipGetLastError());
+  TRY(head_backward(x, w.post.out, mel, lin, simple ? w.spk.emb : nullptr, mel_tgt, lin_tgt, loss_coeff, B, T_out, prioritize_loss, sample_rate, w.dmel, w.dlin,
+                    w.dlin_sum, w.dspk_emb, w.dpost));
+  TRY(cbhg_backward(x, m->post, t->tp.post, "post_cbhg", mel, nullptr, B, T_out, nullptr, w.dpost, w.dmel_post, w.post));
+  TRY(head_backward_join(x, w.dmel, w.dmel_post, B, T_out));
   TRY(decoder_backward(x, enc_out, B, T_in, n, w.teach, w.dmel, w.denc, w.dec, dv ? w.spk.vec[2] : nullptr, dv ? dec_init : nullptr,
                        dv ? w.dvec[2] : nullptr, dv ? d_dec_init : nullptr, simple ? w.dspk_emb : nullptr));
-  if (simple) {
-    run_embed_bwd(x, w.dspk_emb, speaker_id, x.g("speaker_embedding"), B, S, hp.num_speakers);
-    HIPCHK(hipGetLastError());
-  }
-  float* dpre = w.dpre[hp.enc_prenet_n - 1];
-  TRY(cbhg_backward(x, m->enc, t->tp.enc, "encoder_cbhg", cur, nullptr, B, T_in, lengths, w.denc, dpre, w.enc,
+  if (simple) TRY(speaker_rows_backward(x, w.dspk_emb, speaker_id, B));
+  TRY(cbhg_backward(x, m->enc, t->tp.enc, "encoder_cbhg", cur, nullptr, B, T_in, lengths, w.denc, w.dpre[hp.enc_prenet_n - 1], w.enc,
                     dv ? w.spk.vec[1] : nullptr, dv ? w.dvec[1] : nullptr, dv ? w.dvec[0] : nullptr, w.rowidx));
-  if (dv) {   // speaker conditioning backward (tacotron.py:52-79)
-    const std::vector<std::string> names = spk_vector_names(hp);
-    const int dims[3] = {hp.enc_prenet[hp.enc_prenet_n - 1], hp.enc_rnn_size * 2, hp.attention_state_size};
-    if (S == 1) {
-      for (size_t i = 0; i < names.size(); ++i) {
-        const int dd = i < 3 ? dims[i] : hp.dec_rnn_size;
-        run_embed_bwd(x, w.dvec[i], speaker_id, x.g("spk/" + names[i] + "/table"), B, dd, hp.num_speakers);
-      }
-    } else {
-      HIPCHK(zero_async(w.dspk_emb, (size_t)B * S * sizeof(float), st));
-      for (size_t i = 0; i < names.size(); ++i) {
-        const int dd = i < 3 ? dims[i] : hp.dec_rnn_size;
-        hipLaunchKernelGGL(k_softsign_bwd, EWGRID((size_t)B * dd), 0, st, w.dvec[i], w.spk.vec[i], w.dzs, B * dd);
-        TRY(run_wgrad(x, w.spk.emb, nullptr, S, w.dzs, dd, x.g("spk/" + names[i] + "/kernel"), dd, B, 0, S, dd));
-        TRY(run_colsum(x, w.dzs, dd, nullptr, 0, nullptr, nullptr, x.g("spk/" + names[i] + "/bias"), nullptr, B, dd, 0));
-        SkJob j = sk_T(m, t->tp.spk_T[i], w.dzs, dd, w.dec.tmp1, S);
-        TRY(run_skinny(st, B, &j, 1));
-        hipLaunchKernelGGL(k_add2d, EWGRID((size_t)B * S), 0, st, w.dspk_emb, S, w.dec.tmp1, S, B, S);
-      }
-      run_embed_bwd(x, w.dspk_emb, speaker_id, x.g("speaker_embedding"), B, S, hp.num_speakers);
-    }
-    HIPCHK(hipGetLastError());
-  }
-  for (int i = hp.enc_prenet_n - 1; i >= 0; --i) {
-    const int N = hp.enc_prenet[i];
-    const std::string nm = "prenet/dense_" + std::to_string(i + 1);
-    hipLaunchKernelGGL(k_relu_bwd, EWGRID((size_t)Me * N), 0, st, dpre, N, w.pre[i], N, dpre, N, Me, N);
-    HIPCHK(hipGetLastError());
-    if (i > 0) TRY(run_wgrad(x, w.pre[i - 1], nullptr, hp.enc_prenet[i - 1], dpre, N, x.g(nm + "/kernel"), N, Me, 0, hp.enc_prenet[i - 1], N));
-    else TRY(run_wgrad(x, x.p("embedding"), ids, hp.embedding_size, dpre, N, x.g(nm + "/kernel"), N, Me, 0, hp.embedding_size, N));
-    TRY(run_colsum(x, dpre, N, nullptr, 0, nullptr, nullptr, x.g(nm + "/bias"), nullptr, Me, N, 0));
-    float* dnext = (i > 0) ? w.dpre[i - 1] : w.demb;
-    const int nd = (i > 0) ? hp.enc_prenet[i - 1] : hp.embedding_size;
-    TRY(run_dgrad(x, t->tp.encpre_d[i], dpre, N, Me, 0, dnext, nd));
-    dpre = dnext;
-  }
-  run_embed_bwd(x, dpre, ids, x.g("embedding"), (int)Me, hp.embedding_size, hp.num_symbols);
-  HIPCHK(hipGetLastError());
-  return 0;
+  return front_backward(x, ids, speaker_id, B, T_in, w.pre, w.dpre, w.demb, w.spk, w.dvec, w.dspk_emb, w.dzs, w.dec.tmp1);
   };
   const int rc = step();
   t->planes_problems = s.planes_problems;

@@ -283,6 +283,145 @@ int taco_train_debug_decoder(taco_train* t, void* hip_stream, float* d_params, f
   }
   return rc;
 }
+// Test hooks: the two ENDS of the step alone -- front_forward_train + [speaker_rows_backward +] front_backward, and teacher_frames + head_forward_train +
+// head_backward + head_backward_join -- on caller data, as the step calls them: the same TrainCtx and StepState (deterministic scratch, plane scratch sized
+// as the step's for these rows), the step's buffers carved as carve_train carves them, the trainer's current switches.  The scope's parameter gradients are
+// ADDED into d_grads at their taco_train_param_offset; nothing else of d_grads is written.  Every refusal below comes before the first HIP call.
+struct FrontDebugWs { float* pre[4]; float* dpre[4]; float* demb; SpkWs spk; float *dspk_emb, *dzs, *tmp, *detscr; uint4* wpscr; size_t wps_uint4; };
+static void carve_front_debug(Carver& cv, const taco_train* t, int B, int T_in, FrontDebugWs& w) {
+  const taco_model* m = t->sm;
+  const taco_hparams& hp = m->hp;
+  const size_t Me = (size_t)B * T_in;
+  for (int i = 0; i < hp.enc_prenet_n; ++i) { w.pre[i] = cv.f(Me * hp.enc_prenet[i]); w.dpre[i] = cv.f(Me * std::max(hp.enc_prenet[i], hp.embedding_size)); }
+  w.demb = cv.f(Me * hp.embedding_size);
+  carve_spk(cv, m, B, w.spk);
+  int dmax = std::max(std::max(hp.enc_prenet[hp.enc_prenet_n - 1], hp.enc_rnn_size * 2), std::max(hp.attention_state_size, hp.dec_rnn_size));
+  const size_t S = (size_t)std::max(hp.speaker_embedding_size, 1);
+  w.dspk_emb = cv.f(B * S); w.dzs = cv.f((size_t)B * dmax); w.tmp = cv.f(B * S);
+  w.detscr = cv.f(t->deterministic ? DET_SCRATCH_FLOATS : 1);
+  w.wps_uint4 = wps_scratch_uint4(t, Me);
+  w.wpscr = (uint4*)cv.raw(w.wps_uint4 * sizeof(uint4));
+}
+size_t taco_train_debug_front_workspace_bytes(const taco_train* t, int B, int T_in) {
+  if (!t || B <= 0 || T_in <= 0) return 0;
+  Carver cv(nullptr, 0);
+  FrontDebugWs w; carve_front_debug(cv, t, B, T_in, w);
+  return cv.off;
+}
+int taco_train_debug_front(taco_train* t, void* hip_stream, float* d_params, float* d_grads, const int32_t* d_ids, const int32_t* d_speaker_id,
+                           const float* d_dpre, const float* const* d_dvec, const float* d_dspk_emb, int B, int T_in, float* d_pre, float* const* d_vec,
+                           float* d_spk_emb, void* d_ws, size_t ws_bytes, uint32_t* paths) {
+  if (!t || !d_params || !d_grads || !d_ids || !d_dpre || !d_pre || !d_ws) return fail(TACO_ERR_ARG, "null argument");
+  taco_model* m = t->sm;
+  const taco_hparams& hp = m->hp;
+  const bool dv = is_deepvoice(m), simple = is_simple(m);
+  const int nv = 3 + hp.dec_layer_num, S = hp.speaker_embedding_size, np = hp.enc_prenet_n;
+  if (nv > 8 || np < 1 || np > 4) return fail(TACO_ERR_UNSUPPORTED, "%d decoder layers, %d encoder prenet layers", hp.dec_layer_num, np);
+  if (!dv && !simple && (d_speaker_id || d_dvec || d_dspk_emb || d_vec || d_spk_emb)) return fail(TACO_ERR_ARG, "speaker inputs and outputs given to a single-speaker model");
+  if ((dv || simple) && !d_speaker_id) return fail(TACO_ERR_ARG, "speaker_id required for a multi-speaker model");
+  if ((d_dvec && !d_vec) || (d_dspk_emb && !d_spk_emb)) return fail(TACO_ERR_ARG, "a gradient without its forward output (speaker vectors / speaker rows)");
+  if (dv) {
+    if (d_dspk_emb) return fail(TACO_ERR_ARG, "the gradient of the speaker rows is an input of model type simple only");
+    if (!d_vec || !d_dvec) return fail(TACO_ERR_ARG, "model type deepvoice: the speaker vectors and their gradients are required");
+    for (int i = 0; i < nv; ++i) if (!d_vec[i] || !d_dvec[i]) return fail(TACO_ERR_ARG, "model type deepvoice: speaker vector %d or its gradient is null", i);
+    if (S == 1 && d_spk_emb) return fail(TACO_ERR_ARG, "speaker_embedding_size 1 has no speaker rows (the vectors come from tables)");
+  }
+  if (simple) {
+    if (d_vec || d_dvec) return fail(TACO_ERR_ARG, "speaker vectors are model type deepvoice's");
+    if (!d_spk_emb || !d_dspk_emb) return fail(TACO_ERR_ARG, "model type simple: the speaker rows and their gradient are required");
+  }
+  TRY(check_common(m, B, T_in));
+  if (!al16h(d_ws)) return fail(TACO_ERR_ARG, "workspace %p is not 16-byte aligned", d_ws);
+  if ((m->bf3 || m->bf3x6 || t->dgrad_bf3) && !t->bf3_current) return fail(TACO_ERR_STATE, "taco_train_set_exact_gemm(0) needs a taco_train_refresh before the next step (the split-bf16 weight planes are stale)");
+  Carver cv(d_ws, ws_bytes);
+  FrontDebugWs w; carve_front_debug(cv, t, B, T_in, w);
+  if (!cv.ok()) return fail(TACO_ERR_STATE, "workspace too small: need %zu bytes, have %zu", cv.off, ws_bytes);
+  if (!m->d_err) return fail(TACO_ERR_STATE, "a host-only trainer (taco_debug_train_create_host) cannot run");
+  HIPCHK(hipSetDevice(m->device));
+  hipStream_t st = (hipStream_t)hip_stream;
+  StepState s;
+  if (t->deterministic) { s.det = w.detscr; s.det_cap = DET_SCRATCH_FLOATS; }
+  if (t->wgrad_planes) { s.wps = w.wpscr; s.wps_cap = w.wps_uint4; }
+  TrainCtx x{t, st, d_params, d_grads, false, &s};
+  const size_t Me = (size_t)B * T_in;
+  const int dims[3] = {hp.enc_prenet[np - 1], hp.enc_rnn_size * 2, hp.attention_state_size};
+  const auto run = [&]() -> int {
+    TRY(front_forward_train(x, d_ids, d_speaker_id, B, T_in, w.pre, w.spk));
+    HIPCHK(hipMemcpyAsync(d_pre, w.pre[np - 1], Me * hp.enc_prenet[np - 1] * sizeof(float), hipMemcpyDeviceToDevice, st));
+    for (int i = 0; i < nv && dv; ++i)
+      HIPCHK(hipMemcpyAsync(d_vec[i], w.spk.vec[i], (size_t)B * (i < 3 ? dims[i] : hp.dec_rnn_size) * sizeof(float), hipMemcpyDeviceToDevice, st));
+    if (d_spk_emb) HIPCHK(hipMemcpyAsync(d_spk_emb, w.spk.emb, (size_t)B * S * sizeof(float), hipMemcpyDeviceToDevice, st));
+    // the step's dpre is what the encoder CBHG's backward leaves in the last prenet layer's gradient buffer; the prenet backward works in place
+    HIPCHK(hipMemcpyAsync(w.dpre[np - 1], d_dpre, Me * hp.enc_prenet[np - 1] * sizeof(float), hipMemcpyDeviceToDevice, st));
+    if (simple) TRY(speaker_rows_backward(x, d_dspk_emb, d_speaker_id, B));
+    return front_backward(x, d_ids, d_speaker_id, B, T_in, w.pre, w.dpre, w.demb, w.spk, d_dvec, w.dspk_emb, w.dzs, w.tmp);
+  };
+  const int rc = run();
+  t->planes_problems = s.planes_problems;
+  if (paths) *paths = s.end_paths;
+  return rc;
+}
+struct HeadDebugWs { float *dlin, *linrv, *dlin_sum, *losspart, *detscr; uint4* wpscr; size_t wps_uint4; };
+static void carve_head_debug(Carver& cv, const taco_train* t, int B, int T_out, HeadDebugWs& w) {
+  const taco_model* m = t->sm;
+  const taco_hparams& hp = m->hp;
+  const size_t Mp = (size_t)B * T_out;
+  w.dlin = cv.f(Mp * hp.num_freq);
+  w.losspart = (float*)cv.raw((size_t)TR_MAXBLK * 8 * sizeof(double));
+  const size_t nrv = is_simple(m) ? (size_t)B * hp.num_freq : 1;
+  w.linrv = cv.f(nrv); w.dlin_sum = cv.f(nrv);
+  w.detscr = cv.f(t->deterministic ? DET_SCRATCH_FLOATS : 1);
+  w.wps_uint4 = wps_scratch_uint4(t, Mp);
+  w.wpscr = (uint4*)cv.raw(w.wps_uint4 * sizeof(uint4));
+}
+size_t taco_train_debug_head_workspace_bytes(const taco_train* t, int B, int T_out) {
+  if (!t || B <= 0 || T_out <= 0) return 0;
+  Carver cv(nullptr, 0);
+  HeadDebugWs w; carve_head_debug(cv, t, B, T_out, w);
+  return cv.off;
+}
+int taco_train_debug_head(taco_train* t, void* hip_stream, float* d_params, float* d_grads, const float* d_post_out, const float* d_mel, const float* d_mel_tgt,
+                          const float* d_lin_tgt, const float* d_loss_coeff, const float* d_dmel_post, const float* d_spk_emb, int B, int T_out,
+                          int prioritize_loss, int sample_rate, float* d_teacher, float* d_lin, float* d_losses, float* d_dmel, float* d_dpost,
+                          float* d_dspk_emb, void* d_ws, size_t ws_bytes) {
+  if (!t || !d_params || !d_grads || !d_post_out || !d_mel || !d_mel_tgt || !d_lin_tgt || !d_teacher || !d_lin || !d_losses || !d_dmel || !d_dpost || !d_ws)
+    return fail(TACO_ERR_ARG, "null argument");
+  taco_model* m = t->sm;
+  const taco_hparams& hp = m->hp;
+  const int S = simple_S(m), r = hp.reduction_factor;
+  if (d_dspk_emb && !d_spk_emb) return fail(TACO_ERR_ARG, "a gradient output without its input");
+  if (S && !(d_spk_emb && d_dspk_emb)) return fail(TACO_ERR_ARG, "model type simple: the speaker rows and their gradient buffer are required");
+  if (!S && d_spk_emb) return fail(TACO_ERR_ARG, "speaker rows enter the linear head of model type simple only");
+  if (B <= 0 || T_out <= 0 || sample_rate <= 0) return fail(TACO_ERR_ARG, "bad shape B=%d T_out=%d or sample rate %d", B, T_out, sample_rate);
+  if (B > 64) return fail(TACO_ERR_UNSUPPORTED, "batch %d > 64 rows per device is not supported: shard the batch", B);
+  if (T_out % r) return fail(TACO_ERR_SHAPE, "T_out %d is not a multiple of the reduction factor %d", T_out, r);
+  const int n = T_out / r;
+  if (n > hp.max_iters) return fail(TACO_ERR_SHAPE, "T_out/r = %d exceeds max_iters %d", n, hp.max_iters);
+  if (!al16h(d_ws)) return fail(TACO_ERR_ARG, "workspace %p is not 16-byte aligned", d_ws);
+  if ((m->bf3 || m->bf3x6 || t->dgrad_bf3) && !t->bf3_current) return fail(TACO_ERR_STATE, "taco_train_set_exact_gemm(0) needs a taco_train_refresh before the next step (the split-bf16 weight planes are stale)");
+  Carver cv(d_ws, ws_bytes);
+  HeadDebugWs w; carve_head_debug(cv, t, B, T_out, w);
+  if (!cv.ok()) return fail(TACO_ERR_STATE, "workspace too small: need %zu bytes, have %zu", cv.off, ws_bytes);
+  if (!m->d_err) return fail(TACO_ERR_STATE, "a host-only trainer (taco_debug_train_create_host) cannot run");
+  HIPCHK(hipSetDevice(m->device));
+  hipStream_t st = (hipStream_t)hip_stream;
+  StepState s;
+  if (t->deterministic) { s.det = w.detscr; s.det_cap = DET_SCRATCH_FLOATS; }
+  if (t->wgrad_planes) { s.wps = w.wpscr; s.wps_cap = w.wps_uint4; }
+  TrainCtx x{t, st, d_params, d_grads, false, &s};
+  const auto run = [&]() -> int {
+    TRY(teacher_frames(x, d_mel_tgt, B, n, d_teacher));
+    TRY(head_forward_train(x, d_post_out, d_mel, d_spk_emb, d_mel_tgt, d_lin_tgt, d_loss_coeff, B, T_out, prioritize_loss, sample_rate, d_lin, w.linrv, d_losses,
+                           w.losspart));
+    TRY(head_backward(x, d_post_out, d_mel, d_lin, d_spk_emb, d_mel_tgt, d_lin_tgt, d_loss_coeff, B, T_out, prioritize_loss, sample_rate, d_dmel, w.dlin, w.dlin_sum,
+                      d_dspk_emb, d_dpost));
+    if (d_dmel_post) TRY(head_backward_join(x, d_dmel, d_dmel_post, B, T_out));
+    return 0;
+  };
+  const int rc = run();
+  t->planes_problems = s.planes_problems;
+  return rc;
+}
 // Test hook: a trainer that stays on the host -- the shadow model is packed (model_pack_host) and never uploaded, no device is touched.  It serves the
 // argument and state checks of the taco_train_debug_* hooks, which come before their first HIP call; nothing may be launched on it.
 int taco_debug_train_create_host(const taco_hparams* hp, taco_train** out) {

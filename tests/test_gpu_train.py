@@ -3,7 +3,8 @@ forward and tests/torch_formulation.py's reverse-mode autograd of the same graph
 
 The gradient bound of these tests is 2e-3 of max(max|g_k|, 1e-3 * |g|), |g| the norm of the whole model's gradient: tensors far below that
 floor (the attention's query and memory layers, attention_v, attention_b) are bounded per tensor by the block tests instead --
-tests/test_gpu_decoder_train.py for the decoder, tests/test_gpu_cbhg_train.py for the two CBHGs."""
+tests/test_gpu_decoder_train.py for the decoder, tests/test_gpu_cbhg_train.py for the two CBHGs, tests/test_gpu_ends_train.py for the two
+ends of the step (embedding, encoder prenet and speaker conditioning; linear head, losses and the seams between the blocks)."""
 import numpy as np
 import pytest
 
