@@ -221,6 +221,55 @@ int taco_attention_trim(void* hip_stream, const float* d_alignments, const int32
  * 1, 2, 3 -> TACO_ERR_ARG; mode 2 -> TACO_ERR_UNSUPPORTED: the reference calls np.pow there, which does not exist (synthesizer.py:181-188),
  * so mode 2 is refused rather than guessed at. */
 int taco_manual_alignments(void* hip_stream, const float* d_alignments, int B, int T_in, int n_steps, int mode, float* d_manual);
+/* ---- rate, per-token duration and pitch control on the spectrogram, between the attention trim and a vocoder.  NOT in the reference: its
+ * synthesizer says a sentence at the speed and pitch the model chose.  The forward produces a MAGNITUDE spectrogram and Griffin-Lim
+ * invents the phase afterwards, so speed is a resampling of the frame axis and pitch a resampling of the bin axis; the alignments
+ * attribute every decoder step to an input token, so the stretch can differ per token.  tests/warp_reference.py restates both calls in
+ * NumPy, the map in int64 exactly as below. ----
+ * taco_spec_warp_map: the integer time map of every batch row, one launch (k_warp_map, csrc/taco_warp.h).  Inputs: d_alignments
+ * [B, T_in, n_steps] (nullable); d_frames [B] (nullable: T) -- taco_attention_trim's d_spec_end as it stands; d_row_stretch [B] fp32
+ * (nullable: 1); d_token_stretch [B, T_in] fp32 (nullable: 1; needs d_alignments); T = n_steps * reduction_factor source frames; T_out
+ * = the capacity of the outputs.  For row b:
+ *   f = clamp(d_frames[b], 1, T).
+ *   tok(s) = argmax over e in [0, T_in) of d_alignments[b, e, s] for decoder step s: the first maximum wins, a NaN counts as the maximum
+ *   and the first NaN wins (the rule of taco_manual_alignments, on the other axis).  Source frame t < f belongs to step t / r.
+ *   Its duration is an integer in units of 2^-16 output frame:
+ *     d_t = clamp(lrint(fp32(row_stretch[b] * token_stretch[b, tok(t / r)]) * 65536), 2^12, 2^20)
+ *   -- one correctly rounded fp32 product, then an exact scaling; a NaN or a non-positive product gives 2^12.
+ *   C_t = the inclusive prefix sum of d_t in int64, C_-1 = 0 (integer sums are associative: any scan shape gives the same bits).
+ *   d_out_frames[b] = clamp((C_{f-1} + 2^15) >> 16, 1, T_out).
+ *   For output frame j < d_out_frames[b], tau = j << 16: d_src[b, j] = the t with C_{t-1} <= tau < C_t (tau < C_{f-1} always holds there),
+ *   d_frac[b, j] = ((tau - C_{src-1}) << 16) / d_src, an integer division, in [0, 65536).  For j >= d_out_frames[b]: src = f - 1, frac = 0.
+ *   d_token_frames [B, T_in] int32 (nullable; needs d_alignments): the number of source frames t < f attributed to each token -- the
+ *   model's own durations, which a caller needs before asking for different ones.  Every element is written exactly once per call.
+ * d_src, d_frac [B, T_out] int32, d_out_frames [B].  d_workspace: taco_spec_warp_workspace_bytes(B, T), 8-byte aligned; it holds C, so T
+ * is not bounded by the kernel.
+ * taco_spec_warp: the gather and the interpolation, one launch (k_spec_warp): d_spec [B, T, W] fp32 with any W >= 1 (num_freq for the
+ * linear outputs, num_mels for the mel outputs), the map above, d_frames, d_freq_scale [B] fp32 (nullable) -> d_out [B, T_out, W].  Per
+ * output element, THE TIME INTERPOLATION FIRST, THEN THE FREQUENCY INTERPOLATION, every operation an fp32 operation rounded on its own:
+ *   t0 = src, t1 = min(t0 + 1, f - 1), w_t = frac * 2^-16 (exact in fp32);
+ *   v(k) = x[t0, k] when frac == 0 (the bits are copied; a NaN next door never leaks), else x[t0, k] + w_t * (x[t1, k] - x[t0, k]);
+ *   v(k) = +0 for k >= W: normalised 0 is the floor level, and content scaled past Nyquist is gone.
+ *   Without a frequency scale out[j, k] = v(k).  With c = d_freq_scale[b]: q = fp32(k * c), k0 = (int)q, w_f = q - k0; out = v(k0) if
+ *   w_f == 0, otherwise v(k0) + w_f * (v(k0 + 1) - v(k0)).  (c = 2^(-p / 12) raises the pitch by p semitones.  A q outside [0, W) --
+ *   a NaN or a negative c among them -- gives +0.)
+ *   Rows j >= d_out_frames[b] are written as +0.  Every element of d_out is written exactly once; nothing at frames >= f of the input is
+ *   ever read (src is clamped to [0, f - 1] and frac to [0, 65535] on the device: a garbage map gives a wrong picture, nothing worse).
+ * NOT reproduced / out of scope: formant-preserving pitch shifting (it needs the envelope separated; the bin-axis scale moves the formants
+ * with the pitch, as a resampling-based shift does) and waveform-domain stretching of recordings.
+ * Both calls launch on hip_stream only: no read-back, allocation, memset or synchronisation; safe under stream capture; no atomics, two
+ * calls give the same bits.  Checked before any HIP call: a null required pointer (d_src, d_frac, d_out_frames, d_workspace; d_spec,
+ * d_out); B, T, T_out, reduction_factor or W < 1, and T_in or n_steps < 1 when d_alignments is given; T != n_steps * reduction_factor
+ * when d_alignments is given; d_token_stretch or d_token_frames without d_alignments; a misaligned workspace; an output that shares a byte
+ * with an input, the workspace or another output -> TACO_ERR_ARG; a workspace that is too small -> TACO_ERR_STATE; W >= 2^24 ->
+ * TACO_ERR_UNSUPPORTED. */
+size_t taco_spec_warp_workspace_bytes(int B, int T);
+int taco_spec_warp_map(void* hip_stream, const float* d_alignments, const int32_t* d_frames, const float* d_row_stretch,
+                       const float* d_token_stretch, int B, int T_in, int n_steps, int reduction_factor, int T, int T_out,
+                       int32_t* d_src, int32_t* d_frac, int32_t* d_out_frames, int32_t* d_token_frames,
+                       void* d_workspace, size_t workspace_bytes);
+int taco_spec_warp(void* hip_stream, const float* d_spec, const int32_t* d_frames, const int32_t* d_src, const int32_t* d_frac,
+                   const int32_t* d_out_frames, const float* d_freq_scale, int B, int T, int W, int T_out, float* d_out);
 /* The stop rule (helpers.py:29 + dynamic_decode: the loop ends after the first step at which every row has emitted an all-zero
  * step) evaluated on a finished mel buffer d_mel [B, n_steps, width = r*num_mels] per group of rows_per_group consecutive rows:
  * d_stop[B / rows_per_group].  For requests that were served together through one plan (PlanPool coalesce > 1), whose plan-wide

@@ -300,6 +300,17 @@ int taco_debug_f0_info(int* out, int n);
  * frames per workgroup (fewer than taco_debug_f0_info's [3] where that many frames' span does not fit the LDS), floats of LDS.  Host only;
  * TACO_ERR_ARG for a null pointer, window or hop < 1, tau_max < 2 or a frame above the largest. */
 int taco_debug_f0_plan(int window, int tau_max, int hop, int* out);
+/* Test hook: the sizes at which k_warp_map and k_spec_warp (csrc/taco_warp.h) change path, so that tests/test_gpu_warp.py can sit on either
+ * side of each.  The first n (at most 4) values are written: out[0] = frames of one scan chunk (a row beyond it runs as further chunks with a
+ * carry), [1] = lanes of a wave (the shuffle scan inside a chunk; the waves' totals go through LDS), [2] = output rows of one workgroup of
+ * k_spec_warp, [3] = the widest row (W) whose frequency gather is staged in LDS; wider rows read the source rows from the cache.  Host
+ * only; a null pointer or n < 0 is TACO_ERR_ARG. */
+int taco_debug_warp_info(int* out, int n);
+/* Test and timing hook: taco_spec_warp with the frequency gather reading the source rows straight from the cache at every width, the form
+ * rows wider than taco_debug_warp_info's [3] always take, in place of the row staged in LDS.  Arguments, results and errors are
+ * taco_spec_warp's, and so are the bits of d_out. */
+int taco_debug_spec_warp_direct(void* hip_stream, const float* d_spec, const int32_t* d_frames, const int32_t* d_src, const int32_t* d_frac,
+                                const int32_t* d_out_frames, const float* d_freq_scale, int B, int T, int W, int T_out, float* d_out);
 
 #ifdef __cplusplus
 }

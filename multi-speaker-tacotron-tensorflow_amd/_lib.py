@@ -253,6 +253,11 @@ PROTOTYPES = {
     "taco_debug_f0_yin_plain": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, C.c_float, C.c_float, C.c_float, _P, _P, _P]),
     "taco_debug_f0_info": (_I, [C.POINTER(_I), _I]),
     "taco_debug_f0_plan": (_I, [_I, _I, _I, C.POINTER(_I)]),
+    "taco_spec_warp_workspace_bytes": (_S, [_I, _I]),
+    "taco_spec_warp_map": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _S]),
+    "taco_spec_warp": (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P]),
+    "taco_debug_warp_info": (_I, [C.POINTER(_I), _I]),
+    "taco_debug_spec_warp_direct": (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P]),
 }
 
 _lib = None

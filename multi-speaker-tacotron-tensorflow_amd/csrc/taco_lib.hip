@@ -1719,6 +1719,7 @@ static void loss_band(int sample_rate, int num_freq, int* lo, int* hi) {
 #include "taco_align.h"
 #include "taco_dtw.h"
 #include "taco_f0.h"
+#include "taco_warp.h"
 
 extern "C" {
 
@@ -2488,5 +2489,6 @@ int taco_adam_step_f32(void* hip_stream, float* d_params, const float* d_grads, 
 #include "taco_align_api.h"
 #include "taco_dtw_api.h"
 #include "taco_f0_api.h"
+#include "taco_warp_api.h"
 
 }  // extern "C"

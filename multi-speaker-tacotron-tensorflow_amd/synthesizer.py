@@ -155,7 +155,8 @@ class Synthesizer(object):
 
     def synthesize_audio(self, texts=None, tokens=None, speaker_ids=None, end_of_sentence=True, attention_trim=True,
                          manual_alignments=None, seed=0, iters=None, pcm=True, librosa_trim=False, vocoder="griffin_lim",
-                         manual_attention_mode=0, momentum=None, return_convergence=False):
+                         manual_attention_mode=0, momentum=None, return_convergence=False, rate=None, token_stretch=None, pitch=None,
+                         return_durations=False):
         """The reference's synthesize -> plot_graph_and_save_audio chain up to the samples save_audio writes (synthesizer.py:119-126,
         242-264; audio/__init__.py:22-25), everything between the token upload and the audio download on the device: the forward, the
         attention trim on the device alignments, Griffin-Lim on every utterance's own frames read from the trim kernel's output, the
@@ -180,7 +181,18 @@ class Synthesizer(object):
         vocoder handle's value, 0 unless an earlier call set one; a value is set and stays set.
         return_convergence: `convergence` is set to a float32 array [N], each utterance's spectral convergence || |stft(y)| - S || /
         || S || over its own frames (GriffinLim.convergence), measured on the device on the vocoder's output before any librosa_trim;
-        for "griffin_lim" and "mel" -- with "tensorflow" it raises TacoError(TACO_ERR_ARG).  Off (the default): `convergence` is None."""
+        for "griffin_lim" and "mel" -- with "tensorflow" it raises TacoError(TACO_ERR_ARG).  Off (the default): `convergence` is None.
+        rate, token_stretch, pitch (prosody.py; not in the reference): how the sentence is spoken, applied to the spectrogram between the
+        attention trim and the vocoder (prosody.warp_map, prosody.warp) -- to `linear` for "griffin_lim" and "tensorflow", to the mel outputs
+        for "mel".  rate: a scalar or one value per row, > 1 is faster (row_stretch = float32(1 / rate)).  token_stretch: per row a sequence
+        of duration multipliers, one per token (a flat sequence serves a single row); shorter rows are padded with 1; every decoder step
+        takes the multiplier of the token it attends most to.  pitch: semitones, a scalar or one value per row, a scale of the bin axis
+        (prosody.semitones_to_scale), so formants move with it; with vocoder="mel" it raises TacoError(TACO_ERR_ARG): the mel axis is not
+        linear in frequency.  The vocoder receives the warped frame counts, kept in `warped_frames` [N]; `spec_end_idx` keeps meaning the
+        trim's frame counts.  return_durations: `token_frames` [N, T_in] is set, the trimmed frames attributed to each token -- the model's
+        own durations.  Values that are not finite and positive (rate, token_stretch) or finite (pitch), and sequences longer than the batch
+        or the token rows, raise TacoError(TACO_ERR_ARG) before the model runs.  With all four at their defaults nothing of this runs:
+        `warped_frames` and `token_frames` are None."""
         from . import _lib
         if manual_attention_mode > 0 and manual_alignments is not None:
             raise _lib.TacoError(_lib.TACO_ERR_ARG, "manual_attention_mode builds the second pass's alignments itself: it cannot be "
@@ -192,6 +204,7 @@ class Synthesizer(object):
         sequences = self._token_rows(texts, tokens)
         input_lengths = np.argmax(sequences == EOS_ID, 1).astype(np.int32)             # synthesizer.py:120
         speaker = self._speaker_feed(speaker_ids, len(sequences))
+        stretch = self._prosody_args(len(sequences), sequences.shape[1], rate, token_stretch, pitch, vocoder)
         linear, alignments = self.model.run(
             inputs=sequences.astype(np.int32), input_lengths=input_lengths, **speaker,
             manual_alignments=manual_alignments, is_manual_attention=manual_alignments is not None,
@@ -199,6 +212,29 @@ class Synthesizer(object):
         frames = None
         if attention_trim and end_of_sentence:
             frames = self._attention_trim_device(alignments, [len(seq) for seq in sequences])
+        trimmed = frames
+        self.warped_frames = self.token_frames = None
+        mel = None
+        if vocoder == "mel":
+            mel = self.model.mel_outputs                       # [N, steps, r * num_mels] or [N, frames, num_mels]: the same memory
+            mel = mel.reshape(mel.shape[0], -1, self.hparams.num_mels)
+        if stretch is not None:                                # rate / token_stretch / pitch: warp what the vocoder reads, hand it the new frame counts
+            from . import prosody
+            row_stretch, tok_stretch, freq_scale = stretch
+            r, T = self.hparams.reduction_factor, linear.shape[1]
+            wmap = prosody.warp_map(frames, T, r, alignments if tok_stretch is not None or return_durations else None, row_stretch, tok_stretch,
+                                    out_cap=prosody.out_frames_bound(T, row_stretch, tok_stretch), return_token_frames=return_durations)
+            if vocoder == "mel":
+                mel, frames = prosody.warp(mel, trimmed, wmap)
+            else:
+                linear, frames = prosody.warp(linear, trimmed, wmap, freq_scale)
+            self.warped_frames = frames.cpu().numpy()
+            tokf = wmap.token_frames
+        elif return_durations:
+            from . import prosody
+            tokf = prosody.token_frames(alignments, frames, self.hparams.reduction_factor)
+        if return_durations:
+            self.token_frames = tokf.cpu().numpy()
         if vocoder == "tensorflow":
             gl = self._griffin_lim_tf()
             wav, num_samples = gl.inv_spectrogram_tensorflow(linear, frames, iters=iters, momentum=momentum)
@@ -206,8 +242,6 @@ class Synthesizer(object):
             gl = self._griffin_lim()
             if not gl.inv_mels:
                 gl.set_inv_mel_basis()
-            mel = self.model.mel_outputs                       # [N, steps, r * num_mels] or [N, frames, num_mels]: the same memory
-            mel = mel.reshape(mel.shape[0], -1, self.hparams.num_mels)
             wav, num_samples = gl.inv_melspectrogram(mel, frames, seed=seed, iters=iters, momentum=momentum)
             sc = gl.convergence(gl.mel_to_linear(mel) ** float(gl.hp.power), wav, frames, kind="magnitude") if return_convergence else None
         else:
@@ -220,10 +254,59 @@ class Synthesizer(object):
             index = gl.trim(wav, num_samples, **self.LIBROSA_TRIM)
             num_samples = index[:, 1].contiguous()
         audio = gl.pcm16(wav, num_samples) if pcm else wav
-        self.spec_end_idx = None if frames is None else frames.cpu().numpy()
+        self.spec_end_idx = None if trimmed is None else trimmed.cpu().numpy()
         audio = audio.cpu().numpy()
         self.trim_index = None if index is None else index.cpu().numpy()
         return [a[:n] for a, n in zip(audio, num_samples.cpu().numpy() if index is None else self.trim_index[:, 1])]
+
+    @staticmethod
+    def _prosody_args(N, T_in, rate, token_stretch, pitch, vocoder):
+        """synthesize_audio's rate / token_stretch / pitch -> (row_stretch [N] or None, token_stretch [N, T_in] or None, freq_scale [N] or
+        None) as float32 host arrays, or None when all three are at their defaults.  Every refusal is a TacoError(TACO_ERR_ARG)."""
+        from . import _lib
+        from .prosody import semitones_to_scale
+
+        def bad(msg):
+            return _lib.TacoError(_lib.TACO_ERR_ARG, msg)
+
+        def per_row(v, what, positive):
+            try:
+                a = np.asarray(v, np.float64)
+            except (TypeError, ValueError):
+                raise bad("%s must be a number or one number per row" % what)
+            if a.ndim > 1 or (a.ndim == 1 and len(a) != N):
+                raise bad("%s must be a scalar or one value per row (%d), got shape %s" % (what, N, a.shape))
+            if not np.isfinite(a).all() or (positive and not (a > 0).all()):
+                raise bad("%s must be finite%s, got %r" % (what, " and > 0" if positive else "", v))
+            return np.broadcast_to(a, (N,))
+
+        if rate is None and token_stretch is None and pitch is None:
+            return None
+        if pitch is not None and vocoder == "mel":
+            raise bad("pitch scales a linear frequency axis: it serves the vocoders 'griffin_lim' and 'tensorflow', not 'mel'")
+        row = None if rate is None else (1.0 / per_row(rate, "rate", True)).astype(np.float32)
+        scale = None if pitch is None else semitones_to_scale(per_row(pitch, "pitch", False))
+        tok = None
+        if token_stretch is not None:
+            rows = list(token_stretch)
+            if rows and np.ndim(rows[0]) == 0:                 # a flat sequence: the one row of a batch of one
+                if N != 1:
+                    raise bad("token_stretch must hold one sequence per row; a flat sequence serves a batch of one, this one has %d rows" % N)
+                rows = [rows]
+            if len(rows) > N:
+                raise bad("token_stretch has %d rows, the batch has %d" % (len(rows), N))
+            tok = np.ones((N, T_in), np.float32)
+            for i, row_i in enumerate(rows):
+                try:
+                    a = np.asarray(row_i, np.float64)
+                except (TypeError, ValueError):
+                    raise bad("token_stretch row %d is not a sequence of numbers" % i)
+                if a.ndim != 1 or len(a) > T_in:
+                    raise bad("token_stretch row %d has shape %s, the token rows have %d tokens" % (i, a.shape, T_in))
+                if not np.isfinite(a).all() or not (a > 0).all():
+                    raise bad("token_stretch must be finite and > 0, row %d is %r" % (i, row_i))
+                tok[i, :len(a)] = a
+        return row, tok, scale
 
     LIBROSA_TRIM = dict(top_db=50, frame_length=5120, hop_length=256)      # synthesizer.py:267-268
 
