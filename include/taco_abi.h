@@ -255,8 +255,8 @@ int taco_manual_alignments(void* hip_stream, const float* d_alignments, int B, i
  *   a NaN or a negative c among them -- gives +0.)
  *   Rows j >= d_out_frames[b] are written as +0.  Every element of d_out is written exactly once; nothing at frames >= f of the input is
  *   ever read (src is clamped to [0, f - 1] and frac to [0, 65535] on the device: a garbage map gives a wrong picture, nothing worse).
- * NOT reproduced / out of scope: formant-preserving pitch shifting (it needs the envelope separated; the bin-axis scale moves the formants
- * with the pitch, as a resampling-based shift does) and waveform-domain stretching of recordings.
+ * The bin-axis scale moves the formants with the pitch, as a resampling-based shift does; taco_spec_warp_formant below moves the two apart.
+ * NOT reproduced / out of scope: waveform-domain stretching of recordings.
  * Both calls launch on hip_stream only: no read-back, allocation, memset or synchronisation; safe under stream capture; no atomics, two
  * calls give the same bits.  Checked before any HIP call: a null required pointer (d_src, d_frac, d_out_frames, d_workspace; d_spec,
  * d_out); B, T, T_out, reduction_factor or W < 1, and T_in or n_steps < 1 when d_alignments is given; T != n_steps * reduction_factor
@@ -270,6 +270,53 @@ int taco_spec_warp_map(void* hip_stream, const float* d_alignments, const int32_
                        void* d_workspace, size_t workspace_bytes);
 int taco_spec_warp(void* hip_stream, const float* d_spec, const int32_t* d_frames, const int32_t* d_src, const int32_t* d_frac,
                    const int32_t* d_out_frames, const float* d_freq_scale, int B, int T, int W, int T_out, float* d_out);
+/* ---- the spectral envelope of a frame, and pitch and formant shifted apart (k_spec_envelope, k_spec_warp_formant, csrc/taco_envelope.h).
+ * NOT in the reference.  The linear output is normalised dB, affine in log|D|, so the real cepstrum of a frame is a cosine transform of the
+ * frame itself and its low-quefrency part is the envelope -- the vocal tract, the formants -- while the rest, the excitation, carries the
+ * harmonics.  Scaling the two along the bin axis by different factors changes the pitch and keeps the voice, or the other way round.
+ * tests/envelope_reference.py restates everything below in NumPy, in float64 and in fp32. ----
+ * Let W >= 3 be the bins of a frame, M = W - 1, and Q the number of cepstral coefficients kept, 1 <= Q <= min(W - 1, 128).
+ * taco_envelope_create: host_basis [Q, W] doubles, basis[n, k] = cos(pi * n * k / M), and host_lifter [Q] doubles (NULL: all ones), both from
+ * the caller: no libm call of this library decides a bit (as in taco_resample_create, taco_gl_set_mel_basis).  The library forms two fp32
+ * tables on the host in double, in exactly this order, and rounds once:
+ *   A[n, k] = fp32((w_k * basis[n, k]) / M),  w_0 = w_M = 0.5 and every other w_k = 1;
+ *   S[n, k] = fp32((a_n * l[n]) * basis[n, k]),  a_0 = 1 and every other a_n = 2
+ * -- the DCT-I pair of the even extension of length 2 M: c below is the real cepstrum of the frame, and with Q = W and the last a halved S
+ * would give the frame back.  taco_envelope_tables copies both out, [Q, W] each; taco_envelope_width / _order return W / Q (0 for NULL).
+ * For a frame v[0 .. W):  c_n = sum over k of A[n, k] * v_k;  env_k = sum over n of S[n, k] * c_n  -- fp32 products and fp32 sums, the order
+ * of a sum is the kernel's;  e_k = v_k - env_k, one fp32 subtraction.
+ * taco_spec_envelope: d_spec [B, T, W] -> d_env [B, T, W] and, when d_cep is given, d_cep [B, T, Q], for every frame t < f_b =
+ * clamp(d_frames[b], 1, T) (d_frames NULL: T).  Frames t >= f_b are written as +0 in both and are never read.
+ * taco_spec_warp_formant: the inputs of taco_spec_warp with d_pitch_scale [B] and d_formant_scale [B] (both nullable) in place of
+ * d_freq_scale -> d_out [B, T_out, W].  For output frame j < d_out_frames[b]:
+ *   1. v(k) is the time interpolation of taco_spec_warp, to the bit, the frac == 0 copy included;
+ *   2. c, env and e are formed from v as above;
+ *   3. out[j, k] = G(env, formant_scale[b])[k] + G(e, pitch_scale[b])[k], one fp32 addition, where G(y, s) is the frequency gather of
+ *      taco_spec_warp applied to y: q = fp32(k * s), k0 = (int)q, w_f = q - k0; y(k0) when w_f == 0, otherwise y(k0) + w_f * (y(k0 + 1) - y(k0));
+ *      y(k >= W) = +0; a q outside [0, W) gives +0.  A NULL scale means y[k] itself.
+ *   Rows j >= d_out_frames[b] are +0.  Every element of d_out is written exactly once; nothing at frames >= f of the input is read.
+ * A NaN in a source frame makes the cepstrum of every output frame that reads it NaN, and with it every bin G reads there; no other
+ * output frame is affected.  Equal scales give taco_spec_warp(freq_scale) up to rounding (G is linear); a lifter of zeros gives env = +0
+ * and taco_spec_warp on the bits for inputs without -0 and without values that are not finite.
+ * taco_envelope_create needs no device: the first taco_spec_envelope / taco_spec_warp_formant on the handle uploads the tables.  That
+ * call allocates, so it must be made outside stream capture.  After it both calls are one launch on hip_stream: no workspace, read-back,
+ * memset, atomics or synchronisation; capturable; two calls give the same bits.  The handle's `device` is made current.
+ * Checked before any HIP call, TACO_ERR_ARG: a null required pointer (host_basis, out; e, d_spec, d_env; d_src, d_frac, d_out_frames,
+ * d_out); W < 3, Q < 1 or Q > W - 1; a basis or lifter entry that is not finite, a basis entry above 1 in magnitude; B, T or T_out < 1; an
+ * output that shares a byte with an input or with the other output.  TACO_ERR_UNSUPPORTED: Q > 128, or W > 2304 -- one workgroup keeps v
+ * and env of its frames in LDS, 16 frames up to W = 1152 and 8 beyond. */
+typedef struct taco_envelope taco_envelope;
+int taco_envelope_create(int W, int Q, const double* host_basis /* [Q, W] */, const double* host_lifter /* [Q], nullable */, int device,
+                         taco_envelope** out);
+void taco_envelope_destroy(taco_envelope* e);
+int taco_envelope_width(const taco_envelope* e);
+int taco_envelope_order(const taco_envelope* e);
+int taco_envelope_tables(const taco_envelope* e, float* host_A /* [Q, W] */, float* host_S /* [Q, W] */);
+int taco_spec_envelope(taco_envelope* e, void* hip_stream, const float* d_spec, const int32_t* d_frames /* nullable */, int B, int T,
+                       float* d_env, float* d_cep /* nullable */);
+int taco_spec_warp_formant(taco_envelope* e, void* hip_stream, const float* d_spec, const int32_t* d_frames, const int32_t* d_src,
+                           const int32_t* d_frac, const int32_t* d_out_frames, const float* d_pitch_scale, const float* d_formant_scale,
+                           int B, int T, int T_out, float* d_out);
 /* The stop rule (helpers.py:29 + dynamic_decode: the loop ends after the first step at which every row has emitted an all-zero
  * step) evaluated on a finished mel buffer d_mel [B, n_steps, width = r*num_mels] per group of rows_per_group consecutive rows:
  * d_stop[B / rows_per_group].  For requests that were served together through one plan (PlanPool coalesce > 1), whose plan-wide

@@ -311,6 +311,12 @@ int taco_debug_warp_info(int* out, int n);
  * taco_spec_warp's, and so are the bits of d_out. */
 int taco_debug_spec_warp_direct(void* hip_stream, const float* d_spec, const int32_t* d_frames, const int32_t* d_src, const int32_t* d_frac,
                                 const int32_t* d_out_frames, const float* d_freq_scale, int B, int T, int W, int T_out, float* d_out);
+/* Test hook: the tile constants of k_spec_envelope and k_spec_warp_formant (csrc/taco_envelope.h), so that tests/test_gpu_envelope.py can
+ * sit on either side of each.  The first n (at most 8) values are written: out[0] = frames of one workgroup, [1] = lanes of a wave, [2] = the
+ * edge of the matrix tile (v_mfma_f32_16x16x4_f32: 16 frames by 16 coefficients or bins; W and Q are rounded up to it), [3] = terms of the
+ * sum one matrix instruction takes, [4] = the widest frame (W) the kernels serve, [5] = the widest frame a workgroup takes out[0] of --
+ * wider ones get [6] frames a workgroup --, [7] = the largest Q.  Host only; a null pointer or n < 0 is TACO_ERR_ARG. */
+int taco_debug_envelope_info(int* out, int n);
 
 #ifdef __cplusplus
 }

@@ -10,5 +10,5 @@ from .feeder import DeviceCorpus                                                
 from .silence import split_on_silence, split_on_silence_pydub, amplify             # noqa: F401
 from .alignment import align_texts, align_text_batch                                # noqa: F401
 from .metrics import dtw_distance, mel_cepstral_distortion, f0_track, f0_errors, prosody_distance  # noqa: F401
-from .prosody import warp_map, semitones_to_scale                                   # noqa: F401
+from .prosody import warp_map, semitones_to_scale, warp_formant                           # noqa: F401
 from . import audio, weights, dist, _lib, train_ops, tf_checkpoint, text, korean, feeder, silence, alignment, metrics, prosody  # noqa: F401

@@ -258,6 +258,14 @@ PROTOTYPES = {
     "taco_spec_warp": (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P]),
     "taco_debug_warp_info": (_I, [C.POINTER(_I), _I]),
     "taco_debug_spec_warp_direct": (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P]),
+    "taco_envelope_create": (_I, [_I, _I, _P, _P, _I, C.POINTER(_P)]),
+    "taco_envelope_destroy": (None, [_P]),
+    "taco_envelope_width": (_I, [_P]),
+    "taco_envelope_order": (_I, [_P]),
+    "taco_envelope_tables": (_I, [_P, _P, _P]),
+    "taco_spec_envelope": (_I, [_P, _P, _P, _P, _I, _I, _P, _P]),
+    "taco_spec_warp_formant": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P]),
+    "taco_debug_envelope_info": (_I, [C.POINTER(_I), _I]),
 }
 
 _lib = None

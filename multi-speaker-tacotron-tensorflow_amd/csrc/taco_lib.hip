@@ -1720,6 +1720,7 @@ static void loss_band(int sample_rate, int num_freq, int* lo, int* hi) {
 #include "taco_dtw.h"
 #include "taco_f0.h"
 #include "taco_warp.h"
+#include "taco_envelope.h"
 
 extern "C" {
 
@@ -2490,5 +2491,6 @@ int taco_adam_step_f32(void* hip_stream, float* d_params, const float* d_grads, 
 #include "taco_dtw_api.h"
 #include "taco_f0_api.h"
 #include "taco_warp_api.h"
+#include "taco_envelope_api.h"
 
 }  // extern "C"

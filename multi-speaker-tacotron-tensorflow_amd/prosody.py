@@ -10,20 +10,27 @@ maximum wins, a NaN counts as the maximum and the first NaN wins); source frame 
 units of 2^-16 output frame (2^12 for a NaN or a non-positive product); C_t is the inclusive prefix sum of d_t in int64, C_-1 = 0;
 out_frames[b] = clamp((C_{f-1} + 2^15) >> 16, 1, T_out); output frame j < out_frames[b] sits at tau = j << 16, src[b, j] is the t with
 C_{t-1} <= tau < C_t and frac[b, j] = ((tau - C_{src-1}) << 16) / d_src, an integer division, in [0, 65536); for j >= out_frames[b],
-src = f - 1 and frac = 0."""
+src = f - 1 and frac = 0.
+
+Pitch and formants apart (taco_spec_envelope, taco_spec_warp_formant: csrc/taco_envelope.h; tests/envelope_reference.py): the linear output
+is normalised dB, affine in log|D|, so the low-quefrency part of a frame's real cepstrum -- a cosine transform of the frame, Q coefficients
+kept -- is its spectral envelope, the formants, and the rest the excitation, the harmonics.  warp_formant scales the two along the bin axis
+by different factors: the pitch moves and the voice stays, or the other way round."""
+import ctypes as C
 import math
 
 import numpy as np
 import torch
 
 from . import _lib
-from ._device import STREAM, buffers, call, device_of, lengths, tensor
+from ._device import STREAM, Handle, buffers, call, device_of, lengths, tensor
 
 D_MIN, D_MAX = 1 << 12, 1 << 20      # the shortest and the longest duration of a source frame, in 2^-16 output frame
 
 # the result tensors (and the workspace) of every shape a call was made with; the next call of that shape reuses them:
-# (device, "map", B, T, T_out, T_in) and (device, "warp", B, T, W, T_out)
+# (device, "map", B, T, T_out, T_in), (device, "warp", B, T, W, T_out), (device, "envelope", B, T, W, Q) and (device, "formant", B, T, W, T_out)
 _BUFFERS = {}
+_ENVELOPES = {}                      # (device, W, Q, lifter bytes) -> Envelope
 
 
 class WarpMap(object):
@@ -133,3 +140,112 @@ def token_frames(alignments, frames, reduction_factor):
     t / reduction_factor attends most to each token.  Every row sums to its clamped frame count."""
     n_steps = alignments.shape[2]
     return warp_map(frames, n_steps * int(reduction_factor), reduction_factor, alignments=alignments, out_cap=1, return_token_frames=True).token_frames
+
+
+def cosine_basis(W, Q):
+    """basis[n, k] = cos(pi * n * k / (W - 1)) as float64 [Q, W]: what taco_envelope_create takes (the library calls no libm)"""
+    n, k = np.arange(int(Q), dtype=np.float64)[:, None], np.arange(int(W), dtype=np.float64)[None, :]
+    return np.cos(np.pi * n * k / (int(W) - 1))
+
+
+def default_order(sample_rate):
+    """The highest quefrency the envelope keeps, in samples: 2 ms, the period of 500 Hz, so the cepstral peak of any speaking pitch stays in
+    the excitation.  The envelope then has Q = default_order + 1 coefficients (48 and 49 at 24 kHz)."""
+    return int(sample_rate * 0.002)
+
+
+class Envelope(Handle):
+    """A taco_envelope handle: the two fp32 tables for frames of W bins and Q cepstral coefficients under a lifter (None: all ones), made
+    on the host; the first device call uploads them (it allocates: make it outside graph capture)."""
+    _destroy = "taco_envelope_destroy"
+
+    def __init__(self, W, Q, lifter=None, device=None):
+        self._lib = _lib.load_library()
+        self._h = None
+        self.device = torch.device(device if device is not None else "cuda:0")
+        self.W, self.Q = int(W), int(Q)
+        if self.W < 3 or self.Q < 1 or self.Q > self.W - 1:                  # (before the basis is formed: a negative size is no NumPy error here)
+            raise _lib.TacoError(_lib.TACO_ERR_ARG, "W >= 3 and 1 <= Q <= W - 1 are required, got W = %d, Q = %d" % (self.W, self.Q))
+        basis = np.ascontiguousarray(cosine_basis(self.W, self.Q))
+        lift = None if lifter is None else np.ascontiguousarray(np.asarray(lifter, np.float64))
+        if lift is not None and lift.shape != (self.Q,):
+            raise _lib.TacoError(_lib.TACO_ERR_SHAPE, "the lifter must be [Q = %d], got shape %s" % (self.Q, lift.shape))
+        h = C.c_void_p()
+        _lib.check(self._lib.taco_envelope_create(self.W, self.Q, basis.ctypes.data_as(C.c_void_p),
+                                                  None if lift is None else lift.ctypes.data_as(C.c_void_p), self.device.index or 0, C.byref(h)))
+        self._h = h
+
+    def tables(self):
+        """(A, S), float32 [Q, W] each, as the library rounded them"""
+        A, S = np.empty((self.Q, self.W), np.float32), np.empty((self.Q, self.W), np.float32)
+        _lib.check(self._lib.taco_envelope_tables(self._h, A.ctypes.data_as(C.c_void_p), S.ctypes.data_as(C.c_void_p)))
+        return A, S
+
+
+def _envelope_for(dev, W, order, lifter):
+    """The cached handle for frames of W bins on dev.  order: the highest quefrency kept, so Q = order + 1; None: as many as the lifter
+    has entries, else Q = min(49, W - 1) -- default_order at 24 kHz."""
+    if order is not None:
+        Q = int(order) + 1
+    elif lifter is not None:
+        Q = len(lifter)
+    else:
+        Q = min(49, W - 1)
+    lift = None if lifter is None else np.ascontiguousarray(np.asarray(lifter, np.float64))
+    key = (str(dev), W, Q, None if lift is None else lift.tobytes())
+    if key not in _ENVELOPES:
+        _ENVELOPES[key] = Envelope(W, Q, lift, dev)
+    return _ENVELOPES[key]
+
+
+def _spec(spec, T=None):
+    if not (torch.is_tensor(spec) and spec.is_cuda):
+        raise _lib.TacoError(_lib.TACO_ERR_ARG, "spec must be a device tensor (the model's linear_outputs)")
+    return tensor(spec, spec.device, torch.float32, "spec", ("B", "T" if T is None else ("T", T), "W"))
+
+
+def _per_row(v, dev, B, what):
+    if v is None:
+        return None
+    v = torch.as_tensor(np.asarray(v, np.float32)) if not torch.is_tensor(v) else v
+    return tensor(v.expand(B) if v.dim() == 0 else v, dev, torch.float32, what, (("B", B),))
+
+
+def envelope(spec, frames=None, order=None, lifter=None, return_cepstrum=False):
+    """The spectral envelope of every frame (taco_spec_envelope), one launch: spec [B, T, W], a log-magnitude spectrogram such as the
+    model's linear outputs -> env [B, T, W], with return_cepstrum (env, cep [B, T, Q]).  order: the highest quefrency kept in samples
+    (Q = order + 1 coefficients; default_order(sample_rate)); lifter [Q] float64 weights on the coefficients, None for all ones.
+        c_n = sum_k A[n, k] v_k,  env_k = sum_n S[n, k] c_n  -- fp32 sums against the two tables of taco_envelope_create
+    Frames t >= clamp(frames[b], 1, T) are +0 and are not read.  The results belong to a buffer set kept per shape, like warp's."""
+    lib = _lib.load_library()
+    x = _spec(spec)
+    dev = x.device
+    B, T, W = x.shape
+    h = _envelope_for(dev, W, order, lifter)
+    fr = lengths(frames, dev, B, "frames")
+    specs = {"env": ((B, T, W), torch.float32)}
+    if return_cepstrum:
+        specs["cep"] = ((B, T, h.Q), torch.float32)
+    buf = buffers(_BUFFERS, (str(dev), "envelope", B, T, W, h.Q), **specs)
+    call(dev, lib.taco_spec_envelope, h._h, STREAM, x, fr, B, T, buf["env"], buf["cep"] if return_cepstrum else None)
+    return (buf["env"], buf["cep"]) if return_cepstrum else buf["env"]
+
+
+def warp_formant(spec, frames, map, pitch_scale=None, formant_scale=None, order=None, lifter=None):
+    """warp with the pitch and the formants scaled apart (taco_spec_warp_formant), one launch: spec [B, T, W] and a WarpMap ->
+    (out [B, T_out, W], out_frames [B]).  Per output frame: v = warp's time interpolation, to the bit; c, env as in envelope, e = v - env;
+        out[k] = G(env, formant_scale[b])[k] + G(e, pitch_scale[b])[k]
+    with G warp's frequency gather (a scalar or [B] each, semitones_to_scale; None: no scaling of that part).  Equal scales are warp's
+    freq_scale up to rounding.  order, lifter: as in envelope.  out belongs to a buffer set kept per shape."""
+    lib = _lib.load_library()
+    x = _spec(spec, map.T)
+    dev = x.device
+    B, T, W = x.shape
+    if tuple(map.src.shape) != (B, map.T_out):
+        raise _lib.TacoError(_lib.TACO_ERR_SHAPE, "the map is [%d, %d], spec has %d rows" % (tuple(map.src.shape) + (B,)))
+    h = _envelope_for(dev, W, order, lifter)
+    fr = lengths(frames, dev, B, "frames")
+    ps, fs = _per_row(pitch_scale, dev, B, "pitch_scale"), _per_row(formant_scale, dev, B, "formant_scale")
+    out = buffers(_BUFFERS, (str(dev), "formant", B, T, W, map.T_out), out=((B, map.T_out, W), torch.float32))["out"]
+    call(dev, lib.taco_spec_warp_formant, h._h, STREAM, x, fr, map.src, map.frac, map.out_frames, ps, fs, B, T, map.T_out, out)
+    return out, map.out_frames

@@ -156,7 +156,7 @@ class Synthesizer(object):
     def synthesize_audio(self, texts=None, tokens=None, speaker_ids=None, end_of_sentence=True, attention_trim=True,
                          manual_alignments=None, seed=0, iters=None, pcm=True, librosa_trim=False, vocoder="griffin_lim",
                          manual_attention_mode=0, momentum=None, return_convergence=False, rate=None, token_stretch=None, pitch=None,
-                         return_durations=False):
+                         return_durations=False, formant=None, envelope_order=None):
         """The reference's synthesize -> plot_graph_and_save_audio chain up to the samples save_audio writes (synthesizer.py:119-126,
         242-264; audio/__init__.py:22-25), everything between the token upload and the audio download on the device: the forward, the
         attention trim on the device alignments, Griffin-Lim on every utterance's own frames read from the trim kernel's output, the
@@ -192,7 +192,14 @@ class Synthesizer(object):
         trim's frame counts.  return_durations: `token_frames` [N, T_in] is set, the trimmed frames attributed to each token -- the model's
         own durations.  Values that are not finite and positive (rate, token_stretch) or finite (pitch), and sequences longer than the batch
         or the token rows, raise TacoError(TACO_ERR_ARG) before the model runs.  With all four at their defaults nothing of this runs:
-        `warped_frames` and `token_frames` are None."""
+        `warped_frames` and `token_frames` are None.
+        formant, envelope_order (prosody.warp_formant; not in the reference): formant is in semitones, a scalar or one value per row.  With it
+        given (0.0 included) the spectrogram goes through taco_spec_warp_formant in place of taco_spec_warp: every frame is split into its
+        spectral envelope (the low-quefrency part of its cepstrum, envelope_order + 1 coefficients; None: prosody.default_order(sample_rate),
+        2 ms) and the excitation, the envelope's bin axis is scaled by semitones_to_scale(formant) and the excitation's by
+        semitones_to_scale(pitch) (None: 0 semitones).  pitch=3, formant=0 raises the pitch and keeps the voice; formant=-2 alone darkens the
+        voice at the same pitch.  Without rate or token_stretch the time map is the identity.  Refused like pitch: vocoder="mel", values
+        that are not finite, more values than rows; envelope_order without formant, or below 0.  With formant=None nothing of this runs."""
         from . import _lib
         if manual_attention_mode > 0 and manual_alignments is not None:
             raise _lib.TacoError(_lib.TACO_ERR_ARG, "manual_attention_mode builds the second pass's alignments itself: it cannot be "
@@ -204,7 +211,8 @@ class Synthesizer(object):
         sequences = self._token_rows(texts, tokens)
         input_lengths = np.argmax(sequences == EOS_ID, 1).astype(np.int32)             # synthesizer.py:120
         speaker = self._speaker_feed(speaker_ids, len(sequences))
-        stretch = self._prosody_args(len(sequences), sequences.shape[1], rate, token_stretch, pitch, vocoder)
+        formant_scale = self._formant_args(len(sequences), formant, envelope_order, vocoder)
+        stretch = self._prosody_args(len(sequences), sequences.shape[1], rate, token_stretch, pitch if formant is None or pitch is not None else 0.0, vocoder)
         linear, alignments = self.model.run(
             inputs=sequences.astype(np.int32), input_lengths=input_lengths, **speaker,
             manual_alignments=manual_alignments, is_manual_attention=manual_alignments is not None,
@@ -222,10 +230,15 @@ class Synthesizer(object):
             from . import prosody
             row_stretch, tok_stretch, freq_scale = stretch
             r, T = self.hparams.reduction_factor, linear.shape[1]
+            if frames is None and row_stretch is None and tok_stretch is None:      # pitch / formant alone with the trim off: the batch size has to come from somewhere
+                row_stretch = np.ones(len(sequences), np.float32)
             wmap = prosody.warp_map(frames, T, r, alignments if tok_stretch is not None or return_durations else None, row_stretch, tok_stretch,
                                     out_cap=prosody.out_frames_bound(T, row_stretch, tok_stretch), return_token_frames=return_durations)
             if vocoder == "mel":
                 mel, frames = prosody.warp(mel, trimmed, wmap)
+            elif formant_scale is not None:
+                order = prosody.default_order(self.hparams.sample_rate) if envelope_order is None else int(envelope_order)
+                linear, frames = prosody.warp_formant(linear, trimmed, wmap, freq_scale, formant_scale, order=min(order, linear.shape[2] - 2))
             else:
                 linear, frames = prosody.warp(linear, trimmed, wmap, freq_scale)
             self.warped_frames = frames.cpu().numpy()
@@ -307,6 +320,34 @@ class Synthesizer(object):
                     raise bad("token_stretch must be finite and > 0, row %d is %r" % (i, row_i))
                 tok[i, :len(a)] = a
         return row, tok, scale
+
+    @staticmethod
+    def _formant_args(N, formant, envelope_order, vocoder):
+        """synthesize_audio's formant / envelope_order -> formant_scale [N] float32, or None without formant.  Every refusal is a
+        TacoError(TACO_ERR_ARG)."""
+        from . import _lib
+        from .prosody import semitones_to_scale
+
+        def bad(msg):
+            return _lib.TacoError(_lib.TACO_ERR_ARG, msg)
+
+        if formant is None:
+            if envelope_order is not None:
+                raise bad("envelope_order belongs to formant: without it no envelope is formed")
+            return None
+        if vocoder == "mel":
+            raise bad("formant scales a linear frequency axis: it serves the vocoders 'griffin_lim' and 'tensorflow', not 'mel'")
+        try:
+            a = np.asarray(formant, np.float64)
+        except (TypeError, ValueError):
+            raise bad("formant must be a number or one number per row")
+        if a.ndim > 1 or (a.ndim == 1 and len(a) != N):
+            raise bad("formant must be a scalar or one value per row (%d), got shape %s" % (N, a.shape))
+        if not np.isfinite(a).all():
+            raise bad("formant must be finite, got %r" % (formant,))
+        if envelope_order is not None and (isinstance(envelope_order, bool) or not isinstance(envelope_order, (int, np.integer)) or envelope_order < 0):
+            raise bad("envelope_order must be an integer >= 0, got %r" % (envelope_order,))
+        return semitones_to_scale(np.broadcast_to(a, (N,)))
 
     LIBROSA_TRIM = dict(top_db=50, frame_length=5120, hop_length=256)      # synthesizer.py:267-268
 

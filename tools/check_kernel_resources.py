@@ -13,7 +13,8 @@ indexing them dynamically would move the argument block to scratch), or k_gl_mel
 registers: an array the compiler leaves in memory would put a round trip into every fmaf), or k_text_matches / k_text_best_two (a lane's
 columns of the run-length recurrence are registers and the pending rectangles an LDS stack: csrc/taco_align.h), or k_dtw / k_dtw_path (a
 lane's column of features, up to 128 floats, and its rolling anti-diagonal values are registers: csrc/taco_dtw.h), or k_yin / k_f0_path_stats (a
-thread's run of samples, its sliding run and its nine lag sums are registers: csrc/taco_f0.h) has
+thread's run of samples, its sliding run and its nine lag sums are registers: csrc/taco_f0.h), or k_spec_envelope / k_spec_warp_formant (a
+wave's up to eight matrix accumulators and the table operands in flight are registers: csrc/taco_envelope.h) has
 ScratchSize > 0 (no allowances since round 4: the last one, the 8-rows-per-group BPTT kernel's 196 bytes, went when the owner rows' tape
 offsets became per-step values instead of 22 hoisted pointers).
 
@@ -24,7 +25,7 @@ import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 DEFAULT = os.path.join(ROOT, "multi-speaker-tacotron-tensorflow_amd", "csrc", "kernel_resources.txt")
-NO_SCRATCH = ("k_bigru_duo", "k_bigru_oct", "k_decoder_xcd", "k_decoder_bwd_xcd", "k_pointwise_chain", "k_cbhg_front", "k_head_sweep", "k_spec_targets", "k_collate", "k_gl_mel_magnitude", "k_text_matches", "k_text_best_two", "k_dtw", "k_yin", "k_f0_path_stats")  # k_bigru_duo also matches k_bigru_duo_bwd, k_dtw also k_dtw_path, k_yin both its forms
+NO_SCRATCH = ("k_bigru_duo", "k_bigru_oct", "k_decoder_xcd", "k_decoder_bwd_xcd", "k_pointwise_chain", "k_cbhg_front", "k_head_sweep", "k_spec_targets", "k_collate", "k_gl_mel_magnitude", "k_text_matches", "k_text_best_two", "k_dtw", "k_yin", "k_f0_path_stats", "k_spec_envelope", "k_spec_warp_formant")  # k_bigru_duo also matches k_bigru_duo_bwd, k_dtw also k_dtw_path, k_yin both its forms
 ALLOWED_SCRATCH = {}      # (mangled name -> bytes per lane; empty since round 4)
 
 
