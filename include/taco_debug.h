@@ -247,6 +247,37 @@ int taco_debug_gl_create_host(const taco_audio_hparams* hp, int tf_flavor, taco_
  * k_gl_project_tf (c is not used); else k_gl_project_fast on z = est - c * prev. */
 int taco_debug_gl_project(taco_gl* g, void* hip_stream, const float* d_est, const float* d_prev, const float* d_S, float* d_X, float c, int R);
 
+/* Test hooks: the stages of the librosa-flavour Griffin-Lim path alone, on caller data (tests/test_gpu_gl_stages.py against tests/gl_reference.py).
+ * Each one launches the kernels the product path launches (gl_vocode_rows, taco_gl_inv_spectrogram_tf, gl_iterate), with its launch shapes.
+ * Every argument error is returned before the first HIP call; a host-only handle (taco_debug_gl_create_host) that passes them all is
+ * TACO_ERR_STATE.
+ *
+ * taco_debug_gl_info: the slot geometry of a call with T frames, host only.  The first n (at most 8) values are written: out[0] = Tr, frame
+ * rows per utterance slot, [1] = slot, samples per utterance slot, [2] = half = n_fft / 2, [3] = lpad, [4] = floats behind the last slot that
+ * the product path clears with the slots (2 * n_fft + win), [5] = floats of the window-sum table (hop * (T - 1) + n_fft), [6] = the fewest
+ * frames a row keeps (taco_gl_min_frames; 1 on a taco_gl_create_tf handle), [7] = samples of a row of T frames in the handle's flavour.  A null
+ * pointer, n < 0 or T < 1 is TACO_ERR_ARG. */
+int taco_debug_gl_info(const taco_gl* g, int T, int* out, int n);
+/* k_gl_magnitude, then k_gl_init_phase: d_spec [B, T, num_freq], d_frames [B] / NULL, d_init_uniform [B, T, num_freq] / NULL (then the counter
+ * hash of seed) -> d_S [B, Tr, num_freq], d_X [B, Tr, 2 * num_freq].  Frames are clamped as the handle's flavour clamps them (out[6] above). */
+int taco_debug_gl_prologue(taco_gl* g, void* hip_stream, const float* d_spec, const int32_t* d_frames, const float* d_init_uniform,
+                           unsigned long long seed, int B, int T, float* d_S, float* d_X);
+/* The synthesis half of an iteration behind the inverse product: d_ypad [B * slot + out[4]] is cleared as the product path clears it, then
+ * k_gl_wss fills d_wss [out[5]] and k_gl_overlap_add turns the frames d_Y [B, Tr, win] into the padded rows; on a taco_gl_create_tf handle
+ * k_gl_overlap_add_tf runs instead and d_wss is not used (nullable).  d_frames [B] / NULL.  TACO_ERR_SHAPE where the vocoder answers it
+ * (hop * (T - 1) <= n_fft / 2 on a librosa handle). */
+int taco_debug_gl_overlap_add(taco_gl* g, void* hip_stream, const float* d_Y, const int32_t* d_frames, int B, int T, float* d_ypad, float* d_wss);
+/* k_inv_preemphasis as the vocoder launches it, on rows that start at their slot (slot = L = hop * (T - 1), half = 0) and with the
+ * coefficient a passed in: d_x [B, L], d_frames [B] / NULL clamped to [fmin, T] -> d_wav [B, L], d_num_samples [B] / NULL.  No handle: hop = 1
+ * gives every L.  1 <= fmin <= T, T >= 2, hop >= 1, hop * (T - 1) within an int, a finite; else TACO_ERR_ARG. */
+int taco_debug_gl_inv_preemphasis(void* hip_stream, const float* d_x, const int32_t* d_frames, int fmin, int T, int hop, int B, float a,
+                                  float* d_wav, int32_t* d_num_samples);
+/* One run_gemm on a pack of the handle, as gl_iterate calls it: which = 0 the forward pack (K = win, N = 2 * num_freq), 1 the inverse pack
+ * (K = 2 * num_freq, N = win); exact = 0 the split-bf16 planes the product path uses, 1 the exact-fp32 pack.  Row i of the M rows is
+ * d_rows[i * ld .. i * ld + K), so ld < K is the overlapping stride of the loop's forward product; rows_floats is what d_rows holds, and
+ * (M - 1) * ld + K beyond it is TACO_ERR_ARG.  d_out [M, N]. */
+int taco_debug_gl_dft(taco_gl* g, void* hip_stream, int which, int exact, const float* d_rows, size_t rows_floats, int M, int ld, float* d_out);
+
 /* Test hook: the host half of taco_model_finalize alone -- model_pack_host (csrc/taco_pack.h): every weight pack, the GemmVar table and, on a
  * shadow model, the index lists and backward packs -- with no handle and no device.  shadow = 0: flat_weights holds every tensor of the spec in
  * spec order, TF layout, no padding (the flat layout of taco_train_create); another n_floats is TACO_ERR_SHAPE.  shadow = 1: flat_weights must

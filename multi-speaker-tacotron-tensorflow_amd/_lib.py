@@ -154,6 +154,11 @@ PROTOTYPES = {
     "taco_gl_convergence_workspace_bytes": (_S, [_P, _I, _I]),
     "taco_gl_convergence": (_I, [_P, _P, _P, _I, _P, _P, _I, _I, _P, _P, _S]),
     "taco_debug_gl_project": (_I, [_P, _P, _P, _P, _P, _P, C.c_float, _I]),
+    "taco_debug_gl_info": (_I, [_P, _I, C.POINTER(_I), _I]),
+    "taco_debug_gl_prologue": (_I, [_P, _P, _P, _P, _P, C.c_ulonglong, _I, _I, _P, _P]),
+    "taco_debug_gl_overlap_add": (_I, [_P, _P, _P, _P, _I, _I, _P, _P]),
+    "taco_debug_gl_inv_preemphasis": (_I, [_P, _P, _P, _I, _I, _I, _I, C.c_float, _P, _P]),
+    "taco_debug_gl_dft": (_I, [_P, _P, _I, _I, _P, _S, _I, _I, _P]),
     "taco_wav_trim_workspace_bytes": (_S, [_I, _I, _I, _I]),
     "taco_wav_trim": (_I, [_P, _P, _P, _I, _I, C.c_float, _I, _I, _I, _P, _P, _P, _S]),
     "taco_wav_split_workspace_bytes": (_S, [_I, _I, _I, _I]),

@@ -489,6 +489,86 @@ int taco_debug_gl_project(taco_gl* g, void* hip_stream, const float* d_est, cons
   return 0;
 }
 
+// ---- the stages of the Griffin-Lim path alone (include/taco_debug.h): the launches of gl_vocode_rows / taco_gl_inv_spectrogram_tf / gl_iterate on caller data ----
+int taco_debug_gl_info(const taco_gl* g, int T, int* out, int n) {
+  if (!g || !out || n < 0 || T < 1) return fail(TACO_ERR_ARG, "bad argument");
+  const bool tf = g->flavor == GL_TF;
+  const long long v[8] = {gl_rows(g, T), (long long)gl_slot(g, T), g->n_fft / 2, g->lpad, (long long)spec_tail(g), (long long)g->hop * (T - 1) + g->n_fft,
+                          tf ? 1 : taco_gl_min_frames(g), tf ? taco_gl_tf_num_samples(g, T) : taco_gl_num_samples(g, T)};
+  for (int i = 0; i < std::min(n, 8); ++i) out[i] = (int)v[i];
+  return 0;
+}
+// A handle of taco_debug_gl_create_host has no device arena: nothing may be launched on it
+static int gl_debug_device(const taco_gl* g) {
+  if (!g->gm->darena) return fail(TACO_ERR_STATE, "a host-only handle (taco_debug_gl_create_host) serves the argument checks only");
+  HIPCHK(hipSetDevice(g->gm->device));
+  return 0;
+}
+
+int taco_debug_gl_prologue(taco_gl* g, void* hip_stream, const float* d_spec, const int32_t* d_frames, const float* d_init_uniform,
+                           unsigned long long seed, int B, int T, float* d_S, float* d_X) {
+  if (!g || !d_spec || !d_S || !d_X || B <= 0 || B > 65535) return fail(TACO_ERR_ARG, "bad argument");
+  const bool tf = g->flavor == GL_TF;
+  if (T < (tf ? 1 : 2)) return fail(TACO_ERR_ARG, "T = %d", T);
+  const int Tr = gl_rows(g, T), F = g->F, fmin = tf ? 1 : taco_gl_min_frames(g);
+  const size_t R = (size_t)B * Tr;
+  if (R * 2 * F > (size_t)0x7fffffff) return fail(TACO_ERR_SHAPE, "too many elements: %zu", R * 2 * F);
+  TRY(gl_debug_device(g));
+  hipStream_t st = (hipStream_t)hip_stream;
+  hipLaunchKernelGGL(k_gl_magnitude, EWGRID(R * F), 0, st, d_spec, d_S, d_frames, fmin, B, T, Tr, F, g->hp.min_level_db, g->hp.ref_level_db, g->hp.power);
+  hipLaunchKernelGGL(k_gl_init_phase, EWGRID(R * F), 0, st, d_S, d_init_uniform, seed, d_X, d_frames, fmin, B, T, Tr, F);
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
+int taco_debug_gl_overlap_add(taco_gl* g, void* hip_stream, const float* d_Y, const int32_t* d_frames, int B, int T, float* d_ypad, float* d_wss) {
+  if (!g || !d_Y || !d_ypad || B <= 0 || B > 65535) return fail(TACO_ERR_ARG, "bad argument");
+  const bool tf = g->flavor == GL_TF;
+  if (T < (tf ? 1 : 2)) return fail(TACO_ERR_ARG, "T = %d", T);
+  if (!tf && !d_wss) return fail(TACO_ERR_ARG, "the librosa flavour needs the window-sum table");
+  const int half = g->n_fft / 2, Tr = gl_rows(g, T), L = tf ? taco_gl_tf_num_samples(g, T) : g->hop * (T - 1);
+  if (!tf && L <= half) return fail(TACO_ERR_SHAPE, "utterance too short for reflect padding: hop*(T-1) = %d <= n_fft/2 = %d", L, half);
+  const size_t slot = gl_slot(g, T);
+  TRY(gl_debug_device(g));
+  hipStream_t st = (hipStream_t)hip_stream;
+  HIPCHK(zero_async(d_ypad, ((size_t)B * slot + spec_tail(g)) * sizeof(float), st));
+  if (tf) {
+    hipLaunchKernelGGL(k_gl_overlap_add_tf, dim3((L + 255) / 256, B), dim3(256), 0, st, d_Y, d_ypad, d_frames, T, Tr, g->win, g->hop, slot);
+  } else {
+    hipLaunchKernelGGL(k_gl_wss, EWGRID((size_t)L + g->n_fft), 0, st, AP(g->gm, g->w2), d_wss, T, g->n_fft, g->hop);
+    hipLaunchKernelGGL(k_gl_overlap_add, dim3((L + 255) / 256, B), dim3(256), 0, st, d_Y, d_wss, AP(g->gm, g->w2), d_ypad, d_frames, taco_gl_min_frames(g), T,
+                       Tr, g->win, g->hop, g->lpad, g->n_fft, slot);
+  }
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
+int taco_debug_gl_inv_preemphasis(void* hip_stream, const float* d_x, const int32_t* d_frames, int fmin, int T, int hop, int B, float a,
+                                  float* d_wav, int32_t* d_num_samples) {
+  if (!d_x || !d_wav || B <= 0 || B > 65535) return fail(TACO_ERR_ARG, "bad argument");
+  if (T < 2 || hop < 1 || fmin < 1 || fmin > T) return fail(TACO_ERR_ARG, "bad frame parameters: T %d, hop %d, fmin %d", T, hop, fmin);
+  if ((long long)hop * (T - 1) > 0x7fffffffLL) return fail(TACO_ERR_ARG, "hop*(T-1) = %lld does not fit an int", (long long)hop * (T - 1));
+  if (!std::isfinite(a)) return fail(TACO_ERR_ARG, "a = %g", (double)a);
+  const int L = hop * (T - 1);
+  hipLaunchKernelGGL(k_inv_preemphasis, dim3(B), dim3(1024), 0, (hipStream_t)hip_stream, d_x, d_wav, d_frames, fmin, T, hop, d_num_samples, L, 0, (size_t)L, a);
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
+int taco_debug_gl_dft(taco_gl* g, void* hip_stream, int which, int exact, const float* d_rows, size_t rows_floats, int M, int ld, float* d_out) {
+  if (!g || !d_rows || !d_out || M <= 0 || ld < 1) return fail(TACO_ERR_ARG, "bad argument");
+  if ((which != 0 && which != 1) || (exact != 0 && exact != 1)) return fail(TACO_ERR_ARG, "which = %d, exact = %d: each is 0 or 1", which, exact);
+  const ConvL& pack = which ? g->inv : g->fwd;
+  if ((size_t)(M - 1) * ld + pack.cin > rows_floats)
+    return fail(TACO_ERR_ARG, "%d rows of %d at stride %d need %zu floats, d_rows holds %zu", M, pack.cin, ld, (size_t)(M - 1) * ld + pack.cin, rows_floats);
+  if ((size_t)M * std::max(pack.N, ld) > (size_t)0x7fffffff) return fail(TACO_ERR_SHAPE, "too many elements");
+  TRY(gl_debug_device(g));
+  GemmCall c; c.x = d_rows; c.ldx = ld; c.M = M; c.out = d_out; c.ldo = pack.N;
+  c.force = exact ? GEMM_FORCE_EXACT : GEMM_FORCE_NONE;
+  TRY(run_gemm(g->gm, (hipStream_t)hip_stream, &pack, 1, false, c));
+  return 0;
+}
+
 // ---- splitting and levelling 16-bit PCM on silence: pydub.silence.detect_nonsilent (audio/silence.py:81-117, app.py:27-53) ----
 // The workspace of taco_pcm_nonsilent: the energies E [B, Mmax] first (taco_pcm_range_sumsq reads them from there), then the flags
 struct PcmWs { unsigned long long* E; unsigned char* silent; };

@@ -5,6 +5,7 @@ import numpy as np
 import pytest
 
 import audio_oracle as A
+import gl_reference as G
 
 pytestmark = pytest.mark.gpu
 
@@ -140,7 +141,8 @@ def test_pcm16_is_save_audios_arithmetic():
     waveform.  Two fp32 roundings (the scale, the product) move a full-scale value by at most 0.004 of a step, so a sample may land on
     the other side of an integer -- off by one -- only when it lies that close to one: at most 0.8 % of samples; the bar is 1 %.
     A row reaches full scale (32767, or 32766 after the roundings) when its peak is at least the 0.01 floor of the scale; the
-    all-zero row stays zero and the row with peak 0.004 reaches 0.4 of full scale, as save_audio would write them."""
+    all-zero row stays zero and the row with peak 0.004 reaches 0.4 of full scale, as save_audio would write them.
+    Against the float32 restatement of the same arithmetic the samples are equal, all of them."""
     import torch, taco_amd
     ahp = _small()
     rs = np.random.RandomState(2)
@@ -154,7 +156,8 @@ def test_pcm16_is_save_audios_arithmetic():
     ns = torch.cat([ns, torch.tensor([L, int(ns[1])], dtype=torch.int32, device=ns.device)])
     pcm = gl.pcm16(wav, ns)
     assert pcm.dtype == torch.int16 and tuple(pcm.shape) == (5, L)
-    pcm, x, n = pcm.cpu().numpy().astype(np.int64), wav.cpu().numpy().astype(np.float64), ns.cpu().numpy()
+    wav32 = wav.cpu().numpy()
+    pcm, x, n = pcm.cpu().numpy().astype(np.int64), wav32.astype(np.float64), ns.cpu().numpy()
     for b in range(5):
         peak = np.abs(x[b, :n[b]]).max()
         ref = np.trunc(x[b, :n[b]] * 32767 / max(0.01, peak)).astype(np.int64)
@@ -162,6 +165,11 @@ def test_pcm16_is_save_audios_arithmetic():
         print("row %d: n %d peak %.4g max |diff| %d share differing %.4f peak pcm %d" % (b, n[b], peak, d.max(), (d > 0).mean(), np.abs(pcm[b]).max()))
         assert d.max() <= 1 and (d > 0).mean() <= 0.01, (b, d.max(), (d > 0).mean())
         assert np.all(pcm[b, n[b]:] == 0)
+        # and to the sample against the same arithmetic in float32 (tests/gl_reference.py): the kernel is one correctly rounded division
+        # (the scale), one multiplication, a truncation and the clamp, each of which NumPy's float32 reproduces
+        same = G.pcm16_f32(wav32[b], int(n[b])).astype(np.int64)
+        print("row %d: samples differing from the float32 restatement %d of %d" % (b, int((pcm[b] != same).sum()), same.size))
+        assert np.array_equal(pcm[b], same), (b, np.flatnonzero(pcm[b] != same)[:8])
         if peak >= 0.01:
             assert np.abs(pcm[b]).max() in (32767, 32766), b
     assert np.all(pcm[3] == 0)
